@@ -18,7 +18,9 @@ image-sharded, images[g::G]); no data-path collective, only the timing barrier. 
 
 The headline (`value`, `dtype` "f16x3") runs the conv stack in the fp32-class mode -- split-half operands and activations,
 three MFMA products per term (the reference's arithmetic is fp32); the mean-field loop is fp32 throughout.  Inputs are
-resident in HBM.  The same JSON line carries (rank 0, N = 1; --quick skips the extras): `value_steady` (>= 10 s of steps
+resident in HBM.  A plain run sets up, runs --warmup steps, times exactly --steps steps (`ms_per_step`), writes the last
+step's outputs when --dump-outputs DIR is given (dump_outputs) and prints the headline line.  With --full the same JSON
+line also carries (rank 0, N = 1; --quick skips the extras): `value_steady` (>= 10 s of steps
 cycling over four distinct resident batches), `roofline` with the two fractions the north star names (`conv_mfma`,
 `crf_hbm`; `frac` = algorithmic rate / peak, `frac_traffic` = measured HBM traffic / peak), `parity` (final label maps of
 the product chain against the all-fp32 oracle chain on images of this batch -- computed inside the cpu_baseline leg, the
@@ -71,8 +73,8 @@ def parse():
     ap.add_argument("--arch", default="resnet50", choices=["resnet50", "vgg16", "m7"],
                     help="CAM network (resnet50 is the BASELINE.json configuration; vgg16 / m7 are extra "
                          "measurements of the other conv stacks of the reference, 03b_irn/net/{vgg16,m7}.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="skip the extra measurements (steady-state leg, f16, M=K+1, end-to-end)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline / parity")
+    ap.add_argument("--quick", action="store_true", help="with --full: skip the extra legs (steady-state, f16, M=K+1, end-to-end, HSN / IRNet / make_cam)")
     ap.add_argument("--steady-seconds", type=float, default=10.0, help="length of the value_steady leg (0 = skip)")
     ap.add_argument("--seconds", type=float, default=0.0,
                     help="steady-state run: raise --steps so that the timed region lasts at least this long")
@@ -86,7 +88,18 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for the timing barrier (nccl = RCCL; gloo only to exercise the "
                          "N>1 code path on a box with fewer GPUs than ranks, together with WSC_BENCH_DEVICE)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run every other measurement of the line: steady-state leg, per-stage "
+                         "times, per-kernel roofline, f16 / M=K+1 / end-to-end / HSN / IRNet / make_cam legs, CPU baseline "
+                         "and parity (off: the line carries the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as float32 DIR/<name>.npy files, 64 MB at most")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("cam_crf", "cam"):
+        ap.error("--dump-outputs: only the cam_crf and cam workloads")
+    return args
 
 
 def crf_bytes_per_image(N, M, T, vg, vb):
@@ -583,6 +596,34 @@ class Workload:
         return self.ctx.timer_end() / reps
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: what the last step handed its caller, as float32 DIR/<name>.npy -- `cam` and `high_res`, the make_cam
+    tail's per-image maps (each image's K class maps back to back, images in batch order, flattened), and for cam_crf `labels`,
+    the dense-CRF label maps (B, S, S).  Above DUMP_MAX_BYTES in all, every array becomes the same share of its elements, at
+    sorted indices drawn with a fixed seed, flattened."""
+    np = wl.np
+    wl.drain()
+    for c in (wl.ctx, wl.ctx_build, wl.ctx_crf):
+        c.sync()
+    outs = {"cam": wl.ctx.to_host(wl.strided_dev, (max(wl.s_tot, 1),), np.float32)[:wl.s_tot],
+            "high_res": wl.ctx.to_host(wl.highres_dev, (max(wl.h_tot, 1),), np.float32)[:wl.h_tot]}
+    if wl.workload == "cam_crf":
+        outs["labels"] = wl.ctx.to_host(wl.label_dev, (wl.B, S, S), np.int32).astype(np.float32)
+    total = sum(a.nbytes for a in outs.values())
+    budget = DUMP_MAX_BYTES - 1024 * len(outs)  # (room for the .npy headers)
+    if total > budget:
+        rng = np.random.default_rng(0)
+        for k in sorted(outs):
+            a = outs[k].reshape(-1)
+            outs[k] = a[np.sort(rng.choice(a.size, a.size * budget // total, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in outs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def cpu_baseline(wl, budget_s, product_labels=None):
     """-> (cpu_baseline object, parity object or None).
     Oracle on the host cores (the only place bench.py touches oracle/): torch-CPU fp32 restatement of
@@ -1026,6 +1067,8 @@ def main():
     # strong scaling: the K steps are one fixed image set, sharded -- rank g owns ceil(K / N) of them
     my_steps = (steps + world - 1) // world if args.scaling == "strong" else steps
     elapsed = timed_run(wl, do_step, my_steps, args.warmup, wl.drain)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
     # what the line says about the ranks behind it: who contributed, each rank's own time (the value is computed from the MAX)
     ranks_info = {"ranks_seen": 1, "barrier_world_size": 1, "backend": None, "launch": "single process",
                   "per_rank_ms_per_step": [round(elapsed / my_steps * 1e3, 4)],
@@ -1049,6 +1092,44 @@ def main():
         elapsed = float(t.item())
         assert abs(elapsed - max(e[0] for e in every)) < 1e-9
         dist.barrier()
+
+    def headline():
+        """The fields of the result line that a plain run measures; --full adds its objects to them."""
+        images = args.batch * (steps if args.scaling == "strong" else steps * world)
+        return {
+            "metric": "images/sec CAM+CRF pseudo-labels, VOC2012 321x321",
+            "value": round(images / elapsed, 3),
+            "unit": "images/s",
+            "n_gpus": world,
+            "steps": steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / my_steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": args.precision,
+            "data": "synthetic",
+            "config": {"workload": "%s CAM + dense-CRF (M=21, 10 mean-field iters), %dx%d, batch %d "
+                                   "images (=%d samples) per GPU, image-sharded" % (args.arch, S, S, args.batch,
+                                                                                   2 * args.batch)
+                       if args.workload == "cam_crf" else
+                       "%s CAM (make_cam), %dx%d, batch %d images per GPU" % (args.arch, S, S, args.batch),
+                       "batch_images": args.batch, "num_classes": NUM_CLASSES, "crf_config": list(CRF_CFG),
+                       "parallelism": "image-sharded x%d, no collective" % world,
+                       "steps_per_rank": my_steps,
+                       "step_overlap": "mean-field loop of step i overlaps conv stack + lattice build of step i+1 "
+                                       "(3 HIP streams)" if pipelined else "none"},
+            # N = 1 (also `--gpus 1` of a scaling run) is this very path with ranks_seen = 1: no launcher, no process group
+            "ranks": ranks_info,
+        }
+
+    if not args.full:  # a plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(headline()))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- steady state: >= --steady-seconds of steps cycling over four distinct resident batches (rank 0 of a 1-GPU run) ----
     steady = None
@@ -1187,35 +1268,8 @@ def main():
                 stages["value_make_cam"] = {"error": repr(e)}
 
     if rank == 0:
-        images = args.batch * (steps if args.scaling == "strong" else steps * world)
-        out = {
-            "metric": "images/sec CAM+CRF pseudo-labels, VOC2012 321x321",
-            "value": round(images / elapsed, 3),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / my_steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": args.precision,
-            "data": "synthetic",
-            "config": {"workload": "%s CAM + dense-CRF (M=21, 10 mean-field iters), %dx%d, batch %d "
-                                   "images (=%d samples) per GPU, image-sharded" % (args.arch, S, S, args.batch,
-                                                                                   2 * args.batch)
-                       if args.workload == "cam_crf" else
-                       "%s CAM (make_cam), %dx%d, batch %d images per GPU" % (args.arch, S, S, args.batch),
-                       "batch_images": args.batch, "num_classes": NUM_CLASSES, "crf_config": list(CRF_CFG),
-                       "parallelism": "image-sharded x%d, no collective" % world,
-                       "steps_per_rank": my_steps,
-                       "step_overlap": "mean-field loop of step i overlaps conv stack + lattice build of step i+1 "
-                                       "(3 HIP streams)" if pipelined else "none"},
-            "roofline": roofline,
-            "stages": stages,
-            # N = 1 (also `--gpus 1` of a scaling run) is this very path with ranks_seen = 1: no launcher, no process group
-            "ranks": ranks_info,
-        }
+        out = headline()
+        out.update({"roofline": roofline, "stages": stages})
         if steady is not None:
             out["value_steady"] = steady["value"]
             out["steady"] = steady

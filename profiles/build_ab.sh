@@ -10,6 +10,6 @@ for spec in "$@"; do
     last="$flags"
   fi
   echo "#### $label [flags: $flags]"
-  python bench.py --no-cpu-baseline --quick --no-pipeline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['stages']['kernels']; print(d['ms_per_step'], d['stages']['crf_create_ms'], k['crf_build(all)']['avg_us'])"
-  python bench.py --no-cpu-baseline --quick 2>&1 | tail -1 | cut -c88-170
+  python bench.py --full --no-cpu-baseline --quick --no-pipeline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['stages']['kernels']; print(d['ms_per_step'], d['stages']['crf_create_ms'], k['crf_build(all)']['avg_us'])"
+  python bench.py --full --no-cpu-baseline --quick 2>&1 | tail -1 | cut -c88-170
 done

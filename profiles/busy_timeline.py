@@ -2,8 +2,8 @@
 with its last update_splat launch... simpler: the whole window between the first and the last dispatch of the second half of
 the trace), the union of all kernel intervals against the wall span, and the largest idle gaps with the kernels around them.
 
-    rocprofv3 --kernel-trace -d gpurun_out/prof_pipe -- python3 bench.py --steps 12 --warmup 3 --no-cpu-baseline --quick
-    python profiles/busy_timeline.py gpurun_out/prof_pipe/*/*_results.db
+    rocprofv3 --kernel-trace -d OUT/prof_pipe -- python3 bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --quick
+    python profiles/busy_timeline.py OUT/prof_pipe/*/*_results.db
 """
 import sqlite3
 import sys

@@ -10,5 +10,5 @@ for spec in "$@"; do
     last="$flags"
   fi
   echo "#### $label [flags: $flags]"
-  python bench.py --no-cpu-baseline --quick --no-pipeline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['stages']['kernels']; print(d['ms_per_step'], d['stages']['crf_infer_ms'], [v for n, v in k.items() if n.startswith('combine4')][0])"
+  python bench.py --full --no-cpu-baseline --quick --no-pipeline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['stages']['kernels']; print(d['ms_per_step'], d['stages']['crf_infer_ms'], [v for n, v in k.items() if n.startswith('combine4')][0])"
 done

@@ -7,6 +7,6 @@ trap 'cp /tmp/lib_ship.so wsss-analysis_amd/wsscam/libwsscam.so' EXIT  # the shi
 for rep in 1 2; do for v in "$1" "$2"; do
   cp "$v" wsss-analysis_amd/wsscam/libwsscam.so
   echo "== $v"
-  python bench.py --no-cpu-baseline --quick 2>&1 | tail -1 | cut -c88-170
-  python bench.py --no-cpu-baseline --quick --no-pipeline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['stages']['kernels']; print(d['ms_per_step'], d['stages']['crf_create_ms'], d['stages']['crf_infer_ms'], k['update_splat_kernel']['avg_us'], k['crf_build(all)']['avg_us'])"
+  python bench.py --full --no-cpu-baseline --quick 2>&1 | tail -1 | cut -c88-170
+  python bench.py --full --no-cpu-baseline --quick --no-pipeline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['stages']['kernels']; print(d['ms_per_step'], d['stages']['crf_create_ms'], d['stages']['crf_infer_ms'], k['update_splat_kernel']['avg_us'], k['crf_build(all)']['avg_us'])"
 done; done

@@ -6,7 +6,7 @@ for wh in "16 16" "16 12" "12 12" "12 16" "20 16" "16 20" "8 32" ; do
   touch wsss-analysis_amd/csrc/crf.hip
   python __graft_entry__.py > /dev/null 2>&1 || { echo "build failed $wh"; continue; }
   echo "#### TILE_W=$1 TILE_H=$2"
-  python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pipeline --quick 2>/dev/null | python -c "
+  python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pipeline --quick 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stages']
 print('value',d['value'],'crf_infer_ms',s['crf_infer_ms'],'create',s['crf_create_ms'])
