@@ -74,8 +74,7 @@ typedef struct wsc_net wsc_net; /* immutable packed weights of one CNN */
 /* Path selectors of a context (wsc_ctx_set_option).  Each one chooses between two code paths that BOTH serve some inputs
  * in the default configuration (e.g. the Gaussian message is formed on chip only while a tile's vertex set fits the LDS) and
  * are held to identical bits by tests/test_gpu_crf.py and tests/test_gpu_irn.py; the selector forces the fallback for every
- * input so that a test (or a debugging session) can compare.  There are no environment switches in the library; tuning
- * knobs and timing-only ablations exist only in builds with -DWSC_AB_KNOBS (python __graft_entry__.py --ab). */
+ * input so that a test (or a debugging session) can compare.  There are no environment switches in the library. */
 typedef enum {
     WSC_OPT_CRF_GAUSS_ON_CHIP = 0, /* default 1; 0: blur kernels + value-row gathers instead of gauss_msg_kernel */
     WSC_OPT_CRF_FUSED_BLUR = 1,    /* default 1; 0: three blur4 passes instead of blur3_tile_kernel (Gaussian lattice) */

@@ -1,7 +1,6 @@
 """One conv layer through wsc_conv2d_nchw, kernel time from the library's per-launch HIP events.
 
     python profiles/conv_one.py <N> <Cin> <H> <W> <Cout> <k> <stride> <pad> [precision=f16x3] [res=0] [reps=5]
-With the A/B build (ab_tmp/libwsscam_ab.so copied over the package's library) WSC_CONV_DEBUG / WSC_CONV_TILE apply.
 """
 import os
 import sys
@@ -28,17 +27,11 @@ def main():
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     res = ctx.to_device(rng.normal(0, 1, (N, Cout, Ho, Wo)).astype(np.float32)) if use_res else None
     y = ctx.alloc(N * Cout * Ho * Wo * 4)
-    ablation = os.environ.get("WSC_CONV_DEBUG", "0") not in ("", "0")  # (timing-only: results are wrong and may trip the range guard)
     _lib.conv2d_nchw(ctx, x, N, Cin, H, W, w, stride, pad, None, None, res, True, prec, y)
-    if ablation:
-        ctx.range_status(clear=True)
-    else:
-        ctx.sync()
+    ctx.sync()
     ctx.profile_begin()
     for _ in range(reps):
         _lib.conv2d_nchw(ctx, x, N, Cin, H, W, w, stride, pad, None, None, res, True, prec, y)
-    if ablation:
-        ctx.range_status(clear=True)
     prof = ctx.profile_end()
     fl = 2.0 * N * Ho * Wo * Cout * k * k * Cin
     tot = 0.0
@@ -46,8 +39,7 @@ def main():
         if name.startswith("conv_igemm"):
             tot += ms / reps
             print("  %-40s %d launches, %.1f us per layer" % (name, calls // reps, ms / reps * 1e3))
-    print("layer %s: %.1f us, %.0f TFLOP/s algorithmic  [WSC_CONV_DEBUG=%s WSC_CONV_TILE=%s]" % (
-        " ".join(a[:8]), tot * 1e3, fl / (tot * 1e-3) / 1e12, os.environ.get("WSC_CONV_DEBUG", ""), os.environ.get("WSC_CONV_TILE", "")))
+    print("layer %s: %.1f us, %.0f TFLOP/s algorithmic" % (" ".join(a[:8]), tot * 1e3, fl / (tot * 1e-3) / 1e12))
 
 
 if __name__ == "__main__":

@@ -35,8 +35,7 @@ def test_mirror_modules_import(built):
 
 
 def test_shipped_library_has_no_environment_switches(built):
-    """The shipped libwsscam.so reads no WSC_* environment variable: tuning knobs and timing-only ablations exist only in the
-    A/B build (-DWSC_AB_KNOBS, `python __graft_entry__.py --ab`), path selectors are explicit context options
+    """The shipped libwsscam.so reads no WSC_* environment variable: path selectors are explicit context options
     (wsc_ctx_set_option).  Checked on the binary: no 'WSC_<NAME>' string literal is left in it."""
     import re
 

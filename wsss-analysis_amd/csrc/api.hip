@@ -4,6 +4,8 @@
 #include <cerrno>
 #include <cstdarg>
 #include <fcntl.h>
+#include <mutex>
+#include <set>
 #include <sys/uio.h>
 #include <unistd.h>
 #include <vector>
@@ -17,6 +19,16 @@ void wsc_set_error(const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+int wsc_set_max_dynamic_lds(wsc_ctx *ctx, const void *fn, int bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void *, int>> done; // (function, device) pairs whose limit is set
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({fn, ctx->device})) return WSC_OK;
+    WSC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.insert({fn, ctx->device});
+    return WSC_OK;
 }
 
 int wsc_ctx_workspace(wsc_ctx *ctx, size_t bytes, void **out) {

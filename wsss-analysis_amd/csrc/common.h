@@ -104,7 +104,7 @@ void wsc_set_error(const char *fmt, ...);
 
 // ---- per-kernel-class timing (wsc_profile_begin / _end) --------------------------------------------
 enum WscKernelClass {
-    WSC_K_CONV256 = 0,   // conv_igemm_kernel, 256x128 tile, 3-stage LDS-DMA pipeline
+    WSC_K_CONV256 = 0,   // conv_igemm_kernel, 256x256 tile
     WSC_K_CONV128,       // conv_igemm_kernel, 128x128 tile, LDS-DMA staging
     WSC_K_CONV64,        // conv_igemm_kernel, 128x64 tile
     WSC_K_CONV_SMALLCIN, // conv_igemm_kernel, stem / first layer (register staging); stem_pool_kernel (f16x3 ResNet stem + max-pool)
@@ -211,6 +211,10 @@ struct WscCachedGuard {
 };
 // copies `bytes` of host data to dst_dev through the ctx's pinned staging buffer, asynchronously
 int wsc_ctx_upload_small(wsc_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);
+// Raises the dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) of kernel `fn` to `bytes`, once per (function,
+// ctx device), under a lock: the lane threads of the drivers reach the launch sites at the same time.  WSC_ERR_HIP with the
+// error text when the runtime refuses; a failure is not recorded, so the next call tries again.
+int wsc_set_max_dynamic_lds(wsc_ctx *ctx, const void *fn, int bytes);
 
 // ---- conv (implicit GEMM) -----------------------------------------------------------
 // One conv layer as the kernel sees it.  Activations are NHWC bf16; in split

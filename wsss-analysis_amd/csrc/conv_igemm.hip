@@ -29,16 +29,7 @@
 // MFMA instruction.
 #include "common.h"
 
-#include <cstdlib>
 #include <type_traits>
-
-// A/B knobs (tile overrides, timing-only ablations that produce wrong results) exist only in builds with -DWSC_AB_KNOBS
-// (profiles/conv_ab.sh); the shipped library has one code path per decision.
-#ifdef WSC_AB_KNOBS
-#define WSC_DBG(p, bit) ((p).debug & (bit))
-#else
-#define WSC_DBG(p, bit) 0
-#endif
 
 namespace {
 
@@ -67,8 +58,6 @@ struct ConvKArgs {
     int ntiles_n, nblocks;
     const bf16_t *zero; // >= 16 bytes of zeros in HBM: source of padded taps for the LDS-DMA path
     int fast;           // host side only: FAST variant of the kernel this launch may use (0 = generic)
-    int debug;          // WSC_CONV_DEBUG ablations (timing only, results are wrong): 1 = no DMA after the
-                        // first two stages, 2 = no fragment reads / MFMAs
     long long lo_delta; // SPLIT 2: x_lo - x in elements (both planes live in one workspace block)
     // second A source of a 1 x 1 layer (a ResNet stage's first block: conv3 and the projection shortcut as one GEMM, net.hip):
     // channel chunks [0, cc2) come from x (dense [M][ldx]), chunks [cc2, cchunks) from x2 = [N][H2][W2][C2] at pixel
@@ -91,9 +80,7 @@ __device__ __forceinline__ int lds_off(int row, int slot) {
 
 // BM x BN x 64 tile, BM/32 waves (BM/64 along M x 2 along N, 64 x BN/2 per wave), STAGES LDS buffers.
 //   128-row tile: 4 waves, 2 stages, 2 blocks per CU.
-//   256-row tile: 8 waves, 3 stages (144 KB), 1 block per CU: 0.73x the L2->LDS bytes per FLOP and a
-//   prefetch distance of two K-steps, with counted s_waitcnt vmcnt + raw s_barrier so a stage stays in
-//   flight across the barrier (a __syncthreads() would drain the LDS DMA every K-step).
+//   256 x 256 tile: 8 waves of 128 x 64 (WMT = 128), 2 stages, 1 block per CU.
 //
 // FAST (f16, single precision plane, LDS-DMA layers only) removes per-element case handling the common layers do not need:
 //   bit 0  epilogue: fp16 output only, every column tile full (Cout % BN == 0), 32-bit output
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
     constexpr int A_REGION = WIN ? WIN_BYTES : STAGES * A_BYTES;    // bytes in front of the B buffers (two-buffer LDS-DMA path)
     constexpr int CT_STRIDE = BN + 4;
     static_assert(GLDS || (BM == 128 && STAGES <= 2), "register staging exists for the 128-row tile only");
-    static_assert(STAGES >= 1 && STAGES <= 3, "1 (single K-step layers), 2 or 3 LDS buffers");
+    static_assert(STAGES >= 1 && STAGES <= 2, "1 (single K-step layers) or 2 LDS buffers");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -232,38 +219,6 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
     typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     u32x4_t ra[4], rb[NB]; // native vectors: with HIP's uint4 struct the B registers were kept in scratch
 
-    // LDS-DMA issue of one K-step's A and B tiles into buffer `buf` (MODE 0 only)
-    auto issue_dma = [&](int kt, int buf) {
-        int seg = 0, ktl = kt;
-        if (SPLIT) {
-            seg = kt / p.ksteps_base;
-            ktl = kt - seg * p.ksteps_base;
-        }
-        const bf16_t *src = (SPLIT && seg == 1) ? p.x_lo : p.x;
-        const int cc = ktl / p.ntaps;
-        const int tap = ktl - cc * p.ntaps;
-        const int khi = tap / p.kw;
-        const int kwi = tap - khi * p.kw;
-        const long long tap_off = ((long long)khi * p.W + kwi) * p.ldx + cc * 64;
-        char *sa = smem + buf * A_BYTES + wv * 4096;
-        char *sb = smem + STAGES * A_BYTES + buf * B_BYTES + wv * (NB * 1024);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = lrow + RSTEP * i;
-            const int ks = slot ^ ((r >> 1) & 7);
-            const int hi = hb[i] + khi, wi = wb[i] + kwi;
-            const bool ok = PW || ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W);
-            const bf16_t *g = ok ? src + base[i] + tap_off + ks * 8 : p.zero;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                             (__attribute__((address_space(3))) void *)(sa + i * 1024), 16, 0, 0);
-        }
-        const int wk = ((SPLIT && seg == 2) ? p.Kbase : 0) + ktl * 64;
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wrow[i] + wk),
-                                             (__attribute__((address_space(3))) void *)(sb + i * 1024), 16, 0, 0);
-    };
-
     auto load_tile = [&](int kt) __attribute__((always_inline)) {
         int seg = 0, ktl = kt;
         if (SPLIT) {
@@ -326,7 +281,6 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
     const int kgrp = lane >> 5;
 
     auto mfma = [&](const u32x4_t &a, const u32x4_t &b, f32x16_t &c) {
-        if (WSC_DBG(p, 4)) return; // (ablation: no matrix work)
         if (ET == 0)
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b),
                                                         c, 0, 0, 0);
@@ -343,43 +297,8 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
     // LDS byte address of the (only) LDS object
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
 
+    // fragment reads + MFMAs of one K-step of the register-staged (small-Cin) layers
     auto compute = [&](int buf) {
-        if (GLDS) {
-            // Fragment reads in inline asm.  With compiler-visible ds_reads hipcc puts an
-            // s_waitcnt vmcnt(0) in front of the first read of every K-step (it cannot prove that the
-            // in-flight LDS DMA of the NEXT stage does not alias the buffer being read), which drains
-            // the DMA before the MFMAs start and removes all overlap inside a block.  The reads of
-            // k-slice ks+1 are issued before the MFMAs of ks; LDS returns in order, so lgkmcnt(4)
-            // means "all but the 4 newest reads have landed".
-            const unsigned sa = lds0 + buf * A_BYTES, sb = lds0 + STAGES * A_BYTES + buf * B_BYTES;
-            u32x4_t fa[2][MI], fb[2][NI];
-            auto rd = [&](int set, int ks) {
-                const int sl = ks * 2 + kgrp;
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-                    asm volatile("ds_read_b128 %0, %1" : "=v"(fa[set][mi]) : "v"(sa + lds_off(wm * WMT + mi * 32 + l31, sl)) : "memory");
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni)
-                    asm volatile("ds_read_b128 %0, %1" : "=v"(fb[set][ni]) : "v"(sb + lds_off(wn * WN + ni * 32 + l31, sl)) : "memory");
-            };
-            rd(0, 0);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int set = ks & 1;
-                if (ks < 3) {
-                    rd(set ^ 1, ks + 1);
-                    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(MI + NI) : "memory");
-                } else {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < NI; ++ni) mfma(fa[set][mi], fb[set][ni], acc[mi][ni]);
-            }
-            return;
-        }
         const char *sa = smem + buf * A_BYTES;
         const char *sb = smem + STAGES * A_BYTES + buf * B_BYTES;
 #pragma unroll
@@ -401,36 +320,14 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
 
     // ---- main loop ------------------------------------------------------------------
     const int nk = STAGES == 1 ? 1 : p.nk; // (the single-buffer variant is launched for one-K-step layers only)
-    if (GLDS && MODE == 0 && STAGES == 3) {
-        // three LDS buffers, prefetch distance two K-steps.  Every wave issues PER = 4 + NB DMA
-        // instructions per stage; vmcnt(PER) therefore means "everything but the newest stage has
-        // landed".  The raw barrier after it makes the other waves' DMA of that stage visible too and
-        // doubles as the WAR fence for the buffer the next iteration refills.
-        constexpr int PER = 4 + NB;
-        issue_dma(0, 0);
-        if (nk > 1) {
-            issue_dma(1, 1);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        int cur = 0;
-        for (int kt = 0; kt < nk; ++kt) {
-            const bool ahead = kt + 2 < nk;
-            if (ahead && !WSC_DBG(p, 1)) issue_dma(kt + 2, cur == 0 ? 2 : cur - 1);
-            if (!WSC_DBG(p, 2)) compute(cur);
-            if (ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            cur = cur == 2 ? 0 : cur + 1;
-        }
-    } else if (GLDS && MODE == 0) {
+    if (GLDS && MODE == 0) {
         // Two LDS buffers.  The 4 + NB LDS-DMA pieces of K-step kt+1 are issued at the top of K-step kt, before its
         // fragment reads and MFMAs (interleaving one piece after every 1 ... 4 MFMAs was measured: no layer gained,
         // profiles/README.md).  The (segment, tap, channel-chunk) decode of the next K-step is carried incrementally in
         // SGPRs (no per-step integer divisions).  The barrier at the end of a step carries the vmcnt(0) for the pieces
-        // in flight.
+        // in flight.  Fragment reads are inline asm: with compiler-visible ds_reads hipcc puts an s_waitcnt vmcnt(0) in
+        // front of the first read of every K-step (it cannot prove that the in-flight LDS DMA of the NEXT stage does not
+        // alias the buffer being read), which drains the DMA before the MFMAs start.
         int n_seg = 0, n_khi = 0, n_kwi = 0, n_cc = 0, n_ktl = 0; // decode of the next K-step to issue
         const bf16_t *n_src = p.x;
         long long n_tap = 0;
@@ -581,7 +478,7 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
         auto kstep = [&](auto cur_c, int kt) __attribute__((always_inline)) {
             constexpr int cur = decltype(cur_c)::value;
             const unsigned(&oA)[4] = offA, (&oB)[4] = offB; // (named here: the nested lambda below must not be the first use)
-            const bool more = kt + 1 < nk && !WSC_DBG(p, 1);
+            const bool more = kt + 1 < nk;
             if (more) {
                 prep();
                 if (SPLIT != 2) { // (the single-staged split spreads its pieces over the MFMAs, below; spreading them in the
@@ -603,9 +500,8 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
                 auto piece = [&](int j) {
                     if (!more || j % EVERY != 0) return;
                     const int q = j / EVERY;
-                    if (q < NAP) {
-                        if (!(WSC_DBG(p, 32) && (n_khi | n_kwi) != 0)) issue_a(q, cur ^ 1); // (ablation 32: A staged for the first tap of a chunk only)
-                    } else if (q < NAP + NB) issue_b(q - NAP, cur ^ 1);
+                    if (q < NAP) issue_a(q, cur ^ 1);
+                    else if (q < NAP + NB) issue_b(q - NAP, cur ^ 1);
                     __builtin_amdgcn_sched_barrier(0);
                 };
                 // LDS window: the first tap of a chunk sends for the NEXT chunk's window (it has the whole chunk to arrive); the
@@ -674,7 +570,7 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
                             piece((sl * 3 + 2) * MI * NI + mi * NI + ni);
                         }
                 }
-            } else if (STAGES == 1 || !WSC_DBG(p, 2)) {
+            } else {
                 u32x4_t fa[2][MI], fb[2][NI];
 
                 auto rd = [&](int set, int ks) {
@@ -751,13 +647,11 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
                 };
                 static_assert(3 * MI * NI >= 3 * (4 + NB), "a slice has room for every DMA piece");
                 auto rdA = [&](u32x4_t(&f)[MI], int pair) {
-                    if (WSC_DBG(p, 16)) return; // (ablation: no fragment reads)
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi)
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f[mi]) : "v"(oA[pair]), "n"(nbuf * A_BYTES + mi * 4096) : "memory");
                 };
                 auto rdB = [&](u32x4_t(&f)[NI], int pair) {
-                    if (WSC_DBG(p, 16)) return;
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni)
                         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f[ni]) : "v"(oB[pair]), "n"(nbuf * B_BYTES + ni * 4096) : "memory");
@@ -815,10 +709,8 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
             auto rstep = [&](auto cur_c, int kt) __attribute__((always_inline)) {
                 constexpr int cur = decltype(cur_c)::value;
                 slice(std::integral_constant<int, cur>{}, std::integral_constant<int, 1>{}, true, false, 0); // slice 0; requests slice 1
-                if (WSC_DBG(p, 8)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // (ablation: no barrier)
-                else
                 __syncthreads(); // every read of buffer `cur` has landed, for every wave; so has the DMA of K-step kt + 1
-                const bool refill = kt + 2 < nk && !WSC_DBG(p, 1);
+                const bool refill = kt + 2 < nk;
                 if (refill) prep();
                 // slice 1; requests the next K-step's slice 0 and refills buffer `cur`
                 slice(std::integral_constant<int, cur ^ 1>{}, std::integral_constant<int, 0>{}, kt + 1 < nk, refill, cur);
@@ -1092,26 +984,13 @@ int launch_stages(wsc_ctx *ctx, const ConvKArgs &a) {
     constexpr int EPI = (STAGES == 1 ? 64 : (WMT == 128 ? 128 : BM)) * (BN + 4) * 4;
     constexpr int LDS = PIPE > EPI ? PIPE : EPI;
     static_assert(LDS <= 160 * 1024, "LDS budget of a CU");
-    // the attribute belongs to the (function, device) pair: a process may hold contexts on several GPUs
-    static bool attr_set[64] = {};
     auto kern = conv_igemm_kernel<BM, BN, MODE, SPLIT, ET, GLDS, STAGES, WMT, FAST, WPT>;
-    const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-    int lds_req = LDS;
-#ifdef WSC_AB_KNOBS
-    // A/B: pad the LDS request of the multi-K-step tiles (caps the blocks per CU: room for another stream's workgroups)
-    static const int lds_pad = [] { const char *e = getenv("WSC_CONV_LDS_PAD"); return e ? atoi(e) : 0; }();
-    if (STAGES == 2 && lds_pad > lds_req && lds_pad <= 160 * 1024) lds_req = lds_pad;
-#endif
-    if (!attr_set[dev] || ctx->device != dev) {
-        WSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_req > LDS ? 160 * 1024 : LDS));
-        attr_set[dev] = true;
-    }
+    WSC_TRY(wsc_set_max_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), LDS));
     // algorithmic FLOPs: 2 * M * Cout * (kh*kw*Cin_real), x1 regardless of the precision mode
     const double flops = 2.0 * (a.m_end - a.m_base) * a.Cout *
                          ((MODE == 0 && !a.stem_rows) ? (double)a.kh * a.kw * a.Cin : (double)a.kh * (a.stem_rows ? a.kw_real : a.kw) * 3);
     WscKernelTimer timer(ctx, (MODE != 0 || a.stem_rows) ? WSC_K_CONV_SMALLCIN : (BM == 256 ? WSC_K_CONV256 : (BN == 128 ? WSC_K_CONV128 : WSC_K_CONV64)), flops);
-    hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(BM * 2), lds_req, ctx->stream, a);
+    hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(BM * 2), LDS, ctx->stream, a);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
@@ -1124,10 +1003,8 @@ int launch_window(wsc_ctx *ctx, const ConvKArgs &a) {
 
 template <int BM, int BN, int MODE, int SPLIT, int ET, int FAST = 0>
 int launch_variant(wsc_ctx *ctx, const ConvKArgs &a) {
-    if constexpr (BM == 256 && BN == 256) {
+    if constexpr (BM == 256) { // (256 x 256 only)
         return launch_stages<BM, BN, MODE, SPLIT, ET, 2, 128, FAST>(ctx, a);
-    } else if constexpr (BM == 256) {
-        return launch_stages<BM, BN, MODE, SPLIT, ET, 3, 64, FAST>(ctx, a);
     } else if constexpr (MODE == 0) {
         // a one-K-step layer (1x1 conv, 64 input channels) needs one LDS buffer: 34 KB per block, 4 blocks per CU
         // (the single-staged split has 32-channel K-steps: never fewer than two)
@@ -1175,13 +1052,6 @@ int launch_bn(wsc_ctx *ctx, const ConvKArgs &a, int small_cin, int split, int fm
     return launch_variant<128, BN, 2, false, 0>(ctx, a);
 }
 
-// 256 x 128 tile (generic layers only)
-int launch_big(wsc_ctx *ctx, const ConvKArgs &a, int split, int fmt) {
-    if (split) return launch_variant<256, 128, 0, true, 0>(ctx, a);
-    if (fmt && a.fast) return launch_fast<256, 128>(ctx, a, a.fast);
-    if (fmt) return launch_variant<256, 128, 0, false, 1>(ctx, a);
-    return launch_variant<256, 128, 0, false, 0>(ctx, a);
-}
 // 256 x 256 tile, 128 x 64 per wave (generic layers with CoutPad % 256 == 0 only)
 int launch_square(wsc_ctx *ctx, const ConvKArgs &a, int split, int fmt) {
     if (split == 2) return a.fast ? launch_fast<256, 256, 2>(ctx, a, a.fast) : launch_variant<256, 256, 0, 2, 1>(ctx, a);
@@ -1270,13 +1140,6 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     a.ntiles_n = p.CoutPad / BN;
     a.zero = (const bf16_t *)ctx->zero_page;
     a.range = ctx->range_dev;
-#ifdef WSC_AB_KNOBS
-    // timing-only ablations (wrong results): 1 = no DMA after the prologue, 2 = no fragment reads / MFMAs, 4 = no MFMAs
-    static const int debug = [] { const char *e = getenv("WSC_CONV_DEBUG"); return e ? atoi(e) : 0; }();
-    a.debug = debug;
-#else
-    a.debug = 0;
-#endif
     // FAST variants (see the kernel): f16, one precision plane (or the single-staged split), fp16 output only, full column
     // tiles, no post-ReLU affine.  p.generic (wsc_conv2d_nchw's WSC_CONV_GENERIC flag) keeps the generic variants: a test
     // holds the two to the same bits.
@@ -1288,23 +1151,11 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
         if (small_cin_eff == 0 && p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1) a.fast = 3;
     }
     if (a.M == 0) return WSC_OK;
-    // tile choice.  Measured on the ResNet50-CAM stack (64 samples @321^2, f16): 128-row tiles 4.31 ms,
-    // 256-row 3-stage tiles on the K >= 512 layers 4.37 ms, everywhere 4.45 ms -- the stack is bound by
-    // per-block memory latency with 1-2 blocks per CU (an ablation without DMA and without MFMAs still
-    // takes 2.2 ms), not by L2->LDS bytes per FLOP, so the 128-row tile stays the default.  128x64 tiles
-    // (3 blocks per CU) on the K <= 128 / 256 / 512 layers were also measured: no layer gained, layer1.conv3
+    // tile choice: 128 rows.  Measured on the ResNet50-CAM stack (64 samples @321^2, f16): 128-row tiles 4.31 ms, a 256 x 128
+    // three-stage tile on the K >= 512 layers 4.37 ms, everywhere 4.45 ms -- the stack is bound by per-block memory latency
+    // with 1-2 blocks per CU (an ablation without DMA and without MFMAs still takes 2.2 ms), not by L2->LDS bytes per FLOP.
+    // 128x64 tiles (3 blocks per CU) on the K <= 128 / 256 / 512 layers were also measured: no layer gained, layer1.conv3
     // lost 10 %.
-    // WSC_CONV_TILE (A/B runs): 256 selects the 256x128 tile wherever it applies, -1 where K >= 512, 512 the
-    // 256x256 tile wherever CoutPad % 256 == 0, 1 (any other value) the 128-row tiles everywhere.
-#ifdef WSC_AB_KNOBS
-    static const int force = [] { const char *e = getenv("WSC_CONV_TILE"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int force = 0;
-#endif
-    const long long blocks256 = ((a.M + 255) / 256) * (long long)a.ntiles_n;
-    bool big = false;
-    if (force == -1) big = small_cin_eff == 0 && BN == 128 && a.Kbase >= 512 && blocks256 >= 200;
-    if (force == 256) big = small_cin_eff == 0 && BN == 128;
     // 256 x 256 tile: half the L2->LDS bytes per FLOP of the 128 x 128 tile; needs enough K-steps to amortise
     // its 130 KB prologue/epilogue and enough tiles to fill 256 CUs at one block per CU.  VGG16 @321, 64
     // samples: 806 -> 920 TFLOP/s on the 11 layers it takes (stack 11.5 -> 10.8 ms).  Thresholds (>= 4 K-steps, >= one
@@ -1312,14 +1163,10 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     // A grid of 192+ tiles (3/4 of a round: layer4's 3x3 and 1x1 -> 512 convs, 222 tiles) also wins: 4.11 -> 3.97 ms.
     const long long blocks_sq = ((a.M + 255) / 256) * (long long)(p.CoutPad / 256);
     bool square = small_cin_eff == 0 && p.CoutPad % 256 == 0 && a.nk >= 4 && blocks_sq >= 192;
-    if (force == 512) square = small_cin_eff == 0 && p.CoutPad % 256 == 0;
-    if (force != 0 && force != 512) square = false;
-    if (p.split == 2) big = false; // (the three-buffer 256 x 128 tile has no single-staged variant)
-    if (p.x2 != nullptr) big = false; // (nor a second A source)
     if (p.split == 2 && !a.fast) square = false; // (its generic epilogue next to 128 accumulators + both planes' fragments spills)
     // f16x3 K-steps are 32 channels: with fewer than 16 of them (K < 512: layer2's 128 -> 512 and 256 -> 512 convs) the 256 x 256
     // block's prologue + two-group epilogue outweigh its smaller staging traffic (sweep: 109 vs 127 us, 149 vs 162 us)
-    if (p.split == 2 && force == 0 && a.nk < 16) square = false;
+    if (p.split == 2 && a.nk < 16) square = false;
     if (square) {
         const int ntn = p.CoutPad / 256;
         // One block per CU: a grid of r * 256 + rem tiles takes r + 1 rounds.  When the last round would be less
@@ -1327,12 +1174,7 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
         // (<= 512 tiles = one round at 2 blocks per CU, ~0.56 of a square round): VGG16 conv4 (840 tiles) 4 -> 3.6
         // rounds.  The two launches write disjoint output rows.
         const long long rounds = blocks_sq / ctx->num_cus, rem = blocks_sq - rounds * ctx->num_cus;
-#ifdef WSC_AB_KNOBS
-        static const int nosplit = [] { const char *e = getenv("WSC_CONV_NOSPLIT"); return e ? atoi(e) : 0; }();
-#else
-        constexpr int nosplit = 0;
-#endif
-        if (!nosplit && rounds >= 1 && rem > 0 && rem * 2 <= ctx->num_cus && ctx->num_cus > 0) {
+        if (rounds >= 1 && rem > 0 && rem * 2 <= ctx->num_cus && ctx->num_cus > 0) {
             const int big_rows = (int)((rounds * ctx->num_cus) / ntn); // 256-row tile rows given to the square kernel
             ConvKArgs b = a;
             b.ntiles_n = ntn;
@@ -1347,14 +1189,13 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
         a.nblocks = (int)blocks_sq;
         return launch_square(ctx, a, p.split, p.fmt);
     }
-    const int BMsel = big ? 256 : 128;
-    a.nblocks = ((a.M + BMsel - 1) / BMsel) * a.ntiles_n;
+    a.nblocks = ((a.M + 127) / 128) * a.ntiles_n;
     // LDS input window (north star: "3x3 convolutions as MFMA-tiled direct convs with LDS-staged input windows"): the f16x3
     // 3 x 3 / stride 1 / pad 1 layers on 128-row tiles whose window -- the raster positions from (first output pixel - W - 1) to
     // (last output pixel + W + 1), plus the zero row -- fits 256 or 320 positions (32 / 40 KB next to the weight tiles' 32 / 16 KB:
     // two blocks per CU): ResNet50 @321 layer2 / layer3 conv2 (41 x 41: 213, 21 x 21: 173 positions) and, since round 6's
     // unpadded raster, layer1 conv2 (81 x 81: 293).
-    if (!big && single_staged && a.fast == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && p.x2 == nullptr &&
+    if (single_staged && a.fast == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && p.x2 == nullptr &&
         p.Ho == p.H && p.Wo == p.W && ctx->opt[WSC_OPT_CONV_WINDOW] != 0) {
         // positions of a block's window: its 128 output pixels' raster span, one row + one pixel before and after, and the
         // zero row at the window's last position
@@ -1370,7 +1211,6 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
             return need <= 256 ? launch_window<8, 64>(ctx, a) : launch_window<10, 64>(ctx, a);
         }
     }
-    if (big) return launch_big(ctx, a, p.split, p.fmt);
     if (BN == 128) return launch_bn<128>(ctx, a, small_cin_eff, p.split, p.fmt);
     return launch_bn<64>(ctx, a, small_cin_eff, p.split, p.fmt);
 }

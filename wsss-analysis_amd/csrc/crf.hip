@@ -97,13 +97,7 @@ struct LatticeDev {
 // image of W columns is cut into ceil(W / TILE_W) tile columns whose widths differ by at most one).  Neighbouring
 // pixels share lattice vertices (a 16 x 16 tile of a 321 x 321 image touches ~120 of the image's ~10 000 bilateral
 // vertices and ~160 Gaussian ones), so a tile's contribution to a vertex is summed on chip and leaves the CU once.
-#ifndef WSC_TILE_W
-#define WSC_TILE_W 16
-#endif
-#ifndef WSC_TILE_H
-#define WSC_TILE_H 16
-#endif
-constexpr int TILE_W = WSC_TILE_W, TILE_H = WSC_TILE_H, TILE_PIX = TILE_W * TILE_H;
+constexpr int TILE_W = 16, TILE_H = 16, TILE_PIX = TILE_W * TILE_H;
 static_assert(TILE_PIX <= 256, "an entry's pixel index is stored in one byte");
 constexpr int SLOT_ENT = 32;       // entries per slot (bounds the serial chain of one lane group)
 constexpr int SORT_MAX = 2048;     // >= TILE_PIX * 6 entries of a bilateral tile, power of two
@@ -221,44 +215,6 @@ __device__ __forceinline__ int hash_lookup(const unsigned long long *table, unsi
         slot = (slot + 1) & mask;
     }
 }
-
-// ---- wave-aggregated atomics ---------------------------------------------------------------
-// Neighbouring pixels share lattice vertices (57 pixels per bilateral vertex on the bench images),
-// so the lanes of a wave mostly hit the same few table slots / rows.  wave_match returns, for
-// every active lane, the mask of active lanes holding the same (key, tag); the lowest lane of
-// a mask acts for the group: one CAS / atomic per distinct key per wave instead of one per lane.
-__device__ __forceinline__ unsigned long long wave_match(unsigned long long key, int tag) {
-    unsigned long long remaining = __ballot(1);
-    unsigned long long mine = 0;
-    while (remaining) {
-        const int leader = __ffsll((long long)remaining) - 1;
-        const unsigned klo = __shfl((unsigned)key, leader, 64);
-        const unsigned khi = __shfl((unsigned)(key >> 32), leader, 64);
-        const int t = __shfl(tag, leader, 64);
-        const bool same = (unsigned)key == klo && (unsigned)(key >> 32) == khi && tag == t;
-        const unsigned long long m = __ballot(same);
-        if (same) mine = m;
-        remaining &= ~m;
-    }
-    return mine;
-}
-// 32-bit keys (row ids): one shuffle per distinct key instead of three
-__device__ __forceinline__ unsigned long long wave_match32(unsigned key) {
-    unsigned long long remaining = __ballot(1);
-    unsigned long long mine = 0;
-    while (remaining) {
-        const int leader = __ffsll((long long)remaining) - 1;
-        const bool same = key == (unsigned)__shfl((int)key, leader, 64);
-        const unsigned long long m = __ballot(same);
-        if (same) mine = m;
-        remaining &= ~m;
-    }
-    return mine;
-}
-// (Matching only RUNS of adjacent lanes -- three shuffles and two ballots instead of one loop trip per
-// distinct key -- was measured: the lattice build went from 2.6 to 4.5 ms per 32-image batch; equal keys
-// are interleaved across the wave, not adjacent, and the extra atomics cost far more than the loop.)
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // XCD-contiguous work split for the gather kernels.  Blocks are dispatched round-robin over the 8
 // XCDs (block b -> XCD b % 8); a plain grid-stride loop therefore makes every XCD touch every
@@ -646,7 +602,7 @@ __device__ __forceinline__ void tile_slot_flags(const int *srow, int ne, unsigne
 //      the vertex: every group gets a TILE_PIX-bit pixel mask (LDS atomicOr: the result does not depend on arrival order),
 //      rank = popcount of the mask below the pixel.  ~120 instructions per wave instead of the ~1800 of the ballot-matching
 //      walk (wave q walks the q-th quarter of the index range, 64 entries at a time, equal slots matched with ballots),
-//      which stays as the path for tiles with more than RANK_GMAX distinct vertices (noise images) or WSC_CRF_RANK_BALLOT=1
+//      which stays as the path for tiles with more than RANK_GMAX distinct vertices (noise images) or WSC_OPT_CRF_RANK_BALLOT = 1
 //   C  per occupied slot: group size; global insert + atomicMin of the first-touch index (vertex ids are assigned in
 //      first-touch raster order, the CPU reference's insertion order)
 //   D  scan -> group starts; position = start + entries of the group in earlier quarters + rank
@@ -655,10 +611,7 @@ __device__ __forceinline__ void tile_slot_flags(const int *srow, int ne, unsigne
 // first launch runs every tile on a 512-slot table (19 KB of LDS instead of 53: eight blocks per CU instead of three) and
 // a tile with more than 0.75 * 512 distinct vertices -- noise -- quits before it has written anything and puts itself on a
 // list that a second launch works off with the full 2048-slot table (load <= 0.75 even when every entry has its own vertex).
-#ifndef WSC_EMBED_HT
-#define WSC_EMBED_HT 512
-#endif
-constexpr int GROUP_HT_SMALL = WSC_EMBED_HT, GROUP_HT_FULL = SORT_MAX;
+constexpr int GROUP_HT_SMALL = 512, GROUP_HT_FULL = SORT_MAX;
 constexpr int RANK_MW = (TILE_PIX + 31) / 32;            // mask words per group
 template <int D, int GROUP_HT>
 __device__ __forceinline__ void tile_embed_body(const EmbedArgs &a, const TileGeom &tg, float *__restrict__ tent_w,
@@ -1135,9 +1088,8 @@ __global__ void combine1_kernel(const float *__restrict__ part, const int32_t *_
     }
 }
 
-// Rows from slot partials, iteration form (bilateral lattice; the Gaussian lattice combines inside its fused
-// blur).  LP lanes per row, rows padded to Mp = 4*LP floats; a row's partials are consecutive.
-template <bool PLAIN>
+// Rows from slot partials, iteration form (the Gaussian lattice when its fused blur does not run: its partial rows are in a
+// deterministic order, a plain fp32 sum).  LP lanes per row, rows padded to Mp = 4*LP floats; a row's partials are consecutive.
 __global__ __launch_bounds__(256) void combine4_kernel(const f32x4_t *__restrict__ part, const int32_t *__restrict__ row_slot_start,
                                                        int LP, int rows_local, int n_slots, int rep, f32x4_t *__restrict__ val) {
     const int rpb = 256 / LP;
@@ -1152,7 +1104,7 @@ __global__ __launch_bounds__(256) void combine4_kernel(const f32x4_t *__restrict
     for (long long row = rbeg + tr; row < rend; row += rpb) {
         const int sb = row_slot_start[row], se = row_slot_start[row + 1];
         f32x4_t o = {0.f, 0.f, 0.f, 0.f};
-        if (se > sb) o = combine_slots4<PLAIN>(part, sb, se, (unsigned)LP, (unsigned)l);
+        if (se > sb) o = combine_slots4<true>(part, sb, se, (unsigned)LP, (unsigned)l);
         val[(unsigned)row * (unsigned)LP + l] = o;
     }
 }
@@ -1163,13 +1115,7 @@ __global__ __launch_bounds__(256) void combine4_kernel(const f32x4_t *__restrict
 // 96-byte loads in flight each), find a partial's row by bisection in the block's slice of row_slot_start, and add it into
 // the row's 64-bit fixed-point accumulators in LDS (integer atomics: order-independent, so the result is the one of
 // combine_slots4<false>, bit for bit; a row's single partial is passed through unconverted as there).
-#ifndef WSC_CB_ROWS
-#define WSC_CB_ROWS 32 // (A/B on the VOC batch: 128 / 64 / 32 / 16 / 8 rows per block -> 85 / 75 / 67 / 67 / 77 us per launch)
-#endif
-#ifndef WSC_CB_U
-#define WSC_CB_U 4
-#endif
-constexpr int CB_ROWS = WSC_CB_ROWS;
+constexpr int CB_ROWS = 32; // (VOC batch: 128 / 64 / 32 / 16 / 8 rows per block -> 85 / 75 / 67 / 67 / 77 us per launch)
 // part_row != null: a partial row's lattice row (and whether it is the row's only partial) comes from a table written at
 // build time -- one coalesced 4-byte load issued together with the partial row itself -- instead of a bisection in the
 // block's slice of row_slot_start, and the partial loads no longer wait for that slice to be staged in LDS.
@@ -1185,7 +1131,7 @@ __global__ __launch_bounds__(256) void combine4_balanced_kernel(const f32x4_t *_
     for (int i = threadIdx.x; i < CB_ROWS * 32; i += 256) acc[i] = 0ull;
     const int gpb = 256 / LP;
     const int tr = threadIdx.x / LP, l = threadIdx.x - tr * LP;
-    constexpr int U = WSC_CB_U;
+    constexpr int U = 4;
     // the first batch of partial rows travels while the accumulators are cleared
     f32x4_t v[U];
     uint32_t pr[U];
@@ -1324,11 +1270,7 @@ constexpr int BL_THREADS = 1024;
 constexpr int BL_NVAR = 5;
 constexpr int BL_VAR[BL_NVAR][2] = {{4, 4}, {4, 10}, {3, 13}, {2, 20}, {1, 26}};
 inline int blur_lds_variant(int rows) {
-    int v0 = 0;
-#ifdef WSC_AB_KNOBS
-    if (const char *e = getenv("WSC_BLUR_LDS_MINVAR")) v0 = atoi(e); // A/B: start at a later variant (fewer classes per workgroup)
-#endif
-    for (int v = v0; v < BL_NVAR; ++v)
+    for (int v = 0; v < BL_NVAR; ++v)
         if (rows <= BL_VAR[v][1] * BL_THREADS && (size_t)(rows + 1) * BL_VAR[v][0] * 4 <= 160 * 1024 && rows < 65535) return v;
     return -1;
 }
@@ -1477,16 +1419,9 @@ __global__ __launch_bounds__(BL_THREADS) void blur_lds_kernel(BlurLdsArgs p) {
 // three passes there with fixed local offsets (no neighbour table), and writes the GTI x GTJ interior: one read
 // and one write of the value array instead of three of each.  Per pass the arithmetic is blur4_kernel's
 // (c + 0.5f * (a + b), a + b commutes), so the result is bit-identical.
-#ifndef WSC_GTI
-#define WSC_GTI 12
-#endif
-#ifndef WSC_GTJ
-#define WSC_GTJ 12
-#endif
-#ifndef WSC_GLH
-#define WSC_GLH 6
-#endif
-constexpr int GTI = WSC_GTI, GTJ = WSC_GTJ, GBI = GTI + 4, GBJ = GTJ + 4; // tile interior / halo box in i and j
+// (12 x 28, 28 x 12 and 28 x 28 interiors were measured: the smaller halo share does not pay for fewer blocks per CU)
+constexpr int GTI = 12, GTJ = 12, GBI = GTI + 4, GBJ = GTJ + 4; // tile interior / halo box in i and j
+constexpr int GLH = 6; // float4s of a row per load / blur / store group of blur3_tile_kernel (see combine_blur_all4)
 
 __global__ void gauss_ij_kernel(const unsigned long long *__restrict__ rowkey, int rows, int2 *__restrict__ ij,
                                 int *__restrict__ bbox /* imin jmin imax jmax err */) {
@@ -1530,10 +1465,6 @@ __global__ void gauss_tile_pstart_kernel(const int32_t *__restrict__ tile_rows, 
     }
 }
 
-#ifndef WSC_BLUR3_INPLACE
-#define WSC_BLUR3_INPLACE 1
-#endif
-template <int LH>
 __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__restrict__ in, const int32_t *__restrict__ tile_rows,
                                                          const int32_t *__restrict__ tile_list, int n_occ, int LP,
                                                          int rows_local, int rep, f32x4_t *__restrict__ out,
@@ -1543,14 +1474,9 @@ __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__
     // of the splat (combine_slots4, consecutive partial rows) while loading; `in` is unused
     constexpr int P = GBI * GBJ; // one thread per point of the halo box
     // plane stride P + 1: the row-wise load / store phases address (point, float4) with the float4 index fastest, and a
-    // stride of exactly P float4s (4096 B) would put a row's LH float4s on one bank
+    // stride of exactly P float4s (4096 B) would put a row's GLH float4s on one bank
     constexpr int PS = P + 1;
-#if WSC_BLUR3_INPLACE
-    __shared__ f32x4_t b0[LH * PS];
-    f32x4_t *const b1 = b0; // (unused by the in-place passes)
-#else
-    __shared__ f32x4_t b0[LH * PS], b1[LH * PS];
-#endif
+    __shared__ f32x4_t b0[GLH * PS];
     // XCD-contiguous logical block id: neighbouring tiles of one replica (which share halo rows) on one L2
     const int nb = gridDim.x, bid = blockIdx.x;
     const int xcd = bid & 7, qq = nb >> 3, rr = nb & 7;
@@ -1568,14 +1494,14 @@ __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__
     const bool r0 = row && li >= 1 && li < GBI - 1;      // pass 0 region
     const bool r1 = r0 && lj >= 1 && lj < GBJ - 1;       // pass 1 region
     const bool r2 = row && li >= 2 && li < GBI - 2 && lj >= 2 && lj < GBJ - 2; // interior
-    // Memory side: LH consecutive lanes move the LH consecutive float4s of ONE row (a wave instruction touches
-    // 64/LH rows of LH*16 contiguous bytes; with a lane per point it touched 64 different rows, 16 bytes each, and
-    // the kernel was bound by the L1's line rate).  Item i of thread tid is float4 ll = idx % LH of point
-    // pp = idx / LH, idx = i*P + tid; the three passes below stay one thread per point.
-    int prow[LH], psb[LH], pse[LH];
+    // Memory side: GLH consecutive lanes move the GLH consecutive float4s of ONE row (a wave instruction touches
+    // 64/GLH rows of GLH*16 contiguous bytes; with a lane per point it touched 64 different rows, 16 bytes each, and
+    // the kernel was bound by the L1's line rate).  Item i of thread tid is float4 ll = idx % GLH of point
+    // pp = idx / GLH, idx = i*P + tid; the three passes below stay one thread per point.
+    int prow[GLH], psb[GLH], pse[GLH];
 #pragma unroll
-    for (int i = 0; i < LH; ++i) {
-        const int pp = (i * P + p) / LH;
+    for (int i = 0; i < GLH; ++i) {
+        const int pp = (i * P + p) / GLH;
         const int pli = pp / GBJ, plj = pp - pli * GBJ;
         const int r = tile_rows[tbase + pp];
         psb[i] = 0; pse[i] = 0;
@@ -1587,13 +1513,13 @@ __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__
         // negative: the point is not written back (halo, or absent)
         prow[i] = (r && pli >= 2 && pli < GBI - 2 && plj >= 2 && plj < GBJ - 2) ? r : (r ? -r : 0);
     }
-    for (int lbase = 0; lbase < LP; lbase += LH) {
+    for (int lbase = 0; lbase < LP; lbase += GLH) {
         if (lbase > 0) __syncthreads(); // the previous group's reads of b0 / b1 are done
         {
-            f32x4_t v[LH];
+            f32x4_t v[GLH];
 #pragma unroll
-            for (int i = 0; i < LH; ++i) {
-                const int idx = i * P + p, pp = idx / LH, ll = idx - pp * LH;
+            for (int i = 0; i < GLH; ++i) {
+                const int idx = i * P + p, pp = idx / GLH, ll = idx - pp * GLH;
                 const int r = prow[i] < 0 ? -prow[i] : prow[i];
                 v[i] = zero;
                 if (r && lbase + ll < LP) {
@@ -1607,22 +1533,21 @@ __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__
                 }
             }
 #pragma unroll
-            for (int i = 0; i < LH; ++i) {
-                const int idx = i * P + p, pp = idx / LH, ll = idx - pp * LH;
+            for (int i = 0; i < GLH; ++i) {
+                const int idx = i * P + p, pp = idx / GLH, ll = idx - pp * GLH;
                 if (part && pse[i] - psb[i] > 1 && lbase + ll < LP)
                     v[i] = combine_slots4<true>(part, psb[i], pse[i], (unsigned)LP, (unsigned)(lbase + ll));
                 b0[ll * PS + pp] = v[i];
             }
         }
         __syncthreads();
-#if WSC_BLUR3_INPLACE
         // ONE LDS plane set: a pass reads its three taps into registers, a barrier, then writes them back in place (two
         // barriers per pass instead of one, but 24.7 KB of LDS per block instead of 49.3: six blocks per CU instead of three
         // for the load phase's dependent gathers to hide behind)
-        f32x4_t o[LH];
+        f32x4_t o[GLH];
         // pass 0, axis 0: (i +- 1, j) = p +- GBJ
 #pragma unroll
-        for (int l = 0; l < LH; ++l) {
+        for (int l = 0; l < GLH; ++l) {
             o[l] = zero;
             if (r0) {
                 const f32x4_t c = b0[l * PS + p], a = b0[l * PS + p + GBJ], b = b0[l * PS + p - GBJ];
@@ -1632,11 +1557,11 @@ __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__
         }
         __syncthreads();
 #pragma unroll
-        for (int l = 0; l < LH; ++l) b0[l * PS + p] = o[l];
+        for (int l = 0; l < GLH; ++l) b0[l * PS + p] = o[l];
         __syncthreads();
         // pass 1, axis 1: (i, j +- 1) = p +- 1
 #pragma unroll
-        for (int l = 0; l < LH; ++l) {
+        for (int l = 0; l < GLH; ++l) {
             o[l] = zero;
             if (r1) {
                 const f32x4_t c = b0[l * PS + p], a = b0[l * PS + p - 1], b = b0[l * PS + p + 1];
@@ -1646,12 +1571,12 @@ __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__
         }
         __syncthreads();
 #pragma unroll
-        for (int l = 0; l < LH; ++l) b0[l * PS + p] = o[l];
+        for (int l = 0; l < GLH; ++l) b0[l * PS + p] = o[l];
         __syncthreads();
         // pass 2, axis 2: (i -+ 1, j -+ 1) = p -+ (GBJ + 1); interior only
         if (r2) {
 #pragma unroll
-            for (int l = 0; l < LH; ++l) {
+            for (int l = 0; l < GLH; ++l) {
                 const f32x4_t c = b0[l * PS + p], a = b0[l * PS + p - GBJ - 1], b = b0[l * PS + p + GBJ + 1];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) o[l][q] = c[q] + 0.5f * (a[q] + b[q]);
@@ -1660,50 +1585,13 @@ __global__ __launch_bounds__(GBI * GBJ) void blur3_tile_kernel(const f32x4_t *__
         __syncthreads();
         if (r2) {
 #pragma unroll
-            for (int l = 0; l < LH; ++l) b0[l * PS + p] = o[l];
-        }
-#else
-        // pass 0, axis 0: (i +- 1, j) = p +- GBJ
-#pragma unroll
-        for (int l = 0; l < LH; ++l) {
-            f32x4_t o = zero;
-            if (r0) {
-                const f32x4_t c = b0[l * PS + p], a = b0[l * PS + p + GBJ], b = b0[l * PS + p - GBJ];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = c[q] + 0.5f * (a[q] + b[q]);
-            }
-            b1[l * PS + p] = o;
+            for (int l = 0; l < GLH; ++l) b0[l * PS + p] = o[l];
         }
         __syncthreads();
-        // pass 1, axis 1: (i, j +- 1) = p +- 1
 #pragma unroll
-        for (int l = 0; l < LH; ++l) {
-            f32x4_t o = zero;
-            if (r1) {
-                const f32x4_t c = b1[l * PS + p], a = b1[l * PS + p - 1], b = b1[l * PS + p + 1];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = c[q] + 0.5f * (a[q] + b[q]);
-            }
-            b0[l * PS + p] = o;
-        }
-        __syncthreads();
-        // pass 2, axis 2: (i -+ 1, j -+ 1) = p -+ (GBJ + 1); interior only; through b1 to the row-wise store
-        if (r2) {
-#pragma unroll
-            for (int l = 0; l < LH; ++l) {
-                const f32x4_t c = b0[l * PS + p], a = b0[l * PS + p - GBJ - 1], b = b0[l * PS + p + GBJ + 1];
-                f32x4_t o;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = c[q] + 0.5f * (a[q] + b[q]);
-                b1[l * PS + p] = o;
-            }
-        }
-#endif
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < LH; ++i) {
-            const int idx = i * P + p, pp = idx / LH, ll = idx - pp * LH;
-            if (prow[i] > 0 && lbase + ll < LP) out[(unsigned)prow[i] * (unsigned)LP + lbase + ll] = (WSC_BLUR3_INPLACE ? b0 : b1)[ll * PS + pp];
+        for (int i = 0; i < GLH; ++i) {
+            const int idx = i * P + p, pp = idx / GLH, ll = idx - pp * GLH;
+            if (prow[i] > 0 && lbase + ll < LP) out[(unsigned)prow[i] * (unsigned)LP + lbase + ll] = b0[ll * PS + pp];
         }
     }
 }
@@ -1888,18 +1776,7 @@ struct UpdateArgs {
     const uint4 *gt_pix;
     const float *part_g_in;
     int gt_stride;
-    unsigned long long *tl; // A/B builds: per block 8 shader-clock stamps at the phase boundaries (null: off)
 };
-#ifdef WSC_AB_KNOBS
-#define WSC_TL(a, i)                                                                                    \
-    do {                                                                                                \
-        if ((a).tl != nullptr && threadIdx.x == 0) (a).tl[(size_t)blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define WSC_TL(a, i) \
-    do {             \
-    } while (0)
-#endif
 constexpr int SPLAT_TAB_BYTES = (int)(sizeof(uint2) * TILE_PIX * 6 + sizeof(int2) * 256); // entries + slot descriptors
 
 // load through a uniform base + 32-bit byte offset: the compiler can use the SGPR-base addressing form and the
@@ -1914,9 +1791,6 @@ constexpr int GATHER_ENT = TILE_PIX * 6;
 // partial[slot] = sum over the slot's entries of w * stage[pixel] in the entries' order, one slot per lane group per
 // trip.  The tile's entries (contiguous in memory) and slot descriptors are copied into LDS first: the per-slot chains
 // (descriptor -> entries -> Q rows) then run on LDS latency, not on three dependent trips to L2 / HBM per slot.
-#ifndef WSC_SPLAT_ABL
-#define WSC_SPLAT_ABL 0 // timing-only ablations of the splat phase (wrong results): 1 no partial-row stores, 2 no gather, 4 no entry copy
-#endif
 // The splat tables of one (tile, lattice) held in registers between their request and their use: the tile's entries
 // (TILE_PIX * (d+1) of them: EN per thread), the thread's slot descriptor of the first batch and the tile's slot range.
 // Requested early (the Gaussian lattice's before the trips, the bilateral one's before the Gaussian gather), they arrive
@@ -1933,7 +1807,7 @@ template <int EN>
 __device__ __forceinline__ void splat_fetch(const SplatTab &T, int tile, long long ebase_pix, int np, SplatRegs<EN> &r) {
     r.s_beg = T.tslot_start[tile];
     r.s_end = T.tslot_start[tile + 1];
-    const int ne = (WSC_SPLAT_ABL & 4) ? 0 : np * T.dp1;
+    const int ne = np * T.dp1;
     const float *sw = T.tent_w + ebase_pix * T.dp1;
     const uint8_t *sp = T.tent_p + ebase_pix * T.dp1;
 #pragma unroll
@@ -1951,7 +1825,7 @@ __device__ __forceinline__ void splat_fetch(const SplatTab &T, int tile, long lo
 }
 template <int EN>
 __device__ __forceinline__ void splat_commit(const SplatTab &T, int np, const SplatRegs<EN> &r, uint2 *lent, int2 *ldesc, int LP) {
-    const int ne = (WSC_SPLAT_ABL & 4) ? 0 : np * T.dp1;
+    const int ne = np * T.dp1;
 #pragma unroll
     for (int i = 0; i < EN; ++i) {
         const int e = (int)threadIdx.x + i * (int)blockDim.x;
@@ -1976,7 +1850,7 @@ __device__ __forceinline__ void tile_gather(const SplatTab &T, int s_beg, int s_
             const int s = s0 + g;
             const bool ok = act && s < nsb;
             const int2 d = ok ? ldesc[s] : make_int2(0, 0);
-            const int i0 = d.x & 0xffff, n = (WSC_SPLAT_ABL & 2) ? 0 : d.x >> 16;
+            const int i0 = d.x & 0xffff, n = d.x >> 16;
             // explicit packed FMAs (this file is compiled with -ffp-contract=off for the simplex search): the gather
             // is VALU/LDS-issue bound, 8 v_pk_fma_f32 per 4 entries instead of 16 mul + 16 add
             f32x2_t a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
@@ -2016,7 +1890,7 @@ __device__ __forceinline__ void tile_gather(const SplatTab &T, int s_beg, int s_
                 }
             }
             const f32x4_t acc = {a01[0], a01[1], a23[0], a23[1]};
-            if (ok && !(WSC_SPLAT_ABL & 1)) part[(unsigned)d.y * (unsigned)LP + l] = acc;
+            if (ok) part[(unsigned)d.y * (unsigned)LP + l] = acc;
         }
         __syncthreads();
     }
@@ -2036,17 +1910,19 @@ __device__ __forceinline__ void tile_gather(const SplatTab &T, int s_beg, int s_
 // points at E, the energy starts from +E instead of -U, and only the six bilateral rows are gathered.  Bit-identical to
 // the unfused path; the Gaussian lattice's value rows never exist, and the message kernel runs beside the bilateral
 // lattice's combine + blur chain between two updates.
-// DMA (GF variants): the tile's E rows and 52-byte records are streamed into LDS by LDS-DMA loads (global_load_lds: no
-// registers, every byte of the tile in flight at once) before the trips start -- E straight into the Q-stage slots its lanes
+// DMA (the GF updates; the first update stages its U rows the same way): the tile's E rows and 52-byte records are streamed
+// into LDS by LDS-DMA loads (global_load_lds: no registers, every byte of the tile in flight at once) before the trips
+// start -- E straight into the Q-stage slots its lanes
 // overwrite later, the records (padded to 56 bytes) into the region the splat tables use afterwards.  The trips then read
 // both from LDS and only the six bilateral row gathers (L2) remain in a trip's dependent chain; without it a trip waits
 // for its record from HBM before it can request its rows, and the kernel is bound by that latency at 4 waves per SIMD.
 constexpr int REC_LDS_BYTES = 56; // 13 dwords + 1 pad: 8-byte aligned records, TILE_PIX of them fit the splat-table region
 static_assert(TILE_PIX * REC_LDS_BYTES <= (int)(sizeof(uint2) * GATHER_ENT + sizeof(int2) * GATHER_SB), "record stage");
-template <bool SLICE, bool SPLAT, bool GF = false, bool DMA = false, int FG = 0>
+template <bool SLICE, bool SPLAT, bool GF = false, int FG = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void update_splat_kernel(UpdateArgs a) {
-    static_assert(!DMA || (SLICE && GF) || (!SLICE && SPLAT), "the LDS-DMA staging belongs to the GF updates and the first update");
-    static_assert(FG == 0 || (SLICE && GF && DMA), "the in-kernel Gaussian message belongs to the DMA-staged GF updates");
+    constexpr bool DMA = GF || (!SLICE && SPLAT); // LDS-DMA staging: the GF updates and the first update
+    static_assert(!GF || SLICE, "the GF updates slice");
+    static_assert(FG == 0 || GF, "the in-kernel Gaussian message belongs to the GF updates");
     extern __shared__ f32x4_t stage[]; // [TILE_PIX][LP]
     const int LP = a.LP;
     const int gpw = 64 / LP;
@@ -2178,9 +2054,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
     };
     const int t_first = (int)(threadIdx.x >> 6) * gpw;
     // splat tables of the Gaussian lattice: requested now, used after the trips (8 registers across the loop)
-    constexpr int EN_G = (TILE_PIX * 3 + 255) / 256, EN_B = (TILE_PIX * 6 + 255) / 256; // blocks of >= 256 threads (update_threads)
+    constexpr int EN_G = (TILE_PIX * 3 + 255) / 256, EN_B = (TILE_PIX * 6 + 255) / 256; // blocks of >= 256 threads
     SplatRegs<EN_G> rg;
-    WSC_TL(a, 0); // block start
     if (SPLAT && FG == 0) splat_fetch<EN_G>(a.sg, a.sg.shared ? j : lb, (a.sg.shared ? 0ll : (long long)k * N) + tb.ebase, np, rg);
     // FG: the descriptors of the tile's closed vertex set {first partial row, count} are requested before the LDS-DMA pieces
     // (loads return in order: behind them the first wait of the Gaussian phase would sit behind the whole tile's stream)
@@ -2231,7 +2106,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
             __syncthreads();
         }
     }
-    WSC_TL(a, 1); // DMA issued (FG) / landed (two-launch form)
     if constexpr (FG > 0) {
         // ---- Gaussian message of the tile, on chip (round 6): the body of gauss_msg_kernel with E = -U + message left in the
         // Q stage instead of HBM.  blockDim.x == GM_THREADS.  The U rows and the records are already travelling (LDS-DMA above);
@@ -2256,7 +2130,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
                 val[it] = zero;
                 if (ps[it].y > 0) val[it] = partg[(unsigned)ps[it].x * (unsigned)LP + ll];
             }
-            WSC_TL(a, 2); // descriptors arrived, first partials requested
             if (tid < stride) reinterpret_cast<uint4 *>(lnb)[tid] = tn0;
             for (int v = tid + GM_THREADS; v < stride; v += GM_THREADS) reinterpret_cast<uint4 *>(lnb)[v] = tn[v];
             // further partials of the rows that have them (tile-border vertices: up to four tiles touch one): the second, third
@@ -2311,7 +2184,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
         // every load of this wave so far has been consumed -- the partial rows were requested after the LDS-DMA pieces and
         // loads return in order, so the wave's pieces (U rows, records) have landed too; the barrier below publishes them
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        WSC_TL(a, 3); // all partial rows summed into LDS
         // the pixels' Gaussian records (L2: one table for all images) travel under the blur passes
         uint4 gpx[NPI];
 #pragma unroll
@@ -2378,7 +2250,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
         if (SPLAT) splat_fetch<EN_G>(a.sg, a.sg.shared ? j : lb, (a.sg.shared ? 0ll : (long long)k * N) + tb.ebase, np, rg);
         __syncthreads();
     }
-    WSC_TL(a, 4); // E in the Q stage: the trips start
     // softmax of the current trip's energy (e01, e23) -> Q into the tile's stage (and to memory / the arg-max in the last update)
     auto emit = [&](int t0) {
         const int t = t0 + g;
@@ -2471,7 +2342,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
             if (has_next) fold(un1, vgn, vbn, wrn, e01, e23); // the next trip's energy: its rows have had this trip to arrive
         }
     }
-    WSC_TL(a, 5); // this wave's trips done
     if (SPLAT) {
         uint2 *lent = reinterpret_cast<uint2 *>(stage + TILE_PIX * LP);
         int2 *ldesc = reinterpret_cast<int2 *>(lent + GATHER_ENT);
@@ -2482,12 +2352,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
         splat_fetch<EN_B>(a.sb, a.sb.shared ? j : lb, (a.sb.shared ? 0ll : (long long)k * N) + tb.ebase, np, rb);
         __syncthreads(); // Q stage + Gaussian tables complete
         tile_gather(a.sg, rg.s_beg, rg.s_end, k, stage, lent, ldesc, LP, l, g, gpw, act); // (ends with a barrier)
-        WSC_TL(a, 6); // Gaussian slots written
         splat_commit<EN_B>(a.sb, np, rb, lent, ldesc, LP);
         __syncthreads();
         tile_gather(a.sb, rb.s_beg, rb.s_end, k, stage, lent, ldesc, LP, l, g, gpw, act);
     }
-    WSC_TL(a, 7); // block end
 }
 
 // ---- Gaussian message of a pixel tile, on chip ------------------------------------------------------------------------
@@ -2497,9 +2365,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void u
 // blur3_tile_kernel, value for value) and folds the three vertex rows of every pixel into -U with the FMAs, in the order,
 // update_splat_kernel uses -- which then starts from E (its GF variants) and gathers the bilateral rows only.  One read of
 // the partial rows, no value rows in HBM, and the launch runs beside the bilateral lattice's combine + blur chain.
-#ifndef WSC_GF_ABL
-#define WSC_GF_ABL 0 // timing-only ablations (wrong results): 1 no blur passes, 2 no partial-row loads, 4 no slice
-#endif
 struct GaussMsgArgs {
     const int4 *gt_cnt;
     const int2 *gt_rows;
@@ -2548,8 +2413,8 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
         ps[it] = make_int2(0, 0);
         if (i < nitems) ps[it] = trow[((unsigned)i * lp_magic) >> 16];
     }
-    // the pixels' records and unaries: requested up front when the registers allow it (the small variant), else after the blur
-    constexpr bool EARLY = false; // (up front they cost 30 registers: two blocks per CU instead of four, 186 -> 241 us)
+    // the pixels' records and unaries, requested after the blur (up front they cost 30 registers: two blocks per CU instead
+    // of four, 186 -> 241 us)
     uint4 gpx[NPI];
     f32x4_t uu[NPI];
     unsigned poff[NPI];
@@ -2570,7 +2435,6 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             }
         }
     };
-    if (EARLY) load_pixels();
 #pragma unroll 2
     for (int v = tid; v < stride; v += GM_THREADS) reinterpret_cast<uint4 *>(lnb)[v] = tn[v];
     {
@@ -2582,14 +2446,13 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             const int i = tid + it * GM_THREADS;
             const unsigned v = ((unsigned)i * lp_magic) >> 16, ll = (unsigned)i - v * (unsigned)LP;
             val[it] = zero;
-            if (!(WSC_GF_ABL & 2) && ps[it].y > 0) val[it] = partg[(unsigned)ps[it].x * (unsigned)LP + ll];
+            if (ps[it].y > 0) val[it] = partg[(unsigned)ps[it].x * (unsigned)LP + ll];
         }
         // further partials of the rows that have them, all items of the thread per step (static register indices;
         // every row still adds its partials in index order: first + second + ...)
         int maxc = 0;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) maxc = max(maxc, ps[it].y);
-        if (WSC_GF_ABL & 2) maxc = 0;
         // (round 6: requesting the second ... fourth partials of every item together -- what the FG variants of
         // update_splat_kernel do -- costs this kernel 32 registers and a block per CU: 186 -> 220 us; one partial per step stays)
         for (int c = 1; c < maxc; ++c) {
@@ -2616,7 +2479,7 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     }
     __syncthreads();
 #pragma unroll
-    for (int axis = 0; axis < ((WSC_GF_ABL & 1) ? 0 : 3); ++axis) {
+    for (int axis = 0; axis < 3; ++axis) {
         // pass `axis` only has to be right on the vertices the later passes and the slice read: the nested prefixes of the
         // set (gauss_fuse_tables); the rest keeps its old value, which nothing reads any more
         const int nitems = (axis == 0 ? cnt.z : (axis == 1 ? cnt.y : cnt.x)) * LP;
@@ -2643,7 +2506,7 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     }
     // slice into the energy: E = -U, then the three FMAs of update_splat_kernel, same order, same weights
     // ((bary * norm) * (compat * alpha))
-    if (!EARLY) load_pixels();
+    load_pixels();
 #pragma unroll
     for (int it = 0; it < NPI; ++it) {
         const int i = tid + it * GM_THREADS;
@@ -2653,7 +2516,7 @@ __global__ __launch_bounds__(GM_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             f32x2_t o01 = {-uu[it][0], -uu[it][1]}, o23 = {-uu[it][2], -uu[it][3]};
             const float wr[3] = {__uint_as_float(gp.y) * a.cag, __uint_as_float(gp.z) * a.cag, __uint_as_float(gp.w) * a.cag};
 #pragma unroll
-            for (int r = 0; r < ((WSC_GF_ABL & 4) ? 0 : 3); ++r) {
+            for (int r = 0; r < 3; ++r) {
                 const f32x4_t row = gl[((gp.x >> (10 * r)) & 1023u) * (unsigned)LP + ll];
                 const f32x2_t w2 = {wr[r], wr[r]}, lo = {row[0], row[1]}, hi = {row[2], row[3]};
                 o01 = __builtin_elementwise_fma(w2, lo, o01);
@@ -2755,20 +2618,12 @@ __global__ __launch_bounds__(TP) void finish_kernel(const float *__restrict__ q,
     }
 }
 
-__global__ void fill_u32_kernel(unsigned *p, unsigned v, long long n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        p[i] = v;
-}
 // the hash table (EMPTY_KEY) and its first-toucher array (0x7fffffff) in one pass
 __global__ void fill_tables_kernel(unsigned long long *__restrict__ table, unsigned *__restrict__ first, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         table[i] = EMPTY_KEY;
         first[i] = 0x7fffffffu;
     }
-}
-__global__ void fill_u64_kernel(unsigned long long *p, unsigned long long v, long long n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        p[i] = v;
 }
 
 inline int grid1d(long long total, int per_block = 256, int cap = 256 * 32) {
@@ -2819,20 +2674,12 @@ void splat_ones(wsc_ctx *ctx, const LatticeDev &L, const TileGeom &tg, float *va
 // rows of a lattice from the slot partials of the splat
 void combine4(wsc_ctx *ctx, hipStream_t st, const LatticeDev &L, const float *part, int LP, float *val) {
     WscKernelTimer timer(ctx, WSC_K_BLUR, ((double)L.n_slots + L.rows) * L.rep * L.M_cur * 4);
-#ifdef WSC_AB_KNOBS
-    const char *be = getenv("WSC_CRF_COMBINE_BALANCED"); // A/B: 0 keeps the lane-group-per-row kernel
-#else
-    const char *be = nullptr;
-#endif
     if (L.sorted_dest)
-        hipLaunchKernelGGL(combine4_kernel<true>, dim3(grid_rep((long long)L.rows * L.rep, 256 / LP, L.rep)), dim3(256), 0,
+        hipLaunchKernelGGL(combine4_kernel, dim3(grid_rep((long long)L.rows * L.rep, 256 / LP, L.rep)), dim3(256), 0,
                            st, (const f32x4_t *)part, L.row_slot_start, LP, L.rows, L.n_slots, L.rep, (f32x4_t *)val);
-    else if (L.rep == 1 && !(be && atoi(be) == 0))
+    else // (the bilateral lattice: per image, rep == 1)
         hipLaunchKernelGGL(combine4_balanced_kernel, dim3((unsigned)((L.rows + CB_ROWS - 1) / CB_ROWS)), dim3(256), 0, st,
                            (const f32x4_t *)part, L.row_slot_start, (const uint32_t *)L.part_row, LP, L.rows, (f32x4_t *)val);
-    else
-        hipLaunchKernelGGL(combine4_kernel<false>, dim3(grid_rep((long long)L.rows * L.rep, 256 / LP, L.rep)), dim3(256), 0,
-                           st, (const f32x4_t *)part, L.row_slot_start, LP, L.rows, L.n_slots, L.rep, (f32x4_t *)val);
 }
 
 // d+1 blur passes of the one-value-per-row normalisation lattice, ping-pong between a and b
@@ -2847,7 +2694,7 @@ float *blur_all1(wsc_ctx *ctx, const LatticeDev &L, float *a, float *b) {
 
 // blur_lds_kernel on the rows in `val` when the lattice is per image and every image's vertex count admits a variant
 // (BL_VAR: GW classes of its rows in a workgroup's LDS, RPT rows per thread); returns false when the per-pass launches have
-// to run.  WSC_CRF_BLUR_LDS=0 (read per call: a test compares the two paths) switches it off.
+// to run.  WSC_OPT_CRF_BLUR_ON_CHIP = 0 (a ctx option: a test compares the two paths) switches it off.
 // The workgroup table of blur_lds_kernel for a class count, written on the ctx's MAIN stream at the start of an inference
 // call (through the ctx's page-locked staging buffer: the host vector may be rebuilt by the next call at once), so that
 // whichever stream runs the blur later in the call is ordered behind it.
@@ -2883,14 +2730,7 @@ bool blur_lds(wsc_ctx *ctx, hipStream_t st, const LatticeDev &L, int LP, float *
     const int M = L.M_cur;
     if (!ctx->opt[WSC_OPT_CRF_BLUR_ON_CHIP] || L.rep != 1 || !L.img_row || !L.bl_ok || L.bl_M != M) return false;
     if (L.bl_nblk == 0) return true;
-    static bool attr_set[64] = {};
-    const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-    if (!attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(blur_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return false;
-        attr_set[dev] = true;
-    }
+    if (wsc_set_max_dynamic_lds(ctx, reinterpret_cast<const void *>(blur_lds_kernel), 160 * 1024) != WSC_OK) return false;
     BlurLdsArgs ba;
     ba.nbr = L.nbr; ba.img_row = L.img_row; ba.blk = L.bl_blk; ba.val = val; ba.Mp = 4 * LP; ba.M = M; ba.rows = L.rows;
     ba.npass = L.d + 1;
@@ -2910,22 +2750,7 @@ float *combine_blur_all4(wsc_ctx *ctx, hipStream_t st, const LatticeDev &L, int 
         // one read of the partials + one write of the value rows (the halo re-reads come out of L2).  Whole rows
         // per group (6 float4 = 49 KB of LDS, 3 blocks per CU) beat 3 / 2 / 1 float4 per group at 6+ blocks per CU
         WscKernelTimer timer(ctx, WSC_K_BLUR, ((double)L.n_slots + L.rows) * L.rep * L.M_cur * 4);
-#ifdef WSC_AB_KNOBS
-        const char *ge = getenv("WSC_CRF_GLH");
-        const int glh = ge ? atoi(ge) : WSC_GLH;
-#else
-        constexpr int glh = WSC_GLH;
-#endif
-        if (glh == 3)
-            hipLaunchKernelGGL(blur3_tile_kernel<3>, dim3((unsigned)(L.n_tiles_occ * L.rep)), dim3(GBI * GBJ), 0, st,
-                               (const f32x4_t *)nullptr, L.tile_rows, L.tile_list, L.n_tiles_occ, LP, L.rows, L.rep, (f32x4_t *)b,
-                               (const f32x4_t *)part, L.tile_pstart, L.n_slots);
-        else if (glh == 2)
-            hipLaunchKernelGGL(blur3_tile_kernel<2>, dim3((unsigned)(L.n_tiles_occ * L.rep)), dim3(GBI * GBJ), 0, st,
-                               (const f32x4_t *)nullptr, L.tile_rows, L.tile_list, L.n_tiles_occ, LP, L.rows, L.rep, (f32x4_t *)b,
-                               (const f32x4_t *)part, L.tile_pstart, L.n_slots);
-        else
-        hipLaunchKernelGGL(blur3_tile_kernel<WSC_GLH>, dim3((unsigned)(L.n_tiles_occ * L.rep)), dim3(GBI * GBJ), 0, st,
+        hipLaunchKernelGGL(blur3_tile_kernel, dim3((unsigned)(L.n_tiles_occ * L.rep)), dim3(GBI * GBJ), 0, st,
                            (const f32x4_t *)nullptr, L.tile_rows, L.tile_list, L.n_tiles_occ, LP, L.rows, L.rep, (f32x4_t *)b,
                            (const f32x4_t *)part, L.tile_pstart, L.n_slots);
         return b;
@@ -3327,16 +3152,6 @@ void gauss_cache_delete(void *p) { delete static_cast<GaussCache *>(p); }
 
 // slice: messages of both lattices are read (false before the first iteration); splat: the result is splatted
 // (false in the last iteration, whose Q is written to a.q instead)
-// block size of the update kernel (WSC_CRF_UPD_THREADS: A/B runs)
-int update_threads() {
-#ifdef WSC_AB_KNOBS
-    const char *te = getenv("WSC_CRF_UPD_THREADS");
-    const int nthr = te ? atoi(te) : 256;
-    return nthr == 512 ? 512 : 256; // (the kernel's per-thread table registers cover a tile with >= 256 threads)
-#else
-    return 256;
-#endif
-}
 size_t update_splat_lds(int LP) { return sizeof(f32x4_t) * TILE_PIX * LP + sizeof(uint2) * GATHER_ENT + sizeof(int2) * GATHER_SB; }
 size_t gauss_msg_lds(int LP, int gt_stride) { return ((size_t)LP * sizeof(f32x4_t) + sizeof(uint4)) * (size_t)gt_stride; }
 // can the Gaussian message be formed on chip (gauss_msg_kernel) for this call?  The tile vertex sets must exist (sets within
@@ -3351,11 +3166,7 @@ bool update_gf_ok(const wsc_ctx *ctx, const LatticeDev &G, int LP) {
 int launch_gauss_msg(wsc_ctx *ctx, hipStream_t st, const GaussMsgArgs &g, double bytes) {
     WscKernelTimer timer(ctx, WSC_K_GAUSS_MSG, bytes);
     const dim3 grid((unsigned)(g.B * g.tg.tpi)), block(GM_THREADS);
-    size_t lds = gauss_msg_lds(g.LP, g.gt_stride);
-#ifdef WSC_AB_KNOBS
-    const char *le = getenv("WSC_CRF_GM_LDS"); // A/B: pad the LDS request (bytes) to cap the blocks per CU
-    if (le && (size_t)atoi(le) > lds && atoi(le) <= 64 * 1024) lds = (size_t)atoi(le);
-#endif
+    const size_t lds = gauss_msg_lds(g.LP, g.gt_stride);
     if ((long long)g.gt_stride * g.LP <= 4ll * GM_THREADS && g.LP <= 6)
         hipLaunchKernelGGL((gauss_msg_kernel<4, 3>), grid, block, lds, st, g);
     else
@@ -3372,6 +3183,17 @@ bool update_fg_ok(const wsc_ctx *ctx, const LatticeDev &G, int LP) {
     if (!ctx->opt[WSC_OPT_CRF_MSG_IN_UPDATE] || !update_gf_ok(ctx, G, LP)) return false;
     return update_fg_lds(LP, G.gt_stride) <= 80 * 1024;
 }
+// The FG variants take more than 48 KB of LDS per block at most sizes: their dynamic-LDS limit is raised before a call picks
+// the form.  An error leaves the two-launch form (gauss_msg_kernel + update), which gives the same bits.
+int update_fg_lds_limit(wsc_ctx *ctx, int LP, int gt_stride) {
+    if (update_fg_lds(LP, gt_stride) <= 48 * 1024) return WSC_OK;
+    for (const void *fn : {reinterpret_cast<const void *>(update_splat_kernel<true, true, true, 4>),
+                           reinterpret_cast<const void *>(update_splat_kernel<true, false, true, 4>),
+                           reinterpret_cast<const void *>(update_splat_kernel<true, true, true, 6>),
+                           reinterpret_cast<const void *>(update_splat_kernel<true, false, true, 6>)})
+        WSC_TRY(wsc_set_max_dynamic_lds(ctx, fn, 96 * 1024));
+    return WSC_OK;
+}
 // fg: the Gaussian message is formed inside the kernel (a.u = U, a.part_g_in = the previous splat's Gaussian partials)
 int launch_update(wsc_ctx *ctx, const UpdateArgs &a, bool slice, bool splat, bool gf, bool fg = false, double fg_bytes = 0.0) {
     const double npix = (double)a.B * a.tg.H * a.tg.W;
@@ -3382,57 +3204,28 @@ int launch_update(wsc_ctx *ctx, const UpdateArgs &a, bool slice, bool splat, boo
     const double by = npix * (2.0 * a.M * 4 + (slice ? (gf ? 6 * 8 + 1.0 * a.M * 4 : 9 * 8 + 2.0 * a.M * 4) : 0.0) +
                               (splat ? 9 * 8 + 2.0 * a.M * 4 : 0.0));
     WscKernelTimer timer(ctx, WSC_K_SLICE_UPDATE, by + (fg ? fg_bytes : 0.0));
-    const dim3 grid((unsigned)(a.B * a.tg.tpi)), block(update_threads());
+    const dim3 grid((unsigned)(a.B * a.tg.tpi)), block(256);
     size_t lds = splat ? update_splat_lds(a.LP) : 0;
     if (fg) {
         const size_t l = update_fg_lds(a.LP, a.gt_stride);
         const bool small = (long long)a.gt_stride * a.LP <= 4ll * GM_THREADS && a.LP <= 6;
-        auto set_lds = [&](const void *fn) {
-            static bool done[64][4] = {};
-            const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0, vi = (small ? 0 : 2) + (splat ? 0 : 1);
-            if (!done[dev][vi] && l > 48 * 1024) {
-                (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-                done[dev][vi] = true;
-            }
-        };
         if (small) {
-            if (splat) {
-                set_lds(reinterpret_cast<const void *>(update_splat_kernel<true, true, true, true, 4>));
-                hipLaunchKernelGGL((update_splat_kernel<true, true, true, true, 4>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-            } else {
-                set_lds(reinterpret_cast<const void *>(update_splat_kernel<true, false, true, true, 4>));
-                hipLaunchKernelGGL((update_splat_kernel<true, false, true, true, 4>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-            }
+            if (splat) hipLaunchKernelGGL((update_splat_kernel<true, true, true, 4>), grid, dim3(GM_THREADS), l, ctx->stream, a);
+            else hipLaunchKernelGGL((update_splat_kernel<true, false, true, 4>), grid, dim3(GM_THREADS), l, ctx->stream, a);
         } else {
-            if (splat) {
-                set_lds(reinterpret_cast<const void *>(update_splat_kernel<true, true, true, true, 6>));
-                hipLaunchKernelGGL((update_splat_kernel<true, true, true, true, 6>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-            } else {
-                set_lds(reinterpret_cast<const void *>(update_splat_kernel<true, false, true, true, 6>));
-                hipLaunchKernelGGL((update_splat_kernel<true, false, true, true, 6>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-            }
+            if (splat) hipLaunchKernelGGL((update_splat_kernel<true, true, true, 6>), grid, dim3(GM_THREADS), l, ctx->stream, a);
+            else hipLaunchKernelGGL((update_splat_kernel<true, false, true, 6>), grid, dim3(GM_THREADS), l, ctx->stream, a);
         }
         WSC_HIP(hipGetLastError());
         return WSC_OK;
     }
-#ifdef WSC_AB_KNOBS
-    const char *de = getenv("WSC_CRF_UPD_DMA"); // A/B: 0 keeps the register loads of E and the records
-#else
-    const char *de = nullptr;
-#endif
-    const bool dma = slice && gf && !(de && atoi(de) == 0);
-    if (dma) lds = update_splat_lds(a.LP); // the last update stages E + records too
-    if (dma) {
-        if (splat) hipLaunchKernelGGL((update_splat_kernel<true, true, true, true>), grid, block, lds, ctx->stream, a);
-        else hipLaunchKernelGGL((update_splat_kernel<true, false, true, true>), grid, block, lds, ctx->stream, a);
-    } else if (slice && gf) {
+    if (slice && gf) {
+        lds = update_splat_lds(a.LP); // the last update stages E + records too
         if (splat) hipLaunchKernelGGL((update_splat_kernel<true, true, true>), grid, block, lds, ctx->stream, a);
         else hipLaunchKernelGGL((update_splat_kernel<true, false, true>), grid, block, lds, ctx->stream, a);
     } else if (slice && splat) hipLaunchKernelGGL((update_splat_kernel<true, true>), grid, block, lds, ctx->stream, a);
     else if (slice) hipLaunchKernelGGL((update_splat_kernel<true, false>), grid, block, lds, ctx->stream, a);
-    else if (splat && !(de && atoi(de) == 0)) // the first update: U rows staged by LDS-DMA like the E rows of the later ones
-        hipLaunchKernelGGL((update_splat_kernel<false, true, false, true>), grid, block, lds, ctx->stream, a);
-    else if (splat) hipLaunchKernelGGL((update_splat_kernel<false, true>), grid, block, lds, ctx->stream, a);
+    else if (splat) hipLaunchKernelGGL((update_splat_kernel<false, true>), grid, block, lds, ctx->stream, a); // U rows by LDS-DMA
     else hipLaunchKernelGGL((update_splat_kernel<false, false>), grid, block, lds, ctx->stream, a);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
@@ -3559,7 +3352,7 @@ int wsc_crf_create(wsc_ctx *ctx, const uint8_t *rgb_dev, int B, int H, int W, fl
     }
     // The 80-byte record (both lattices) serves the updates that gather the Gaussian rows themselves.  When the Gaussian
     // message can be formed on chip for every class count (the tile vertex sets fit at LP = 8), it is not built here: a
-    // call that still wants it (WSC_CRF_NO_GFUSE=1) builds it on first use (crf_full_records).
+    // call that still wants it (WSC_OPT_CRF_GAUSS_ON_CHIP = 0) builds it on first use (crf_full_records).
     if (st == WSC_OK && !(crf->lat[0].gt_rows && update_gf_ok(ctx, crf->lat[0], 8))) st = crf_full_records(crf, ctx->stream);
     if (st == WSC_OK && crf->lat[0].gt_rows) st = crf_bilateral_records(crf, ctx->stream);
     if (st != WSC_OK) {
@@ -3656,14 +3449,9 @@ static int crf_inference_impl(wsc_ctx *ctx, wsc_crf *crf, const float *unary_dev
     }
     // The side stream pays off only for the per-pass bilateral launches (seven short kernels beside the Gaussian message);
     // with the on-chip blur (two launches whose workgroups fill the CUs' LDS) one stream and two are the same to +-0.5 %
-    // (profiles/README.md), so that path stays on one stream.  WSC_CRF_NO_FORK=1 / 0 forces either.
-#ifdef WSC_AB_KNOBS
-    const char *nf = getenv("WSC_CRF_NO_FORK");
-#else
-    const char *nf = nullptr;
-#endif
+    // (profiles/README.md), so that path stays on one stream.
     const bool lds_blur = Bl.bl_ok && Bl.img_row && ctx->opt[WSC_OPT_CRF_BLUR_ON_CHIP];
-    const bool no_fork = (nf ? atoi(nf) != 0 : lds_blur) || ctx->profiling; // per-kernel timing wants the launches one after the other
+    const bool no_fork = lds_blur || ctx->profiling; // per-kernel timing wants the launches one after the other
     if (!no_fork && !ctx->aux_stream) {
         // (default priority: a high-priority side stream, or any other priority split between the stages of a pipelined
         // caller, was measured and lost 3-20 %: profiles/README.md)
@@ -3686,26 +3474,9 @@ static int crf_inference_impl(wsc_ctx *ctx, wsc_crf *crf, const float *unary_dev
     // gauss_msg_kernel turns the Gaussian slot partials into E = -U + message (in the Q buffer: an update reads its slot of
     // E before it writes Q there) beside the bilateral lattice's combine + six passes, and the update starts from E
     const bool gf = update_gf_ok(ctx, G, LP);
-    const bool fg = gf && update_fg_ok(ctx, G, LP);
+    const bool fg = gf && update_fg_ok(ctx, G, LP) && update_fg_lds_limit(ctx, LP, G.gt_stride) == WSC_OK;
     a.gt_cnt = G.gt_cnt; a.gt_rows = G.gt_rows; a.gt_nbr = G.gt_nbr; a.gt_pix = G.gt_pix; a.gt_stride = G.gt_stride;
     a.part_g_in = nullptr;
-    a.tl = nullptr;
-#ifdef WSC_AB_KNOBS
-    if (const char *te = getenv("WSC_CRF_UPD_TIMELINE")) { // A/B: file the stamps of the LAST splatting update of this call go to
-        static unsigned long long *tl_dev = nullptr;
-        static size_t tl_cap = 0;
-        const size_t need = (size_t)B * a.tg.tpi * 8;
-        if (need > tl_cap) {
-            if (tl_dev) (void)hipFree(tl_dev);
-            WSC_HIP(hipMalloc((void **)&tl_dev, need * sizeof(unsigned long long)));
-            tl_cap = need;
-        }
-        WSC_HIP(hipMemsetAsync(tl_dev, 0, need * sizeof(unsigned long long), ctx->stream));
-        a.tl = tl_dev;
-        (void)te;
-    }
-    unsigned long long *const tl_keep = a.tl;
-#endif
     if (gf && n_iters > 0) { // (built by wsc_crf_create whenever the lattice has its tile vertex sets; here for completeness)
         WSC_TRY(crf_bilateral_records(crf, ctx->stream));
         a.pix_rec_b = crf->pix_rec_b;
@@ -3733,10 +3504,6 @@ static int crf_inference_impl(wsc_ctx *ctx, wsc_crf *crf, const float *unary_dev
         a.q = last && !labels_only ? q : nullptr;
         a.argmax = labels_only ? argmax_dev : nullptr;
         a.u = (gf && !fg && it > 0) ? q : u;
-#ifdef WSC_AB_KNOBS
-        if (last || it == 0) a.tl = nullptr; // (the stamps are those of the last SPLATTING update with messages)
-        else a.tl = tl_keep;
-#endif
         if (fg) { // iteration `it` reads the Gaussian partials of splat it - 1 and writes those of splat `it`
             a.part_g_in = (it & 1) ? partg : partg2;
             a.sg.part = (it & 1) ? partg2 : partg;
@@ -3765,18 +3532,6 @@ static int crf_inference_impl(wsc_ctx *ctx, wsc_crf *crf, const float *unary_dev
                                N, q_dev, argmax_dev);
     }
     WSC_HIP(hipGetLastError());
-#ifdef WSC_AB_KNOBS
-    if (tl_keep != nullptr) {
-        const size_t need = (size_t)B * a.tg.tpi * 8;
-        std::vector<unsigned long long> h(need);
-        WSC_HIP(hipMemcpyAsync(h.data(), tl_keep, need * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        WSC_HIP(hipStreamSynchronize(ctx->stream));
-        if (FILE *f = fopen(getenv("WSC_CRF_UPD_TIMELINE"), "wb")) {
-            fwrite(h.data(), sizeof(unsigned long long), need, f);
-            fclose(f);
-        }
-    }
-#endif
     if (ctx != crf->ctx) { // destroy must not hand the lattices back to the build ctx's cache before this loop is done
         if (!crf->use_ev) WSC_HIP(hipEventCreateWithFlags(&crf->use_ev, hipEventDisableTiming));
         WSC_HIP(hipEventRecord(crf->use_ev, ctx->stream));

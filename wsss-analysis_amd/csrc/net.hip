@@ -256,10 +256,6 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
     add_pool_op(net, 3, 2, 1, 0, 1);
     net->taps.push_back((int)net->ops.size() - 1); // stage1 = conv1, bn1, relu, maxpool (resnet50_irn.py:15)
     int cur = 1;
-    bool fuse_shortcut = true;
-#ifdef WSC_AB_KNOBS
-    if (const char *e = getenv("WSC_NET_SHORTCUT_FUSED")) fuse_shortcut = atoi(e) != 0; // A/B: the four-launch form of a stage's first block
-#endif
     const int planes[4] = {64, 128, 256, 512};
     const int blocks[4] = {3, 4, 6, 3};
     const int strides[4] = {1, 2, 2, 1}; // resnet50_cam.py:15 strides=(2,2,2,1): [0] is the stem
@@ -274,7 +270,7 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
             // Bottleneck.forward, resnet50.py:34-54; the stride sits on conv2 (resnet50.py:24)
             WSC_TRY(resnet_conv(net, d, pre + ".conv1", pre + ".bn1", 1, 0, 1, 0, cur, f[0], -1));
             bool fuse_here = false;
-            if (has(d, pre + ".downsample.0.weight") && has(d, pre + ".conv3.weight") && fuse_shortcut) {
+            if (has(d, pre + ".downsample.0.weight") && has(d, pre + ".conv3.weight")) {
                 // (only for the shapes the concatenated GEMM takes: 1x1 kernels, K1 + K2 a multiple of the 64-channel K chunk;
                 // anything else keeps the separate projection conv + residual)
                 const HostTensor *w3, *wd;

@@ -129,17 +129,14 @@ __global__ __launch_bounds__(RW_T * RW_T) void rw_step_tile_kernel(const RwImg *
                                                                     const double *__restrict__ inv_col_all,
                                                                     const int32_t *__restrict__ dirs, int D,
                                                                     double *__restrict__ out_all, float *__restrict__ out_f32_all,
-                                                                    int max_tiles, int xcd_map) {
+                                                                    int max_tiles) {
     __shared__ double vt[RW_KC][RW_W * RW_W];
     // 1-D grid of n_img * max_tiles blocks.  Blocks go round-robin over the 8 XCDs (block b -> XCD b % 8): with the plain order
     // every XCD's 4 MB L2 sees tiles of every image, i.e. all 34 weight maps of the whole batch (51 MB at 32 VOC images) plus
     // the halo overlap.  The bijective remap gives an XCD a contiguous range of logical ids = whole images (4 of 32), whose
     // weights and state it then re-reads from its own L2 for all 2^8 steps.
-    int lb = (int)blockIdx.x;
-    if (xcd_map) {
-        const int nb = (int)gridDim.x, xcd = lb & 7, q = nb >> 3, r = nb & 7;
-        lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lb >> 3);
-    }
+    const int nb = (int)gridDim.x, bid = (int)blockIdx.x, xcd = bid & 7, q = nb >> 3, r = nb & 7;
+    const int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     const int img = lb / max_tiles, tile = lb - img * max_tiles;
     const RwImg im = imgs[img];
     const int h = im.h, w = im.w, hw = im.hw;
@@ -285,7 +282,7 @@ extern "C" int wsc_rw_propagate_batch(wsc_ctx *ctx, int n_img, const int32_t *K_
     hipLaunchKernelGGL(rw_mask_kernel, g_khw, dim3(256), 0, ctx->stream, imgs_dev, x_dev, edge_dev, va,
                        n_steps == 0 ? rw_dev : (float *)nullptr);
     double *cur = va, *nxt = vbuf;
-    // tiled step (values through LDS) when every direction stays inside its halo; WSC_RW_TILED=0 keeps the flat kernel
+    // tiled step (values through LDS) when every direction stays inside its halo; WSC_OPT_RW_TILED = 0 keeps the flat kernel
     bool tiled = ctx->opt[WSC_OPT_RW_TILED] != 0;
     for (int d = 0; d < D; ++d) tiled = tiled && dirs_host[2 * d] <= RW_R && std::abs(dirs_host[2 * d + 1]) <= RW_R;
     int max_tiles = 1, max_K = 1;
@@ -301,21 +298,16 @@ extern "C" int wsc_rw_propagate_batch(wsc_ctx *ctx, int n_img, const int32_t *K_
     // 2^8 steps: 1 image (48 tiles) 3.95 / 4.95, 2: 2.03 / 2.46, 4: 1.53 / 1.22, 8: 0.91 / 0.62, 16: 0.50 / 0.35, 24: 0.61 / 0.34,
     // 32: - / 0.27 (0.31 before the block order) -- smaller calls keep the flat kernel
     if (ctx->opt[WSC_OPT_RW_TILED] < 0) tiled = tiled && all_tiles * 8 >= 5ll * ctx->num_cus;
-#ifdef WSC_AB_KNOBS
-    static const int xcd_map = [] { const char *e = getenv("WSC_RW_XCD"); return e ? atoi(e) : 1; }();
-#else
-    constexpr int xcd_map = 1;
-#endif
     for (int s = 0; s < n_steps; ++s) {
         if (tiled) {
             const dim3 tg((unsigned)max_tiles * (unsigned)n_img);
             float *of = s == n_steps - 1 ? rw_dev : (float *)nullptr;
             if (max_K <= 2)
-                hipLaunchKernelGGL(rw_step_tile_kernel<2>, tg, dim3(RW_T * RW_T), 0, ctx->stream, imgs_dev, cur, S, inv_col, dirs, D, nxt, of, max_tiles, xcd_map);
+                hipLaunchKernelGGL(rw_step_tile_kernel<2>, tg, dim3(RW_T * RW_T), 0, ctx->stream, imgs_dev, cur, S, inv_col, dirs, D, nxt, of, max_tiles);
             else if (max_K <= 4)
-                hipLaunchKernelGGL(rw_step_tile_kernel<4>, tg, dim3(RW_T * RW_T), 0, ctx->stream, imgs_dev, cur, S, inv_col, dirs, D, nxt, of, max_tiles, xcd_map);
+                hipLaunchKernelGGL(rw_step_tile_kernel<4>, tg, dim3(RW_T * RW_T), 0, ctx->stream, imgs_dev, cur, S, inv_col, dirs, D, nxt, of, max_tiles);
             else
-                hipLaunchKernelGGL(rw_step_tile_kernel<8>, tg, dim3(RW_T * RW_T), 0, ctx->stream, imgs_dev, cur, S, inv_col, dirs, D, nxt, of, max_tiles, xcd_map);
+                hipLaunchKernelGGL(rw_step_tile_kernel<8>, tg, dim3(RW_T * RW_T), 0, ctx->stream, imgs_dev, cur, S, inv_col, dirs, D, nxt, of, max_tiles);
         }
         else
         hipLaunchKernelGGL(rw_step_kernel, g_khw, dim3(256), 0, ctx->stream, imgs_dev, cur, S, inv_col, dirs, D, nxt,

@@ -47,14 +47,8 @@ struct StemPoolArgs {
     const float *s1, *b1;
     bf16_t *y, *y_lo;       // [N][Hq][Wq][64]
     int Hp, Wp, Kw, Ho, Wo, Hq, Wq, nti, ntj, relu;
-    int debug; // A/B builds only (-DWSC_AB_KNOBS): phases switched off for the ablations of profiles/README.md
     unsigned *range; // the ctx's range flag (common.h): raised when a pooled value sits at the half ceiling
 };
-#ifdef WSC_AB_KNOBS
-#define WSC_SDBG(p, bit) ((p).debug & (bit))
-#else
-#define WSC_SDBG(p, bit) false
-#endif
 
 __device__ __forceinline__ int b_off(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
 
@@ -78,7 +72,6 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolArgs p) {
         const int row = o / PITCH, c16 = (o - row * PITCH) >> 4;
         const bool ok = row < PROWS && c16 < (PPIX * 8) / 16;
         const bf16_t *g = (plane ? p.x_lo : p.x) + porg + (ok ? ((long long)row * p.Wp * 4 + c16 * 8) : 0ll);
-        if (!WSC_SDBG(p, 1))
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
                                          (__attribute__((address_space(3))) void *)(smem + plane * PLANE + pq * 1024), 16, 0, 0);
     }
@@ -91,7 +84,6 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolArgs p) {
         wsrc[i] = p.w + (long long)row * p.Kw + ks * 8;
     }
     auto issue_b = [&](int r, int buf) {
-        if (WSC_SDBG(p, 2)) return;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc[i] + r * 64),
@@ -132,7 +124,6 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolArgs p) {
     }
 
     auto mfma = [&](const u32x4_t &a, const u32x4_t &b, f32x16_t &c) {
-        if (WSC_SDBG(p, 4)) return;
         c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
     };
 
@@ -141,7 +132,6 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolArgs p) {
     u32x4_t fa[2][2][2], fb[2][2][2]; // [set][hi / lo][mi | ni]
     auto rd = [&](auto set_c, auto r_c, auto s_c) __attribute__((always_inline)) {
         constexpr int set = decltype(set_c)::value, r = decltype(r_c)::value, sl = decltype(s_c)::value, buf = r % NSTB;
-        if (WSC_SDBG(p, 8)) return;
         // inline asm: compiler-visible reads would be fenced by an s_waitcnt vmcnt(0) against the DMA in flight (conv_igemm.hip)
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -207,7 +197,6 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolArgs p) {
     // monotone (a value just below the midpoint of two halves rounds to at most the midpoint, one just above to at least it), so
     // max(round(v_i)) = round(max(v_i)) -- the bits of maxpool_f16x2_kernel over the conv's rounded planes, at 1/5 of the roundings.
     float *ct = reinterpret_cast<float *>(smem);
-    if (WSC_SDBG(p, 16)) return;
     const int c0 = 2 * PQ * ti - 1, u0 = 2 * PQ * tj - 1; // conv coordinates of tile position (0, 0)
     const float sat_lo = p.relu ? 0.f : -65504.f;
     // Tile positions outside the conv output (row / column -1 of the first tiles, the far side of the last ones) hold finite
@@ -280,10 +269,8 @@ __global__ __launch_bounds__(256, 3) void stem_pool_kernel(StemPoolArgs p) {
                 if ((half2_at_ceiling(hw[0]) | half2_at_ceiling(hw[1]) | half2_at_ceiling(hw[2]) | half2_at_ceiling(hw[3])) & 0x80008000u)
                     *p.range = 64u;
                 const long long oo = (((long long)n * p.Hq + qi) * p.Wq + qj) * 64 + c8 * 8;
-                if (!WSC_SDBG(p, 32)) {
-                    *reinterpret_cast<uint4 *>(p.y + oo) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-                    *reinterpret_cast<uint4 *>(p.y_lo + oo) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
-                }
+                *reinterpret_cast<uint4 *>(p.y + oo) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+                *reinterpret_cast<uint4 *>(p.y_lo + oo) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
             }
         }
     }
@@ -309,24 +296,15 @@ int launch_stem_pool(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, i
     StemPoolArgs a;
     a.x = x; a.x_lo = x_lo; a.w = w; a.s1 = s1; a.b1 = b1; a.y = y; a.y_lo = y_lo;
     stem_pool_input_dims(H, W, &a.Hp, &a.Wp);
-    a.Kw = Kw; a.relu = relu; a.debug = 0;
+    a.Kw = Kw; a.relu = relu;
     a.range = ctx->range_dev;
-#ifdef WSC_AB_KNOBS
-    static const int dbg = [] { const char *e = getenv("WSC_STEM_DEBUG"); return e ? atoi(e) : 0; }();
-    a.debug = dbg;
-#endif
     a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1;
     a.Hq = (a.Ho + 2 - 3) / 2 + 1; a.Wq = (a.Wo + 2 - 3) / 2 + 1;
     a.nti = (a.Hq + PQ - 1) / PQ; a.ntj = (a.Wq + PQ - 1) / PQ;
     WSC_CHECK(x_lo != nullptr && y_lo != nullptr && Kw == 7 * 64, WSC_ERR_INVALID, "stem_pool: f16x3 planes and the 7-row packing only");
     const long long nblk = (long long)N * a.nti * a.ntj;
     WSC_CHECK(nblk < (1ll << 31), WSC_ERR_SHAPE, "stem_pool: too many tiles");
-    static bool attr_set[64] = {};
-    const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-    if (!attr_set[dev]) {
-        WSC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(stem_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_set[dev] = true;
-    }
+    WSC_TRY(wsc_set_max_dynamic_lds(ctx, reinterpret_cast<const void *>(stem_pool_kernel), LDS_BYTES));
     // algorithmic FLOPs of the conv (the pool adds none): 2 * M * Cout * kh * kw * Cin_real
     WscKernelTimer timer(ctx, WSC_K_CONV_SMALLCIN, 2.0 * N * a.Ho * a.Wo * 64 * 7 * 7 * 3);
     hipLaunchKernelGGL(stem_pool_kernel, dim3((unsigned)nblk), dim3(256), LDS_BYTES, ctx->stream, a);
