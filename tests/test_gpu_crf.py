@@ -405,6 +405,43 @@ def test_crf_gaussian_cache_evicts_least_recently_used():
     assert np.array_equal(q2, last[2]) and np.array_equal(a2, last[3])
 
 
+@pytest.mark.parametrize("gauss_on_chip", [1, 0])
+def test_crf_loop_on_another_context(gauss_on_chip):
+    """Lattices built on context A, mean-field loop on context B (bench.py's ctx_build / ctx_crf split): B waits for A and runs
+    the loop twice, the Crf is closed while those loops may still be queued -- A's stream must wait for them before its cache
+    hands the blocks on -- and a Crf of OTHER images built on A right after takes the blocks.  Q and labels of every run are
+    bit-identical to the same work done on A alone.  gauss_on_chip = 0 on B: the loop builds the 80-byte pixel records on B's
+    stream from a block of A's cache (the lattice build skipped them: its Gaussian message is formed on chip)."""
+    rng = np.random.default_rng(2024)
+    H, W, M, B = 45, 61, 6, 2
+    cfg = (1.5, 3, 40, 13, 10, 5)
+    first = [helpers.synth_crf_case(rng, H, W, M) for _ in range(B)]
+    second = [helpers.synth_crf_case(rng, H, W, M) for _ in range(B)]
+    ctx_a, ctx_b = _lib.Context(0), _lib.Context(0)
+    ctx_b.set_option(_lib.OPT_CRF_GAUSS_ON_CHIP, gauss_on_chip)
+    ref1 = _gpu_crf(ctx_a, [c[0] for c in first], [c[1] for c in first], cfg)    # first use of the size on A
+    ref2 = _gpu_crf(ctx_a, [c[0] for c in second], [c[1] for c in second], cfg)  # second use: tile vertex sets
+    rgb1, u1 = ctx_a.to_device(np.stack([c[0] for c in first])), ctx_a.to_device(np.stack([c[1] for c in first]))
+    rgb2, u2 = ctx_a.to_device(np.stack([c[0] for c in second])), ctx_a.to_device(np.stack([c[1] for c in second]))
+    outs_b = [(ctx_b.alloc(B * M * H * W * 4), ctx_b.alloc(B * H * W * 4)) for _ in range(2)]
+    q2_dev, a2_dev = ctx_a.alloc(B * M * H * W * 4), ctx_a.alloc(B * H * W * 4)
+    crf = _lib.Crf(ctx_a, rgb1, B, H, W, cfg[0], cfg[2], cfg[3])
+    ctx_b.wait_for(ctx_a)
+    for q_dev, a_dev in outs_b:
+        crf.inference(u1, M, cfg[1], cfg[4], cfg[5], q_dev, a_dev, ctx=ctx_b)
+    crf.close()
+    crf2 = _lib.Crf(ctx_a, rgb2, B, H, W, cfg[0], cfg[2], cfg[3])
+    crf2.inference(u2, M, cfg[1], cfg[4], cfg[5], q2_dev, a2_dev)
+    q2, a2 = ctx_a.to_host(q2_dev, (B, M, H * W), np.float32), ctx_a.to_host(a2_dev, (B, H * W), np.int32)
+    crf2.close()
+    for i, (q_dev, a_dev) in enumerate(outs_b):
+        q, a = ctx_b.to_host(q_dev, (B, M, H * W), np.float32), ctx_b.to_host(a_dev, (B, H * W), np.int32)
+        assert np.array_equal(q, ref1[0]) and np.array_equal(a, ref1[1]), i
+    assert np.array_equal(q2, ref2[0]) and np.array_equal(a2, ref2[1])
+    ctx_b.close()
+    ctx_a.close()
+
+
 def test_crf_ragged_batch(ctx):
     """wsc_crf_v: a list of images with their own sizes AND class counts in one object (the reference's per-image loops:
     cam_to_ir_label.py:25-58, 03c_hsn/utilities.py:420-445).  Seven images of three sizes, M from 1 to 21, in mixed order,

@@ -229,7 +229,6 @@ int wsc_ctx_create(int device, void *stream, wsc_ctx **out) {
     WSC_HIP(hipHostMalloc((void **)&ctx->range_host, 64, hipHostMallocMapped));
     memset(ctx->range_host, 0, 64);
     WSC_HIP(hipHostGetDevicePointer((void **)&ctx->range_dev, ctx->range_host, 0));
-    WSC_HIP(hipEventCreateWithFlags(&ctx->pinned_ev, hipEventDisableTiming));
     WSC_HIP(hipEventCreateWithFlags(&ctx->join_ev, hipEventDisableTiming));
     WSC_HIP(hipEventCreate(&ctx->ev0));
     WSC_HIP(hipEventCreate(&ctx->ev1));
@@ -248,18 +247,16 @@ void wsc_ctx_destroy(wsc_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (auto &a : ctx->attachments) a.second(a.first);
+    wsc_gauss_cache_destroy(ctx->gauss_cache);
     if (ctx->ws) (void)hipFree(ctx->ws);
     if (ctx->zero_page) (void)hipFree(ctx->zero_page);
     if (ctx->range_host) (void)hipHostFree(ctx->range_host);
     for (auto &kv : ctx->free_blocks) (void)hipFree(kv.second);
     for (auto &kv : ctx->live_blocks) (void)hipFree(kv.first);
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     for (wsc_ctx::PinSlot &s : ctx->pin_ring) {
         if (s.p) (void)hipHostFree(s.p);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
-    if (ctx->pinned_ev) (void)hipEventDestroy(ctx->pinned_ev);
     if (ctx->join_ev) (void)hipEventDestroy(ctx->join_ev);
     for (hipEvent_t e : ctx->marks)
         if (e) (void)hipEventDestroy(e);

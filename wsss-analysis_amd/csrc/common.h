@@ -124,6 +124,8 @@ struct WscProfRecord {
 };
 
 // ---- context --------------------------------------------------------------------
+struct WscGaussCache; // crf.hip
+void wsc_gauss_cache_destroy(WscGaussCache *cache);
 struct wsc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -150,15 +152,11 @@ struct wsc_ctx {
     // per-wave quarters, a different fp32 summation order from the tiled kernel: equal to fp32 round-off (test bound 2e-6
     // relative), not bit-identical.  Defaults: wsc_option in include/wsscam.h.
     int opt[WSC_OPT_COUNT] = {1, 1, 1, 0, 0, -1, 1, 1, 1, 1};
-    void *pinned = nullptr; // (legacy single buffer: unused)
-    size_t pinned_bytes = 0;
     void *zero_page = nullptr; // 256 bytes of zeros in HBM (source of padded conv taps)
     // range guard of the IEEE-half conv modes: one word of mapped, page-locked host memory that a conv epilogue stores to
     // (plain store of a non-zero value, no atomic needed: every writer writes "raised") when an activation saturates at the
     // half ceiling; read by the host after a stream synchronisation (wsc_sync, wsc_memcpy_d2h, wsc_ctx_range_status)
     unsigned *range_host = nullptr, *range_dev = nullptr;
-    hipEvent_t pinned_ev = nullptr; // completion of the last copy out of `pinned`
-    bool pinned_busy = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t join_ev = nullptr; // wsc_ctx_wait
     hipEvent_t marks[8] = {};     // wsc_ctx_mark / wsc_ctx_wait_mark (created on first use)
@@ -175,9 +173,9 @@ struct wsc_ctx {
     // previous user) instead of going through hipFree/hipMalloc (both synchronise the device).
     std::multimap<size_t, void *> free_blocks;
     std::unordered_map<void *, size_t> live_blocks;
-    // host-side objects owned by the ctx (crf.hip keeps its per-image-size Gaussian lattices here);
-    // their device arrays are cached-alloc blocks, released with everything else at destroy
-    std::vector<std::pair<void *, void (*)(void *)>> attachments;
+    // crf.hip's per-image-size Gaussian lattices (created by the first wsc_crf_create); their device arrays are cached-alloc
+    // blocks, handed back when the cache is destroyed and freed with everything else at destroy
+    WscGaussCache *gauss_cache = nullptr;
 };
 int wsc_ctx_workspace(wsc_ctx *ctx, size_t bytes, void **out);
 // WSC_ERR_RANGE (with the error text) when the ctx's range flag is raised; the stream must have been synchronised

@@ -7,20 +7,25 @@
 // filtering, NORMALIZE_SYMMETRIC kernels, Potts compatibility (see oracle/densecrf_ref.c
 // for the CPU restatement this file is checked against).
 //
-// Data layout in HBM (whole batch of B images of H x W, N = H*W pixels each):
-//   lattice vertex rows of ALL images share one index space: row 0 is a permanent zero row
-//   (a missing blur neighbour points at it), image 0's vertices follow in first-touch
-//   raster order (the CPU reference's insertion order), then image 1's, ...
-//   offset[e], bary[e]   e = (b*N + n)*(d+1) + r : row id / barycentric weight of the r-th
-//                        enclosing simplex vertex of pixel n
-//   csr_start[row], csr_pix[], csr_w[] : per row, the pixels splatting into it (gather form
-//                        of the splat: no float atomics in the iteration loop)
-//   nbr[j][row] = (n1, n2) : blur neighbours along axis j
-//   norm[b*N+n]          : 1/sqrt(Lattice(1)+1e-20)
-//   val[row][M]          : lattice values, class-minor (M contiguous floats per row)
-//   Q[pixel][M], U[pixel][M] : pixel-major, class-minor
-// Every iteration kernel is a flat, fully coalesced pass over these arrays; all are
-// HBM-bound (SURVEY.md section 8d gives the algorithmic byte count).
+// Lattices (wsc_crf_create): a Gaussian one (d = 2: position) and a bilateral one (d = 5: position + colour).  Vertex rows of
+// a lattice share one index space: row 0 is a permanent zero row (a missing blur neighbour points at it), then the vertices
+// in first-touch raster order (the CPU reference's insertion order), image after image.  Values are [row][Mp] and Q, U
+// [pixel][Mp] (class-minor, Mp = M rounded up to 4).  The splat is a gather over 16 x 16 pixel tiles: a tile's (pixel,
+// weight) entries are grouped into slots of one row each (slot tables tslot_start / slot_desc / tent_w / tent_p), every slot
+// writes one partial row, and a row is the sum of its partial rows (row_slot_start): no float atomics, the same bits on every
+// run.  Per pixel, the update kernel reads an 80-byte record (pix_rec: vertex ids, barycentric weights and norm of both
+// lattices) or, when it starts from a Gaussian message formed elsewhere, the 52-byte bilateral part alone (pix_rec_b).
+// The Gaussian lattice depends on (H, W, sxy) only: one copy per ctx serves every batch of that size (GaussEntry, an LRU
+// cache of 64 sizes).  Its message takes one of three paths, chosen per call:
+//   - blur kernels (blur3_tile_kernel, or combine4 + three blur4_kernel passes) write value rows that the update gathers:
+//     the first use of a size, tile vertex sets too large for the LDS, or WSC_OPT_CRF_GAUSS_ON_CHIP = 0;
+//   - gauss_msg_kernel blurs each pixel tile's closed vertex set (gauss_fuse_tables, built at a size's second use) in LDS
+//     and writes E = -U + message, which the update starts from: when the fused form below does not fit its LDS, or with
+//     WSC_OPT_CRF_MSG_IN_UPDATE = 0;
+//   - by default, the update kernel forms that message itself, and E never reaches HBM.
+// The bilateral lattice is per image: blur_lds_kernel blurs one image's rows in a workgroup's LDS when every image's vertex
+// count admits a variant, else combine4 + one blur4_kernel launch per pass run on the ctx's side stream.  The update kernel
+// is VALU / LDS-bound, not HBM-bound (profiles/r06_pmc_crf.txt).
 //
 // This file is compiled with -ffp-contract=off: the simplex search compares rounded
 // float expressions and must not be re-associated into FMAs, or pixels near a cell
@@ -30,6 +35,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 namespace {
 
@@ -133,6 +139,47 @@ __host__ __device__ inline TileBox tile_box(const TileGeom &g, int j) {
 static_assert(TILE_W <= 26 && TILE_PIX <= 4096, "tile_div_magic range");
 __host__ __device__ inline unsigned tile_div_magic(int cw) { return (65536u + (unsigned)cw - 1u) / (unsigned)cw; }
 
+// Owner of cached blocks of a ctx (wsc_ctx_cached_alloc): hands them back, in allocation order, when released or destroyed.
+// All work of a ctx is on its stream, so a block handed back is reused behind its previous user without a sync.
+struct CtxBlocks {
+    wsc_ctx *ctx;
+    std::vector<void *> ptrs;
+    explicit CtxBlocks(wsc_ctx *c) : ctx(c) {}
+    CtxBlocks(CtxBlocks &&o) noexcept : ctx(o.ctx), ptrs(std::move(o.ptrs)) { o.ptrs.clear(); } // (no copies)
+    ~CtxBlocks() { release(); }
+    template <class T>
+    int alloc(size_t bytes, T **out) {
+        void *p = nullptr;
+        WSC_TRY(wsc_ctx_cached_alloc(ctx, bytes, &p));
+        ptrs.push_back(p);
+        *out = static_cast<T *>(p);
+        return WSC_OK;
+    }
+    void take(CtxBlocks &&o) { // o's blocks are ours from now on (handed back after the ones we hold)
+        ptrs.insert(ptrs.end(), o.ptrs.begin(), o.ptrs.end());
+        o.ptrs.clear();
+    }
+    void release() {
+        for (void *p : ptrs) wsc_ctx_cached_free(ctx, p);
+        ptrs.clear();
+    }
+};
+
+// The ctx's Gaussian lattice of one (H, W, sxy) (gauss_lattice).  A ctx keeps GAUSS_CACHE_MAX sizes (~25 MB each at 375 x 500):
+// a new size evicts the least recently used entry no live wsc_crf refers to (cam_to_ir_label walks hundreds of sizes); only
+// when every entry is in use is a lattice built for the one crf, without the tile vertex sets of the on-chip message path.
+struct GaussEntry {
+    int H, W;
+    float sxy;
+    LatticeDev L;
+    CtxBlocks blocks;           // its device arrays: handed back when the entry is evicted
+    int users = 0;              // live wsc_crf objects whose lat[0] aliases L
+    unsigned long long last_use = 0;
+    bool fuse_pending = true;   // the tile vertex sets of the on-chip message are built at the entry's second use
+};
+constexpr int GAUSS_CACHE_MAX = 64;
+std::atomic<unsigned long long> g_gauss_use_clock{0}; // (contexts of several host threads share it: only the order matters)
+
 } // namespace
 
 struct wsc_crf {
@@ -144,14 +191,18 @@ struct wsc_crf {
     // per pixel, 13 dwords (52 bytes): the bilateral part alone -- offB[6] baryB[6] normB -- for the updates that start from
     // the Gaussian message kernel's E (GF variants); built when the Gaussian lattice has its tile vertex sets
     uint32_t *pix_rec_b = nullptr;
-    std::vector<void *> allocs;
-    void *gauss_entry = nullptr;        // the ctx's GaussCache entry lat[0] aliases (its `users` count is ours to drop)
-    std::vector<void *> persist_allocs; // blocks of a cached Gaussian lattice under construction (freed if the build fails)
-    bool persist = false; // allocations made while set belong to the ctx (cached Gaussian lattice)
+    CtxBlocks blocks; // the bilateral lattice, the records, and the Gaussian lattice when the ctx's cache could not take it
+    GaussEntry *gauss = nullptr; // the cache entry lat[0] aliases (its `users` count is ours to drop)
     // set by wsc_crf_inference on a ctx other than the build ctx: the last loop's completion on that stream
     hipEvent_t use_ev = nullptr;
     bool used_elsewhere = false;
+    explicit wsc_crf(wsc_ctx *c) : ctx(c), blocks(c) {}
 };
+
+struct WscGaussCache {
+    std::vector<std::unique_ptr<GaussEntry>> entries;
+};
+void wsc_gauss_cache_destroy(WscGaussCache *cache) { delete cache; }
 
 namespace {
 
@@ -2639,31 +2690,6 @@ inline int grid_rep(long long total, int per_block, int rep) {
     return g <= rep ? rep : g / rep * rep;
 }
 
-int crf_alloc(wsc_crf *crf, size_t bytes, void **out) {
-    void *p = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(crf->ctx, bytes, &p));
-    if (!crf->persist) crf->allocs.push_back(p);
-    else crf->persist_allocs.push_back(p);
-    *out = p;
-    return WSC_OK;
-}
-
-struct TempBuf { // build-time scratch handed back to the ctx cache at the end of a lattice build
-    wsc_ctx *ctx;
-    std::vector<void *> ptrs;
-    explicit TempBuf(wsc_ctx *c) : ctx(c) {}
-    int alloc(size_t bytes, void **out) {
-        void *p = nullptr;
-        WSC_TRY(wsc_ctx_cached_alloc(ctx, bytes, &p));
-        ptrs.push_back(p);
-        *out = p;
-        return WSC_OK;
-    }
-    ~TempBuf() {
-        for (void *p : ptrs) wsc_ctx_cached_free(ctx, p); // stream-ordered reuse: no sync needed
-    }
-};
-
 // the normalisation pass: val = Lattice-splat of the all-ones vector (one value per row)
 void splat_ones(wsc_ctx *ctx, const LatticeDev &L, const TileGeom &tg, float *val, float *part) {
     hipLaunchKernelGGL(slot_ones_kernel, dim3((unsigned)L.n_tiles), dim3(256), 0, ctx->stream, L.tslot_start, L.slot_desc,
@@ -2778,9 +2804,8 @@ float *combine_blur_all4(wsc_ctx *ctx, hipStream_t st, const LatticeDev &L, int 
 // Tables: see LatticeDev::gt_*.  Sets of more than GT_MAX_LOCAL vertices (tiny sxy: every pixel its own simplex) switch
 // the fusion off for the lattice (gt_rows stays null) and the separate blur kernel runs.
 constexpr int GT_MAX_LOCAL = 1022; // local ids are packed in 10 bits; the set's zero row takes one more id
-int gauss_fuse_tables(wsc_crf *crf, LatticeDev &L, const TileGeom &tg) {
-    wsc_ctx *ctx = crf->ctx;
-    const int N = crf->N, rows = L.rows, W = crf->W;
+int gauss_fuse_tables(wsc_ctx *ctx, const TileGeom &tg, LatticeDev &L, CtxBlocks &own) {
+    const int N = tg.H * tg.W, rows = L.rows, W = tg.W;
     std::vector<int32_t> off((size_t)N * 3), rss((size_t)rows + 1);
     std::vector<float> bary((size_t)N * 3), norm((size_t)N);
     std::vector<int2> nbr((size_t)3 * rows);
@@ -2863,11 +2888,11 @@ int gauss_fuse_tables(wsc_crf *crf, LatticeDev &L, const TileGeom &tg) {
             }
         for (int R : list) loc[R] = -1;
     }
-    WSC_TRY(crf_alloc(crf, sizeof(int4) * cnt.size(), (void **)&L.gt_cnt));
+    WSC_TRY(own.alloc(sizeof(int4) * cnt.size(), &L.gt_cnt));
     WSC_HIP(hipMemcpyAsync(L.gt_cnt, cnt.data(), sizeof(int4) * cnt.size(), hipMemcpyHostToDevice, ctx->stream));
-    WSC_TRY(crf_alloc(crf, sizeof(int2) * trows.size(), (void **)&L.gt_rows));
-    WSC_TRY(crf_alloc(crf, sizeof(uint4) * tnbr.size(), (void **)&L.gt_nbr));
-    WSC_TRY(crf_alloc(crf, sizeof(uint4) * pix.size(), (void **)&L.gt_pix));
+    WSC_TRY(own.alloc(sizeof(int2) * trows.size(), &L.gt_rows));
+    WSC_TRY(own.alloc(sizeof(uint4) * tnbr.size(), &L.gt_nbr));
+    WSC_TRY(own.alloc(sizeof(uint4) * pix.size(), &L.gt_pix));
     WSC_HIP(hipMemcpyAsync(L.gt_rows, trows.data(), sizeof(int2) * trows.size(), hipMemcpyHostToDevice, ctx->stream));
     WSC_HIP(hipMemcpyAsync(L.gt_nbr, tnbr.data(), sizeof(uint4) * tnbr.size(), hipMemcpyHostToDevice, ctx->stream));
     WSC_HIP(hipMemcpyAsync(L.gt_pix, pix.data(), sizeof(uint4) * pix.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -2878,8 +2903,10 @@ int gauss_fuse_tables(wsc_crf *crf, LatticeDev &L, const TileGeom &tg) {
 
 constexpr int WSC_RETRY_FULL_TABLE = 1; // internal status of build_lattice: the right-sized hash table overflowed
 
+// The lattice of crf's images into L, its device arrays into `own`.  WSC_RETRY_FULL_TABLE: the right-sized hash table
+// overflowed, nothing of this attempt is needed any more.
 template <int D>
-int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy, float srgb, bool shared,
+int build_lattice(wsc_crf *crf, LatticeDev &L, CtxBlocks &own, const uint8_t *rgb_dev, float sxy, float srgb, bool shared,
                   bool full_table) {
     wsc_ctx *ctx = crf->ctx;
     // shared: build the lattice of ONE image and let all crf->B images use it (position-only features)
@@ -2902,33 +2929,33 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
     WSC_CHECK(B * cap < (1ll << 31), WSC_ERR_CAPACITY, "CRF batch too large for the hash tables");
     WSC_CHECK(cap <= (1ll << 28), WSC_ERR_CAPACITY, "CRF image too large: hash slots do not fit 28 bits"); // (tile pass: slot | r << 28)
 
-    TempBuf tmp(ctx);
+    CtxBlocks tmp(ctx); // build-time scratch, handed back when the build returns
     unsigned long long *table;
     int32_t *first, *slot2row, *rowimg;
     unsigned *bitmap, *wcount, *wprefix, *sums, *bound_dev;
     unsigned long long *rowkey;
     int *err;
-    WSC_TRY(tmp.alloc(sizeof(unsigned long long) * B * cap, (void **)&table));
-    WSC_TRY(tmp.alloc(sizeof(int32_t) * B * cap, (void **)&first));
-    WSC_TRY(tmp.alloc(sizeof(int32_t) * B * cap, (void **)&slot2row));
+    WSC_TRY(tmp.alloc(sizeof(unsigned long long) * B * cap, &table));
+    WSC_TRY(tmp.alloc(sizeof(int32_t) * B * cap, &first));
+    WSC_TRY(tmp.alloc(sizeof(int32_t) * B * cap, &slot2row));
     const long long nw = (total + 31) / 32 + 1; // first-toucher bitmap over the entries
-    WSC_TRY(tmp.alloc(sizeof(unsigned) * nw, (void **)&bitmap));
-    WSC_TRY(tmp.alloc(sizeof(unsigned) * nw, (void **)&wcount));
-    WSC_TRY(tmp.alloc(sizeof(unsigned) * (nw + 1), (void **)&wprefix));
-    WSC_TRY(tmp.alloc(sizeof(unsigned) * (size_t)(B + 1), (void **)&bound_dev));
+    WSC_TRY(tmp.alloc(sizeof(unsigned) * nw, &bitmap));
+    WSC_TRY(tmp.alloc(sizeof(unsigned) * nw, &wcount));
+    WSC_TRY(tmp.alloc(sizeof(unsigned) * (nw + 1), &wprefix));
+    WSC_TRY(tmp.alloc(sizeof(unsigned) * (size_t)(B + 1), &bound_dev));
     const int nblk = (int)((nw + SCAN_CHUNK - 1) / SCAN_CHUNK);
-    WSC_TRY(tmp.alloc(sizeof(unsigned) * (nblk + 2), (void **)&sums));
+    WSC_TRY(tmp.alloc(sizeof(unsigned) * (nblk + 2), &sums));
     // zero-initialised scratch in ONE block (one memset instead of three): err | redo_count | tile_nslots[n_tiles + 1]
     const TileGeom tg0 = make_geom(crf->H, crf->W);
     const int n_tiles0 = B * tg0.tpi;
     unsigned *zblk;
-    WSC_TRY(tmp.alloc(sizeof(unsigned) * (size_t)(n_tiles0 + 1 + 4), (void **)&zblk));
+    WSC_TRY(tmp.alloc(sizeof(unsigned) * (size_t)(n_tiles0 + 1 + 4), &zblk));
     err = reinterpret_cast<int *>(zblk);
-    WSC_TRY(crf_alloc(crf, sizeof(int32_t) * total, (void **)&L.offset));
-    WSC_TRY(crf_alloc(crf, sizeof(float) * total, (void **)&L.bary));
-    WSC_TRY(crf_alloc(crf, sizeof(float) * npix, (void **)&L.norm));
-    WSC_TRY(crf_alloc(crf, sizeof(float) * total, (void **)&L.tent_w));
-    WSC_TRY(crf_alloc(crf, sizeof(uint8_t) * total, (void **)&L.tent_p));
+    WSC_TRY(own.alloc(sizeof(int32_t) * total, &L.offset));
+    WSC_TRY(own.alloc(sizeof(float) * total, &L.bary));
+    WSC_TRY(own.alloc(sizeof(float) * npix, &L.norm));
+    WSC_TRY(own.alloc(sizeof(float) * total, &L.tent_w));
+    WSC_TRY(own.alloc(sizeof(uint8_t) * total, &L.tent_p));
 
     hipLaunchKernelGGL(fill_tables_kernel, dim3(grid1d(B * cap)), dim3(256), 0, ctx->stream, table, (unsigned *)first,
                        (long long)B * cap);
@@ -2948,7 +2975,7 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
     L.n_tiles = B * tg.tpi;
     int32_t *sslot;
     unsigned *tile_nslots;
-    WSC_TRY(tmp.alloc(sizeof(int32_t) * total, (void **)&sslot));
+    WSC_TRY(tmp.alloc(sizeof(int32_t) * total, &sslot));
     tile_nslots = zblk + 4; // (zeroed above)
     {
         // small-table launch for every tile, full-table launch for the ones that gave up (WSC_OPT_CRF_EMBED_FULL: full table
@@ -2960,7 +2987,7 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
         } else {
             int32_t *redo_list;
             unsigned *redo_count;
-            WSC_TRY(tmp.alloc(sizeof(int32_t) * (size_t)L.n_tiles, (void **)&redo_list));
+            WSC_TRY(tmp.alloc(sizeof(int32_t) * (size_t)L.n_tiles, &redo_list));
             redo_count = zblk + 1; // (zeroed above)
             hipLaunchKernelGGL(tile_embed_kernel<D>, dim3((unsigned)L.n_tiles), dim3(256), 0, ctx->stream, ea, tg, L.tent_w, L.tent_p,
                                sslot, tile_nslots, fb, redo_list, redo_count);
@@ -2992,7 +3019,7 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
               (double)sxy, (double)srgb);
     if (herr & 2) {
         WSC_CHECK(!full_table, WSC_ERR_CAPACITY, "CRF lattice hash table overflow at worst-case size");
-        return WSC_RETRY_FULL_TABLE; // crf_alloc'ed arrays of this attempt are released with the crf / reused
+        return WSC_RETRY_FULL_TABLE;
     }
     L.rows = (int)vtot + 1;
     L.v_per_image.resize(crf->B);
@@ -3001,7 +3028,7 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
     else
         for (int b = 0; b < B; ++b) L.v_per_image[b] = (int)((b + 1 < B ? bound[b + 1] : vtot) - bound[b]);
     if (!shared) { // row range of every image (blur_lds_kernel takes one image's rows into a workgroup's LDS)
-        WSC_TRY(crf_alloc(crf, sizeof(int32_t) * (size_t)(B + 1), (void **)&L.img_row));
+        WSC_TRY(own.alloc(sizeof(int32_t) * (size_t)(B + 1), &L.img_row));
         hipLaunchKernelGGL(image_rows_kernel, dim3((unsigned)(B / 64 + 1)), dim3(64), 0, ctx->stream, bound_dev, B, (int)vtot + 1,
                            L.img_row);
         L.max_img_rows = 0;
@@ -3011,13 +3038,13 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
             if (blur_lds_variant(L.v_per_image[b]) < 0) L.bl_ok = false; // an image with too many vertices for any variant
         if (L.bl_ok) { // the workgroup table: at most 32 class groups per image, the images dealt to 8 XCD queues
             L.bl_cap = 8 * ((B + 7) / 8) * 32;
-            WSC_TRY(crf_alloc(crf, sizeof(int2) * (size_t)L.bl_cap, (void **)&L.bl_blk));
+            WSC_TRY(own.alloc(sizeof(int2) * (size_t)L.bl_cap, &L.bl_blk));
         }
     }
 
-    WSC_TRY(tmp.alloc(sizeof(unsigned long long) * L.rows, (void **)&rowkey));
-    WSC_TRY(tmp.alloc(sizeof(int32_t) * L.rows, (void **)&rowimg));
-    WSC_TRY(crf_alloc(crf, sizeof(int2) * (size_t)dp1 * L.rows, (void **)&L.nbr));
+    WSC_TRY(tmp.alloc(sizeof(unsigned long long) * L.rows, &rowkey));
+    WSC_TRY(tmp.alloc(sizeof(int32_t) * L.rows, &rowimg));
+    WSC_TRY(own.alloc(sizeof(int2) * (size_t)dp1 * L.rows, &L.nbr));
 
     hipLaunchKernelGGL(assign_rows_kernel, grid_tab, dim3(256), 0, ctx->stream, first, table, cap, per_img, bitmap, wprefix, slot2row,
                        rowkey, rowimg);
@@ -3025,31 +3052,31 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
         int32_t *slot_row;
         unsigned *sums2, *row_nslots, *cursor, *sums3;
         const int nb2 = (L.n_tiles + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK, nb3 = (L.rows + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        WSC_TRY(tmp.alloc(sizeof(unsigned) * (nb2 + 2), (void **)&sums2));
-        WSC_TRY(tmp.alloc(sizeof(unsigned) * 2 * (size_t)(L.rows + 1), (void **)&row_nslots)); // row_nslots | cursor: one memset
+        WSC_TRY(tmp.alloc(sizeof(unsigned) * (nb2 + 2), &sums2));
+        WSC_TRY(tmp.alloc(sizeof(unsigned) * 2 * (size_t)(L.rows + 1), &row_nslots)); // row_nslots | cursor: one memset
         cursor = row_nslots + (L.rows + 1);
-        WSC_TRY(tmp.alloc(sizeof(unsigned) * (nb3 + 2), (void **)&sums3));
-        WSC_TRY(crf_alloc(crf, sizeof(int32_t) * (L.n_tiles + 2), (void **)&L.tslot_start));
-        WSC_TRY(crf_alloc(crf, sizeof(int32_t) * (L.rows + 2), (void **)&L.row_slot_start));
+        WSC_TRY(tmp.alloc(sizeof(unsigned) * (nb3 + 2), &sums3));
+        WSC_TRY(own.alloc(sizeof(int32_t) * (L.n_tiles + 2), &L.tslot_start));
+        WSC_TRY(own.alloc(sizeof(int32_t) * (L.rows + 2), &L.row_slot_start));
         WSC_HIP(hipMemsetAsync(row_nslots, 0, sizeof(unsigned) * 2 * (size_t)(L.rows + 1), ctx->stream));
         WSC_TRY(exclusive_scan(ctx, tile_nslots, L.n_tiles + 1, (unsigned *)L.tslot_start, sums2));
         unsigned ns = 0;
         WSC_HIP(hipMemcpyAsync(&ns, sums2 + nb2, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
         WSC_HIP(hipStreamSynchronize(ctx->stream));
         L.n_slots = (int)ns;
-        WSC_TRY(crf_alloc(crf, sizeof(int2) * (size_t)(L.n_slots + 1), (void **)&L.slot_desc));
-        WSC_TRY(tmp.alloc(sizeof(int32_t) * (size_t)(L.n_slots + 1), (void **)&slot_row));
+        WSC_TRY(own.alloc(sizeof(int2) * (size_t)(L.n_slots + 1), &L.slot_desc));
+        WSC_TRY(tmp.alloc(sizeof(int32_t) * (size_t)(L.n_slots + 1), &slot_row));
         unsigned *slot_key = nullptr;
         int32_t *dest_slot = nullptr;
         if (D == 2) {
-            WSC_TRY(tmp.alloc(sizeof(unsigned) * (size_t)(L.n_slots + 1), (void **)&slot_key));
-            WSC_TRY(tmp.alloc(sizeof(int32_t) * (size_t)(L.n_slots + 1), (void **)&dest_slot));
+            WSC_TRY(tmp.alloc(sizeof(unsigned) * (size_t)(L.n_slots + 1), &slot_key));
+            WSC_TRY(tmp.alloc(sizeof(int32_t) * (size_t)(L.n_slots + 1), &dest_slot));
         }
         hipLaunchKernelGGL(tile_slots_kernel, dim3((unsigned)L.n_tiles), dim3(256), 0, ctx->stream, sslot, L.tent_p, L.offset, slot2row,
                            cap, dp1, tg,
                            L.tslot_start, L.slot_desc, slot_row, slot_key, row_nslots);
         WSC_TRY(exclusive_scan(ctx, row_nslots, L.rows + 1, (unsigned *)L.row_slot_start, sums3));
-        if (!shared) WSC_TRY(crf_alloc(crf, sizeof(uint32_t) * (size_t)(L.n_slots + 1), (void **)&L.part_row));
+        if (!shared) WSC_TRY(own.alloc(sizeof(uint32_t) * (size_t)(L.n_slots + 1), &L.part_row));
         hipLaunchKernelGGL(slot_dest_kernel, dim3(grid1d(L.n_slots)), dim3(256), 0, ctx->stream, slot_row, L.n_slots,
                            L.row_slot_start, cursor, L.slot_desc, L.part_row);
         if (D == 2) { // Gaussian lattice (built once per image size): deterministic partial-row order, plain fp32 combine
@@ -3067,8 +3094,8 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
     if (D == 2) { // tile tables of the fused blur (one-off per cached Gaussian lattice: the host syncs are fine)
         int2 *ij;
         int *bbox;
-        WSC_TRY(tmp.alloc(sizeof(int2) * L.rows, (void **)&ij));
-        WSC_TRY(tmp.alloc(sizeof(int) * 5, (void **)&bbox));
+        WSC_TRY(tmp.alloc(sizeof(int2) * L.rows, &ij));
+        WSC_TRY(tmp.alloc(sizeof(int) * 5, &bbox));
         const int init[5] = {0x7fffffff, 0x7fffffff, -0x7fffffff, -0x7fffffff, 0};
         WSC_TRY(wsc_ctx_upload_small(ctx, bbox, init, sizeof(init)));
         hipLaunchKernelGGL(gauss_ij_kernel, dim3(grid1d(L.rows)), dim3(256), 0, ctx->stream, rowkey, L.rows, ij, bbox);
@@ -3081,8 +3108,8 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
         if (hb[4] == 0 && nti > 0 && ntj > 0 && nti * ntj <= 4ll * L.rows + 64) {
             const long long nt = nti * ntj;
             int32_t *occ;
-            WSC_TRY(tmp.alloc(sizeof(int32_t) * nt, (void **)&occ));
-            WSC_TRY(crf_alloc(crf, sizeof(int32_t) * nt * GBI * GBJ, (void **)&L.tile_rows));
+            WSC_TRY(tmp.alloc(sizeof(int32_t) * nt, &occ));
+            WSC_TRY(own.alloc(sizeof(int32_t) * nt * GBI * GBJ, &L.tile_rows));
             WSC_HIP(hipMemsetAsync(L.tile_rows, 0, sizeof(int32_t) * nt * GBI * GBJ, ctx->stream));
             WSC_HIP(hipMemsetAsync(occ, 0, sizeof(int32_t) * nt, ctx->stream));
             hipLaunchKernelGGL(gauss_tile_fill_kernel, dim3(grid1d(L.rows)), dim3(256), 0, ctx->stream, ij, L.rows, hb[0],
@@ -3094,11 +3121,11 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
                 if (hocc[t]) list.push_back((int32_t)t);
             L.n_tiles_occ = (int)list.size();
             if (L.n_tiles_occ > 0) {
-                WSC_TRY(crf_alloc(crf, sizeof(int32_t) * list.size(), (void **)&L.tile_list));
+                WSC_TRY(own.alloc(sizeof(int32_t) * list.size(), &L.tile_list));
                 WSC_HIP(hipMemcpyAsync(L.tile_list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice,
                                        ctx->stream));
                 WSC_HIP(hipStreamSynchronize(ctx->stream)); // `list` is pageable host memory
-                WSC_TRY(crf_alloc(crf, sizeof(int2) * nt * GBI * GBJ, (void **)&L.tile_pstart));
+                WSC_TRY(own.alloc(sizeof(int2) * nt * GBI * GBJ, &L.tile_pstart));
                 hipLaunchKernelGGL(gauss_tile_pstart_kernel, dim3(grid1d(nt * GBI * GBJ)), dim3(256), 0, ctx->stream,
                                    L.tile_rows, L.row_slot_start, nt * GBI * GBJ, L.tile_pstart);
             }
@@ -3106,18 +3133,15 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
     }
     // norm = 1/sqrt(Lattice(1) + 1e-20)
     float *va, *vb, *vp;
-    WSC_TRY(tmp.alloc(sizeof(float) * L.rows, (void **)&va));
-    WSC_TRY(tmp.alloc(sizeof(float) * L.rows, (void **)&vb));
-    WSC_TRY(tmp.alloc(sizeof(float) * (size_t)(L.n_slots + 1), (void **)&vp));
+    WSC_TRY(tmp.alloc(sizeof(float) * L.rows, &va));
+    WSC_TRY(tmp.alloc(sizeof(float) * L.rows, &vb));
+    WSC_TRY(tmp.alloc(sizeof(float) * (size_t)(L.n_slots + 1), &vp));
     splat_ones(ctx, L, make_geom(crf->H, crf->W), va, vp);
     float *res = blur_all1(ctx, L, va, vb);
     // the bilateral lattice of a crf whose updates start from the on-chip Gaussian message: their 52-byte record is
     // written by the same pass (crf_bilateral_records finds it done)
     uint32_t *rec_b = nullptr;
-    if (D == 5 && !shared && crf->lat[0].gt_rows && !crf->pix_rec_b) {
-        WSC_TRY(crf_alloc(crf, sizeof(uint32_t) * 13 * (size_t)npix, (void **)&crf->pix_rec_b));
-        rec_b = crf->pix_rec_b;
-    }
+    if (D == 5 && !shared && crf->lat[0].gt_rows && !crf->pix_rec_b) WSC_TRY(own.alloc(sizeof(uint32_t) * 13 * (size_t)npix, &rec_b));
     if (!shared && D == 5) { // per-image lattices of a batch: norm + record + entry scaling in one pass per pixel tile
         hipLaunchKernelGGL(slice_norm_tile_kernel, dim3((unsigned)L.n_tiles), dim3(256), 0, ctx->stream, L.offset, L.bary, dp1,
                            L.alpha, res, make_geom(crf->H, crf->W), L.norm, rec_b, L.tent_w, L.tent_p);
@@ -3128,32 +3152,16 @@ int build_lattice(wsc_crf *crf, LatticeDev &L, const uint8_t *rgb_dev, float sxy
                            make_geom(crf->H, crf->W), L.tent_w, L.tent_p);
     }
     WSC_HIP(hipGetLastError());
+    if (rec_b) crf->pix_rec_b = rec_b;
     // (the tile vertex sets of the on-chip Gaussian message -- gauss_fuse_tables: a device -> host copy of the lattice and a
-    // host pass, 3-4 ms -- are added when a cached lattice is used a SECOND time: wsc_crf_create)
+    // host pass, 3-4 ms -- are added when a cached lattice is used a SECOND time: gauss_lattice)
     return WSC_OK;
 }
 
-struct GaussCache {
-    int H, W;
-    float sxy;
-    LatticeDev L;
-    std::vector<void *> blocks; // its device arrays (cached-alloc blocks of the ctx): handed back when the entry is evicted
-    int users = 0;              // live wsc_crf objects whose lat[0] aliases L
-    unsigned long long last_use = 0;
-    bool fuse_pending = true;   // the tile vertex sets of the on-chip message are built at the entry's second use
-};
-// distinct image sizes kept per ctx (~25 MB each at 375 x 500).  When the table is full the least recently used entry that
-// no live wsc_crf refers to makes room (round 3 had no eviction: after 64 sizes every later size was rebuilt per call,
-// without the on-chip message path -- cam_to_ir_label walks hundreds of sizes).  Only when all entries are in use is a
-// lattice built for the one call, without the host-built tile vertex sets of the on-chip message path.
-constexpr int GAUSS_CACHE_MAX = 64;
-std::atomic<unsigned long long> g_gauss_use_clock{0}; // (contexts of several host threads share it: only the order matters)
-void gauss_cache_delete(void *p) { delete static_cast<GaussCache *>(p); }
-
-// slice: messages of both lattices are read (false before the first iteration); splat: the result is splatted
-// (false in the last iteration, whose Q is written to a.q instead)
 size_t update_splat_lds(int LP) { return sizeof(f32x4_t) * TILE_PIX * LP + sizeof(uint2) * GATHER_ENT + sizeof(int2) * GATHER_SB; }
 size_t gauss_msg_lds(int LP, int gt_stride) { return ((size_t)LP * sizeof(f32x4_t) + sizeof(uint4)) * (size_t)gt_stride; }
+// LDS of the FG variants: Q stage + splat tables / records + the tile's closed vertex set (rows + neighbour words)
+size_t update_fg_lds(int LP, int gt_stride) { return update_splat_lds(LP) + gauss_msg_lds(LP, gt_stride); }
 // can the Gaussian message be formed on chip (gauss_msg_kernel) for this call?  The tile vertex sets must exist (sets within
 // the local-id range) and fit the kernel's LDS and its per-thread item bound.
 bool update_gf_ok(const wsc_ctx *ctx, const LatticeDev &G, int LP) {
@@ -3162,39 +3170,48 @@ bool update_gf_ok(const wsc_ctx *ctx, const LatticeDev &G, int LP) {
     if ((long long)G.gt_stride * LP > 6ll * GM_THREADS || (long long)G.gt_stride * LP >= 8192) return false;
     return gauss_msg_lds(LP, G.gt_stride) <= 64 * 1024;
 }
-
-int launch_gauss_msg(wsc_ctx *ctx, hipStream_t st, const GaussMsgArgs &g, double bytes) {
-    WscKernelTimer timer(ctx, WSC_K_GAUSS_MSG, bytes);
-    const dim3 grid((unsigned)(g.B * g.tg.tpi)), block(GM_THREADS);
-    const size_t lds = gauss_msg_lds(g.LP, g.gt_stride);
-    if ((long long)g.gt_stride * g.LP <= 4ll * GM_THREADS && g.LP <= 6)
-        hipLaunchKernelGGL((gauss_msg_kernel<4, 3>), grid, block, lds, st, g);
-    else
-        hipLaunchKernelGGL((gauss_msg_kernel<6, 4>), grid, block, lds, st, g);
-    WSC_HIP(hipGetLastError());
-    return WSC_OK;
-}
-
-// gf: the energy starts from the E buffer of gauss_msg_kernel (a.u points at it), no Gaussian rows are gathered
-// LDS of the FG variants: Q stage + splat tables / records + the tile's closed vertex set (rows + neighbour words)
-size_t update_fg_lds(int LP, int gt_stride) { return update_splat_lds(LP) + gauss_msg_lds(LP, gt_stride); }
 // can the Gaussian message be formed INSIDE the update kernel?  Two blocks of GM_THREADS threads per CU must fit
 bool update_fg_ok(const wsc_ctx *ctx, const LatticeDev &G, int LP) {
     if (!ctx->opt[WSC_OPT_CRF_MSG_IN_UPDATE] || !update_gf_ok(ctx, G, LP)) return false;
     return update_fg_lds(LP, G.gt_stride) <= 80 * 1024;
 }
+// the Gaussian message's per-thread item counts, wherever it is formed: the small form (4 vertex items per blur pass) when
+// the tile's vertex set admits it, else 6 (gauss_msg_kernel<4, 3> / <6, 4>, update_splat_kernel<.., 4> / <.., 6>)
+bool gauss_msg_small(int gt_stride, int LP) { return (long long)gt_stride * LP <= 4ll * GM_THREADS && LP <= 6; }
+
+int launch_gauss_msg(wsc_ctx *ctx, hipStream_t st, const GaussMsgArgs &g, double bytes) {
+    WscKernelTimer timer(ctx, WSC_K_GAUSS_MSG, bytes);
+    const auto kernel = gauss_msg_small(g.gt_stride, g.LP) ? gauss_msg_kernel<4, 3> : gauss_msg_kernel<6, 4>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(g.B * g.tg.tpi)), dim3(GM_THREADS), gauss_msg_lds(g.LP, g.gt_stride), st, g);
+    WSC_HIP(hipGetLastError());
+    return WSC_OK;
+}
+
+// The update_splat_kernel variant of a launch, its block size and its dynamic LDS.  slice: messages of both lattices are read
+// (false before the first iteration); splat: the result is splatted (false in the last iteration, whose Q is written to a.q
+// instead); gf: the energy starts from the E buffer of gauss_msg_kernel (a.u points at it), no Gaussian rows are gathered --
+// it counts only with slice; fg: the Gaussian message is formed inside the kernel (a.u = U, a.part_g_in = the previous
+// splat's Gaussian partials), which implies slice and gf; small: gauss_msg_small.
+typedef void (*UpdateKernel)(UpdateArgs);
+template <bool SLICE, bool GF, int FG>
+UpdateKernel update_kernel(bool splat) { return splat ? update_splat_kernel<SLICE, true, GF, FG> : update_splat_kernel<SLICE, false, GF, FG>; }
+struct UpdateVariant { UpdateKernel kernel; int threads; size_t lds; };
+UpdateVariant update_variant(bool slice, bool splat, bool gf, bool fg, bool small, int LP, int gt_stride) {
+    if (fg) return {small ? update_kernel<true, true, 4>(splat) : update_kernel<true, true, 6>(splat), GM_THREADS, update_fg_lds(LP, gt_stride)};
+    if (slice && gf) return {update_kernel<true, true, 0>(splat), 256, update_splat_lds(LP)}; // the last update stages E + records too
+    return {slice ? update_kernel<true, false, 0>(splat) : update_kernel<false, false, 0>(splat), 256, splat ? update_splat_lds(LP) : 0};
+}
 // The FG variants take more than 48 KB of LDS per block at most sizes: their dynamic-LDS limit is raised before a call picks
 // the form.  An error leaves the two-launch form (gauss_msg_kernel + update), which gives the same bits.
 int update_fg_lds_limit(wsc_ctx *ctx, int LP, int gt_stride) {
     if (update_fg_lds(LP, gt_stride) <= 48 * 1024) return WSC_OK;
-    for (const void *fn : {reinterpret_cast<const void *>(update_splat_kernel<true, true, true, 4>),
-                           reinterpret_cast<const void *>(update_splat_kernel<true, false, true, 4>),
-                           reinterpret_cast<const void *>(update_splat_kernel<true, true, true, 6>),
-                           reinterpret_cast<const void *>(update_splat_kernel<true, false, true, 6>)})
-        WSC_TRY(wsc_set_max_dynamic_lds(ctx, fn, 96 * 1024));
+    for (const bool small : {true, false})
+        for (const bool splat : {true, false}) {
+            const UpdateKernel k = update_variant(true, splat, true, true, small, LP, gt_stride).kernel;
+            WSC_TRY(wsc_set_max_dynamic_lds(ctx, reinterpret_cast<const void *>(k), 96 * 1024));
+        }
     return WSC_OK;
 }
-// fg: the Gaussian message is formed inside the kernel (a.u = U, a.part_g_in = the previous splat's Gaussian partials)
 int launch_update(wsc_ctx *ctx, const UpdateArgs &a, bool slice, bool splat, bool gf, bool fg = false, double fg_bytes = 0.0) {
     const double npix = (double)a.B * a.tg.H * a.tg.W;
     // algorithmic bytes: read U, write Q; slice: index+weight of both lattices (9 entries of 8 bytes) and the
@@ -3204,64 +3221,127 @@ int launch_update(wsc_ctx *ctx, const UpdateArgs &a, bool slice, bool splat, boo
     const double by = npix * (2.0 * a.M * 4 + (slice ? (gf ? 6 * 8 + 1.0 * a.M * 4 : 9 * 8 + 2.0 * a.M * 4) : 0.0) +
                               (splat ? 9 * 8 + 2.0 * a.M * 4 : 0.0));
     WscKernelTimer timer(ctx, WSC_K_SLICE_UPDATE, by + (fg ? fg_bytes : 0.0));
-    const dim3 grid((unsigned)(a.B * a.tg.tpi)), block(256);
-    size_t lds = splat ? update_splat_lds(a.LP) : 0;
-    if (fg) {
-        const size_t l = update_fg_lds(a.LP, a.gt_stride);
-        const bool small = (long long)a.gt_stride * a.LP <= 4ll * GM_THREADS && a.LP <= 6;
-        if (small) {
-            if (splat) hipLaunchKernelGGL((update_splat_kernel<true, true, true, 4>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-            else hipLaunchKernelGGL((update_splat_kernel<true, false, true, 4>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-        } else {
-            if (splat) hipLaunchKernelGGL((update_splat_kernel<true, true, true, 6>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-            else hipLaunchKernelGGL((update_splat_kernel<true, false, true, 6>), grid, dim3(GM_THREADS), l, ctx->stream, a);
-        }
-        WSC_HIP(hipGetLastError());
-        return WSC_OK;
-    }
-    if (slice && gf) {
-        lds = update_splat_lds(a.LP); // the last update stages E + records too
-        if (splat) hipLaunchKernelGGL((update_splat_kernel<true, true, true>), grid, block, lds, ctx->stream, a);
-        else hipLaunchKernelGGL((update_splat_kernel<true, false, true>), grid, block, lds, ctx->stream, a);
-    } else if (slice && splat) hipLaunchKernelGGL((update_splat_kernel<true, true>), grid, block, lds, ctx->stream, a);
-    else if (slice) hipLaunchKernelGGL((update_splat_kernel<true, false>), grid, block, lds, ctx->stream, a);
-    else if (splat) hipLaunchKernelGGL((update_splat_kernel<false, true>), grid, block, lds, ctx->stream, a); // U rows by LDS-DMA
-    else hipLaunchKernelGGL((update_splat_kernel<false, false>), grid, block, lds, ctx->stream, a);
+    const UpdateVariant v = update_variant(slice, splat, gf, fg, gauss_msg_small(a.gt_stride, a.LP), a.LP, a.gt_stride);
+    hipLaunchKernelGGL(v.kernel, dim3((unsigned)(a.B * a.tg.tpi)), dim3(v.threads), v.lds, ctx->stream, a);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
-// the 80-byte per-pixel records (pack_pixels_kernel) of a crf, built on `st`.  The block comes from the BUILD ctx's
-// stream-ordered cache: when `st` is another stream, it first waits for everything enqueued on the build stream so far
-// (the block's previous user), and the build stream waits for this launch before it can hand the block on (crf->use_ev).
-int crf_full_records(wsc_crf *crf, hipStream_t st) {
-    if (crf->pix_rec) return WSC_OK;
+// the splat tables of one lattice as the update kernel sees them, its slot partials written to `part`
+SplatTab splat_tab(const LatticeDev &L, float *part) {
+    return SplatTab{L.tslot_start, L.slot_desc, L.tent_w, L.tent_p, part, L.n_slots, L.rep > 1 ? 1 : 0, L.d + 1};
+}
+// the arguments of a crf's update launches that stay put over its mean-field loop (q, argmax, u and the FG variants' partial
+// arrays are per iteration)
+UpdateArgs update_args(const wsc_crf *crf, int M, float g_compat, float bi_compat, const float *u, float *partg, float *partb) {
+    const LatticeDev &G = crf->lat[0], &Bl = crf->lat[1];
+    UpdateArgs a;
+    a.pix_rec = crf->pix_rec; a.pix_rec_b = crf->pix_rec_b; a.val_g = nullptr; a.val_b = nullptr;
+    a.u = u; a.q = nullptr; a.argmax = nullptr;
+    a.alpha_g = G.alpha; a.alpha_b = Bl.alpha; a.compat_g = g_compat; a.compat_b = bi_compat;
+    a.M = M; a.LP = (M + 3) / 4; a.B = crf->B; a.tg = make_geom(crf->H, crf->W);
+    a.g_pix = (unsigned)G.n_pix; a.g_rows = G.rep > 1 ? (unsigned)G.rows : 0u;
+    a.sg = splat_tab(G, partg); a.sb = splat_tab(Bl, partb);
+    a.gt_cnt = G.gt_cnt; a.gt_rows = G.gt_rows; a.gt_nbr = G.gt_nbr; a.gt_pix = G.gt_pix; a.gt_stride = G.gt_stride;
+    a.part_g_in = nullptr;
+    return a;
+}
+// gauss_msg_kernel's arguments: E = -U + Gaussian message from the slot partials `part`
+GaussMsgArgs gauss_msg_args(const wsc_crf *crf, int M, float g_compat, const float *part, const float *u, float *e) {
+    const LatticeDev &G = crf->lat[0];
+    return GaussMsgArgs{G.gt_cnt, G.gt_rows, G.gt_nbr, G.gt_pix, part, u, e, G.gt_stride, G.n_slots, G.rep > 1 ? 1 : 0,
+                        (M + 3) / 4, crf->B, g_compat * G.alpha, make_geom(crf->H, crf->W)};
+}
+
+// A crf's pixel records are built on `st` (the stream of the ctx running its loop) in blocks from the BUILD ctx's
+// stream-ordered cache: when `st` is another stream, it first waits for everything enqueued on the build stream so far (the
+// block's previous user), and the build stream waits for the loop before it can hand the block on (crf->use_ev).
+int order_after_build(const wsc_crf *crf, hipStream_t st) {
     wsc_ctx *bctx = crf->ctx;
-    WSC_TRY(crf_alloc(crf, sizeof(uint4) * 5 * (size_t)crf->B * crf->N, (void **)&crf->pix_rec));
     if (st != bctx->stream) {
         WSC_HIP(hipEventRecord(bctx->join_ev, bctx->stream));
         WSC_HIP(hipStreamWaitEvent(st, bctx->join_ev, 0));
     }
+    return WSC_OK;
+}
+// the 80-byte per-pixel records (pack_pixels_kernel): both lattices, for the updates that gather the Gaussian rows themselves
+int crf_full_records(wsc_crf *crf, hipStream_t st) {
+    if (crf->pix_rec) return WSC_OK;
+    WSC_TRY(crf->blocks.alloc(sizeof(uint4) * 5 * (size_t)crf->B * crf->N, &crf->pix_rec));
+    WSC_TRY(order_after_build(crf, st));
     hipLaunchKernelGGL(pack_pixels_kernel, dim3((unsigned)grid1d((long long)crf->N * 5, 256, 2048), (unsigned)crf->B), dim3(256), 0, st,
                        crf->lat[0].offset, crf->lat[0].bary, crf->lat[0].norm, crf->lat[1].offset, crf->lat[1].bary,
                        crf->lat[1].norm, crf->N, crf->lat[0].rep > 1 ? 1 : 0, crf->pix_rec);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
-
-// the 52-byte bilateral records (pack_pixels_b_kernel) of the GF updates; same stream rules as crf_full_records
+// the 52-byte bilateral records (pack_pixels_b_kernel) of the GF updates
 int crf_bilateral_records(wsc_crf *crf, hipStream_t st) {
     if (crf->pix_rec_b) return WSC_OK;
-    wsc_ctx *bctx = crf->ctx;
-    WSC_TRY(crf_alloc(crf, sizeof(uint32_t) * 13 * (size_t)crf->B * crf->N, (void **)&crf->pix_rec_b));
-    if (st != bctx->stream) {
-        WSC_HIP(hipEventRecord(bctx->join_ev, bctx->stream));
-        WSC_HIP(hipStreamWaitEvent(st, bctx->join_ev, 0));
-    }
+    WSC_TRY(crf->blocks.alloc(sizeof(uint32_t) * 13 * (size_t)crf->B * crf->N, &crf->pix_rec_b));
+    WSC_TRY(order_after_build(crf, st));
     hipLaunchKernelGGL(pack_pixels_b_kernel, dim3((unsigned)grid1d((long long)crf->B * crf->N * 13, 256, 8192)), dim3(256), 0, st,
                        crf->lat[1].offset, crf->lat[1].bary, crf->lat[1].norm, (long long)crf->B * crf->N, crf->pix_rec_b);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
+}
+
+// The crf's Gaussian lattice (lat[0]).  It is a function of (H, W, sxy) alone: one copy per ctx serves every batch of that
+// image size (the reference rebuilds it per image, addPairwiseGaussian in dcrf_process / crf_inference_label, and gets the
+// same table every time).  Found in or added to the ctx's cache, which the crf then holds a use of (crf->gauss); built
+// into crf->blocks when every cached entry is in use.
+int gauss_lattice(wsc_crf *crf, const uint8_t *rgb_dev, float sxy) {
+    wsc_ctx *ctx = crf->ctx;
+    if (!ctx->gauss_cache) ctx->gauss_cache = new WscGaussCache();
+    std::vector<std::unique_ptr<GaussEntry>> &cache = ctx->gauss_cache->entries;
+    GaussEntry *hit = nullptr;
+    auto lru = cache.end();
+    for (auto it = cache.begin(); it != cache.end(); ++it) {
+        GaussEntry &g = **it;
+        if (g.H == crf->H && g.W == crf->W && g.sxy == sxy) hit = &g;
+        if (g.users == 0 && (lru == cache.end() || g.last_use < (*lru)->last_use)) lru = it;
+    }
+    // evict: its blocks go back to the build ctx's stream-ordered cache.  No live wsc_crf refers to it, and every wsc_crf that
+    // did has been destroyed -- which made this stream wait for loops it ran on other streams.
+    if (!hit && (int)cache.size() >= GAUSS_CACHE_MAX && lru != cache.end()) cache.erase(lru);
+    if (!hit) {
+        CtxBlocks own(ctx);
+        WSC_TRY(build_lattice<2>(crf, crf->lat[0], own, rgb_dev, sxy, 1.f, true, true)); // built once: worst-case table
+        if ((int)cache.size() >= GAUSS_CACHE_MAX) {
+            crf->blocks.take(std::move(own));
+            return WSC_OK;
+        }
+        cache.emplace_back(new GaussEntry{crf->H, crf->W, sxy, crf->lat[0], std::move(own)});
+        hit = cache.back().get();
+    } else {
+        if (hit->fuse_pending) {
+            // second use of this image size: now the host-built tile vertex sets pay (a size seen once -- cam_to_ir_label walks
+            // hundreds of native VOC sizes -- never pays the 3-4 ms; its loop takes the blur-kernel path, same bits)
+            hit->fuse_pending = false;
+            if (gauss_fuse_tables(ctx, make_geom(crf->H, crf->W), hit->L, hit->blocks) != WSC_OK) { // (the lattice stays valid)
+                hit->L.gt_cnt = nullptr; hit->L.gt_rows = nullptr; hit->L.gt_nbr = nullptr; hit->L.gt_pix = nullptr; hit->L.gt_stride = 0;
+            }
+        }
+        crf->lat[0] = hit->L;
+    }
+    hit->users += 1;
+    hit->last_use = ++g_gauss_use_clock;
+    crf->gauss = hit;
+    return WSC_OK;
+}
+
+// The crf's bilateral lattice (lat[1]), into crf->blocks.  A noise-like image has more vertices than the right-sized hash
+// table holds: the blocks of that attempt go back and the build is repeated with the worst-case table.
+int bilateral_lattice(wsc_crf *crf, const uint8_t *rgb_dev, float sxy, float srgb) {
+    CtxBlocks own(crf->ctx);
+    int st = build_lattice<5>(crf, crf->lat[1], own, rgb_dev, sxy, srgb, false, false);
+    if (st == WSC_RETRY_FULL_TABLE) {
+        own.release();
+        crf->lat[1] = LatticeDev();
+        st = build_lattice<5>(crf, crf->lat[1], own, rgb_dev, sxy, srgb, false, true);
+    }
+    if (st == WSC_OK) crf->blocks.take(std::move(own));
+    return st;
 }
 
 } // namespace
@@ -3275,81 +3355,13 @@ int wsc_crf_create(wsc_ctx *ctx, const uint8_t *rgb_dev, int B, int H, int W, fl
     WSC_CHECK(g_sxy > 0.f && bi_sxy > 0.f && bi_srgb > 0.f, WSC_ERR_INVALID,
               "wsc_crf_create: kernel widths must be positive");
     WSC_HIP(hipSetDevice(ctx->device));
-    wsc_crf *crf = new wsc_crf();
-    crf->ctx = ctx; crf->B = B; crf->H = H; crf->W = W; crf->N = H * W;
+    wsc_crf *crf = new wsc_crf(ctx);
+    crf->B = B; crf->H = H; crf->W = W; crf->N = H * W;
     WscKernelTimer timer(ctx, WSC_K_CRF_BUILD, (double)B * H * W * (3.0 * 16 + 6.0 * 16));
-    // The Gaussian lattice is a function of (H, W, sxy) alone: one copy per ctx serves every batch of
-    // that image size (the reference rebuilds it per image, addPairwiseGaussian in dcrf_process /
-    // crf_inference_label, and gets the same table every time).
-    int st = WSC_OK;
-    GaussCache *hit = nullptr, *lru = nullptr;
-    int n_cached = 0;
-    size_t lru_at = 0;
-    for (size_t i = 0; i < ctx->attachments.size(); ++i) {
-        auto &a = ctx->attachments[i];
-        if (a.second == &gauss_cache_delete) {
-            ++n_cached;
-            GaussCache *g = static_cast<GaussCache *>(a.first);
-            if (g->H == H && g->W == W && g->sxy == g_sxy) hit = g;
-            if (g->users == 0 && (!lru || g->last_use < lru->last_use)) {
-                lru = g;
-                lru_at = i;
-            }
-        }
-    }
-    if (!hit && n_cached >= GAUSS_CACHE_MAX && lru) {
-        // evict: its blocks go back to the build ctx's stream-ordered cache.  No live wsc_crf refers to it, and every
-        // wsc_crf that did has been destroyed -- which made this stream wait for loops it ran on other streams.
-        for (void *p : lru->blocks) wsc_ctx_cached_free(ctx, p);
-        delete lru;
-        ctx->attachments.erase(ctx->attachments.begin() + (long)lru_at);
-        --n_cached;
-    }
-    if (hit) {
-        if (hit->fuse_pending) {
-            // second use of this image size: now the host-built tile vertex sets pay (a size seen once -- cam_to_ir_label walks
-            // hundreds of native VOC sizes -- never pays the 3-4 ms; its loop takes the blur-kernel path, same bits)
-            hit->fuse_pending = false;
-            crf->persist = true;
-            const int st_f = gauss_fuse_tables(crf, hit->L, make_geom(H, W));
-            hit->blocks.insert(hit->blocks.end(), crf->persist_allocs.begin(), crf->persist_allocs.end());
-            crf->persist_allocs.clear();
-            crf->persist = false;
-            if (st_f != WSC_OK) { // (the lattice itself stays valid without the tables)
-                hit->L.gt_cnt = nullptr; hit->L.gt_rows = nullptr; hit->L.gt_nbr = nullptr; hit->L.gt_pix = nullptr;
-                hit->L.gt_stride = 0;
-            }
-        }
-        crf->lat[0] = hit->L;
-        hit->users += 1;
-        hit->last_use = ++g_gauss_use_clock;
-        crf->gauss_entry = hit;
-    } else {
-        crf->persist = n_cached < GAUSS_CACHE_MAX;
-        st = build_lattice<2>(crf, crf->lat[0], rgb_dev, g_sxy, 1.f, true, true); // built once: worst-case table
-        if (st == WSC_OK && crf->persist) {
-            GaussCache *g = new GaussCache{H, W, g_sxy, crf->lat[0], crf->persist_allocs, 1, ++g_gauss_use_clock};
-            ctx->attachments.emplace_back(g, &gauss_cache_delete);
-            crf->gauss_entry = g;
-        }
-        if (st != WSC_OK) // a failed build must not leave its arrays with the ctx for the rest of its life
-            for (void *p : crf->persist_allocs) wsc_ctx_cached_free(ctx, p);
-        crf->persist_allocs.clear();
-        crf->persist = false;
-    }
+    int st = gauss_lattice(crf, rgb_dev, g_sxy);
     crf->lat[0].rep = B;
     crf->lat[0].v_per_image.assign(B, crf->lat[0].rows - 1);
-    if (st == WSC_OK) {
-        const size_t mark = crf->allocs.size();
-        st = build_lattice<5>(crf, crf->lat[1], rgb_dev, bi_sxy, bi_srgb, false, false);
-        if (st == WSC_RETRY_FULL_TABLE) { // noise-like image: more vertices than the right-sized table holds
-            for (size_t i = mark; i < crf->allocs.size(); ++i) wsc_ctx_cached_free(ctx, crf->allocs[i]);
-            crf->allocs.resize(mark);
-            crf->pix_rec_b = nullptr; // (allocated by the failed attempt: handed back with its other blocks)
-            crf->lat[1] = LatticeDev();
-            st = build_lattice<5>(crf, crf->lat[1], rgb_dev, bi_sxy, bi_srgb, false, true);
-        }
-    }
+    if (st == WSC_OK) st = bilateral_lattice(crf, rgb_dev, bi_sxy, bi_srgb);
     // The 80-byte record (both lattices) serves the updates that gather the Gaussian rows themselves.  When the Gaussian
     // message can be formed on chip for every class count (the tile vertex sets fit at LP = 8), it is not built here: a
     // call that still wants it (WSC_OPT_CRF_GAUSS_ON_CHIP = 0) builds it on first use (crf_full_records).
@@ -3368,8 +3380,8 @@ void wsc_crf_destroy(wsc_crf *crf) {
     // The blocks go back to the build ctx's stream-ordered cache.  A mean-field loop enqueued on ANOTHER ctx may still
     // be reading them: make the build stream wait for it before anything it launches later can reuse the memory.
     if (crf->used_elsewhere && crf->use_ev) (void)hipStreamWaitEvent(crf->ctx->stream, crf->use_ev, 0);
-    if (crf->gauss_entry) static_cast<GaussCache *>(crf->gauss_entry)->users -= 1;
-    for (void *p : crf->allocs) wsc_ctx_cached_free(crf->ctx, p); // reused in stream order
+    if (crf->gauss) crf->gauss->users -= 1;
+    crf->blocks.release(); // reused in stream order
     if (crf->use_ev) (void)hipEventDestroy(crf->use_ev);
     delete crf;
 }
@@ -3459,36 +3471,15 @@ static int crf_inference_impl(wsc_ctx *ctx, wsc_crf *crf, const float *unary_dev
         WSC_HIP(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
         WSC_HIP(hipEventCreateWithFlags(&ctx->aux_done_ev, hipEventDisableTiming));
     }
-    UpdateArgs a;
-    a.pix_rec = crf->pix_rec; a.pix_rec_b = crf->pix_rec_b; a.val_g = nullptr; a.val_b = nullptr;
-    a.u = u; a.q = nullptr; a.argmax = nullptr;
-    a.alpha_g = G.alpha; a.alpha_b = Bl.alpha; a.compat_g = g_compat; a.compat_b = bi_compat;
-    a.M = M; a.LP = LP; a.B = B;
-    a.tg = make_geom(crf->H, crf->W);
-    a.g_pix = (unsigned)G.n_pix; a.g_rows = G.rep > 1 ? (unsigned)G.rows : 0u;
-    a.sg.tslot_start = G.tslot_start; a.sg.slot_desc = G.slot_desc; a.sg.tent_w = G.tent_w; a.sg.tent_p = G.tent_p; a.sg.part = partg;
-    a.sg.n_slots = G.n_slots; a.sg.shared = G.rep > 1 ? 1 : 0; a.sg.dp1 = 3;
-    a.sb.tslot_start = Bl.tslot_start; a.sb.slot_desc = Bl.slot_desc; a.sb.tent_w = Bl.tent_w; a.sb.tent_p = Bl.tent_p; a.sb.part = partb;
-    a.sb.n_slots = Bl.n_slots; a.sb.shared = 0; a.sb.dp1 = 6;
     // Gaussian message on chip (tile vertex sets that fit the LDS): no Gaussian value rows, no Gaussian blur launch --
     // gauss_msg_kernel turns the Gaussian slot partials into E = -U + message (in the Q buffer: an update reads its slot of
     // E before it writes Q there) beside the bilateral lattice's combine + six passes, and the update starts from E
     const bool gf = update_gf_ok(ctx, G, LP);
     const bool fg = gf && update_fg_ok(ctx, G, LP) && update_fg_lds_limit(ctx, LP, G.gt_stride) == WSC_OK;
-    a.gt_cnt = G.gt_cnt; a.gt_rows = G.gt_rows; a.gt_nbr = G.gt_nbr; a.gt_pix = G.gt_pix; a.gt_stride = G.gt_stride;
-    a.part_g_in = nullptr;
-    if (gf && n_iters > 0) { // (built by wsc_crf_create whenever the lattice has its tile vertex sets; here for completeness)
-        WSC_TRY(crf_bilateral_records(crf, ctx->stream));
-        a.pix_rec_b = crf->pix_rec_b;
-    }
-    if (!gf && n_iters > 0) {
-        WSC_TRY(crf_full_records(crf, ctx->stream));
-        a.pix_rec = crf->pix_rec;
-    }
-    GaussMsgArgs gm;
-    gm.gt_cnt = G.gt_cnt; gm.gt_rows = G.gt_rows; gm.gt_nbr = G.gt_nbr; gm.gt_pix = G.gt_pix; gm.part = partg; gm.u = u; gm.e = q;
-    gm.gt_stride = G.gt_stride; gm.n_slots = G.n_slots; gm.shared = G.rep > 1 ? 1 : 0; gm.LP = LP; gm.B = B;
-    gm.cag = g_compat * G.alpha; gm.tg = a.tg;
+    // (the 52-byte records are built by wsc_crf_create whenever the lattice has its tile vertex sets; here for completeness)
+    if (n_iters > 0) WSC_TRY(gf ? crf_bilateral_records(crf, ctx->stream) : crf_full_records(crf, ctx->stream));
+    UpdateArgs a = update_args(crf, M, g_compat, bi_compat, u, partg, partb);
+    const GaussMsgArgs gm = gauss_msg_args(crf, M, g_compat, partg, u, q);
     // SURVEY 8d terms of the Gaussian kernel this launch covers: the blur (2 (d+1) V M 4) and the slice (index + weight of the
     // 3 vertices per pixel, the message N M 4)
     const double gf_bytes = 2.0 * 3.0 * (double)(G.rows - 1) * G.rep * M * 4 + (double)npix * (3 * 8 + 1.0 * M * 4);
