@@ -33,6 +33,16 @@ SHAPES = [
     (1, 512, 9, 9, 512, 3, 1, 1),     # deep 3x3
     (2, 2048, 5, 5, 512, 1, 1, 0),    # K = 2048
     (5, 128, 7, 9, 136, 1, 1, 0),     # Cout not a multiple of the tile (136 -> pad 256), ragged M
+    # kernel instantiations no other shape reaches (conv_igemm.hip select_variant):
+    (2, 3, 33, 33, 128, 7, 1, 3),     # 7x7 small-Cin on 128-column tiles; odd stride: f16x3 in three segments too
+    (2, 3, 21, 21, 64, 7, 1, 3),      # ... and the latter on 64-column tiles
+    (2, 3, 33, 37, 128, 3, 1, 1),     # 3x3 small-Cin on 128-column tiles
+    (1, 3, 20, 20, 136, 7, 2, 3),     # small-Cin layers with a partial column tile (no FAST epilogue): 7x7, 128 columns
+    (1, 3, 20, 20, 136, 3, 1, 1),     # ... 3x3, 128 columns
+    (2, 3, 20, 20, 40, 3, 1, 1),      # ... 3x3, 64 columns
+    (2, 64, 16, 16, 64, 1, 2, 0),     # one K-step, strided: FAST epilogue without the pointwise prologue, 64 columns
+    (2, 64, 16, 16, 128, 1, 2, 0),    # ... 128 columns
+    (3, 512, 64, 64, 1024, 1, 1, 0),  # 1x1 on the 256 x 256 tile (192 tiles): bf16, and the pointwise prologue of f16 / f16x3
 ]
 
 
@@ -169,7 +179,8 @@ def test_conv_square_tile_large_layer(ctx, precision):
 
 @pytest.mark.parametrize("shape", [(2, 3, 65, 65, 64, 7, 2, 3), (3, 64, 21, 23, 256, 1, 1, 0), (2, 256, 17, 17, 64, 1, 1, 0),
                                    (2, 64, 19, 19, 64, 3, 1, 1), (2, 128, 21, 21, 128, 3, 2, 1), (2, 256, 16, 16, 512, 1, 2, 0),
-                                   (3, 512, 13, 11, 512, 3, 1, 1), (2, 1024, 9, 9, 256, 1, 1, 0)])
+                                   (3, 512, 13, 11, 512, 3, 1, 1), (2, 1024, 9, 9, 256, 1, 1, 0),
+                                   (3, 512, 64, 64, 1024, 1, 1, 0)])  # (the last: f16's generic epilogue on the 256 x 256 tile)
 @pytest.mark.parametrize("precision", [_lib.PREC_F16, _lib.PREC_F16X3])
 def test_conv_fast_variants_equal_generic_path(ctx, shape, precision):
     """The FAST kernel variants (case-free epilogue with ReLU + saturation as one median, pointwise prologue, one-K-step

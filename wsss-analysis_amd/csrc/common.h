@@ -215,24 +215,95 @@ int wsc_ctx_upload_small(wsc_ctx *ctx, void *dst_dev, const void *src_host, size
 int wsc_set_max_dynamic_lds(wsc_ctx *ctx, const void *fn, int bytes);
 
 // ---- conv (implicit GEMM) -----------------------------------------------------------
-// One conv layer as the kernel sees it.  Activations are NHWC bf16; in split
-// precision every activation has a second ("lo") plane.
+// A wsc_precision as the kernels see it: the 16-bit format of both planes, and what the second ("lo") plane does
+inline int conv_fmt(wsc_precision prec) { return (prec == WSC_PREC_F16 || prec == WSC_PREC_F16X3) ? 1 : 0; } // 0 bf16, 1 IEEE half
+// 0: one plane; 1: bf16x3 (three K segments); 2: f16x3 (hi + lo staged once per K-step where the layer is LDS-DMA staged)
+inline int conv_split(wsc_precision prec) { return prec == WSC_PREC_BF16X3 ? 1 : (prec == WSC_PREC_F16X3 ? 2 : 0); }
+
+// How a layer's input reaches the kernel
+enum ConvForm {
+    CONV_FORM_GENERIC = 0, // [N][H][W][Cin], Cin % 64 == 0: LDS-DMA staging, a K-step = one tap of one channel chunk
+    CONV_FORM_SMALL2,      // Cin <= 4 as NHWC4, register staging: a kernel row = 2 slots of (2 pixels x 4 channels) (3 x 3 first conv)
+    CONV_FORM_SMALL4,      // the same with 4 slots per kernel row (7 x 7 stem)
+    CONV_FORM_STEM_ROWS    // f16x3 stem on a zero-PADDED NHWC4 input (H, W = the padded size, pad = 0): the 8-pixel x 4-channel window
+                           // of kernel row r of an output pixel is 32 contiguous elements of either plane, 16-byte aligned (even
+                           // stride: the window starts at an even pixel), so a K-step = one kernel row = 32 hi + 32 lo values and the
+                           // layer is an LDS-DMA layer of kh K-steps with no bounds tests (the padding is in the buffer)
+};
+inline bool conv_form_dma(ConvForm f) { return f == CONV_FORM_GENERIC || f == CONV_FORM_STEM_ROWS; }
+
+// K layout of a layer's packed weights [CoutPad][Kw] (16-bit) and of the kernel's K loop: THE description both the packing
+// (net.hip make_conv) and the launch (conv_igemm.hip) read.  A K-step is 64 weight elements per output channel.
+//   generic: K order (cin / ck, kh, kw, cin % ck) -- the kh * kw taps of one channel chunk are consecutive K-steps, so the
+//            activation lines a block gathers are re-touched within a few K-steps (L2 hits) instead of Cin / ck steps later
+//   small-Cin forms: kernel row r owns `slots` 8-element slots of (2 pixels x 4 channels), 8 slots per K-step
+//   stem rows: K-step r = kernel row r, 8 pixels x 4 channels (pixel 7 and channel 3: zero weights)
+// Two planes: interleaved (f16x3, LDS-DMA layers) = every K-step holds [32 hi | 32 lo] of a 32-channel chunk and the K loop
+// runs once; else [hi K | lo K] and the K loop runs three segments hi*hi, lo*hi, hi*lo.
+struct ConvKLayout {
+    ConvForm form;
+    int kh, kw;       // the layer's kernel
+    int kw_steps;     // kernel columns the K loop walks per row (kw; 1 where a K-step is a whole kernel row)
+    int ck;           // channels of a generic layer's K-step (64; 32 interleaved)
+    bool interleaved;
+    int cchunks;      // channel chunks of ck (1 in the 4-channel forms)
+    int ksteps_base;  // K-steps of one precision segment
+    int Kbase;        // elements of one segment per weight row
+    int Kw;           // weight row length in elements
+    int nk;           // K-steps of the whole K loop
+    int lo_at;        // the lo part of the weight at element k sits at k + lo_at
+    // element of weight (ci, r, s) (hi part) in its row
+    int index(int ci, int r, int s) const {
+        if (form == CONV_FORM_STEM_ROWS) return r * 64 + s * 4 + ci;
+        if (form == CONV_FORM_GENERIC) return (((ci / ck) * kh + r) * kw + s) * 64 + ci % ck;
+        return r * (form == CONV_FORM_SMALL2 ? 2 : 4) * 8 + s * 4 + ci;
+    }
+};
+// Cin: the activation's channel count (a multiple of 64, or 4 in the NHWC4 forms)
+inline ConvKLayout conv_k_layout(int kh, int kw, int Cin, ConvForm form, wsc_precision prec) {
+    ConvKLayout L;
+    const int split = conv_split(prec);
+    L.form = form; L.kh = kh; L.kw = kw;
+    L.interleaved = split == 2 && conv_form_dma(form);
+    L.ck = L.interleaved ? 32 : 64;
+    L.kw_steps = form == CONV_FORM_STEM_ROWS ? 1 : kw;
+    L.cchunks = form == CONV_FORM_GENERIC ? Cin / L.ck : 1;
+    if (form == CONV_FORM_GENERIC) L.ksteps_base = kh * kw * L.cchunks;
+    else if (form == CONV_FORM_STEM_ROWS) L.ksteps_base = kh;
+    else L.ksteps_base = (kh * (form == CONV_FORM_SMALL2 ? 2 : 4) + 7) / 8;
+    L.Kbase = L.ksteps_base * 64;
+    const bool segments = split != 0 && !L.interleaved;
+    L.Kw = L.Kbase * (segments ? 2 : 1);
+    L.nk = L.ksteps_base * (segments ? 3 : 1);
+    L.lo_at = L.interleaved ? 32 : L.Kbase;
+    return L;
+}
+// rows of the packed weights (and of scale / shift): whole 64-column tiles up to 64 channels, whole 128-column tiles beyond
+inline int conv_cout_pad(int Cout) { return Cout <= 64 ? 64 : ((Cout + 127) / 128) * 128; }
+// ... and the tile width the kernel takes for them
+inline int conv_tile_bn(int CoutPad) { return CoutPad % 128 == 0 ? 128 : 64; }
+// size of the zero-padded input of a CONV_FORM_STEM_ROWS layer: the rows the kernel rows of the last output pixel reach, an
+// 8-pixel window per kernel row
+inline void conv_stem_rows_input_dims(int Ho, int Wo, int stride, int kh, int *Hp, int *Wp) {
+    *Hp = (Ho - 1) * stride + kh;
+    *Wp = (Wo - 1) * stride + 8;
+}
+
+// One conv layer as the kernel sees it.  Activations are NHWC 16-bit; in the two-plane precisions every activation has a
+// second ("lo") plane of the same format.
 struct ConvLaunch {
-    const bf16_t *x, *x_lo;     // input  [N][H][W][Cin]   (Cin = 4 in small-Cin mode)
-    const bf16_t *w;            // packed [CoutPad][Kw] 16-bit, K order (cin/64, kh, kw, cin%64); split 1 (and the small-Cin layers of
-                                // split 2): [hi K | lo K]; split 2 generic: K order (cin/32, kh, kw) x [32 hi | 32 lo]
+    const bf16_t *x, *x_lo;     // input  [N][H][W][Cin]   (Cin = 4 in the NHWC4 forms)
+    const bf16_t *w;            // packed [CoutPad][Kw]: conv_k_layout(kh, kw, Cin, form, prec)
     const float *s1, *b1;       // y = acc*s1 + b1 (folded BN, or conv bias with s1 = 1)
     const float *s2, *b2;       // optional post-ReLU affine (VGG's conv->ReLU->BN order), or null
     const bf16_t *res, *res_lo; // optional residual [M][Cout]
-    bf16_t *y, *y_lo;           // output [M][Cout] bf16 (may be null when y_f32 is set)
+    bf16_t *y, *y_lo;           // output [M][Cout] 16-bit (may be null when y_f32 is set)
     float *y_f32;               // optional fp32 output [M][Cout]
     int N, H, W, Cin, Ho, Wo, Cout, CoutPad;
     int kh, kw, stride, pad;
     int relu;
-    int small_cin; // 0: generic (Cin % 64 == 0); else log2(slots per kernel row): 2 = 7x7 stem, 1 = 3x3 Cin<=4;
-                   // 3: f16x3 stem on a zero-padded NHWC4 input (H, W = the padded size, pad = 0; conv_igemm.hip)
-    int split;     // 0: one plane; 1: bf16x3 (three K segments); 2: f16x3 (hi + lo staged once per K-step).  The lo plane has the hi plane's format
-    int fmt;       // 16-bit operand format: 0 bf16, 1 f16 (split 1 requires bf16, split 2 f16)
+    ConvForm form;
+    wsc_precision prec;
     int generic;   // 1: keep the generic kernel variants (testing: the FAST variants give the same bits)
     int ldy;       // row pitch of y / y_lo in elements; 0 = Cout (wider: the output is a channel range of a concatenated tensor)
     // optional second input of a 1x1 / stride 1 layer: the last C2 of the Cin input channels of output pixel (n, ho, wo) come from

@@ -7,26 +7,34 @@
 // vgg16_cam.py:48).
 //
 // GEMM view:  M = N*Ho*Wo output pixels, N = Cout, K = kh*kw*Cin.
-//   A[m][k]  gathered on the fly from the NHWC bf16 activation (zero padding by predicate)
-//   B[n][k]  packed weights, K contiguous
+//   A[m][k]  gathered on the fly from the NHWC 16-bit activation (zero padding by predicate)
+//   B[n][k]  packed weights, K contiguous, in the order of ConvKLayout (common.h) -- the one description of the K loop
 //   C        fp32 accumulators in registers (v_mfma_f32_32x32x16_bf16 / _f16)
-// Block tile 128 x BN x 64, 4 waves (2x2), each wave 64 x BN/2 as 32x32 MFMA tiles.
-// LDS tiles are [row][64 k] bf16 (128 B rows) with the 16-byte slot XOR-swizzled by
-// (row>>1)&7 so both the ds_write_b128 staging stores and the ds_read_b128 fragment
-// loads are bank-conflict free.  Staging is double-buffered, one barrier per K-step, one K-step
-// ahead: generic layers use the LDS DMA (global_load_lds_dwordx4: no staging VGPRs, no
-// ds_write pass -- the ds_write_b128 path tops out at ~79 B/clk/CU and together with the fragment
-// reads made the first version of this kernel LDS-bound at ~300 TFLOP/s); the swizzle is applied
-// to the per-lane SOURCE address because a DMA's LDS destination is lane-linear, and padded taps
-// read a zero page.  The small-Cin layers (stem) keep global -> register -> LDS staging.
-// Epilogue: accumulators go through LDS as an fp32 tile so that each thread owns 8
-// consecutive channels of one pixel: folded-BN scale/shift, residual add, ReLU,
-// optional post-ReLU affine, then one 16-byte coalesced store.
+// One kernel template, conv_igemm_kernel; what is instantiated and which layer gets what is select_variant, the tile policy
+// is conv_igemm_launch (both at the end of the file).  The paths, each described where it is implemented:
 //
-// Split precision (bf16x3): activations and weights carry a second bf16 plane with the
-// rounding remainder; the K loop runs three segments (x_hi*w_hi, x_lo*w_hi, x_hi*w_lo)
-// into the same accumulators, giving ~2^-16 relative operand error with the same
-// MFMA instruction.
+// Tile and LDS.  Block tile BM x BN x 64: 128 x 64 or 128 x 128 with 4 waves (2 x 2) and two blocks per CU, or 256 x 256 with
+// 8 waves of 128 x 64 and one block per CU (half the L2 -> LDS bytes per FLOP; layers with enough K-steps and tiles).  LDS
+// tiles are [row][64 k] (128 B rows) with the 16-byte slot XOR-swizzled by (row>>1)&7, so staging stores and ds_read_b128
+// fragment loads are bank-conflict free.  Two LDS buffers, one barrier per K-step, one K-step ahead; a one-K-step layer of
+// one plane takes ONE buffer (34 KB, four blocks per CU).
+//
+// LDS-DMA staging (generic layers, Cin % 64 == 0, and the padded-input stem rows): global_load_lds_dwordx4, no staging
+// VGPRs and no ds_write pass; the swizzle is applied to the per-lane SOURCE address because a DMA's LDS destination is
+// lane-linear, and padded taps read a zero page.  A 1 x 1 layer may take its last channels from a SECOND A source (a ResNet
+// stage's first block: conv3 and the projection shortcut as one GEMM).
+// Register staging (the small-Cin forms: first layers on an NHWC4 input): global -> register -> LDS.
+//
+// Precisions.  bf16 / f16: one plane.  bf16x3 (and the small-Cin layers of f16x3): a second plane holds the rounding
+// remainder and the K loop runs three segments x_hi*w_hi, x_lo*w_hi, x_hi*w_lo into the same accumulators, each staging its
+// own tiles.  f16x3 on LDS-DMA layers -- the shipped mode: both planes are staged ONCE, a K-step is one tap of a 32-channel
+// chunk as [32 hi | 32 lo], and feeds 2 k-slices x 3 MFMA products (SPLIT 2 below).  Its 3 x 3 / stride 1 / pad 1 layers
+// stage the A operand of all nine taps as one LDS WINDOW of the input raster per chunk (WPT below).
+//
+// Epilogue: accumulators go through LDS as an fp32 tile so that each thread owns 8 consecutive channels of one pixel:
+// folded-BN scale/shift, residual add, ReLU, optional post-ReLU affine, then one 16-byte coalesced store (both planes in
+// the two-plane modes).  The FAST variants (IEEE half, full column tiles) drop the per-element case handling; the
+// IEEE-half epilogues raise the ctx's range flag when a stored value sits at the half ceiling.
 #include "common.h"
 
 #include <type_traits>
@@ -43,21 +51,22 @@ struct ConvKArgs {
     float *y_f32;
     int H, W, Cin, Ho, Wo, Cout;
     int ldy;            // row pitch of y / y_lo in elements (Cout, or wider: the output is a channel range of a concatenated tensor)
-    int kh, kw, stride, pad, relu;
+    int kh, kw, stride, pad, relu; // (kw: kernel columns the K loop walks, ConvKLayout::kw_steps)
     int M, HoWo;
     int m_base, m_end; // rows [m_base, m_end) of the M = N*Ho*Wo output rows are this launch's (a layer may be cut in two)
     // exact unsigned division by HoWo / Wo as multiply-high + shifts (Granlund-Montgomery): the prologue
     // decodes 4 output rows per thread and a hardware-less 32-bit division costs ~25 VALU instructions
     unsigned div_howo_mul, div_howo_s1, div_howo_s2, div_wo_mul, div_wo_s1, div_wo_s2;
-    int cchunks;     // Cin / 64 (generic mode)
-    int ntaps;       // kh * kw
+    // the K layout, ConvKLayout (common.h):
+    int cchunks;     // channel chunks of one K-step's channels
+    int spare0;
     int ksteps_base; // K-steps of one precision segment
-    int nk;          // total K-steps (x3 in split mode)
+    int nk;          // total K-steps
     int Kw;          // packed weight row length in elements
-    int Kbase;       // elements of one weight plane per row
+    int Kbase;       // elements of one segment per weight row
     int ntiles_n, nblocks;
     const bf16_t *zero; // >= 16 bytes of zeros in HBM: source of padded taps for the LDS-DMA path
-    int fast;           // host side only: FAST variant of the kernel this launch may use (0 = generic)
+    int spare1;
     long long lo_delta; // SPLIT 2: x_lo - x in elements (both planes live in one workspace block)
     // second A source of a 1 x 1 layer (a ResNet stage's first block: conv3 and the projection shortcut as one GEMM, net.hip):
     // channel chunks [0, cc2) come from x (dense [M][ldx]), chunks [cc2, cchunks) from x2 = [N][H2][W2][C2] at pixel
@@ -69,8 +78,10 @@ struct ConvKArgs {
     // LDS input window of a 3 x 3 / stride 1 / pad 1 layer (WPT > 0 variants): positions of the input raster [N][H][W]
     // starting at index (first output pixel of the block) - W - 1; win_npix = N H W (pieces outside the tensor load zeros)
     int win_npix;
-    int stem_rows;      // host side only: the padded-input stem form (a K-step = one kernel row of 8 pixels x 4 channels)
-    int kw_real;        // host side only: kernel width of the layer (FLOP accounting; kw is 1 in the stem form)
+    // spare0-3: read by nobody.  They hold the places of four values that only the host used to carry here; taking them out
+    // moves the other arguments, and the compiler then merges the kernels' scalar argument loads differently and allocates
+    // other registers in 4 to 25 of the instantiations (seven layouts tried) -- the kernels are kept as they were instead.
+    int spare2, spare3;
     unsigned *range;    // the ctx's range flag (common.h): raised by an IEEE-half epilogue that stores a value at the half ceiling
 };
 
@@ -78,9 +89,19 @@ __device__ __forceinline__ int lds_off(int row, int slot) {
     return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
 }
 
+// output row m = (n * Ho + ho) * Wo + wo, by the multiply-high divisions of ConvKArgs
+__device__ __forceinline__ void decode_row(const ConvKArgs &p, int m, int &n, int &ho, int &wo) {
+    const unsigned t1 = __umulhi(p.div_howo_mul, (unsigned)m);
+    n = (int)((t1 + (((unsigned)m - t1) >> p.div_howo_s1)) >> p.div_howo_s2);
+    const int rem = m - n * p.HoWo;
+    const unsigned t2 = __umulhi(p.div_wo_mul, (unsigned)rem);
+    ho = (int)((t2 + (((unsigned)rem - t2) >> p.div_wo_s1)) >> p.div_wo_s2);
+    wo = rem - ho * p.Wo;
+}
+
 // BM x BN x 64 tile, BM/32 waves (BM/64 along M x 2 along N, 64 x BN/2 per wave), STAGES LDS buffers.
 //   128-row tile: 4 waves, 2 stages, 2 blocks per CU.
-//   256 x 256 tile: 8 waves of 128 x 64 (WMT = 128), 2 stages, 1 block per CU.
+//   256 x 256 tile: 8 waves of 128 x 64, 2 stages, 1 block per CU.
 //
 // FAST (f16, single precision plane, LDS-DMA layers only) removes per-element case handling the common layers do not need:
 //   bit 0  epilogue: fp16 output only, every column tile full (Cout % BN == 0), 32-bit output
@@ -102,35 +123,38 @@ __device__ __forceinline__ int lds_off(int row, int slot) {
 // so the block's 128 consecutive output pixels read, for tap (r, s), the window positions (m - m0) + r W + s of the window that
 // starts at raster index m0 - W - 1 -- staged once per chunk (WPT x 32 positions x [32 hi | 32 lo], same 128-byte rows and XOR
 // swizzle as an A tile, so the fragment reads only change their base address per tap) instead of nine per-tap A tiles: 2.7-5.6x
-// fewer A bytes through L2 -> LDS.  Round 6: the raster is NOT padded.  Where a tap leaves the image (left / right column, top /
+// fewer A bytes through L2 -> LDS.  The raster is NOT padded.  Where a tap leaves the image (left / right column, top /
 // bottom row) the position holds the neighbouring row's or image's pixel, and the lane reads the window's ZERO ROW instead (a
 // 9-bit per-lane tap mask decided once; one v_cndmask per fragment address).  The positions of 32 consecutive output pixels are
-// then consecutive for every tap, which is what the swizzle needs to be conflict-free: round 5's zero-padded raster jumped by
-// two positions at a row's end and lost 21-30 % of its LDS cycles to bank conflicts there.  It is also smaller: 127 + 2 W + 4
+// then consecutive for every tap, which is what the swizzle needs to be conflict-free: a zero-padded raster jumps by
+// two positions at a row's end and loses 21-30 % of its LDS cycles to bank conflicts there.  It is also smaller: 127 + 2 W + 4
 // positions (21 x 21: 173, 41 x 41: 213, 81 x 81: 293) against 236 / 312 / 468.  The next chunk's
 // window travels in registers (WPT 16-byte loads per thread, issued at the chunk's first tap) and is written to LDS between
 // the chunk's last tap and the next one's first; the weight tiles keep their per-K-step LDS-DMA double buffer.  Same MFMA
 // sequence on the same operands as the per-tap kernel: bit-identical results (tests/test_gpu_conv.py).
-template <int BM, int BN, int MODE, int SPLIT, int ET, bool GLDS, int STAGES, int WMT = 64, int FAST = 0, int WPT = 0>
+template <int BM, int BN, int MODE, int SPLIT, int ET, int STAGES, int FAST = 0, int WPT = 0>
 __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void conv_igemm_kernel(ConvKArgs p) {
+    constexpr bool GLDS = MODE == 0;          // LDS-DMA staging; the small-Cin forms (MODE 1, 2) stage through registers
+    constexpr int WMT = BM == 256 ? 128 : 64; // rows of a wave's tile
     constexpr bool FEPI = (FAST & 1) != 0, PW = (FAST & 2) != 0;
     constexpr bool WIN = WPT > 0;
-    static_assert(!WIN || (SPLIT == 2 && BM == 128 && WMT == 64 && STAGES == 2 && FAST == 1), "LDS window: single-staged split, 128-row tile");
-    static_assert(FAST == 0 || (SPLIT != 1 && ET == 1 && ((GLDS && MODE == 0) || FAST == 1)),
+    static_assert(!WIN || (SPLIT == 2 && BM == 128 && STAGES == 2 && FAST == 1), "LDS window: single-staged split, 128-row tile");
+    static_assert(FAST == 0 || (SPLIT != 1 && ET == 1 && (MODE == 0 || FAST == 1)),
                   "FAST paths: f16, one plane or the single-staged split; the pointwise prologue belongs to the LDS-DMA layers");
-    static_assert(SPLIT != 2 || (GLDS && MODE == 0 && STAGES == 2), "single-staged split: LDS-DMA layers, two LDS buffers");
+    static_assert(SPLIT != 2 || (MODE == 0 && STAGES == 2), "single-staged split: LDS-DMA layers, two LDS buffers");
+    static_assert(STAGES == 2 || SPLIT == 0, "one LDS buffer serves a one-K-step layer, which a layer of three K segments never is");
     constexpr int CK = SPLIT == 2 ? 32 : 64; // channels of one K-step
     constexpr int NT = BM * 2;   // threads
     constexpr int NW = BM / 32;  // waves
     // waves are laid out WR (along M) x WC (along N); a wave owns a WMT x WN tile = MI x NI MFMA tiles.
-    // WMT = 64 (default): WC = 2, 64 x BN/2 per wave.  WMT = 128 with a 256 x 256 block: 2 x 4 waves of 128 x 64 --
+    // WMT = 64 (128-row block): WC = 2, 64 x BN/2 per wave.  WMT = 128 (256 x 256 block): 2 x 4 waves of 128 x 64 --
     // half the LDS-DMA bytes per FLOP of the 128 x 128 block and 0.75x the fragment reads per MFMA.
     constexpr int WR = BM / WMT;
     constexpr int WC = NW / WR;
     constexpr int WN = BN / WC;
     constexpr int MI = WMT / 32;
     constexpr int NI = WN / 32;
-    static_assert(WR * WC == NW && WN % 32 == 0 && (WMT == 64 || WMT == 128), "wave layout");
+    static_assert(WR * WC == NW && WN % 32 == 0, "wave layout");
     constexpr int NB = BN * 8 / NT; // B 16-byte slots per thread per K-step
     constexpr int A_BYTES = BM * BK * 2;
     constexpr int B_BYTES = BN * BK * 2;
@@ -181,12 +205,8 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
             wb[i] = 0;
             base[i] = (long long)mc * p.ldx;
         } else if (m < p.m_end) {
-            const unsigned t1 = __umulhi(p.div_howo_mul, (unsigned)m);
-            const int n = (int)((t1 + (((unsigned)m - t1) >> p.div_howo_s1)) >> p.div_howo_s2);
-            const int rem = m - n * p.HoWo;
-            const unsigned t2 = __umulhi(p.div_wo_mul, (unsigned)rem);
-            const int ho = (int)((t2 + (((unsigned)rem - t2) >> p.div_wo_s1)) >> p.div_wo_s2);
-            const int wo = rem - ho * p.Wo;
+            int n, ho, wo;
+            decode_row(p, m, n, ho, wo);
             hb[i] = ho * p.stride - p.pad;
             wb[i] = wo * p.stride - p.pad;
             base[i] = (((long long)n * p.H + hb[i]) * p.W + wb[i]) * (long long)p.ldx;
@@ -226,34 +246,20 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
             ktl = kt - seg * p.ksteps_base;
         }
         const bf16_t *src = (SPLIT && seg == 1) ? p.x_lo : p.x;
-        if (MODE == 0) {
-            const int cc = ktl / p.ntaps;
-            const int tap = ktl - cc * p.ntaps;
-            const int khi = tap / p.kw;
-            const int kwi = tap - khi * p.kw;
-            const long long tap_off = ((long long)khi * p.W + kwi) * p.ldx + cc * 64 + slot * 8;
+        // (register staging is the small-Cin forms': the LDS-DMA layers never come here)  The activation is [N][H][W][4]; one
+        // kernel row = 2^MODE slots of 2 pixels (8 bf16) each; weights are packed to match, zero in the padding.
+        const int g = ktl * 8 + slot;
+        const int khi = g >> MODE;
+        const int px = (g & ((1 << MODE) - 1)) * 2;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int hi = hb[i] + khi, wi = wb[i] + kwi;
-                const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-                ra[i] = ok ? *reinterpret_cast<const u32x4_t *>(src + base[i] + tap_off) : u32x4_t{0u, 0u, 0u, 0u};
-            }
-        } else {
-            // small-Cin mode: activation is [N][H][W][4]; one kernel row = 2^MODE slots of
-            // 2 pixels (8 bf16) each; weights are packed to match, zero in the padding.
-            const int g = ktl * 8 + slot;
-            const int khi = g >> MODE;
-            const int px = (g & ((1 << MODE) - 1)) * 2;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int hi = hb[i] + khi, wi = wb[i] + px;
-                const bool okh = khi < p.kh && (unsigned)hi < (unsigned)p.H;
-                const uint2 *q = reinterpret_cast<const uint2 *>(src + base[i] + ((long long)khi * p.W + px) * 4);
-                uint2 v0 = make_uint2(0, 0), v1 = make_uint2(0, 0);
-                if (okh && (unsigned)wi < (unsigned)p.W) v0 = q[0];
-                if (okh && (unsigned)(wi + 1) < (unsigned)p.W) v1 = q[1];
-                ra[i] = u32x4_t{v0.x, v0.y, v1.x, v1.y};
-            }
+        for (int i = 0; i < 4; ++i) {
+            const int hi = hb[i] + khi, wi = wb[i] + px;
+            const bool okh = khi < p.kh && (unsigned)hi < (unsigned)p.H;
+            const uint2 *q = reinterpret_cast<const uint2 *>(src + base[i] + ((long long)khi * p.W + px) * 4);
+            uint2 v0 = make_uint2(0, 0), v1 = make_uint2(0, 0);
+            if (okh && (unsigned)wi < (unsigned)p.W) v0 = q[0];
+            if (okh && (unsigned)(wi + 1) < (unsigned)p.W) v1 = q[1];
+            ra[i] = u32x4_t{v0.x, v0.y, v1.x, v1.y};
         }
         const int wk = ((SPLIT && seg == 2) ? p.Kbase : 0) + ktl * 64;
 #pragma unroll
@@ -320,7 +326,7 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
 
     // ---- main loop ------------------------------------------------------------------
     const int nk = STAGES == 1 ? 1 : p.nk; // (the single-buffer variant is launched for one-K-step layers only)
-    if (GLDS && MODE == 0) {
+    if (GLDS) {
         // Two LDS buffers.  The 4 + NB LDS-DMA pieces of K-step kt+1 are issued at the top of K-step kt, before its
         // fragment reads and MFMAs (interleaving one piece after every 1 ... 4 MFMAs was measured: no layer gained,
         // profiles/README.md).  The (segment, tap, channel-chunk) decode of the next K-step is carried incrementally in
@@ -347,13 +353,8 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int m = m0 + lrow + RSTEP * i;
-                const unsigned mc = (unsigned)(m < p.m_end ? m : p.m_end - 1);
-                const unsigned t1 = __umulhi(p.div_howo_mul, mc);
-                const int n = (int)((t1 + ((mc - t1) >> p.div_howo_s1)) >> p.div_howo_s2);
-                const int rem = (int)mc - n * p.HoWo;
-                const unsigned t2 = __umulhi(p.div_wo_mul, (unsigned)rem);
-                const int ho = (int)((t2 + (((unsigned)rem - t2) >> p.div_wo_s1)) >> p.div_wo_s2);
-                const int wo = rem - ho * p.Wo;
+                int n, ho, wo;
+                decode_row(p, m < p.m_end ? m : p.m_end - 1, n, ho, wo);
                 const long long b2 = (((long long)n * p.H2 + ho * p.stride2) * p.W2 + wo * p.stride2) * (long long)p.C2;
                 const int r = lrow + RSTEP * i;
                 const int ks = slot ^ ((r >> 1) & 7);
@@ -420,12 +421,8 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
             for (int mi = 0; mi < MI; ++mi) {
                 const int mr = m0 + wm * WMT + mi * 32 + l31;
                 const int m = mr < p.m_end ? mr : p.m_end - 1; // (rows past the end: a valid position, results never stored)
-                const unsigned t1 = __umulhi(p.div_howo_mul, (unsigned)m);
-                const int n = (int)((t1 + (((unsigned)m - t1) >> p.div_howo_s1)) >> p.div_howo_s2);
-                const int rem = m - n * p.HoWo;
-                const unsigned t2 = __umulhi(p.div_wo_mul, (unsigned)rem);
-                const int ho = (int)((t2 + (((unsigned)rem - t2) >> p.div_wo_s1)) >> p.div_wo_s2);
-                const int wo = rem - ho * p.Wo;
+                int n, ho, wo;
+                decode_row(p, m, n, ho, wo);
                 qm[mi] = m - m0; // window position of the pixel's tap (0, 0)
                 const unsigned left = wo == 0 ? 0x49u : 0u, right = wo == p.W - 1 ? 0x124u : 0u;   // s = 0: bits 0, 3, 6; s = 2: 2, 5, 8
                 const unsigned top = ho == 0 ? 0x7u : 0u, bottom = ho == p.H - 1 ? 0x1c0u : 0u;     // r = 0: bits 0-2; r = 2: bits 6-8
@@ -975,96 +972,92 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
     if (ET && (ovf & 0x80008000u)) *p.range = (unsigned)p.Cout;
 }
 
-template <int BM, int BN, int MODE, int SPLIT, int ET, int STAGES, int WMT = 64, int FAST = 0, int WPT = 0>
-int launch_stages(wsc_ctx *ctx, const ConvKArgs &a) {
-    constexpr bool GLDS = MODE == 0; // LDS-DMA staging for every generic layer; small-Cin layers stage via registers
+// ---- the kernel variants ------------------------------------------------------------------------------------------------
+// One instantiation as the host sees it: its kernel, tile, dynamic LDS and profiler class.
+typedef void (*ConvKernel)(ConvKArgs);
+struct ConvVariant {
+    ConvKernel kernel;
+    int bm, bn; // tile; the block has 2 * bm threads
+    int lds;
+    int cls;    // WscKernelClass
+};
+template <int BM, int BN, int MODE, int SPLIT, int ET, int STAGES, int FAST = 0, int WPT = 0>
+ConvVariant variant() {
     constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
     constexpr int PIPE = WPT > 0 ? WPT * 4096 + STAGES * B_BYTES : STAGES * (A_BYTES + B_BYTES);
     // fp32 transpose: 64-row groups in the single-buffer variant, 128-row groups in the 256 x 256 tile
-    constexpr int EPI = (STAGES == 1 ? 64 : (WMT == 128 ? 128 : BM)) * (BN + 4) * 4;
+    constexpr int EPI = (STAGES == 1 ? 64 : (BM == 256 ? 128 : BM)) * (BN + 4) * 4;
     constexpr int LDS = PIPE > EPI ? PIPE : EPI;
     static_assert(LDS <= 160 * 1024, "LDS budget of a CU");
-    auto kern = conv_igemm_kernel<BM, BN, MODE, SPLIT, ET, GLDS, STAGES, WMT, FAST, WPT>;
-    WSC_TRY(wsc_set_max_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), LDS));
-    // algorithmic FLOPs: 2 * M * Cout * (kh*kw*Cin_real), x1 regardless of the precision mode
-    const double flops = 2.0 * (a.m_end - a.m_base) * a.Cout *
-                         ((MODE == 0 && !a.stem_rows) ? (double)a.kh * a.kw * a.Cin : (double)a.kh * (a.stem_rows ? a.kw_real : a.kw) * 3);
-    WscKernelTimer timer(ctx, (MODE != 0 || a.stem_rows) ? WSC_K_CONV_SMALLCIN : (BM == 256 ? WSC_K_CONV256 : (BN == 128 ? WSC_K_CONV128 : WSC_K_CONV64)), flops);
-    hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(BM * 2), LDS, ctx->stream, a);
-    WSC_HIP(hipGetLastError());
-    return WSC_OK;
+    return {conv_igemm_kernel<BM, BN, MODE, SPLIT, ET, STAGES, FAST, WPT>, BM, BN, LDS,
+            MODE != 0 ? WSC_K_CONV_SMALLCIN : (BM == 256 ? WSC_K_CONV256 : (BN == 128 ? WSC_K_CONV128 : WSC_K_CONV64))};
 }
-
-// 3 x 3 / stride 1 / pad 1 layer of the f16x3 mode on the LDS-window variant (WPT x 32 window positions)
-template <int WPT, int BN = 128>
-int launch_window(wsc_ctx *ctx, const ConvKArgs &a) {
-    return launch_stages<128, BN, 0, 2, 1, 2, 64, 1, WPT>(ctx, a);
+// One precision plane on a 128-row tile: a one-K-step layer (1x1 conv with 64 input channels; 3x3 on <= 4 channels: VGG16 / M7
+// first conv) needs one LDS buffer -- 34 KB per block, 4 blocks per CU, 64-row epilogue groups.  (Two planes never have one
+// K-step: three segments, or 32-channel K-steps.)
+template <int BM, int BN, int MODE, int ET, int FAST = 0>
+ConvVariant one_plane(bool one_kstep) {
+    if constexpr (BM == 128)
+        if (one_kstep) return variant<BM, BN, MODE, 0, ET, 1, FAST>();
+    return variant<BM, BN, MODE, 0, ET, 2, FAST>();
 }
-
-template <int BM, int BN, int MODE, int SPLIT, int ET, int FAST = 0>
-int launch_variant(wsc_ctx *ctx, const ConvKArgs &a) {
-    if constexpr (BM == 256) { // (256 x 256 only)
-        return launch_stages<BM, BN, MODE, SPLIT, ET, 2, 128, FAST>(ctx, a);
-    } else if constexpr (MODE == 0) {
-        // a one-K-step layer (1x1 conv, 64 input channels) needs one LDS buffer: 34 KB per block, 4 blocks per CU
-        // (the single-staged split has 32-channel K-steps: never fewer than two)
-        if constexpr (SPLIT != 2)
-            if (a.nk == 1) return launch_stages<BM, BN, MODE, SPLIT, ET, 1, 64, FAST>(ctx, a);
-        return launch_stages<BM, BN, MODE, SPLIT, ET, 2, 64, FAST>(ctx, a);
-    } else {
-        // one-K-step small-Cin layer (3x3 on <= 4 channels: VGG16 / M7 first conv): single LDS buffer, 64-row epilogue
-        if (a.nk == 1) return launch_stages<BM, BN, MODE, SPLIT, ET, 1, 64, FAST>(ctx, a);
-        return launch_stages<BM, BN, MODE, SPLIT, ET, 2, 64, FAST>(ctx, a);
+// Every instantiation the library holds, and the layers that get it.  Tile BM x BN = 128 x 64, 128 x 128 or 256 x 256 (LDS-DMA
+// layers only); fast = the FAST bits the layer qualifies for (conv_igemm_launch); wpt > 0: the LDS window of that many x 32
+// positions (f16x3, 128-row tile, fast == 1).
+//   LDS-DMA layers (generic, stem rows)      bf16: 1 | 2 buffers            bf16x3: three segments
+//                                            f16:  (1 | 2 buffers) x FAST 0, 1, 3
+//                                            f16x3: single-staged, FAST 0, 1, 3; window 8, 10
+//   small-Cin forms (MODE = log2 slots/row)  bf16: 1 | 2 buffers            bf16x3, f16x3: three segments (of bf16 / half planes)
+//                                            f16:  (1 | 2 buffers) x FAST 0, 1
+template <int BM, int BN>
+ConvVariant select_variant(ConvForm form, wsc_precision prec, int fast, bool one_kstep, int wpt) {
+    if constexpr (BM == 128) { // (register staging exists for the 128-row tile only)
+        auto small = [&](auto mode) {
+            constexpr int MODE = decltype(mode)::value;
+            switch (prec) {
+            case WSC_PREC_BF16: return one_plane<128, BN, MODE, 0>(one_kstep);
+            case WSC_PREC_BF16X3: return variant<128, BN, MODE, 1, 0, 2>();
+            case WSC_PREC_F16: return fast ? one_plane<128, BN, MODE, 1, 1>(one_kstep) : one_plane<128, BN, MODE, 1>(one_kstep);
+            default: return variant<128, BN, MODE, 1, 1, 2>(); // (f16x3)
+            }
+        };
+        if (form == CONV_FORM_SMALL2) return small(std::integral_constant<int, 1>{});
+        if (form == CONV_FORM_SMALL4) return small(std::integral_constant<int, 2>{});
+        if (wpt == 8) return variant<128, BN, 0, 2, 1, 2, 1, 8>();
+        if (wpt == 10) return variant<128, BN, 0, 2, 1, 2, 1, 10>();
     }
-}
-
-// f16 LDS-DMA layer on its FAST variant (fast = 1: epilogue, 3: epilogue + pointwise)
-template <int BM, int BN, int SPLIT = 0>
-int launch_fast(wsc_ctx *ctx, const ConvKArgs &a, int fast) {
-    if (fast == 3) return launch_variant<BM, BN, 0, SPLIT, 1, 3>(ctx, a);
-    return launch_variant<BM, BN, 0, SPLIT, 1, 1>(ctx, a);
-}
-
-template <int BN>
-int launch_bn(wsc_ctx *ctx, const ConvKArgs &a, int small_cin, int split, int fmt) {
-    if (split == 2) { // f16x3: generic layers single-staged, small-Cin layers in three segments on half planes
-        if (small_cin == 0 && a.fast == 3) return launch_variant<128, BN, 0, 2, 1, 3>(ctx, a);
-        if (small_cin == 0 && a.fast) return launch_variant<128, BN, 0, 2, 1, 1>(ctx, a);
-        if (small_cin == 0) return launch_variant<128, BN, 0, 2, 1>(ctx, a);
-        if (small_cin == 1) return launch_variant<128, BN, 1, 1, 1>(ctx, a);
-        return launch_variant<128, BN, 2, 1, 1>(ctx, a);
+    ConvVariant v;
+    switch (prec) {
+    case WSC_PREC_BF16: v = one_plane<BM, BN, 0, 0>(one_kstep); break;
+    case WSC_PREC_BF16X3: v = variant<BM, BN, 0, 1, 0, 2>(); break;
+    case WSC_PREC_F16:
+        v = fast == 3 ? one_plane<BM, BN, 0, 1, 3>(one_kstep) : (fast ? one_plane<BM, BN, 0, 1, 1>(one_kstep) : one_plane<BM, BN, 0, 1>(one_kstep));
+        break;
+    default: // (f16x3)
+        v = fast == 3 ? variant<BM, BN, 0, 2, 1, 2, 3>() : (fast ? variant<BM, BN, 0, 2, 1, 2, 1>() : variant<BM, BN, 0, 2, 1, 2>());
+        break;
     }
-    if (split) {
-        if (small_cin == 0) return launch_variant<128, BN, 0, true, 0>(ctx, a);
-        if (small_cin == 1) return launch_variant<128, BN, 1, true, 0>(ctx, a);
-        return launch_variant<128, BN, 2, true, 0>(ctx, a);
-    }
-    if (fmt) {
-        if (small_cin == 0 && a.fast) return launch_fast<128, BN>(ctx, a, a.fast);
-        if (small_cin == 1 && a.fast) return launch_variant<128, BN, 1, false, 1, 1>(ctx, a);
-        if (small_cin == 2 && a.fast) return launch_variant<128, BN, 2, false, 1, 1>(ctx, a);
-        if (small_cin == 0) return launch_variant<128, BN, 0, false, 1>(ctx, a);
-        if (small_cin == 1) return launch_variant<128, BN, 1, false, 1>(ctx, a);
-        return launch_variant<128, BN, 2, false, 1>(ctx, a);
-    }
-    if (small_cin == 0) return launch_variant<128, BN, 0, false, 0>(ctx, a);
-    if (small_cin == 1) return launch_variant<128, BN, 1, false, 0>(ctx, a);
-    return launch_variant<128, BN, 2, false, 0>(ctx, a);
+    if (form == CONV_FORM_STEM_ROWS) v.cls = WSC_K_CONV_SMALLCIN; // (the stem is accounted as the stem, whatever stages it)
+    return v;
 }
-
-// 256 x 256 tile, 128 x 64 per wave (generic layers with CoutPad % 256 == 0 only)
-int launch_square(wsc_ctx *ctx, const ConvKArgs &a, int split, int fmt) {
-    if (split == 2) return a.fast ? launch_fast<256, 256, 2>(ctx, a, a.fast) : launch_variant<256, 256, 0, 2, 1>(ctx, a);
-    if (split) return launch_variant<256, 256, 0, true, 0>(ctx, a);
-    if (fmt && a.fast) return launch_fast<256, 256>(ctx, a, a.fast);
-    if (fmt) return launch_variant<256, 256, 0, false, 1>(ctx, a);
-    return launch_variant<256, 256, 0, false, 0>(ctx, a);
+ConvVariant conv_variant(int bm, int bn, ConvForm form, wsc_precision prec, int fast, bool one_kstep, int wpt = 0) {
+    if (bm == 256) return select_variant<256, 256>(form, prec, fast, one_kstep, wpt);
+    return bn == 128 ? select_variant<128, 128>(form, prec, fast, one_kstep, wpt) : select_variant<128, 64>(form, prec, fast, one_kstep, wpt);
 }
 
 } // namespace
 
 int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
-    ConvKArgs a;
+    const int split = conv_split(p.prec), fmt = conv_fmt(p.prec);
+    const bool dma = conv_form_dma(p.form);
+    if (p.form == CONV_FORM_STEM_ROWS)
+        WSC_CHECK(split == 2 && p.Cin == 4 && p.pad == 0 && p.kw <= 7 && (p.stride & 1) == 0, WSC_ERR_INVALID,
+                  "conv: the padded-stem form needs split 2, a 4-channel padded input, kw <= 7 and an even stride");
+    else if (p.form == CONV_FORM_GENERIC) WSC_CHECK(p.Cin % 64 == 0, WSC_ERR_INVALID, "conv: Cin=%d not a multiple of 64", p.Cin);
+    else WSC_CHECK(p.Cin == 4, WSC_ERR_INVALID, "conv: small-Cin mode needs a 4-channel activation");
+    const ConvKLayout k = conv_k_layout(p.kh, p.kw, p.Cin, p.form, p.prec);
+    const bool single_staged = k.interleaved; // f16x3 on an LDS-DMA layer: both planes in one K-step
+    ConvKArgs a = {};
     a.x = p.x; a.x_lo = p.x_lo; a.w = p.w;
     a.s1 = p.s1; a.b1 = p.b1; a.s2 = p.s2; a.b2 = p.b2;
     a.res = p.res; a.res_lo = p.res_lo;
@@ -1073,10 +1066,8 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     a.ldy = p.ldy > 0 ? p.ldy : p.Cout;
     a.win_npix = 0;
     a.ldx = p.Cin; a.x2 = nullptr; a.lo_delta2 = 0; a.cc2 = 0; a.H2 = a.W2 = a.C2 = 0; a.stride2 = 1;
-    a.kh = p.kh; a.kw = p.kw; a.stride = p.stride; a.pad = p.pad; a.relu = p.relu;
+    a.kh = p.kh; a.kw = k.kw_steps; a.stride = p.stride; a.pad = p.pad; a.relu = p.relu;
     a.M = p.N * p.Ho * p.Wo;
-    a.m_base = 0;
-    a.m_end = a.M;
     a.HoWo = p.Ho * p.Wo;
     auto fastdiv = [](unsigned d, unsigned &mul, unsigned &s1, unsigned &s2) {
         unsigned l = 0;
@@ -1087,70 +1078,51 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     };
     fastdiv((unsigned)(a.HoWo > 0 ? a.HoWo : 1), a.div_howo_mul, a.div_howo_s1, a.div_howo_s2);
     fastdiv((unsigned)(p.Wo > 0 ? p.Wo : 1), a.div_wo_mul, a.div_wo_s1, a.div_wo_s2);
-    WSC_CHECK(p.split >= 0 && p.split <= 2 && !(p.split == 1 && p.fmt) && !(p.split == 2 && !p.fmt), WSC_ERR_INVALID,
-              "conv: split mode %d with operand format %d (bf16x3 = split 1 on bf16 planes, f16x3 = split 2 on half planes)", p.split, p.fmt);
-    // small_cin == 3: the stem of the f16x3 mode on a zero-PADDED NHWC4 input (net.hip run_backbone): the 8-pixel x 4-channel
-    // window of kernel row r of an output pixel is 32 contiguous elements of either plane, 16-byte aligned (stride 2: the
-    // window starts at an even pixel), so a K-step = one kernel row = 32 hi + 32 lo values -- exactly the single-staged
-    // split's K-step.  The layer then IS a generic single-staged layer with kh K-steps: no bounds tests (the padding is
-    // in the buffer), LDS-DMA staging, the FAST epilogue (round 3 ran it in three register-staged K segments: 342 us).
-    const bool stem_rows = p.small_cin == 3;
-    if (stem_rows)
-        WSC_CHECK(p.split == 2 && p.Cin == 4 && p.pad == 0 && p.kw <= 7 && (p.stride & 1) == 0, WSC_ERR_INVALID,
-                  "conv: the padded-stem form needs split 2, a 4-channel padded input, kw <= 7 and an even stride");
-    const int small_cin_eff = stem_rows ? 0 : p.small_cin;
-    a.stem_rows = stem_rows ? 1 : 0;
-    a.kw_real = p.kw;
-    const bool single_staged = p.split == 2 && small_cin_eff == 0;
-    if (stem_rows) {
-        a.kw = 1;
-        a.cchunks = 1;
-        a.ntaps = p.kh;
-        a.ksteps_base = p.kh;
-    } else if (p.small_cin == 0) {
-        WSC_CHECK(p.Cin % 64 == 0, WSC_ERR_INVALID, "conv: Cin=%d not a multiple of 64", p.Cin);
-        a.cchunks = p.Cin / (single_staged ? 32 : 64);
-        a.ntaps = p.kh * p.kw;
-        a.ksteps_base = p.kh * p.kw * a.cchunks;
-    } else {
-        WSC_CHECK(p.Cin == 4, WSC_ERR_INVALID, "conv: small-Cin mode needs a 4-channel activation");
-        a.cchunks = 1;
-        a.ntaps = p.kh * p.kw;
-        // kh kernel rows, 2^small_cin slots each, 8 slots per K-step
-        a.ksteps_base = ((p.kh << p.small_cin) + 7) / 8;
-    }
-    a.Kbase = a.ksteps_base * 64; // (single-staged split: a K-step's 64 weight elements are 32 hi + 32 lo)
-    a.Kw = a.Kbase * ((p.split && !single_staged) ? 2 : 1);
-    a.nk = a.ksteps_base * ((p.split && !single_staged) ? 3 : 1);
+    a.cchunks = k.cchunks; a.ksteps_base = k.ksteps_base;
+    a.Kbase = k.Kbase; a.Kw = k.Kw; a.nk = k.nk;
     a.lo_delta = single_staged ? (long long)(p.x_lo - p.x) : 0;
     if (p.x2 != nullptr) { // two A sources: [x (Cin - C2 channels, dense) | x2 at (ho, wo) * stride2 (C2 channels)]
         const int K1 = p.Cin - p.C2;
-        WSC_CHECK(p.split != 1 && small_cin_eff == 0 && p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && K1 > 0 &&
+        WSC_CHECK(split != 1 && dma && p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && K1 > 0 &&
                   K1 % 64 == 0 && p.C2 % 64 == 0 && p.stride2 >= 1 && (p.Ho - 1) * p.stride2 < p.H2 && (p.Wo - 1) * p.stride2 < p.W2 &&
                   (!single_staged || p.x2_lo != nullptr),
                   WSC_ERR_INVALID, "conv: a second input needs a 1x1 / stride 1 layer, channel counts in multiples of 64 and no bf16x3");
         a.x2 = p.x2;
         a.lo_delta2 = single_staged ? (long long)(p.x2_lo - p.x2) : 0;
-        a.cc2 = K1 / (single_staged ? 32 : 64);
+        a.cc2 = K1 / k.ck;
         a.H2 = p.H2; a.W2 = p.W2; a.C2 = p.C2; a.stride2 = p.stride2;
         a.ldx = K1;
     }
-    const int BN = p.CoutPad % 128 == 0 ? 128 : 64;
     WSC_CHECK(p.CoutPad % 64 == 0, WSC_ERR_INVALID, "conv: CoutPad=%d not a multiple of 64", p.CoutPad);
-    a.ntiles_n = p.CoutPad / BN;
+    const int BN = conv_tile_bn(p.CoutPad);
     a.zero = (const bf16_t *)ctx->zero_page;
     a.range = ctx->range_dev;
     // FAST variants (see the kernel): f16, one precision plane (or the single-staged split), fp16 output only, full column
     // tiles, no post-ReLU affine.  p.generic (wsc_conv2d_nchw's WSC_CONV_GENERIC flag) keeps the generic variants: a test
     // holds the two to the same bits.
-    const int nofast = p.generic;
-    a.fast = 0;
-    if (!nofast && p.fmt && (p.split == 0 || single_staged) && p.y != nullptr && p.y_f32 == nullptr &&
+    int fast = 0;
+    if (!p.generic && fmt && (split == 0 || single_staged) && p.y != nullptr && p.y_f32 == nullptr &&
         p.Cout == p.CoutPad && (long long)a.M * a.ldy < (1ll << 31)) {
-        a.fast = 1;
-        if (small_cin_eff == 0 && p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1) a.fast = 3;
+        fast = 1;
+        if (dma && p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1) fast = 3;
     }
     if (a.M == 0) return WSC_OK;
+    // rows [m_base, m_end) of the M output rows on variant v (a layer may be cut in two: the launches write disjoint rows)
+    auto launch = [&](const ConvVariant &v, int m_base, int m_end) -> int {
+        ConvKArgs b = a;
+        b.m_base = m_base;
+        b.m_end = m_end;
+        b.ntiles_n = p.CoutPad / v.bn;
+        b.nblocks = ((m_end - m_base + v.bm - 1) / v.bm) * b.ntiles_n;
+        WSC_TRY(wsc_set_max_dynamic_lds(ctx, reinterpret_cast<const void *>(v.kernel), v.lds));
+        // algorithmic FLOPs: 2 * M * Cout * (kh*kw*Cin_real), x1 regardless of the precision mode
+        const double flops = 2.0 * (m_end - m_base) * a.Cout * (p.form == CONV_FORM_GENERIC ? (double)p.kh * p.kw * p.Cin : (double)p.kh * p.kw * 3);
+        WscKernelTimer timer(ctx, v.cls, flops);
+        hipLaunchKernelGGL(v.kernel, dim3(b.nblocks), dim3(v.bm * 2), v.lds, ctx->stream, b);
+        WSC_HIP(hipGetLastError());
+        return WSC_OK;
+    };
+    const bool one_kstep = a.nk == 1;
     // tile choice: 128 rows.  Measured on the ResNet50-CAM stack (64 samples @321^2, f16): 128-row tiles 4.31 ms, a 256 x 128
     // three-stage tile on the K >= 512 layers 4.37 ms, everywhere 4.45 ms -- the stack is bound by per-block memory latency
     // with 1-2 blocks per CU (an ablation without DMA and without MFMAs still takes 2.2 ms), not by L2->LDS bytes per FLOP.
@@ -1162,55 +1134,45 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     // round of tiles, later 3/4 of a round) from a sweep on ResNet50: (8, 768) 3.96 ms, (8, 256) 3.96, (4, 768) 3.94, (4, 256) 3.92; VGG16 +-0.
     // A grid of 192+ tiles (3/4 of a round: layer4's 3x3 and 1x1 -> 512 convs, 222 tiles) also wins: 4.11 -> 3.97 ms.
     const long long blocks_sq = ((a.M + 255) / 256) * (long long)(p.CoutPad / 256);
-    bool square = small_cin_eff == 0 && p.CoutPad % 256 == 0 && a.nk >= 4 && blocks_sq >= 192;
-    if (p.split == 2 && !a.fast) square = false; // (its generic epilogue next to 128 accumulators + both planes' fragments spills)
+    bool square = dma && p.CoutPad % 256 == 0 && a.nk >= 4 && blocks_sq >= 192;
+    if (split == 2 && !fast) square = false; // (its generic epilogue next to 128 accumulators + both planes' fragments spills)
     // f16x3 K-steps are 32 channels: with fewer than 16 of them (K < 512: layer2's 128 -> 512 and 256 -> 512 convs) the 256 x 256
     // block's prologue + two-group epilogue outweigh its smaller staging traffic (sweep: 109 vs 127 us, 149 vs 162 us)
-    if (p.split == 2 && a.nk < 16) square = false;
+    if (split == 2 && a.nk < 16) square = false;
     if (square) {
-        const int ntn = p.CoutPad / 256;
+        const ConvVariant sq = conv_variant(256, 256, p.form, p.prec, fast, one_kstep);
         // One block per CU: a grid of r * 256 + rem tiles takes r + 1 rounds.  When the last round would be less
         // than half full, the square tiles take whole rounds only and the remaining rows go to the 128 x 128 kernel
         // (<= 512 tiles = one round at 2 blocks per CU, ~0.56 of a square round): VGG16 conv4 (840 tiles) 4 -> 3.6
         // rounds.  The two launches write disjoint output rows.
         const long long rounds = blocks_sq / ctx->num_cus, rem = blocks_sq - rounds * ctx->num_cus;
         if (rounds >= 1 && rem > 0 && rem * 2 <= ctx->num_cus && ctx->num_cus > 0) {
-            const int big_rows = (int)((rounds * ctx->num_cus) / ntn); // 256-row tile rows given to the square kernel
-            ConvKArgs b = a;
-            b.ntiles_n = ntn;
-            b.m_end = big_rows * 256;
-            b.nblocks = big_rows * ntn;
-            WSC_TRY(launch_square(ctx, b, p.split, p.fmt));
-            a.m_base = big_rows * 256;
-            a.nblocks = ((a.M - a.m_base + 127) / 128) * a.ntiles_n; // BN = 128 here (CoutPad % 256 == 0)
-            return launch_bn<128>(ctx, a, small_cin_eff, p.split, p.fmt);
+            const int big_rows = (int)((rounds * ctx->num_cus) / (p.CoutPad / 256)); // 256-row tile rows given to the square kernel
+            WSC_TRY(launch(sq, 0, big_rows * 256));
+            return launch(conv_variant(128, BN, p.form, p.prec, fast, one_kstep), big_rows * 256, a.M); // BN = 128 here (CoutPad % 256 == 0)
         }
-        a.ntiles_n = ntn;
-        a.nblocks = (int)blocks_sq;
-        return launch_square(ctx, a, p.split, p.fmt);
+        return launch(sq, 0, a.M);
     }
-    a.nblocks = ((a.M + 127) / 128) * a.ntiles_n;
     // LDS input window (north star: "3x3 convolutions as MFMA-tiled direct convs with LDS-staged input windows"): the f16x3
     // 3 x 3 / stride 1 / pad 1 layers on 128-row tiles whose window -- the raster positions from (first output pixel - W - 1) to
     // (last output pixel + W + 1), plus the zero row -- fits 256 or 320 positions (32 / 40 KB next to the weight tiles' 32 / 16 KB:
-    // two blocks per CU): ResNet50 @321 layer2 / layer3 conv2 (41 x 41: 213, 21 x 21: 173 positions) and, since round 6's
-    // unpadded raster, layer1 conv2 (81 x 81: 293).
-    if (single_staged && a.fast == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && p.x2 == nullptr &&
+    // two blocks per CU): ResNet50 @321 layer2 / layer3 conv2 (41 x 41: 213, 21 x 21: 173 positions) and, since the raster is
+    // unpadded, layer1 conv2 (81 x 81: 293).
+    int wpt = 0;
+    if (single_staged && fast == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && p.x2 == nullptr &&
         p.Ho == p.H && p.Wo == p.W && ctx->opt[WSC_OPT_CONV_WINDOW] != 0) {
         // positions of a block's window: its 128 output pixels' raster span, one row + one pixel before and after, and the
         // zero row at the window's last position
         const long long need = 127 + 2ll * p.W + 3 + 1;
         const long long npix = (long long)p.N * p.H * p.W;
         // (64-column tiles -- Cout = 64: ResNet50 layer1 conv2 at 81 x 81 -- take the 320-position window: 40 KB + 16 KB of weight
-        // tiles, two blocks per CU instead of three -- measured below; round 5's padded raster needed 480 positions there: rejected)
+        // tiles, two blocks per CU instead of three; a zero-padded raster needed 480 positions there: rejected)
         // (window source offsets are non-negative 32-bit counts of 16-byte units measured from x, the lo plane's distance included:
-        // a lo plane BELOW x keeps the per-tap tiles -- ADVICE r5)
+        // a lo plane BELOW x keeps the per-tap tiles)
         if (need <= 320 && npix < (1ll << 30) && a.lo_delta >= 0 && npix * p.Cin + a.lo_delta < (1ll << 33) && (a.lo_delta & 7) == 0) {
             a.win_npix = (int)npix;
-            if (BN == 128) return need <= 256 ? launch_window<8>(ctx, a) : launch_window<10>(ctx, a);
-            return need <= 256 ? launch_window<8, 64>(ctx, a) : launch_window<10, 64>(ctx, a);
+            wpt = need <= 256 ? 8 : 10;
         }
     }
-    if (BN == 128) return launch_bn<128>(ctx, a, small_cin_eff, p.split, p.fmt);
-    return launch_bn<64>(ctx, a, small_cin_eff, p.split, p.fmt);
+    return launch(conv_variant(128, BN, p.form, p.prec, fast, one_kstep, wpt), 0, a.M);
 }

@@ -25,7 +25,7 @@ __global__ void nchw_to_nhwc4_kernel(const float *__restrict__ x, int N, int HW,
 }
 
 // The same with a zero border baked in: out [N][Hp][Wp][4], pixel (py, px) = input (py - pad, px - pad) or zeros.  The f16x3
-// stem reads this buffer without bounds tests (conv_igemm.hip, small_cin == 3): the 8-pixel window of a kernel row is 64
+// stem reads this buffer without bounds tests (conv_igemm.hip, CONV_FORM_STEM_ROWS): the 8-pixel window of a kernel row is 64
 // contiguous, 16-byte aligned bytes of either plane.
 __global__ void nchw_to_nhwc4_pad_kernel(const float *__restrict__ x, int N, int H, int W, int Hp, int Wp, int pad,
                                          bf16_t *__restrict__ y, bf16_t *__restrict__ y_lo, int fmt) {

@@ -32,7 +32,8 @@ typedef std::unordered_map<std::string, HostTensor> Dict;
 struct ConvW {
     bf16_t *w = nullptr;
     float *s1 = nullptr, *b1 = nullptr, *s2 = nullptr, *b2 = nullptr;
-    int Cin = 0, Cout = 0, CoutPad = 0, kh = 1, kw = 1, stride = 1, pad = 0, relu = 0, small_cin = 0;
+    int Cin = 0, Cout = 0, CoutPad = 0, kh = 1, kw = 1, stride = 1, pad = 0, relu = 0;
+    ConvForm form = CONV_FORM_GENERIC;
 };
 
 // one Conv2d(1x1, bias=False) -> GroupNorm -> [Upsample] -> ReLU head of the IRNet branches
@@ -63,7 +64,9 @@ struct Op {
 
 struct wsc_net {
     wsc_ctx *ctx = nullptr;
-    int arch = 0, C = 0, split = 0, fmt = 0, F = 0;
+    int arch = 0, C = 0, F = 0;
+    wsc_precision prec = WSC_PREC_BF16;
+    int split = 0, fmt = 0; // conv_split(prec), conv_fmt(prec)
     std::vector<ConvW> convs;
     std::vector<Op> ops;
     int final_buf = 0;
@@ -81,6 +84,19 @@ struct wsc_net {
 };
 
 namespace {
+
+// the precision argument of the C ABI
+int decode_precision(int precision, wsc_precision *prec) {
+    WSC_CHECK(precision == WSC_PREC_BF16 || precision == WSC_PREC_BF16X3 || precision == WSC_PREC_F16 || precision == WSC_PREC_F16X3,
+              WSC_ERR_INVALID, "unknown precision %d", precision);
+    *prec = (wsc_precision)precision;
+    return WSC_OK;
+}
+void set_precision(wsc_net *net, wsc_precision prec) {
+    net->prec = prec;
+    net->split = conv_split(prec);
+    net->fmt = conv_fmt(prec);
+}
 
 int upload(wsc_net *net, const void *host, size_t bytes, void **out) {
     void *d = nullptr;
@@ -125,37 +141,28 @@ int fold_bn(const Dict &d, const std::string &bn, int C, double eps_default, std
     return WSC_OK;
 }
 
-// Pack OIHW fp32 weights to [CoutPad][Kw] bf16 in the kernel's K order: generic layers
-// (cin / 64, kh, kw, cin % 64) -- the kh*kw taps of one 64-channel chunk are consecutive K-steps, so the
-// activation lines a block gathers are re-touched within a few K-steps (L2 hits) instead of Cin/64 steps later.
-int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, int small_cin,
+// Pack OIHW fp32 weights to [CoutPad][Kw] 16-bit in the kernel's K order (conv_k_layout, common.h).
+int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, ConvForm form,
               const std::vector<float> &s1, const std::vector<float> &b1, const std::vector<float> *s2,
               const std::vector<float> *b2, ConvW *out) {
     const int Cout = (int)w->shape[0], Cin = (int)w->shape[1], kh = (int)w->shape[2], kw = (int)w->shape[3];
     ConvW c;
     c.Cout = Cout;
-    c.CoutPad = Cout <= 64 ? 64 : ((Cout + 127) / 128) * 128;
-    c.kh = kh; c.kw = kw; c.stride = stride; c.pad = pad; c.relu = relu; c.small_cin = small_cin;
-    int Kbase;
-    if (small_cin == 0) {
+    c.CoutPad = conv_cout_pad(Cout);
+    c.kh = kh; c.kw = kw; c.stride = stride; c.pad = pad; c.relu = relu; c.form = form;
+    if (form == CONV_FORM_GENERIC) {
         WSC_CHECK(Cin % 64 == 0, WSC_ERR_SHAPE, "conv with Cin=%d is not supported (need a multiple of 64)", Cin);
         c.Cin = Cin;
-        Kbase = kh * kw * Cin;
-    } else if (small_cin == 3) { // f16x3 stem on the padded input: one K-step (32 hi + 32 lo) per kernel row
+    } else if (form == CONV_FORM_STEM_ROWS) {
         WSC_CHECK(Cin <= 4 && kw <= 7 && net->split == 2, WSC_ERR_SHAPE, "padded-stem conv needs Cin <= 4, kw <= 7, f16x3");
         c.Cin = 4;
-        Kbase = kh * 32;
     } else {
         WSC_CHECK(Cin <= 4, WSC_ERR_SHAPE, "small-Cin conv needs Cin <= 4, got %d", Cin);
-        WSC_CHECK(kw <= (2 << small_cin), WSC_ERR_SHAPE, "small-Cin conv: kw=%d too wide", kw);
+        WSC_CHECK(kw <= (form == CONV_FORM_SMALL2 ? 4 : 8), WSC_ERR_SHAPE, "small-Cin conv: kw=%d too wide", kw);
         c.Cin = 4;
-        Kbase = (((kh << small_cin) + 7) / 8) * 64;
     }
-    const int planes = net->split ? 2 : 1;
-    const int Kw = Kbase * planes;
-    // f16x3 (split 2), generic layers: K order (cin / 32, kh, kw) and per K-step 32 hi values followed by their 32 lo values
-    // (conv_igemm.hip, SPLIT 2); everything else: [hi K | lo K]
-    const bool interleaved = net->split == 2 && (small_cin == 0 || small_cin == 3);
+    const ConvKLayout lay = conv_k_layout(kh, kw, c.Cin, form, net->prec);
+    const int Kw = lay.Kw;
     std::vector<bf16_t> wp((size_t)c.CoutPad * Kw, 0);
     // IEEE-half modes (f16, f16x3): every output channel's weights are stored times a power of two that puts the channel's
     // largest |w| into [2^12, 2^13), and the epilogue scale s1 takes the inverse -- exact in fp32, the accumulators are fp32.
@@ -187,25 +194,12 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
         auto put = [&](int k, float v) {
             v *= wsc;
             const bf16_t h = f32_to_h16(v, net->fmt);
-            const int lo_at = interleaved ? 32 : Kbase;
             row[k] = h;
-            if (net->split) row[lo_at + k] = f32_to_h16(v - h16_to_f32(h, net->fmt), net->fmt);
+            if (net->split) row[lay.lo_at + k] = f32_to_h16(v - h16_to_f32(h, net->fmt), net->fmt);
         };
         for (int ci = 0; ci < Cin; ++ci)
             for (int r = 0; r < kh; ++r)
-                for (int s = 0; s < kw; ++s) {
-                    const float v = w->data[(((size_t)co * Cin + ci) * kh + r) * kw + s];
-                    if (small_cin == 3) {
-                        put(r * 64 + s * 4 + ci, v); // kernel row r: 8 pixels x 4 channels (pixel 7, channel 3: zero weights)
-                    } else if (interleaved) {
-                        put((((ci >> 5) * kh + r) * kw + s) * 64 + (ci & 31), v);
-                    } else if (small_cin == 0) {
-                        put((((ci >> 6) * kh + r) * kw + s) * 64 + (ci & 63), v);
-                    } else {
-                        // kernel row r owns 2^small_cin slots of 8 = (2 pixels x 4 channels)
-                        put((r << small_cin) * 8 + s * 4 + ci, v);
-                    }
-                }
+                for (int s = 0; s < kw; ++s) put(lay.index(ci, r, s), w->data[(((size_t)co * Cin + ci) * kh + r) * kw + s]);
     }
     WSC_TRY(upload(net, wp.data(), wp.size() * sizeof(bf16_t), (void **)&c.w));
     auto up_vec = [&](const std::vector<float> &v, float **dst) -> int {
@@ -221,6 +215,22 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
     }
     *out = c;
     return WSC_OK;
+}
+
+// The weight- and precision-derived fields of a layer's launch; the caller adds what is its own (activations and their sizes,
+// residual, second input, output pitch, ...)
+ConvLaunch conv_launch(const ConvW &c, wsc_precision prec) {
+    ConvLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.w = c.w; L.s1 = c.s1; L.b1 = c.b1; L.s2 = c.s2; L.b2 = c.b2;
+    L.Cin = c.Cin; L.Cout = c.Cout; L.CoutPad = c.CoutPad;
+    L.kh = c.kh; L.kw = c.kw; L.stride = c.stride; L.pad = c.pad; L.relu = c.relu;
+    L.form = c.form; L.prec = prec;
+    return L;
+}
+// ... and on the zero-padded input of a CONV_FORM_STEM_ROWS layer: the buffer's own size, no padding left to apply
+void on_padded_input(ConvLaunch &L, int in_h, int in_w) {
+    L.H = in_h; L.W = in_w; L.pad = 0;
 }
 
 int add_conv_op(wsc_net *net, const ConvW &c, int in, int out, int res) {
@@ -239,28 +249,26 @@ void add_pool_op(wsc_net *net, int k, int s, int p, int in, int out) {
 
 // ResNet conv (bias-free) + FixedBatchNorm.
 int resnet_conv(wsc_net *net, const Dict &d, const std::string &conv, const std::string &bn, int stride, int pad,
-                int relu, int small_cin, int in, int out, int res) {
+                int relu, ConvForm form, int in, int out, int res) {
     const HostTensor *w;
     WSC_TRY(get(d, conv + ".weight", 4, &w));
     std::vector<float> s, b;
     WSC_TRY(fold_bn(d, bn, (int)w->shape[0], 1e-5, s, b));
     ConvW c;
-    WSC_TRY(make_conv(net, w, stride, pad, relu, small_cin, s, b, nullptr, nullptr, &c));
+    WSC_TRY(make_conv(net, w, stride, pad, relu, form, s, b, nullptr, nullptr, &c));
     return add_conv_op(net, c, in, out, res);
 }
 
 int build_resnet50_backbone(wsc_net *net, const Dict &d) {
     // stem: conv1 7x7 s2 p3 + bn1 + relu, maxpool 3x3 s2 p1          (resnet50.py:62-64, 96-99)
     // (f16x3: the padded-input form, staged like every other layer of that mode)
-    WSC_TRY(resnet_conv(net, d, "resnet50.conv1", "resnet50.bn1", 2, 3, 1, /*small_cin*/ net->split == 2 ? 3 : 2, -1, 0, -1));
+    WSC_TRY(resnet_conv(net, d, "resnet50.conv1", "resnet50.bn1", 2, 3, 1, net->split == 2 ? CONV_FORM_STEM_ROWS : CONV_FORM_SMALL4, -1, 0, -1));
     add_pool_op(net, 3, 2, 1, 0, 1);
     net->taps.push_back((int)net->ops.size() - 1); // stage1 = conv1, bn1, relu, maxpool (resnet50_irn.py:15)
     int cur = 1;
-    const int planes[4] = {64, 128, 256, 512};
     const int blocks[4] = {3, 4, 6, 3};
     const int strides[4] = {1, 2, 2, 1}; // resnet50_cam.py:15 strides=(2,2,2,1): [0] is the stem
     for (int L = 0; L < 4; ++L) {
-        (void)planes;
         for (int bi = 0; bi < blocks[L]; ++bi) {
             const std::string pre = "resnet50.layer" + std::to_string(L + 1) + "." + std::to_string(bi);
             const int s = bi == 0 ? strides[L] : 1;
@@ -268,7 +276,7 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
             for (int i = 0; i < 4 && nf < 3; ++i)
                 if (i != cur) f[nf++] = i;
             // Bottleneck.forward, resnet50.py:34-54; the stride sits on conv2 (resnet50.py:24)
-            WSC_TRY(resnet_conv(net, d, pre + ".conv1", pre + ".bn1", 1, 0, 1, 0, cur, f[0], -1));
+            WSC_TRY(resnet_conv(net, d, pre + ".conv1", pre + ".bn1", 1, 0, 1, CONV_FORM_GENERIC, cur, f[0], -1));
             bool fuse_here = false;
             if (has(d, pre + ".downsample.0.weight") && has(d, pre + ".conv3.weight")) {
                 // (only for the shapes the concatenated GEMM takes: 1x1 kernels, K1 + K2 a multiple of the 64-channel K chunk;
@@ -305,9 +313,9 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
                 }
                 HostTensor wt;
                 wt.data = wc.data(); wt.ndim = 4; wt.shape[0] = Co; wt.shape[1] = K1 + K2; wt.shape[2] = 1; wt.shape[3] = 1;
-                WSC_TRY(resnet_conv(net, d, pre + ".conv2", pre + ".bn2", s, 1, 1, 0, f[0], f[1], -1));
+                WSC_TRY(resnet_conv(net, d, pre + ".conv2", pre + ".bn2", s, 1, 1, CONV_FORM_GENERIC, f[0], f[1], -1));
                 ConvW c;
-                WSC_TRY(make_conv(net, &wt, 1, 0, 1, 0, sig, sh, nullptr, nullptr, &c));
+                WSC_TRY(make_conv(net, &wt, 1, 0, 1, CONV_FORM_GENERIC, sig, sh, nullptr, nullptr, &c));
                 if (net->split != 1) {
                     // the kernel reads the two inputs where they are: channel chunks [0, K1) from conv2's output, the rest from
                     // the block input at the block's stride (conv_igemm.hip, second A source)
@@ -328,13 +336,13 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
                 cur = f[0];
                 continue;
             }
-            WSC_TRY(resnet_conv(net, d, pre + ".conv2", pre + ".bn2", s, 1, 1, 0, f[0], f[1], -1));
+            WSC_TRY(resnet_conv(net, d, pre + ".conv2", pre + ".bn2", s, 1, 1, CONV_FORM_GENERIC, f[0], f[1], -1));
             int res = cur;
             if (has(d, pre + ".downsample.0.weight")) {
-                WSC_TRY(resnet_conv(net, d, pre + ".downsample.0", pre + ".downsample.1", s, 0, 0, 0, cur, f[2], -1));
+                WSC_TRY(resnet_conv(net, d, pre + ".downsample.0", pre + ".downsample.1", s, 0, 0, CONV_FORM_GENERIC, cur, f[2], -1));
                 res = f[2];
             }
-            WSC_TRY(resnet_conv(net, d, pre + ".conv3", pre + ".bn3", 1, 0, 1, 0, f[1], f[0], res));
+            WSC_TRY(resnet_conv(net, d, pre + ".conv3", pre + ".bn3", 1, 0, 1, CONV_FORM_GENERIC, f[1], f[0], res));
             cur = f[0];
         }
         net->taps.push_back((int)net->ops.size() - 1); // stage L+2 = layer L+1
@@ -352,7 +360,7 @@ int build_resnet50(wsc_net *net, const Dict &d) {
               "classifier.weight must be [%d][F][1][1]", net->C);
     net->F = (int)cw->shape[1];
     std::vector<float> one(net->C, 1.f), zero(net->C, 0.f);
-    WSC_TRY(make_conv(net, cw, 1, 0, 0, 0, one, zero, nullptr, nullptr, &net->head));
+    WSC_TRY(make_conv(net, cw, 1, 0, 0, CONV_FORM_GENERIC, one, zero, nullptr, nullptr, &net->head));
     return WSC_OK;
 }
 
@@ -386,10 +394,10 @@ int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
                 if (has(d, bn + ".running_mean")) { // conv -> ReLU -> BatchNorm(eps=1e-3): common_cnn.py:138
                     std::vector<float> s2, b2;
                     WSC_TRY(fold_bn(d, bn, v, 1e-3, s2, b2));
-                    WSC_TRY(make_conv(net, w, 1, 1, 1, first ? 1 : 0, one, bb, &s2, &b2, &c));
+                    WSC_TRY(make_conv(net, w, 1, 1, 1, first ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, one, bb, &s2, &b2, &c));
                     idx += 3;
                 } else {
-                    WSC_TRY(make_conv(net, w, 1, 1, 1, first ? 1 : 0, one, bb, nullptr, nullptr, &c));
+                    WSC_TRY(make_conv(net, w, 1, 1, 1, first ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, one, bb, nullptr, nullptr, &c));
                     idx += 2;
                 }
                 const int in = first ? -1 : cur;
@@ -451,7 +459,7 @@ int build_vgg16(wsc_net *net, const Dict &d) {
         hw.data = wt.data();
         WSC_TRY(gradcam_bias(d, net->C, zero));
     }
-    WSC_TRY(make_conv(net, &hw, 1, 0, 0, 0, one, zero, nullptr, nullptr, &net->head));
+    WSC_TRY(make_conv(net, &hw, 1, 0, 0, CONV_FORM_GENERIC, one, zero, nullptr, nullptr, &net->head));
     net->Ccls = net->C;
     net->cls_max = 0;
     WSC_TRY(upload(net, lw->data, (size_t)net->C * net->F * sizeof(float), (void **)&net->cls_w));
@@ -481,7 +489,7 @@ int build_m7(wsc_net *net, const Dict &d) {
     hw.data = wt.data(); hw.ndim = 4; hw.shape[0] = net->C; hw.shape[1] = net->F; hw.shape[2] = 1; hw.shape[3] = 1;
     std::vector<float> one(net->C, 1.f), zero(net->C, 0.f);
     WSC_TRY(gradcam_bias(d, net->C, zero));
-    WSC_TRY(make_conv(net, &hw, 1, 0, 0, 0, one, zero, nullptr, nullptr, &net->head));
+    WSC_TRY(make_conv(net, &hw, 1, 0, 0, CONV_FORM_GENERIC, one, zero, nullptr, nullptr, &net->head));
     // classifier branch: layer3_p2 (MaxPool 2x2 + Dropout) -> AdaptiveMaxPool2d(1) -> Linear + Sigmoid
     // (m7_cam.py:32-35).  max over 2x2-pooled map == global max when h, w are even.
     const HostTensor *lw;
@@ -506,7 +514,7 @@ struct HeadSpec {
 };
 
 // Conv2d(Cin, Cout, 1, bias=False) weights `<name>.0.weight`, GroupNorm affine `<name>.1.{weight,bias}`
-int add_irn_head(wsc_net *net, const Dict &d, const HeadSpec &hs, int cin_pad) {
+int add_irn_head(wsc_net *net, const Dict &d, const HeadSpec &hs) {
     const HostTensor *w, *g, *b;
     const std::string nm = hs.name;
     WSC_TRY(get(d, nm + ".0.weight", 4, &w));
@@ -515,10 +523,9 @@ int add_irn_head(wsc_net *net, const Dict &d, const HeadSpec &hs, int cin_pad) {
     WSC_CHECK(w->shape[0] == hs.cout && w->shape[2] == 1 && w->shape[3] == 1 && g->shape[0] == hs.cout &&
                   b->shape[0] == hs.cout,
               WSC_ERR_SHAPE, "'%s': expected a 1x1 conv with %d outputs + GroupNorm", hs.name, hs.cout);
-    (void)cin_pad;
     IrnHead h;
     std::vector<float> one(hs.cout, 1.f), zero(hs.cout, 0.f);
-    WSC_TRY(make_conv(net, w, hs.stride, 0, 0, 0, one, zero, nullptr, nullptr, &h.conv));
+    WSC_TRY(make_conv(net, w, hs.stride, 0, 0, CONV_FORM_GENERIC, one, zero, nullptr, nullptr, &h.conv));
     h.groups = hs.groups; h.up = hs.up; h.src = hs.src; h.dst = hs.dst; h.coff = hs.coff;
     WSC_TRY(upload(net, g->data, sizeof(float) * hs.cout, (void **)&h.gamma));
     WSC_TRY(upload(net, b->data, sizeof(float) * hs.cout, (void **)&h.beta));
@@ -529,7 +536,7 @@ int add_irn_head(wsc_net *net, const Dict &d, const HeadSpec &hs, int cin_pad) {
 int build_irn_heads(wsc_net *net, const Dict &d, const std::vector<HeadSpec> &specs, const std::vector<IrnCat> &cats,
                     const std::string &edge_final, int edge_in, const std::string &dp_final) {
     net->cats = cats;
-    for (const HeadSpec &hs : specs) WSC_TRY(add_irn_head(net, d, hs, 0));
+    for (const HeadSpec &hs : specs) WSC_TRY(add_irn_head(net, d, hs));
     // final edge conv = Conv2d(edge_in, 1, 1, bias=True) on the edge concat, zero-padded to cats[0].channels inputs
     const HostTensor *w6, *b6, *w7;
     WSC_TRY(get(d, edge_final + ".weight", 4, &w6));
@@ -542,14 +549,14 @@ int build_irn_heads(wsc_net *net, const Dict &d, const std::vector<HeadSpec> &sp
     HostTensor t6;
     t6.data = w6p.data(); t6.ndim = 4; t6.shape[0] = 1; t6.shape[1] = cin_pad; t6.shape[2] = 1; t6.shape[3] = 1;
     std::vector<float> one1(1, 1.f), bias1(1, b6->data[0]);
-    WSC_TRY(make_conv(net, &t6, 1, 0, 0, 0, one1, bias1, nullptr, nullptr, &net->edge6));
+    WSC_TRY(make_conv(net, &t6, 1, 0, 0, CONV_FORM_GENERIC, one1, bias1, nullptr, nullptr, &net->edge6));
     // final displacement conv = Conv2d(256, 2, 1, bias=False); MeanShift subtracts running_mean in eval
     // (resnet50_irn.py:96-108)
     WSC_TRY(get(d, dp_final + ".weight", 4, &w7));
     WSC_CHECK(w7->shape[0] == 2 && w7->shape[1] == cats.back().channels, WSC_ERR_SHAPE, "%s.weight must be [2][%d][1][1]",
               dp_final.c_str(), cats.back().channels);
     std::vector<float> one2(2, 1.f), zero2(2, 0.f);
-    WSC_TRY(make_conv(net, w7, 1, 0, 0, 0, one2, zero2, nullptr, nullptr, &net->dp7b));
+    WSC_TRY(make_conv(net, w7, 1, 0, 0, CONV_FORM_GENERIC, one2, zero2, nullptr, nullptr, &net->dp7b));
     if (has(d, "mean_shift.running_mean")) {
         const HostTensor *ms;
         WSC_TRY(get(d, "mean_shift.running_mean", 1, &ms));
@@ -678,14 +685,12 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
     Plan pl;
     WSC_TRY(plan_dims(net, N, S, SW, &pl));
     const int planes = net->split ? 2 : 1;
-    // f16x3 stem (small_cin == 3): the NHWC4 input carries its zero border -- rows / columns the kernel rows of the last
-    // output pixel reach, an 8-pixel window per kernel row (conv_igemm.hip)
+    // f16x3 stem (CONV_FORM_STEM_ROWS): the NHWC4 input carries its zero border
     int in_h = S, in_w = SW, in_pad = 0;
     bool fused_stem = false;
-    if (!net->ops.empty() && net->ops[0].type == OP_CONV && net->ops[0].in < 0 && net->convs[net->ops[0].conv].small_cin == 3) {
+    if (!net->ops.empty() && net->ops[0].type == OP_CONV && net->ops[0].in < 0 && net->convs[net->ops[0].conv].form == CONV_FORM_STEM_ROWS) {
         const ConvW &c0 = net->convs[net->ops[0].conv];
-        in_h = (pl.H[0] - 1) * c0.stride + c0.kh;
-        in_w = (pl.W[0] - 1) * c0.stride + 8;
+        conv_stem_rows_input_dims(pl.H[0], pl.W[0], c0.stride, c0.kh, &in_h, &in_w);
         in_pad = c0.pad;
         // conv 7x7 / 2 / 3 (-> 64) + BN + ReLU followed by MaxPool 3 / 2 / 1 (resnet50.py:54-64): one kernel (stem_pool.hip),
         // unless the conv's own output is wanted (a tap) or the path is switched off
@@ -727,16 +732,14 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
         if (fused_stem && i == 0) continue; // computed together with the pool that follows
         if (fused_stem && i == 1) {
             const ConvW &c0 = net->convs[net->ops[0].conv];
-            WSC_TRY(launch_stem_pool(ctx, xin, xin_lo, N, S, SW, c0.w, c0.kh * 64, c0.s1, c0.b1, c0.relu, buf[op.out], buf_lo[op.out]));
+            WSC_TRY(launch_stem_pool(ctx, xin, xin_lo, N, S, SW, c0.w, conv_k_layout(c0.kh, c0.kw, c0.Cin, c0.form, net->prec).Kw, c0.s1, c0.b1, c0.relu, buf[op.out], buf_lo[op.out]));
         } else if (op.type == OP_CONV) {
             const ConvW &c = net->convs[op.conv];
-            ConvLaunch L;
-            memset(&L, 0, sizeof(L));
-            L.x = src; L.x_lo = src_lo; L.w = c.w;
-            L.s1 = c.s1; L.b1 = c.b1; L.s2 = c.s2; L.b2 = c.b2;
+            ConvLaunch L = conv_launch(c, net->prec);
+            L.x = src; L.x_lo = src_lo;
             L.res = op.res >= 0 ? buf[op.res] : nullptr;
             L.res_lo = op.res >= 0 ? buf_lo[op.res] : nullptr;
-            L.y = buf[op.out]; L.y_lo = buf_lo[op.out]; L.y_f32 = nullptr;
+            L.y = buf[op.out]; L.y_lo = buf_lo[op.out];
             if (op.in2 >= 0) {
                 L.x2 = buf[op.in2]; L.x2_lo = buf_lo[op.in2];
                 L.H2 = bh[op.in2]; L.W2 = bw[op.in2]; L.C2 = bc[op.in2]; L.stride2 = op.ps;
@@ -746,13 +749,8 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
                 L.y += op.coff;
                 if (L.y_lo) L.y_lo += op.coff;
             }
-            L.N = N; L.H = H; L.W = W; L.Cin = c.Cin; L.Ho = pl.H[i]; L.Wo = pl.W[i];
-            L.Cout = c.Cout; L.CoutPad = c.CoutPad;
-            L.kh = c.kh; L.kw = c.kw; L.stride = c.stride; L.pad = c.pad; L.relu = c.relu;
-            L.small_cin = c.small_cin; L.split = net->split; L.fmt = net->fmt;
-            if (c.small_cin == 3 && op.in < 0) { // the padded input buffer: its own size, no padding left to apply
-                L.H = in_h; L.W = in_w; L.pad = 0;
-            }
+            L.N = N; L.H = H; L.W = W; L.Ho = pl.H[i]; L.Wo = pl.W[i];
+            if (c.form == CONV_FORM_STEM_ROWS && op.in < 0) on_padded_input(L, in_h, in_w);
             WSC_TRY(conv_igemm_launch(ctx, L));
         } else if (op.type == OP_GATHER) {
             WSC_TRY(launch_gather_strided(ctx, src, src_lo, N, H, W, C, op.ps, pl.H[i], pl.W[i], buf[op.out] + op.coff,
@@ -791,9 +789,8 @@ int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n
                    int precision, wsc_net **out) {
     WSC_CHECK(ctx && weights && out && n_weights > 0, WSC_ERR_INVALID, "wsc_net_create: null argument");
     WSC_CHECK(num_classes > 0 && num_classes <= 64, WSC_ERR_INVALID, "num_classes=%d outside [1,64]", num_classes);
-    WSC_CHECK(precision == WSC_PREC_BF16 || precision == WSC_PREC_BF16X3 || precision == WSC_PREC_F16 ||
-                  precision == WSC_PREC_F16X3,
-              WSC_ERR_INVALID, "unknown precision %d", precision);
+    wsc_precision prec;
+    WSC_TRY(decode_precision(precision, &prec));
     WSC_HIP(hipSetDevice(ctx->device));
     Dict d;
     for (int i = 0; i < n_weights; ++i) {
@@ -811,8 +808,7 @@ int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n
     net->ctx = ctx;
     net->arch = arch;
     net->C = num_classes;
-    net->split = precision == WSC_PREC_BF16X3 ? 1 : (precision == WSC_PREC_F16X3 ? 2 : 0);
-    net->fmt = (precision == WSC_PREC_F16 || precision == WSC_PREC_F16X3) ? 1 : 0;
+    set_precision(net, prec);
     int st;
     switch (arch) {
     case WSC_ARCH_RESNET50_CAM: st = build_resnet50(net, d); break;
@@ -864,16 +860,15 @@ int wsc_net_cam_size_hw(const wsc_net *net, int H, int W, int *h_out, int *w_out
 
 // The 1x1 head (CAM classifier weights / Grad-CAM alpha) with an fp32 NHWC output: in the IEEE-half modes (f16, f16x3) with at
 // most 32 classes it is the streaming kernel of cam_head.hip (an HBM stream, not a tile problem); else the tiled kernel.
-static int run_head(wsc_ctx *ctx, const wsc_net *net, const ConvLaunch &L) {
+static int run_head(wsc_ctx *ctx, const ConvLaunch &L) {
     // (K % 256: each wave's quarter of K is whole trips of four 16-channel slices)
-    if (L.fmt == 1 && L.split != 1 && L.Cout <= 32 && L.CoutPad >= 32 && L.Cin % 256 == 0 && L.y_f32 != nullptr &&
+    if (conv_fmt(L.prec) == 1 && L.Cout <= 32 && L.CoutPad >= 32 && L.Cin % 256 == 0 && L.y_f32 != nullptr &&
         ctx->opt[WSC_OPT_CAM_HEAD_STREAM] != 0) {
         // (the streaming form checks packing and alignment itself; anything it does not take goes to the tiled kernel)
-        const int st = launch_cam_head(ctx, L.x, L.split == 2 ? L.x_lo : nullptr, L.N * L.Ho * L.Wo, L.Cin, L.w,
-                                       L.Cin * (L.split == 2 ? 2 : 1), L.CoutPad, L.s1, L.b1, L.Cout, L.relu, L.y_f32);
+        const int st = launch_cam_head(ctx, L.x, conv_split(L.prec) == 2 ? L.x_lo : nullptr, L.N * L.Ho * L.Wo, L.Cin, L.w,
+                                       conv_k_layout(L.kh, L.kw, L.Cin, L.form, L.prec).Kw, L.CoutPad, L.s1, L.b1, L.Cout, L.relu, L.y_f32);
         if (st != WSC_ERR_INVALID) return st;
     }
-    (void)net;
     return conv_igemm_launch(ctx, L);
 }
 
@@ -898,14 +893,11 @@ int wsc_net_forward_cam_hw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev,
     void *extra;
     WSC_TRY(run_backbone(ctx, net, x_dev, N, S, head_bytes, &feat, &feat_lo, &hf, &wf, &extra, false, SW));
     float *head_out = (float *)extra;
-    ConvLaunch L;
-    memset(&L, 0, sizeof(L));
-    const ConvW &c = net->head;
-    L.x = feat; L.x_lo = feat_lo; L.w = c.w; L.s1 = c.s1; L.b1 = c.b1;
+    ConvLaunch L = conv_launch(net->head, net->prec);
+    L.x = feat; L.x_lo = feat_lo;
     L.y_f32 = head_out;
-    L.N = N; L.H = hf; L.W = wf; L.Cin = c.Cin; L.Ho = hf; L.Wo = wf; L.Cout = c.Cout; L.CoutPad = c.CoutPad;
-    L.kh = 1; L.kw = 1; L.stride = 1; L.pad = 0; L.relu = 0; L.small_cin = 0; L.split = net->split; L.fmt = net->fmt;
-    WSC_TRY(run_head(ctx, net, L));
+    L.N = N; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf;
+    WSC_TRY(run_head(ctx, L));
     WSC_TRY(launch_flip_add(ctx, head_out, B, hf, wf, net->C, net->C, cam_dev));
     if (score_dev != nullptr)
         WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, feat_lo, B, net->cls_max ? -(hf * wf) : hf * wf, net->F,
@@ -924,15 +916,12 @@ int wsc_net_forward_gradcam(wsc_ctx *ctx, const wsc_net *net, const float *x_dev
     int hf, wf;
     void *extra;
     WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &feat_lo, &hf, &wf, &extra));
-    ConvLaunch L;
-    memset(&L, 0, sizeof(L));
-    const ConvW &c = net->head;
-    L.x = feat; L.x_lo = feat_lo; L.w = c.w; L.s1 = c.s1; L.b1 = c.b1;
+    ConvLaunch L = conv_launch(net->head, net->prec);
+    L.x = feat; L.x_lo = feat_lo;
     L.y_f32 = cams_dev; // fp32 NHWC [N][h][w][C]: the layout of np.einsum('ijkl,lm->ijkm')
-    L.N = N; L.H = hf; L.W = wf; L.Cin = c.Cin; L.Ho = hf; L.Wo = wf; L.Cout = c.Cout; L.CoutPad = c.CoutPad;
-    L.kh = 1; L.kw = 1; L.stride = 1; L.pad = 0; L.relu = relu ? 1 : 0; L.small_cin = 0; L.split = net->split;
-    L.fmt = net->fmt;
-    WSC_TRY(run_head(ctx, net, L));
+    L.N = N; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf;
+    L.relu = relu ? 1 : 0;
+    WSC_TRY(run_head(ctx, L));
     if (score_dev != nullptr)
         WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, feat_lo, N, net->cls_max ? -(hf * wf) : hf * wf, net->F,
                                           net->cls_w, net->cls_b, net->Ccls, score_dev, net->fmt, 1));
@@ -1018,15 +1007,10 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
         return which == 0 ? (bf16_t *)(base + o) : (net->split ? (bf16_t *)(base + o + bytes) : nullptr);
     };
     auto run_conv = [&](const ConvW &c, const bf16_t *x, const bf16_t *x_lo, int H, int W, float *y_f32) -> int {
-        ConvLaunch L;
-        memset(&L, 0, sizeof(L));
-        L.x = x; L.x_lo = x_lo; L.w = c.w;
-        L.s1 = c.s1; L.b1 = c.b1; L.s2 = nullptr; L.b2 = nullptr;
-        L.y = nullptr; L.y_lo = nullptr; L.y_f32 = y_f32;
-        L.N = N; L.H = H; L.W = W; L.Cin = c.Cin; L.Ho = outdim(H, c.stride); L.Wo = outdim(W, c.stride);
-        L.Cout = c.Cout; L.CoutPad = c.CoutPad;
-        L.kh = 1; L.kw = 1; L.stride = c.stride; L.pad = 0; L.relu = 0;
-        L.small_cin = 0; L.split = net->split; L.fmt = net->fmt;
+        ConvLaunch L = conv_launch(c, net->prec); // (1 x 1, no padding, no ReLU: build_irn_heads)
+        L.x = x; L.x_lo = x_lo;
+        L.y_f32 = y_f32;
+        L.N = N; L.H = H; L.W = W; L.Ho = outdim(H, c.stride); L.Wo = outdim(W, c.stride);
         return conv_igemm_launch(ctx, L);
     };
     float *ftmp = (float *)(base + ftmp_off);
@@ -1073,20 +1057,19 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
     wsc_net tmp;
     tmp.ctx = ctx;
     const int generic = (precision & WSC_CONV_GENERIC) ? 1 : 0;
-    precision &= ~WSC_CONV_GENERIC;
-    WSC_CHECK(precision >= WSC_PREC_BF16 && precision <= WSC_PREC_F16X3, WSC_ERR_INVALID, "unknown precision %d", precision);
-    tmp.split = precision == WSC_PREC_BF16X3 ? 1 : (precision == WSC_PREC_F16X3 ? 2 : 0);
-    tmp.fmt = (precision == WSC_PREC_F16 || precision == WSC_PREC_F16X3) ? 1 : 0;
+    wsc_precision prec;
+    WSC_TRY(decode_precision(precision & ~WSC_CONV_GENERIC, &prec));
+    set_precision(&tmp, prec);
     HostTensor wt;
     wt.data = w_host; wt.ndim = 4; wt.shape[0] = Cout; wt.shape[1] = Cin; wt.shape[2] = kh; wt.shape[3] = kw;
     std::vector<float> s1(Cout, 1.f), b1(Cout, 0.f);
     if (scale_host) s1.assign(scale_host, scale_host + Cout);
     if (shift_host) b1.assign(shift_host, shift_host + Cout);
-    int small = 0;
-    if (Cin <= 4) small = kw <= 4 ? 1 : 2;
-    if (small == 2 && tmp.split == 2 && (stride & 1) == 0 && kw <= 7) small = 3; // the f16x3 stem form (padded input)
+    ConvForm form = CONV_FORM_GENERIC;
+    if (Cin <= 4) form = kw <= 4 ? CONV_FORM_SMALL2 : CONV_FORM_SMALL4;
+    if (form == CONV_FORM_SMALL4 && tmp.split == 2 && (stride & 1) == 0 && kw <= 7) form = CONV_FORM_STEM_ROWS; // (padded input)
     ConvW c;
-    int st = make_conv(&tmp, &wt, stride, pad, relu, small, s1, b1, nullptr, nullptr, &c);
+    int st = make_conv(&tmp, &wt, stride, pad, relu, form, s1, b1, nullptr, nullptr, &c);
     auto cleanup = [&]() {
         (void)hipStreamSynchronize(ctx->stream);
         for (void *p : tmp.allocs) (void)hipFree(p);
@@ -1094,7 +1077,8 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
     if (st != WSC_OK) { cleanup(); return st; }
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
     const int planes = tmp.split ? 2 : 1;
-    const int in_h = small == 3 ? (Ho - 1) * stride + kh : H, in_w = small == 3 ? (Wo - 1) * stride + 8 : W;
+    int in_h = H, in_w = W;
+    if (form == CONV_FORM_STEM_ROWS) conv_stem_rows_input_dims(Ho, Wo, stride, kh, &in_h, &in_w);
     const size_t in_e = (size_t)N * in_h * in_w * c.Cin, out_e = (size_t)N * Ho * Wo * Cout;
     auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     void *ws;
@@ -1107,18 +1091,16 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
     bf16_t *yo_lo = nullptr; if (tmp.split) { yo_lo = (bf16_t *)p; p += al(out_e * 2); }
     bf16_t *ri = nullptr, *ri_lo = nullptr;
     if (residual_dev) { ri = (bf16_t *)p; p += al(out_e * 2); if (tmp.split) { ri_lo = (bf16_t *)p; p += al(out_e * 2); } }
-    if (small == 3) st = launch_nchw_to_nhwc4_pad(ctx, x_dev, N, H, W, in_h, in_w, pad, xi, xi_lo, tmp.fmt);
-    else if (small) st = launch_nchw_to_nhwc4(ctx, x_dev, N, H, W, xi, xi_lo, tmp.fmt);
+    if (form == CONV_FORM_STEM_ROWS) st = launch_nchw_to_nhwc4_pad(ctx, x_dev, N, H, W, in_h, in_w, pad, xi, xi_lo, tmp.fmt);
+    else if (form != CONV_FORM_GENERIC) st = launch_nchw_to_nhwc4(ctx, x_dev, N, H, W, xi, xi_lo, tmp.fmt);
     else st = launch_nchw_to_nhwc(ctx, x_dev, N, Cin, H * W, xi, xi_lo, tmp.fmt);
     if (st == WSC_OK && residual_dev) st = launch_nchw_to_nhwc(ctx, residual_dev, N, Cout, Ho * Wo, ri, ri_lo, tmp.fmt);
     if (st == WSC_OK) {
-        ConvLaunch L;
-        memset(&L, 0, sizeof(L));
-        L.x = xi; L.x_lo = xi_lo; L.w = c.w; L.s1 = c.s1; L.b1 = c.b1; L.res = ri; L.res_lo = ri_lo;
+        ConvLaunch L = conv_launch(c, prec);
+        L.x = xi; L.x_lo = xi_lo; L.res = ri; L.res_lo = ri_lo;
         L.y = yo; L.y_lo = yo_lo;
-        L.N = N; L.H = in_h; L.W = in_w; L.Cin = c.Cin; L.Ho = Ho; L.Wo = Wo; L.Cout = Cout; L.CoutPad = c.CoutPad;
-        L.kh = kh; L.kw = kw; L.stride = stride; L.pad = small == 3 ? 0 : pad; L.relu = relu; L.small_cin = small; L.split = tmp.split;
-        L.fmt = tmp.fmt;
+        L.N = N; L.H = H; L.W = W; L.Ho = Ho; L.Wo = Wo;
+        if (form == CONV_FORM_STEM_ROWS) on_padded_input(L, in_h, in_w);
         L.generic = generic;
         st = conv_igemm_launch(ctx, L);
     }

@@ -1,7 +1,7 @@
 // The ResNet stem of the f16x3 mode as ONE kernel: conv 7x7 / 2 (3 -> 64) + BatchNorm + ReLU + MaxPool 3x3 / 2 / 1
 // (reference: network/resnet50.py:54-64 -- conv1, bn1, relu, maxpool -- the first four modules of every ResNet50 variant).
 //
-// Why its own kernel.  As an implicit GEMM (conv_igemm.hip, small_cin == 3) the stem spends its time moving bytes, not
+// Why its own kernel.  As an implicit GEMM (conv_igemm.hip, CONV_FORM_STEM_ROWS) the stem spends its time moving bytes, not
 // multiplying: the 128 x 224 A tile of a block is a 4 x amplified copy of the 29 KB of input the block really covers
 // (2.2 GB of LDS-DMA per 64 x 321^2 batch), the epilogue writes 424 MB of two-plane activations and the pool that follows
 // reads them back (ablation in profiles/README.md: 133 of the stem's 207 us remain with neither DMA nor MFMA).  Here a block
@@ -10,7 +10,7 @@
 //     fragments are read straight out of it: output pixel (t, u), kernel row r needs the 8 pixels x 4 channels at patch
 //     row 2t + r, pixels 2u .. 2u + 7 -- 64 contiguous bytes, i.e. the four 16-byte k-groups of the two MFMA slices.
 //     A row pitch of 384 B (a multiple of 128) makes those reads conflict-free without a swizzle;
-//   * the weights ([64][7 K-steps x (32 hi | 32 lo)], the small_cin == 3 packing of net.hip make_conv) stream per kernel
+//   * the weights ([64][7 K-steps x (32 hi | 32 lo)], the CONV_FORM_STEM_ROWS packing of conv_k_layout) stream per kernel
 //     row through a ring of three 8 KB stages by LDS-DMA, swizzled like the B tiles of conv_igemm.hip;
 //   * BN + ReLU are applied to the accumulators, the tile goes to LDS as fp32 (nine tile rows at a time: 39 KB, three blocks
 //     per CU) and the 3 x 3 / 2 maximum is taken there: only the pooled planes (1/4 of the pixels) are written.
