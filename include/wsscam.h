@@ -47,7 +47,8 @@ typedef enum wsc_status {
     WSC_ERR_RANGE = -9        /* an activation of an IEEE-half mode (f16, f16x3) left half's finite range (|v| >= 65504) and was
                                  saturated: the reference's fp32 (03b_irn/net/resnet50.py:11-14) has no such ceiling, so the maps
                                  of this ctx are NOT the reference's.  Sticky: returned by wsc_sync / wsc_memcpy_d2h until
-                                 wsc_ctx_range_status(ctx, &f, 1) clears it.  Run the model in WSC_PREC_BF16X3 instead */
+                                 wsc_ctx_range_status(ctx, &f, 1) clears it.  Run the model in WSC_PREC_F32, the exact fallback, instead
+                                 (WSC_PREC_BF16X3 also has fp32's range, with a 16-bit significand) */
 } wsc_status;
 
 /* architectures: 03b_irn/net/{resnet50_cam,vgg16_cam,m7_cam}.py */
@@ -65,8 +66,10 @@ typedef enum wsc_precision {
     WSC_PREC_BF16 = 0,  /* bf16 operands, fp32 MFMA accumulation, bf16 activations in HBM */
     WSC_PREC_BF16X3 = 1, /* split-bf16 (hi+lo) operands, 3 MFMA products: fp32-class accuracy */
     WSC_PREC_F16 = 2,    /* IEEE half operands (11-bit significand, saturating), fp32 accumulation */
-    WSC_PREC_F16X3 = 3   /* split-half (hi+lo, 22-bit significand) operands and activations, 3 MFMA products per K-slice with
+    WSC_PREC_F16X3 = 3,  /* split-half (hi+lo, 22-bit significand) operands and activations, 3 MFMA products per K-slice with
                             both planes staged once: the fp32-class mode (reference arithmetic is fp32, SURVEY 8 header) */
+    WSC_PREC_F32 = 4     /* exact fp32: fp32 weights and activations, fp32-input MFMA (an fmaf chain), no range guard needed --
+                            the reference's arithmetic and range, the fallback for WSC_ERR_RANGE */
 } wsc_precision;
 
 typedef struct wsc_ctx wsc_ctx; /* device + stream + workspace arena */

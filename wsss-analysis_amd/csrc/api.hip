@@ -146,7 +146,7 @@ int wsc_ctx_range_check(wsc_ctx *ctx) {
     if (f == 0u) return WSC_OK;
     wsc_set_error("an activation of an IEEE-half conv mode (f16 / f16x3) reached half's ceiling (|v| >= 65504) in a layer with %u "
                   "output channels and was saturated -- the reference's fp32 would have kept it, these maps are not the reference's; "
-                  "use WSC_PREC_BF16X3 for this model (wsc_ctx_range_status clears the flag)", f);
+                  "use WSC_PREC_F32, the exact fp32 mode, for this model (wsc_ctx_range_status clears the flag)", f);
     return WSC_ERR_RANGE;
 }
 

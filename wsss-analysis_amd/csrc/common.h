@@ -105,7 +105,7 @@ void wsc_set_error(const char *fmt, ...);
 // ---- per-kernel-class timing (wsc_profile_begin / _end) --------------------------------------------
 enum WscKernelClass {
     WSC_K_CONV256 = 0,   // conv_igemm_kernel, 256x256 tile
-    WSC_K_CONV128,       // conv_igemm_kernel, 128x128 tile, LDS-DMA staging
+    WSC_K_CONV128,       // conv_igemm_kernel, 128x128 tile, LDS-DMA staging (and conv_f32_kernel's, like the two classes below)
     WSC_K_CONV64,        // conv_igemm_kernel, 128x64 tile
     WSC_K_CONV_SMALLCIN, // conv_igemm_kernel, stem / first layer (register staging); stem_pool_kernel (f16x3 ResNet stem + max-pool)
     WSC_K_POOL_MISC,     // maxpool, layout changes, flip-add, classifier branch
@@ -216,7 +216,14 @@ int wsc_set_max_dynamic_lds(wsc_ctx *ctx, const void *fn, int bytes);
 
 // ---- conv (implicit GEMM) -----------------------------------------------------------
 // A wsc_precision as the kernels see it: the 16-bit format of both planes, and what the second ("lo") plane does
-inline int conv_fmt(wsc_precision prec) { return (prec == WSC_PREC_F16 || prec == WSC_PREC_F16X3) ? 1 : 0; } // 0 bf16, 1 IEEE half
+// (WSC_PREC_F32: one plane of fp32 -- no 16-bit format at all, conv_f32.hip and the _f32 kernels of misc / irn_kernels.hip)
+constexpr int CONV_FMT_F32 = 2;
+inline int conv_fmt(wsc_precision prec) { // 0 bf16, 1 IEEE half, CONV_FMT_F32
+    if (prec == WSC_PREC_F32) return CONV_FMT_F32;
+    return (prec == WSC_PREC_F16 || prec == WSC_PREC_F16X3) ? 1 : 0;
+}
+// bytes of one activation / packed-weight element of a plane: THE helper every size of such a buffer goes through
+inline size_t conv_elem_bytes(wsc_precision prec) { return prec == WSC_PREC_F32 ? sizeof(float) : sizeof(bf16_t); }
 // 0: one plane; 1: bf16x3 (three K segments); 2: f16x3 (hi + lo staged once per K-step where the layer is LDS-DMA staged)
 inline int conv_split(wsc_precision prec) { return prec == WSC_PREC_BF16X3 ? 1 : (prec == WSC_PREC_F16X3 ? 2 : 0); }
 
@@ -232,19 +239,24 @@ enum ConvForm {
 };
 inline bool conv_form_dma(ConvForm f) { return f == CONV_FORM_GENERIC || f == CONV_FORM_STEM_ROWS; }
 
-// K layout of a layer's packed weights [CoutPad][Kw] (16-bit) and of the kernel's K loop: THE description both the packing
-// (net.hip make_conv) and the launch (conv_igemm.hip) read.  A K-step is 64 weight elements per output channel.
+// K layout of a layer's packed weights [CoutPad][Kw] (16-bit; fp32 in WSC_PREC_F32) and of the kernel's K loop: THE description
+// both the packing (net.hip make_conv) and the launches (conv_igemm.hip, conv_f32.hip) read.  A K-step is 128 bytes per output
+// channel: `kstep` = 64 16-bit or 32 fp32 weight elements.
 //   generic: K order (cin / ck, kh, kw, cin % ck) -- the kh * kw taps of one channel chunk are consecutive K-steps, so the
 //            activation lines a block gathers are re-touched within a few K-steps (L2 hits) instead of Cin / ck steps later
-//   small-Cin forms: kernel row r owns `slots` 8-element slots of (2 pixels x 4 channels), 8 slots per K-step
+//   small-Cin forms: kernel row r owns 4 (SMALL2) or 8 (SMALL4) pixels x 4 channels, i.e. 2 / 4 16-byte slots of 16-bit values
+//            or 4 / 8 of fp32 values, 8 slots per K-step
 //   stem rows: K-step r = kernel row r, 8 pixels x 4 channels (pixel 7 and channel 3: zero weights)
 // Two planes: interleaved (f16x3, LDS-DMA layers) = every K-step holds [32 hi | 32 lo] of a 32-channel chunk and the K loop
 // runs once; else [hi K | lo K] and the K loop runs three segments hi*hi, lo*hi, hi*lo.
+// fp32 (one plane): a generic K-step is one tap of a 32-channel chunk, the interleaved layout's row with 32 fp32 in place of
+// [32 hi | 32 lo].
 struct ConvKLayout {
     ConvForm form;
     int kh, kw;       // the layer's kernel
     int kw_steps;     // kernel columns the K loop walks per row (kw; 1 where a K-step is a whole kernel row)
-    int ck;           // channels of a generic layer's K-step (64; 32 interleaved)
+    int kstep;        // weight elements of one K-step per output channel (64; 32 fp32)
+    int ck;           // channels of a generic layer's K-step (64; 32 interleaved or fp32)
     bool interleaved;
     int cchunks;      // channel chunks of ck (1 in the 4-channel forms)
     int ksteps_base;  // K-steps of one precision segment
@@ -255,8 +267,8 @@ struct ConvKLayout {
     // element of weight (ci, r, s) (hi part) in its row
     int index(int ci, int r, int s) const {
         if (form == CONV_FORM_STEM_ROWS) return r * 64 + s * 4 + ci;
-        if (form == CONV_FORM_GENERIC) return (((ci / ck) * kh + r) * kw + s) * 64 + ci % ck;
-        return r * (form == CONV_FORM_SMALL2 ? 2 : 4) * 8 + s * 4 + ci;
+        if (form == CONV_FORM_GENERIC) return (((ci / ck) * kh + r) * kw + s) * kstep + ci % ck;
+        return r * (form == CONV_FORM_SMALL2 ? 4 : 8) * 4 + s * 4 + ci;
     }
 };
 // Cin: the activation's channel count (a multiple of 64, or 4 in the NHWC4 forms)
@@ -265,13 +277,14 @@ inline ConvKLayout conv_k_layout(int kh, int kw, int Cin, ConvForm form, wsc_pre
     const int split = conv_split(prec);
     L.form = form; L.kh = kh; L.kw = kw;
     L.interleaved = split == 2 && conv_form_dma(form);
-    L.ck = L.interleaved ? 32 : 64;
+    L.kstep = prec == WSC_PREC_F32 ? 32 : 64;
+    L.ck = (L.interleaved || prec == WSC_PREC_F32) ? 32 : 64;
     L.kw_steps = form == CONV_FORM_STEM_ROWS ? 1 : kw;
     L.cchunks = form == CONV_FORM_GENERIC ? Cin / L.ck : 1;
     if (form == CONV_FORM_GENERIC) L.ksteps_base = kh * kw * L.cchunks;
     else if (form == CONV_FORM_STEM_ROWS) L.ksteps_base = kh;
-    else L.ksteps_base = (kh * (form == CONV_FORM_SMALL2 ? 2 : 4) + 7) / 8;
-    L.Kbase = L.ksteps_base * 64;
+    else L.ksteps_base = (kh * (form == CONV_FORM_SMALL2 ? 4 : 8) * 4 + L.kstep - 1) / L.kstep;
+    L.Kbase = L.ksteps_base * L.kstep;
     const bool segments = split != 0 && !L.interleaved;
     L.Kw = L.Kbase * (segments ? 2 : 1);
     L.nk = L.ksteps_base * (segments ? 3 : 1);
@@ -291,6 +304,8 @@ inline void conv_stem_rows_input_dims(int Ho, int Wo, int stride, int kh, int *H
 
 // One conv layer as the kernel sees it.  Activations are NHWC 16-bit; in the two-plane precisions every activation has a
 // second ("lo") plane of the same format.
+// WSC_PREC_F32: x, w, res and y are OPAQUE here -- they point at fp32 values (one plane, the *_lo pointers are null), sizes and
+// pitches still count elements; only conv_f32.hip and the _f32 kernels look behind them, as float.
 struct ConvLaunch {
     const bf16_t *x, *x_lo;     // input  [N][H][W][Cin]   (Cin = 4 in the NHWC4 forms)
     const bf16_t *w;            // packed [CoutPad][Kw]: conv_k_layout(kh, kw, Cin, form, prec)
@@ -312,6 +327,8 @@ struct ConvLaunch {
     int H2, W2, C2, stride2;
 };
 int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p);
+// conv_f32.hip: the WSC_PREC_F32 layers (conv_igemm_launch sends them there)
+int conv_f32_launch(wsc_ctx *ctx, const ConvLaunch &p);
 // cam_head.hip: the 1x1 head with <= 32 output channels as a streaming GEMM (IEEE-half planes, fp32 [M][C] output)
 int launch_cam_head(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int M, int K, const bf16_t *w, int Kw, int CoutPad,
                     const float *s1, const float *b1, int C, int relu, float *y);

@@ -1048,6 +1048,7 @@ ConvVariant conv_variant(int bm, int bn, ConvForm form, wsc_precision prec, int 
 } // namespace
 
 int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
+    if (p.prec == WSC_PREC_F32) return conv_f32_launch(ctx, p); // exact fp32: its own kernel (conv_f32.hip), nothing below applies
     const int split = conv_split(p.prec), fmt = conv_fmt(p.prec);
     const bool dma = conv_form_dma(p.form);
     if (p.form == CONV_FORM_STEM_ROWS)

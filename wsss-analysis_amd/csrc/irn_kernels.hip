@@ -218,6 +218,52 @@ __global__ __launch_bounds__(256) void gn_apply8_kernel(GnApplyArgs a) {
     }
 }
 
+// WSC_PREC_F32: the same map into an fp32 concat buffer, four channels of one output pixel per thread (C, Ctot, coff multiples
+// of 4): 16-byte loads per tap, one 16-byte store; every element goes through the expressions of gn_apply_kernel.
+__global__ __launch_bounds__(256) void gn_apply_f32_kernel(GnApplyArgs a) {
+    const int C4 = a.C >> 2;
+    const long long total = (long long)a.N * a.Hd * a.Wd * C4;
+    const int Cg = a.C / a.G;
+    float *yf = reinterpret_cast<float *>(a.y);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c0 = (int)(i % C4) * 4;
+        long long t = i / C4;
+        const int wo = (int)(t % a.Wd);
+        t /= a.Wd;
+        const int ho = (int)(t % a.Hd);
+        const int n = (int)(t / a.Hd);
+        const float *xn = a.x + (long long)n * a.H * a.W * a.C + c0;
+        f32x4_t v;
+        if (a.up == 1) {
+            v = *reinterpret_cast<const f32x4_t *>(xn + ((long long)ho * a.W + wo) * a.C);
+        } else {
+            const float inv = 1.0f / (float)a.up;
+            float sy = ((float)ho + 0.5f) * inv - 0.5f, sx = ((float)wo + 0.5f) * inv - 0.5f;
+            sy = sy < 0.f ? 0.f : sy;
+            sx = sx < 0.f ? 0.f : sx;
+            const int y0 = (int)sy, x0 = (int)sx;
+            const int y1 = y0 + (y0 < a.H - 1 ? 1 : 0), x1 = x0 + (x0 < a.W - 1 ? 1 : 0);
+            const float ly = sy - (float)y0, lx = sx - (float)x0;
+            const float hy = 1.f - ly, hx = 1.f - lx;
+            const f32x4_t v00 = *reinterpret_cast<const f32x4_t *>(xn + ((long long)y0 * a.W + x0) * a.C);
+            const f32x4_t v01 = *reinterpret_cast<const f32x4_t *>(xn + ((long long)y0 * a.W + x1) * a.C);
+            const f32x4_t v10 = *reinterpret_cast<const f32x4_t *>(xn + ((long long)y1 * a.W + x0) * a.C);
+            const f32x4_t v11 = *reinterpret_cast<const f32x4_t *>(xn + ((long long)y1 * a.W + x1) * a.C);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = hy * (hx * v00[j] + lx * v01[j]) + ly * (hx * v10[j] + lx * v11[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const float2 st = a.stats[n * a.G + c / Cg];
+            float r = (v[j] - st.x) * st.y * a.gamma[c] + a.beta[c];
+            if (a.relu) r = fmaxf(r, 0.f);
+            v[j] = r;
+        }
+        *reinterpret_cast<f32x4_t *>(yf + (((long long)n * a.Hd + ho) * a.Wd + wo) * a.Ctot + a.coff + c0) = v;
+    }
+}
+
 // e: fp32 [2B][He][We] (Cout = 1), d: fp32 [2B][Hd][Wd][2] (the M7 net has its edge map at twice the resolution)
 __global__ void edge_finish_kernel(const float *__restrict__ e, int He, int We, const float *__restrict__ d, int Hd,
                                    int Wd, int B, int fh, int fw, float ms0, float ms1, float *__restrict__ edge,
@@ -278,6 +324,13 @@ int launch_group_norm_apply(wsc_ctx *ctx, const float *x, const void *stats, con
     a.x = x; a.stats = (const float2 *)stats; a.gamma = gamma; a.beta = beta; a.y = y; a.y_lo = y_lo;
     a.N = N; a.H = H; a.W = W; a.C = C; a.G = G; a.up = up; a.relu = relu; a.Hd = Hd; a.Wd = Wd; a.Ctot = Ctot;
     a.coff = coff; a.fmt = fmt; a.split = y_lo != nullptr;
+    if (fmt == CONV_FMT_F32) { // (y: an fp32 concat buffer, carried opaquely)
+        WSC_CHECK(C % 4 == 0 && Ctot % 4 == 0 && coff % 4 == 0 && y_lo == nullptr && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0,
+                  WSC_ERR_INVALID, "GroupNorm apply (fp32): %d of %d channels at %d are not 16-byte groups", C, Ctot, coff);
+        hipLaunchKernelGGL(gn_apply_f32_kernel, dim3(grid_for((long long)N * Hd * Wd * (C / 4))), dim3(256), 0, ctx->stream, a);
+        WSC_HIP(hipGetLastError());
+        return WSC_OK;
+    }
     const long long items8 = (long long)N * Hd * Wd * (C / 8);
     const bool vec = C % 8 == 0 && Ctot % 8 == 0 && coff % 8 == 0 && items8 < (1ll << 31) && ((uintptr_t)x & 15) == 0 &&
                      ((uintptr_t)y & 15) == 0 && (!y_lo || ((uintptr_t)y_lo & 15) == 0);

@@ -339,6 +339,90 @@ __global__ void nhwc_to_nchw_kernel(const bf16_t *__restrict__ x, const bf16_t *
     }
 }
 
+// ---- WSC_PREC_F32: the same maps on one plane of fp32 (the bf16_t pointers of the launch functions are opaque in that mode,
+// common.h ConvLaunch).  HBM-bound, 16 bytes per access where the layout has them.
+__global__ void nchw_to_nhwc4_f32_kernel(const float *__restrict__ x, int N, int HW, f32x4_t *__restrict__ y) {
+    const long long total = (long long)N * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long n = i / HW;
+        const int p = (int)(i - n * HW);
+        const float *s = x + n * 3 * HW + p;
+        y[i] = f32x4_t{s[0], s[HW], s[2 * HW], 0.f};
+    }
+}
+// nn.MaxPool2d(k, stride, pad) on NHWC fp32, 4 channels per thread
+__global__ __launch_bounds__(256) void maxpool_f32_kernel(const float *__restrict__ x, int N, int H, int W, int C, int k, int stride,
+                                                          int pad, int Ho, int Wo, float *__restrict__ y) {
+    const int C4 = C >> 2;
+    const long long total = (long long)N * Ho * Wo * C4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % C4);
+        long long pix = i / C4;
+        const int wo = (int)(pix % Wo);
+        pix /= Wo;
+        const int ho = (int)(pix % Ho);
+        const int n = (int)(pix / Ho);
+        f32x4_t best = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+        for (int dy = 0; dy < k; ++dy) {
+            const int hi = ho * stride - pad + dy;
+            if ((unsigned)hi >= (unsigned)H) continue;
+            for (int dx = 0; dx < k; ++dx) {
+                const int wi = wo * stride - pad + dx;
+                if ((unsigned)wi >= (unsigned)W) continue;
+                const f32x4_t v = *reinterpret_cast<const f32x4_t *>(x + ((((long long)n * H + hi) * W + wi) * C + c4 * 4));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) best[j] = fmaxf(best[j], v[j]);
+            }
+        }
+        *reinterpret_cast<f32x4_t *>(y + ((((long long)n * Ho + ho) * Wo + wo) * C + c4 * 4)) = best;
+    }
+}
+// gap_kernel's decomposition and summation order on fp32 features
+__global__ __launch_bounds__(64 * GAP_WAVES) void gap_f32_kernel(const float *__restrict__ feat, int hw, int F, float *__restrict__ gap,
+                                                                 int sample_stride) {
+    __shared__ float part[GAP_WAVES][64];
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int f = blockIdx.x * 64 + lane;
+    const bool use_max = hw < 0;
+    const int npix = use_max ? -hw : hw;
+    const int run = (npix + GAP_WAVES - 1) / GAP_WAVES;
+    const int pb = wv * run, pe = min(npix, pb + run);
+    float s = use_max ? -3.0e38f : 0.f;
+    if (f < F) {
+        const float *f0 = feat + (long long)(sample_stride * b) * npix * F + f;
+        int p = pb;
+        for (; p + 8 <= pe; p += 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = f0[(long long)(p + u) * F];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s = use_max ? fmaxf(s, v[u]) : s + v[u];
+        }
+        for (; p < pe; ++p) s = use_max ? fmaxf(s, f0[(long long)p * F]) : s + f0[(long long)p * F];
+    }
+    part[wv][lane] = s;
+    __syncthreads();
+    if (wv == 0 && f < F) {
+        float t = part[0][lane];
+        for (int k = 1; k < GAP_WAVES; ++k) t = use_max ? fmaxf(t, part[k][lane]) : t + part[k][lane];
+        gap[(long long)b * F + f] = use_max ? t : t / (float)npix;
+    }
+}
+// layout changes of the single-layer entry point; TO_NHWC: y[n][p][c] = x[n][c][p], else y[n][c][p] = x[n][p][c]
+template <bool TO_NHWC>
+__global__ void relayout_f32_kernel(const float *__restrict__ x, int N, int C, int HW, float *__restrict__ y) {
+    const long long total = (long long)N * C * HW;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int inner = TO_NHWC ? C : HW, outer = TO_NHWC ? HW : C;
+        const int a = (int)(i % inner);
+        const long long r = i / inner;
+        const int b = (int)(r % outer);
+        const long long n = r / outer;
+        y[i] = x[(n * inner + a) * outer + b];
+    }
+}
+
 inline int grid_for(long long total, int block = 256, int cap = 256 * 16) {
     long long g = (total + block - 1) / block;
     if (g > cap) g = cap;
@@ -350,7 +434,12 @@ inline int grid_for(long long total, int block = 256, int cap = 256 * 16) {
 
 int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, bf16_t *y, bf16_t *y_lo, int fmt) {
     const long long total = (long long)N * H * W;
-    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * (12 + 8));
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * (12 + (fmt == CONV_FMT_F32 ? 16 : 8)));
+    if (fmt == CONV_FMT_F32) {
+        hipLaunchKernelGGL(nchw_to_nhwc4_f32_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, (f32x4_t *)y);
+        WSC_HIP(hipGetLastError());
+        return WSC_OK;
+    }
     hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, y,
                        y_lo, fmt);
     WSC_HIP(hipGetLastError());
@@ -359,6 +448,7 @@ int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, bf16
 
 int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, bf16_t *y, bf16_t *y_lo,
                              int fmt) {
+    WSC_CHECK(fmt != CONV_FMT_F32, WSC_ERR_INVALID, "the padded NHWC4 input is a half-mode path");
     const long long total = (long long)N * Hp * Wp;
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)N * H * W * 12 + (double)total * (y_lo ? 16 : 8));
     hipLaunchKernelGGL(nchw_to_nhwc4_pad_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H, W, Hp, Wp, pad, y,
@@ -382,7 +472,13 @@ int launch_maxpool(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int
                    int stride, int pad, int Ho, int Wo, bf16_t *y, bf16_t *y_lo, int fmt) {
     WSC_CHECK(C % 8 == 0, WSC_ERR_INVALID, "maxpool: C=%d not a multiple of 8", C);
     const long long total = (long long)N * Ho * Wo * (C / 8);
-    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, ((double)N * H * W * C + (double)N * Ho * Wo * C) * 2);
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, ((double)N * H * W * C + (double)N * Ho * Wo * C) * (fmt == CONV_FMT_F32 ? 4 : 2));
+    if (fmt == CONV_FMT_F32) {
+        hipLaunchKernelGGL(maxpool_f32_kernel, dim3(grid_for(total * 2)), dim3(256), 0, ctx->stream, (const float *)x, N, H, W, C, k, stride,
+                           pad, Ho, Wo, (float *)y);
+        WSC_HIP(hipGetLastError());
+        return WSC_OK;
+    }
     if (fmt == 1 && x_lo == nullptr && y_lo == nullptr && (long long)N * Ho <= 65535) {
         const int per_row = Wo * (C / 8);
         hipLaunchKernelGGL(maxpool_f16_kernel, dim3((unsigned)((per_row + 255) / 256), (unsigned)(N * Ho)), dim3(256), 0, ctx->stream,
@@ -417,6 +513,10 @@ int launch_gap_linear_sigmoid(wsc_ctx *ctx, const bf16_t *feat, const bf16_t *fe
     float *gapbuf = nullptr;
     WSC_TRY(wsc_ctx_cached_alloc(ctx, sizeof(float) * (size_t)B * F, (void **)&gapbuf));
     WscCachedGuard gapbuf_guard(ctx, gapbuf);
+    if (fmt == CONV_FMT_F32)
+        hipLaunchKernelGGL(gap_f32_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)B), dim3(64 * GAP_WAVES), 0, ctx->stream,
+                           (const float *)feat, hw, F, gapbuf, sample_stride);
+    else
     hipLaunchKernelGGL(gap_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)B), dim3(64 * GAP_WAVES), 0, ctx->stream, feat, feat_lo, hw, F, gapbuf,
                        fmt, sample_stride);
     hipLaunchKernelGGL(linear_sigmoid_kernel, dim3(B), dim3(256), F * sizeof(float), ctx->stream, (const float *)gapbuf, F, Wc, bias, C,
@@ -427,6 +527,10 @@ int launch_gap_linear_sigmoid(wsc_ctx *ctx, const bf16_t *feat, const bf16_t *fe
 }
 
 int launch_bf16_to_f32(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, size_t n, float *y, int fmt) {
+    if (fmt == CONV_FMT_F32) { // (the activation is the fp32 tensor already)
+        WSC_HIP(hipMemcpyAsync(y, x, n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        return WSC_OK;
+    }
     hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for((long long)n)), dim3(256), 0, ctx->stream, x, x_lo, n,
                        y, fmt);
     WSC_HIP(hipGetLastError());
@@ -434,6 +538,9 @@ int launch_bf16_to_f32(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, size_t
 }
 
 int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, bf16_t *y, bf16_t *y_lo, int fmt) {
+    if (fmt == CONV_FMT_F32)
+        hipLaunchKernelGGL(relayout_f32_kernel<true>, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, x, N, C, HW, (float *)y);
+    else
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, x, N, C,
                        HW, y, y_lo, fmt);
     WSC_HIP(hipGetLastError());
@@ -441,6 +548,9 @@ int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, bf16
 }
 
 int launch_nhwc_to_nchw(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int C, int HW, float *y, int fmt) {
+    if (fmt == CONV_FMT_F32)
+        hipLaunchKernelGGL(relayout_f32_kernel<false>, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, (const float *)x, N, C, HW, y);
+    else
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, x, x_lo,
                        N, C, HW, y, fmt);
     WSC_HIP(hipGetLastError());

@@ -87,7 +87,8 @@ namespace {
 
 // the precision argument of the C ABI
 int decode_precision(int precision, wsc_precision *prec) {
-    WSC_CHECK(precision == WSC_PREC_BF16 || precision == WSC_PREC_BF16X3 || precision == WSC_PREC_F16 || precision == WSC_PREC_F16X3,
+    WSC_CHECK(precision == WSC_PREC_BF16 || precision == WSC_PREC_BF16X3 || precision == WSC_PREC_F16 || precision == WSC_PREC_F16X3 ||
+                  precision == WSC_PREC_F32,
               WSC_ERR_INVALID, "unknown precision %d", precision);
     *prec = (wsc_precision)precision;
     return WSC_OK;
@@ -97,6 +98,8 @@ void set_precision(wsc_net *net, wsc_precision prec) {
     net->split = conv_split(prec);
     net->fmt = conv_fmt(prec);
 }
+// element i of an activation plane (16-bit, or fp32 behind the opaque pointer in WSC_PREC_F32: common.h ConvLaunch)
+bf16_t *elem_at(bf16_t *p, size_t i, wsc_precision prec) { return (bf16_t *)((char *)p + i * conv_elem_bytes(prec)); }
 
 int upload(wsc_net *net, const void *host, size_t bytes, void **out) {
     void *d = nullptr;
@@ -141,7 +144,8 @@ int fold_bn(const Dict &d, const std::string &bn, int C, double eps_default, std
     return WSC_OK;
 }
 
-// Pack OIHW fp32 weights to [CoutPad][Kw] 16-bit in the kernel's K order (conv_k_layout, common.h).
+// Pack OIHW fp32 weights to [CoutPad][Kw] 16-bit in the kernel's K order (conv_k_layout, common.h); WSC_PREC_F32: the fp32
+// values themselves in that order -- no rounding, no power-of-two packing.
 int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, ConvForm form,
               const std::vector<float> &s1, const std::vector<float> &b1, const std::vector<float> *s2,
               const std::vector<float> *b2, ConvW *out) {
@@ -163,7 +167,8 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
     }
     const ConvKLayout lay = conv_k_layout(kh, kw, c.Cin, form, net->prec);
     const int Kw = lay.Kw;
-    std::vector<bf16_t> wp((size_t)c.CoutPad * Kw, 0);
+    const bool f32 = net->prec == WSC_PREC_F32;
+    std::vector<char> wp((size_t)c.CoutPad * Kw * conv_elem_bytes(net->prec), 0); // (zero bits = 0 in every format)
     // IEEE-half modes (f16, f16x3): every output channel's weights are stored times a power of two that puts the channel's
     // largest |w| into [2^12, 2^13), and the epilogue scale s1 takes the inverse -- exact in fp32, the accumulators are fp32.
     // Half has 5 exponent bits: a checkpoint's late-layer weights (|w| ~ 1e-4 ... 1e-3, below half's smallest normal
@@ -189,9 +194,14 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
         }
     }
     for (int co = 0; co < Cout; ++co) {
-        bf16_t *row = wp.data() + (size_t)co * Kw;
+        bf16_t *row = f32 ? nullptr : (bf16_t *)wp.data() + (size_t)co * Kw;
+        float *row_f32 = f32 ? (float *)wp.data() + (size_t)co * Kw : nullptr;
         const float wsc = wscale[co];
         auto put = [&](int k, float v) {
+            if (f32) { // the weight itself
+                row_f32[k] = v;
+                return;
+            }
             v *= wsc;
             const bf16_t h = f32_to_h16(v, net->fmt);
             row[k] = h;
@@ -201,7 +211,7 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
             for (int r = 0; r < kh; ++r)
                 for (int s = 0; s < kw; ++s) put(lay.index(ci, r, s), w->data[(((size_t)co * Cin + ci) * kh + r) * kw + s]);
     }
-    WSC_TRY(upload(net, wp.data(), wp.size() * sizeof(bf16_t), (void **)&c.w));
+    WSC_TRY(upload(net, wp.data(), wp.size(), (void **)&c.w));
     auto up_vec = [&](const std::vector<float> &v, float **dst) -> int {
         std::vector<float> p(c.CoutPad, 0.f);
         for (int i = 0; i < Cout; ++i) p[i] = v[i];
@@ -278,7 +288,10 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
             // Bottleneck.forward, resnet50.py:34-54; the stride sits on conv2 (resnet50.py:24)
             WSC_TRY(resnet_conv(net, d, pre + ".conv1", pre + ".bn1", 1, 0, 1, CONV_FORM_GENERIC, cur, f[0], -1));
             bool fuse_here = false;
-            if (has(d, pre + ".downsample.0.weight") && has(d, pre + ".conv3.weight")) {
+            // (WSC_PREC_F32 keeps the reference's operations: the projection is its own conv and conv3 adds it as a residual --
+            // folding the two BatchNorm scales into one weight matrix rounds every weight once more, which is not the
+            // reference's arithmetic and does not commute with powers of two moved between a BatchNorm and its neighbours)
+            if (net->prec != WSC_PREC_F32 && has(d, pre + ".downsample.0.weight") && has(d, pre + ".conv3.weight")) {
                 // (only for the shapes the concatenated GEMM takes: 1x1 kernels, K1 + K2 a multiple of the 64-channel K chunk;
                 // anything else keeps the separate projection conv + residual)
                 const HostTensor *w3, *wd;
@@ -673,7 +686,7 @@ int plan_dims(const wsc_net *net, int N, int SH, int SW, Plan *pl) {
 // bytes of one plane of stage tap k (x_{k+1}), 256-byte aligned
 size_t tap_plane_bytes(const wsc_net *net, const Plan &pl, int N, int k) {
     const int op = net->taps[k];
-    return align_up((size_t)N * pl.H[op] * pl.W[op] * pl.C[op] * sizeof(bf16_t), 256);
+    return align_up((size_t)N * pl.H[op] * pl.W[op] * pl.C[op] * conv_elem_bytes(net->prec), 256);
 }
 
 // Runs the conv stack on N samples; returns pointers to the final feature map planes.  With copy_taps
@@ -705,8 +718,8 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             in_pad = 5;
         }
     }
-    const size_t in_bytes = align_up((size_t)N * in_h * in_w * 4 * sizeof(bf16_t), 256);
-    const size_t act_bytes = align_up(pl.max_act * sizeof(bf16_t), 256);
+    const size_t in_bytes = align_up((size_t)N * in_h * in_w * 4 * conv_elem_bytes(net->prec), 256);
+    const size_t act_bytes = align_up(pl.max_act * conv_elem_bytes(net->prec), 256);
     const size_t total = in_bytes * planes + act_bytes * 4 * planes + align_up(extra_bytes, 256);
     void *ws;
     WSC_TRY(wsc_ctx_workspace(ctx, total, &ws));
@@ -746,13 +759,14 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             }
             L.ldy = op.pitch; // (0: dense)
             if (op.pitch) {
-                L.y += op.coff;
+                L.y = elem_at(L.y, op.coff, net->prec);
                 if (L.y_lo) L.y_lo += op.coff;
             }
             L.N = N; L.H = H; L.W = W; L.Ho = pl.H[i]; L.Wo = pl.W[i];
             if (c.form == CONV_FORM_STEM_ROWS && op.in < 0) on_padded_input(L, in_h, in_w);
             WSC_TRY(conv_igemm_launch(ctx, L));
         } else if (op.type == OP_GATHER) {
+            WSC_CHECK(net->split == 1, WSC_ERR_INVALID, "internal: the gathered shortcut input is a bf16x3 path");
             WSC_TRY(launch_gather_strided(ctx, src, src_lo, N, H, W, C, op.ps, pl.H[i], pl.W[i], buf[op.out] + op.coff,
                                           buf_lo[op.out] ? buf_lo[op.out] + op.coff : nullptr, op.pitch));
         } else {
@@ -765,7 +779,7 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
                 if (net->taps[k] == (int)i) {
                     char *dst = (char *)*extra;
                     for (size_t j = 0; j < k; ++j) dst += tap_plane_bytes(net, pl, N, (int)j) * planes;
-                    const size_t nb = (size_t)N * pl.H[i] * pl.W[i] * pl.C[i] * sizeof(bf16_t);
+                    const size_t nb = (size_t)N * pl.H[i] * pl.W[i] * pl.C[i] * conv_elem_bytes(net->prec);
                     WSC_HIP(hipMemcpyAsync(dst, buf[op.out], nb, hipMemcpyDeviceToDevice, ctx->stream));
                     if (net->split)
                         WSC_HIP(hipMemcpyAsync(dst + tap_plane_bytes(net, pl, N, (int)k), buf_lo[op.out], nb,
@@ -972,7 +986,7 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
         cat_c[i] = c.channels;
         cat_h[i] = outdim(Hs[c.stage - 1], c.stride);
         cat_w[i] = outdim(Ws[c.stage - 1], c.stride);
-        cat_bytes[i] = align_up((size_t)N * cat_h[i] * cat_w[i] * cat_c[i] * sizeof(bf16_t), 256);
+        cat_bytes[i] = align_up((size_t)N * cat_h[i] * cat_w[i] * cat_c[i] * conv_elem_bytes(net->prec), 256);
         cat_off[i] = off;
         off += cat_bytes[i] * planes;
     }
@@ -1079,18 +1093,19 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
     const int planes = tmp.split ? 2 : 1;
     int in_h = H, in_w = W;
     if (form == CONV_FORM_STEM_ROWS) conv_stem_rows_input_dims(Ho, Wo, stride, kh, &in_h, &in_w);
+    const size_t eb = conv_elem_bytes(prec);
     const size_t in_e = (size_t)N * in_h * in_w * c.Cin, out_e = (size_t)N * Ho * Wo * Cout;
     auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     void *ws;
-    st = wsc_ctx_workspace(ctx, planes * (al(in_e * 2) + 2 * al(out_e * 2)), &ws);
+    st = wsc_ctx_workspace(ctx, planes * (al(in_e * eb) + 2 * al(out_e * eb)), &ws);
     if (st != WSC_OK) { cleanup(); return st; }
     char *p = (char *)ws;
-    bf16_t *xi = (bf16_t *)p; p += al(in_e * 2);
-    bf16_t *xi_lo = nullptr; if (tmp.split) { xi_lo = (bf16_t *)p; p += al(in_e * 2); }
-    bf16_t *yo = (bf16_t *)p; p += al(out_e * 2);
-    bf16_t *yo_lo = nullptr; if (tmp.split) { yo_lo = (bf16_t *)p; p += al(out_e * 2); }
+    bf16_t *xi = (bf16_t *)p; p += al(in_e * eb);
+    bf16_t *xi_lo = nullptr; if (tmp.split) { xi_lo = (bf16_t *)p; p += al(in_e * eb); }
+    bf16_t *yo = (bf16_t *)p; p += al(out_e * eb);
+    bf16_t *yo_lo = nullptr; if (tmp.split) { yo_lo = (bf16_t *)p; p += al(out_e * eb); }
     bf16_t *ri = nullptr, *ri_lo = nullptr;
-    if (residual_dev) { ri = (bf16_t *)p; p += al(out_e * 2); if (tmp.split) { ri_lo = (bf16_t *)p; p += al(out_e * 2); } }
+    if (residual_dev) { ri = (bf16_t *)p; p += al(out_e * eb); if (tmp.split) { ri_lo = (bf16_t *)p; p += al(out_e * eb); } }
     if (form == CONV_FORM_STEM_ROWS) st = launch_nchw_to_nhwc4_pad(ctx, x_dev, N, H, W, in_h, in_w, pad, xi, xi_lo, tmp.fmt);
     else if (form != CONV_FORM_GENERIC) st = launch_nchw_to_nhwc4(ctx, x_dev, N, H, W, xi, xi_lo, tmp.fmt);
     else st = launch_nchw_to_nhwc(ctx, x_dev, N, Cin, H * W, xi, xi_lo, tmp.fmt);

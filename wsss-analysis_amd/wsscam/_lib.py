@@ -36,6 +36,7 @@ PREC_BF16 = 0
 PREC_BF16X3 = 1
 PREC_F16 = 2
 PREC_F16X3 = 3  # split-half operands and activations (hi + lo), three MFMA products: the fp32-class mode
+PREC_F32 = 4  # exact fp32 (weights, activations, fp32-input MFMA): the reference's range, the fallback for WSC_ERR_RANGE
 # path selectors of a context (include/wsscam.h wsc_option; Context.set_option / Context.option)
 OPT_CRF_GAUSS_ON_CHIP, OPT_CRF_FUSED_BLUR, OPT_CRF_BLUR_ON_CHIP, OPT_CRF_RANK_BALLOT, OPT_CRF_EMBED_FULL, OPT_RW_TILED, \
     OPT_STEM_POOL_FUSED, OPT_CONV_WINDOW, OPT_CAM_HEAD_STREAM, OPT_CRF_MSG_IN_UPDATE = range(10)
