@@ -26,11 +26,30 @@
  *   03a_sec-dsrg/SEC.py:275, DSRG.py:328, model.py:689,693 (lib.crf.crf_inference)
  *
  * Build: gcc -O2 -fPIC -shared -ffp-contract=off -o libdensecrf_ref.so densecrf_ref.c -lm
+ *
+ * -DCRF_F64 builds the float64 EVALUATION of the same lattice (libdensecrf_ref64.so): the value arithmetic from
+ * lattice_compute down (splat, blur, slice, norm, message, soft-max) runs in double, the exported names carry a `64`
+ * suffix and take / return double unaries and Q.  lattice_init, the feature arrays, L->barycentric and the kernel-width /
+ * compat parameters stay float, so vertex ids, neighbour tables and barycentric weights are the fp32 oracle's own: the
+ * result is what the fp32 code would give without rounding, the yardstick fp32 implementations (this file's default build
+ * and the device) are measured against.  Without the define nothing changes: `real_t` is float.
  */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+
+#ifdef CRF_F64
+typedef double real_t;
+#define REAL_EXP exp
+#define REAL_POW pow
+#define CRF_NAME(n) n##64
+#else
+typedef float real_t;
+#define REAL_EXP expf
+#define REAL_POW powf
+#define CRF_NAME(n) n
+#endif
 
 /* ---- hash table over short keys, linear probing (insertion order = vertex id) ---- */
 typedef struct {
@@ -200,11 +219,11 @@ static void lattice_init(lattice_t *L, const float *feature, int N, int d) {
 }
 
 /* in/out: [N][vs] pixel-major, class-minor (Eigen column-major M x N) */
-static void lattice_compute(const lattice_t *L, float *out, const float *in, int vs) {
+static void lattice_compute(const lattice_t *L, real_t *out, const real_t *in, int vs) {
     const int d = L->d, N = L->N, M = L->M;
     size_t sz = (size_t)(M + 2) * vs;
-    float *values = (float *)calloc(sz, sizeof(float));
-    float *new_values = (float *)calloc(sz, sizeof(float));
+    real_t *values = (real_t *)calloc(sz, sizeof(real_t));
+    real_t *new_values = (real_t *)calloc(sz, sizeof(real_t));
     /* splat */
     for (int i = 0; i < N; ++i)
         for (int j = 0; j <= d; ++j) {
@@ -215,20 +234,20 @@ static void lattice_compute(const lattice_t *L, float *out, const float *in, int
     /* blur along each of the d+1 axes */
     for (int j = 0; j <= d; ++j) {
         for (int i = 0; i < M; ++i) {
-            const float *old_val = values + (size_t)(i + 1) * vs;
-            float *new_val = new_values + (size_t)(i + 1) * vs;
+            const real_t *old_val = values + (size_t)(i + 1) * vs;
+            real_t *new_val = new_values + (size_t)(i + 1) * vs;
             int n1 = L->n1[(size_t)j * M + i] + 1;
             int n2 = L->n2[(size_t)j * M + i] + 1;
-            const float *n1_val = values + (size_t)n1 * vs;
-            const float *n2_val = values + (size_t)n2 * vs;
+            const real_t *n1_val = values + (size_t)n1 * vs;
+            const real_t *n2_val = values + (size_t)n2 * vs;
             for (int k = 0; k < vs; ++k) new_val[k] = old_val[k] + 0.5f * (n1_val[k] + n2_val[k]);
         }
-        float *t = values;
+        real_t *t = values;
         values = new_values;
         new_values = t;
     }
     /* slice */
-    float alpha = 1.0f / (1 + powf(2, -d));
+    real_t alpha = (real_t)1 / (1 + REAL_POW(2, -d));
     for (int i = 0; i < N; ++i) {
         for (int k = 0; k < vs; ++k) out[(size_t)i * vs + k] = 0;
         for (int j = 0; j <= d; ++j) {
@@ -244,14 +263,14 @@ static void lattice_compute(const lattice_t *L, float *out, const float *in, int
 /* ---- dense kernel with NORMALIZE_SYMMETRIC ---- */
 typedef struct {
     lattice_t L;
-    float *norm; /* [N] */
+    real_t *norm; /* [N] */
 } dkernel_t;
 
 static void dkernel_init(dkernel_t *K, const float *feature, int N, int d) {
     lattice_init(&K->L, feature, N, d);
-    K->norm = (float *)malloc(sizeof(float) * N);
-    float *ones = (float *)malloc(sizeof(float) * N);
-    for (int i = 0; i < N; ++i) ones[i] = 1.f;
+    K->norm = (real_t *)malloc(sizeof(real_t) * N);
+    real_t *ones = (real_t *)malloc(sizeof(real_t) * N);
+    for (int i = 0; i < N; ++i) ones[i] = 1;
     lattice_compute(&K->L, K->norm, ones, 1);
     for (int i = 0; i < N; ++i) K->norm[i] = 1.0 / sqrt(K->norm[i] + 1e-20);
     free(ones);
@@ -261,7 +280,7 @@ static void dkernel_free(dkernel_t *K) {
     free(K->norm);
 }
 /* out = norm * Lattice(norm * in) */
-static void dkernel_apply(const dkernel_t *K, float *out, const float *in, int vs, float *tmp) {
+static void dkernel_apply(const dkernel_t *K, real_t *out, const real_t *in, int vs, real_t *tmp) {
     const int N = K->L.N;
     for (int i = 0; i < N; ++i)
         for (int k = 0; k < vs; ++k) tmp[(size_t)i * vs + k] = in[(size_t)i * vs + k] * K->norm[i];
@@ -270,16 +289,16 @@ static void dkernel_apply(const dkernel_t *K, float *out, const float *in, int v
         for (int k = 0; k < vs; ++k) out[(size_t)i * vs + k] *= K->norm[i];
 }
 
-static void exp_and_normalize(float *out, const float *in, int N, int M) {
+static void exp_and_normalize(real_t *out, const real_t *in, int N, int M) {
     for (int i = 0; i < N; ++i) {
-        const float *b = in + (size_t)i * M;
-        float *o = out + (size_t)i * M;
-        float mx = b[0];
+        const real_t *b = in + (size_t)i * M;
+        real_t *o = out + (size_t)i * M;
+        real_t mx = b[0];
         for (int k = 1; k < M; ++k)
             if (b[k] > mx) mx = b[k];
-        float s = 0;
+        real_t s = 0;
         for (int k = 0; k < M; ++k) {
-            o[k] = expf(b[k] - mx);
+            o[k] = REAL_EXP(b[k] - mx);
             s += o[k];
         }
         for (int k = 0; k < M; ++k) o[k] = o[k] / s;
@@ -287,15 +306,15 @@ static void exp_and_normalize(float *out, const float *in, int N, int M) {
 }
 
 /*
- * One image.  rgb: uint8 [H][W][3]; unary: float [M][H*W] (= -log p, class-major as
- * unary_from_softmax returns); q_out: float [M][H*W] or NULL; argmax_out: int32 [H*W] or
+ * One image.  rgb: uint8 [H][W][3]; unary: real_t [M][H*W] (= -log p, class-major as
+ * unary_from_softmax returns); q_out: real_t [M][H*W] or NULL; argmax_out: int32 [H*W] or
  * NULL; lattice_sizes: int[2] (Gaussian, bilateral vertex counts) or NULL.
  * Pairwise terms with compat == 0 AND sxy <= 0 are skipped entirely.
  * Returns 0.
  */
-int densecrf_ref_inference(const uint8_t *rgb, int H, int W, const float *unary, int M, float g_sxy,
-                           float g_compat, float bi_sxy, float bi_srgb, float bi_compat, int n_iters,
-                           float *q_out, int32_t *argmax_out, int *lattice_sizes) {
+int CRF_NAME(densecrf_ref_inference)(const uint8_t *rgb, int H, int W, const real_t *unary, int M, float g_sxy,
+                                     float g_compat, float bi_sxy, float bi_srgb, float bi_compat, int n_iters,
+                                     real_t *q_out, int32_t *argmax_out, int *lattice_sizes) {
     const int N = H * W;
     dkernel_t KG, KB;
     int use_g = g_sxy > 0, use_b = bi_sxy > 0 && bi_srgb > 0;
@@ -328,11 +347,11 @@ int densecrf_ref_inference(const uint8_t *rgb, int H, int W, const float *unary,
         lattice_sizes[1] = use_b ? KB.L.M : 0;
     }
     size_t sz = (size_t)N * M;
-    float *U = (float *)malloc(sizeof(float) * sz);    /* pixel-major */
-    float *Q = (float *)malloc(sizeof(float) * sz);
-    float *tmp1 = (float *)malloc(sizeof(float) * sz);
-    float *tmp2 = (float *)malloc(sizeof(float) * sz);
-    float *scratch = (float *)malloc(sizeof(float) * sz);
+    real_t *U = (real_t *)malloc(sizeof(real_t) * sz);    /* pixel-major */
+    real_t *Q = (real_t *)malloc(sizeof(real_t) * sz);
+    real_t *tmp1 = (real_t *)malloc(sizeof(real_t) * sz);
+    real_t *tmp2 = (real_t *)malloc(sizeof(real_t) * sz);
+    real_t *scratch = (real_t *)malloc(sizeof(real_t) * sz);
     for (int m = 0; m < M; ++m)
         for (int i = 0; i < N; ++i) U[(size_t)i * M + m] = unary[(size_t)m * N + i];
 
@@ -369,8 +388,8 @@ int densecrf_ref_inference(const uint8_t *rgb, int H, int W, const float *unary,
 }
 
 /* Standalone lattice filter for tests: out = Lattice(in) without normalisation.
- * feature [N][d], in/out [N][vs]. Returns the vertex count. */
-int densecrf_ref_lattice_filter(const float *feature, int N, int d, const float *in, float *out, int vs) {
+ * feature float [N][d], in/out real_t [N][vs]. Returns the vertex count. */
+int CRF_NAME(densecrf_ref_lattice_filter)(const float *feature, int N, int d, const real_t *in, real_t *out, int vs) {
     lattice_t L;
     lattice_init(&L, feature, N, d);
     lattice_compute(&L, out, in, vs);

@@ -57,6 +57,81 @@ def crf_oracle(rgb, U, cfg):
     return q, am, ls
 
 
+_crf_lib64 = None
+
+
+def crf_oracle64_lib():
+    """oracle/densecrf_ref.c built with -DCRF_F64 (same gcc flags as __graft_entry__.build_oracle), compiled on first use into
+    oracle/_build/libdensecrf_ref64.so: the float64 evaluation of the fp32 oracle's lattice."""
+    global _crf_lib64
+    if _crf_lib64 is None:
+        import subprocess
+
+        import __graft_entry__ as ge
+
+        src = os.path.join(ge.ORACLE_DIR, "densecrf_ref.c")
+        out = os.path.join(os.path.dirname(ge.ORACLE_OUT), "libdensecrf_ref64.so")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        if not (os.path.exists(out) and os.path.getmtime(src) <= os.path.getmtime(out)):
+            tmp = "%s.%d.tmp" % (out, os.getpid())  # (several test processes may get here at once: publish with a rename)
+            r = subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-DCRF_F64", "-o", tmp, src, "-lm"],
+                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("gcc failed on the float64 oracle:\n" + r.stdout)
+            os.replace(tmp, out)
+        lib = ctypes.CDLL(out)
+        f32p = np.ctypeslib.ndpointer(np.float32, flags="C")
+        f64p = np.ctypeslib.ndpointer(np.float64, flags="C")
+        u8p = np.ctypeslib.ndpointer(np.uint8, flags="C")
+        i32p = np.ctypeslib.ndpointer(np.int32, flags="C")
+        lib.densecrf_ref_inference64.argtypes = [u8p, ctypes.c_int, ctypes.c_int, f64p, ctypes.c_int] + \
+            [ctypes.c_float] * 5 + [ctypes.c_int, f64p, i32p, i32p]
+        lib.densecrf_ref_inference64.restype = ctypes.c_int
+        lib.densecrf_ref_lattice_filter64.argtypes = [f32p, ctypes.c_int, ctypes.c_int, f64p, f64p, ctypes.c_int]
+        lib.densecrf_ref_lattice_filter64.restype = ctypes.c_int
+        _crf_lib64 = lib
+    return _crf_lib64
+
+
+def crf_oracle64(rgb, U, cfg):
+    """The fp32 oracle's lattice (vertex ids, neighbour tables, barycentric weights: bit for bit crf_oracle's) evaluated in
+    float64 from the splat down: what an fp32 implementation of this mean-field would give without rounding.  U is the fp32
+    unary (widened exactly).  Returns (Q (M,N) float64, argmax (N,), [V_g, V_b])."""
+    lib = crf_oracle64_lib()
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    U = np.ascontiguousarray(U, dtype=np.float64)
+    H, W, _ = rgb.shape
+    M = U.shape[0]
+    q = np.empty((M, H * W), np.float64)
+    am = np.empty(H * W, np.int32)
+    ls = np.zeros(2, np.int32)
+    lib.densecrf_ref_inference64(rgb, H, W, U, M, cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], int(cfg[5]), q, am, ls)
+    return q, am, ls
+
+
+# Worst max|Q32 - Q64| of the fp32 C oracle against crf_oracle64 over tests/crf_f64_cases.py's one-iteration list (5.40e-7, the
+# ragged batch) and its contractive list (compats (1, 2), 10 iterations: 3.91e-7): the distance fp32 arithmetic alone puts an
+# implementation from the exact lattice result while the iteration does not amplify rounding.  A property of the REFERENCE,
+# re-checked on every run by tests/test_crf_oracle.py::test_fp32_oracle_distance_to_float64_without_amplification; the device
+# bounds of tests/test_gpu_crf_f64.py are multiples of it and it is never derived from the device.  Produced by
+#     python -m tests.crf_f64_cases
+# (prints every case's distance and the maxima; the constant is the larger, rounded up to two digits).
+D32_ONE_STEP = 5.4e-7
+# The constant image of those lists is apart: 9216 pixels splat onto a handful of bilateral vertices, and the oracle adds them
+# one after the other in fp32 -- a sum of n terms carries up to n/2 ulp, here a relative 1e-5 on the vertex values and through
+# the norm, against the few dozen terms of an ordinary vertex.  Measured 2.40e-6 (one iteration) / 2.39e-6 (contractive) with
+# the same command; the flat image alone is held to this constant, every other case to D32_ONE_STEP.
+D32_LONG_ROWS = 2.5e-6
+
+
+def top2_margin(Q):
+    """Per pixel, the gap between the largest and the second-largest class probability of Q (M, N); 1 for M = 1."""
+    if Q.shape[0] == 1:
+        return np.ones(Q.shape[1])
+    s = np.sort(Q, axis=0)
+    return s[-1] - s[-2]
+
+
 def crf_exact(rgb, U, cfg):
     """Exact O(N^2) mean-field with true Gaussian kernels (float64) -- the model the lattice approximates."""
     H, W, _ = rgb.shape
@@ -165,7 +240,7 @@ def label_parity(lab, ref, n_class):
             "images": int(len(ref))}
 
 
-def oracle_chain_hsn_adp(images, sd, alpha, thr, cfgs, all_classes=None, size=None, adipose_as_written=True):
+def oracle_chain_hsn_adp(images, sd, alpha, thr, cfgs, all_classes=None, size=None, adipose_as_written=True, with_f64=False):
     """The reference chain of 03c_hsn/demo.py:271-380 (ADP) for a list of (S, S, 3) uint8 patches, all fp32 / float64 on the
     CPU: VGG16 features (torch) -> sigmoid scores -> Grad-CAM einsum -> bilinear upsample, ReLU, / max, x score x pass ->
     per HTT type: valid-class stack, modify_by_htt (background / other channels, 03c_hsn/utilities.py:306-364),
@@ -176,6 +251,8 @@ def oracle_chain_hsn_adp(images, sd, alpha, thr, cfgs, all_classes=None, size=No
     own (oracle/hsn_ref.py), not the product's.  adipose_as_written: demo.py:368-369 takes the positions of A.W / A.B / A.M in
     classes['morph'] and indexes the VALID morph stack with them (channel 0 = Background: the maps picked are S.R, A.W, A.B);
     False = the evidently intended channels, only to show that a test can tell the two apart.
+    with_f64: also run the float64 evaluation of each dense CRF (crf_oracle64, same fp32 unaries and lattice) and return its label
+    maps under 'morph64' / 'func64' -- to tell the fp32 oracle's own conditioning from a difference of the product's.
     Returns {'morph': [label maps], 'func': [label maps]}."""
     import scipy.ndimage
     import scipy.special
@@ -198,6 +275,8 @@ def oracle_chain_hsn_adp(images, sd, alpha, thr, cfgs, all_classes=None, size=No
     H = up / np.maximum(up.max(axis=(1, 2, 3), keepdims=True), 1e-7) * (sc * (sc >= thr))[:, :, None, None]
     a_classes, a_inds = hsn_ref.adp_class_tables(all_classes)
     Y, out = {}, {"morph": [], "func": []}
+    if with_f64:
+        out.update({"morph64": [], "func64": []})
     for htt in ("morph", "func"):
         valid = a_classes["valid_" + htt]
         Y[htt] = np.zeros((n, len(valid), S, S))
@@ -221,4 +300,7 @@ def oracle_chain_hsn_adp(images, sd, alpha, thr, cfgs, all_classes=None, size=No
             U = np.ascontiguousarray(-np.log(np.clip(cs[b][keep], 1e-5, 1.0)).reshape(len(keep), -1).astype(np.float32))
             _, ar, _ = crf_oracle(images[b], U, tuple(cfgs[htt]))
             out[htt].append(keep[ar.reshape(S, S)])
+            if with_f64:
+                _, ar64, _ = crf_oracle64(images[b], U, tuple(cfgs[htt]))
+                out[htt + "64"].append(keep[ar64.reshape(S, S)])
     return out
