@@ -43,6 +43,8 @@ SHAPES = [
     (2, 64, 16, 16, 64, 1, 2, 0),     # one K-step, strided: FAST epilogue without the pointwise prologue, 64 columns
     (2, 64, 16, 16, 128, 1, 2, 0),    # ... 128 columns
     (3, 512, 64, 64, 1024, 1, 1, 0),  # 1x1 on the 256 x 256 tile (192 tiles): bf16, and the pointwise prologue of f16 / f16x3
+    (2, 64, 9, 11, 72, 3, 1, 1),      # workspace carving: Cout % 8 == 0 but != CoutPad and an odd pixel count, so the lo, output and
+                                      # residual planes all start where the 256-byte rounding put them (every precision; fp32 in test_gpu_f32.py)
 ]
 
 

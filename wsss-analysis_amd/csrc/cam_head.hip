@@ -110,8 +110,10 @@ __global__ __launch_bounds__(256, 2) void cam_head_kernel(HeadArgs p) {
 // Returns WSC_ERR_INVALID for anything the streaming form does not take (the caller keeps the tiled kernel for those): the kernel
 // reads weight rows 0 .. 31 unconditionally, indexes the packed rows with (k >> 5) * 64, and moves 16-byte pieces of both planes
 // through one per-lane offset -- all of that is checked HERE, not left to the caller.
-int launch_cam_head(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int M, int K, const bf16_t *w, int Kw, int CoutPad,
-                    const float *s1, const float *b1, int C, int relu, float *y) {
+int launch_cam_head(wsc_ctx *ctx, Act xa, int M, int K, const bf16_t *w, int Kw, int CoutPad, const float *s1, const float *b1,
+                    int C, int relu, float *y) {
+    WSC_CHECK(xa.fmt() == 1, WSC_ERR_INVALID, "cam head: IEEE-half planes only");
+    const bf16_t *x = xa.h16(), *x_lo = xa.h16_lo();
     WSC_CHECK(M > 0 && K > 0 && K % 256 == 0 && C > 0 && C <= 32, WSC_ERR_INVALID, "cam head: M=%d K=%d C=%d (K in multiples of 256)", M, K, C);
     WSC_CHECK(CoutPad >= 32 && Kw == K * (x_lo ? 2 : 1), WSC_ERR_INVALID, "cam head: CoutPad=%d Kw=%d for K=%d (%s packing)", CoutPad, Kw, K,
               x_lo ? "f16x3" : "f16");

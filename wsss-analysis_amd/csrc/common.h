@@ -1,6 +1,7 @@
 // common.h -- shared declarations of libwsscam (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <stdint.h>
 #include <map>
 #include <string>
@@ -302,17 +303,58 @@ inline void conv_stem_rows_input_dims(int Ho, int Wo, int stride, int kh, int *H
     *Wp = (Wo - 1) * stride + 8;
 }
 
-// One conv layer as the kernel sees it.  Activations are NHWC 16-bit; in the two-plane precisions every activation has a
-// second ("lo") plane of the same format.
-// WSC_PREC_F32: x, w, res and y are OPAQUE here -- they point at fp32 values (one plane, the *_lo pointers are null), sizes and
-// pitches still count elements; only conv_f32.hip and the _f32 kernels look behind them, as float.
+// The (mul, s1, s2) with which the conv kernels divide an unsigned n by d (d >= 1) without a division
+inline void conv_fastdiv(unsigned d, unsigned *mul, unsigned *s1, unsigned *s2) {
+    unsigned l = 0;
+    while ((1ull << l) < d) ++l; // ceil(log2 d)
+    *mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
+    *s1 = l < 1 ? l : 1;
+    *s2 = l > 0 ? l - 1 : 0;
+}
+
+// One NHWC activation as host code passes it: its plane(s) and what they hold (16-bit values of conv_fmt(prec), or fp32 in
+// WSC_PREC_F32).  In the two-plane precisions `lo` is a second plane of the same format and size.  The typed views are the
+// only way to the values: the view of the other element type is a bug and aborts (a null Act has every view, null).
+struct Act {
+    void *hi = nullptr, *lo = nullptr; // lo: null in the one-plane precisions
+    wsc_precision prec = WSC_PREC_BF16;
+    explicit operator bool() const { return hi != nullptr; }
+    int fmt() const { return conv_fmt(prec); }
+    int split() const { return conv_split(prec); }
+    // element `elems` of BOTH planes: THE place an element offset becomes a byte offset
+    Act at(size_t elems) const {
+        Act a = *this;
+        a.hi = (char *)hi + elems * conv_elem_bytes(prec);
+        if (lo) a.lo = (char *)lo + elems * conv_elem_bytes(prec);
+        return a;
+    }
+    bool is_f32() const { return prec == WSC_PREC_F32; }
+    bf16_t *h16() const { assert(!hi || !is_f32()); return (bf16_t *)hi; }
+    bf16_t *h16_lo() const { assert(!hi || !is_f32()); return (bf16_t *)lo; }
+    float *f32() const { assert(!hi || (is_f32() && !lo)); return (float *)hi; }
+};
+// Workspace layout of an activation of n elements: the hi plane, then (two-plane precisions) the lo plane, each a whole
+// number of 256-byte lines.  act_carve hands the next one out at `cursor` and moves the cursor past it.
+inline size_t act_bytes(size_t n, wsc_precision prec) {
+    return (n * conv_elem_bytes(prec) + 255) / 256 * 256 * (conv_split(prec) ? 2 : 1);
+}
+inline Act act_carve(char *&cursor, size_t n, wsc_precision prec) {
+    Act a;
+    a.prec = prec;
+    a.hi = cursor;
+    if (conv_split(prec)) a.lo = cursor + act_bytes(n, prec) / 2;
+    cursor += act_bytes(n, prec);
+    return a;
+}
+
+// One conv layer as the kernel sees it.  Every activation operand has the layer's precision.
 struct ConvLaunch {
-    const bf16_t *x, *x_lo;     // input  [N][H][W][Cin]   (Cin = 4 in the NHWC4 forms)
-    const bf16_t *w;            // packed [CoutPad][Kw]: conv_k_layout(kh, kw, Cin, form, prec)
+    Act x;                      // input  [N][H][W][Cin]   (Cin = 4 in the NHWC4 forms)
+    const void *w;              // packed [CoutPad][Kw]: conv_k_layout(kh, kw, Cin, form, prec); fp32 in WSC_PREC_F32, else 16-bit
     const float *s1, *b1;       // y = acc*s1 + b1 (folded BN, or conv bias with s1 = 1)
     const float *s2, *b2;       // optional post-ReLU affine (VGG's conv->ReLU->BN order), or null
-    const bf16_t *res, *res_lo; // optional residual [M][Cout]
-    bf16_t *y, *y_lo;           // output [M][Cout] 16-bit (may be null when y_f32 is set)
+    Act res;                    // optional residual [M][Cout]
+    Act y;                      // output [M][Cout] (may be null when y_f32 is set)
     float *y_f32;               // optional fp32 output [M][Cout]
     int N, H, W, Cin, Ho, Wo, Cout, CoutPad;
     int kh, kw, stride, pad;
@@ -320,50 +362,55 @@ struct ConvLaunch {
     ConvForm form;
     wsc_precision prec;
     int generic;   // 1: keep the generic kernel variants (testing: the FAST variants give the same bits)
-    int ldy;       // row pitch of y / y_lo in elements; 0 = Cout (wider: the output is a channel range of a concatenated tensor)
+    int ldy;       // row pitch of y in elements; 0 = Cout (wider: the output is a channel range of a concatenated tensor)
     // optional second input of a 1x1 / stride 1 layer: the last C2 of the Cin input channels of output pixel (n, ho, wo) come from
     // x2[n][ho * stride2][wo * stride2][0 .. C2) instead of x (which then holds Cin - C2 channels per pixel); null: one input
-    const bf16_t *x2, *x2_lo;
+    Act x2;
     int H2, W2, C2, stride2;
+    // every operand that is there holds values of `prec` (what the launchers check before they take the typed views)
+    bool operands_match() const {
+        for (const Act *a : {&x, &res, &y, &x2})
+            if (*a && a->prec != prec) return false;
+        return true;
+    }
 };
 int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p);
 // conv_f32.hip: the WSC_PREC_F32 layers (conv_igemm_launch sends them there)
 int conv_f32_launch(wsc_ctx *ctx, const ConvLaunch &p);
 // cam_head.hip: the 1x1 head with <= 32 output channels as a streaming GEMM (IEEE-half planes, fp32 [M][C] output)
-int launch_cam_head(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int M, int K, const bf16_t *w, int Kw, int CoutPad,
-                    const float *s1, const float *b1, int C, int relu, float *y);
+int launch_cam_head(wsc_ctx *ctx, Act x, int M, int K, const bf16_t *w, int Kw, int CoutPad, const float *s1, const float *b1,
+                    int C, int relu, float *y);
 
 // ---- misc kernels ---------------------------------------------------------------------
-int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, bf16_t *y, bf16_t *y_lo, int fmt);
+// (the kernel and its grid follow the activation's precision)
+int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y);
 // stem_pool.hip: conv 7x7/2 + BN + ReLU + MaxPool 3x3/2/1 of the f16x3 ResNet stem in one kernel
 void stem_pool_input_dims(int H, int W, int *Hp, int *Wp);
-int launch_stem_pool(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int H, int W, const bf16_t *w, int Kw, const float *s1,
-                     const float *b1, int relu, bf16_t *y, bf16_t *y_lo);
-// x[n][ho * stride][wo * stride][0 .. C) -> y[(n, ho, wo)][0 .. C) with row pitch ldy (both planes; y points at the first channel)
-int launch_gather_strided(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int H, int W, int C, int stride, int Ho, int Wo,
-                          bf16_t *y, bf16_t *y_lo, int ldy);
+int launch_stem_pool(wsc_ctx *ctx, Act x, int N, int H, int W, const bf16_t *w, int Kw, const float *s1, const float *b1, int relu,
+                     Act y);
+// x[n][ho * stride][wo * stride][0 .. C) -> y[(n, ho, wo)][0 .. C) with row pitch ldy (both planes; y is at the first channel:
+// Act::at(coff) of the wider tensor)
+int launch_gather_strided(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int stride, int Ho, int Wo, Act y, int ldy);
 // [N][Hp][Wp][4] with a zero border of `pad` pixels on the top / left (and whatever Hp, Wp leave on the bottom / right)
-int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, bf16_t *y, bf16_t *y_lo,
-                             int fmt);
-int launch_maxpool(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int H, int W, int C, int k,
-                   int stride, int pad, int Ho, int Wo, bf16_t *y, bf16_t *y_lo, int fmt);
+int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, Act y);
+int launch_maxpool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo, Act y);
 // cam[b][c][y][x] = relu(head[2b][y][x][c]) + relu(head[2b+1][y][w-1-x][c])   (head fp32 NHWC, stride Cs)
 int launch_flip_add(wsc_ctx *ctx, const float *head, int B, int h, int w, int C, int Cs, float *cam);
 // score[b][c] = sigmoid(sum_f mean_hw(feat[2b])[f] * Wc[c][f] + bias[c])
-int launch_gap_linear_sigmoid(wsc_ctx *ctx, const bf16_t *feat, const bf16_t *feat_lo, int B, int hw, int F,
-                              const float *Wc, const float *bias, int C, float *score, int fmt,
+int launch_gap_linear_sigmoid(wsc_ctx *ctx, Act feat, int B, int hw, int F, const float *Wc, const float *bias, int C, float *score,
                               int sample_stride);
-int launch_bf16_to_f32(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, size_t n, float *y, int fmt);
-int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, bf16_t *y, bf16_t *y_lo, int fmt);
-int launch_nhwc_to_nchw(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int C, int HW, float *y, int fmt);
+// y[i] = the fp32 value of activation element i (hi + lo in the two-plane precisions), i < n
+int launch_act_to_f32(wsc_ctx *ctx, Act x, size_t n, float *y);
+int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y);
+int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y);
 
 // ---- irn_kernels.hip ---------------------------------------------------------------------
 int launch_group_norm_stats(wsc_ctx *ctx, const float *x, int N, int H, int W, int C, int G, float eps, void *partial,
                             void *stats);
 size_t group_norm_partial_bytes(int N, int H, int W, int G);
+// y: the whole [N][Hd][Wd][Ctot] concat tensor; this head writes its channels [coff, coff + C)
 int launch_group_norm_apply(wsc_ctx *ctx, const float *x, const void *stats, const float *gamma, const float *beta,
-                            int N, int H, int W, int C, int G, int up, int relu, bf16_t *y, bf16_t *y_lo, int Hd, int Wd,
-                            int Ctot, int coff, int fmt);
+                            int N, int H, int W, int C, int G, int up, int relu, Act y, int Hd, int Wd, int Ctot, int coff);
 int launch_edge_finish(wsc_ctx *ctx, const float *e, int He, int We, const float *d, int Hd, int Wd, int B, int fh, int fw,
                        float ms0, float ms1, float *edge, float *dp);
 

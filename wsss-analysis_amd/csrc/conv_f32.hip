@@ -353,23 +353,23 @@ constexpr int conv_f32_lds() {
 } // namespace
 
 int conv_f32_launch(wsc_ctx *ctx, const ConvLaunch &p) {
-    WSC_CHECK(p.prec == WSC_PREC_F32 && p.x_lo == nullptr && p.res_lo == nullptr && p.y_lo == nullptr, WSC_ERR_INVALID,
+    WSC_CHECK(p.prec == WSC_PREC_F32 && p.operands_match() && !p.x.lo && !p.res.lo && !p.y.lo, WSC_ERR_INVALID,
               "conv (fp32): one plane of fp32 activations");
-    WSC_CHECK(p.form != CONV_FORM_STEM_ROWS && p.x2 == nullptr, WSC_ERR_INVALID,
+    WSC_CHECK(p.form != CONV_FORM_STEM_ROWS && !p.x2, WSC_ERR_INVALID,
               "conv (fp32): the padded-stem form and the second input are half-mode paths");
     if (p.form == CONV_FORM_GENERIC) WSC_CHECK(p.Cin % 32 == 0, WSC_ERR_INVALID, "conv (fp32): Cin=%d not a multiple of 32", p.Cin);
     else WSC_CHECK(p.Cin == 4 && p.kw <= (p.form == CONV_FORM_SMALL2 ? 4 : 8), WSC_ERR_INVALID, "conv (fp32): small-Cin mode needs a 4-channel activation");
     WSC_CHECK(p.CoutPad % 64 == 0 && p.Cout <= p.CoutPad, WSC_ERR_INVALID, "conv (fp32): CoutPad=%d not a multiple of 64", p.CoutPad);
     const int ldy = p.ldy > 0 ? p.ldy : p.Cout;
-    WSC_CHECK((p.y == nullptr && p.res == nullptr) || (p.Cout % 8 == 0 && ldy % 4 == 0), WSC_ERR_INVALID,
+    WSC_CHECK((!p.y && !p.res) || (p.Cout % 8 == 0 && ldy % 4 == 0), WSC_ERR_INVALID,
               "conv (fp32): an activation output / residual needs Cout=%d in multiples of 8", p.Cout);
-    WSC_CHECK(p.y != nullptr || p.y_f32 != nullptr, WSC_ERR_INVALID, "conv (fp32): no output");
+    WSC_CHECK(p.y || p.y_f32 != nullptr, WSC_ERR_INVALID, "conv (fp32): no output");
     const ConvKLayout k = conv_k_layout(p.kh, p.kw, p.Cin, p.form, p.prec);
     ConvF32Args a = {};
-    a.x = (const float *)p.x; a.w = (const float *)p.w; // (ConvLaunch carries the fp32 plane opaquely)
+    a.x = p.x.f32(); a.w = (const float *)p.w;
     a.s1 = p.s1; a.b1 = p.b1; a.s2 = p.s2; a.b2 = p.b2;
-    a.res = (const float *)p.res;
-    a.y = (float *)p.y; a.y_f32 = p.y_f32;
+    a.res = p.res.f32();
+    a.y = p.y.f32(); a.y_f32 = p.y_f32;
     a.H = p.H; a.W = p.W; a.Cin = p.Cin; a.Ho = p.Ho; a.Wo = p.Wo; a.Cout = p.Cout;
     a.ldy = ldy;
     a.kh = p.kh; a.kw = p.kw; a.stride = p.stride; a.pad = p.pad; a.relu = p.relu;
@@ -377,15 +377,8 @@ int conv_f32_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     WSC_CHECK(M < (1ll << 31) - 256, WSC_ERR_INVALID, "conv (fp32): %lld output pixels", M);
     a.M = (int)M;
     a.HoWo = p.Ho * p.Wo;
-    auto fastdiv = [](unsigned d, unsigned &mul, unsigned &s1, unsigned &s2) {
-        unsigned l = 0;
-        while ((1ull << l) < d) ++l; // ceil(log2 d)
-        mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-        s1 = l < 1 ? l : 1;
-        s2 = l > 0 ? l - 1 : 0;
-    };
-    fastdiv((unsigned)(a.HoWo > 0 ? a.HoWo : 1), a.div_howo_mul, a.div_howo_s1, a.div_howo_s2);
-    fastdiv((unsigned)(p.Wo > 0 ? p.Wo : 1), a.div_wo_mul, a.div_wo_s1, a.div_wo_s2);
+    conv_fastdiv((unsigned)(a.HoWo > 0 ? a.HoWo : 1), &a.div_howo_mul, &a.div_howo_s1, &a.div_howo_s2);
+    conv_fastdiv((unsigned)(p.Wo > 0 ? p.Wo : 1), &a.div_wo_mul, &a.div_wo_s1, &a.div_wo_s2);
     a.nk = k.nk; a.Kw = k.Kw;
     a.zero = (const float *)ctx->zero_page;
     if (a.M == 0) return WSC_OK;

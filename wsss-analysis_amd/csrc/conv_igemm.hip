@@ -1049,6 +1049,7 @@ ConvVariant conv_variant(int bm, int bn, ConvForm form, wsc_precision prec, int 
 
 int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     if (p.prec == WSC_PREC_F32) return conv_f32_launch(ctx, p); // exact fp32: its own kernel (conv_f32.hip), nothing below applies
+    WSC_CHECK(p.operands_match(), WSC_ERR_INVALID, "conv: an operand is not of the layer's precision %d", (int)p.prec);
     const int split = conv_split(p.prec), fmt = conv_fmt(p.prec);
     const bool dma = conv_form_dma(p.form);
     if (p.form == CONV_FORM_STEM_ROWS)
@@ -1059,10 +1060,10 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     const ConvKLayout k = conv_k_layout(p.kh, p.kw, p.Cin, p.form, p.prec);
     const bool single_staged = k.interleaved; // f16x3 on an LDS-DMA layer: both planes in one K-step
     ConvKArgs a = {};
-    a.x = p.x; a.x_lo = p.x_lo; a.w = p.w;
+    a.x = p.x.h16(); a.x_lo = p.x.h16_lo(); a.w = (const bf16_t *)p.w;
     a.s1 = p.s1; a.b1 = p.b1; a.s2 = p.s2; a.b2 = p.b2;
-    a.res = p.res; a.res_lo = p.res_lo;
-    a.y = p.y; a.y_lo = p.y_lo; a.y_f32 = p.y_f32;
+    a.res = p.res.h16(); a.res_lo = p.res.h16_lo();
+    a.y = p.y.h16(); a.y_lo = p.y.h16_lo(); a.y_f32 = p.y_f32;
     a.H = p.H; a.W = p.W; a.Cin = p.Cin; a.Ho = p.Ho; a.Wo = p.Wo; a.Cout = p.Cout;
     a.ldy = p.ldy > 0 ? p.ldy : p.Cout;
     a.win_npix = 0;
@@ -1070,26 +1071,19 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     a.kh = p.kh; a.kw = k.kw_steps; a.stride = p.stride; a.pad = p.pad; a.relu = p.relu;
     a.M = p.N * p.Ho * p.Wo;
     a.HoWo = p.Ho * p.Wo;
-    auto fastdiv = [](unsigned d, unsigned &mul, unsigned &s1, unsigned &s2) {
-        unsigned l = 0;
-        while ((1ull << l) < d) ++l; // ceil(log2 d)
-        mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-        s1 = l < 1 ? l : 1;
-        s2 = l > 0 ? l - 1 : 0;
-    };
-    fastdiv((unsigned)(a.HoWo > 0 ? a.HoWo : 1), a.div_howo_mul, a.div_howo_s1, a.div_howo_s2);
-    fastdiv((unsigned)(p.Wo > 0 ? p.Wo : 1), a.div_wo_mul, a.div_wo_s1, a.div_wo_s2);
+    conv_fastdiv((unsigned)(a.HoWo > 0 ? a.HoWo : 1), &a.div_howo_mul, &a.div_howo_s1, &a.div_howo_s2);
+    conv_fastdiv((unsigned)(p.Wo > 0 ? p.Wo : 1), &a.div_wo_mul, &a.div_wo_s1, &a.div_wo_s2);
     a.cchunks = k.cchunks; a.ksteps_base = k.ksteps_base;
     a.Kbase = k.Kbase; a.Kw = k.Kw; a.nk = k.nk;
-    a.lo_delta = single_staged ? (long long)(p.x_lo - p.x) : 0;
-    if (p.x2 != nullptr) { // two A sources: [x (Cin - C2 channels, dense) | x2 at (ho, wo) * stride2 (C2 channels)]
+    a.lo_delta = single_staged ? (long long)(a.x_lo - a.x) : 0;
+    if (p.x2) { // two A sources: [x (Cin - C2 channels, dense) | x2 at (ho, wo) * stride2 (C2 channels)]
         const int K1 = p.Cin - p.C2;
         WSC_CHECK(split != 1 && dma && p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && K1 > 0 &&
                   K1 % 64 == 0 && p.C2 % 64 == 0 && p.stride2 >= 1 && (p.Ho - 1) * p.stride2 < p.H2 && (p.Wo - 1) * p.stride2 < p.W2 &&
-                  (!single_staged || p.x2_lo != nullptr),
+                  (!single_staged || p.x2.h16_lo() != nullptr),
                   WSC_ERR_INVALID, "conv: a second input needs a 1x1 / stride 1 layer, channel counts in multiples of 64 and no bf16x3");
-        a.x2 = p.x2;
-        a.lo_delta2 = single_staged ? (long long)(p.x2_lo - p.x2) : 0;
+        a.x2 = p.x2.h16();
+        a.lo_delta2 = single_staged ? (long long)(p.x2.h16_lo() - a.x2) : 0;
         a.cc2 = K1 / k.ck;
         a.H2 = p.H2; a.W2 = p.W2; a.C2 = p.C2; a.stride2 = p.stride2;
         a.ldx = K1;
@@ -1102,7 +1096,7 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     // tiles, no post-ReLU affine.  p.generic (wsc_conv2d_nchw's WSC_CONV_GENERIC flag) keeps the generic variants: a test
     // holds the two to the same bits.
     int fast = 0;
-    if (!p.generic && fmt && (split == 0 || single_staged) && p.y != nullptr && p.y_f32 == nullptr &&
+    if (!p.generic && fmt && (split == 0 || single_staged) && p.y && p.y_f32 == nullptr &&
         p.Cout == p.CoutPad && (long long)a.M * a.ldy < (1ll << 31)) {
         fast = 1;
         if (dma && p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1) fast = 3;
@@ -1160,7 +1154,7 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     // two blocks per CU): ResNet50 @321 layer2 / layer3 conv2 (41 x 41: 213, 21 x 21: 173 positions) and, since the raster is
     // unpadded, layer1 conv2 (81 x 81: 293).
     int wpt = 0;
-    if (single_staged && fast == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && p.x2 == nullptr &&
+    if (single_staged && fast == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && !p.x2 &&
         p.Ho == p.H && p.Wo == p.W && ctx->opt[WSC_OPT_CONV_WINDOW] != 0) {
         // positions of a block's window: its 128 output pixels' raster span, one row + one pixel before and after, and the
         // zero row at the window's last position

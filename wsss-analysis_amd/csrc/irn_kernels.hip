@@ -316,16 +316,19 @@ size_t group_norm_partial_bytes(int N, int H, int W, int G) {
 }
 
 int launch_group_norm_apply(wsc_ctx *ctx, const float *x, const void *stats, const float *gamma, const float *beta,
-                            int N, int H, int W, int C, int G, int up, int relu, bf16_t *y, bf16_t *y_lo, int Hd, int Wd,
-                            int Ctot, int coff, int fmt) {
+                            int N, int H, int W, int C, int G, int up, int relu, Act y, int Hd, int Wd, int Ctot, int coff) {
     WSC_CHECK(Hd <= H * up && Wd <= W * up, WSC_ERR_INVALID, "GroupNorm apply: crop %dx%d larger than %dx%d", Hd, Wd,
               H * up, W * up);
+    const bool f32 = y.is_f32();
     GnApplyArgs a;
-    a.x = x; a.stats = (const float2 *)stats; a.gamma = gamma; a.beta = beta; a.y = y; a.y_lo = y_lo;
+    a.x = x; a.stats = (const float2 *)stats; a.gamma = gamma; a.beta = beta;
+    // (gn_apply_f32_kernel takes its fp32 output through the struct's 16-bit pointer)
+    a.y = f32 ? reinterpret_cast<bf16_t *>(y.f32()) : y.h16();
+    a.y_lo = f32 ? nullptr : y.h16_lo();
     a.N = N; a.H = H; a.W = W; a.C = C; a.G = G; a.up = up; a.relu = relu; a.Hd = Hd; a.Wd = Wd; a.Ctot = Ctot;
-    a.coff = coff; a.fmt = fmt; a.split = y_lo != nullptr;
-    if (fmt == CONV_FMT_F32) { // (y: an fp32 concat buffer, carried opaquely)
-        WSC_CHECK(C % 4 == 0 && Ctot % 4 == 0 && coff % 4 == 0 && y_lo == nullptr && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0,
+    a.coff = coff; a.fmt = y.fmt(); a.split = a.y_lo != nullptr;
+    if (f32) {
+        WSC_CHECK(C % 4 == 0 && Ctot % 4 == 0 && coff % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)a.y & 15) == 0,
                   WSC_ERR_INVALID, "GroupNorm apply (fp32): %d of %d channels at %d are not 16-byte groups", C, Ctot, coff);
         hipLaunchKernelGGL(gn_apply_f32_kernel, dim3(grid_for((long long)N * Hd * Wd * (C / 4))), dim3(256), 0, ctx->stream, a);
         WSC_HIP(hipGetLastError());
@@ -333,7 +336,7 @@ int launch_group_norm_apply(wsc_ctx *ctx, const float *x, const void *stats, con
     }
     const long long items8 = (long long)N * Hd * Wd * (C / 8);
     const bool vec = C % 8 == 0 && Ctot % 8 == 0 && coff % 8 == 0 && items8 < (1ll << 31) && ((uintptr_t)x & 15) == 0 &&
-                     ((uintptr_t)y & 15) == 0 && (!y_lo || ((uintptr_t)y_lo & 15) == 0);
+                     ((uintptr_t)a.y & 15) == 0 && (!a.y_lo || ((uintptr_t)a.y_lo & 15) == 0);
     if (vec && up == 1)
         hipLaunchKernelGGL(gn_apply8_kernel<false>, dim3(grid_for(items8)), dim3(256), 0, ctx->stream, a);
     else if (vec)

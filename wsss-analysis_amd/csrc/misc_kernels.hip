@@ -339,8 +339,8 @@ __global__ void nhwc_to_nchw_kernel(const bf16_t *__restrict__ x, const bf16_t *
     }
 }
 
-// ---- WSC_PREC_F32: the same maps on one plane of fp32 (the bf16_t pointers of the launch functions are opaque in that mode,
-// common.h ConvLaunch).  HBM-bound, 16 bytes per access where the layout has them.
+// ---- WSC_PREC_F32: the same maps on one plane of fp32 (the launch functions take them for an Act of that precision).
+// HBM-bound, 16 bytes per access where the layout has them.
 __global__ void nchw_to_nhwc4_f32_kernel(const float *__restrict__ x, int N, int HW, f32x4_t *__restrict__ y) {
     const long long total = (long long)N * HW;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -432,69 +432,60 @@ inline int grid_for(long long total, int block = 256, int cap = 256 * 16) {
 
 } // namespace
 
-int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, bf16_t *y, bf16_t *y_lo, int fmt) {
+int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y) {
     const long long total = (long long)N * H * W;
-    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * (12 + (fmt == CONV_FMT_F32 ? 16 : 8)));
-    if (fmt == CONV_FMT_F32) {
-        hipLaunchKernelGGL(nchw_to_nhwc4_f32_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, (f32x4_t *)y);
-        WSC_HIP(hipGetLastError());
-        return WSC_OK;
-    }
-    hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, y,
-                       y_lo, fmt);
+    const bool f32 = y.is_f32();
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * (12 + (f32 ? 16 : 8)));
+    if (f32)
+        hipLaunchKernelGGL(nchw_to_nhwc4_f32_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, (f32x4_t *)y.f32());
+    else
+        hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, y.h16(), y.h16_lo(),
+                           y.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
-int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, bf16_t *y, bf16_t *y_lo,
-                             int fmt) {
-    WSC_CHECK(fmt != CONV_FMT_F32, WSC_ERR_INVALID, "the padded NHWC4 input is a half-mode path");
+int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, Act y) {
+    WSC_CHECK(!y.is_f32(), WSC_ERR_INVALID, "the padded NHWC4 input is a half-mode path");
     const long long total = (long long)N * Hp * Wp;
-    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)N * H * W * 12 + (double)total * (y_lo ? 16 : 8));
-    hipLaunchKernelGGL(nchw_to_nhwc4_pad_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H, W, Hp, Wp, pad, y,
-                       y_lo, fmt);
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)N * H * W * 12 + (double)total * (y.lo ? 16 : 8));
+    hipLaunchKernelGGL(nchw_to_nhwc4_pad_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H, W, Hp, Wp, pad, y.h16(),
+                       y.h16_lo(), y.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
-int launch_gather_strided(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int H, int W, int C, int stride, int Ho, int Wo,
-                          bf16_t *y, bf16_t *y_lo, int ldy) {
+int launch_gather_strided(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int stride, int Ho, int Wo, Act y, int ldy) {
+    WSC_CHECK(!x.is_f32() && y.prec == x.prec, WSC_ERR_INVALID, "gather: 16-bit planes of one precision only");
     WSC_CHECK(C % 8 == 0 && ldy % 8 == 0, WSC_ERR_INVALID, "gather: C=%d, pitch=%d not multiples of 8", C, ldy);
     const long long total = (long long)N * Ho * Wo * (C / 8);
-    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * 32 * (x_lo ? 2 : 1));
-    hipLaunchKernelGGL(gather_strided_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, x_lo, H, W, C / 8, stride, Ho, Wo, y,
-                       y_lo, ldy, total);
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * 32 * (x.lo ? 2 : 1));
+    hipLaunchKernelGGL(gather_strided_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x.h16(), x.h16_lo(), H, W, C / 8, stride,
+                       Ho, Wo, y.h16(), y.h16_lo(), ldy, total);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
-int launch_maxpool(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int H, int W, int C, int k,
-                   int stride, int pad, int Ho, int Wo, bf16_t *y, bf16_t *y_lo, int fmt) {
+int launch_maxpool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo, Act y) {
     WSC_CHECK(C % 8 == 0, WSC_ERR_INVALID, "maxpool: C=%d not a multiple of 8", C);
+    WSC_CHECK(y.prec == x.prec, WSC_ERR_INVALID, "maxpool: input and output of different precisions");
     const long long total = (long long)N * Ho * Wo * (C / 8);
-    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, ((double)N * H * W * C + (double)N * Ho * Wo * C) * (fmt == CONV_FMT_F32 ? 4 : 2));
-    if (fmt == CONV_FMT_F32) {
-        hipLaunchKernelGGL(maxpool_f32_kernel, dim3(grid_for(total * 2)), dim3(256), 0, ctx->stream, (const float *)x, N, H, W, C, k, stride,
-                           pad, Ho, Wo, (float *)y);
-        WSC_HIP(hipGetLastError());
-        return WSC_OK;
-    }
-    if (fmt == 1 && x_lo == nullptr && y_lo == nullptr && (long long)N * Ho <= 65535) {
-        const int per_row = Wo * (C / 8);
+    const bool f32 = x.is_f32();
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, ((double)N * H * W * C + (double)N * Ho * Wo * C) * (f32 ? 4 : 2));
+    const int per_row = Wo * (C / 8);
+    const bool rows = x.fmt() == 1 && (long long)N * Ho <= 65535; // IEEE half, one block row per output row
+    if (f32)
+        hipLaunchKernelGGL(maxpool_f32_kernel, dim3(grid_for(total * 2)), dim3(256), 0, ctx->stream, x.f32(), N, H, W, C, k, stride,
+                           pad, Ho, Wo, y.f32());
+    else if (rows && !x.lo && !y.lo)
         hipLaunchKernelGGL(maxpool_f16_kernel, dim3((unsigned)((per_row + 255) / 256), (unsigned)(N * Ho)), dim3(256), 0, ctx->stream,
-                           x, H, W, C, k, stride, pad, Ho, Wo, y);
-        WSC_HIP(hipGetLastError());
-        return WSC_OK;
-    }
-    if (fmt == 1 && x_lo != nullptr && y_lo != nullptr && (long long)N * Ho <= 65535) {
-        const int per_row = Wo * (C / 8);
+                           x.h16(), H, W, C, k, stride, pad, Ho, Wo, y.h16());
+    else if (rows && x.lo && y.lo)
         hipLaunchKernelGGL(maxpool_f16x2_kernel, dim3((unsigned)((per_row + 255) / 256), (unsigned)(N * Ho)), dim3(256), 0, ctx->stream,
-                           x, x_lo, H, W, C, k, stride, pad, Ho, Wo, y, y_lo);
-        WSC_HIP(hipGetLastError());
-        return WSC_OK;
-    }
-    hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, x_lo, N, H, W, C, k,
-                       stride, pad, Ho, Wo, y, y_lo, fmt);
+                           x.h16(), x.h16_lo(), H, W, C, k, stride, pad, Ho, Wo, y.h16(), y.h16_lo());
+    else
+        hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x.h16(), x.h16_lo(), N, H, W, C, k, stride,
+                           pad, Ho, Wo, y.h16(), y.h16_lo(), x.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
@@ -508,17 +499,17 @@ int launch_flip_add(wsc_ctx *ctx, const float *head, int B, int h, int w, int C,
     return WSC_OK;
 }
 
-int launch_gap_linear_sigmoid(wsc_ctx *ctx, const bf16_t *feat, const bf16_t *feat_lo, int B, int hw, int F,
-                              const float *Wc, const float *bias, int C, float *score, int fmt, int sample_stride) {
+int launch_gap_linear_sigmoid(wsc_ctx *ctx, Act feat, int B, int hw, int F, const float *Wc, const float *bias, int C, float *score,
+                              int sample_stride) {
     float *gapbuf = nullptr;
     WSC_TRY(wsc_ctx_cached_alloc(ctx, sizeof(float) * (size_t)B * F, (void **)&gapbuf));
     WscCachedGuard gapbuf_guard(ctx, gapbuf);
-    if (fmt == CONV_FMT_F32)
-        hipLaunchKernelGGL(gap_f32_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)B), dim3(64 * GAP_WAVES), 0, ctx->stream,
-                           (const float *)feat, hw, F, gapbuf, sample_stride);
+    const dim3 grid((unsigned)((F + 63) / 64), (unsigned)B), block(64 * GAP_WAVES);
+    if (feat.is_f32())
+        hipLaunchKernelGGL(gap_f32_kernel, grid, block, 0, ctx->stream, (const float *)feat.f32(), hw, F, gapbuf, sample_stride);
     else
-    hipLaunchKernelGGL(gap_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)B), dim3(64 * GAP_WAVES), 0, ctx->stream, feat, feat_lo, hw, F, gapbuf,
-                       fmt, sample_stride);
+        hipLaunchKernelGGL(gap_kernel, grid, block, 0, ctx->stream, (const bf16_t *)feat.h16(), (const bf16_t *)feat.h16_lo(), hw, F,
+                           gapbuf, feat.fmt(), sample_stride);
     hipLaunchKernelGGL(linear_sigmoid_kernel, dim3(B), dim3(256), F * sizeof(float), ctx->stream, (const float *)gapbuf, F, Wc, bias, C,
                        score);
     WSC_HIP(hipGetLastError());
@@ -526,33 +517,34 @@ int launch_gap_linear_sigmoid(wsc_ctx *ctx, const bf16_t *feat, const bf16_t *fe
     return WSC_OK;
 }
 
-int launch_bf16_to_f32(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, size_t n, float *y, int fmt) {
-    if (fmt == CONV_FMT_F32) { // (the activation is the fp32 tensor already)
-        WSC_HIP(hipMemcpyAsync(y, x, n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+int launch_act_to_f32(wsc_ctx *ctx, Act x, size_t n, float *y) {
+    if (x.is_f32()) { // (the activation is the fp32 tensor already)
+        WSC_HIP(hipMemcpyAsync(y, x.f32(), n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         return WSC_OK;
     }
-    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for((long long)n)), dim3(256), 0, ctx->stream, x, x_lo, n,
-                       y, fmt);
+    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for((long long)n)), dim3(256), 0, ctx->stream, (const bf16_t *)x.h16(),
+                       (const bf16_t *)x.h16_lo(), n, y, x.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
-int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, bf16_t *y, bf16_t *y_lo, int fmt) {
-    if (fmt == CONV_FMT_F32)
-        hipLaunchKernelGGL(relayout_f32_kernel<true>, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, x, N, C, HW, (float *)y);
+int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y) {
+    const dim3 grid(grid_for((long long)N * C * HW));
+    if (y.is_f32())
+        hipLaunchKernelGGL(relayout_f32_kernel<true>, grid, dim3(256), 0, ctx->stream, x, N, C, HW, y.f32());
     else
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, x, N, C,
-                       HW, y, y_lo, fmt);
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, ctx->stream, x, N, C, HW, y.h16(), y.h16_lo(), y.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
-int launch_nhwc_to_nchw(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int C, int HW, float *y, int fmt) {
-    if (fmt == CONV_FMT_F32)
-        hipLaunchKernelGGL(relayout_f32_kernel<false>, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, (const float *)x, N, C, HW, y);
+int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y) {
+    const dim3 grid(grid_for((long long)N * C * HW));
+    if (x.is_f32())
+        hipLaunchKernelGGL(relayout_f32_kernel<false>, grid, dim3(256), 0, ctx->stream, (const float *)x.f32(), N, C, HW, y);
     else
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for((long long)N * C * HW)), dim3(256), 0, ctx->stream, x, x_lo,
-                       N, C, HW, y, fmt);
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel, grid, dim3(256), 0, ctx->stream, (const bf16_t *)x.h16(), (const bf16_t *)x.h16_lo(), N,
+                           C, HW, y, x.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }

@@ -30,7 +30,7 @@ struct HostTensor {
 typedef std::unordered_map<std::string, HostTensor> Dict;
 
 struct ConvW {
-    bf16_t *w = nullptr;
+    void *w = nullptr; // packed weights: 16-bit, fp32 in WSC_PREC_F32 (make_conv)
     float *s1 = nullptr, *b1 = nullptr, *s2 = nullptr, *b2 = nullptr;
     int Cin = 0, Cout = 0, CoutPad = 0, kh = 1, kw = 1, stride = 1, pad = 0, relu = 0;
     ConvForm form = CONV_FORM_GENERIC;
@@ -66,7 +66,6 @@ struct wsc_net {
     wsc_ctx *ctx = nullptr;
     int arch = 0, C = 0, F = 0;
     wsc_precision prec = WSC_PREC_BF16;
-    int split = 0, fmt = 0; // conv_split(prec), conv_fmt(prec)
     std::vector<ConvW> convs;
     std::vector<Op> ops;
     int final_buf = 0;
@@ -93,13 +92,6 @@ int decode_precision(int precision, wsc_precision *prec) {
     *prec = (wsc_precision)precision;
     return WSC_OK;
 }
-void set_precision(wsc_net *net, wsc_precision prec) {
-    net->prec = prec;
-    net->split = conv_split(prec);
-    net->fmt = conv_fmt(prec);
-}
-// element i of an activation plane (16-bit, or fp32 behind the opaque pointer in WSC_PREC_F32: common.h ConvLaunch)
-bf16_t *elem_at(bf16_t *p, size_t i, wsc_precision prec) { return (bf16_t *)((char *)p + i * conv_elem_bytes(prec)); }
 
 int upload(wsc_net *net, const void *host, size_t bytes, void **out) {
     void *d = nullptr;
@@ -158,7 +150,7 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
         WSC_CHECK(Cin % 64 == 0, WSC_ERR_SHAPE, "conv with Cin=%d is not supported (need a multiple of 64)", Cin);
         c.Cin = Cin;
     } else if (form == CONV_FORM_STEM_ROWS) {
-        WSC_CHECK(Cin <= 4 && kw <= 7 && net->split == 2, WSC_ERR_SHAPE, "padded-stem conv needs Cin <= 4, kw <= 7, f16x3");
+        WSC_CHECK(Cin <= 4 && kw <= 7 && conv_split(net->prec) == 2, WSC_ERR_SHAPE, "padded-stem conv needs Cin <= 4, kw <= 7, f16x3");
         c.Cin = 4;
     } else {
         WSC_CHECK(Cin <= 4, WSC_ERR_SHAPE, "small-Cin conv needs Cin <= 4, got %d", Cin);
@@ -168,6 +160,7 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
     const ConvKLayout lay = conv_k_layout(kh, kw, c.Cin, form, net->prec);
     const int Kw = lay.Kw;
     const bool f32 = net->prec == WSC_PREC_F32;
+    const int fmt = conv_fmt(net->prec), split = conv_split(net->prec);
     std::vector<char> wp((size_t)c.CoutPad * Kw * conv_elem_bytes(net->prec), 0); // (zero bits = 0 in every format)
     // IEEE-half modes (f16, f16x3): every output channel's weights are stored times a power of two that puts the channel's
     // largest |w| into [2^12, 2^13), and the epilogue scale s1 takes the inverse -- exact in fp32, the accumulators are fp32.
@@ -177,7 +170,7 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
     // absolute error of 2^-25 against a maximum of >= 2^12 (bfloat16 has fp32's exponent range).
     std::vector<float> s1v(s1);
     std::vector<float> wscale(Cout, 1.f);
-    if (net->fmt == 1) {
+    if (fmt == 1) {
         const size_t per = (size_t)Cin * kh * kw;
         for (int co = 0; co < Cout; ++co) {
             float mx = 0.f;
@@ -203,15 +196,15 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
                 return;
             }
             v *= wsc;
-            const bf16_t h = f32_to_h16(v, net->fmt);
+            const bf16_t h = f32_to_h16(v, fmt);
             row[k] = h;
-            if (net->split) row[lay.lo_at + k] = f32_to_h16(v - h16_to_f32(h, net->fmt), net->fmt);
+            if (split) row[lay.lo_at + k] = f32_to_h16(v - h16_to_f32(h, fmt), fmt);
         };
         for (int ci = 0; ci < Cin; ++ci)
             for (int r = 0; r < kh; ++r)
                 for (int s = 0; s < kw; ++s) put(lay.index(ci, r, s), w->data[(((size_t)co * Cin + ci) * kh + r) * kw + s]);
     }
-    WSC_TRY(upload(net, wp.data(), wp.size(), (void **)&c.w));
+    WSC_TRY(upload(net, wp.data(), wp.size(), &c.w));
     auto up_vec = [&](const std::vector<float> &v, float **dst) -> int {
         std::vector<float> p(c.CoutPad, 0.f);
         for (int i = 0; i < Cout; ++i) p[i] = v[i];
@@ -230,8 +223,7 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
 // The weight- and precision-derived fields of a layer's launch; the caller adds what is its own (activations and their sizes,
 // residual, second input, output pitch, ...)
 ConvLaunch conv_launch(const ConvW &c, wsc_precision prec) {
-    ConvLaunch L;
-    memset(&L, 0, sizeof(L));
+    ConvLaunch L = {};
     L.w = c.w; L.s1 = c.s1; L.b1 = c.b1; L.s2 = c.s2; L.b2 = c.b2;
     L.Cin = c.Cin; L.Cout = c.Cout; L.CoutPad = c.CoutPad;
     L.kh = c.kh; L.kw = c.kw; L.stride = c.stride; L.pad = c.pad; L.relu = c.relu;
@@ -272,7 +264,7 @@ int resnet_conv(wsc_net *net, const Dict &d, const std::string &conv, const std:
 int build_resnet50_backbone(wsc_net *net, const Dict &d) {
     // stem: conv1 7x7 s2 p3 + bn1 + relu, maxpool 3x3 s2 p1          (resnet50.py:62-64, 96-99)
     // (f16x3: the padded-input form, staged like every other layer of that mode)
-    WSC_TRY(resnet_conv(net, d, "resnet50.conv1", "resnet50.bn1", 2, 3, 1, net->split == 2 ? CONV_FORM_STEM_ROWS : CONV_FORM_SMALL4, -1, 0, -1));
+    WSC_TRY(resnet_conv(net, d, "resnet50.conv1", "resnet50.bn1", 2, 3, 1, conv_split(net->prec) == 2 ? CONV_FORM_STEM_ROWS : CONV_FORM_SMALL4, -1, 0, -1));
     add_pool_op(net, 3, 2, 1, 0, 1);
     net->taps.push_back((int)net->ops.size() - 1); // stage1 = conv1, bn1, relu, maxpool (resnet50_irn.py:15)
     int cur = 1;
@@ -329,7 +321,7 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
                 WSC_TRY(resnet_conv(net, d, pre + ".conv2", pre + ".bn2", s, 1, 1, CONV_FORM_GENERIC, f[0], f[1], -1));
                 ConvW c;
                 WSC_TRY(make_conv(net, &wt, 1, 0, 1, CONV_FORM_GENERIC, sig, sh, nullptr, nullptr, &c));
-                if (net->split != 1) {
+                if (conv_split(net->prec) != 1) {
                     // the kernel reads the two inputs where they are: channel chunks [0, K1) from conv2's output, the rest from
                     // the block input at the block's stride (conv_igemm.hip, second A source)
                     WSC_TRY(add_conv_op(net, c, f[1], f[0], -1));
@@ -635,10 +627,16 @@ int build_m7_irn(wsc_net *net, const Dict &d) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+struct OpDims {
+    int H, W, C;    // the op's input (Op::in) as the op finds it
+    int Ho, Wo, Co; // its output; Co = all channels of the tensor it writes into (Op::pitch where set)
+    int H2, W2, C2; // the second input (Op::in2), zeros without one
+};
 struct Plan {
-    std::vector<int> H, W, C; // per op output dims
-    size_t max_act = 0;       // elements
-    int hf = 0, wf = 0;       // final feature map size
+    std::vector<OpDims> ops;
+    size_t max_act = 0; // elements
+    int hf = 0, wf = 0; // final feature map size
+    size_t out_elems(int N, int op) const { return (size_t)N * ops[op].Ho * ops[op].Wo * ops[op].Co; }
 };
 
 // (SH x SW network input: square for the fixed-size configurations, the image's own size for outsize = None)
@@ -648,62 +646,61 @@ int plan_dims(const wsc_net *net, int N, int SH, int SW, Plan *pl) {
     int bh[4] = {0, 0, 0, 0}, bw[4] = {0, 0, 0, 0}, bc[4] = {0, 0, 0, 0};
     pl->max_act = 0;
     for (const Op &op : net->ops) {
-        int H = op.in < 0 ? SH : bh[op.in], W = op.in < 0 ? SW : bw[op.in], C = op.in < 0 ? 4 : bc[op.in];
-        int Ho, Wo, Co;
+        OpDims d = {};
+        d.H = op.in < 0 ? SH : bh[op.in]; d.W = op.in < 0 ? SW : bw[op.in]; d.C = op.in < 0 ? 4 : bc[op.in];
         if (op.type == OP_CONV) {
             const ConvW &c = net->convs[op.conv];
-            Ho = (H + 2 * c.pad - c.kh) / c.stride + 1;
-            Wo = (W + 2 * c.pad - c.kw) / c.stride + 1;
-            Co = op.pitch ? op.pitch : c.Cout;
+            d.Ho = (d.H + 2 * c.pad - c.kh) / c.stride + 1;
+            d.Wo = (d.W + 2 * c.pad - c.kw) / c.stride + 1;
+            d.Co = op.pitch ? op.pitch : c.Cout;
             if (op.in2 >= 0) {
-                WSC_CHECK(c.kh == 1 && c.kw == 1 && c.stride == 1 && (H - 1) * op.ps < bh[op.in2] && (W - 1) * op.ps < bw[op.in2],
-                          WSC_ERR_INVALID, "internal: second input of a %d x %d layer does not cover its %d x %d output", c.kh, c.kw, H, W);
-                C += bc[op.in2];
+                d.H2 = bh[op.in2]; d.W2 = bw[op.in2]; d.C2 = bc[op.in2];
+                WSC_CHECK(c.kh == 1 && c.kw == 1 && c.stride == 1 && (d.H - 1) * op.ps < d.H2 && (d.W - 1) * op.ps < d.W2,
+                          WSC_ERR_INVALID, "internal: second input of a %d x %d layer does not cover its %d x %d output", c.kh, c.kw, d.H, d.W);
             }
-            WSC_CHECK(C == c.Cin, WSC_ERR_INVALID, "internal: channel mismatch %d vs %d", C, c.Cin);
+            WSC_CHECK(d.C + d.C2 == c.Cin, WSC_ERR_INVALID, "internal: channel mismatch %d vs %d", d.C + d.C2, c.Cin);
         } else if (op.type == OP_GATHER) {
-            Ho = (H - 1) / op.ps + 1;
-            Wo = (W - 1) / op.ps + 1;
-            Co = op.pitch;
-            WSC_CHECK(Ho == bh[op.out] && Wo == bw[op.out] && bc[op.out] == op.pitch && op.coff + C <= op.pitch, WSC_ERR_INVALID,
+            d.Ho = (d.H - 1) / op.ps + 1;
+            d.Wo = (d.W - 1) / op.ps + 1;
+            d.Co = op.pitch;
+            WSC_CHECK(d.Ho == bh[op.out] && d.Wo == bw[op.out] && bc[op.out] == op.pitch && op.coff + d.C <= op.pitch, WSC_ERR_INVALID,
                       "internal: gather into a %d x %d x %d tensor does not fit", bh[op.out], bw[op.out], bc[op.out]);
         } else {
-            Ho = (H + 2 * op.pp - op.pk) / op.ps + 1;
-            Wo = (W + 2 * op.pp - op.pk) / op.ps + 1;
-            Co = C;
+            d.Ho = (d.H + 2 * op.pp - op.pk) / op.ps + 1;
+            d.Wo = (d.W + 2 * op.pp - op.pk) / op.ps + 1;
+            d.Co = d.C;
         }
-        WSC_CHECK(Ho > 0 && Wo > 0, WSC_ERR_INVALID, "input size %d x %d too small for this network", SH, SW);
-        bh[op.out] = Ho; bw[op.out] = Wo; bc[op.out] = Co;
-        pl->H.push_back(Ho); pl->W.push_back(Wo); pl->C.push_back(Co);
-        const size_t e = (size_t)N * Ho * Wo * Co;
-        if (e > pl->max_act) pl->max_act = e;
+        WSC_CHECK(d.Ho > 0 && d.Wo > 0, WSC_ERR_INVALID, "input size %d x %d too small for this network", SH, SW);
+        bh[op.out] = d.Ho; bw[op.out] = d.Wo; bc[op.out] = d.Co;
+        pl->ops.push_back(d);
+        pl->max_act = std::max(pl->max_act, pl->out_elems(N, (int)pl->ops.size() - 1));
     }
     pl->hf = bh[net->final_buf];
     pl->wf = bw[net->final_buf];
     return WSC_OK;
 }
 
-// bytes of one plane of stage tap k (x_{k+1}), 256-byte aligned
-size_t tap_plane_bytes(const wsc_net *net, const Plan &pl, int N, int k) {
-    const int op = net->taps[k];
-    return align_up((size_t)N * pl.H[op] * pl.W[op] * pl.C[op] * conv_elem_bytes(net->prec), 256);
+// workspace bytes of the copies of the stage taps x1..x5 (run_backbone's `taps`)
+size_t taps_bytes(const wsc_net *net, const Plan &pl, int N) {
+    size_t b = 0;
+    for (int op : net->taps) b += act_bytes(pl.out_elems(N, op), net->prec);
+    return b;
 }
 
-// Runs the conv stack on N samples; returns pointers to the final feature map planes.  With copy_taps
-// the stage outputs x1..x5 (net->taps) are copied, plane by plane (hi [, lo]), to the start of the extra
-// region in stage order -- the rotating activation buffers are overwritten as the stack proceeds.
-int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, size_t extra_bytes,
-                 const bf16_t **feat, const bf16_t **feat_lo, int *hf, int *wf, void **extra, bool copy_taps = false, int SW = 0) {
+// Runs the conv stack on N samples; *feat is the final feature map.  *extra: `extra_bytes` of workspace for the caller.  With
+// `taps` the stage outputs x1..x5 (net->taps) are copied to the start of that region, in stage order, and *extra is what
+// follows them -- the rotating activation buffers are overwritten as the stack proceeds.
+int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, size_t extra_bytes, Act *feat, int *hf, int *wf,
+                 void **extra, std::vector<Act> *taps = nullptr, int SW = 0) {
     if (SW <= 0) SW = S; // S x SW input (SW given for the non-square, native-size path)
     Plan pl;
     WSC_TRY(plan_dims(net, N, S, SW, &pl));
-    const int planes = net->split ? 2 : 1;
     // f16x3 stem (CONV_FORM_STEM_ROWS): the NHWC4 input carries its zero border
     int in_h = S, in_w = SW, in_pad = 0;
     bool fused_stem = false;
     if (!net->ops.empty() && net->ops[0].type == OP_CONV && net->ops[0].in < 0 && net->convs[net->ops[0].conv].form == CONV_FORM_STEM_ROWS) {
         const ConvW &c0 = net->convs[net->ops[0].conv];
-        conv_stem_rows_input_dims(pl.H[0], pl.W[0], c0.stride, c0.kh, &in_h, &in_w);
+        conv_stem_rows_input_dims(pl.ops[0].Ho, pl.ops[0].Wo, c0.stride, c0.kh, &in_h, &in_w);
         in_pad = c0.pad;
         // conv 7x7 / 2 / 3 (-> 64) + BN + ReLU followed by MaxPool 3 / 2 / 1 (resnet50.py:54-64): one kernel (stem_pool.hip),
         // unless the conv's own output is wanted (a tap) or the path is switched off
@@ -712,82 +709,62 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
         fused_stem = ctx->opt[WSC_OPT_STEM_POOL_FUSED] && net->ops.size() > 1 && net->ops[1].type == OP_POOL &&
                      net->ops[1].in == net->ops[0].out && net->ops[1].pk == 3 && net->ops[1].ps == 2 && net->ops[1].pp == 1 &&
                      c0.kh == 7 && c0.kw == 7 && c0.stride == 2 && c0.pad == 3 && c0.Cout == 64 && c0.s2 == nullptr &&
-                     net->ops[0].res < 0 && net->fmt == 1 && !tapped;
+                     net->ops[0].res < 0 && conv_fmt(net->prec) == 1 && !tapped;
         if (fused_stem) {
             stem_pool_input_dims(S, SW, &in_h, &in_w);
             in_pad = 5;
         }
     }
-    const size_t in_bytes = align_up((size_t)N * in_h * in_w * 4 * conv_elem_bytes(net->prec), 256);
-    const size_t act_bytes = align_up(pl.max_act * conv_elem_bytes(net->prec), 256);
-    const size_t total = in_bytes * planes + act_bytes * 4 * planes + align_up(extra_bytes, 256);
+    const size_t in_elems = (size_t)N * in_h * in_w * 4;
     void *ws;
-    WSC_TRY(wsc_ctx_workspace(ctx, total, &ws));
+    WSC_TRY(wsc_ctx_workspace(ctx, act_bytes(in_elems, net->prec) + 4 * act_bytes(pl.max_act, net->prec) + align_up(extra_bytes, 256), &ws));
     char *p = (char *)ws;
-    bf16_t *xin = (bf16_t *)p; p += in_bytes;
-    bf16_t *xin_lo = nullptr;
-    if (net->split) { xin_lo = (bf16_t *)p; p += in_bytes; }
-    bf16_t *buf[4], *buf_lo[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 4; ++i) {
-        buf[i] = (bf16_t *)p; p += act_bytes;
-        if (net->split) { buf_lo[i] = (bf16_t *)p; p += act_bytes; }
-    }
+    const Act xin = act_carve(p, in_elems, net->prec);
+    Act buf[4];
+    for (Act &b : buf) b = act_carve(p, pl.max_act, net->prec);
+    if (taps)
+        for (int op : net->taps) taps->push_back(act_carve(p, pl.out_elems(N, op), net->prec));
     *extra = (void *)p;
 
-    if (in_pad > 0) WSC_TRY(launch_nchw_to_nhwc4_pad(ctx, x_dev, N, S, SW, in_h, in_w, in_pad, xin, xin_lo, net->fmt));
-    else WSC_TRY(launch_nchw_to_nhwc4(ctx, x_dev, N, S, SW, xin, xin_lo, net->fmt));
-    int bh[4] = {0, 0, 0, 0}, bw[4] = {0, 0, 0, 0}, bc[4] = {0, 0, 0, 0};
+    if (in_pad > 0) WSC_TRY(launch_nchw_to_nhwc4_pad(ctx, x_dev, N, S, SW, in_h, in_w, in_pad, xin));
+    else WSC_TRY(launch_nchw_to_nhwc4(ctx, x_dev, N, S, SW, xin));
     for (size_t i = 0; i < net->ops.size(); ++i) {
         const Op &op = net->ops[i];
-        const int H = op.in < 0 ? S : bh[op.in], W = op.in < 0 ? SW : bw[op.in], C = op.in < 0 ? 4 : bc[op.in];
-        const bf16_t *src = op.in < 0 ? xin : buf[op.in];
-        const bf16_t *src_lo = op.in < 0 ? xin_lo : buf_lo[op.in];
+        const OpDims &d = pl.ops[i];
+        const Act src = op.in < 0 ? xin : buf[op.in];
         if (fused_stem && i == 0) continue; // computed together with the pool that follows
         if (fused_stem && i == 1) {
             const ConvW &c0 = net->convs[net->ops[0].conv];
-            WSC_TRY(launch_stem_pool(ctx, xin, xin_lo, N, S, SW, c0.w, conv_k_layout(c0.kh, c0.kw, c0.Cin, c0.form, net->prec).Kw, c0.s1, c0.b1, c0.relu, buf[op.out], buf_lo[op.out]));
+            WSC_TRY(launch_stem_pool(ctx, xin, N, S, SW, (const bf16_t *)c0.w, conv_k_layout(c0.kh, c0.kw, c0.Cin, c0.form, net->prec).Kw, c0.s1,
+                                     c0.b1, c0.relu, buf[op.out]));
         } else if (op.type == OP_CONV) {
             const ConvW &c = net->convs[op.conv];
             ConvLaunch L = conv_launch(c, net->prec);
-            L.x = src; L.x_lo = src_lo;
-            L.res = op.res >= 0 ? buf[op.res] : nullptr;
-            L.res_lo = op.res >= 0 ? buf_lo[op.res] : nullptr;
-            L.y = buf[op.out]; L.y_lo = buf_lo[op.out];
-            if (op.in2 >= 0) {
-                L.x2 = buf[op.in2]; L.x2_lo = buf_lo[op.in2];
-                L.H2 = bh[op.in2]; L.W2 = bw[op.in2]; L.C2 = bc[op.in2]; L.stride2 = op.ps;
-            }
+            L.x = src;
+            if (op.res >= 0) L.res = buf[op.res];
+            L.y = buf[op.out].at(op.coff);
             L.ldy = op.pitch; // (0: dense)
-            if (op.pitch) {
-                L.y = elem_at(L.y, op.coff, net->prec);
-                if (L.y_lo) L.y_lo += op.coff;
+            if (op.in2 >= 0) {
+                L.x2 = buf[op.in2];
+                L.H2 = d.H2; L.W2 = d.W2; L.C2 = d.C2; L.stride2 = op.ps;
             }
-            L.N = N; L.H = H; L.W = W; L.Ho = pl.H[i]; L.Wo = pl.W[i];
+            L.N = N; L.H = d.H; L.W = d.W; L.Ho = d.Ho; L.Wo = d.Wo;
             if (c.form == CONV_FORM_STEM_ROWS && op.in < 0) on_padded_input(L, in_h, in_w);
             WSC_TRY(conv_igemm_launch(ctx, L));
         } else if (op.type == OP_GATHER) {
-            WSC_CHECK(net->split == 1, WSC_ERR_INVALID, "internal: the gathered shortcut input is a bf16x3 path");
-            WSC_TRY(launch_gather_strided(ctx, src, src_lo, N, H, W, C, op.ps, pl.H[i], pl.W[i], buf[op.out] + op.coff,
-                                          buf_lo[op.out] ? buf_lo[op.out] + op.coff : nullptr, op.pitch));
+            WSC_TRY(launch_gather_strided(ctx, src, N, d.H, d.W, d.C, op.ps, d.Ho, d.Wo, buf[op.out].at(op.coff), op.pitch));
         } else {
-            WSC_TRY(launch_maxpool(ctx, src, src_lo, N, H, W, C, op.pk, op.ps, op.pp, pl.H[i], pl.W[i], buf[op.out],
-                                   buf_lo[op.out], net->fmt));
+            WSC_TRY(launch_maxpool(ctx, src, N, d.H, d.W, d.C, op.pk, op.ps, op.pp, d.Ho, d.Wo, buf[op.out]));
         }
-        bh[op.out] = pl.H[i]; bw[op.out] = pl.W[i]; bc[op.out] = pl.C[i];
-        if (copy_taps)
+        if (taps)
             for (size_t k = 0; k < net->taps.size(); ++k)
                 if (net->taps[k] == (int)i) {
-                    char *dst = (char *)*extra;
-                    for (size_t j = 0; j < k; ++j) dst += tap_plane_bytes(net, pl, N, (int)j) * planes;
-                    const size_t nb = (size_t)N * pl.H[i] * pl.W[i] * pl.C[i] * conv_elem_bytes(net->prec);
-                    WSC_HIP(hipMemcpyAsync(dst, buf[op.out], nb, hipMemcpyDeviceToDevice, ctx->stream));
-                    if (net->split)
-                        WSC_HIP(hipMemcpyAsync(dst + tap_plane_bytes(net, pl, N, (int)k), buf_lo[op.out], nb,
-                                               hipMemcpyDeviceToDevice, ctx->stream));
+                    const size_t nb = pl.out_elems(N, (int)i) * conv_elem_bytes(net->prec);
+                    WSC_HIP(hipMemcpyAsync((*taps)[k].hi, buf[op.out].hi, nb, hipMemcpyDeviceToDevice, ctx->stream));
+                    if (buf[op.out].lo) WSC_HIP(hipMemcpyAsync((*taps)[k].lo, buf[op.out].lo, nb, hipMemcpyDeviceToDevice, ctx->stream));
                 }
     }
     *feat = buf[net->final_buf];
-    *feat_lo = buf_lo[net->final_buf];
     *hf = pl.hf;
     *wf = pl.wf;
     return WSC_OK;
@@ -822,7 +799,7 @@ int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n
     net->ctx = ctx;
     net->arch = arch;
     net->C = num_classes;
-    set_precision(net, prec);
+    net->prec = prec;
     int st;
     switch (arch) {
     case WSC_ARCH_RESNET50_CAM: st = build_resnet50(net, d); break;
@@ -879,7 +856,8 @@ static int run_head(wsc_ctx *ctx, const ConvLaunch &L) {
     if (conv_fmt(L.prec) == 1 && L.Cout <= 32 && L.CoutPad >= 32 && L.Cin % 256 == 0 && L.y_f32 != nullptr &&
         ctx->opt[WSC_OPT_CAM_HEAD_STREAM] != 0) {
         // (the streaming form checks packing and alignment itself; anything it does not take goes to the tiled kernel)
-        const int st = launch_cam_head(ctx, L.x, conv_split(L.prec) == 2 ? L.x_lo : nullptr, L.N * L.Ho * L.Wo, L.Cin, L.w,
+        WSC_CHECK(L.operands_match(), WSC_ERR_INVALID, "cam head: the input is not of the layer's precision %d", (int)L.prec);
+        const int st = launch_cam_head(ctx, L.x, L.N * L.Ho * L.Wo, L.Cin, (const bf16_t *)L.w,
                                        conv_k_layout(L.kh, L.kw, L.Cin, L.form, L.prec).Kw, L.CoutPad, L.s1, L.b1, L.Cout, L.relu, L.y_f32);
         if (st != WSC_ERR_INVALID) return st;
     }
@@ -902,20 +880,20 @@ int wsc_net_forward_cam_hw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev,
     Plan pl;
     WSC_TRY(plan_dims(net, N, S, SW, &pl));
     const size_t head_bytes = (size_t)N * pl.hf * pl.wf * net->C * sizeof(float);
-    const bf16_t *feat, *feat_lo;
+    Act feat;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, head_bytes, &feat, &feat_lo, &hf, &wf, &extra, false, SW));
+    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, head_bytes, &feat, &hf, &wf, &extra, nullptr, SW));
     float *head_out = (float *)extra;
     ConvLaunch L = conv_launch(net->head, net->prec);
-    L.x = feat; L.x_lo = feat_lo;
+    L.x = feat;
     L.y_f32 = head_out;
     L.N = N; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf;
     WSC_TRY(run_head(ctx, L));
     WSC_TRY(launch_flip_add(ctx, head_out, B, hf, wf, net->C, net->C, cam_dev));
     if (score_dev != nullptr)
-        WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, feat_lo, B, net->cls_max ? -(hf * wf) : hf * wf, net->F,
-                                          net->cls_w, net->cls_b, net->Ccls, score_dev, net->fmt, 2));
+        WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, B, net->cls_max ? -(hf * wf) : hf * wf, net->F, net->cls_w, net->cls_b, net->Ccls,
+                                          score_dev, 2));
     return WSC_OK;
 }
 
@@ -926,19 +904,19 @@ int wsc_net_forward_gradcam(wsc_ctx *ctx, const wsc_net *net, const float *x_dev
     WSC_CHECK(score_dev == nullptr || net->cls_w != nullptr, WSC_ERR_INVALID,
               "this architecture has no classifier branch (score_dev must be NULL)");
     WSC_HIP(hipSetDevice(ctx->device));
-    const bf16_t *feat, *feat_lo;
+    Act feat;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &feat_lo, &hf, &wf, &extra));
+    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &hf, &wf, &extra));
     ConvLaunch L = conv_launch(net->head, net->prec);
-    L.x = feat; L.x_lo = feat_lo;
+    L.x = feat;
     L.y_f32 = cams_dev; // fp32 NHWC [N][h][w][C]: the layout of np.einsum('ijkl,lm->ijkm')
     L.N = N; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf;
     L.relu = relu ? 1 : 0;
     WSC_TRY(run_head(ctx, L));
     if (score_dev != nullptr)
-        WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, feat_lo, N, net->cls_max ? -(hf * wf) : hf * wf, net->F,
-                                          net->cls_w, net->cls_b, net->Ccls, score_dev, net->fmt, 1));
+        WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, N, net->cls_max ? -(hf * wf) : hf * wf, net->F, net->cls_w, net->cls_b, net->Ccls,
+                                          score_dev, 1));
     return WSC_OK;
 }
 
@@ -946,11 +924,11 @@ int wsc_net_forward_features(wsc_ctx *ctx, const wsc_net *net, const float *x_de
     WSC_CHECK(ctx && net && x_dev && feat_dev, WSC_ERR_INVALID, "wsc_net_forward_features: null argument");
     WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_forward_features: N=%d S=%d", N, S);
     WSC_HIP(hipSetDevice(ctx->device));
-    const bf16_t *feat, *feat_lo;
+    Act feat;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &feat_lo, &hf, &wf, &extra));
-    return launch_bf16_to_f32(ctx, feat, feat_lo, (size_t)N * hf * wf * net->F, feat_dev, net->fmt);
+    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &hf, &wf, &extra));
+    return launch_act_to_f32(ctx, feat, (size_t)N * hf * wf * net->F, feat_dev);
 }
 
 // EdgeDisplacement.forward (resnet50_irn.py:212-232 / vgg16_irn.py:306-321) for B images: x is the
@@ -965,30 +943,25 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
     WSC_CHECK(B > 0 && S > 0 && feat_h > 0 && feat_w > 0, WSC_ERR_INVALID, "wsc_net_forward_edge: B=%d S=%d", B, S);
     WSC_HIP(hipSetDevice(ctx->device));
     const int N = 2 * B;
-    const int planes = net->split ? 2 : 1;
     Plan pl;
     WSC_TRY(plan_dims(net, N, S, &pl));
     const int NS = (int)net->taps.size(), NC = (int)net->cats.size();
     std::vector<int> Hs(NS), Ws(NS), Cs(NS);
-    std::vector<size_t> tap_off(NS);
-    size_t off = 0;
     for (int k = 0; k < NS; ++k) {
-        const int op = net->taps[k];
-        Hs[k] = pl.H[op]; Ws[k] = pl.W[op]; Cs[k] = pl.C[op];
-        tap_off[k] = off;
-        off += tap_plane_bytes(net, pl, N, k) * planes;
+        const OpDims &d = pl.ops[net->taps[k]];
+        Hs[k] = d.Ho; Ws[k] = d.Wo; Cs[k] = d.Co;
     }
     auto outdim = [](int v, int stride) { return (v - 1) / stride + 1; };
     std::vector<int> cat_c(NC), cat_h(NC), cat_w(NC);
-    std::vector<size_t> cat_off(NC), cat_bytes(NC);
+    std::vector<size_t> cat_elems(NC);
+    size_t off = taps_bytes(net, pl, N); // workspace after the backbone's: taps, concat buffers, then the scratch below
     for (int i = 0; i < NC; ++i) {
         const IrnCat &c = net->cats[i];
         cat_c[i] = c.channels;
         cat_h[i] = outdim(Hs[c.stage - 1], c.stride);
         cat_w[i] = outdim(Ws[c.stage - 1], c.stride);
-        cat_bytes[i] = align_up((size_t)N * cat_h[i] * cat_w[i] * cat_c[i] * conv_elem_bytes(net->prec), 256);
-        cat_off[i] = off;
-        off += cat_bytes[i] * planes;
+        cat_elems[i] = (size_t)N * cat_h[i] * cat_w[i] * cat_c[i];
+        off += act_bytes(cat_elems[i], net->prec);
     }
     const int He = cat_h[0], We = cat_w[0], Hd = cat_h[NC - 1], Wd = cat_w[NC - 1]; // edge / displacement maps
     WSC_CHECK(feat_h <= He && feat_w <= We && feat_h <= Hd && feat_w <= Wd, WSC_ERR_INVALID,
@@ -1003,58 +976,46 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
         part_bytes = std::max(part_bytes, group_norm_partial_bytes(N, ho, wo, h.groups));
         max_groups = std::max(max_groups, h.groups);
     }
-    const size_t ftmp_off = off; off += align_up(ftmp_elems * sizeof(float), 256);
-    const size_t part_off = off; off += align_up(part_bytes, 256);
-    const size_t stat_off = off; off += align_up(sizeof(float) * 2 * N * max_groups, 256);
-    const size_t e_off = off; off += align_up(sizeof(float) * (size_t)N * He * We, 256);
-    const size_t d_off = off; off += align_up(sizeof(float) * (size_t)N * Hd * Wd * 2, 256);
+    // head conv output, GroupNorm partial sums, GroupNorm statistics, edge map, displacement map
+    const size_t scratch[5] = {ftmp_elems * sizeof(float), part_bytes, sizeof(float) * 2 * N * max_groups,
+                               sizeof(float) * (size_t)N * He * We, sizeof(float) * (size_t)N * Hd * Wd * 2};
+    for (size_t b : scratch) off += align_up(b, 256);
 
-    const bf16_t *feat, *feat_lo;
+    Act feat;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, off, &feat, &feat_lo, &hf, &wf, &extra, true));
-    char *base = (char *)extra;
+    std::vector<Act> taps, cats;
+    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, off, &feat, &hf, &wf, &extra, &taps));
+    char *p = (char *)extra;
+    for (int i = 0; i < NC; ++i) cats.push_back(act_carve(p, cat_elems[i], net->prec));
+    char *sp[5];
+    for (int i = 0; i < 5; ++i) { sp[i] = p; p += align_up(scratch[i], 256); }
+    float *ftmp = (float *)sp[0], *e_out = (float *)sp[3], *d_out = (float *)sp[4];
+    void *gn_part = sp[1], *gn_stats = sp[2];
     // the padding channels of the edge concat feed zero weights but must not hold NaN bit patterns
-    WSC_HIP(hipMemsetAsync(base + cat_off[0], 0, cat_bytes[0] * planes, ctx->stream));
+    WSC_HIP(hipMemsetAsync(cats[0].hi, 0, act_bytes(cat_elems[0], net->prec), ctx->stream));
 
-    auto plane = [&](size_t o, size_t bytes, int which) -> bf16_t * {
-        return which == 0 ? (bf16_t *)(base + o) : (net->split ? (bf16_t *)(base + o + bytes) : nullptr);
-    };
-    auto run_conv = [&](const ConvW &c, const bf16_t *x, const bf16_t *x_lo, int H, int W, float *y_f32) -> int {
+    auto run_conv = [&](const ConvW &c, Act x, int H, int W, float *y_f32) -> int {
         ConvLaunch L = conv_launch(c, net->prec); // (1 x 1, no padding, no ReLU: build_irn_heads)
-        L.x = x; L.x_lo = x_lo;
+        L.x = x;
         L.y_f32 = y_f32;
         L.N = N; L.H = H; L.W = W; L.Ho = outdim(H, c.stride); L.Wo = outdim(W, c.stride);
         return conv_igemm_launch(ctx, L);
     };
-    float *ftmp = (float *)(base + ftmp_off);
     for (const IrnHead &h : net->heads) {
-        const bf16_t *x, *x_lo;
-        int sh, sw, sc;
-        if (h.src > 0) {
-            const int k = h.src - 1;
-            const size_t pb = tap_plane_bytes(net, pl, N, k);
-            x = plane(tap_off[k], pb, 0); x_lo = plane(tap_off[k], pb, 1);
-            sh = Hs[k]; sw = Ws[k]; sc = Cs[k];
-        } else {
-            const int ci = -h.src - 1;
-            x = plane(cat_off[ci], cat_bytes[ci], 0); x_lo = plane(cat_off[ci], cat_bytes[ci], 1);
-            sh = cat_h[ci]; sw = cat_w[ci]; sc = cat_c[ci];
-        }
+        const int k = h.src > 0 ? h.src - 1 : -h.src - 1; // a stage tap, or a concat buffer
+        const Act x = h.src > 0 ? taps[k] : cats[k];
+        const int sh = h.src > 0 ? Hs[k] : cat_h[k], sw = h.src > 0 ? Ws[k] : cat_w[k], sc = h.src > 0 ? Cs[k] : cat_c[k];
         WSC_CHECK(sc == h.conv.Cin, WSC_ERR_SHAPE, "IRNet head: %d input channels, the weights expect %d", sc, h.conv.Cin);
-        WSC_TRY(run_conv(h.conv, x, x_lo, sh, sw, ftmp));
+        WSC_TRY(run_conv(h.conv, x, sh, sw, ftmp));
         const int ho = outdim(sh, h.conv.stride), wo = outdim(sw, h.conv.stride);
-        WSC_TRY(launch_group_norm_stats(ctx, ftmp, N, ho, wo, h.conv.Cout, h.groups, 1e-5f, base + part_off,
-                                        base + stat_off));
+        WSC_TRY(launch_group_norm_stats(ctx, ftmp, N, ho, wo, h.conv.Cout, h.groups, 1e-5f, gn_part, gn_stats));
         const int di = h.dst;
-        WSC_TRY(launch_group_norm_apply(ctx, ftmp, base + stat_off, h.gamma, h.beta, N, ho, wo, h.conv.Cout, h.groups,
-                                        h.up, 1, plane(cat_off[di], cat_bytes[di], 0), plane(cat_off[di], cat_bytes[di], 1),
-                                        cat_h[di], cat_w[di], cat_c[di], h.coff, net->fmt));
+        WSC_TRY(launch_group_norm_apply(ctx, ftmp, gn_stats, h.gamma, h.beta, N, ho, wo, h.conv.Cout, h.groups,
+                                        h.up, 1, cats[di], cat_h[di], cat_w[di], cat_c[di], h.coff));
     }
-    float *e_out = (float *)(base + e_off), *d_out = (float *)(base + d_off);
-    WSC_TRY(run_conv(net->edge6, plane(cat_off[0], cat_bytes[0], 0), plane(cat_off[0], cat_bytes[0], 1), He, We, e_out));
-    WSC_TRY(run_conv(net->dp7b, plane(cat_off[NC - 1], cat_bytes[NC - 1], 0), plane(cat_off[NC - 1], cat_bytes[NC - 1], 1),
-                     Hd, Wd, d_out));
+    WSC_TRY(run_conv(net->edge6, cats[0], He, We, e_out));
+    WSC_TRY(run_conv(net->dp7b, cats[NC - 1], Hd, Wd, d_out));
     WSC_TRY(launch_edge_finish(ctx, e_out, He, We, d_out, Hd, Wd, B, feat_h, feat_w, net->mean_shift[0],
                                net->mean_shift[1], edge_dev, dp_dev));
     return WSC_OK;
@@ -1073,7 +1034,7 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
     const int generic = (precision & WSC_CONV_GENERIC) ? 1 : 0;
     wsc_precision prec;
     WSC_TRY(decode_precision(precision & ~WSC_CONV_GENERIC, &prec));
-    set_precision(&tmp, prec);
+    tmp.prec = prec;
     HostTensor wt;
     wt.data = w_host; wt.ndim = 4; wt.shape[0] = Cout; wt.shape[1] = Cin; wt.shape[2] = kh; wt.shape[3] = kw;
     std::vector<float> s1(Cout, 1.f), b1(Cout, 0.f);
@@ -1081,7 +1042,7 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
     if (shift_host) b1.assign(shift_host, shift_host + Cout);
     ConvForm form = CONV_FORM_GENERIC;
     if (Cin <= 4) form = kw <= 4 ? CONV_FORM_SMALL2 : CONV_FORM_SMALL4;
-    if (form == CONV_FORM_SMALL4 && tmp.split == 2 && (stride & 1) == 0 && kw <= 7) form = CONV_FORM_STEM_ROWS; // (padded input)
+    if (form == CONV_FORM_SMALL4 && conv_split(prec) == 2 && (stride & 1) == 0 && kw <= 7) form = CONV_FORM_STEM_ROWS; // (padded input)
     ConvW c;
     int st = make_conv(&tmp, &wt, stride, pad, relu, form, s1, b1, nullptr, nullptr, &c);
     auto cleanup = [&]() {
@@ -1090,36 +1051,28 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
     };
     if (st != WSC_OK) { cleanup(); return st; }
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-    const int planes = tmp.split ? 2 : 1;
     int in_h = H, in_w = W;
     if (form == CONV_FORM_STEM_ROWS) conv_stem_rows_input_dims(Ho, Wo, stride, kh, &in_h, &in_w);
-    const size_t eb = conv_elem_bytes(prec);
     const size_t in_e = (size_t)N * in_h * in_w * c.Cin, out_e = (size_t)N * Ho * Wo * Cout;
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     void *ws;
-    st = wsc_ctx_workspace(ctx, planes * (al(in_e * eb) + 2 * al(out_e * eb)), &ws);
+    st = wsc_ctx_workspace(ctx, act_bytes(in_e, prec) + 2 * act_bytes(out_e, prec), &ws);
     if (st != WSC_OK) { cleanup(); return st; }
     char *p = (char *)ws;
-    bf16_t *xi = (bf16_t *)p; p += al(in_e * eb);
-    bf16_t *xi_lo = nullptr; if (tmp.split) { xi_lo = (bf16_t *)p; p += al(in_e * eb); }
-    bf16_t *yo = (bf16_t *)p; p += al(out_e * eb);
-    bf16_t *yo_lo = nullptr; if (tmp.split) { yo_lo = (bf16_t *)p; p += al(out_e * eb); }
-    bf16_t *ri = nullptr, *ri_lo = nullptr;
-    if (residual_dev) { ri = (bf16_t *)p; p += al(out_e * eb); if (tmp.split) { ri_lo = (bf16_t *)p; p += al(out_e * eb); } }
-    if (form == CONV_FORM_STEM_ROWS) st = launch_nchw_to_nhwc4_pad(ctx, x_dev, N, H, W, in_h, in_w, pad, xi, xi_lo, tmp.fmt);
-    else if (form != CONV_FORM_GENERIC) st = launch_nchw_to_nhwc4(ctx, x_dev, N, H, W, xi, xi_lo, tmp.fmt);
-    else st = launch_nchw_to_nhwc(ctx, x_dev, N, Cin, H * W, xi, xi_lo, tmp.fmt);
-    if (st == WSC_OK && residual_dev) st = launch_nchw_to_nhwc(ctx, residual_dev, N, Cout, Ho * Wo, ri, ri_lo, tmp.fmt);
+    const Act xi = act_carve(p, in_e, prec), yo = act_carve(p, out_e, prec);
+    const Act ri = residual_dev ? act_carve(p, out_e, prec) : Act();
+    if (form == CONV_FORM_STEM_ROWS) st = launch_nchw_to_nhwc4_pad(ctx, x_dev, N, H, W, in_h, in_w, pad, xi);
+    else if (form != CONV_FORM_GENERIC) st = launch_nchw_to_nhwc4(ctx, x_dev, N, H, W, xi);
+    else st = launch_nchw_to_nhwc(ctx, x_dev, N, Cin, H * W, xi);
+    if (st == WSC_OK && residual_dev) st = launch_nchw_to_nhwc(ctx, residual_dev, N, Cout, Ho * Wo, ri);
     if (st == WSC_OK) {
         ConvLaunch L = conv_launch(c, prec);
-        L.x = xi; L.x_lo = xi_lo; L.res = ri; L.res_lo = ri_lo;
-        L.y = yo; L.y_lo = yo_lo;
+        L.x = xi; L.res = ri; L.y = yo;
         L.N = N; L.H = H; L.W = W; L.Ho = Ho; L.Wo = Wo;
         if (form == CONV_FORM_STEM_ROWS) on_padded_input(L, in_h, in_w);
         L.generic = generic;
         st = conv_igemm_launch(ctx, L);
     }
-    if (st == WSC_OK) st = launch_nhwc_to_nchw(ctx, yo, yo_lo, N, Cout, Ho * Wo, y_dev, tmp.fmt);
+    if (st == WSC_OK) st = launch_nhwc_to_nchw(ctx, yo, N, Cout, Ho * Wo, y_dev);
     cleanup();
     return st;
 }

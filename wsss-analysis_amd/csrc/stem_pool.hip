@@ -290,18 +290,19 @@ void stem_pool_input_dims(int H, int W, int *Hp, int *Wp) {
     *Wp += *Wp & 1; // 16-byte rows
 }
 
-// x / x_lo: the padded input (stem_pool_input_dims, launch_nchw_to_nhwc4_pad with pad 5); H, W: the image size.
-int launch_stem_pool(wsc_ctx *ctx, const bf16_t *x, const bf16_t *x_lo, int N, int H, int W, const bf16_t *w, int Kw, const float *s1,
-                     const float *b1, int relu, bf16_t *y, bf16_t *y_lo) {
+// x: the padded input (stem_pool_input_dims, launch_nchw_to_nhwc4_pad with pad 5); H, W: the image size.
+int launch_stem_pool(wsc_ctx *ctx, Act x, int N, int H, int W, const bf16_t *w, int Kw, const float *s1, const float *b1, int relu,
+                     Act y) {
+    WSC_CHECK(x.prec == WSC_PREC_F16X3 && y.prec == WSC_PREC_F16X3, WSC_ERR_INVALID, "stem_pool: f16x3 planes only");
     StemPoolArgs a;
-    a.x = x; a.x_lo = x_lo; a.w = w; a.s1 = s1; a.b1 = b1; a.y = y; a.y_lo = y_lo;
+    a.x = x.h16(); a.x_lo = x.h16_lo(); a.w = w; a.s1 = s1; a.b1 = b1; a.y = y.h16(); a.y_lo = y.h16_lo();
     stem_pool_input_dims(H, W, &a.Hp, &a.Wp);
     a.Kw = Kw; a.relu = relu;
     a.range = ctx->range_dev;
     a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1;
     a.Hq = (a.Ho + 2 - 3) / 2 + 1; a.Wq = (a.Wo + 2 - 3) / 2 + 1;
     a.nti = (a.Hq + PQ - 1) / PQ; a.ntj = (a.Wq + PQ - 1) / PQ;
-    WSC_CHECK(x_lo != nullptr && y_lo != nullptr && Kw == 7 * 64, WSC_ERR_INVALID, "stem_pool: f16x3 planes and the 7-row packing only");
+    WSC_CHECK(x.lo != nullptr && y.lo != nullptr && Kw == 7 * 64, WSC_ERR_INVALID, "stem_pool: f16x3 planes and the 7-row packing only");
     const long long nblk = (long long)N * a.nti * a.ntj;
     WSC_CHECK(nblk < (1ll << 31), WSC_ERR_SHAPE, "stem_pool: too many tiles");
     WSC_TRY(wsc_set_max_dynamic_lds(ctx, reinterpret_cast<const void *>(stem_pool_kernel), LDS_BYTES));
