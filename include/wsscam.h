@@ -408,6 +408,24 @@ int wsc_label_unary_from_cam(wsc_ctx *ctx, const float *highres_dev, int B, int 
 int wsc_ir_label_combine(wsc_ctx *ctx, const int32_t *fg_pred_dev, const int32_t *bg_pred_dev, const int32_t *keys_host,
                          int B, int M, int N, uint8_t *conf_dev);
 
+/* ---- SEC / DSRG (03a_sec-dsrg): the host py_funcs of the training graph ------------------------ */
+
+/* DSRG seeded region growing (03a_sec-dsrg/DSRG.py:7-62 single_generate_seed_step, batch driver :356-371): per image,
+ * e = prob * tag, the candidate class of a pixel by the mask arithmetic of :28-39 (arg-max over the tagged classes, foreground
+ * above th_f / background above th_b), and for every tagged class c the connected components of the pixels whose candidate
+ * is c; a component that holds a pixel with cue[p][c] == 1 gets cue[p][c] = 1 everywhere except on pixels that are seeded for
+ * exactly one other class (those still connect).  Nothing is ever cleared.
+ * ASSUMPTION: the reference's labeller lib/CC_labeling_8.py is not in the reference tree; by its name and upstream DSRG the
+ * components are 8-CONNECTED, label 0 means "not a candidate of c", and such pixels are never filled.
+ *   tags_dev  float32 [B][C]          0/1
+ *   cues_dev  float32 [B][H][W][C]    0/1   (NHWC, as the reference's py_func receives it)
+ *   probs_dev float32 [B][H][W][C]
+ *   out_dev   float32 [B][H][W][C]    may be the same buffer as cues_dev
+ * th_f / th_b are arguments (reference constants 0.5 / 0.7).  1 <= C <= 32; H * W <= 8192 (an image's label plane lives in
+ * LDS; the reference's maps are 41 x 41, model.py:35): WSC_ERR_INVALID beyond, before any launch. */
+int wsc_dsrg_seed_grow(wsc_ctx *ctx, const float *tags_dev, const float *cues_dev, const float *probs_dev,
+                       int B, int H, int W, int C, float th_f, float th_b, float *out_dev);
+
 /* ---- HistoSegNet post-processing (03c_hsn/utilities.py:231-397), device resident ---------- */
 
 /* HSN grad_cam after the einsum (utilities.py:262-277), for the NHWC maps of wsc_net_forward_gradcam(relu = 0):

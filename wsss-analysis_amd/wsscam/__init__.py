@@ -7,6 +7,7 @@ libwsscam (HIP, gfx950).  Sub-packages keep the reference's module names:
     wsscam.misc.imutils / torchutils          03b_irn/misc (not in the reference tree)
     wsscam.hsn.utilities.dcrf_process         03c_hsn/utilities.py:399-445
     wsscam.cues.utilities.grad_cam ...        02_cues/utilities.py
+    wsscam.secdsrg.generate_seed_step / crf_layer   03a_sec-dsrg/DSRG.py:356-369, :323-332 (host py_funcs)
 
 There is no CPU fallback: every compute entry point goes through the C ABI of
 include/wsscam.h and raises WscError when the library or a gfx950 device is missing.

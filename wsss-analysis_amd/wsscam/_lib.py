@@ -124,6 +124,7 @@ _SIGNATURES = {
     "wsc_resize_u8": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "wsc_label_unary_from_cam": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     "wsc_ir_label_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "wsc_dsrg_seed_grow": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
     "wsc_hsn_gradcam_post": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i]),
     "wsc_hsn_voc_background": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "wsc_hsn_class_mass": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -866,6 +867,12 @@ def resize_u8(ctx, images_dev, sizes, offsets, out_hw, out_dev):
 def label_unary_from_cam(ctx, highres_dev, B, K, N, thres, gt_prob, unary_dev, labels_dev=None):
     check(ctx._lib.wsc_label_unary_from_cam(ctx.h, _ptr(highres_dev), B, K, N, float(thres), float(gt_prob), _ptr(unary_dev),
                                             _ptr(labels_dev)))
+
+
+def dsrg_seed_grow(ctx, tags_dev, cues_dev, probs_dev, B, H, W, C, out_dev, th_f=0.5, th_b=0.7):
+    """wsc_dsrg_seed_grow: DSRG seeded region growing of a batch (NHWC float32); out_dev may be cues_dev."""
+    check(ctx._lib.wsc_dsrg_seed_grow(ctx.h, _ptr(tags_dev), _ptr(cues_dev), _ptr(probs_dev), int(B), int(H), int(W), int(C),
+                                      float(th_f), float(th_b), _ptr(out_dev)))
 
 
 def ir_label_combine(ctx, fg_pred_dev, bg_pred_dev, keys, N, conf_dev):
