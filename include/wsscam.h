@@ -426,6 +426,41 @@ int wsc_ir_label_combine(wsc_ctx *ctx, const int32_t *fg_pred_dev, const int32_t
 int wsc_dsrg_seed_grow(wsc_ctx *ctx, const float *tags_dev, const float *cues_dev, const float *probs_dev,
                        int B, int H, int W, int C, float th_f, float th_b, float *out_dev);
 
+/* ---- 02_cues: the localization seeds SEC / DSRG train on (02_cues/utilities.py:183-278 get_localization_cues /
+ * get_localization_cues_sec, 02_cues/adp_cues.py:304-339 update_cues; consumer 03a_sec-dsrg/model.py:238-246) ---- */
+
+/* The gated, channel-selected, resized Grad-CAM stack, from the NHWC maps of wsc_net_forward_gradcam in place:
+ *   out[b][c] = bilinear(cams[b][:, :, chan[c]] * gate[b][c])  to S x S
+ * -- exactly the bits of "multiply by the 0/1 gate on the host, transpose NHWC -> NCHW, wsc_bilinear_resize" (one sampler,
+ * csrc/bilerp.h; the gate is a multiplication here too, so a gated negative value is -0 on both paths).
+ *   cams_nhwc_dev float32 [B][h][w][C_all];  chan_host int32 [C], each in [0, C_all);  gate_dev float32 [B][C] or NULL (all 1);
+ *   out_dev float32 [B][C][S][S]. */
+int wsc_cue_maps(wsc_ctx *ctx, const float *cams_nhwc_dev, int B, int h, int w, int C_all, const int32_t *chan_host, int C,
+                 const float *gate_dev, int S, float *out_dev);
+
+/* Seed label maps of a batch.  The localization stack has L = C + (bg_dev != NULL) channels; with bg_dev channel 0 is the
+ * background and foreground class c is channel c + 1, else class c is channel c.
+ *   foreground mask of class c: (double)fg[b][c][p] > thresh * (double)max_c, product and comparison in double as numpy forms
+ *     them from a Python-float thresh and float64 maps.  max_c is the maximum of class c over the WHOLE BATCH when
+ *     per_image_max == 0 (utilities.py:218,262 -- SURVEY Q7), over image b's own map when per_image_max != 0
+ *     (adp_cues.py:322-323).  Maps of either sign are legal (the ADP background channel can be <= 0 everywhere); a class whose
+ *     maximum is 0 has an empty mask.
+ *   background mask: s[p] = sum_k (double)bg[b][k][p], added sequentially in channel order from 0 (np.sum(axis=0) of the float64
+ *     stack); m = 3 x 3 median of s with scipy.ndimage's default mode='reflect' border (the edge sample is repeated); the mask
+ *     is m[p] < sorted(m)[int(bg_fraction * H * W)], strict -- a constant plane yields no background seed.
+ *   overlap resolution: the area of a channel is the pixel count of its mask; label[b][p] = k + 1 for the covering channel k of
+ *     the smallest area, 0 where no mask covers the pixel.  TIE RULE: among covering channels of equal area the HIGHER channel
+ *     index wins -- "visit the masks from the largest to the smallest, each paints over what is there" under
+ *     np.argsort(-area, kind='stable').  The reference calls np.argsort(-area) with the default kind, whose order among equal
+ *     areas is unspecified; its result on such pixels is not a contract.
+ *   fg_dev float32 [B][C][H][W];  bg_dev float32 [B][Cb][H][W] or NULL;  label_dev uint8 [B][H*W];
+ *   area_dev int32 [B][L] or NULL: the mask areas.  The inputs are not modified.
+ * Limits, checked before any launch (WSC_ERR_INVALID): 1 <= L <= 32; H * W <= 4096 (an image's planes live in LDS; the
+ * reference's maps are 41 x 41); B, C, H, W >= 1 and Cb >= 1 with bg_dev; 0 <= bg_fraction < 1; only bg_dev and area_dev may be
+ * NULL.  NaN inputs are out of contract. */
+int wsc_cue_seeds(wsc_ctx *ctx, const float *fg_dev, const float *bg_dev, int B, int C, int Cb, int H, int W, double thresh,
+                  int per_image_max, double bg_fraction, uint8_t *label_dev, int32_t *area_dev);
+
 /* ---- HistoSegNet post-processing (03c_hsn/utilities.py:231-397), device resident ---------- */
 
 /* HSN grad_cam after the einsum (utilities.py:262-277), for the NHWC maps of wsc_net_forward_gradcam(relu = 0):

@@ -13,6 +13,7 @@
 //   i1 = i0 + (i0 < in-1); l1 = src - i0; l0 = 1 - l1;
 //   out = lh0*(lw0*a + lw1*b) + lh1*(lw0*c + lw1*d)
 #include "common.h"
+#include "bilerp.h" // src_index, bilerp: shared with cue_seeds.hip
 
 #include <algorithm>
 #include <cstring>
@@ -27,26 +28,6 @@ struct TailJob {
 };
 
 constexpr int PIX_PER_BLOCK = 4096;
-
-__device__ __forceinline__ void src_index(int dst, float scale, int in, int &i0, int &i1, float &l0, float &l1) {
-    float s = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-    l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-    l0 = 1.f - l1;
-}
-
-__device__ __forceinline__ float bilerp(const float *src, int w, int y0, int y1, float ly0, float ly1, int x0, int x1,
-                                        float lx0, float lx1) {
-    // the fused multiply-adds are spelled out (not left to -ffp-contract): every kernel that samples a map --
-    // cam_tail_kernel, cam_max_kernel, cam_unary_kernel, bilinear_kernel -- then computes the same bits
-    const float top = __builtin_fmaf(lx0, src[y0 * w + x0], lx1 * src[y0 * w + x1]);
-    const float bot = __builtin_fmaf(lx0, src[y1 * w + x0], lx1 * src[y1 * w + x1]);
-    return __builtin_fmaf(ly0, top, ly1 * bot);
-}
 
 // -log(clip(p, 1e-5, 1)) of pydensecrf.utils.unary_from_softmax (03c_hsn/utilities.py:431): the clip is one median, the
 // logarithm the hardware log2 times ln 2 (|error| <= ~2e-6 on values up to 11.5; the tests hold the unaries to 2e-5 x

@@ -67,6 +67,7 @@ _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
+_d = ctypes.c_double
 
 # name -> (restype, argtypes); must list every symbol include/wsscam.h declares
 _SIGNATURES = {
@@ -125,6 +126,8 @@ _SIGNATURES = {
     "wsc_label_unary_from_cam": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     "wsc_ir_label_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "wsc_dsrg_seed_grow": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
+    "wsc_cue_maps": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "wsc_cue_seeds": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d, _vp, _vp]),
     "wsc_hsn_gradcam_post": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i]),
     "wsc_hsn_voc_background": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "wsc_hsn_class_mass": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -873,6 +876,20 @@ def dsrg_seed_grow(ctx, tags_dev, cues_dev, probs_dev, B, H, W, C, out_dev, th_f
     """wsc_dsrg_seed_grow: DSRG seeded region growing of a batch (NHWC float32); out_dev may be cues_dev."""
     check(ctx._lib.wsc_dsrg_seed_grow(ctx.h, _ptr(tags_dev), _ptr(cues_dev), _ptr(probs_dev), int(B), int(H), int(W), int(C),
                                       float(th_f), float(th_b), _ptr(out_dev)))
+
+
+def cue_maps(ctx, cams_nhwc_dev, B, h, w, C_all, chan, gate_dev, S, out_dev):
+    """wsc_cue_maps: out[b][c] = bilinear(cams[b][:, :, chan[c]] * gate[b][c]) to S x S, float32 [B][len(chan)][S][S]."""
+    ch = np.ascontiguousarray(chan, dtype=np.int32)
+    check(ctx._lib.wsc_cue_maps(ctx.h, _ptr(cams_nhwc_dev), int(B), int(h), int(w), int(C_all), ch.ctypes.data, len(ch),
+                                _ptr(gate_dev), int(S), _ptr(out_dev)))
+
+
+def cue_seeds(ctx, fg_dev, bg_dev, B, C, Cb, H, W, thresh, label_dev, area_dev=None, per_image_max=False, bg_fraction=0.1):
+    """wsc_cue_seeds: float32 [B][C][H][W] foreground (+ [B][Cb][H][W] background, or None) stacks -> uint8 [B][H*W] seed labels
+    (0 = none, k + 1 = localization channel k) and, with area_dev, int32 [B][L] mask areas."""
+    check(ctx._lib.wsc_cue_seeds(ctx.h, _ptr(fg_dev), _ptr(bg_dev), int(B), int(C), int(Cb), int(H), int(W), float(thresh),
+                                 int(bool(per_image_max)), float(bg_fraction), _ptr(label_dev), _ptr(area_dev)))
 
 
 def ir_label_combine(ctx, fg_pred_dev, bg_pred_dev, keys, N, conf_dev):

@@ -70,7 +70,13 @@ def read_batch(images, size, img_mean, img_std, ctx=None):
 
 
 def gen_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=True, is_verbose=True, *, models=None,
-             alphas=None, thresholds=None, images=None, labels=None, out_dir=None, class_names=None, settings=None):
+             alphas=None, thresholds=None, images=None, labels=None, out_dir=None, class_names=None, settings=None,
+             device_seeds=False):
+    """device_seeds=True: everything between the CNN and the pickle's np.where stays on the device -- only the scores (B, C_all)
+    come to the host and the gate (B, C) goes up; wsc_cue_maps gates, selects and resizes the Grad-CAM buffer of each model in
+    place, wsc_cue_seeds thresholds, median-filters, ranks and resolves the overlaps, and B x 1681 label bytes come back.
+    Same seeds as the host path except where two covering masks of a pixel have the same area: there the host path's
+    np.argsort(-area) order is unspecified and the device gives the higher channel (include/wsscam.h)."""
     assert dataset in ["VOC2012", "DeepGlobe", "DeepGlobe_balanced"], "ADP: use gen_cues_adp"
     assert model_type in ["X1.7", "M7", "VGG16"]
     assert batch_size > 0 and set_name in [None, "tuning", "segtest"]
@@ -118,6 +124,10 @@ def gen_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=T
             print("\tBatch #%d of %d" % (ib + 1, n_batches))
         norm, _ = read_batch(images[lo:hi], (img_size, img_size), mean, std, ctx=models["fg"].ctx)
         H, is_pass = {}, {}
+        if device_seeds:
+            cues = _device_seed_batch(cues, models, alphas, thr, fgbg_modes, norm, labels[lo:hi][:, keep_inds], keep_inds,
+                                      list(range(lo, hi)), thresh, dataset == "VOC2012")
+            continue
         for m in fgbg_modes:
             cams, scores = cu.conv_and_cams(models[m], np.asarray(alphas[m]), norm, relu=True, want_scores=True)
             scores = scores[:, keep_inds]
@@ -136,6 +146,33 @@ def gen_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=T
     with open(os.path.join(out_dir, name), "wb") as f:
         pickle.dump(cues, f)
     return cues
+
+
+def _device_seed_batch(cues, models, alphas, thr, fgbg_modes, norm, labels_keep, keep_inds, idx, thresh, is_voc):
+    """One batch of gen_cues(device_seeds=True): the Grad-CAM maps never leave the device."""
+    from .. import _lib
+
+    n, C = len(idx), len(keep_inds)
+    seed_ctx = models["fg"].ctx
+    stacks, is_pass, keep = {}, {}, []
+    for m in fgbg_modes:
+        cams_dev, scores, (B, h, w, C_all), ctx = cu.conv_and_cams_device(models[m], np.asarray(alphas[m]), norm, relu=True,
+                                                                         want_scores=True)
+        is_pass[m] = np.greater_equal(scores[:, keep_inds], thr[m]) * labels_keep
+        gate_dev = ctx.to_device(np.ascontiguousarray(is_pass[m], dtype=np.float32), pooled=True)
+        stacks[m] = ctx.alloc(n * C * SEED_SIZE * SEED_SIZE * 4, pooled=True)
+        _lib.cue_maps(ctx, cams_dev, n, h, w, C_all, keep_inds, gate_dev, SEED_SIZE, stacks[m])
+        if ctx is not seed_ctx:
+            seed_ctx.wait_for(ctx)
+        keep += [cams_dev, gate_dev]
+    lab_dev = seed_ctx.alloc(n * SEED_SIZE * SEED_SIZE, pooled=True)
+    _lib.cue_seeds(seed_ctx, stacks["fg"], stacks.get("bg"), n, C, C, SEED_SIZE, SEED_SIZE, thresh, lab_dev)
+    labels = seed_ctx.to_host(lab_dev, (n, SEED_SIZE, SEED_SIZE), np.uint8)
+    for buf in keep + list(stacks.values()) + [lab_dev]:
+        buf.free()
+    # get_fgbg_cues' channel 0 is the background, so a foreground class k is pickled as k + 1 there (demo.py:213-219)
+    class_inds = [np.where(is_pass["fg"][i])[0] + (1 if is_voc else 0) for i in range(n)]
+    return cu.cues_from_label_maps(cues, labels, class_inds, idx)
 
 
 def gen_cues_adp(model_type, thresh, batch_size, size, cues_dir, set_name, is_verbose, *, model, alpha, thresholds,

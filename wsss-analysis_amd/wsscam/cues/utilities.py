@@ -50,9 +50,9 @@ def _to_nchw(images):
     return np.ascontiguousarray(np.transpose(x, (0, 3, 1, 2)))
 
 
-def conv_and_cams(input_model, weights, images, relu, want_scores=False):
-    """One device pass: (cams (B,h,w,C) float32 = [relu] einsum(conv_val, weights), scores (B,C) or None); conv_val is the
-    final Activation's output (pre-BatchNorm, `gradcam_net(pre_bn=True)`), as K.function([input], [conv_output]) gives it."""
+def conv_and_cams_device(input_model, weights, images, relu, want_scores=False):
+    """The device pass of conv_and_cams with the maps left where they are: (cams_dev float32 [B][h][h][C], scores (B, C) on the
+    host or None, (B, h, h, C), ctx)."""
     net, ctx = input_model.gradcam_net(weights)
     x = _to_nchw(images)
     B, S = x.shape[0], x.shape[2]
@@ -62,9 +62,15 @@ def conv_and_cams(input_model, weights, images, relu, want_scores=False):
     cams_dev = ctx.alloc(B * h * h * C * 4)
     score_dev = ctx.alloc(B * C * 4) if want_scores else None
     net.forward_gradcam(x_dev, B, S, relu, cams_dev, score_dev)
-    cams = ctx.to_host(cams_dev, (B, h, h, C), np.float32)
     scores = ctx.to_host(score_dev, (B, C), np.float32) if want_scores else None
-    return cams, scores
+    return cams_dev, scores, (B, h, h, C), ctx
+
+
+def conv_and_cams(input_model, weights, images, relu, want_scores=False):
+    """One device pass: (cams (B,h,w,C) float32 = [relu] einsum(conv_val, weights), scores (B,C) or None); conv_val is the
+    final Activation's output (pre-BatchNorm, `gradcam_net(pre_bn=True)`), as K.function([input], [conv_output]) gives it."""
+    cams_dev, scores, shape, ctx = conv_and_cams_device(input_model, weights, images, relu, want_scores)
+    return ctx.to_host(cams_dev, shape, np.float32), scores
 
 
 def _upsample_nhwc(ctx, cams, size):
@@ -159,3 +165,52 @@ def update_cues_adp(cues, gradcam, class_inds, indices, thresh):
     gradcam = np.asarray(gradcam)
     loc = (gradcam > thresh * np.max(gradcam, axis=(2, 3))[:, :, None, None]).astype("int64")
     return _resolve_and_store(cues, loc, class_inds, indices)
+
+
+# ---- the same seeds on the device (csrc/cue_seeds.hip) --------------------------------------------------------------------
+def _exact_float32(a, name):
+    a = np.asarray(a)
+    a32 = np.ascontiguousarray(a, dtype=np.float32)
+    if a.dtype != np.float32 and not np.array_equal(a32.astype(np.float64), a.astype(np.float64)):
+        raise ValueError("%s is not exactly representable in float32: rounding it would move a seed threshold" % name)
+    return a32
+
+
+def seed_label_maps(H_fg, H_bg, thresh, per_image_max=False, ctx=None):
+    """wsc_cue_seeds on host stacks: H_fg (B, C, H, W), H_bg (B, Cb, H, W) or None -> (labels uint8 (B, H, W), areas int32
+    (B, L)), L = C + (H_bg is not None).  label k + 1 = localization channel k (channel 0 the background when H_bg is given --
+    get_fgbg_cues' layout; else class k -- get_fg_cues', and update_cues_adp's with per_image_max=True), 0 = no seed.  An
+    overlap goes to the covering mask of the smallest area, the higher channel among equal areas (include/wsscam.h).  The maps
+    must be exactly representable in float32 (what resize_stack returns is): ValueError otherwise."""
+    from ..misc.imutils import default_context
+
+    ctx = ctx or default_context()
+    fg = _exact_float32(H_fg, "H_fg")
+    bg = None if H_bg is None else _exact_float32(H_bg, "H_bg")
+    if fg.ndim != 4 or (bg is not None and (bg.ndim != 4 or bg.shape[0] != fg.shape[0] or bg.shape[2:] != fg.shape[2:])):
+        raise ValueError("H_fg (B, C, H, W) and H_bg (B, Cb, H, W) expected")
+    B, C, H, W = fg.shape
+    L = C + (bg is not None)
+    fg_dev = ctx.to_device(fg, pooled=True)
+    bg_dev = None if bg is None else ctx.to_device(bg, pooled=True)
+    lab_dev, area_dev = ctx.alloc(B * H * W, pooled=True), ctx.alloc(B * L * 4, pooled=True)
+    _lib.cue_seeds(ctx, fg_dev, bg_dev, B, C, 0 if bg is None else bg.shape[1], H, W, thresh, lab_dev, area_dev,
+                   per_image_max=per_image_max)
+    out = ctx.to_host(lab_dev, (B, H, W), np.uint8), ctx.to_host(area_dev, (B, L), np.int32)
+    for buf in (fg_dev, bg_dev, lab_dev, area_dev):
+        if buf is not None:
+            buf.free()
+    return out
+
+
+def cues_from_label_maps(cues, labels, class_inds, indices):
+    """The pickle layout of _resolve_and_store from seed label maps (B, H, W), label = channel + 1: `'%d_cues'` is exactly what
+    np.where(onehot) gives -- int64 (3, n) rows (class, row, col), ordered by class, then row, then column."""
+    labels = np.asarray(labels)
+    for i, x in enumerate(indices):
+        rows, cols = np.nonzero(labels[i])  # row-major
+        cls = labels[i][rows, cols].astype(np.int64) - 1
+        order = np.argsort(cls, kind="stable")
+        cues["%d_labels" % x] = class_inds[i]
+        cues["%d_cues" % x] = np.array([cls[order], rows[order].astype(np.int64), cols[order].astype(np.int64)], dtype=np.int64)
+    return cues
