@@ -461,6 +461,33 @@ int wsc_cue_maps(wsc_ctx *ctx, const float *cams_nhwc_dev, int B, int h, int w, 
 int wsc_cue_seeds(wsc_ctx *ctx, const float *fg_dev, const float *bg_dev, int B, int C, int Cb, int H, int W, double thresh,
                   int per_image_max, double bg_fraction, uint8_t *label_dev, int32_t *area_dev);
 
+/* ---- SEC / DSRG prediction tail (03a_sec-dsrg/model.py:665-719): eval_miou with is_eval=True, the glue around the dense CRF ----
+ * Both calls take a ragged batch packed back to back with host offset arrays (the convention of wsc_sem_seg_finish and
+ * wsc_label_confusion_nn) and run as ONE launch over the batch.  The resize is the sampler of wsc_bilinear_resize
+ * (csrc/bilerp.h: half-pixel centres, clamped, separate fp32 scales h/H and w/W), so a resized value has the bits that
+ * wsc_bilinear_resize gives for that class plane, and equal source and output sizes pass the map through unchanged (weights
+ * exactly 1 and 0).  That rule is cv2's INTER_LINEAR rule (csrc/hsn.hip); cv2 itself is absent offline, parity with its
+ * float arithmetic is unpinned.
+ * Limits, checked before any launch (WSC_ERR_INVALID): 1 <= C <= 32; 1 <= B <= 65535; every size >= 1 and every image's pixel
+ * count within int32; no NULL pointer. */
+
+/* cv2.resize(prob, (W, H)) followed by the unary of lib.crf.crf_inference(use_log=True)  (model.py:686,689):
+ *   U[b][c][p] = -log( bilinear(prob[b][:, :, c])[p] )
+ * prob_dev: image b's NHWC block float32 [h_b][w_b][C] at float offset prob_off[b] (as the network's rescale_output leaves it);
+ * unary_dev: image b's CLASS-major block float32 [C][H_b*W_b] at float offset unary_off[b] (what wsc_crf_v_inference takes).
+ * No clip: the mirror (misc.imutils.crf_inference) takes -log of the map as it is; probabilities must be > 0. */
+int wsc_seg_unary_nhwc(wsc_ctx *ctx, const float *prob_dev, int B, int C, const int64_t *prob_off_host /*[B]*/,
+                       const int32_t *src_hw_host /*[B][2]*/, const int32_t *out_hw_host /*[B][2]*/,
+                       const int64_t *unary_off_host /*[B]*/, float *unary_dev);
+
+/* The DeepGlobe branch's tail (model.py:695 + :699): cv2.resize of the CRF marginals to the ground truth's size, then arg-max over
+ * the classes (FIRST maximum, as np.argmax; NaN is out of contract).  q_dev: class-major [C][h_b*w_b] at float offset q_off[b]
+ * (wsc_crf_v_inference's q); label_dev int32, H_b*W_b per image at int32 offset label_off[b] (what wsc_label_confusion_nn
+ * takes).  The resized marginals are never written. */
+int wsc_seg_resize_argmax(wsc_ctx *ctx, const float *q_dev, int B, int C, const int64_t *q_off_host /*[B]*/,
+                          const int32_t *src_hw_host /*[B][2]*/, const int32_t *out_hw_host /*[B][2]*/,
+                          const int64_t *label_off_host /*[B]*/, int32_t *label_dev);
+
 /* ---- HistoSegNet post-processing (03c_hsn/utilities.py:231-397), device resident ---------- */
 
 /* HSN grad_cam after the einsum (utilities.py:262-277), for the NHWC maps of wsc_net_forward_gradcam(relu = 0):

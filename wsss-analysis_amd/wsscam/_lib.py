@@ -128,6 +128,8 @@ _SIGNATURES = {
     "wsc_dsrg_seed_grow": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
     "wsc_cue_maps": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "wsc_cue_seeds": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d, _vp, _vp]),
+    "wsc_seg_unary_nhwc": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "wsc_seg_resize_argmax": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "wsc_hsn_gradcam_post": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i]),
     "wsc_hsn_voc_background": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "wsc_hsn_class_mass": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -890,6 +892,28 @@ def cue_seeds(ctx, fg_dev, bg_dev, B, C, Cb, H, W, thresh, label_dev, area_dev=N
     (0 = none, k + 1 = localization channel k) and, with area_dev, int32 [B][L] mask areas."""
     check(ctx._lib.wsc_cue_seeds(ctx.h, _ptr(fg_dev), _ptr(bg_dev), int(B), int(C), int(Cb), int(H), int(W), float(thresh),
                                  int(bool(per_image_max)), float(bg_fraction), _ptr(label_dev), _ptr(area_dev)))
+
+
+def _seg_tables(src_sizes, out_sizes, src_off, dst_off):
+    B = len(src_sizes)
+    return (B, np.ascontiguousarray(src_off, dtype=np.int64), np.ascontiguousarray(src_sizes, dtype=np.int32).reshape(B, 2),
+            np.ascontiguousarray(out_sizes, dtype=np.int32).reshape(B, 2), np.ascontiguousarray(dst_off, dtype=np.int64))
+
+
+def seg_unary_nhwc(ctx, prob_dev, C, src_sizes, out_sizes, prob_off, unary_off, unary_dev):
+    """wsc_seg_unary_nhwc: packed NHWC softmax blocks [h_b][w_b][C] (float offsets prob_off) -> class-major unaries
+    -log(bilinear resize to out_sizes[b]), [C][H_b*W_b] at float offsets unary_off."""
+    B, so, sh, oh, do = _seg_tables(src_sizes, out_sizes, prob_off, unary_off)
+    check(ctx._lib.wsc_seg_unary_nhwc(ctx.h, _ptr(prob_dev), B, int(C), so.ctypes.data, sh.ctypes.data, oh.ctypes.data, do.ctypes.data,
+                                      _ptr(unary_dev)))
+
+
+def seg_resize_argmax(ctx, q_dev, C, src_sizes, out_sizes, q_off, label_off, label_dev):
+    """wsc_seg_resize_argmax: packed class-major marginals [C][h_b*w_b] (float offsets q_off) -> int32 labels, the first maximum
+    over the classes of the bilinear resize to out_sizes[b], H_b*W_b per image at int32 offsets label_off."""
+    B, so, sh, oh, do = _seg_tables(src_sizes, out_sizes, q_off, label_off)
+    check(ctx._lib.wsc_seg_resize_argmax(ctx.h, _ptr(q_dev), B, int(C), so.ctypes.data, sh.ctypes.data, oh.ctypes.data, do.ctypes.data,
+                                         _ptr(label_dev)))
 
 
 def ir_label_combine(ctx, fg_pred_dev, bg_pred_dev, keys, N, conf_dev):
