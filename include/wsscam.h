@@ -58,7 +58,10 @@ typedef enum wsc_arch {
     WSC_ARCH_M7_CAM = 2,       /* net/m7.py:41 + m7_cam.py:22-57 */
     WSC_ARCH_RESNET50_IRN = 3, /* net/resnet50_irn.py:8-132,210-232 (EdgeDisplacement) */
     WSC_ARCH_VGG16_IRN = 4,    /* net/vgg16_irn.py:8-212,301-321 (EdgeDisplacement, ds_fac = 0.25) */
-    WSC_ARCH_M7_IRN = 5        /* net/m7_irn.py:8-118,195-213 (EdgeDisplacement; edge map at 1/2 resolution) */
+    WSC_ARCH_M7_IRN = 5,       /* net/m7_irn.py:8-118,195-213 (EdgeDisplacement; edge map at 1/2 resolution) */
+    WSC_ARCH_DEEPLAB_LFOV = 6, /* 03a_sec-dsrg/SEC.py:117-128,150-218: DeepLab-VGG16, one fc6 / fc7 / fc8 branch at rate 12 */
+    WSC_ARCH_DEEPLAB_ASPP = 7  /* 03a_sec-dsrg/DSRG.py:169-186,203-295: the same trunk, branches _1 .. _4 at rates 6 / 12 / 18 / 24,
+                                  fc8 = their sum */
 } wsc_arch;
 
 /* arithmetic of the conv stack */
@@ -189,7 +192,8 @@ const char *wsc_profile_class_name(int cls);
  * (03b_irn/step/make_cam.py:96-100, 33).  Inference BatchNorm
  * (net/resnet50.py:11-14, eps from "<bn>.eps" if given else 1e-5) is folded
  * into per-channel scale/shift applied in the conv epilogue.
- * Missing keys -> WSC_ERR_MISSING_KEY, wrong shapes -> WSC_ERR_SHAPE. */
+ * Missing keys -> WSC_ERR_MISSING_KEY, wrong shapes -> WSC_ERR_SHAPE (the WSC_ARCH_DEEPLAB_* nets: WSC_ERR_SHAPE for both,
+ * see wsc_net_forward_seg). */
 int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n_weights,
                    int num_classes, int precision, wsc_net **out);
 void wsc_net_destroy(wsc_net *net);
@@ -273,6 +277,55 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
                     int Cout, int kh, int kw, int stride, int pad, const float *scale_host,
                     const float *shift_host, const float *residual_dev, int relu, int precision,
                     float *y_dev);
+/* The same with a dilation `dil` >= 1, one rate for both axes (tf.nn.atrous_conv2d's `rate`, DSRG.py:222,268): tap (r, s) of output
+ * pixel (ho, wo) reads input (ho * stride - pad + r * dil, wo * stride - pad + s * dil), a tap outside the image contributes
+ * zero; the output is (H + 2 pad - ((kh - 1) dil + 1)) / stride + 1 rows.  TF's padding="SAME" for a 3x3 kernel is pad = dil,
+ * stride = 1.  dil > 1 needs Cin in multiples of 64 (the generic form) and takes the kernel's per-tap gather, whatever the
+ * precision; dil = 1 IS wsc_conv2d_nchw (one implementation, identical bits). */
+int wsc_conv2d_nchw_dil(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int W, const float *w_host,
+                        int Cout, int kh, int kw, int stride, int pad, int dil, const float *scale_host,
+                        const float *shift_host, const float *residual_dev, int relu, int precision,
+                        float *y_dev);
+
+/* ---- SEC / DSRG segmentation network (03a_sec-dsrg) ----------------------- */
+
+/* The DeepLab-VGG16 forward pass of SEC / DSRG at drop_prob = 0 (every non-training phase; the losses, the optimiser and the
+ * training loop are out of scope).  A net created with WSC_ARCH_DEEPLAB_LFOV / _ASPP takes its weights under the reference's
+ * layer names (get_weights_and_bias, DSRG.py:379-425): `conv1_1` ... `conv5_3`, and `fc6`, `fc7`, `fc8` (LFOV) or `fc6_1` ...
+ * `fc8_4` (ASPP); each as `<layer>.w` in TensorFlow's HWIO order [kh][kw][Cin][Cout] and `<layer>.b` [Cout].  Channel widths
+ * are read from the tensors (multiples of 64; fc8 has num_classes outputs).  A missing or mis-shaped tensor is WSC_ERR_SHAPE
+ * and the error text names the layer.  Layers (build_block / build_fc): 3x3 conv + bias + ReLU with padding SAME, conv5_* at
+ * rate 2, fc6 at its branch's rate; 3x3 max pools with TF's SAME padding (pad_before = floor(pad_total / 2): 0 / 1 on an even
+ * size at stride 2; padding never wins the maximum) at stride 2 (pool1-3) and 1 (pool4, pool5); pool5a, a 3x3 stride-1 average
+ * over the in-image taps; dropout is the identity.
+ *
+ * wsc_net_seg_size_hw: the fc8 map size for an H x W input (41 x 41 at 321 x 321). */
+int wsc_net_seg_size_hw(const wsc_net *net, int H, int W, int *h_out, int *w_out);
+/* x_dev    float32 [B][H][W][3] NHWC, BGR minus mean: what the reference feeds net["input"] (model.py:337-340)
+ * prob_dev float32 [B][h][w][C] NHWC `fc8-softmax` (build_sp_softmax, DSRG.py:297-300 / SEC.py:246-249):
+ *          e = exp(x - max), p = e / sum(e) + min_prob, p /= sum(p) over the classes, in fp32 on the fp32 logits --
+ *          the layout wsc_dsrg_seed_grow and wsc_seg_unary_nhwc take
+ * fc8_dev  NULL, or float32 [B][h][w][C]: the logits (ASPP: fc8_1 + fc8_2 + fc8_3 + fc8_4 in that order, DSRG.py:181)
+ * Any H, W >= 1 (non-square and even sizes included).  The IEEE-half modes raise the range flag (WSC_ERR_RANGE at the next
+ * synchronising call) as for the other nets; the input itself counts.  Asynchronous on the ctx stream. */
+int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob,
+                        float *fc8_dev, float *prob_dev);
+/* TensorFlow 1.x tf.image.resize_bilinear(align_corners=False) -- the legacy sampler WITHOUT the half-pixel offset of
+ * wsc_bilinear_resize -- on NHWC float32: rescale_output (DSRG.py:450 / SEC.py pred), the CRF layer's zoomed image and map
+ * (DSRG.py:319-321) and the input resize of image_preprocess (model.py:335).  Per axis scale = in / out (float32),
+ * src = dst * scale, i0 = floor(src), i1 = min(i0 + 1, in - 1), t = src - i0; top = tl + (tr - tl) tx, bottom likewise,
+ * out = top + (bottom - top) ty.  src_dev [B][h][w][C] -> dst_dev [B][H][W][C]. */
+int wsc_resize_bilinear_tf(wsc_ctx *ctx, const float *src_dev, int B, int h, int w, int C, float *dst_dev, int H, int W);
+/* The two pieces of that network the per-layer tests drive on their own (float32 NHWC in and out; the values go through the
+ * activation planes of `precision` as they do inside the net):
+ * wsc_pool_same_nhwc: the 3x3 TF-SAME pool of build_block (DSRG.py:229-246): avg = 0 max at stride 1 / 2, avg = 1 the average
+ *   over the in-image taps at stride 1; y_dev [N][ceil(H / stride)][ceil(W / stride)][C], C a multiple of 8.
+ * wsc_fc8_softmax: fc8-softmax of the sum of n_in (1 .. 4) float32 [M][C] logit arrays (device pointers in a host array);
+ *   sum_dev NULL or [M][C] receives the summed logits. */
+int wsc_pool_same_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, int avg, int stride, int precision,
+                       float *y_dev);
+int wsc_fc8_softmax(wsc_ctx *ctx, const float *const *fc8_dev, int n_in, long long M, int C, float min_prob, float *sum_dev,
+                    float *prob_dev);
 
 /* ---- CAM tail ---------------------------------------------------------- */
 

@@ -358,6 +358,8 @@ struct ConvLaunch {
     float *y_f32;               // optional fp32 output [M][Cout]
     int N, H, W, Cin, Ho, Wo, Cout, CoutPad;
     int kh, kw, stride, pad;
+    int dil = 1;   // dilation, one rate for both axes: tap (r, s) of output pixel (ho, wo) reads input (ho * stride - pad + r * dil,
+                   // wo * stride - pad + s * dil); > 1 on generic layers only (conv_igemm_launch sends them to the per-tap gather)
     int relu;
     ConvForm form;
     wsc_precision prec;
@@ -403,6 +405,16 @@ int launch_gap_linear_sigmoid(wsc_ctx *ctx, Act feat, int B, int hw, int F, cons
 int launch_act_to_f32(wsc_ctx *ctx, Act x, size_t n, float *y);
 int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y);
 int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y);
+
+// ---- deeplab.hip: the kernels around the conv stack of the SEC / DSRG DeepLab nets -------------------------------------
+// TF `SAME` 3x3 pooling of one axis: out = ceil(in / stride), pad_before = max((out - 1) stride + 3 - in, 0) / 2
+void pool_same_dims(int in, int stride, int *out, int *pad_before);
+// 3x3 max (stride 1 / 2; padding is -inf) or average over the in-image taps (stride 1) on an NHWC activation, every plane
+int launch_pool_same(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int avg, int stride, Act y);
+// float32 [N][H][W][3] -> NHWC4 activation (raises the range flag where an IEEE-half plane saturates)
+int launch_nhwc3_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y);
+// prob[m][c] = fc8-softmax of (in[0] + ... + in[n_in - 1])[m][c]; fc8 (optional) receives the summed logits
+int launch_fc8_softmax(wsc_ctx *ctx, const float *const *in, int n_in, long long M, int C, float min_prob, float *fc8, float *prob);
 
 // ---- irn_kernels.hip ---------------------------------------------------------------------
 int launch_group_norm_stats(wsc_ctx *ctx, const float *x, int N, int H, int W, int C, int G, float eps, void *partial,

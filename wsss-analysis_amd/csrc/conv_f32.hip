@@ -9,7 +9,7 @@
 // at BN = 128), two LDS buffers, one barrier per K-step, one K-step ahead.  A K-step is 32 fp32 = one 128-byte LDS row per pixel /
 // output channel: the row size, 16-byte-slot XOR swizzle and staging ownership of conv_igemm.hip's tiles.
 //   generic layers (Cin % 32 == 0): a K-step = one tap of a 32-channel chunk, staged by global_load_lds_dwordx4 (swizzle on the
-//       source slot, padded taps from the zero page).
+//       source slot, padded taps from the zero page); the tap offset is scaled by the layer's dilation.
 //   small-Cin forms (NHWC4 input): a K-step = 8 pixels x 4 channels (two kernel rows of 4 pixels, or one of 8), global ->
 //       register -> LDS.
 // Fragments: the MFMA takes ONE fp32 per lane and operand (lane l: row l & 31, k = l >> 5).  A ds_read_b128 of slot 2 q + (l >> 5)
@@ -37,6 +37,7 @@ struct ConvF32Args {
     int Kw; // packed weight row length in elements
     int ntiles_n, nblocks;
     const float *zero; // >= 16 bytes of zeros in HBM: source of padded taps
+    int dil;           // tap (r, s) reads input (ho * stride - pad + r * dil, wo * stride - pad + s * dil); generic layers only
 };
 
 __device__ __forceinline__ int lds_off(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
@@ -141,10 +142,12 @@ __global__ __launch_bounds__(256, 2) void conv_f32_kernel(ConvF32Args p) {
         // the MFMAs start (conv_igemm.hip).
         int n_khi = 0, n_kwi = 0, n_cc = 0, n_kt = 0; // (tap, chunk) of the next K-step to issue: K order (chunk, kh, kw)
         auto issue = [&](int buf) __attribute__((always_inline)) {
-            const long long tap = ((long long)n_khi * p.W + n_kwi) * p.Cin + n_cc * 32;
+            // (a dilated tap outside the image contributes zero like any padded tap: the bounds test below is per tap)
+            const int dh = n_khi * p.dil, dw = n_kwi * p.dil;
+            const long long tap = ((long long)dh * p.W + dw) * p.Cin + n_cc * 32;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int hi = hb[i] + n_khi, wi = wb[i] + n_kwi;
+                const int hi = hb[i] + dh, wi = wb[i] + dw;
                 const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
                 const float *g = ok ? p.x + (aoff[i] + tap) : p.zero;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
@@ -359,6 +362,7 @@ int conv_f32_launch(wsc_ctx *ctx, const ConvLaunch &p) {
               "conv (fp32): the padded-stem form and the second input are half-mode paths");
     if (p.form == CONV_FORM_GENERIC) WSC_CHECK(p.Cin % 32 == 0, WSC_ERR_INVALID, "conv (fp32): Cin=%d not a multiple of 32", p.Cin);
     else WSC_CHECK(p.Cin == 4 && p.kw <= (p.form == CONV_FORM_SMALL2 ? 4 : 8), WSC_ERR_INVALID, "conv (fp32): small-Cin mode needs a 4-channel activation");
+    WSC_CHECK(p.dil >= 1 && (p.dil == 1 || p.form == CONV_FORM_GENERIC), WSC_ERR_INVALID, "conv (fp32): dilation %d needs a generic layer", p.dil);
     WSC_CHECK(p.CoutPad % 64 == 0 && p.Cout <= p.CoutPad, WSC_ERR_INVALID, "conv (fp32): CoutPad=%d not a multiple of 64", p.CoutPad);
     const int ldy = p.ldy > 0 ? p.ldy : p.Cout;
     WSC_CHECK((!p.y && !p.res) || (p.Cout % 8 == 0 && ldy % 4 == 0), WSC_ERR_INVALID,
@@ -372,7 +376,7 @@ int conv_f32_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     a.y = p.y.f32(); a.y_f32 = p.y_f32;
     a.H = p.H; a.W = p.W; a.Cin = p.Cin; a.Ho = p.Ho; a.Wo = p.Wo; a.Cout = p.Cout;
     a.ldy = ldy;
-    a.kh = p.kh; a.kw = p.kw; a.stride = p.stride; a.pad = p.pad; a.relu = p.relu;
+    a.kh = p.kh; a.kw = p.kw; a.stride = p.stride; a.pad = p.pad; a.relu = p.relu; a.dil = p.dil;
     const long long M = (long long)p.N * p.Ho * p.Wo;
     WSC_CHECK(M < (1ll << 31) - 256, WSC_ERR_INVALID, "conv (fp32): %lld output pixels", M);
     a.M = (int)M;

@@ -24,6 +24,8 @@
 // lane-linear, and padded taps read a zero page.  A 1 x 1 layer may take its last channels from a SECOND A source (a ResNet
 // stage's first block: conv3 and the projection shortcut as one GEMM).
 // Register staging (the small-Cin forms: first layers on an NHWC4 input): global -> register -> LDS.
+// Dilation (tf.nn.atrous_conv2d of the SEC / DSRG DeepLab nets, 03a_sec-dsrg/DSRG.py:222,268): the per-tap gather of the generic
+// (FAST == 0) LDS-DMA variants scales the tap offset by ConvKArgs::dil; every other path is launched with dil == 1.
 //
 // Precisions.  bf16 / f16: one plane.  bf16x3 (and the small-Cin layers of f16x3): a second plane holds the rounding
 // remainder and the K loop runs three segments x_hi*w_hi, x_lo*w_hi, x_hi*w_lo into the same accumulators, each staging its
@@ -59,7 +61,7 @@ struct ConvKArgs {
     unsigned div_howo_mul, div_howo_s1, div_howo_s2, div_wo_mul, div_wo_s1, div_wo_s2;
     // the K layout, ConvKLayout (common.h):
     int cchunks;     // channel chunks of one K-step's channels
-    int spare0;
+    int dil;         // dilation of the per-tap gather (FAST == 0 LDS-DMA variants; every other path is launched with dil == 1)
     int ksteps_base; // K-steps of one precision segment
     int nk;          // total K-steps
     int Kw;          // packed weight row length in elements
@@ -78,7 +80,7 @@ struct ConvKArgs {
     // LDS input window of a 3 x 3 / stride 1 / pad 1 layer (WPT > 0 variants): positions of the input raster [N][H][W]
     // starting at index (first output pixel of the block) - W - 1; win_npix = N H W (pieces outside the tensor load zeros)
     int win_npix;
-    // spare0-3: read by nobody.  They hold the places of four values that only the host used to carry here; taking them out
+    // spare1-3: read by nobody.  They hold the places of values that only the host used to carry here; taking them out
     // moves the other arguments, and the compiler then merges the kernels' scalar argument loads differently and allocates
     // other registers in 4 to 25 of the instantiations (seven layouts tried) -- the kernels are kept as they were instead.
     int spare2, spare3;
@@ -338,9 +340,14 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
         const bf16_t *n_src = p.x;
         long long n_tap = 0;
         int n_wk = 0;
+        // Dilation: tap (r, s) sits (r dil, s dil) pixels from tap (0, 0).  Only the generic variants carry it (the FAST, window,
+        // two-source and stem layers are launched with dil == 1: conv_igemm_launch); the bounds test of issue_a is per tap, so a
+        // dilated tap outside the image reads the zero page like a padded one.
+        // (the FAST variants keep the expressions they had, so that they stay the instructions they were)
         auto prep = [&]() {
             n_src = (SPLIT == 1 && n_seg == 1) ? p.x_lo : p.x;
-            n_tap = ((long long)n_khi * p.W + n_kwi) * p.ldx + n_cc * CK;
+            if constexpr (FAST == 0) n_tap = ((long long)(n_khi * p.dil) * p.W + n_kwi * p.dil) * p.ldx + n_cc * CK;
+            else n_tap = ((long long)n_khi * p.W + n_kwi) * p.ldx + n_cc * CK;
             if (SPLIT != 1 && p.x2 != nullptr && n_cc >= p.cc2) { // second source (1 x 1 layers only): its own chunk count
                 n_src = p.x2;
                 n_tap = (n_cc - p.cc2) * CK;
@@ -379,7 +386,7 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
             }
         };
         auto issue_a = [&](int i, int buf) {
-            const int hi = hb[i] + n_khi, wi = wb[i] + n_kwi;
+            const int hi = hb[i] + (FAST == 0 ? n_khi * p.dil : n_khi), wi = wb[i] + (FAST == 0 ? n_kwi * p.dil : n_kwi);
             const bool ok = PW || ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W);
             const bf16_t *g = ok ? n_src + (aoff[i] + n_tap) : p.zero;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
@@ -1073,6 +1080,15 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     a.HoWo = p.Ho * p.Wo;
     conv_fastdiv((unsigned)(a.HoWo > 0 ? a.HoWo : 1), &a.div_howo_mul, &a.div_howo_s1, &a.div_howo_s2);
     conv_fastdiv((unsigned)(p.Wo > 0 ? p.Wo : 1), &a.div_wo_mul, &a.div_wo_s1, &a.div_wo_s2);
+    // Dilation (one rate for both axes).  A 1 x 1 kernel has no off-centre tap: any rate is rate 1 there.  A dilated layer takes
+    // the per-tap gather of the generic variants and nothing else: every other path -- FAST, the LDS window, the second
+    // source, the stem and small-Cin forms -- has address arithmetic of adjacent taps (or is compiled without the rate) and
+    // requires dil == 1 below.
+    WSC_CHECK(p.dil >= 1, WSC_ERR_INVALID, "conv: dilation %d", p.dil);
+    const int dil = (p.kh == 1 && p.kw == 1) ? 1 : p.dil;
+    WSC_CHECK(dil == 1 || (p.form == CONV_FORM_GENERIC && !p.x2), WSC_ERR_INVALID,
+              "conv: dilation %d needs a generic layer (Cin %% 64 == 0) with one input", dil);
+    a.dil = dil;
     a.cchunks = k.cchunks; a.ksteps_base = k.ksteps_base;
     a.Kbase = k.Kbase; a.Kw = k.Kw; a.nk = k.nk;
     a.lo_delta = single_staged ? (long long)(a.x_lo - a.x) : 0;
@@ -1096,7 +1112,7 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     // tiles, no post-ReLU affine.  p.generic (wsc_conv2d_nchw's WSC_CONV_GENERIC flag) keeps the generic variants: a test
     // holds the two to the same bits.
     int fast = 0;
-    if (!p.generic && fmt && (split == 0 || single_staged) && p.y && p.y_f32 == nullptr &&
+    if (!p.generic && dil == 1 && fmt && (split == 0 || single_staged) && p.y && p.y_f32 == nullptr &&
         p.Cout == p.CoutPad && (long long)a.M * a.ldy < (1ll << 31)) {
         fast = 1;
         if (dma && p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1) fast = 3;
@@ -1154,7 +1170,7 @@ int conv_igemm_launch(wsc_ctx *ctx, const ConvLaunch &p) {
     // two blocks per CU): ResNet50 @321 layer2 / layer3 conv2 (41 x 41: 213, 21 x 21: 173 positions) and, since the raster is
     // unpadded, layer1 conv2 (81 x 81: 293).
     int wpt = 0;
-    if (single_staged && fast == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && !p.x2 &&
+    if (single_staged && fast == 1 && dil == 1 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == 1 && !p.x2 &&
         p.Ho == p.H && p.Wo == p.W && ctx->opt[WSC_OPT_CONV_WINDOW] != 0) {
         // positions of a block's window: its 128 output pixels' raster span, one row + one pixel before and after, and the
         // zero row at the window's last position

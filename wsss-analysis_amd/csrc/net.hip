@@ -8,6 +8,8 @@
 //                  (conv(bias) -> ReLU -> BatchNorm(eps=1e-3)); vgg16_cam.py:24-50
 //   m7_cam       : net/m7.py:41 cfg; m7_cam.py:22-47 (Grad-CAM weights as the 1x1 head)
 //   construction/load: 03b_irn/step/make_cam.py:96-100
+//   deeplab_lfov / deeplab_aspp : the DeepLab-VGG16 of 03a_sec-dsrg, SEC.py:117-128 / DSRG.py:169-186 (build_block, build_fc):
+//                  forward pass at drop_prob = 0, weights under the reference's layer names in TF's HWIO order
 #include "common.h"
 
 #include <algorithm>
@@ -33,6 +35,7 @@ struct ConvW {
     void *w = nullptr; // packed weights: 16-bit, fp32 in WSC_PREC_F32 (make_conv)
     float *s1 = nullptr, *b1 = nullptr, *s2 = nullptr, *b2 = nullptr;
     int Cin = 0, Cout = 0, CoutPad = 0, kh = 1, kw = 1, stride = 1, pad = 0, relu = 0;
+    int dil = 1; // dilation (tf.nn.atrous_conv2d's rate); make_conv leaves 1, the DeepLab builder sets it
     ConvForm form = CONV_FORM_GENERIC;
 };
 
@@ -49,7 +52,11 @@ struct IrnCat {
     int channels, stage, stride;
 };
 
-enum OpType { OP_CONV = 0, OP_POOL = 1, OP_GATHER = 2 };
+enum OpType { OP_CONV = 0, OP_POOL = 1, OP_GATHER = 2, OP_POOL_SAME = 3 /* TF SAME 3x3: ps = stride, pp = 1 for the average */ };
+// one fc6 (3x3 atrous) -> fc7 (1x1) -> fc8 (1x1, no ReLU, fp32 logits) branch of the DeepLab head
+struct SegBranch {
+    ConvW fc6, fc7, fc8;
+};
 struct Op {
     int type;
     int conv;         // index into convs (OP_CONV)
@@ -79,6 +86,7 @@ struct wsc_net {
     std::vector<IrnCat> cats;    // concat buffers; cats[0] feeds the final edge conv, cats.back() the final dp conv
     ConvW edge6, dp7b;           // final edge conv (bias) / final displacement conv
     float mean_shift[2] = {0.f, 0.f};
+    std::vector<SegBranch> seg;  // WSC_ARCH_DEEPLAB_*: one branch (LFOV, SEC) or four (ASPP, DSRG); fc8 = their sum
     std::vector<void *> allocs;
 };
 
@@ -226,7 +234,7 @@ ConvLaunch conv_launch(const ConvW &c, wsc_precision prec) {
     ConvLaunch L = {};
     L.w = c.w; L.s1 = c.s1; L.b1 = c.b1; L.s2 = c.s2; L.b2 = c.b2;
     L.Cin = c.Cin; L.Cout = c.Cout; L.CoutPad = c.CoutPad;
-    L.kh = c.kh; L.kw = c.kw; L.stride = c.stride; L.pad = c.pad; L.relu = c.relu;
+    L.kh = c.kh; L.kw = c.kw; L.stride = c.stride; L.pad = c.pad; L.relu = c.relu; L.dil = c.dil;
     L.form = c.form; L.prec = prec;
     return L;
 }
@@ -625,6 +633,78 @@ int build_m7_irn(wsc_net *net, const Dict &d) {
     return build_irn_heads(net, d, specs, cats, "fc_edge4", 96, "fc_dp5.3");
 }
 
+// ---- DeepLab-VGG16 of 03a_sec-dsrg (SEC.py:117-128,150-218 / DSRG.py:169-186,203-295) ----------------------------------
+// `<layer>.w` is TensorFlow's HWIO [kh][kw][Cin][Cout], `<layer>.b` [Cout].  A missing or mis-shaped tensor is WSC_ERR_SHAPE
+// with the layer's name.  Every layer is conv + bias + ReLU except fc8; dropout is the identity (drop_prob = 0).
+int deeplab_conv(wsc_net *net, const Dict &d, const std::string &layer, int k, int in_ch, int want_cout, int dil, int relu,
+                 ConvForm form, ConvW *out) {
+    auto wi = d.find(layer + ".w"), bi = d.find(layer + ".b");
+    WSC_CHECK(wi != d.end() && wi->second.data != nullptr && bi != d.end() && bi->second.data != nullptr, WSC_ERR_SHAPE,
+              "layer '%s': '%s.w' / '%s.b' missing", layer.c_str(), layer.c_str(), layer.c_str());
+    const HostTensor &w = wi->second, &b = bi->second;
+    WSC_CHECK(w.ndim == 4 && w.shape[0] == k && w.shape[1] == k && w.shape[2] == in_ch && w.shape[3] >= 1, WSC_ERR_SHAPE,
+              "layer '%s': '.w' must be HWIO [%d][%d][%d][Cout], got ndim %d [%lld][%lld][%lld][%lld]", layer.c_str(), k, k, in_ch, w.ndim,
+              (long long)w.shape[0], (long long)w.shape[1], (long long)w.shape[2], (long long)w.shape[3]);
+    const int Cout = (int)w.shape[3];
+    WSC_CHECK(want_cout > 0 ? Cout == want_cout : Cout % 64 == 0, WSC_ERR_SHAPE,
+              "layer '%s': %d output channels (%s)", layer.c_str(), Cout, want_cout > 0 ? "the class count is expected" : "a multiple of 64 is needed");
+    WSC_CHECK(b.numel() == Cout, WSC_ERR_SHAPE, "layer '%s': '.b' has %lld entries for %d output channels", layer.c_str(),
+              (long long)b.numel(), Cout);
+    std::vector<float> oihw((size_t)Cout * in_ch * k * k);
+    for (int r = 0; r < k; ++r)
+        for (int q = 0; q < k; ++q)
+            for (int ci = 0; ci < in_ch; ++ci)
+                for (int co = 0; co < Cout; ++co)
+                    oihw[(((size_t)co * in_ch + ci) * k + r) * k + q] = w.data[(((size_t)r * k + q) * in_ch + ci) * Cout + co];
+    HostTensor t;
+    t.data = oihw.data(); t.ndim = 4; t.shape[0] = Cout; t.shape[1] = in_ch; t.shape[2] = k; t.shape[3] = k;
+    std::vector<float> one(Cout, 1.f), bias(b.data, b.data + Cout);
+    // TF SAME for an odd kernel at stride 1: pad = dil (k - 1) / 2 on every side
+    WSC_TRY(make_conv(net, &t, 1, dil * (k - 1) / 2, relu, form, one, bias, nullptr, nullptr, out));
+    out->dil = dil;
+    return WSC_OK;
+}
+
+int build_deeplab(wsc_net *net, const Dict &d, bool aspp) {
+    // {layer, dilation}; "" = a pool: 2 / 1 = max at that stride, 0 = the 3x3 average pool5a
+    struct Item { const char *name; int v; };
+    const Item trunk[] = {{"conv1_1", 1}, {"conv1_2", 1}, {"", 2}, {"conv2_1", 1}, {"conv2_2", 1}, {"", 2},
+                          {"conv3_1", 1}, {"conv3_2", 1}, {"conv3_3", 1}, {"", 2}, {"conv4_1", 1}, {"conv4_2", 1}, {"conv4_3", 1}, {"", 1},
+                          {"conv5_1", 2}, {"conv5_2", 2}, {"conv5_3", 2}, {"", 1}, {"", 0}};
+    int cur = 0, in_ch = 3;
+    bool first = true;
+    for (const Item &it : trunk) {
+        if (it.name[0] == 0) {
+            Op op;
+            op.type = OP_POOL_SAME; op.conv = -1; op.in = cur; op.out = (cur + 1) & 1; op.res = -1;
+            op.pk = 3; op.ps = it.v == 0 ? 1 : it.v; op.pp = it.v == 0 ? 1 : 0;
+            net->ops.push_back(op);
+            cur = op.out;
+            continue;
+        }
+        ConvW c;
+        WSC_TRY(deeplab_conv(net, d, it.name, 3, in_ch, 0, it.v, 1, first ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, &c));
+        const int out = first ? 0 : ((cur + 1) & 1);
+        WSC_TRY(add_conv_op(net, c, first ? -1 : cur, out, -1));
+        cur = out;
+        in_ch = c.Cout;
+        first = false;
+    }
+    net->final_buf = cur;
+    net->F = in_ch;
+    const int rates_aspp[4] = {6, 12, 18, 24};
+    const int nb = aspp ? 4 : 1;
+    for (int k = 0; k < nb; ++k) {
+        const std::string sfx = aspp ? "_" + std::to_string(k + 1) : "";
+        SegBranch br;
+        WSC_TRY(deeplab_conv(net, d, "fc6" + sfx, 3, in_ch, 0, aspp ? rates_aspp[k] : 12, 1, CONV_FORM_GENERIC, &br.fc6));
+        WSC_TRY(deeplab_conv(net, d, "fc7" + sfx, 1, br.fc6.Cout, 0, 1, 1, CONV_FORM_GENERIC, &br.fc7));
+        WSC_TRY(deeplab_conv(net, d, "fc8" + sfx, 1, br.fc7.Cout, net->C, 1, 0, CONV_FORM_GENERIC, &br.fc8));
+        net->seg.push_back(br);
+    }
+    return WSC_OK;
+}
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct OpDims {
@@ -650,8 +730,8 @@ int plan_dims(const wsc_net *net, int N, int SH, int SW, Plan *pl) {
         d.H = op.in < 0 ? SH : bh[op.in]; d.W = op.in < 0 ? SW : bw[op.in]; d.C = op.in < 0 ? 4 : bc[op.in];
         if (op.type == OP_CONV) {
             const ConvW &c = net->convs[op.conv];
-            d.Ho = (d.H + 2 * c.pad - c.kh) / c.stride + 1;
-            d.Wo = (d.W + 2 * c.pad - c.kw) / c.stride + 1;
+            d.Ho = (d.H + 2 * c.pad - ((c.kh - 1) * c.dil + 1)) / c.stride + 1;
+            d.Wo = (d.W + 2 * c.pad - ((c.kw - 1) * c.dil + 1)) / c.stride + 1;
             d.Co = op.pitch ? op.pitch : c.Cout;
             if (op.in2 >= 0) {
                 d.H2 = bh[op.in2]; d.W2 = bw[op.in2]; d.C2 = bc[op.in2];
@@ -665,6 +745,11 @@ int plan_dims(const wsc_net *net, int N, int SH, int SW, Plan *pl) {
             d.Co = op.pitch;
             WSC_CHECK(d.Ho == bh[op.out] && d.Wo == bw[op.out] && bc[op.out] == op.pitch && op.coff + d.C <= op.pitch, WSC_ERR_INVALID,
                       "internal: gather into a %d x %d x %d tensor does not fit", bh[op.out], bw[op.out], bc[op.out]);
+        } else if (op.type == OP_POOL_SAME) {
+            int pad_before;
+            pool_same_dims(d.H, op.ps, &d.Ho, &pad_before);
+            pool_same_dims(d.W, op.ps, &d.Wo, &pad_before);
+            d.Co = d.C;
         } else {
             d.Ho = (d.H + 2 * op.pp - op.pk) / op.ps + 1;
             d.Wo = (d.W + 2 * op.pp - op.pk) / op.ps + 1;
@@ -691,7 +776,8 @@ size_t taps_bytes(const wsc_net *net, const Plan &pl, int N) {
 // `taps` the stage outputs x1..x5 (net->taps) are copied to the start of that region, in stage order, and *extra is what
 // follows them -- the rotating activation buffers are overwritten as the stack proceeds.
 int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, size_t extra_bytes, Act *feat, int *hf, int *wf,
-                 void **extra, std::vector<Act> *taps = nullptr, int SW = 0) {
+                 void **extra, std::vector<Act> *taps = nullptr, int SW = 0, bool nhwc_in = false) {
+    // (nhwc_in: x_dev is [N][S][SW][3] instead of [N][3][S][SW] -- the DeepLab nets take TensorFlow's layout)
     if (SW <= 0) SW = S; // S x SW input (SW given for the non-square, native-size path)
     Plan pl;
     WSC_TRY(plan_dims(net, N, S, SW, &pl));
@@ -726,7 +812,10 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
         for (int op : net->taps) taps->push_back(act_carve(p, pl.out_elems(N, op), net->prec));
     *extra = (void *)p;
 
-    if (in_pad > 0) WSC_TRY(launch_nchw_to_nhwc4_pad(ctx, x_dev, N, S, SW, in_h, in_w, in_pad, xin));
+    if (nhwc_in) {
+        WSC_CHECK(in_pad == 0, WSC_ERR_INVALID, "internal: an NHWC input has no padded-stem form");
+        WSC_TRY(launch_nhwc3_to_nhwc4(ctx, x_dev, N, S, SW, xin));
+    } else if (in_pad > 0) WSC_TRY(launch_nchw_to_nhwc4_pad(ctx, x_dev, N, S, SW, in_h, in_w, in_pad, xin));
     else WSC_TRY(launch_nchw_to_nhwc4(ctx, x_dev, N, S, SW, xin));
     for (size_t i = 0; i < net->ops.size(); ++i) {
         const Op &op = net->ops[i];
@@ -753,6 +842,8 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             WSC_TRY(conv_igemm_launch(ctx, L));
         } else if (op.type == OP_GATHER) {
             WSC_TRY(launch_gather_strided(ctx, src, N, d.H, d.W, d.C, op.ps, d.Ho, d.Wo, buf[op.out].at(op.coff), op.pitch));
+        } else if (op.type == OP_POOL_SAME) {
+            WSC_TRY(launch_pool_same(ctx, src, N, d.H, d.W, d.C, op.pp, op.ps, buf[op.out]));
         } else {
             WSC_TRY(launch_maxpool(ctx, src, N, d.H, d.W, d.C, op.pk, op.ps, op.pp, d.Ho, d.Wo, buf[op.out]));
         }
@@ -808,6 +899,8 @@ int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n
     case WSC_ARCH_RESNET50_IRN: st = build_resnet50_irn(net, d); break;
     case WSC_ARCH_VGG16_IRN: st = build_vgg16_irn(net, d); break;
     case WSC_ARCH_M7_IRN: st = build_m7_irn(net, d); break;
+    case WSC_ARCH_DEEPLAB_LFOV: st = build_deeplab(net, d, false); break;
+    case WSC_ARCH_DEEPLAB_ASPP: st = build_deeplab(net, d, true); break;
     default:
         wsc_set_error("unknown arch %d", arch);
         st = WSC_ERR_INVALID;
@@ -873,6 +966,7 @@ int wsc_net_forward_cam_hw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev,
                            float *score_dev) {
     WSC_CHECK(ctx && net && x_dev && cam_dev, WSC_ERR_INVALID, "wsc_net_forward_cam: null argument");
     WSC_CHECK(B > 0 && S > 0 && SW > 0, WSC_ERR_INVALID, "wsc_net_forward_cam: B=%d input %d x %d", B, S, SW);
+    WSC_CHECK(net->head.w != nullptr, WSC_ERR_INVALID, "wsc_net_forward_cam: the network has no CAM head (a segmentation net: wsc_net_forward_seg)");
     WSC_CHECK(score_dev == nullptr || net->cls_w != nullptr, WSC_ERR_INVALID,
               "this architecture has no classifier branch (score_dev must be NULL)");
     WSC_HIP(hipSetDevice(ctx->device));
@@ -901,6 +995,7 @@ int wsc_net_forward_gradcam(wsc_ctx *ctx, const wsc_net *net, const float *x_dev
                             float *cams_dev, float *score_dev) {
     WSC_CHECK(ctx && net && x_dev && cams_dev, WSC_ERR_INVALID, "wsc_net_forward_gradcam: null argument");
     WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_forward_gradcam: N=%d S=%d", N, S);
+    WSC_CHECK(net->head.w != nullptr, WSC_ERR_INVALID, "wsc_net_forward_gradcam: the network has no CAM head (a segmentation net: wsc_net_forward_seg)");
     WSC_CHECK(score_dev == nullptr || net->cls_w != nullptr, WSC_ERR_INVALID,
               "this architecture has no classifier branch (score_dev must be NULL)");
     WSC_HIP(hipSetDevice(ctx->device));
@@ -923,6 +1018,7 @@ int wsc_net_forward_gradcam(wsc_ctx *ctx, const wsc_net *net, const float *x_dev
 int wsc_net_forward_features(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, float *feat_dev) {
     WSC_CHECK(ctx && net && x_dev && feat_dev, WSC_ERR_INVALID, "wsc_net_forward_features: null argument");
     WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_forward_features: N=%d S=%d", N, S);
+    WSC_CHECK(net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_features: a segmentation net takes an NHWC input (wsc_net_forward_seg)");
     WSC_HIP(hipSetDevice(ctx->device));
     Act feat;
     int hf, wf;
@@ -1021,12 +1117,77 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
     return WSC_OK;
 }
 
+// The DeepLab forward pass of SEC / DSRG (create_network up to "fc8-softmax", SEC.py:117-128,246-249 / DSRG.py:169-186,297-300)
+int wsc_net_seg_size_hw(const wsc_net *net, int H, int W, int *h_out, int *w_out) {
+    WSC_CHECK(net && h_out && w_out, WSC_ERR_INVALID, "wsc_net_seg_size_hw: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_seg_size_hw: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_CHECK(H >= 1 && W >= 1, WSC_ERR_INVALID, "wsc_net_seg_size_hw: input %d x %d", H, W);
+    Plan pl;
+    WSC_TRY(plan_dims(net, 1, H, W, &pl));
+    *h_out = pl.hf;
+    *w_out = pl.wf;
+    return WSC_OK;
+}
+
+int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *fc8_dev,
+                        float *prob_dev) {
+    WSC_CHECK(ctx && net && x_dev && prob_dev, WSC_ERR_INVALID, "wsc_net_forward_seg: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg: B=%d input %d x %d min_prob=%g", B, H, W,
+              (double)min_prob);
+    WSC_HIP(hipSetDevice(ctx->device));
+    Plan pl;
+    WSC_TRY(plan_dims(net, B, H, W, &pl));
+    const size_t M = (size_t)B * pl.hf * pl.wf;
+    // behind the trunk's buffers: fc6's and fc7's outputs (one pair, the branches run one after the other), then every
+    // branch's fp32 logits -- kept at fp32 and summed by the softmax kernel in the reference's order fc8_1 + fc8_2 + fc8_3 + fc8_4
+    size_t e6 = 0, e7 = 0;
+    for (const SegBranch &br : net->seg) {
+        e6 = std::max(e6, M * br.fc6.Cout);
+        e7 = std::max(e7, M * br.fc7.Cout);
+    }
+    const size_t logit_bytes = align_up(M * net->C * sizeof(float), 256);
+    const size_t extra_bytes = act_bytes(e6, net->prec) + act_bytes(e7, net->prec) + net->seg.size() * logit_bytes;
+    Act feat;
+    int hf, wf;
+    void *extra;
+    WSC_TRY(run_backbone(ctx, net, x_dev, B, H, extra_bytes, &feat, &hf, &wf, &extra, nullptr, W, true));
+    char *p = (char *)extra;
+    const Act a6 = act_carve(p, e6, net->prec), a7 = act_carve(p, e7, net->prec);
+    const float *logits[4] = {nullptr, nullptr, nullptr, nullptr};
+    WSC_CHECK(net->seg.size() <= 4, WSC_ERR_INVALID, "internal: %d head branches", (int)net->seg.size());
+    for (size_t k = 0; k < net->seg.size(); ++k) {
+        const SegBranch &br = net->seg[k];
+        float *out = (float *)(p + k * logit_bytes);
+        logits[k] = out;
+        auto run = [&](const ConvW &c, Act x, Act y, float *y_f32) -> int {
+            ConvLaunch L = conv_launch(c, net->prec);
+            L.x = x; L.y = y; L.y_f32 = y_f32;
+            L.N = B; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf; // (SAME at stride 1: pad = dil (k - 1) / 2)
+            return conv_igemm_launch(ctx, L);
+        };
+        WSC_TRY(run(br.fc6, feat, a6, nullptr));
+        WSC_TRY(run(br.fc7, a6, a7, nullptr));
+        WSC_TRY(run(br.fc8, a7, Act(), out));
+    }
+    return launch_fc8_softmax(ctx, logits, (int)net->seg.size(), (long long)M, net->C, min_prob, fc8_dev, prob_dev);
+}
+
 // One convolution layer through the production kernel, NCHW fp32 in / out (layout changes and
 // weight packing included): y = [relu]( conv(x, w) * scale + shift [+ residual] ).
 int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int W, const float *w_host, int Cout,
                     int kh, int kw, int stride, int pad, const float *scale_host, const float *shift_host,
                     const float *residual_dev, int relu, int precision, float *y_dev) {
+    return wsc_conv2d_nchw_dil(ctx, x_dev, N, Cin, H, W, w_host, Cout, kh, kw, stride, pad, 1, scale_host, shift_host, residual_dev, relu,
+                               precision, y_dev);
+}
+
+int wsc_conv2d_nchw_dil(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int W, const float *w_host, int Cout, int kh, int kw,
+                        int stride, int pad, int dil, const float *scale_host, const float *shift_host, const float *residual_dev,
+                        int relu, int precision, float *y_dev) {
     WSC_CHECK(ctx && x_dev && w_host && y_dev, WSC_ERR_INVALID, "wsc_conv2d_nchw: null argument");
+    WSC_CHECK(dil >= 1 && (dil == 1 || (Cin > 4 && stride >= 1)), WSC_ERR_INVALID,
+              "wsc_conv2d_nchw: dilation %d (>= 1; > 1 on the generic form only, Cin a multiple of 64)", dil);
     WSC_CHECK(Cout % 8 == 0, WSC_ERR_INVALID, "wsc_conv2d_nchw: Cout=%d must be a multiple of 8", Cout);
     WSC_HIP(hipSetDevice(ctx->device));
     wsc_net tmp;
@@ -1050,7 +1211,13 @@ int wsc_conv2d_nchw(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H, int
         for (void *p : tmp.allocs) (void)hipFree(p);
     };
     if (st != WSC_OK) { cleanup(); return st; }
-    const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
+    c.dil = dil;
+    const int Ho = (H + 2 * pad - ((kh - 1) * dil + 1)) / stride + 1, Wo = (W + 2 * pad - ((kw - 1) * dil + 1)) / stride + 1;
+    if (Ho < 1 || Wo < 1) {
+        cleanup();
+        wsc_set_error("wsc_conv2d_nchw: a %d x %d input is too small for this kernel, padding and dilation", H, W);
+        return WSC_ERR_INVALID;
+    }
     int in_h = H, in_w = W;
     if (form == CONV_FORM_STEM_ROWS) conv_stem_rows_input_dims(Ho, Wo, stride, kh, &in_h, &in_w);
     const size_t in_e = (size_t)N * in_h * in_w * c.Cin, out_e = (size_t)N * Ho * Wo * Cout;

@@ -31,6 +31,8 @@ ARCH_M7_CAM = 2
 ARCH_RESNET50_IRN = 3
 ARCH_VGG16_IRN = 4
 ARCH_M7_IRN = 5
+ARCH_DEEPLAB_LFOV = 6  # SEC: DeepLab-VGG16, one fc6 / fc7 / fc8 branch at rate 12
+ARCH_DEEPLAB_ASPP = 7  # DSRG: branches _1 .. _4 at rates 6 / 12 / 18 / 24, fc8 = their sum
 
 PREC_BF16 = 0
 PREC_BF16X3 = 1
@@ -111,6 +113,12 @@ _SIGNATURES = {
     "wsc_rw_propagate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "wsc_rw_propagate_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "wsc_conv2d_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "wsc_conv2d_nchw_dil": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "wsc_net_seg_size_hw": (_i, [_vp, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "wsc_net_forward_seg": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "wsc_resize_bilinear_tf": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i]),
+    "wsc_pool_same_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_fc8_softmax": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _f, _vp, _vp]),
     "wsc_cam_postprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wsc_cam_eval_confusion": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp]),
     "wsc_unary_from_maps": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
@@ -544,6 +552,19 @@ class Net:
         check(self.ctx._lib.wsc_net_forward_edge(run.h, self.h, _ptr(x_dev), B, S, feat_h, feat_w,
                                                  _ptr(edge_dev), _ptr(dp_dev)))
 
+    def seg_size_hw(self, H, W):
+        """The fc8 map size of an ARCH_DEEPLAB_* net for an H x W input (41 x 41 at 321 x 321)."""
+        h, w = _i(), _i()
+        check(self.ctx._lib.wsc_net_seg_size_hw(self.h, int(H), int(W), ctypes.byref(h), ctypes.byref(w)))
+        return h.value, w.value
+
+    def forward_seg(self, x_dev, B, H, W, prob_dev, fc8_dev=None, min_prob=1e-4, ctx=None):
+        """SEC / DSRG forward pass (wsc_net_forward_seg): x_dev float32 [B][H][W][3] NHWC (BGR minus mean) ->
+        prob_dev float32 [B][h][w][C] fc8-softmax, fc8_dev (optional) the logits in the same layout."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_forward_seg(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(min_prob), _ptr(fc8_dev),
+                                                _ptr(prob_dev)))
+
 
 def cam_postprocess(ctx, cam_dev, B, C, h, w, sizes, keys_per_image, strided_dev=None, highres_dev=None):
     """Batched make_cam tail.  sizes: [(H0, W0)], keys_per_image: list of int sequences.
@@ -583,19 +604,60 @@ def cam_postprocess(ctx, cam_dev, B, C, h, w, sizes, keys_per_image, strided_dev
 
 
 def conv2d_nchw(ctx, x_dev, N, Cin, H, W, w, stride, pad, scale=None, shift=None, residual_dev=None, relu=False,
-                precision=PREC_BF16, y_dev=None):
-    """One conv layer through the production kernel (test/diagnostic entry)."""
+                precision=PREC_BF16, y_dev=None, dil=1):
+    """One conv layer through the production kernel (test/diagnostic entry).  dil: the dilation (wsc_conv2d_nchw_dil; 1 through
+    that entry is wsc_conv2d_nchw itself)."""
     w = np.ascontiguousarray(w, dtype=np.float32)
     Cout, _, kh, kw = w.shape
-    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    dil = int(dil)
+    Ho, Wo = (H + 2 * pad - ((kh - 1) * dil + 1)) // stride + 1, (W + 2 * pad - ((kw - 1) * dil + 1)) // stride + 1
     if y_dev is None:
         y_dev = ctx.alloc(N * Cout * Ho * Wo * 4)
     sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
     sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float32)
-    check(ctx._lib.wsc_conv2d_nchw(ctx.h, _ptr(x_dev), N, Cin, H, W, w.ctypes.data, Cout, kh, kw, stride, pad,
-                                   None if sc is None else sc.ctypes.data, None if sh is None else sh.ctypes.data,
-                                   _ptr(residual_dev), int(relu), precision, _ptr(y_dev)))
+    if dil == 1:
+        check(ctx._lib.wsc_conv2d_nchw(ctx.h, _ptr(x_dev), N, Cin, H, W, w.ctypes.data, Cout, kh, kw, stride, pad,
+                                       None if sc is None else sc.ctypes.data, None if sh is None else sh.ctypes.data,
+                                       _ptr(residual_dev), int(relu), precision, _ptr(y_dev)))
+    else:
+        conv2d_nchw_dil(ctx, x_dev, N, Cin, H, W, w, stride, pad, dil, sc, sh, residual_dev, relu, precision, y_dev)
     return y_dev, (N, Cout, Ho, Wo)
+
+
+def conv2d_nchw_dil(ctx, x_dev, N, Cin, H, W, w, stride, pad, dil, scale, shift, residual_dev, relu, precision, y_dev):
+    """wsc_conv2d_nchw_dil as it is (conv2d_nchw(dil=) routes here for dil > 1; a test calls it with dil = 1)."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    Cout, _, kh, kw = w.shape
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+    sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float32)
+    check(ctx._lib.wsc_conv2d_nchw_dil(ctx.h, _ptr(x_dev), N, Cin, H, W, w.ctypes.data, Cout, kh, kw, stride, pad, int(dil),
+                                       None if sc is None else sc.ctypes.data, None if sh is None else sh.ctypes.data,
+                                       _ptr(residual_dev), int(relu), precision, _ptr(y_dev)))
+
+
+def resize_bilinear_tf(ctx, src_dev, B, h, w, C, H, W, dst_dev=None):
+    """TensorFlow 1.x tf.image.resize_bilinear(align_corners=False) on NHWC float32 (wsc_resize_bilinear_tf):
+    src_dev [B][h][w][C] -> dst_dev [B][H][W][C] (allocated when not given)."""
+    if dst_dev is None:
+        dst_dev = ctx.alloc(B * H * W * C * 4)
+    check(ctx._lib.wsc_resize_bilinear_tf(ctx.h, _ptr(src_dev), int(B), int(h), int(w), int(C), _ptr(dst_dev), int(H), int(W)))
+    return dst_dev
+
+
+def pool_same_nhwc(ctx, x_dev, N, H, W, C, avg, stride, precision, y_dev=None):
+    """One TF-SAME 3x3 pool of the SEC / DSRG nets on float32 NHWC (wsc_pool_same_nhwc) -> (y_dev, (N, Ho, Wo, C))."""
+    Ho, Wo = -(-H // stride), -(-W // stride)
+    if y_dev is None:
+        y_dev = ctx.alloc(N * Ho * Wo * C * 4)
+    check(ctx._lib.wsc_pool_same_nhwc(ctx.h, _ptr(x_dev), int(N), int(H), int(W), int(C), int(bool(avg)), int(stride), int(precision),
+                                      _ptr(y_dev)))
+    return y_dev, (N, Ho, Wo, C)
+
+
+def fc8_softmax(ctx, fc8_devs, M, C, prob_dev, min_prob=1e-4, sum_dev=None):
+    """fc8-softmax of the sum of 1 .. 4 float32 [M][C] logit arrays on the device (wsc_fc8_softmax)."""
+    ptrs = (_vp * len(fc8_devs))(*[_ptr(d) for d in fc8_devs])
+    check(ctx._lib.wsc_fc8_softmax(ctx.h, ptrs, len(fc8_devs), int(M), int(C), float(min_prob), _ptr(sum_dev), _ptr(prob_dev)))
 
 
 def cam_eval_confusion(ctx, highres_dev, sizes, keys_per_image, highres_off, bg_thres, gt_dev, n_class, confusion_dev,

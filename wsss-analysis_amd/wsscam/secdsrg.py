@@ -1,10 +1,13 @@
-"""03a_sec-dsrg mirror: the two host `py_func`s its training graph calls on every step, on libwsscam.
+"""03a_sec-dsrg mirror on libwsscam: the network's forward pass, the two host `py_func`s of its graph, the prediction tail.
 
+    SegNet               the DeepLab-VGG16 forward pass of SEC.py:117-128 / DSRG.py:169-186 at drop_prob = 0: fc8-softmax,
+                         create_network's output (the CRF layer) and pred()'s rescale_output; image_preprocess (model.py:335-340)
     generate_seed_step   DSRG.py:356-369 (and single_generate_seed_step :7-62 behind its process pool)
     crf_layer            the `crf` closure of DSRG.py:323-332 / SEC.py:270-280
+    SegEvaluator         eval_miou (model.py:665-719)
 
-The TF graph and the training of SEC / DSRG are out of scope; a DSRG model binds these two in place of the
-closures it hands to tf.py_func and needs neither the process pool nor pydensecrf."""
+The losses, the optimiser and the training loop of SEC / DSRG are out of scope.  Nothing here imports
+TensorFlow: Model.predict runs on this module alone."""
 import numpy as np
 
 from . import _lib
@@ -238,3 +241,151 @@ class SegEvaluator:
     def metrics(self):
         conf = self.ctx.to_host(self.conf_dev, (self.C + 1, self.C + 1), np.int64)
         return seg_metrics_from_confusion(conf)
+
+
+# ---- the network: create_network up to its CRF layer, and pred() (SEC.py:117-128, DSRG.py:169-186,439-452) --------------------------
+SEG_TRUNK = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3",
+             "conv5_1", "conv5_2", "conv5_3")
+
+
+def seg_layer_names(method):
+    """The reference's layer names of a method's network, in execution order."""
+    if method == "SEC":
+        return SEG_TRUNK + ("fc6", "fc7", "fc8")
+    if method == "DSRG":
+        return SEG_TRUNK + tuple("fc%d_%d" % (l, k) for k in (1, 2, 3, 4) for l in (6, 7, 8))
+    raise ValueError("SegNet: method %r is neither 'SEC' nor 'DSRG'" % (method,))
+
+
+def seg_state_dict(method, weights, num_classes):
+    """{'<layer>.w': HWIO float32, '<layer>.b': float32} for wsc_net_create from either form the reference keeps weights in:
+    the init-model dict {layer: {'w': HWIO, 'b': ...}} of np.load(init_model_path, allow_pickle=True).item() (SEC.py:289,
+    DSRG.py:377), or a flat dict of checkpoint variables '<layer>_weights' / '<layer>_bias' (get_weights_and_bias).  A pickled
+    init model has no fc8 -- the reference draws it at random -- so a missing layer raises KeyError naming it."""
+    out = {}
+    for layer in seg_layer_names(method):
+        if layer in weights and isinstance(weights[layer], dict):
+            ent = weights[layer]
+            if "w" not in ent or "b" not in ent:
+                raise KeyError("SegNet: weights[%r] needs 'w' and 'b'" % layer)
+            w, b = ent["w"], ent["b"]
+        elif layer + "_weights" in weights and layer + "_bias" in weights:
+            w, b = weights[layer + "_weights"], weights[layer + "_bias"]
+        else:
+            raise KeyError("SegNet: no weights for layer %r (neither weights[%r]['w' / 'b'] nor '%s_weights' / '%s_bias'); an init "
+                           "model has no fc8: give it explicitly" % (layer, layer, layer, layer))
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        if w.ndim != 4 or w.shape[0] != w.shape[1] or b.shape[0] != w.shape[3]:
+            raise ValueError("SegNet: layer %r: weights %r must be HWIO with a bias of Cout entries, got bias %r"
+                             % (layer, w.shape, b.shape))
+        if layer.startswith("fc8") and w.shape[3] != num_classes:
+            raise ValueError("SegNet: layer %r has %d outputs, num_classes = %d" % (layer, w.shape[3], num_classes))
+        out[layer + ".w"], out[layer + ".b"] = w, b
+    return out
+
+
+class SegNet:
+    """The SEC / DSRG segmentation network on the device, forward pass only (drop_prob = 0).
+
+    method 'SEC' (one fc6 / fc7 / fc8 branch at rate 12) or 'DSRG' (four ASPP branches at 6 / 12 / 18 / 24, fc8 their sum);
+    weights as seg_state_dict takes them; precision _lib.PREC_F16X3 by default -- a forward whose activations leave half's range
+    raises WscError(WSC_ERR_RANGE) once (the context's flag is cleared with the report): construct with _lib.PREC_F32 then."""
+
+    def __init__(self, method, weights, num_classes, precision=_lib.PREC_F16X3, ctx=None, min_prob=1e-4):
+        self.method = method
+        self.C = int(num_classes)
+        self.min_prob = float(min_prob)
+        sd = seg_state_dict(method, weights, self.C)
+        self.ctx = ctx or default_context()
+        self.net = _lib.Net(self.ctx, _lib.ARCH_DEEPLAB_LFOV if method == "SEC" else _lib.ARCH_DEEPLAB_ASPP, sd, self.C, precision)
+
+    def close(self):
+        """Releases the packed weights.  Never raises for a pending range error: the stream is drained through the non-raising
+        wsc_ctx_range_status, not wsc_sync."""
+        net = getattr(self, "net", None)
+        if net is not None and getattr(net, "h", None) and self.ctx.h:
+            self.ctx.range_status(clear=False)
+            self.ctx._lib.wsc_net_destroy(net.h)
+            net.h = None
+        self.net = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def map_size(self, H, W):
+        """The fc8 map size for an H x W input: (41, 41) at 321 x 321."""
+        return self.net.seg_size_hw(H, W)
+
+    def forward(self, x, want_fc8=False):
+        """x (B, H, W, 3) float32 BGR minus mean -> fc8-softmax (B, h, w, C) float32; with want_fc8 also the logits."""
+        ctx = self.ctx
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError("SegNet: input %r must be (B, H, W, 3)" % (x.shape,))
+        B, H, W, _ = x.shape
+        h, w = self.map_size(H, W)
+        n = B * h * w * self.C
+        x_dev = ctx.to_device(x, pooled=True)
+        out_dev = ctx.alloc(2 * n * 4, pooled=True)
+        try:
+            self.net.forward_seg(x_dev, B, H, W, out_dev.ptr, out_dev.ptr + 4 * n if want_fc8 else None, self.min_prob)
+            flag = ctx.range_status(clear=True)  # drains the stream; the flag is scoped to this forward
+            if flag:
+                raise _lib.WscError(_lib.WSC_ERR_RANGE, "SegNet: an activation reached half's ceiling (|v| >= 65504) in a layer "
+                                    "with %d output channels; use precision=_lib.PREC_F32 for this model" % flag)
+            both = ctx.to_host(out_dev, (2 if want_fc8 else 1, B, h, w, self.C), np.float32)
+        finally:
+            x_dev.free()
+            out_dev.free()
+        return (both[0], both[1]) if want_fc8 else both[0]
+
+    def softmax(self, x):
+        """net['fc8-softmax']: (B, H, W, 3) float32 -> (B, h, w, C), the array generate_seed_step and SegEvaluator.update take."""
+        return self.forward(x)
+
+    def resize(self, a, size):
+        """tf.image.resize_bilinear(a, size) of TensorFlow 1.x (align_corners=False) on an NHWC array, on the device."""
+        ctx = self.ctx
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        B, h, w, C = a.shape
+        H, W = int(size[0]), int(size[1])
+        src = ctx.to_device(a, pooled=True)
+        dst = ctx.alloc(B * H * W * C * 4, pooled=True)
+        try:
+            _lib.resize_bilinear_tf(ctx, src, B, h, w, C, H, W, dst)
+            return ctx.to_host(dst, (B, H, W, C), np.float32)
+        finally:
+            src.free()
+            dst.free()
+
+    def output(self, x, img_mean, crf_config, seed_size=None):
+        """create_network's return value (build_crf, DSRG.py:302-335 / SEC.py:252-283): the dense-CRF layer on fc8-softmax and on
+        the image x + img_mean, both brought to the seed size with the TF sampler; log-probabilities (B, s, s, C).
+        seed_size None: the map's own size (41 x 41 at 321 x 321, the reference's seed_size)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        prob = self.softmax(x)
+        size = prob.shape[1:3] if seed_size is None else ((seed_size, seed_size) if np.isscalar(seed_size) else tuple(seed_size))
+        image = self.resize(x + np.asarray(img_mean, dtype=np.float32).reshape(1, 1, 1, 3), size)
+        fmap = prob if tuple(prob.shape[1:3]) == tuple(size) else self.resize(prob, size)  # (the TF resize to the same size is the identity)
+        return crf_layer(fmap, image, crf_config, self.C, min_prob=self.min_prob, ctx=self.ctx)
+
+    def rescale_output(self, x, img_mean, crf_config, size=None, seed_size=None):
+        """pred()'s net['rescale_output'] (DSRG.py:439-452): output() resized to `size`, the input's (H, W) by default."""
+        out = self.output(x, img_mean, crf_config, seed_size=seed_size)
+        return self.resize(out, np.shape(x)[1:3] if size is None else size)
+
+    def preprocess(self, images, img_mean, size=(321, 321)):
+        """image_preprocess of the evaluation phases (model.py:331-342): every RGB image (H, W, 3) is resized to `size` with the TF
+        sampler, turned to BGR and has img_mean (BGR) subtracted -> (B, size[0], size[1], 3) float32, the network's input."""
+        mean = np.asarray(img_mean, dtype=np.float32).reshape(1, 1, 3)
+        out = np.empty((len(images), int(size[0]), int(size[1]), 3), np.float32)
+        for i, im in enumerate(images):
+            im = np.asarray(im, dtype=np.float32)
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("SegNet.preprocess: image %d is %r, not (H, W, 3)" % (i, im.shape))
+            out[i] = self.resize(im[None], size)[0][:, :, ::-1] - mean
+        return out
