@@ -541,6 +541,34 @@ int wsc_seg_resize_argmax(wsc_ctx *ctx, const float *q_dev, int B, int C, const 
                           const int32_t *src_hw_host /*[B][2]*/, const int32_t *out_hw_host /*[B][2]*/,
                           const int64_t *label_off_host /*[B]*/, int32_t *label_dev);
 
+/* ---- SEC / DSRG: the steps that keep Model.predict (model.py:542-586) and the CRF layer (build_crf) on the device ----------------
+ * All four are asynchronous on the ctx stream, copy their host descriptor arrays during the call, and check their limits before
+ * any launch (WSC_ERR_INVALID, the text names the argument): no NULL pointer, every size >= 1 (a pixel count within int32),
+ * 1 <= C <= 32, 1 <= n / B <= 65535.  The TF resize is wsc_resize_bilinear_tf's, operation for operation (no FMA contraction):
+ * a value has the bits that call gives for it, and equal sizes pass through exactly (t == 0). */
+
+/* image_preprocess of the evaluation phases (model.py:332-346) for a ragged batch in ONE launch.
+ * img_dev: packed uint8 RGB images, image i's [h_i][w_i][3] block at BYTE offset src_off_host[i], sizes src_hw_host[i] = {h_i, w_i};
+ * x_dev float32 [n][H][W][3]:  x[i][y][x][c] = resize_bilinear_tf(float(img_i), (H, W))[y][x][2 - c] - mean_bgr_host[c]  (fp32). */
+int wsc_seg_preprocess_u8(wsc_ctx *ctx, const uint8_t *img_dev, int n, const int32_t *src_hw_host /*[n][2]*/,
+                          const int64_t *src_off_host /*[n]*/, const float *mean_bgr_host /*[3]*/, int H, int W, float *x_dev);
+
+/* The CRF layer's zoomed image (DSRG.py:318-319,325 / SEC.py build_crf): v = x + mean_host[c] (one fp32 rounding), TF-resized to
+ * (sh, sw), then image.astype(np.uint8), DEFINED here as truncation toward zero to int32 and the low 8 bits of that,
+ * (uint8_t)(int32_t)v: numpy's result for every in-range value, astype(np.int32).astype(np.uint8) for finite |v| < 2^31.  NaN and
+ * larger magnitudes are outside the contract.  The channel order stays as it is.
+ * x_dev float32 [B][H][W][3];  out_dev uint8 [B][sh][sw][3] (what wsc_crf_create takes). */
+int wsc_seg_crf_image_u8(wsc_ctx *ctx, const float *x_dev, int B, int H, int W, const float *mean_host /*[3]*/, int sh, int sw,
+                         uint8_t *out_dev);
+
+/* The tail of the `crf` closure (DSRG.py:329-332): p_c = q_c < min_prob ? min_prob : q_c;  s = the fp32 sum of p_c in class order;
+ * out_c = logf(p_c / s).  q_dev float32 [B][C][n] class-major (wsc_crf_inference's q);  out_dev float32 [B][n][C] NHWC. */
+int wsc_seg_crf_logprob(wsc_ctx *ctx, const float *q_dev, int B, int C, long long n, float min_prob, float *out_dev);
+
+/* NHWC maps [B][n][C] -> class-major planes [B][C][n], the layout wsc_seg_resize_argmax reads: the is_eval=False pass of eval_miou
+ * (model.py:666-669) takes the arg-max of the network's NHWC softmax through that call at equal sizes. */
+int wsc_seg_planes_from_nhwc(wsc_ctx *ctx, const float *src_dev, int B, int C, long long n, float *dst_dev);
+
 /* ---- HistoSegNet post-processing (03c_hsn/utilities.py:231-397), device resident ---------- */
 
 /* HSN grad_cam after the einsum (utilities.py:262-277), for the NHWC maps of wsc_net_forward_gradcam(relu = 0):

@@ -138,6 +138,10 @@ _SIGNATURES = {
     "wsc_cue_seeds": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d, _vp, _vp]),
     "wsc_seg_unary_nhwc": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "wsc_seg_resize_argmax": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "wsc_seg_preprocess_u8": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "wsc_seg_crf_image_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    "wsc_seg_crf_logprob": (_i, [_vp, _vp, _i, _i, ctypes.c_longlong, _f, _vp]),
+    "wsc_seg_planes_from_nhwc": (_i, [_vp, _vp, _i, _i, ctypes.c_longlong, _vp]),
     "wsc_hsn_gradcam_post": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i]),
     "wsc_hsn_voc_background": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "wsc_hsn_class_mass": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -976,6 +980,35 @@ def seg_resize_argmax(ctx, q_dev, C, src_sizes, out_sizes, q_off, label_off, lab
     B, so, sh, oh, do = _seg_tables(src_sizes, out_sizes, q_off, label_off)
     check(ctx._lib.wsc_seg_resize_argmax(ctx.h, _ptr(q_dev), B, int(C), so.ctypes.data, sh.ctypes.data, oh.ctypes.data, do.ctypes.data,
                                          _ptr(label_dev)))
+
+
+def seg_preprocess_u8(ctx, img_dev, sizes, offsets, mean_bgr, out_hw, x_dev):
+    """wsc_seg_preprocess_u8: packed uint8 RGB images ([h_i][w_i][3] blocks at byte `offsets`) -> float32 [n][H][W][3], the TF 1.x
+    bilinear resize to out_hw, BGR, minus mean_bgr: image_preprocess of a ragged batch in one launch."""
+    n = len(sizes)
+    size_hw = np.ascontiguousarray(sizes, dtype=np.int32).reshape(n, 2)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    m = np.ascontiguousarray(mean_bgr, dtype=np.float32).reshape(3)
+    check(ctx._lib.wsc_seg_preprocess_u8(ctx.h, _ptr(img_dev), n, size_hw.ctypes.data, off.ctypes.data, m.ctypes.data, int(out_hw[0]),
+                                         int(out_hw[1]), _ptr(x_dev)))
+
+
+def seg_crf_image_u8(ctx, x_dev, B, H, W, mean, out_hw, out_dev):
+    """wsc_seg_crf_image_u8: float32 [B][H][W][3] -> uint8 [B][sh][sw][3], (x + mean) TF-resized to out_hw and cast as
+    image.astype(np.uint8) (truncation to int32, low 8 bits): the CRF layer's zoomed image."""
+    m = np.ascontiguousarray(mean, dtype=np.float32).reshape(3)
+    check(ctx._lib.wsc_seg_crf_image_u8(ctx.h, _ptr(x_dev), int(B), int(H), int(W), m.ctypes.data, int(out_hw[0]), int(out_hw[1]),
+                                        _ptr(out_dev)))
+
+
+def seg_crf_logprob(ctx, q_dev, B, C, n, min_prob, out_dev):
+    """wsc_seg_crf_logprob: class-major marginals [B][C][n] -> NHWC [B][n][C] log(clamp(q, min_prob) / their sum over the classes)."""
+    check(ctx._lib.wsc_seg_crf_logprob(ctx.h, _ptr(q_dev), int(B), int(C), int(n), float(min_prob), _ptr(out_dev)))
+
+
+def seg_planes_from_nhwc(ctx, src_dev, B, C, n, dst_dev):
+    """wsc_seg_planes_from_nhwc: NHWC maps [B][n][C] -> class-major planes [B][C][n] (the layout seg_resize_argmax reads)."""
+    check(ctx._lib.wsc_seg_planes_from_nhwc(ctx.h, _ptr(src_dev), int(B), int(C), int(n), _ptr(dst_dev)))
 
 
 def ir_label_combine(ctx, fg_pred_dev, bg_pred_dev, keys, N, conf_dev):

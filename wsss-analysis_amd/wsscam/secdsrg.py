@@ -5,6 +5,10 @@
     generate_seed_step   DSRG.py:356-369 (and single_generate_seed_step :7-62 behind its process pool)
     crf_layer            the `crf` closure of DSRG.py:323-332 / SEC.py:270-280
     SegEvaluator         eval_miou (model.py:665-719)
+    DeviceMaps           an array that stays on the device between those calls; SegNet's *_dev methods, crf_layer_dev and
+                         SegEvaluator.update take and return it
+    Predictor            Model.predict's loop (model.py:542-586): decoded images in, confusion matrix out, nothing in between
+                         on the host
 
 The losses, the optimiser and the training loop of SEC / DSRG are out of scope.  Nothing here imports
 TensorFlow: Model.predict runs on this module alone."""
@@ -12,6 +16,69 @@ import numpy as np
 
 from . import _lib
 from .misc.imutils import default_context
+
+
+class DeviceMaps:
+    """A C-contiguous array in ONE pooled device buffer of a context: `shape`, `dtype`, `.ptr` (device address), `.to_host()`,
+    `.free()`; a context manager frees it on exit.  The buffer is pooled, so it belongs to its context's stream alone.
+    A packed ragged batch of uint8 images (SegNet.preprocess_dev(keep_images=True)) also carries `sizes` [(h, w)] and `offsets`
+    (bytes); its shape is the flat byte count."""
+
+    def __init__(self, ctx, shape, dtype=np.float32, buf=None):
+        self.ctx = ctx
+        self.shape = tuple(int(v) for v in shape)
+        self.dtype = np.dtype(dtype)
+        self.sizes = self.offsets = None
+        self.buf = buf if buf is not None else ctx.alloc(max(self.nbytes, 1), pooled=True)
+
+    @classmethod
+    def from_host(cls, ctx, arr, dtype=None):
+        """One upload of a host array."""
+        a = np.ascontiguousarray(arr, dtype=dtype)
+        return cls(ctx, a.shape, a.dtype, ctx.to_device(a, pooled=True))
+
+    @property
+    def nbytes(self):
+        return int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+
+    @property
+    def ptr(self):
+        return None if self.buf is None else self.buf.ptr
+
+    def to_host(self):
+        if self.buf is None:
+            raise ValueError("DeviceMaps: freed")
+        return self.ctx.to_host(self.buf, self.shape, self.dtype)
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+            self.buf = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+def _image_blocks(images):
+    """uint8 DeviceMaps -> ([(h, w)], byte offsets): a packed ragged batch, or (B, H, W, 3)."""
+    if images.dtype != np.uint8:
+        raise ValueError("device images must be uint8, got %s" % images.dtype)
+    if images.sizes is not None:
+        return [tuple(int(v) for v in hw) for hw in images.sizes], [int(o) for o in images.offsets]
+    if len(images.shape) != 4 or images.shape[3] != 3:
+        raise ValueError("device images %r must be (B, H, W, 3) or a packed ragged batch" % (images.shape,))
+    B, H, W, _ = images.shape
+    return [(H, W)] * B, [b * H * W * 3 for b in range(B)]
+
+
+def _seed_hw(seed_size, map_hw):
+    if seed_size is None:
+        return tuple(map_hw)
+    return (int(seed_size), int(seed_size)) if np.isscalar(seed_size) else (int(seed_size[0]), int(seed_size[1]))
 
 
 def generate_seed_step(tags, cues, probs, ctx=None, th_f=0.5, th_b=0.7):
@@ -80,6 +147,51 @@ def crf_layer(featmap, image, crf_config, num_classes, min_prob=1e-4, ctx=None, 
     return (ret, q) if return_q else ret
 
 
+def crf_layer_dev(prob, x, img_mean, crf_config, num_classes, min_prob=1e-4, seed_size=None, ctx=None):
+    """The whole build_crf layer (DSRG.py:302-335 / SEC.py:252-283) without a host copy.
+
+    prob DeviceMaps (B, h, w, C) fc8-softmax;  x DeviceMaps (B, H, W, 3), the network's input;  img_mean (3,) in x's channel order.
+    The image x + img_mean and -- when seed_size differs from (h, w) -- the map are brought to the seed size with the TF sampler
+    (wsc_seg_crf_image_u8, wsc_resize_bilinear_tf), the unaries are -log of the map (wsc_seg_unary_nhwc at equal sizes: its
+    pass-through), ONE wsc_crf runs over the B images, and wsc_seg_crf_logprob clamps, renormalises and takes the log.
+    -> DeviceMaps float32 (B, s_h, s_w, C) log-probabilities.  Against crf_layer on SegNet.resize's image: the unaries use the
+    device logf where crf_layer uses np.log, and the tail sums in class order in fp32."""
+    ctx = ctx or prob.ctx
+    if len(prob.shape) != 4 or prob.dtype != np.float32 or len(x.shape) != 4 or x.shape[3] != 3 or x.dtype != np.float32:
+        raise ValueError("crf_layer_dev: prob %r must be float32 (B, h, w, C), x %r float32 (B, H, W, 3)" % (prob.shape, x.shape))
+    B, h, w, C = prob.shape
+    if C != num_classes:
+        raise ValueError("crf_layer_dev: prob has %d classes, num_classes = %d" % (C, num_classes))
+    if x.shape[0] != B:
+        raise ValueError("crf_layer_dev: %d maps for %d images" % (B, x.shape[0]))
+    sh, sw = _seed_hw(seed_size, (h, w))
+    n = sh * sw
+    bufs = [ctx.alloc(B * n * 3, pooled=True), ctx.alloc(B * n * C * 4, pooled=True), ctx.alloc(B * n * C * 4, pooled=True)]
+    img_dev, u_dev, q_dev = bufs
+    out = DeviceMaps(ctx, (B, sh, sw, C), np.float32)
+    crf = None
+    try:
+        _lib.seg_crf_image_u8(ctx, x.ptr, B, x.shape[1], x.shape[2], img_mean, (sh, sw), img_dev)
+        fmap = prob.ptr
+        if (h, w) != (sh, sw):  # (the TF resize to the same size is the identity)
+            bufs.append(ctx.alloc(B * n * C * 4, pooled=True))
+            fmap = _lib.resize_bilinear_tf(ctx, prob.ptr, B, h, w, C, sh, sw, bufs[-1]).ptr
+        off = np.arange(B, dtype=np.int64) * (n * C)
+        _lib.seg_unary_nhwc(ctx, fmap, C, [(sh, sw)] * B, [(sh, sw)] * B, off, off, u_dev)
+        crf = _lib.Crf(ctx, img_dev, B, sh, sw, crf_config["g_sxy"], crf_config["bi_sxy"], crf_config["bi_srgb"])
+        crf.inference(u_dev, C, crf_config["g_compat"], crf_config["bi_compat"], int(crf_config["iterations"]), q_dev, None)
+        _lib.seg_crf_logprob(ctx, q_dev, B, C, n, min_prob, out.ptr)
+        return out
+    except Exception:
+        out.free()
+        raise
+    finally:
+        if crf is not None:
+            crf.close()
+        for d in bufs:
+            d.free()
+
+
 # ---- the prediction tail: eval_miou with is_eval=True (model.py:665-719, called from predict :542-586) -------------------------
 def seg_gt_index(gt, num_classes, colours=None):
     """Ground truth of one image -> uint8 class index plane (H, W) in [0, num_classes].
@@ -121,24 +233,27 @@ def seg_metrics_from_confusion(conf):
 
 
 class SegEvaluator:
-    """The per-image loop of eval_miou (model.py:665-719, is_eval=True) for a batch at a time, device resident between the
-    upload of the network's softmax maps and the confusion matrix.
+    """The per-image loop of eval_miou (model.py:665-719) for a batch at a time, device resident between the network's softmax maps
+    and the confusion matrix.
 
     resize_after_crf=False (VOC, ADP; :686-689): image and map are brought to the ground truth's size, CRF there.
     resize_after_crf=True (DeepGlobe; :693-695): CRF at the network size on the image as given, the marginals are resized.
     crf_config: {g_sxy, g_compat, bi_sxy, bi_srgb, bi_compat, iterations} (model.crf_config_test).
+    crf=False: the is_eval=False pass (:666-669, :698-719) -- no resize and no CRF, the arg-max of the map as it is against a
+    ground truth of the map's size; crf_config, resize_after_crf and update()'s images are not used.
     The matrix stays on the device over the whole run; metrics() downloads it."""
 
-    def __init__(self, num_classes, crf_config, colours=None, resize_after_crf=False, ctx=None):
+    def __init__(self, num_classes, crf_config, colours=None, resize_after_crf=False, ctx=None, crf=True):
         self.ctx = ctx or default_context()
         self.C = int(num_classes)
         if not 1 <= self.C <= 32:
             raise ValueError("SegEvaluator: num_classes = %d (the dense CRF takes 1..32 classes)" % self.C)
-        self.cfg = dict(crf_config)
+        self.cfg = dict(crf_config) if crf_config is not None else {}
         self.colours = None if colours is None else [tuple(int(v) for v in c) for c in colours]
         if self.colours is not None and len(self.colours) != self.C:
             raise ValueError("SegEvaluator: %d colours for %d classes" % (len(self.colours), self.C))
         self.resize_after_crf = bool(resize_after_crf)
+        self.crf = bool(crf)
         nbytes = (self.C + 1) * (self.C + 1) * 8
         self.conf_dev = self.ctx.alloc(nbytes, pooled=True)
         _lib.check(self.ctx._lib.wsc_memset(self.ctx.h, self.conf_dev.ptr, 0, nbytes))
@@ -148,48 +263,78 @@ class SegEvaluator:
             self.conf_dev.free()
             self.conf_dev = None
 
-    def update(self, probs, images, gts, want_pred=False):
-        """probs[b] (h_b, w_b, C) float32 softmax (> 0), images[b] (H, W, 3) uint8, gts[b] as seg_gt_index takes it.
-        -> with want_pred the list of (H_b, W_b) uint8 label maps at the ground truths' sizes, else None."""
-        ctx, C, cfg = self.ctx, self.C, self.cfg
-        B = len(probs)
-        if B == 0 or len(images) != B or len(gts) != B:
-            raise ValueError("SegEvaluator.update: %d maps, %d images, %d ground truths" % (B, len(images), len(gts)))
+    def _map_blocks(self, probs):
+        """-> (host maps or None when they are on the device already, [(h_b, w_b)])"""
+        C = self.C
+        if isinstance(probs, DeviceMaps):
+            if probs.dtype != np.float32 or len(probs.shape) != 4 or probs.shape[3] != C or probs.shape[0] == 0:
+                raise ValueError("SegEvaluator.update: device maps %r %s must be float32 (B, h, w, %d)" % (probs.shape, probs.dtype, C))
+            return None, [tuple(probs.shape[1:3])] * probs.shape[0]
         maps = [np.ascontiguousarray(p, dtype=np.float32) for p in probs]
-        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        return maps, [tuple(m.shape[:2]) for m in maps]
+
+    def update(self, probs, images, gts, want_pred=False):
+        """probs[b] (h_b, w_b, C) float32 softmax (> 0) -- a list of host arrays, or ONE DeviceMaps (B, h, w, C) that is read in
+        place (no upload); images[b] (H, W, 3) uint8 -- host arrays, or a uint8 DeviceMaps: (B, H, W, 3), or the packed ragged
+        batch SegNet.preprocess_dev(keep_images=True) returns; gts[b] as seg_gt_index takes it.
+        -> with want_pred the list of (H_b, W_b) uint8 label maps at the ground truths' sizes, else None."""
+        if not self.crf:
+            return self._update_argmax(probs, gts, want_pred)
+        ctx, C, cfg = self.ctx, self.C, self.cfg
+        dev_imgs = isinstance(images, DeviceMaps)
+        B = probs.shape[0] if isinstance(probs, DeviceMaps) else len(probs)
+        n_img = len(_image_blocks(images)[0]) if dev_imgs else len(images)
+        if B == 0 or n_img != B or len(gts) != B:
+            raise ValueError("SegEvaluator.update: %d maps, %d images, %d ground truths" % (B, n_img, len(gts)))
+        maps, src_hw = self._map_blocks(probs)
+        if dev_imgs:
+            img_hw, img_at = _image_blocks(images)
+            imgs = None
+        else:
+            imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+            img_hw = [tuple(im.shape[:2]) for im in imgs]
         gt = [np.ascontiguousarray(seg_gt_index(g, C, self.colours)) for g in gts]
         for b in range(B):
-            if maps[b].ndim != 3 or maps[b].shape[2] != C or imgs[b].ndim != 3 or imgs[b].shape[2] != 3:
+            if (maps is not None and (maps[b].ndim != 3 or maps[b].shape[2] != C)) or \
+                    (imgs is not None and (imgs[b].ndim != 3 or imgs[b].shape[2] != 3)):
                 raise ValueError("SegEvaluator.update: image %d: map %r must be (h, w, %d), image %r (H, W, 3)"
-                                 % (b, maps[b].shape, C, imgs[b].shape))
-            if self.resize_after_crf and imgs[b].shape[:2] != maps[b].shape[:2]:
+                                 % (b, maps[b].shape if maps is not None else src_hw[b], C,
+                                    imgs[b].shape if imgs is not None else img_hw[b]))
+            if self.resize_after_crf and img_hw[b] != src_hw[b]:
                 raise ValueError("SegEvaluator.update: image %d: with resize_after_crf the image %r has the map's size %r"
-                                 % (b, imgs[b].shape[:2], maps[b].shape[:2]))
-        src_hw = [m.shape[:2] for m in maps]
+                                 % (b, img_hw[b], src_hw[b]))
         out_hw = [g.shape for g in gt]
         crf_hw = src_hw if self.resize_after_crf else out_hw  # where the CRF runs
         n_out = [h * w for h, w in out_hw]
         n_crf = [h * w for h, w in crf_hw]
-        prob_off = np.concatenate(([0], np.cumsum([m.size for m in maps])))
+        prob_off = np.concatenate(([0], np.cumsum([h * w * C for h, w in src_hw])))
         crf_off = np.concatenate(([0], np.cumsum(n_crf)))  # pixels; times C: the unaries / marginals
         out_off = np.concatenate(([0], np.cumsum(n_out)))
-        # one uint8 upload: [images that already have the CRF's size | images to resize | ground truths]; an image that is
-        # resized lands in `res_dev`, the images of one target size next to each other (one wsc_resize_u8 per size)
+        # one uint8 upload: [images that already have the CRF's size | images to resize | ground truths] (device images stay
+        # where they are); an image that is resized lands in `res_dev`, the images of one target size next to each other (one
+        # wsc_resize_u8 per size)
         todo = {}
         for b in range(B):
-            if imgs[b].shape[:2] != tuple(crf_hw[b]):  # (cv2.resize returns a copy otherwise)
+            if img_hw[b] != tuple(crf_hw[b]):  # (cv2.resize returns a copy otherwise)
                 todo.setdefault(tuple(crf_hw[b]), []).append(b)
         rgb_at, res_at, src_at, parts, pos, res_bytes = [None] * B, [None] * B, [None] * B, [], 0, 0
         for b in range(B):
-            if imgs[b].shape[:2] == tuple(crf_hw[b]):
-                rgb_at[b] = pos
-                parts.append(imgs[b].reshape(-1))
-                pos += imgs[b].size
+            if img_hw[b] == tuple(crf_hw[b]):
+                if dev_imgs:
+                    rgb_at[b] = img_at[b]
+                else:
+                    rgb_at[b] = pos
+                    parts.append(imgs[b].reshape(-1))
+                    pos += imgs[b].size
         for hw, bs in todo.items():
             for b in bs:
-                src_at[b], res_at[b] = pos, res_bytes
-                parts.append(imgs[b].reshape(-1))
-                pos += imgs[b].size
+                res_at[b] = res_bytes
+                if dev_imgs:
+                    src_at[b] = img_at[b]
+                else:
+                    src_at[b] = pos
+                    parts.append(imgs[b].reshape(-1))
+                    pos += imgs[b].size
                 res_bytes += hw[0] * hw[1] * 3
         gt_at = pos
         parts.extend(g.reshape(-1) for g in gt)
@@ -202,17 +347,18 @@ class SegEvaluator:
         crf = None
         try:
             u8_dev = dev(ctx.to_device(np.concatenate(parts), pooled=True))
-            prob_dev = dev(ctx.to_device(np.concatenate([m.reshape(-1) for m in maps]), pooled=True))
-            rgb_ptr = [None if rgb_at[b] is None else u8_dev.ptr + rgb_at[b] for b in range(B)]
+            img_ptr = images.ptr if dev_imgs else u8_dev.ptr
+            prob_ptr = probs.ptr if maps is None else dev(ctx.to_device(np.concatenate([m.reshape(-1) for m in maps]), pooled=True)).ptr
+            rgb_ptr = [None if rgb_at[b] is None else img_ptr + rgb_at[b] for b in range(B)]
             if todo:
                 res_dev = dev(ctx.alloc(res_bytes, pooled=True))
                 for hw, bs in todo.items():
-                    _lib.resize_u8(ctx, u8_dev, [imgs[b].shape[:2] for b in bs], [src_at[b] for b in bs], hw,
+                    _lib.resize_u8(ctx, img_ptr, [img_hw[b] for b in bs], [src_at[b] for b in bs], hw,
                                    res_dev.ptr + res_at[bs[0]])
                     for b in bs:
                         rgb_ptr[b] = res_dev.ptr + res_at[b]
             u_dev = dev(ctx.alloc(int(crf_off[-1]) * C * 4, pooled=True))
-            _lib.seg_unary_nhwc(ctx, prob_dev, C, src_hw, crf_hw, prob_off[:-1], crf_off[:-1] * C, u_dev)
+            _lib.seg_unary_nhwc(ctx, prob_ptr, C, src_hw, crf_hw, prob_off[:-1], crf_off[:-1] * C, u_dev)
             lab_dev = dev(ctx.alloc(int(out_off[-1]) * 4, pooled=True))
             crf = _lib.CrfV(ctx, rgb_ptr, crf_hw, cfg["g_sxy"], cfg["bi_sxy"], cfg["bi_srgb"])
             u_ptr = [u_dev.ptr + int(crf_off[b]) * C * 4 for b in range(B)]
@@ -224,17 +370,62 @@ class SegEvaluator:
             else:
                 crf.inference(u_ptr, [C] * B, cfg["g_compat"], cfg["bi_compat"], int(cfg["iterations"]),
                               argmax_ptrs=[lab_dev.ptr + int(out_off[b]) * 4 for b in range(B)])
-            pred_dev = dev(ctx.alloc(int(out_off[-1]), pooled=True)) if want_pred else None
-            # ignore_label -1: no uint8 ground-truth index equals it, every pixel is counted
-            _lib.label_confusion_nn(ctx, lab_dev, out_hw, out_hw, out_off[:-1], u8_dev.ptr + gt_at, C + 1, self.conf_dev,
-                                    pred_dev=pred_dev, ignore_label=-1)
-            if want_pred:
-                flat = ctx.to_host(pred_dev, (int(out_off[-1]),), np.uint8)
-                return [flat[out_off[b]:out_off[b + 1]].reshape(out_hw[b]) for b in range(B)]
-            return None
+            return self._count(lab_dev, out_hw, out_off, u8_dev.ptr + gt_at, want_pred, dev)
         finally:
             if crf is not None:
                 crf.close()
+            for d in bufs:
+                d.free()
+
+    def _count(self, lab_dev, out_hw, out_off, gt_ptr, want_pred, dev):
+        """int32 labels at the ground truths' sizes -> the confusion matrix (accumulated) and, with want_pred, the uint8 maps"""
+        ctx = self.ctx
+        pred_dev = dev(ctx.alloc(int(out_off[-1]), pooled=True)) if want_pred else None
+        # ignore_label -1: no uint8 ground-truth index equals it, every pixel is counted
+        _lib.label_confusion_nn(ctx, lab_dev, out_hw, out_hw, out_off[:-1], gt_ptr, self.C + 1, self.conf_dev,
+                                pred_dev=pred_dev, ignore_label=-1)
+        if want_pred:
+            flat = ctx.to_host(pred_dev, (int(out_off[-1]),), np.uint8)
+            return [flat[out_off[b]:out_off[b + 1]].reshape(out_hw[b]) for b in range(len(out_hw))]
+        return None
+
+    def _update_argmax(self, probs, gts, want_pred):
+        """crf=False: np.argmax(pred_curr, axis=-1) of the map as it is (first maximum: wsc_seg_resize_argmax at equal sizes, on
+        the class-major planes wsc_seg_planes_from_nhwc writes) and the same counting."""
+        ctx, C = self.ctx, self.C
+        B = probs.shape[0] if isinstance(probs, DeviceMaps) else len(probs)
+        if B == 0 or len(gts) != B:
+            raise ValueError("SegEvaluator.update: %d maps, %d ground truths" % (B, len(gts)))
+        maps, src_hw = self._map_blocks(probs)
+        gt = [np.ascontiguousarray(seg_gt_index(g, C, self.colours)) for g in gts]
+        for b in range(B):
+            if maps is not None and (maps[b].ndim != 3 or maps[b].shape[2] != C):
+                raise ValueError("SegEvaluator.update: image %d: map %r must be (h, w, %d)" % (b, maps[b].shape, C))
+            if tuple(gt[b].shape) != src_hw[b]:
+                raise ValueError("SegEvaluator.update: image %d: without the CRF the ground truth %r has the map's size %r"
+                                 % (b, gt[b].shape, src_hw[b]))
+        n_pix = [h * w for h, w in src_hw]
+        out_off = np.concatenate(([0], np.cumsum(n_pix)))
+        bufs = []
+
+        def dev(buf):
+            bufs.append(buf)
+            return buf
+
+        try:
+            gt_dev = dev(ctx.to_device(np.concatenate([g.reshape(-1) for g in gt]), pooled=True))
+            prob_ptr = probs.ptr if maps is None else dev(ctx.to_device(np.concatenate([m.reshape(-1) for m in maps]), pooled=True)).ptr
+            planes = dev(ctx.alloc(int(out_off[-1]) * C * 4, pooled=True))
+            if maps is None:
+                _lib.seg_planes_from_nhwc(ctx, prob_ptr, B, C, n_pix[0], planes)
+            else:
+                for b in range(B):
+                    o = int(out_off[b]) * C * 4
+                    _lib.seg_planes_from_nhwc(ctx, prob_ptr + o, 1, C, n_pix[b], planes.ptr + o)
+            lab_dev = dev(ctx.alloc(int(out_off[-1]) * 4, pooled=True))
+            _lib.seg_resize_argmax(ctx, planes, C, src_hw, src_hw, out_off[:-1] * C, out_off[:-1], lab_dev)
+            return self._count(lab_dev, src_hw, out_off, gt_dev.ptr, want_pred, dev)
+        finally:
             for d in bufs:
                 d.free()
 
@@ -389,3 +580,167 @@ class SegNet:
                 raise ValueError("SegNet.preprocess: image %d is %r, not (H, W, 3)" % (i, im.shape))
             out[i] = self.resize(im[None], size)[0][:, :, ::-1] - mean
         return out
+
+    # ---- device-resident twins: the same kernels, DeviceMaps in and out, no host array in between -----------------------------
+    def _on_device(self, x):
+        """-> (DeviceMaps (B, H, W, 3), whether this call uploaded it and so frees it)"""
+        if isinstance(x, DeviceMaps):
+            if x.dtype != np.float32 or len(x.shape) != 4 or x.shape[3] != 3:
+                raise ValueError("SegNet: input %r %s must be float32 (B, H, W, 3)" % (x.shape, x.dtype))
+            return x, False
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError("SegNet: input %r must be (B, H, W, 3)" % (x.shape,))
+        return DeviceMaps.from_host(self.ctx, x), True
+
+    def forward_dev(self, x, want_fc8=False):
+        """forward() with the maps left on the device: x a DeviceMaps (B, H, W, 3) (a host array is uploaded once) ->
+        DeviceMaps (B, h, w, C) fc8-softmax; with want_fc8 (softmax, logits).  The range flag as in forward(): the stream is
+        drained through range_status(clear=True) and a saturated forward raises WscError(WSC_ERR_RANGE) once."""
+        ctx = self.ctx
+        xd, mine = self._on_device(x)
+        outs = []
+        try:
+            B, H, W, _ = xd.shape
+            h, w = self.map_size(H, W)
+            outs = [DeviceMaps(ctx, (B, h, w, self.C), np.float32) for _ in range(2 if want_fc8 else 1)]
+            self.net.forward_seg(xd.ptr, B, H, W, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
+            flag = ctx.range_status(clear=True)  # drains the stream; the flag is scoped to this forward
+            if flag:
+                raise _lib.WscError(_lib.WSC_ERR_RANGE, "SegNet: an activation reached half's ceiling (|v| >= 65504) in a layer "
+                                    "with %d output channels; use precision=_lib.PREC_F32 for this model" % flag)
+        except Exception:
+            for o in outs:
+                o.free()
+            raise
+        finally:
+            if mine:
+                xd.free()
+        return (outs[0], outs[1]) if want_fc8 else outs[0]
+
+    def softmax_dev(self, x):
+        """net['fc8-softmax'] on the device: what SegEvaluator.update and crf_layer_dev take."""
+        return self.forward_dev(x)
+
+    def resize_dev(self, a, size):
+        """tf.image.resize_bilinear(a, size) of a float32 NHWC DeviceMaps -> a new DeviceMaps."""
+        B, h, w, C = a.shape
+        out = DeviceMaps(self.ctx, (B, int(size[0]), int(size[1]), C), np.float32)
+        try:
+            _lib.resize_bilinear_tf(self.ctx, a.ptr, B, h, w, C, out.shape[1], out.shape[2], out.ptr)
+        except Exception:
+            out.free()
+            raise
+        return out
+
+    def output_dev(self, x, img_mean, crf_config, seed_size=None):
+        """output() on the device: fc8-softmax, then crf_layer_dev on it and on x -> DeviceMaps (B, s_h, s_w, C)."""
+        xd, mine = self._on_device(x)
+        prob = None
+        try:
+            prob = self.softmax_dev(xd)
+            return crf_layer_dev(prob, xd, img_mean, crf_config, self.C, min_prob=self.min_prob, seed_size=seed_size, ctx=self.ctx)
+        finally:
+            if prob is not None:
+                prob.free()
+            if mine:
+                xd.free()
+
+    def rescale_output_dev(self, x, img_mean, crf_config, size=None, seed_size=None):
+        """rescale_output() on the device: wsc_resize_bilinear_tf of output_dev's log-probabilities to `size`, the input's (H, W)
+        by default -> DeviceMaps (B, H, W, C).  (The log is taken once per seed pixel, before the resize.)"""
+        xd, mine = self._on_device(x)
+        try:
+            with self.output_dev(xd, img_mean, crf_config, seed_size=seed_size) as out:
+                return self.resize_dev(out, xd.shape[1:3] if size is None else size)
+        finally:
+            if mine:
+                xd.free()
+
+    def preprocess_dev(self, images, img_mean, size=(321, 321), keep_images=False):
+        """preprocess() for the whole ragged batch in one upload of the packed uint8 images and ONE wsc_seg_preprocess_u8 launch
+        -> DeviceMaps (B, size[0], size[1], 3) with preprocess()'s bits; with keep_images (that, the packed images as a uint8
+        DeviceMaps carrying `sizes` and `offsets`: SegEvaluator.update takes it as its `images`)."""
+        ctx = self.ctx
+        imgs = [np.asarray(im) for im in images]
+        for i, im in enumerate(imgs):
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("SegNet.preprocess_dev: image %d is %r, not (H, W, 3)" % (i, im.shape))
+            if im.dtype != np.uint8:
+                raise ValueError("SegNet.preprocess_dev: image %d is %s, not uint8 (preprocess() takes other dtypes)" % (i, im.dtype))
+        if not imgs:
+            raise ValueError("SegNet.preprocess_dev: no images")
+        sizes = [im.shape[:2] for im in imgs]
+        offsets = np.concatenate(([0], np.cumsum([im.size for im in imgs])))[:-1]
+        packed = DeviceMaps.from_host(ctx, np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in imgs]))
+        packed.sizes, packed.offsets = sizes, [int(o) for o in offsets]
+        x = None
+        try:
+            x = DeviceMaps(ctx, (len(imgs), int(size[0]), int(size[1]), 3), np.float32)
+            _lib.seg_preprocess_u8(ctx, packed.ptr, sizes, offsets, img_mean, x.shape[1:3], x.ptr)
+        except Exception:
+            packed.free()
+            if x is not None:
+                x.free()
+            raise
+        if keep_images:
+            return x, packed
+        packed.free()
+        return x
+
+
+class Predictor:
+    """Model.predict's loop (model.py:542-586 with eval_miou :614-739) bound to one SegNet and one SegEvaluator: update() takes the
+    decoded RGB uint8 images and the ground truths of a batch and runs preprocess_dev -> softmax_dev -> SegEvaluator.update.  The
+    images are uploaded once, the network's input and its maps never leave the device; without want_pred nothing is downloaded.
+    The evaluator takes fc8-softmax.
+
+    resize_after_crf=False (VOC, ADP): the CRF runs at the ground truth's size on the image as decoded (:686-689).
+    resize_after_crf=True (DeepGlobe): the CRF image is `np.uint8(img[j])` of :693 -- the PREPROCESSED network input cast back to
+    uint8 (wsc_seg_crf_image_u8 with a zero mean), brought to the map's size with the TF sampler since the evaluator runs that CRF
+    at the map's size.  This follows the reference literally: the values are BGR minus the mean, negative ones wrap modulo 256.
+    precision, ctx, weights: as SegNet takes them;  crf_config_test, colours: as SegEvaluator."""
+
+    def __init__(self, method, weights, num_classes, crf_config_test, img_mean, size=(321, 321), colours=None, resize_after_crf=False,
+                 precision=_lib.PREC_F16X3, ctx=None):
+        self.ctx = ctx or default_context()
+        self.size = (int(size[0]), int(size[1]))
+        self.img_mean = np.asarray(img_mean, dtype=np.float32).reshape(3)
+        self.resize_after_crf = bool(resize_after_crf)
+        self.net = self.ev = None
+        self.net = SegNet(method, weights, num_classes, precision=precision, ctx=self.ctx)
+        try:
+            self.ev = SegEvaluator(num_classes, crf_config_test, colours=colours, resize_after_crf=resize_after_crf, ctx=self.ctx)
+        except Exception:
+            self.close()
+            raise
+
+    def update(self, img_list, gt_list, want_pred=False):
+        """img_list[b] (H_b, W_b, 3) uint8 RGB, gt_list[b] as seg_gt_index takes it -> SegEvaluator.update's return value."""
+        ctx, held = self.ctx, []
+        try:
+            x, images = self.net.preprocess_dev(img_list, self.img_mean, self.size, keep_images=True)
+            held += [x, images]
+            prob = self.net.softmax_dev(x)
+            held.append(prob)
+            if self.resize_after_crf:
+                B, h, w, _ = prob.shape
+                images.free()
+                images = DeviceMaps(ctx, (B, h, w, 3), np.uint8)
+                held.append(images)
+                _lib.seg_crf_image_u8(ctx, x.ptr, B, self.size[0], self.size[1], np.zeros(3, np.float32), (h, w), images.ptr)
+            return self.ev.update(prob, images, gt_list, want_pred=want_pred)
+        finally:
+            for d in held:
+                d.free()
+
+    def metrics(self):
+        return self.ev.metrics()
+
+    def close(self):
+        if self.ev is not None:
+            self.ev.close()
+            self.ev = None
+        if self.net is not None:
+            self.net.close()
+            self.net = None
