@@ -584,6 +584,59 @@ def test_round4_api_edges(ctx):
     assert c.sum() == 48 and c[0, 0] == 48  # the 2 x 2 block of label 1 lies under the ignored quadrant
 
 
+def _confusion(gt, pred, n_class, ignore_label=255):
+    """confusion[g][p] over the pixels whose ground truth is not ignore_label (numpy)."""
+    keep = gt != ignore_label
+    c = np.zeros((n_class, n_class), np.int64)
+    np.add.at(c, (gt[keep].astype(np.int64), pred[keep].astype(np.int64)), 1)
+    return c
+
+
+def test_label_confusion_error_twice_then_valid_call(ctx):
+    """The early return of the out-of-range read-back leaves the context usable: the same error twice in a row, then the valid
+    call gives the right matrix (1 image, 4 x 4 labels -> 8 x 8)."""
+    lab = (np.arange(16, dtype=np.int32).reshape(1, 4, 4) * 5 // 3) % 3
+    gt = ((np.arange(64).reshape(1, 8, 8) * 7 // 5) % 4).astype(np.uint8)
+    gt[gt == 3] = 255
+    gt_dev = ctx.to_device(gt)
+    conf = ctx.alloc(3 * 3 * 8)
+    bad = lab.copy()
+    bad[0, 0, 0] = 7
+    bad_dev = ctx.to_device(bad)
+    for _ in range(2):
+        with pytest.raises(_lib.WscError) as ei:
+            _lib.label_confusion_nn(ctx, bad_dev, [(4, 4)], [(8, 8)], [0], gt_dev, 3, conf)
+        assert ei.value.status == _lib.WSC_ERR_INVALID and "outside" in str(ei.value)
+    _lib.check(ctx._lib.wsc_memset(ctx.h, conf.ptr, 0, 72))  # (the failed calls counted their in-range pixels)
+    pred_dev = ctx.alloc(64)
+    _lib.label_confusion_nn(ctx, ctx.to_device(lab), [(4, 4)], [(8, 8)], [0], gt_dev, 3, conf, pred_dev=pred_dev)
+    pred = np.repeat(np.repeat(lab[0], 2, axis=0), 2, axis=1)  # cv2 nearest at exactly 2 x: source pixel (Y // 2, X // 2)
+    assert np.array_equal(ctx.to_host(pred_dev, (8, 8), np.uint8), pred)
+    expect = _confusion(gt[0], pred, 3)
+    assert expect.sum() == np.count_nonzero(gt != 255) and np.count_nonzero(expect) >= 6  # (the pattern spreads over the matrix)
+    assert np.array_equal(ctx.to_host(conf, (3, 3), np.int64), expect)
+
+
+def test_cam_eval_confusion_without_keys(ctx):
+    """wsc_cam_eval_confusion on a batch in which no image has a class key (an empty key section in the job table): every
+    pixel is background, so every non-ignored pixel lands in column 0 of its ground-truth row and the predictions are zeros."""
+    sizes = [(3, 5), (4, 4)]
+    n = sum(h * w for h, w in sizes)
+    gt = np.array([0, 1, 255, 1, 0, 0, 255, 1, 1, 0, 1, 1, 0, 255, 0,
+                   1, 0, 0, 255, 1, 1, 255, 0, 0, 1, 0, 1, 1, 0, 255, 1], np.uint8)
+    assert gt.size == n
+    conf = ctx.alloc(2 * 2 * 8)
+    _lib.check(ctx._lib.wsc_memset(ctx.h, conf.ptr, 0, 32))
+    pred_dev = ctx.alloc(n)
+    _lib.check(ctx._lib.wsc_memset(ctx.h, pred_dev.ptr, 0xff, n))
+    highres_dev = ctx.alloc(16)  # no map at all: nothing of it is read
+    _lib.cam_eval_confusion(ctx, highres_dev, sizes, [[], []], [0, 0], 0.25, ctx.to_device(gt), 2, conf, pred_dev=pred_dev)
+    assert not ctx.to_host(pred_dev, (n,), np.uint8).any()
+    expect = _confusion(gt, np.zeros(n, np.uint8), 2)
+    assert expect.tolist() == [[np.count_nonzero(gt == 0), 0], [np.count_nonzero(gt == 1), 0]] and expect[:, 0].min() > 0
+    assert np.array_equal(ctx.to_host(conf, (2, 2), np.int64), expect)
+
+
 @pytest.mark.parametrize("precision", [_lib.PREC_F16X3, _lib.PREC_F16])
 def test_forward_cam_hw_matches_square_call_and_oracle(precision):
     """wsc_net_forward_cam_hw: on a square input it is the square entry point (same bits); on non-square inputs of odd sizes

@@ -110,6 +110,24 @@ int wsc_ctx_upload_small(wsc_ctx *ctx, void *dst_dev, const void *src_host, size
     return WSC_OK;
 }
 
+size_t WscStagedTable::add(const void *src, size_t bytes) {
+    const size_t off = host.size();
+    host.resize(off + (bytes + 15) / 16 * 16); // (the new bytes are zeros)
+    if (src && bytes) memcpy(host.data() + off, src, bytes);
+    return off;
+}
+
+int WscStagedTable::upload() {
+    WSC_TRY(wsc_ctx_cached_alloc(ctx, host.size(), (void **)&dev));
+    return wsc_ctx_upload_small(ctx, dev, host.data(), host.size());
+}
+
+int WscStagedTable::read_back(size_t off, void *dst, size_t bytes) {
+    WSC_HIP(hipMemcpyAsync(dst, dev + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    WSC_HIP(hipStreamSynchronize(ctx->stream));
+    return WSC_OK;
+}
+
 static hipEvent_t prof_event(wsc_ctx *ctx) {
     if (!ctx->prof_pool.empty()) {
         hipEvent_t e = ctx->prof_pool.back();

@@ -16,7 +16,6 @@
 #include "bilerp.h" // src_index, bilerp: shared with cue_seeds.hip
 
 #include <algorithm>
-#include <cstring>
 
 namespace {
 
@@ -482,6 +481,16 @@ __global__ __launch_bounds__(256) void sem_seg_finish_kernel(const float *__rest
 
 extern "C" {
 
+// The tail of the three confusion entry points: the out-of-range counter at `off` comes back (the call's one synchronisation),
+// the table goes, and a non-zero count is WSC_ERR_INVALID with the entry point's text (%u, %d, %d: count, n_class, ignore_label)
+static int check_n_bad(WscStagedTable &tab, size_t off, const char *text, int n_class, int ignore_label) {
+    unsigned n_bad = 0;
+    WSC_TRY(tab.read_back(off, &n_bad, sizeof(unsigned)));
+    tab.release();
+    WSC_CHECK(n_bad == 0, WSC_ERR_INVALID, text, n_bad, n_class, ignore_label);
+    return WSC_OK;
+}
+
 int wsc_cam_eval_confusion(wsc_ctx *ctx, const float *highres_dev, int B, const int32_t *size_hw_host,
                            const int32_t *keys_host, const int32_t *key_off_host, const int64_t *highres_off_host,
                            float bg_thres, const uint8_t *gt_dev, int n_class, int ignore_label, uint8_t *pred_dev,
@@ -509,27 +518,41 @@ int wsc_cam_eval_confusion(wsc_ctx *ctx, const float *highres_dev, int B, const 
     for (int i = 0; i < nkeys; ++i)
         WSC_CHECK(keys_host[i] >= 0 && keys_host[i] + 1 < n_class, WSC_ERR_INVALID,
                   "wsc_cam_eval_confusion: key %d outside [0, %d) (n_class counts the background)", keys_host[i], n_class - 1);
-    const size_t jb = (jobs.size() * sizeof(EvalJob) + 15) / 16 * 16,
-                 kb = ((size_t)std::max(nkeys, 1) * sizeof(int32_t) + 15) / 16 * 16;
-    char *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jb + kb + 16, (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    std::vector<char> stage(jb + kb + 16, 0); // the last 16 bytes: out-of-range counter, zeroed
-    memcpy(stage.data(), jobs.data(), jobs.size() * sizeof(EvalJob));
-    if (nkeys > 0) memcpy(stage.data() + jb, keys_host, (size_t)nkeys * sizeof(int32_t));
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, stage.data(), stage.size()));
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs), ko = tab.add(keys_host, (size_t)nkeys * sizeof(int32_t)), bo = tab.add(nullptr, sizeof(unsigned));
+    WSC_TRY(tab.upload());
     const dim3 grid((unsigned)std::min((max_pix + 255) / 256, 64), (unsigned)B);
     hipLaunchKernelGGL(cam_eval_kernel, grid, dim3(256), (size_t)n_class * n_class * sizeof(unsigned), ctx->stream,
-                       highres_dev, (const EvalJob *)d, (const int32_t *)(d + jb), bg_thres, gt_dev, n_class,
-                       ignore_label, pred_dev, (unsigned long long *)confusion_dev, (unsigned *)(d + jb + kb));
+                       highres_dev, tab.at<const EvalJob>(jo), tab.at<const int32_t>(ko), bg_thres, gt_dev, n_class,
+                       ignore_label, pred_dev, (unsigned long long *)confusion_dev, tab.at<unsigned>(bo));
     WSC_HIP(hipGetLastError());
-    unsigned n_bad = 0;
-    WSC_HIP(hipMemcpyAsync(&n_bad, d + jb + kb, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    WSC_HIP(hipStreamSynchronize(ctx->stream));
-    d_guard.free_now();
-    WSC_CHECK(n_bad == 0, WSC_ERR_INVALID,
-              "wsc_cam_eval_confusion: %u pixels carry a ground-truth label outside [0, %d) (and != ignore_label %d)", n_bad,
-              n_class, ignore_label);
+    return check_n_bad(tab, bo, "wsc_cam_eval_confusion: %u pixels carry a ground-truth label outside [0, %d) (and != ignore_label %d)",
+                       n_class, ignore_label);
+}
+
+// The job table of the two nearest-neighbour confusion entry points.  key_off_host == nullptr: the labels case (K = 0, key_base = 0).
+static int eval_nn_jobs(const char *who, int B, const int32_t *src_hw_host, const int32_t *out_hw_host, const int32_t *key_off_host,
+                        const int64_t *maps_off_host, std::vector<EvalNNJob> &jobs, long long *max_pix) {
+    jobs.resize(B);
+    long long pix = 0;
+    *max_pix = 0;
+    for (int b = 0; b < B; ++b) {
+        EvalNNJob &j = jobs[b];
+        j.h = src_hw_host[2 * b]; j.w = src_hw_host[2 * b + 1];
+        j.out_h = out_hw_host[2 * b]; j.out_w = out_hw_host[2 * b + 1];
+        WSC_CHECK(j.h > 0 && j.w > 0 && j.out_h > 0 && j.out_w > 0, WSC_ERR_INVALID, "image %d: %dx%d -> %dx%d", b, j.h, j.w,
+                  j.out_h, j.out_w);
+        j.K = key_off_host ? key_off_host[b + 1] - key_off_host[b] : 0;
+        WSC_CHECK(!key_off_host || j.K >= 1, WSC_ERR_INVALID, "%s: image %d has no class map (np.argmax of an empty stack)", who, b);
+        j.key_base = key_off_host ? key_off_host[b] : 0;
+        j.maps_off = maps_off_host[b];
+        j.pix_off = pix;
+        // cv2.resize: inv_scale = 1. / (dsize / ssize), both in double
+        j.inv_y = 1.0 / ((double)j.out_h / (double)j.h);
+        j.inv_x = 1.0 / ((double)j.out_w / (double)j.w);
+        pix += (long long)j.out_h * j.out_w;
+        *max_pix = std::max(*max_pix, (long long)j.out_h * j.out_w);
+    }
     return WSC_OK;
 }
 
@@ -541,50 +564,23 @@ int wsc_cam_eval_confusion_nn(wsc_ctx *ctx, const float *maps_dev, int B, const 
               WSC_ERR_INVALID, "wsc_cam_eval_confusion_nn: null argument");
     WSC_CHECK(B > 0 && n_class > 0 && n_class <= 64, WSC_ERR_INVALID, "wsc_cam_eval_confusion_nn: B=%d n_class=%d", B, n_class);
     WSC_HIP(hipSetDevice(ctx->device));
-    std::vector<EvalNNJob> jobs(B);
-    long long pix = 0, max_pix = 0;
-    for (int b = 0; b < B; ++b) {
-        EvalNNJob &j = jobs[b];
-        j.h = src_hw_host[2 * b]; j.w = src_hw_host[2 * b + 1];
-        j.out_h = out_hw_host[2 * b]; j.out_w = out_hw_host[2 * b + 1];
-        WSC_CHECK(j.h > 0 && j.w > 0 && j.out_h > 0 && j.out_w > 0, WSC_ERR_INVALID, "image %d: %dx%d -> %dx%d", b, j.h, j.w,
-                  j.out_h, j.out_w);
-        j.K = key_off_host[b + 1] - key_off_host[b];
-        WSC_CHECK(j.K >= 1, WSC_ERR_INVALID, "wsc_cam_eval_confusion_nn: image %d has no class map (np.argmax of an empty stack)", b);
-        j.key_base = key_off_host[b];
-        j.maps_off = maps_off_host[b];
-        j.pix_off = pix;
-        // cv2.resize: inv_scale = 1. / (dsize / ssize), both in double
-        j.inv_y = 1.0 / ((double)j.out_h / (double)j.h);
-        j.inv_x = 1.0 / ((double)j.out_w / (double)j.w);
-        pix += (long long)j.out_h * j.out_w;
-        max_pix = std::max(max_pix, (long long)j.out_h * j.out_w);
-    }
+    std::vector<EvalNNJob> jobs;
+    long long max_pix;
+    WSC_TRY(eval_nn_jobs("wsc_cam_eval_confusion_nn", B, src_hw_host, out_hw_host, key_off_host, maps_off_host, jobs, &max_pix));
     const int nkeys = key_off_host[B];
     for (int i = 0; i < nkeys; ++i)
         WSC_CHECK(keys_host[i] >= 0 && keys_host[i] < n_class, WSC_ERR_INVALID,
                   "wsc_cam_eval_confusion_nn: key %d outside [0, %d)", keys_host[i], n_class);
-    const size_t jb = (jobs.size() * sizeof(EvalNNJob) + 15) / 16 * 16, kb = ((size_t)nkeys * sizeof(int32_t) + 15) / 16 * 16;
-    char *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jb + kb + 16, (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    std::vector<char> stage(jb + kb + 16, 0); // the last 16 bytes: out-of-range counter, zeroed
-    memcpy(stage.data(), jobs.data(), jobs.size() * sizeof(EvalNNJob));
-    memcpy(stage.data() + jb, keys_host, (size_t)nkeys * sizeof(int32_t));
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, stage.data(), stage.size()));
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs), ko = tab.add(keys_host, (size_t)nkeys * sizeof(int32_t)), bo = tab.add(nullptr, sizeof(unsigned));
+    WSC_TRY(tab.upload());
     const dim3 grid((unsigned)std::min<long long>((max_pix + 255) / 256, 1024), (unsigned)B);
     hipLaunchKernelGGL(cam_eval_nn_kernel<false>, grid, dim3(256), (size_t)n_class * n_class * sizeof(unsigned), ctx->stream, maps_dev,
-                       (const EvalNNJob *)d, (const int32_t *)(d + jb), gt_dev, n_class, ignore_label, pred_dev,
-                       (unsigned long long *)confusion_dev, (unsigned *)(d + jb + kb));
+                       tab.at<const EvalNNJob>(jo), tab.at<const int32_t>(ko), gt_dev, n_class, ignore_label, pred_dev,
+                       (unsigned long long *)confusion_dev, tab.at<unsigned>(bo));
     WSC_HIP(hipGetLastError());
-    unsigned n_bad = 0;
-    WSC_HIP(hipMemcpyAsync(&n_bad, d + jb + kb, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    WSC_HIP(hipStreamSynchronize(ctx->stream));
-    d_guard.free_now();
-    WSC_CHECK(n_bad == 0, WSC_ERR_INVALID,
-              "wsc_cam_eval_confusion_nn: %u pixels carry a ground-truth label outside [0, %d) (and != ignore_label %d)", n_bad,
-              n_class, ignore_label);
-    return WSC_OK;
+    return check_n_bad(tab, bo, "wsc_cam_eval_confusion_nn: %u pixels carry a ground-truth label outside [0, %d) (and != ignore_label %d)",
+                       n_class, ignore_label);
 }
 
 int wsc_label_confusion_nn(wsc_ctx *ctx, const int32_t *labels_dev, int B, const int32_t *src_hw_host, const int32_t *out_hw_host,
@@ -594,43 +590,20 @@ int wsc_label_confusion_nn(wsc_ctx *ctx, const int32_t *labels_dev, int B, const
               "wsc_label_confusion_nn: null argument");
     WSC_CHECK(B > 0 && n_class > 0 && n_class <= 64, WSC_ERR_INVALID, "wsc_label_confusion_nn: B=%d n_class=%d", B, n_class);
     WSC_HIP(hipSetDevice(ctx->device));
-    std::vector<EvalNNJob> jobs(B);
-    long long pix = 0, max_pix = 0;
-    for (int b = 0; b < B; ++b) {
-        EvalNNJob &j = jobs[b];
-        j.h = src_hw_host[2 * b]; j.w = src_hw_host[2 * b + 1];
-        j.out_h = out_hw_host[2 * b]; j.out_w = out_hw_host[2 * b + 1];
-        WSC_CHECK(j.h > 0 && j.w > 0 && j.out_h > 0 && j.out_w > 0, WSC_ERR_INVALID, "image %d: %dx%d -> %dx%d", b, j.h, j.w,
-                  j.out_h, j.out_w);
-        j.K = 0;
-        j.key_base = 0;
-        j.maps_off = labels_off_host[b];
-        j.pix_off = pix;
-        j.inv_y = 1.0 / ((double)j.out_h / (double)j.h); // cv2.resize: inv_scale = 1. / (dsize / ssize), both in double
-        j.inv_x = 1.0 / ((double)j.out_w / (double)j.w);
-        pix += (long long)j.out_h * j.out_w;
-        max_pix = std::max(max_pix, (long long)j.out_h * j.out_w);
-    }
-    const size_t jb = (jobs.size() * sizeof(EvalNNJob) + 15) / 16 * 16;
-    char *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jb + 16, (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    std::vector<char> stage(jb + 16, 0); // the last 16 bytes: out-of-range counter, zeroed
-    memcpy(stage.data(), jobs.data(), jobs.size() * sizeof(EvalNNJob));
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, stage.data(), stage.size()));
+    std::vector<EvalNNJob> jobs;
+    long long max_pix;
+    WSC_TRY(eval_nn_jobs("wsc_label_confusion_nn", B, src_hw_host, out_hw_host, nullptr, labels_off_host, jobs, &max_pix));
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs), bo = tab.add(nullptr, sizeof(unsigned));
+    WSC_TRY(tab.upload());
     const dim3 grid((unsigned)std::min<long long>((max_pix + 255) / 256, 1024), (unsigned)B);
     hipLaunchKernelGGL(cam_eval_nn_kernel<true>, grid, dim3(256), (size_t)n_class * n_class * sizeof(unsigned), ctx->stream,
-                       reinterpret_cast<const float *>(labels_dev), (const EvalNNJob *)d, (const int32_t *)nullptr, gt_dev, n_class,
-                       ignore_label, pred_dev, (unsigned long long *)confusion_dev, (unsigned *)(d + jb));
+                       reinterpret_cast<const float *>(labels_dev), tab.at<const EvalNNJob>(jo), (const int32_t *)nullptr, gt_dev, n_class,
+                       ignore_label, pred_dev, (unsigned long long *)confusion_dev, tab.at<unsigned>(bo));
     WSC_HIP(hipGetLastError());
-    unsigned n_bad = 0;
-    WSC_HIP(hipMemcpyAsync(&n_bad, d + jb, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    WSC_HIP(hipStreamSynchronize(ctx->stream));
-    d_guard.free_now();
-    WSC_CHECK(n_bad == 0, WSC_ERR_INVALID,
-              "wsc_label_confusion_nn: %u pixels carry a label or a ground-truth label outside [0, %d) (and != ignore_label %d)", n_bad,
-              n_class, ignore_label);
-    return WSC_OK;
+    return check_n_bad(tab, bo,
+                       "wsc_label_confusion_nn: %u pixels carry a label or a ground-truth label outside [0, %d) (and != ignore_label %d)",
+                       n_class, ignore_label);
 }
 
 int wsc_sem_seg_finish(wsc_ctx *ctx, const float *rw_dev, int B, const int64_t *rw_off_host, const int32_t *khw_host,
@@ -662,23 +635,18 @@ int wsc_sem_seg_finish(wsc_ctx *ctx, const float *rw_dev, int B, const int64_t *
     const int nkeys = key_off_host[B];
     for (int i = 0; i < nkeys; ++i)
         WSC_CHECK(keys_host[i] >= 0 && keys_host[i] <= 255, WSC_ERR_INVALID, "wsc_sem_seg_finish: key %d does not fit a uint8 label", keys_host[i]);
-    const size_t jb = (jobs.size() * sizeof(SemSegJob) + 15) / 16 * 16, kb = ((size_t)nkeys * sizeof(int32_t) + 15) / 16 * 16,
-                 mb = ((size_t)B * sizeof(unsigned) + 15) / 16 * 16;
-    char *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jb + kb + mb, (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    std::vector<char> stage(jb + kb + mb, 0); // the maxima start at code 0 = "below every real number"
-    memcpy(stage.data(), jobs.data(), jobs.size() * sizeof(SemSegJob));
-    memcpy(stage.data() + jb, keys_host, (size_t)nkeys * sizeof(int32_t));
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, stage.data(), stage.size()));
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs), ko = tab.add(keys_host, (size_t)nkeys * sizeof(int32_t)),
+                 mo = tab.add(nullptr, (size_t)B * sizeof(unsigned)); // the maxima start at code 0 = "below every real number"
+    WSC_TRY(tab.upload());
     const dim3 grid((unsigned)std::min((max_pix + 255) / 256, 256), (unsigned)B);
     WscKernelTimer timer(ctx, WSC_K_CAM_TAIL, (double)pix * 4);
-    hipLaunchKernelGGL(sem_seg_finish_kernel<false>, grid, dim3(256), 0, ctx->stream, rw_dev, (const SemSegJob *)d,
-                       (const int32_t *)(d + jb), has_bg, bg_thres, (unsigned int *)(d + jb + kb), label_dev);
-    hipLaunchKernelGGL(sem_seg_finish_kernel<true>, grid, dim3(256), 0, ctx->stream, rw_dev, (const SemSegJob *)d,
-                       (const int32_t *)(d + jb), has_bg, bg_thres, (unsigned int *)(d + jb + kb), label_dev);
+    hipLaunchKernelGGL(sem_seg_finish_kernel<false>, grid, dim3(256), 0, ctx->stream, rw_dev, tab.at<const SemSegJob>(jo),
+                       tab.at<const int32_t>(ko), has_bg, bg_thres, tab.at<unsigned int>(mo), label_dev);
+    hipLaunchKernelGGL(sem_seg_finish_kernel<true>, grid, dim3(256), 0, ctx->stream, rw_dev, tab.at<const SemSegJob>(jo),
+                       tab.at<const int32_t>(ko), has_bg, bg_thres, tab.at<unsigned int>(mo), label_dev);
     WSC_HIP(hipGetLastError());
-    d_guard.free_now(); // stream-ordered reuse
+    tab.release(); // stream-ordered reuse
     return WSC_OK;
 }
 
@@ -810,13 +778,12 @@ int wsc_cam_postprocess(wsc_ctx *ctx, const float *cam_dev, int B, int C, int h,
     if (jobs.empty()) return WSC_OK;
     WSC_CHECK(strided_dev && highres_dev, WSC_ERR_INVALID, "wsc_cam_postprocess: null output");
     WSC_CHECK(jobs.size() <= 65535, WSC_ERR_INVALID, "too many (image, class) jobs in one call: %zu", jobs.size());
-    // descriptor + maxima live in a small block of the ctx's stream-ordered cache
-    const size_t jb = jobs.size() * sizeof(TailJob), mb = jobs.size() * 2 * sizeof(unsigned int);
-    char *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jb + mb, (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, jobs.data(), jb)); // through pinned staging: no host sync
-    WSC_HIP(hipMemsetAsync(d + jb, 0, mb, ctx->stream));
+    // descriptors + maxima (code 0 = no value) live in a small block of the ctx's stream-ordered cache
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs), mo = tab.add(nullptr, jobs.size() * 2 * sizeof(unsigned int));
+    WSC_TRY(tab.upload()); // through pinned staging: no host sync
+    const TailJob *d_jobs = tab.at<const TailJob>(jo);
+    unsigned int *d_mx = tab.at<unsigned int>(mo);
     const dim3 grid((max_pix + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK, (unsigned)jobs.size());
     const size_t lds = (size_t)h * w * sizeof(float);
     double out_bytes = 0;
@@ -830,14 +797,14 @@ int wsc_cam_postprocess(wsc_ctx *ctx, const float *cam_dev, int B, int C, int h,
                            (size_t)((max_rows + bands - 1) / bands) * sizeof(float4);
     if (lds_max <= 64 * 1024)
         hipLaunchKernelGGL(cam_tail_max_kernel, dim3((unsigned)jobs.size(), (unsigned)bands), dim3(512), lds_max, ctx->stream,
-                           cam_dev, (const TailJob *)d, h, w, (unsigned int *)(d + jb));
+                           cam_dev, d_jobs, h, w, d_mx);
     else
-        hipLaunchKernelGGL(cam_tail_kernel<false>, grid, dim3(256), lds, ctx->stream, cam_dev, (const TailJob *)d, h, w,
-                           (unsigned int *)(d + jb), strided_dev, highres_dev);
-    hipLaunchKernelGGL(cam_tail_kernel<true>, grid, dim3(256), lds, ctx->stream, cam_dev, (const TailJob *)d, h, w,
-                       (unsigned int *)(d + jb), strided_dev, highres_dev);
+        hipLaunchKernelGGL(cam_tail_kernel<false>, grid, dim3(256), lds, ctx->stream, cam_dev, d_jobs, h, w, d_mx, strided_dev,
+                           highres_dev);
+    hipLaunchKernelGGL(cam_tail_kernel<true>, grid, dim3(256), lds, ctx->stream, cam_dev, d_jobs, h, w, d_mx, strided_dev,
+                       highres_dev);
     WSC_HIP(hipGetLastError());
-    d_guard.free_now(); // stream-ordered reuse
+    tab.release(); // stream-ordered reuse
     return WSC_OK;
 }
 

@@ -210,6 +210,29 @@ struct WscCachedGuard {
 };
 // copies `bytes` of host data to dst_dev through the ctx's pinned staging buffer, asynchronously
 int wsc_ctx_upload_small(wsc_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);
+// A small host-built table on the device for ONE call (the per-image jobs of a ragged batch, their keys, zeroed counters or
+// maxima): add() the sections, upload() them as one cached block through one pinned-ring copy, hand at<T>(offset) to the
+// launches, release() after the last launch that reads the table (stream-ordered reuse, as WscCachedGuard::free_now()).  An
+// early `return` of WSC_TRY / WSC_HIP / WSC_CHECK gives the block back too.  Only read_back() synchronises.
+class WscStagedTable {
+  public:
+    explicit WscStagedTable(wsc_ctx *c) : ctx(c) {}
+    WscStagedTable(const WscStagedTable &) = delete;
+    WscStagedTable &operator=(const WscStagedTable &) = delete;
+    ~WscStagedTable() { release(); }
+    // appends a 16-byte aligned section, returns its byte offset; src == nullptr: zeros; an empty section is legal and free
+    size_t add(const void *src, size_t bytes);
+    template <class T> size_t add(const std::vector<T> &v) { return add(v.data(), v.size() * sizeof(T)); }
+    int upload();
+    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(dev + off); }
+    // device -> host copy of part of the table, then a stream synchronisation (the out-of-range counters)
+    int read_back(size_t off, void *dst, size_t bytes);
+    void release() { wsc_ctx_cached_free(ctx, dev); dev = nullptr; }
+  private:
+    wsc_ctx *ctx;
+    std::vector<char> host;
+    char *dev = nullptr;
+};
 // Raises the dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) of kernel `fn` to `bytes`, once per (function,
 // ctx device), under a lock: the lane threads of the drivers reach the launch sites at the same time.  WSC_ERR_HIP with the
 // error text when the runtime refuses; a failure is not recorded, so the next call tries again.
@@ -415,6 +438,9 @@ int launch_pool_same(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int avg, i
 int launch_nhwc3_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y);
 // prob[m][c] = fc8-softmax of (in[0] + ... + in[n_in - 1])[m][c]; fc8 (optional) receives the summed logits
 int launch_fc8_softmax(wsc_ctx *ctx, const float *const *in, int n_in, long long M, int C, float min_prob, float *fc8, float *prob);
+
+// ---- seg_eval.hip / seg_chain.hip: the SEC / DSRG prediction loop around the dense CRF ------------------------------------
+constexpr int SEG_MAX_C = 32; // the class limit of wsc_crf_v_inference, whose unaries / marginals these files handle
 
 // ---- irn_kernels.hip ---------------------------------------------------------------------
 int launch_group_norm_stats(wsc_ctx *ctx, const float *x, int N, int H, int W, int C, int G, float eps, void *partial,

@@ -216,18 +216,17 @@ int wsc_cue_maps(wsc_ctx *ctx, const float *cams_nhwc_dev, int B, int h, int w, 
         WSC_CHECK(chan_host[c] >= 0 && chan_host[c] < C_all, WSC_ERR_INVALID, "wsc_cue_maps: chan[%d]=%d is no channel of C_all=%d", c,
                   (int)chan_host[c], C_all);
     WSC_HIP(hipSetDevice(ctx->device));
-    int *chan = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, sizeof(int) * (size_t)C, (void **)&chan));
-    WscCachedGuard chan_guard(ctx, chan);
-    WSC_TRY(wsc_ctx_upload_small(ctx, chan, chan_host, sizeof(int) * (size_t)C));
+    WscStagedTable tab(ctx);
+    const size_t co = tab.add(chan_host, sizeof(int) * (size_t)C);
+    WSC_TRY(tab.upload());
     const long long total = (long long)B * C * S * S;
     long long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * 4 + (double)B * C * h * w * 4);
-    hipLaunchKernelGGL(cue_maps_kernel, dim3((unsigned)g), dim3(256), 0, ctx->stream, cams_nhwc_dev, h, w, C_all, (const int *)chan, C,
+    hipLaunchKernelGGL(cue_maps_kernel, dim3((unsigned)g), dim3(256), 0, ctx->stream, cams_nhwc_dev, h, w, C_all, tab.at<const int>(co), C,
                        gate_dev, S, total, out_dev);
     WSC_HIP(hipGetLastError());
-    chan_guard.free_now(); // stream-ordered reuse
+    tab.release(); // stream-ordered reuse
     return WSC_OK;
 }
 

@@ -10,6 +10,7 @@
 // the rest after: 1 / 1 on an odd size, 0 / 1 on an even size at stride 2 (which one symmetric `pad` cannot express).  Max
 // ignores the padding (-inf, not 0); the average divides by the number of IN-IMAGE taps (4 at a corner, 6 on an edge).
 #include "common.h"
+#include "tf_resize.h"
 
 #include <cmath>
 
@@ -189,9 +190,8 @@ __global__ __launch_bounds__(256) void fc8_softmax_kernel(SoftmaxIn in, long lon
     }
 }
 
-// tf.image.resize_bilinear(align_corners=False) of TensorFlow 1.x on NHWC float32: scale = in / out (float32), src = dst * scale,
-// i0 = floor(src), i1 = min(i0 + 1, in - 1), t = src - i0; top = tl + (tr - tl) tx, bottom likewise, out = top + (bottom - top) ty.
-// (compiled without FMA contraction: the lerps are the products and sums written here)
+// tf.image.resize_bilinear(align_corners=False) of TensorFlow 1.x on NHWC float32: tf_resize.h's rule and its lerp (this file is
+// compiled without FMA contraction, as the header demands)
 __global__ __launch_bounds__(256) void resize_bilinear_tf_kernel(const float *__restrict__ src, int B, int h, int w, int C,
                                                                  float *__restrict__ dst, int H, int W, float sy, float sx) {
     const long long total = (long long)B * H * W * C;
@@ -202,16 +202,15 @@ __global__ __launch_bounds__(256) void resize_bilinear_tf_kernel(const float *__
         pix /= W;
         const int Y = (int)(pix % H);
         const long long b = pix / H;
+        // tf_tap of both axes, written out interleaved (two calls: the same values, another instruction schedule of this kernel)
         const float fy = (float)Y * sy, fx = (float)X * sx;
-        const int y0 = min((int)floorf(fy), h - 1), x0 = min((int)floorf(fx), w - 1); // (floor(src) <= in - 1 but for rounding of the product)
+        const int y0 = min((int)floorf(fy), h - 1), x0 = min((int)floorf(fx), w - 1);
         const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
         const float ty = fy - (float)y0, tx = fx - (float)x0;
         const float *s = src + b * h * w * C + c;
         const float tl = s[((long long)y0 * w + x0) * C], tr = s[((long long)y0 * w + x1) * C];
         const float bl = s[((long long)y1 * w + x0) * C], br = s[((long long)y1 * w + x1) * C];
-        const float top = tl + (tr - tl) * tx;
-        const float bottom = bl + (br - bl) * tx;
-        dst[i] = top + (bottom - top) * ty;
+        dst[i] = tf_lerp(tl, tr, bl, br, tx, ty);
     }
 }
 

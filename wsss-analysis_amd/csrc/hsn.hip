@@ -501,16 +501,15 @@ int wsc_hsn_gather_unary(wsc_ctx *ctx, const float *maps_dev, const int64_t *cha
     WSC_CHECK(ctx && maps_dev && chan_off_host && unary_dev, WSC_ERR_INVALID, "wsc_hsn_gather_unary: null argument");
     WSC_CHECK(n_chan > 0 && N > 0, WSC_ERR_INVALID, "wsc_hsn_gather_unary: n_chan=%d N=%d", n_chan, N);
     WSC_HIP(hipSetDevice(ctx->device));
-    long long *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, sizeof(long long) * (size_t)n_chan, (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, chan_off_host, sizeof(long long) * (size_t)n_chan));
+    WscStagedTable tab(ctx);
+    const size_t co = tab.add(chan_off_host, sizeof(long long) * (size_t)n_chan);
+    WSC_TRY(tab.upload());
     const long long total = (long long)n_chan * N;
     WscKernelTimer timer(ctx, WSC_K_CAM_TAIL, (double)total * 8);
-    hipLaunchKernelGGL(hsn_gather_unary_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, maps_dev, (const long long *)d, N,
-                       total, unary_dev);
+    hipLaunchKernelGGL(hsn_gather_unary_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, maps_dev, tab.at<const long long>(co),
+                       N, total, unary_dev);
     WSC_HIP(hipGetLastError());
-    d_guard.free_now();
+    tab.release();
     return WSC_OK;
 }
 

@@ -14,7 +14,6 @@
 // to wsscam.voc12.dataloader.resize_bilinear_f64 + TorchvisionNormalize.
 #include "common.h"
 
-#include <cstring>
 #include <vector>
 
 namespace {
@@ -129,6 +128,19 @@ __global__ __launch_bounds__(256) void resize_u8_cv2_kernel(const uint8_t *__res
 
 } // namespace
 
+// The checks on the image sizes and the job table both entry points fill
+static int in_jobs(int B, const int32_t *size_hw_host, const int64_t *offset_host, std::vector<InJob> &jobs) {
+    jobs.resize(B);
+    for (int b = 0; b < B; ++b) {
+        WSC_CHECK(size_hw_host[2 * b] > 0 && size_hw_host[2 * b + 1] > 0, WSC_ERR_INVALID, "image %d has size %dx%d", b,
+                  size_hw_host[2 * b], size_hw_host[2 * b + 1]);
+        jobs[b].src_off = offset_host[b];
+        jobs[b].H0 = size_hw_host[2 * b];
+        jobs[b].W0 = size_hw_host[2 * b + 1];
+    }
+    return WSC_OK;
+}
+
 extern "C" {
 
 int wsc_msf_input_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32_t *size_hw_host, const int64_t *offset_host,
@@ -137,29 +149,18 @@ int wsc_msf_input_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32
               "wsc_msf_input_u8: null argument");
     WSC_CHECK(B > 0 && B <= 65535 && S > 0, WSC_ERR_INVALID, "wsc_msf_input_u8: B=%d S=%d", B, S);
     WSC_HIP(hipSetDevice(ctx->device));
-    std::vector<InJob> jobs(B);
-    for (int b = 0; b < B; ++b) {
-        WSC_CHECK(size_hw_host[2 * b] > 0 && size_hw_host[2 * b + 1] > 0, WSC_ERR_INVALID, "image %d has size %dx%d", b,
-                  size_hw_host[2 * b], size_hw_host[2 * b + 1]);
-        jobs[b].src_off = offset_host[b];
-        jobs[b].H0 = size_hw_host[2 * b];
-        jobs[b].W0 = size_hw_host[2 * b + 1];
-    }
-    InJob *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, sizeof(InJob) * (size_t)B, (void **)&d));
-    int st = wsc_ctx_upload_small(ctx, d, jobs.data(), sizeof(InJob) * (size_t)B);
-    if (st == WSC_OK) {
-        const dim3 grid((unsigned)std::min((S * S + 255) / 256, 64), (unsigned)B);
-        WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)B * S * S * 3 * (pair ? 8 : 4));
-        hipLaunchKernelGGL(msf_input_kernel, grid, dim3(256), 0, ctx->stream, images_dev, (const InJob *)d, S, mean3_host[0],
-                           mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2], pre_div255, pair, x_dev);
-        if (hipGetLastError() != hipSuccess) {
-            wsc_set_error("wsc_msf_input_u8: launch failed");
-            st = WSC_ERR_HIP;
-        }
-    }
-    wsc_ctx_cached_free(ctx, d);
-    return st;
+    std::vector<InJob> jobs;
+    WSC_TRY(in_jobs(B, size_hw_host, offset_host, jobs));
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs);
+    WSC_TRY(tab.upload());
+    const dim3 grid((unsigned)std::min((S * S + 255) / 256, 64), (unsigned)B);
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)B * S * S * 3 * (pair ? 8 : 4));
+    hipLaunchKernelGGL(msf_input_kernel, grid, dim3(256), 0, ctx->stream, images_dev, tab.at<const InJob>(jo), S, mean3_host[0],
+                       mean3_host[1], mean3_host[2], std3_host[0], std3_host[1], std3_host[2], pre_div255, pair, x_dev);
+    WSC_HIP(hipGetLastError());
+    tab.release(); // stream-ordered reuse
+    return WSC_OK;
 }
 
 int wsc_resize_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32_t *size_hw_host, const int64_t *offset_host, int OH,
@@ -167,28 +168,17 @@ int wsc_resize_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32_t 
     WSC_CHECK(ctx && images_dev && size_hw_host && offset_host && out_dev, WSC_ERR_INVALID, "wsc_resize_u8: null argument");
     WSC_CHECK(B > 0 && B <= 65535 && OH > 0 && OW > 0, WSC_ERR_INVALID, "wsc_resize_u8: B=%d out=%dx%d", B, OH, OW);
     WSC_HIP(hipSetDevice(ctx->device));
-    std::vector<InJob> jobs(B);
-    for (int b = 0; b < B; ++b) {
-        WSC_CHECK(size_hw_host[2 * b] > 0 && size_hw_host[2 * b + 1] > 0, WSC_ERR_INVALID, "image %d has size %dx%d", b,
-                  size_hw_host[2 * b], size_hw_host[2 * b + 1]);
-        jobs[b].src_off = offset_host[b];
-        jobs[b].H0 = size_hw_host[2 * b];
-        jobs[b].W0 = size_hw_host[2 * b + 1];
-    }
-    InJob *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, sizeof(InJob) * (size_t)B, (void **)&d));
-    int st = wsc_ctx_upload_small(ctx, d, jobs.data(), sizeof(InJob) * (size_t)B);
-    if (st == WSC_OK) {
-        const dim3 grid((unsigned)std::min((OH * OW + 255) / 256, 64), (unsigned)B);
-        WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)B * OH * OW * 3 * 5);
-        hipLaunchKernelGGL(resize_u8_cv2_kernel, grid, dim3(256), 0, ctx->stream, images_dev, (const InJob *)d, OH, OW, out_dev);
-        if (hipGetLastError() != hipSuccess) {
-            wsc_set_error("wsc_resize_u8: launch failed");
-            st = WSC_ERR_HIP;
-        }
-    }
-    wsc_ctx_cached_free(ctx, d);
-    return st;
+    std::vector<InJob> jobs;
+    WSC_TRY(in_jobs(B, size_hw_host, offset_host, jobs));
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs);
+    WSC_TRY(tab.upload());
+    const dim3 grid((unsigned)std::min((OH * OW + 255) / 256, 64), (unsigned)B);
+    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)B * OH * OW * 3 * 5);
+    hipLaunchKernelGGL(resize_u8_cv2_kernel, grid, dim3(256), 0, ctx->stream, images_dev, tab.at<const InJob>(jo), OH, OW, out_dev);
+    WSC_HIP(hipGetLastError());
+    tab.release(); // stream-ordered reuse
+    return WSC_OK;
 }
 
 } // extern "C"

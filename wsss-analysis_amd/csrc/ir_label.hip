@@ -82,15 +82,14 @@ int wsc_ir_label_combine(wsc_ctx *ctx, const int32_t *fg_pred_dev, const int32_t
     WSC_CHECK(ctx && fg_pred_dev && keys_host && conf_dev, WSC_ERR_INVALID, "wsc_ir_label_combine: null argument");
     WSC_CHECK(B > 0 && M > 0 && N > 0, WSC_ERR_INVALID, "wsc_ir_label_combine: B=%d M=%d N=%d", B, M, N);
     WSC_HIP(hipSetDevice(ctx->device));
-    int32_t *k = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, sizeof(int32_t) * (size_t)B * M, (void **)&k));
-    WscCachedGuard k_guard(ctx, k);
-    WSC_TRY(wsc_ctx_upload_small(ctx, k, keys_host, sizeof(int32_t) * (size_t)B * M));
+    WscStagedTable tab(ctx);
+    const size_t ko = tab.add(keys_host, sizeof(int32_t) * (size_t)B * M);
+    WSC_TRY(tab.upload());
     const long long total = (long long)B * N;
     hipLaunchKernelGGL(ir_combine_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, fg_pred_dev, bg_pred_dev,
-                       (const int32_t *)k, M, N, total, bg_pred_dev != nullptr ? 1 : 0, conf_dev);
+                       tab.at<const int32_t>(ko), M, N, total, bg_pred_dev != nullptr ? 1 : 0, conf_dev);
     WSC_HIP(hipGetLastError());
-    k_guard.free_now();
+    tab.release();
     return WSC_OK;
 }
 

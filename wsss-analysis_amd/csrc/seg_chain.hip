@@ -9,11 +9,10 @@
 //   seg_planes_from_nhwc_kernel  NHWC maps -> class-major planes (what wsc_seg_resize_argmax reads): the is_eval=False pass
 // One thread per output pixel, grid-stride; every kernel moves each byte once and has no reuse: no LDS.
 //
-// The TF sampler is resize_bilinear_tf_kernel's (deeplab.hip), operation for operation: scale = in / out (float32),
-// src = dst * scale, i0 = floor(src), i1 = min(i0 + 1, in - 1), t = src - i0; top = tl + (tr - tl) tx, bottom likewise,
-// out = top + (bottom - top) ty.  This file is compiled without FMA contraction: the lerps are the products and sums written
-// here, so a value has the bits wsc_resize_bilinear_tf gives for it.
+// The TF sampler is tf_resize.h's, the one wsc_resize_bilinear_tf runs: a value has the bits that entry point gives for it (this
+// file is compiled without FMA contraction, as the header demands).
 #include "common.h"
+#include "tf_resize.h"
 
 #include <limits.h>
 
@@ -22,22 +21,6 @@
 #include <vector>
 
 namespace {
-
-constexpr int SEG_MAX_C = 32; // the class limit of the dense CRF whose marginals these are
-
-// taps and weights of one output coordinate (resize_bilinear_tf_kernel's lines)
-__device__ __forceinline__ void tf_tap(int dst, float scale, int in, int &i0, int &i1, float &t) {
-    const float f = (float)dst * scale;
-    i0 = min((int)floorf(f), in - 1); // (floor(src) <= in - 1 but for rounding of the product)
-    i1 = min(i0 + 1, in - 1);
-    t = f - (float)i0;
-}
-
-__device__ __forceinline__ float tf_lerp(float tl, float tr, float bl, float br, float tx, float ty) {
-    const float top = tl + (tr - tl) * tx;
-    const float bottom = bl + (br - bl) * tx;
-    return top + (bottom - top) * ty;
-}
 
 struct PreJob {
     long long src_off; // byte offset of the image's [h][w][3] block
@@ -161,16 +144,15 @@ int wsc_seg_preprocess_u8(wsc_ctx *ctx, const uint8_t *img_dev, int n, const int
     }
     Mean3 mean = {{mean_bgr_host[0], mean_bgr_host[1], mean_bgr_host[2]}};
     WSC_HIP(hipSetDevice(ctx->device));
-    PreJob *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jobs.size() * sizeof(PreJob), (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, jobs.data(), jobs.size() * sizeof(PreJob)));
+    WscStagedTable tab(ctx);
+    const size_t jo = tab.add(jobs);
+    WSC_TRY(tab.upload());
     const long long npix = (long long)H * W;
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, src_bytes + 12.0 * n * (double)npix);
-    hipLaunchKernelGGL(seg_preprocess_u8_kernel, pixel_grid(npix, n), dim3(256), 0, ctx->stream, img_dev, (const PreJob *)d, mean, H, W,
-                       x_dev);
+    hipLaunchKernelGGL(seg_preprocess_u8_kernel, pixel_grid(npix, n), dim3(256), 0, ctx->stream, img_dev, tab.at<const PreJob>(jo), mean, H,
+                       W, x_dev);
     WSC_HIP(hipGetLastError());
-    d_guard.free_now(); // stream-ordered reuse
+    tab.release(); // stream-ordered reuse
     return WSC_OK;
 }
 

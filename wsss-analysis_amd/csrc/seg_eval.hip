@@ -23,8 +23,6 @@
 
 namespace {
 
-constexpr int SEG_MAX_C = 32; // the class limit of wsc_crf_v_inference, whose unaries / marginals these are
-
 struct SegJob {
     long long src_off; // float offset of the image's source block
     long long dst_off; // element offset of the image's output block
@@ -90,7 +88,7 @@ __global__ __launch_bounds__(256) void seg_resize_argmax_kernel(const float *__r
     }
 }
 
-// The checks both entry points share, and the job table they fill.  `max_pix`: the largest output image.
+// The checks both entry points share, and the job table they fill.
 int seg_jobs(const char *who, int B, int C, const int64_t *src_off, const int32_t *src_hw, const int32_t *out_hw, const int64_t *dst_off,
              std::vector<SegJob> &jobs, long long *max_pix, long long *out_pix, long long *src_pix) {
     WSC_CHECK(B >= 1 && B <= 65535 && C >= 1 && C <= SEG_MAX_C, WSC_ERR_INVALID, "%s: B=%d C=%d (1 <= B <= 65535, 1 <= C <= %d)", who, B, C,
@@ -116,6 +114,14 @@ int seg_jobs(const char *who, int B, int C, const int64_t *src_off, const int32_
     return WSC_OK;
 }
 
+// The job table on the device (its only section: offset 0) and the grid of both kernels: x over the largest output, y = image
+int seg_stage(WscStagedTable &tab, const std::vector<SegJob> &jobs, long long max_pix, dim3 *grid) {
+    tab.add(jobs);
+    WSC_TRY(tab.upload());
+    *grid = dim3((unsigned)std::min<long long>((max_pix + 255) / 256, 1024), (unsigned)jobs.size());
+    return WSC_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -131,16 +137,15 @@ int wsc_seg_unary_nhwc(wsc_ctx *ctx, const float *prob_dev, int B, int C, const 
     bool vec4 = C % 4 == 0 && (uintptr_t)prob_dev % 16 == 0;
     for (const SegJob &j : jobs) vec4 = vec4 && j.src_off % 4 == 0;
     WSC_HIP(hipSetDevice(ctx->device));
-    SegJob *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jobs.size() * sizeof(SegJob), (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, jobs.data(), jobs.size() * sizeof(SegJob)));
-    const dim3 grid((unsigned)std::min<long long>((max_pix + 255) / 256, 1024), (unsigned)B);
+    WscStagedTable tab(ctx);
+    dim3 grid;
+    WSC_TRY(seg_stage(tab, jobs, max_pix, &grid));
+    const SegJob *d = tab.at<const SegJob>(0);
     WscKernelTimer timer(ctx, WSC_K_CAM_TAIL, 4.0 * C * (double)(out_pix + src_pix));
-    if (vec4) hipLaunchKernelGGL(seg_unary_nhwc_kernel<true>, grid, dim3(256), 0, ctx->stream, prob_dev, (const SegJob *)d, C, unary_dev);
-    else hipLaunchKernelGGL(seg_unary_nhwc_kernel<false>, grid, dim3(256), 0, ctx->stream, prob_dev, (const SegJob *)d, C, unary_dev);
+    if (vec4) hipLaunchKernelGGL(seg_unary_nhwc_kernel<true>, grid, dim3(256), 0, ctx->stream, prob_dev, d, C, unary_dev);
+    else hipLaunchKernelGGL(seg_unary_nhwc_kernel<false>, grid, dim3(256), 0, ctx->stream, prob_dev, d, C, unary_dev);
     WSC_HIP(hipGetLastError());
-    d_guard.free_now(); // stream-ordered reuse
+    tab.release(); // stream-ordered reuse
     return WSC_OK;
 }
 
@@ -153,15 +158,14 @@ int wsc_seg_resize_argmax(wsc_ctx *ctx, const float *q_dev, int B, int C, const 
     WSC_TRY(seg_jobs("wsc_seg_resize_argmax", B, C, q_off_host, src_hw_host, out_hw_host, label_off_host, jobs, &max_pix, &out_pix,
                      &src_pix));
     WSC_HIP(hipSetDevice(ctx->device));
-    SegJob *d = nullptr;
-    WSC_TRY(wsc_ctx_cached_alloc(ctx, jobs.size() * sizeof(SegJob), (void **)&d));
-    WscCachedGuard d_guard(ctx, d);
-    WSC_TRY(wsc_ctx_upload_small(ctx, d, jobs.data(), jobs.size() * sizeof(SegJob)));
-    const dim3 grid((unsigned)std::min<long long>((max_pix + 255) / 256, 1024), (unsigned)B);
+    WscStagedTable tab(ctx);
+    dim3 grid;
+    WSC_TRY(seg_stage(tab, jobs, max_pix, &grid));
+    const SegJob *d = tab.at<const SegJob>(0);
     WscKernelTimer timer(ctx, WSC_K_CAM_TAIL, 4.0 * ((double)out_pix + (double)C * src_pix));
-    hipLaunchKernelGGL(seg_resize_argmax_kernel, grid, dim3(256), 0, ctx->stream, q_dev, (const SegJob *)d, C, label_dev);
+    hipLaunchKernelGGL(seg_resize_argmax_kernel, grid, dim3(256), 0, ctx->stream, q_dev, d, C, label_dev);
     WSC_HIP(hipGetLastError());
-    d_guard.free_now(); // stream-ordered reuse
+    tab.release(); // stream-ordered reuse
     return WSC_OK;
 }
 

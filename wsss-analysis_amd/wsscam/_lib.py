@@ -570,19 +570,28 @@ class Net:
                                                 _ptr(prob_dev)))
 
 
+def _key_table(keys_per_image, B=None):
+    """The int sequences of the first B images (default: all) -> (keys, key_off): the int32 keys one image after the other
+    (length >= 1, so that the array always has an address) and the int32 offsets [0, n_0, n_0 + n_1, ...] of the images."""
+    per = [np.asarray(k, dtype=np.int32).reshape(-1) for k in list(keys_per_image)[:B]]
+    key_off = np.zeros(len(per) + 1, dtype=np.int32)
+    key_off[1:] = np.cumsum([len(k) for k in per])
+    return np.concatenate(per + [np.zeros(0 if key_off[-1] else 1, np.int32)]), key_off
+
+
+def _size_table(sizes, B):
+    """B (height, width) pairs -> C-contiguous int32 (B, 2)."""
+    return np.ascontiguousarray(sizes, dtype=np.int32).reshape(B, 2)
+
+
 def cam_postprocess(ctx, cam_dev, B, C, h, w, sizes, keys_per_image, strided_dev=None, highres_dev=None):
     """Batched make_cam tail.  sizes: [(H0, W0)], keys_per_image: list of int sequences.
 
     Returns (strided_dev, highres_dev, strided_off, highres_off, shapes) where shapes[b] =
     (K, h4, w4, H0, W0); buffers are allocated when not given.
     """
-    size_hw = np.asarray(sizes, dtype=np.int32).reshape(B, 2)
-    key_off = np.zeros(B + 1, dtype=np.int32)
-    for b in range(B):
-        key_off[b + 1] = key_off[b] + len(keys_per_image[b])
-    keys = np.zeros(max(int(key_off[-1]), 1), dtype=np.int32)
-    for b in range(B):
-        keys[key_off[b]:key_off[b + 1]] = np.asarray(keys_per_image[b], dtype=np.int32)
+    size_hw = _size_table(sizes, B)
+    keys, key_off = _key_table(keys_per_image, B)
     s_off = np.zeros(B, dtype=np.int64)
     h_off = np.zeros(B, dtype=np.int64)
     shapes = []
@@ -668,13 +677,8 @@ def cam_eval_confusion(ctx, highres_dev, sizes, keys_per_image, highres_off, bg_
                        pred_dev=None, ignore_label=255):
     """Accumulates the eval_cam confusion matrix of a batch into confusion_dev (int64 [n_class][n_class])."""
     B = len(sizes)
-    size_hw = np.asarray(sizes, dtype=np.int32).reshape(B, 2)
-    key_off = np.zeros(B + 1, dtype=np.int32)
-    for b in range(B):
-        key_off[b + 1] = key_off[b] + len(keys_per_image[b])
-    keys = np.zeros(max(int(key_off[-1]), 1), dtype=np.int32)
-    for b in range(B):
-        keys[key_off[b]:key_off[b + 1]] = np.asarray(keys_per_image[b], dtype=np.int32)
+    size_hw = _size_table(sizes, B)
+    keys, key_off = _key_table(keys_per_image, B)
     h_off = np.ascontiguousarray(highres_off, dtype=np.int64)
     check(ctx._lib.wsc_cam_eval_confusion(ctx.h, _ptr(highres_dev), B, size_hw.ctypes.data, keys.ctypes.data,
                                           key_off.ctypes.data, h_off.ctypes.data, float(bg_thres), _ptr(gt_dev),
@@ -685,14 +689,9 @@ def cam_eval_confusion_nn(ctx, maps_dev, src_sizes, out_sizes, keys_per_image, m
                           pred_dev=None, ignore_label=255):
     """ADP / DeepGlobe eval_cam branch: keys[argmax(maps)] at the maps' size, cv2 nearest resize to out_sizes, confusion."""
     B = len(src_sizes)
-    src_hw = np.asarray(src_sizes, dtype=np.int32).reshape(B, 2)
-    out_hw = np.asarray(out_sizes, dtype=np.int32).reshape(B, 2)
-    key_off = np.zeros(B + 1, dtype=np.int32)
-    for b in range(B):
-        key_off[b + 1] = key_off[b] + len(keys_per_image[b])
-    keys = np.zeros(max(int(key_off[-1]), 1), dtype=np.int32)
-    for b in range(B):
-        keys[key_off[b]:key_off[b + 1]] = np.asarray(keys_per_image[b], dtype=np.int32)
+    src_hw = _size_table(src_sizes, B)
+    out_hw = _size_table(out_sizes, B)
+    keys, key_off = _key_table(keys_per_image, B)
     m_off = np.ascontiguousarray(maps_off, dtype=np.int64)
     check(ctx._lib.wsc_cam_eval_confusion_nn(ctx.h, _ptr(maps_dev), B, src_hw.ctypes.data, out_hw.ctypes.data, keys.ctypes.data,
                                              key_off.ctypes.data, m_off.ctypes.data, _ptr(gt_dev), int(n_class),
@@ -703,8 +702,8 @@ def label_confusion_nn(ctx, labels_dev, src_sizes, out_sizes, labels_off, gt_dev
                        ignore_label=255):
     """HSN evaluation tail: int32 label maps -> cv2 nearest resize to out_sizes -> confusion[gt][pred] (accumulated)."""
     B = len(src_sizes)
-    src_hw = np.asarray(src_sizes, dtype=np.int32).reshape(B, 2)
-    out_hw = np.asarray(out_sizes, dtype=np.int32).reshape(B, 2)
+    src_hw = _size_table(src_sizes, B)
+    out_hw = _size_table(out_sizes, B)
     off = np.ascontiguousarray(labels_off, dtype=np.int64)
     check(ctx._lib.wsc_label_confusion_nn(ctx.h, _ptr(labels_dev), B, src_hw.ctypes.data, out_hw.ctypes.data, off.ctypes.data,
                                           _ptr(gt_dev), int(n_class), int(ignore_label), _ptr(pred_dev), _ptr(confusion_dev)))
@@ -713,12 +712,7 @@ def label_confusion_nn(ctx, labels_dev, src_sizes, out_sizes, labels_off, gt_dev
 def sem_seg_finish(ctx, rw_dev, rw_off, khw, up_hw, out_hw, keys_per_image, has_bg, bg_thres, label_dev):
     """make_sem_seg_labels tail on the device: upsample + crop + / max + [bg pad] + argmax + keys -> packed uint8 labels."""
     B = len(khw)
-    key_off = np.zeros(B + 1, dtype=np.int32)
-    for b in range(B):
-        key_off[b + 1] = key_off[b] + len(keys_per_image[b])
-    keys = np.zeros(max(int(key_off[-1]), 1), dtype=np.int32)
-    for b in range(B):
-        keys[key_off[b]:key_off[b + 1]] = np.asarray(keys_per_image[b], dtype=np.int32)
+    keys, key_off = _key_table(keys_per_image, B)
     off = np.ascontiguousarray(rw_off, dtype=np.int64)
     a, u, o = (np.ascontiguousarray(v, dtype=np.int32).reshape(B, -1) for v in (khw, up_hw, out_hw))
     check(ctx._lib.wsc_sem_seg_finish(ctx.h, _ptr(rw_dev), B, off.ctypes.data, a.ctypes.data, u.ctypes.data, o.ctypes.data,
@@ -804,7 +798,7 @@ class CrfV:
         self.B = len(rgb_ptrs)
         self.sizes = [(int(h), int(w)) for h, w in sizes]
         assert len(self.sizes) == self.B
-        hw = np.ascontiguousarray(self.sizes, dtype=np.int32).reshape(self.B, 2)
+        hw = _size_table(self.sizes, self.B)
         arr = _ptr_array(rgb_ptrs)
         h = _vp()
         check(ctx._lib.wsc_crf_v_create(ctx.h, arr, hw.ctypes.data, self.B, float(g_sxy), float(bi_sxy), float(bi_srgb),
@@ -918,7 +912,7 @@ def hsn_gather_unary(ctx, maps_dev, chan_off, N, unary_dev):
 def msf_input_u8(ctx, images_dev, sizes, offsets, S, mean, std, x_dev, pre_div255=False, pair=True):
     """wsc_msf_input_u8: decoded uint8 images (packed HWC blocks at byte `offsets`) -> float32 network input."""
     B = len(sizes)
-    size_hw = np.ascontiguousarray(sizes, dtype=np.int32).reshape(B, 2)
+    size_hw = _size_table(sizes, B)
     off = np.ascontiguousarray(offsets, dtype=np.int64)
     m = np.ascontiguousarray(mean, dtype=np.float32)
     sd = np.ascontiguousarray(std, dtype=np.float32)
@@ -929,7 +923,7 @@ def msf_input_u8(ctx, images_dev, sizes, offsets, S, mean, std, x_dev, pre_div25
 def resize_u8(ctx, images_dev, sizes, offsets, out_hw, out_dev):
     """wsc_resize_u8: cv2.resize (INTER_LINEAR, 8-bit fixed point) of packed uint8 HWC images -> uint8 [B][OH][OW][3]."""
     B = len(sizes)
-    size_hw = np.ascontiguousarray(sizes, dtype=np.int32).reshape(B, 2)
+    size_hw = _size_table(sizes, B)
     off = np.ascontiguousarray(offsets, dtype=np.int64)
     check(ctx._lib.wsc_resize_u8(ctx.h, _ptr(images_dev), B, size_hw.ctypes.data, off.ctypes.data, int(out_hw[0]), int(out_hw[1]),
                                  _ptr(out_dev)))
@@ -962,8 +956,8 @@ def cue_seeds(ctx, fg_dev, bg_dev, B, C, Cb, H, W, thresh, label_dev, area_dev=N
 
 def _seg_tables(src_sizes, out_sizes, src_off, dst_off):
     B = len(src_sizes)
-    return (B, np.ascontiguousarray(src_off, dtype=np.int64), np.ascontiguousarray(src_sizes, dtype=np.int32).reshape(B, 2),
-            np.ascontiguousarray(out_sizes, dtype=np.int32).reshape(B, 2), np.ascontiguousarray(dst_off, dtype=np.int64))
+    return (B, np.ascontiguousarray(src_off, dtype=np.int64), _size_table(src_sizes, B), _size_table(out_sizes, B),
+            np.ascontiguousarray(dst_off, dtype=np.int64))
 
 
 def seg_unary_nhwc(ctx, prob_dev, C, src_sizes, out_sizes, prob_off, unary_off, unary_dev):
@@ -986,7 +980,7 @@ def seg_preprocess_u8(ctx, img_dev, sizes, offsets, mean_bgr, out_hw, x_dev):
     """wsc_seg_preprocess_u8: packed uint8 RGB images ([h_i][w_i][3] blocks at byte `offsets`) -> float32 [n][H][W][3], the TF 1.x
     bilinear resize to out_hw, BGR, minus mean_bgr: image_preprocess of a ragged batch in one launch."""
     n = len(sizes)
-    size_hw = np.ascontiguousarray(sizes, dtype=np.int32).reshape(n, 2)
+    size_hw = _size_table(sizes, n)
     off = np.ascontiguousarray(offsets, dtype=np.int64)
     m = np.ascontiguousarray(mean_bgr, dtype=np.float32).reshape(3)
     check(ctx._lib.wsc_seg_preprocess_u8(ctx.h, _ptr(img_dev), n, size_hw.ctypes.data, off.ctypes.data, m.ctypes.data, int(out_hw[0]),
