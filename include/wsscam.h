@@ -193,7 +193,17 @@ const char *wsc_profile_class_name(int cls);
  * (net/resnet50.py:11-14, eps from "<bn>.eps" if given else 1e-5) is folded
  * into per-channel scale/shift applied in the conv epilogue.
  * Missing keys -> WSC_ERR_MISSING_KEY, wrong shapes -> WSC_ERR_SHAPE (the WSC_ARCH_DEEPLAB_* nets: WSC_ERR_SHAPE for both,
- * see wsc_net_forward_seg). */
+ * see wsc_net_forward_seg).
+ *
+ * Optional key `pool_spec` (WSC_ARCH_VGG16_CAM, WSC_ARCH_M7_CAM), float32 [3][3]: row i = (window, stride, same) of the i-th
+ * MaxPooling2D in the order the pools occur -- the three 'M' entries of the VGG16 table; for M7 the two of the stack, then
+ * layer3_p2 of the classifier branch.  It carries what a Keras-side session's architecture file says (02_cues/demo.py:104-124,
+ * 03c_hsn/utilities.py build_model: model_from_json) where the torch port has MaxPool2d(2, 2) (common_cnn.py:131-132): each pool
+ * then follows the rule of wsc_pool_tf_nhwc, wsc_net_cam_size* the sizes it gives (41 at 321 for 3 x 3 / 2 SAME pools), and the
+ * M7 classifier branch takes the global maximum of the POOLED map (a VALID pool can leave the last row / column out).  Without
+ * the key: the fixed architectures.  Another row count or shape -> WSC_ERR_SHAPE; a non-integral value, a window outside
+ * {2, 3}, a stride outside {1, 2} or above the window, same outside {0, 1} -> WSC_ERR_INVALID naming the row; the key on any
+ * other arch -> WSC_ERR_INVALID (the IRN flavours keep the torch port's geometry). */
 int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n_weights,
                    int num_classes, int precision, wsc_net **out);
 void wsc_net_destroy(wsc_net *net);
@@ -324,6 +334,16 @@ int wsc_resize_bilinear_tf(wsc_ctx *ctx, const float *src_dev, int B, int h, int
  *   sum_dev NULL or [M][C] receives the summed logits. */
 int wsc_pool_same_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, int avg, int stride, int precision,
                        float *y_dev);
+/* TensorFlow / Keras MaxPooling2D(pool_size = k, strides = stride, padding = 'same' | 'valid') on float32 NHWC, through the
+ * activation planes of `precision` -- the pool of a `pool_spec` row (wsc_net_create), i.e. of the Keras-side CNNs the drivers
+ * of 02_cues/demo.py:104-124 and 03c_hsn/demo.py load from <sess_id>.json.  k 2 or 3, stride 1 or 2 (<= k), same 0 or 1, max
+ * only.  Per axis, TensorFlow's rule:
+ *   SAME   out = ceil(in / stride), pad_total = max((out - 1) stride + k - in, 0), pad_before = floor(pad_total / 2)
+ *   VALID  out = floor((in - k) / stride) + 1, no padding; in < k is WSC_ERR_INVALID
+ * Padding never wins the maximum (-inf, not 0).  The two-plane precisions take the maximum of hi + lo; a maximum is one of
+ * its inputs, so the result is exact on values the planes hold.  y_dev [N][out_h][out_w][C], C a multiple of 8. */
+int wsc_pool_tf_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, int k, int stride, int same, int precision,
+                     float *y_dev);
 int wsc_fc8_softmax(wsc_ctx *ctx, const float *const *fc8_dev, int n_in, long long M, int C, float min_prob, float *sum_dev,
                     float *prob_dev);
 

@@ -434,6 +434,11 @@ int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y);
 void pool_same_dims(int in, int stride, int *out, int *pad_before);
 // 3x3 max (stride 1 / 2; padding is -inf) or average over the in-image taps (stride 1) on an NHWC activation, every plane
 int launch_pool_same(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int avg, int stride, Act y);
+// TF / Keras MaxPooling2D of one axis, window k, `same` 1 / 0: SAME out = ceil(in / stride), pad_before = max((out - 1) stride +
+// k - in, 0) / 2; VALID out = (in - k) / stride + 1, no padding.  false: the axis is no input of that window (VALID, in < k)
+bool pool_tf_dims(int in, int k, int stride, int same, int *out, int *pad_before);
+// k x k max (k 2 / 3, stride 1 / 2 <= k, padding is -inf) of that geometry on an NHWC activation, every plane
+int launch_pool_tf(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int k, int stride, int same, Act y);
 // float32 [N][H][W][3] -> NHWC4 activation (raises the range flag where an IEEE-half plane saturates)
 int launch_nhwc3_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y);
 // prob[m][c] = fc8-softmax of (in[0] + ... + in[n_in - 1])[m][c]; fc8 (optional) receives the summed logits

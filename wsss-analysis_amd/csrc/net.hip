@@ -52,7 +52,14 @@ struct IrnCat {
     int channels, stage, stride;
 };
 
-enum OpType { OP_CONV = 0, OP_POOL = 1, OP_GATHER = 2, OP_POOL_SAME = 3 /* TF SAME 3x3: ps = stride, pp = 1 for the average */ };
+enum OpType {
+    OP_CONV = 0, OP_POOL = 1, OP_GATHER = 2, OP_POOL_SAME = 3 /* TF SAME 3x3: ps = stride, pp = 1 for the average */,
+    OP_POOL_TF = 4 /* a `pool_spec` row, TF / Keras MaxPooling2D: pk = window, ps = stride, pp = 1 for SAME, 0 for VALID */
+};
+// one row of `pool_spec`
+struct PoolSpec {
+    int k, stride, same;
+};
 // one fc6 (3x3 atrous) -> fc7 (1x1) -> fc8 (1x1, no ReLU, fp32 logits) branch of the DeepLab head
 struct SegBranch {
     ConvW fc6, fc7, fc8;
@@ -80,6 +87,8 @@ struct wsc_net {
     float *cls_w = nullptr, *cls_b = nullptr; // classifier branch (vgg16 / m7), fp32 [Ccls][F]
     int Ccls = 0;
     int cls_max = 0; // 1: global max pooling (m7), 0: global average (vgg16)
+    bool cls_pool_set = false; // m7 with a `pool_spec`: its third row, the classifier branch's layer3_p2 pool
+    PoolSpec cls_pool = {2, 2, 0};
     // IRNet EdgeDisplacement (arch >= WSC_ARCH_RESNET50_IRN): backbone stage taps + the two head branches
     std::vector<int> taps;       // op index whose output is stage k+1 (x1..x5)
     std::vector<IrnHead> heads;  // every Conv-GroupNorm-[Upsample]-ReLU head in execution order
@@ -377,19 +386,49 @@ int build_resnet50(wsc_net *net, const Dict &d) {
     return WSC_OK;
 }
 
-// VGG-style stacks of common_cnn.make_layers: cfg entries >0 = conv out channels, -1 = 'M', -2 = 'D'.
+// The optional `pool_spec` tensor, float32 [n_pools][3]: row i = (window, stride, same) of the i-th MaxPooling2D in the order the
+// pools occur -- what a Keras-side session's architecture file says (02_cues/demo.py:104-124 builds the model with
+// model_from_json) where the torch port has MaxPool2d(2, 2).  *present = false without the key: the fixed architecture.
+int read_pool_spec(const Dict &d, int n_pools, std::vector<PoolSpec> *spec, bool *present) {
+    *present = has(d, "pool_spec");
+    if (!*present) return WSC_OK;
+    const HostTensor *t;
+    WSC_TRY(get(d, "pool_spec", 2, &t));
+    WSC_CHECK(t->shape[0] == n_pools && t->shape[1] == 3, WSC_ERR_SHAPE, "pool_spec must be [%d][3] (window, stride, same) for this arch, got [%lld][%lld]",
+              n_pools, (long long)t->shape[0], (long long)t->shape[1]);
+    for (int i = 0; i < n_pools; ++i) {
+        const float *r = t->data + 3 * i;
+        WSC_CHECK(r[0] == std::floor(r[0]) && r[1] == std::floor(r[1]) && r[2] == std::floor(r[2]), WSC_ERR_INVALID,
+                  "pool_spec row %d: (%g, %g, %g) is not integral", i, (double)r[0], (double)r[1], (double)r[2]);
+        const PoolSpec ps = {(int)r[0], (int)r[1], (int)r[2]};
+        WSC_CHECK((ps.k == 2 || ps.k == 3) && (ps.stride == 1 || ps.stride == 2) && ps.stride <= ps.k && (ps.same == 0 || ps.same == 1),
+                  WSC_ERR_INVALID, "pool_spec row %d: window %d (2 / 3), stride %d (1 / 2, <= window), same %d (0 / 1)", i, ps.k, ps.stride, ps.same);
+        spec->push_back(ps);
+    }
+    return WSC_OK;
+}
+
+// VGG-style stacks of common_cnn.make_layers: cfg entries >0 = conv out channels, -1 = 'M', -2 = 'D'.  `pools`: the geometry of
+// the 'M' entries in their order (a `pool_spec`), or null for MaxPool2d(2, 2).
 int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
                       const std::vector<std::pair<std::string, std::vector<int>>> &cfg, int *cur_io,
-                      int *feat_channels, std::vector<int> *layer_taps = nullptr) {
+                      int *feat_channels, std::vector<int> *layer_taps = nullptr, const std::vector<PoolSpec> *pools = nullptr) {
     int cur = *cur_io;
     int in_ch = 3;
     bool first = true;
+    size_t n_pool = 0;
     for (const auto &layer : cfg) {
         int idx = 0;
         for (int v : layer.second) {
-            if (v == -1) { // nn.MaxPool2d(2, 2), common_cnn.py:131-132
+            if (v == -1) { // nn.MaxPool2d(2, 2), common_cnn.py:131-132 -- or the session's own MaxPooling2D
                 const int out = (cur + 1) & 1;
-                add_pool_op(net, 2, 2, 0, cur, out);
+                if (pools) {
+                    WSC_CHECK(n_pool < pools->size(), WSC_ERR_INVALID, "internal: pool_spec has %d rows, the stack more pools", (int)pools->size());
+                    const PoolSpec &ps = (*pools)[n_pool++];
+                    Op op;
+                    op.type = OP_POOL_TF; op.conv = -1; op.in = cur; op.out = out; op.res = -1; op.pk = ps.k; op.ps = ps.stride; op.pp = ps.same;
+                    net->ops.push_back(op);
+                } else add_pool_op(net, 2, 2, 0, cur, out);
                 cur = out;
                 idx += 1;
             } else if (v == -2) { // nn.Dropout: identity in eval()
@@ -449,7 +488,10 @@ int build_vgg16(wsc_net *net, const Dict &d) {
         {"layer4", {512, 512, 512, 512, 512, 512}},
         {"layer5", {1024, -2, 1024, -2}}}; // vgg16.py:44
     int cur = 0;
-    WSC_TRY(build_plain_stack(net, d, "vgg16", cfg, &cur, &net->F));
+    std::vector<PoolSpec> pools;
+    bool spec;
+    WSC_TRY(read_pool_spec(d, 3, &pools, &spec));
+    WSC_TRY(build_plain_stack(net, d, "vgg16", cfg, &cur, &net->F, nullptr, spec ? &pools : nullptr));
     net->final_buf = cur;
     const HostTensor *lw;
     WSC_TRY(get(d, "vgg16.classifier.0.weight", 2, &lw));
@@ -488,7 +530,10 @@ int build_m7(wsc_net *net, const Dict &d) {
     const std::vector<std::pair<std::string, std::vector<int>>> cfg = {
         {"layer1", {64, 64, -1}}, {"layer2", {128, 128, -1}}, {"layer3_p1", {256, 256, 256}}}; // m7.py:41
     int cur = 0;
-    WSC_TRY(build_plain_stack(net, d, "m7", cfg, &cur, &net->F));
+    std::vector<PoolSpec> pools; // the two of the stack, then layer3_p2 of the classifier branch
+    WSC_TRY(read_pool_spec(d, 3, &pools, &net->cls_pool_set));
+    if (net->cls_pool_set) net->cls_pool = pools[2];
+    WSC_TRY(build_plain_stack(net, d, "m7", cfg, &cur, &net->F, nullptr, net->cls_pool_set ? &pools : nullptr));
     net->final_buf = cur;
     // Grad-CAM weights (F x C) transposed as the 1x1 head: m7_cam.py:45-46
     const HostTensor *gw;
@@ -504,7 +549,8 @@ int build_m7(wsc_net *net, const Dict &d) {
     WSC_TRY(gradcam_bias(d, net->C, zero));
     WSC_TRY(make_conv(net, &hw, 1, 0, 0, CONV_FORM_GENERIC, one, zero, nullptr, nullptr, &net->head));
     // classifier branch: layer3_p2 (MaxPool 2x2 + Dropout) -> AdaptiveMaxPool2d(1) -> Linear + Sigmoid
-    // (m7_cam.py:32-35).  max over 2x2-pooled map == global max when h, w are even.
+    // (m7_cam.py:32-35).  max over 2x2-pooled map == global max when h, w are even.  With a `pool_spec` the pool is its third
+    // row and run_classifier takes the maximum of the pooled map where the two differ.
     const HostTensor *lw;
     WSC_TRY(get(d, "m7.classifier.0.weight", 2, &lw));
     WSC_CHECK(lw->shape[0] >= net->C && lw->shape[1] == net->F, WSC_ERR_SHAPE,
@@ -750,6 +796,11 @@ int plan_dims(const wsc_net *net, int N, int SH, int SW, Plan *pl) {
             pool_same_dims(d.H, op.ps, &d.Ho, &pad_before);
             pool_same_dims(d.W, op.ps, &d.Wo, &pad_before);
             d.Co = d.C;
+        } else if (op.type == OP_POOL_TF) {
+            int pad_before; // (a VALID window wider than the map: out = 0, the check below)
+            pool_tf_dims(d.H, op.pk, op.ps, op.pp, &d.Ho, &pad_before);
+            pool_tf_dims(d.W, op.pk, op.ps, op.pp, &d.Wo, &pad_before);
+            d.Co = d.C;
         } else {
             d.Ho = (d.H + 2 * op.pp - op.pk) / op.ps + 1;
             d.Wo = (d.W + 2 * op.pp - op.pk) / op.ps + 1;
@@ -776,7 +827,8 @@ size_t taps_bytes(const wsc_net *net, const Plan &pl, int N) {
 // `taps` the stage outputs x1..x5 (net->taps) are copied to the start of that region, in stage order, and *extra is what
 // follows them -- the rotating activation buffers are overwritten as the stack proceeds.
 int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, size_t extra_bytes, Act *feat, int *hf, int *wf,
-                 void **extra, std::vector<Act> *taps = nullptr, int SW = 0, bool nhwc_in = false) {
+                 void **extra, std::vector<Act> *taps = nullptr, int SW = 0, bool nhwc_in = false, Act *spare = nullptr) {
+    // (spare: a rotating buffer other than *feat, free once the stack has run -- any tensor no larger than the feature map fits)
     // (nhwc_in: x_dev is [N][S][SW][3] instead of [N][3][S][SW] -- the DeepLab nets take TensorFlow's layout)
     if (SW <= 0) SW = S; // S x SW input (SW given for the non-square, native-size path)
     Plan pl;
@@ -844,6 +896,8 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             WSC_TRY(launch_gather_strided(ctx, src, N, d.H, d.W, d.C, op.ps, d.Ho, d.Wo, buf[op.out].at(op.coff), op.pitch));
         } else if (op.type == OP_POOL_SAME) {
             WSC_TRY(launch_pool_same(ctx, src, N, d.H, d.W, d.C, op.pp, op.ps, buf[op.out]));
+        } else if (op.type == OP_POOL_TF) {
+            WSC_TRY(launch_pool_tf(ctx, src, N, d.H, d.W, d.C, op.pk, op.ps, op.pp, buf[op.out]));
         } else {
             WSC_TRY(launch_maxpool(ctx, src, N, d.H, d.W, d.C, op.pk, op.ps, op.pp, d.Ho, d.Wo, buf[op.out]));
         }
@@ -856,9 +910,34 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
                 }
     }
     *feat = buf[net->final_buf];
+    if (spare) *spare = buf[net->final_buf == 3 ? 2 : 3];
     *hf = pl.hf;
     *wf = pl.wf;
     return WSC_OK;
+}
+
+// The classifier branch on the feature map of `count` samples, every `sample_stride`-th of the N in `feat`: global average
+// (vgg16) or global max (m7) -> Linear -> Sigmoid.  m7 pools first (layer3_p2, m7_cam.py:32-35).  The maximum of the pooled map
+// is the maximum of the map itself unless the pool's windows leave positions out -- a VALID pool whose last window ends before
+// the last row or column (9 x 9 under 2 x 2 / 2: row and column 8).  Only then, and only for a `pool_spec` net, the pool is run
+// into `spare` and the pooled map reduced; a net without the key keeps the one-pass form whatever the size.
+int run_classifier(wsc_ctx *ctx, const wsc_net *net, Act feat, Act spare, int N, int count, int sample_stride, int hf, int wf,
+                   float *score_dev) {
+    int hw = hf * wf;
+    if (net->cls_max && net->cls_pool_set) {
+        const PoolSpec &ps = net->cls_pool;
+        int hp, wp, pad;
+        WSC_CHECK(pool_tf_dims(hf, ps.k, ps.stride, ps.same, &hp, &pad) && pool_tf_dims(wf, ps.k, ps.stride, ps.same, &wp, &pad), WSC_ERR_INVALID,
+                  "the %d x %d feature map is smaller than the classifier branch's %d x %d VALID pool", hf, wf, ps.k, ps.k);
+        const bool crops = !ps.same && ((hp - 1) * ps.stride + ps.k < hf || (wp - 1) * ps.stride + ps.k < wf);
+        if (crops) {
+            WSC_TRY(launch_pool_tf(ctx, feat, N, hf, wf, net->F, ps.k, ps.stride, ps.same, spare));
+            feat = spare;
+            hw = hp * wp;
+        }
+    }
+    return launch_gap_linear_sigmoid(ctx, feat, count, net->cls_max ? -hw : hw, net->F, net->cls_w, net->cls_b, net->Ccls, score_dev,
+                                     sample_stride);
 }
 
 } // namespace
@@ -886,6 +965,9 @@ int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n
         if (t.ndim == 0) { t.ndim = 1; t.shape[0] = 1; }
         d[weights[i].name] = t;
     }
+    // (never ignored: the IRN flavours keep the torch port's MaxPool2d(2, 2), the other nets have their own pools)
+    WSC_CHECK(!has(d, "pool_spec") || arch == WSC_ARCH_VGG16_CAM || arch == WSC_ARCH_M7_CAM, WSC_ERR_INVALID,
+              "pool_spec is a key of WSC_ARCH_VGG16_CAM / WSC_ARCH_M7_CAM only (arch %d)", arch);
     wsc_net *net = new wsc_net();
     net->ctx = ctx;
     net->arch = arch;
@@ -974,10 +1056,10 @@ int wsc_net_forward_cam_hw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev,
     Plan pl;
     WSC_TRY(plan_dims(net, N, S, SW, &pl));
     const size_t head_bytes = (size_t)N * pl.hf * pl.wf * net->C * sizeof(float);
-    Act feat;
+    Act feat, spare;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, head_bytes, &feat, &hf, &wf, &extra, nullptr, SW));
+    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, head_bytes, &feat, &hf, &wf, &extra, nullptr, SW, false, &spare));
     float *head_out = (float *)extra;
     ConvLaunch L = conv_launch(net->head, net->prec);
     L.x = feat;
@@ -985,9 +1067,7 @@ int wsc_net_forward_cam_hw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev,
     L.N = N; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf;
     WSC_TRY(run_head(ctx, L));
     WSC_TRY(launch_flip_add(ctx, head_out, B, hf, wf, net->C, net->C, cam_dev));
-    if (score_dev != nullptr)
-        WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, B, net->cls_max ? -(hf * wf) : hf * wf, net->F, net->cls_w, net->cls_b, net->Ccls,
-                                          score_dev, 2));
+    if (score_dev != nullptr) WSC_TRY(run_classifier(ctx, net, feat, spare, N, B, 2, hf, wf, score_dev));
     return WSC_OK;
 }
 
@@ -999,19 +1079,17 @@ int wsc_net_forward_gradcam(wsc_ctx *ctx, const wsc_net *net, const float *x_dev
     WSC_CHECK(score_dev == nullptr || net->cls_w != nullptr, WSC_ERR_INVALID,
               "this architecture has no classifier branch (score_dev must be NULL)");
     WSC_HIP(hipSetDevice(ctx->device));
-    Act feat;
+    Act feat, spare;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &hf, &wf, &extra));
+    WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &hf, &wf, &extra, nullptr, 0, false, &spare));
     ConvLaunch L = conv_launch(net->head, net->prec);
     L.x = feat;
     L.y_f32 = cams_dev; // fp32 NHWC [N][h][w][C]: the layout of np.einsum('ijkl,lm->ijkm')
     L.N = N; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf;
     L.relu = relu ? 1 : 0;
     WSC_TRY(run_head(ctx, L));
-    if (score_dev != nullptr)
-        WSC_TRY(launch_gap_linear_sigmoid(ctx, feat, N, net->cls_max ? -(hf * wf) : hf * wf, net->F, net->cls_w, net->cls_b, net->Ccls,
-                                          score_dev, 1));
+    if (score_dev != nullptr) WSC_TRY(run_classifier(ctx, net, feat, spare, N, N, 1, hf, wf, score_dev));
     return WSC_OK;
 }
 

@@ -118,6 +118,7 @@ _SIGNATURES = {
     "wsc_net_forward_seg": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "wsc_resize_bilinear_tf": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i]),
     "wsc_pool_same_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_pool_tf_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "wsc_fc8_softmax": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _f, _vp, _vp]),
     "wsc_cam_postprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wsc_cam_eval_confusion": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp]),
@@ -664,6 +665,23 @@ def pool_same_nhwc(ctx, x_dev, N, H, W, C, avg, stride, precision, y_dev=None):
         y_dev = ctx.alloc(N * Ho * Wo * C * 4)
     check(ctx._lib.wsc_pool_same_nhwc(ctx.h, _ptr(x_dev), int(N), int(H), int(W), int(C), int(bool(avg)), int(stride), int(precision),
                                       _ptr(y_dev)))
+    return y_dev, (N, Ho, Wo, C)
+
+
+def pool_tf_nhwc(ctx, x_dev, N, H, W, C, k, stride, same, precision, y_dev=None):
+    """One TF / Keras MaxPooling2D(k, stride, 'same' if same else 'valid') on float32 NHWC (wsc_pool_tf_nhwc) ->
+    (y_dev, (N, Ho, Wo, C)); the output size is net.common.pooled_size's (a VALID window wider than the map: WscError)."""
+    from .net.common import pooled_size
+
+    row = (int(k), int(stride), "same" if same else "valid")
+    try:
+        Ho, Wo = pooled_size(H, [row]), pooled_size(W, [row])
+    except ValueError:
+        Ho = Wo = 0  # (no such output: the library says so before it launches anything)
+    if y_dev is None:
+        y_dev = ctx.alloc(max(N * Ho * Wo * C, 1) * 4)
+    check(ctx._lib.wsc_pool_tf_nhwc(ctx.h, _ptr(x_dev), int(N), int(H), int(W), int(C), int(k), int(stride), int(same),
+                                    int(precision), _ptr(y_dev)))
     return y_dev, (N, Ho, Wo, C)
 
 

@@ -30,15 +30,17 @@ def get_grad_cam_weights(input_model, final_layer, dummy_image, should_normalize
         evenly over the ties, as TF's reduce_max does, keeps the mean but changes the RMS normaliser; the Keras
         architecture files are not in the tree, so this is the torch port's reading, m7.py:17 AdaptiveMaxPool2d.)
     Equal to torch.autograd on the restated nets up to round-off (tests/test_cues_host.py)."""
-    from ..net.common import PLAIN_CFG, grad_cam_alpha, last_bn_affine
+    from ..net.common import PLAIN_CFG, grad_cam_alpha, last_bn_affine, pooled_size
 
     sd = input_model._sd
     root = input_model.root
     W = np.asarray(sd[root + ".classifier.0.weight"], dtype=np.float64)  # (C, F)
     S = int(dummy_image.shape[1])
-    h = S
-    for _, layer in PLAIN_CFG[root]:
-        h //= 2 ** sum(1 for v in layer if v == "M")
+    n_pools = sum(1 for _, layer in PLAIN_CFG[root] for v in layer if v == "M")
+    pooling = getattr(input_model, "pooling", None)
+    # MaxPool2d(2, 2) per 'M' -- or the session's own pools (a spec's rows beyond the stack's belong to the classifier branch:
+    # they do not change A's size, and the mean of the one-hot gradient does not depend on which position the pooling selects)
+    h = S // 2 ** n_pools if pooling is None else pooled_size(S, pooling[:n_pools])
     affine = last_bn_affine(sd, root)
     return grad_cam_alpha(W, h, h, "max" if root == "m7" else "avg", should_normalize,
                           bn_scale=None if affine is None else affine[0])

@@ -3,8 +3,13 @@ do not hand the loaded objects in: `settings.ini`, the classifier CNN of a sessi
 thresholds under MODEL_ROOT/<dataset>_<model_type>/) and the image list + image-level labels of a split (the CSV files the
 reference's `Dataset` class feeds to Keras' flow_from_dataframe, 02_cues/dataset.py:98-124).
 
-The `.json` architecture files are not read: the device networks have the two fixed architectures of the reference's
-torch mirrors (net/vgg16.py:44, net/m7.py:41), selected by `model_type` -- 'VGG16*' -> modified VGG16, 'M7*' / 'X1.7' -> M7.
+The device networks have the two fixed conv tables of the reference's torch mirrors (net/vgg16.py:44, net/m7.py:41), selected
+by `model_type` -- 'VGG16*' -> modified VGG16, 'M7*' / 'X1.7' -> M7.  A session's `<sess_id>.json` (Keras 2 `model.to_json()`,
+what the reference hands to model_from_json) is read when it lies beside the `.h5`: `read_architecture` checks its layer
+sequence against that table -- any other layer, order, kernel, activation placement or BatchNorm epsilon is a ValueError, never
+a fallback -- and takes from it what the table leaves open, the geometry of the MaxPooling2D layers, which `load_model` sets
+on the model (`set_pooling`) before the network is packed and before the Grad-CAM weights are computed.  With no `.json` on
+disk the pools are the torch port's MaxPool2d(2, 2), exactly as before.
 Reading `.h5` needs h5py (net.common.keras_h5_weight_list); a missing file or module is an error, never a fallback."""
 import configparser
 import csv
@@ -108,6 +113,120 @@ class Dataset:
                                        .reshape(len(rows), len(self.class_names)))
 
 
+def _square(v, what, i):
+    """An int, or a pair of equal ints, of a Keras layer config -> the int."""
+    if isinstance(v, (list, tuple)):
+        if len(v) != 2 or v[0] != v[1]:
+            raise ValueError("layer %d: %s %r is not square" % (i, what, v))
+        v = v[0]
+    if not isinstance(v, int) or isinstance(v, bool):
+        raise ValueError("layer %d: %s %r is not an integer" % (i, what, v))
+    return v
+
+
+def read_architecture(path, model_type):
+    """The session's architecture file -> (pooling, has_batchnorm): pooling = [(k, stride, 'same' | 'valid'), ...] of the
+    MaxPooling2D layers in the order they occur (for M7 the classifier branch's pool last), as the CAM wrappers' `pooling` takes it.
+
+    `path` holds Keras 2 `model.to_json()` of a Sequential model, `"config"` either the layer list or `{"layers": [...]}`.
+    InputLayer and Dropout entries are skipped; the rest must be the model type's table (net.common.PLAIN_CFG):
+    per conv entry Conv2D(filters, 3 x 3, stride 1, 'same', linear) -> Activation('relu') [-> BatchNormalization(epsilon 1e-3):
+    after every Activation or after none], MaxPooling2D at the 'M' positions (and, M7, before the global pooling),
+    GlobalAveragePooling2D (VGG16) / GlobalMaxPooling2D (M7), Dense with the model type's use_bias, optionally a final
+    Activation('sigmoid').  Anything else raises ValueError with the layer's index and what was expected there -- a ReLU fused
+    into the Conv2D included: find_final_layer would then name the BatchNorm, another Grad-CAM contraction point."""
+    import json
+
+    from .net.common import PLAIN_CFG, normalize_pooling
+
+    root = "vgg16" if "VGG16" in model_type else "m7"
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or doc.get("class_name") != "Sequential":
+        raise ValueError("%s: a Keras Sequential model is expected, got class_name %r" %
+                         (path, doc.get("class_name") if isinstance(doc, dict) else type(doc).__name__))
+    cfg = doc.get("config")
+    if isinstance(cfg, dict):
+        cfg = cfg.get("layers")
+    if not isinstance(cfg, list):
+        raise ValueError("%s: no layer list under 'config'" % path)
+    layers = [(i, l.get("class_name"), l.get("config") or {}) for i, l in enumerate(cfg)
+              if l.get("class_name") not in ("InputLayer", "Dropout")]
+    pos = [0]
+
+    def take(expected):
+        if pos[0] >= len(layers):
+            raise ValueError("%s: the model ends after %d layers where %s was expected" % (path, len(cfg), expected))
+        i, name, c = layers[pos[0]]
+        if name != expected:
+            raise ValueError("%s: layer %d is %s, expected %s" % (path, i, name, expected))
+        pos[0] += 1
+        return i, c
+
+    def peek():
+        return layers[pos[0]][1] if pos[0] < len(layers) else None
+
+    def max_pool():
+        i, c = take("MaxPooling2D")
+        k = _square(c.get("pool_size"), "pool_size", i)
+        stride = k if c.get("strides") is None else _square(c.get("strides"), "strides", i)
+        padding = c.get("padding")
+        if k not in (2, 3) or stride not in (1, 2) or stride > k or padding not in ("same", "valid"):
+            raise ValueError("%s: layer %d: MaxPooling2D(%r, strides %r, %r) -- window 2 / 3, stride 1 / 2 (<= window), 'same' / "
+                             "'valid' are supported" % (path, i, k, stride, padding))
+        return k, stride, padding
+
+    pooling, has_bn = [], None
+    for _, table in PLAIN_CFG[root]:
+        for v in table:
+            if v == "D":
+                continue
+            if v == "M":
+                pooling.append(max_pool())
+                continue
+            i, c = take("Conv2D")
+            if c.get("filters") != v:
+                raise ValueError("%s: layer %d: Conv2D with %r filters, expected %d" % (path, i, c.get("filters"), v))
+            if _square(c.get("kernel_size"), "kernel_size", i) != 3 or _square(c.get("strides", 1), "strides", i) != 1 \
+                    or c.get("padding") != "same" or _square(c.get("dilation_rate", 1), "dilation_rate", i) != 1:
+                raise ValueError("%s: layer %d: Conv2D must be 3 x 3, stride 1, padding 'same', got kernel %r strides %r padding %r"
+                                 % (path, i, c.get("kernel_size"), c.get("strides"), c.get("padding")))
+            if c.get("activation", "linear") != "linear":
+                raise ValueError("%s: layer %d: Conv2D with a fused %r activation, expected a linear Conv2D followed by an "
+                                 "Activation layer" % (path, i, c.get("activation")))
+            if c.get("use_bias", True) is not True:
+                raise ValueError("%s: layer %d: Conv2D without a bias" % (path, i))
+            i, c = take("Activation")
+            if c.get("activation") != "relu":
+                raise ValueError("%s: layer %d: Activation %r, expected 'relu'" % (path, i, c.get("activation")))
+            bn = peek() == "BatchNormalization"
+            if has_bn is None:
+                has_bn = bn
+            elif bn != has_bn:
+                raise ValueError("%s: layer %d: BatchNormalization must follow every Activation or none"
+                                 % (path, layers[min(pos[0], len(layers) - 1)][0]))
+            if bn:
+                i, c = take("BatchNormalization")
+                if abs(float(c.get("epsilon", 1e-3)) - 1e-3) > 1e-9:
+                    raise ValueError("%s: layer %d: BatchNormalization epsilon %r, expected 1e-3" % (path, i, c.get("epsilon")))
+    if root == "m7":
+        pooling.append(max_pool())  # layer3_p2 of the classifier branch (net/m7.py:15-21)
+    take("GlobalAveragePooling2D" if root == "vgg16" else "GlobalMaxPooling2D")
+    i, c = take("Dense")
+    use_bias = "VGG16" not in model_type  # common_cnn.py:44
+    if bool(c.get("use_bias", True)) != use_bias:
+        raise ValueError("%s: layer %d: Dense use_bias %r, a %s model has %r" % (path, i, c.get("use_bias"), model_type, use_bias))
+    if c.get("activation", "linear") not in ("linear", "sigmoid"):
+        raise ValueError("%s: layer %d: Dense activation %r, expected 'sigmoid' (or linear + Activation)" % (path, i, c.get("activation")))
+    if peek() == "Activation":
+        i, c = take("Activation")
+        if c.get("activation") != "sigmoid":
+            raise ValueError("%s: layer %d: Activation %r after the Dense layer, expected 'sigmoid'" % (path, i, c.get("activation")))
+    if pos[0] != len(layers):
+        raise ValueError("%s: layer %d is %s, expected the end of the model" % (path, layers[pos[0]][0], layers[pos[0]][1]))
+    return normalize_pooling(pooling), bool(has_bn)
+
+
 def load_model(model_dir, sess_id, model_type, dataset, device=0, precision=None):
     """02_cues/demo.py:104-124 / 03c_hsn/utilities.py build_model + load_thresholds + get_grad_cam_weights:
     (device CAM wrapper with the session's weights, alpha (F, C), final layer name, thresholds (1, C))."""
@@ -123,6 +242,13 @@ def load_model(model_dir, sess_id, model_type, dataset, device=0, precision=None
     num_classes = int(np.asarray(thresholds).shape[1])
     ds_tag = {"ADP": "adp_morph", "VOC2012": "voc12"}.get(dataset, "deepglobe")
     model = cls(None, ds_tag, model_type, num_classes, None, precision=precision)
+    arch_path = os.path.join(model_dir, sess_id + ".json")
+    if os.path.exists(arch_path):  # the session's own pools: before the net is packed and before alpha (its map size)
+        pooling, has_bn = read_architecture(arch_path, model_type)
+        if has_bn != bool(model.batchnorm):
+            raise ValueError("%s: the architecture %s BatchNorm, the %s / %s model type %s" % (
+                arch_path, "has" if has_bn else "has no", dataset, model_type, "has it" if model.batchnorm else "has none"))
+        model.set_pooling(pooling)
     model.load_state_dict(state_dict_from_keras_weights(weights, model_type, cls.root, model.batchnorm, np.asarray(thresholds)[0]))
     model.cuda(device)
     img_size = 321 if model_type in ("VGG16", "VGG16bg") else 224

@@ -16,10 +16,57 @@ def _to_numpy_sd(state_dict):
     return out
 
 
+def pool_axis(n, k, stride, padding):
+    """TensorFlow / Keras MaxPooling2D on one axis of n positions -> (out, pad_before, pad_after):
+      'same'   out = ceil(n / stride), pad_total = max((out - 1) stride + k - n, 0), pad_before = floor(pad_total / 2)
+      'valid'  out = floor((n - k) / stride) + 1, no padding; n < k is an error.
+    THE host statement of the rule (csrc/deeplab.hip::pool_tf_dims is the device's)."""
+    n, k, stride = int(n), int(k), int(stride)
+    if n < 1 or k < 1 or stride < 1:
+        raise ValueError("pool of window %d, stride %d on %d positions" % (k, stride, n))
+    if padding == "same":
+        out = -(-n // stride)
+        total = max((out - 1) * stride + k - n, 0)
+        return out, total // 2, total - total // 2
+    if padding != "valid":
+        raise ValueError("padding must be 'same' or 'valid', got %r" % (padding,))
+    if n < k:
+        raise ValueError("a 'valid' pool of window %d does not fit %d positions" % (k, n))
+    return (n - k) // stride + 1, 0, 0
+
+
+def pooled_size(n, spec_rows):
+    """Size of an axis of n positions after the pools `spec_rows` = [(k, stride, 'same' | 'valid'), ...], in order."""
+    for k, stride, padding in spec_rows:
+        n = pool_axis(n, k, stride, padding)[0]
+    return n
+
+
+def normalize_pooling(spec, n_pools=3):
+    """A pooling spec as the CAM wrappers keep it: None, or n_pools rows (int k in {2, 3}, int stride in {1, 2} <= k,
+    'same' | 'valid').  Anything else is a ValueError naming the row."""
+    if spec is None:
+        return None
+    rows = [tuple(r) for r in spec]
+    if len(rows) != n_pools:
+        raise ValueError("pooling: %d rows, this architecture has %d pools" % (len(rows), n_pools))
+    out = []
+    for i, row in enumerate(rows):
+        if len(row) != 3:
+            raise ValueError("pooling row %d: (k, stride, 'same' | 'valid') expected, got %r" % (i, row))
+        k, stride, padding = row
+        if k != int(k) or stride != int(stride) or int(k) not in (2, 3) or int(stride) not in (1, 2) or int(stride) > int(k) \
+                or padding not in ("same", "valid"):
+            raise ValueError("pooling row %d: window 2 / 3, stride 1 / 2 (<= window), 'same' / 'valid'; got %r" % (i, row))
+        out.append((int(k), int(stride), padding))
+    return out
+
+
 class DeviceCAMBase:
     """Common plumbing: a lazily created wsc_ctx + wsc_net, numpy/torch in, same kind out."""
 
     arch = None
+    pooling = None  # the fixed architecture's MaxPool2d(2, 2); vgg16_cam / m7_cam: set_pooling
     # the fp32-class mode: the reference's arithmetic is fp32 and the package is a drop-in (PREC_F16 / PREC_BF16: fast 16-bit
     # modes, 1.5e-2 / 8e-2 on the normalised CAM maps -- args.cam_precision or the constructor's `precision`)
     precision = _lib.PREC_F16X3
@@ -55,6 +102,14 @@ class DeviceCAMBase:
             self._net.close()
             self._net = None
 
+    def _with_pool_spec(self, sd):
+        """`sd`, plus the `pool_spec` tensor of include/wsscam.h when a pooling spec is set."""
+        if self.pooling is None:
+            return sd
+        sd = dict(sd)
+        sd["pool_spec"] = np.array([[k, s, 1 if p == "same" else 0] for k, s, p in self.pooling], dtype=np.float32)
+        return sd
+
     def _ensure_net(self):
         if self._net is None:
             if self._sd is None:
@@ -66,7 +121,7 @@ class DeviceCAMBase:
         return self._net
 
     def _extra_tensors(self, sd):
-        return sd
+        return self._with_pool_spec(sd)
 
     @property
     def ctx(self):
@@ -92,7 +147,7 @@ class DeviceCAMBase:
         if key not in cache:
             if self._ctx is None:
                 self._ctx = _lib.Context(self._device)
-            sd = dict(self._sd)
+            sd = dict(self._with_pool_spec(self._sd))
             affine = last_bn_affine(sd, self.root) if pre_bn and getattr(self, "root", None) in PLAIN_CFG else None
             hw, hb = pre_bn_head(w, affine)
             sd["gradcam_weights"] = np.ascontiguousarray(hw, dtype=np.float32)

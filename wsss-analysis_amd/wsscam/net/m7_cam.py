@@ -9,7 +9,7 @@ import numpy as np
 
 from .. import _lib
 from . import vgg16_cam
-from .common import grad_cam_alpha, last_bn_affine
+from .common import grad_cam_alpha, last_bn_affine, pooled_size
 
 
 class CAM(vgg16_cam.CAM):
@@ -17,19 +17,22 @@ class CAM(vgg16_cam.CAM):
     root = "m7"
     keras_input_size = 224  # 02_cues/demo.py:60-66, 03b_irn/func_sample.py:151-156
 
-    def __init__(self, model_dir=None, dataset="voc12", tag="", num_classes=20, use_cls=None, precision=None):
+    def __init__(self, model_dir=None, dataset="voc12", tag="", num_classes=20, use_cls=None, precision=None, *, pooling=None):
+        # pooling: three rows -- the two pools of the stack, then layer3_p2 of the classifier branch (vgg16_cam's docstring)
         if dataset in ("adp_morph", "adp_func") and "X1.7" in tag:
             num_classes = 51  # m7_cam.py:16-17: the X1.7 models score all 51 ADP classes, filtered to 31 afterwards
-        super().__init__(model_dir, dataset, tag, num_classes, use_cls, precision)
+        super().__init__(model_dir, dataset, tag, num_classes, use_cls, precision, pooling=pooling)
 
     def _has_batchnorm(self):
         return True  # m7_cam.py:18: m7.m7(..., batchnorm=True) for every dataset (only vgg16_cam switches it off for ADP)
 
     def _extra_tensors(self, sd):
+        sd = self._with_pool_spec(sd)
         if "gradcam_weights" in sd:
             return sd
         sd = dict(sd)
-        h = self.keras_input_size // 4  # two 2x2 pools before the final feature map (net/m7.py:41)
+        # two pools before the final feature map (net/m7.py:41): 2x2 / 2, or the first two rows of the spec
+        h = self.keras_input_size // 4 if self.pooling is None else pooled_size(self.keras_input_size, self.pooling[:2])
         affine = last_bn_affine(sd, self.root)
         alpha = grad_cam_alpha(sd["m7.classifier.0.weight"][:self.num_classes], h, h, "max",
                                bn_scale=None if affine is None else affine[0])

@@ -2,11 +2,15 @@
 net/vgg16.py:44 + common_cnn.make_layers :128-141.  Weights: a torch-style state_dict with keys
 `vgg16.layer<L>.<idx>.{weight,bias,...}`, `vgg16.classifier.0.{weight,bias}` and `thresholds`
 (what common_cnn._load_pretrained leaves in the module after transplanting the Keras .h5/.mat,
-common_cnn.py:25-82)."""
+common_cnn.py:25-82).
+
+`pooling`: the geometry of the three MaxPooling2D layers when it is not the torch port's MaxPool2d(2, 2) -- a list of
+(k, stride, 'same' | 'valid') in the order the pools occur, as keras_store.read_architecture takes it from a session's
+architecture file; None is the fixed architecture."""
 import numpy as np
 
 from .. import _lib
-from .common import DeviceCAMBase
+from .common import DeviceCAMBase, normalize_pooling
 
 ADP_INDS_X17 = [2, 3, 4, 6, 7, 8, 9, 12, 13, 14, 16, 17, 18, 21, 22, 23, 25, 26, 28, 29, 30, 32, 33, 35, 37, 38, 40,
                 45, 48, 49, 50]  # common_cam.py:26-29
@@ -16,8 +20,9 @@ class CAM(DeviceCAMBase):
     arch = _lib.ARCH_VGG16_CAM
     root = "vgg16"
 
-    def __init__(self, model_dir=None, dataset="voc12", tag="", num_classes=20, use_cls=None, precision=None):
+    def __init__(self, model_dir=None, dataset="voc12", tag="", num_classes=20, use_cls=None, precision=None, *, pooling=None):
         super().__init__(num_classes, precision)
+        self.pooling = normalize_pooling(pooling)
         self.model_dir = model_dir
         self.dataset = dataset
         self.tag = tag
@@ -29,6 +34,14 @@ class CAM(DeviceCAMBase):
 
     def _has_batchnorm(self):
         return self.dataset not in ("adp_morph", "adp_func")  # vgg16_cam.py:16-19: the ADP VGG16 models carry no BatchNorm
+
+    def set_pooling(self, spec):
+        """The pools' geometry (see the module docstring); the packed nets built for the previous one are released."""
+        self.pooling = normalize_pooling(spec)
+        self._release_net()
+        for net in self.__dict__.pop("_gradcam_nets", {}).values():
+            net.close()
+        return self
 
     def _load_pretrained(self, model_dir, tag):
         """CommonCNN._load_pretrained (common_cnn.py:25-41): Keras <tag>.h5 + <tag>.mat under <model_dir>/<tag>/.
