@@ -299,8 +299,8 @@ int wsc_conv2d_nchw_dil(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H,
 
 /* ---- SEC / DSRG segmentation network (03a_sec-dsrg) ----------------------- */
 
-/* The DeepLab-VGG16 forward pass of SEC / DSRG at drop_prob = 0 (every non-training phase; the losses, the optimiser and the
- * training loop are out of scope).  A net created with WSC_ARCH_DEEPLAB_LFOV / _ASPP takes its weights under the reference's
+/* The DeepLab-VGG16 forward pass of SEC / DSRG at drop_prob = 0 (every non-training phase; the optimiser and the training loop
+ * are out of scope, the losses and their gradient into fc8 are wsc_seg_loss).  A net created with WSC_ARCH_DEEPLAB_LFOV / _ASPP takes its weights under the reference's
  * layer names (get_weights_and_bias, DSRG.py:379-425): `conv1_1` ... `conv5_3`, and `fc6`, `fc7`, `fc8` (LFOV) or `fc6_1` ...
  * `fc8_4` (ASPP); each as `<layer>.w` in TensorFlow's HWIO order [kh][kw][Cin][Cout] and `<layer>.b` [Cout].  Channel widths
  * are read from the tensors (multiples of 64; fc8 has num_classes outputs).  A missing or mis-shaped tensor is WSC_ERR_SHAPE
@@ -498,6 +498,63 @@ int wsc_ir_label_combine(wsc_ctx *ctx, const int32_t *fg_pred_dev, const int32_t
  * LDS; the reference's maps are 41 x 41, model.py:35): WSC_ERR_INVALID beyond, before any launch. */
 int wsc_dsrg_seed_grow(wsc_ctx *ctx, const float *tags_dev, const float *cues_dev, const float *probs_dev,
                        int B, int H, int W, int C, float th_f, float th_b, float *out_dev);
+
+/* The loss head of the training graph and the gradient it sends into fc8 (03a_sec-dsrg/SEC.py:363-465 getloss, get_seed_loss,
+ * get_expand_loss, get_constrain_loss; DSRG.py:459-518 getloss, get_balanced_seed_loss, get_constrain_loss).  `crf` and the cues
+ * come out of tf.py_func in the reference graph, so they are constants to the gradient: no backward pass through the CRF or the
+ * region growing.  Out of scope: the backward pass of the convolution stack, the optimiser, the weight decay term, dropout.
+ *   prob_dev   float32 [B][H][W][C]  fc8-softmax p (wsc_net_forward_seg), > 0;  n = H W
+ *   crf_dev    float32 [B][H][W][C]  the CRF layer's log-probabilities (wsc_seg_crf_logprob);  q = exp(crf)
+ *   cues_dev   float32 [B][H][W][C]  0/1 (DSRG: the grown cues of wsc_dsrg_seed_grow)
+ *   labels_dev float32 [B][C]        SEC only (NULL for DSRG), class 0 = background;  stat_bc = labels[b][c] > 0 for c >= 1
+ * WSC_SEG_LOSS_SEC:
+ *   seed      = -(1/B) sum_b [sum cues log p]_b / max([sum cues]_b, 1e-5)
+ *   constrain = (1/(B n)) sum q log(q / p)
+ *   mean_bc   = sum_i sorted_i w_i / Z over the ascending sort of map (b, c), w = w_fg_host, Z = z_fg for c >= 1 (q_fg = 0.996),
+ *               w_bg_host, z_bg for c = 0 (q_bg = 0.999);  max_bc = the map's maximum
+ *   loss_1    = -(1/B) sum_b sum_c stat log(mean) / max(sum_c stat, 1e-5)
+ *   loss_2    = -(1/B) sum_b sum_c (1 - stat) log(1 - max) / max(sum_c (1 - stat), 1e-5)
+ *   loss_3    = -(1/B) sum_b log(mean_b0);   expand = loss_1 + loss_2 + loss_3;   norm = seed + expand + constrain
+ *   The weight tables [n] are the reference's constants as TensorFlow sees them: float32(w64) and float32(np.sum(w64)) of
+ *   w64 = [q ** i for i in range(n - 1, -1, -1)].  The caller forms them (secdsrg.rank_weights); they are copied during the call.
+ * WSC_SEG_LOSS_DSRG (labels, weight tables and sums are not read):
+ *   seed_bg   = -(1/B) sum_b [sum cues_0 log p_0]_b / ([sum cues_0]_b + 1e-8);  seed_fg likewise over the channels 1 .. C-1
+ *   seed      = seed_bg + seed_fg;   constrain = (1/(B n)) sum q log(q / (p + 1e-8) + 1e-8);   norm = seed + constrain
+ * loss_dev double [WSC_SEG_LOSS_N], indexed by the WSC_SEG_LOSS_* slots below; a slot the method lacks is 0.
+ * Gradient of norm, both optional (NULL: not computed, the buffer is not touched), float32 [B][H][W][C], every element written:
+ *   grad_prob_dev  g_p = d norm / d p.  Seed and constrain terms per element; loss_1 / loss_3 give pixel x of map (b, c)
+ *                  -(1/B) coeff_bc (w[rank(x)] / Z) / mean_bc; loss_2 gives +(1/B) coeff_bc / (1 - max_bc) to the maximum.
+ *   grad_fc8_dev   g_z = s (g_p - sum_j g_p,j s_j) / (1 + C min_prob) with s = p (1 + C min_prob) - min_prob, the chain rule
+ *                  through build_sp_softmax (SEC.py:246-249): d norm / d fc8.  DSRG's fc8 is the sum of fc8_1 .. fc8_4, so the
+ *                  same array is the gradient of each of them.
+ *   Both may be requested in one call.  They must not overlap each other or any input.
+ * TIE RULES: among equal values of a map the lower pixel index gets the lower rank (np.argsort(kind='stable')); the loss values
+ * do not depend on it, the placement of the rank weights inside a tied group does.  The share of the maximum is split EQUALLY
+ * among the pixels that hold it (TensorFlow's reduce_max gradient).  -0 counts as +0; NaN is out of contract.
+ * ARITHMETIC: inputs are float32; every log, exp, product and sum runs in double and each output is rounded once.  Every sum
+ * has one fixed order and there are no floating-point atomics: two calls on the same input give the same bits.  TensorFlow
+ * evaluates the same graph in float32 with its own summation order: parity with it is UNPINNED.
+ * Limits, checked before any launch (WSC_ERR_INVALID, the text names the argument): H * W <= 8192 (a map is sorted in LDS),
+ * 2 <= C <= 32, 1 <= B <= 65535, 0 <= min_prob < 1; no NULL among prob_dev, crf_dev, cues_dev, loss_dev and, for SEC,
+ * labels_dev and the weight tables.  Asynchronous on the ctx stream. */
+#define WSC_SEG_LOSS_SEC 0
+#define WSC_SEG_LOSS_DSRG 1
+enum {
+    WSC_SEG_LOSS_SEED = 0,  /* self.loss["seed"] */
+    WSC_SEG_LOSS_CONSTRAIN, /* self.loss["constrain"] */
+    WSC_SEG_LOSS_EXPAND,    /* self.loss["expand"] (SEC) */
+    WSC_SEG_LOSS_1,         /* SEC self.loss_1 */
+    WSC_SEG_LOSS_2,         /* SEC self.loss_2 */
+    WSC_SEG_LOSS_3,         /* SEC self.loss_3 */
+    WSC_SEG_LOSS_NORM,      /* getloss's return value */
+    WSC_SEG_LOSS_SEED_BG,   /* DSRG loss_bg */
+    WSC_SEG_LOSS_SEED_FG,   /* DSRG loss_fg */
+    WSC_SEG_LOSS_N
+};
+int wsc_seg_loss(wsc_ctx *ctx, int method /* WSC_SEG_LOSS_SEC | WSC_SEG_LOSS_DSRG */, const float *prob_dev, const float *crf_dev,
+                 const float *cues_dev, const float *labels_dev /* [B][C]; SEC only, NULL for DSRG */, int B, int H, int W, int C,
+                 float min_prob, const float *w_fg_host, float z_fg, const float *w_bg_host, float z_bg /* [H*W] each; SEC only */,
+                 double *loss_dev /* [WSC_SEG_LOSS_N] */, float *grad_prob_dev /* or NULL */, float *grad_fc8_dev /* or NULL */);
 
 /* ---- 02_cues: the localization seeds SEC / DSRG train on (02_cues/utilities.py:183-278 get_localization_cues /
  * get_localization_cues_sec, 02_cues/adp_cues.py:304-339 update_cues; consumer 03a_sec-dsrg/model.py:238-246) ---- */

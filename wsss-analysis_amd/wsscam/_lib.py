@@ -135,6 +135,7 @@ _SIGNATURES = {
     "wsc_label_unary_from_cam": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     "wsc_ir_label_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "wsc_dsrg_seed_grow": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
+    "wsc_seg_loss": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _f, _vp, _f, _vp, _vp, _vp]),
     "wsc_cue_maps": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "wsc_cue_seeds": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _d, _vp, _vp]),
     "wsc_seg_unary_nhwc": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -956,6 +957,27 @@ def dsrg_seed_grow(ctx, tags_dev, cues_dev, probs_dev, B, H, W, C, out_dev, th_f
     """wsc_dsrg_seed_grow: DSRG seeded region growing of a batch (NHWC float32); out_dev may be cues_dev."""
     check(ctx._lib.wsc_dsrg_seed_grow(ctx.h, _ptr(tags_dev), _ptr(cues_dev), _ptr(probs_dev), int(B), int(H), int(W), int(C),
                                       float(th_f), float(th_b), _ptr(out_dev)))
+
+
+SEG_LOSS_SEC, SEG_LOSS_DSRG = 0, 1
+# slots of wsc_seg_loss's loss_dev (include/wsscam.h WSC_SEG_LOSS_*), under the reference's names
+SEG_LOSS_SLOTS = ("seed", "constrain", "expand", "loss_1", "loss_2", "loss_3", "norm", "seed_bg", "seed_fg")
+
+
+def seg_loss(ctx, method, prob_dev, crf_dev, cues_dev, labels_dev, B, H, W, C, min_prob, w_fg, z_fg, w_bg, z_bg, loss_dev,
+             grad_prob_dev=None, grad_fc8_dev=None):
+    """wsc_seg_loss: the SEC / DSRG losses (float64 [len(SEG_LOSS_SLOTS)] in loss_dev) and, where a buffer is given, d norm / d p and
+    d norm / d fc8 (float32 NHWC).  w_fg / w_bg: float32 host tables [H * W] (SEC; None for DSRG); asynchronous."""
+    tabs = []
+    for w in (w_fg, w_bg):
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != (int(H) * int(W),):
+                raise ValueError("seg_loss: a weight table of shape %r for %d x %d maps" % (w.shape, H, W))
+        tabs.append(w)
+    check(ctx._lib.wsc_seg_loss(ctx.h, int(method), _ptr(prob_dev), _ptr(crf_dev), _ptr(cues_dev), _ptr(labels_dev), int(B), int(H),
+                                int(W), int(C), float(min_prob), _ptr(tabs[0]), float(z_fg), _ptr(tabs[1]), float(z_bg),
+                                _ptr(loss_dev), _ptr(grad_prob_dev), _ptr(grad_fc8_dev)))
 
 
 def cue_maps(ctx, cams_nhwc_dev, B, h, w, C_all, chan, gate_dev, S, out_dev):

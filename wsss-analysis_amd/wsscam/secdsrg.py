@@ -9,9 +9,12 @@
                          SegEvaluator.update take and return it
     Predictor            Model.predict's loop (model.py:542-586): decoded images in, confusion matrix out, nothing in between
                          on the host
+    SegLoss              getloss() (SEC.py:363-465, DSRG.py:459-518) and the gradient it sends into fc8 (wsc_seg_loss);
+                         rank_weights forms SEC's rank-pooling tables; SegNet.loss_step_dev is the non-backward half of one
+                         training step of Model.train at drop_prob = 0: forward, CRF layer, region growing, losses
 
-The losses, the optimiser and the training loop of SEC / DSRG are out of scope.  Nothing here imports
-TensorFlow: Model.predict runs on this module alone."""
+The backward pass of the convolution stack, the optimiser, the weight decay term, dropout and the training loop of SEC / DSRG are
+out of scope.  Nothing here imports TensorFlow: Model.predict runs on this module alone."""
 import numpy as np
 
 from . import _lib
@@ -113,6 +116,41 @@ def generate_seed_step(tags, cues, probs, ctx=None, th_f=0.5, th_b=0.7):
         buf.free()
 
 
+def generate_seed_step_dev(tags, cues, probs, ctx=None, th_f=0.5, th_b=0.7):
+    """generate_seed_step on device buffers: cues and probs are float32 DeviceMaps (B, H, W, C), tags a DeviceMaps (B, C) or a host
+    array as generate_seed_step takes it (uploaded once) -> a NEW DeviceMaps (B, H, W, C) with the grown cues, generate_seed_step's
+    bits (the same wsc_dsrg_seed_grow).  The inputs are not modified."""
+    ctx = ctx or cues.ctx
+    for name, a in (("cues", cues), ("probs", probs)):
+        if not isinstance(a, DeviceMaps) or a.dtype != np.float32 or len(a.shape) != 4:
+            raise ValueError("generate_seed_step_dev: %s must be a float32 DeviceMaps (B, H, W, C), got %r" % (name, getattr(a, "shape", type(a))))
+    if probs.shape != cues.shape:
+        raise ValueError("generate_seed_step_dev: cues %r and probs %r must both be (B, H, W, C)" % (cues.shape, probs.shape))
+    B, H, W, C = cues.shape
+    tags_dev = mine = None
+    if isinstance(tags, DeviceMaps):
+        if tags.dtype != np.float32 or tags.shape not in ((B, C), (B, 1, 1, C)):
+            raise ValueError("generate_seed_step_dev: tags %r %s must be float32 (B, C) for cues %r" % (tags.shape, tags.dtype, cues.shape))
+        tags_dev = tags
+    else:
+        tags_f = np.ascontiguousarray(tags, dtype=np.float32)
+        if tags_f.shape not in ((B, C), (B, 1, 1, C)):
+            raise ValueError("generate_seed_step_dev: tags %r must be (B, C) or (B, 1, 1, C) for cues %r" % (tags_f.shape, cues.shape))
+        tags_dev = mine = DeviceMaps.from_host(ctx, tags_f)
+    out = None
+    try:
+        out = DeviceMaps(ctx, cues.shape, np.float32)
+        _lib.dsrg_seed_grow(ctx, tags_dev.ptr, cues.ptr, probs.ptr, B, H, W, C, out.ptr, th_f=th_f, th_b=th_b)
+        return out
+    except Exception:
+        if out is not None:
+            out.free()
+        raise
+    finally:
+        if mine is not None:
+            mine.free()
+
+
 def crf_layer(featmap, image, crf_config, num_classes, min_prob=1e-4, ctx=None, return_q=False):
     """The dense-CRF layer of SEC / DSRG: lib.crf.crf_inference(image[i], crf_config, num_classes, featmap[i],
     use_log=True) for every image of the batch, then clamp at min_prob, renormalise over classes and take the log.
@@ -190,6 +228,103 @@ def crf_layer_dev(prob, x, img_mean, crf_config, num_classes, min_prob=1e-4, see
             crf.close()
         for d in bufs:
             d.free()
+
+
+# ---- the loss head: getloss() and d loss / d fc8 (SEC.py:363-465, DSRG.py:459-518) ---------------------------------------------
+SEC_Q_FG, SEC_Q_BG = 0.996, 0.999  # get_expand_loss's decay rates (SEC.py:413,420)
+
+
+def rank_weights(n, q):
+    """The global-weighted-rank-pooling constants of get_expand_loss (SEC.py:415-418) as TensorFlow sees them:
+    w64 = np.array([q ** i for i in range(n - 1, -1, -1)]) -> (float32(w64), float32(np.sum(w64)))."""
+    w64 = np.array([q ** i for i in range(int(n) - 1, -1, -1)])
+    return w64.astype(np.float32), np.float32(np.sum(w64))
+
+
+class SegLoss:
+    """getloss() of SEC / DSRG on the device, with the gradient of its value with respect to fc8-softmax or to the fc8 logits
+    (wsc_seg_loss; the formulas, the tie rules and the double arithmetic: include/wsscam.h).  `crf` and the cues are constants to
+    the gradient, as they are in the reference graph (both come out of tf.py_func).
+
+    loss = SegLoss("SEC" | "DSRG", num_classes, min_prob=1e-4, ctx=None)
+    losses, grad = loss(prob, crf, cues, labels=None, want_grad="fc8")
+      prob, crf, cues  (B, h, w, C): fc8-softmax, the CRF layer's log-probabilities, the 0/1 cues (DSRG: the grown ones) -- float32
+                       DeviceMaps, read in place, or host arrays, uploaded once
+      labels           (B, C) or (B, 1, 1, C) image labels, class 0 = background: SEC's expand loss needs them; DSRG ignores them
+      want_grad        "fc8": d norm / d fc8 (for DSRG the gradient of each of fc8_1 .. fc8_4);  "prob": d norm / d fc8-softmax;
+                       None: losses only
+      -> ({"seed", "constrain", "expand", "norm", "loss_1", "loss_2", "loss_3", "seed_bg", "seed_fg"} as Python floats -- the
+          reference's self.loss keys and getloss's value under "norm", as Model.train logs it; a part the method lacks is 0.0 --,
+          a new float32 DeviceMaps (B, h, w, C) or None)
+    The call downloads the nine loss values and nothing else.  SEC's weight tables are cached per h * w."""
+
+    def __init__(self, method, num_classes, min_prob=1e-4, ctx=None):
+        if method not in ("SEC", "DSRG"):
+            raise ValueError("SegLoss: method %r is neither 'SEC' nor 'DSRG'" % (method,))
+        self.method = method
+        self.C = int(num_classes)
+        if not 2 <= self.C <= 32:
+            raise ValueError("SegLoss: num_classes = %d (2 .. 32, class 0 is the background)" % self.C)
+        self.min_prob = float(min_prob)
+        self.ctx = ctx or default_context()
+        self._weights = {}  # n -> (w_fg, z_fg, w_bg, z_bg)
+
+    def weights(self, n):
+        if n not in self._weights:
+            self._weights[n] = rank_weights(n, SEC_Q_FG) + rank_weights(n, SEC_Q_BG)
+        return self._weights[n]
+
+    def _maps(self, name, a, shape, held):
+        """-> DeviceMaps of `shape` (None: any (B, h, w, C)); an upload of this call is appended to `held`"""
+        if isinstance(a, DeviceMaps):
+            if a.dtype != np.float32:
+                raise ValueError("SegLoss: %s is %s on the device, not float32" % (name, a.dtype))
+            got = a.shape
+        else:
+            a = np.asarray(a)
+            if a.dtype.kind not in "fiub":
+                raise ValueError("SegLoss: %s has dtype %s, not a real number type" % (name, a.dtype))
+            got = a.shape
+        if name == "labels" and got == (shape[0], 1, 1, shape[1]):
+            got = shape
+        if (shape is None and (len(got) != 4 or got[3] != self.C or 0 in got)) or (shape is not None and tuple(got) != tuple(shape)):
+            raise ValueError("SegLoss: %s has shape %r, expected %s" % (name, tuple(a.shape), "(B, h, w, %d)" % self.C if shape is None else (shape,)))
+        if isinstance(a, DeviceMaps):
+            return a
+        held.append(DeviceMaps.from_host(self.ctx, a, dtype=np.float32))
+        return held[-1]
+
+    def __call__(self, prob, crf, cues, labels=None, want_grad="fc8"):
+        if want_grad not in ("fc8", "prob", None):
+            raise ValueError("SegLoss: want_grad %r is not 'fc8', 'prob' or None" % (want_grad,))
+        sec = self.method == "SEC"
+        if sec and labels is None:
+            raise ValueError("SegLoss: labels is None: SEC's expand loss reads the image labels")
+        ctx, held, grad = self.ctx, [], None
+        try:
+            p = self._maps("prob", prob, None, held)
+            B, h, w, C = p.shape
+            q = self._maps("crf", crf, p.shape, held)
+            cu = self._maps("cues", cues, p.shape, held)
+            lab = self._maps("labels", labels, (B, C), held) if sec else None
+            w_fg, z_fg, w_bg, z_bg = self.weights(h * w) if sec else (None, 0.0, None, 0.0)
+            loss_dev = DeviceMaps(ctx, (len(_lib.SEG_LOSS_SLOTS),), np.float64)
+            held.append(loss_dev)
+            if want_grad is not None:
+                grad = DeviceMaps(ctx, p.shape, np.float32)
+            _lib.seg_loss(ctx, _lib.SEG_LOSS_SEC if sec else _lib.SEG_LOSS_DSRG, p.ptr, q.ptr, cu.ptr, lab.ptr if sec else None, B, h, w,
+                          C, self.min_prob, w_fg, z_fg, w_bg, z_bg, loss_dev.ptr,
+                          grad_prob_dev=grad.ptr if want_grad == "prob" else None,
+                          grad_fc8_dev=grad.ptr if want_grad == "fc8" else None)
+            values = loss_dev.to_host()
+            return {k: float(v) for k, v in zip(_lib.SEG_LOSS_SLOTS, values)}, grad
+        except Exception:
+            if grad is not None:
+                grad.free()
+            raise
+        finally:
+            for d in held:
+                d.free()
 
 
 # ---- the prediction tail: eval_miou with is_eval=True (model.py:665-719, called from predict :542-586) -------------------------
@@ -655,6 +790,52 @@ class SegNet:
                 return self.resize_dev(out, xd.shape[1:3] if size is None else size)
         finally:
             if mine:
+                xd.free()
+
+    def loss_step_dev(self, x, cues, labels_or_tags, img_mean, crf_config_train, seed_size=None, want_grad="fc8"):
+        """The non-backward half of one training step of Model.train (model.py:464-511) at drop_prob = 0, without a host copy in
+        between: forward_dev -> crf_layer_dev -> (DSRG) wsc_dsrg_seed_grow on the device buffers -> SegLoss.
+
+        x (B, H, W, 3) the network's input, cues (B, h, w, C) the 0/1 seed cues at the map's size -- DeviceMaps, or host arrays that
+        are uploaded once; labels_or_tags (B, C) or (B, 1, 1, C): SEC's labels, DSRG's tags (one array in the reference, class 0 =
+        background); crf_config_train as crf_layer_dev takes it; seed_size None: the map's own size, the only one at which the
+        reference's losses are defined (its seed_size is the fc8 map's 41).
+        -> (losses, grad, new_cues) as SegLoss returns the first two; new_cues a float32 DeviceMaps (B, h, w, C): DSRG's grown cues
+        (a new buffer), for SEC the cues themselves on the device (the caller's DeviceMaps where one was given).  The caller frees
+        grad and new_cues; every other buffer of the step is freed on every path."""
+        ctx = self.ctx
+        xd, x_mine = self._on_device(x)
+        own, out = [], []  # buffers of the step, freed on every path; what the caller receives, freed on a failure only
+        try:
+            cd = cues
+            if not isinstance(cues, DeviceMaps):
+                cd = DeviceMaps.from_host(ctx, cues, dtype=np.float32)
+                own.append(cd)
+            prob = self.forward_dev(xd)
+            own.append(prob)
+            if cd.dtype != np.float32 or cd.shape != prob.shape:
+                raise ValueError("SegNet.loss_step_dev: cues %r %s must be float32 %r, the fc8 map's shape" % (cd.shape, cd.dtype, prob.shape))
+            crf = crf_layer_dev(prob, xd, img_mean, crf_config_train, self.C, min_prob=self.min_prob, seed_size=seed_size, ctx=ctx)
+            own.append(crf)
+            if self.method == "DSRG":
+                new_cues = generate_seed_step_dev(labels_or_tags, cd, prob, ctx=ctx)
+                out.append(new_cues)
+            else:
+                new_cues = cd
+                if own[0] is cd:  # uploaded here: it leaves with the result
+                    out.append(own.pop(0))
+            loss = SegLoss(self.method, self.C, min_prob=self.min_prob, ctx=ctx)
+            loss._weights = self.__dict__.setdefault("_rank_weights", {})  # SEC's tables, cached per map size on the net
+            losses, grad = loss(prob, crf, new_cues, labels=labels_or_tags if self.method == "SEC" else None, want_grad=want_grad)
+            return losses, grad, new_cues
+        except Exception:
+            for d in out:
+                d.free()
+            raise
+        finally:
+            for d in own:
+                d.free()
+            if x_mine:
                 xd.free()
 
     def preprocess_dev(self, images, img_mean, size=(321, 321), keep_images=False):
