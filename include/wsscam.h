@@ -344,6 +344,33 @@ int wsc_pool_same_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, in
  * its inputs, so the result is exact on values the planes hold.  y_dev [N][out_h][out_w][C], C a multiple of 8. */
 int wsc_pool_tf_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, int k, int stride, int same, int precision,
                      float *y_dev);
+/* The small kernels between the convolutions of the torch-side nets, one layer each, for the per-layer tests (float32 in and
+ * out; in the entries with a `precision` the values go through the activation planes of that precision as inside the net; the
+ * production launchers run unchanged; a bad argument is WSC_ERR_INVALID before anything is launched):
+ * wsc_group_norm_nhwc: one IRNet head after its 1 x 1 convolution -- nn.GroupNorm(G, C) (biased variance, eps inside the
+ *   square root) of x_dev [N][H][W][C] with gamma_host / beta_host [C], bilinear upsampling by `up` (1, 2 or 4,
+ *   align_corners = False), crop to Hd x Wd (<= H up x W up), ReLU if `relu`, written to channels [coff, coff + C) of y_dev
+ *   [N][Hd][Wd][Ctot].  y_dev is READ AND WRITTEN: it is staged into the planes first (the concat buffer as the other heads
+ *   left it), so its channels outside the slice come back as they went in, rounded to the precision.  WSC_PREC_F32 needs C,
+ *   Ctot and coff to be multiples of 4.
+ * wsc_maxpool_nhwc: nn.MaxPool2d(k, stride, pad) on NHWC, out = floor((in + 2 pad - k) / stride) + 1 per axis, 2 pad <= k (so
+ *   that every window has a tap; padding never wins the maximum), C a multiple of 8.
+ * wsc_gap_linear_sigmoid: the classifier branch, score_dev [B][C] = sigmoid(bias + W . pool(feat[sample_stride b])) with
+ *   feat_dev [B sample_stride][|hw|][F], the pool the mean over the |hw| positions, or their maximum when hw < 0 (the M7 net);
+ *   w_host [C][F], bias_host [C] or NULL; sample_stride 1 or 2 (2: sample 0 of every [image, flipped image] pair).
+ * wsc_cam_flip_add: cam_dev [B][C][h][w] = relu(head[2b]) + relu(head[2b + 1]) flipped along w, head_dev [2B][h][w][Cs] NHWC of
+ *   which the first C channels are read.
+ * wsc_irn_edge_finish: the end of EdgeDisplacement.forward: edge_dev [B][fh][fw] = sigmoid(e[2b] / 2 + flip(e[2b + 1]) / 2) with
+ *   e_dev [2B][He][We] cropped to fh x fw BEFORE the flip, dp_dev [B][2][fh][fw] = d[2b] - (ms0, ms1) with d_dev [2B][Hd][Wd][2]. */
+int wsc_group_norm_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, const float *gamma_host, const float *beta_host,
+                        int G, float eps, int up, int relu, int Hd, int Wd, int Ctot, int coff, int precision, float *y_dev);
+int wsc_maxpool_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, int k, int stride, int pad, int precision,
+                     float *y_dev);
+int wsc_gap_linear_sigmoid(wsc_ctx *ctx, const float *feat_dev, int B, int hw, int F, const float *w_host, const float *bias_host, int C,
+                           int sample_stride, int precision, float *score_dev);
+int wsc_cam_flip_add(wsc_ctx *ctx, const float *head_dev, int B, int h, int w, int C, int Cs, float *cam_dev);
+int wsc_irn_edge_finish(wsc_ctx *ctx, const float *e_dev, int He, int We, const float *d_dev, int Hd, int Wd, int B, int fh, int fw,
+                        float ms0, float ms1, float *edge_dev, float *dp_dev);
 int wsc_fc8_softmax(wsc_ctx *ctx, const float *const *fc8_dev, int n_in, long long M, int C, float min_prob, float *sum_dev,
                     float *prob_dev);
 

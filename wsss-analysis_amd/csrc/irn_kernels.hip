@@ -111,6 +111,20 @@ struct GnApplyArgs {
     int N, H, W, C, G, up, relu, Hd, Wd, Ctot, coff, fmt, split;
 };
 
+// The arithmetic of the four apply kernels below, spelled once with explicit fused operations: the file is compiled with the
+// default contraction, under which the compiler fused `hy * top + ly * bot` in one kernel and not in another (and in two of the
+// four lanes of gn_apply_f32_kernel).  With these every element of every kernel takes the same roundings -- "same bits" in
+// the kernels' comments means exactly that, and tests/test_gpu_layers.py holds the scalar and the vector kernel to it.
+// (bilerp.h and hsn.hip spell their taps the same way.)
+__device__ __forceinline__ float gn_lerp(float hy, float ly, float hx, float lx, float v00, float v01, float v10, float v11) {
+    const float top = __builtin_fmaf(hx, v00, lx * v01);
+    const float bot = __builtin_fmaf(hx, v10, lx * v11);
+    return __builtin_fmaf(hy, top, ly * bot);
+}
+__device__ __forceinline__ float gn_affine(float v, float2 st, float gamma, float beta) {
+    return __builtin_fmaf((v - st.x) * st.y, gamma, beta);
+}
+
 __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
     const long long total = (long long)a.N * a.Hd * a.Wd * a.C;
     const int Cg = a.C / a.G;
@@ -138,10 +152,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
             const float hy = 1.f - ly, hx = 1.f - lx;
             const float v00 = xn[((long long)y0 * a.W + x0) * a.C], v01 = xn[((long long)y0 * a.W + x1) * a.C];
             const float v10 = xn[((long long)y1 * a.W + x0) * a.C], v11 = xn[((long long)y1 * a.W + x1) * a.C];
-            v = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+            v = gn_lerp(hy, ly, hx, lx, v00, v01, v10, v11);
         }
         const float2 st = a.stats[n * a.G + c / Cg];
-        v = (v - st.x) * st.y * a.gamma[c] + a.beta[c];
+        v = gn_affine(v, st, a.gamma[c], a.beta[c]);
         if (a.relu) v = fmaxf(v, 0.f);
         const long long o = (((long long)n * a.Hd + ho) * a.Wd + wo) * a.Ctot + a.coff + c;
         const bf16_t h = f32_to_h16(v, a.fmt);
@@ -193,14 +207,14 @@ __global__ __launch_bounds__(256) void gn_apply8_kernel(GnApplyArgs a) {
                 dst[k][4] = hi4.x; dst[k][5] = hi4.y; dst[k][6] = hi4.z; dst[k][7] = hi4.w;
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = hy * (hx * t00[j] + lx * t01[j]) + ly * (hx * t10[j] + lx * t11[j]);
+            for (int j = 0; j < 8; ++j) v[j] = gn_lerp(hy, ly, hx, lx, t00[j], t01[j], t10[j], t11[j]);
         }
         uint16_t hh[8], ll[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int c = c0 + j;
             const float2 st = a.stats[n * a.G + c / Cg];
-            float r = (v[j] - st.x) * st.y * a.gamma[c] + a.beta[c];
+            float r = gn_affine(v[j], st, a.gamma[c], a.beta[c]);
             if (a.relu) r = fmaxf(r, 0.f);
             hh[j] = f32_to_h16(r, a.fmt);
             ll[j] = a.split ? f32_to_h16(r - h16_to_f32(hh[j], a.fmt), a.fmt) : (uint16_t)0;
@@ -250,13 +264,13 @@ __global__ __launch_bounds__(256) void gn_apply_f32_kernel(GnApplyArgs a) {
             const f32x4_t v10 = *reinterpret_cast<const f32x4_t *>(xn + ((long long)y1 * a.W + x0) * a.C);
             const f32x4_t v11 = *reinterpret_cast<const f32x4_t *>(xn + ((long long)y1 * a.W + x1) * a.C);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = hy * (hx * v00[j] + lx * v01[j]) + ly * (hx * v10[j] + lx * v11[j]);
+            for (int j = 0; j < 4; ++j) v[j] = gn_lerp(hy, ly, hx, lx, v00[j], v01[j], v10[j], v11[j]);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int c = c0 + j;
             const float2 st = a.stats[n * a.G + c / Cg];
-            float r = (v[j] - st.x) * st.y * a.gamma[c] + a.beta[c];
+            float r = gn_affine(v[j], st, a.gamma[c], a.beta[c]);
             if (a.relu) r = fmaxf(r, 0.f);
             v[j] = r;
         }

@@ -1322,4 +1322,98 @@ int wsc_conv2d_nchw_dil(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H,
     return st;
 }
 
+// ---- single layers of the nets for the per-layer tests (tests/test_gpu_layers.py): fp32 in and out, the values staged into an
+// activation of `precision` with the layout change of the entries above (one "pixel" per row: the layout stays, the values take
+// the planes), then the PRODUCTION launcher, unchanged.  Every argument is checked before anything is launched.
+int wsc_group_norm_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, const float *gamma_host, const float *beta_host,
+                        int G, float eps, int up, int relu, int Hd, int Wd, int Ctot, int coff, int precision, float *y_dev) {
+    WSC_CHECK(ctx && x_dev && gamma_host && beta_host && y_dev, WSC_ERR_INVALID, "wsc_group_norm_nhwc: null argument");
+    wsc_precision prec;
+    WSC_TRY(decode_precision(precision, &prec));
+    WSC_CHECK(N > 0 && H > 0 && W > 0 && C > 0 && G > 0 && C % G == 0, WSC_ERR_INVALID,
+              "wsc_group_norm_nhwc: %d x %d x %d x %d in %d groups", N, H, W, C, G);
+    WSC_CHECK(up == 1 || up == 2 || up == 4, WSC_ERR_INVALID, "wsc_group_norm_nhwc: upsample factor %d (1, 2 or 4)", up);
+    WSC_CHECK(Hd >= 1 && Wd >= 1 && Hd <= H * up && Wd <= W * up, WSC_ERR_INVALID,
+              "wsc_group_norm_nhwc: crop %d x %d of a %d x %d map", Hd, Wd, H * up, W * up);
+    WSC_CHECK(coff >= 0 && Ctot >= 1 && coff <= Ctot - C, WSC_ERR_INVALID, "wsc_group_norm_nhwc: channels [%d, %d + %d) of %d", coff, coff, C,
+              Ctot);
+    WSC_CHECK(prec != WSC_PREC_F32 || (C % 4 == 0 && Ctot % 4 == 0 && coff % 4 == 0 && ((uintptr_t)x_dev & 15) == 0), WSC_ERR_INVALID,
+              "wsc_group_norm_nhwc (fp32): %d of %d channels at %d are not 16-byte groups", C, Ctot, coff);
+    WSC_HIP(hipSetDevice(ctx->device));
+    const size_t out_e = (size_t)N * Hd * Wd * Ctot;
+    const size_t part_b = align_up(group_norm_partial_bytes(N, H, W, G), 256), stats_b = align_up(sizeof(float) * 2 * N * G, 256),
+                 vec_b = align_up(sizeof(float) * C, 256);
+    void *ws;
+    WSC_TRY(wsc_ctx_workspace(ctx, act_bytes(out_e, prec) + part_b + stats_b + 2 * vec_b, &ws));
+    char *p = (char *)ws;
+    const Act yo = act_carve(p, out_e, prec);
+    void *part = p, *stats = p + part_b;
+    float *gamma = (float *)(p + part_b + stats_b), *beta = (float *)(p + part_b + stats_b + vec_b);
+    WSC_TRY(wsc_ctx_upload_small(ctx, gamma, gamma_host, sizeof(float) * C));
+    WSC_TRY(wsc_ctx_upload_small(ctx, beta, beta_host, sizeof(float) * C));
+    WSC_TRY(launch_nchw_to_nhwc(ctx, y_dev, N * Hd * Wd, Ctot, 1, yo)); // (what the other heads of the concat buffer wrote)
+    WSC_TRY(launch_group_norm_stats(ctx, x_dev, N, H, W, C, G, eps, part, stats));
+    WSC_TRY(launch_group_norm_apply(ctx, x_dev, stats, gamma, beta, N, H, W, C, G, up, relu, yo, Hd, Wd, Ctot, coff));
+    return launch_act_to_f32(ctx, yo, out_e, y_dev);
+}
+
+int wsc_maxpool_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, int k, int stride, int pad, int precision,
+                     float *y_dev) {
+    WSC_CHECK(ctx && x_dev && y_dev, WSC_ERR_INVALID, "wsc_maxpool_nhwc: null argument");
+    wsc_precision prec;
+    WSC_TRY(decode_precision(precision, &prec));
+    WSC_CHECK(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, WSC_ERR_INVALID, "wsc_maxpool_nhwc: %d x %d x %d x %d (C a multiple of 8)", N,
+              H, W, C);
+    WSC_CHECK(k >= 1 && stride >= 1 && pad >= 0 && 2 * pad <= k, WSC_ERR_INVALID,
+              "wsc_maxpool_nhwc: window %d stride %d padding %d (padding at most half the window)", k, stride, pad);
+    WSC_CHECK(H + 2 * pad >= k && W + 2 * pad >= k, WSC_ERR_INVALID, "wsc_maxpool_nhwc: a %d x %d map is smaller than the window %d", H, W, k);
+    WSC_HIP(hipSetDevice(ctx->device));
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    const size_t in_e = (size_t)N * H * W * C, out_e = (size_t)N * Ho * Wo * C;
+    void *ws;
+    WSC_TRY(wsc_ctx_workspace(ctx, act_bytes(in_e, prec) + act_bytes(out_e, prec), &ws));
+    char *p = (char *)ws;
+    const Act xi = act_carve(p, in_e, prec), yo = act_carve(p, out_e, prec);
+    WSC_TRY(launch_nchw_to_nhwc(ctx, x_dev, (int)((size_t)N * H * W), C, 1, xi));
+    WSC_TRY(launch_maxpool(ctx, xi, N, H, W, C, k, stride, pad, Ho, Wo, yo));
+    return launch_act_to_f32(ctx, yo, out_e, y_dev);
+}
+
+int wsc_gap_linear_sigmoid(wsc_ctx *ctx, const float *feat_dev, int B, int hw, int F, const float *w_host, const float *bias_host, int C,
+                           int sample_stride, int precision, float *score_dev) {
+    WSC_CHECK(ctx && feat_dev && w_host && score_dev, WSC_ERR_INVALID, "wsc_gap_linear_sigmoid: null argument");
+    wsc_precision prec;
+    WSC_TRY(decode_precision(precision, &prec));
+    WSC_CHECK(B > 0 && hw != 0 && hw > -(1 << 24) && hw < (1 << 24) && F > 0 && F <= 8192 && C > 0 && sample_stride >= 1 && sample_stride <= 2,
+              WSC_ERR_INVALID, "wsc_gap_linear_sigmoid: B=%d, %d positions, F=%d, C=%d, sample stride %d", B, hw, F, C, sample_stride);
+    WSC_HIP(hipSetDevice(ctx->device));
+    const int npix = hw < 0 ? -hw : hw;
+    const size_t in_e = (size_t)B * sample_stride * npix * F;
+    const size_t w_b = align_up(sizeof(float) * (size_t)C * F, 256), b_b = align_up(sizeof(float) * C, 256);
+    void *ws;
+    WSC_TRY(wsc_ctx_workspace(ctx, act_bytes(in_e, prec) + w_b + b_b, &ws));
+    char *p = (char *)ws;
+    const Act feat = act_carve(p, in_e, prec);
+    float *w = (float *)p, *bias = bias_host ? (float *)(p + w_b) : nullptr;
+    WSC_TRY(wsc_ctx_upload_small(ctx, w, w_host, sizeof(float) * (size_t)C * F));
+    if (bias) WSC_TRY(wsc_ctx_upload_small(ctx, bias, bias_host, sizeof(float) * C));
+    WSC_TRY(launch_nchw_to_nhwc(ctx, feat_dev, B * sample_stride * npix, F, 1, feat));
+    return launch_gap_linear_sigmoid(ctx, feat, B, hw, F, w, bias, C, score_dev, sample_stride);
+}
+
+int wsc_cam_flip_add(wsc_ctx *ctx, const float *head_dev, int B, int h, int w, int C, int Cs, float *cam_dev) {
+    WSC_CHECK(ctx && head_dev && cam_dev, WSC_ERR_INVALID, "wsc_cam_flip_add: null argument");
+    WSC_CHECK(B > 0 && h > 0 && w > 0 && C > 0 && C <= Cs, WSC_ERR_INVALID, "wsc_cam_flip_add: B=%d, %d x %d, %d of %d channels", B, h, w, C, Cs);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return launch_flip_add(ctx, head_dev, B, h, w, C, Cs, cam_dev);
+}
+
+int wsc_irn_edge_finish(wsc_ctx *ctx, const float *e_dev, int He, int We, const float *d_dev, int Hd, int Wd, int B, int fh, int fw,
+                        float ms0, float ms1, float *edge_dev, float *dp_dev) {
+    WSC_CHECK(ctx && e_dev && d_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_irn_edge_finish: null argument");
+    WSC_CHECK(B > 0 && fh > 0 && fw > 0, WSC_ERR_INVALID, "wsc_irn_edge_finish: B=%d, feature size %d x %d", B, fh, fw);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return launch_edge_finish(ctx, e_dev, He, We, d_dev, Hd, Wd, B, fh, fw, ms0, ms1, edge_dev, dp_dev); // (checks fh, fw against the maps)
+}
+
 } // extern "C"

@@ -119,6 +119,11 @@ _SIGNATURES = {
     "wsc_resize_bilinear_tf": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i]),
     "wsc_pool_same_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "wsc_pool_tf_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_group_norm_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _f, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_maxpool_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_gap_linear_sigmoid": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "wsc_cam_flip_add": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "wsc_irn_edge_finish": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     "wsc_fc8_softmax": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _f, _vp, _vp]),
     "wsc_cam_postprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wsc_cam_eval_confusion": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp]),
@@ -684,6 +689,61 @@ def pool_tf_nhwc(ctx, x_dev, N, H, W, C, k, stride, same, precision, y_dev=None)
     check(ctx._lib.wsc_pool_tf_nhwc(ctx.h, _ptr(x_dev), int(N), int(H), int(W), int(C), int(k), int(stride), int(same),
                                     int(precision), _ptr(y_dev)))
     return y_dev, (N, Ho, Wo, C)
+
+
+def group_norm_nhwc(ctx, x_dev, N, H, W, C, gamma, beta, G, eps, up, relu, Hd, Wd, Ctot, coff, precision, y_dev):
+    """One IRNet head after its convolution (wsc_group_norm_nhwc): GroupNorm(G, C) of float32 NHWC x_dev, bilinear x `up`, crop to
+    Hd x Wd, ReLU if `relu`, into channels [coff, coff + C) of y_dev float32 [N][Hd][Wd][Ctot] -- which is read first: its other
+    channels come back rounded to the precision.  gamma / beta: host arrays [C]."""
+    g = None if gamma is None else np.ascontiguousarray(gamma, dtype=np.float32)
+    b = None if beta is None else np.ascontiguousarray(beta, dtype=np.float32)
+    check(ctx._lib.wsc_group_norm_nhwc(ctx.h, _ptr(x_dev), int(N), int(H), int(W), int(C), _ptr(g), _ptr(b), int(G), float(eps), int(up),
+                                       int(bool(relu)), int(Hd), int(Wd), int(Ctot), int(coff), int(precision), _ptr(y_dev)))
+    return y_dev, (N, Hd, Wd, Ctot)
+
+
+def maxpool_nhwc(ctx, x_dev, N, H, W, C, k, stride, pad, precision, y_dev=None):
+    """nn.MaxPool2d(k, stride, pad) of the torch-side nets on float32 NHWC (wsc_maxpool_nhwc) -> (y_dev, (N, Ho, Wo, C))."""
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if y_dev is None:
+        y_dev = ctx.alloc(max(N * Ho * Wo * C, 1) * 4)
+    check(ctx._lib.wsc_maxpool_nhwc(ctx.h, _ptr(x_dev), int(N), int(H), int(W), int(C), int(k), int(stride), int(pad), int(precision),
+                                    _ptr(y_dev)))
+    return y_dev, (N, Ho, Wo, C)
+
+
+def gap_linear_sigmoid(ctx, feat_dev, B, hw, F, w, bias, sample_stride, precision, score_dev=None):
+    """The classifier branch (wsc_gap_linear_sigmoid): feat_dev float32 [B * sample_stride][|hw|][F] -> (score_dev, (B, C)), the
+    sigmoid of Linear(w [C][F], bias [C] or None) on the mean (hw > 0) or the maximum (hw < 0) over the positions."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    C = w.shape[0]
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    if score_dev is None:
+        score_dev = ctx.alloc(max(B * C, 1) * 4)
+    check(ctx._lib.wsc_gap_linear_sigmoid(ctx.h, _ptr(feat_dev), int(B), int(hw), int(F), _ptr(w), _ptr(b), int(C), int(sample_stride),
+                                          int(precision), _ptr(score_dev)))
+    return score_dev, (B, C)
+
+
+def cam_flip_add(ctx, head_dev, B, h, w, C, Cs, cam_dev=None):
+    """cam [B][C][h][w] = relu(head[2b]) + relu(head[2b + 1]).flip(-1) of float32 NHWC head_dev [2B][h][w][Cs] (wsc_cam_flip_add)."""
+    if cam_dev is None:
+        cam_dev = ctx.alloc(max(B * C * h * w, 1) * 4)
+    check(ctx._lib.wsc_cam_flip_add(ctx.h, _ptr(head_dev), int(B), int(h), int(w), int(C), int(Cs), _ptr(cam_dev)))
+    return cam_dev, (B, C, h, w)
+
+
+def irn_edge_finish(ctx, e_dev, He, We, d_dev, Hd, Wd, B, fh, fw, ms0, ms1, edge_dev=None, dp_dev=None):
+    """The end of EdgeDisplacement.forward (wsc_irn_edge_finish): e_dev [2B][He][We], d_dev [2B][Hd][Wd][2] ->
+    (edge_dev [B][fh][fw], dp_dev [B][2][fh][fw])."""
+    n = max(B * fh * fw, 1)
+    if edge_dev is None:
+        edge_dev = ctx.alloc(n * 4)
+    if dp_dev is None:
+        dp_dev = ctx.alloc(2 * n * 4)
+    check(ctx._lib.wsc_irn_edge_finish(ctx.h, _ptr(e_dev), int(He), int(We), _ptr(d_dev), int(Hd), int(Wd), int(B), int(fh), int(fw),
+                                       float(ms0), float(ms1), _ptr(edge_dev), _ptr(dp_dev)))
+    return edge_dev, dp_dev
 
 
 def fc8_softmax(ctx, fc8_devs, M, C, prob_dev, min_prob=1e-4, sum_dev=None):
