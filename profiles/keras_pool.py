@@ -1,10 +1,8 @@
-"""The TF / Keras max pool of a `pool_spec` (pool_tf_*_kernel<3>, wsc_pool_tf_nhwc at 3 x 3 / 2 SAME) against the 3 x 3 SAME max
-pool the DeepLab nets already had (pool_same_*_kernel, wsc_pool_same_nhwc, max at stride 2) on the same tensors, f16x3:
+"""The max pool of a `pool_spec` at 3 x 3 / 2 SAME (launch_pool of csrc/pool.hip, through wsc_pool_tf_nhwc) on two tensors, f16x3:
   pool1   64 samples x 321 x 321 x 64   the VGG16 stack's first-pool tensor at the bench batch (32 images, [orig, flip])
   pool3   64 samples x  81 x  81 x 256  its third
-Both are one-pass maps over the same bytes and give the same values (checked here before anything is timed).  The kernel time is
-the library's own per-class event timing (wsc_profile_*: the pool launch alone -- the entry's layout changes carry no timer),
-CALLS launches per figure, REPS figures per kernel, the two kernels alternating.
+The kernel time is the library's own per-class event timing (wsc_profile_*: the pool launch alone -- the entry's layout changes
+carry no timer), CALLS launches per figure, REPS figures per tensor.
 
 Then the VGG16 CAM stack at 321 x 321, 32 images, f16x3, with 3 x 3 / 2 SAME pools (41 x 41 maps) against the fixed architecture
 (2 x 2 / 2, 40 x 40): wsc_net_forward_cam between device events, alternating.
@@ -53,25 +51,18 @@ out = {"samples": N, "precision": "f16x3", "reps": REPS, "calls_per_rep": CALLS,
 for name, (H, W, C) in TENSORS.items():
     x_dev = fill(H, W, C, 7)
     Ho, Wo = -(-H // 2), -(-W // 2)
-    y_same, y_tf = ctx.alloc(N * Ho * Wo * C * 4), ctx.alloc(N * Ho * Wo * C * 4)
-    same = lambda: _lib.pool_same_nhwc(ctx, x_dev, N, H, W, C, False, 2, PREC, y_same)  # noqa: E731
+    y_tf = ctx.alloc(N * Ho * Wo * C * 4)
     tf = lambda: _lib.pool_tf_nhwc(ctx, x_dev, N, H, W, C, 3, 2, True, PREC, y_tf)  # noqa: E731
-    same(), tf()
-    a, b = ctx.to_host(y_same, (Ho * Wo * C,), np.float32), ctx.to_host(y_tf, (Ho * Wo * C,), np.float32)
-    assert np.array_equal(a, b) and a.min() < 0  # (sample 0; every sample holds the same values)
+    tf()
+    assert ctx.to_host(y_tf, (Ho * Wo * C,), np.float32).min() < 0  # (sample 0: signed values, the padding did not win)
     for _ in range(2):
-        pool_ms(same), pool_ms(tf)
-    t_same, t_tf = [], []
-    for _ in range(REPS):
-        t_same.append(pool_ms(same))
-        t_tf.append(pool_ms(tf))
+        pool_ms(tf)
+    t_tf = [pool_ms(tf) for _ in range(REPS)]
     planes = (N * H * W * C + N * Ho * Wo * C) * 4  # hi + lo, 2 bytes each, read + written
-    out["pools"][name] = {"shape": [N, H, W, C], "bytes": planes,
-                          "pool_same_ms": [round(v, 4) for v in t_same], "pool_tf_ms": [round(v, 4) for v in t_tf],
-                          "pool_same_median_ms": round(float(np.median(t_same)), 4), "pool_tf_median_ms": round(float(np.median(t_tf)), 4),
-                          "pool_same_spread_ms": round(max(t_same) - min(t_same), 4),
+    out["pools"][name] = {"shape": [N, H, W, C], "bytes": planes, "pool_tf_ms": [round(v, 4) for v in t_tf],
+                          "pool_tf_median_ms": round(float(np.median(t_tf)), 4), "pool_tf_spread_ms": round(max(t_tf) - min(t_tf), 4),
                           "pool_tf_TBps": round(planes / float(np.median(t_tf)) * 1e-9, 3)}
-    for buf in (x_dev, y_same, y_tf):
+    for buf in (x_dev, y_tf):
         buf.free()
 
 # the VGG16 CAM stack at the bench batch

@@ -1,4 +1,4 @@
-"""GPU: the MaxPooling2D geometry of a Keras-side session (`pool_spec`) -- the TF max pool kernel (csrc/deeplab.hip, through
+"""GPU: the MaxPooling2D geometry of a Keras-side session (`pool_spec`) -- the TF max pool (csrc/pool.hip, through
 wsc_pool_tf_nhwc), the VGG16 / M7 CAM nets built with a spec against the torch-CPU oracle tests/keras_arch_ref.py, the key's
 validation in wsc_net_create, and keras_store.load_model reading a session's architecture file.
 

@@ -1,6 +1,6 @@
 """GPU: the small kernels between the convolutions, one layer at a time against the float64 references of tests/layer_ref.py --
 the GroupNorm of the IRNet heads (csrc/irn_kernels.hip: two statistics kernels, four apply kernels), nn.MaxPool2d
-(csrc/misc_kernels.hip: four kernels), the classifier branch (gap + linear + sigmoid), flip-add and the IRNet edge finish.  The
+(csrc/pool.hip: four kernels, shared with the TF / Keras pools), the classifier branch (gap + linear + sigmoid), flip-add and the IRNet edge finish.  The
 entries (wsc_group_norm_nhwc, wsc_maxpool_nhwc, wsc_gap_linear_sigmoid, wsc_cam_flip_add, wsc_irn_edge_finish) stage float32 into
 the activation planes of a precision and run the production launchers unchanged.
 
@@ -24,16 +24,20 @@ def _prec_id(p):
 
 
 # ---- nn.MaxPool2d ---------------------------------------------------------------------------------------------------------------
-def _maxpool(ctx, x, k, stride, pad, prec):
+def _run_pool(ctx, x, entry, *args):
     N, H, W, C = x.shape
     x_dev = ctx.to_device(x)
     try:
-        y_dev, shp = _lib.maxpool_nhwc(ctx, x_dev, N, H, W, C, k, stride, pad, prec)
+        y_dev, shp = entry(ctx, x_dev, N, H, W, C, *args)
         y = ctx.to_host(y_dev, shp, np.float32)
         y_dev.free()
         return y
     finally:
         x_dev.free()
+
+
+def _maxpool(ctx, x, k, stride, pad, prec):
+    return _run_pool(ctx, x, _lib.maxpool_nhwc, k, stride, pad, prec)
 
 
 def _assert_pool_exact(ctx, x, k, stride, pad, prec):
@@ -52,8 +56,8 @@ POOL_CASES = [(3, 2, 1, 7, 9), (3, 2, 1, 8, 8), (3, 2, 1, 1, 1), (2, 2, 0, 2, 2)
 @pytest.mark.parametrize("C", [8, 72])
 @pytest.mark.parametrize("geom", POOL_CASES, ids=lambda g: "k%ds%dp%d-%dx%d" % g)
 def test_maxpool_exact(ctx, geom, C):
-    """Every precision (bf16 / bf16x3: maxpool_kernel; f16: maxpool_f16_kernel; f16x3: maxpool_f16x2_kernel; f32:
-    maxpool_f32_kernel) returns exactly the maximum of the values its planes hold: odd sizes whose last row / column is dropped
+    """Every precision (bf16 / bf16x3: pool_h16_kernel; f16: maxpool_f16_kernel; f16x3: maxpool_f16x2_kernel; f32:
+    pool_f32_kernel) returns exactly the maximum of the values its planes hold: odd sizes whose last row / column is dropped
     (2 x 2 / 2) or is padding (3 x 3 / 2 pad 1), a 1 x 1 map that is all border, signed values."""
     k, stride, pad, H, W = geom
     rng = np.random.default_rng(H * 1000 + W * 10 + k + C)
@@ -92,14 +96,79 @@ def test_maxpool_lo_plane_decides(ctx, prec):
 
 @pytest.mark.parametrize("prec", [_lib.PREC_F16, _lib.PREC_F16X3], ids=_prec_id)
 def test_maxpool_many_rows_takes_generic_kernel(ctx, prec):
-    """N * Ho = 65536 > 65535: the IEEE-half modes leave their one-block-row-per-output-row kernels for maxpool_kernel with the
-    half format (launch_maxpool's `rows`).  2 x 2 / 2 on 2 x 2 maps: the result is the maximum of each sample's four pixels."""
+    """N * Ho = 65536 > 65535: the IEEE-half modes leave their one-block-row-per-output-row kernels for pool_h16_kernel with the
+    half format (launch_pool's `rows`).  2 x 2 / 2 on 2 x 2 maps: the result is the maximum of each sample's four pixels."""
     rng = np.random.default_rng(13)
     x = (rng.normal(0, 3, (65536, 2, 2, 8)) - 1.0).astype(np.float32)
     want = lr.as_precision(x, prec).reshape(65536, 4, 8).max(1).reshape(65536, 1, 1, 8)
     y = _maxpool(ctx, x, 2, 2, 0, prec)
     assert y.shape == want.shape and np.array_equal(y, want)
     assert (want < 0).any() and (want > 0).any()
+
+
+# ---- one launcher behind three entries (csrc/pool.hip) --------------------------------------------------------------------------
+def _pool_same(ctx, x, avg, stride, prec):
+    return _run_pool(ctx, x, _lib.pool_same_nhwc, avg, stride, prec)
+
+
+def _pool_tf(ctx, x, k, stride, same, prec):
+    return _run_pool(ctx, x, _lib.pool_tf_nhwc, k, stride, same, prec)
+
+
+def test_pool_entries_agree_where_their_rules_coincide(ctx):
+    """wsc_maxpool_nhwc, wsc_pool_same_nhwc and wsc_pool_tf_nhwc are one launcher under three rules.  On an odd size torch's
+    3 / 2 / pad 1 and TF SAME 3 / 2 are the same windows (one row / column of padding on either side), and without padding
+    torch's 2 / 2 / 0 is TF VALID 2 / 2: identical arrays in every precision.  On an even size TF SAME pads AFTER (0 / 1) where
+    torch pads before and drops nothing: the two must DIFFER in the last output row and column -- three entries that ignored
+    their rule would agree -- while each still equals its own float64 reference."""
+    from tests import keras_arch_ref as kref
+
+    rng = np.random.default_rng(29)
+    for prec in lr.ALL_PRECISIONS:
+        for C in (8, 72):
+            x = (rng.normal(0, 3, (3, 7, 9, C)) - 1.0).astype(np.float32)
+            assert (x < 0).any() and (x > 0).any()
+            torch_y = _maxpool(ctx, x, 3, 2, 1, prec)
+            assert torch_y.shape == (3, 4, 5, C)
+            assert np.array_equal(torch_y, _pool_same(ctx, x, False, 2, prec)), (lr.PREC_NAME[prec], C)
+            assert np.array_equal(torch_y, _pool_tf(ctx, x, 3, 2, 1, prec)), (lr.PREC_NAME[prec], C)
+        x = (rng.normal(0, 3, (3, 5, 4, 8)) - 1.0).astype(np.float32)
+        assert np.array_equal(_maxpool(ctx, x, 2, 2, 0, prec), _pool_tf(ctx, x, 2, 2, 0, prec)), lr.PREC_NAME[prec]
+        x = (rng.normal(0, 3, (3, 8, 8, 8)) - 1.0).astype(np.float32)
+        v = lr.as_precision(x, prec)
+        torch_y, same_y, tf_y = _maxpool(ctx, x, 3, 2, 1, prec), _pool_same(ctx, x, False, 2, prec), _pool_tf(ctx, x, 3, 2, 1, prec)
+        assert np.array_equal(same_y, tf_y)
+        assert not np.array_equal(torch_y[:, -1], tf_y[:, -1]) and not np.array_equal(torch_y[:, :, -1], tf_y[:, :, -1]), lr.PREC_NAME[prec]
+        assert np.array_equal(torch_y.astype(np.float64), lr.max_pool(v, 3, 2, 1)), lr.PREC_NAME[prec]
+        assert np.array_equal(tf_y.astype(np.float64), kref.tf_max_pool(v, 3, 2, True)), lr.PREC_NAME[prec]
+
+
+@pytest.mark.parametrize("prec", [_lib.PREC_F16, _lib.PREC_F16X3], ids=_prec_id)
+def test_pool_tf_many_rows_takes_generic_kernel(ctx, prec):
+    """The twin of test_maxpool_many_rows_takes_generic_kernel under the TF VALID rule: N * Ho = 65536 > 65535, so pool_h16_kernel
+    with the half format runs in place of a row kernel.  2 x 2 / 2 on 2 x 2 maps: the maximum of each sample's four pixels."""
+    rng = np.random.default_rng(31)
+    x = (rng.normal(0, 3, (65536, 2, 2, 8)) - 1.0).astype(np.float32)
+    want = lr.as_precision(x, prec).reshape(65536, 4, 8).max(1).reshape(65536, 1, 1, 8)
+    y = _pool_tf(ctx, x, 2, 2, 0, prec)
+    assert y.shape == want.shape and np.array_equal(y, want)
+    assert (want < 0).any() and (want > 0).any()
+
+
+@pytest.mark.parametrize("prec", [_lib.PREC_F16, _lib.PREC_F16X3], ids=_prec_id)
+def test_pool_tf_asymmetric_padding_on_row_kernel(ctx, prec):
+    """TF SAME 3 / 2 on an even 8 x 6 map, the IEEE-half row kernels (maxpool_f16_kernel / maxpool_f16x2_kernel): no padding
+    before (pad_t = pad_l = 0), one row / column after.  Every value negative: a kernel that still applied a symmetric pad reads
+    other windows, one that let the padding win returns 0 -- both show at the last row / column."""
+    from tests import keras_arch_ref as kref
+
+    rng = np.random.default_rng(37)
+    x = (-np.abs(rng.normal(0, 3, (3, 8, 6, 8))) - 2.0 ** -6).astype(np.float32)
+    want = kref.tf_max_pool(lr.as_precision(x, prec), 3, 2, True)
+    y = _pool_tf(ctx, x, 3, 2, 1, prec)
+    assert y.shape == want.shape == (3, 4, 3, 8)
+    assert np.array_equal(y.astype(np.float64), want), np.argwhere(y != want)[:4].tolist()
+    assert (want < 0).all()
 
 
 # ---- GroupNorm head -------------------------------------------------------------------------------------------------------------

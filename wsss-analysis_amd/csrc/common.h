@@ -407,6 +407,14 @@ int launch_cam_head(wsc_ctx *ctx, Act x, int M, int K, const bf16_t *w, int Kw, 
                     int C, int relu, float *y);
 
 // ---- misc kernels ---------------------------------------------------------------------
+// 1-D grid of a grid-stride kernel over `total` items (misc_kernels.hip, deeplab.hip, pool.hip; the files with a `grid_for` of
+// their own cap theirs differently)
+inline int wsc_grid_for(long long total, int block = 256, int cap = 256 * 16) {
+    long long g = (total + block - 1) / block;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
 // (the kernel and its grid follow the activation's precision)
 int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y);
 // stem_pool.hip: conv 7x7/2 + BN + ReLU + MaxPool 3x3/2/1 of the f16x3 ResNet stem in one kernel
@@ -418,7 +426,6 @@ int launch_stem_pool(wsc_ctx *ctx, Act x, int N, int H, int W, const bf16_t *w, 
 int launch_gather_strided(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int stride, int Ho, int Wo, Act y, int ldy);
 // [N][Hp][Wp][4] with a zero border of `pad` pixels on the top / left (and whatever Hp, Wp leave on the bottom / right)
 int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, Act y);
-int launch_maxpool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo, Act y);
 // cam[b][c][y][x] = relu(head[2b][y][x][c]) + relu(head[2b+1][y][w-1-x][c])   (head fp32 NHWC, stride Cs)
 int launch_flip_add(wsc_ctx *ctx, const float *head, int B, int h, int w, int C, int Cs, float *cam);
 // score[b][c] = sigmoid(sum_f mean_hw(feat[2b])[f] * Wc[c][f] + bias[c])
@@ -429,16 +436,46 @@ int launch_act_to_f32(wsc_ctx *ctx, Act x, size_t n, float *y);
 int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y);
 int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y);
 
+// ---- pool.hip: every K x K pooling window on an NHWC activation ----------------------------------------------------------------
+// How (out, pad_before) of an axis follow from (in, k, stride) -- THE statement of the three rules (wsscam/net/common.py::
+// pool_axis is the Python side's):
+//   POOL_TORCH     nn.MaxPool2d(k, stride, pad): out = (in + 2 pad - k) / stride + 1, pad_before = pad
+//                  (C division: an axis less than `stride` short of the padded window keeps one window, the part of it inside
+//                  the image -- the nets always sized their pools so; wsc_maxpool_nhwc rejects such a map itself)
+//   POOL_TF_SAME   out = ceil(in / stride), pad_before = max((out - 1) stride + k - in, 0) / 2 (floor; the rest after: 1 / 1 on an
+//                  odd size, 0 / 1 on an even size at 3 x 3 / 2 -- what one symmetric pad cannot express)
+//   POOL_TF_VALID  out = (in - k) / stride + 1, no padding
+enum PoolRule { POOL_TORCH, POOL_TF_SAME, POOL_TF_VALID };
+struct PoolGeom {
+    int k, stride, pad_t, pad_l, Ho, Wo;
+    bool avg; // the average over the in-image taps instead of their maximum
+};
+inline bool pool_axis(PoolRule rule, int in, int k, int stride, int pad, int *out, int *pad_before) {
+    *out = *pad_before = 0;
+    if (in < 1 || k < 1 || stride < 1) return false;
+    if (rule == POOL_TF_SAME) {
+        *out = (in + stride - 1) / stride;
+        const int pad_total = (*out - 1) * stride + k - in;
+        *pad_before = pad_total > 0 ? pad_total / 2 : 0;
+    } else if (rule == POOL_TF_VALID) {
+        *out = in >= k ? (in - k) / stride + 1 : 0;
+    } else {
+        if (pad < 0) return false;
+        *pad_before = pad;
+        *out = (in + 2 * pad - k) / stride + 1;
+    }
+    return *out >= 1;
+}
+// false (and nothing to launch) when H x W is no input of that window: an axis shorter than the (padded) window
+inline bool pool_geom(PoolRule rule, int k, int stride, int pad /* POOL_TORCH only */, bool avg, int H, int W, PoolGeom *g) {
+    g->k = k; g->stride = stride; g->avg = avg;
+    const bool okh = pool_axis(rule, H, k, stride, pad, &g->Ho, &g->pad_t), okw = pool_axis(rule, W, k, stride, pad, &g->Wo, &g->pad_l);
+    return okh && okw;
+}
+// max (padding never wins) or average (k = 3, stride 1) of that geometry, every plane; the kernel follows the activation's precision
+int launch_pool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, const PoolGeom &g, Act y);
+
 // ---- deeplab.hip: the kernels around the conv stack of the SEC / DSRG DeepLab nets -------------------------------------
-// TF `SAME` 3x3 pooling of one axis: out = ceil(in / stride), pad_before = max((out - 1) stride + 3 - in, 0) / 2
-void pool_same_dims(int in, int stride, int *out, int *pad_before);
-// 3x3 max (stride 1 / 2; padding is -inf) or average over the in-image taps (stride 1) on an NHWC activation, every plane
-int launch_pool_same(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int avg, int stride, Act y);
-// TF / Keras MaxPooling2D of one axis, window k, `same` 1 / 0: SAME out = ceil(in / stride), pad_before = max((out - 1) stride +
-// k - in, 0) / 2; VALID out = (in - k) / stride + 1, no padding.  false: the axis is no input of that window (VALID, in < k)
-bool pool_tf_dims(int in, int k, int stride, int same, int *out, int *pad_before);
-// k x k max (k 2 / 3, stride 1 / 2 <= k, padding is -inf) of that geometry on an NHWC activation, every plane
-int launch_pool_tf(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int k, int stride, int same, Act y);
 // float32 [N][H][W][3] -> NHWC4 activation (raises the range flag where an IEEE-half plane saturates)
 int launch_nhwc3_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y);
 // prob[m][c] = fc8-softmax of (in[0] + ... + in[n_in - 1])[m][c]; fc8 (optional) receives the summed logits

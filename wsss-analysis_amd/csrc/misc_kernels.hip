@@ -73,146 +73,6 @@ __global__ __launch_bounds__(256) void gather_strided_kernel(const bf16_t *__res
     }
 }
 
-// nn.MaxPool2d(k, stride, pad) on NHWC bf16, 8 channels per thread.
-// resnet50.py:64 (3x3 s2 p1), common_cnn.py:131-132 (2x2 s2).
-__global__ void maxpool_kernel(const bf16_t *__restrict__ x, const bf16_t *__restrict__ x_lo, int N, int H,
-                               int W, int C, int k, int stride, int pad, int Ho, int Wo,
-                               bf16_t *__restrict__ y, bf16_t *__restrict__ y_lo, int fmt) {
-    const int C8 = C >> 3;
-    const long long total = (long long)N * Ho * Wo * C8;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int c8 = (int)(i % C8);
-        long long pix = i / C8;
-        const int wo = (int)(pix % Wo);
-        pix /= Wo;
-        const int ho = (int)(pix % Ho);
-        const int n = (int)(pix / Ho);
-        float best[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) best[j] = -3.0e38f;
-        for (int dy = 0; dy < k; ++dy) {
-            const int hi = ho * stride - pad + dy;
-            if ((unsigned)hi >= (unsigned)H) continue;
-            for (int dx = 0; dx < k; ++dx) {
-                const int wi = wo * stride - pad + dx;
-                if ((unsigned)wi >= (unsigned)W) continue;
-                const long long o = (((long long)n * H + hi) * W + wi) * C + c8 * 8;
-                const uint4 v = *reinterpret_cast<const uint4 *>(x + o);
-                const uint32_t vw[4] = {v.x, v.y, v.z, v.w};
-                float f[8];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f[2 * j] = h16_to_f32((bf16_t)(vw[j] & 0xffffu), fmt);
-                    f[2 * j + 1] = h16_to_f32((bf16_t)(vw[j] >> 16), fmt);
-                }
-                if (x_lo != nullptr) {
-                    const uint4 l = *reinterpret_cast<const uint4 *>(x_lo + o);
-                    const uint32_t lw[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        f[2 * j] += h16_to_f32((bf16_t)(lw[j] & 0xffffu), fmt);
-                        f[2 * j + 1] += h16_to_f32((bf16_t)(lw[j] >> 16), fmt);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) best[j] = fmaxf(best[j], f[j]);
-            }
-        }
-        uint32_t hw[4], lw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bf16_t h0 = f32_to_h16(best[2 * j], fmt), h1 = f32_to_h16(best[2 * j + 1], fmt);
-            hw[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-            const bf16_t l0 = f32_to_h16(best[2 * j] - h16_to_f32(h0, fmt), fmt);
-            const bf16_t l1 = f32_to_h16(best[2 * j + 1] - h16_to_f32(h1, fmt), fmt);
-            lw[j] = (uint32_t)l0 | ((uint32_t)l1 << 16);
-        }
-        const long long oo = (((long long)n * Ho + ho) * Wo + wo) * C + c8 * 8;
-        *reinterpret_cast<uint4 *>(y + oo) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-        if (y_lo != nullptr) *reinterpret_cast<uint4 *>(y_lo + oo) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
-    }
-}
-
-// The same pooling for IEEE-half activations with one precision plane (the default path): the maximum of halves is taken
-// on the halves themselves (v_pk_max_f16, two channels per instruction -- exact, no conversion), one block row per output
-// row (blockIdx.y = n * Ho + ho: no 64-bit index divisions).  8 channels = one 16-byte load per tap.
-__global__ __launch_bounds__(256) void maxpool_f16_kernel(const bf16_t *__restrict__ x, int H, int W, int C, int k, int stride,
-                                                          int pad, int Ho, int Wo, bf16_t *__restrict__ y) {
-    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-    const int C8 = C >> 3;
-    const int row = blockIdx.y; // n * Ho + ho
-    const int n = row / Ho, ho = row - n * Ho;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Wo * C8; i += gridDim.x * blockDim.x) {
-        const int wo = i / C8, c8 = i - wo * C8;
-        const h2_t lowest = {(_Float16)-65504.f, (_Float16)-65504.f};
-        h2_t best[4] = {lowest, lowest, lowest, lowest};
-        bool any = false;
-        for (int dy = 0; dy < k; ++dy) {
-            const int hi = ho * stride - pad + dy;
-            if ((unsigned)hi >= (unsigned)H) continue;
-            for (int dx = 0; dx < k; ++dx) {
-                const int wi = wo * stride - pad + dx;
-                if ((unsigned)wi >= (unsigned)W) continue;
-                const uint4 v = *reinterpret_cast<const uint4 *>(x + ((((long long)n * H + hi) * W + wi) * C + c8 * 8));
-                const uint32_t vw[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) best[j] = __builtin_elementwise_max(best[j], __builtin_bit_cast(h2_t, vw[j]));
-                any = true;
-            }
-        }
-        (void)any;
-        *reinterpret_cast<uint4 *>(y + (((long long)row * Wo + wo) * C + c8 * 8)) =
-            make_uint4(__builtin_bit_cast(uint32_t, best[0]), __builtin_bit_cast(uint32_t, best[1]),
-                       __builtin_bit_cast(uint32_t, best[2]), __builtin_bit_cast(uint32_t, best[3]));
-    }
-}
-
-// The same mapping for the two-plane half activations of the f16x3 mode: the value of a tap is hi + lo (exact in fp32: 22
-// bits), the maximum is taken on the values and split again (value-exact: the planes of the maximum are re-derived, the
-// value is one of the inputs').  The generic kernel above spends a 64-bit index division chain per 8 channels and ran the
-// ResNet stem's pool at 3.75 TB/s (142 us for 532 MB).
-__global__ __launch_bounds__(256) void maxpool_f16x2_kernel(const bf16_t *__restrict__ x, const bf16_t *__restrict__ x_lo, int H, int W,
-                                                            int C, int k, int stride, int pad, int Ho, int Wo, bf16_t *__restrict__ y,
-                                                            bf16_t *__restrict__ y_lo) {
-    const int C8 = C >> 3;
-    const int row = blockIdx.y; // n * Ho + ho
-    const int n = row / Ho, ho = row - n * Ho;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Wo * C8; i += gridDim.x * blockDim.x) {
-        const int wo = i / C8, c8 = i - wo * C8;
-        float best[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) best[j] = -3.0e38f;
-        for (int dy = 0; dy < k; ++dy) {
-            const int hi = ho * stride - pad + dy;
-            if ((unsigned)hi >= (unsigned)H) continue;
-            for (int dx = 0; dx < k; ++dx) {
-                const int wi = wo * stride - pad + dx;
-                if ((unsigned)wi >= (unsigned)W) continue;
-                const long long o = (((long long)n * H + hi) * W + wi) * C + c8 * 8;
-                const uint4 v = *reinterpret_cast<const uint4 *>(x + o), l = *reinterpret_cast<const uint4 *>(x_lo + o);
-                const uint32_t vw[4] = {v.x, v.y, v.z, v.w}, lw[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    best[2 * j] = fmaxf(best[2 * j], f16_to_f32((bf16_t)(vw[j] & 0xffffu)) + f16_to_f32((bf16_t)(lw[j] & 0xffffu)));
-                    best[2 * j + 1] = fmaxf(best[2 * j + 1], f16_to_f32((bf16_t)(vw[j] >> 16)) + f16_to_f32((bf16_t)(lw[j] >> 16)));
-                }
-            }
-        }
-        uint32_t hw[4], lw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bf16_t h0 = f32_to_f16(best[2 * j]), h1 = f32_to_f16(best[2 * j + 1]);
-            hw[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-            const bf16_t l0 = f32_to_f16(best[2 * j] - f16_to_f32(h0)), l1 = f32_to_f16(best[2 * j + 1] - f16_to_f32(h1));
-            lw[j] = (uint32_t)l0 | ((uint32_t)l1 << 16);
-        }
-        const long long oo = ((long long)row * Wo + wo) * C + c8 * 8;
-        *reinterpret_cast<uint4 *>(y + oo) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-        *reinterpret_cast<uint4 *>(y_lo + oo) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
-    }
-}
-
 // x = relu(head); cam = x[0] + x[1].flip(-1)   (resnet50_cam.py:66-68, vgg16_cam.py:49-50)
 // head: fp32 [2B][h][w][Cs] (NHWC, first C channels valid) -> cam fp32 [B][C][h][w]
 __global__ void flip_add_kernel(const float *__restrict__ head, int B, int h, int w, int C, int Cs,
@@ -350,33 +210,6 @@ __global__ void nchw_to_nhwc4_f32_kernel(const float *__restrict__ x, int N, int
         y[i] = f32x4_t{s[0], s[HW], s[2 * HW], 0.f};
     }
 }
-// nn.MaxPool2d(k, stride, pad) on NHWC fp32, 4 channels per thread
-__global__ __launch_bounds__(256) void maxpool_f32_kernel(const float *__restrict__ x, int N, int H, int W, int C, int k, int stride,
-                                                          int pad, int Ho, int Wo, float *__restrict__ y) {
-    const int C4 = C >> 2;
-    const long long total = (long long)N * Ho * Wo * C4;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(i % C4);
-        long long pix = i / C4;
-        const int wo = (int)(pix % Wo);
-        pix /= Wo;
-        const int ho = (int)(pix % Ho);
-        const int n = (int)(pix / Ho);
-        f32x4_t best = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
-        for (int dy = 0; dy < k; ++dy) {
-            const int hi = ho * stride - pad + dy;
-            if ((unsigned)hi >= (unsigned)H) continue;
-            for (int dx = 0; dx < k; ++dx) {
-                const int wi = wo * stride - pad + dx;
-                if ((unsigned)wi >= (unsigned)W) continue;
-                const f32x4_t v = *reinterpret_cast<const f32x4_t *>(x + ((((long long)n * H + hi) * W + wi) * C + c4 * 4));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) best[j] = fmaxf(best[j], v[j]);
-            }
-        }
-        *reinterpret_cast<f32x4_t *>(y + ((((long long)n * Ho + ho) * Wo + wo) * C + c4 * 4)) = best;
-    }
-}
 // gap_kernel's decomposition and summation order on fp32 features
 __global__ __launch_bounds__(64 * GAP_WAVES) void gap_f32_kernel(const float *__restrict__ feat, int hw, int F, float *__restrict__ gap,
                                                                  int sample_stride) {
@@ -423,13 +256,6 @@ __global__ void relayout_f32_kernel(const float *__restrict__ x, int N, int C, i
     }
 }
 
-inline int grid_for(long long total, int block = 256, int cap = 256 * 16) {
-    long long g = (total + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 } // namespace
 
 int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y) {
@@ -437,9 +263,9 @@ int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act 
     const bool f32 = y.is_f32();
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * (12 + (f32 ? 16 : 8)));
     if (f32)
-        hipLaunchKernelGGL(nchw_to_nhwc4_f32_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, (f32x4_t *)y.f32());
+        hipLaunchKernelGGL(nchw_to_nhwc4_f32_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, (f32x4_t *)y.f32());
     else
-        hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, y.h16(), y.h16_lo(),
+        hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, y.h16(), y.h16_lo(),
                            y.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
@@ -449,7 +275,7 @@ int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, 
     WSC_CHECK(!y.is_f32(), WSC_ERR_INVALID, "the padded NHWC4 input is a half-mode path");
     const long long total = (long long)N * Hp * Wp;
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)N * H * W * 12 + (double)total * (y.lo ? 16 : 8));
-    hipLaunchKernelGGL(nchw_to_nhwc4_pad_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x, N, H, W, Hp, Wp, pad, y.h16(),
+    hipLaunchKernelGGL(nchw_to_nhwc4_pad_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x, N, H, W, Hp, Wp, pad, y.h16(),
                        y.h16_lo(), y.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
@@ -460,32 +286,8 @@ int launch_gather_strided(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int s
     WSC_CHECK(C % 8 == 0 && ldy % 8 == 0, WSC_ERR_INVALID, "gather: C=%d, pitch=%d not multiples of 8", C, ldy);
     const long long total = (long long)N * Ho * Wo * (C / 8);
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * 32 * (x.lo ? 2 : 1));
-    hipLaunchKernelGGL(gather_strided_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x.h16(), x.h16_lo(), H, W, C / 8, stride,
+    hipLaunchKernelGGL(gather_strided_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x.h16(), x.h16_lo(), H, W, C / 8, stride,
                        Ho, Wo, y.h16(), y.h16_lo(), ldy, total);
-    WSC_HIP(hipGetLastError());
-    return WSC_OK;
-}
-
-int launch_maxpool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo, Act y) {
-    WSC_CHECK(C % 8 == 0, WSC_ERR_INVALID, "maxpool: C=%d not a multiple of 8", C);
-    WSC_CHECK(y.prec == x.prec, WSC_ERR_INVALID, "maxpool: input and output of different precisions");
-    const long long total = (long long)N * Ho * Wo * (C / 8);
-    const bool f32 = x.is_f32();
-    WscKernelTimer timer(ctx, WSC_K_POOL_MISC, ((double)N * H * W * C + (double)N * Ho * Wo * C) * (f32 ? 4 : 2));
-    const int per_row = Wo * (C / 8);
-    const bool rows = x.fmt() == 1 && (long long)N * Ho <= 65535; // IEEE half, one block row per output row
-    if (f32)
-        hipLaunchKernelGGL(maxpool_f32_kernel, dim3(grid_for(total * 2)), dim3(256), 0, ctx->stream, x.f32(), N, H, W, C, k, stride,
-                           pad, Ho, Wo, y.f32());
-    else if (rows && !x.lo && !y.lo)
-        hipLaunchKernelGGL(maxpool_f16_kernel, dim3((unsigned)((per_row + 255) / 256), (unsigned)(N * Ho)), dim3(256), 0, ctx->stream,
-                           x.h16(), H, W, C, k, stride, pad, Ho, Wo, y.h16());
-    else if (rows && x.lo && y.lo)
-        hipLaunchKernelGGL(maxpool_f16x2_kernel, dim3((unsigned)((per_row + 255) / 256), (unsigned)(N * Ho)), dim3(256), 0, ctx->stream,
-                           x.h16(), x.h16_lo(), H, W, C, k, stride, pad, Ho, Wo, y.h16(), y.h16_lo());
-    else
-        hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, x.h16(), x.h16_lo(), N, H, W, C, k, stride,
-                           pad, Ho, Wo, y.h16(), y.h16_lo(), x.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
@@ -493,7 +295,7 @@ int launch_maxpool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int k, int s
 int launch_flip_add(wsc_ctx *ctx, const float *head, int B, int h, int w, int C, int Cs, float *cam) {
     const long long total = (long long)B * C * h * w;
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * 12);
-    hipLaunchKernelGGL(flip_add_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, head, B, h, w, C, Cs,
+    hipLaunchKernelGGL(flip_add_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, head, B, h, w, C, Cs,
                        cam);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
@@ -522,14 +324,14 @@ int launch_act_to_f32(wsc_ctx *ctx, Act x, size_t n, float *y) {
         WSC_HIP(hipMemcpyAsync(y, x.f32(), n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         return WSC_OK;
     }
-    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for((long long)n)), dim3(256), 0, ctx->stream, (const bf16_t *)x.h16(),
+    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(wsc_grid_for((long long)n)), dim3(256), 0, ctx->stream, (const bf16_t *)x.h16(),
                        (const bf16_t *)x.h16_lo(), n, y, x.fmt());
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
 int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y) {
-    const dim3 grid(grid_for((long long)N * C * HW));
+    const dim3 grid(wsc_grid_for((long long)N * C * HW));
     if (y.is_f32())
         hipLaunchKernelGGL(relayout_f32_kernel<true>, grid, dim3(256), 0, ctx->stream, x, N, C, HW, y.f32());
     else
@@ -539,7 +341,7 @@ int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act 
 }
 
 int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y) {
-    const dim3 grid(grid_for((long long)N * C * HW));
+    const dim3 grid(wsc_grid_for((long long)N * C * HW));
     if (x.is_f32())
         hipLaunchKernelGGL(relayout_f32_kernel<false>, grid, dim3(256), 0, ctx->stream, (const float *)x.f32(), N, C, HW, y);
     else

@@ -52,26 +52,27 @@ struct IrnCat {
     int channels, stage, stride;
 };
 
-enum OpType {
-    OP_CONV = 0, OP_POOL = 1, OP_GATHER = 2, OP_POOL_SAME = 3 /* TF SAME 3x3: ps = stride, pp = 1 for the average */,
-    OP_POOL_TF = 4 /* a `pool_spec` row, TF / Keras MaxPooling2D: pk = window, ps = stride, pp = 1 for SAME, 0 for VALID */
-};
+enum OpType { OP_CONV = 0, OP_POOL = 1, OP_GATHER = 2 };
 // one row of `pool_spec`
 struct PoolSpec {
     int k, stride, same;
+    PoolRule rule() const { return same ? POOL_TF_SAME : POOL_TF_VALID; }
 };
 // one fc6 (3x3 atrous) -> fc7 (1x1) -> fc8 (1x1, no ReLU, fp32 logits) branch of the DeepLab head
 struct SegBranch {
     ConvW fc6, fc7, fc8;
 };
+// (made by add_conv_op / add_pool_op / add_gather_op only)
 struct Op {
-    int type;
-    int conv;         // index into convs (OP_CONV)
-    int in, out, res; // activation buffer ids; res = -1 if none; in = -1 means the NHWC4 input
-    int pk, ps, pp;   // pool kernel / stride / pad (OP_GATHER: ps = pixel stride)
-    int pitch = 0;    // channels per output row when the op writes a channel range of a wider (concatenated) tensor, else 0
-    int coff = 0;     // first channel of that range
-    int in2 = -1;     // OP_CONV, 1x1: buffer whose pixels (ho * ps, wo * ps) supply the LAST input channels (ConvLaunch::x2), or -1
+    int type = OP_CONV;
+    int conv = -1;                  // index into convs (OP_CONV)
+    int in = -1, out = 0, res = -1; // activation buffer ids; res = -1 if none; in = -1 means the NHWC4 input
+    PoolRule rule = POOL_TORCH;     // OP_POOL: how the window meets the border (pool_geom)
+    int pk = 0, ps = 0, pp = 0;     // OP_POOL: window / stride / torch pad (POOL_TORCH only); OP_GATHER, OP_CONV with in2: ps = pixel stride
+    bool avg = false;               // OP_POOL: the average instead of the maximum
+    int pitch = 0;                  // channels per output row when the op writes a channel range of a wider (concatenated) tensor, else 0
+    int coff = 0;                   // first channel of that range
+    int in2 = -1;                   // OP_CONV, 1x1: buffer whose pixels (ho * ps, wo * ps) supply the LAST input channels (ConvLaunch::x2), or -1
 };
 
 } // namespace
@@ -252,17 +253,24 @@ void on_padded_input(ConvLaunch &L, int in_h, int in_w) {
     L.H = in_h; L.W = in_w; L.pad = 0;
 }
 
-int add_conv_op(wsc_net *net, const ConvW &c, int in, int out, int res) {
+// (in2: the buffer of a 1x1 layer's second input, read at pixel stride `stride2`)
+int add_conv_op(wsc_net *net, const ConvW &c, int in, int out, int res, int in2 = -1, int stride2 = 0) {
     net->convs.push_back(c);
     Op op;
-    op.type = OP_CONV; op.conv = (int)net->convs.size() - 1; op.in = in; op.out = out; op.res = res;
-    op.pk = op.ps = op.pp = 0;
+    op.type = OP_CONV; op.conv = (int)net->convs.size() - 1; op.in = in; op.out = out; op.res = res; op.in2 = in2; op.ps = stride2;
     net->ops.push_back(op);
     return WSC_OK;
 }
-void add_pool_op(wsc_net *net, int k, int s, int p, int in, int out) {
+// (pad: POOL_TORCH only)
+void add_pool_op(wsc_net *net, PoolRule rule, int k, int stride, int pad, bool avg, int in, int out) {
     Op op;
-    op.type = OP_POOL; op.conv = -1; op.in = in; op.out = out; op.res = -1; op.pk = k; op.ps = s; op.pp = p;
+    op.type = OP_POOL; op.in = in; op.out = out; op.rule = rule; op.pk = k; op.ps = stride; op.pp = pad; op.avg = avg;
+    net->ops.push_back(op);
+}
+// pixels (ho * stride, wo * stride) of `in` into channels [coff, coff + its channels) of `out`, a tensor of `pitch` channels
+void add_gather_op(wsc_net *net, int stride, int in, int out, int pitch, int coff) {
+    Op op;
+    op.type = OP_GATHER; op.in = in; op.out = out; op.ps = stride; op.pitch = pitch; op.coff = coff;
     net->ops.push_back(op);
 }
 
@@ -282,7 +290,7 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
     // stem: conv1 7x7 s2 p3 + bn1 + relu, maxpool 3x3 s2 p1          (resnet50.py:62-64, 96-99)
     // (f16x3: the padded-input form, staged like every other layer of that mode)
     WSC_TRY(resnet_conv(net, d, "resnet50.conv1", "resnet50.bn1", 2, 3, 1, conv_split(net->prec) == 2 ? CONV_FORM_STEM_ROWS : CONV_FORM_SMALL4, -1, 0, -1));
-    add_pool_op(net, 3, 2, 1, 0, 1);
+    add_pool_op(net, POOL_TORCH, 3, 2, 1, false, 0, 1);
     net->taps.push_back((int)net->ops.size() - 1); // stage1 = conv1, bn1, relu, maxpool (resnet50_irn.py:15)
     int cur = 1;
     const int blocks[4] = {3, 4, 6, 3};
@@ -341,18 +349,13 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
                 if (conv_split(net->prec) != 1) {
                     // the kernel reads the two inputs where they are: channel chunks [0, K1) from conv2's output, the rest from
                     // the block input at the block's stride (conv_igemm.hip, second A source)
-                    WSC_TRY(add_conv_op(net, c, f[1], f[0], -1));
-                    net->ops.back().in2 = cur;
-                    net->ops.back().ps = s;
+                    WSC_TRY(add_conv_op(net, c, f[1], f[0], -1, cur, s));
                 } else {
                     // bf16x3 (three K segments per source): the concatenated tensor is materialised -- conv2 writes its channel
                     // range, the shortcut input is gathered beside it
                     net->ops.back().pitch = K1 + K2;
                     net->ops.back().coff = 0;
-                    Op g;
-                    g.type = OP_GATHER; g.conv = -1; g.in = cur; g.out = f[1]; g.res = -1; g.pk = 1; g.ps = s; g.pp = 0;
-                    g.pitch = K1 + K2; g.coff = K1;
-                    net->ops.push_back(g);
+                    add_gather_op(net, s, cur, f[1], K1 + K2, K1);
                     WSC_TRY(add_conv_op(net, c, f[1], f[0], -1));
                 }
                 cur = f[0];
@@ -425,10 +428,8 @@ int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
                 if (pools) {
                     WSC_CHECK(n_pool < pools->size(), WSC_ERR_INVALID, "internal: pool_spec has %d rows, the stack more pools", (int)pools->size());
                     const PoolSpec &ps = (*pools)[n_pool++];
-                    Op op;
-                    op.type = OP_POOL_TF; op.conv = -1; op.in = cur; op.out = out; op.res = -1; op.pk = ps.k; op.ps = ps.stride; op.pp = ps.same;
-                    net->ops.push_back(op);
-                } else add_pool_op(net, 2, 2, 0, cur, out);
+                    add_pool_op(net, ps.rule(), ps.k, ps.stride, 0, false, cur, out);
+                } else add_pool_op(net, POOL_TORCH, 2, 2, 0, false, cur, out);
                 cur = out;
                 idx += 1;
             } else if (v == -2) { // nn.Dropout: identity in eval()
@@ -480,18 +481,19 @@ int gradcam_bias(const Dict &d, int C, std::vector<float> &bias) {
     return WSC_OK;
 }
 
+// vgg16.py:44
+const std::vector<std::pair<std::string, std::vector<int>>> VGG16_CFG = {{"layer1", {64, 64, -1}},
+                                                                         {"layer2", {128, 128, -1}},
+                                                                         {"layer3", {256, 256, 256, -1}},
+                                                                         {"layer4", {512, 512, 512, 512, 512, 512}},
+                                                                         {"layer5", {1024, -2, 1024, -2}}};
+
 int build_vgg16(wsc_net *net, const Dict &d) {
-    const std::vector<std::pair<std::string, std::vector<int>>> cfg = {
-        {"layer1", {64, 64, -1}},
-        {"layer2", {128, 128, -1}},
-        {"layer3", {256, 256, 256, -1}},
-        {"layer4", {512, 512, 512, 512, 512, 512}},
-        {"layer5", {1024, -2, 1024, -2}}}; // vgg16.py:44
     int cur = 0;
     std::vector<PoolSpec> pools;
     bool spec;
     WSC_TRY(read_pool_spec(d, 3, &pools, &spec));
-    WSC_TRY(build_plain_stack(net, d, "vgg16", cfg, &cur, &net->F, nullptr, spec ? &pools : nullptr));
+    WSC_TRY(build_plain_stack(net, d, "vgg16", VGG16_CFG, &cur, &net->F, nullptr, spec ? &pools : nullptr));
     net->final_buf = cur;
     const HostTensor *lw;
     WSC_TRY(get(d, "vgg16.classifier.0.weight", 2, &lw));
@@ -643,14 +645,8 @@ int build_resnet50_irn(wsc_net *net, const Dict &d) {
 }
 
 int build_vgg16_irn(wsc_net *net, const Dict &d) {
-    const std::vector<std::pair<std::string, std::vector<int>>> cfg = {
-        {"layer1", {64, 64, -1}},
-        {"layer2", {128, 128, -1}},
-        {"layer3", {256, 256, 256, -1}},
-        {"layer4", {512, 512, 512, 512, 512, 512}},
-        {"layer5", {1024, -2, 1024, -2}}}; // vgg16.py:44; stage k = layer k (vgg16_irn.py:21-25)
     int cur = 0;
-    WSC_TRY(build_plain_stack(net, d, "vgg16", cfg, &cur, &net->F, &net->taps));
+    WSC_TRY(build_plain_stack(net, d, "vgg16", VGG16_CFG, &cur, &net->F, &net->taps)); // stage k = layer k (vgg16_irn.py:21-25)
     net->final_buf = cur;
     // ds_fac = 0.25 (vgg16_irn.py:30-98): stage1 is at 1/2 resolution and its heads use a stride-2 1x1 conv
     const std::vector<HeadSpec> specs = {
@@ -721,11 +717,9 @@ int build_deeplab(wsc_net *net, const Dict &d, bool aspp) {
     bool first = true;
     for (const Item &it : trunk) {
         if (it.name[0] == 0) {
-            Op op;
-            op.type = OP_POOL_SAME; op.conv = -1; op.in = cur; op.out = (cur + 1) & 1; op.res = -1;
-            op.pk = 3; op.ps = it.v == 0 ? 1 : it.v; op.pp = it.v == 0 ? 1 : 0;
-            net->ops.push_back(op);
-            cur = op.out;
+            const int out = (cur + 1) & 1;
+            add_pool_op(net, POOL_TF_SAME, 3, it.v == 0 ? 1 : it.v, 0, it.v == 0, cur, out);
+            cur = out;
             continue;
         }
         ConvW c;
@@ -791,20 +785,10 @@ int plan_dims(const wsc_net *net, int N, int SH, int SW, Plan *pl) {
             d.Co = op.pitch;
             WSC_CHECK(d.Ho == bh[op.out] && d.Wo == bw[op.out] && bc[op.out] == op.pitch && op.coff + d.C <= op.pitch, WSC_ERR_INVALID,
                       "internal: gather into a %d x %d x %d tensor does not fit", bh[op.out], bw[op.out], bc[op.out]);
-        } else if (op.type == OP_POOL_SAME) {
-            int pad_before;
-            pool_same_dims(d.H, op.ps, &d.Ho, &pad_before);
-            pool_same_dims(d.W, op.ps, &d.Wo, &pad_before);
-            d.Co = d.C;
-        } else if (op.type == OP_POOL_TF) {
-            int pad_before; // (a VALID window wider than the map: out = 0, the check below)
-            pool_tf_dims(d.H, op.pk, op.ps, op.pp, &d.Ho, &pad_before);
-            pool_tf_dims(d.W, op.pk, op.ps, op.pp, &d.Wo, &pad_before);
-            d.Co = d.C;
         } else {
-            d.Ho = (d.H + 2 * op.pp - op.pk) / op.ps + 1;
-            d.Wo = (d.W + 2 * op.pp - op.pk) / op.ps + 1;
-            d.Co = d.C;
+            PoolGeom g; // (a window wider than the map: Ho or Wo = 0, the check below)
+            pool_geom(op.rule, op.pk, op.ps, op.pp, op.avg, d.H, d.W, &g);
+            d.Ho = g.Ho; d.Wo = g.Wo; d.Co = d.C;
         }
         WSC_CHECK(d.Ho > 0 && d.Wo > 0, WSC_ERR_INVALID, "input size %d x %d too small for this network", SH, SW);
         bh[op.out] = d.Ho; bw[op.out] = d.Wo; bc[op.out] = d.Co;
@@ -845,7 +829,8 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
         bool tapped = false;
         for (int tp : net->taps) tapped = tapped || tp == 0;
         fused_stem = ctx->opt[WSC_OPT_STEM_POOL_FUSED] && net->ops.size() > 1 && net->ops[1].type == OP_POOL &&
-                     net->ops[1].in == net->ops[0].out && net->ops[1].pk == 3 && net->ops[1].ps == 2 && net->ops[1].pp == 1 &&
+                     net->ops[1].in == net->ops[0].out && net->ops[1].rule == POOL_TORCH && !net->ops[1].avg && net->ops[1].pk == 3 &&
+                     net->ops[1].ps == 2 && net->ops[1].pp == 1 &&
                      c0.kh == 7 && c0.kw == 7 && c0.stride == 2 && c0.pad == 3 && c0.Cout == 64 && c0.s2 == nullptr &&
                      net->ops[0].res < 0 && conv_fmt(net->prec) == 1 && !tapped;
         if (fused_stem) {
@@ -894,12 +879,10 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             WSC_TRY(conv_igemm_launch(ctx, L));
         } else if (op.type == OP_GATHER) {
             WSC_TRY(launch_gather_strided(ctx, src, N, d.H, d.W, d.C, op.ps, d.Ho, d.Wo, buf[op.out].at(op.coff), op.pitch));
-        } else if (op.type == OP_POOL_SAME) {
-            WSC_TRY(launch_pool_same(ctx, src, N, d.H, d.W, d.C, op.pp, op.ps, buf[op.out]));
-        } else if (op.type == OP_POOL_TF) {
-            WSC_TRY(launch_pool_tf(ctx, src, N, d.H, d.W, d.C, op.pk, op.ps, op.pp, buf[op.out]));
         } else {
-            WSC_TRY(launch_maxpool(ctx, src, N, d.H, d.W, d.C, op.pk, op.ps, op.pp, d.Ho, d.Wo, buf[op.out]));
+            PoolGeom g;
+            WSC_CHECK(pool_geom(op.rule, op.pk, op.ps, op.pp, op.avg, d.H, d.W, &g), WSC_ERR_INVALID, "internal: a pool plan_dims let through");
+            WSC_TRY(launch_pool(ctx, src, N, d.H, d.W, d.C, g, buf[op.out]));
         }
         if (taps)
             for (size_t k = 0; k < net->taps.size(); ++k)
@@ -926,14 +909,14 @@ int run_classifier(wsc_ctx *ctx, const wsc_net *net, Act feat, Act spare, int N,
     int hw = hf * wf;
     if (net->cls_max && net->cls_pool_set) {
         const PoolSpec &ps = net->cls_pool;
-        int hp, wp, pad;
-        WSC_CHECK(pool_tf_dims(hf, ps.k, ps.stride, ps.same, &hp, &pad) && pool_tf_dims(wf, ps.k, ps.stride, ps.same, &wp, &pad), WSC_ERR_INVALID,
+        PoolGeom g;
+        WSC_CHECK(pool_geom(ps.rule(), ps.k, ps.stride, 0, false, hf, wf, &g), WSC_ERR_INVALID,
                   "the %d x %d feature map is smaller than the classifier branch's %d x %d VALID pool", hf, wf, ps.k, ps.k);
-        const bool crops = !ps.same && ((hp - 1) * ps.stride + ps.k < hf || (wp - 1) * ps.stride + ps.k < wf);
+        const bool crops = !ps.same && ((g.Ho - 1) * ps.stride + ps.k < hf || (g.Wo - 1) * ps.stride + ps.k < wf);
         if (crops) {
-            WSC_TRY(launch_pool_tf(ctx, feat, N, hf, wf, net->F, ps.k, ps.stride, ps.same, spare));
+            WSC_TRY(launch_pool(ctx, feat, N, hf, wf, net->F, g, spare));
             feat = spare;
-            hw = hp * wp;
+            hw = g.Ho * g.Wo;
         }
     }
     return launch_gap_linear_sigmoid(ctx, feat, count, net->cls_max ? -hw : hw, net->F, net->cls_w, net->cls_b, net->Ccls, score_dev,
@@ -1354,28 +1337,6 @@ int wsc_group_norm_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, i
     WSC_TRY(launch_nchw_to_nhwc(ctx, y_dev, N * Hd * Wd, Ctot, 1, yo)); // (what the other heads of the concat buffer wrote)
     WSC_TRY(launch_group_norm_stats(ctx, x_dev, N, H, W, C, G, eps, part, stats));
     WSC_TRY(launch_group_norm_apply(ctx, x_dev, stats, gamma, beta, N, H, W, C, G, up, relu, yo, Hd, Wd, Ctot, coff));
-    return launch_act_to_f32(ctx, yo, out_e, y_dev);
-}
-
-int wsc_maxpool_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, int k, int stride, int pad, int precision,
-                     float *y_dev) {
-    WSC_CHECK(ctx && x_dev && y_dev, WSC_ERR_INVALID, "wsc_maxpool_nhwc: null argument");
-    wsc_precision prec;
-    WSC_TRY(decode_precision(precision, &prec));
-    WSC_CHECK(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, WSC_ERR_INVALID, "wsc_maxpool_nhwc: %d x %d x %d x %d (C a multiple of 8)", N,
-              H, W, C);
-    WSC_CHECK(k >= 1 && stride >= 1 && pad >= 0 && 2 * pad <= k, WSC_ERR_INVALID,
-              "wsc_maxpool_nhwc: window %d stride %d padding %d (padding at most half the window)", k, stride, pad);
-    WSC_CHECK(H + 2 * pad >= k && W + 2 * pad >= k, WSC_ERR_INVALID, "wsc_maxpool_nhwc: a %d x %d map is smaller than the window %d", H, W, k);
-    WSC_HIP(hipSetDevice(ctx->device));
-    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    const size_t in_e = (size_t)N * H * W * C, out_e = (size_t)N * Ho * Wo * C;
-    void *ws;
-    WSC_TRY(wsc_ctx_workspace(ctx, act_bytes(in_e, prec) + act_bytes(out_e, prec), &ws));
-    char *p = (char *)ws;
-    const Act xi = act_carve(p, in_e, prec), yo = act_carve(p, out_e, prec);
-    WSC_TRY(launch_nchw_to_nhwc(ctx, x_dev, (int)((size_t)N * H * W), C, 1, xi));
-    WSC_TRY(launch_maxpool(ctx, xi, N, H, W, C, k, stride, pad, Ho, Wo, yo));
     return launch_act_to_f32(ctx, yo, out_e, y_dev);
 }
 

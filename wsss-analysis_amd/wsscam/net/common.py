@@ -20,7 +20,7 @@ def pool_axis(n, k, stride, padding):
     """TensorFlow / Keras MaxPooling2D on one axis of n positions -> (out, pad_before, pad_after):
       'same'   out = ceil(n / stride), pad_total = max((out - 1) stride + k - n, 0), pad_before = floor(pad_total / 2)
       'valid'  out = floor((n - k) / stride) + 1, no padding; n < k is an error.
-    THE host statement of the rule (csrc/deeplab.hip::pool_tf_dims is the device's)."""
+    THE Python statement of the rule (csrc/common.h::pool_geom, POOL_TF_SAME / POOL_TF_VALID, is the library's)."""
     n, k, stride = int(n), int(k), int(stride)
     if n < 1 or k < 1 or stride < 1:
         raise ValueError("pool of window %d, stride %d on %d positions" % (k, stride, n))
