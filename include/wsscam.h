@@ -374,6 +374,38 @@ int wsc_irn_edge_finish(wsc_ctx *ctx, const float *e_dev, int He, int We, const 
 int wsc_fc8_softmax(wsc_ctx *ctx, const float *const *fc8_dev, int n_in, long long M, int C, float min_prob, float *sum_dev,
                     float *prob_dev);
 
+/* The per-op view of a forward pass, for the per-op tests (tests/test_gpu_net_trace.py): what the conv stack of a net does for an
+ * N x H x W input, one entry per op in execution order plus one for the CAM head where the net has one, and a forward pass that
+ * hands out every op's output.  The IRNet heads and the DeepLab fc6 - fc8 branches run behind the stack and are not listed. */
+enum { WSC_TRACE_CONV = 0, WSC_TRACE_POOL = 1, WSC_TRACE_GATHER = 2, WSC_TRACE_HEAD = 3 };
+enum { WSC_TRACE_INPUT = -1 /* the operand is the network input */, WSC_TRACE_NONE = -2 /* no such operand */ };
+typedef struct wsc_trace_op {
+    int32_t kind;         /* WSC_TRACE_CONV / _POOL / _GATHER / _HEAD */
+    int32_t in, in2, res; /* index of the entry that wrote the operand LAST: the input, the second source of a stage-entry conv
+                             (its last input channels, read at pixel (ho stride2, wo stride2)), the residual; or WSC_TRACE_INPUT /
+                             WSC_TRACE_NONE.  An op that reads a concatenated tensor names the op that completed it (the gather) */
+    int32_t Ho, Wo;       /* output map */
+    int32_t C, coff, pitch; /* the op writes channels [coff, coff + C) of a tensor of `pitch` channels (pitch = C, coff = 0: dense) */
+    int32_t kh, kw, stride, pad, dil, relu; /* conv, head; stride also of a gather */
+    int32_t affine2;      /* conv: a second affine map follows the ReLU (conv -> bias -> ReLU -> BatchNorm of the plain stacks) */
+    int32_t stride2;      /* conv with in2: the pixel stride of the second source, else 0 */
+    int32_t pool_rule, pool_k, pool_stride, pool_pad, pool_avg; /* pool: rule 0 torch (pool_pad), 1 TF SAME, 2 TF VALID; avg 0 / 1 */
+    int32_t fused_next;   /* 1: this run computes the op together with the next entry and never writes its output (the f16x3 ResNet
+                             stem with WSC_OPT_STEM_POOL_FUSED); follows the ctx's options at the time of the call */
+    char label[100];      /* the state-dict layers the op implements: "resnet50.layer2.0.conv3+downsample", "vgg16.layer3.0",
+                             "conv5_2", "resnet50.layer2.0.gather", "pool:2" (the third pool), "head" */
+} wsc_trace_op;
+/* Writes min(max_ops, *n_ops_out) entries to ops_out; call with max_ops = 0 for the count. */
+int wsc_net_trace_plan(wsc_ctx *ctx, const wsc_net *net, int N, int H, int W, wsc_trace_op *ops_out, int max_ops, int *n_ops_out);
+/* The forward pass of the stack (and the head, before the flip-add) with the production launches, and between them a copy of
+ * every wanted entry to trace_dev + offsets_host[i] as float32 NHWC [N][Ho][Wo][pitch] -- the WHOLE tensor the op wrote into, hi +
+ * lo of the two-plane precisions summed (exact in fp32): the value the next op reads.  Of a tensor wider than the op's own range
+ * the other channels are what the buffer held (after the gather of a materialised stage entry: the finished concatenation).
+ * offsets_host[i] < 0 skips entry i; n_offsets is the plan's count; a `fused_next` entry must be skipped; every entry must lie in
+ * the trace_elems floats of trace_dev.  x_dev float32 [N][3][H][W], or [N][H][W][3] for the WSC_ARCH_DEEPLAB_* nets. */
+int wsc_net_forward_trace(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int H, int W, const long long *offsets_host,
+                          int n_offsets, float *trace_dev, long long trace_elems);
+
 /* ---- CAM tail ---------------------------------------------------------- */
 
 /* make_cam._work tail for a batch (03b_irn/step/make_cam.py:41-42,62-76 with

@@ -73,6 +73,8 @@ struct Op {
     int pitch = 0;                  // channels per output row when the op writes a channel range of a wider (concatenated) tensor, else 0
     int coff = 0;                   // first channel of that range
     int in2 = -1;                   // OP_CONV, 1x1: buffer whose pixels (ho * ps, wo * ps) supply the LAST input channels (ConvLaunch::x2), or -1
+    std::string label;              // the state-dict layers the op implements (wsc_net_trace_plan): a conv's weight key without ".weight",
+                                    // "<block>.conv3+downsample" for the stage-entry GEMM, "<block>.gather", "pool:<ordinal>"
 };
 
 } // namespace
@@ -254,9 +256,10 @@ void on_padded_input(ConvLaunch &L, int in_h, int in_w) {
 }
 
 // (in2: the buffer of a 1x1 layer's second input, read at pixel stride `stride2`)
-int add_conv_op(wsc_net *net, const ConvW &c, int in, int out, int res, int in2 = -1, int stride2 = 0) {
+int add_conv_op(wsc_net *net, const std::string &label, const ConvW &c, int in, int out, int res, int in2 = -1, int stride2 = 0) {
     net->convs.push_back(c);
     Op op;
+    op.label = label;
     op.type = OP_CONV; op.conv = (int)net->convs.size() - 1; op.in = in; op.out = out; op.res = res; op.in2 = in2; op.ps = stride2;
     net->ops.push_back(op);
     return WSC_OK;
@@ -264,12 +267,16 @@ int add_conv_op(wsc_net *net, const ConvW &c, int in, int out, int res, int in2 
 // (pad: POOL_TORCH only)
 void add_pool_op(wsc_net *net, PoolRule rule, int k, int stride, int pad, bool avg, int in, int out) {
     Op op;
+    int n_pools = 0;
+    for (const Op &o : net->ops) n_pools += o.type == OP_POOL;
+    op.label = "pool:" + std::to_string(n_pools);
     op.type = OP_POOL; op.in = in; op.out = out; op.rule = rule; op.pk = k; op.ps = stride; op.pp = pad; op.avg = avg;
     net->ops.push_back(op);
 }
 // pixels (ho * stride, wo * stride) of `in` into channels [coff, coff + its channels) of `out`, a tensor of `pitch` channels
-void add_gather_op(wsc_net *net, int stride, int in, int out, int pitch, int coff) {
+void add_gather_op(wsc_net *net, const std::string &label, int stride, int in, int out, int pitch, int coff) {
     Op op;
+    op.label = label;
     op.type = OP_GATHER; op.in = in; op.out = out; op.ps = stride; op.pitch = pitch; op.coff = coff;
     net->ops.push_back(op);
 }
@@ -283,7 +290,7 @@ int resnet_conv(wsc_net *net, const Dict &d, const std::string &conv, const std:
     WSC_TRY(fold_bn(d, bn, (int)w->shape[0], 1e-5, s, b));
     ConvW c;
     WSC_TRY(make_conv(net, w, stride, pad, relu, form, s, b, nullptr, nullptr, &c));
-    return add_conv_op(net, c, in, out, res);
+    return add_conv_op(net, conv, c, in, out, res);
 }
 
 int build_resnet50_backbone(wsc_net *net, const Dict &d) {
@@ -349,14 +356,14 @@ int build_resnet50_backbone(wsc_net *net, const Dict &d) {
                 if (conv_split(net->prec) != 1) {
                     // the kernel reads the two inputs where they are: channel chunks [0, K1) from conv2's output, the rest from
                     // the block input at the block's stride (conv_igemm.hip, second A source)
-                    WSC_TRY(add_conv_op(net, c, f[1], f[0], -1, cur, s));
+                    WSC_TRY(add_conv_op(net, pre + ".conv3+downsample", c, f[1], f[0], -1, cur, s));
                 } else {
                     // bf16x3 (three K segments per source): the concatenated tensor is materialised -- conv2 writes its channel
                     // range, the shortcut input is gathered beside it
                     net->ops.back().pitch = K1 + K2;
                     net->ops.back().coff = 0;
-                    add_gather_op(net, s, cur, f[1], K1 + K2, K1);
-                    WSC_TRY(add_conv_op(net, c, f[1], f[0], -1));
+                    add_gather_op(net, pre + ".gather", s, cur, f[1], K1 + K2, K1);
+                    WSC_TRY(add_conv_op(net, pre + ".conv3+downsample", c, f[1], f[0], -1));
                 }
                 cur = f[0];
                 continue;
@@ -455,7 +462,7 @@ int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
                 }
                 const int in = first ? -1 : cur;
                 const int out = first ? 0 : ((cur + 1) & 1);
-                WSC_TRY(add_conv_op(net, c, in, out, -1));
+                WSC_TRY(add_conv_op(net, key, c, in, out, -1));
                 cur = out;
                 in_ch = v;
                 first = false;
@@ -725,7 +732,7 @@ int build_deeplab(wsc_net *net, const Dict &d, bool aspp) {
         ConvW c;
         WSC_TRY(deeplab_conv(net, d, it.name, 3, in_ch, 0, it.v, 1, first ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, &c));
         const int out = first ? 0 : ((cur + 1) & 1);
-        WSC_TRY(add_conv_op(net, c, first ? -1 : cur, out, -1));
+        WSC_TRY(add_conv_op(net, it.name, c, first ? -1 : cur, out, -1));
         cur = out;
         in_ch = c.Cout;
         first = false;
@@ -807,11 +814,35 @@ size_t taps_bytes(const wsc_net *net, const Plan &pl, int N) {
     return b;
 }
 
+// conv 7x7 / 2 / 3 (-> 64) + BN + ReLU followed by MaxPool 3 / 2 / 1 (resnet50.py:54-64) of the f16x3 padded-input stem: one kernel
+// (stem_pool.hip), unless the conv's own output is wanted (a tap) or the path is switched off
+bool stem_pool_fused(const wsc_ctx *ctx, const wsc_net *net) {
+    if (net->ops.empty() || net->ops[0].type != OP_CONV || net->ops[0].in >= 0 || net->convs[net->ops[0].conv].form != CONV_FORM_STEM_ROWS)
+        return false;
+    const ConvW &c0 = net->convs[net->ops[0].conv];
+    bool tapped = false;
+    for (int tp : net->taps) tapped = tapped || tp == 0;
+    return ctx->opt[WSC_OPT_STEM_POOL_FUSED] && net->ops.size() > 1 && net->ops[1].type == OP_POOL &&
+           net->ops[1].in == net->ops[0].out && net->ops[1].rule == POOL_TORCH && !net->ops[1].avg && net->ops[1].pk == 3 &&
+           net->ops[1].ps == 2 && net->ops[1].pp == 1 &&
+           c0.kh == 7 && c0.kw == 7 && c0.stride == 2 && c0.pad == 3 && c0.Cout == 64 && c0.s2 == nullptr &&
+           net->ops[0].res < 0 && conv_fmt(net->prec) == 1 && !tapped;
+}
+
+// wsc_net_forward_trace's observer: after op i, the tensor the op wrote into (all `Co` channels of it, OpDims) goes to
+// out + off[i] as fp32 NHWC (launch_act_to_f32: hi + lo, the exact value the next op reads); off[i] < 0: not wanted
+struct TraceSink {
+    const long long *off;
+    float *out;
+};
+
 // Runs the conv stack on N samples; *feat is the final feature map.  *extra: `extra_bytes` of workspace for the caller.  With
 // `taps` the stage outputs x1..x5 (net->taps) are copied to the start of that region, in stage order, and *extra is what
 // follows them -- the rotating activation buffers are overwritten as the stack proceeds.
 int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, size_t extra_bytes, Act *feat, int *hf, int *wf,
-                 void **extra, std::vector<Act> *taps = nullptr, int SW = 0, bool nhwc_in = false, Act *spare = nullptr) {
+                 void **extra, std::vector<Act> *taps = nullptr, int SW = 0, bool nhwc_in = false, Act *spare = nullptr,
+                 const TraceSink *trace = nullptr) {
+    // (trace: copies between the launches, nothing else -- the launches are the ones of a run without it)
     // (spare: a rotating buffer other than *feat, free once the stack has run -- any tensor no larger than the feature map fits)
     // (nhwc_in: x_dev is [N][S][SW][3] instead of [N][3][S][SW] -- the DeepLab nets take TensorFlow's layout)
     if (SW <= 0) SW = S; // S x SW input (SW given for the non-square, native-size path)
@@ -824,15 +855,7 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
         const ConvW &c0 = net->convs[net->ops[0].conv];
         conv_stem_rows_input_dims(pl.ops[0].Ho, pl.ops[0].Wo, c0.stride, c0.kh, &in_h, &in_w);
         in_pad = c0.pad;
-        // conv 7x7 / 2 / 3 (-> 64) + BN + ReLU followed by MaxPool 3 / 2 / 1 (resnet50.py:54-64): one kernel (stem_pool.hip),
-        // unless the conv's own output is wanted (a tap) or the path is switched off
-        bool tapped = false;
-        for (int tp : net->taps) tapped = tapped || tp == 0;
-        fused_stem = ctx->opt[WSC_OPT_STEM_POOL_FUSED] && net->ops.size() > 1 && net->ops[1].type == OP_POOL &&
-                     net->ops[1].in == net->ops[0].out && net->ops[1].rule == POOL_TORCH && !net->ops[1].avg && net->ops[1].pk == 3 &&
-                     net->ops[1].ps == 2 && net->ops[1].pp == 1 &&
-                     c0.kh == 7 && c0.kw == 7 && c0.stride == 2 && c0.pad == 3 && c0.Cout == 64 && c0.s2 == nullptr &&
-                     net->ops[0].res < 0 && conv_fmt(net->prec) == 1 && !tapped;
+        fused_stem = stem_pool_fused(ctx, net);
         if (fused_stem) {
             stem_pool_input_dims(S, SW, &in_h, &in_w);
             in_pad = 5;
@@ -884,6 +907,7 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             WSC_CHECK(pool_geom(op.rule, op.pk, op.ps, op.pp, op.avg, d.H, d.W, &g), WSC_ERR_INVALID, "internal: a pool plan_dims let through");
             WSC_TRY(launch_pool(ctx, src, N, d.H, d.W, d.C, g, buf[op.out]));
         }
+        if (trace && trace->off[i] >= 0) WSC_TRY(launch_act_to_f32(ctx, buf[op.out], pl.out_elems(N, (int)i), trace->out + trace->off[i]));
         if (taps)
             for (size_t k = 0; k < net->taps.size(); ++k)
                 if (net->taps[k] == (int)i) {
@@ -1086,6 +1110,107 @@ int wsc_net_forward_features(wsc_ctx *ctx, const wsc_net *net, const float *x_de
     void *extra;
     WSC_TRY(run_backbone(ctx, net, x_dev, N, S, 0, &feat, &hf, &wf, &extra));
     return launch_act_to_f32(ctx, feat, (size_t)N * hf * wf * net->F, feat_dev);
+}
+
+// ---- the per-op view of a forward pass (tests/test_gpu_net_trace.py) ------------------------------------------------------------
+static int trace_plan(const wsc_ctx *ctx, const wsc_net *net, int N, int H, int W, std::vector<wsc_trace_op> *out, Plan *pl) {
+    WSC_TRY(plan_dims(net, N, H, W, pl));
+    const bool fused = stem_pool_fused(ctx, net);
+    int writer[4] = {WSC_TRACE_NONE, WSC_TRACE_NONE, WSC_TRACE_NONE, WSC_TRACE_NONE}; // the op that wrote each rotating buffer last
+    auto producer = [&](int b) { return b < 0 ? WSC_TRACE_INPUT : writer[b]; };
+    auto set_label = [](wsc_trace_op &t, const std::string &s) {
+        std::memset(t.label, 0, sizeof(t.label));
+        std::strncpy(t.label, s.c_str(), sizeof(t.label) - 1);
+    };
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        const Op &op = net->ops[i];
+        const OpDims &d = pl->ops[i];
+        wsc_trace_op t = {};
+        set_label(t, op.label);
+        t.in = producer(op.in);
+        t.in2 = t.res = WSC_TRACE_NONE;
+        t.Ho = d.Ho; t.Wo = d.Wo; t.pitch = d.Co; t.coff = op.coff; t.C = d.Co;
+        if (op.type == OP_CONV) {
+            const ConvW &c = net->convs[op.conv];
+            t.kind = WSC_TRACE_CONV;
+            t.C = c.Cout;
+            if (op.in2 >= 0) t.in2 = producer(op.in2);
+            if (op.res >= 0) t.res = producer(op.res);
+            t.kh = c.kh; t.kw = c.kw; t.stride = c.stride; t.pad = c.pad; t.dil = c.dil; t.relu = c.relu;
+            t.affine2 = c.s2 != nullptr;
+            t.stride2 = op.in2 >= 0 ? op.ps : 0;
+            t.fused_next = fused && i == 0;
+        } else if (op.type == OP_GATHER) {
+            t.kind = WSC_TRACE_GATHER;
+            t.C = d.C;
+            t.stride = op.ps;
+        } else {
+            t.kind = WSC_TRACE_POOL;
+            t.pool_rule = (int)op.rule; t.pool_k = op.pk; t.pool_stride = op.ps; t.pool_pad = op.pp; t.pool_avg = op.avg;
+        }
+        writer[op.out] = (int)i;
+        out->push_back(t);
+    }
+    if (net->head.w != nullptr) {
+        wsc_trace_op t = {};
+        set_label(t, "head");
+        t.kind = WSC_TRACE_HEAD;
+        t.in = producer(net->final_buf);
+        t.in2 = t.res = WSC_TRACE_NONE;
+        t.Ho = pl->hf; t.Wo = pl->wf; t.C = t.pitch = net->C;
+        t.kh = t.kw = t.stride = t.dil = 1;
+        out->push_back(t);
+    }
+    return WSC_OK;
+}
+
+int wsc_net_trace_plan(wsc_ctx *ctx, const wsc_net *net, int N, int H, int W, wsc_trace_op *ops_out, int max_ops, int *n_ops_out) {
+    WSC_CHECK(ctx && net && n_ops_out, WSC_ERR_INVALID, "wsc_net_trace_plan: null argument");
+    WSC_CHECK(N > 0 && H > 0 && W > 0 && max_ops >= 0 && (ops_out != nullptr || max_ops == 0), WSC_ERR_INVALID,
+              "wsc_net_trace_plan: N=%d input %d x %d, room for %d ops", N, H, W, max_ops);
+    std::vector<wsc_trace_op> ops;
+    Plan pl;
+    WSC_TRY(trace_plan(ctx, net, N, H, W, &ops, &pl));
+    *n_ops_out = (int)ops.size();
+    for (int i = 0; i < max_ops && i < (int)ops.size(); ++i) ops_out[i] = ops[i];
+    return WSC_OK;
+}
+
+int wsc_net_forward_trace(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int H, int W, const long long *offsets_host,
+                          int n_offsets, float *trace_dev, long long trace_elems) {
+    WSC_CHECK(ctx && net && x_dev && offsets_host && trace_dev, WSC_ERR_INVALID, "wsc_net_forward_trace: null argument");
+    WSC_CHECK(N > 0 && H > 0 && W > 0 && trace_elems >= 0, WSC_ERR_INVALID, "wsc_net_forward_trace: N=%d input %d x %d", N, H, W);
+    WSC_HIP(hipSetDevice(ctx->device));
+    std::vector<wsc_trace_op> ops;
+    Plan pl;
+    WSC_TRY(trace_plan(ctx, net, N, H, W, &ops, &pl));
+    WSC_CHECK(n_offsets == (int)ops.size(), WSC_ERR_INVALID, "wsc_net_forward_trace: %d offsets for %d entries (wsc_net_trace_plan)", n_offsets,
+              (int)ops.size());
+    // every wanted entry lies inside the caller's buffer, and is an op this run computes on its own
+    for (int i = 0; i < n_offsets; ++i) {
+        if (offsets_host[i] < 0) continue;
+        const long long elems = (long long)N * ops[i].Ho * ops[i].Wo * ops[i].pitch;
+        WSC_CHECK(!ops[i].fused_next, WSC_ERR_INVALID, "wsc_net_forward_trace: op %d is computed together with op %d in this run", i, i + 1);
+        WSC_CHECK(offsets_host[i] <= trace_elems - elems, WSC_ERR_INVALID, "wsc_net_forward_trace: entry %d (%lld floats at %lld) leaves the %lld-float buffer",
+                  i, elems, offsets_host[i], trace_elems);
+    }
+    const bool has_head = net->head.w != nullptr;
+    const size_t head_bytes = has_head ? (size_t)N * pl.hf * pl.wf * net->C * sizeof(float) : 0;
+    const TraceSink sink = {offsets_host, trace_dev};
+    Act feat, spare;
+    int hf, wf;
+    void *extra;
+    WSC_TRY(run_backbone(ctx, net, x_dev, N, H, head_bytes, &feat, &hf, &wf, &extra, nullptr, W, !net->seg.empty(), &spare, &sink));
+    if (has_head && offsets_host[n_offsets - 1] >= 0) {
+        float *head_out = (float *)extra; // (as wsc_net_forward_cam_hw has it, before the flip-add)
+        ConvLaunch L = conv_launch(net->head, net->prec);
+        L.x = feat;
+        L.y_f32 = head_out;
+        L.N = N; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf;
+        WSC_TRY(run_head(ctx, L));
+        WSC_HIP(hipMemcpyAsync(trace_dev + offsets_host[n_offsets - 1], head_out, head_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return WSC_OK;
 }
 
 // EdgeDisplacement.forward (resnet50_irn.py:212-232 / vgg16_irn.py:306-321) for B images: x is the

@@ -63,6 +63,16 @@ class TensorDesc(ctypes.Structure):
     ]
 
 
+class TraceOp(ctypes.Structure):
+    """wsc_trace_op: one entry of Net.trace_plan"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "kind", "in_", "in2", "res", "Ho", "Wo", "C", "coff", "pitch", "kh", "kw", "stride", "pad", "dil", "relu", "affine2", "stride2",
+        "pool_rule", "pool_k", "pool_stride", "pool_pad", "pool_avg", "fused_next")] + [("label", ctypes.c_char * 100)]
+
+
+TRACE_CONV, TRACE_POOL, TRACE_GATHER, TRACE_HEAD = range(4)
+TRACE_INPUT, TRACE_NONE = -1, -2
+
 _lib = None
 
 _vp = ctypes.c_void_p
@@ -125,6 +135,8 @@ _SIGNATURES = {
     "wsc_cam_flip_add": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "wsc_irn_edge_finish": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     "wsc_fc8_softmax": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _f, _vp, _vp]),
+    "wsc_net_trace_plan": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(TraceOp), _i, ctypes.POINTER(_i)]),
+    "wsc_net_forward_trace": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_longlong), _i, _vp, ctypes.c_longlong]),
     "wsc_cam_postprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wsc_cam_eval_confusion": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp]),
     "wsc_unary_from_maps": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
@@ -575,6 +587,28 @@ class Net:
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_forward_seg(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(min_prob), _ptr(fc8_dev),
                                                 _ptr(prob_dev)))
+
+    def trace_plan(self, N, H, W, ctx=None):
+        """wsc_net_trace_plan: one dict per op of the stack for an N x H x W input (+ the CAM head), the fields of wsc_trace_op
+        (`in` under its own name, the label as str).  Follows the options of `ctx` (the fused stem)."""
+        run = ctx or self.ctx
+        n = _i()
+        check(self.ctx._lib.wsc_net_trace_plan(run.h, self.h, int(N), int(H), int(W), None, 0, ctypes.byref(n)))
+        ops = (TraceOp * n.value)()
+        check(self.ctx._lib.wsc_net_trace_plan(run.h, self.h, int(N), int(H), int(W), ops, n.value, ctypes.byref(n)))
+        out = []
+        for o in ops:
+            d = {name.rstrip("_"): getattr(o, name) for name, _ in TraceOp._fields_ if name != "label"}
+            d["label"] = o.label.decode()
+            out.append(d)
+        return out
+
+    def forward_trace(self, x_dev, N, H, W, offsets, trace_dev, trace_elems, ctx=None):
+        """wsc_net_forward_trace: entry i of the plan as float32 [N][Ho][Wo][pitch] at trace_dev + offsets[i] floats (< 0: skipped)."""
+        run = ctx or self.ctx
+        off = (ctypes.c_longlong * len(offsets))(*[int(o) for o in offsets])
+        check(self.ctx._lib.wsc_net_forward_trace(run.h, self.h, _ptr(x_dev), int(N), int(H), int(W), off, len(offsets), _ptr(trace_dev),
+                                                  int(trace_elems)))
 
 
 def _key_table(keys_per_image, B=None):
