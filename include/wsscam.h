@@ -374,6 +374,68 @@ int wsc_irn_edge_finish(wsc_ctx *ctx, const float *e_dev, int He, int We, const 
 int wsc_fc8_softmax(wsc_ctx *ctx, const float *const *fc8_dev, int n_in, long long M, int C, float min_prob, float *sum_dev,
                     float *prob_dev);
 
+/* ---- backward pass of the SEC / DSRG network: compute_gradients at drop_prob = 0 ------------------------------------------
+ * The reference's statement after getloss() is opt.compute_gradients(loss["total"]) (model.py:382-387).  wsc_seg_loss hands out
+ * d loss / d fc8; wsc_net_backward_seg carries it to the gradient of every weight and bias of the net, in exact fp32 whatever the
+ * net's forward precision.  The definition: the chain rule EVALUATED AT THE TAPE, the fp32 values every op read in the forward
+ * pass (hi + lo of a two-plane precision, exact in fp32).  A ReLU passes dy where its kept output is > 0, else +0.0; a max pool
+ * sends a window's dy to the window's first maximum in row-major window order (padding is never a candidate); pool5a sends
+ * dy / (in-image tap count) to every in-image tap; every ASPP branch receives dfc8 and their gradients into pool5a's output are
+ * summed in the order _1 ... _4; no gradient is formed for the network input.  Out of scope: dropout, the weight-decay term, the
+ * learning-rate multipliers, the optimiser.
+ *
+ * The tape: wsc_net_seg_tape_plan lists the kept tensors for a B x H x W input -- "input", every op of the trunk ("conv1_1", ...,
+ * "pool:0", ..., "pool5a"), every branch's "fc6[_k]" and "fc7[_k]" -- each float32 NHWC [B][Ho][Wo][C] at `offset` floats of one
+ * buffer of *tape_elems_out floats; max_entries = 0 for the count.  wsc_net_forward_seg_tape is wsc_net_forward_seg (the same
+ * launches, the same bits in fc8_dev / prob_dev) with those tensors copied to the caller's buffer between the launches.  The
+ * caller owns the tape; nothing is kept between the forward and the backward pass. */
+typedef struct wsc_tape_entry {
+    char name[32];
+    int32_t Ho, Wo, C;
+    int64_t offset; /* floats */
+} wsc_tape_entry;
+int wsc_net_seg_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W, wsc_tape_entry *entries_out, int max_entries,
+                          int *n_out, long long *tape_elems_out);
+int wsc_net_forward_seg_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob,
+                             float *tape_dev, long long tape_elems, float *fc8_dev, float *prob_dev);
+/* wsc_seg_grad: what the backward pass of one net keeps -- the rotated, channel-transposed fp32 kernels of the data-gradient
+ * convolutions (packed once) and the backward workspace (two gradient activations, the masked dz, the split-K slabs; grown on
+ * demand).  `weights`: the list wsc_net_create took; a tensor that is not the net's is WSC_ERR_SHAPE naming the layer.  The net
+ * must outlive the object.  wsc_seg_grad_layout: per layer its name, kernel, channels and where dW ([kh][kw][Cin][Cout], TF's
+ * HWIO: the layout the weights came in) and db ([Cout]) lie in the gradient buffer of *grad_elems_out floats. */
+typedef struct wsc_seg_grad wsc_seg_grad;
+typedef struct wsc_grad_entry {
+    char name[32];
+    int32_t kh, kw, Cin, Cout;
+    int64_t w_off, b_off; /* floats */
+} wsc_grad_entry;
+int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_seg_grad **out);
+void wsc_seg_grad_destroy(wsc_seg_grad *g);
+int wsc_seg_grad_layout(const wsc_seg_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out);
+/* dfc8_dev float32 [B][h][w][C] -> every element of grad_dev (nothing accumulates into the caller's buffer).  ctx: the context
+ * the wsc_seg_grad was created on (its workspace belongs to that stream; another one is WSC_ERR_INVALID).  Asynchronous on the
+ * ctx stream (the first call at a larger size allocates the workspace).  A tape or gradient size other than the plan's / the
+ * layout's is WSC_ERR_INVALID before any launch.  Two calls give the same bits: the split-K slices of a weight gradient are
+ * summed in slice order, no floating-point atomic anywhere. */
+int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                         const float *dfc8_dev, float *grad_dev, long long grad_elems);
+/* The layers of that pass one by one, for the per-op tests (float32 NHWC in and out, the launchers of the pass unchanged):
+ * wsc_conv2d_wgrad_nhwc: dw_dev [k][k][Cin][Cout] and db_dev [Cout] of a stride-1 SAME convolution (k 1 or 3, pad = dil (k - 1) / 2)
+ *   from its input x_dev [N][H][W][Cin] and the gradient dy_dev [N][H][W][Cout] of its (pre-activation) output: fp32 operands on
+ *   v_mfma_f32_32x32x2_f32, K = the pixels.  Cin 3 or a multiple of 64; Cout 2 .. 32 (Cin a multiple of 64) or a multiple of 64.
+ *   splits = 0: the launcher's choice of K slices, > 0: that many (at most one per K-step of 32 pixels).  A tap outside the image for every pixel is exactly 0.0.
+ * wsc_conv2d_dgrad_nhwc: dx_dev [N][H][W][Cin] from dy_dev and the layer's weights w_host [k][k][Cin][Cout]; Cin a multiple of 64.
+ * wsc_relu_bias_grad: dz_dev [M][C] = dy [y > 0] (y_dev NULL: dz = dy), db_dev [C] = the column sums of dz.
+ * wsc_pool_same_grad_nhwc: the gradient of wsc_pool_same_nhwc at x_dev [N][H][W][C] (C a multiple of 8) for dy_dev of the pool's
+ *   output size -> dx_dev [N][H][W][C]. */
+int wsc_conv2d_wgrad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int Cin, int Cout, int k, int dil,
+                          int splits, float *dw_dev, float *db_dev);
+int wsc_conv2d_dgrad_nhwc(wsc_ctx *ctx, const float *dy_dev, const float *w_host, int N, int H, int W, int Cin, int Cout, int k, int dil,
+                          float *dx_dev);
+int wsc_relu_bias_grad(wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float *dz_dev, float *db_dev);
+int wsc_pool_same_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int avg, int stride,
+                            float *dx_dev);
+
 /* The per-op view of a forward pass, for the per-op tests (tests/test_gpu_net_trace.py): what the conv stack of a net does for an
  * N x H x W input, one entry per op in execution order plus one for the CAM head where the net has one, and a forward pass that
  * hands out every op's output.  The IRNet heads and the DeepLab fc6 - fc8 branches run behind the stack and are not listed. */

@@ -116,6 +116,8 @@ enum WscKernelClass {
     WSC_K_BLUR,          // combine4_kernel + blur4_kernel (bilateral) + blur3_tile_kernel (Gaussian, when its message is not formed on chip)
     WSC_K_SLICE_UPDATE,  // update_splat_kernel: slice + mean-field update + splat of the result
     WSC_K_CRF_MISC,      // init_q / finish
+    WSC_K_WGRAD,         // wgrad_kernel + wgrad_reduce_kernel (seg_grad.hip); work = algorithmic FLOPs
+    WSC_K_GRAD_MISC,     // ReLU mask + bias gradient, pool gradients, channel copies of the backward pass
     WSC_K_COUNT
 };
 struct WscProfRecord {
@@ -474,6 +476,42 @@ inline bool pool_geom(PoolRule rule, int k, int stride, int pad /* POOL_TORCH on
 }
 // max (padding never wins) or average (k = 3, stride 1) of that geometry, every plane; the kernel follows the activation's precision
 int launch_pool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, const PoolGeom &g, Act y);
+
+// the gradient of launch_pool with respect to its input (fp32 planes): dx[n][hi][wi][c] = the sum, in window order, of dy over the
+// windows whose first maximum (row-major window order, recomputed from x) is that pixel -- or of dy / (in-image tap count) over
+// the windows that cover it (g.avg).  Gather form: no atomics.  C a multiple of 4.
+int launch_pool_grad(wsc_ctx *ctx, const float *x, const float *dy, int N, int H, int W, int C, const PoolGeom &g, float *dx);
+
+// ---- seg_grad.hip: the fp32 kernels of the DeepLab backward pass -------------------------------------------------------------
+// How one layer's weight gradient is cut into blocks (wgrad_plan) -- what its caller sizes the slabs by
+struct WgradPlan {
+    int M, nk, pad;             // pixels, K-steps of 32 pixels, SAME padding
+    bool small_cin;             // Cin = 3: the (tap, channel) pairs as one 32-row operand
+    int bn, tiles_ci, tiles_co; // column tile (32 / 64 / 128), 64-row and bn-column tiles
+    int ntaps;                  // taps that get blocks
+    unsigned long long taps;    // their r k + s, 4 bits each
+    unsigned dead;              // bit r k + s: the tap is outside the image for every pixel (exact zeros, nothing read)
+    int splits;                 // K slices
+    long long out_elems, slab_elems; // k k Cin Cout; floats of the split-K slabs
+};
+// splits = 0: the launcher's choice (blocks ~ 1 - 2 x the CU count); Cin 3 or a multiple of 64, Cout 2 .. 32 or a multiple of 64
+int wgrad_plan(const wsc_ctx *ctx, int N, int H, int W, int Cin, int Cout, int k, int dil, int splits, WgradPlan *pl);
+// dw [k][k][Cin][Cout] (HWIO) of a stride-1 SAME convolution from x [N][H][W][Cin] and dz [N][H][W][Cout]; every element is written
+int wgrad_launch(wsc_ctx *ctx, const WgradPlan &pl, const float *x, const float *dz, int H, int W, int Cin, int Cout, int k, int dil,
+                 float *slab, float *dw);
+// dz = dy [y > 0] (y null: dz = dy; dz null: not written), db[c] = sum_m dz[m][c]; partial: relu_bias_grad_blocks(M) * C floats
+int relu_bias_grad_blocks(long long M);
+int launch_relu_bias_grad(wsc_ctx *ctx, const float *y, const float *dy, long long M, int C, float *dz, float *partial, float *db);
+// dst [M][Cd] = the first channels of src [M][Cs], zeros beyond
+int launch_copy_channels(wsc_ctx *ctx, const float *src, long long M, int Cs, int Cd, float *dst);
+// The data gradient of a stride-1 SAME convolution w [k][k][Cin][Cout] as conv_f32_launch's generic layer: its input is dz with
+// dgrad_cz(Cout) channels (zeros past Cout), its kernel the rotated, transposed one in conv_k_layout(k, k, dgrad_cz(Cout), generic,
+// WSC_PREC_F32) with conv_cout_pad(Cin) rows; ones / zeros: that many 1.0 / 0.0.  sum_with: null, or [M][Cin] added to the result
+// (may be dx itself: every element is read and written by one thread).
+inline int dgrad_cz(int Cout) { return (Cout + 31) / 32 * 32; }
+void dgrad_pack(const float *w_hwio, int k, int Cin, int Cout, std::vector<float> *packed);
+int dgrad_launch(wsc_ctx *ctx, const float *dz, const float *w_packed, const float *ones, const float *zeros, int N, int H, int W, int Cin,
+                 int Cout, int k, int dil, const float *sum_with, float *dx);
 
 // ---- deeplab.hip: the kernels around the conv stack of the SEC / DSRG DeepLab nets -------------------------------------
 // float32 [N][H][W][3] -> NHWC4 activation (raises the range flag where an IEEE-half plane saturates)

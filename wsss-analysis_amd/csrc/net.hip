@@ -133,6 +133,22 @@ int get(const Dict &d, const std::string &k, int ndim, const HostTensor **out) {
 }
 bool has(const Dict &d, const std::string &k) { return d.find(k) != d.end(); }
 
+// the wsc_tensor_desc list of the C ABI as a dictionary (the data stays the caller's)
+int descs_to_dict(const wsc_tensor_desc *weights, int n_weights, Dict *d) {
+    for (int i = 0; i < n_weights; ++i) {
+        WSC_CHECK(weights[i].name != nullptr, WSC_ERR_INVALID, "weights[%d].name is null", i);
+        WSC_CHECK(weights[i].ndim >= 0 && weights[i].ndim <= 4, WSC_ERR_SHAPE, "'%s': ndim %d unsupported",
+                  weights[i].name, weights[i].ndim);
+        HostTensor t;
+        t.data = weights[i].data;
+        t.ndim = weights[i].ndim;
+        for (int k = 0; k < 4; ++k) t.shape[k] = k < t.ndim ? weights[i].shape[k] : 1;
+        if (t.ndim == 0) { t.ndim = 1; t.shape[0] = 1; }
+        (*d)[weights[i].name] = t;
+    }
+    return WSC_OK;
+}
+
 // Fold inference batch-norm y = (x - mean) / sqrt(var + eps) * gamma + beta into scale/shift.
 int fold_bn(const Dict &d, const std::string &bn, int C, double eps_default, std::vector<float> &s,
             std::vector<float> &b) {
@@ -841,8 +857,9 @@ struct TraceSink {
 // follows them -- the rotating activation buffers are overwritten as the stack proceeds.
 int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, size_t extra_bytes, Act *feat, int *hf, int *wf,
                  void **extra, std::vector<Act> *taps = nullptr, int SW = 0, bool nhwc_in = false, Act *spare = nullptr,
-                 const TraceSink *trace = nullptr) {
+                 const TraceSink *trace = nullptr, Act *xin_out = nullptr) {
     // (trace: copies between the launches, nothing else -- the launches are the ones of a run without it)
+    // (xin_out: the NHWC4 input activation the first op reads; no op writes it)
     // (spare: a rotating buffer other than *feat, free once the stack has run -- any tensor no larger than the feature map fits)
     // (nhwc_in: x_dev is [N][S][SW][3] instead of [N][3][S][SW] -- the DeepLab nets take TensorFlow's layout)
     if (SW <= 0) SW = S; // S x SW input (SW given for the non-square, native-size path)
@@ -917,6 +934,7 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
                 }
     }
     *feat = buf[net->final_buf];
+    if (xin_out) *xin_out = xin;
     if (spare) *spare = buf[net->final_buf == 3 ? 2 : 3];
     *hf = pl.hf;
     *wf = pl.wf;
@@ -961,17 +979,7 @@ int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n
     WSC_TRY(decode_precision(precision, &prec));
     WSC_HIP(hipSetDevice(ctx->device));
     Dict d;
-    for (int i = 0; i < n_weights; ++i) {
-        WSC_CHECK(weights[i].name != nullptr, WSC_ERR_INVALID, "weights[%d].name is null", i);
-        WSC_CHECK(weights[i].ndim >= 0 && weights[i].ndim <= 4, WSC_ERR_SHAPE, "'%s': ndim %d unsupported",
-                  weights[i].name, weights[i].ndim);
-        HostTensor t;
-        t.data = weights[i].data;
-        t.ndim = weights[i].ndim;
-        for (int k = 0; k < 4; ++k) t.shape[k] = k < t.ndim ? weights[i].shape[k] : 1;
-        if (t.ndim == 0) { t.ndim = 1; t.shape[0] = 1; }
-        d[weights[i].name] = t;
-    }
+    WSC_TRY(descs_to_dict(weights, n_weights, &d));
     // (never ignored: the IRN flavours keep the torch port's MaxPool2d(2, 2), the other nets have their own pools)
     WSC_CHECK(!has(d, "pool_spec") || arch == WSC_ARCH_VGG16_CAM || arch == WSC_ARCH_M7_CAM, WSC_ERR_INVALID,
               "pool_spec is a key of WSC_ARCH_VGG16_CAM / WSC_ARCH_M7_CAM only (arch %d)", arch);
@@ -1315,13 +1323,46 @@ int wsc_net_seg_size_hw(const wsc_net *net, int H, int W, int *h_out, int *w_out
     return WSC_OK;
 }
 
-int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *fc8_dev,
-                        float *prob_dev) {
-    WSC_CHECK(ctx && net && x_dev && prob_dev, WSC_ERR_INVALID, "wsc_net_forward_seg: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg: the network is not a WSC_ARCH_DEEPLAB_* net");
-    WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg: B=%d input %d x %d min_prob=%g", B, H, W,
-              (double)min_prob);
-    WSC_HIP(hipSetDevice(ctx->device));
+// The tensors a backward pass needs of a forward pass ("the tape"), as float32 NHWC in one buffer: the network input, every op's
+// output of the trunk (the last pool is pool5a), every branch's fc6 and fc7 -- each the value the next op read (hi + lo)
+struct TapePlan {
+    Plan pl;
+    std::vector<wsc_tape_entry> e;
+    std::vector<int> op_entry;   // entry of op i's output
+    std::vector<int> fc6, fc7;   // entries of branch k
+    long long elems = 0;
+};
+static int seg_tape_plan(const wsc_net *net, int B, int H, int W, TapePlan *tp) {
+    WSC_TRY(plan_dims(net, B, H, W, &tp->pl));
+    auto add = [&](const std::string &name, int Ho, int Wo, int C) {
+        wsc_tape_entry t = {};
+        std::strncpy(t.name, name.c_str(), sizeof(t.name) - 1);
+        t.Ho = Ho; t.Wo = Wo; t.C = C;
+        t.offset = tp->elems;
+        tp->elems += ((long long)B * Ho * Wo * C + 63) / 64 * 64; // (entries start on 256-byte lines)
+        tp->e.push_back(t);
+        return (int)tp->e.size() - 1;
+    };
+    add("input", H, W, 3);
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        const Op &op = net->ops[i];
+        const OpDims &d = tp->pl.ops[i];
+        // (the backward pass walks a chain: every op reads the op before it and nothing else)
+        WSC_CHECK(op.type != OP_GATHER && op.res < 0 && op.in2 < 0 && op.pitch == 0 && (i == 0 ? op.in < 0 : op.in == net->ops[i - 1].out),
+                  WSC_ERR_INVALID, "internal: op %d of a segmentation net is no link of a chain", (int)i);
+        tp->op_entry.push_back(add(i + 1 == net->ops.size() && op.type == OP_POOL && op.avg ? "pool5a" : op.label, d.Ho, d.Wo, d.Co));
+    }
+    for (size_t k = 0; k < net->seg.size(); ++k) {
+        const std::string sfx = net->seg.size() > 1 ? "_" + std::to_string(k + 1) : "";
+        tp->fc6.push_back(add("fc6" + sfx, tp->pl.hf, tp->pl.wf, net->seg[k].fc6.Cout));
+        tp->fc7.push_back(add("fc7" + sfx, tp->pl.hf, tp->pl.wf, net->seg[k].fc7.Cout));
+    }
+    return WSC_OK;
+}
+
+// wsc_net_forward_seg (tp null) and wsc_net_forward_seg_tape: the same launches; with a tape, copies between them
+static int forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *fc8_dev,
+                       float *prob_dev, const TapePlan *tp, float *tape) {
     Plan pl;
     WSC_TRY(plan_dims(net, B, H, W, &pl));
     const size_t M = (size_t)B * pl.hf * pl.wf;
@@ -1333,12 +1374,24 @@ int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, in
         e7 = std::max(e7, M * br.fc7.Cout);
     }
     const size_t logit_bytes = align_up(M * net->C * sizeof(float), 256);
-    const size_t extra_bytes = act_bytes(e6, net->prec) + act_bytes(e7, net->prec) + net->seg.size() * logit_bytes;
-    Act feat;
+    // (tape: behind those, the NHWC4 input as fp32 on its way to the tape's 3-channel entry)
+    const size_t in4_elems = (size_t)B * H * W * 4;
+    const size_t extra_bytes = act_bytes(e6, net->prec) + act_bytes(e7, net->prec) + net->seg.size() * logit_bytes +
+                               (tp ? in4_elems * sizeof(float) : 0);
+    Act feat, xin;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, B, H, extra_bytes, &feat, &hf, &wf, &extra, nullptr, W, true));
+    std::vector<long long> op_off;
+    if (tp)
+        for (int e : tp->op_entry) op_off.push_back(tp->e[e].offset);
+    const TraceSink sink = {op_off.data(), tape};
+    WSC_TRY(run_backbone(ctx, net, x_dev, B, H, extra_bytes, &feat, &hf, &wf, &extra, nullptr, W, true, nullptr, tp ? &sink : nullptr, &xin));
     char *p = (char *)extra;
+    if (tp) {
+        float *in4 = (float *)(p + extra_bytes - in4_elems * sizeof(float));
+        WSC_TRY(launch_act_to_f32(ctx, xin, in4_elems, in4));
+        WSC_TRY(launch_copy_channels(ctx, in4, (long long)B * H * W, 4, 3, tape + tp->e[0].offset));
+    }
     const Act a6 = act_carve(p, e6, net->prec), a7 = act_carve(p, e7, net->prec);
     const float *logits[4] = {nullptr, nullptr, nullptr, nullptr};
     WSC_CHECK(net->seg.size() <= 4, WSC_ERR_INVALID, "internal: %d head branches", (int)net->seg.size());
@@ -1353,10 +1406,271 @@ int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, in
             return conv_igemm_launch(ctx, L);
         };
         WSC_TRY(run(br.fc6, feat, a6, nullptr));
+        if (tp) WSC_TRY(launch_act_to_f32(ctx, a6, M * br.fc6.Cout, tape + tp->e[tp->fc6[k]].offset));
         WSC_TRY(run(br.fc7, a6, a7, nullptr));
+        if (tp) WSC_TRY(launch_act_to_f32(ctx, a7, M * br.fc7.Cout, tape + tp->e[tp->fc7[k]].offset));
         WSC_TRY(run(br.fc8, a7, Act(), out));
     }
     return launch_fc8_softmax(ctx, logits, (int)net->seg.size(), (long long)M, net->C, min_prob, fc8_dev, prob_dev);
+}
+
+int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *fc8_dev,
+                        float *prob_dev) {
+    WSC_CHECK(ctx && net && x_dev && prob_dev, WSC_ERR_INVALID, "wsc_net_forward_seg: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg: B=%d input %d x %d min_prob=%g", B, H, W,
+              (double)min_prob);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return forward_seg(ctx, net, x_dev, B, H, W, min_prob, fc8_dev, prob_dev, nullptr, nullptr);
+}
+
+int wsc_net_seg_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W, wsc_tape_entry *entries_out, int max_entries, int *n_out,
+                          long long *tape_elems_out) {
+    WSC_CHECK(ctx && net && n_out && tape_elems_out, WSC_ERR_INVALID, "wsc_net_seg_tape_plan: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_seg_tape_plan: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
+              "wsc_net_seg_tape_plan: B=%d input %d x %d, room for %d entries", B, H, W, max_entries);
+    TapePlan tp;
+    WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
+    *n_out = (int)tp.e.size();
+    *tape_elems_out = tp.elems;
+    for (int i = 0; i < max_entries && i < (int)tp.e.size(); ++i) entries_out[i] = tp.e[i];
+    return WSC_OK;
+}
+
+int wsc_net_forward_seg_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *tape_dev,
+                             long long tape_elems, float *fc8_dev, float *prob_dev) {
+    WSC_CHECK(ctx && net && x_dev && prob_dev && tape_dev, WSC_ERR_INVALID, "wsc_net_forward_seg_tape: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg_tape: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg_tape: B=%d input %d x %d min_prob=%g", B, H,
+              W, (double)min_prob);
+    TapePlan tp;
+    WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
+    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_forward_seg_tape: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)",
+              tape_elems, tp.elems);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return forward_seg(ctx, net, x_dev, B, H, W, min_prob, fc8_dev, prob_dev, &tp, tape_dev);
+}
+
+// ---- the backward pass of the DeepLab nets: d loss / d fc8 -> the gradient of every weight and bias -----------------------------
+namespace {
+struct GradLayer {
+    std::string name;
+    int k = 1, Cin = 0, Cout = 0, dil = 1;
+    float *w_rot = nullptr; // the data-gradient kernel (dgrad_pack); null for the first layer: no gradient goes to the input
+    long long w_off = 0, b_off = 0;
+};
+} // namespace
+struct wsc_seg_grad {
+    wsc_ctx *ctx = nullptr;
+    const wsc_net *net = nullptr;
+    std::vector<GradLayer> layers; // the trunk's convs in op order, then fc6, fc7, fc8 of every branch
+    std::vector<int> op_layer;     // layer of op i, -1 for a pool
+    long long grad_elems = 0;
+    float *ones = nullptr, *zeros = nullptr; // conv_cout_pad(widest layer) of each
+    void *ws = nullptr;            // the backward workspace, grown on demand
+    size_t ws_bytes = 0;
+    std::vector<void *> allocs;
+};
+
+void wsc_seg_grad_destroy(wsc_seg_grad *g) {
+    if (!g) return;
+    if (g->ctx) (void)hipStreamSynchronize(g->ctx->stream);
+    for (void *p : g->allocs) (void)hipFree(p);
+    if (g->ws) (void)hipFree(g->ws);
+    delete g;
+}
+
+int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_seg_grad **out) {
+    WSC_CHECK(ctx && net && weights && out && n_weights > 0, WSC_ERR_INVALID, "wsc_seg_grad_create: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_seg_grad_create: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_HIP(hipSetDevice(ctx->device));
+    Dict d;
+    WSC_TRY(descs_to_dict(weights, n_weights, &d));
+    wsc_seg_grad *g = new wsc_seg_grad();
+    g->ctx = ctx;
+    g->net = net;
+    auto fail = [&](int st) {
+        wsc_seg_grad_destroy(g);
+        return st;
+    };
+    auto up = [&](const std::vector<float> &v, float **dst) -> int {
+        void *p = nullptr;
+        WSC_HIP(hipMalloc(&p, v.size() * sizeof(float)));
+        g->allocs.push_back(p);
+        WSC_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+        *dst = (float *)p;
+        return WSC_OK;
+    };
+    int widest = 64;
+    auto add = [&](const std::string &name, const ConvW &c, bool first) -> int {
+        GradLayer L;
+        L.name = name;
+        L.k = c.kh; L.Cin = first ? 3 : c.Cin; L.Cout = c.Cout; L.dil = c.dil;
+        auto wi = d.find(name + ".w");
+        WSC_CHECK(wi != d.end() && wi->second.data != nullptr, WSC_ERR_SHAPE, "layer '%s': '%s.w' missing", name.c_str(), name.c_str());
+        const HostTensor &w = wi->second;
+        WSC_CHECK(w.ndim == 4 && w.shape[0] == L.k && w.shape[1] == L.k && w.shape[2] == L.Cin && w.shape[3] == L.Cout, WSC_ERR_SHAPE,
+                  "layer '%s': '.w' must be HWIO [%d][%d][%d][%d] as the net has it, got ndim %d [%lld][%lld][%lld][%lld]", name.c_str(), L.k, L.k,
+                  L.Cin, L.Cout, w.ndim, (long long)w.shape[0], (long long)w.shape[1], (long long)w.shape[2], (long long)w.shape[3]);
+        WSC_CHECK(c.kh == c.kw && c.stride == 1 && c.pad == c.dil * (c.kh - 1) / 2 && (c.kh == 1 || c.kh == 3), WSC_ERR_INVALID,
+                  "internal: layer '%s' is no stride-1 SAME convolution", name.c_str());
+        if (!first) {
+            std::vector<float> packed;
+            dgrad_pack(w.data, L.k, L.Cin, L.Cout, &packed);
+            WSC_TRY(up(packed, &L.w_rot));
+            widest = std::max(widest, conv_cout_pad(L.Cin));
+        }
+        L.w_off = g->grad_elems;
+        g->grad_elems += (long long)L.k * L.k * L.Cin * L.Cout; // (no gaps: every float of the buffer is some layer's)
+        L.b_off = g->grad_elems;
+        g->grad_elems += L.Cout;
+        g->layers.push_back(L);
+        return WSC_OK;
+    };
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        const Op &op = net->ops[i];
+        g->op_layer.push_back(op.type == OP_CONV ? (int)g->layers.size() : -1);
+        if (op.type != OP_CONV) continue;
+        const int st = add(op.label, net->convs[op.conv], i == 0);
+        if (st != WSC_OK) return fail(st);
+    }
+    for (size_t k = 0; k < net->seg.size(); ++k) {
+        const std::string sfx = net->seg.size() > 1 ? "_" + std::to_string(k + 1) : "";
+        const ConvW *cs[3] = {&net->seg[k].fc6, &net->seg[k].fc7, &net->seg[k].fc8};
+        for (int j = 0; j < 3; ++j) {
+            const int st = add("fc" + std::to_string(6 + j) + sfx, *cs[j], false);
+            if (st != WSC_OK) return fail(st);
+        }
+    }
+    int st = up(std::vector<float>(widest, 1.f), &g->ones);
+    if (st == WSC_OK) st = up(std::vector<float>(widest, 0.f), &g->zeros);
+    if (st != WSC_OK) return fail(st);
+    *out = g;
+    return WSC_OK;
+}
+
+int wsc_seg_grad_layout(const wsc_seg_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out) {
+    WSC_CHECK(g && n_out && grad_elems_out && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
+              "wsc_seg_grad_layout: null argument");
+    *n_out = (int)g->layers.size();
+    *grad_elems_out = g->grad_elems;
+    for (int i = 0; i < max_entries && i < (int)g->layers.size(); ++i) {
+        const GradLayer &L = g->layers[i];
+        wsc_grad_entry e = {};
+        std::strncpy(e.name, L.name.c_str(), sizeof(e.name) - 1);
+        e.kh = e.kw = L.k; e.Cin = L.Cin; e.Cout = L.Cout;
+        e.w_off = L.w_off; e.b_off = L.b_off;
+        entries_out[i] = e;
+    }
+    return WSC_OK;
+}
+
+int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                         const float *dfc8_dev, float *grad_dev, long long grad_elems) {
+    WSC_CHECK(ctx && g && tape_dev && dfc8_dev && grad_dev, WSC_ERR_INVALID, "wsc_net_backward_seg: null argument");
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1, WSC_ERR_INVALID, "wsc_net_backward_seg: B=%d input %d x %d", B, H, W);
+    // (the workspace is the object's: one stream uses it, the one wsc_seg_grad_destroy drains)
+    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_net_backward_seg: the context is not the one the wsc_seg_grad was created on");
+    const wsc_net *net = g->net;
+    TapePlan tp;
+    WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
+    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_backward_seg: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)",
+              tape_elems, tp.elems);
+    WSC_CHECK(grad_elems == g->grad_elems, WSC_ERR_INVALID, "wsc_net_backward_seg: a gradient buffer of %lld floats, the layout has %lld",
+              grad_elems, g->grad_elems);
+    // every layer's plan and the workspace they need, before anything is launched
+    const int hf = tp.pl.hf, wf = tp.pl.wf;
+    const long long M8 = (long long)B * hf * wf;
+    const size_t n_trunk = g->layers.size() - 3 * net->seg.size();
+    std::vector<WgradPlan> plans(g->layers.size());
+    long long g_max = 0, dz_max = M8 * dgrad_cz(net->C), slab_max = 0, part_max = 0;
+    auto plan_layer = [&](size_t li, int h, int w) -> int {
+        const GradLayer &L = g->layers[li];
+        WSC_TRY(wgrad_plan(ctx, B, h, w, L.Cin, L.Cout, L.k, L.dil, 0, &plans[li]));
+        const long long M = (long long)B * h * w;
+        g_max = std::max(g_max, M * std::max(L.Cout, L.Cin));
+        dz_max = std::max(dz_max, M * L.Cout);
+        slab_max = std::max(slab_max, plans[li].slab_elems);
+        part_max = std::max(part_max, (long long)relu_bias_grad_blocks(M) * L.Cout);
+        return WSC_OK;
+    };
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        const OpDims &d = tp.pl.ops[i];
+        g_max = std::max(g_max, (long long)B * d.H * d.W * d.C);
+        if (g->op_layer[i] >= 0) WSC_TRY(plan_layer((size_t)g->op_layer[i], d.Ho, d.Wo));
+    }
+    for (size_t li = n_trunk; li < g->layers.size(); ++li) WSC_TRY(plan_layer(li, hf, wf));
+    auto lines = [](long long elems) { return align_up((size_t)elems * sizeof(float), 256); };
+    const size_t sum_bytes = lines(M8 * net->F);
+    const size_t need = 2 * lines(g_max) + 2 * sum_bytes + lines(dz_max) + lines(slab_max) + lines(part_max);
+    WSC_HIP(hipSetDevice(ctx->device));
+    if (need > g->ws_bytes) {
+        if (g->ws) {
+            WSC_HIP(hipStreamSynchronize(ctx->stream));
+            WSC_HIP(hipFree(g->ws));
+            g->ws = nullptr;
+            g->ws_bytes = 0;
+        }
+        WSC_HIP(hipMalloc(&g->ws, need));
+        g->ws_bytes = need;
+    }
+    char *p = (char *)g->ws;
+    auto carve = [&](size_t bytes) { float *q = (float *)p; p += bytes; return q; };
+    float *ga = carve(lines(g_max)), *gb = carve(lines(g_max));
+    float *gs[2] = {carve(sum_bytes), carve(sum_bytes)};
+    float *dz = carve(lines(dz_max)), *slab = carve(lines(slab_max)), *partial = carve(lines(part_max));
+
+    // one layer at gradient dy of its output [B][h][w][Cout]: db, dW, and (dx non-null) the gradient of its input
+    auto layer_back = [&](size_t li, int h, int w, const float *x, const float *y /* null: no ReLU */, const float *dy, const float *sum_with,
+                          float *dx) -> int {
+        const GradLayer &L = g->layers[li];
+        const long long M = (long long)B * h * w;
+        const float *dzp = dy;
+        if (y) {
+            WSC_TRY(launch_relu_bias_grad(ctx, y, dy, M, L.Cout, dz, partial, grad_dev + L.b_off));
+            dzp = dz;
+        } else {
+            WSC_TRY(launch_relu_bias_grad(ctx, nullptr, dy, M, L.Cout, nullptr, partial, grad_dev + L.b_off));
+        }
+        WSC_TRY(wgrad_launch(ctx, plans[li], x, dzp, h, w, L.Cin, L.Cout, L.k, L.dil, slab, grad_dev + L.w_off));
+        if (!dx) return WSC_OK;
+        if (dgrad_cz(L.Cout) != L.Cout) { // (fc8: the class count padded to 32 input channels)
+            WSC_TRY(launch_copy_channels(ctx, dzp, M, L.Cout, dgrad_cz(L.Cout), dz));
+            dzp = dz;
+        }
+        return dgrad_launch(ctx, dzp, L.w_rot, g->ones, g->zeros, B, h, w, L.Cin, L.Cout, L.k, L.dil, sum_with, dx);
+    };
+    auto at = [&](int entry) { return tape_dev + tp.e[entry].offset; };
+
+    // the branches, _1 ... _4: each receives dfc8; their gradients into pool5a's output are summed in that order
+    const int e_pool5a = tp.op_entry.back();
+    for (size_t k = 0; k < net->seg.size(); ++k) {
+        const size_t l6 = n_trunk + 3 * k;
+        WSC_TRY(layer_back(l6 + 2, hf, wf, at(tp.fc7[k]), nullptr, dfc8_dev, nullptr, ga));
+        WSC_TRY(layer_back(l6 + 1, hf, wf, at(tp.fc6[k]), at(tp.fc7[k]), ga, nullptr, gb));
+        WSC_TRY(layer_back(l6, hf, wf, at(e_pool5a), at(tp.fc6[k]), gb, k > 0 ? gs[(k + 1) & 1] : nullptr, gs[k & 1]));
+    }
+    // the trunk, last op first
+    const float *gcur = gs[(net->seg.size() - 1) & 1];
+    float *gfree[2] = {ga, gb};
+    int nf = 0;
+    for (int i = (int)net->ops.size() - 1; i >= 0; --i) {
+        const Op &op = net->ops[i];
+        const OpDims &d = tp.pl.ops[i];
+        const float *x = at(i == 0 ? 0 : tp.op_entry[i - 1]);
+        float *gout = gfree[nf];
+        if (op.type == OP_POOL) {
+            PoolGeom pg;
+            WSC_CHECK(pool_geom(op.rule, op.pk, op.ps, op.pp, op.avg, d.H, d.W, &pg), WSC_ERR_INVALID, "internal: a pool plan_dims let through");
+            WSC_TRY(launch_pool_grad(ctx, x, gcur, B, d.H, d.W, d.C, pg, gout));
+        } else {
+            WSC_TRY(layer_back((size_t)g->op_layer[i], d.Ho, d.Wo, x, at(tp.op_entry[i]), gcur, nullptr, i == 0 ? nullptr : gout));
+        }
+        gcur = gout;
+        nf ^= 1;
+    }
+    return WSC_OK;
 }
 
 // One convolution layer through the production kernel, NCHW fp32 in / out (layout changes and

@@ -253,6 +253,85 @@ int launch_pool(wsc_ctx *ctx, Act x, int N, int H, int W, int C, const PoolGeom 
     return WSC_OK;
 }
 
+// ---- the gradient with respect to the input (the backward pass of the SEC / DSRG nets, fp32 planes only) -----------------------
+namespace {
+
+// Gather form: one thread per 4 channels of an INPUT pixel walks the windows that cover it (<= 4 at stride 2, <= 9 at stride 1)
+// in row-major order of (ho, wo).  Max: the window's first maximum in row-major window order is recomputed from x (strict >, the
+// rule of torch's and TensorFlow's kernels; padding is never a candidate) and dy goes to that tap alone.  Average: dy / (in-image
+// tap count) to every tap.  No atomics, no argmax plane; the sum is in window order.
+template <bool AVG>
+__global__ __launch_bounds__(256) void pool_grad_f32_kernel(const float *__restrict__ x, const float *__restrict__ dy, PoolArgs a,
+                                                            float *__restrict__ dx) {
+    const int C4 = a.C >> 2;
+    const long long total = (long long)a.N * a.H * a.W * C4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % C4);
+        long long pix = i / C4;
+        const int wi = (int)(pix % a.W);
+        pix /= a.W;
+        const int hi = (int)(pix % a.H);
+        const int n = (int)(pix / a.H);
+        // windows ho with ho stride - pad_t <= hi <= ho stride - pad_t + k - 1
+        const int nh = hi + a.pad_t - a.k + 1, nw = wi + a.pad_l - a.k + 1;
+        const int ho_lo = nh > 0 ? (nh + a.stride - 1) / a.stride : 0, wo_lo = nw > 0 ? (nw + a.stride - 1) / a.stride : 0;
+        const int ho_hi = min((hi + a.pad_t) / a.stride, a.Ho - 1), wo_hi = min((wi + a.pad_l) / a.stride, a.Wo - 1);
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+        for (int ho = ho_lo; ho <= ho_hi; ++ho)
+            for (int wo = wo_lo; wo <= wo_hi; ++wo) {
+                const int h0 = ho * a.stride - a.pad_t, w0 = wo * a.stride - a.pad_l;
+                const f32x4_t g = *reinterpret_cast<const f32x4_t *>(dy + ((((long long)n * a.Ho + ho) * a.Wo + wo) * a.C + c4 * 4));
+                if (AVG) {
+                    const int cnt = (min(h0 + a.k, a.H) - max(h0, 0)) * (min(w0 + a.k, a.W) - max(w0, 0));
+                    const float fc = (float)cnt;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[j] += g[j] / fc;
+                } else {
+                    f32x4_t best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                    int arg[4] = {-1, -1, -1, -1};
+                    for (int dy_ = 0; dy_ < a.k; ++dy_) {
+                        const int h = h0 + dy_;
+                        if ((unsigned)h >= (unsigned)a.H) continue;
+                        for (int dx_ = 0; dx_ < a.k; ++dx_) {
+                            const int w = w0 + dx_;
+                            if ((unsigned)w >= (unsigned)a.W) continue;
+                            const f32x4_t v = *reinterpret_cast<const f32x4_t *>(x + ((((long long)n * a.H + h) * a.W + w) * a.C + c4 * 4));
+#pragma unroll
+                            for (int j = 0; j < 4; ++j)
+                                if (v[j] > best[j]) {
+                                    best[j] = v[j];
+                                    arg[j] = dy_ * a.k + dx_;
+                                }
+                        }
+                    }
+                    const int mine = (hi - h0) * a.k + (wi - w0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (arg[j] == mine) acc[j] += g[j];
+                }
+            }
+        *reinterpret_cast<f32x4_t *>(dx + ((((long long)n * a.H + hi) * a.W + wi) * a.C + c4 * 4)) = acc;
+    }
+}
+
+} // namespace
+
+int launch_pool_grad(wsc_ctx *ctx, const float *x, const float *dy, int N, int H, int W, int C, const PoolGeom &g, float *dx) {
+    WSC_CHECK(x && dy && dx, WSC_ERR_INVALID, "pool gradient: null argument");
+    WSC_CHECK(C > 0 && C % 4 == 0, WSC_ERR_INVALID, "pool gradient: C=%d not a multiple of 4", C);
+    WSC_CHECK(N > 0 && H > 0 && W > 0 && g.Ho >= 1 && g.Wo >= 1 && g.k >= 1 && g.stride >= 1 && g.pad_t >= 0 && g.pad_l >= 0 &&
+                  2 * g.pad_t <= g.k && 2 * g.pad_l <= g.k,
+              WSC_ERR_INVALID, "pool gradient: window %d stride %d padding %d / %d before on %d x %d x %d -> %d x %d", g.k, g.stride, g.pad_t,
+              g.pad_l, N, H, W, g.Ho, g.Wo);
+    const PoolArgs a = {N, H, W, C, g.Ho, g.Wo, g.k, g.stride, g.pad_t, g.pad_l};
+    WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, (2.0 * N * H * W * C + (double)N * g.Ho * g.Wo * C) * 4);
+    const dim3 grid(wsc_grid_for((long long)N * H * W * (C / 4))), block(256);
+    if (g.avg) hipLaunchKernelGGL((pool_grad_f32_kernel<true>), grid, block, 0, ctx->stream, x, dy, a, dx);
+    else hipLaunchKernelGGL((pool_grad_f32_kernel<false>), grid, block, 0, ctx->stream, x, dy, a, dx);
+    WSC_HIP(hipGetLastError());
+    return WSC_OK;
+}
+
 // ---- the per-layer entries: float32 NHWC through the activation planes of a precision, the production launcher unchanged ------
 namespace {
 
@@ -310,6 +389,17 @@ int wsc_pool_tf_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int 
     WSC_CHECK(pool_geom(same ? POOL_TF_SAME : POOL_TF_VALID, k, stride, 0, false, H, W, &g), WSC_ERR_INVALID,
               "wsc_pool_tf_nhwc: %d x %d x %d x %d is no input of a %d x %d %s window", N, H, W, C, k, k, same ? "SAME" : "VALID");
     return pool_staged(ctx, x_dev, N, H, W, C, g, precision, y_dev);
+}
+
+int wsc_pool_same_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int avg, int stride,
+                            float *dx_dev) {
+    WSC_TRY(check_tensor("wsc_pool_same_grad_nhwc", ctx, x_dev, dx_dev, N, H, W, C, WSC_PREC_F32));
+    WSC_CHECK(dy_dev != nullptr, WSC_ERR_INVALID, "wsc_pool_same_grad_nhwc: null argument");
+    PoolGeom g;
+    WSC_CHECK((stride == 1 || stride == 2) && (!avg || stride == 1) && pool_geom(POOL_TF_SAME, 3, stride, 0, avg != 0, H, W, &g),
+              WSC_ERR_INVALID, "wsc_pool_same_grad_nhwc: 3x3 max at stride 1 / 2 or 3x3 average at stride 1, got stride %d", stride);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return launch_pool_grad(ctx, x_dev, dy_dev, N, H, W, C, g, dx_dev);
 }
 
 } // extern "C"

@@ -70,6 +70,18 @@ class TraceOp(ctypes.Structure):
         "pool_rule", "pool_k", "pool_stride", "pool_pad", "pool_avg", "fused_next")] + [("label", ctypes.c_char * 100)]
 
 
+class TapeEntry(ctypes.Structure):
+    """wsc_tape_entry: one kept tensor of Net.seg_tape_plan"""
+    _fields_ = [("name", ctypes.c_char * 32), ("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("offset", ctypes.c_int64)]
+
+
+class GradEntry(ctypes.Structure):
+    """wsc_grad_entry: one layer of SegGrad.layout"""
+    _fields_ = [("name", ctypes.c_char * 32), ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("Cin", ctypes.c_int32),
+                ("Cout", ctypes.c_int32), ("w_off", ctypes.c_int64), ("b_off", ctypes.c_int64)]
+
+
 TRACE_CONV, TRACE_POOL, TRACE_GATHER, TRACE_HEAD = range(4)
 TRACE_INPUT, TRACE_NONE = -1, -2
 
@@ -126,6 +138,17 @@ _SIGNATURES = {
     "wsc_conv2d_nchw_dil": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "wsc_net_seg_size_hw": (_i, [_vp, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "wsc_net_forward_seg": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "wsc_net_seg_tape_plan": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i),
+                                   ctypes.POINTER(ctypes.c_longlong)]),
+    "wsc_net_forward_seg_tape": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, ctypes.c_longlong, _vp, _vp]),
+    "wsc_seg_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
+    "wsc_seg_grad_destroy": (None, [_vp]),
+    "wsc_seg_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
+    "wsc_net_backward_seg": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong]),
+    "wsc_conv2d_wgrad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "wsc_conv2d_dgrad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_relu_bias_grad": (_i, [_vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp]),
+    "wsc_pool_same_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "wsc_resize_bilinear_tf": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i]),
     "wsc_pool_same_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "wsc_pool_tf_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -588,6 +611,21 @@ class Net:
         check(self.ctx._lib.wsc_net_forward_seg(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(min_prob), _ptr(fc8_dev),
                                                 _ptr(prob_dev)))
 
+    def seg_tape_plan(self, B, H, W):
+        """wsc_net_seg_tape_plan: ([{'name', 'Ho', 'Wo', 'C', 'offset'}], tape_elems) -- the tensors a backward pass needs of a
+        forward pass of a B x H x W input, float32 NHWC at `offset` floats of one buffer of tape_elems floats."""
+        n, elems = _i(), ctypes.c_longlong()
+        check(self.ctx._lib.wsc_net_seg_tape_plan(self.ctx.h, self.h, int(B), int(H), int(W), None, 0, ctypes.byref(n), ctypes.byref(elems)))
+        ent = (TapeEntry * n.value)()
+        check(self.ctx._lib.wsc_net_seg_tape_plan(self.ctx.h, self.h, int(B), int(H), int(W), ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
+        return [{"name": e.name.decode(), "Ho": e.Ho, "Wo": e.Wo, "C": e.C, "offset": e.offset} for e in ent], elems.value
+
+    def forward_seg_tape(self, x_dev, B, H, W, tape_dev, tape_elems, prob_dev, fc8_dev=None, min_prob=1e-4, ctx=None):
+        """wsc_net_forward_seg_tape: forward_seg with the tape's tensors copied to tape_dev (float32, tape_elems of them)."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_forward_seg_tape(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(min_prob), _ptr(tape_dev),
+                                                     int(tape_elems), _ptr(fc8_dev), _ptr(prob_dev)))
+
     def trace_plan(self, N, H, W, ctx=None):
         """wsc_net_trace_plan: one dict per op of the stack for an N x H x W input (+ the CAM head), the fields of wsc_trace_op
         (`in` under its own name, the label as str).  Follows the options of `ctx` (the fused stem)."""
@@ -609,6 +647,69 @@ class Net:
         off = (ctypes.c_longlong * len(offsets))(*[int(o) for o in offsets])
         check(self.ctx._lib.wsc_net_forward_trace(run.h, self.h, _ptr(x_dev), int(N), int(H), int(W), off, len(offsets), _ptr(trace_dev),
                                                   int(trace_elems)))
+
+
+class SegGrad:
+    """wsc_seg_grad: what the backward pass of one ARCH_DEEPLAB_* net keeps (the data-gradient kernels, the workspace).
+    state_dict: the one the net was created from.  The net must outlive it."""
+
+    def __init__(self, net, state_dict):
+        self.ctx = net.ctx
+        self.net = net
+        descs, keep = make_tensor_descs(state_dict)
+        h = _vp()
+        check(self.ctx._lib.wsc_seg_grad_create(self.ctx.h, net.h, descs, len(descs), ctypes.byref(h)))
+        del keep
+        self.h = h
+        n, elems = _i(), ctypes.c_longlong()
+        check(self.ctx._lib.wsc_seg_grad_layout(h, None, 0, ctypes.byref(n), ctypes.byref(elems)))
+        ent = (GradEntry * n.value)()
+        check(self.ctx._lib.wsc_seg_grad_layout(h, ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
+        # layer -> its kernel, channels and the float offsets of dW (HWIO) and db in the gradient buffer
+        self.layout = {e.name.decode(): {"k": e.kh, "Cin": e.Cin, "Cout": e.Cout, "w_off": e.w_off, "b_off": e.b_off} for e in ent}
+        self.grad_elems = elems.value
+
+    def close(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx._lib.wsc_seg_grad_destroy(self.h)  # (drains the stream)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def backward(self, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, grad_elems=None):
+        """wsc_net_backward_seg: dfc8_dev float32 [B][h][w][C] -> every element of grad_dev (self.grad_elems floats), on the
+        net's own context (the workspace belongs to its stream)."""
+        check(self.ctx._lib.wsc_net_backward_seg(self.ctx.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfc8_dev),
+                                                 _ptr(grad_dev), int(self.grad_elems if grad_elems is None else grad_elems)))
+
+
+def conv2d_wgrad_nhwc(ctx, x_dev, dy_dev, N, H, W, Cin, Cout, k, dil, splits, dw_dev, db_dev):
+    """wsc_conv2d_wgrad_nhwc: dw_dev [k][k][Cin][Cout], db_dev [Cout] of a stride-1 SAME convolution; splits 0 = the launcher's."""
+    check(ctx._lib.wsc_conv2d_wgrad_nhwc(ctx.h, _ptr(x_dev), _ptr(dy_dev), int(N), int(H), int(W), int(Cin), int(Cout), int(k), int(dil),
+                                         int(splits), _ptr(dw_dev), _ptr(db_dev)))
+
+
+def conv2d_dgrad_nhwc(ctx, dy_dev, w, N, H, W, Cin, Cout, k, dil, dx_dev):
+    """wsc_conv2d_dgrad_nhwc: dx_dev [N][H][W][Cin] from dy_dev [N][H][W][Cout] and the host weights w [k][k][Cin][Cout]."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    assert w.shape == (k, k, Cin, Cout)
+    check(ctx._lib.wsc_conv2d_dgrad_nhwc(ctx.h, _ptr(dy_dev), _ptr(w), int(N), int(H), int(W), int(Cin), int(Cout), int(k), int(dil),
+                                         _ptr(dx_dev)))
+
+
+def relu_bias_grad(ctx, y_dev, dy_dev, M, C, dz_dev, db_dev):
+    """wsc_relu_bias_grad: dz = dy [y > 0] (y_dev None: dz = dy), db = the column sums of dz."""
+    check(ctx._lib.wsc_relu_bias_grad(ctx.h, _ptr(y_dev), _ptr(dy_dev), int(M), int(C), _ptr(dz_dev), _ptr(db_dev)))
+
+
+def pool_same_grad_nhwc(ctx, x_dev, dy_dev, N, H, W, C, avg, stride, dx_dev):
+    """wsc_pool_same_grad_nhwc: the gradient of pool_same_nhwc with respect to its input."""
+    check(ctx._lib.wsc_pool_same_grad_nhwc(ctx.h, _ptr(x_dev), _ptr(dy_dev), int(N), int(H), int(W), int(C), int(bool(avg)), int(stride),
+                                           _ptr(dx_dev)))
 
 
 def _key_table(keys_per_image, B=None):

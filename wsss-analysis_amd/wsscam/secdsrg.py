@@ -12,9 +12,12 @@
     SegLoss              getloss() (SEC.py:363-465, DSRG.py:459-518) and the gradient it sends into fc8 (wsc_seg_loss);
                          rank_weights forms SEC's rank-pooling tables; SegNet.loss_step_dev is the non-backward half of one
                          training step of Model.train at drop_prob = 0: forward, CRF layer, region growing, losses
+    SegGrads             opt.compute_gradients (model.py:382-387) at drop_prob = 0: SegNet.forward_dev(keep=True) keeps the tape,
+                         SegNet.backward_dev carries d loss / d fc8 to the gradient of every weight and bias, in exact fp32;
+                         SegNet.grad_step_dev is loss_step_dev followed by it
 
-The backward pass of the convolution stack, the optimiser, the weight decay term, dropout and the training loop of SEC / DSRG are
-out of scope.  Nothing here imports TensorFlow: Model.predict runs on this module alone."""
+The optimiser, the weight decay term, the learning-rate multipliers, dropout and the training loop of SEC / DSRG are out of scope
+(DESIGN.md section 7).  Nothing here imports TensorFlow: Model.predict runs on this module alone."""
 import numpy as np
 
 from . import _lib
@@ -57,6 +60,52 @@ class DeviceMaps:
         if self.buf is not None:
             self.buf.free()
             self.buf = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+class SegGrads:
+    """The gradient of every weight and bias of a SegNet, on the device: one float32 DeviceMaps (`maps`) and the `layout`
+    {layer: {'k', 'Cin', 'Cout', 'w_off', 'b_off'}} (offsets in floats).  grads[layer] downloads that layer as {'w': HWIO array,
+    'b': [Cout] array}; .ptr(layer, 'w' | 'b') is the device address for a trainer that wraps the buffer; .to_host() every layer
+    in one download; .free() / a context manager releases the buffer."""
+
+    def __init__(self, maps, layout):
+        self.maps = maps
+        self.layout = layout
+
+    def _shape(self, layer, which):
+        e = self.layout[layer]
+        return (e["k"], e["k"], e["Cin"], e["Cout"]) if which == "w" else (e["Cout"],)
+
+    def ptr(self, layer, which):
+        if which not in ("w", "b"):
+            raise KeyError("SegGrads: %r is neither 'w' nor 'b'" % (which,))
+        return self.maps.ptr + 4 * self.layout[layer][which + "_off"]
+
+    def keys(self):
+        return self.layout.keys()
+
+    def __getitem__(self, layer):
+        e = self.layout[layer]
+        return {which: self.maps.ctx.to_host(self.maps.buf, self._shape(layer, which), np.float32, offset_bytes=4 * e[which + "_off"])
+                for which in ("w", "b")}
+
+    def to_host(self):
+        flat = self.maps.to_host()
+        out = {}
+        for layer, e in self.layout.items():
+            out[layer] = {which: flat[e[which + "_off"]:e[which + "_off"] + int(np.prod(self._shape(layer, which)))]
+                          .reshape(self._shape(layer, which)).copy() for which in ("w", "b")}
+        return out
+
+    def free(self):
+        self.maps.free()
 
     def __enter__(self):
         return self
@@ -612,7 +661,8 @@ def seg_state_dict(method, weights, num_classes):
 
 
 class SegNet:
-    """The SEC / DSRG segmentation network on the device, forward pass only (drop_prob = 0).
+    """The SEC / DSRG segmentation network on the device at drop_prob = 0: the forward pass, and the backward pass from
+    d loss / d fc8 to the weight and bias gradients (forward_dev(keep=True), backward_dev, grad_step_dev).
 
     method 'SEC' (one fc6 / fc7 / fc8 branch at rate 12) or 'DSRG' (four ASPP branches at 6 / 12 / 18 / 24, fc8 their sum);
     weights as seg_state_dict takes them; precision _lib.PREC_F16X3 by default -- a forward whose activations leave half's range
@@ -625,11 +675,16 @@ class SegNet:
         sd = seg_state_dict(method, weights, self.C)
         self.ctx = ctx or default_context()
         self.net = _lib.Net(self.ctx, _lib.ARCH_DEEPLAB_LFOV if method == "SEC" else _lib.ARCH_DEEPLAB_ASPP, sd, self.C, precision)
+        self._sd = sd        # what the backward pass packs its data-gradient kernels from, on its first call
+        self._grad = None    # _lib.SegGrad, created lazily
 
     def close(self):
         """Releases the packed weights.  Never raises for a pending range error: the stream is drained through the non-raising
         wsc_ctx_range_status, not wsc_sync."""
         net = getattr(self, "net", None)
+        if getattr(self, "_grad", None) is not None:
+            self._grad.close()
+            self._grad = None
         if net is not None and getattr(net, "h", None) and self.ctx.h:
             self.ctx.range_status(clear=False)
             self.ctx._lib.wsc_net_destroy(net.h)
@@ -728,10 +783,12 @@ class SegNet:
             raise ValueError("SegNet: input %r must be (B, H, W, 3)" % (x.shape,))
         return DeviceMaps.from_host(self.ctx, x), True
 
-    def forward_dev(self, x, want_fc8=False):
+    def forward_dev(self, x, want_fc8=False, keep=False):
         """forward() with the maps left on the device: x a DeviceMaps (B, H, W, 3) (a host array is uploaded once) ->
         DeviceMaps (B, h, w, C) fc8-softmax; with want_fc8 (softmax, logits).  The range flag as in forward(): the stream is
-        drained through range_status(clear=True) and a saturated forward raises WscError(WSC_ERR_RANGE) once."""
+        drained through range_status(clear=True) and a saturated forward raises WscError(WSC_ERR_RANGE) once.
+        keep: the last element returned is the tape backward_dev takes -- a flat float32 DeviceMaps with `.entries` (the plan of
+        wsc_net_seg_tape_plan) and `.input_shape` (B, H, W); the maps have the bits of a forward without it."""
         ctx = self.ctx
         xd, mine = self._on_device(x)
         outs = []
@@ -739,7 +796,14 @@ class SegNet:
             B, H, W, _ = xd.shape
             h, w = self.map_size(H, W)
             outs = [DeviceMaps(ctx, (B, h, w, self.C), np.float32) for _ in range(2 if want_fc8 else 1)]
-            self.net.forward_seg(xd.ptr, B, H, W, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
+            if keep:
+                entries, elems = self.net.seg_tape_plan(B, H, W)
+                tape = DeviceMaps(ctx, (elems,), np.float32)
+                tape.entries, tape.input_shape = entries, (B, H, W)
+                outs.append(tape)
+                self.net.forward_seg_tape(xd.ptr, B, H, W, tape.ptr, elems, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
+            else:
+                self.net.forward_seg(xd.ptr, B, H, W, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
             flag = ctx.range_status(clear=True)  # drains the stream; the flag is scoped to this forward
             if flag:
                 raise _lib.WscError(_lib.WSC_ERR_RANGE, "SegNet: an activation reached half's ceiling (|v| >= 65504) in a layer "
@@ -751,7 +815,34 @@ class SegNet:
         finally:
             if mine:
                 xd.free()
-        return (outs[0], outs[1]) if want_fc8 else outs[0]
+        return tuple(outs) if len(outs) > 1 else outs[0]
+
+    def backward_dev(self, tape, dfc8):
+        """opt.compute_gradients at drop_prob = 0 (wsc_net_backward_seg): the tape of forward_dev(keep=True) and d loss / d fc8
+        (B, h, w, C) float32 -- a DeviceMaps, e.g. the gradient loss_step_dev returns, or a host array -- -> SegGrads.  The chain rule
+        evaluated at the tape, in exact fp32 whatever the net's precision.  The caller frees the result."""
+        ctx = self.ctx
+        if self._grad is None:
+            self._grad = _lib.SegGrad(self.net, self._sd)
+        B, H, W = tape.input_shape
+        want = (B,) + tuple(self.map_size(H, W)) + (self.C,)
+        gd, mine = dfc8, False
+        if not isinstance(dfc8, DeviceMaps):
+            gd, mine = DeviceMaps.from_host(ctx, dfc8, dtype=np.float32), True
+        out = None
+        try:
+            if gd.dtype != np.float32 or gd.shape != want:
+                raise ValueError("SegNet.backward_dev: dfc8 %r %s must be float32 %r, the fc8 map's shape" % (gd.shape, gd.dtype, want))
+            out = DeviceMaps(ctx, (self._grad.grad_elems,), np.float32)
+            self._grad.backward(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr)
+            return SegGrads(out, self._grad.layout)
+        except Exception:
+            if out is not None:
+                out.free()
+            raise
+        finally:
+            if mine:
+                gd.free()
 
     def softmax_dev(self, x):
         """net['fc8-softmax'] on the device: what SegEvaluator.update and crf_layer_dev take."""
@@ -803,6 +894,26 @@ class SegNet:
         -> (losses, grad, new_cues) as SegLoss returns the first two; new_cues a float32 DeviceMaps (B, h, w, C): DSRG's grown cues
         (a new buffer), for SEC the cues themselves on the device (the caller's DeviceMaps where one was given).  The caller frees
         grad and new_cues; every other buffer of the step is freed on every path."""
+        return self._loss_step(x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, want_grad, False)[:3]
+
+    def grad_step_dev(self, x, cues, labels_or_tags, img_mean, crf_config_train, seed_size=None):
+        """One training step of Model.train up to and including compute_gradients, at drop_prob = 0: loss_step_dev's chain on a
+        kept forward pass, then backward_dev on its gradient -> (losses, grads, new_cues): loss_step_dev's losses and new_cues (bit
+        for bit), grads a SegGrads.  The caller frees grads and new_cues; every other buffer of the step -- the tape and
+        d loss / d fc8 among them -- is freed on every path."""
+        losses, grad, new_cues, tape = self._loss_step(x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, "fc8", True)
+        try:
+            return losses, self.backward_dev(tape, grad), new_cues
+        except Exception:
+            if new_cues is not cues:
+                new_cues.free()
+            raise
+        finally:
+            grad.free()
+            tape.free()
+
+    def _loss_step(self, x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, want_grad, keep):
+        """loss_step_dev's body -> (losses, grad, new_cues, tape); tape (keep) is forward_dev's, else None"""
         ctx = self.ctx
         xd, x_mine = self._on_device(x)
         own, out = [], []  # buffers of the step, freed on every path; what the caller receives, freed on a failure only
@@ -811,7 +922,12 @@ class SegNet:
             if not isinstance(cues, DeviceMaps):
                 cd = DeviceMaps.from_host(ctx, cues, dtype=np.float32)
                 own.append(cd)
-            prob = self.forward_dev(xd)
+            tape = None
+            if keep:
+                prob, tape = self.forward_dev(xd, keep=True)
+                out.append(tape)
+            else:
+                prob = self.forward_dev(xd)
             own.append(prob)
             if cd.dtype != np.float32 or cd.shape != prob.shape:
                 raise ValueError("SegNet.loss_step_dev: cues %r %s must be float32 %r, the fc8 map's shape" % (cd.shape, cd.dtype, prob.shape))
@@ -827,7 +943,7 @@ class SegNet:
             loss = SegLoss(self.method, self.C, min_prob=self.min_prob, ctx=ctx)
             loss._weights = self.__dict__.setdefault("_rank_weights", {})  # SEC's tables, cached per map size on the net
             losses, grad = loss(prob, crf, new_cues, labels=labels_or_tags if self.method == "SEC" else None, want_grad=want_grad)
-            return losses, grad, new_cues
+            return losses, grad, new_cues, tape
         except Exception:
             for d in out:
                 d.free()
