@@ -9,11 +9,14 @@ float64, it is the reference every device gradient is held to.
 
 Tape names: "input", the trunk's layers, "pool:0" ... "pool:4" (behind conv1_2, conv2_2, conv3_3, conv4_3, conv5_3), "pool5a",
 and every branch's "fc6[_k]", "fc7[_k]".  Activations are NHWC numpy arrays, weights HWIO, as in deeplab_ref."""
+import functools
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from tests.deeplab_ref import ASPP_RATES, LFOV_RATE, THIN_CASES, TRUNK, avg_pool_same_t, layer_weights, max_pool_same_t
+from tests.deeplab_ref import (ASPP_RATES, LFOV_RATE, THIN_CASES, TRUNK, avg_pool_same_t, layer_weights, max_pool_same_t, net_input,
+                               random_weights)
 
 # The worst per-layer max|g32 - g64| / max|g64| of chain_grads in float32 against chain_grads in float64 on ONE float32 tape, over
 # GRAD_CASES at B = 2 with dfc8 = 1e-3 N(0, 1): measured by tests/test_deeplab_grad_oracle.py::test_float32_chain_error, which holds
@@ -21,6 +24,39 @@ from tests.deeplab_ref import ASPP_RATES, LFOV_RATE, THIN_CASES, TRUNK, avg_pool
 R32_CHAIN = 2.08e-6
 
 GRAD_CASES = THIN_CASES + [("SEC", 5, (97, 97)), ("DSRG", 5, (97, 97))]
+
+# The real widths (64 / 128 / 256 / 512 / 512, fc 1024, 21 classes), He-scaled like a checkpoint: (method, C, (H, W), B).  65 x 65 is
+# a 9 x 9 map (SEC's fc6 and DSRG's fc6_2 ... fc6_4: the centre tap only; fc6_1 at rate 6: all nine), 64 x 48 an 8 x 6 map (fc6_1: the
+# middle column of taps only).
+FULL_WIDTHS = (64, 128, 256, 512, 512)
+FULL_FC_WIDTH = 1024
+FULL_GRAD_CASES = [("SEC", 21, (65, 65), 1), ("DSRG", 21, (65, 65), 1), ("DSRG", 21, (64, 48), 2)]
+
+# R32_CHAIN's figure over FULL_GRAD_CASES (full_case's inputs, full_dfc8's gradient): the worst layer is conv2_1 of
+# ("DSRG", 21, (65, 65), 1) (SEC 65 x 65: 1.05e-6 at conv1_2; DSRG 64 x 48, B = 2: 1.46e-6 at conv2_1); measured by
+# tests/test_deeplab_grad_oracle.py::test_float32_chain_error_full_width, which holds the re-measured figure to 1.5 x this.  The
+# device's full-width end-to-end bound is 64 x this.
+R32_CHAIN_FULL = 1.54e-6
+
+
+@functools.lru_cache(maxsize=None)
+def full_weights(method, C):
+    """the weights of the forward pass's full-width test: built once per (method, C), shared, never modified"""
+    return random_weights(method, C, fc_width=FULL_FC_WIDTH, seed=11, widths=FULL_WIDTHS)
+
+
+def full_case(case):
+    """-> (weights, x) of a FULL_GRAD_CASES entry: the weights and the input recipe of the forward pass's full-width test"""
+    method, C, hw, B = case
+    return full_weights(method, C), net_input(B, hw[0], hw[1], 12)
+
+
+def full_dfc8(case, shape):
+    """d loss / d fc8 of a FULL_GRAD_CASES entry: 1e-3 N(0, 1), the seed from the case"""
+    method, C, hw, B = case
+    rng = np.random.default_rng(1900 + 3 * C + hw[1] + 7 * B + (1 if method == "SEC" else 0))
+    return (1e-3 * rng.standard_normal(shape)).astype(np.float32)
+
 
 POOL_AFTER = {"conv1_2": 2, "conv2_2": 2, "conv3_3": 2, "conv4_3": 1, "conv5_3": 1}  # layer -> stride of the max pool behind it
 
