@@ -299,8 +299,10 @@ int wsc_conv2d_nchw_dil(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H,
 
 /* ---- SEC / DSRG segmentation network (03a_sec-dsrg) ----------------------- */
 
-/* The DeepLab-VGG16 forward pass of SEC / DSRG at drop_prob = 0 (every non-training phase; the optimiser and the training loop
- * are out of scope, the losses and their gradient into fc8 are wsc_seg_loss).  A net created with WSC_ARCH_DEEPLAB_LFOV / _ASPP takes its weights under the reference's
+/* The DeepLab-VGG16 forward pass of SEC / DSRG at drop_prob = 0 (every non-training phase, and the training step of the
+ * reference's `debug` graph: the losses and their gradient into fc8 are wsc_seg_loss, the backward pass wsc_net_backward_seg, the
+ * SGD-momentum update and the write-back of the weights wsc_seg_sgd_* / wsc_net_seg_load_params below; dropout at drop_prob > 0
+ * is out of scope).  A net created with WSC_ARCH_DEEPLAB_LFOV / _ASPP takes its weights under the reference's
  * layer names (get_weights_and_bias, DSRG.py:379-425): `conv1_1` ... `conv5_3`, and `fc6`, `fc7`, `fc8` (LFOV) or `fc6_1` ...
  * `fc8_4` (ASPP); each as `<layer>.w` in TensorFlow's HWIO order [kh][kw][Cin][Cout] and `<layer>.b` [Cout].  Channel widths
  * are read from the tensors (multiples of 64; fc8 has num_classes outputs).  A missing or mis-shaped tensor is WSC_ERR_SHAPE
@@ -381,8 +383,8 @@ int wsc_fc8_softmax(wsc_ctx *ctx, const float *const *fc8_dev, int n_in, long lo
  * pass (hi + lo of a two-plane precision, exact in fp32).  A ReLU passes dy where its kept output is > 0, else +0.0; a max pool
  * sends a window's dy to the window's first maximum in row-major window order (padding is never a candidate); pool5a sends
  * dy / (in-image tap count) to every in-image tap; every ASPP branch receives dfc8 and their gradients into pool5a's output are
- * summed in the order _1 ... _4; no gradient is formed for the network input.  Out of scope: dropout, the weight-decay term, the
- * learning-rate multipliers, the optimiser.
+ * summed in the order _1 ... _4; no gradient is formed for the network input.  The weight-decay term, the learning-rate
+ * multipliers and the optimiser follow below (wsc_seg_sgd_*); out of scope: dropout.
  *
  * The tape: wsc_net_seg_tape_plan lists the kept tensors for a B x H x W input -- "input", every op of the trunk ("conv1_1", ...,
  * "pool:0", ..., "pool5a"), every branch's "fc6[_k]" and "fc7[_k]" -- each float32 NHWC [B][Ho][Wo][C] at `offset` floats of one
@@ -435,6 +437,39 @@ int wsc_conv2d_dgrad_nhwc(wsc_ctx *ctx, const float *dy_dev, const float *w_host
 int wsc_relu_bias_grad(wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float *dz_dev, float *db_dev);
 int wsc_pool_same_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int avg, int stride,
                             float *dx_dev);
+
+/* ---- the update half of the training step: Model.optimize() and the update branch of Model.train() ------------------------------
+ * (model.py:379-404, 491-504) at drop_prob = 0.  Parameters, the momentum slot and the gradient accumulator are each ONE fp32
+ * device buffer of grad_elems floats in the layout of wsc_seg_grad_layout (per layer w in HWIO, then b, no gaps): a gradient
+ * buffer of wsc_net_backward_seg, a parameter buffer and a slot buffer are element-for-element parallel.  Both calls are
+ * asynchronous on the ctx stream; every product, sum and quotient below is rounded to fp32 on its own (no fused multiply-add).
+ *
+ * wsc_seg_sgd_accumulate: the graph op `accum_gradient_accum` with the gradient of loss["total"] = norm + weight_decay l2:
+ *     t = grad + weight_decay param   on the weights of every layer (fc8 included: l2 sums over weights[layer][0]); t = grad on biases
+ *     t = mult t                      mult = 1 (weights), 2 (biases), 10 (fc8 weights), 20 (fc8 biases); fc8 = `fc8`, `fc8_1` .. `fc8_4`
+ *     accum += t / accum_num
+ *   l2_dev: NULL, or one float that receives loss["l2"] = sum over the layers of sum(w^2) / 2, accumulated in double in one fixed
+ *   order (per-block partials, then the last block to arrive -- an integer ticket -- adds them in block order) and rounded once:
+ *   two calls give the same bits, no floating-point atomic.  The other outputs do not depend on l2_dev.
+ * wsc_seg_sgd_apply: `accum_gradient_update` then (clear_accum) `accum_gradient_clean` -- TensorFlow's ApplyMomentum without
+ *   Nesterov on the accumulated gradient: mom = mom momentum + accum, param = param - lr mom; clear_accum: accum = +0.0.
+ * Both return WSC_ERR_INVALID before any launch when elems is not the layout's grad_elems, ctx is not the context the
+ * wsc_seg_grad was created on (its l2 scratch belongs to that stream), or a pointer that must not be NULL is.
+ *
+ * wsc_net_seg_load_params: rewrites, in place and without a host copy, everything derived from the weights, from the floats of
+ * param_dev: (a) of every convolution of the net (the trunk, fc6 / fc7 / fc8 of every branch) the packed weight rows in the
+ * kernel's K order -- the IEEE-half modes with the per-output-channel power-of-two scale taken from the channel's largest |w|,
+ * the split modes with both parts --, the epilogue scale and the bias; (b) every layer's rotated, channel-transposed fp32
+ * data-gradient kernel in the wsc_seg_grad.  Afterwards the device weights of both objects are byte for byte what wsc_net_create
+ * and wsc_seg_grad_create make of the same floats.  `g` must be the wsc_seg_grad of `net`, ctx its context.  The call WRITES the
+ * net: the net must not be in use on another stream during it, and work of other streams that reads the net must be ordered
+ * behind it by the caller (wsc_ctx_wait).  A net that is no WSC_ARCH_DEEPLAB_* net, a foreign ctx or a wrong elems is
+ * WSC_ERR_INVALID before any launch.  Asynchronous on the ctx stream. */
+int wsc_seg_sgd_accumulate(wsc_ctx *ctx, wsc_seg_grad *g, const float *param_dev, const float *grad_dev, float *accum_dev,
+                           long long elems, float weight_decay, int accum_num, float *l2_dev);
+int wsc_seg_sgd_apply(wsc_ctx *ctx, wsc_seg_grad *g, float *param_dev, float *accum_dev, float *mom_dev, long long elems, float lr,
+                      float momentum, int clear_accum);
+int wsc_net_seg_load_params(wsc_ctx *ctx, wsc_net *net, wsc_seg_grad *g, const float *param_dev, long long elems);
 
 /* The per-op view of a forward pass, for the per-op tests (tests/test_gpu_net_trace.py): what the conv stack of a net does for an
  * N x H x W input, one entry per op in execution order plus one for the CAM head where the net has one, and a forward pass that
@@ -623,7 +658,8 @@ int wsc_dsrg_seed_grow(wsc_ctx *ctx, const float *tags_dev, const float *cues_de
 /* The loss head of the training graph and the gradient it sends into fc8 (03a_sec-dsrg/SEC.py:363-465 getloss, get_seed_loss,
  * get_expand_loss, get_constrain_loss; DSRG.py:459-518 getloss, get_balanced_seed_loss, get_constrain_loss).  `crf` and the cues
  * come out of tf.py_func in the reference graph, so they are constants to the gradient: no backward pass through the CRF or the
- * region growing.  Out of scope: the backward pass of the convolution stack, the optimiser, the weight decay term, dropout.
+ * region growing.  The backward pass of the convolution stack is wsc_net_backward_seg, the weight decay term and the optimiser
+ * wsc_seg_sgd_*; out of scope: dropout.
  *   prob_dev   float32 [B][H][W][C]  fc8-softmax p (wsc_net_forward_seg), > 0;  n = H W
  *   crf_dev    float32 [B][H][W][C]  the CRF layer's log-probabilities (wsc_seg_crf_logprob);  q = exp(crf)
  *   cues_dev   float32 [B][H][W][C]  0/1 (DSRG: the grown cues of wsc_dsrg_seed_grow)

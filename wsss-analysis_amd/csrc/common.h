@@ -317,6 +317,25 @@ inline ConvKLayout conv_k_layout(int kh, int kw, int Cin, ConvForm form, wsc_pre
     L.lo_at = L.interleaved ? 32 : L.Kbase;
     return L;
 }
+// The IEEE-half modes store every output channel's weights times 2^shift, the power of two that puts the channel's largest |w|
+// (`mx`) into [2^12, 2^13): mx = m 2^e with m in [0.5, 1) (frexp, fp32 denormals included), shift = 13 - e bounded to +-100 (a
+// channel of ~1e-40 would otherwise ask for 2^(13 - e) = inf); a channel whose maximum is zero or not finite keeps shift 0.
+// Integer arithmetic on the bits: the host packing (net.hip make_conv) and the device repack (seg_sgd.hip) get the same shift.
+__host__ __device__ inline int conv_half_shift(float mx) {
+    union { float f; uint32_t u; } v;
+    v.f = mx;
+    if (!(mx > 0.f) || (v.u & 0x7f800000u) == 0x7f800000u) return 0;
+    const int E = (int)(v.u >> 23);
+    const int e = E ? E - 126 : (31 - __builtin_clz(v.u)) - 148; // (denormal: M 2^-149, its top bit at 31 - clz)
+    const int sh = 13 - e;
+    return sh > 100 ? 100 : (sh < -100 ? -100 : sh);
+}
+// 2^sh as fp32, |sh| <= 126
+__host__ __device__ inline float conv_pow2(int sh) {
+    union { float f; uint32_t u; } v;
+    v.u = (uint32_t)(sh + 127) << 23;
+    return v.f;
+}
 // rows of the packed weights (and of scale / shift): whole 64-column tiles up to 64 channels, whole 128-column tiles beyond
 inline int conv_cout_pad(int Cout) { return Cout <= 64 ? 64 : ((Cout + 127) / 128) * 128; }
 // ... and the tile width the kernel takes for them
@@ -512,6 +531,55 @@ inline int dgrad_cz(int Cout) { return (Cout + 31) / 32 * 32; }
 void dgrad_pack(const float *w_hwio, int k, int Cin, int Cout, std::vector<float> *packed);
 int dgrad_launch(wsc_ctx *ctx, const float *dz, const float *w_packed, const float *ones, const float *zeros, int N, int H, int W, int Cin,
                  int Cout, int k, int dil, const float *sum_with, float *dx);
+
+// ---- seg_sgd.hip: the SGD-momentum step on the flat parameter layout of wsc_seg_grad_layout, and the device repack --------------
+// One run of floats of that layout with one learning-rate multiplier: a layer's w (decay = 1: the weight-decay term applies and
+// the floats count into loss["l2"]) or its b.  The table has a segment per run in offset order; the kernels find an element's
+// segment themselves, so the offsets may be any (odd ones included).
+struct SgdSegment {
+    long long start; // first float
+    float mult;      // 1 / 2 (bias) / 10 (fc8 w) / 20 (fc8 b)
+    int decay;
+};
+constexpr int SGD_MAX_SEGMENTS = 128;  // (a DSRG net has 50)
+constexpr int SGD_L2_MAX_BLOCKS = 1024; // blocks of the accumulate kernel = doubles of `l2_partials`
+// accum += mult (grad [+ wd param]) / accum_num, every operation rounded to fp32 on its own; l2_dev (or null) = sum w^2 / 2 over the
+// decay segments, summed in double in a fixed order (l2_partials: SGD_L2_MAX_BLOCKS doubles, l2_counter: one unsigned, both the
+// caller's and used by one stream)
+int sgd_accumulate_launch(wsc_ctx *ctx, const SgdSegment *segs_dev, int n_segs, const float *param, const float *grad, float *accum,
+                          long long elems, float weight_decay, int accum_num, double *l2_partials, unsigned *l2_counter, float *l2_dev);
+// mom = mom momentum + accum, param -= lr mom (TensorFlow's ApplyMomentum, use_nesterov = False); clear_accum: accum = +0.0
+int sgd_apply_launch(wsc_ctx *ctx, float *param, float *accum, float *mom, long long elems, float lr, float momentum, int clear_accum);
+// The device repack: every DeepLab layer's weights w [k][k][Cin][Cout] (HWIO) and bias b [Cout], at their offsets of the flat
+// parameter buffer, into everything derived from them -- the packed rows `wp` [CoutPad][Kw] of conv_k_layout(k, k, Cin or 4, form,
+// prec) with s1 / b1, the bytes make_conv gives, and (w_rot non-null) the rotated, channel-transposed fp32 kernel of dgrad_pack.
+// One RepackJob per layer in a device table built once per wsc_seg_grad: the caller fills the layer's fields, repack_plan adds the
+// layout, the split of the channel maxima and where the layer's blocks lie in each of the (at most four) launches of a repack.
+struct RepackJob {
+    long long w_off, b_off;          // floats into the parameter buffer
+    int k, Cin, Cout;                // Cin as in the HWIO tensor (3 for the first layer)
+    int small;                       // CONV_FORM_SMALL2 (the first layer), else CONV_FORM_GENERIC
+    int kstep, Kw, lo_at, nsteps;    // conv_k_layout; nsteps: the K-steps of one precision segment
+    int rot_Kw;                      // k k dgrad_cz(Cout), the row of the rotated kernel; 0 without one
+    int splits, rows_per;            // partial channel maxima (IEEE-half modes, generic layers): row ranges of rows_per rows
+    int max_block0, pack_block0, rot_block0; // the layer's first block in the maxima / pack / rotate launch
+    int tiles;                       // 64-channel column tiles
+    long long pmax_off;              // floats into the scratch of the partial maxima
+    void *wp;
+    float *s1, *b1, *w_rot;
+};
+struct RepackPlan {
+    RepackJob *jobs_dev = nullptr;
+    int n_jobs = 0, small_job = -1, small_tiles = 0;
+    int ck = 0; // channels of a generic layer's K-step (conv_k_layout)
+    int max_blocks = 0, pack_blocks = 0, rot_blocks = 0;
+    long long pmax_elems = 0;
+    float *pmax = nullptr;
+    wsc_precision prec = WSC_PREC_BF16;
+    double bytes = 0; // algorithmic traffic of one repack
+};
+int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *plan);
+int repack_launch(wsc_ctx *ctx, const RepackPlan &plan, const float *param);
 
 // ---- deeplab.hip: the kernels around the conv stack of the SEC / DSRG DeepLab nets -------------------------------------
 // float32 [N][H][W][3] -> NHWC4 activation (raises the range flag where an IEEE-half plane saturates)

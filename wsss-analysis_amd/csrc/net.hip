@@ -211,15 +211,12 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
         for (int co = 0; co < Cout; ++co) {
             float mx = 0.f;
             for (size_t i = 0; i < per; ++i) mx = std::max(mx, std::fabs(w->data[(size_t)co * per + i]));
-            if (!(mx > 0.f) || !std::isfinite(mx)) continue;
-            int e;
-            std::frexp(mx, &e); // mx = m * 2^e, m in [0.5, 1)
             // (bounded shift: a dead channel in fp32's denormal range -- weight decay leaves |w| ~ 1e-40 -- would otherwise
             // ask for 2^(13 - e) = inf, every weight * inf = inf, lo = inf - inf = NaN; with the bound such a channel keeps
             // its tiny values as half subnormals / zeros like before the packing)
-            const int sh = std::max(std::min(13 - e, 100), -100);
-            wscale[co] = std::ldexp(1.f, sh);
-            s1v[co] = s1[co] * std::ldexp(1.f, -sh);
+            const int sh = conv_half_shift(mx); // (common.h: the device repack of seg_sgd.hip takes the same shift)
+            wscale[co] = conv_pow2(sh);
+            s1v[co] = s1[co] * conv_pow2(-sh);
         }
     }
     for (int co = 0; co < Cout; ++co) {
@@ -1470,6 +1467,13 @@ struct wsc_seg_grad {
     float *ones = nullptr, *zeros = nullptr; // conv_cout_pad(widest layer) of each
     void *ws = nullptr;            // the backward workspace, grown on demand
     size_t ws_bytes = 0;
+    // the optimiser's view of the layout (seg_sgd.hip): a segment per w and per b in offset order, built once; the partials and
+    // the arrival counter of loss["l2"]
+    SgdSegment *segs = nullptr;
+    int n_segs = 0;
+    double *l2_partials = nullptr;
+    unsigned *l2_counter = nullptr;
+    RepackPlan repack;             // the per-layer jobs of wsc_net_seg_load_params, built by its first call
     std::vector<void *> allocs;
 };
 
@@ -1545,6 +1549,32 @@ int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
     }
     int st = up(std::vector<float>(widest, 1.f), &g->ones);
     if (st == WSC_OK) st = up(std::vector<float>(widest, 0.f), &g->zeros);
+    if (st != WSC_OK) return fail(st);
+    // the segment table of the optimiser: lr multipliers 1 (w) / 2 (b), 10 / 20 on fc8 (model.py:393-398, DSRG.py:434-439)
+    std::vector<SgdSegment> segs;
+    for (const GradLayer &L : g->layers) {
+        const bool fc8 = L.name.compare(0, 3, "fc8") == 0;
+        segs.push_back({L.w_off, fc8 ? 10.f : 1.f, 1});
+        segs.push_back({L.b_off, fc8 ? 20.f : 2.f, 0});
+    }
+    if ((int)segs.size() > SGD_MAX_SEGMENTS || g->grad_elems >= (1ll << 31)) {
+        wsc_set_error("wsc_seg_grad_create: %d layers, %lld parameters", (int)g->layers.size(), g->grad_elems);
+        return fail(WSC_ERR_INVALID);
+    }
+    g->n_segs = (int)segs.size();
+    auto dev_alloc = [&](size_t bytes, void **dst) -> int {
+        WSC_HIP(hipMalloc(dst, bytes));
+        g->allocs.push_back(*dst);
+        WSC_HIP(hipMemset(*dst, 0, bytes));
+        return WSC_OK;
+    };
+    st = dev_alloc(segs.size() * sizeof(SgdSegment), (void **)&g->segs);
+    if (st == WSC_OK && hipMemcpy(g->segs, segs.data(), segs.size() * sizeof(SgdSegment), hipMemcpyHostToDevice) != hipSuccess) {
+        wsc_set_error("wsc_seg_grad_create: the upload of the segment table failed");
+        st = WSC_ERR_HIP;
+    }
+    if (st == WSC_OK) st = dev_alloc(SGD_L2_MAX_BLOCKS * sizeof(double), (void **)&g->l2_partials);
+    if (st == WSC_OK) st = dev_alloc(256, (void **)&g->l2_counter);
     if (st != WSC_OK) return fail(st);
     *out = g;
     return WSC_OK;
@@ -1671,6 +1701,86 @@ int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, con
         nf ^= 1;
     }
     return WSC_OK;
+}
+
+// ---- the update half of the training step: Model.optimize() (model.py:379-404) on the layout of wsc_seg_grad_layout ----------------
+namespace {
+int sgd_check(const char *fn, const wsc_ctx *ctx, const wsc_seg_grad *g, long long elems, bool pointers) {
+    WSC_CHECK(ctx && g && pointers, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "%s: the context is not the one the wsc_seg_grad was created on", fn);
+    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "%s: buffers of %lld floats, the layout has %lld", fn, elems, g->grad_elems);
+    return WSC_OK;
+}
+} // namespace
+
+int wsc_seg_sgd_accumulate(wsc_ctx *ctx, wsc_seg_grad *g, const float *param_dev, const float *grad_dev, float *accum_dev, long long elems,
+                           float weight_decay, int accum_num, float *l2_dev) {
+    WSC_TRY(sgd_check("wsc_seg_sgd_accumulate", ctx, g, elems, param_dev && grad_dev && accum_dev));
+    WSC_CHECK(accum_num >= 1, WSC_ERR_INVALID, "wsc_seg_sgd_accumulate: accum_num=%d", accum_num);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return sgd_accumulate_launch(ctx, g->segs, g->n_segs, param_dev, grad_dev, accum_dev, elems, weight_decay, accum_num, g->l2_partials,
+                                 g->l2_counter, l2_dev);
+}
+
+int wsc_seg_sgd_apply(wsc_ctx *ctx, wsc_seg_grad *g, float *param_dev, float *accum_dev, float *mom_dev, long long elems, float lr,
+                      float momentum, int clear_accum) {
+    WSC_TRY(sgd_check("wsc_seg_sgd_apply", ctx, g, elems, param_dev && accum_dev && mom_dev));
+    WSC_HIP(hipSetDevice(ctx->device));
+    return sgd_apply_launch(ctx, param_dev, accum_dev, mom_dev, elems, lr, momentum, clear_accum);
+}
+
+int wsc_net_seg_load_params(wsc_ctx *ctx, wsc_net *net, wsc_seg_grad *g, const float *param_dev, long long elems) {
+    WSC_CHECK(ctx && net && g && param_dev, WSC_ERR_INVALID, "wsc_net_seg_load_params: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_seg_load_params: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_CHECK(g->net == net, WSC_ERR_INVALID, "wsc_net_seg_load_params: the wsc_seg_grad was created for another net");
+    WSC_TRY(sgd_check("wsc_net_seg_load_params", ctx, g, elems, true));
+    // the layers in the order wsc_seg_grad_create listed them: the trunk's convs in op order, then fc6, fc7, fc8 of every branch
+    std::vector<ConvW *> convs;
+    for (const Op &op : net->ops)
+        if (op.type == OP_CONV) convs.push_back(&net->convs[op.conv]);
+    for (SegBranch &br : net->seg) {
+        convs.push_back(&br.fc6);
+        convs.push_back(&br.fc7);
+        convs.push_back(&br.fc8);
+    }
+    WSC_CHECK(convs.size() == g->layers.size(), WSC_ERR_INVALID, "internal: %d layers of the net, %d of the layout", (int)convs.size(),
+              (int)g->layers.size());
+    for (size_t i = 0; i < convs.size(); ++i) {
+        const ConvW &c = *convs[i];
+        const GradLayer &L = g->layers[i];
+        WSC_CHECK(c.kh == L.k && c.kw == L.k && c.Cout == L.Cout && (c.form == CONV_FORM_GENERIC ? c.Cin == L.Cin : (c.Cin == 4 && L.Cin <= 4)) &&
+                      !c.s2 && !c.b2,
+                  WSC_ERR_INVALID, "internal: layer '%s' of the layout is not the net's", L.name.c_str());
+    }
+    WSC_HIP(hipSetDevice(ctx->device));
+    if (!g->repack.jobs_dev) { // the job table: once per wsc_seg_grad (the packed buffers of both objects never move)
+        std::vector<RepackJob> jobs(convs.size());
+        for (size_t i = 0; i < convs.size(); ++i) {
+            const ConvW &c = *convs[i];
+            const GradLayer &L = g->layers[i];
+            RepackJob &J = jobs[i];
+            J = RepackJob();
+            J.w_off = L.w_off; J.b_off = L.b_off;
+            J.k = L.k; J.Cin = L.Cin; J.Cout = L.Cout;
+            J.small = c.form != CONV_FORM_GENERIC;
+            J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
+            J.w_rot = L.w_rot;
+        }
+        RepackPlan plan;
+        WSC_TRY(repack_plan(jobs, net->prec, &plan));
+        void *jd = nullptr, *pm = nullptr;
+        WSC_HIP(hipMalloc(&jd, jobs.size() * sizeof(RepackJob)));
+        g->allocs.push_back(jd);
+        WSC_HIP(hipMemcpy(jd, jobs.data(), jobs.size() * sizeof(RepackJob), hipMemcpyHostToDevice));
+        if (plan.pmax_elems > 0) {
+            WSC_HIP(hipMalloc(&pm, (size_t)plan.pmax_elems * sizeof(float)));
+            g->allocs.push_back(pm);
+        }
+        plan.pmax = (float *)pm;
+        plan.jobs_dev = (RepackJob *)jd;
+        g->repack = plan;
+    }
+    return repack_launch(ctx, g->repack, param_dev);
 }
 
 // One convolution layer through the production kernel, NCHW fp32 in / out (layout changes and

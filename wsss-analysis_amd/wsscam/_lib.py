@@ -146,6 +146,9 @@ _SIGNATURES = {
     "wsc_seg_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_backward_seg": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong]),
     "wsc_conv2d_wgrad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "wsc_seg_sgd_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _i, _vp]),
+    "wsc_seg_sgd_apply": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _f, _i]),
+    "wsc_net_seg_load_params": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong]),
     "wsc_conv2d_dgrad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "wsc_relu_bias_grad": (_i, [_vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp]),
     "wsc_pool_same_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -685,6 +688,28 @@ class SegGrad:
         net's own context (the workspace belongs to its stream)."""
         check(self.ctx._lib.wsc_net_backward_seg(self.ctx.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfc8_dev),
                                                  _ptr(grad_dev), int(self.grad_elems if grad_elems is None else grad_elems)))
+
+
+    def sgd_accumulate(self, param_dev, grad_dev, accum_dev, weight_decay, accum_num, l2_dev=None, elems=None, ctx=None):
+        """wsc_seg_sgd_accumulate on three buffers of self.grad_elems floats in self.layout: accum += mult (grad [+ weight_decay
+        param on weights]) / accum_num; l2_dev (optional, one float) receives loss["l2"]."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_seg_sgd_accumulate(run.h, self.h, _ptr(param_dev), _ptr(grad_dev), _ptr(accum_dev),
+                                                   int(self.grad_elems if elems is None else elems), float(weight_decay), int(accum_num),
+                                                   _ptr(l2_dev)))
+
+    def sgd_apply(self, param_dev, accum_dev, mom_dev, lr, momentum, clear_accum=True, elems=None, ctx=None):
+        """wsc_seg_sgd_apply: mom = mom momentum + accum, param -= lr mom, and (clear_accum) accum = 0."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_seg_sgd_apply(run.h, self.h, _ptr(param_dev), _ptr(accum_dev), _ptr(mom_dev),
+                                              int(self.grad_elems if elems is None else elems), float(lr), float(momentum), int(bool(clear_accum))))
+
+    def load_params(self, param_dev, elems=None, net=None, ctx=None):
+        """wsc_net_seg_load_params: the net's packed weights and this object's data-gradient kernels rewritten on the device from
+        the flat parameter buffer.  The net must not be in use on another stream."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_seg_load_params(run.h, (net or self.net).h, self.h, _ptr(param_dev),
+                                                    int(self.grad_elems if elems is None else elems)))
 
 
 def conv2d_wgrad_nhwc(ctx, x_dev, dy_dev, N, H, W, Cin, Cout, k, dil, splits, dw_dev, db_dev):

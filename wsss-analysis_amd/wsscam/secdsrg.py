@@ -16,8 +16,13 @@
                          SegNet.backward_dev carries d loss / d fc8 to the gradient of every weight and bias, in exact fp32;
                          SegNet.grad_step_dev is loss_step_dev followed by it
 
-The optimiser, the weight decay term, the learning-rate multipliers, dropout and the training loop of SEC / DSRG are out of scope
-(DESIGN.md section 7).  Nothing here imports TensorFlow: Model.predict runs on this module alone."""
+    SegTrainer           Model.optimize() and the update branch of Model.train() (model.py:379-404, 491-504) at drop_prob = 0, the
+                         reference's `debug` graph: the weight decay term, the lr multipliers, gradient accumulation, the momentum
+                         update and the write-back of the weights into the net (wsc_seg_sgd_accumulate / _apply,
+                         wsc_net_seg_load_params); parameters, momentum and accumulator never leave the device
+
+Dropout at drop_prob > 0 and reading TensorFlow checkpoints are out of scope.  Nothing here imports
+TensorFlow: Model.predict runs on this module alone."""
 import numpy as np
 
 from . import _lib
@@ -844,6 +849,42 @@ class SegNet:
             if mine:
                 gd.free()
 
+    def _ensure_grad(self):
+        if self._grad is None:
+            self._grad = _lib.SegGrad(self.net, self._sd)
+        return self._grad
+
+    def flat_params(self, weights):
+        """Weights in either form seg_state_dict takes -> one float32 array in the layout of wsc_seg_grad_layout (per layer w in
+        HWIO, then b): the host form of what load_params_dev takes.  The shapes must be the net's."""
+        g = self._ensure_grad()
+        sd = seg_state_dict(self.method, weights, self.C)
+        flat = np.empty((g.grad_elems,), np.float32)
+        for layer, e in g.layout.items():
+            w, b = sd[layer + ".w"], sd[layer + ".b"]
+            if w.shape != (e["k"], e["k"], e["Cin"], e["Cout"]):
+                raise ValueError("SegNet.flat_params: layer %r is %r, the net has %r" % (layer, w.shape, (e["k"], e["k"], e["Cin"], e["Cout"])))
+            flat[e["w_off"]:e["w_off"] + w.size] = w.reshape(-1)
+            flat[e["b_off"]:e["b_off"] + b.size] = b
+        return flat
+
+    def load_params_dev(self, flat):
+        """wsc_net_seg_load_params: every packed weight of the net and every data-gradient kernel of its backward pass rewritten on
+        the device from `flat`, float32 (grad_elems,) in the layout of SegGrads -- a DeviceMaps (read in place), or a host array
+        (uploaded once).  Afterwards the net has the bits of a SegNet created from those weights.  The net must not be in use on
+        another context's stream during the call."""
+        g = self._ensure_grad()
+        fd, mine = flat, False
+        if not isinstance(flat, DeviceMaps):
+            fd, mine = DeviceMaps.from_host(self.ctx, np.asarray(flat).reshape(-1), dtype=np.float32), True
+        try:
+            if fd.dtype != np.float32 or fd.shape != (g.grad_elems,):
+                raise ValueError("SegNet.load_params_dev: %r %s must be float32 (%d,), the layout's size" % (fd.shape, fd.dtype, g.grad_elems))
+            g.load_params(fd.ptr)
+        finally:
+            if mine:
+                fd.free()
+
     def softmax_dev(self, x):
         """net['fc8-softmax'] on the device: what SegEvaluator.update and crf_layer_dev take."""
         return self.forward_dev(x)
@@ -984,6 +1025,137 @@ class SegNet:
             return x, packed
         packed.free()
         return x
+
+
+class SegTrainer:
+    """One SEC / DSRG training step after another at drop_prob = 0 (the reference's phase == 'debug' graph): Model.optimize() and
+    the update branch of Model.train() (model.py:379-404, 491-504).  Owns a SegNet (`net`), the flat float32 parameter buffer and
+    the two slot buffers (momentum, gradient accumulator) -- DeviceMaps of net._grad.grad_elems floats in SegGrads' layout, never
+    downloaded by a step.  The defaults are the reference's (model.py:36-40).
+
+    step(x, cues, labels_or_tags, img_mean, crf_config_train, epoch=None) -> (losses, new_cues)
+        SegNet.grad_step_dev, then wsc_seg_sgd_accumulate (accum += mult (grad + weight_decay w) / accum_num); on every
+        accum_num-th call also wsc_seg_sgd_apply (mom = mom momentum + accum, param -= lr mom, accum = 0) and
+        wsc_net_seg_load_params, after which the net computes with the updated weights.  losses: grad_step_dev's, plus "l2" =
+        sum of sum(w^2) / 2 over the layers (at the weights the gradient was taken at) and "total" = norm + weight_decay l2
+        (model.py:383-384).  new_cues as grad_step_dev returns it; the caller frees it.  epoch: sets the rate to lr_at(epoch) first.
+    lr_at(epoch)    float32(base_lr * lr_decay ** (epoch // lr_step)) (model.py:493)
+    params_host()   {layer: {"w": HWIO, "b": ...}}: the init-model format SegNet takes;  momentum_host() likewise
+    save(path) / SegTrainer.load(path, method, num_classes, ...)   np.save / np.load(...).item() of that dict -- the .npy
+                    load_init_model reads (DSRG.py:374-377) -- with the slots and the step count under "__momentum__", "__accum__",
+                    "__step__"
+    close()         releases everything"""
+
+    def __init__(self, method, weights, num_classes, precision=_lib.PREC_F16X3, ctx=None, base_lr=1e-4, momentum=0.9, weight_decay=5e-4,
+                 accum_num=1, lr_decay=0.5, lr_step=4, min_prob=1e-4):
+        if int(accum_num) < 1:
+            raise ValueError("SegTrainer: accum_num = %r" % (accum_num,))
+        self.base_lr, self.momentum, self.weight_decay = float(base_lr), float(momentum), float(weight_decay)
+        self.accum_num, self.lr_decay, self.lr_step = int(accum_num), float(lr_decay), lr_step
+        self.lr = np.float32(base_lr)
+        self.calls = 0
+        self.params = self.mom = self.accum = None
+        self.net = SegNet(method, weights, num_classes, precision=precision, ctx=ctx, min_prob=min_prob)
+        self.ctx = self.net.ctx
+        try:
+            flat = self.net.flat_params(weights)
+            self.params = DeviceMaps.from_host(self.ctx, flat)
+            self.mom = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
+            self.accum = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def layout(self):
+        return self.net._grad.layout
+
+    def close(self):
+        for name in ("params", "mom", "accum"):
+            buf = getattr(self, name, None)
+            if buf is not None:
+                buf.free()
+            setattr(self, name, None)
+        if getattr(self, "net", None) is not None:
+            self.net.close()
+            self.net = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lr_at(self, epoch):
+        return np.float32(self.base_lr * self.lr_decay ** (epoch // self.lr_step))
+
+    def step(self, x, cues, labels_or_tags, img_mean, crf_config_train, epoch=None):
+        if epoch is not None:
+            self.lr = self.lr_at(epoch)
+        g = self.net._ensure_grad()
+        losses, grads, new_cues = self.net.grad_step_dev(x, cues, labels_or_tags, img_mean, crf_config_train)
+        l2 = None
+        try:
+            l2 = DeviceMaps(self.ctx, (1,), np.float32)
+            g.sgd_accumulate(self.params.ptr, grads.maps.ptr, self.accum.ptr, self.weight_decay, self.accum_num, l2.ptr)
+            self.calls += 1
+            if self.calls % self.accum_num == 0:
+                g.sgd_apply(self.params.ptr, self.accum.ptr, self.mom.ptr, self.lr, self.momentum, clear_accum=True)
+                g.load_params(self.params.ptr)
+            l2_value = float(l2.to_host()[0])
+        except Exception:
+            if new_cues is not cues:
+                new_cues.free()
+            raise
+        finally:
+            grads.free()
+            if l2 is not None:
+                l2.free()
+        losses = dict(losses)
+        losses["l2"] = l2_value
+        losses["total"] = losses["norm"] + self.weight_decay * l2_value
+        return losses, new_cues
+
+    def _unflatten(self, flat):
+        out = {}
+        for layer, e in self.layout.items():
+            shape = (e["k"], e["k"], e["Cin"], e["Cout"])
+            out[layer] = {"w": flat[e["w_off"]:e["w_off"] + int(np.prod(shape))].reshape(shape).copy(),
+                          "b": flat[e["b_off"]:e["b_off"] + e["Cout"]].copy()}
+        return out
+
+    def params_host(self):
+        return self._unflatten(self.params.to_host())
+
+    def momentum_host(self):
+        return self._unflatten(self.mom.to_host())
+
+    def save(self, path):
+        d = self.params_host()
+        d["__momentum__"] = self.momentum_host()
+        d["__accum__"] = self._unflatten(self.accum.to_host())
+        d["__step__"] = {"calls": self.calls, "lr": float(self.lr)}
+        with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
+            np.save(fh, d, allow_pickle=True)
+
+    @classmethod
+    def load(cls, path, method, num_classes, **kwargs):
+        d = np.load(path, encoding="latin1", allow_pickle=True).item()
+        tr = cls(method, {k: v for k, v in d.items() if not k.startswith("__")}, num_classes, **kwargs)
+        try:
+            for key, name in (("__momentum__", "mom"), ("__accum__", "accum")):
+                if key in d:
+                    flat = tr.net.flat_params(d[key])  # (a slot has the weights' shapes)
+                    getattr(tr, name).free()
+                    setattr(tr, name, None)
+                    setattr(tr, name, DeviceMaps.from_host(tr.ctx, flat))
+            if "__step__" in d:
+                tr.calls = int(d["__step__"]["calls"])
+                tr.lr = np.float32(d["__step__"]["lr"])
+        except Exception:
+            tr.close()
+            raise
+        return tr
 
 
 class Predictor:
