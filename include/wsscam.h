@@ -301,15 +301,15 @@ int wsc_conv2d_nchw_dil(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H,
 
 /* The DeepLab-VGG16 forward pass of SEC / DSRG at drop_prob = 0 (every non-training phase, and the training step of the
  * reference's `debug` graph: the losses and their gradient into fc8 are wsc_seg_loss, the backward pass wsc_net_backward_seg, the
- * SGD-momentum update and the write-back of the weights wsc_seg_sgd_* / wsc_net_seg_load_params below; dropout at drop_prob > 0
- * is out of scope).  A net created with WSC_ARCH_DEEPLAB_LFOV / _ASPP takes its weights under the reference's
+ * SGD-momentum update and the write-back of the weights wsc_seg_sgd_* / wsc_net_seg_load_params below; the `train` phase's
+ * dropout behind fc6 / fc7 is wsc_net_forward_seg_train / wsc_net_backward_seg_drop, with the project's own keep-masks).  A net created with WSC_ARCH_DEEPLAB_LFOV / _ASPP takes its weights under the reference's
  * layer names (get_weights_and_bias, DSRG.py:379-425): `conv1_1` ... `conv5_3`, and `fc6`, `fc7`, `fc8` (LFOV) or `fc6_1` ...
  * `fc8_4` (ASPP); each as `<layer>.w` in TensorFlow's HWIO order [kh][kw][Cin][Cout] and `<layer>.b` [Cout].  Channel widths
  * are read from the tensors (multiples of 64; fc8 has num_classes outputs).  A missing or mis-shaped tensor is WSC_ERR_SHAPE
  * and the error text names the layer.  Layers (build_block / build_fc): 3x3 conv + bias + ReLU with padding SAME, conv5_* at
  * rate 2, fc6 at its branch's rate; 3x3 max pools with TF's SAME padding (pad_before = floor(pad_total / 2): 0 / 1 on an even
  * size at stride 2; padding never wins the maximum) at stride 2 (pool1-3) and 1 (pool4, pool5); pool5a, a 3x3 stride-1 average
- * over the in-image taps; dropout is the identity.
+ * over the in-image taps; dropout is the identity in every entry but wsc_net_forward_seg_train.
  *
  * wsc_net_seg_size_hw: the fc8 map size for an H x W input (41 x 41 at 321 x 321). */
 int wsc_net_seg_size_hw(const wsc_net *net, int H, int W, int *h_out, int *w_out);
@@ -384,7 +384,7 @@ int wsc_fc8_softmax(wsc_ctx *ctx, const float *const *fc8_dev, int n_in, long lo
  * sends a window's dy to the window's first maximum in row-major window order (padding is never a candidate); pool5a sends
  * dy / (in-image tap count) to every in-image tap; every ASPP branch receives dfc8 and their gradients into pool5a's output are
  * summed in the order _1 ... _4; no gradient is formed for the network input.  The weight-decay term, the learning-rate
- * multipliers and the optimiser follow below (wsc_seg_sgd_*); out of scope: dropout.
+ * multipliers and the optimiser follow below (wsc_seg_sgd_*); dropout: wsc_net_backward_seg_drop below.
  *
  * The tape: wsc_net_seg_tape_plan lists the kept tensors for a B x H x W input -- "input", every op of the trunk ("conv1_1", ...,
  * "pool:0", ..., "pool5a"), every branch's "fc6[_k]" and "fc7[_k]" -- each float32 NHWC [B][Ho][Wo][C] at `offset` floats of one
@@ -400,6 +400,42 @@ int wsc_net_seg_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W,
                           int *n_out, long long *tape_elems_out);
 int wsc_net_forward_seg_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob,
                              float *tape_dev, long long tape_elems, float *fc8_dev, float *prob_dev);
+/* ---- dropout: the `train` phase of SEC / DSRG (drop_prob = 0.5, SEC.py:81 / DSRG.py:128) -------------------------------------
+ * The sites are drop6 / drop7 behind fc6 / fc7 (SEC.py:123,225-227), drop6_k / drop7_k in each ASPP branch (DSRG.py:174-177,276-278).
+ * PARITY WITH TENSORFLOW'S RANDOM STREAM IS UNPINNED: TensorFlow's generator is not reproduced.  The project defines its own
+ * counter-based contract, under which a keep-mask depends on (seed, step, site, element index) alone -- never on the launch
+ * geometry, the precision, the stream or how a batch is split:
+ *   generator  Philox4x32-10: multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85, key = (seed low 32 bits,
+ *              seed high 32 bits)
+ *   counter    of element i, the linear NHWC index in the [B][h][w][Cout] output of fc6 / fc7: (low 32 bits of i >> 2, high 32 bits
+ *              of i >> 2, step, site); element i takes output word i & 3.  step < 2^32, else WSC_ERR_INVALID
+ *   site       branch k (0-based; SEC has one) uses 2 k for drop6 and 2 k + 1 for drop7: DSRG's sites 0 .. 7 are independent
+ *   keep rule  u = float(word >> 8) 2^-24 (exact); keep iff u >= drop_prob in fp32 -- TF 1.13's random_uniform >= rate.
+ *              0 <= drop_prob < 1 (NaN: WSC_ERR_INVALID); drop_prob = 0 keeps everything
+ *   value      d = y scale on kept elements, +0.0 on dropped ones; scale = 1.0f / (1.0f - drop_prob), every operation in fp32; the
+ *              product is ONE fp32 rounding of the exact value hi + lo of the activation, stored by the split the conv epilogue
+ *              uses for the net's precision.  At 0.5 the scale is 2 and everything is exact.  An IEEE half that reaches the
+ *              ceiling (a doubled value >= 65504) raises the range flag as a conv epilogue does
+ *   tape       keeps its meaning, "the value the next op read": the fc6* / fc7* entries hold the dropped, scaled activations
+ *   backward   needs no mask buffer: scale >= 1, so a tape value is > 0 exactly where the unit was kept AND its ReLU output was
+ *              positive; fc6 / fc7 form dz = dy scale (one fp32 rounding) there and +0.0 elsewhere, and the bias and weight
+ *              gradients follow from that dz.  Nothing but the tape is stored between the passes.
+ *
+ * wsc_seg_dropout_f32: the kernel on plain fp32, for the tests: y_dev[j] = the dropout of x_dev[j] (y_dev may be x_dev) where
+ *   x_dev[0] is element `first` of the logical tensor (so that a small buffer reaches the counter's high word); keep_dev NULL or
+ *   `elems` bytes that receive the keep decisions (1 / 0).  Any alignment (16-byte accesses where first is a multiple of 4 and the
+ *   buffers allow, else the scalar form: the same words).  Asynchronous on the ctx stream.
+ * wsc_net_forward_seg_train: wsc_net_forward_seg_tape with the dropout sites active; in place of the tape copy behind fc6 / fc7
+ *   one kernel drops and scales the activation in place and writes the tape entry in the same pass.  At drop_prob = 0 it launches
+ *   what wsc_net_forward_seg_tape launches and gives the same bits.
+ * wsc_net_backward_seg_drop: wsc_net_backward_seg (below) with scale = 1 / (1 - drop_prob) at the fc6 / fc7 mask step, on a tape
+ *   of wsc_net_forward_seg_train at that drop_prob; the same launches.
+ * Every argument error is WSC_ERR_INVALID before any launch. */
+int wsc_seg_dropout_f32(wsc_ctx *ctx, const float *x_dev, long long elems, long long first, float drop_prob, unsigned long long seed,
+                        long long step, int site, float *y_dev, unsigned char *keep_dev);
+int wsc_net_forward_seg_train(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float drop_prob,
+                              unsigned long long seed, long long step, float *tape_dev, long long tape_elems, float *fc8_dev,
+                              float *prob_dev);
 /* wsc_seg_grad: what the backward pass of one net keeps -- the rotated, channel-transposed fp32 kernels of the data-gradient
  * convolutions (packed once) and the backward workspace (two gradient activations, the masked dz, the split-K slabs; grown on
  * demand).  `weights`: the list wsc_net_create took; a tensor that is not the net's is WSC_ERR_SHAPE naming the layer.  The net
@@ -421,6 +457,8 @@ int wsc_seg_grad_layout(const wsc_seg_grad *g, wsc_grad_entry *entries_out, int 
  * summed in slice order, no floating-point atomic anywhere. */
 int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
                          const float *dfc8_dev, float *grad_dev, long long grad_elems);
+int wsc_net_backward_seg_drop(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                              const float *dfc8_dev, float *grad_dev, long long grad_elems, float drop_prob);
 /* The layers of that pass one by one, for the per-op tests (float32 NHWC in and out, the launchers of the pass unchanged):
  * wsc_conv2d_wgrad_nhwc: dw_dev [k][k][Cin][Cout] and db_dev [Cout] of a stride-1 SAME convolution (k 1 or 3, pad = dil (k - 1) / 2)
  *   from its input x_dev [N][H][W][Cin] and the gradient dy_dev [N][H][W][Cout] of its (pre-activation) output: fp32 operands on
@@ -428,6 +466,8 @@ int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, con
  *   splits = 0: the launcher's choice of K slices, > 0: that many (at most one per K-step of 32 pixels).  A tap outside the image for every pixel is exactly 0.0.
  * wsc_conv2d_dgrad_nhwc: dx_dev [N][H][W][Cin] from dy_dev and the layer's weights w_host [k][k][Cin][Cout]; Cin a multiple of 64.
  * wsc_relu_bias_grad: dz_dev [M][C] = dy [y > 0] (y_dev NULL: dz = dy), db_dev [C] = the column sums of dz.
+ * wsc_relu_bias_grad_scaled: the same with dz = dy scale [y > 0], the product one fp32 rounding (the mask step behind a dropout
+ *   site; 1 <= scale < inf, 1.0f gives wsc_relu_bias_grad's bits; y_dev NULL: dz = dy, no scale).
  * wsc_pool_same_grad_nhwc: the gradient of wsc_pool_same_nhwc at x_dev [N][H][W][C] (C a multiple of 8) for dy_dev of the pool's
  *   output size -> dx_dev [N][H][W][C]. */
 int wsc_conv2d_wgrad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int Cin, int Cout, int k, int dil,
@@ -435,11 +475,13 @@ int wsc_conv2d_wgrad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev,
 int wsc_conv2d_dgrad_nhwc(wsc_ctx *ctx, const float *dy_dev, const float *w_host, int N, int H, int W, int Cin, int Cout, int k, int dil,
                           float *dx_dev);
 int wsc_relu_bias_grad(wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float *dz_dev, float *db_dev);
+int wsc_relu_bias_grad_scaled(wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float scale, float *dz_dev,
+                              float *db_dev);
 int wsc_pool_same_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int avg, int stride,
                             float *dx_dev);
 
 /* ---- the update half of the training step: Model.optimize() and the update branch of Model.train() ------------------------------
- * (model.py:379-404, 491-504) at drop_prob = 0.  Parameters, the momentum slot and the gradient accumulator are each ONE fp32
+ * (model.py:379-404, 491-504), whatever the drop_prob of the gradient.  Parameters, the momentum slot and the gradient accumulator are each ONE fp32
  * device buffer of grad_elems floats in the layout of wsc_seg_grad_layout (per layer w in HWIO, then b, no gaps): a gradient
  * buffer of wsc_net_backward_seg, a parameter buffer and a slot buffer are element-for-element parallel.  Both calls are
  * asynchronous on the ctx stream; every product, sum and quotient below is rounded to fp32 on its own (no fused multiply-add).
@@ -659,7 +701,7 @@ int wsc_dsrg_seed_grow(wsc_ctx *ctx, const float *tags_dev, const float *cues_de
  * get_expand_loss, get_constrain_loss; DSRG.py:459-518 getloss, get_balanced_seed_loss, get_constrain_loss).  `crf` and the cues
  * come out of tf.py_func in the reference graph, so they are constants to the gradient: no backward pass through the CRF or the
  * region growing.  The backward pass of the convolution stack is wsc_net_backward_seg, the weight decay term and the optimiser
- * wsc_seg_sgd_*; out of scope: dropout.
+ * wsc_seg_sgd_*, the `train` phase's dropout wsc_net_forward_seg_train / wsc_net_backward_seg_drop.
  *   prob_dev   float32 [B][H][W][C]  fc8-softmax p (wsc_net_forward_seg), > 0;  n = H W
  *   crf_dev    float32 [B][H][W][C]  the CRF layer's log-probabilities (wsc_seg_crf_logprob);  q = exp(crf)
  *   cues_dev   float32 [B][H][W][C]  0/1 (DSRG: the grown cues of wsc_dsrg_seed_grow)

@@ -518,9 +518,12 @@ int wgrad_plan(const wsc_ctx *ctx, int N, int H, int W, int Cin, int Cout, int k
 // dw [k][k][Cin][Cout] (HWIO) of a stride-1 SAME convolution from x [N][H][W][Cin] and dz [N][H][W][Cout]; every element is written
 int wgrad_launch(wsc_ctx *ctx, const WgradPlan &pl, const float *x, const float *dz, int H, int W, int Cin, int Cout, int k, int dil,
                  float *slab, float *dw);
-// dz = dy [y > 0] (y null: dz = dy; dz null: not written), db[c] = sum_m dz[m][c]; partial: relu_bias_grad_blocks(M) * C floats
+// dz = dy scale [y > 0], the product one fp32 rounding (scale 1.0f: dy itself, bit for bit; > 1 behind a dropout site, whose tape
+// entry is > 0 exactly where the unit was kept and its ReLU positive); y null: dz = dy, no scale; dz null: not written;
+// db[c] = sum_m dz[m][c]; partial: relu_bias_grad_blocks(M) * C floats
 int relu_bias_grad_blocks(long long M);
-int launch_relu_bias_grad(wsc_ctx *ctx, const float *y, const float *dy, long long M, int C, float *dz, float *partial, float *db);
+int launch_relu_bias_grad(wsc_ctx *ctx, const float *y, const float *dy, long long M, int C, float scale, float *dz, float *partial,
+                          float *db);
 // dst [M][Cd] = the first channels of src [M][Cs], zeros beyond
 int launch_copy_channels(wsc_ctx *ctx, const float *src, long long M, int Cs, int Cd, float *dst);
 // The data gradient of a stride-1 SAME convolution w [k][k][Cin][Cout] as conv_f32_launch's generic layer: its input is dz with
@@ -580,6 +583,20 @@ struct RepackPlan {
 };
 int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *plan);
 int repack_launch(wsc_ctx *ctx, const RepackPlan &plan, const float *param);
+
+// ---- seg_dropout.hip: the dropout sites behind fc6 / fc7 of the SEC / DSRG training graph (the contract: its header) -----------
+// WSC_ERR_INVALID unless 0 <= drop_prob < 1 (NaN included) and 0 <= step < 2^32; `fn` names the caller in the error text
+int seg_dropout_check(const char *fn, float drop_prob, long long step);
+// 1 / (1 - drop_prob) in fp32: the forward kernel's factor and the backward pass's
+float seg_dropout_scale(float drop_prob);
+// y[i] = dropout of x[i] (y may be x) with element i at index first + i of the logical tensor; tape (fp32 copy of y) and keep (one
+// byte per element) are optional
+int launch_seg_dropout_f32(wsc_ctx *ctx, const float *x, float *y, float *tape, uint8_t *keep, long long n, unsigned long long first,
+                           float drop_prob, unsigned long long seed, unsigned step, unsigned site);
+// the activation's n elements in place, every precision; tape (or null) receives the fp32 value the planes hold afterwards (in
+// place of launch_act_to_f32); Cout: what the range flag is raised with where an IEEE half reaches the ceiling
+int launch_seg_dropout(wsc_ctx *ctx, Act a, size_t n, int Cout, float drop_prob, unsigned long long seed, unsigned step, unsigned site,
+                       float *tape);
 
 // ---- deeplab.hip: the kernels around the conv stack of the SEC / DSRG DeepLab nets -------------------------------------
 // float32 [N][H][W][3] -> NHWC4 activation (raises the range flag where an IEEE-half plane saturates)

@@ -1357,9 +1357,17 @@ static int seg_tape_plan(const wsc_net *net, int B, int H, int W, TapePlan *tp) 
     return WSC_OK;
 }
 
-// wsc_net_forward_seg (tp null) and wsc_net_forward_seg_tape: the same launches; with a tape, copies between them
+// the dropout sites of a training forward pass (wsc_net_forward_seg_train); drop_prob = 0: none, the launches of the tape pass
+struct SegDropout {
+    float drop_prob = 0.f;
+    unsigned long long seed = 0;
+    unsigned step = 0;
+};
+// wsc_net_forward_seg (tp null) and wsc_net_forward_seg_tape: the same launches; with a tape, copies between them.  drop (with a
+// tape, drop_prob > 0): the copy behind fc6 / fc7 of branch k is the dropout kernel of site 2 k / 2 k + 1 instead, which drops
+// and scales the activation in place and writes the tape entry in the same pass.
 static int forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *fc8_dev,
-                       float *prob_dev, const TapePlan *tp, float *tape) {
+                       float *prob_dev, const TapePlan *tp, float *tape, const SegDropout *drop = nullptr) {
     Plan pl;
     WSC_TRY(plan_dims(net, B, H, W, &pl));
     const size_t M = (size_t)B * pl.hf * pl.wf;
@@ -1402,10 +1410,17 @@ static int forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int
             L.N = B; L.H = hf; L.W = wf; L.Ho = hf; L.Wo = wf; // (SAME at stride 1: pad = dil (k - 1) / 2)
             return conv_igemm_launch(ctx, L);
         };
+        const bool dropping = tp && drop && drop->drop_prob > 0.f;
+        auto keep = [&](Act a, int Cout, int entry, unsigned site) -> int {
+            if (!tp) return WSC_OK;
+            float *dst = tape + tp->e[entry].offset;
+            if (dropping) return launch_seg_dropout(ctx, a, M * Cout, Cout, drop->drop_prob, drop->seed, drop->step, site, dst);
+            return launch_act_to_f32(ctx, a, M * Cout, dst);
+        };
         WSC_TRY(run(br.fc6, feat, a6, nullptr));
-        if (tp) WSC_TRY(launch_act_to_f32(ctx, a6, M * br.fc6.Cout, tape + tp->e[tp->fc6[k]].offset));
+        WSC_TRY(keep(a6, br.fc6.Cout, tp ? tp->fc6[k] : 0, 2u * (unsigned)k));
         WSC_TRY(run(br.fc7, a6, a7, nullptr));
-        if (tp) WSC_TRY(launch_act_to_f32(ctx, a7, M * br.fc7.Cout, tape + tp->e[tp->fc7[k]].offset));
+        WSC_TRY(keep(a7, br.fc7.Cout, tp ? tp->fc7[k] : 0, 2u * (unsigned)k + 1u));
         WSC_TRY(run(br.fc8, a7, Act(), out));
     }
     return launch_fc8_softmax(ctx, logits, (int)net->seg.size(), (long long)M, net->C, min_prob, fc8_dev, prob_dev);
@@ -1447,6 +1462,24 @@ int wsc_net_forward_seg_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_de
               tape_elems, tp.elems);
     WSC_HIP(hipSetDevice(ctx->device));
     return forward_seg(ctx, net, x_dev, B, H, W, min_prob, fc8_dev, prob_dev, &tp, tape_dev);
+}
+
+int wsc_net_forward_seg_train(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float drop_prob,
+                              unsigned long long seed, long long step, float *tape_dev, long long tape_elems, float *fc8_dev,
+                              float *prob_dev) {
+    WSC_CHECK(ctx && net && x_dev && prob_dev && tape_dev, WSC_ERR_INVALID, "wsc_net_forward_seg_train: null argument");
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg_train: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg_train: B=%d input %d x %d min_prob=%g", B, H,
+              W, (double)min_prob);
+    WSC_TRY(seg_dropout_check("wsc_net_forward_seg_train", drop_prob, step));
+    TapePlan tp;
+    WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
+    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_forward_seg_train: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)",
+              tape_elems, tp.elems);
+    WSC_HIP(hipSetDevice(ctx->device));
+    SegDropout drop;
+    drop.drop_prob = drop_prob; drop.seed = seed; drop.step = (unsigned)step;
+    return forward_seg(ctx, net, x_dev, B, H, W, min_prob, fc8_dev, prob_dev, &tp, tape_dev, &drop);
 }
 
 // ---- the backward pass of the DeepLab nets: d loss / d fc8 -> the gradient of every weight and bias -----------------------------
@@ -1596,19 +1629,20 @@ int wsc_seg_grad_layout(const wsc_seg_grad *g, wsc_grad_entry *entries_out, int 
     return WSC_OK;
 }
 
-int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
-                         const float *dfc8_dev, float *grad_dev, long long grad_elems) {
-    WSC_CHECK(ctx && g && tape_dev && dfc8_dev && grad_dev, WSC_ERR_INVALID, "wsc_net_backward_seg: null argument");
-    WSC_CHECK(B >= 1 && H >= 1 && W >= 1, WSC_ERR_INVALID, "wsc_net_backward_seg: B=%d input %d x %d", B, H, W);
+// wsc_net_backward_seg (fc_scale 1.0f) and wsc_net_backward_seg_drop (1 / (1 - drop_prob)): the same launches
+static int backward_seg(const char *fn, wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                        const float *dfc8_dev, float *grad_dev, long long grad_elems, float fc_scale) {
+    WSC_CHECK(ctx && g && tape_dev && dfc8_dev && grad_dev, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1, WSC_ERR_INVALID, "%s: B=%d input %d x %d", fn, B, H, W);
     // (the workspace is the object's: one stream uses it, the one wsc_seg_grad_destroy drains)
-    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_net_backward_seg: the context is not the one the wsc_seg_grad was created on");
+    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "%s: the context is not the one the wsc_seg_grad was created on", fn);
     const wsc_net *net = g->net;
     TapePlan tp;
     WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
-    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_backward_seg: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)",
-              tape_elems, tp.elems);
-    WSC_CHECK(grad_elems == g->grad_elems, WSC_ERR_INVALID, "wsc_net_backward_seg: a gradient buffer of %lld floats, the layout has %lld",
-              grad_elems, g->grad_elems);
+    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "%s: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)", fn, tape_elems,
+              tp.elems);
+    WSC_CHECK(grad_elems == g->grad_elems, WSC_ERR_INVALID, "%s: a gradient buffer of %lld floats, the layout has %lld", fn, grad_elems,
+              g->grad_elems);
     // every layer's plan and the workspace they need, before anything is launched
     const int hf = tp.pl.hf, wf = tp.pl.wf;
     const long long M8 = (long long)B * hf * wf;
@@ -1651,17 +1685,18 @@ int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, con
     float *gs[2] = {carve(sum_bytes), carve(sum_bytes)};
     float *dz = carve(lines(dz_max)), *slab = carve(lines(slab_max)), *partial = carve(lines(part_max));
 
-    // one layer at gradient dy of its output [B][h][w][Cout]: db, dW, and (dx non-null) the gradient of its input
+    // one layer at gradient dy of its output [B][h][w][Cout]: db, dW, and (dx non-null) the gradient of its input; scale: 1.0f,
+    // or the factor of the dropout site behind the layer (fc6 / fc7: y is then the dropped, scaled tape entry)
     auto layer_back = [&](size_t li, int h, int w, const float *x, const float *y /* null: no ReLU */, const float *dy, const float *sum_with,
-                          float *dx) -> int {
+                          float *dx, float scale = 1.0f) -> int {
         const GradLayer &L = g->layers[li];
         const long long M = (long long)B * h * w;
         const float *dzp = dy;
         if (y) {
-            WSC_TRY(launch_relu_bias_grad(ctx, y, dy, M, L.Cout, dz, partial, grad_dev + L.b_off));
+            WSC_TRY(launch_relu_bias_grad(ctx, y, dy, M, L.Cout, scale, dz, partial, grad_dev + L.b_off));
             dzp = dz;
         } else {
-            WSC_TRY(launch_relu_bias_grad(ctx, nullptr, dy, M, L.Cout, nullptr, partial, grad_dev + L.b_off));
+            WSC_TRY(launch_relu_bias_grad(ctx, nullptr, dy, M, L.Cout, 1.0f, nullptr, partial, grad_dev + L.b_off));
         }
         WSC_TRY(wgrad_launch(ctx, plans[li], x, dzp, h, w, L.Cin, L.Cout, L.k, L.dil, slab, grad_dev + L.w_off));
         if (!dx) return WSC_OK;
@@ -1678,8 +1713,8 @@ int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, con
     for (size_t k = 0; k < net->seg.size(); ++k) {
         const size_t l6 = n_trunk + 3 * k;
         WSC_TRY(layer_back(l6 + 2, hf, wf, at(tp.fc7[k]), nullptr, dfc8_dev, nullptr, ga));
-        WSC_TRY(layer_back(l6 + 1, hf, wf, at(tp.fc6[k]), at(tp.fc7[k]), ga, nullptr, gb));
-        WSC_TRY(layer_back(l6, hf, wf, at(e_pool5a), at(tp.fc6[k]), gb, k > 0 ? gs[(k + 1) & 1] : nullptr, gs[k & 1]));
+        WSC_TRY(layer_back(l6 + 1, hf, wf, at(tp.fc6[k]), at(tp.fc7[k]), ga, nullptr, gb, fc_scale));
+        WSC_TRY(layer_back(l6, hf, wf, at(e_pool5a), at(tp.fc6[k]), gb, k > 0 ? gs[(k + 1) & 1] : nullptr, gs[k & 1], fc_scale));
     }
     // the trunk, last op first
     const float *gcur = gs[(net->seg.size() - 1) & 1];
@@ -1701,6 +1736,18 @@ int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, con
         nf ^= 1;
     }
     return WSC_OK;
+}
+
+int wsc_net_backward_seg(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                         const float *dfc8_dev, float *grad_dev, long long grad_elems) {
+    return backward_seg("wsc_net_backward_seg", ctx, g, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, grad_elems, 1.0f);
+}
+
+int wsc_net_backward_seg_drop(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                              const float *dfc8_dev, float *grad_dev, long long grad_elems, float drop_prob) {
+    WSC_TRY(seg_dropout_check("wsc_net_backward_seg_drop", drop_prob, 0));
+    return backward_seg("wsc_net_backward_seg_drop", ctx, g, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, grad_elems,
+                        seg_dropout_scale(drop_prob));
 }
 
 // ---- the update half of the training step: Model.optimize() (model.py:379-404) on the layout of wsc_seg_grad_layout ----------------

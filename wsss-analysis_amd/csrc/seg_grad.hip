@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
 // stage 1 of the mask + bias pass: block g owns rows [g R, (g + 1) R); lane tx a channel of every 64-channel group, the four
 // waves the rows r % 4; partial[g][c] = ((wave 0 + wave 1) + wave 2) + wave 3
 __global__ __launch_bounds__(256) void relu_bias_grad_kernel(const float *__restrict__ y, const float *__restrict__ dy, long long M, int C,
-                                                             long long R, float *__restrict__ dz, float *__restrict__ partial) {
+                                                             long long R, float scale, float *__restrict__ dz, float *__restrict__ partial) {
     __shared__ float red[4][64];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const long long r0 = (long long)blockIdx.x * R;
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void relu_bias_grad_kernel(const float *__rest
             for (long long r = r0 + ty; r < r1; r += 4) {
                 const long long o = r * C + c;
                 float v = dy[o];
-                if (y != nullptr) v = y[o] > 0.f ? v : 0.f;
+                if (y != nullptr) v = y[o] > 0.f ? __fmul_rn(v, scale) : 0.f; // (one rounding, never fused into the sum; 1.0f: exact)
                 if (dz != nullptr) dz[o] = v;
                 s += v;
             }
@@ -354,12 +354,13 @@ int wgrad_launch(wsc_ctx *ctx, const WgradPlan &pl, const float *x, const float 
 
 int relu_bias_grad_blocks(long long M) { return (int)std::min<long long>(std::max<long long>((M + 63) / 64, 1), 1024); }
 
-int launch_relu_bias_grad(wsc_ctx *ctx, const float *y, const float *dy, long long M, int C, float *dz, float *partial, float *db) {
+int launch_relu_bias_grad(wsc_ctx *ctx, const float *y, const float *dy, long long M, int C, float scale, float *dz, float *partial,
+                          float *db) {
     WSC_CHECK(M > 0 && C > 0, WSC_ERR_INVALID, "mask + bias gradient: %lld x %d", M, C);
     const int G = relu_bias_grad_blocks(M);
     const long long R = (M + G - 1) / G;
     WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, (double)M * C * 4 * (1 + (y != nullptr) + (dz != nullptr)));
-    hipLaunchKernelGGL(relu_bias_grad_kernel, dim3(G), dim3(256), 0, ctx->stream, y, dy, M, C, R, dz, partial);
+    hipLaunchKernelGGL(relu_bias_grad_kernel, dim3(G), dim3(256), 0, ctx->stream, y, dy, M, C, R, scale, dz, partial);
     WSC_HIP(hipGetLastError());
     hipLaunchKernelGGL(bias_grad_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, ctx->stream, partial, G, C, db);
     WSC_HIP(hipGetLastError());
@@ -412,7 +413,7 @@ int wsc_conv2d_wgrad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev,
     WSC_TRY(wsc_ctx_workspace(ctx, (size_t)pl.slab_elems * sizeof(float) + partial_bytes, &ws));
     float *slab = (float *)ws, *partial = slab + pl.slab_elems;
     WSC_TRY(wgrad_launch(ctx, pl, x_dev, dy_dev, H, W, Cin, Cout, k, dil, slab, dw_dev));
-    return launch_relu_bias_grad(ctx, nullptr, dy_dev, pl.M, Cout, nullptr, partial, db_dev);
+    return launch_relu_bias_grad(ctx, nullptr, dy_dev, pl.M, Cout, 1.0f, nullptr, partial, db_dev);
 }
 
 int wsc_conv2d_dgrad_nhwc(wsc_ctx *ctx, const float *dy_dev, const float *w_host, int N, int H, int W, int Cin, int Cout, int k, int dil,
@@ -443,13 +444,25 @@ int wsc_conv2d_dgrad_nhwc(wsc_ctx *ctx, const float *dy_dev, const float *w_host
     return dgrad_launch(ctx, dz_in, w_dev, vec_dev, vec_dev + rows, N, H, W, Cin, Cout, k, dil, nullptr, dx_dev);
 }
 
-int wsc_relu_bias_grad(wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float *dz_dev, float *db_dev) {
-    WSC_CHECK(ctx && dy_dev && dz_dev && db_dev, WSC_ERR_INVALID, "wsc_relu_bias_grad: null argument");
-    WSC_CHECK(M > 0 && C > 0, WSC_ERR_INVALID, "wsc_relu_bias_grad: %lld x %d", M, C);
+static int relu_bias_grad_entry(const char *fn, wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float scale,
+                                float *dz_dev, float *db_dev) {
+    WSC_CHECK(ctx && dy_dev && dz_dev && db_dev, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_CHECK(M > 0 && C > 0, WSC_ERR_INVALID, "%s: %lld x %d", fn, M, C);
+    WSC_CHECK(scale >= 1.f && scale < INFINITY, WSC_ERR_INVALID, "%s: scale=%g is not 1 / (1 - drop_prob) of a drop_prob in [0, 1)", fn,
+              (double)scale);
     WSC_HIP(hipSetDevice(ctx->device));
     void *ws;
     WSC_TRY(wsc_ctx_workspace(ctx, (size_t)relu_bias_grad_blocks(M) * C * sizeof(float), &ws));
-    return launch_relu_bias_grad(ctx, y_dev, dy_dev, M, C, dz_dev, (float *)ws, db_dev);
+    return launch_relu_bias_grad(ctx, y_dev, dy_dev, M, C, scale, dz_dev, (float *)ws, db_dev);
+}
+
+int wsc_relu_bias_grad(wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float *dz_dev, float *db_dev) {
+    return relu_bias_grad_entry("wsc_relu_bias_grad", ctx, y_dev, dy_dev, M, C, 1.0f, dz_dev, db_dev);
+}
+
+int wsc_relu_bias_grad_scaled(wsc_ctx *ctx, const float *y_dev, const float *dy_dev, long long M, int C, float scale, float *dz_dev,
+                              float *db_dev) {
+    return relu_bias_grad_entry("wsc_relu_bias_grad_scaled", ctx, y_dev, dy_dev, M, C, scale, dz_dev, db_dev);
 }
 
 } // extern "C"

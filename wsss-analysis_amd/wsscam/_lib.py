@@ -141,6 +141,11 @@ _SIGNATURES = {
     "wsc_net_seg_tape_plan": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i),
                                    ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_forward_seg_tape": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, ctypes.c_longlong, _vp, _vp]),
+    "wsc_net_forward_seg_train": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, ctypes.c_ulonglong, ctypes.c_longlong, _vp, ctypes.c_longlong,
+                                       _vp, _vp]),
+    "wsc_seg_dropout_f32": (_i, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _f, ctypes.c_ulonglong, ctypes.c_longlong, _i, _vp, _vp]),
+    "wsc_net_backward_seg_drop": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _f]),
+    "wsc_relu_bias_grad_scaled": (_i, [_vp, _vp, _vp, ctypes.c_longlong, _i, _f, _vp, _vp]),
     "wsc_seg_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
     "wsc_seg_grad_destroy": (None, [_vp]),
     "wsc_seg_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
@@ -629,6 +634,14 @@ class Net:
         check(self.ctx._lib.wsc_net_forward_seg_tape(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(min_prob), _ptr(tape_dev),
                                                      int(tape_elems), _ptr(fc8_dev), _ptr(prob_dev)))
 
+    def forward_seg_train(self, x_dev, B, H, W, drop_prob, seed, step, tape_dev, tape_elems, prob_dev, fc8_dev=None, min_prob=1e-4, ctx=None):
+        """wsc_net_forward_seg_train: forward_seg_tape with the dropout sites behind fc6 / fc7 active -- keep-masks of
+        (seed, step, site, element index), the tape's fc6* / fc7* entries the dropped, scaled activations."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_forward_seg_train(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(min_prob), float(drop_prob),
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _ptr(tape_dev), int(tape_elems),
+                                                      _ptr(fc8_dev), _ptr(prob_dev)))
+
     def trace_plan(self, N, H, W, ctx=None):
         """wsc_net_trace_plan: one dict per op of the stack for an N x H x W input (+ the CAM head), the fields of wsc_trace_op
         (`in` under its own name, the label as str).  Follows the options of `ctx` (the fused stem)."""
@@ -689,6 +702,11 @@ class SegGrad:
         check(self.ctx._lib.wsc_net_backward_seg(self.ctx.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfc8_dev),
                                                  _ptr(grad_dev), int(self.grad_elems if grad_elems is None else grad_elems)))
 
+    def backward_drop(self, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, drop_prob, grad_elems=None):
+        """wsc_net_backward_seg_drop: backward() on a tape of forward_seg_train at `drop_prob`."""
+        check(self.ctx._lib.wsc_net_backward_seg_drop(self.ctx.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems),
+                                                      _ptr(dfc8_dev), _ptr(grad_dev),
+                                                      int(self.grad_elems if grad_elems is None else grad_elems), float(drop_prob)))
 
     def sgd_accumulate(self, param_dev, grad_dev, accum_dev, weight_decay, accum_num, l2_dev=None, elems=None, ctx=None):
         """wsc_seg_sgd_accumulate on three buffers of self.grad_elems floats in self.layout: accum += mult (grad [+ weight_decay
@@ -729,6 +747,18 @@ def conv2d_dgrad_nhwc(ctx, dy_dev, w, N, H, W, Cin, Cout, k, dil, dx_dev):
 def relu_bias_grad(ctx, y_dev, dy_dev, M, C, dz_dev, db_dev):
     """wsc_relu_bias_grad: dz = dy [y > 0] (y_dev None: dz = dy), db = the column sums of dz."""
     check(ctx._lib.wsc_relu_bias_grad(ctx.h, _ptr(y_dev), _ptr(dy_dev), int(M), int(C), _ptr(dz_dev), _ptr(db_dev)))
+
+
+def relu_bias_grad_scaled(ctx, y_dev, dy_dev, M, C, scale, dz_dev, db_dev):
+    """wsc_relu_bias_grad_scaled: dz = dy scale [y > 0] (one fp32 rounding), db = the column sums of dz."""
+    check(ctx._lib.wsc_relu_bias_grad_scaled(ctx.h, _ptr(y_dev), _ptr(dy_dev), int(M), int(C), float(scale), _ptr(dz_dev), _ptr(db_dev)))
+
+
+def seg_dropout_f32(ctx, x_dev, elems, first, drop_prob, seed, step, site, y_dev, keep_dev=None):
+    """wsc_seg_dropout_f32: the dropout kernel on plain float32; x_dev[0] is element `first` of the logical tensor, keep_dev
+    (optional) receives one byte per element."""
+    check(ctx._lib.wsc_seg_dropout_f32(ctx.h, _ptr(x_dev), int(elems), int(first), float(drop_prob), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step),
+                                       int(site), _ptr(y_dev), _ptr(keep_dev)))
 
 
 def pool_same_grad_nhwc(ctx, x_dev, dy_dev, N, H, W, C, avg, stride, dx_dev):

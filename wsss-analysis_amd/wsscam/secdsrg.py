@@ -16,12 +16,13 @@
                          SegNet.backward_dev carries d loss / d fc8 to the gradient of every weight and bias, in exact fp32;
                          SegNet.grad_step_dev is loss_step_dev followed by it
 
-    SegTrainer           Model.optimize() and the update branch of Model.train() (model.py:379-404, 491-504) at drop_prob = 0, the
-                         reference's `debug` graph: the weight decay term, the lr multipliers, gradient accumulation, the momentum
+    SegTrainer           Model.optimize() and the update branch of Model.train() (model.py:379-404, 491-504): at drop_prob = 0 the
+                         reference's `debug` graph, at 0.5 its `train` phase (dropout behind fc6 / fc7): the weight decay term, the lr multipliers, gradient accumulation, the momentum
                          update and the write-back of the weights into the net (wsc_seg_sgd_accumulate / _apply,
                          wsc_net_seg_load_params); parameters, momentum and accumulator never leave the device
 
-Dropout at drop_prob > 0 and reading TensorFlow checkpoints are out of scope.  Nothing here imports
+Dropout (SegNet.forward_dev(dropout=...), SegTrainer(drop_prob=0.5)) has the project's own counter-based keep-masks, not
+TensorFlow's random stream; reading TensorFlow checkpoints is out of scope.  Nothing here imports
 TensorFlow: Model.predict runs on this module alone."""
 import numpy as np
 
@@ -788,13 +789,19 @@ class SegNet:
             raise ValueError("SegNet: input %r must be (B, H, W, 3)" % (x.shape,))
         return DeviceMaps.from_host(self.ctx, x), True
 
-    def forward_dev(self, x, want_fc8=False, keep=False):
+    def forward_dev(self, x, want_fc8=False, keep=False, dropout=None):
         """forward() with the maps left on the device: x a DeviceMaps (B, H, W, 3) (a host array is uploaded once) ->
         DeviceMaps (B, h, w, C) fc8-softmax; with want_fc8 (softmax, logits).  The range flag as in forward(): the stream is
         drained through range_status(clear=True) and a saturated forward raises WscError(WSC_ERR_RANGE) once.
         keep: the last element returned is the tape backward_dev takes -- a flat float32 DeviceMaps with `.entries` (the plan of
-        wsc_net_seg_tape_plan) and `.input_shape` (B, H, W); the maps have the bits of a forward without it."""
+        wsc_net_seg_tape_plan), `.input_shape` (B, H, W) and `.drop_prob`; the maps have the bits of a forward without it.
+        dropout: None, or (drop_prob, seed, step) -- the training forward pass (wsc_net_forward_seg_train) with the dropout sites
+        behind fc6 / fc7 active: keep-masks of (seed, step, site, element index) under the project's own counter-based contract
+        (not TensorFlow's stream), the tape's fc6* / fc7* entries the dropped, scaled activations.  0.5 is
+        the reference's `train` phase.  Needs keep=True: the tape is what backward_dev evaluates the chain rule at."""
         ctx = self.ctx
+        if dropout is not None and not keep:
+            raise ValueError("SegNet.forward_dev: dropout=%r needs keep=True (the backward pass reads the dropped tape)" % (dropout,))
         xd, mine = self._on_device(x)
         outs = []
         try:
@@ -804,9 +811,15 @@ class SegNet:
             if keep:
                 entries, elems = self.net.seg_tape_plan(B, H, W)
                 tape = DeviceMaps(ctx, (elems,), np.float32)
-                tape.entries, tape.input_shape = entries, (B, H, W)
+                tape.entries, tape.input_shape, tape.drop_prob = entries, (B, H, W), 0.0
                 outs.append(tape)
-                self.net.forward_seg_tape(xd.ptr, B, H, W, tape.ptr, elems, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
+                if dropout is None:
+                    self.net.forward_seg_tape(xd.ptr, B, H, W, tape.ptr, elems, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
+                else:
+                    drop_prob, seed, step = dropout
+                    tape.drop_prob = float(drop_prob)
+                    self.net.forward_seg_train(xd.ptr, B, H, W, drop_prob, seed, step, tape.ptr, elems, outs[0].ptr,
+                                               outs[1].ptr if want_fc8 else None, self.min_prob)
             else:
                 self.net.forward_seg(xd.ptr, B, H, W, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
             flag = ctx.range_status(clear=True)  # drains the stream; the flag is scoped to this forward
@@ -823,7 +836,7 @@ class SegNet:
         return tuple(outs) if len(outs) > 1 else outs[0]
 
     def backward_dev(self, tape, dfc8):
-        """opt.compute_gradients at drop_prob = 0 (wsc_net_backward_seg): the tape of forward_dev(keep=True) and d loss / d fc8
+        """opt.compute_gradients (wsc_net_backward_seg; wsc_net_backward_seg_drop where tape.drop_prob > 0): the tape of forward_dev(keep=True) and d loss / d fc8
         (B, h, w, C) float32 -- a DeviceMaps, e.g. the gradient loss_step_dev returns, or a host array -- -> SegGrads.  The chain rule
         evaluated at the tape, in exact fp32 whatever the net's precision.  The caller frees the result."""
         ctx = self.ctx
@@ -839,7 +852,11 @@ class SegNet:
             if gd.dtype != np.float32 or gd.shape != want:
                 raise ValueError("SegNet.backward_dev: dfc8 %r %s must be float32 %r, the fc8 map's shape" % (gd.shape, gd.dtype, want))
             out = DeviceMaps(ctx, (self._grad.grad_elems,), np.float32)
-            self._grad.backward(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr)
+            drop_prob = float(getattr(tape, "drop_prob", 0.0))
+            if drop_prob == 0.0:
+                self._grad.backward(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr)
+            else:
+                self._grad.backward_drop(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr, drop_prob)
             return SegGrads(out, self._grad.layout)
         except Exception:
             if out is not None:
@@ -937,12 +954,13 @@ class SegNet:
         grad and new_cues; every other buffer of the step is freed on every path."""
         return self._loss_step(x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, want_grad, False)[:3]
 
-    def grad_step_dev(self, x, cues, labels_or_tags, img_mean, crf_config_train, seed_size=None):
-        """One training step of Model.train up to and including compute_gradients, at drop_prob = 0: loss_step_dev's chain on a
-        kept forward pass, then backward_dev on its gradient -> (losses, grads, new_cues): loss_step_dev's losses and new_cues (bit
-        for bit), grads a SegGrads.  The caller frees grads and new_cues; every other buffer of the step -- the tape and
-        d loss / d fc8 among them -- is freed on every path."""
-        losses, grad, new_cues, tape = self._loss_step(x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, "fc8", True)
+    def grad_step_dev(self, x, cues, labels_or_tags, img_mean, crf_config_train, seed_size=None, dropout=None):
+        """One training step of Model.train up to and including compute_gradients: loss_step_dev's chain on a kept forward pass,
+        then backward_dev on its gradient -> (losses, grads, new_cues): at dropout=None (drop_prob = 0) loss_step_dev's losses and
+        new_cues (bit for bit), grads a SegGrads.  dropout: (drop_prob, seed, step) as forward_dev takes it.  The caller frees grads
+        and new_cues; every other buffer of the step -- the tape and d loss / d fc8 among them -- is freed on every path."""
+        losses, grad, new_cues, tape = self._loss_step(x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, "fc8", True,
+                                                       dropout=dropout)
         try:
             return losses, self.backward_dev(tape, grad), new_cues
         except Exception:
@@ -953,7 +971,7 @@ class SegNet:
             grad.free()
             tape.free()
 
-    def _loss_step(self, x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, want_grad, keep):
+    def _loss_step(self, x, cues, labels_or_tags, img_mean, crf_config_train, seed_size, want_grad, keep, dropout=None):
         """loss_step_dev's body -> (losses, grad, new_cues, tape); tape (keep) is forward_dev's, else None"""
         ctx = self.ctx
         xd, x_mine = self._on_device(x)
@@ -965,7 +983,7 @@ class SegNet:
                 own.append(cd)
             tape = None
             if keep:
-                prob, tape = self.forward_dev(xd, keep=True)
+                prob, tape = self.forward_dev(xd, keep=True, dropout=dropout)
                 out.append(tape)
             else:
                 prob = self.forward_dev(xd)
@@ -1028,8 +1046,10 @@ class SegNet:
 
 
 class SegTrainer:
-    """One SEC / DSRG training step after another at drop_prob = 0 (the reference's phase == 'debug' graph): Model.optimize() and
-    the update branch of Model.train() (model.py:379-404, 491-504).  Owns a SegNet (`net`), the flat float32 parameter buffer and
+    """One SEC / DSRG training step after another: Model.optimize() and the update branch of Model.train() (model.py:379-404,
+    491-504).  drop_prob = 0.0 (the default) is the reference's phase == 'debug' graph, 0.5 its 'train' phase (SEC.py:81 /
+    DSRG.py:128): dropout behind fc6 / fc7 with the keep-masks of (seed, RNG step = self.calls, site, element index) under the
+    project's own counter-based contract -- not TensorFlow's random stream.  Owns a SegNet (`net`), the flat float32 parameter buffer and
     the two slot buffers (momentum, gradient accumulator) -- DeviceMaps of net._grad.grad_elems floats in SegGrads' layout, never
     downloaded by a step.  The defaults are the reference's (model.py:36-40).
 
@@ -1042,14 +1062,17 @@ class SegTrainer:
     lr_at(epoch)    float32(base_lr * lr_decay ** (epoch // lr_step)) (model.py:493)
     params_host()   {layer: {"w": HWIO, "b": ...}}: the init-model format SegNet takes;  momentum_host() likewise
     save(path) / SegTrainer.load(path, method, num_classes, ...)   np.save / np.load(...).item() of that dict -- the .npy
-                    load_init_model reads (DSRG.py:374-377) -- with the slots and the step count under "__momentum__", "__accum__",
-                    "__step__"
+                    load_init_model reads (DSRG.py:374-377) -- with the slots under "__momentum__", "__accum__" and the step count
+                    (the RNG step of the next call), rate, seed and drop_prob under "__step__" (a file without the last two loads as 0)
     close()         releases everything"""
 
     def __init__(self, method, weights, num_classes, precision=_lib.PREC_F16X3, ctx=None, base_lr=1e-4, momentum=0.9, weight_decay=5e-4,
-                 accum_num=1, lr_decay=0.5, lr_step=4, min_prob=1e-4):
+                 accum_num=1, lr_decay=0.5, lr_step=4, min_prob=1e-4, drop_prob=0.0, seed=0):
         if int(accum_num) < 1:
             raise ValueError("SegTrainer: accum_num = %r" % (accum_num,))
+        if not 0.0 <= float(drop_prob) < 1.0:
+            raise ValueError("SegTrainer: drop_prob = %r is not in [0, 1)" % (drop_prob,))
+        self.drop_prob, self.seed = float(drop_prob), int(seed)
         self.base_lr, self.momentum, self.weight_decay = float(base_lr), float(momentum), float(weight_decay)
         self.accum_num, self.lr_decay, self.lr_step = int(accum_num), float(lr_decay), lr_step
         self.lr = np.float32(base_lr)
@@ -1093,7 +1116,8 @@ class SegTrainer:
         if epoch is not None:
             self.lr = self.lr_at(epoch)
         g = self.net._ensure_grad()
-        losses, grads, new_cues = self.net.grad_step_dev(x, cues, labels_or_tags, img_mean, crf_config_train)
+        dropout = (self.drop_prob, self.seed, self.calls) if self.drop_prob > 0.0 else None
+        losses, grads, new_cues = self.net.grad_step_dev(x, cues, labels_or_tags, img_mean, crf_config_train, dropout=dropout)
         l2 = None
         try:
             l2 = DeviceMaps(self.ctx, (1,), np.float32)
@@ -1134,13 +1158,17 @@ class SegTrainer:
         d = self.params_host()
         d["__momentum__"] = self.momentum_host()
         d["__accum__"] = self._unflatten(self.accum.to_host())
-        d["__step__"] = {"calls": self.calls, "lr": float(self.lr)}
+        d["__step__"] = {"calls": self.calls, "lr": float(self.lr), "seed": self.seed, "drop_prob": self.drop_prob}
         with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
             np.save(fh, d, allow_pickle=True)
 
     @classmethod
     def load(cls, path, method, num_classes, **kwargs):
         d = np.load(path, encoding="latin1", allow_pickle=True).item()
+        step = d.get("__step__", {})
+        # (the RNG's seed and drop_prob travel with the file, 0 where it has none; an explicit keyword wins)
+        kwargs.setdefault("seed", int(step.get("seed", 0)))
+        kwargs.setdefault("drop_prob", float(step.get("drop_prob", 0.0)))
         tr = cls(method, {k: v for k, v in d.items() if not k.startswith("__")}, num_classes, **kwargs)
         try:
             for key, name in (("__momentum__", "mom"), ("__accum__", "accum")):
