@@ -246,6 +246,13 @@ int wsc_net_forward_features(wsc_ctx *ctx, const wsc_net *net, const float *x_de
  *   dp_dev   float32 [B][2][feat_h][feat_w] = displacement field of sample 0 (minus MeanShift.running_mean) */
 int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int S, int feat_h, int feat_w,
                          float *edge_dev, float *dp_dev);
+/* Net.forward in training mode (resnet50_irn.py:110-133, as AffinityDisplacementLoss.forward calls it, :200) for N plain samples
+ * x_dev float32 [N][3][S][S]: no flip pairing, no crop, no mean shift (MeanShift is the identity while training, :105-107) and
+ * no sigmoid.  edge_dev float32 [N][He][We] = edge_out, dp_dev float32 [N][2][Hd][Wd] = dp_out, the sizes from
+ * wsc_net_edge_size (edge_hw = {He, We}, dp_hw = {Hd, Wd}; equal except for the M7 net, whose edge map is at twice the
+ * resolution).  It runs the body of wsc_net_forward_edge: that call's outputs are wsc_irn_edge_finish of these. */
+int wsc_net_edge_size(const wsc_net *net, int S, int *edge_hw, int *dp_hw);
+int wsc_net_forward_edge_raw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, float *edge_dev, float *dp_dev);
 
 /* misc.indexing.propagate_to_edge(x, edge, radius, beta, exp_times) -- the IRNet random walk called by
  * 03b_irn/step/make_sem_seg_labels.py:59,76,93 (the `misc` package is missing from the reference tree; the
@@ -754,6 +761,57 @@ int wsc_seg_loss(wsc_ctx *ctx, int method /* WSC_SEG_LOSS_SEC | WSC_SEG_LOSS_DSR
                  const float *cues_dev, const float *labels_dev /* [B][C]; SEC only, NULL for DSRG */, int B, int H, int W, int C,
                  float min_prob, const float *w_fg_host, float z_fg, const float *w_bg_host, float z_bg /* [H*W] each; SEC only */,
                  double *loss_dev /* [WSC_SEG_LOSS_N] */, float *grad_prob_dev /* or NULL */, float *grad_fc8_dev /* or NULL */);
+
+/* ---- 03b_irn: the training loss of step/train_irn.py and its gradient into the two head outputs ------------------------------
+ * AffinityDisplacementLoss.forward's four loss tensors (net/resnet50_irn.py:162-213 to_affinity, to_pair_displacement,
+ * to_displacement_loss, forward), the pair labels of GetAffinityLabelFromIndices (voc12/dataloader.py:115-131) and the
+ * reductions of step/train_irn.py:114-125, without any of the per-pair tensors:
+ *   edge_dev  float32 [B][h][w]     edge_out BEFORE the sigmoid (wsc_net_forward_edge_raw)
+ *   dp_dev    float32 [B][2][h][w]  dp_out
+ *   label_dev uint8   [B][h][w]     the reduced IR label (imutils.pil_rescale(label, 0.25, 0), voc12/dataloader.py:317)
+ *   dirs_host, path_start_host, path_yx_host, D: the PathIndex tables exactly as wsc_rw_propagate takes them
+ *   radius_floor rf = ceil(radius) - 1; valid_below: labels >= it are ignored (21 in all three dataloaders, :122; 255 = ignore)
+ * Sources are the pixels (y, x) with y < h - rf and rf <= x < w - rf; pair (s, d) joins s to t = s + dir_d.  Per pair
+ *   valid = L(s) < valid_below and L(t) < valid_below;  bg = valid and L(s) == L(t) == 0;  fg = valid and L(s) == L(t) > 0;
+ *   neg = valid and L(s) != L(t)
+ *   m = the maximum of the edge LOGITS over the path's pixels (the sigmoid is monotonic: the reference's maximum of the
+ *       sigmoids is the sigmoid of m);  aff = 1 - sigmoid(m);  pos = -log(aff + 1e-5);  neg = -log(1 + 1e-5 - aff)
+ *   pd_c = dp_c(s) - dp_c(t);  fgl = |pd_0 - dy| + |pd_1 - dx| with (dy, dx) = dir_d (disp_target);  bgl = |pd_0| + |pd_1|
+ * and over the WHOLE batch, with n_bg, n_fg, n_neg the pair counts:
+ *   pos_bg = sum(bg pos) / (n_bg + 1e-5);  pos_fg = sum(fg pos) / (n_fg + 1e-5);  pos = pos_bg / 2 + pos_fg / 2
+ *   neg    = sum(neg neg) / (n_neg + 1e-5)
+ *   dp_fg  = sum(fg fgl) / (2 n_fg + 1e-5);  dp_bg = sum(bg bgl) / (2 n_bg + 1e-5)
+ *   total  = (pos + neg) / 2 + (dp_fg + dp_bg) / 2
+ * loss_dev double [WSC_IRN_LOSS_N], the slots below.  Gradients of total, both optional (NULL: not computed, the buffer is not
+ * touched), every element written, +0.0 where no pair reaches: grad_edge_dev float32 [B][h][w], grad_dp_dev float32 [B][2][h][w].
+ * TIE RULES: the gradient of a path maximum goes to the FIRST pixel that holds it in stored path order (destination first),
+ * F.max_pool2d's rule; d|v|/dv at v == 0 is 0, as torch has it.
+ * ARITHMETIC: inputs are float32; every sigmoid, log, product and sum runs in double and each output is rounded once; the
+ * sigmoid is stable for any finite logit.  Per-pixel pair counts are integers (integer atomics: exact whatever the order);
+ * every floating-point sum has one fixed order and there is no floating-point atomic: two calls give the same bits.  The
+ * reference evaluates in float32, where 1 - sigmoid loses digits near saturation and count + 1e-5 rounds the 1e-5 away:
+ * parity with float32 torch is UNPINNED.
+ * Limits, checked before any launch (WSC_ERR_INVALID, the text names the argument): h > rf, w > 2 rf, 0 <= rf <= 16 (a tile and
+ * its halo live in LDS), 1 <= B <= 65535, D >= 1, 1 <= valid_below <= 255, every path non-empty, every direction and path
+ * offset inside [0, rf] x [-rf, rf]; no NULL among edge_dev, dp_dev, label_dev, loss_dev and the tables; the gradients overlap
+ * neither the inputs nor each other.  Asynchronous on the ctx stream. */
+enum {
+    WSC_IRN_LOSS_POS_BG = 0, /* bg_pos_aff_loss */
+    WSC_IRN_LOSS_POS_FG,     /* fg_pos_aff_loss */
+    WSC_IRN_LOSS_POS,        /* pos_aff_loss, 'loss1' */
+    WSC_IRN_LOSS_NEG,        /* neg_aff_loss, 'loss2' */
+    WSC_IRN_LOSS_DP_FG,      /* dp_fg_loss, 'loss3' */
+    WSC_IRN_LOSS_DP_BG,      /* dp_bg_loss, 'loss4' */
+    WSC_IRN_LOSS_TOTAL,      /* total_loss */
+    WSC_IRN_LOSS_N_BG,       /* sum(bg_pos_label) */
+    WSC_IRN_LOSS_N_FG,       /* sum(fg_pos_label) */
+    WSC_IRN_LOSS_N_NEG,      /* sum(neg_label) */
+    WSC_IRN_LOSS_N
+};
+int wsc_irn_aff_loss(wsc_ctx *ctx, const float *edge_dev, const float *dp_dev, const uint8_t *label_dev, int B, int h, int w,
+                     const int32_t *dirs_host, const int32_t *path_start_host, const int32_t *path_yx_host, int D, int radius_floor,
+                     int valid_below, double *loss_dev /* [WSC_IRN_LOSS_N] */, float *grad_edge_dev /* or NULL */,
+                     float *grad_dp_dev /* or NULL */);
 
 /* ---- 02_cues: the localization seeds SEC / DSRG train on (02_cues/utilities.py:183-278 get_localization_cues /
  * get_localization_cues_sec, 02_cues/adp_cues.py:304-339 update_cues; consumer 03a_sec-dsrg/model.py:238-246) ---- */

@@ -235,6 +235,25 @@ class WscStagedTable {
     std::vector<char> host;
     char *dev = nullptr;
 };
+// v[k] summed over the workgroup (a multiple of 64 threads), in every thread, in ONE order: xor butterfly inside a wave, then the
+// waves in wave order (seg_loss.hip, irn_loss.hip).  Every thread of the workgroup calls it; scratch: (waves) * NV doubles of LDS.
+template <int NV> __device__ __forceinline__ void block_sum(double (&v)[NV], double *scratch) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64); // a + b == b + a: the lanes agree to the bit
+    const int wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    __syncthreads(); // (an earlier call's readers are done with scratch)
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < NV; ++k) scratch[wave * NV + k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        double s = 0.0;
+        for (int w = 0; w < n_waves; ++w) s += scratch[w * NV + k];
+        v[k] = s;
+    }
+}
+
 // Raises the dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) of kernel `fn` to `bytes`, once per (function,
 // ctx device), under a lock: the lane threads of the drivers reach the launch sites at the same time.  WSC_ERR_HIP with the
 // error text when the runtime refuses; a failure is not recorded, so the next call tries again.
@@ -616,4 +635,6 @@ int launch_group_norm_apply(wsc_ctx *ctx, const float *x, const void *stats, con
                             int N, int H, int W, int C, int G, int up, int relu, Act y, int Hd, int Wd, int Ctot, int coff);
 int launch_edge_finish(wsc_ctx *ctx, const float *e, int He, int We, const float *d, int Hd, int Wd, int B, int fh, int fw,
                        float ms0, float ms1, float *edge, float *dp);
+// e [N][He][We], d [N][Hd][Wd][2] (8-byte aligned) -> edge [N][He][We], dp [N][2][Hd][Wd]
+int launch_edge_raw(wsc_ctx *ctx, const float *e, int He, int We, const float *d, int Hd, int Wd, int N, float *edge, float *dp);
 

@@ -299,6 +299,21 @@ __global__ void edge_finish_kernel(const float *__restrict__ e, int He, int We, 
     }
 }
 
+// Net.forward's own outputs: edge [N][He][We] = e, dp [N][2][Hd][Wd] = d [N][Hd][Wd][2] with the channel moved in front
+__global__ void edge_raw_kernel(const float *__restrict__ e, long long n_e, const float *__restrict__ d, int hw_d, long long n_d,
+                                float *__restrict__ edge, float *__restrict__ dp) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_e + n_d; i += (long long)gridDim.x * blockDim.x) {
+        if (i < n_e) {
+            edge[i] = e[i];
+        } else {
+            const long long j = i - n_e, b = j / hw_d, p = j - b * hw_d; // pixel p of sample b
+            const float2 v = *reinterpret_cast<const float2 *>(d + 2 * j);
+            dp[(2 * b) * hw_d + p] = v.x;
+            dp[(2 * b + 1) * hw_d + p] = v.y;
+        }
+    }
+}
+
 inline int grid_for(long long total) {
     long long g = (total + 255) / 256;
     if (g > 65535) g = 65535;
@@ -307,6 +322,13 @@ inline int grid_for(long long total) {
 }
 
 } // namespace
+
+int launch_edge_raw(wsc_ctx *ctx, const float *e, int He, int We, const float *d, int Hd, int Wd, int N, float *edge, float *dp) {
+    const long long n_e = (long long)N * He * We, n_d = (long long)N * Hd * Wd;
+    hipLaunchKernelGGL(edge_raw_kernel, dim3(grid_for(n_e + n_d)), dim3(256), 0, ctx->stream, e, n_e, d, Hd * Wd, n_d, edge, dp);
+    WSC_HIP(hipGetLastError());
+    return WSC_OK;
+}
 
 // x fp32 NHWC [N][H][W][C]; `partial` needs N*G*ceil(H*W/1024) double2, `stats` N*G float2
 int launch_group_norm_stats(wsc_ctx *ctx, const float *x, int N, int H, int W, int C, int G, float eps, void *partial,

@@ -1218,18 +1218,15 @@ int wsc_net_forward_trace(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, 
     return WSC_OK;
 }
 
-// EdgeDisplacement.forward (resnet50_irn.py:212-232 / vgg16_irn.py:306-321) for B images: x is the
-// [orig, h-flip] pair of each image already zero-padded to the crop size S (F.pad(x, [0, S-w, 0, S-h])).
-// Backbone with stage taps -> 12 Conv-GroupNorm-[Upsample]-ReLU heads into three concat buffers -> fc_edge6 /
-// fc_dp7[3] -> crop to (feat_h, feat_w), sigmoid(edge[0]/2 + edge[1].flip(-1)/2), dp[0] - mean_shift.
-int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int S, int feat_h, int feat_w,
-                         float *edge_dev, float *dp_dev) {
-    WSC_CHECK(ctx && net && x_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_net_forward_edge: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_net_forward_edge: the network is not an IRNet EdgeDisplacement net");
-    WSC_CHECK(B > 0 && S > 0 && feat_h > 0 && feat_w > 0, WSC_ERR_INVALID, "wsc_net_forward_edge: B=%d S=%d", B, S);
-    WSC_HIP(hipSetDevice(ctx->device));
-    const int N = 2 * B;
+// Net.forward (resnet50_irn.py:110-133 / vgg16_irn.py:192-212) for N samples [N][3][S][S], the body wsc_net_forward_edge and
+// wsc_net_forward_edge_raw share: backbone with stage taps -> 12 Conv-GroupNorm-[Upsample]-ReLU heads into three concat
+// buffers -> fc_edge6 / fc_dp7[3].  The two maps stay in the workspace: e [N][He][We], d [N][Hd][Wd][2].
+struct EdgeMaps {
+    float *e, *d;
+    int He, We, Hd, Wd;
+};
+// feat_h > 0: the crop (feat_h, feat_w) is checked against the maps before anything runs; x_dev == nullptr: the sizes alone
+static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, int feat_h, int feat_w, EdgeMaps *out) {
     Plan pl;
     WSC_TRY(plan_dims(net, N, S, &pl));
     const int NS = (int)net->taps.size(), NC = (int)net->cats.size();
@@ -1253,6 +1250,9 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
     const int He = cat_h[0], We = cat_w[0], Hd = cat_h[NC - 1], Wd = cat_w[NC - 1]; // edge / displacement maps
     WSC_CHECK(feat_h <= He && feat_w <= We && feat_h <= Hd && feat_w <= Wd, WSC_ERR_INVALID,
               "feature size %dx%d exceeds the head resolution %dx%d / %dx%d", feat_h, feat_w, He, We, Hd, Wd);
+    out->e = out->d = nullptr;
+    out->He = He; out->We = We; out->Hd = Hd; out->Wd = Wd;
+    if (!x_dev) return WSC_OK;
     size_t ftmp_elems = 0, part_bytes = 0;
     int max_groups = 1;
     for (const IrnHead &h : net->heads) {
@@ -1303,9 +1303,51 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
     }
     WSC_TRY(run_conv(net->edge6, cats[0], He, We, e_out));
     WSC_TRY(run_conv(net->dp7b, cats[NC - 1], Hd, Wd, d_out));
-    WSC_TRY(launch_edge_finish(ctx, e_out, He, We, d_out, Hd, Wd, B, feat_h, feat_w, net->mean_shift[0],
+    out->e = e_out;
+    out->d = d_out;
+    return WSC_OK;
+}
+
+// EdgeDisplacement.forward (resnet50_irn.py:212-232 / vgg16_irn.py:306-321) for B images: x is the
+// [orig, h-flip] pair of each image already zero-padded to the crop size S (F.pad(x, [0, S-w, 0, S-h])).
+// Net.forward -> crop to (feat_h, feat_w), sigmoid(edge[0]/2 + edge[1].flip(-1)/2), dp[0] - mean_shift.
+int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int S, int feat_h, int feat_w,
+                         float *edge_dev, float *dp_dev) {
+    WSC_CHECK(ctx && net && x_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_net_forward_edge: null argument");
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
+              "wsc_net_forward_edge: the network is not an IRNet EdgeDisplacement net");
+    WSC_CHECK(B > 0 && S > 0 && feat_h > 0 && feat_w > 0, WSC_ERR_INVALID, "wsc_net_forward_edge: B=%d S=%d", B, S);
+    WSC_HIP(hipSetDevice(ctx->device));
+    EdgeMaps m;
+    WSC_TRY(forward_edge_maps(ctx, net, x_dev, 2 * B, S, feat_h, feat_w, &m));
+    WSC_TRY(launch_edge_finish(ctx, m.e, m.He, m.We, m.d, m.Hd, m.Wd, B, feat_h, feat_w, net->mean_shift[0],
                                net->mean_shift[1], edge_dev, dp_dev));
     return WSC_OK;
+}
+
+// (He, We) and (Hd, Wd) of the two maps for an S x S input
+int wsc_net_edge_size(const wsc_net *net, int S, int *edge_hw, int *dp_hw) {
+    WSC_CHECK(net && edge_hw && dp_hw, WSC_ERR_INVALID, "wsc_net_edge_size: null argument");
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
+              "wsc_net_edge_size: the network is not an IRNet EdgeDisplacement net");
+    WSC_CHECK(S > 0, WSC_ERR_INVALID, "wsc_net_edge_size: S=%d", S);
+    EdgeMaps m;
+    WSC_TRY(forward_edge_maps(nullptr, net, nullptr, 1, S, 0, 0, &m));
+    edge_hw[0] = m.He; edge_hw[1] = m.We;
+    dp_hw[0] = m.Hd; dp_hw[1] = m.Wd;
+    return WSC_OK;
+}
+
+// Net.forward in training mode (resnet50_irn.py:110-133): N plain samples, no flip pairing, no crop, MeanShift the identity, no sigmoid
+int wsc_net_forward_edge_raw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, float *edge_dev, float *dp_dev) {
+    WSC_CHECK(ctx && net && x_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_net_forward_edge_raw: null argument");
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
+              "wsc_net_forward_edge_raw: the network is not an IRNet EdgeDisplacement net");
+    WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_forward_edge_raw: N=%d S=%d", N, S);
+    WSC_HIP(hipSetDevice(ctx->device));
+    EdgeMaps m;
+    WSC_TRY(forward_edge_maps(ctx, net, x_dev, N, S, 0, 0, &m));
+    return launch_edge_raw(ctx, m.e, m.He, m.We, m.d, m.Hd, m.Wd, N, edge_dev, dp_dev);
 }
 
 // The DeepLab forward pass of SEC / DSRG (create_network up to "fc8-softmax", SEC.py:117-128,246-249 / DSRG.py:169-186,297-300)

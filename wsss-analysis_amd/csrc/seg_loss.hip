@@ -48,23 +48,7 @@ struct SlMapStat { // one (image, class) map after the sort
 // per-image sums, [B][SL_P_N]
 enum { SL_P_SEED_BG = 0, SL_P_SEED_FG, SL_P_CNT_BG, SL_P_CNT_FG, SL_P_CONSTRAIN, SL_P_L1, SL_P_L2, SL_P_L3, SL_P_N };
 
-// v[k] summed over the workgroup, in every thread.  Every thread of the workgroup calls it; scratch: SL_MAX_WAVES * NV doubles.
-template <int NV> __device__ __forceinline__ void block_sum(double (&v)[NV], double *scratch) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64); // a + b == b + a: the lanes agree to the bit
-    const int wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    __syncthreads(); // (an earlier call's readers are done with scratch)
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < NV; ++k) scratch[wave * NV + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double s = 0.0;
-        for (int w = 0; w < n_waves; ++w) s += scratch[w * NV + k];
-        v[k] = s;
-    }
-}
+// (block_sum, the workgroup sum every kernel here ends in: common.h; scratch: SL_MAX_WAVES * NV doubles)
 
 // float -> uint32 whose unsigned order is the float order (-0 counts as +0: equal values must tie)
 __device__ __forceinline__ uint32_t sl_order_bits(float v) {

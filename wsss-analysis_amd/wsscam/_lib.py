@@ -132,6 +132,9 @@ _SIGNATURES = {
     "wsc_net_cam_size_hw": (_i, [_vp, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "wsc_net_forward_cam_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "wsc_net_forward_edge": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "wsc_net_edge_size": (_i, [_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "wsc_net_forward_edge_raw": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "wsc_irn_aff_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "wsc_rw_propagate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "wsc_rw_propagate_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "wsc_conv2d_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
@@ -605,6 +608,17 @@ class Net:
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_forward_edge(run.h, self.h, _ptr(x_dev), B, S, feat_h, feat_w,
                                                  _ptr(edge_dev), _ptr(dp_dev)))
+
+    def edge_size(self, S):
+        """((He, We), (Hd, Wd)): the sizes of edge_out and dp_out of an ARCH_*_IRN net for an S x S input."""
+        e, d = (_i * 2)(), (_i * 2)()
+        check(self.ctx._lib.wsc_net_edge_size(self.h, int(S), e, d))
+        return (e[0], e[1]), (d[0], d[1])
+
+    def forward_edge_raw(self, x_dev, N, S, edge_dev, dp_dev, ctx=None):
+        """Net.forward in training mode (wsc_net_forward_edge_raw): x_dev [N][3][S][S] -> edge_out [N][He][We], dp_out [N][2][Hd][Wd]."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_forward_edge_raw(run.h, self.h, _ptr(x_dev), int(N), int(S), _ptr(edge_dev), _ptr(dp_dev)))
 
     def seg_size_hw(self, H, W):
         """The fc8 map size of an ARCH_DEEPLAB_* net for an H x W input (41 x 41 at 321 x 321)."""
@@ -1228,6 +1242,26 @@ def seg_loss(ctx, method, prob_dev, crf_dev, cues_dev, labels_dev, B, H, W, C, m
     check(ctx._lib.wsc_seg_loss(ctx.h, int(method), _ptr(prob_dev), _ptr(crf_dev), _ptr(cues_dev), _ptr(labels_dev), int(B), int(H),
                                 int(W), int(C), float(min_prob), _ptr(tabs[0]), float(z_fg), _ptr(tabs[1]), float(z_bg),
                                 _ptr(loss_dev), _ptr(grad_prob_dev), _ptr(grad_fc8_dev)))
+
+
+# slots of wsc_irn_aff_loss's loss_dev (include/wsscam.h WSC_IRN_LOSS_*)
+IRN_LOSS_SLOTS = ("pos_bg", "pos_fg", "pos", "neg", "dp_fg", "dp_bg", "total", "n_bg", "n_fg", "n_neg")
+
+
+def irn_aff_loss(ctx, edge_dev, dp_dev, label_dev, B, h, w, dirs, path_start, path_yx, radius_floor, valid_below, loss_dev,
+                 grad_edge_dev=None, grad_dp_dev=None):
+    """wsc_irn_aff_loss: the IRNet training loss (float64 [len(IRN_LOSS_SLOTS)] in loss_dev) of edge_dev float32 [B][h][w] (logits),
+    dp_dev float32 [B][2][h][w] and label_dev uint8 [B][h][w] and, where a buffer is given, d total / d edge and d total / d dp.
+    dirs / path_start / path_yx: PathIndex.device_tables(); asynchronous."""
+    dirs = np.ascontiguousarray(dirs, dtype=np.int32)
+    path_start = np.ascontiguousarray(path_start, dtype=np.int32)
+    path_yx = np.ascontiguousarray(path_yx, dtype=np.int32)
+    if dirs.ndim != 2 or dirs.shape[1] != 2 or path_start.shape != (dirs.shape[0] + 1,) or path_yx.ndim != 2 or path_yx.shape[1] != 2 \
+            or (len(path_start) and int(path_start.max()) > path_yx.shape[0]):
+        raise ValueError("irn_aff_loss: path tables of shapes %r, %r, %r" % (dirs.shape, path_start.shape, path_yx.shape))
+    check(ctx._lib.wsc_irn_aff_loss(ctx.h, _ptr(edge_dev), _ptr(dp_dev), _ptr(label_dev), int(B), int(h), int(w), _ptr(dirs),
+                                    _ptr(path_start), _ptr(path_yx), int(dirs.shape[0]), int(radius_floor), int(valid_below),
+                                    _ptr(loss_dev), _ptr(grad_edge_dev), _ptr(grad_dp_dev)))
 
 
 def cue_maps(ctx, cams_nhwc_dev, B, h, w, C_all, chan, gate_dev, S, out_dev):

@@ -66,6 +66,43 @@ class EdgeDisplacementBase(DeviceCAMBase):
             net.forward_edge(st["dev"], B, S, fh, fw, edge_dev, dp_dev, ctx=ctx)
         return edge_dev, dp_dev, (B, fh, fw)
 
+    def forward_train_dev(self, x):
+        """Net.forward in training mode (resnet50_irn.py:110-133, what AffinityDisplacementLoss.forward calls at :200), outputs
+        left in HBM: x float32 (N,3,S,S), a host array / tensor or a secdsrg.DeviceMaps of the model's context (read in place)
+        -> (edge_out DeviceMaps (N,He,We), dp_out DeviceMaps (N,2,Hd,Wd)): plain samples, no flip pairing, no crop, no mean shift
+        (MeanShift is the identity while training), no sigmoid."""
+        from ..secdsrg import DeviceMaps
+
+        net = self._ensure_net()
+        ctx = self._ctx
+        mine = None
+        if isinstance(x, DeviceMaps):
+            if x.dtype != np.float32 or x.ctx is not ctx:
+                raise ValueError("forward_train_dev: x is %s on %s, not float32 on the model's context" %
+                                 (x.dtype, "another context" if x.ctx is not ctx else "this context"))
+            xd = x
+        else:
+            xn = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+            xd = mine = DeviceMaps.from_host(ctx, xn, dtype=np.float32)
+        edge = dp = None
+        try:
+            if len(xd.shape) != 4 or xd.shape[1] != 3 or xd.shape[2] != xd.shape[3] or 0 in xd.shape:
+                raise ValueError("forward_train_dev: x has shape %r, expected (N, 3, S, S)" % (xd.shape,))
+            N, S = xd.shape[0], xd.shape[2]
+            (He, We), (Hd, Wd) = net.edge_size(S)
+            edge = DeviceMaps(ctx, (N, He, We), np.float32)
+            dp = DeviceMaps(ctx, (N, 2, Hd, Wd), np.float32)
+            net.forward_edge_raw(xd.ptr, N, S, edge.ptr, dp.ptr)
+            return edge, dp
+        except Exception:
+            for m in (edge, dp):
+                if m is not None:
+                    m.free()
+            raise
+        finally:
+            if mine is not None:
+                mine.free()
+
     def forward(self, x):
         is_torch = hasattr(x, "detach")
         xn = x.detach().cpu().numpy() if is_torch else np.asarray(x)
