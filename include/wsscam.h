@@ -813,6 +813,59 @@ int wsc_irn_aff_loss(wsc_ctx *ctx, const float *edge_dev, const float *dp_dev, c
                      int valid_below, double *loss_dev /* [WSC_IRN_LOSS_N] */, float *grad_edge_dev /* or NULL */,
                      float *grad_dp_dev /* or NULL */);
 
+/* ---- backward pass of the IRNet heads: total_loss.backward() of step/train_irn.py:127 ------------------------------------------
+ * Net.forward detaches every backbone stage (resnet50_irn.py:111-115) and trainable_parameters() is edge_layers + dp_layers, so
+ * the gradient of the heads is the whole gradient of a step.  wsc_irn_aff_loss hands out d total / d edge_out and d total /
+ * d dp_out; wsc_net_backward_edge carries them to every head parameter in exact fp32 / double whatever the net's forward
+ * precision.  The definition is the chain rule EVALUATED AT THE TAPE: a ReLU passes its gradient where the taped concat value is
+ * > 0 (an exact 0 masks); the bilinear upsample's adjoint uses the float weights of the forward kernel, both taps counting where
+ * they land on one source pixel; the crop drops what lies outside; GroupNorm's backward takes xh = (z - mean) rstd from the taped
+ * z and the taped float {mean, rstd}; stage taps receive no gradient; each concat buffer has one reader, so its gradient is
+ * written whole and never accumulated.
+ *
+ * The tape: wsc_net_edge_tape_plan lists, for N samples of S x S, every stage tap a head reads ("x<k>", [N][H][W][C]), per head
+ * its conv output ("<head>.z", [N][ho][wo][Cout]) and its GroupNorm statistics ("<head>.stats", [N][1][1][2 G]: the {mean, rstd}
+ * float pairs of the forward pass), and every concat buffer ("cat<i>", [N][Hc][Wc][Ctot], padding channels included) -- float32
+ * at `offset` floats of one buffer of *tape_elems_out floats, each the value the next op read (hi + lo of a two-plane precision);
+ * entries start on 256-byte lines and the floats between them are not written.  max_entries = 0 for the count.
+ * wsc_net_forward_edge_tape is wsc_net_forward_edge_raw (the same launches, the same bits in edge_dev / dp_dev) with a head's conv
+ * and statistics written straight into their entries and the taps and concat buffers copied.  tape_dev starts on a 256-byte line.
+ *
+ * wsc_irn_grad: the rotated fp32 kernels of the data-gradient convolutions (packed once) and the backward workspace (grown on
+ * demand; it belongs to the stream of the ctx the object was created on).  `weights`: the list wsc_net_create took; a head tensor
+ * that is not the net's is WSC_ERR_SHAPE naming the layer.  The net must outlive the object.  wsc_irn_grad_layout: ONE ENTRY PER
+ * PARAMETER in the order of trainable_parameters() -- the heads of edge_layers (`<head>.0.weight`, `<head>.1.weight`,
+ * `<head>.1.bias`), the final edge conv's `.weight` / `.bias`, the heads of dp_layers, the final displacement conv's `.weight` --
+ * under their state-dict names.  A conv weight has kh = kw = 1, its Cin / Cout, w_off its first float and b_off = -1; it lies as
+ * [Cin][Cout] (what the GEMM writes: the transpose of torch's [Cout][Cin][1][1]).  A vector (GroupNorm weight / bias, conv bias)
+ * has kh = kw = 0, Cin = 0, Cout its length, b_off its first float and w_off = -1.  No gaps; the padding channels of a concat
+ * buffer (160 -> 192) have no entry.
+ *
+ * wsc_net_backward_edge: dedge_dev float32 [N][He][We], ddp_dev float32 [N][2][Hd][Wd] (the layouts wsc_irn_aff_loss writes) ->
+ * every element of grad_dev.  Asynchronous on the ctx stream (the first call at a larger size allocates the workspace).  A net
+ * that is no IRNet net, a ctx other than the object's, a tape or gradient size other than the plan's / the layout's is
+ * WSC_ERR_INVALID before any launch.  Two calls give the same bits: no floating-point atomic, every sum in one fixed order.
+ *
+ * The two new kernels one by one, for the per-op tests (float32 NHWC, the pass's own launchers unchanged):
+ * wsc_relu_upsample_grad_nhwc: dy_dev [N][H][W][C] = the adjoint of "upsample by up (1, 2, 4), crop to Hd x Wd, ReLU, write
+ *   channels [coff, coff + C) of [N][Hd][Wd][Ctot]" applied to dcat_dev, masked by cat_dev > 0 (both [N][Hd][Wd][Ctot]).
+ * wsc_group_norm_grad_nhwc: dz_dev [N][H][W][C], dgamma_dev [C], dbeta_dev [C] of nn.GroupNorm(G, C) at input z_dev and output
+ *   gradient dy_dev; gamma_host [C]; the statistics are formed as the forward pass forms them (float {mean, rstd}). */
+int wsc_net_edge_tape_plan(wsc_ctx *ctx, const wsc_net *net, int N, int S, wsc_tape_entry *entries_out, int max_entries, int *n_out,
+                           long long *tape_elems_out);
+int wsc_net_forward_edge_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, float *tape_dev, long long tape_elems,
+                              float *edge_dev, float *dp_dev);
+typedef struct wsc_irn_grad wsc_irn_grad;
+int wsc_irn_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_irn_grad **out);
+void wsc_irn_grad_destroy(wsc_irn_grad *g);
+int wsc_irn_grad_layout(const wsc_irn_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out);
+int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const float *tape_dev, long long tape_elems, const float *dedge_dev,
+                          const float *ddp_dev, float *grad_dev, long long grad_elems);
+int wsc_relu_upsample_grad_nhwc(wsc_ctx *ctx, const float *dcat_dev, const float *cat_dev, int N, int H, int W, int C, int up, int Hd, int Wd,
+                                int Ctot, int coff, float *dy_dev);
+int wsc_group_norm_grad_nhwc(wsc_ctx *ctx, const float *z_dev, const float *dy_dev, int N, int H, int W, int C, const float *gamma_host, int G,
+                             float eps, float *dz_dev, float *dgamma_dev, float *dbeta_dev);
+
 /* ---- 02_cues: the localization seeds SEC / DSRG train on (02_cues/utilities.py:183-278 get_localization_cues /
  * get_localization_cues_sec, 02_cues/adp_cues.py:304-339 update_cues; consumer 03a_sec-dsrg/model.py:238-246) ---- */
 

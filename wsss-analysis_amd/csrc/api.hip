@@ -157,7 +157,8 @@ WscKernelTimer::~WscKernelTimer() {
 static const char *kClassNames[WSC_K_COUNT] = {
     "conv_igemm_kernel<256-row tiles,glds>", "conv_igemm_kernel<128x128,glds>", "conv_igemm_kernel<128x64,glds>", "conv_igemm_kernel<small-Cin> / stem_pool_kernel",
     "pool/layout/flip-add", "cam_tail+unary", "crf_build(all)", "gauss_msg_kernel", "combine4+blur_lds+blur4+blur3_tile",
-    "update_splat_kernel", "crf init/finish", "wgrad_kernel+reduce", "grad mask/bias/pool"};
+    "update_splat_kernel", "crf init/finish", "wgrad_kernel+reduce", "grad mask/bias/pool", "relu_up_grad_kernel",
+    "gn_grad partial+columns+finish+apply"};
 
 int wsc_ctx_range_check(wsc_ctx *ctx) {
     const unsigned f = *(volatile unsigned *)ctx->range_host;

@@ -118,6 +118,8 @@ enum WscKernelClass {
     WSC_K_CRF_MISC,      // init_q / finish
     WSC_K_WGRAD,         // wgrad_kernel + wgrad_reduce_kernel (seg_grad.hip); work = algorithmic FLOPs
     WSC_K_GRAD_MISC,     // ReLU mask + bias gradient, pool gradients, channel copies of the backward pass
+    WSC_K_UPSAMPLE_GRAD, // relu_up_grad_kernel (irn_grad.hip)
+    WSC_K_GN_GRAD,       // gn_grad_partial / columns / finish / apply kernels (irn_grad.hip)
     WSC_K_COUNT
 };
 struct WscProfRecord {
@@ -637,4 +639,19 @@ int launch_edge_finish(wsc_ctx *ctx, const float *e, int He, int We, const float
                        float ms0, float ms1, float *edge, float *dp);
 // e [N][He][We], d [N][Hd][Wd][2] (8-byte aligned) -> edge [N][He][We], dp [N][2][Hd][Wd]
 int launch_edge_raw(wsc_ctx *ctx, const float *e, int He, int We, const float *d, int Hd, int Wd, int N, float *edge, float *dp);
+
+// ---- irn_grad.hip: the fp32 / double kernels of the backward pass of the IRNet heads (the contract: its header) ----------------
+// dy [N][H][W][C] = the adjoint of "upsample by `up`, crop to Hd x Wd, ReLU, write channels [coff, coff + C)" applied to dcat
+// [N][Hd][Wd][Ctot]; the ReLU mask is cat > 0 (the taped concat values); every element of dy is written
+int launch_relu_upsample_grad(wsc_ctx *ctx, const float *dcat, const float *cat, int N, int H, int W, int C, int up, int Hd, int Wd, int Ctot,
+                              int coff, float *dy);
+// dz [N][H][W][C], dgamma [C], dbeta [C] of GroupNorm(G, C) from its input z, the {mean, rstd} pairs `stats` [N][G] of the forward
+// pass and the gradient dy of its output; partial: group_norm_grad_partial_bytes, ms: N G double2
+size_t group_norm_grad_partial_bytes(int N, int H, int W, int C);
+int launch_group_norm_grad(wsc_ctx *ctx, const float *z, const void *stats, const float *gamma, const float *dy, int N, int H, int W, int C,
+                           int G, void *partial, void *ms, float *dz, float *dgamma, float *dbeta);
+// y [N][Ho][Wo][C] = x[:, ::stride, ::stride, :] (C a multiple of 4)
+int launch_strided_rows_f32(wsc_ctx *ctx, const float *x, int N, int H, int W, int C, int stride, int Ho, int Wo, float *y);
+// ddp [N][2][HW] -> out [N HW][Cd], zeros past channel 1
+int launch_dp_to_nhwc(wsc_ctx *ctx, const float *ddp, int N, int HW, int Cd, float *out);
 

@@ -41,6 +41,7 @@ struct ConvW {
 
 // one Conv2d(1x1, bias=False) -> GroupNorm -> [Upsample] -> ReLU head of the IRNet branches
 struct IrnHead {
+    std::string name; // the state-dict prefix: `<name>.0.weight`, `<name>.1.{weight,bias}`
     ConvW conv;
     int groups = 1, up = 1;
     float *gamma = nullptr, *beta = nullptr; // device, [Cout]
@@ -97,6 +98,8 @@ struct wsc_net {
     std::vector<IrnHead> heads;  // every Conv-GroupNorm-[Upsample]-ReLU head in execution order
     std::vector<IrnCat> cats;    // concat buffers; cats[0] feeds the final edge conv, cats.back() the final dp conv
     ConvW edge6, dp7b;           // final edge conv (bias) / final displacement conv
+    std::string edge_final, dp_final; // their state-dict names without ".weight"
+    int edge_in = 0;             // input channels of the final edge conv before the padding to cats[0].channels
     float mean_shift[2] = {0.f, 0.f};
     std::vector<SegBranch> seg;  // WSC_ARCH_DEEPLAB_*: one branch (LFOV, SEC) or four (ASPP, DSRG); fc8 = their sum
     std::vector<void *> allocs;
@@ -605,6 +608,7 @@ int add_irn_head(wsc_net *net, const Dict &d, const HeadSpec &hs) {
                   b->shape[0] == hs.cout,
               WSC_ERR_SHAPE, "'%s': expected a 1x1 conv with %d outputs + GroupNorm", hs.name, hs.cout);
     IrnHead h;
+    h.name = nm;
     std::vector<float> one(hs.cout, 1.f), zero(hs.cout, 0.f);
     WSC_TRY(make_conv(net, w, hs.stride, 0, 0, CONV_FORM_GENERIC, one, zero, nullptr, nullptr, &h.conv));
     h.groups = hs.groups; h.up = hs.up; h.src = hs.src; h.dst = hs.dst; h.coff = hs.coff;
@@ -617,6 +621,7 @@ int add_irn_head(wsc_net *net, const Dict &d, const HeadSpec &hs) {
 int build_irn_heads(wsc_net *net, const Dict &d, const std::vector<HeadSpec> &specs, const std::vector<IrnCat> &cats,
                     const std::string &edge_final, int edge_in, const std::string &dp_final) {
     net->cats = cats;
+    net->edge_final = edge_final; net->dp_final = dp_final; net->edge_in = edge_in;
     for (const HeadSpec &hs : specs) WSC_TRY(add_irn_head(net, d, hs));
     // final edge conv = Conv2d(edge_in, 1, 1, bias=True) on the edge concat, zero-padded to cats[0].channels inputs
     const HostTensor *w6, *b6, *w7;
@@ -1225,29 +1230,100 @@ struct EdgeMaps {
     float *e, *d;
     int He, We, Hd, Wd;
 };
-// feat_h > 0: the crop (feat_h, feat_w) is checked against the maps before anything runs; x_dev == nullptr: the sizes alone
-static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, int feat_h, int feat_w, EdgeMaps *out) {
+// The sizes of everything between the stage taps and the two maps for N samples of S x S
+struct EdgeGeom {
     Plan pl;
-    WSC_TRY(plan_dims(net, N, S, &pl));
+    std::vector<int> Hs, Ws, Cs;             // stage taps
+    std::vector<int> cat_c, cat_h, cat_w;    // concat buffers
+    std::vector<size_t> cat_elems;
+    struct Head { int sh, sw, sc, ho, wo; }; // a head's source tensor and its conv output (before the upsample)
+    std::vector<Head> heads;
+    int He, We, Hd, Wd;
+};
+static int edge_outdim(int v, int stride) { return (v - 1) / stride + 1; }
+static int edge_geom(const wsc_net *net, int N, int S, EdgeGeom *g) {
+    WSC_TRY(plan_dims(net, N, S, &g->pl));
     const int NS = (int)net->taps.size(), NC = (int)net->cats.size();
-    std::vector<int> Hs(NS), Ws(NS), Cs(NS);
+    g->Hs.resize(NS); g->Ws.resize(NS); g->Cs.resize(NS);
     for (int k = 0; k < NS; ++k) {
-        const OpDims &d = pl.ops[net->taps[k]];
-        Hs[k] = d.Ho; Ws[k] = d.Wo; Cs[k] = d.Co;
+        const OpDims &d = g->pl.ops[net->taps[k]];
+        g->Hs[k] = d.Ho; g->Ws[k] = d.Wo; g->Cs[k] = d.Co;
     }
-    auto outdim = [](int v, int stride) { return (v - 1) / stride + 1; };
-    std::vector<int> cat_c(NC), cat_h(NC), cat_w(NC);
-    std::vector<size_t> cat_elems(NC);
-    size_t off = taps_bytes(net, pl, N); // workspace after the backbone's: taps, concat buffers, then the scratch below
+    g->cat_c.resize(NC); g->cat_h.resize(NC); g->cat_w.resize(NC); g->cat_elems.resize(NC);
     for (int i = 0; i < NC; ++i) {
         const IrnCat &c = net->cats[i];
-        cat_c[i] = c.channels;
-        cat_h[i] = outdim(Hs[c.stage - 1], c.stride);
-        cat_w[i] = outdim(Ws[c.stage - 1], c.stride);
-        cat_elems[i] = (size_t)N * cat_h[i] * cat_w[i] * cat_c[i];
-        off += act_bytes(cat_elems[i], net->prec);
+        g->cat_c[i] = c.channels;
+        g->cat_h[i] = edge_outdim(g->Hs[c.stage - 1], c.stride);
+        g->cat_w[i] = edge_outdim(g->Ws[c.stage - 1], c.stride);
+        g->cat_elems[i] = (size_t)N * g->cat_h[i] * g->cat_w[i] * g->cat_c[i];
     }
-    const int He = cat_h[0], We = cat_w[0], Hd = cat_h[NC - 1], Wd = cat_w[NC - 1]; // edge / displacement maps
+    g->He = g->cat_h[0]; g->We = g->cat_w[0]; g->Hd = g->cat_h[NC - 1]; g->Wd = g->cat_w[NC - 1]; // edge / displacement maps
+    g->heads.clear();
+    for (const IrnHead &h : net->heads) {
+        const int k = h.src > 0 ? h.src - 1 : -h.src - 1; // a stage tap, or a concat buffer
+        EdgeGeom::Head hg;
+        hg.sh = h.src > 0 ? g->Hs[k] : g->cat_h[k];
+        hg.sw = h.src > 0 ? g->Ws[k] : g->cat_w[k];
+        hg.sc = h.src > 0 ? g->Cs[k] : g->cat_c[k];
+        hg.ho = edge_outdim(hg.sh, h.conv.stride);
+        hg.wo = edge_outdim(hg.sw, h.conv.stride);
+        g->heads.push_back(hg);
+    }
+    return WSC_OK;
+}
+
+// What the backward pass of the heads needs of a forward pass, as float32 in one buffer (each "the value the next op read": hi +
+// lo of a two-plane precision): every stage tap a head reads "x<k>" [N][H][W][C]; per head its conv output "<head>.z"
+// [N][ho][wo][Cout] and its GroupNorm statistics "<head>.stats" [N][1][1][2 G] = {mean, rstd} pairs as gn_finish_kernel wrote
+// them; every concat buffer "cat<i>" [N][Hc][Wc][Ctot], padding channels included
+struct EdgeTapePlan {
+    EdgeGeom g;
+    std::vector<wsc_tape_entry> e;
+    std::vector<int> tap, z, stats, cat; // entry of stage k (-1: no head reads it), of head j (two), of concat buffer i
+    long long elems = 0;
+};
+static int edge_tape_plan(const wsc_net *net, int N, int S, EdgeTapePlan *tp) {
+    WSC_TRY(edge_geom(net, N, S, &tp->g));
+    const EdgeGeom &g = tp->g;
+    auto add = [&](const std::string &name, int Ho, int Wo, int C) {
+        wsc_tape_entry t = {};
+        std::strncpy(t.name, name.c_str(), sizeof(t.name) - 1);
+        t.Ho = Ho; t.Wo = Wo; t.C = C;
+        t.offset = tp->elems;
+        tp->elems += ((long long)N * Ho * Wo * C + 63) / 64 * 64; // (entries start on 256-byte lines)
+        tp->e.push_back(t);
+        return (int)tp->e.size() - 1;
+    };
+    tp->tap.assign(net->taps.size(), -1);
+    for (size_t k = 0; k < net->taps.size(); ++k) {
+        bool read = false;
+        for (const IrnHead &h : net->heads) read = read || h.src == (int)k + 1;
+        if (read) tp->tap[k] = add("x" + std::to_string(k + 1), g.Hs[k], g.Ws[k], g.Cs[k]);
+    }
+    for (size_t j = 0; j < net->heads.size(); ++j) {
+        const IrnHead &h = net->heads[j];
+        tp->z.push_back(add(h.name + ".z", g.heads[j].ho, g.heads[j].wo, h.conv.Cout));
+        tp->stats.push_back(add(h.name + ".stats", 1, 1, 2 * h.groups));
+    }
+    for (size_t i = 0; i < net->cats.size(); ++i) tp->cat.push_back(add("cat" + std::to_string(i), g.cat_h[i], g.cat_w[i], g.cat_c[i]));
+    return WSC_OK;
+}
+
+// feat_h > 0: the crop (feat_h, feat_w) is checked against the maps before anything runs; x_dev == nullptr: the sizes alone.
+// tp / tape (wsc_net_forward_edge_tape): the same launches; a head's conv and statistics kernels write straight into their tape
+// entries (instead of the scratch they otherwise use), the taps and the concat buffers are copied
+static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, int feat_h, int feat_w, EdgeMaps *out,
+                             const EdgeTapePlan *tp = nullptr, float *tape = nullptr) {
+    EdgeGeom geom;
+    if (!tp) WSC_TRY(edge_geom(net, N, S, &geom));
+    const EdgeGeom &g = tp ? tp->g : geom;
+    const Plan &pl = g.pl;
+    const int NC = (int)net->cats.size();
+    const std::vector<int> &Hs = g.Hs, &Ws = g.Ws, &Cs = g.Cs, &cat_c = g.cat_c, &cat_h = g.cat_h, &cat_w = g.cat_w;
+    const std::vector<size_t> &cat_elems = g.cat_elems;
+    size_t off = taps_bytes(net, pl, N); // workspace after the backbone's: taps, concat buffers, then the scratch below
+    for (int i = 0; i < NC; ++i) off += act_bytes(cat_elems[i], net->prec);
+    const int He = g.He, We = g.We, Hd = g.Hd, Wd = g.Wd;
     WSC_CHECK(feat_h <= He && feat_w <= We && feat_h <= Hd && feat_w <= Wd, WSC_ERR_INVALID,
               "feature size %dx%d exceeds the head resolution %dx%d / %dx%d", feat_h, feat_w, He, We, Hd, Wd);
     out->e = out->d = nullptr;
@@ -1255,10 +1331,9 @@ static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_de
     if (!x_dev) return WSC_OK;
     size_t ftmp_elems = 0, part_bytes = 0;
     int max_groups = 1;
-    for (const IrnHead &h : net->heads) {
-        const int sh = h.src > 0 ? Hs[h.src - 1] : cat_h[-h.src - 1];
-        const int sw = h.src > 0 ? Ws[h.src - 1] : cat_w[-h.src - 1];
-        const int ho = outdim(sh, h.conv.stride), wo = outdim(sw, h.conv.stride);
+    for (size_t j = 0; j < net->heads.size(); ++j) {
+        const IrnHead &h = net->heads[j];
+        const int ho = g.heads[j].ho, wo = g.heads[j].wo;
         ftmp_elems = std::max(ftmp_elems, (size_t)N * ho * wo * h.conv.Cout);
         part_bytes = std::max(part_bytes, group_norm_partial_bytes(N, ho, wo, h.groups));
         max_groups = std::max(max_groups, h.groups);
@@ -1281,26 +1356,33 @@ static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_de
     void *gn_part = sp[1], *gn_stats = sp[2];
     // the padding channels of the edge concat feed zero weights but must not hold NaN bit patterns
     WSC_HIP(hipMemsetAsync(cats[0].hi, 0, act_bytes(cat_elems[0], net->prec), ctx->stream));
+    if (tp)
+        for (size_t k = 0; k < taps.size(); ++k)
+            if (tp->tap[k] >= 0) WSC_TRY(launch_act_to_f32(ctx, taps[k], (size_t)N * Hs[k] * Ws[k] * Cs[k], tape + tp->e[tp->tap[k]].offset));
 
     auto run_conv = [&](const ConvW &c, Act x, int H, int W, float *y_f32) -> int {
         ConvLaunch L = conv_launch(c, net->prec); // (1 x 1, no padding, no ReLU: build_irn_heads)
         L.x = x;
         L.y_f32 = y_f32;
-        L.N = N; L.H = H; L.W = W; L.Ho = outdim(H, c.stride); L.Wo = outdim(W, c.stride);
+        L.N = N; L.H = H; L.W = W; L.Ho = edge_outdim(H, c.stride); L.Wo = edge_outdim(W, c.stride);
         return conv_igemm_launch(ctx, L);
     };
-    for (const IrnHead &h : net->heads) {
+    for (size_t j = 0; j < net->heads.size(); ++j) {
+        const IrnHead &h = net->heads[j];
+        const EdgeGeom::Head &hg = g.heads[j];
         const int k = h.src > 0 ? h.src - 1 : -h.src - 1; // a stage tap, or a concat buffer
         const Act x = h.src > 0 ? taps[k] : cats[k];
-        const int sh = h.src > 0 ? Hs[k] : cat_h[k], sw = h.src > 0 ? Ws[k] : cat_w[k], sc = h.src > 0 ? Cs[k] : cat_c[k];
-        WSC_CHECK(sc == h.conv.Cin, WSC_ERR_SHAPE, "IRNet head: %d input channels, the weights expect %d", sc, h.conv.Cin);
-        WSC_TRY(run_conv(h.conv, x, sh, sw, ftmp));
-        const int ho = outdim(sh, h.conv.stride), wo = outdim(sw, h.conv.stride);
-        WSC_TRY(launch_group_norm_stats(ctx, ftmp, N, ho, wo, h.conv.Cout, h.groups, 1e-5f, gn_part, gn_stats));
+        WSC_CHECK(hg.sc == h.conv.Cin, WSC_ERR_SHAPE, "IRNet head: %d input channels, the weights expect %d", hg.sc, h.conv.Cin);
+        float *z = tp ? tape + tp->e[tp->z[j]].offset : ftmp;
+        void *stats = tp ? (void *)(tape + tp->e[tp->stats[j]].offset) : gn_stats;
+        WSC_TRY(run_conv(h.conv, x, hg.sh, hg.sw, z));
+        WSC_TRY(launch_group_norm_stats(ctx, z, N, hg.ho, hg.wo, h.conv.Cout, h.groups, 1e-5f, gn_part, stats));
         const int di = h.dst;
-        WSC_TRY(launch_group_norm_apply(ctx, ftmp, gn_stats, h.gamma, h.beta, N, ho, wo, h.conv.Cout, h.groups,
+        WSC_TRY(launch_group_norm_apply(ctx, z, stats, h.gamma, h.beta, N, hg.ho, hg.wo, h.conv.Cout, h.groups,
                                         h.up, 1, cats[di], cat_h[di], cat_w[di], cat_c[di], h.coff));
     }
+    if (tp)
+        for (int i = 0; i < NC; ++i) WSC_TRY(launch_act_to_f32(ctx, cats[i], cat_elems[i], tape + tp->e[tp->cat[i]].offset));
     WSC_TRY(run_conv(net->edge6, cats[0], He, We, e_out));
     WSC_TRY(run_conv(net->dp7b, cats[NC - 1], Hd, Wd, d_out));
     out->e = e_out;
@@ -1347,6 +1429,38 @@ int wsc_net_forward_edge_raw(wsc_ctx *ctx, const wsc_net *net, const float *x_de
     WSC_HIP(hipSetDevice(ctx->device));
     EdgeMaps m;
     WSC_TRY(forward_edge_maps(ctx, net, x_dev, N, S, 0, 0, &m));
+    return launch_edge_raw(ctx, m.e, m.He, m.We, m.d, m.Hd, m.Wd, N, edge_dev, dp_dev);
+}
+
+int wsc_net_edge_tape_plan(wsc_ctx *ctx, const wsc_net *net, int N, int S, wsc_tape_entry *entries_out, int max_entries, int *n_out,
+                           long long *tape_elems_out) {
+    WSC_CHECK(ctx && net && n_out && tape_elems_out, WSC_ERR_INVALID, "wsc_net_edge_tape_plan: null argument");
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
+              "wsc_net_edge_tape_plan: the network is not an IRNet EdgeDisplacement net");
+    WSC_CHECK(N > 0 && S > 0 && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
+              "wsc_net_edge_tape_plan: N=%d S=%d, room for %d entries", N, S, max_entries);
+    EdgeTapePlan tp;
+    WSC_TRY(edge_tape_plan(net, N, S, &tp));
+    *n_out = (int)tp.e.size();
+    *tape_elems_out = tp.elems;
+    for (int i = 0; i < max_entries && i < (int)tp.e.size(); ++i) entries_out[i] = tp.e[i];
+    return WSC_OK;
+}
+
+int wsc_net_forward_edge_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, float *tape_dev, long long tape_elems,
+                              float *edge_dev, float *dp_dev) {
+    WSC_CHECK(ctx && net && x_dev && tape_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: null argument");
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
+              "wsc_net_forward_edge_tape: the network is not an IRNet EdgeDisplacement net");
+    WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: N=%d S=%d", N, S);
+    WSC_CHECK(((uintptr_t)tape_dev & 255) == 0, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: the tape must start on a 256-byte line");
+    EdgeTapePlan tp;
+    WSC_TRY(edge_tape_plan(net, N, S, &tp));
+    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: a tape of %lld floats, the plan has %lld (wsc_net_edge_tape_plan)",
+              tape_elems, tp.elems);
+    WSC_HIP(hipSetDevice(ctx->device));
+    EdgeMaps m;
+    WSC_TRY(forward_edge_maps(ctx, net, x_dev, N, S, 0, 0, &m, &tp, tape_dev));
     return launch_edge_raw(ctx, m.e, m.He, m.We, m.d, m.Hd, m.Wd, N, edge_dev, dp_dev);
 }
 
@@ -1790,6 +1904,241 @@ int wsc_net_backward_seg_drop(wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W
     WSC_TRY(seg_dropout_check("wsc_net_backward_seg_drop", drop_prob, 0));
     return backward_seg("wsc_net_backward_seg_drop", ctx, g, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, grad_elems,
                         seg_dropout_scale(drop_prob));
+}
+
+// ---- the backward pass of the IRNet heads: d total / d edge_out, d total / d dp_out -> the gradient of every head parameter --------
+// Every backbone stage is detached in Net.forward (resnet50_irn.py:111-115), so this is the whole gradient of a step.  The pass walks
+// net->heads in reverse; the kernels are irn_grad.hip's, the GEMMs seg_grad.hip's.
+namespace {
+struct IrnGradHead {
+    long long w_off = 0, g_off = 0, b_off = 0; // conv weight [Cin][Cout], GroupNorm weight, GroupNorm bias
+    float *w_rot = nullptr;                    // the data-gradient kernel (dgrad_pack) of a head that reads a concat buffer
+};
+} // namespace
+struct wsc_irn_grad {
+    wsc_ctx *ctx = nullptr;
+    const wsc_net *net = nullptr;
+    std::vector<IrnGradHead> heads; // one per net->heads
+    long long edge_w_off = 0, edge_b_off = 0, dp_w_off = 0;
+    float *edge_rot = nullptr, *dp_rot = nullptr;
+    std::vector<wsc_grad_entry> layout; // one entry per parameter, in the order of trainable_parameters()
+    long long grad_elems = 0;
+    float *ones = nullptr, *zeros = nullptr; // conv_cout_pad(widest concat buffer) of each
+    void *ws = nullptr;                      // the backward workspace, grown on demand
+    size_t ws_bytes = 0;
+    std::vector<void *> allocs;
+};
+
+void wsc_irn_grad_destroy(wsc_irn_grad *g) {
+    if (!g) return;
+    if (g->ctx) (void)hipStreamSynchronize(g->ctx->stream);
+    for (void *p : g->allocs) (void)hipFree(p);
+    if (g->ws) (void)hipFree(g->ws);
+    delete g;
+}
+
+int wsc_irn_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_irn_grad **out) {
+    WSC_CHECK(ctx && net && weights && out && n_weights > 0, WSC_ERR_INVALID, "wsc_irn_grad_create: null argument");
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
+              "wsc_irn_grad_create: the network is not an IRNet EdgeDisplacement net");
+    WSC_HIP(hipSetDevice(ctx->device));
+    Dict d;
+    WSC_TRY(descs_to_dict(weights, n_weights, &d));
+    wsc_irn_grad *g = new wsc_irn_grad();
+    g->ctx = ctx;
+    g->net = net;
+    g->heads.resize(net->heads.size());
+    auto up = [&](const std::vector<float> &v, float **dst) -> int {
+        void *p = nullptr;
+        WSC_HIP(hipMalloc(&p, v.size() * sizeof(float)));
+        g->allocs.push_back(p);
+        WSC_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+        *dst = (float *)p;
+        return WSC_OK;
+    };
+    // `<name>` as torch has it, [Cout][Cin][1][1] (vec: [Cout]); the net's own tensor has that shape
+    auto tensor = [&](const std::string &name, int Cout, int Cin, const HostTensor **t) -> int {
+        auto it = d.find(name);
+        WSC_CHECK(it != d.end() && it->second.data != nullptr, WSC_ERR_SHAPE, "layer '%s': missing", name.c_str());
+        const HostTensor &w = it->second;
+        const bool ok = Cin > 0 ? (w.ndim == 4 && w.shape[0] == Cout && w.shape[1] == Cin && w.shape[2] == 1 && w.shape[3] == 1)
+                                : (w.ndim == 1 && w.shape[0] == Cout);
+        WSC_CHECK(ok, WSC_ERR_SHAPE, "layer '%s': the net has it as [%d]%s, got ndim %d [%lld][%lld][%lld][%lld]", name.c_str(), Cout,
+                  Cin > 0 ? ("[" + std::to_string(Cin) + "][1][1]").c_str() : "", w.ndim, (long long)w.shape[0], (long long)w.shape[1],
+                  (long long)w.shape[2], (long long)w.shape[3]);
+        *t = &w;
+        return WSC_OK;
+    };
+    auto entry = [&](const std::string &name, int Cin, int Cout) {
+        wsc_grad_entry e = {};
+        std::strncpy(e.name, name.c_str(), sizeof(e.name) - 1);
+        e.kh = e.kw = Cin > 0 ? 1 : 0;
+        e.Cin = Cin; e.Cout = Cout;
+        e.w_off = Cin > 0 ? g->grad_elems : -1;
+        e.b_off = Cin > 0 ? -1 : g->grad_elems;
+        g->layout.push_back(e);
+        const long long at = g->grad_elems;
+        g->grad_elems += Cin > 0 ? (long long)Cin * Cout : Cout; // (no gaps: every float of the buffer is some parameter's)
+        return at;
+    };
+    int widest = 64;
+    // the rotated kernel of a 1 x 1 layer [Cout][Cin] whose input has cin_pad >= Cin channels (zero rows beyond)
+    auto rot = [&](const HostTensor *w, int Cin, int cin_pad, int Cout, float **dst) -> int {
+        std::vector<float> hwio((size_t)cin_pad * Cout, 0.f), packed;
+        for (int co = 0; co < Cout; ++co)
+            for (int ci = 0; ci < Cin; ++ci) hwio[(size_t)ci * Cout + co] = w->data[(size_t)co * Cin + ci];
+        dgrad_pack(hwio.data(), 1, cin_pad, Cout, &packed);
+        widest = std::max(widest, conv_cout_pad(cin_pad));
+        return up(packed, dst);
+    };
+    auto add_head = [&](size_t j) -> int {
+        const IrnHead &h = net->heads[j];
+        const HostTensor *w, *ga, *be;
+        WSC_CHECK(h.conv.Cin % 64 == 0 && (h.src > 0 || (h.conv.stride == 1 && h.conv.Cout % 32 == 0)), WSC_ERR_INVALID,
+                  "internal: head '%s' (%d -> %d channels, stride %d) has no backward form", h.name.c_str(), h.conv.Cin, h.conv.Cout, h.conv.stride);
+        WSC_TRY(tensor(h.name + ".0.weight", h.conv.Cout, h.conv.Cin, &w));
+        WSC_TRY(tensor(h.name + ".1.weight", h.conv.Cout, 0, &ga));
+        WSC_TRY(tensor(h.name + ".1.bias", h.conv.Cout, 0, &be));
+        if (h.src < 0) WSC_TRY(rot(w, h.conv.Cin, h.conv.Cin, h.conv.Cout, &g->heads[j].w_rot));
+        g->heads[j].w_off = entry(h.name + ".0.weight", h.conv.Cin, h.conv.Cout);
+        g->heads[j].g_off = entry(h.name + ".1.weight", 0, h.conv.Cout);
+        g->heads[j].b_off = entry(h.name + ".1.bias", 0, h.conv.Cout);
+        return WSC_OK;
+    };
+    auto build = [&]() -> int {
+        // edge_layers: the heads of the edge concat, then the final edge conv; dp_layers: the other heads, then the final dp conv
+        for (size_t j = 0; j < net->heads.size(); ++j)
+            if (net->heads[j].dst == 0) WSC_TRY(add_head(j));
+        const HostTensor *w6, *b6, *w7;
+        WSC_TRY(tensor(net->edge_final + ".weight", 1, net->edge_in, &w6));
+        WSC_TRY(tensor(net->edge_final + ".bias", 1, 0, &b6));
+        WSC_TRY(rot(w6, net->edge_in, net->cats[0].channels, 1, &g->edge_rot));
+        g->edge_w_off = entry(net->edge_final + ".weight", net->edge_in, 1);
+        g->edge_b_off = entry(net->edge_final + ".bias", 0, 1);
+        for (size_t j = 0; j < net->heads.size(); ++j)
+            if (net->heads[j].dst != 0) WSC_TRY(add_head(j));
+        const int cd = net->cats.back().channels;
+        WSC_TRY(tensor(net->dp_final + ".weight", 2, cd, &w7));
+        WSC_TRY(rot(w7, cd, cd, 2, &g->dp_rot));
+        g->dp_w_off = entry(net->dp_final + ".weight", cd, 2);
+        WSC_TRY(up(std::vector<float>(widest, 1.f), &g->ones));
+        return up(std::vector<float>(widest, 0.f), &g->zeros);
+    };
+    const int st = build();
+    if (st != WSC_OK) {
+        wsc_irn_grad_destroy(g);
+        return st;
+    }
+    *out = g;
+    return WSC_OK;
+}
+
+int wsc_irn_grad_layout(const wsc_irn_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out) {
+    WSC_CHECK(g && n_out && grad_elems_out && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
+              "wsc_irn_grad_layout: null argument");
+    *n_out = (int)g->layout.size();
+    *grad_elems_out = g->grad_elems;
+    for (int i = 0; i < max_entries && i < (int)g->layout.size(); ++i) entries_out[i] = g->layout[i];
+    return WSC_OK;
+}
+
+int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const float *tape_dev, long long tape_elems, const float *dedge_dev,
+                          const float *ddp_dev, float *grad_dev, long long grad_elems) {
+    WSC_CHECK(ctx && g && tape_dev && dedge_dev && ddp_dev && grad_dev, WSC_ERR_INVALID, "wsc_net_backward_edge: null argument");
+    WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_backward_edge: N=%d S=%d", N, S);
+    // (the workspace is the object's: one stream uses it, the one wsc_irn_grad_destroy drains)
+    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_net_backward_edge: the context is not the one the wsc_irn_grad was created on");
+    WSC_CHECK(((uintptr_t)tape_dev & 255) == 0, WSC_ERR_INVALID, "wsc_net_backward_edge: the tape must start on a 256-byte line");
+    const wsc_net *net = g->net;
+    EdgeTapePlan tp;
+    WSC_TRY(edge_tape_plan(net, N, S, &tp));
+    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_backward_edge: a tape of %lld floats, the plan has %lld (wsc_net_edge_tape_plan)",
+              tape_elems, tp.elems);
+    WSC_CHECK(grad_elems == g->grad_elems, WSC_ERR_INVALID, "wsc_net_backward_edge: a gradient buffer of %lld floats, the layout has %lld",
+              grad_elems, g->grad_elems);
+    const EdgeGeom &eg = tp.g;
+    const int NC = (int)net->cats.size(), NH = (int)net->heads.size();
+    const long long Me = (long long)N * eg.He * eg.We, Md = (long long)N * eg.Hd * eg.Wd;
+    // every GEMM's plan and the workspace, before anything is launched
+    std::vector<WgradPlan> plans(NH);
+    WgradPlan plan_e, plan_d;
+    WSC_TRY(wgrad_plan(ctx, N, eg.He, eg.We, eg.cat_c[0], 2, 1, 1, 0, &plan_e)); // (two columns: column 1 is zeros, see below)
+    WSC_TRY(wgrad_plan(ctx, N, eg.Hd, eg.Wd, eg.cat_c[NC - 1], 2, 1, 1, 0, &plan_d));
+    long long dy_max = 0, dz_max = 32 * std::max(Me, Md), xs_max = 0, slab_max = std::max(plan_e.slab_elems, plan_d.slab_elems);
+    size_t gpart_max = 0;
+    int max_groups = 1;
+    for (int j = 0; j < NH; ++j) {
+        const IrnHead &h = net->heads[j];
+        const EdgeGeom::Head &hg = eg.heads[j];
+        WSC_TRY(wgrad_plan(ctx, N, hg.ho, hg.wo, h.conv.Cin, h.conv.Cout, 1, 1, 0, &plans[j]));
+        const long long M = (long long)N * hg.ho * hg.wo;
+        dy_max = std::max(dy_max, M * h.conv.Cout);
+        if (h.conv.stride > 1) xs_max = std::max(xs_max, M * h.conv.Cin);
+        slab_max = std::max(slab_max, plans[j].slab_elems);
+        gpart_max = std::max(gpart_max, group_norm_grad_partial_bytes(N, hg.ho, hg.wo, h.conv.Cout));
+        max_groups = std::max(max_groups, h.groups);
+    }
+    dz_max = std::max(dz_max, dy_max);
+    auto lines = [](long long elems) { return align_up((size_t)elems * sizeof(float), 256); };
+    size_t need = 2 * lines(dy_max > dz_max ? dy_max : dz_max) + lines(xs_max) + lines(slab_max) + lines(2 * std::max(Me, Md)) +
+                  lines(2 * eg.cat_c[0]) + lines(relu_bias_grad_blocks(Me)) + align_up(gpart_max, 256) +
+                  align_up(sizeof(double) * 2 * N * max_groups, 256);
+    for (int i = 0; i < NC; ++i) need += lines((long long)eg.cat_elems[i]);
+    WSC_HIP(hipSetDevice(ctx->device));
+    if (need > g->ws_bytes) {
+        if (g->ws) {
+            WSC_HIP(hipStreamSynchronize(ctx->stream));
+            WSC_HIP(hipFree(g->ws));
+            g->ws = nullptr;
+            g->ws_bytes = 0;
+        }
+        WSC_HIP(hipMalloc(&g->ws, need));
+        g->ws_bytes = need;
+    }
+    char *p = (char *)g->ws;
+    auto carve = [&](size_t bytes) { float *q = (float *)p; p += bytes; return q; };
+    float *dy = carve(lines(std::max(dy_max, dz_max))), *dz = carve(lines(std::max(dy_max, dz_max)));
+    float *xs = carve(lines(xs_max)), *slab = carve(lines(slab_max)), *two = carve(lines(2 * std::max(Me, Md)));
+    float *wtmp = carve(lines(2 * eg.cat_c[0])), *partial = carve(lines(relu_bias_grad_blocks(Me)));
+    void *gpart = carve(align_up(gpart_max, 256)), *ms = carve(align_up(sizeof(double) * 2 * N * max_groups, 256));
+    std::vector<float *> dcat(NC);
+    for (int i = 0; i < NC; ++i) dcat[i] = carve(lines((long long)eg.cat_elems[i]));
+    auto at = [&](int entry) { return tape_dev + tp.e[entry].offset; };
+
+    // the final edge conv (Cout = 1, bias): the GEMM takes two columns, d_edge and zeros, and column 0 of its result is dW; the
+    // padding channels of the edge concat have no entry in the layout
+    WSC_TRY(launch_copy_channels(ctx, dedge_dev, Me, 1, 2, two));
+    WSC_TRY(wgrad_launch(ctx, plan_e, at(tp.cat[0]), two, eg.He, eg.We, eg.cat_c[0], 2, 1, 1, slab, wtmp));
+    WSC_TRY(launch_copy_channels(ctx, wtmp, net->edge_in, 2, 1, grad_dev + g->edge_w_off));
+    WSC_TRY(launch_relu_bias_grad(ctx, nullptr, dedge_dev, Me, 1, 1.0f, nullptr, partial, grad_dev + g->edge_b_off));
+    WSC_TRY(launch_copy_channels(ctx, dedge_dev, Me, 1, dgrad_cz(1), dz));
+    WSC_TRY(dgrad_launch(ctx, dz, g->edge_rot, g->ones, g->zeros, N, eg.He, eg.We, eg.cat_c[0], 1, 1, 1, nullptr, dcat[0]));
+    // the final displacement conv (Cout = 2): dp_out's gradient comes channel-major
+    WSC_TRY(launch_dp_to_nhwc(ctx, ddp_dev, N, eg.Hd * eg.Wd, dgrad_cz(2), dz));
+    WSC_TRY(launch_copy_channels(ctx, dz, Md, dgrad_cz(2), 2, two));
+    WSC_TRY(wgrad_launch(ctx, plan_d, at(tp.cat[NC - 1]), two, eg.Hd, eg.Wd, eg.cat_c[NC - 1], 2, 1, 1, slab, grad_dev + g->dp_w_off));
+    WSC_TRY(dgrad_launch(ctx, dz, g->dp_rot, g->ones, g->zeros, N, eg.Hd, eg.Wd, eg.cat_c[NC - 1], 2, 1, 1, nullptr, dcat[NC - 1]));
+    // the heads, last first: a concat buffer's reader ran after all of its writers, so its gradient is whole when they get here
+    for (int j = NH - 1; j >= 0; --j) {
+        const IrnHead &h = net->heads[j];
+        const EdgeGeom::Head &hg = eg.heads[j];
+        const IrnGradHead &gh = g->heads[j];
+        const int di = h.dst, C = h.conv.Cout, Cin = h.conv.Cin;
+        WSC_TRY(launch_relu_upsample_grad(ctx, dcat[di], at(tp.cat[di]), N, hg.ho, hg.wo, C, h.up, eg.cat_h[di], eg.cat_w[di], eg.cat_c[di], h.coff,
+                                          dy));
+        WSC_TRY(launch_group_norm_grad(ctx, at(tp.z[j]), at(tp.stats[j]), h.gamma, dy, N, hg.ho, hg.wo, C, h.groups, gpart, ms, dz,
+                                       grad_dev + gh.g_off, grad_dev + gh.b_off));
+        const int k = h.src > 0 ? h.src - 1 : -h.src - 1;
+        const float *x = at(h.src > 0 ? tp.tap[k] : tp.cat[k]);
+        if (h.conv.stride > 1) { // the pixels the strided 1 x 1 conv read, as a dense operand
+            WSC_TRY(launch_strided_rows_f32(ctx, x, N, hg.sh, hg.sw, Cin, h.conv.stride, hg.ho, hg.wo, xs));
+            x = xs;
+        }
+        WSC_TRY(wgrad_launch(ctx, plans[j], x, dz, hg.ho, hg.wo, Cin, C, 1, 1, slab, grad_dev + gh.w_off));
+        // (stage taps are detached in the reference: no data gradient)
+        if (h.src < 0) WSC_TRY(dgrad_launch(ctx, dz, gh.w_rot, g->ones, g->zeros, N, hg.ho, hg.wo, Cin, C, 1, 1, nullptr, dcat[k]));
+    }
+    return WSC_OK;
 }
 
 // ---- the update half of the training step: Model.optimize() (model.py:379-404) on the layout of wsc_seg_grad_layout ----------------

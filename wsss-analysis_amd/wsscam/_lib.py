@@ -135,6 +135,14 @@ _SIGNATURES = {
     "wsc_net_edge_size": (_i, [_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "wsc_net_forward_edge_raw": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "wsc_irn_aff_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "wsc_net_edge_tape_plan": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
+    "wsc_net_forward_edge_tape": (_i, [_vp, _vp, _vp, _i, _i, _vp, ctypes.c_longlong, _vp, _vp]),
+    "wsc_irn_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
+    "wsc_irn_grad_destroy": (None, [_vp]),
+    "wsc_irn_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
+    "wsc_net_backward_edge": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong]),
+    "wsc_relu_upsample_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_group_norm_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp]),
     "wsc_rw_propagate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "wsc_rw_propagate_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp]),
     "wsc_conv2d_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
@@ -620,6 +628,29 @@ class Net:
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_forward_edge_raw(run.h, self.h, _ptr(x_dev), int(N), int(S), _ptr(edge_dev), _ptr(dp_dev)))
 
+    def edge_tape_plan(self, N, S):
+        """wsc_net_edge_tape_plan: ([{'name', 'Ho', 'Wo', 'C', 'offset'}], tape_elems) -- what the backward pass of the heads needs
+        of a forward pass of N samples of S x S: "x<k>" stage taps, "<head>.z", "<head>.stats" ([N][1][1][2 G] {mean, rstd}
+        pairs), "cat<i>" concat buffers, float32 at `offset` floats of one buffer of tape_elems floats."""
+        n, elems = _i(), ctypes.c_longlong()
+        check(self.ctx._lib.wsc_net_edge_tape_plan(self.ctx.h, self.h, int(N), int(S), None, 0, ctypes.byref(n), ctypes.byref(elems)))
+        ent = (TapeEntry * n.value)()
+        check(self.ctx._lib.wsc_net_edge_tape_plan(self.ctx.h, self.h, int(N), int(S), ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
+        return [{"name": e.name.decode(), "Ho": e.Ho, "Wo": e.Wo, "C": e.C, "offset": e.offset} for e in ent], elems.value
+
+    def forward_edge_tape(self, x_dev, N, S, tape_dev, tape_elems, edge_dev, dp_dev, ctx=None):
+        """wsc_net_forward_edge_tape: forward_edge_raw (the same bits) that also fills tape_dev (float32, tape_elems of them)."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_forward_edge_tape(run.h, self.h, _ptr(x_dev), int(N), int(S), _ptr(tape_dev), int(tape_elems),
+                                                      _ptr(edge_dev), _ptr(dp_dev)))
+
+    def backward_edge(self, grad, N, S, tape_dev, tape_elems, dedge_dev, ddp_dev, grad_dev, grad_elems=None, ctx=None):
+        """wsc_net_backward_edge through `grad`, the IrnGrad of this net: dedge_dev [N][He][We], ddp_dev [N][2][Hd][Wd] -> every
+        element of grad_dev (grad.grad_elems floats in grad.layout)."""
+        if grad.net is not self:
+            raise ValueError("backward_edge: the IrnGrad was created for another net")
+        grad.backward(N, S, tape_dev, tape_elems, dedge_dev, ddp_dev, grad_dev, grad_elems=grad_elems, ctx=ctx)
+
     def seg_size_hw(self, H, W):
         """The fc8 map size of an ARCH_DEEPLAB_* net for an H x W input (41 x 41 at 321 x 321)."""
         h, w = _i(), _i()
@@ -742,6 +773,63 @@ class SegGrad:
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_seg_load_params(run.h, (net or self.net).h, self.h, _ptr(param_dev),
                                                     int(self.grad_elems if elems is None else elems)))
+
+
+class IrnGrad:
+    """wsc_irn_grad: what the backward pass of the heads of one ARCH_*_IRN net keeps (the data-gradient kernels, the workspace).
+    state_dict: the one the net was created from.  The net must outlive it.
+    layout: [{'name', 'shape', 'offset', 'size', 'conv'}] one per parameter in the order of trainable_parameters(), `shape`
+    torch's ((Cout, Cin, 1, 1) or (C,)); a conv weight lies as [Cin][Cout] at its offset."""
+
+    def __init__(self, net, state_dict):
+        self.ctx = net.ctx
+        self.net = net
+        descs, keep = make_tensor_descs(state_dict)
+        h = _vp()
+        check(self.ctx._lib.wsc_irn_grad_create(self.ctx.h, net.h, descs, len(descs), ctypes.byref(h)))
+        del keep
+        self.h = h
+        n, elems = _i(), ctypes.c_longlong()
+        check(self.ctx._lib.wsc_irn_grad_layout(h, None, 0, ctypes.byref(n), ctypes.byref(elems)))
+        ent = (GradEntry * n.value)()
+        check(self.ctx._lib.wsc_irn_grad_layout(h, ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
+        self.layout = []
+        for e in ent:
+            conv = e.kh == 1
+            self.layout.append({"name": e.name.decode(), "conv": conv, "shape": (e.Cout, e.Cin, 1, 1) if conv else (e.Cout,),
+                                "offset": e.w_off if conv else e.b_off, "size": e.Cin * e.Cout if conv else e.Cout})
+        self.grad_elems = elems.value
+
+    def close(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx._lib.wsc_irn_grad_destroy(self.h)  # (drains the stream)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def backward(self, N, S, tape_dev, tape_elems, dedge_dev, ddp_dev, grad_dev, grad_elems=None, ctx=None):
+        """wsc_net_backward_edge on the net's own context (the workspace belongs to its stream; `ctx`: another one is an error)."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_backward_edge(run.h, self.h, int(N), int(S), _ptr(tape_dev), int(tape_elems), _ptr(dedge_dev),
+                                                  _ptr(ddp_dev), _ptr(grad_dev), int(self.grad_elems if grad_elems is None else grad_elems)))
+
+
+def relu_upsample_grad_nhwc(ctx, dcat_dev, cat_dev, N, H, W, C, up, Hd, Wd, Ctot, coff, dy_dev):
+    """wsc_relu_upsample_grad_nhwc: dy_dev [N][H][W][C] from dcat_dev and the concat values cat_dev, both [N][Hd][Wd][Ctot]."""
+    check(ctx._lib.wsc_relu_upsample_grad_nhwc(ctx.h, _ptr(dcat_dev), _ptr(cat_dev), int(N), int(H), int(W), int(C), int(up), int(Hd), int(Wd),
+                                               int(Ctot), int(coff), _ptr(dy_dev)))
+
+
+def group_norm_grad_nhwc(ctx, z_dev, dy_dev, N, H, W, C, gamma, G, eps, dz_dev, dgamma_dev, dbeta_dev):
+    """wsc_group_norm_grad_nhwc: dz_dev [N][H][W][C], dgamma_dev [C], dbeta_dev [C] of GroupNorm(G, C); gamma on the host."""
+    gamma = np.ascontiguousarray(gamma, dtype=np.float32)
+    assert gamma.shape == (C,)
+    check(ctx._lib.wsc_group_norm_grad_nhwc(ctx.h, _ptr(z_dev), _ptr(dy_dev), int(N), int(H), int(W), int(C), _ptr(gamma), int(G), float(eps),
+                                            _ptr(dz_dev), _ptr(dgamma_dev), _ptr(dbeta_dev)))
 
 
 def conv2d_wgrad_nhwc(ctx, x_dev, dy_dev, N, H, W, Cin, Cout, k, dil, splits, dw_dev, db_dev):

@@ -4,11 +4,16 @@
                    affinity datasets attach (GetAffinityLabelFromIndices, voc12/dataloader.py:115-131) and the reductions of
                    step/train_irn.py:114-125 in one device call (wsc_irn_aff_loss; the formulas, the tie rules and the double
                    arithmetic: include/wsscam.h), with d total / d edge_out and d total / d dp_out.  loss_step chains it behind
-                   EdgeDisplacement.forward_train_dev (Net.forward in training mode).
+                   EdgeDisplacement.forward_train_dev (Net.forward in training mode); grad_step adds the backward pass of the
+                   heads (EdgeDisplacement.backward_dev, wsc_net_backward_edge) on a kept tape: total_loss.backward().
+    EdgeTape       what a forward pass keeps for that backward pass (one float32 device buffer and its plan)
+    IrnGrads       the gradient of every trainable parameter on the device: a flat buffer, its layout, to_state_dict() in
+                   torch's shapes, and `groups`, the two name lists of trainable_parameters() (train_irn's lr and 10 lr groups)
     reduce_label   the IR label at the resolution of the head outputs (voc12/dataloader.py:317)
 
-The backward pass of the heads (GroupNorm, 1x1 conv, bilinear upsample), PolyOptimizer, the affinity datasets' augmentation and
-the closing dp_mean pass are not here."""
+Every backbone stage is detached in Net.forward, so the gradient of the heads is the whole gradient of a step.  PolyOptimizer and
+the on-device update / repack of the head weights, the affinity datasets' augmentation and the closing dp_mean pass are not
+here."""
 import numpy as np
 
 from . import _lib
@@ -23,6 +28,68 @@ def reduce_label(label):
     if label.ndim != 2:
         raise ValueError("reduce_label: label has shape %r, expected (H, W)" % (label.shape,))
     return np.ascontiguousarray(imutils.pil_rescale(label.astype(np.uint8), 0.25, 0))
+
+
+class EdgeTape:
+    """The tape of EdgeDisplacement.forward_train_dev(x, keep=True): `maps` one float32 DeviceMaps of `elems` floats, `entries`
+    the plan of Net.edge_tape_plan for N samples of S x S.  entry(name) downloads one tensor ([N][Ho][Wo][C]); free() / a
+    context manager releases the buffer."""
+
+    def __init__(self, maps, entries, N, S):
+        self.maps, self.entries, self.N, self.S = maps, entries, int(N), int(S)
+        self.elems = maps.shape[0]
+
+    def entry(self, name):
+        e = next(e for e in self.entries if e["name"] == name)
+        return self.maps.ctx.to_host(self.maps.buf, (self.N, e["Ho"], e["Wo"], e["C"]), np.float32, offset_bytes=4 * e["offset"])
+
+    def free(self):
+        self.maps.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+class IrnGrads:
+    """The gradient of every trainable parameter of an EdgeDisplacement net, on the device: `maps` one float32 DeviceMaps and
+    `layout`, _lib.IrnGrad.layout ([{'name', 'shape', 'offset', 'size', 'conv'}] in the order of trainable_parameters(); a conv
+    weight lies as [Cin][Cout] at its offset).  ptr(name) is a parameter's device address; to_state_dict() downloads everything
+    once -> {name: ndarray} in torch's shapes; groups = (edge names, dp names): train_irn.py:60-65 gives the first lr, the second
+    10 lr.  free() / a context manager releases the buffer."""
+
+    def __init__(self, maps, layout):
+        self.maps = maps
+        self.layout = layout
+        self.groups = ([e["name"] for e in layout if e["name"].startswith("fc_edge")],
+                       [e["name"] for e in layout if not e["name"].startswith("fc_edge")])
+
+    def ptr(self, name):
+        return self.maps.ptr + 4 * next(e for e in self.layout if e["name"] == name)["offset"]
+
+    def to_state_dict(self):
+        flat = self.maps.to_host()
+        out = {}
+        for e in self.layout:
+            v = flat[e["offset"]:e["offset"] + e["size"]]
+            if e["conv"]:
+                cout, cin = e["shape"][:2]
+                v = v.reshape(cin, cout).T.reshape(e["shape"])
+            out[e["name"]] = np.ascontiguousarray(v)
+        return out
+
+    def free(self):
+        self.maps.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
 
 
 class AffinityLoss:
@@ -91,19 +158,31 @@ class AffinityLoss:
             for m in held:
                 m.free()
 
-    def loss_step(self, net, x, label, want_grad=True):
+    def loss_step(self, net, x, label, want_grad=True, keep=False):
         """One training step up to the gradient of the head outputs: net.forward_train_dev(x) (an EdgeDisplacement wrapper; x
         (B, 3, S, S)), then this loss on its outputs -> (losses, grad_edge, grad_dp, edge_out, dp_out), the last four DeviceMaps
-        the caller frees (the gradients None when want_grad is false).  `net` must live on this loss's context."""
+        the caller frees (the gradients None when want_grad is false); keep=True: the forward pass keeps its tape (the same
+        launches and bits) and the EdgeTape comes sixth.  `net` must live on this loss's context."""
         if net.ctx is not self.ctx:
             raise ValueError("AffinityLoss.loss_step: the network lives on another context than the loss")
-        edge, dp = net.forward_train_dev(x)
+        outs = net.forward_train_dev(x, keep=True) if keep else net.forward_train_dev(x)
+        edge, dp = outs[0], outs[1]
         try:
             if edge.shape[1:] != dp.shape[2:]:
                 raise ValueError("AffinityLoss.loss_step: edge_out is %r and dp_out %r: the loss needs one resolution" % (edge.shape, dp.shape))
             losses, g_edge, g_dp = self(edge, dp, label, want_grad=want_grad)
         except Exception:
-            edge.free()
-            dp.free()
+            for m in outs:
+                m.free()
             raise
-        return losses, g_edge, g_dp, edge, dp
+        return (losses, g_edge, g_dp) + tuple(outs)
+
+    def grad_step(self, net, x, label):
+        """One training step up to the gradient of every trainable parameter: loss_step on a kept tape, then net.backward_dev
+        -> (losses, IrnGrads); the caller frees the IrnGrads.  Everything else the step allocated is freed on every path."""
+        losses, g_edge, g_dp, edge, dp, tape = self.loss_step(net, x, label, keep=True)
+        try:
+            return losses, net.backward_dev(tape, g_edge, g_dp)
+        finally:
+            for m in (g_edge, g_dp, edge, dp, tape):
+                m.free()

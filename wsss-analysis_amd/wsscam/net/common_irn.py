@@ -15,6 +15,7 @@ class EdgeDisplacementBase(DeviceCAMBase):
         super().__init__(num_classes, precision)
         self.crop_size = crop_size
         self.stride = stride
+        self._irn_grad = None  # the _lib.IrnGrad of the net (irn_grad())
 
     def forward_batch(self, x):
         """x: numpy/torch float32 (B,2,3,h,w) -> (edge (B,1,fh,fw), dp (B,2,fh,fw)) numpy."""
@@ -66,11 +67,13 @@ class EdgeDisplacementBase(DeviceCAMBase):
             net.forward_edge(st["dev"], B, S, fh, fw, edge_dev, dp_dev, ctx=ctx)
         return edge_dev, dp_dev, (B, fh, fw)
 
-    def forward_train_dev(self, x):
+    def forward_train_dev(self, x, keep=False):
         """Net.forward in training mode (resnet50_irn.py:110-133, what AffinityDisplacementLoss.forward calls at :200), outputs
         left in HBM: x float32 (N,3,S,S), a host array / tensor or a secdsrg.DeviceMaps of the model's context (read in place)
         -> (edge_out DeviceMaps (N,He,We), dp_out DeviceMaps (N,2,Hd,Wd)): plain samples, no flip pairing, no crop, no mean shift
-        (MeanShift is the identity while training), no sigmoid."""
+        (MeanShift is the identity while training), no sigmoid.  keep=True: (edge_out, dp_out, tape) -- the same launches and
+        bits, and the tape backward_dev needs (an irn_train.EdgeTape; the caller frees it)."""
+        from ..irn_train import EdgeTape
         from ..secdsrg import DeviceMaps
 
         net = self._ensure_net()
@@ -84,7 +87,7 @@ class EdgeDisplacementBase(DeviceCAMBase):
         else:
             xn = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
             xd = mine = DeviceMaps.from_host(ctx, xn, dtype=np.float32)
-        edge = dp = None
+        edge = dp = tape = None
         try:
             if len(xd.shape) != 4 or xd.shape[1] != 3 or xd.shape[2] != xd.shape[3] or 0 in xd.shape:
                 raise ValueError("forward_train_dev: x has shape %r, expected (N, 3, S, S)" % (xd.shape,))
@@ -92,16 +95,61 @@ class EdgeDisplacementBase(DeviceCAMBase):
             (He, We), (Hd, Wd) = net.edge_size(S)
             edge = DeviceMaps(ctx, (N, He, We), np.float32)
             dp = DeviceMaps(ctx, (N, 2, Hd, Wd), np.float32)
-            net.forward_edge_raw(xd.ptr, N, S, edge.ptr, dp.ptr)
-            return edge, dp
+            if not keep:
+                net.forward_edge_raw(xd.ptr, N, S, edge.ptr, dp.ptr)
+                return edge, dp
+            entries, elems = net.edge_tape_plan(N, S)
+            tape = EdgeTape(DeviceMaps(ctx, (elems,), np.float32), entries, N, S)
+            net.forward_edge_tape(xd.ptr, N, S, tape.maps.ptr, elems, edge.ptr, dp.ptr)
+            return edge, dp, tape
         except Exception:
-            for m in (edge, dp):
+            for m in (edge, dp, tape):
                 if m is not None:
                     m.free()
             raise
         finally:
             if mine is not None:
                 mine.free()
+
+    def _release_net(self):
+        grad = getattr(self, "_irn_grad", None)
+        if grad is not None:  # (it holds kernels packed from the net's weights: it goes first)
+            grad.close()
+            self._irn_grad = None
+        super()._release_net()
+
+    def irn_grad(self):
+        """The _lib.IrnGrad of the model's net (created on first use, released with the net)."""
+        net = self._ensure_net()
+        if getattr(self, "_irn_grad", None) is None:
+            self._irn_grad = _lib.IrnGrad(net, self._extra_tensors(self._sd))
+        return self._irn_grad
+
+    def backward_dev(self, tape, grad_edge, grad_dp):
+        """total_loss.backward() through the heads (train_irn.py:127; the backbone stages are detached): tape of
+        forward_train_dev(x, keep=True), grad_edge (N,He,We) or (N,1,He,We) and grad_dp (N,2,Hd,Wd) float32 DeviceMaps of the
+        model's context (what AffinityLoss hands out), read in place -> irn_train.IrnGrads (the caller frees it)."""
+        from ..irn_train import EdgeTape, IrnGrads
+        from ..secdsrg import DeviceMaps
+
+        net = self._ensure_net()
+        ctx = self._ctx
+        if not isinstance(tape, EdgeTape) or tape.maps.ptr is None or tape.maps.ctx is not ctx:
+            raise ValueError("backward_dev: tape is no live EdgeTape of the model's context")
+        (He, We), (Hd, Wd) = net.edge_size(tape.S)
+        for name, m, shapes in (("grad_edge", grad_edge, ((tape.N, He, We), (tape.N, 1, He, We))), ("grad_dp", grad_dp, ((tape.N, 2, Hd, Wd),))):
+            if not isinstance(m, DeviceMaps) or m.dtype != np.float32 or m.ctx is not ctx or m.ptr is None:
+                raise ValueError("backward_dev: %s is no live float32 DeviceMaps of the model's context" % name)
+            if tuple(m.shape) not in shapes:
+                raise ValueError("backward_dev: %s has shape %r, expected %r" % (name, tuple(m.shape), shapes[0]))
+        grad = self.irn_grad()
+        out = DeviceMaps(ctx, (grad.grad_elems,), np.float32)
+        try:
+            net.backward_edge(grad, tape.N, tape.S, tape.maps.ptr, tape.elems, grad_edge.ptr, grad_dp.ptr, out.ptr)
+        except Exception:
+            out.free()
+            raise
+        return IrnGrads(out, grad.layout)
 
     def forward(self, x):
         is_torch = hasattr(x, "detach")
