@@ -866,6 +866,47 @@ int wsc_relu_upsample_grad_nhwc(wsc_ctx *ctx, const float *dcat_dev, const float
 int wsc_group_norm_grad_nhwc(wsc_ctx *ctx, const float *z_dev, const float *dy_dev, int N, int H, int W, int C, const float *gamma_host, int G,
                              float eps, float *dz_dev, float *dgamma_dev, float *dbeta_dev);
 
+/* ---- the update half of an IRNet training step and the closing dp_mean pass (step/train_irn.py:86-90, 127-129, 148-164) ---------
+ * Parameters, gradient and momentum are each ONE fp32 device buffer of grad_elems floats in the layout of wsc_irn_grad_layout,
+ * element-for-element parallel.  train_irn.py:86-90 builds PolyOptimizer with two groups: param_groups[0] (edge_layers: every
+ * `fc_edge*` entry, the layout's leading ones) at lr, param_groups[1] (dp_layers: the rest) at 10 lr, one weight decay.
+ *
+ * wsc_irn_sgd_step: optimizer.step() of lines 127-129, torch.optim.SGD with dampening 0 and no Nesterov, per element
+ *     g = grad + weight_decay p       (every parameter: conv weights, GroupNorm weight AND bias, the edge conv's bias)
+ *     m = sgd_momentum m + g          (a momentum buffer that starts at +0.0 gives torch's first step, m = g)
+ *     p = p - lr_group m              lr_group = lr_edge before the first dp entry's offset, lr_dp from there on
+ *   every product and sum rounded to fp32 on its own (no fused multiply-add), the same roundings in the 16-byte form and in the
+ *   scalar form an unaligned buffer takes.  The poly schedule lr0 (1 - step / max_step)^power is the caller's (evaluated in
+ *   double on the host and rounded to float, as torch does for fp32 tensors).  One launch, asynchronous on the ctx stream;
+ *   grad_dev is only read.  WSC_ERR_INVALID before any launch: ctx is not the context of `g`, elems is not the layout's
+ *   grad_elems, a null pointer, a scalar that is not finite.
+ *
+ * wsc_net_irn_load_params: the counterpart of wsc_net_seg_load_params.  Rewrites, in place and without a host copy, everything
+ * derived from the head parameters, from the floats of param_dev: (a) of every head the packed conv rows in the kernel's K order
+ * for the net's precision with the epilogue scale (IEEE-half modes: the per-output-channel power-of-two scale from the channel's
+ * largest |w|; split modes: both parts; fp32 in WSC_PREC_F32) and its device GroupNorm weight / bias; (b) the final edge conv (its
+ * edge_in = 160 input channels inside a row padded to the edge concat's 192, the padding exact zeros, its bias) and the final
+ * displacement conv; (c) in the wsc_irn_grad the rotated fp32 data-gradient kernels of the heads that read a concat buffer and of
+ * the two final convs.  Afterwards the device bytes of both objects are what wsc_net_create and wsc_irn_grad_create make of the
+ * same floats.  mean_shift is not a parameter: wsc_net_set_mean_shift.  The call WRITES the net, with the ordering caveat of
+ * wsc_net_seg_load_params.  WSC_ERR_INVALID before any launch: a net that is no IRNet net, a `g` of another net, a foreign ctx,
+ * a wrong elems.  Asynchronous on the ctx stream, a handful of launches whatever the number of heads.
+ *
+ * wsc_channel_mean_nchw: out_dev[c] (double, 8-byte aligned) = mean over (n, h, w) of x_dev [N][C][H][W] (float32) in double,
+ * minus sub_host[c] (float, NULL: nothing) -- torch.mean(dp, dim=(0, 2, 3)) of train_irn.py:158 with MeanShift's eval-mode
+ * subtraction of running_mean.  Per-block partial sums in one fixed order, the last block of a channel to arrive (an integer
+ * ticket) adds them in block order: no floating-point atomic, two calls give the same bits.  C <= 1024.  Asynchronous.
+ *
+ * wsc_net_set_mean_shift / wsc_net_get_mean_shift: the two floats (mean_shift.running_mean, train_irn.py:164) that
+ * wsc_net_forward_edge subtracts from dp; host state of the net, read when a forward call is enqueued. */
+int wsc_irn_sgd_step(wsc_ctx *ctx, wsc_irn_grad *g, float *param_dev, const float *grad_dev, float *mom_dev, long long elems, float lr_edge,
+                     float lr_dp, float weight_decay, float sgd_momentum);
+int wsc_net_irn_load_params(wsc_ctx *ctx, wsc_net *net, wsc_irn_grad *g, const float *param_dev, long long elems);
+int wsc_channel_mean_nchw(wsc_ctx *ctx, const float *x_dev, int N, int C, int H, int W, const float *sub_host /* [C] or NULL */,
+                          double *out_dev /* [C] */);
+int wsc_net_set_mean_shift(wsc_net *net, const float m[2]);
+int wsc_net_get_mean_shift(const wsc_net *net, float m_out[2]);
+
 /* ---- 02_cues: the localization seeds SEC / DSRG train on (02_cues/utilities.py:183-278 get_localization_cues /
  * get_localization_cues_sec, 02_cues/adp_cues.py:304-339 update_cues; consumer 03a_sec-dsrg/model.py:238-246) ---- */
 

@@ -580,8 +580,10 @@ int sgd_apply_launch(wsc_ctx *ctx, float *param, float *accum, float *mom, long 
 // One RepackJob per layer in a device table built once per wsc_seg_grad: the caller fills the layer's fields, repack_plan adds the
 // layout, the split of the channel maxima and where the layer's blocks lie in each of the (at most four) launches of a repack.
 struct RepackJob {
-    long long w_off, b_off;          // floats into the parameter buffer
+    long long w_off, b_off;          // floats into the parameter buffer; b_off < 0: no bias, b1 = 0 (the IRNet heads)
     int k, Cin, Cout;                // Cin as in the HWIO tensor (3 for the first layer)
+    int Cin_pad;                     // 0, or the channels of the layer's INPUT where it is wider than the tensor (the final edge conv
+                                     // of IRNet: 160 in 192); the packed rows hold exact zeros for the channels past Cin
     int small;                       // CONV_FORM_SMALL2 (the first layer), else CONV_FORM_GENERIC
     int kstep, Kw, lo_at, nsteps;    // conv_k_layout; nsteps: the K-steps of one precision segment
     int rot_Kw;                      // k k dgrad_cz(Cout), the row of the rotated kernel; 0 without one
@@ -604,6 +606,27 @@ struct RepackPlan {
 };
 int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *plan);
 int repack_launch(wsc_ctx *ctx, const RepackPlan &plan, const float *param);
+
+// ---- irn_sgd.hip: the update half of an IRNet training step on the layout of wsc_irn_grad_layout, the vectors of its repack and
+// the per-channel mean of the closing dp_mean pass (the contract: its header) ---------------------------------------------------
+// g = grad + wd p; m = momentum m + g; p = p - lr m with lr = lr_a for the elements before `boundary`, lr_b from there on; every
+// product and sum one fp32 rounding; grad is only read
+int irn_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, long long boundary, float lr_a, float lr_b,
+                   float weight_decay, float momentum);
+// One run of floats of the parameter buffer that a repack copies as it is (GroupNorm weight / bias of a head)
+struct VecCopyJob {
+    long long off; // floats into the parameter buffer
+    int n, block0; // its length; the job's first block in the launch
+    float *dst;
+};
+constexpr int VEC_COPY_PER_BLOCK = 256;
+// (block0 filled by the caller: jobs in order, ceil(n / VEC_COPY_PER_BLOCK) blocks each)
+int vec_copy_launch(wsc_ctx *ctx, const VecCopyJob *jobs_dev, int n_jobs, int blocks, const float *param);
+// out[c] (device doubles) = mean over (n, p) of x[n][c][p] in double, minus sub_host[c] (floats, or null); the scratch (tickets,
+// partials, the uploaded sub) is one cached block of the ctx, handed back behind the launch
+constexpr int CHANNEL_MEAN_MAX_BLOCKS = 64; // per channel
+constexpr int CHANNEL_MEAN_MAX_C = 1024;
+int channel_mean_launch(wsc_ctx *ctx, const float *x, int N, int C, long long HW, const float *sub_host, double *out);
 
 // ---- seg_dropout.hip: the dropout sites behind fc6 / fc7 of the SEC / DSRG training graph (the contract: its header) -----------
 // WSC_ERR_INVALID unless 0 <= drop_prob < 1 (NaN included) and 0 <= step < 2^32; `fn` names the caller in the error text

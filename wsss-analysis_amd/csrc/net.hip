@@ -1920,7 +1920,11 @@ struct wsc_irn_grad {
     const wsc_net *net = nullptr;
     std::vector<IrnGradHead> heads; // one per net->heads
     long long edge_w_off = 0, edge_b_off = 0, dp_w_off = 0;
+    long long dp_start = 0; // the first float of the dp group (train_irn.py:86-90: 10 lr); the edge group lies before it
     float *edge_rot = nullptr, *dp_rot = nullptr;
+    RepackPlan repack;      // the jobs of wsc_net_irn_load_params, built by its first call
+    VecCopyJob *vec_jobs = nullptr;
+    int n_vec_jobs = 0, vec_blocks = 0;
     std::vector<wsc_grad_entry> layout; // one entry per parameter, in the order of trainable_parameters()
     long long grad_elems = 0;
     float *ones = nullptr, *zeros = nullptr; // conv_cout_pad(widest concat buffer) of each
@@ -2015,6 +2019,7 @@ int wsc_irn_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
         WSC_TRY(rot(w6, net->edge_in, net->cats[0].channels, 1, &g->edge_rot));
         g->edge_w_off = entry(net->edge_final + ".weight", net->edge_in, 1);
         g->edge_b_off = entry(net->edge_final + ".bias", 0, 1);
+        g->dp_start = g->grad_elems;
         for (size_t j = 0; j < net->heads.size(); ++j)
             if (net->heads[j].dst != 0) WSC_TRY(add_head(j));
         const int cd = net->cats.back().channels;
@@ -2138,6 +2143,115 @@ int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const flo
         // (stage taps are detached in the reference: no data gradient)
         if (h.src < 0) WSC_TRY(dgrad_launch(ctx, dz, gh.w_rot, g->ones, g->zeros, N, hg.ho, hg.wo, Cin, C, 1, 1, nullptr, dcat[k]));
     }
+    return WSC_OK;
+}
+
+// ---- the update half of an IRNet step (train_irn.py:86-90, 127-129) and the closing dp_mean pass (148-164); kernels: irn_sgd.hip ----
+int wsc_irn_sgd_step(wsc_ctx *ctx, wsc_irn_grad *g, float *param_dev, const float *grad_dev, float *mom_dev, long long elems, float lr_edge,
+                     float lr_dp, float weight_decay, float sgd_momentum) {
+    WSC_CHECK(ctx && g && param_dev && grad_dev && mom_dev, WSC_ERR_INVALID, "wsc_irn_sgd_step: null argument");
+    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_irn_sgd_step: the context is not the one the wsc_irn_grad was created on");
+    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "wsc_irn_sgd_step: buffers of %lld floats, the layout has %lld", elems, g->grad_elems);
+    WSC_CHECK(std::isfinite(lr_edge) && std::isfinite(lr_dp) && std::isfinite(weight_decay) && std::isfinite(sgd_momentum), WSC_ERR_INVALID,
+              "wsc_irn_sgd_step: lr_edge %g, lr_dp %g, weight_decay %g, sgd_momentum %g must be finite", (double)lr_edge, (double)lr_dp,
+              (double)weight_decay, (double)sgd_momentum);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return irn_sgd_launch(ctx, param_dev, grad_dev, mom_dev, elems, g->dp_start, lr_edge, lr_dp, weight_decay, sgd_momentum);
+}
+
+int wsc_net_irn_load_params(wsc_ctx *ctx, wsc_net *net, wsc_irn_grad *g, const float *param_dev, long long elems) {
+    WSC_CHECK(ctx && net && g && param_dev, WSC_ERR_INVALID, "wsc_net_irn_load_params: null argument");
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
+              "wsc_net_irn_load_params: the network is not an IRNet EdgeDisplacement net");
+    WSC_CHECK(g->net == net, WSC_ERR_INVALID, "wsc_net_irn_load_params: the wsc_irn_grad was created for another net");
+    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_net_irn_load_params: the context is not the one the wsc_irn_grad was created on");
+    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "wsc_net_irn_load_params: a buffer of %lld floats, the layout has %lld", elems,
+              g->grad_elems);
+    WSC_CHECK(g->heads.size() == net->heads.size(), WSC_ERR_INVALID, "internal: %d heads of the net, %d of the layout", (int)net->heads.size(),
+              (int)g->heads.size());
+    WSC_HIP(hipSetDevice(ctx->device));
+    if (!g->repack.jobs_dev) { // the job tables: once per wsc_irn_grad (the packed buffers of both objects never move)
+        std::vector<RepackJob> jobs;
+        std::vector<VecCopyJob> vecs;
+        int vec_blocks = 0;
+        // a 1 x 1 layer [Cin][Cout] at w_off; bias: b_off or -1; cin_pad: the channels of its input where wider
+        auto job = [&](const ConvW &c, long long w_off, long long b_off, int Cin, int cin_pad, float *w_rot) {
+            RepackJob J = RepackJob();
+            J.w_off = w_off; J.b_off = b_off;
+            J.k = 1; J.Cin = Cin; J.Cout = c.Cout; J.Cin_pad = cin_pad;
+            J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
+            J.w_rot = w_rot;
+            jobs.push_back(J);
+        };
+        auto vec = [&](long long off, int n, float *dst) {
+            VecCopyJob V;
+            V.off = off; V.n = n; V.block0 = vec_blocks; V.dst = dst;
+            vec_blocks += (n + VEC_COPY_PER_BLOCK - 1) / VEC_COPY_PER_BLOCK;
+            vecs.push_back(V);
+        };
+        for (size_t j = 0; j < net->heads.size(); ++j) {
+            const IrnHead &h = net->heads[j];
+            const IrnGradHead &gh = g->heads[j];
+            WSC_CHECK(h.conv.kh == 1 && h.conv.kw == 1 && h.conv.form == CONV_FORM_GENERIC && !h.conv.s2, WSC_ERR_INVALID,
+                      "internal: head '%s' is no 1 x 1 layer", h.name.c_str());
+            job(h.conv, gh.w_off, -1, h.conv.Cin, 0, gh.w_rot);
+            vec(gh.g_off, h.conv.Cout, h.gamma);
+            vec(gh.b_off, h.conv.Cout, h.beta);
+        }
+        WSC_CHECK(net->edge6.Cin == net->cats[0].channels && net->edge6.Cout == 1 && net->dp7b.Cin == net->cats.back().channels &&
+                      net->dp7b.Cout == 2,
+                  WSC_ERR_INVALID, "internal: the final convs are not the layout's");
+        job(net->edge6, g->edge_w_off, g->edge_b_off, net->edge_in, net->edge6.Cin, g->edge_rot);
+        job(net->dp7b, g->dp_w_off, -1, net->dp7b.Cin, 0, g->dp_rot);
+        RepackPlan plan;
+        WSC_TRY(repack_plan(jobs, net->prec, &plan));
+        void *jd = nullptr, *pm = nullptr, *vd = nullptr;
+        WSC_HIP(hipMalloc(&jd, jobs.size() * sizeof(RepackJob)));
+        g->allocs.push_back(jd);
+        WSC_HIP(hipMemcpy(jd, jobs.data(), jobs.size() * sizeof(RepackJob), hipMemcpyHostToDevice));
+        if (plan.pmax_elems > 0) {
+            WSC_HIP(hipMalloc(&pm, (size_t)plan.pmax_elems * sizeof(float)));
+            g->allocs.push_back(pm);
+        }
+        WSC_HIP(hipMalloc(&vd, vecs.size() * sizeof(VecCopyJob)));
+        g->allocs.push_back(vd);
+        WSC_HIP(hipMemcpy(vd, vecs.data(), vecs.size() * sizeof(VecCopyJob), hipMemcpyHostToDevice));
+        g->vec_jobs = (VecCopyJob *)vd;
+        g->n_vec_jobs = (int)vecs.size();
+        g->vec_blocks = vec_blocks;
+        plan.pmax = (float *)pm;
+        plan.jobs_dev = (RepackJob *)jd;
+        g->repack = plan;
+    }
+    WSC_TRY(repack_launch(ctx, g->repack, param_dev));
+    return vec_copy_launch(ctx, g->vec_jobs, g->n_vec_jobs, g->vec_blocks, param_dev);
+}
+
+int wsc_channel_mean_nchw(wsc_ctx *ctx, const float *x_dev, int N, int C, int H, int W, const float *sub_host, double *out_dev) {
+    WSC_CHECK(ctx && x_dev && out_dev, WSC_ERR_INVALID, "wsc_channel_mean_nchw: null argument");
+    WSC_CHECK(N > 0 && C > 0 && C <= CHANNEL_MEAN_MAX_C && H > 0 && W > 0, WSC_ERR_INVALID, "wsc_channel_mean_nchw: %d x %d x %d x %d (C <= %d)",
+              N, C, H, W, CHANNEL_MEAN_MAX_C);
+    WSC_CHECK(((uintptr_t)x_dev & 3) == 0 && ((uintptr_t)out_dev & 7) == 0, WSC_ERR_INVALID,
+              "wsc_channel_mean_nchw: x_dev must be 4-byte and out_dev 8-byte aligned");
+    WSC_HIP(hipSetDevice(ctx->device));
+    return channel_mean_launch(ctx, x_dev, N, C, (long long)H * W, sub_host, out_dev);
+}
+
+int wsc_net_set_mean_shift(wsc_net *net, const float m[2]) {
+    WSC_CHECK(net && m, WSC_ERR_INVALID, "wsc_net_set_mean_shift: null argument");
+    WSC_CHECK(!net->heads.empty(), WSC_ERR_INVALID, "wsc_net_set_mean_shift: the network is not an IRNet EdgeDisplacement net");
+    WSC_CHECK(std::isfinite(m[0]) && std::isfinite(m[1]), WSC_ERR_INVALID, "wsc_net_set_mean_shift: (%g, %g) is not finite", (double)m[0],
+              (double)m[1]);
+    net->mean_shift[0] = m[0];
+    net->mean_shift[1] = m[1];
+    return WSC_OK;
+}
+
+int wsc_net_get_mean_shift(const wsc_net *net, float m_out[2]) {
+    WSC_CHECK(net && m_out, WSC_ERR_INVALID, "wsc_net_get_mean_shift: null argument");
+    WSC_CHECK(!net->heads.empty(), WSC_ERR_INVALID, "wsc_net_get_mean_shift: the network is not an IRNet EdgeDisplacement net");
+    m_out[0] = net->mean_shift[0];
+    m_out[1] = net->mean_shift[1];
     return WSC_OK;
 }
 

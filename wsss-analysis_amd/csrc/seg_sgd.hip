@@ -17,6 +17,9 @@
 //                ranges into partial maxima the pack blocks finish (a maximum is exact in any order).  The rotated kernel of the
 //                data gradient keeps 32 output channels contiguous: a gather copy, one thread per output float.
 //                The first layer (Cin = 3 in a 4-channel slot, 27 weights per channel) has a small kernel of its own.
+//                The IRNet heads (wsc_net_irn_load_params) come through the same jobs at k = 1: a job without a bias (b_off < 0)
+//                gets b1 = 0, and one whose input is wider than its tensor (Cin_pad: the final edge conv, 160 in 192) packs
+//                zeros for the channels past Cin; a DeepLab job has neither, and its bits and launches are what they were.
 //                Four launches for the whole net, whatever its depth: each kernel finds its layer in a device table of per-layer
 //                jobs built once per wsc_seg_grad (a launch per layer and kernel was launch-bound: ~10 us each, 75 of them).
 #include "common.h"
@@ -230,7 +233,7 @@ __global__ __launch_bounds__(256) void repack_generic_kernel(const RepackJob *__
             }
             if (by == 0) {
                 J.s1[c] = inv;
-                J.b1[c] = param[J.b_off + c];
+                J.b1[c] = J.b_off >= 0 ? param[J.b_off + c] : 0.f;
             }
         }
         s_scale[tid] = scale;
@@ -243,7 +246,7 @@ __global__ __launch_bounds__(256) void repack_generic_kernel(const RepackJob *__
 #pragma unroll
         for (int i = 0; i < CK / 4; ++i) {
             const int row = (tid >> 6) + 4 * i, col = tid & 63;
-            tile[row][col] = co0 + col < Cout ? src[(long long)row * Cout + col] : 0.f;
+            tile[row][col] = co0 + col < Cout && cc * CK + row < Cin ? src[(long long)row * Cout + col] : 0.f; // (Cin_pad: zeros past Cin)
         }
         __syncthreads();
         for (int j = tid; j < 64 * G; j += 256) {
@@ -371,9 +374,12 @@ int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *pl
         RepackJob &J = jobs[i];
         WSC_CHECK(!J.small || (J.Cin <= 4 && J.k <= 4 && plan->small_job < 0), WSC_ERR_INVALID, "internal: repack of a small-Cin layer %d x %d x %d",
                   J.k, J.k, J.Cin); // (one such layer, the first)
-        const ConvKLayout lay = conv_k_layout(J.k, J.k, J.small ? 4 : J.Cin, J.small ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, prec);
-        WSC_CHECK(J.small || (J.Cin % lay.ck == 0 && (lay.ck == 32 || lay.ck == 64)), WSC_ERR_INVALID, "internal: repack of Cin=%d in chunks of %d",
-                  J.Cin, lay.ck);
+        const int cin_lay = J.Cin_pad ? J.Cin_pad : J.Cin; // the channels of the packed rows
+        WSC_CHECK(J.Cin_pad == 0 || (!J.small && J.k == 1 && J.Cin_pad >= J.Cin), WSC_ERR_INVALID,
+                  "internal: repack of %d x %d x %d into rows of %d channels", J.k, J.k, J.Cin, J.Cin_pad); // (a padded input: 1 x 1 layers)
+        const ConvKLayout lay = conv_k_layout(J.k, J.k, J.small ? 4 : cin_lay, J.small ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, prec);
+        WSC_CHECK(J.small || (cin_lay % lay.ck == 0 && (lay.ck == 32 || lay.ck == 64)), WSC_ERR_INVALID, "internal: repack of Cin=%d in chunks of %d",
+                  cin_lay, lay.ck);
         if (!J.small) plan->ck = lay.ck; // (the precision's: one value for every generic layer)
         J.kstep = lay.kstep; J.Kw = lay.Kw; J.lo_at = lay.lo_at; J.nsteps = lay.ksteps_base;
         J.rot_Kw = J.w_rot ? J.k * J.k * dgrad_cz(J.Cout) : 0;

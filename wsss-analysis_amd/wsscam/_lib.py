@@ -141,6 +141,11 @@ _SIGNATURES = {
     "wsc_irn_grad_destroy": (None, [_vp]),
     "wsc_irn_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_backward_edge": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong]),
+    "wsc_irn_sgd_step": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _f, _f, _f]),
+    "wsc_net_irn_load_params": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong]),
+    "wsc_channel_mean_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "wsc_net_set_mean_shift": (_i, [_vp, ctypes.POINTER(_f)]),
+    "wsc_net_get_mean_shift": (_i, [_vp, ctypes.POINTER(_f)]),
     "wsc_relu_upsample_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "wsc_group_norm_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp]),
     "wsc_rw_propagate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp]),
@@ -628,6 +633,15 @@ class Net:
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_forward_edge_raw(run.h, self.h, _ptr(x_dev), int(N), int(S), _ptr(edge_dev), _ptr(dp_dev)))
 
+    def set_mean_shift(self, m):
+        """wsc_net_set_mean_shift: the two floats (mean_shift.running_mean) forward_edge subtracts from dp."""
+        check(self.ctx._lib.wsc_net_set_mean_shift(self.h, (_f * 2)(float(m[0]), float(m[1]))))
+
+    def get_mean_shift(self):
+        m = (_f * 2)()
+        check(self.ctx._lib.wsc_net_get_mean_shift(self.h, m))
+        return np.array([m[0], m[1]], np.float32)
+
     def edge_tape_plan(self, N, S):
         """wsc_net_edge_tape_plan: ([{'name', 'Ho', 'Wo', 'C', 'offset'}], tape_elems) -- what the backward pass of the heads needs
         of a forward pass of N samples of S x S: "x<k>" stage taps, "<head>.z", "<head>.stats" ([N][1][1][2 G] {mean, rstd}
@@ -816,6 +830,49 @@ class IrnGrad:
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_backward_edge(run.h, self.h, int(N), int(S), _ptr(tape_dev), int(tape_elems), _ptr(dedge_dev),
                                                   _ptr(ddp_dev), _ptr(grad_dev), int(self.grad_elems if grad_elems is None else grad_elems)))
+
+
+    def flat_params(self, state_dict):
+        """The head tensors of a state dict ({name: array in torch's shape}; other keys are ignored) -> one float32 array of
+        grad_elems floats in `layout` order, conv weights transposed to [Cin][Cout]: the host form of what sgd_step and
+        load_params take, the inverse of irn_train.IrnGrads.to_state_dict."""
+        flat = np.empty((self.grad_elems,), np.float32)
+        for e in self.layout:
+            if e["name"] not in state_dict:
+                raise ValueError("IrnGrad.flat_params: the state dict has no %r" % e["name"])
+            v = state_dict[e["name"]]
+            v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+            if tuple(v.shape) != tuple(e["shape"]):
+                raise ValueError("IrnGrad.flat_params: %r is %r, the net has %r" % (e["name"], tuple(v.shape), tuple(e["shape"])))
+            if e["conv"]:
+                v = v.reshape(e["shape"][0], e["shape"][1]).T
+            flat[e["offset"]:e["offset"] + e["size"]] = v.reshape(-1)
+        return flat
+
+    def sgd_step(self, param_dev, grad_dev, mom_dev, lr_edge, lr_dp, weight_decay, sgd_momentum, elems=None, ctx=None):
+        """wsc_irn_sgd_step on three buffers of grad_elems floats in `layout`: g = grad + weight_decay p; m = sgd_momentum m + g;
+        p -= lr m with lr_edge on the `fc_edge*` entries and lr_dp on the rest, every product and sum one fp32 rounding."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_irn_sgd_step(run.h, self.h, _ptr(param_dev), _ptr(grad_dev), _ptr(mom_dev),
+                                             int(self.grad_elems if elems is None else elems), float(lr_edge), float(lr_dp),
+                                             float(weight_decay), float(sgd_momentum)))
+
+    def load_params(self, param_dev, elems=None, net=None, ctx=None):
+        """wsc_net_irn_load_params: the heads' packed weights and GroupNorm vectors, the two final convs and this object's
+        data-gradient kernels rewritten on the device from the flat parameter buffer.  The net must not be in use on another
+        stream."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_irn_load_params(run.h, (net or self.net).h, self.h, _ptr(param_dev),
+                                                    int(self.grad_elems if elems is None else elems)))
+
+
+def channel_mean_nchw(ctx, x_dev, N, C, H, W, out_dev, sub=None):
+    """wsc_channel_mean_nchw: out_dev[c] (float64) = mean over (n, h, w) of x_dev float32 [N][C][H][W], in double in one fixed
+    order, minus sub[c] (host floats, or None)."""
+    s = None if sub is None else np.ascontiguousarray(sub, dtype=np.float32)
+    if s is not None and s.shape != (int(C),):
+        raise ValueError("channel_mean_nchw: sub has shape %r, expected (%d,)" % (s.shape, C))
+    check(ctx._lib.wsc_channel_mean_nchw(ctx.h, _ptr(x_dev), int(N), int(C), int(H), int(W), _ptr(s), _ptr(out_dev)))
 
 
 def relu_upsample_grad_nhwc(ctx, dcat_dev, cat_dev, N, H, W, C, up, Hd, Wd, Ctot, coff, dy_dev):

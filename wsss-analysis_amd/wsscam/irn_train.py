@@ -11,13 +11,17 @@
                    torch's shapes, and `groups`, the two name lists of trainable_parameters() (train_irn's lr and 10 lr groups)
     reduce_label   the IR label at the resolution of the head outputs (voc12/dataloader.py:317)
 
-Every backbone stage is detached in Net.forward, so the gradient of the heads is the whole gradient of a step.  PolyOptimizer and
-the on-device update / repack of the head weights, the affinity datasets' augmentation and the closing dp_mean pass are not
-here."""
+    IrnTrainer     train_irn.run's loop end to end: grad_step, the PolyOptimizer update (misc.torchutils.PolyOptimizer,
+                   wsc_irn_sgd_step) and the repack of the head weights into the net (wsc_net_irn_load_params) per step, the
+                   closing dp_mean pass (fit_dp_mean, train_irn.py:148-164), and the trained state dict
+
+Every backbone stage is detached in Net.forward, so the gradient of the heads is the whole gradient of a step.  The affinity
+datasets' crop / rescale / flip, DataLoader shuffling and DataParallel are not here."""
 import numpy as np
 
 from . import _lib
 from .misc import imutils
+from .misc.torchutils import PolyOptimizer
 from .secdsrg import DeviceMaps
 
 
@@ -186,3 +190,145 @@ class AffinityLoss:
         finally:
             for m in (g_edge, g_dp, edge, dp, tape):
                 m.free()
+
+
+class IrnTrainer:
+    """One IRNet training step after another, and the closing pass: step/train_irn.py:86-90, 105-164 on the device.
+
+        IrnTrainer(model, path_index, lr, weight_decay, max_step, power=0.9, sgd_momentum=None, valid_below=21)
+          model         an EdgeDisplacement wrapper with its state dict loaded; the trainer trains ITS net in place
+          lr, weight_decay, max_step, power, sgd_momentum    PolyOptimizer's (misc.torchutils: power is upstream's `momentum`
+                        argument, the poly exponent; sgd_momentum None = the value of weight_decay, the upstream behaviour)
+    The parameters and the momentum are two resident float32 DeviceMaps of irn_grad().grad_elems floats in the layout of IrnGrads,
+    initialised from the model's state dict and zeros; a step never downloads them.
+
+    step(x, label) -> losses   AffinityLoss.grad_step, wsc_irn_sgd_step at the schedule's two rates, wsc_net_irn_load_params:
+                    afterwards the net computes with the updated heads.  Downloads the loss values and nothing else; everything
+                    it allocates is freed on every path.
+    global_step, lr             the optimiser's step count and the (edge, dp) rates of the NEXT step
+    params_host() / momentum_host()   {name: array in torch's shape}
+    fit_dp_mean(batches) -> float32 (2,)   the closing loop: per batch (x (N,3,S,S), plain samples) forward_train_dev, the
+                    per-channel mean of dp_out over (N, H, W) in double minus the net's current mean shift (eval-mode MeanShift
+                    subtracts running_mean) into slot i of a device array; ONE download of the [n_batches][2] doubles at the
+                    end, their mean in double rounded to float32, installed in the net (wsc_net_set_mean_shift)
+    state_dict()    the model's full state dict with the updated head tensors and mean_shift.running_mean; also refreshes the
+                    wrapper's own copy, so the trained model and a fresh one loaded from the dict behave identically
+    save(path) / IrnTrainer.load(path, model, path_index, ...)   np.save / np.load(...).item() of state_dict() with the momentum
+                    under "__momentum__" and the step count under "__step__"
+    close() / a context manager releases the two buffers (the model stays the caller's)"""
+
+    def __init__(self, model, path_index, lr, weight_decay, max_step, power=0.9, sgd_momentum=None, valid_below=21, ctx=None):
+        self.params = self.mom = None
+        self.model = model
+        self.ctx = model.ctx
+        if ctx is not None and ctx is not self.ctx:
+            raise ValueError("IrnTrainer: the model lives on another context")
+        self.loss = AffinityLoss(path_index, valid_below=valid_below, ctx=self.ctx)
+        self.grad = model.irn_grad()
+        self.opt = PolyOptimizer(self.grad, lr, weight_decay, max_step, momentum=power, sgd_momentum=sgd_momentum)
+        try:
+            flat = self.grad.flat_params(model._sd)
+            self.params = DeviceMaps.from_host(self.ctx, flat)
+            self.mom = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for name in ("params", "mom"):
+            buf = getattr(self, name, None)
+            if buf is not None:
+                buf.free()
+            setattr(self, name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def global_step(self):
+        return self.opt.global_step
+
+    @property
+    def lr(self):
+        return self.opt.lr_now()
+
+    def _live(self):
+        if self.params is None or self.model.irn_grad() is not self.grad:
+            raise ValueError("IrnTrainer: closed, or the model's net was rebuilt since the trainer was made")
+
+    def step(self, x, label):
+        self._live()
+        losses, grads = self.loss.grad_step(self.model, x, label)
+        try:
+            self.opt.step(self.params, grads.maps, self.mom)
+            self.grad.load_params(self.params.ptr)
+        finally:
+            grads.free()
+        return losses
+
+    def params_host(self):
+        return IrnGrads(self.params, self.grad.layout).to_state_dict()
+
+    def momentum_host(self):
+        return IrnGrads(self.mom, self.grad.layout).to_state_dict()
+
+    def fit_dp_mean(self, batches):
+        self._live()
+        batches = list(batches)
+        if not batches:
+            raise ValueError("IrnTrainer.fit_dp_mean: no batches")
+        net = self.model._ensure_net()
+        shift = net.get_mean_shift()
+        with DeviceMaps(self.ctx, (len(batches), 2), np.float64) as slots:
+            for i, x in enumerate(batches):
+                edge, dp = self.model.forward_train_dev(x)
+                with edge, dp:
+                    N, C, Hd, Wd = dp.shape
+                    _lib.channel_mean_nchw(self.ctx, dp.ptr, N, C, Hd, Wd, slots.ptr + 16 * i, sub=shift)
+            means = slots.to_host()  # the pass's one download
+        mean = (means.sum(axis=0) / len(batches)).astype(np.float32)
+        net.set_mean_shift(mean)
+        self.model._sd["mean_shift.running_mean"] = mean.copy()
+        return mean
+
+    def state_dict(self):
+        self._live()
+        sd = self.model._sd
+        sd.update(self.params_host())
+        sd["mean_shift.running_mean"] = self.model._ensure_net().get_mean_shift()
+        return {k: v.copy() for k, v in sd.items()}
+
+    def save(self, path):
+        d = self.state_dict()
+        d["__momentum__"] = self.momentum_host()
+        d["__step__"] = {"global_step": self.global_step}
+        with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
+            np.save(fh, d, allow_pickle=True)
+
+    @classmethod
+    def load(cls, path, model, path_index, lr, weight_decay, max_step, **kwargs):
+        d = np.load(path, encoding="latin1", allow_pickle=True).item()
+        model.load_state_dict({k: v for k, v in d.items() if not k.startswith("__")})
+        model.cuda()
+        tr = cls(model, path_index, lr, weight_decay, max_step, **kwargs)
+        try:
+            if "__momentum__" in d:
+                flat = tr.grad.flat_params(d["__momentum__"])  # (a slot has the parameters' shapes)
+                tr.mom.free()
+                tr.mom = None
+                tr.mom = DeviceMaps.from_host(tr.ctx, flat)
+            tr.opt.global_step = int(d.get("__step__", {}).get("global_step", 0))
+        except Exception:
+            tr.close()
+            raise
+        return tr

@@ -125,6 +125,26 @@ class EdgeDisplacementBase(DeviceCAMBase):
             self._irn_grad = _lib.IrnGrad(net, self._extra_tensors(self._sd))
         return self._irn_grad
 
+    def load_params_dev(self, flat):
+        """wsc_net_irn_load_params: the heads' packed weights and GroupNorm vectors, the two final convs and the data-gradient
+        kernels of the backward pass rewritten on the device from `flat`, float32 (grad_elems,) in the layout of IrnGrads -- a
+        DeviceMaps of the model's context (read in place), or a host array (uploaded once; irn_grad().flat_params(sd) makes one).
+        Afterwards the net has the bits of a model loaded with those head tensors.  The wrapper's own state dict is not touched
+        (irn_train.IrnTrainer.state_dict does both)."""
+        from ..secdsrg import DeviceMaps
+
+        g = self.irn_grad()
+        fd, mine = flat, False
+        if not isinstance(flat, DeviceMaps):
+            fd, mine = DeviceMaps.from_host(self._ctx, np.asarray(flat).reshape(-1), dtype=np.float32), True
+        try:
+            if fd.dtype != np.float32 or fd.shape != (g.grad_elems,) or fd.ctx is not self._ctx or fd.ptr is None:
+                raise ValueError("load_params_dev: %r %s must be a live float32 (%d,) of the model's context" % (fd.shape, fd.dtype, g.grad_elems))
+            g.load_params(fd.ptr)
+        finally:
+            if mine:
+                fd.free()
+
     def backward_dev(self, tape, grad_edge, grad_dp):
         """total_loss.backward() through the heads (train_irn.py:127; the backbone stages are detached): tape of
         forward_train_dev(x, keep=True), grad_edge (N,He,We) or (N,1,He,We) and grad_dp (N,2,Hd,Wd) float32 DeviceMaps of the
