@@ -667,6 +667,41 @@ int wsc_msf_input_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32
 int wsc_resize_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32_t *size_hw_host, const int64_t *offset_host,
                   int OH, int OW, uint8_t *out_dev);
 
+/* PIL's Image.resize for a ragged batch of uint8 images (csrc/irn_batch.hip): imutils.pil_resize(img, size, order) of upstream
+ * IRN -- `Image.fromarray(img).resize(size[::-1], Image.BICUBIC | Image.NEAREST)`, what imutils.random_scale / pil_rescale call
+ * (voc12/dataloader.py:169, 236, 280, 317 and the ADP / DeepGlobe twins).  order 3: Resample.c's two-pass bicubic with 22-bit
+ * integer coefficients and a uint8 intermediate; order 0: ImagingScaleAffine's nearest index (a running sum in double).  The
+ * coefficient and index tables are built on the host in PIL's order of operations; the kernels are integer arithmetic.  Equal to
+ * PIL 12 on every byte (tests/test_irn_batch_oracle.py pins the numpy restatement the kernels are tested against).
+ *   images_dev uint8: image b is the block [H_b][W_b][channels] at byte offset_host[b];  size_hw_host int32 [B][2];
+ *   out_dev uint8: result b is the block [OH_b][OW_b][channels] at byte out_offset_host[b];  out_hw_host int32 [B][2];
+ *   channels 1 or 3; order 3 or 0 (anything else: WSC_ERR_INVALID); B 1 .. 65535. */
+int wsc_pil_resize_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32_t *size_hw_host, const int64_t *offset_host,
+                      const int32_t *out_hw_host, const int64_t *out_offset_host, int channels, int order, uint8_t *out_dev);
+
+/* One IRNet training batch from decoded images and their IR labels (csrc/irn_batch.hip): the sample transform of
+ * VOC12AffinityDataset.__getitem__ (voc12/dataloader.py:270-321; adp/dataloader.py:270-321, deepglobe/dataloader.py:257-308), in
+ * the reference's order --
+ *   1. resize     stage 0: none (the sample must be scaled_h x scaled_w already); stage 1: imutils.random_scale's PIL rescale
+ *                 to scaled_h x scaled_w (:280; bicubic on the image, nearest on the label); stage 2: TorchvisionResize to
+ *                 scaled_h x scaled_w (:282-284; the float64 bilinear of wsc_msf_input_u8 on the image AND the label, the label
+ *                 truncated to uint8 as np.uint8 inside pil_resize does at :317 -- the vgg16 / m7 configuration)
+ *   2. normalise  (:286-287) (v - mean[c]) / std[c], one fp32 subtract and one fp32 divide; pre_div255: v / 255 first
+ *   3. flip       (:289-290) np.fliplr of the resized image and label where flip = 1
+ *   4. crop       (:292-296) an S x S container of 0.0 (image) / 255 (label);
+ *                 container[cont_top : cont_top + ch, cont_left : cont_left + cw] = img[img_top : img_top + ch, img_left : img_left + cw]
+ *   5. HWC -> CHW (:298), and imutils.pil_rescale(label, 0.25, 0) of the cropped label (:317): s = round-half-even(S / 4)
+ *   images_dev uint8: sample b's image [H_b][W_b][3] at byte image_offset_host[b]; labels_dev uint8: its label [H_b][W_b] at byte
+ *   label_offset_host[b]; size_hw_host int32 [B][2];
+ *   params_host int32 [B][9]: {scaled_h, scaled_w, flip, cont_top, cont_left, img_top, img_left, ch, cw};
+ *   x_dev float32 [B][3][S][S]; label_dev uint8 [B][S][S]; reduced_dev uint8 [B][s][s].
+ * WSC_ERR_INVALID, naming the sample and before any launch: a window that leaves the resized image or the container, stage 0 on a
+ * sample of another size, B outside 1 .. 65535.  The temporary (the horizontal pass's rows) is a cached block of the context. */
+int wsc_irn_train_batch(wsc_ctx *ctx, const uint8_t *images_dev, const uint8_t *labels_dev, int B, const int32_t *size_hw_host,
+                        const int64_t *image_offset_host, const int64_t *label_offset_host, const int32_t *params_host, int S,
+                        const float *mean3_host, const float *std3_host, int pre_div255, int stage, float *x_dev,
+                        uint8_t *label_dev, uint8_t *reduced_dev);
+
 /* F.interpolate(mode='bilinear', align_corners=False) on float32 [C][h][w] -> [C][H][W]
  * (make_cam.py:64-69; also resize_stack 02_cues/utilities.py:20-40 up to the
  * cv2/torch border convention). */

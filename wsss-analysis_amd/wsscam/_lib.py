@@ -196,6 +196,8 @@ _SIGNATURES = {
     "wsc_bilinear_resize": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
     "wsc_msf_input_u8": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "wsc_resize_u8": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "wsc_pil_resize_u8": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "wsc_irn_train_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "wsc_label_unary_from_cam": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     "wsc_ir_label_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "wsc_dsrg_seed_grow": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
@@ -1355,6 +1357,78 @@ def resize_u8(ctx, images_dev, sizes, offsets, out_hw, out_dev):
     off = np.ascontiguousarray(offsets, dtype=np.int64)
     check(ctx._lib.wsc_resize_u8(ctx.h, _ptr(images_dev), B, size_hw.ctypes.data, off.ctypes.data, int(out_hw[0]), int(out_hw[1]),
                                  _ptr(out_dev)))
+
+
+def _offset_table(name, offsets, B):
+    """B byte offsets -> C-contiguous int64 (B,); anything that is no whole number, negative or of another length is an error"""
+    off = np.asarray(offsets)
+    if off.shape != (B,) or off.dtype.kind not in "iu":
+        raise ValueError("%s: %r %s, expected %d integer byte offsets" % (name, off.shape, off.dtype, B))
+    if B and int(off.min()) < 0:
+        raise ValueError("%s: negative byte offset" % name)
+    return np.ascontiguousarray(off, dtype=np.int64)
+
+
+def _hw_table(name, sizes, B):
+    """B (height, width) pairs of whole numbers >= 1 -> C-contiguous int32 (B, 2)"""
+    t = np.asarray(sizes)
+    if t.dtype.kind not in "iu" or t.size != 2 * B:
+        raise ValueError("%s: %r %s, expected %d (height, width) pairs of integers" % (name, t.shape, t.dtype, B))
+    t = t.reshape(B, 2)
+    if B and (int(t.min()) < 1 or int(t.max()) > 32768):
+        raise ValueError("%s: a side outside 1 .. 32768" % name)
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def pil_resize_u8(ctx, images_dev, sizes, offsets, out_sizes, out_offsets, channels, order, out_dev):
+    """wsc_pil_resize_u8: PIL's Image.resize (order 3 bicubic, 0 nearest) of packed uint8 images ([H][W][channels] blocks at byte
+    `offsets`) -> uint8 blocks [OH][OW][channels] at byte `out_offsets` of out_dev.  Shapes and dtypes are checked here, before
+    any C call."""
+    B = len(sizes)
+    if not 1 <= B <= 65535:
+        raise ValueError("pil_resize_u8: %d images (1 .. 65535)" % B)
+    if channels not in (1, 3):
+        raise ValueError("pil_resize_u8: channels = %r (1 or 3)" % (channels,))
+    size_hw, out_hw = _hw_table("pil_resize_u8: sizes", sizes, B), _hw_table("pil_resize_u8: out_sizes", out_sizes, B)
+    off, out_off = _offset_table("pil_resize_u8: offsets", offsets, B), _offset_table("pil_resize_u8: out_offsets", out_offsets, B)
+    check(ctx._lib.wsc_pil_resize_u8(ctx.h, _ptr(images_dev), B, size_hw.ctypes.data, off.ctypes.data, out_hw.ctypes.data,
+                                     out_off.ctypes.data, int(channels), int(order), _ptr(out_dev)))
+
+
+IRN_BATCH_PARAMS = ("scaled_h", "scaled_w", "flip", "cont_top", "cont_left", "img_top", "img_left", "ch", "cw")
+IRN_STAGE_NONE, IRN_STAGE_PIL_RESCALE, IRN_STAGE_TV_RESIZE = 0, 1, 2
+
+
+def irn_reduced_size(S):
+    """the side of imutils.pil_rescale(label, 0.25, 0) of an S x S crop"""
+    return int(np.round(int(S) * 0.25))
+
+
+def irn_train_batch(ctx, images_dev, labels_dev, sizes, image_offsets, label_offsets, params, S, mean, std, pre_div255, stage, x_dev,
+                    label_dev, reduced_dev):
+    """wsc_irn_train_batch: packed decoded images ([H][W][3] at byte `image_offsets`) and IR labels ([H][W] at byte
+    `label_offsets`) -> x_dev float32 [B][3][S][S], label_dev uint8 [B][S][S], reduced_dev uint8 [B][s][s] (irn_reduced_size).
+    params: integer (B, 9) records in the order of IRN_BATCH_PARAMS.  Shapes and dtypes are checked here, before any C call; the
+    windows by the library."""
+    B = len(sizes)
+    if not 1 <= B <= 65535:
+        raise ValueError("irn_train_batch: %d samples (1 .. 65535)" % B)
+    size_hw = _hw_table("irn_train_batch: sizes", sizes, B)
+    ioff = _offset_table("irn_train_batch: image_offsets", image_offsets, B)
+    loff = _offset_table("irn_train_batch: label_offsets", label_offsets, B)
+    p = np.asarray(params)
+    if p.shape != (B, len(IRN_BATCH_PARAMS)) or p.dtype.kind not in "iu":
+        raise ValueError("irn_train_batch: params %r %s, expected integer (%d, %d)" % (p.shape, p.dtype, B, len(IRN_BATCH_PARAMS)))
+    p = np.ascontiguousarray(p, dtype=np.int32)
+    m, sd = np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32)
+    if m.shape != (3,) or sd.shape != (3,) or not np.isfinite(m).all() or not np.isfinite(sd).all() or (sd == 0).any():
+        raise ValueError("irn_train_batch: mean %r / std %r, expected three finite values each and no zero std" % (m.shape, sd.shape))
+    m, sd = np.ascontiguousarray(m), np.ascontiguousarray(sd)
+    if int(S) != S or not 2 <= int(S) <= 8192:
+        raise ValueError("irn_train_batch: S = %r (2 .. 8192)" % (S,))
+    check(ctx._lib.wsc_irn_train_batch(ctx.h, _ptr(images_dev), _ptr(labels_dev), B, size_hw.ctypes.data, ioff.ctypes.data,
+                                       loff.ctypes.data, p.ctypes.data, int(S), m.ctypes.data, sd.ctypes.data, int(bool(pre_div255)),
+                                       int(stage), _ptr(x_dev), _ptr(label_dev), _ptr(reduced_dev)))
 
 
 def label_unary_from_cam(ctx, highres_dev, B, K, N, thres, gt_prob, unary_dev, labels_dev=None):

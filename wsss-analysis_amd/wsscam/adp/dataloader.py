@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from ..voc12.dataloader import resize_bilinear_f64
+from ..voc12.dataloader import AffinityDatasetMixin, SegmentationDatasetBase, resize_bilinear_f64
 
 CAT_LIST = {
     "morph": ["E.M.S", "E.M.U", "E.M.O", "E.T.S", "E.T.U", "E.T.O", "E.P", "C.D.I", "C.D.R", "C.L", "H.E", "H.K",
@@ -138,3 +138,30 @@ class ADPImageDataset:
 
         name = self.img_name_list[idx]
         return {"name": name, "img": np.asarray(Image.open(get_img_path(name, self.dev_root, self.is_eval)).convert("RGB"))}
+
+
+class ADPSegmentationDataset(SegmentationDatasetBase):
+    """adp/dataloader.py:242-300: the transform of voc12.dataloader.SegmentationDatasetBase (decoded / draw / item) on the ADP
+    files and constants."""
+    normalize_cls = TorchvisionNormalize
+
+    def __init__(self, img_name_list_path, label_dir, crop_size, dev_root, htt_type, is_eval, outsize=None, rescale=None,
+                 norm_mode="int", hor_flip=False, crop_method="random"):
+        super().__init__(label_dir, crop_size, outsize, rescale, norm_mode, hor_flip, crop_method)
+        self.img_name_list = load_img_name_list(img_name_list_path)
+        self.dev_root, self.htt_type, self.is_eval = dev_root, htt_type, is_eval
+        missing = [n for n in self.img_name_list if not os.path.exists(get_img_path(str(n), dev_root, is_eval))]
+        if missing:  # (the reference asserts the same at :249-252)
+            raise FileNotFoundError("ADP images not found under %s: %s" % (dev_root, missing[:4]))
+
+    def image_path(self, name_str):
+        return get_img_path(name_str, self.dev_root, self.is_eval)
+
+
+class ADPAffinityDataset(AffinityDatasetMixin, ADPSegmentationDataset):
+    """adp/dataloader.py:302-321."""
+
+    def __init__(self, img_name_list_path, label_dir, crop_size, dev_root, htt_type, indices_from=None, indices_to=None,
+                 is_eval=False, rescale=None, norm_mode="int", hor_flip=False, crop_method=None, outsize=None):
+        super().__init__(img_name_list_path, label_dir, crop_size, dev_root, htt_type, is_eval, outsize, rescale, norm_mode,
+                         hor_flip, crop_method)

@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 from ..adp.dataloader import find_cls_labels, load_img_name_list, msf_item
+from ..voc12.dataloader import AffinityDatasetMixin, SegmentationDatasetBase
 
 CAT_LIST = ["urban", "agriculture", "rangeland", "forest", "water", "barren", "unknown"]
 
@@ -93,3 +94,27 @@ class DeepGlobeImageDataset:
 
         name = self.img_name_list[idx]
         return {"name": name, "img": np.asarray(Image.open(get_img_path(name, self.dev_root)).convert("RGB"))}
+
+
+class DeepGlobeSegmentationDataset(SegmentationDatasetBase):
+    """deepglobe/dataloader.py:233-287: the transform of voc12.dataloader.SegmentationDatasetBase (decoded / draw / item) on the
+    DeepGlobe files and constants."""
+    normalize_cls = TorchvisionNormalize
+
+    def __init__(self, img_name_list_path, label_dir, crop_size, dev_root, is_balanced, outsize=None, rescale=None,
+                 norm_mode="int", hor_flip=False, crop_method="random"):
+        super().__init__(label_dir, crop_size, outsize, rescale, norm_mode, hor_flip, crop_method)
+        self.img_name_list = load_img_name_list(img_name_list_path)
+        self.dev_root, self.is_balanced = dev_root, is_balanced
+
+    def image_path(self, name_str):
+        return get_img_path(name_str, self.dev_root)
+
+
+class DeepGlobeAffinityDataset(AffinityDatasetMixin, DeepGlobeSegmentationDataset):
+    """deepglobe/dataloader.py:289-308."""
+
+    def __init__(self, img_name_list_path, label_dir, crop_size, dev_root, is_balanced, indices_from=None, indices_to=None,
+                 rescale=None, norm_mode="int", hor_flip=False, crop_method=None, outsize=None):
+        super().__init__(img_name_list_path, label_dir, crop_size, dev_root, is_balanced, outsize, rescale, norm_mode, hor_flip,
+                         crop_method)

@@ -15,8 +15,12 @@
                    wsc_irn_sgd_step) and the repack of the head weights into the net (wsc_net_irn_load_params) per step, the
                    closing dp_mean pass (fit_dp_mean, train_irn.py:148-164), and the trained state dict
 
-Every backbone stage is detached in Net.forward, so the gradient of the heads is the whole gradient of a step.  The affinity
-datasets' crop / rescale / flip, DataLoader shuffling and DataParallel are not here."""
+    TrainBatcher   what feeds a step: the affinity datasets' rescale / normalise / flip / crop and the quarter-size label
+                   (voc12/dataloader.py:270-321) from decoded files, on the device (wsc_irn_train_batch); step.train_irn.run is
+                   the loop around it (shuffled epochs, drop_last)
+
+Every backbone stage is detached in Net.forward, so the gradient of the heads is the whole gradient of a step.  DataParallel is
+not here."""
 import numpy as np
 
 from . import _lib
@@ -192,6 +196,80 @@ class AffinityLoss:
                 m.free()
 
 
+class TrainBatcher:
+    """One training batch on the device from decoded files: the sample transform of the *AffinityDataset classes
+    (voc12/dataloader.py:270-321 and twins) as wsc_irn_train_batch, bit for bit what the host datasets' item() returns.
+
+        TrainBatcher(ctx, crop_size, norm_mode, outsize=None, normalize=None, rescale=None)
+          norm_mode   'int' / 'float' of TorchvisionNormalize; normalize: the dataset's TorchvisionNormalize class (its
+                      constants differ per dataset; default voc12.dataloader's)
+          outsize     None: the records' (scaled_h, scaled_w) are the target of the PIL rescale (stage 1; a sample that has that
+                      size already is left alone); (h, w): TorchvisionResize of image and label to it (stage 2: vgg16 / m7)
+          rescale     the dataset's scale range, only checked: rescale together with outsize is a ValueError (no reference
+                      configuration combines them)
+        apply(images, labels, params) -> (x float32 (B,3,S,S), label uint8 (B,S,S), reduced uint8 (B,s,s)), three DeviceMaps
+          images      B uint8 (H, W, 3) arrays, labels B uint8 (H, W) arrays (dataset.decoded), params B records (dataset.draw)
+          One upload of the packed images, one of the packed labels, no download; the caller frees the three results.
+          x and reduced are what IrnTrainer.step(x, reduced) takes."""
+
+    def __init__(self, ctx, crop_size, norm_mode, outsize=None, normalize=None, rescale=None):
+        if rescale and outsize is not None:
+            raise ValueError("TrainBatcher: rescale together with outsize: no reference configuration combines them")
+        if normalize is None:
+            from .voc12.dataloader import TorchvisionNormalize as normalize
+        if norm_mode not in ("int", "float"):
+            raise ValueError("norm_mode value is not 'int' or 'float'")
+        self.ctx = ctx
+        self.crop_size = int(crop_size)
+        self.reduced_size = _lib.irn_reduced_size(self.crop_size)
+        self.norm = normalize(norm_mode)
+        self.pre_div255 = norm_mode == "float"
+        self.outsize = None if outsize is None else (int(outsize[0]), int(outsize[1]))
+        self.stage = _lib.IRN_STAGE_PIL_RESCALE if self.outsize is None else _lib.IRN_STAGE_TV_RESIZE
+
+    @staticmethod
+    def _pack(name, arrays, ndim):
+        """-> (one uint8 vector, byte offsets, sizes)"""
+        arrays = [np.asarray(a) for a in arrays]
+        for i, a in enumerate(arrays):
+            if a.dtype != np.uint8 or a.ndim != ndim or (ndim == 3 and a.shape[2] != 3) or 0 in a.shape:
+                raise ValueError("TrainBatcher: %s %d is %r %s, expected uint8 %s" % (name, i, a.shape, a.dtype, "(H, W, 3)" if ndim == 3 else "(H, W)"))
+        offs = np.concatenate([[0], np.cumsum([a.size for a in arrays])]).astype(np.int64)
+        flat = np.empty(int(offs[-1]), np.uint8)
+        for a, o in zip(arrays, offs):
+            flat[o:o + a.size] = a.reshape(-1)
+        return flat, offs[:-1], [a.shape[:2] for a in arrays]
+
+    def apply(self, images, labels, params):
+        B, S, s = len(images), self.crop_size, self.reduced_size
+        p = np.asarray(params)
+        if B < 1 or len(labels) != B or p.shape != (B, len(_lib.IRN_BATCH_PARAMS)) or p.dtype.kind not in "iu":
+            raise ValueError("TrainBatcher.apply: %d images, %d labels, params %r %s" % (B, len(labels), p.shape, p.dtype))
+        img, ioff, sizes = self._pack("image", images, 3)
+        lab, loff, lsizes = self._pack("label", labels, 2)
+        if sizes != lsizes:
+            raise ValueError("TrainBatcher.apply: the labels' sizes %r are not the images' %r" % (lsizes[:4], sizes[:4]))
+        if self.outsize is not None and any((int(r[0]), int(r[1])) != self.outsize for r in p):
+            raise ValueError("TrainBatcher.apply: a record resizes to another size than outsize %r" % (self.outsize,))
+        outs, held = [], []
+        try:
+            held.append(DeviceMaps.from_host(self.ctx, img))
+            held.append(DeviceMaps.from_host(self.ctx, lab))
+            outs.append(DeviceMaps(self.ctx, (B, 3, S, S), np.float32))
+            outs.append(DeviceMaps(self.ctx, (B, S, S), np.uint8))
+            outs.append(DeviceMaps(self.ctx, (B, s, s), np.uint8))
+            _lib.irn_train_batch(self.ctx, held[0].ptr, held[1].ptr, sizes, ioff, loff, p, S, self.norm.mean, self.norm.std, self.pre_div255,
+                                 self.stage, outs[0].ptr, outs[1].ptr, outs[2].ptr)
+            return tuple(outs)
+        except Exception:
+            for m in outs:
+                m.free()
+            raise
+        finally:
+            for m in held:  # (pooled: reuse is ordered behind the launches on the context's stream)
+                m.free()
+
+
 class IrnTrainer:
     """One IRNet training step after another, and the closing pass: step/train_irn.py:86-90, 105-164 on the device.
 
@@ -282,21 +360,32 @@ class IrnTrainer:
     def momentum_host(self):
         return IrnGrads(self.mom, self.grad.layout).to_state_dict()
 
-    def fit_dp_mean(self, batches):
+    def fit_dp_mean(self, batches, n_batches=None):
+        """n_batches: the count of an iterable that is consumed one batch at a time (step.train_irn: each batch is a DeviceMaps
+        that lives only until the next one is asked for); None: `batches` is listed first"""
         self._live()
-        batches = list(batches)
-        if not batches:
+        if n_batches is None:
+            batches = list(batches)
+            n_batches = len(batches)
+        n_batches = int(n_batches)
+        if n_batches < 1:
             raise ValueError("IrnTrainer.fit_dp_mean: no batches")
         net = self.model._ensure_net()
         shift = net.get_mean_shift()
-        with DeviceMaps(self.ctx, (len(batches), 2), np.float64) as slots:
+        with DeviceMaps(self.ctx, (n_batches, 2), np.float64) as slots:
+            seen = 0
             for i, x in enumerate(batches):
+                if i >= n_batches:
+                    raise ValueError("IrnTrainer.fit_dp_mean: more than the %d batches announced" % n_batches)
                 edge, dp = self.model.forward_train_dev(x)
                 with edge, dp:
                     N, C, Hd, Wd = dp.shape
                     _lib.channel_mean_nchw(self.ctx, dp.ptr, N, C, Hd, Wd, slots.ptr + 16 * i, sub=shift)
+                seen = i + 1
+            if seen != n_batches:
+                raise ValueError("IrnTrainer.fit_dp_mean: %d batches, %d announced" % (seen, n_batches))
             means = slots.to_host()  # the pass's one download
-        mean = (means.sum(axis=0) / len(batches)).astype(np.float32)
+        mean = (means.sum(axis=0) / n_batches).astype(np.float32)
         net.set_mean_shift(mean)
         self.model._sd["mean_shift.running_mean"] = mean.copy()
         return mean

@@ -1,7 +1,14 @@
 """misc.imutils helpers used by the CAM path.  The reference imports them from a `misc`
 package that is git-ignored there (03b_irn/.gitignore); semantics follow upstream
 jiwoon-ahn/irn as recorded in SURVEY.md Appendix A.  Call sites:
-03b_irn/step/make_cam.py:41-42, 03b_irn/step/cam_to_ir_label.py:35,47,52,67."""
+03b_irn/step/make_cam.py:41-42, 03b_irn/step/cam_to_ir_label.py:35,47,52,67.
+
+The training-time augmentations of the affinity datasets (random_scale, random_lr_flip, get_random_crop_box, random_crop,
+top_left_crop; voc12/dataloader.py:280-296) are upstream IRN's as SURVEY.md Appendix A records them, with upstream's draws from
+Python's `random` in upstream's order.  Their parity against upstream itself is UNPINNED (the module is not in the reference
+tree); the draw order is pinned by tests/test_irn_batch_oracle.py."""
+import random
+
 import numpy as np
 
 from .. import _lib
@@ -43,6 +50,82 @@ def pil_rescale(img, scale, order):
 def scale_images(img_u8, scales):
     """[img at every scale of `scales`] as the MSF datasets build them (s == 1: the image itself)."""
     return [img_u8 if s == 1 else pil_rescale(img_u8, s, order=3) for s in scales]
+
+
+# ---- the training-time augmentations (call sites: voc12/dataloader.py:169, 178-184, 280, 290-296 and the ADP / DeepGlobe twins) --
+# Upstream IRN's misc/imutils.py as SURVEY.md Appendix A records it: the draws come from Python's `random`, in upstream's order.
+# The module is not in the reference tree, so the parity of these five against upstream is UNPINNED; what is pinned is the draw
+# order stated here (tests/test_irn_batch_oracle.py) and that the device transform applies the same records (wsc_irn_train_batch).
+def random_scale(img, scale_range, order):
+    """One random.random() draw: the factor scale_range[0] + r * (scale_range[1] - scale_range[0]); a tuple of images is
+    rescaled with the tuple of orders, e.g. (3, 0) for (image, label)."""
+    target_scale = scale_range[0] + random.random() * (scale_range[1] - scale_range[0])
+    if isinstance(img, tuple):
+        return (pil_rescale(img[0], target_scale, order[0]), pil_rescale(img[1], target_scale, order[1]))
+    return pil_rescale(img, target_scale, order)
+
+
+def random_lr_flip(img):
+    """One random.getrandbits(1) draw; np.fliplr of the image (of every image of a tuple) where it is 1."""
+    if bool(random.getrandbits(1)):
+        if isinstance(img, tuple):
+            return [np.fliplr(m) for m in img]
+        return np.fliplr(img)
+    return img
+
+
+def get_random_crop_box(imgsize, cropsize):
+    """-> (cont_top, cont_bottom, cont_left, cont_right, img_top, img_bottom, img_left, img_right).  Two random.randrange
+    draws, the width's space first and then the height's: where the image is larger than the crop (space > 0) the draw places
+    the window in the image (img_*), otherwise it places the image in the container (cont_*)."""
+    h, w = imgsize
+    ch = min(cropsize, h)
+    cw = min(cropsize, w)
+    w_space = w - cropsize
+    h_space = h - cropsize
+    if w_space > 0:
+        cont_left = 0
+        img_left = random.randrange(w_space + 1)
+    else:
+        cont_left = random.randrange(-w_space + 1)
+        img_left = 0
+    if h_space > 0:
+        cont_top = 0
+        img_top = random.randrange(h_space + 1)
+    else:
+        cont_top = random.randrange(-h_space + 1)
+        img_top = 0
+    return cont_top, cont_top + ch, cont_left, cont_left + cw, img_top, img_top + ch, img_left, img_left + cw
+
+
+def _crop_container(img, cropsize, fill):
+    shape = (cropsize, cropsize) + tuple(img.shape[2:])
+    return np.ones(shape, img.dtype) * fill
+
+
+def random_crop(images, cropsize, default_values):
+    """One get_random_crop_box for all the images (the first one's size); each lands in a cropsize x cropsize container filled
+    with its default value."""
+    if isinstance(images, np.ndarray):
+        images = (images,)
+    if isinstance(default_values, int):
+        default_values = (default_values,)
+    box = get_random_crop_box(images[0].shape[:2], cropsize)
+    new_images = []
+    for img, f in zip(images, default_values):
+        cont = _crop_container(img, cropsize, f)
+        cont[box[0]:box[1], box[2]:box[3]] = img[box[4]:box[5], box[6]:box[7]]
+        new_images.append(cont)
+    return new_images[0] if len(new_images) == 1 else new_images
+
+
+def top_left_crop(img, cropsize, default_value):
+    h, w = img.shape[:2]
+    ch = min(cropsize, h)
+    cw = min(cropsize, w)
+    container = _crop_container(img, cropsize, default_value)
+    container[:ch, :cw] = img[:ch, :cw]
+    return container
 
 
 def HWC_to_CHW(img):

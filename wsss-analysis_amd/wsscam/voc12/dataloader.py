@@ -174,3 +174,148 @@ class VOC12ImageDataset:
 
         name_str = decode_int_filename(self.img_name_list[idx])
         return {"name": name_str, "img": np.asarray(Image.open(get_img_path(name_str, self.dev_root)).convert("RGB"))}
+
+
+class SegmentationDatasetBase:
+    """The sample transform the three *SegmentationDataset classes of the reference share (voc12/dataloader.py:248-300,
+    adp/dataloader.py:242-300, deepglobe/dataloader.py:233-287), split so that the device can apply the same random choices:
+
+        decoded(idx)        -> (uint8 (H, W, 3) image, uint8 (H, W) label): the two files, decoded (PIL)
+        draw(idx, hw=None)  -> the parameter record, int32 (9,) in the order of _lib.IRN_BATCH_PARAMS: (scaled_h, scaled_w,
+                               flip, cont_top, cont_left, img_top, img_left, ch, cw).  The draws are the reference's, from
+                               Python's `random` in its order: random.random() (rescale), random.getrandbits(1) (hor_flip),
+                               imutils.get_random_crop_box's two randrange (crop_method 'random').  hw: the image's size where
+                               the caller has it (else the file's header is read)
+        item(idx, params, decoded=None)   the record applied on the host -> {'name', 'img' float32 (3, S, S), 'label' uint8
+                               (S, S)}: rescale (PIL bicubic / nearest) or TorchvisionResize (image AND label), normalise,
+                               flip, crop into the 0.0 / 255 containers, HWC -> CHW.  The reference's label is float64 from
+                               TorchvisionResize on; its only reader is imutils.pil_resize, which takes np.uint8 of it first, so
+                               the label is truncated here
+        __getitem__(idx)    item(idx, draw(idx))
+
+    irn_train.TrainBatcher.apply(images, labels, params) computes the same arrays on the device (wsc_irn_train_batch), to the bit.
+    Subclasses give `names`, image_path(name), the label file's stem and their TorchvisionNormalize."""
+    normalize_cls = TorchvisionNormalize
+
+    def __init__(self, label_dir, crop_size, outsize=None, rescale=None, norm_mode="int", hor_flip=False, crop_method="random"):
+        if rescale and outsize is not None:
+            raise ValueError("rescale together with outsize: no reference configuration combines them")
+        if norm_mode not in ("int", "float"):
+            raise ValueError("norm_mode value is not 'int' or 'float'")
+        self.label_dir = label_dir
+        self.crop_size = int(crop_size)
+        self.outsize = None if outsize is None else (int(outsize[0]), int(outsize[1]))
+        self.rescale = tuple(rescale) if rescale else None
+        self.norm_mode = norm_mode
+        self.img_normal = self.normalize_cls(norm_mode)
+        self.hor_flip = hor_flip
+        self.crop_method = crop_method
+
+    def __len__(self):
+        return len(self.img_name_list)
+
+    def name_str(self, idx):
+        return str(self.img_name_list[idx])
+
+    def image_path(self, name_str):
+        raise NotImplementedError
+
+    def decoded(self, idx):
+        from PIL import Image
+
+        name_str = self.name_str(idx)
+        img = np.asarray(Image.open(self.image_path(name_str)).convert("RGB"))
+        label = np.asarray(Image.open(os.path.join(self.label_dir, name_str + ".png")))
+        if label.ndim != 2 or label.dtype != np.uint8 or label.shape != img.shape[:2]:
+            raise ValueError("label %s.png is %r %s, expected uint8 %r" % (name_str, label.shape, label.dtype, img.shape[:2]))
+        return img, label
+
+    def draw(self, idx, hw=None):
+        import random
+
+        from ..misc import imutils
+
+        if hw is None:
+            from PIL import Image
+
+            with Image.open(self.image_path(self.name_str(idx))) as im:
+                hw = (im.size[1], im.size[0])
+        sh, sw = int(hw[0]), int(hw[1])
+        if self.rescale:  # imutils.random_scale -> pil_rescale's target size
+            f = self.rescale[0] + random.random() * (self.rescale[1] - self.rescale[0])
+            sh, sw = int(np.round(sh * f)), int(np.round(sw * f))
+        if self.outsize is not None:
+            sh, sw = self.outsize
+        flip = int(bool(random.getrandbits(1))) if self.hor_flip else 0
+        S = self.crop_size
+        if self.crop_method == "random":
+            b = imutils.get_random_crop_box((sh, sw), S)
+            box = (b[0], b[2], b[4], b[6], b[1] - b[0], b[3] - b[2])
+        elif self.crop_method is not None:  # imutils.top_left_crop
+            box = (0, 0, 0, 0, min(S, sh), min(S, sw))
+        else:
+            if (sh, sw) != (S, S):
+                raise ValueError("crop_method None on a %dx%d sample: the batch needs %dx%d" % (sh, sw, S, S))
+            box = (0, 0, 0, 0, S, S)
+        return np.array((sh, sw, flip) + box, np.int32)
+
+    def item(self, idx, params, decoded=None):
+        from ..misc import imutils
+
+        img, label = decoded if decoded is not None else self.decoded(idx)
+        sh, sw, flip, cont_top, cont_left, img_top, img_left, ch, cw = (int(v) for v in params)
+        if self.outsize is not None:  # TorchvisionResize, image and label (float64)
+            img, label = resize_bilinear_f64(img, (sh, sw)), resize_bilinear_f64(label[..., None], (sh, sw))[..., 0]
+        else:
+            img, label = imutils.pil_resize(img, (sh, sw), 3), imutils.pil_resize(label, (sh, sw), 0)
+        img = self.img_normal(img)
+        if flip:
+            img, label = np.fliplr(img), np.fliplr(label)
+        S = self.crop_size
+        x = np.zeros((S, S, 3), np.float32)
+        lab = np.full((S, S), 255, label.dtype)
+        x[cont_top:cont_top + ch, cont_left:cont_left + cw] = img[img_top:img_top + ch, img_left:img_left + cw]
+        lab[cont_top:cont_top + ch, cont_left:cont_left + cw] = label[img_top:img_top + ch, img_left:img_left + cw]
+        return {"name": self.img_name_list[idx], "img": np.ascontiguousarray(np.transpose(x, (2, 0, 1))), "label": np.uint8(lab)}
+
+    def __getitem__(self, idx):
+        dec = self.decoded(idx)
+        return self.item(idx, self.draw(idx, dec[0].shape[:2]), dec)
+
+
+class AffinityDatasetMixin:
+    """*AffinityDataset.__getitem__ (voc12/dataloader.py:314-321): adds 'reduced_label' = imutils.pil_rescale(label, 0.25, 0),
+    the array irn_train.AffinityLoss takes.  The three pair-label tensors of GetAffinityLabelFromIndices are what
+    wsc_irn_aff_loss computes from it on the device, so they are not materialised (indices_from / indices_to are accepted and
+    unused)."""
+
+    def item(self, idx, params, decoded=None):
+        from ..misc import imutils
+
+        out = super().item(idx, params, decoded)
+        out["reduced_label"] = np.ascontiguousarray(imutils.pil_rescale(out["label"], 0.25, 0))
+        return out
+
+
+class VOC12SegmentationDataset(SegmentationDatasetBase):
+    """voc12/dataloader.py:248-300."""
+
+    def __init__(self, img_name_list_path, label_dir, crop_size, dev_root, outsize=None, rescale=None, norm_mode="int",
+                 hor_flip=False, crop_method="random"):
+        super().__init__(label_dir, crop_size, outsize, rescale, norm_mode, hor_flip, crop_method)
+        self.img_name_list = load_img_name_list(img_name_list_path)
+        self.dev_root = dev_root
+
+    def name_str(self, idx):
+        return decode_int_filename(self.img_name_list[idx])
+
+    def image_path(self, name_str):
+        return get_img_path(name_str, self.dev_root)
+
+
+class VOC12AffinityDataset(AffinityDatasetMixin, VOC12SegmentationDataset):
+    """voc12/dataloader.py:302-321."""
+
+    def __init__(self, img_name_list_path, label_dir, crop_size, dev_root, indices_from=None, indices_to=None, rescale=None,
+                 norm_mode="int", hor_flip=False, crop_method=None, outsize=None):
+        super().__init__(img_name_list_path, label_dir, crop_size, dev_root, outsize, rescale, norm_mode, hor_flip, crop_method)
