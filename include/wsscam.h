@@ -1032,6 +1032,38 @@ int wsc_seg_crf_logprob(wsc_ctx *ctx, const float *q_dev, int B, int C, long lon
  * (model.py:666-669) takes the arg-max of the network's NHWC softmax through that call at equal sizes. */
 int wsc_seg_planes_from_nhwc(wsc_ctx *ctx, const float *src_dev, int B, int C, long long n, float *dst_dev);
 
+/* ---- SEC / DSRG: the inputs of a training step and the ground truth of a validation batch (csrc/seg_batch.hip) --------------------
+ * Both are asynchronous on the ctx stream, copy their host arrays during the call (one staged table each) and check every limit
+ * and every list entry on the host arrays BEFORE any launch: WSC_ERR_INVALID, the text names the sample, nothing is written.
+ * Limits: 1 <= B <= 65535, 1 <= C / n_class <= 32, s * s <= 8192, every size >= 1 with a pixel count within int32, byte offsets
+ * >= 0, list offsets neither negative nor decreasing. */
+
+/* One training batch of Model.next_batch: m_train / get_data (model.py:229-252) and image_preprocess (:318-331).
+ * img_dev, src_hw_host, src_off_host, mean_bgr_host, H, W, x_dev: exactly wsc_seg_preprocess_u8's, which forms x_dev (its bits).
+ * cues_host: the (class, row, col) lists of localization_cues.pickle, sample b's [3][n_b] int32 block at int index
+ *   3 * cue_off_host[b], n_b = cue_off_host[b + 1] - cue_off_host[b] (0 is legal, duplicates are legal);
+ * labels_host: sample b's classes at int index label_off_host[b] .. label_off_host[b + 1].
+ * cues_dev float32 [B][s][s][C]: 1.0 where (row, col, class) is listed, 0.0 elsewhere (cues[cues_i[1], cues_i[2], cues_i[0]] = 1.0);
+ * labels_dev float32 [B][C]: 1.0 at the listed classes and at class 0 (label[0] = 1.0, :240-242), 0.0 elsewhere.
+ * Every element of both is written exactly once by a plain store (no memset, no global atomic).  Two launches. */
+int wsc_seg_train_batch(wsc_ctx *ctx, const uint8_t *img_dev, int B, const int32_t *src_hw_host /*[B][2]*/,
+                        const int64_t *src_off_host /*[B]*/, const int32_t *cues_host, const int32_t *cue_off_host /*[B+1]*/,
+                        const int32_t *labels_host, const int32_t *label_off_host /*[B+1]*/, const float *mean_bgr_host /*[3]*/,
+                        int H, int W, int s, int C, float *x_dev, float *cues_dev, float *labels_dev);
+
+/* The ground truth of a validation batch: m_val / image_preprocess (model.py:254-270, :338-342), then the class test of
+ * eval_miou (:701, :709-714).  gt_dev: packed uint8 blocks [h_b][w_b][channels] (channels 1 or 3) at BYTE offset src_off_host[b].
+ * Resize: TF 1.x resize_nearest_neighbor(align_corners=False), in float32 as TF computes it --
+ *   scale = (float)in / (float)out;  src = min((int)floorf((float)dst * scale), in - 1)
+ * (tf_tap's scale and product; parity unpinned against TensorFlow, which the project does not install).
+ * Class test: colours_host == NULL: channel 0's value k if k < n_class, else n_class (secdsrg.seg_gt_index);
+ *   colours_host uint8 [n_class][3]: the first class whose colour equals all three channels, else n_class
+ *   (hsn.demo.gt_index_from_colours); a colour table with channels == 1 is WSC_ERR_INVALID.
+ * index_dev uint8 [B][OH][OW], values in [0, n_class]. */
+int wsc_seg_gt_index_tf(wsc_ctx *ctx, const uint8_t *gt_dev, int B, const int32_t *src_hw_host /*[B][2]*/,
+                        const int64_t *src_off_host /*[B]*/, int channels, const uint8_t *colours_host, int n_class, int OH, int OW,
+                        uint8_t *index_dev);
+
 /* ---- HistoSegNet post-processing (03c_hsn/utilities.py:231-397), device resident ---------- */
 
 /* HSN grad_cam after the einsum (utilities.py:262-277), for the NHWC maps of wsc_net_forward_gradcam(relu = 0):

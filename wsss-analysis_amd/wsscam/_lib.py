@@ -210,6 +210,8 @@ _SIGNATURES = {
     "wsc_seg_crf_image_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "wsc_seg_crf_logprob": (_i, [_vp, _vp, _i, _i, ctypes.c_longlong, _f, _vp]),
     "wsc_seg_planes_from_nhwc": (_i, [_vp, _vp, _i, _i, ctypes.c_longlong, _vp]),
+    "wsc_seg_train_batch": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "wsc_seg_gt_index_tf": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "wsc_hsn_gradcam_post": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i]),
     "wsc_hsn_voc_background": (_i, [_vp, _vp, _i, _i, _i, _vp, _i]),
     "wsc_hsn_class_mass": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -1546,6 +1548,57 @@ def seg_crf_logprob(ctx, q_dev, B, C, n, min_prob, out_dev):
 def seg_planes_from_nhwc(ctx, src_dev, B, C, n, dst_dev):
     """wsc_seg_planes_from_nhwc: NHWC maps [B][n][C] -> class-major planes [B][C][n] (the layout seg_resize_argmax reads)."""
     check(ctx._lib.wsc_seg_planes_from_nhwc(ctx.h, _ptr(src_dev), int(B), int(C), int(n), _ptr(dst_dev)))
+
+
+def seg_cue_tables(cues_per_sample, labels_per_sample):
+    """The ragged host tables wsc_seg_train_batch takes -> (cues, cue_off, labels, label_off): cues_per_sample[b] the (3, n_b)
+    (class, row, col) index lists of localization_cues.pickle (n_b = 0 is legal), labels_per_sample[b] the listed classes.
+    cues: sample b's [3][n_b] int32 block at int index 3 * cue_off[b]; the offsets are int32 [B + 1]."""
+    per = []
+    for b, c in enumerate(cues_per_sample):
+        c = np.asarray(c)
+        if c.size and (c.ndim != 2 or c.shape[0] != 3 or c.dtype.kind not in "iu"):
+            raise ValueError("seg_cue_tables: sample %d: cues %r %s, expected integer (3, n)" % (b, c.shape, c.dtype))
+        per.append(c.reshape(-1))
+    cues, off3 = _key_table(per)
+    labels, label_off = _key_table(labels_per_sample)
+    return cues, off3 // 3, labels, label_off
+
+
+def seg_train_batch(ctx, img_dev, sizes, offsets, cues, cue_off, labels, label_off, mean_bgr, out_hw, s, C, x_dev, cues_dev, labels_dev):
+    """wsc_seg_train_batch: packed uint8 RGB images (as seg_preprocess_u8 takes them) and the tables of seg_cue_tables ->
+    x_dev float32 [B][H][W][3] (seg_preprocess_u8's bits), cues_dev float32 [B][s][s][C] (1.0 at the listed (row, col, class)),
+    labels_dev float32 [B][C] (1.0 at the listed classes and at class 0).  The library checks every entry before any launch."""
+    B = len(sizes)
+    size_hw = _size_table(sizes, B)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    tabs = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in (cues, cue_off, labels, label_off)]
+    if off.shape != (B,) or tabs[1].shape != (B + 1,) or tabs[3].shape != (B + 1,):
+        raise ValueError("seg_train_batch: %d images, %r byte offsets, %r cue offsets, %r label offsets"
+                         % (B, off.shape, tabs[1].shape, tabs[3].shape))
+    m = np.ascontiguousarray(mean_bgr, dtype=np.float32).reshape(3)
+    check(ctx._lib.wsc_seg_train_batch(ctx.h, _ptr(img_dev), B, size_hw.ctypes.data, off.ctypes.data, tabs[0].ctypes.data,
+                                       tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, m.ctypes.data, int(out_hw[0]),
+                                       int(out_hw[1]), int(s), int(C), _ptr(x_dev), _ptr(cues_dev), _ptr(labels_dev)))
+
+
+def seg_gt_index_tf(ctx, gt_dev, sizes, offsets, channels, colours, n_class, out_hw, index_dev):
+    """wsc_seg_gt_index_tf: packed uint8 ground truths ([h_b][w_b][channels] blocks at byte `offsets`) -> uint8 [B][OH][OW] class
+    indices in [0, n_class]: the TF 1.x nearest-neighbour resize (float32 index), then channel 0's value (colours None) or the
+    first matching row of the uint8 (n_class, 3) colour table; no match: n_class."""
+    B = len(sizes)
+    size_hw = _size_table(sizes, B)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    if off.shape != (B,):
+        raise ValueError("seg_gt_index_tf: %d ground truths, %r byte offsets" % (B, off.shape))
+    col = None
+    if colours is not None:
+        col = np.ascontiguousarray(colours, dtype=np.uint8)
+        if col.shape != (int(n_class), 3):
+            raise ValueError("seg_gt_index_tf: colours %r for %d classes" % (col.shape, n_class))
+    check(ctx._lib.wsc_seg_gt_index_tf(ctx.h, _ptr(gt_dev), B, size_hw.ctypes.data, off.ctypes.data, int(channels),
+                                       None if col is None else col.ctypes.data, int(n_class), int(out_hw[0]), int(out_hw[1]),
+                                       _ptr(index_dev)))
 
 
 def ir_label_combine(ctx, fg_pred_dev, bg_pred_dev, keys, N, conf_dev):

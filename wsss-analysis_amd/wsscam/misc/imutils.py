@@ -207,3 +207,15 @@ def crf_inference(img, crf_config, num_classes, featmap, use_log=True, ctx=None)
     Q = ctx.to_host(q_dev, (num_classes, h, w), np.float32)
     crf.close()
     return np.ascontiguousarray(np.transpose(Q, (1, 2, 0)))
+
+
+def prefetched(pool, batches, load):
+    """(indices, [load(i) for i in indices]) per batch, the next batch's loads running while the caller works on this one"""
+    batches = iter(batches)
+    nxt = next(batches, None)
+    futures = [pool.submit(load, i) for i in nxt] if nxt is not None else None
+    while nxt is not None:
+        cur, cur_f = nxt, futures
+        nxt = next(batches, None)
+        futures = [pool.submit(load, i) for i in nxt] if nxt is not None else None
+        yield cur, [f.result() for f in cur_f]

@@ -21,13 +21,20 @@
                          update and the write-back of the weights into the net (wsc_seg_sgd_accumulate / _apply,
                          wsc_net_seg_load_params); parameters, momentum and accumulator never leave the device
 
+    SegBatcher           Model.next_batch (model.py:207-348): the inputs of a training step -- network input, dense cues from the
+                         sparse lists of localization_cues.pickle (load_cues), labels -- and of a validation batch -- network input,
+                         ground-truth class indices -- as DeviceMaps (wsc_seg_train_batch, wsc_seg_gt_index_tf), with numpy twins
+    SegTrainLoop, train  Model.train() (model.py:435-540): shuffled_ids' order, one SegTrainer.step per iteration, the reports with
+                         the validation mIoU of the is_eval=False pass, epoch-<i>.npy / final-0.npy, resume
+
 Dropout (SegNet.forward_dev(dropout=...), SegTrainer(drop_prob=0.5)) has the project's own counter-based keep-masks, not
-TensorFlow's random stream; reading TensorFlow checkpoints is out of scope.  Nothing here imports
+TensorFlow's random stream, and so has the shuffle order (shuffled_ids: numpy's generator); reading TensorFlow checkpoints is out of
+scope.  Nothing here imports
 TensorFlow: Model.predict runs on this module alone."""
 import numpy as np
 
 from . import _lib
-from .misc.imutils import default_context
+from .misc.imutils import default_context, prefetched
 
 
 class DeviceMaps:
@@ -466,7 +473,8 @@ class SegEvaluator:
     def update(self, probs, images, gts, want_pred=False):
         """probs[b] (h_b, w_b, C) float32 softmax (> 0) -- a list of host arrays, or ONE DeviceMaps (B, h, w, C) that is read in
         place (no upload); images[b] (H, W, 3) uint8 -- host arrays, or a uint8 DeviceMaps: (B, H, W, 3), or the packed ragged
-        batch SegNet.preprocess_dev(keep_images=True) returns; gts[b] as seg_gt_index takes it.
+        batch SegNet.preprocess_dev(keep_images=True) returns; gts[b] as seg_gt_index takes it (crf=False: or one uint8 DeviceMaps
+        (B, h, w) of class indices, SegBatcher.val_batch's).
         -> with want_pred the list of (H_b, W_b) uint8 label maps at the ground truths' sizes, else None."""
         if not self.crf:
             return self._update_argmax(probs, gts, want_pred)
@@ -581,19 +589,29 @@ class SegEvaluator:
 
     def _update_argmax(self, probs, gts, want_pred):
         """crf=False: np.argmax(pred_curr, axis=-1) of the map as it is (first maximum: wsc_seg_resize_argmax at equal sizes, on
-        the class-major planes wsc_seg_planes_from_nhwc writes) and the same counting."""
+        the class-major planes wsc_seg_planes_from_nhwc writes) and the same counting.  gts may also be ONE uint8 DeviceMaps
+        (B, h, w) of class indices in [0, num_classes] (SegBatcher.val_batch): it is counted against where it lies, no host copy
+        and no upload."""
         ctx, C = self.ctx, self.C
         B = probs.shape[0] if isinstance(probs, DeviceMaps) else len(probs)
-        if B == 0 or len(gts) != B:
-            raise ValueError("SegEvaluator.update: %d maps, %d ground truths" % (B, len(gts)))
+        gt_on_dev = isinstance(gts, DeviceMaps)
+        n_gt = gts.shape[0] if gt_on_dev else len(gts)
+        if B == 0 or n_gt != B:
+            raise ValueError("SegEvaluator.update: %d maps, %d ground truths" % (B, n_gt))
         maps, src_hw = self._map_blocks(probs)
-        gt = [np.ascontiguousarray(seg_gt_index(g, C, self.colours)) for g in gts]
+        if gt_on_dev:
+            if gts.dtype != np.uint8 or len(gts.shape) != 3:
+                raise ValueError("SegEvaluator.update: device ground truth %r %s must be uint8 (B, h, w) class indices" % (gts.shape, gts.dtype))
+            gt, gt_hw = None, [tuple(gts.shape[1:])] * B
+        else:
+            gt = [np.ascontiguousarray(seg_gt_index(g, C, self.colours)) for g in gts]
+            gt_hw = [tuple(g.shape) for g in gt]
         for b in range(B):
             if maps is not None and (maps[b].ndim != 3 or maps[b].shape[2] != C):
                 raise ValueError("SegEvaluator.update: image %d: map %r must be (h, w, %d)" % (b, maps[b].shape, C))
-            if tuple(gt[b].shape) != src_hw[b]:
+            if gt_hw[b] != src_hw[b]:
                 raise ValueError("SegEvaluator.update: image %d: without the CRF the ground truth %r has the map's size %r"
-                                 % (b, gt[b].shape, src_hw[b]))
+                                 % (b, gt_hw[b], src_hw[b]))
         n_pix = [h * w for h, w in src_hw]
         out_off = np.concatenate(([0], np.cumsum(n_pix)))
         bufs = []
@@ -603,7 +621,7 @@ class SegEvaluator:
             return buf
 
         try:
-            gt_dev = dev(ctx.to_device(np.concatenate([g.reshape(-1) for g in gt]), pooled=True))
+            gt_ptr = gts.ptr if gt_on_dev else dev(ctx.to_device(np.concatenate([g.reshape(-1) for g in gt]), pooled=True)).ptr
             prob_ptr = probs.ptr if maps is None else dev(ctx.to_device(np.concatenate([m.reshape(-1) for m in maps]), pooled=True)).ptr
             planes = dev(ctx.alloc(int(out_off[-1]) * C * 4, pooled=True))
             if maps is None:
@@ -614,7 +632,7 @@ class SegEvaluator:
                     _lib.seg_planes_from_nhwc(ctx, prob_ptr + o, 1, C, n_pix[b], planes.ptr + o)
             lab_dev = dev(ctx.alloc(int(out_off[-1]) * 4, pooled=True))
             _lib.seg_resize_argmax(ctx, planes, C, src_hw, src_hw, out_off[:-1] * C, out_off[:-1], lab_dev)
-            return self._count(lab_dev, src_hw, out_off, gt_dev.ptr, want_pred, dev)
+            return self._count(lab_dev, src_hw, out_off, gt_ptr, want_pred, dev)
         finally:
             for d in bufs:
                 d.free()
@@ -1241,3 +1259,332 @@ class Predictor:
         if self.net is not None:
             self.net.close()
             self.net = None
+
+
+# ---- Model.train: the batches, the shuffle order and the loop (model.py:207-348, 435-540) --------------------------------------
+CRF_CONFIG_TRAIN = {"g_sxy": 3 / 12, "g_compat": 3, "bi_sxy": 80 / 12, "bi_srgb": 13, "bi_compat": 10, "iterations": 5}  # DSRG.py:77
+
+
+def load_cues(path):
+    """localization_cues.pickle (model.py:174-178) -> its dict: "%s_labels" % id the listed classes of an image, "%s_cues" % id
+    its (3, n) index lists (class, row, col) at the seed size (:238-246)."""
+    import pickle
+
+    with open(path, "rb") as fh:
+        return pickle.load(fh, encoding="iso-8859-1")
+
+
+def shuffled_ids(n, seed, skip=0):
+    """The order of dataset.repeat(-1).shuffle(n) (model.py:278-279) over the ids 0 .. n-1, endlessly: a buffer holds the first n
+    elements of the stream 0, 1, .. n-1, 0, 1, ..; every draw picks a uniformly random slot, emits it and refills the slot with
+    the stream's next element.  The draws are `np.random.default_rng(seed).integers(0, n)`, one call per emission: the project's
+    own stream (as the dropout masks are), NOT TensorFlow's.  skip: the generator's state after `skip` emissions -- how a resumed
+    run continues the order of the run it resumes."""
+    n = int(n)
+    if n < 1 or int(skip) < 0:
+        raise ValueError("shuffled_ids: n = %r, skip = %r" % (n, skip))
+    rng = np.random.default_rng(seed)
+    buf, emitted = list(range(n)), 0  # (the stream's next element is emitted % n)
+    while True:
+        slot = int(rng.integers(0, n))
+        out, buf[slot] = buf[slot], emitted % n
+        emitted += 1
+        if emitted > skip:
+            yield out
+
+
+def tf_nearest_index(n_in, n_out):
+    """The source index of every destination index under TF 1.x resize_nearest_neighbor(align_corners=False), in float32 as
+    TensorFlow computes it: scale = float32(in) / float32(out); src = min((int)floor(float32(dst) * scale), in - 1)."""
+    scale = np.float32(n_in) / np.float32(n_out)
+    return np.minimum(np.floor(np.arange(n_out, dtype=np.float32) * scale).astype(np.int64), int(n_in) - 1)
+
+
+def _tf_resize_bilinear_host(img, H, W):
+    """tf.image.resize_bilinear (TF 1.x, align_corners=False) of one (h, w, c) array in float32, the products and sums of
+    csrc/tf_resize.h each rounded on its own"""
+    a = np.asarray(img, dtype=np.float32)
+    h, w = a.shape[:2]
+
+    def taps(n_in, n_out):
+        f = np.arange(n_out, dtype=np.float32) * (np.float32(n_in) / np.float32(n_out))
+        i0 = np.minimum(np.floor(f).astype(np.int64), n_in - 1)
+        return i0, np.minimum(i0 + 1, n_in - 1), f - i0.astype(np.float32)
+
+    y0, y1, ty = taps(h, H)
+    x0, x1, tx = taps(w, W)
+    tx, ty = tx[None, :, None], ty[:, None, None]
+    top = a[y0][:, x0] + (a[y0][:, x1] - a[y0][:, x0]) * tx
+    bottom = a[y1][:, x0] + (a[y1][:, x1] - a[y1][:, x0]) * tx
+    return top + (bottom - top) * ty
+
+
+class SegBatcher:
+    """The inputs of a SEC / DSRG training step and of a validation batch from decoded files (Model.next_batch, model.py:207-348).
+
+    train_batch(ids, images, cues_data) -> (x, cues, labels), DeviceMaps: m_train / get_data (:229-252) -- x (B, H, W, 3) the
+        network's input with SegNet.preprocess_dev's bits, cues float32 (B, s, s, C) dense from cues_data["%s_cues" % id],
+        labels float32 (B, C) from cues_data["%s_labels" % id] with class 0 set.  One upload of the packed uint8 images, one
+        wsc_seg_train_batch (the index lists travel in its staged table).
+    val_batch(images, gts) -> (x, gt_index), DeviceMaps: m_val (:254-270) -- x through wsc_seg_preprocess_u8, gt_index uint8
+        (B, H, W) in [0, C]: the ground truth (h, w), (h, w, 1) or (h, w, 3) uint8 resized with TF's nearest rule
+        (tf_nearest_index) and passed through seg_gt_index's class test (wsc_seg_gt_index_tf): what SegEvaluator(crf=False)
+        counts against.  One upload.
+    train_batch_host / val_batch_host: the same arrays in numpy alone.
+    images[b]: (h_b, w_b, 3) uint8 RGB as decoded.  colours: the (C, 3) table of the colour-coded datasets, or None (VOC)."""
+
+    def __init__(self, num_classes, img_mean, size=(321, 321), seed_size=41, colours=None, ctx=None):
+        self.ctx = ctx
+        self.C = int(num_classes)
+        self.img_mean = np.asarray(img_mean, dtype=np.float32).reshape(3)
+        self.size = (int(size[0]), int(size[1]))
+        self.seed_size = int(seed_size)
+        self.colours = None if colours is None else np.ascontiguousarray(colours, dtype=np.uint8).reshape(-1, 3)
+        if self.colours is not None and len(self.colours) != self.C:
+            raise ValueError("SegBatcher: %d colours for %d classes" % (len(self.colours), self.C))
+
+    @staticmethod
+    def _lists(ids, cues_data):
+        try:
+            return [np.asarray(cues_data["%s_cues" % i]) for i in ids], [np.asarray(cues_data["%s_labels" % i]).reshape(-1) for i in ids]
+        except KeyError as e:
+            raise KeyError("SegBatcher: the cue file has no entry %s" % e)
+
+    @staticmethod
+    def _blocks(arrays, what, channels=(3,)):
+        """uint8 arrays -> (flat views, [(h, w)], channel count)"""
+        out = []
+        for b, a in enumerate(arrays):
+            a = np.asarray(a)
+            if a.ndim == 2 and 1 in channels:
+                a = a[:, :, None]
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in channels or 0 in a.shape:
+                raise ValueError("SegBatcher: %s %d is %r %s, not uint8 (h, w, %s)" % (what, b, a.shape, a.dtype, " or ".join(map(str, channels))))
+            out.append(np.ascontiguousarray(a))
+        if not out or len({a.shape[2] for a in out}) != 1:
+            raise ValueError("SegBatcher: %d %ss, one channel count for all" % (len(out), what))
+        return [a.reshape(-1) for a in out], [a.shape[:2] for a in out], out[0].shape[2]
+
+    def train_batch(self, ids, images, cues_data):
+        ctx = self.ctx or default_context()
+        cue_lists, label_lists = self._lists(ids, cues_data)
+        flat, sizes, _ = self._blocks(images, "image")
+        if len(flat) != len(cue_lists):
+            raise ValueError("SegBatcher.train_batch: %d ids, %d images" % (len(cue_lists), len(flat)))
+        tables = _lib.seg_cue_tables(cue_lists, label_lists)
+        B, (H, W), s, C = len(flat), self.size, self.seed_size, self.C
+        offsets = np.concatenate(([0], np.cumsum([f.size for f in flat])))[:-1]
+        held = []
+        try:
+            held.append(DeviceMaps.from_host(ctx, np.concatenate(flat)))
+            for shape in ((B, H, W, 3), (B, s, s, C), (B, C)):
+                held.append(DeviceMaps(ctx, shape, np.float32))
+            packed, x, cues, labels = held
+            _lib.seg_train_batch(ctx, packed.ptr, sizes, offsets, *tables, self.img_mean, (H, W), s, C, x.ptr, cues.ptr, labels.ptr)
+            held = [packed]
+            return x, cues, labels
+        finally:
+            for d in held:
+                d.free()
+
+    def val_batch(self, images, gts):
+        ctx = self.ctx or default_context()
+        flat, sizes, _ = self._blocks(images, "image")
+        gflat, gsizes, channels = self._blocks(gts, "ground truth", (1, 3))
+        if len(flat) != len(gflat):
+            raise ValueError("SegBatcher.val_batch: %d images, %d ground truths" % (len(flat), len(gflat)))
+        B, (H, W) = len(flat), self.size
+        offsets = np.concatenate(([0], np.cumsum([f.size for f in flat + gflat])))[:-1]
+        held = []
+        try:
+            packed = DeviceMaps.from_host(ctx, np.concatenate(flat + gflat))
+            held.append(packed)
+            x = DeviceMaps(ctx, (B, H, W, 3), np.float32)
+            held.append(x)
+            gt = DeviceMaps(ctx, (B, H, W), np.uint8)
+            held.append(gt)
+            _lib.seg_preprocess_u8(ctx, packed.ptr, sizes, offsets[:B], self.img_mean, (H, W), x.ptr)
+            _lib.seg_gt_index_tf(ctx, packed.ptr, gsizes, offsets[B:], channels, self.colours, self.C, (H, W), gt.ptr)
+            held = [packed]
+            return x, gt
+        finally:
+            for d in held:
+                d.free()
+
+    def _x_host(self, images):
+        H, W = self.size
+        mean = self.img_mean.reshape(1, 1, 3)
+        return np.stack([_tf_resize_bilinear_host(im, H, W)[:, :, ::-1] - mean for im in images]).astype(np.float32)
+
+    def train_batch_host(self, ids, images, cues_data):
+        cue_lists, label_lists = self._lists(ids, cues_data)
+        s, C = self.seed_size, self.C
+        cues = np.zeros((len(cue_lists), s, s, C), np.float32)
+        labels = np.zeros((len(cue_lists), C), np.float32)
+        for b, (c, l) in enumerate(zip(cue_lists, label_lists)):
+            c = c.reshape(3, -1).astype(np.int64)
+            if c.size and (c.min() < 0 or c[0].max() >= C or c[1:].max() >= s):
+                raise ValueError("SegBatcher: sample %d: a cue entry outside the (%d, %d, %d) plane" % (b, s, s, C))
+            cues[b, c[1], c[2], c[0]] = 1.0
+            labels[b, l.astype(np.int64)] = 1.0
+            labels[b, 0] = 1.0
+        return self._x_host(images), cues, labels
+
+    def val_batch_host(self, images, gts):
+        H, W = self.size
+        out = np.empty((len(gts), H, W), np.uint8)
+        for b, g in enumerate(gts):
+            g = np.asarray(g)
+            r = g[tf_nearest_index(g.shape[0], H)][:, tf_nearest_index(g.shape[1], W)]
+            out[b] = seg_gt_index(r, self.C, None if self.colours is None else [tuple(c) for c in self.colours])
+        return self._x_host(images), out
+
+
+def latest_checkpoint(save_dir):
+    """-> (path, i) of the epoch-<i>.npy with the largest i in save_dir (get_latest_checkpoint, model.py:406-415), or (None, 0)"""
+    import os
+
+    done = [int(f[len("epoch-"):-len(".npy")]) for f in os.listdir(save_dir)
+            if f.startswith("epoch-") and f.endswith(".npy") and f[len("epoch-"):-len(".npy")].isdigit()]
+    return (os.path.join(save_dir, "epoch-%d.npy" % max(done)), max(done)) if done else (None, 0)
+
+
+class SegTrainLoop:
+    """Model.train() (model.py:435-540): image files and the cue pickle in, checkpoints and the list of reports out.
+
+    method, weights, num_classes: as SegTrainer takes them; weights may also be the path of an init-model .npy, or of a checkpoint
+    directory (its final-0.npy, else its latest epoch-<i>.npy; the weights alone are taken from it).
+    train_ids, load_image: the training images' ids and id -> decoded uint8 RGB (h, w, 3); cues_data: load_cues' dict.
+    val_sets: {category: (ids, load_image, load_gt)} or None; load_gt(id) -> uint8 (h, w[, 1 | 3]).
+    batch_size, max_epochs, accum_num, base_lr, lr_decay, lr_step, momentum, weight_decay: model.py:29-145 (batch size 16 is
+    demo.py's default); drop_prob 0.5 is the 'train' phase; seed seeds the dropout masks and the shuffle; img_mean (BGR) is the
+    dataset's; crf_config_train DSRG.py:77 / SEC.py:19; size, seed_size: the network's input and its fc8 map (321 -> 41).
+    save_dir: where the checkpoints go (None: none are written); report_every: the reference's 200.
+
+    run() -> the list of reports, {"iteration", "epoch", "lr", "seed", "constrain", "total", "miou": {category: mIoU}}.
+    Per iteration i: epoch = i / iterations_per_epoch (len(train_ids) // batch_size; 0 is a ValueError), the rate is set to
+    lr_at(epoch) when i % iterations_per_epoch == 0 (:493-495), then ONE SegTrainer.step on a SegBatcher.train_batch of the next
+    batch_size ids of shuffled_ids(len(train_ids), seed).  Every report_every iterations, i = 0 included, a report holds the
+    means of the seed / constrain / total losses since the last one (:505-511) and, per validation category, the mIoU of the
+    is_eval=False pass (:520-527, :665-669, :698-719): val_batch -> SegNet.rescale_output_dev on the trainer's own net (no
+    dropout) -> SegEvaluator(crf=False), once over the category's images, nothing on the host.  At every epoch boundary
+    SegTrainer.save writes save_dir/epoch-<i>.npy, at the end final-0.npy (:536-538).  On start the latest epoch-<i>.npy of
+    save_dir, if any, is loaded with SegTrainer.load and the loop continues at i.  Decoding runs on a small thread pool, one
+    batch ahead.
+
+    Deviations from the reference:
+      1. it evaluates the logged losses in a second sess.run (:498), which pulls another batch from the iterator: its log
+         describes a different batch from the one whose gradient it accumulated, and it consumes two batches per iteration.
+         Here an iteration consumes one batch and the reported losses are those of the batch the gradient was taken on.
+      2. its checkpoints hold the trainable variables only: on resume momentum restarts at zero and the shuffle restarts.  Here
+         momentum, accumulator, RNG step and shuffle position (i * batch_size emissions) are restored: a resumed run equals the
+         uninterrupted one bit for bit.  (final-0.npy is an output only; the reference would resume from it at i = 0.)
+      3. the debug-image writers (should_saveimg), the TensorBoard summaries and TF checkpoint files are out of scope."""
+
+    def __init__(self, method, weights, num_classes, train_ids, load_image, cues_data, val_sets=None, batch_size=16, max_epochs=1,
+                 accum_num=1, base_lr=1e-4, lr_decay=0.5, lr_step=4, momentum=0.9, weight_decay=5e-4, drop_prob=0.5, seed=0,
+                 img_mean=None, crf_config_train=None, size=(321, 321), seed_size=41, save_dir=None, report_every=200, colours=None,
+                 precision=_lib.PREC_F16X3, ctx=None, num_workers=4):
+        import os
+
+        self.ids, self.load_image, self.cues_data = list(train_ids), load_image, cues_data
+        self.batch_size, self.max_epochs, self.report_every = int(batch_size), int(max_epochs), int(report_every)
+        if self.batch_size < 1 or self.report_every < 1:
+            raise ValueError("SegTrainLoop: batch_size = %r, report_every = %r" % (batch_size, report_every))
+        self.per_epoch = len(self.ids) // self.batch_size
+        if self.per_epoch == 0:
+            raise ValueError("SegTrainLoop: %d training ids give no batch of %d" % (len(self.ids), self.batch_size))
+        if img_mean is None:
+            raise ValueError("SegTrainLoop: img_mean (BGR) is the dataset's and has no default")
+        self.C, self.seed, self.save_dir = int(num_classes), int(seed), save_dir
+        self.val_sets = dict(val_sets or {})
+        self.crf_cfg = dict(CRF_CONFIG_TRAIN if crf_config_train is None else crf_config_train)
+        self.num_workers = max(1, int(num_workers))
+        self.i, self.trainer = 0, None
+        kwargs = dict(precision=precision, ctx=ctx, base_lr=base_lr, momentum=momentum, weight_decay=weight_decay, accum_num=accum_num,
+                      lr_decay=lr_decay, lr_step=lr_step, drop_prob=drop_prob, seed=seed)
+        resume = None
+        if save_dir is not None:
+            os.makedirs(save_dir, exist_ok=True)
+            resume, self.i = latest_checkpoint(save_dir)
+        if resume is not None:  # (:476-484)
+            self.trainer = SegTrainer.load(resume, method, num_classes, **kwargs)
+        else:
+            if isinstance(weights, str):  # an init-model file, or a checkpoint directory: its final-0.npy, else its latest epoch
+                if os.path.isdir(weights):
+                    final = os.path.join(weights, "final-0.npy")
+                    weights = final if os.path.exists(final) else latest_checkpoint(weights)[0]
+                    if weights is None:
+                        raise ValueError("SegTrainLoop: the weights directory holds no final-0.npy and no epoch-<i>.npy")
+                weights = {k: v for k, v in np.load(weights, encoding="latin1", allow_pickle=True).item().items() if not k.startswith("__")}
+            self.trainer = SegTrainer(method, weights, num_classes, **kwargs)
+        self.batcher = SegBatcher(num_classes, img_mean, size=size, seed_size=seed_size, colours=colours, ctx=self.trainer.ctx)
+
+    def close(self):
+        if self.trainer is not None:
+            self.trainer.close()
+            self.trainer = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def validate(self, pool, ids, load_image, load_gt):
+        """the mIoU of the is_eval=False pass over `ids`, in batches of batch_size (the last one may be smaller)"""
+        tr, bs = self.trainer, self.batch_size
+        ev = SegEvaluator(self.C, None, ctx=tr.ctx, crf=False)
+        try:
+            chunks = (ids[k:k + bs] for k in range(0, len(ids), bs))
+            for _, loaded in prefetched(pool, chunks, lambda i: (load_image(i), load_gt(i))):
+                x, gt = self.batcher.val_batch([d[0] for d in loaded], [d[1] for d in loaded])
+                with x, gt:
+                    with tr.net.rescale_output_dev(x, self.batcher.img_mean, self.crf_cfg, seed_size=self.batcher.seed_size) as out:
+                        ev.update(out, None, gt)
+            return ev.metrics()["mIoU"]
+        finally:
+            ev.close()
+
+    def run(self):
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+
+        tr, bs, per_epoch = self.trainer, self.batch_size, self.per_epoch
+        total = per_epoch * self.max_epochs
+        order = shuffled_ids(len(self.ids), self.seed, skip=self.i * bs)
+        batches = ([self.ids[next(order)] for _ in range(bs)] for _ in range(self.i, total))
+        reports, sums, count = [], np.zeros(3), 0
+        with ThreadPoolExecutor(max_workers=self.num_workers) as pool:
+            for ids, images in prefetched(pool, batches, self.load_image):
+                i = self.i
+                epoch = i / per_epoch
+                x, cues, labels = self.batcher.train_batch(ids, images, self.cues_data)
+                with x, cues, labels:
+                    losses, new_cues = tr.step(x, cues, labels, self.batcher.img_mean, self.crf_cfg,
+                                               epoch=epoch if i % per_epoch == 0 else None)
+                    if new_cues is not cues:
+                        new_cues.free()
+                sums += (losses["seed"], losses["constrain"], losses["total"])
+                count += 1
+                if i % self.report_every == 0:
+                    means = sums / count
+                    sums, count = np.zeros(3), 0
+                    miou = {cat: self.validate(pool, list(v[0]), v[1], v[2]) for cat, v in self.val_sets.items()}
+                    reports.append({"iteration": i, "epoch": epoch, "lr": float(tr.lr), "seed": float(means[0]),
+                                    "constrain": float(means[1]), "total": float(means[2]), "miou": miou})
+                    print("epoch=%f | seed_loss=%f, constrain_loss=%f, total_loss=%f" % (epoch, means[0], means[1], means[2])
+                          + "".join(" | mIoU [%s] = %f" % kv for kv in miou.items()), flush=True)
+                self.i = i + 1
+                if self.i % per_epoch == 0 and self.save_dir is not None:
+                    tr.save(os.path.join(self.save_dir, "epoch-%d.npy" % self.i))
+        if self.save_dir is not None:
+            tr.save(os.path.join(self.save_dir, "final-0.npy"))
+        return reports
+
+
+def train(*args, **kwargs):
+    """SegTrainLoop(*args, **kwargs).run() with the trainer released afterwards -> the list of reports."""
+    with SegTrainLoop(*args, **kwargs) as loop:
+        return loop.run()

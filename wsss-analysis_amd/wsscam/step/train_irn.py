@@ -23,6 +23,7 @@ import numpy as np
 
 from .. import irn_train
 from ..misc import indexing
+from ..misc.imutils import prefetched as _prefetched
 from .make_sem_seg_labels import _build_model
 
 
@@ -56,18 +57,6 @@ def _initial_state_dict(args):
     if not name:
         raise ValueError("train_irn.run: args.state_dict (or args.irn_init_weights_name) must give the initial EdgeDisplacement state dict")
     return {k: v for k, v in np.load(name, encoding="latin1", allow_pickle=True).item().items() if not k.startswith("__")}
-
-
-def _prefetched(pool, batches, load):
-    """(indices, [load(i) for i in indices]) per batch, the next batch's loads running while the caller works on this one"""
-    batches = iter(batches)
-    nxt = next(batches, None)
-    futures = [pool.submit(load, i) for i in nxt] if nxt is not None else None
-    while nxt is not None:
-        cur, cur_f = nxt, futures
-        nxt = next(batches, None)
-        futures = [pool.submit(load, i) for i in nxt] if nxt is not None else None
-        yield cur, [f.result() for f in cur_f]
 
 
 def _infer_batches(pool, batcher, infer_dataset, bs):
