@@ -121,6 +121,18 @@ int wsc_ctx_create(int device, void *stream, wsc_ctx **out);
 void wsc_ctx_destroy(wsc_ctx *ctx);
 /* Sets a path selector (wsc_option) of the context; WSC_ERR_INVALID for an unknown option. */
 int wsc_ctx_set_option(wsc_ctx *ctx, int option, int value);
+/* Test hook for the scratch contract: scratch holds arbitrary bits on entry, and whatever a kernel reads, a kernel or
+ * memset of the same call wrote.  value 0..255 sets the context's fill byte, -1 turns the fill off (the default); anything else is
+ * WSC_ERR_INVALID (the hook then stays as it was, as after a failed fill).  On the call the workspace arena and every block on
+ * the cached allocator's free list are set to the byte, in stream order; while it is on, every cached block handed out (fresh or
+ * reused) and the WHOLE arena at every request of an entry point (no entry keeps arena contents across a request) are set to it
+ * before the caller gets them; so are the private workspaces of a wsc_seg_grad / wsc_irn_grad at the start of every backward or
+ * load_params call (nothing in them outlives a call).  Live blocks (weights, lattices, the Gaussian-lattice cache) and caller
+ * buffers are never touched.
+ * Not a wsc_option: results must not depend on it at all, which tests/test_gpu_scratch.py checks.  Off: no launch, no sync. */
+int wsc_ctx_scratch_fill(wsc_ctx *ctx, int value);
+/* The hook's current value: -1 (off) or the fill byte. */
+int wsc_ctx_scratch_fill_value(const wsc_ctx *ctx);
 int wsc_sync(wsc_ctx *ctx);
 /* Range guard of the IEEE-half conv modes.  Every conv epilogue that writes half activations raises a sticky per-ctx flag when
  * a value reaches the half ceiling (it is stored saturated at +-65504; fp32 in the reference would have kept it).  wsc_sync and

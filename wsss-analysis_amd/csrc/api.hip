@@ -46,6 +46,10 @@ int wsc_ctx_workspace(wsc_ctx *ctx, size_t bytes, void **out) {
         }
         ctx->ws_bytes = want;
     }
+    // wsc_ctx_scratch_fill: every request finds the whole arena at the fill byte, not what the call before left in it (no entry
+    // needs arena contents across a request: wsc_crf_v_inference, the only one that asks twice, keeps a group's results in a
+    // cached block)
+    if (ctx->scratch_fill >= 0 && ctx->ws) WSC_HIP(hipMemsetAsync(ctx->ws, ctx->scratch_fill, ctx->ws_bytes, ctx->stream));
     *out = ctx->ws;
     return WSC_OK;
 }
@@ -55,8 +59,12 @@ int wsc_ctx_cached_alloc(wsc_ctx *ctx, size_t bytes, void **out) {
     want = want <= (1u << 20) ? (want + 4095) / 4096 * 4096 : (want + (2u << 20) - 1) / (2u << 20) * (2u << 20);
     auto it = ctx->free_blocks.lower_bound(want);
     if (it != ctx->free_blocks.end() && it->first <= 2 * want + (1u << 20)) {
-        *out = it->second;
-        ctx->live_blocks[it->second] = it->first;
+        void *p = it->second;
+        const size_t have = it->first;
+        // (filled while the block is still on the free list: a failed memset leaves the lists as they were)
+        if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(p, ctx->scratch_fill, have, ctx->stream));
+        *out = p;
+        ctx->live_blocks[p] = have;
         ctx->free_blocks.erase(it);
         return WSC_OK;
     }
@@ -72,6 +80,14 @@ int wsc_ctx_cached_alloc(wsc_ctx *ctx, size_t bytes, void **out) {
     if (e != hipSuccess) {
         wsc_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
         return WSC_ERR_NOMEM;
+    }
+    if (ctx->scratch_fill >= 0) {
+        hipError_t f = hipMemsetAsync(p, ctx->scratch_fill, want, ctx->stream);
+        if (f != hipSuccess) {
+            (void)hipFree(p);
+            wsc_set_error("scratch fill of a fresh block (%zu bytes) failed: %s", want, hipGetErrorString(f));
+            return WSC_ERR_HIP;
+        }
     }
     ctx->live_blocks[p] = want;
     *out = p;
@@ -261,6 +277,24 @@ int wsc_ctx_set_option(wsc_ctx *ctx, int option, int value) {
     ctx->opt[option] = value;
     return WSC_OK;
 }
+
+int wsc_ctx_scratch_fill(wsc_ctx *ctx, int value) {
+    WSC_CHECK(ctx != nullptr, WSC_ERR_INVALID, "wsc_ctx_scratch_fill: null context");
+    WSC_CHECK(value >= -1 && value <= 255, WSC_ERR_INVALID, "wsc_ctx_scratch_fill: value %d is neither a byte nor -1 (off)", value);
+    if (value < 0) {
+        ctx->scratch_fill = -1;
+        return WSC_OK;
+    }
+    WSC_HIP(hipSetDevice(ctx->device));
+    // the scratch nobody owns right now: the arena and the free list (live blocks -- weights, lattices, the Gaussian cache --
+    // and caller buffers are never touched); stream-ordered, so whatever is enqueued still sees what it wrote
+    if (ctx->ws) WSC_HIP(hipMemsetAsync(ctx->ws, value, ctx->ws_bytes, ctx->stream));
+    for (auto &kv : ctx->free_blocks) WSC_HIP(hipMemsetAsync(kv.second, value, kv.first, ctx->stream));
+    ctx->scratch_fill = value; // (only now: a failed memset above leaves the hook as it was)
+    return WSC_OK;
+}
+
+int wsc_ctx_scratch_fill_value(const wsc_ctx *ctx) { return ctx ? ctx->scratch_fill : -1; }
 
 void wsc_ctx_destroy(wsc_ctx *ctx) {
     if (!ctx) return;

@@ -181,6 +181,10 @@ struct wsc_ctx {
     // crf.hip's per-image-size Gaussian lattices (created by the first wsc_crf_create); their device arrays are cached-alloc
     // blocks, handed back when the cache is destroyed and freed with everything else at destroy
     WscGaussCache *gauss_cache = nullptr;
+    // wsc_ctx_scratch_fill: -1 = off, else the byte that the arena (on the call and at every request), every cached block
+    // handed out and the grad objects' own workspaces (net.hip, seg_sgd.hip) are set to.  Not a path selector: a test hook that
+    // makes a read of scratch nobody wrote show up in values
+    int scratch_fill = -1;
 };
 int wsc_ctx_workspace(wsc_ctx *ctx, size_t bytes, void **out);
 // WSC_ERR_RANGE (with the error text) when the ctx's range flag is raised; the stream must have been synchronised

@@ -1835,6 +1835,8 @@ static int backward_seg(const char *fn, wsc_ctx *ctx, wsc_seg_grad *g, int B, in
         WSC_HIP(hipMalloc(&g->ws, need));
         g->ws_bytes = need;
     }
+    // (wsc_ctx_scratch_fill: the object's own workspace is scratch like the arena -- nothing in it outlives a call)
+    if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(g->ws, ctx->scratch_fill, g->ws_bytes, ctx->stream));
     char *p = (char *)g->ws;
     auto carve = [&](size_t bytes) { float *q = (float *)p; p += bytes; return q; };
     float *ga = carve(lines(g_max)), *gb = carve(lines(g_max));
@@ -2100,6 +2102,8 @@ int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const flo
         WSC_HIP(hipMalloc(&g->ws, need));
         g->ws_bytes = need;
     }
+    // (wsc_ctx_scratch_fill: the object's own workspace is scratch like the arena -- nothing in it outlives a call)
+    if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(g->ws, ctx->scratch_fill, g->ws_bytes, ctx->stream));
     char *p = (char *)g->ws;
     auto carve = [&](size_t bytes) { float *q = (float *)p; p += bytes; return q; };
     float *dy = carve(lines(std::max(dy_max, dz_max))), *dz = carve(lines(std::max(dy_max, dz_max)));

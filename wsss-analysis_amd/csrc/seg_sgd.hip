@@ -410,6 +410,8 @@ int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *pl
 int repack_launch(wsc_ctx *ctx, const RepackPlan &plan, const float *param) {
     const int fmt = conv_fmt(plan.prec), split = conv_split(plan.prec) != 0;
     WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, plan.bytes);
+    // (wsc_ctx_scratch_fill: the partial maxima are scratch of this call, kept by the grad object between calls)
+    if (ctx->scratch_fill >= 0 && plan.pmax) WSC_HIP(hipMemsetAsync(plan.pmax, ctx->scratch_fill, (size_t)plan.pmax_elems * sizeof(float), ctx->stream));
     if (plan.max_blocks > 0) {
         hipLaunchKernelGGL(repack_colmax_kernel, dim3(plan.max_blocks), dim3(256), 0, ctx->stream, plan.jobs_dev, plan.n_jobs, param, plan.pmax);
         WSC_HIP(hipGetLastError());

@@ -112,6 +112,8 @@ _SIGNATURES = {
     "wsc_memcpy_d2h": (_i, [_vp, _vp, _vp, _sz]),
     "wsc_memset": (_i, [_vp, _vp, _i, _sz]),
     "wsc_ctx_set_option": (_i, [_vp, _i, _i]),
+    "wsc_ctx_scratch_fill": (_i, [_vp, _i]),
+    "wsc_ctx_scratch_fill_value": (_i, [_vp]),
     "wsc_host_alloc": (_i, [_vp, _sz, ctypes.POINTER(_vp)]),
     "wsc_host_free": (_i, [_vp, _vp]),
     "wsc_host_write_segments": (_i, [ctypes.c_char_p, _i, ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
@@ -442,6 +444,26 @@ class Context:
                 self.set_option(option, before)
 
         return _cm()
+
+    def scratch_fill(self, value):
+        """Context manager (testing): inside the block the workspace arena and every cached scratch block this context hands to
+        a kernel hold the byte `value` (0 .. 255) instead of what the previous call left; the fill is off again afterwards,
+        whatever happened inside.  Results must not depend on it (wsc_ctx_scratch_fill)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def _cm():
+            check(self._lib.wsc_ctx_scratch_fill(self.h, int(value)))
+            try:
+                yield self
+            finally:
+                check(self._lib.wsc_ctx_scratch_fill(self.h, -1))
+
+        return _cm()
+
+    def scratch_fill_value(self):
+        """-1 (off) or the byte of the scratch fill that is on (wsc_ctx_scratch_fill_value)."""
+        return int(self._lib.wsc_ctx_scratch_fill_value(self.h))
 
     def profile_begin(self):
         check(self._lib.wsc_profile_begin(self.h))
