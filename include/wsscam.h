@@ -860,6 +860,92 @@ int wsc_irn_aff_loss(wsc_ctx *ctx, const float *edge_dev, const float *dp_dev, c
                      int valid_below, double *loss_dev /* [WSC_IRN_LOSS_N] */, float *grad_edge_dev /* or NULL */,
                      float *grad_dp_dev /* or NULL */);
 
+/* ---- 01_train: the loss head of the classifier with the gradient through the head, and the score side of predict() -----------
+ * wsc_cls_loss is model.compile(loss='binary_crossentropy', metrics=['binary_accuracy', f1]) (01_train/demo.py:60-61,
+ * utilities.py:69-97) on the head global pool -> Dense -> sigmoid, with the gradient of the loss through that head.  The backward
+ * pass through the plain stacks, BatchNorm in training mode, the Nesterov SGD / cyclic-LR step and the generators are not here.
+ *   feat_dev      float32 [B][n][F]  the NHWC map the head reduces, as wsc_net_forward_features writes it; n = h w
+ *   pool          WSC_CLS_POOL_MEAN: the mean over the n positions (VGG16);  WSC_CLS_POOL_MAX: their maximum (M7) -- the two
+ *                 cases of wsc_gap_linear_sigmoid
+ *   w_dev         float32 [C][F]     Dense weights;   bias_dev float32 [C] or NULL
+ *   target_dev    float32 [B][C]     targets z, 0/1
+ *   sample_w_host float32 [B] or NULL: per-sample weights w_b, NULL = ones; copied during the call
+ * With l the logit, p = sigmoid(l), eps = float32(1e-7) (K.epsilon()), hi = float32(1) - eps (a float32 subtraction: 1 - 2^-23)
+ * and p_c = clip(p, eps, hi):
+ *   l_b  = (1/C) sum_c -(z log p_c + (1 - z) log(1 - p_c))          the per-sample loss (K.mean(K.binary_crossentropy, axis=-1))
+ *   L    = sum_b w_b l_b / #{b : w_b != 0}                           Keras' weighted_masked_objective
+ *   n_equal = #{z == round(p)};  tp = sum round(z p);  possible = sum round(z);  predicted = sum round(p)
+ *   with round half to even, so p = 0.5 rounds to 0.  binary_accuracy = n_equal / (B C); recall = tp / (possible + 1e-7),
+ *   precision = tp / (predicted + 1e-7), f1 = 2 precision recall / (precision + recall + 1e-7): the caller forms the ratios.
+ * loss_dev double [WSC_CLS_LOSS_N], the slots below (the counts are integers held in doubles); score_dev float32 [B][C] =
+ * float32(p), optional.
+ * Gradients of L, each optional (NULL: not computed, the buffer is not touched), every element written:
+ *   g_l[b][c]     = (w_b / (C #{w != 0})) (p - z) where eps <= p <= hi, else +0.0 (TensorFlow's clip_by_value gradient)
+ *                 (a sample of weight 0 has g_l = +0.0 as well: its rows of grad_feat_dev are +0.0 to the bit)
+ *   grad_w_dev    float32 [C][F]     sum_b g_l[b][c] pooled[b][f]
+ *   grad_bias_dev float32 [C]        sum_b g_l[b][c]
+ *   grad_feat_dev float32 [B][n][F]  from g_pooled[b][f] = sum_c g_l[b][c] W[c][f]: mean pool g_pooled / n at every position; max
+ *                 pool g_pooled / (positions that hold the maximum) at each of them, +0.0 elsewhere
+ * TIE RULES: the share of a maximum is split EQUALLY among the positions that hold it (TensorFlow's reduce_max gradient, the
+ * rule of wsc_seg_loss); -0 counts as +0; NaN is out of contract.
+ * ARITHMETIC: inputs are float32; every sum, product, sigmoid and log runs in double and each output is rounded once.  p and
+ * 1 - p are both formed from exp(-|l|), so the sigmoid and log(1 - p_c) are stable for any finite logit.  Every floating-point sum
+ * has one fixed order (the pooled reduction: fixed chunks of positions, combined in chunk order) and there is no floating-point
+ * atomic: two calls give the same bits.  Keras evaluates the same graph in float32: parity with it is UNPINNED.  In particular
+ * what Keras does with the LIST class_weight of demo.py:80-82,107 is not reproduced: the interface takes per-sample weights only.
+ * Limits, checked before any launch (WSC_ERR_INVALID, the text names the argument): 1 <= B <= 1024, 1 <= C <= 64, F a multiple of
+ * 4 and <= 4096, 1 <= n <= 65536; a negative or non-finite weight, or no non-zero weight; no NULL among feat_dev, w_dev,
+ * target_dev, loss_dev; feat_dev, w_dev, grad_feat_dev and grad_w_dev 16-byte aligned; no output overlaps an input or another
+ * output.  Asynchronous on the ctx stream. */
+#define WSC_CLS_POOL_MEAN 0
+#define WSC_CLS_POOL_MAX 1
+enum {
+    WSC_CLS_LOSS_TOTAL = 0, /* L, the value Keras reports as `loss` */
+    WSC_CLS_LOSS_MEAN,      /* (1/B) sum_b l_b, unweighted */
+    WSC_CLS_LOSS_N_EQUAL,   /* #{z == round(p)} */
+    WSC_CLS_LOSS_TP,        /* sum round(z p) */
+    WSC_CLS_LOSS_POSSIBLE,  /* sum round(z) */
+    WSC_CLS_LOSS_PREDICTED, /* sum round(p) */
+    WSC_CLS_LOSS_N
+};
+int wsc_cls_loss(wsc_ctx *ctx, const float *feat_dev, int B, int n, int F, int pool /* WSC_CLS_POOL_MEAN | WSC_CLS_POOL_MAX */,
+                 const float *w_dev, const float *bias_dev /* or NULL */, int C, const float *target_dev,
+                 const float *sample_w_host /* [B] or NULL */, double *loss_dev /* [WSC_CLS_LOSS_N] */, float *score_dev /* or NULL */,
+                 float *grad_feat_dev /* or NULL */, float *grad_w_dev /* or NULL */, float *grad_bias_dev /* or NULL */);
+
+/* get_optimal_thresholds (01_train/utilities.py:99-114): per class the threshold of sklearn's roc_curve(drop_intermediate=True) at
+ * the first minimum of |tpr - (1 - fpr)|.  score_dev float32 [N][C], target_dev float32 [N][C] 0/1 (positive: == 1).  Per class:
+ *   1. the scores in their distinct values, descending (-0 counts as +0);
+ *   2. at the end of each group tps = positives so far, fps = (samples so far) - tps;
+ *   3. interior point i is dropped when fps[i-1] - 2 fps[i] + fps[i+1] and tps[i-1] - 2 tps[i] + tps[i+1] are both 0; the first
+ *      and the last point always stay;
+ *   4. ONLY THEN the point (0, 0) with threshold +inf is put in front.
+ *   tpr = tps / P, fpr = fps / Nn (double divisions, P / Nn the positive / negative samples); the threshold is the one at the
+ *   FIRST minimum of |tpr - (1 - fpr)|, evaluated in double in exactly that order.
+ * A class without a positive or without a negative sample returns +inf and sets WSC_ROC_NO_POSITIVE / WSC_ROC_NO_NEGATIVE in
+ * status_dev[c] (sklearn yields NaN rates there and argmin returns 0); a class whose scores are all equal returns +inf too (both
+ * points are at distance 1).  thresh_dev float32 [C], status_dev int32 [C]; optional: n_points_dev int32 [C] (the kept points, the
+ * one in front included) and, together, fps_dev / tps_dev int32 [C][N + 1] (zeros behind the kept points) -- class_fprs /
+ * class_tprs are these over Nn / P.  Every output is an integer or a copy of an input score: exact.
+ * Limits, checked before any launch (WSC_ERR_INVALID): 1 <= N <= 16384 (a class is sorted in LDS; beyond 64 KiB the launch limit
+ * is raised first and a refusal fails the call), 1 <= C <= 64.  NaN is out of contract.  Asynchronous on the ctx stream. */
+#define WSC_ROC_NO_POSITIVE 1
+#define WSC_ROC_NO_NEGATIVE 2
+int wsc_roc_thresholds(wsc_ctx *ctx, const float *score_dev, const float *target_dev, int N, int C, float *thresh_dev,
+                       int32_t *status_dev, int32_t *n_points_dev /* or NULL */, int32_t *fps_dev /* or NULL */,
+                       int32_t *tps_dev /* or NULL */);
+
+/* The counts of get_thresholded_metrics_class / _overall (utilities.py:118-165) with pred = score >= thresh_dev[c] (float32
+ * comparison; thresh_dev float32 [C] on the device, +inf allowed): counts_dev int64 [C][WSC_CLS_COUNT_N] = TP (target == 1 and
+ * pred), FP (target == 0 and pred), TN, FN and #{target == pred}; the caller forms the ratios, per class and from the sums over
+ * the classes.  Integer atomics: exact whatever the order.  1 <= N <= 16384, 1 <= C <= 64.  Asynchronous on the ctx stream.
+ * wsc_cls_scores_append copies elems floats from src_dev to dst_dev on the stream (the batches of a prediction pass into one
+ * [N][C] array); the two must not overlap. */
+enum { WSC_CLS_COUNT_TP = 0, WSC_CLS_COUNT_FP, WSC_CLS_COUNT_TN, WSC_CLS_COUNT_FN, WSC_CLS_COUNT_EQUAL, WSC_CLS_COUNT_N };
+int wsc_cls_threshold_counts(wsc_ctx *ctx, const float *score_dev, const float *target_dev, int N, int C, const float *thresh_dev,
+                             int64_t *counts_dev /* [C][WSC_CLS_COUNT_N] */);
+int wsc_cls_scores_append(wsc_ctx *ctx, const float *src_dev, long long elems, float *dst_dev);
+
 /* ---- backward pass of the IRNet heads: total_loss.backward() of step/train_irn.py:127 ------------------------------------------
  * Net.forward detaches every backbone stage (resnet50_irn.py:111-115) and trainable_parameters() is edge_layers + dp_layers, so
  * the gradient of the heads is the whole gradient of a step.  wsc_irn_aff_loss hands out d total / d edge_out and d total /

@@ -260,6 +260,14 @@ template <int NV> __device__ __forceinline__ void block_sum(double (&v)[NV], dou
     }
 }
 
+// float -> uint32 whose unsigned order is the float order (-0 counts as +0: equal values must tie), and back: the sort keys of
+// seg_loss.hip and cls_head.hip
+__device__ __forceinline__ uint32_t float_order_bits(float v) {
+    const uint32_t u = __float_as_uint(v + 0.f);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float float_from_order_bits(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
+
 // Raises the dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) of kernel `fn` to `bytes`, once per (function,
 // ctx device), under a lock: the lane threads of the drivers reach the launch sites at the same time.  WSC_ERR_HIP with the
 // error text when the runtime refuses; a failure is not recorded, so the next call tries again.

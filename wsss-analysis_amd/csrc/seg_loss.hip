@@ -50,12 +50,7 @@ enum { SL_P_SEED_BG = 0, SL_P_SEED_FG, SL_P_CNT_BG, SL_P_CNT_FG, SL_P_CONSTRAIN,
 
 // (block_sum, the workgroup sum every kernel here ends in: common.h; scratch: SL_MAX_WAVES * NV doubles)
 
-// float -> uint32 whose unsigned order is the float order (-0 counts as +0: equal values must tie)
-__device__ __forceinline__ uint32_t sl_order_bits(float v) {
-    const uint32_t u = __float_as_uint(v + 0.f);
-    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float sl_from_order_bits(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
+// (float_order_bits / float_from_order_bits, the order-preserving key of a value: common.h)
 
 // grid (C, B).  LDS: uint64 key[P], then block_sum's scratch.
 __global__ __launch_bounds__(SL_SORT_THREADS) void seg_loss_rank_kernel(const float *__restrict__ prob, int n, int P, int C,
@@ -68,7 +63,7 @@ __global__ __launch_bounds__(SL_SORT_THREADS) void seg_loss_rank_kernel(const fl
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const float *src = prob + (size_t)b * n * C + c;
     for (int i = tid; i < P; i += SL_SORT_THREADS)
-        key[i] = i < n ? ((unsigned long long)sl_order_bits(src[(size_t)i * C]) << 32) | (unsigned)i : ~0ull; // padding sorts last
+        key[i] = i < n ? ((unsigned long long)float_order_bits(src[(size_t)i * C]) << 32) | (unsigned)i : ~0ull; // padding sorts last
     __syncthreads();
     for (int k = 2; k <= P; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -90,14 +85,14 @@ __global__ __launch_bounds__(SL_SORT_THREADS) void seg_loss_rank_kernel(const fl
         const unsigned long long k = key[i];
         const uint32_t bits = (uint32_t)(k >> 32);
         r[(uint32_t)k] = (uint16_t)i; // (uint32_t)k < n: a pixel index
-        acc[0] += (double)sl_from_order_bits(bits) * (double)w[i];
+        acc[0] += (double)float_from_order_bits(bits) * (double)w[i];
         acc[1] += bits == top ? 1.0 : 0.0;
     }
     block_sum<2>(acc, scratch);
     if (tid == 0) {
         SlMapStat s;
         s.mean = acc[0] / (c ? z_fg : z_bg);
-        s.vmax = (double)sl_from_order_bits(top);
+        s.vmax = (double)float_from_order_bits(top);
         s.log_mean = log(s.mean);
         s.log_rest = log(1.0 - s.vmax);
         s.ties = (int)acc[1];

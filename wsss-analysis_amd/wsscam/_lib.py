@@ -137,6 +137,10 @@ _SIGNATURES = {
     "wsc_net_edge_size": (_i, [_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "wsc_net_forward_edge_raw": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "wsc_irn_aff_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "wsc_cls_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wsc_roc_thresholds": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "wsc_cls_threshold_counts": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "wsc_cls_scores_append": (_i, [_vp, _vp, ctypes.c_longlong, _vp]),
     "wsc_net_edge_tape_plan": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_forward_edge_tape": (_i, [_vp, _vp, _vp, _i, _i, _vp, ctypes.c_longlong, _vp, _vp]),
     "wsc_irn_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
@@ -1505,6 +1509,47 @@ def irn_aff_loss(ctx, edge_dev, dp_dev, label_dev, B, h, w, dirs, path_start, pa
     check(ctx._lib.wsc_irn_aff_loss(ctx.h, _ptr(edge_dev), _ptr(dp_dev), _ptr(label_dev), int(B), int(h), int(w), _ptr(dirs),
                                     _ptr(path_start), _ptr(path_yx), int(dirs.shape[0]), int(radius_floor), int(valid_below),
                                     _ptr(loss_dev), _ptr(grad_edge_dev), _ptr(grad_dp_dev)))
+
+
+CLS_POOL_MEAN, CLS_POOL_MAX = 0, 1
+# slots of wsc_cls_loss's loss_dev (include/wsscam.h WSC_CLS_LOSS_*)
+CLS_LOSS_SLOTS = ("loss", "mean_loss", "n_equal", "tp", "possible", "predicted")
+ROC_NO_POSITIVE, ROC_NO_NEGATIVE = 1, 2
+# columns of wsc_cls_threshold_counts's counts_dev (WSC_CLS_COUNT_*)
+CLS_COUNT_SLOTS = ("tp", "fp", "tn", "fn", "equal")
+
+
+def cls_loss(ctx, feat_dev, B, n, F, pool, w_dev, bias_dev, C, target_dev, sample_weight, loss_dev, score_dev=None, grad_feat_dev=None,
+             grad_w_dev=None, grad_bias_dev=None):
+    """wsc_cls_loss: binary cross-entropy and the metric counts of the classifier head (float64 [len(CLS_LOSS_SLOTS)] in loss_dev) on
+    feat_dev float32 [B][n][F], w_dev [C][F], bias_dev [C] or None, target_dev [B][C]; sample_weight: host float32 [B] or None; where
+    a buffer is given, the scores [B][C] and the gradients of the loss (feat [B][n][F], w [C][F], bias [C]); asynchronous."""
+    sw = None
+    if sample_weight is not None:
+        sw = np.ascontiguousarray(sample_weight, dtype=np.float32)
+        if sw.shape != (int(B),):
+            raise ValueError("cls_loss: sample_weight of shape %r for %d samples" % (sw.shape, B))
+    check(ctx._lib.wsc_cls_loss(ctx.h, _ptr(feat_dev), int(B), int(n), int(F), int(pool), _ptr(w_dev), _ptr(bias_dev), int(C),
+                                _ptr(target_dev), _ptr(sw), _ptr(loss_dev), _ptr(score_dev), _ptr(grad_feat_dev), _ptr(grad_w_dev),
+                                _ptr(grad_bias_dev)))
+
+
+def roc_thresholds(ctx, score_dev, target_dev, N, C, thresh_dev, status_dev, n_points_dev=None, fps_dev=None, tps_dev=None):
+    """wsc_roc_thresholds: per class the roc_curve threshold at the first minimum of |tpr - (1 - fpr)| (float32 [C]) and the status
+    bits (int32 [C]) of score_dev / target_dev float32 [N][C]; optionally the kept curve, n_points int32 [C] and fps / tps int32
+    [C][N + 1]; asynchronous."""
+    check(ctx._lib.wsc_roc_thresholds(ctx.h, _ptr(score_dev), _ptr(target_dev), int(N), int(C), _ptr(thresh_dev), _ptr(status_dev),
+                                      _ptr(n_points_dev), _ptr(fps_dev), _ptr(tps_dev)))
+
+
+def cls_threshold_counts(ctx, score_dev, target_dev, N, C, thresh_dev, counts_dev):
+    """wsc_cls_threshold_counts: counts_dev int64 [C][len(CLS_COUNT_SLOTS)] of score_dev >= thresh_dev[c] against target_dev."""
+    check(ctx._lib.wsc_cls_threshold_counts(ctx.h, _ptr(score_dev), _ptr(target_dev), int(N), int(C), _ptr(thresh_dev), _ptr(counts_dev)))
+
+
+def cls_scores_append(ctx, src_dev, elems, dst_dev):
+    """wsc_cls_scores_append: elems floats from src_dev to dst_dev, on the stream."""
+    check(ctx._lib.wsc_cls_scores_append(ctx.h, _ptr(src_dev), int(elems), _ptr(dst_dev)))
 
 
 def cue_maps(ctx, cams_nhwc_dev, B, h, w, C_all, chan, gate_dev, S, out_dev):

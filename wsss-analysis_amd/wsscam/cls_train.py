@@ -1,0 +1,272 @@
+"""01_train mirror on libwsscam: the loss head of the classifier and the score side of predict().
+
+    ClsLoss          model.compile(loss='binary_crossentropy', metrics=['binary_accuracy', f1]) (01_train/demo.py:60-61,
+                     utilities.py:69-97) on the head global pool -> Dense -> sigmoid, and the gradient of the loss through that head
+                     (wsc_cls_loss; the formulas, the tie rule and the double arithmetic: include/wsscam.h)
+    ScoreEvaluator   get_optimal_thresholds, get_thresholded_metrics_class, get_thresholded_metrics_overall (utilities.py:99-165)
+                     on scores that stay on the device (wsc_roc_thresholds, wsc_cls_threshold_counts)
+    predict          the score side of demo.py:167-205: thresholds from the validation scores, written as optimalScoreThresh into
+                     <sess_id>.mat -- the file net.common.load_pretrained and keras_store.load_model read --, metrics on the split
+                     `eval_on` names
+
+Not here: the backward pass through the plain stacks, BatchNorm in training mode, the Nesterov SGD /
+cyclic-LR step and the data generators (the reference's data_loader.py / model_loader.py are missing).  Keras evaluates the loss in
+float32, and what it does with the LIST class_weight of demo.py:80-82,107 is not reproduced: ClsLoss takes per-sample weights."""
+import collections
+import os
+
+import numpy as np
+
+from . import _lib
+from .misc.imutils import default_context
+from .secdsrg import DeviceMaps
+
+K_EPSILON = 1e-7  # K.epsilon()
+POOLS = {"mean": _lib.CLS_POOL_MEAN, "max": _lib.CLS_POOL_MAX}
+MAX_SCORES = 16384  # wsc_roc_thresholds sorts a class in LDS
+
+HeadGrads = collections.namedtuple("HeadGrads", "feat w bias")  # float32 DeviceMaps (B, n, F), (C, F), (C,)
+
+
+def keras_metrics(values, n_elems):
+    """The six values of wsc_cls_loss on B C = n_elems targets -> {'loss', 'mean_loss', 'binary_accuracy', 'f1', 'counts'}:
+    binary_accuracy = K.mean(K.equal(y_true, K.round(y_pred))) and f1 formed from the counts exactly as utilities.py:69-97 writes
+    it."""
+    v = dict(zip(_lib.CLS_LOSS_SLOTS, (float(x) for x in values)))
+    counts = {k: int(v[k]) for k in ("n_equal", "tp", "possible", "predicted")}
+    recall = counts["tp"] / (counts["possible"] + K_EPSILON)
+    precision = counts["tp"] / (counts["predicted"] + K_EPSILON)
+    return {"loss": v["loss"], "mean_loss": v["mean_loss"], "counts": counts, "binary_accuracy": counts["n_equal"] / float(n_elems),
+            "f1": 2 * ((precision * recall) / (precision + recall + K_EPSILON))}
+
+
+class ClsLoss:
+    """loss = ClsLoss(ctx, "mean" | "max", num_classes)          ("mean": the VGG16 head, "max": M7's)
+    loss.loss_step(feat, w, bias, targets, sample_weight=None) -> {'loss', 'mean_loss', 'binary_accuracy', 'f1', 'counts'}
+    loss.grad_step(...)                                        -> (that dict, HeadGrads(feat, w, bias))
+      feat     (B, h, w, F) or (B, n, F): the map the head reduces (wsc_net_forward_features); w (C, F); bias (C,) or None;
+               targets (B, C) 0/1 -- float32 DeviceMaps, read in place, or host arrays, uploaded once
+      sample_weight  host (B,) or None (ones): 'loss' = sum_b w_b l_b / #{w_b != 0}; 'mean_loss' is the unweighted mean
+      'counts' {'n_equal', 'tp', 'possible', 'predicted'}: the integers behind the two metrics
+    The gradients are new float32 DeviceMaps the caller frees.  A call downloads the six loss values and nothing else."""
+
+    def __init__(self, ctx, pool, num_classes):
+        if pool not in POOLS:
+            raise ValueError("ClsLoss: pool %r is neither 'mean' nor 'max'" % (pool,))
+        self.ctx = ctx or default_context()
+        self.pool = POOLS[pool]
+        self.C = int(num_classes)
+        if not 1 <= self.C <= 64:
+            raise ValueError("ClsLoss: num_classes = %d (1 .. 64)" % self.C)
+
+    def _maps(self, name, a, shape, held):
+        if isinstance(a, DeviceMaps):
+            if a.dtype != np.float32:
+                raise ValueError("ClsLoss: %s is %s on the device, not float32" % (name, a.dtype))
+        else:
+            a = np.asarray(a)
+            if a.dtype.kind not in "fiub":
+                raise ValueError("ClsLoss: %s has dtype %s, not a real number type" % (name, a.dtype))
+        if shape is not None and tuple(a.shape) != tuple(shape):
+            raise ValueError("ClsLoss: %s has shape %r, expected %r" % (name, tuple(a.shape), tuple(shape)))
+        if isinstance(a, DeviceMaps):
+            return a
+        held.append(DeviceMaps.from_host(self.ctx, a, dtype=np.float32))
+        return held[-1]
+
+    def _run(self, feat, w, bias, targets, sample_weight, want_grad):
+        ctx, held, grads = self.ctx, [], None
+        try:
+            f = self._maps("feat", feat, None, held)
+            if len(f.shape) not in (3, 4) or 0 in f.shape:
+                raise ValueError("ClsLoss: feat has shape %r, expected (B, h, w, F) or (B, n, F)" % (f.shape,))
+            B, F = f.shape[0], f.shape[-1]
+            n = int(np.prod(f.shape[1:-1]))
+            wd = self._maps("w", w, (self.C, F), held)
+            bd = None if bias is None else self._maps("bias", bias, (self.C,), held)
+            t = self._maps("targets", targets, (B, self.C), held)
+            loss_dev = DeviceMaps(ctx, (len(_lib.CLS_LOSS_SLOTS),), np.float64)
+            held.append(loss_dev)
+            if want_grad:
+                grads = HeadGrads(DeviceMaps(ctx, f.shape), DeviceMaps(ctx, (self.C, F)), DeviceMaps(ctx, (self.C,)))
+            _lib.cls_loss(ctx, f.ptr, B, n, F, self.pool, wd.ptr, None if bd is None else bd.ptr, self.C, t.ptr, sample_weight,
+                          loss_dev.ptr, grad_feat_dev=grads.feat.ptr if grads else None, grad_w_dev=grads.w.ptr if grads else None,
+                          grad_bias_dev=grads.bias.ptr if grads else None)
+            return keras_metrics(loss_dev.to_host(), B * self.C), grads
+        except Exception:
+            for d in grads or ():
+                d.free()
+            raise
+        finally:
+            for d in held:
+                d.free()
+
+    def loss_step(self, feat, w, bias, targets, sample_weight=None):
+        return self._run(feat, w, bias, targets, sample_weight, False)[0]
+
+    def grad_step(self, feat, w, bias, targets, sample_weight=None):
+        return self._run(feat, w, bias, targets, sample_weight, True)
+
+
+def threshold_ratios(counts, n_samples):
+    """int64 (C, 5) [TP, FP, TN, FN, #{target == prediction}] of n_samples samples -> {'class': {...}, 'overall': {...}} with the
+    keys tpr, fpr, tnr, fnr, acc, f1: the ratios of utilities.py:132-138 per class and :157-163 over all classes.  An empty
+    denominator gives nan, as numpy's division does there."""
+    c = np.asarray(counts, np.int64).reshape(-1, len(_lib.CLS_COUNT_SLOTS))
+
+    def ratios(tp, fp, tn, fn, eq, total):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pos, neg = tp + fn, fp + tn  # cond_positive, cond_negative
+            return {"tpr": tp / pos, "fpr": fp / neg, "tnr": tn / neg, "fnr": fn / pos, "acc": eq / np.float64(total),
+                    "f1": (2 * tp) / (2 * tp + fp + fn)}
+
+    cols = [c[:, k].astype(np.float64) for k in range(c.shape[1])]
+    tot = [np.float64(c[:, k].sum()) for k in range(c.shape[1])]
+    return {"class": ratios(*cols, int(n_samples)), "overall": ratios(*tot, int(n_samples) * c.shape[0])}
+
+
+class ScoreEvaluator:
+    """The scores and targets of a prediction pass, kept on the device, and what predict() derives from them.
+
+    ev = ScoreEvaluator(ctx, num_classes)
+    ev.update(scores, targets)     scores (b, C): a float32 DeviceMaps / device buffer (the score_dev of a forward pass), copied on
+                                   the device, or a host array; targets (b, C) 0/1 host array.  At most 16384 samples in all.
+    ev.thresholds() -> float32 (C,)      get_optimal_thresholds: roc_curve's threshold at the first minimum of |tpr - (1 - fpr)|,
+                                   +inf for a class without positives or negatives (ev.status: ROC_NO_POSITIVE / ROC_NO_NEGATIVE bits)
+    ev.curves() -> [(fprs, tprs)] per class, the arrays roc_curve returns (class_fprs / class_tprs)
+    ev.metrics(thresholds) -> threshold_ratios' dict, plus 'counts' int64 (C, 5)"""
+
+    def __init__(self, ctx, num_classes):
+        self.ctx = ctx or default_context()
+        self.C = int(num_classes)
+        if not 1 <= self.C <= 64:
+            raise ValueError("ScoreEvaluator: num_classes = %d (1 .. 64)" % self.C)
+        self.N = 0
+        self.status = None
+        self._scores = DeviceMaps(self.ctx, (MAX_SCORES, self.C))
+        self._targets = DeviceMaps(self.ctx, (MAX_SCORES, self.C))
+
+    def close(self):
+        self._scores.free()
+        self._targets.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def update(self, scores, targets):
+        t = np.ascontiguousarray(targets, dtype=np.float32)
+        if t.ndim != 2 or t.shape[1] != self.C:
+            raise ValueError("ScoreEvaluator: targets have shape %r, expected (b, %d)" % (t.shape, self.C))
+        b = t.shape[0]
+        if self.N + b > MAX_SCORES:
+            raise ValueError("ScoreEvaluator: %d + %d samples, at most %d" % (self.N, b, MAX_SCORES))
+        if b == 0:
+            return
+        lib, ctx, at = self.ctx._lib, self.ctx, 4 * self.N * self.C
+        if isinstance(scores, np.ndarray) or isinstance(scores, (list, tuple)):
+            s = np.ascontiguousarray(scores, dtype=np.float32)
+            if s.shape != t.shape:
+                raise ValueError("ScoreEvaluator: scores have shape %r, targets %r" % (s.shape, t.shape))
+            _lib.check(lib.wsc_memcpy_h2d(ctx.h, self._scores.ptr + at, s.ctypes.data, s.nbytes))
+        else:
+            if isinstance(scores, DeviceMaps) and (scores.dtype != np.float32 or int(np.prod(scores.shape)) != b * self.C):
+                raise ValueError("ScoreEvaluator: scores are %s %r on the device, expected float32 (%d, %d)"
+                                 % (scores.dtype, scores.shape, b, self.C))
+            _lib.cls_scores_append(ctx, scores.ptr if isinstance(scores, DeviceMaps) else scores, b * self.C, self._scores.ptr + at)
+        _lib.check(lib.wsc_memcpy_h2d(ctx.h, self._targets.ptr + at, t.ctypes.data, t.nbytes))
+        ctx.sync()  # the host arrays may be temporaries
+        self.N += b
+
+    def _roc(self, curves):
+        if self.N < 1:
+            raise ValueError("ScoreEvaluator: no scores yet")
+        ctx, C, N = self.ctx, self.C, self.N
+        with DeviceMaps(ctx, (C,), np.float32) as thr, DeviceMaps(ctx, (C,), np.int32) as status, \
+                DeviceMaps(ctx, (C,), np.int32) as n_points, DeviceMaps(ctx, (C, N + 1), np.int32) as fps, \
+                DeviceMaps(ctx, (C, N + 1), np.int32) as tps:
+            _lib.roc_thresholds(ctx, self._scores.ptr, self._targets.ptr, N, C, thr.ptr, status.ptr, n_points.ptr,
+                                fps.ptr if curves else None, tps.ptr if curves else None)
+            self.status = status.to_host()
+            if not curves:
+                return thr.to_host(), n_points.to_host(), None, None
+            return thr.to_host(), n_points.to_host(), fps.to_host(), tps.to_host()
+
+    def thresholds(self):
+        return self._roc(False)[0]
+
+    def curve_points(self):
+        """-> (thresholds float32 (C,), n_points int32 (C,), fps, tps int32 (C, N + 1)): the kept points as integers"""
+        return self._roc(True)
+
+    def curves(self):
+        _, n_points, fps, tps = self._roc(True)
+        out = []
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for c in range(self.C):
+                k = int(n_points[c])
+                out.append((fps[c, :k] / np.float64(fps[c, k - 1]), tps[c, :k] / np.float64(tps[c, k - 1])))
+        return out
+
+    def metrics(self, thresholds):
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+        if thr.shape != (self.C,):
+            raise ValueError("ScoreEvaluator: %d thresholds for %d classes" % (thr.size, self.C))
+        if self.N < 1:
+            raise ValueError("ScoreEvaluator: no scores yet")
+        ctx = self.ctx
+        with DeviceMaps.from_host(ctx, thr) as td, DeviceMaps(ctx, (self.C, len(_lib.CLS_COUNT_SLOTS)), np.int64) as cd:
+            _lib.cls_threshold_counts(ctx, self._scores.ptr, self._targets.ptr, self.N, self.C, td.ptr, cd.ptr)
+            counts = cd.to_host()
+        out = threshold_ratios(counts, self.N)
+        out["counts"] = counts
+        return out
+
+
+def write_thresholds(model_dir, sess_id, thresholds):
+    """<model_dir>/<sess_id>.mat with optimalScoreThresh = the LIST of thresholds (demo.py:189-192: scipy.io.savemat makes it a
+    (1, C) array, which net.common.load_pretrained and keras_store.load_model index) -> the path"""
+    import scipy.io
+
+    os.makedirs(model_dir, exist_ok=True)
+    mat_path = os.path.join(model_dir, sess_id + ".mat")
+    scipy.io.savemat(mat_path, {"optimalScoreThresh": list(thresholds)})
+    return mat_path
+
+
+def predict(score_batches_val, score_batches_test, model_dir, sess_id, eval_on, ctx=None):
+    """The score side of predict() (01_train/demo.py:167-205).
+
+    score_batches_val / score_batches_test: iterables of (scores, targets) batches as ScoreEvaluator.update takes them -- the scores
+    of the existing forward passes (the score_dev of wsc_net_forward_cam / wsc_gap_linear_sigmoid), the targets of the split.
+    The optimal thresholds of the validation scores go to <model_dir>/<sess_id>.mat as optimalScoreThresh (scipy.io.savemat of the
+    list, so a (1, C) array: what load_pretrained and load_model index); the metrics are those of the split eval_on names, 'val'
+    (VOC2012) or 'test' (ADP, DeepGlobe).  -> {'thresholds' float32 (C,), 'status', 'class': {...}, 'overall': {...}, 'counts',
+    'curves' [(fprs, tprs)] of the evaluated split, 'mat_path'}.
+    Out of scope: the .xlsx writer, the ROC plot, the X1.7 class subset and the generators."""
+    if eval_on not in ("val", "test"):
+        raise ValueError("predict: eval_on %r is neither 'val' nor 'test'" % (eval_on,))
+    ctx = ctx or default_context()
+    evs = {}
+    try:
+        for split, batches in (("val", score_batches_val), ("test", score_batches_test)):
+            if split == "test" and eval_on != "test":
+                continue
+            for scores, targets in batches:
+                if split not in evs:
+                    evs[split] = ScoreEvaluator(ctx, np.asarray(targets).shape[1])
+                evs[split].update(scores, targets)
+        if "val" not in evs or eval_on not in evs:
+            raise ValueError("predict: no %s batches" % ("val" if "val" not in evs else eval_on))
+        thresholds = evs["val"].thresholds()
+        status = evs["val"].status
+        mat_path = write_thresholds(model_dir, sess_id, thresholds)
+        out = evs[eval_on].metrics(thresholds)
+        out.update(thresholds=thresholds, status=status, curves=evs[eval_on].curves(), mat_path=mat_path)
+        return out
+    finally:
+        for ev in evs.values():
+            ev.close()
