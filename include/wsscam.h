@@ -48,7 +48,15 @@ typedef enum wsc_status {
                                  saturated: the reference's fp32 (03b_irn/net/resnet50.py:11-14) has no such ceiling, so the maps
                                  of this ctx are NOT the reference's.  Sticky: returned by wsc_sync / wsc_memcpy_d2h until
                                  wsc_ctx_range_status(ctx, &f, 1) clears it.  Run the model in WSC_PREC_F32, the exact fallback, instead
-                                 (WSC_PREC_BF16X3 also has fp32's range, with a 16-bit significand) */
+                                 (WSC_PREC_BF16X3 also has fp32's range, with a 16-bit significand).
+                                 NaN and inf: a non-finite element given to a network-path entry point is either LOUD -- this
+                                 status from the call, with a text that names the cause (a non-finite state-dict tensor at
+                                 wsc_net_create, a non-finite weight / scale / shift of an IEEE-half layer), or the same sticky flag,
+                                 raised by the fp32 -> activation packs, the device repack and the GroupNorm store -- or it
+                                 PROPAGATES: every cell that is non-finite in the reference is non-finite on the device.  Never a
+                                 plausible finite map.  Which one per entry point and precision: DESIGN.md section 5, "NaN and
+                                 inf".  Every whole-net forward and every IEEE-half entry is loud; the single-layer entries in
+                                 bf16 / bf16x3 / f32, the fp32 gradient kernels, wsc_cls_loss and the SGD steps propagate */
 } wsc_status;
 
 /* architectures: 03b_irn/net/{resnet50_cam,vgg16_cam,m7_cam}.py */

@@ -49,9 +49,11 @@ def cls_loss(feat, kind, w, bias, target, sample_w=None):
     ell = term.sum(axis=1) / C
     rp = np.rint(p)  # half to even
     values = {"loss": float((wts * ell).sum() / nz), "mean_loss": float(ell.sum() / B), "n_equal": int((z == rp).sum()),
-              "tp": int(np.rint(z * p).sum()), "possible": int(np.rint(z).sum()), "predicted": int(rp.sum())}
+              "tp": int(np.nansum(np.rint(z * p))), "possible": int(np.rint(z).sum()), "predicted": int(np.nansum(rp))}
+    # (nansum: a NaN score has no rounding, the counts then cover the other cells -- the losses and the gradients are what carries it)
     mag = {"loss": float((wts[:, None] * np.abs(term)).sum() / (C * nz)), "mean_loss": float(np.abs(term).sum() / (C * B))}
     g_l = np.where((p >= EPS) & (p <= HI), (wts / (C * nz))[:, None] * (p - z), 0.0) + 0.0  # (+0.0 under a zero weight as well)
+    g_l = np.where(np.isnan(p), p, g_l)  # (the clip's mask is false for a NaN, but what it gates is the sigmoid's NaN derivative times 0)
     g_pooled = g_l @ w
     if kind == "max":
         at_max = (feat + 0.0) == pooled[:, None, :]

@@ -180,8 +180,10 @@ int wsc_ctx_range_check(wsc_ctx *ctx) {
     const unsigned f = *(volatile unsigned *)ctx->range_host;
     if (f == 0u) return WSC_OK;
     wsc_set_error("an activation of an IEEE-half conv mode (f16 / f16x3) reached half's ceiling (|v| >= 65504) in a layer with %u "
-                  "output channels and was saturated -- the reference's fp32 would have kept it, these maps are not the reference's; "
-                  "use WSC_PREC_F32, the exact fp32 mode, for this model (wsc_ctx_range_status clears the flag)", f);
+                  "output channels and was saturated -- the reference's fp32 would have kept it, these maps are not the reference's: "
+                  "a model that saturates runs in WSC_PREC_F32, the exact fp32 mode.  Or a tensor of %u channels given to a network, a "
+                  "layer or a parameter load held NaN / inf: no precision helps then, the input or the parameters are wrong "
+                  "(wsc_ctx_range_status clears the flag)", f, f);
     return WSC_ERR_RANGE;
 }
 

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256, 2) void cam_head_kernel(HeadArgs p) {
         if (c < p.C && m < p.M) {
             float v = ((red[0][row][c] + red[1][row][c]) + red[2][row][c]) + red[3][row][c];
             v = v * p.s1[c] + p.b1[c];
-            if (p.relu) v = fmaxf(v, 0.f);
+            if (p.relu) v = relu_keep_nan(v);
             p.y[(long long)m * p.C + c] = v;
         }
     }

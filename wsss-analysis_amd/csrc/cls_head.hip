@@ -56,7 +56,7 @@ __device__ __forceinline__ void ch_unpack(double d, float *v, int *cnt) {
 }
 __device__ __forceinline__ void ch_max_join(float &mv, int &mc, float v, int cnt) {
     mc = v > mv ? cnt : (v == mv ? mc + cnt : mc);
-    mv = fmaxf(mv, v);
+    mv = max_keep_nan(mv, v); // (a NaN position makes the maximum NaN, as MaxPooling2D's does)
 }
 
 // grid (S, ceil(F / CH_TILE_F), B); partial [B][S][F]
@@ -167,11 +167,15 @@ __global__ __launch_bounds__(CH_DENSE_THREADS) void cls_dense_kernel(const doubl
         const double l = term[c] + (bias ? (double)bias[c] : 0.0), z = (double)target[(size_t)b * C + c];
         double p, q;
         ch_sigmoid(l, &p, &q);
-        const double pc = fmin(fmax(p, eps), hi), qc = fmin(fmax(q, 1.0 - hi), 1.0 - eps); // qc = 1 - pc
+        // (a NaN score stays NaN through the clip, as K.clip's does: fmin / fmax would return the bound, a finite loss and a zero
+        // gradient for a diverged model)
+        const bool nan = p != p;
+        const double pc = nan ? p : fmin(fmax(p, eps), hi), qc = nan ? p : fmin(fmax(q, 1.0 - hi), 1.0 - eps); // qc = 1 - pc
         term[c] = -(z * log(pc) + (1.0 - z) * log(qc));
-        gl[c] = (p >= eps && p <= hi) ? cf * (p - z) + 0.0 : 0.0; // (+ 0.0: a zero weight gives +0.0 too, never -0.0)
+        gl[c] = nan ? p : ((p >= eps && p <= hi) ? cf * (p - z) + 0.0 : 0.0); // (+ 0.0: a zero weight gives +0.0 too, never -0.0)
         const double rp = rint(p); // half to even: 0.5 -> 0
-        flags[c] = (z == rp ? 1 : 0) | (rint(z * p) != 0.0 ? 2 : 0) | (rint(z) != 0.0 ? 4 : 0) | (rp != 0.0 ? 8 : 0);
+        // (a NaN score has no rounding: it counts as neither equal, true positive nor predicted -- NaN != 0.0 is true)
+        flags[c] = nan ? (rint(z) != 0.0 ? 4 : 0) : (z == rp ? 1 : 0) | (rint(z * p) != 0.0 ? 2 : 0) | (rint(z) != 0.0 ? 4 : 0) | (rp != 0.0 ? 8 : 0);
         if (score) score[(size_t)b * C + c] = (float)p;
         gl_out[(size_t)b * C + c] = gl[c];
     }

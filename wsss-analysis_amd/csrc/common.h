@@ -33,6 +33,9 @@ __host__ __device__ inline float bf16_to_f32(bf16_t h) {
 }
 
 // ---- IEEE half helpers: round-to-nearest-even, SATURATING at +-65504 (no infinities) -------
+// NaN: the host form keeps it (0x7e00), the device form stores -65504 (fmaxf / fminf return the other operand) -- at the ceiling,
+// so every site that tests half2_at_ceiling or |v| < 65504 flags it.  They need not agree: no NaN passes the host form, make_conv
+// rejects a non-finite weight, scale or shift of an IEEE-half model before it packs.
 __host__ __device__ inline uint16_t f32_to_f16(float f) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const _Float16 h = (_Float16)fminf(fmaxf(f, -65504.f), 65504.f);
@@ -78,6 +81,11 @@ __host__ __device__ inline float f16_to_f32(uint16_t h) {
 // 16-bit storage format of activations / weights: 0 = bfloat16, 1 = IEEE half
 __host__ __device__ inline uint16_t f32_to_h16(float f, int fmt) { return fmt ? f32_to_f16(f) : f32_to_bf16(f); }
 __host__ __device__ inline float h16_to_f32(uint16_t h, int fmt) { return fmt ? f16_to_f32(h) : bf16_to_f32(h); }
+
+// ReLU and maximum that carry a NaN like torch / TensorFlow do (fmaxf returns the other operand): what the bf16, bf16x3 and fp32
+// paths propagate, and what keeps a NaN in front of the saturating half conversion where it is flagged
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return (b > a || b != b) ? b : a; }
 
 // ---- error plumbing -----------------------------------------------------------
 void wsc_set_error(const char *fmt, ...);
@@ -190,7 +198,11 @@ int wsc_ctx_workspace(wsc_ctx *ctx, size_t bytes, void **out);
 // WSC_ERR_RANGE (with the error text) when the ctx's range flag is raised; the stream must have been synchronised
 int wsc_ctx_range_check(wsc_ctx *ctx);
 // One packed pair of IEEE halves as the saturation test of an epilogue: bit 15 / 31 of the result is set iff the low / high
-// half's magnitude is >= 0x7bff (65504: the value the saturating conversion stores for anything beyond, and NaN / inf)
+// half's magnitude is >= 0x7bff (65504: the value the saturating conversion stores for anything beyond, +-inf included; a half
+// NaN or inf pattern, which no conversion of this library stores, tests true as well).  An fp32 NaN reaches this test only where
+// the conversion in front of it keeps it out of a ReLU: f32_to_f16's device form stores -65504 for it (flagged), the median
+// of the FAST epilogues stores its lower bound -- 0 under ReLU, NOT flagged.  The IEEE-half modes therefore keep NaN / inf out at
+// the doors (the packs above, make_conv, the device repack); finite halves and fp32 accumulators cannot form one in flight.
 __device__ __forceinline__ unsigned half2_at_ceiling(unsigned hw) { return (hw & 0x7fff7fffu) + 0x04010401u; }
 // Brackets the launches enqueued during its lifetime with a pair of HIP events on the ctx stream
 // when profiling is on (no-op otherwise).
@@ -469,8 +481,13 @@ inline int wsc_grid_for(long long total, int block = 256, int cap = 256 * 16) {
     if (g < 1) g = 1;
     return (int)g;
 }
+// The fp32 -> activation packs below are the doors of the range guard: with `range` = ctx->range_dev a value the planes cannot
+// hold (NaN, +-inf; |v| >= 65504 in the IEEE-half formats) raises the ctx's range flag; null: no test (scratch that need not
+// hold numbers, and the single-layer entries in the precisions that carry NaN / inf through: DESIGN.md section 5)
+// (the single-layer entries: a door in the IEEE-half modes only)
+inline unsigned *layer_door(wsc_ctx *ctx, wsc_precision prec) { return conv_fmt(prec) == 1 ? ctx->range_dev : nullptr; }
 // (the kernel and its grid follow the activation's precision)
-int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y);
+int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y, unsigned *range);
 // stem_pool.hip: conv 7x7/2 + BN + ReLU + MaxPool 3x3/2/1 of the f16x3 ResNet stem in one kernel
 void stem_pool_input_dims(int H, int W, int *Hp, int *Wp);
 int launch_stem_pool(wsc_ctx *ctx, Act x, int N, int H, int W, const bf16_t *w, int Kw, const float *s1, const float *b1, int relu,
@@ -479,7 +496,7 @@ int launch_stem_pool(wsc_ctx *ctx, Act x, int N, int H, int W, const bf16_t *w, 
 // Act::at(coff) of the wider tensor)
 int launch_gather_strided(wsc_ctx *ctx, Act x, int N, int H, int W, int C, int stride, int Ho, int Wo, Act y, int ldy);
 // [N][Hp][Wp][4] with a zero border of `pad` pixels on the top / left (and whatever Hp, Wp leave on the bottom / right)
-int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, Act y);
+int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, Act y, unsigned *range);
 // cam[b][c][y][x] = relu(head[2b][y][x][c]) + relu(head[2b+1][y][w-1-x][c])   (head fp32 NHWC, stride Cs)
 int launch_flip_add(wsc_ctx *ctx, const float *head, int B, int h, int w, int C, int Cs, float *cam);
 // score[b][c] = sigmoid(sum_f mean_hw(feat[2b])[f] * Wc[c][f] + bias[c])
@@ -487,7 +504,7 @@ int launch_gap_linear_sigmoid(wsc_ctx *ctx, Act feat, int B, int hw, int F, cons
                               int sample_stride);
 // y[i] = the fp32 value of activation element i (hi + lo in the two-plane precisions), i < n
 int launch_act_to_f32(wsc_ctx *ctx, Act x, size_t n, float *y);
-int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y);
+int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y, unsigned *range);
 int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y);
 
 // ---- pool.hip: every K x K pooling window on an NHWC activation ----------------------------------------------------------------

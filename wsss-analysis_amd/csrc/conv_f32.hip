@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void conv_f32_kernel(ConvF32Args p) {
         }
         if (p.relu) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+            for (int j = 0; j < 8; ++j) v[j] = relu_keep_nan(v[j]);
         }
         if (post) {
 #pragma unroll

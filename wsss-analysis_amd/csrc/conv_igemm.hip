@@ -900,7 +900,9 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
                     }
                 }
                 if (m < p.m_end) {
-                    // range guard (wsc_ctx_range_status): a stored half at the ceiling = a value the clamp above cut (or NaN)
+                    // range guard (wsc_ctx_range_status): a stored half at the ceiling = a value the clamp above cut.  NOT a NaN: the
+                    // median returns its lower bound for one (0 under ReLU).  None can arise here -- finite halves, fp32
+                    // accumulators -- and none gets in: the packs and make_conv are the doors (common.h half2_at_ceiling)
                     ovf |= half2_at_ceiling(hw[0]) | half2_at_ceiling(hw[1]) | half2_at_ceiling(hw[2]) | half2_at_ceiling(hw[3]);
                     *reinterpret_cast<uint4 *>(p.y + ((unsigned)m * (unsigned)p.ldy + (unsigned)c)) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
                     if (SPLIT) *reinterpret_cast<uint4 *>(p.y_lo + ((unsigned)m * (unsigned)p.ldy + (unsigned)c)) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
@@ -938,7 +940,7 @@ __global__ __launch_bounds__(BM * 2, (STAGES == 1 && FAST != 0) ? 4 : 2) void co
                 }
                 if (p.relu) {
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+                    for (int j = 0; j < 8; ++j) v[j] = relu_keep_nan(v[j]);
                 }
                 if (post) {
 #pragma unroll

@@ -13,14 +13,16 @@ namespace {
 
 // float32 NHWC [N][H][W][3] (what the reference feeds net["input"]: BGR minus mean) -> NHWC4 activation, 4th channel zero.
 // IEEE-half planes: a value the saturating conversion cuts (|v| >= 65504, NaN) raises the ctx's range flag like a conv epilogue
-// does -- the planes then do not hold the reference's input.
+// does -- the planes then do not hold the reference's input.  bfloat16 and fp32 planes: NaN and +-inf raise it (a whole net is
+// loud in every precision; misc_kernels.hip's packs have the same test).
 __global__ __launch_bounds__(256) void nhwc3_to_nhwc4_kernel(const float *__restrict__ x, long long npix, bf16_t *__restrict__ y,
                                                              bf16_t *__restrict__ y_lo, int fmt, unsigned *range) {
     bool ovf = false;
+    const float lim = fmt == 1 ? 65504.f : INFINITY;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
         const float c0 = x[3 * i], c1 = x[3 * i + 1], c2 = x[3 * i + 2];
         const bf16_t h0 = f32_to_h16(c0, fmt), h1 = f32_to_h16(c1, fmt), h2 = f32_to_h16(c2, fmt);
-        if (fmt == 1) ovf = ovf || !(fabsf(c0) < 65504.f) || !(fabsf(c1) < 65504.f) || !(fabsf(c2) < 65504.f);
+        ovf = ovf || !(fabsf(c0) < lim) || !(fabsf(c1) < lim) || !(fabsf(c2) < lim);
         reinterpret_cast<uint2 *>(y)[i] = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2);
         if (y_lo != nullptr) {
             const bf16_t l0 = f32_to_h16(c0 - h16_to_f32(h0, fmt), fmt), l1 = f32_to_h16(c1 - h16_to_f32(h1, fmt), fmt),
@@ -30,9 +32,15 @@ __global__ __launch_bounds__(256) void nhwc3_to_nhwc4_kernel(const float *__rest
     }
     if (ovf) *range = 3u;
 }
-__global__ __launch_bounds__(256) void nhwc3_to_nhwc4_f32_kernel(const float *__restrict__ x, long long npix, f32x4_t *__restrict__ y) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x)
-        y[i] = f32x4_t{x[3 * i], x[3 * i + 1], x[3 * i + 2], 0.f};
+__global__ __launch_bounds__(256) void nhwc3_to_nhwc4_f32_kernel(const float *__restrict__ x, long long npix, f32x4_t *__restrict__ y,
+                                                                 unsigned *range) {
+    bool bad = false;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
+        const float c0 = x[3 * i], c1 = x[3 * i + 1], c2 = x[3 * i + 2];
+        bad = bad || !(fabsf(c0) < INFINITY) || !(fabsf(c1) < INFINITY) || !(fabsf(c2) < INFINITY);
+        y[i] = f32x4_t{c0, c1, c2, 0.f};
+    }
+    if (bad) *range = 3u;
 }
 
 // fc8-softmax of one pixel per thread, fp32: x = in[0] + in[1] + ... in that order (the ASPP branches; one input for SEC),
@@ -94,7 +102,8 @@ int launch_nhwc3_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act
     const long long npix = (long long)N * H * W;
     const bool f32 = y.is_f32();
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)npix * (12 + (f32 ? 16 : (y.lo ? 16 : 8))));
-    if (f32) hipLaunchKernelGGL(nhwc3_to_nhwc4_f32_kernel, dim3(wsc_grid_for(npix)), dim3(256), 0, ctx->stream, x, npix, (f32x4_t *)y.f32());
+    if (f32) hipLaunchKernelGGL(nhwc3_to_nhwc4_f32_kernel, dim3(wsc_grid_for(npix)), dim3(256), 0, ctx->stream, x, npix, (f32x4_t *)y.f32(),
+                              ctx->range_dev);
     else
         hipLaunchKernelGGL(nhwc3_to_nhwc4_kernel, dim3(wsc_grid_for(npix)), dim3(256), 0, ctx->stream, x, npix, y.h16(), y.h16_lo(), y.fmt(),
                            ctx->range_dev);

@@ -109,6 +109,7 @@ struct GnApplyArgs {
     const float *gamma, *beta;
     bf16_t *y, *y_lo;    // NHWC [N][Hd][Wd][Ctot], this head writes channels [coff, coff + C)
     int N, H, W, C, G, up, relu, Hd, Wd, Ctot, coff, fmt, split;
+    unsigned *range;     // the ctx's range flag: raised where an IEEE-half plane cannot hold the value (|v| >= 65504, NaN)
 };
 
 // The arithmetic of the four apply kernels below, spelled once with explicit fused operations: the file is compiled with the
@@ -128,6 +129,7 @@ __device__ __forceinline__ float gn_affine(float v, float2 st, float gamma, floa
 __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
     const long long total = (long long)a.N * a.Hd * a.Wd * a.C;
     const int Cg = a.C / a.G;
+    bool bad = false;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(i % a.C);
@@ -156,12 +158,14 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs a) {
         }
         const float2 st = a.stats[n * a.G + c / Cg];
         v = gn_affine(v, st, a.gamma[c], a.beta[c]);
-        if (a.relu) v = fmaxf(v, 0.f);
+        if (a.relu) v = relu_keep_nan(v);
+        bad = bad || (a.fmt == 1 && !(fabsf(v) < 65504.f));
         const long long o = (((long long)n * a.Hd + ho) * a.Wd + wo) * a.Ctot + a.coff + c;
         const bf16_t h = f32_to_h16(v, a.fmt);
         a.y[o] = h;
         if (a.split) a.y_lo[o] = f32_to_h16(v - h16_to_f32(h, a.fmt), a.fmt); // the lo plane has the hi plane's format
     }
+    if (bad) *a.range = (unsigned)a.C;
 }
 
 // The same map, eight channels of one output pixel per thread (C, Ctot, coff multiples of 8; fewer than 2^31 items): 32-byte
@@ -173,6 +177,7 @@ __global__ __launch_bounds__(256) void gn_apply8_kernel(GnApplyArgs a) {
     const unsigned C8 = (unsigned)a.C >> 3;
     const unsigned total = (unsigned)a.N * (unsigned)a.Hd * (unsigned)a.Wd * C8;
     const int Cg = a.C / a.G;
+    bool bad = false;
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const unsigned c8 = i % C8;
         unsigned t = i / C8;
@@ -215,7 +220,8 @@ __global__ __launch_bounds__(256) void gn_apply8_kernel(GnApplyArgs a) {
             const int c = c0 + j;
             const float2 st = a.stats[n * a.G + c / Cg];
             float r = gn_affine(v[j], st, a.gamma[c], a.beta[c]);
-            if (a.relu) r = fmaxf(r, 0.f);
+            if (a.relu) r = relu_keep_nan(r);
+            bad = bad || (a.fmt == 1 && !(fabsf(r) < 65504.f));
             hh[j] = f32_to_h16(r, a.fmt);
             ll[j] = a.split ? f32_to_h16(r - h16_to_f32(hh[j], a.fmt), a.fmt) : (uint16_t)0;
         }
@@ -230,6 +236,7 @@ __global__ __launch_bounds__(256) void gn_apply8_kernel(GnApplyArgs a) {
             *reinterpret_cast<uint4 *>(a.y_lo + o) = pw;
         }
     }
+    if (bad) *a.range = (unsigned)a.C;
 }
 
 // WSC_PREC_F32: the same map into an fp32 concat buffer, four channels of one output pixel per thread (C, Ctot, coff multiples
@@ -271,7 +278,7 @@ __global__ __launch_bounds__(256) void gn_apply_f32_kernel(GnApplyArgs a) {
             const int c = c0 + j;
             const float2 st = a.stats[n * a.G + c / Cg];
             float r = gn_affine(v[j], st, a.gamma[c], a.beta[c]);
-            if (a.relu) r = fmaxf(r, 0.f);
+            if (a.relu) r = relu_keep_nan(r);
             v[j] = r;
         }
         *reinterpret_cast<f32x4_t *>(yf + (((long long)n * a.Hd + ho) * a.Wd + wo) * a.Ctot + a.coff + c0) = v;
@@ -363,6 +370,7 @@ int launch_group_norm_apply(wsc_ctx *ctx, const float *x, const void *stats, con
     a.y_lo = f32 ? nullptr : y.h16_lo();
     a.N = N; a.H = H; a.W = W; a.C = C; a.G = G; a.up = up; a.relu = relu; a.Hd = Hd; a.Wd = Wd; a.Ctot = Ctot;
     a.coff = coff; a.fmt = y.fmt(); a.split = a.y_lo != nullptr;
+    a.range = ctx->range_dev;
     if (f32) {
         WSC_CHECK(C % 4 == 0 && Ctot % 4 == 0 && coff % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)a.y & 15) == 0,
                   WSC_ERR_INVALID, "GroupNorm apply (fp32): %d of %d channels at %d are not 16-byte groups", C, Ctot, coff);

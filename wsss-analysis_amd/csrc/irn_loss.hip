@@ -101,7 +101,7 @@ __global__ __launch_bounds__(IL_THREADS) void irn_pair_kernel(const float *__res
             for (++c; c < c1; ++c) {
                 const int o = me + path_off[c];
                 const float val = le[o];
-                if (val > m) {
+                if (val > m || val != val) { // (a NaN logit is the path's maximum, as torch's max makes it: the pair's term is NaN)
                     m = val;
                     arg = o;
                 }

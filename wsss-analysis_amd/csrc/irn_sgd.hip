@@ -59,12 +59,16 @@ __global__ __launch_bounds__(ISGD_BLOCK) void irn_sgd_kernel(float *param, const
 
 // block b copies floats [VEC_COPY_PER_BLOCK lb, ...) of the job whose block range holds it
 __global__ __launch_bounds__(VEC_COPY_PER_BLOCK) void vec_copy_kernel(const VecCopyJob *__restrict__ jobs, int n_jobs,
-                                                                      const float *__restrict__ param) {
+                                                                      const float *__restrict__ param, unsigned *range) {
     int ji = 0;
     while (ji + 1 < n_jobs && (int)blockIdx.x >= jobs[ji + 1].block0) ++ji;
     const VecCopyJob &J = jobs[ji];
     const int i = ((int)blockIdx.x - J.block0) * VEC_COPY_PER_BLOCK + threadIdx.x;
-    if (i < J.n) J.dst[i] = param[J.off + i];
+    if (i < J.n) {
+        const float v = param[J.off + i];
+        J.dst[i] = v;
+        if (!(fabsf(v) < INFINITY)) *range = (unsigned)J.n; // (a non-finite parameter: the door of the range guard, as the repack's)
+    }
 }
 
 struct ChannelMeanArgs {
@@ -143,7 +147,7 @@ int irn_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, lo
 int vec_copy_launch(wsc_ctx *ctx, const VecCopyJob *jobs_dev, int n_jobs, int blocks, const float *param) {
     if (n_jobs <= 0 || blocks <= 0) return WSC_OK;
     WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, 8.0 * blocks * VEC_COPY_PER_BLOCK);
-    hipLaunchKernelGGL(vec_copy_kernel, dim3(blocks), dim3(VEC_COPY_PER_BLOCK), 0, ctx->stream, jobs_dev, n_jobs, param);
+    hipLaunchKernelGGL(vec_copy_kernel, dim3(blocks), dim3(VEC_COPY_PER_BLOCK), 0, ctx->stream, jobs_dev, n_jobs, param, ctx->range_dev);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }

@@ -3,17 +3,28 @@
 
 namespace {
 
+// The door of the range guard (include/wsscam.h, WSC_ERR_RANGE) at the fp32 -> activation packs: the largest magnitude a plane
+// of `fmt` holds as it is.  IEEE half: below the ceiling the saturating conversion stores (deeplab.hip's pack has the same
+// test); bfloat16 and fp32: every finite value.  pack_bad is true for NaN as well (the comparison is false).
+__device__ __forceinline__ float pack_limit(int fmt) { return fmt == 1 ? 65504.f : INFINITY; }
+__device__ __forceinline__ bool pack_bad(float v, float lim) { return !(fabsf(v) < lim); }
+
 // float32 NCHW [N][3][H][W] -> bf16 NHWC4 [N][H][W][4] (4th channel zero), optional lo plane.
 // Replaces img.cuda() + the layout torch/cuDNN picks internally (make_cam.py:48).
+// A value the planes cannot hold -- NaN, +-inf, and in the IEEE-half formats anything the saturating conversion cuts (|v| >=
+// 65504) -- raises the ctx's range flag (pack_limit / pack_bad above) where the caller passes `range`.
 __global__ void nchw_to_nhwc4_kernel(const float *__restrict__ x, int N, int HW, bf16_t *__restrict__ y,
-                                     bf16_t *__restrict__ y_lo, int fmt) {
+                                     bf16_t *__restrict__ y_lo, int fmt, unsigned *range) {
     const long long total = (long long)N * HW;
+    const float lim = pack_limit(fmt);
+    bool bad = false;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
         const long long n = i / HW;
         const int p = (int)(i - n * HW);
         const float *s = x + n * 3 * HW + p;
         const float c0 = s[0], c1 = s[HW], c2 = s[2 * HW];
+        bad = bad || pack_bad(c0, lim) || pack_bad(c1, lim) || pack_bad(c2, lim);
         const bf16_t h0 = f32_to_h16(c0, fmt), h1 = f32_to_h16(c1, fmt), h2 = f32_to_h16(c2, fmt);
         reinterpret_cast<uint2 *>(y)[i] = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2);
         if (y_lo != nullptr) {
@@ -22,15 +33,18 @@ __global__ void nchw_to_nhwc4_kernel(const float *__restrict__ x, int N, int HW,
             reinterpret_cast<uint2 *>(y_lo)[i] = make_uint2((uint32_t)l0 | ((uint32_t)l1 << 16), (uint32_t)l2);
         }
     }
+    if (bad && range != nullptr) *range = 3u;
 }
 
 // The same with a zero border baked in: out [N][Hp][Wp][4], pixel (py, px) = input (py - pad, px - pad) or zeros.  The f16x3
 // stem reads this buffer without bounds tests (conv_igemm.hip, CONV_FORM_STEM_ROWS): the 8-pixel window of a kernel row is 64
 // contiguous, 16-byte aligned bytes of either plane.
 __global__ void nchw_to_nhwc4_pad_kernel(const float *__restrict__ x, int N, int H, int W, int Hp, int Wp, int pad,
-                                         bf16_t *__restrict__ y, bf16_t *__restrict__ y_lo, int fmt) {
+                                         bf16_t *__restrict__ y, bf16_t *__restrict__ y_lo, int fmt, unsigned *range) {
     const long long total = (long long)N * Hp * Wp;
     const long long HW = (long long)H * W;
+    const float lim = pack_limit(fmt);
+    bool bad = false;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
         const int px = (int)(i % Wp);
@@ -43,6 +57,7 @@ __global__ void nchw_to_nhwc4_pad_kernel(const float *__restrict__ x, int N, int
             const float *s = x + n * 3 * HW + (long long)iy * W + ix;
             c0 = s[0]; c1 = s[HW]; c2 = s[2 * HW];
         }
+        bad = bad || pack_bad(c0, lim) || pack_bad(c1, lim) || pack_bad(c2, lim);
         const bf16_t h0 = f32_to_h16(c0, fmt), h1 = f32_to_h16(c1, fmt), h2 = f32_to_h16(c2, fmt);
         reinterpret_cast<uint2 *>(y)[i] = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2);
         if (y_lo != nullptr) {
@@ -51,6 +66,7 @@ __global__ void nchw_to_nhwc4_pad_kernel(const float *__restrict__ x, int N, int
             reinterpret_cast<uint2 *>(y_lo)[i] = make_uint2((uint32_t)l0 | ((uint32_t)l1 << 16), (uint32_t)l2);
         }
     }
+    if (bad && range != nullptr) *range = 3u;
 }
 
 // Strided pixel gather into a channel range of a wider tensor: y[(n, ho, wo)][0 .. C) = x[n][ho * stride][wo * stride][0 .. C),
@@ -88,7 +104,7 @@ __global__ void flip_add_kernel(const float *__restrict__ head, int B, int h, in
         const int b = (int)(r / C);
         const float a = head[(((long long)(2 * b) * h + yy) * w + xx) * Cs + c];
         const float f = head[(((long long)(2 * b + 1) * h + yy) * w + (w - 1 - xx)) * Cs + c];
-        cam[i] = fmaxf(a, 0.f) + fmaxf(f, 0.f);
+        cam[i] = relu_keep_nan(a) + relu_keep_nan(f);
     }
 }
 
@@ -126,19 +142,19 @@ __global__ __launch_bounds__(64 * GAP_WAVES) void gap_kernel(const bf16_t *__res
                 if (l0) v[u] += h16_to_f32(l0[(long long)(p + u) * F], fmt);
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) s = use_max ? fmaxf(s, v[u]) : s + v[u];
+            for (int u = 0; u < 8; ++u) s = use_max ? max_keep_nan(s, v[u]) : s + v[u];
         }
         for (; p < pe; ++p) {
             float v = h16_to_f32(f0[(long long)p * F], fmt);
             if (l0) v += h16_to_f32(l0[(long long)p * F], fmt);
-            s = use_max ? fmaxf(s, v) : s + v;
+            s = use_max ? max_keep_nan(s, v) : s + v;
         }
     }
     part[wv][lane] = s;
     __syncthreads();
     if (wv == 0 && f < F) {
         float t = part[0][lane];
-        for (int k = 1; k < GAP_WAVES; ++k) t = use_max ? fmaxf(t, part[k][lane]) : t + part[k][lane];
+        for (int k = 1; k < GAP_WAVES; ++k) t = use_max ? max_keep_nan(t, part[k][lane]) : t + part[k][lane];
         gap[(long long)b * F + f] = use_max ? t : t / (float)npix;
     }
 }
@@ -169,8 +185,10 @@ __global__ void bf16_to_f32_kernel(const bf16_t *__restrict__ x, const bf16_t *_
 
 // generic layout changes for the single-layer entry point (wsc_conv2d_nchw)
 __global__ void nchw_to_nhwc_kernel(const float *__restrict__ x, int N, int C, int HW, bf16_t *__restrict__ y,
-                                    bf16_t *__restrict__ y_lo, int fmt) {
+                                    bf16_t *__restrict__ y_lo, int fmt, unsigned *range) {
     const long long total = (long long)N * C * HW;
+    const float lim = pack_limit(fmt);
+    bool bad = false;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(i % C);
@@ -178,10 +196,12 @@ __global__ void nchw_to_nhwc_kernel(const float *__restrict__ x, int N, int C, i
         const int p = (int)(r % HW);
         const long long n = r / HW;
         const float v = x[(n * C + c) * HW + p];
+        bad = bad || pack_bad(v, lim);
         const bf16_t h = f32_to_h16(v, fmt);
         y[i] = h;
         if (y_lo) y_lo[i] = f32_to_h16(v - h16_to_f32(h, fmt), fmt);
     }
+    if (bad && range != nullptr) *range = (unsigned)C;
 }
 __global__ void nhwc_to_nchw_kernel(const bf16_t *__restrict__ x, const bf16_t *__restrict__ x_lo, int N, int C,
                                     int HW, float *__restrict__ y, int fmt) {
@@ -201,14 +221,18 @@ __global__ void nhwc_to_nchw_kernel(const bf16_t *__restrict__ x, const bf16_t *
 
 // ---- WSC_PREC_F32: the same maps on one plane of fp32 (the launch functions take them for an Act of that precision).
 // HBM-bound, 16 bytes per access where the layout has them.
-__global__ void nchw_to_nhwc4_f32_kernel(const float *__restrict__ x, int N, int HW, f32x4_t *__restrict__ y) {
+__global__ void nchw_to_nhwc4_f32_kernel(const float *__restrict__ x, int N, int HW, f32x4_t *__restrict__ y, unsigned *range) {
     const long long total = (long long)N * HW;
+    bool bad = false;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long n = i / HW;
         const int p = (int)(i - n * HW);
         const float *s = x + n * 3 * HW + p;
-        y[i] = f32x4_t{s[0], s[HW], s[2 * HW], 0.f};
+        const float c0 = s[0], c1 = s[HW], c2 = s[2 * HW];
+        bad = bad || pack_bad(c0, INFINITY) || pack_bad(c1, INFINITY) || pack_bad(c2, INFINITY);
+        y[i] = f32x4_t{c0, c1, c2, 0.f};
     }
+    if (bad && range != nullptr) *range = 3u;
 }
 // gap_kernel's decomposition and summation order on fp32 features
 __global__ __launch_bounds__(64 * GAP_WAVES) void gap_f32_kernel(const float *__restrict__ feat, int hw, int F, float *__restrict__ gap,
@@ -230,53 +254,57 @@ __global__ __launch_bounds__(64 * GAP_WAVES) void gap_f32_kernel(const float *__
 #pragma unroll
             for (int u = 0; u < 8; ++u) v[u] = f0[(long long)(p + u) * F];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) s = use_max ? fmaxf(s, v[u]) : s + v[u];
+            for (int u = 0; u < 8; ++u) s = use_max ? max_keep_nan(s, v[u]) : s + v[u];
         }
-        for (; p < pe; ++p) s = use_max ? fmaxf(s, f0[(long long)p * F]) : s + f0[(long long)p * F];
+        for (; p < pe; ++p) s = use_max ? max_keep_nan(s, f0[(long long)p * F]) : s + f0[(long long)p * F];
     }
     part[wv][lane] = s;
     __syncthreads();
     if (wv == 0 && f < F) {
         float t = part[0][lane];
-        for (int k = 1; k < GAP_WAVES; ++k) t = use_max ? fmaxf(t, part[k][lane]) : t + part[k][lane];
+        for (int k = 1; k < GAP_WAVES; ++k) t = use_max ? max_keep_nan(t, part[k][lane]) : t + part[k][lane];
         gap[(long long)b * F + f] = use_max ? t : t / (float)npix;
     }
 }
 // layout changes of the single-layer entry point; TO_NHWC: y[n][p][c] = x[n][c][p], else y[n][c][p] = x[n][p][c]
 template <bool TO_NHWC>
-__global__ void relayout_f32_kernel(const float *__restrict__ x, int N, int C, int HW, float *__restrict__ y) {
+__global__ void relayout_f32_kernel(const float *__restrict__ x, int N, int C, int HW, float *__restrict__ y, unsigned *range) {
     const long long total = (long long)N * C * HW;
+    bool bad = false;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int inner = TO_NHWC ? C : HW, outer = TO_NHWC ? HW : C;
         const int a = (int)(i % inner);
         const long long r = i / inner;
         const int b = (int)(r % outer);
         const long long n = r / outer;
-        y[i] = x[(n * inner + a) * outer + b];
+        const float v = x[(n * inner + a) * outer + b];
+        bad = bad || pack_bad(v, INFINITY);
+        y[i] = v;
     }
+    if (bad && range != nullptr) *range = (unsigned)C;
 }
 
 } // namespace
 
-int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y) {
+int launch_nchw_to_nhwc4(wsc_ctx *ctx, const float *x, int N, int H, int W, Act y, unsigned *range) {
     const long long total = (long long)N * H * W;
     const bool f32 = y.is_f32();
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)total * (12 + (f32 ? 16 : 8)));
     if (f32)
-        hipLaunchKernelGGL(nchw_to_nhwc4_f32_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, (f32x4_t *)y.f32());
+        hipLaunchKernelGGL(nchw_to_nhwc4_f32_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, (f32x4_t *)y.f32(), range);
     else
         hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x, N, H * W, y.h16(), y.h16_lo(),
-                           y.fmt());
+                           y.fmt(), range);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
 
-int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, Act y) {
+int launch_nchw_to_nhwc4_pad(wsc_ctx *ctx, const float *x, int N, int H, int W, int Hp, int Wp, int pad, Act y, unsigned *range) {
     WSC_CHECK(!y.is_f32(), WSC_ERR_INVALID, "the padded NHWC4 input is a half-mode path");
     const long long total = (long long)N * Hp * Wp;
     WscKernelTimer timer(ctx, WSC_K_POOL_MISC, (double)N * H * W * 12 + (double)total * (y.lo ? 16 : 8));
     hipLaunchKernelGGL(nchw_to_nhwc4_pad_kernel, dim3(wsc_grid_for(total)), dim3(256), 0, ctx->stream, x, N, H, W, Hp, Wp, pad, y.h16(),
-                       y.h16_lo(), y.fmt());
+                       y.h16_lo(), y.fmt(), range);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
@@ -330,12 +358,12 @@ int launch_act_to_f32(wsc_ctx *ctx, Act x, size_t n, float *y) {
     return WSC_OK;
 }
 
-int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y) {
+int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act y, unsigned *range) {
     const dim3 grid(wsc_grid_for((long long)N * C * HW));
     if (y.is_f32())
-        hipLaunchKernelGGL(relayout_f32_kernel<true>, grid, dim3(256), 0, ctx->stream, x, N, C, HW, y.f32());
+        hipLaunchKernelGGL(relayout_f32_kernel<true>, grid, dim3(256), 0, ctx->stream, x, N, C, HW, y.f32(), range);
     else
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, ctx->stream, x, N, C, HW, y.h16(), y.h16_lo(), y.fmt());
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, ctx->stream, x, N, C, HW, y.h16(), y.h16_lo(), y.fmt(), range);
     WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
@@ -343,7 +371,7 @@ int launch_nchw_to_nhwc(wsc_ctx *ctx, const float *x, int N, int C, int HW, Act 
 int launch_nhwc_to_nchw(wsc_ctx *ctx, Act x, int N, int C, int HW, float *y) {
     const dim3 grid(wsc_grid_for((long long)N * C * HW));
     if (x.is_f32())
-        hipLaunchKernelGGL(relayout_f32_kernel<false>, grid, dim3(256), 0, ctx->stream, (const float *)x.f32(), N, C, HW, y);
+        hipLaunchKernelGGL(relayout_f32_kernel<false>, grid, dim3(256), 0, ctx->stream, (const float *)x.f32(), N, C, HW, y, (unsigned *)nullptr);
     else
         hipLaunchKernelGGL(nhwc_to_nchw_kernel, grid, dim3(256), 0, ctx->stream, (const bf16_t *)x.h16(), (const bf16_t *)x.h16_lo(), N,
                            C, HW, y, x.fmt());

@@ -211,6 +211,17 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
     std::vector<float> wscale(Cout, 1.f);
     if (fmt == 1) {
         const size_t per = (size_t)Cin * kh * kw;
+        // the door of the range guard for what the host packs: a half cannot hold NaN / inf (the saturating conversion would
+        // store +-65504 for an inf and raise nothing, std::max below passes over a NaN), so an IEEE-half layer takes none
+        for (size_t i = 0; i < per * Cout; ++i)
+            WSC_CHECK(std::isfinite(w->data[i]), WSC_ERR_RANGE,
+                      "a weight of an IEEE-half layer is not finite (%g, output channel %d of %d): WSC_PREC_F32 computes with it, as the reference does",
+                      (double)w->data[i], (int)(i / per), Cout);
+        for (const std::vector<float> *v : {&s1, &b1, s2, b2})
+            for (int co = 0; v && co < Cout; ++co)
+                WSC_CHECK(std::isfinite((*v)[co]), WSC_ERR_RANGE,
+                          "a scale / shift of an IEEE-half layer is not finite (%g, output channel %d of %d): WSC_PREC_F32 computes with it, as the reference does",
+                          (double)(*v)[co], co, Cout);
         for (int co = 0; co < Cout; ++co) {
             float mx = 0.f;
             for (size_t i = 0; i < per; ++i) mx = std::max(mx, std::fabs(w->data[(size_t)co * per + i]));
@@ -894,8 +905,8 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
     if (nhwc_in) {
         WSC_CHECK(in_pad == 0, WSC_ERR_INVALID, "internal: an NHWC input has no padded-stem form");
         WSC_TRY(launch_nhwc3_to_nhwc4(ctx, x_dev, N, S, SW, xin));
-    } else if (in_pad > 0) WSC_TRY(launch_nchw_to_nhwc4_pad(ctx, x_dev, N, S, SW, in_h, in_w, in_pad, xin));
-    else WSC_TRY(launch_nchw_to_nhwc4(ctx, x_dev, N, S, SW, xin));
+    } else if (in_pad > 0) WSC_TRY(launch_nchw_to_nhwc4_pad(ctx, x_dev, N, S, SW, in_h, in_w, in_pad, xin, ctx->range_dev));
+    else WSC_TRY(launch_nchw_to_nhwc4(ctx, x_dev, N, S, SW, xin, ctx->range_dev)); // (a net raises the flag in every precision)
     for (size_t i = 0; i < net->ops.size(); ++i) {
         const Op &op = net->ops[i];
         const OpDims &d = pl.ops[i];
@@ -982,6 +993,12 @@ int wsc_net_create(wsc_ctx *ctx, int arch, const wsc_tensor_desc *weights, int n
     WSC_HIP(hipSetDevice(ctx->device));
     Dict d;
     WSC_TRY(descs_to_dict(weights, n_weights, &d));
+    // a checkpoint saved after a diverged step: refused here, in every precision (the maps of such a model are NaN nearly
+    // everywhere in the reference)
+    for (const auto &kv : d)
+        for (int64_t i = 0, n = kv.second.numel(); i < n; ++i)
+            WSC_CHECK(std::isfinite(kv.second.data[i]), WSC_ERR_RANGE, "wsc_net_create: state-dict tensor '%s' holds a non-finite value (%g at element %lld)",
+                      kv.first.c_str(), (double)kv.second.data[i], (long long)i);
     // (never ignored: the IRN flavours keep the torch port's MaxPool2d(2, 2), the other nets have their own pools)
     WSC_CHECK(!has(d, "pool_spec") || arch == WSC_ARCH_VGG16_CAM || arch == WSC_ARCH_M7_CAM, WSC_ERR_INVALID,
               "pool_spec is a key of WSC_ARCH_VGG16_CAM / WSC_ARCH_M7_CAM only (arch %d)", arch);
@@ -2393,10 +2410,14 @@ int wsc_conv2d_nchw_dil(wsc_ctx *ctx, const float *x_dev, int N, int Cin, int H,
     char *p = (char *)ws;
     const Act xi = act_carve(p, in_e, prec), yo = act_carve(p, out_e, prec);
     const Act ri = residual_dev ? act_carve(p, out_e, prec) : Act();
-    if (form == CONV_FORM_STEM_ROWS) st = launch_nchw_to_nhwc4_pad(ctx, x_dev, N, H, W, in_h, in_w, pad, xi);
-    else if (form != CONV_FORM_GENERIC) st = launch_nchw_to_nhwc4(ctx, x_dev, N, H, W, xi);
-    else st = launch_nchw_to_nhwc(ctx, x_dev, N, Cin, H * W, xi);
-    if (st == WSC_OK && residual_dev) st = launch_nchw_to_nhwc(ctx, residual_dev, N, Cout, Ho * Wo, ri);
+    // (the small-Cin forms multiply a zero-weighted extra pixel per kernel row: 0 * NaN would spread a non-finite input beyond the
+    // cells that read it, so in the 16-bit modes their input is loud in bf16 / bf16x3 as well)
+    unsigned *door = layer_door(ctx, prec);
+    unsigned *door_x = (form != CONV_FORM_GENERIC && prec != WSC_PREC_F32) ? ctx->range_dev : door;
+    if (form == CONV_FORM_STEM_ROWS) st = launch_nchw_to_nhwc4_pad(ctx, x_dev, N, H, W, in_h, in_w, pad, xi, door_x);
+    else if (form != CONV_FORM_GENERIC) st = launch_nchw_to_nhwc4(ctx, x_dev, N, H, W, xi, door_x);
+    else st = launch_nchw_to_nhwc(ctx, x_dev, N, Cin, H * W, xi, door);
+    if (st == WSC_OK && residual_dev) st = launch_nchw_to_nhwc(ctx, residual_dev, N, Cout, Ho * Wo, ri, door);
     if (st == WSC_OK) {
         ConvLaunch L = conv_launch(c, prec);
         L.x = xi; L.res = ri; L.y = yo;
@@ -2439,7 +2460,7 @@ int wsc_group_norm_nhwc(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, i
     float *gamma = (float *)(p + part_b + stats_b), *beta = (float *)(p + part_b + stats_b + vec_b);
     WSC_TRY(wsc_ctx_upload_small(ctx, gamma, gamma_host, sizeof(float) * C));
     WSC_TRY(wsc_ctx_upload_small(ctx, beta, beta_host, sizeof(float) * C));
-    WSC_TRY(launch_nchw_to_nhwc(ctx, y_dev, N * Hd * Wd, Ctot, 1, yo)); // (what the other heads of the concat buffer wrote)
+    WSC_TRY(launch_nchw_to_nhwc(ctx, y_dev, N * Hd * Wd, Ctot, 1, yo, nullptr)); // (no door: it may be scratch -- what the other heads of the concat buffer wrote)
     WSC_TRY(launch_group_norm_stats(ctx, x_dev, N, H, W, C, G, eps, part, stats));
     WSC_TRY(launch_group_norm_apply(ctx, x_dev, stats, gamma, beta, N, H, W, C, G, up, relu, yo, Hd, Wd, Ctot, coff));
     return launch_act_to_f32(ctx, yo, out_e, y_dev);
@@ -2463,7 +2484,7 @@ int wsc_gap_linear_sigmoid(wsc_ctx *ctx, const float *feat_dev, int B, int hw, i
     float *w = (float *)p, *bias = bias_host ? (float *)(p + w_b) : nullptr;
     WSC_TRY(wsc_ctx_upload_small(ctx, w, w_host, sizeof(float) * (size_t)C * F));
     if (bias) WSC_TRY(wsc_ctx_upload_small(ctx, bias, bias_host, sizeof(float) * C));
-    WSC_TRY(launch_nchw_to_nhwc(ctx, feat_dev, B * sample_stride * npix, F, 1, feat));
+    WSC_TRY(launch_nchw_to_nhwc(ctx, feat_dev, B * sample_stride * npix, F, 1, feat, layer_door(ctx, prec)));
     return launch_gap_linear_sigmoid(ctx, feat, B, hw, F, w, bias, C, score_dev, sample_stride);
 }
 

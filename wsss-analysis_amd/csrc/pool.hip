@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void pool_h16_kernel(const bf16_t *__restrict_
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     if (AVG) sum[j] += (double)f[j];
-                    else best[j] = fmaxf(best[j], f[j]);
+                    else best[j] = max_keep_nan(best[j], f[j]);
                 }
             }
         }
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void pool_f32_kernel(const float *__restrict__
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (AVG) sum[j] += (double)v[j];
-                    else best[j] = fmaxf(best[j], v[j]);
+                    else best[j] = max_keep_nan(best[j], v[j]);
                 }
             }
         }
@@ -352,7 +352,7 @@ int pool_staged(wsc_ctx *ctx, const float *x_dev, int N, int H, int W, int C, co
     WSC_TRY(wsc_ctx_workspace(ctx, act_bytes(in_e, prec) + act_bytes(out_e, prec), &ws));
     char *p = (char *)ws;
     const Act xi = act_carve(p, in_e, prec), yo = act_carve(p, out_e, prec);
-    WSC_TRY(launch_nchw_to_nhwc(ctx, x_dev, (int)((size_t)N * H * W), C, 1, xi));
+    WSC_TRY(launch_nchw_to_nhwc(ctx, x_dev, (int)((size_t)N * H * W), C, 1, xi, layer_door(ctx, xi.prec)));
     WSC_TRY(launch_pool(ctx, xi, N, H, W, C, g, yo));
     return launch_act_to_f32(ctx, yo, out_e, y_dev);
 }

@@ -178,7 +178,8 @@ int sgd_blocks(long long elems, bool vec) {
     const RepackJob &J = jobs[ji];                                                    \
     const int lb = (int)blockIdx.x - J.field /* the block's index inside the layer */
 
-// pmax[split][c] = max |w[r][c]| over the split's rows (a NaN is passed over, as std::max passes it over in make_conv);
+// pmax[split][c] = max |w[r][c]| over the split's rows (a NaN is passed over, as std::max passes it over in make_conv: the pack
+// kernels below raise the range flag for it);
 // block (tile, split) of a layer = lb % tiles, lb / tiles
 __global__ __launch_bounds__(256) void repack_colmax_kernel(const RepackJob *__restrict__ jobs, int n_jobs, const float *__restrict__ param,
                                                             float *__restrict__ pmax_all) {
@@ -209,8 +210,11 @@ __device__ __forceinline__ unsigned pack2(uint16_t a, uint16_t b) { return (unsi
 // (cc, r, s) = CK channels of tap (r, s).  fmt / split: conv_fmt / conv_split != 0 of the net's precision.
 template <int CK>
 __global__ __launch_bounds__(256) void repack_generic_kernel(const RepackJob *__restrict__ jobs, int n_jobs, const float *__restrict__ param,
-                                                             const float *__restrict__ pmax_all, int fmt, int split) {
+                                                             const float *__restrict__ pmax_all, int fmt, int split, unsigned *range) {
     constexpr int LD = 65, G = CK / 8;
+    // the door of the range guard for what the device packs (make_conv's for the host): a weight or bias that is not finite raises
+    // the ctx's flag, in every precision -- the step that made it has diverged, and the half formats cannot hold it at all
+    bool bad = false;
     __shared__ float tile[CK][LD];
     __shared__ float s_scale[64];
     REPACK_FIND_JOB(pack_block0);
@@ -234,6 +238,7 @@ __global__ __launch_bounds__(256) void repack_generic_kernel(const RepackJob *__
             if (by == 0) {
                 J.s1[c] = inv;
                 J.b1[c] = J.b_off >= 0 ? param[J.b_off + c] : 0.f;
+                bad = !(fabsf(J.b1[c]) < INFINITY);
             }
         }
         s_scale[tid] = scale;
@@ -246,7 +251,9 @@ __global__ __launch_bounds__(256) void repack_generic_kernel(const RepackJob *__
 #pragma unroll
         for (int i = 0; i < CK / 4; ++i) {
             const int row = (tid >> 6) + 4 * i, col = tid & 63;
-            tile[row][col] = co0 + col < Cout && cc * CK + row < Cin ? src[(long long)row * Cout + col] : 0.f; // (Cin_pad: zeros past Cin)
+            const float wv = co0 + col < Cout && cc * CK + row < Cin ? src[(long long)row * Cout + col] : 0.f; // (Cin_pad: zeros past Cin)
+            tile[row][col] = wv;
+            bad = bad || !(fabsf(wv) < INFINITY);
         }
         __syncthreads();
         for (int j = tid; j < 64 * G; j += 256) {
@@ -277,11 +284,12 @@ __global__ __launch_bounds__(256) void repack_generic_kernel(const RepackJob *__
                 *reinterpret_cast<uint4 *>(row + J.lo_at) = make_uint4(pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7]));
         }
     }
+    if (bad) *range = (unsigned)Cout;
 }
 
 // the first layer: CONV_FORM_SMALL2, weight (ci, r, s) at r 16 + s 4 + ci of its row; one thread per output channel
 __global__ __launch_bounds__(64) void repack_small2_kernel(const RepackJob *__restrict__ jobs, int job, const float *__restrict__ param, int fmt,
-                                                           int split) {
+                                                           int split, unsigned *range) {
     const RepackJob &J = jobs[job];
     const float *w = param + J.w_off;
     const int Cout = J.Cout;
@@ -298,9 +306,11 @@ __global__ __launch_bounds__(64) void repack_small2_kernel(const RepackJob *__re
     }
     J.s1[c] = inv;
     J.b1[c] = param[J.b_off + c];
+    bool bad = !(fabsf(J.b1[c]) < INFINITY); // (the door, as repack_generic_kernel's)
     for (int i = 0; i < n; ++i) {
         const int ci = i % J.Cin, s = (i / J.Cin) % J.k, r = i / (J.Cin * J.k);
         const float v = w[(long long)i * Cout + c];
+        bad = bad || !(fabsf(v) < INFINITY);
         const long long at = (long long)c * J.Kw + r * 16 + s * 4 + ci;
         if (fmt == CONV_FMT_F32) {
             ((float *)J.wp)[at] = v;
@@ -311,6 +321,7 @@ __global__ __launch_bounds__(64) void repack_small2_kernel(const RepackJob *__re
         ((uint16_t *)J.wp)[at] = h;
         if (split) ((uint16_t *)J.wp)[at + J.lo_at] = f32_to_h16(x - h16_to_f32(h, fmt), fmt);
     }
+    if (bad) *range = (unsigned)Cout;
 }
 
 // rot[ci][((co / 32) k + r) k + s][co % 32] = w[k - 1 - r][k - 1 - s][ci][co], co < Cout (the floats past Cout keep their zeros);
@@ -419,14 +430,14 @@ int repack_launch(wsc_ctx *ctx, const RepackPlan &plan, const float *param) {
     if (plan.pack_blocks > 0) {
         if (plan.ck == 32)
             hipLaunchKernelGGL(repack_generic_kernel<32>, dim3(plan.pack_blocks), dim3(256), 0, ctx->stream, plan.jobs_dev, plan.n_jobs, param,
-                               plan.pmax, fmt, split);
+                               plan.pmax, fmt, split, ctx->range_dev);
         else
             hipLaunchKernelGGL(repack_generic_kernel<64>, dim3(plan.pack_blocks), dim3(256), 0, ctx->stream, plan.jobs_dev, plan.n_jobs, param,
-                               plan.pmax, fmt, split);
+                               plan.pmax, fmt, split, ctx->range_dev);
         WSC_HIP(hipGetLastError());
     }
     if (plan.small_job >= 0) {
-        hipLaunchKernelGGL(repack_small2_kernel, dim3(plan.small_tiles), dim3(64), 0, ctx->stream, plan.jobs_dev, plan.small_job, param, fmt, split);
+        hipLaunchKernelGGL(repack_small2_kernel, dim3(plan.small_tiles), dim3(64), 0, ctx->stream, plan.jobs_dev, plan.small_job, param, fmt, split, ctx->range_dev);
         WSC_HIP(hipGetLastError());
     }
     if (plan.rot_blocks > 0) {

@@ -353,6 +353,13 @@ class Context:
     def sync(self):
         check(self._lib.wsc_sync(self.h))
 
+    def drain(self):
+        """sync() for the release paths: waits for the stream, and leaves a raised range flag to the next sync() / to_host()
+        instead of raising WSC_ERR_RANGE itself (the flag is sticky, so nothing is lost; what has to be freed is freed)."""
+        st = self._lib.wsc_sync(self.h)
+        if st != WSC_ERR_RANGE:
+            check(st)
+
     def range_status(self, clear=False):
         """Range guard of the IEEE-half conv modes: 0 = clean, else the output-channel count of a layer whose activations
         reached half's ceiling and were saturated (sync() / to_host() raise WscError(WSC_ERR_RANGE) until cleared)."""
@@ -404,8 +411,12 @@ class Context:
     def to_device(self, arr, pooled=False):
         arr = np.ascontiguousarray(arr)
         buf = self.alloc(arr.nbytes, pooled=pooled)
-        check(self._lib.wsc_memcpy_h2d(self.h, buf.ptr, arr.ctypes.data, arr.nbytes))
-        self.sync()  # arr may be a temporary
+        try:
+            check(self._lib.wsc_memcpy_h2d(self.h, buf.ptr, arr.ctypes.data, arr.nbytes))
+            self.drain()  # arr may be a temporary; an earlier call's range error is not this copy's to report
+        except Exception:
+            buf.free()
+            raise
         return buf
 
     def to_host(self, buf, shape, dtype, offset_bytes=0):
@@ -603,8 +614,11 @@ class Net:
 
     def close(self):
         if getattr(self, "h", None) and self.ctx.h:
-            self.ctx.sync()
-            self.ctx._lib.wsc_net_destroy(self.h)
+            try:
+                self.ctx.drain()
+            finally:  # (whatever the wait reports, the weights are released)
+                h, self.h = self.h, None
+                self.ctx._lib.wsc_net_destroy(h)
         self.h = None
 
     def __del__(self):
