@@ -1289,28 +1289,58 @@ static int edge_geom(const wsc_net *net, int N, int S, EdgeGeom *g) {
     return WSC_OK;
 }
 
+// The layout of a tape: float32 tensors [N][Ho][Wo][C] in one buffer of `elems` floats, each on a 256-byte line.  Every training
+// path's tape plan embeds this one and keeps only its own indices into `e` (embed it, do not copy it).
+struct TapeLayout {
+    std::vector<wsc_tape_entry> e;
+    long long elems = 0;
+    int add(const std::string &name, int N, int Ho, int Wo, int C) {
+        wsc_tape_entry t = {};
+        std::strncpy(t.name, name.c_str(), sizeof(t.name) - 1);
+        t.Ho = Ho; t.Wo = Wo; t.C = C;
+        t.offset = elems;
+        elems += ((long long)N * Ho * Wo * C + 63) / 64 * 64; // (entries start on 256-byte lines)
+        e.push_back(t);
+        return (int)e.size() - 1;
+    }
+    long long off(int entry) const { return e[entry].offset; }
+};
+// the out-parameters of a wsc_net_*_tape_plan entry (entries_out may be short or null: n_out is the whole count)
+static int tape_export(const TapeLayout &t, wsc_tape_entry *entries_out, int max_entries, int *n_out, long long *tape_elems_out) {
+    *n_out = (int)t.e.size();
+    *tape_elems_out = t.elems;
+    for (int i = 0; i < max_entries && i < (int)t.e.size(); ++i) entries_out[i] = t.e[i];
+    return WSC_OK;
+}
+// the caller's tape is the one `plan_fn` describes, checked before anything is launched
+static int tape_check(const char *fn, const char *plan_fn, long long tape_elems, const TapeLayout &t) {
+    WSC_CHECK(tape_elems == t.elems, WSC_ERR_INVALID, "%s: a tape of %lld floats, the plan has %lld (%s)", fn, tape_elems, t.elems, plan_fn);
+    return WSC_OK;
+}
+
+// one guard per net kind, under the name of the entry point that asks
+static int need_irn(const char *fn, const wsc_net *net) {
+    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID, "%s: the network is not an IRNet EdgeDisplacement net", fn);
+    return WSC_OK;
+}
+static int need_seg(const char *fn, const wsc_net *net) {
+    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "%s: the network is not a WSC_ARCH_DEEPLAB_* net", fn);
+    return WSC_OK;
+}
+
 // What the backward pass of the heads needs of a forward pass, as float32 in one buffer (each "the value the next op read": hi +
 // lo of a two-plane precision): every stage tap a head reads "x<k>" [N][H][W][C]; per head its conv output "<head>.z"
 // [N][ho][wo][Cout] and its GroupNorm statistics "<head>.stats" [N][1][1][2 G] = {mean, rstd} pairs as gn_finish_kernel wrote
 // them; every concat buffer "cat<i>" [N][Hc][Wc][Ctot], padding channels included
 struct EdgeTapePlan {
     EdgeGeom g;
-    std::vector<wsc_tape_entry> e;
+    TapeLayout t;
     std::vector<int> tap, z, stats, cat; // entry of stage k (-1: no head reads it), of head j (two), of concat buffer i
-    long long elems = 0;
 };
 static int edge_tape_plan(const wsc_net *net, int N, int S, EdgeTapePlan *tp) {
     WSC_TRY(edge_geom(net, N, S, &tp->g));
     const EdgeGeom &g = tp->g;
-    auto add = [&](const std::string &name, int Ho, int Wo, int C) {
-        wsc_tape_entry t = {};
-        std::strncpy(t.name, name.c_str(), sizeof(t.name) - 1);
-        t.Ho = Ho; t.Wo = Wo; t.C = C;
-        t.offset = tp->elems;
-        tp->elems += ((long long)N * Ho * Wo * C + 63) / 64 * 64; // (entries start on 256-byte lines)
-        tp->e.push_back(t);
-        return (int)tp->e.size() - 1;
-    };
+    auto add = [&](const std::string &name, int Ho, int Wo, int C) { return tp->t.add(name, N, Ho, Wo, C); };
     tp->tap.assign(net->taps.size(), -1);
     for (size_t k = 0; k < net->taps.size(); ++k) {
         bool read = false;
@@ -1375,7 +1405,7 @@ static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_de
     WSC_HIP(hipMemsetAsync(cats[0].hi, 0, act_bytes(cat_elems[0], net->prec), ctx->stream));
     if (tp)
         for (size_t k = 0; k < taps.size(); ++k)
-            if (tp->tap[k] >= 0) WSC_TRY(launch_act_to_f32(ctx, taps[k], (size_t)N * Hs[k] * Ws[k] * Cs[k], tape + tp->e[tp->tap[k]].offset));
+            if (tp->tap[k] >= 0) WSC_TRY(launch_act_to_f32(ctx, taps[k], (size_t)N * Hs[k] * Ws[k] * Cs[k], tape + tp->t.off(tp->tap[k])));
 
     auto run_conv = [&](const ConvW &c, Act x, int H, int W, float *y_f32) -> int {
         ConvLaunch L = conv_launch(c, net->prec); // (1 x 1, no padding, no ReLU: build_irn_heads)
@@ -1390,8 +1420,8 @@ static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_de
         const int k = h.src > 0 ? h.src - 1 : -h.src - 1; // a stage tap, or a concat buffer
         const Act x = h.src > 0 ? taps[k] : cats[k];
         WSC_CHECK(hg.sc == h.conv.Cin, WSC_ERR_SHAPE, "IRNet head: %d input channels, the weights expect %d", hg.sc, h.conv.Cin);
-        float *z = tp ? tape + tp->e[tp->z[j]].offset : ftmp;
-        void *stats = tp ? (void *)(tape + tp->e[tp->stats[j]].offset) : gn_stats;
+        float *z = tp ? tape + tp->t.off(tp->z[j]) : ftmp;
+        void *stats = tp ? (void *)(tape + tp->t.off(tp->stats[j])) : gn_stats;
         WSC_TRY(run_conv(h.conv, x, hg.sh, hg.sw, z));
         WSC_TRY(launch_group_norm_stats(ctx, z, N, hg.ho, hg.wo, h.conv.Cout, h.groups, 1e-5f, gn_part, stats));
         const int di = h.dst;
@@ -1399,7 +1429,7 @@ static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_de
                                         h.up, 1, cats[di], cat_h[di], cat_w[di], cat_c[di], h.coff));
     }
     if (tp)
-        for (int i = 0; i < NC; ++i) WSC_TRY(launch_act_to_f32(ctx, cats[i], cat_elems[i], tape + tp->e[tp->cat[i]].offset));
+        for (int i = 0; i < NC; ++i) WSC_TRY(launch_act_to_f32(ctx, cats[i], cat_elems[i], tape + tp->t.off(tp->cat[i])));
     WSC_TRY(run_conv(net->edge6, cats[0], He, We, e_out));
     WSC_TRY(run_conv(net->dp7b, cats[NC - 1], Hd, Wd, d_out));
     out->e = e_out;
@@ -1413,8 +1443,7 @@ static int forward_edge_maps(wsc_ctx *ctx, const wsc_net *net, const float *x_de
 int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int S, int feat_h, int feat_w,
                          float *edge_dev, float *dp_dev) {
     WSC_CHECK(ctx && net && x_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_net_forward_edge: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_net_forward_edge: the network is not an IRNet EdgeDisplacement net");
+    WSC_TRY(need_irn("wsc_net_forward_edge", net));
     WSC_CHECK(B > 0 && S > 0 && feat_h > 0 && feat_w > 0, WSC_ERR_INVALID, "wsc_net_forward_edge: B=%d S=%d", B, S);
     WSC_HIP(hipSetDevice(ctx->device));
     EdgeMaps m;
@@ -1427,8 +1456,7 @@ int wsc_net_forward_edge(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, i
 // (He, We) and (Hd, Wd) of the two maps for an S x S input
 int wsc_net_edge_size(const wsc_net *net, int S, int *edge_hw, int *dp_hw) {
     WSC_CHECK(net && edge_hw && dp_hw, WSC_ERR_INVALID, "wsc_net_edge_size: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_net_edge_size: the network is not an IRNet EdgeDisplacement net");
+    WSC_TRY(need_irn("wsc_net_edge_size", net));
     WSC_CHECK(S > 0, WSC_ERR_INVALID, "wsc_net_edge_size: S=%d", S);
     EdgeMaps m;
     WSC_TRY(forward_edge_maps(nullptr, net, nullptr, 1, S, 0, 0, &m));
@@ -1440,8 +1468,7 @@ int wsc_net_edge_size(const wsc_net *net, int S, int *edge_hw, int *dp_hw) {
 // Net.forward in training mode (resnet50_irn.py:110-133): N plain samples, no flip pairing, no crop, MeanShift the identity, no sigmoid
 int wsc_net_forward_edge_raw(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, float *edge_dev, float *dp_dev) {
     WSC_CHECK(ctx && net && x_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_net_forward_edge_raw: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_net_forward_edge_raw: the network is not an IRNet EdgeDisplacement net");
+    WSC_TRY(need_irn("wsc_net_forward_edge_raw", net));
     WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_forward_edge_raw: N=%d S=%d", N, S);
     WSC_HIP(hipSetDevice(ctx->device));
     EdgeMaps m;
@@ -1452,29 +1479,23 @@ int wsc_net_forward_edge_raw(wsc_ctx *ctx, const wsc_net *net, const float *x_de
 int wsc_net_edge_tape_plan(wsc_ctx *ctx, const wsc_net *net, int N, int S, wsc_tape_entry *entries_out, int max_entries, int *n_out,
                            long long *tape_elems_out) {
     WSC_CHECK(ctx && net && n_out && tape_elems_out, WSC_ERR_INVALID, "wsc_net_edge_tape_plan: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_net_edge_tape_plan: the network is not an IRNet EdgeDisplacement net");
+    WSC_TRY(need_irn("wsc_net_edge_tape_plan", net));
     WSC_CHECK(N > 0 && S > 0 && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
               "wsc_net_edge_tape_plan: N=%d S=%d, room for %d entries", N, S, max_entries);
     EdgeTapePlan tp;
     WSC_TRY(edge_tape_plan(net, N, S, &tp));
-    *n_out = (int)tp.e.size();
-    *tape_elems_out = tp.elems;
-    for (int i = 0; i < max_entries && i < (int)tp.e.size(); ++i) entries_out[i] = tp.e[i];
-    return WSC_OK;
+    return tape_export(tp.t, entries_out, max_entries, n_out, tape_elems_out);
 }
 
 int wsc_net_forward_edge_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, float *tape_dev, long long tape_elems,
                               float *edge_dev, float *dp_dev) {
     WSC_CHECK(ctx && net && x_dev && tape_dev && edge_dev && dp_dev, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_net_forward_edge_tape: the network is not an IRNet EdgeDisplacement net");
+    WSC_TRY(need_irn("wsc_net_forward_edge_tape", net));
     WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: N=%d S=%d", N, S);
     WSC_CHECK(((uintptr_t)tape_dev & 255) == 0, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: the tape must start on a 256-byte line");
     EdgeTapePlan tp;
     WSC_TRY(edge_tape_plan(net, N, S, &tp));
-    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_forward_edge_tape: a tape of %lld floats, the plan has %lld (wsc_net_edge_tape_plan)",
-              tape_elems, tp.elems);
+    WSC_TRY(tape_check("wsc_net_forward_edge_tape", "wsc_net_edge_tape_plan", tape_elems, tp.t));
     WSC_HIP(hipSetDevice(ctx->device));
     EdgeMaps m;
     WSC_TRY(forward_edge_maps(ctx, net, x_dev, N, S, 0, 0, &m, &tp, tape_dev));
@@ -1484,7 +1505,7 @@ int wsc_net_forward_edge_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_d
 // The DeepLab forward pass of SEC / DSRG (create_network up to "fc8-softmax", SEC.py:117-128,246-249 / DSRG.py:169-186,297-300)
 int wsc_net_seg_size_hw(const wsc_net *net, int H, int W, int *h_out, int *w_out) {
     WSC_CHECK(net && h_out && w_out, WSC_ERR_INVALID, "wsc_net_seg_size_hw: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_seg_size_hw: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_TRY(need_seg("wsc_net_seg_size_hw", net));
     WSC_CHECK(H >= 1 && W >= 1, WSC_ERR_INVALID, "wsc_net_seg_size_hw: input %d x %d", H, W);
     Plan pl;
     WSC_TRY(plan_dims(net, 1, H, W, &pl));
@@ -1497,22 +1518,13 @@ int wsc_net_seg_size_hw(const wsc_net *net, int H, int W, int *h_out, int *w_out
 // output of the trunk (the last pool is pool5a), every branch's fc6 and fc7 -- each the value the next op read (hi + lo)
 struct TapePlan {
     Plan pl;
-    std::vector<wsc_tape_entry> e;
+    TapeLayout t;
     std::vector<int> op_entry;   // entry of op i's output
     std::vector<int> fc6, fc7;   // entries of branch k
-    long long elems = 0;
 };
 static int seg_tape_plan(const wsc_net *net, int B, int H, int W, TapePlan *tp) {
     WSC_TRY(plan_dims(net, B, H, W, &tp->pl));
-    auto add = [&](const std::string &name, int Ho, int Wo, int C) {
-        wsc_tape_entry t = {};
-        std::strncpy(t.name, name.c_str(), sizeof(t.name) - 1);
-        t.Ho = Ho; t.Wo = Wo; t.C = C;
-        t.offset = tp->elems;
-        tp->elems += ((long long)B * Ho * Wo * C + 63) / 64 * 64; // (entries start on 256-byte lines)
-        tp->e.push_back(t);
-        return (int)tp->e.size() - 1;
-    };
+    auto add = [&](const std::string &name, int Ho, int Wo, int C) { return tp->t.add(name, B, Ho, Wo, C); };
     add("input", H, W, 3);
     for (size_t i = 0; i < net->ops.size(); ++i) {
         const Op &op = net->ops[i];
@@ -1561,14 +1573,14 @@ static int forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int
     void *extra;
     std::vector<long long> op_off;
     if (tp)
-        for (int e : tp->op_entry) op_off.push_back(tp->e[e].offset);
+        for (int e : tp->op_entry) op_off.push_back(tp->t.off(e));
     const TraceSink sink = {op_off.data(), tape};
     WSC_TRY(run_backbone(ctx, net, x_dev, B, H, extra_bytes, &feat, &hf, &wf, &extra, nullptr, W, true, nullptr, tp ? &sink : nullptr, &xin));
     char *p = (char *)extra;
     if (tp) {
         float *in4 = (float *)(p + extra_bytes - in4_elems * sizeof(float));
         WSC_TRY(launch_act_to_f32(ctx, xin, in4_elems, in4));
-        WSC_TRY(launch_copy_channels(ctx, in4, (long long)B * H * W, 4, 3, tape + tp->e[0].offset));
+        WSC_TRY(launch_copy_channels(ctx, in4, (long long)B * H * W, 4, 3, tape + tp->t.off(0)));
     }
     const Act a6 = act_carve(p, e6, net->prec), a7 = act_carve(p, e7, net->prec);
     const float *logits[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1586,7 +1598,7 @@ static int forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int
         const bool dropping = tp && drop && drop->drop_prob > 0.f;
         auto keep = [&](Act a, int Cout, int entry, unsigned site) -> int {
             if (!tp) return WSC_OK;
-            float *dst = tape + tp->e[entry].offset;
+            float *dst = tape + tp->t.off(entry);
             if (dropping) return launch_seg_dropout(ctx, a, M * Cout, Cout, drop->drop_prob, drop->seed, drop->step, site, dst);
             return launch_act_to_f32(ctx, a, M * Cout, dst);
         };
@@ -1602,7 +1614,7 @@ static int forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int
 int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *fc8_dev,
                         float *prob_dev) {
     WSC_CHECK(ctx && net && x_dev && prob_dev, WSC_ERR_INVALID, "wsc_net_forward_seg: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_TRY(need_seg("wsc_net_forward_seg", net));
     WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg: B=%d input %d x %d min_prob=%g", B, H, W,
               (double)min_prob);
     WSC_HIP(hipSetDevice(ctx->device));
@@ -1612,27 +1624,23 @@ int wsc_net_forward_seg(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, in
 int wsc_net_seg_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W, wsc_tape_entry *entries_out, int max_entries, int *n_out,
                           long long *tape_elems_out) {
     WSC_CHECK(ctx && net && n_out && tape_elems_out, WSC_ERR_INVALID, "wsc_net_seg_tape_plan: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_seg_tape_plan: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_TRY(need_seg("wsc_net_seg_tape_plan", net));
     WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
               "wsc_net_seg_tape_plan: B=%d input %d x %d, room for %d entries", B, H, W, max_entries);
     TapePlan tp;
     WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
-    *n_out = (int)tp.e.size();
-    *tape_elems_out = tp.elems;
-    for (int i = 0; i < max_entries && i < (int)tp.e.size(); ++i) entries_out[i] = tp.e[i];
-    return WSC_OK;
+    return tape_export(tp.t, entries_out, max_entries, n_out, tape_elems_out);
 }
 
 int wsc_net_forward_seg_tape(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float min_prob, float *tape_dev,
                              long long tape_elems, float *fc8_dev, float *prob_dev) {
     WSC_CHECK(ctx && net && x_dev && prob_dev && tape_dev, WSC_ERR_INVALID, "wsc_net_forward_seg_tape: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg_tape: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_TRY(need_seg("wsc_net_forward_seg_tape", net));
     WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg_tape: B=%d input %d x %d min_prob=%g", B, H,
               W, (double)min_prob);
     TapePlan tp;
     WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
-    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_forward_seg_tape: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)",
-              tape_elems, tp.elems);
+    WSC_TRY(tape_check("wsc_net_forward_seg_tape", "wsc_net_seg_tape_plan", tape_elems, tp.t));
     WSC_HIP(hipSetDevice(ctx->device));
     return forward_seg(ctx, net, x_dev, B, H, W, min_prob, fc8_dev, prob_dev, &tp, tape_dev);
 }
@@ -1641,14 +1649,13 @@ int wsc_net_forward_seg_train(wsc_ctx *ctx, const wsc_net *net, const float *x_d
                               unsigned long long seed, long long step, float *tape_dev, long long tape_elems, float *fc8_dev,
                               float *prob_dev) {
     WSC_CHECK(ctx && net && x_dev && prob_dev && tape_dev, WSC_ERR_INVALID, "wsc_net_forward_seg_train: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_forward_seg_train: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_TRY(need_seg("wsc_net_forward_seg_train", net));
     WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && min_prob >= 0.f, WSC_ERR_INVALID, "wsc_net_forward_seg_train: B=%d input %d x %d min_prob=%g", B, H,
               W, (double)min_prob);
     WSC_TRY(seg_dropout_check("wsc_net_forward_seg_train", drop_prob, step));
     TapePlan tp;
     WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
-    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_forward_seg_train: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)",
-              tape_elems, tp.elems);
+    WSC_TRY(tape_check("wsc_net_forward_seg_train", "wsc_net_seg_tape_plan", tape_elems, tp.t));
     WSC_HIP(hipSetDevice(ctx->device));
     SegDropout drop;
     drop.drop_prob = drop_prob; drop.seed = seed; drop.step = (unsigned)step;
@@ -1657,6 +1664,93 @@ int wsc_net_forward_seg_train(wsc_ctx *ctx, const wsc_net *net, const float *x_d
 
 // ---- the backward pass of the DeepLab nets: d loss / d fc8 -> the gradient of every weight and bias -----------------------------
 namespace {
+// What the gradient object of every training path owns: the context and the net it was made for, its device allocations, the ones
+// and zeros of the data-gradient GEMM, the backward workspace, the repack jobs of its load-params entry, the size of its flat
+// layout.  wsc_seg_grad and wsc_irn_grad derive from it and keep only what differs (embed it, do not copy it).
+struct GradCore {
+    const char *kind; // the C type's name, for the messages
+    wsc_ctx *ctx;
+    const wsc_net *net;
+    long long grad_elems = 0;
+    float *ones = nullptr, *zeros = nullptr; // conv_cout_pad(widest input of a data-gradient GEMM) of each
+    void *ws = nullptr;                      // the backward workspace, grown on demand
+    size_t ws_bytes = 0;
+    RepackPlan repack;                       // the jobs of the load-params entry, built by its first call
+    std::vector<void *> allocs;
+    GradCore(const char *kind_, wsc_ctx *ctx_, const wsc_net *net_) : kind(kind_), ctx(ctx_), net(net_) {}
+
+    int own(size_t bytes, void **dst) {
+        WSC_HIP(hipMalloc(dst, bytes));
+        allocs.push_back(*dst);
+        return WSC_OK;
+    }
+    int zeroed(size_t bytes, void **dst) {
+        WSC_TRY(own(bytes, dst));
+        WSC_HIP(hipMemset(*dst, 0, bytes));
+        return WSC_OK;
+    }
+    int upload(const void *host, size_t bytes, void **dst) {
+        WSC_TRY(own(bytes, dst));
+        WSC_HIP(hipMemcpy(*dst, host, bytes, hipMemcpyHostToDevice));
+        return WSC_OK;
+    }
+    int upload(const std::vector<float> &v, float **dst) { return upload(v.data(), v.size() * sizeof(float), (void **)dst); }
+    // `widest` ones and as many zeros
+    int ones_zeros(int widest) {
+        WSC_TRY(upload(std::vector<float>(widest, 1.f), &ones));
+        return upload(std::vector<float>(widest, 0.f), &zeros);
+    }
+    // at least `need` bytes of workspace on the object's stream, wsc_ctx_scratch_fill applied: the workspace is scratch like the
+    // arena -- nothing in it outlives a call
+    int workspace(size_t need) {
+        WSC_HIP(hipSetDevice(ctx->device));
+        if (need > ws_bytes) {
+            if (ws) {
+                WSC_HIP(hipStreamSynchronize(ctx->stream));
+                WSC_HIP(hipFree(ws));
+                ws = nullptr;
+                ws_bytes = 0;
+            }
+            WSC_HIP(hipMalloc(&ws, need));
+            ws_bytes = need;
+        }
+        if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(ws, ctx->scratch_fill, ws_bytes, ctx->stream));
+        return WSC_OK;
+    }
+    // the job table of the load-params entry and the scratch of its channel maxima, once per object (the packed buffers never move)
+    int plan_repack(std::vector<RepackJob> &jobs) {
+        RepackPlan plan;
+        void *jd = nullptr, *pm = nullptr;
+        WSC_TRY(repack_plan(jobs, net->prec, &plan));
+        WSC_TRY(upload(jobs.data(), jobs.size() * sizeof(RepackJob), &jd));
+        if (plan.pmax_elems > 0) WSC_TRY(own((size_t)plan.pmax_elems * sizeof(float), &pm));
+        plan.pmax = (float *)pm;
+        plan.jobs_dev = (RepackJob *)jd;
+        repack = plan;
+        return WSC_OK;
+    }
+    void release() {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : allocs) (void)hipFree(p);
+        if (ws) (void)hipFree(ws);
+    }
+};
+// the arguments every entry that takes a gradient object shares, checked before anything is launched (the workspace and the
+// optimiser's scratch are the object's: one stream uses them, the one release() drains)
+int grad_check(const char *fn, const wsc_ctx *ctx, const GradCore *g, long long elems, bool pointers_ok) {
+    WSC_CHECK(ctx && g && pointers_ok, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "%s: the context is not the one the %s was created on", fn, g->kind);
+    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "%s: buffers of %lld floats, the layout has %lld", fn, elems, g->grad_elems);
+    return WSC_OK;
+}
+// the workspace of GradCore::workspace in 256-byte lines
+struct LineCarver {
+    char *p;
+    static size_t lines(long long elems) { return align_up((size_t)elems * sizeof(float), 256); }
+    float *bytes(size_t n) { float *q = (float *)p; p += n; return q; }
+    float *floats(long long elems) { return bytes(lines(elems)); }
+};
+
 struct GradLayer {
     std::string name;
     int k = 1, Cin = 0, Cout = 0, dil = 1;
@@ -1664,53 +1758,34 @@ struct GradLayer {
     long long w_off = 0, b_off = 0;
 };
 } // namespace
-struct wsc_seg_grad {
-    wsc_ctx *ctx = nullptr;
-    const wsc_net *net = nullptr;
+struct wsc_seg_grad : GradCore {
+    using GradCore::GradCore;
     std::vector<GradLayer> layers; // the trunk's convs in op order, then fc6, fc7, fc8 of every branch
     std::vector<int> op_layer;     // layer of op i, -1 for a pool
-    long long grad_elems = 0;
-    float *ones = nullptr, *zeros = nullptr; // conv_cout_pad(widest layer) of each
-    void *ws = nullptr;            // the backward workspace, grown on demand
-    size_t ws_bytes = 0;
     // the optimiser's view of the layout (seg_sgd.hip): a segment per w and per b in offset order, built once; the partials and
     // the arrival counter of loss["l2"]
     SgdSegment *segs = nullptr;
     int n_segs = 0;
     double *l2_partials = nullptr;
     unsigned *l2_counter = nullptr;
-    RepackPlan repack;             // the per-layer jobs of wsc_net_seg_load_params, built by its first call
-    std::vector<void *> allocs;
 };
 
 void wsc_seg_grad_destroy(wsc_seg_grad *g) {
     if (!g) return;
-    if (g->ctx) (void)hipStreamSynchronize(g->ctx->stream);
-    for (void *p : g->allocs) (void)hipFree(p);
-    if (g->ws) (void)hipFree(g->ws);
+    g->release();
     delete g;
 }
 
 int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_seg_grad **out) {
     WSC_CHECK(ctx && net && weights && out && n_weights > 0, WSC_ERR_INVALID, "wsc_seg_grad_create: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_seg_grad_create: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_TRY(need_seg("wsc_seg_grad_create", net));
     WSC_HIP(hipSetDevice(ctx->device));
     Dict d;
     WSC_TRY(descs_to_dict(weights, n_weights, &d));
-    wsc_seg_grad *g = new wsc_seg_grad();
-    g->ctx = ctx;
-    g->net = net;
+    wsc_seg_grad *g = new wsc_seg_grad("wsc_seg_grad", ctx, net);
     auto fail = [&](int st) {
         wsc_seg_grad_destroy(g);
         return st;
-    };
-    auto up = [&](const std::vector<float> &v, float **dst) -> int {
-        void *p = nullptr;
-        WSC_HIP(hipMalloc(&p, v.size() * sizeof(float)));
-        g->allocs.push_back(p);
-        WSC_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-        *dst = (float *)p;
-        return WSC_OK;
     };
     int widest = 64;
     auto add = [&](const std::string &name, const ConvW &c, bool first) -> int {
@@ -1728,7 +1803,7 @@ int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
         if (!first) {
             std::vector<float> packed;
             dgrad_pack(w.data, L.k, L.Cin, L.Cout, &packed);
-            WSC_TRY(up(packed, &L.w_rot));
+            WSC_TRY(g->upload(packed, &L.w_rot));
             widest = std::max(widest, conv_cout_pad(L.Cin));
         }
         L.w_off = g->grad_elems;
@@ -1753,8 +1828,7 @@ int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
             if (st != WSC_OK) return fail(st);
         }
     }
-    int st = up(std::vector<float>(widest, 1.f), &g->ones);
-    if (st == WSC_OK) st = up(std::vector<float>(widest, 0.f), &g->zeros);
+    int st = g->ones_zeros(widest);
     if (st != WSC_OK) return fail(st);
     // the segment table of the optimiser: lr multipliers 1 (w) / 2 (b), 10 / 20 on fc8 (model.py:393-398, DSRG.py:434-439)
     std::vector<SgdSegment> segs;
@@ -1768,19 +1842,9 @@ int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
         return fail(WSC_ERR_INVALID);
     }
     g->n_segs = (int)segs.size();
-    auto dev_alloc = [&](size_t bytes, void **dst) -> int {
-        WSC_HIP(hipMalloc(dst, bytes));
-        g->allocs.push_back(*dst);
-        WSC_HIP(hipMemset(*dst, 0, bytes));
-        return WSC_OK;
-    };
-    st = dev_alloc(segs.size() * sizeof(SgdSegment), (void **)&g->segs);
-    if (st == WSC_OK && hipMemcpy(g->segs, segs.data(), segs.size() * sizeof(SgdSegment), hipMemcpyHostToDevice) != hipSuccess) {
-        wsc_set_error("wsc_seg_grad_create: the upload of the segment table failed");
-        st = WSC_ERR_HIP;
-    }
-    if (st == WSC_OK) st = dev_alloc(SGD_L2_MAX_BLOCKS * sizeof(double), (void **)&g->l2_partials);
-    if (st == WSC_OK) st = dev_alloc(256, (void **)&g->l2_counter);
+    st = g->upload(segs.data(), segs.size() * sizeof(SgdSegment), (void **)&g->segs);
+    if (st == WSC_OK) st = g->zeroed(SGD_L2_MAX_BLOCKS * sizeof(double), (void **)&g->l2_partials);
+    if (st == WSC_OK) st = g->zeroed(256, (void **)&g->l2_counter);
     if (st != WSC_OK) return fail(st);
     *out = g;
     return WSC_OK;
@@ -1805,17 +1869,12 @@ int wsc_seg_grad_layout(const wsc_seg_grad *g, wsc_grad_entry *entries_out, int 
 // wsc_net_backward_seg (fc_scale 1.0f) and wsc_net_backward_seg_drop (1 / (1 - drop_prob)): the same launches
 static int backward_seg(const char *fn, wsc_ctx *ctx, wsc_seg_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
                         const float *dfc8_dev, float *grad_dev, long long grad_elems, float fc_scale) {
-    WSC_CHECK(ctx && g && tape_dev && dfc8_dev && grad_dev, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_TRY(grad_check(fn, ctx, g, grad_elems, tape_dev && dfc8_dev && grad_dev));
     WSC_CHECK(B >= 1 && H >= 1 && W >= 1, WSC_ERR_INVALID, "%s: B=%d input %d x %d", fn, B, H, W);
-    // (the workspace is the object's: one stream uses it, the one wsc_seg_grad_destroy drains)
-    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "%s: the context is not the one the wsc_seg_grad was created on", fn);
     const wsc_net *net = g->net;
     TapePlan tp;
     WSC_TRY(seg_tape_plan(net, B, H, W, &tp));
-    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "%s: a tape of %lld floats, the plan has %lld (wsc_net_seg_tape_plan)", fn, tape_elems,
-              tp.elems);
-    WSC_CHECK(grad_elems == g->grad_elems, WSC_ERR_INVALID, "%s: a gradient buffer of %lld floats, the layout has %lld", fn, grad_elems,
-              g->grad_elems);
+    WSC_TRY(tape_check(fn, "wsc_net_seg_tape_plan", tape_elems, tp.t));
     // every layer's plan and the workspace they need, before anything is launched
     const int hf = tp.pl.hf, wf = tp.pl.wf;
     const long long M8 = (long long)B * hf * wf;
@@ -1838,27 +1897,13 @@ static int backward_seg(const char *fn, wsc_ctx *ctx, wsc_seg_grad *g, int B, in
         if (g->op_layer[i] >= 0) WSC_TRY(plan_layer((size_t)g->op_layer[i], d.Ho, d.Wo));
     }
     for (size_t li = n_trunk; li < g->layers.size(); ++li) WSC_TRY(plan_layer(li, hf, wf));
-    auto lines = [](long long elems) { return align_up((size_t)elems * sizeof(float), 256); };
-    const size_t sum_bytes = lines(M8 * net->F);
-    const size_t need = 2 * lines(g_max) + 2 * sum_bytes + lines(dz_max) + lines(slab_max) + lines(part_max);
-    WSC_HIP(hipSetDevice(ctx->device));
-    if (need > g->ws_bytes) {
-        if (g->ws) {
-            WSC_HIP(hipStreamSynchronize(ctx->stream));
-            WSC_HIP(hipFree(g->ws));
-            g->ws = nullptr;
-            g->ws_bytes = 0;
-        }
-        WSC_HIP(hipMalloc(&g->ws, need));
-        g->ws_bytes = need;
-    }
-    // (wsc_ctx_scratch_fill: the object's own workspace is scratch like the arena -- nothing in it outlives a call)
-    if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(g->ws, ctx->scratch_fill, g->ws_bytes, ctx->stream));
-    char *p = (char *)g->ws;
-    auto carve = [&](size_t bytes) { float *q = (float *)p; p += bytes; return q; };
-    float *ga = carve(lines(g_max)), *gb = carve(lines(g_max));
-    float *gs[2] = {carve(sum_bytes), carve(sum_bytes)};
-    float *dz = carve(lines(dz_max)), *slab = carve(lines(slab_max)), *partial = carve(lines(part_max));
+    auto lines = LineCarver::lines;
+    const long long sum_elems = M8 * net->F;
+    WSC_TRY(g->workspace(2 * lines(g_max) + 2 * lines(sum_elems) + lines(dz_max) + lines(slab_max) + lines(part_max)));
+    LineCarver ws = {(char *)g->ws};
+    float *ga = ws.floats(g_max), *gb = ws.floats(g_max);
+    float *gs[2] = {ws.floats(sum_elems), ws.floats(sum_elems)};
+    float *dz = ws.floats(dz_max), *slab = ws.floats(slab_max), *partial = ws.floats(part_max);
 
     // one layer at gradient dy of its output [B][h][w][Cout]: db, dW, and (dx non-null) the gradient of its input; scale: 1.0f,
     // or the factor of the dropout site behind the layer (fc6 / fc7: y is then the dropped, scaled tape entry)
@@ -1881,7 +1926,7 @@ static int backward_seg(const char *fn, wsc_ctx *ctx, wsc_seg_grad *g, int B, in
         }
         return dgrad_launch(ctx, dzp, L.w_rot, g->ones, g->zeros, B, h, w, L.Cin, L.Cout, L.k, L.dil, sum_with, dx);
     };
-    auto at = [&](int entry) { return tape_dev + tp.e[entry].offset; };
+    auto at = [&](int entry) { return tape_dev + tp.t.off(entry); };
 
     // the branches, _1 ... _4: each receives dfc8; their gradients into pool5a's output are summed in that order
     const int e_pool5a = tp.op_entry.back();
@@ -1934,51 +1979,31 @@ struct IrnGradHead {
     float *w_rot = nullptr;                    // the data-gradient kernel (dgrad_pack) of a head that reads a concat buffer
 };
 } // namespace
-struct wsc_irn_grad {
-    wsc_ctx *ctx = nullptr;
-    const wsc_net *net = nullptr;
+struct wsc_irn_grad : GradCore {
+    using GradCore::GradCore;
     std::vector<IrnGradHead> heads; // one per net->heads
     long long edge_w_off = 0, edge_b_off = 0, dp_w_off = 0;
     long long dp_start = 0; // the first float of the dp group (train_irn.py:86-90: 10 lr); the edge group lies before it
     float *edge_rot = nullptr, *dp_rot = nullptr;
-    RepackPlan repack;      // the jobs of wsc_net_irn_load_params, built by its first call
-    VecCopyJob *vec_jobs = nullptr;
+    VecCopyJob *vec_jobs = nullptr; // the GroupNorm vectors of wsc_net_irn_load_params, built with its repack jobs
     int n_vec_jobs = 0, vec_blocks = 0;
     std::vector<wsc_grad_entry> layout; // one entry per parameter, in the order of trainable_parameters()
-    long long grad_elems = 0;
-    float *ones = nullptr, *zeros = nullptr; // conv_cout_pad(widest concat buffer) of each
-    void *ws = nullptr;                      // the backward workspace, grown on demand
-    size_t ws_bytes = 0;
-    std::vector<void *> allocs;
 };
 
 void wsc_irn_grad_destroy(wsc_irn_grad *g) {
     if (!g) return;
-    if (g->ctx) (void)hipStreamSynchronize(g->ctx->stream);
-    for (void *p : g->allocs) (void)hipFree(p);
-    if (g->ws) (void)hipFree(g->ws);
+    g->release();
     delete g;
 }
 
 int wsc_irn_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_irn_grad **out) {
     WSC_CHECK(ctx && net && weights && out && n_weights > 0, WSC_ERR_INVALID, "wsc_irn_grad_create: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_irn_grad_create: the network is not an IRNet EdgeDisplacement net");
+    WSC_TRY(need_irn("wsc_irn_grad_create", net));
     WSC_HIP(hipSetDevice(ctx->device));
     Dict d;
     WSC_TRY(descs_to_dict(weights, n_weights, &d));
-    wsc_irn_grad *g = new wsc_irn_grad();
-    g->ctx = ctx;
-    g->net = net;
+    wsc_irn_grad *g = new wsc_irn_grad("wsc_irn_grad", ctx, net);
     g->heads.resize(net->heads.size());
-    auto up = [&](const std::vector<float> &v, float **dst) -> int {
-        void *p = nullptr;
-        WSC_HIP(hipMalloc(&p, v.size() * sizeof(float)));
-        g->allocs.push_back(p);
-        WSC_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-        *dst = (float *)p;
-        return WSC_OK;
-    };
     // `<name>` as torch has it, [Cout][Cin][1][1] (vec: [Cout]); the net's own tensor has that shape
     auto tensor = [&](const std::string &name, int Cout, int Cin, const HostTensor **t) -> int {
         auto it = d.find(name);
@@ -2012,7 +2037,7 @@ int wsc_irn_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
             for (int ci = 0; ci < Cin; ++ci) hwio[(size_t)ci * Cout + co] = w->data[(size_t)co * Cin + ci];
         dgrad_pack(hwio.data(), 1, cin_pad, Cout, &packed);
         widest = std::max(widest, conv_cout_pad(cin_pad));
-        return up(packed, dst);
+        return g->upload(packed, dst);
     };
     auto add_head = [&](size_t j) -> int {
         const IrnHead &h = net->heads[j];
@@ -2045,8 +2070,7 @@ int wsc_irn_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
         WSC_TRY(tensor(net->dp_final + ".weight", 2, cd, &w7));
         WSC_TRY(rot(w7, cd, cd, 2, &g->dp_rot));
         g->dp_w_off = entry(net->dp_final + ".weight", cd, 2);
-        WSC_TRY(up(std::vector<float>(widest, 1.f), &g->ones));
-        return up(std::vector<float>(widest, 0.f), &g->zeros);
+        return g->ones_zeros(widest);
     };
     const int st = build();
     if (st != WSC_OK) {
@@ -2068,18 +2092,13 @@ int wsc_irn_grad_layout(const wsc_irn_grad *g, wsc_grad_entry *entries_out, int 
 
 int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const float *tape_dev, long long tape_elems, const float *dedge_dev,
                           const float *ddp_dev, float *grad_dev, long long grad_elems) {
-    WSC_CHECK(ctx && g && tape_dev && dedge_dev && ddp_dev && grad_dev, WSC_ERR_INVALID, "wsc_net_backward_edge: null argument");
+    WSC_TRY(grad_check("wsc_net_backward_edge", ctx, g, grad_elems, tape_dev && dedge_dev && ddp_dev && grad_dev));
     WSC_CHECK(N > 0 && S > 0, WSC_ERR_INVALID, "wsc_net_backward_edge: N=%d S=%d", N, S);
-    // (the workspace is the object's: one stream uses it, the one wsc_irn_grad_destroy drains)
-    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_net_backward_edge: the context is not the one the wsc_irn_grad was created on");
     WSC_CHECK(((uintptr_t)tape_dev & 255) == 0, WSC_ERR_INVALID, "wsc_net_backward_edge: the tape must start on a 256-byte line");
     const wsc_net *net = g->net;
     EdgeTapePlan tp;
     WSC_TRY(edge_tape_plan(net, N, S, &tp));
-    WSC_CHECK(tape_elems == tp.elems, WSC_ERR_INVALID, "wsc_net_backward_edge: a tape of %lld floats, the plan has %lld (wsc_net_edge_tape_plan)",
-              tape_elems, tp.elems);
-    WSC_CHECK(grad_elems == g->grad_elems, WSC_ERR_INVALID, "wsc_net_backward_edge: a gradient buffer of %lld floats, the layout has %lld",
-              grad_elems, g->grad_elems);
+    WSC_TRY(tape_check("wsc_net_backward_edge", "wsc_net_edge_tape_plan", tape_elems, tp.t));
     const EdgeGeom &eg = tp.g;
     const int NC = (int)net->cats.size(), NH = (int)net->heads.size();
     const long long Me = (long long)N * eg.He * eg.We, Md = (long long)N * eg.Hd * eg.Wd;
@@ -2103,33 +2122,20 @@ int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const flo
         max_groups = std::max(max_groups, h.groups);
     }
     dz_max = std::max(dz_max, dy_max);
-    auto lines = [](long long elems) { return align_up((size_t)elems * sizeof(float), 256); };
-    size_t need = 2 * lines(dy_max > dz_max ? dy_max : dz_max) + lines(xs_max) + lines(slab_max) + lines(2 * std::max(Me, Md)) +
-                  lines(2 * eg.cat_c[0]) + lines(relu_bias_grad_blocks(Me)) + align_up(gpart_max, 256) +
-                  align_up(sizeof(double) * 2 * N * max_groups, 256);
+    auto lines = LineCarver::lines;
+    const size_t gpart_bytes = align_up(gpart_max, 256), ms_bytes = align_up(sizeof(double) * 2 * N * max_groups, 256);
+    size_t need = 2 * lines(dz_max) + lines(xs_max) + lines(slab_max) + lines(2 * std::max(Me, Md)) + lines(2 * eg.cat_c[0]) +
+                  lines(relu_bias_grad_blocks(Me)) + gpart_bytes + ms_bytes;
     for (int i = 0; i < NC; ++i) need += lines((long long)eg.cat_elems[i]);
-    WSC_HIP(hipSetDevice(ctx->device));
-    if (need > g->ws_bytes) {
-        if (g->ws) {
-            WSC_HIP(hipStreamSynchronize(ctx->stream));
-            WSC_HIP(hipFree(g->ws));
-            g->ws = nullptr;
-            g->ws_bytes = 0;
-        }
-        WSC_HIP(hipMalloc(&g->ws, need));
-        g->ws_bytes = need;
-    }
-    // (wsc_ctx_scratch_fill: the object's own workspace is scratch like the arena -- nothing in it outlives a call)
-    if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(g->ws, ctx->scratch_fill, g->ws_bytes, ctx->stream));
-    char *p = (char *)g->ws;
-    auto carve = [&](size_t bytes) { float *q = (float *)p; p += bytes; return q; };
-    float *dy = carve(lines(std::max(dy_max, dz_max))), *dz = carve(lines(std::max(dy_max, dz_max)));
-    float *xs = carve(lines(xs_max)), *slab = carve(lines(slab_max)), *two = carve(lines(2 * std::max(Me, Md)));
-    float *wtmp = carve(lines(2 * eg.cat_c[0])), *partial = carve(lines(relu_bias_grad_blocks(Me)));
-    void *gpart = carve(align_up(gpart_max, 256)), *ms = carve(align_up(sizeof(double) * 2 * N * max_groups, 256));
+    WSC_TRY(g->workspace(need));
+    LineCarver ws = {(char *)g->ws};
+    float *dy = ws.floats(dz_max), *dz = ws.floats(dz_max); // (dz_max >= dy_max)
+    float *xs = ws.floats(xs_max), *slab = ws.floats(slab_max), *two = ws.floats(2 * std::max(Me, Md));
+    float *wtmp = ws.floats(2 * eg.cat_c[0]), *partial = ws.floats(relu_bias_grad_blocks(Me));
+    void *gpart = ws.bytes(gpart_bytes), *ms = ws.bytes(ms_bytes);
     std::vector<float *> dcat(NC);
-    for (int i = 0; i < NC; ++i) dcat[i] = carve(lines((long long)eg.cat_elems[i]));
-    auto at = [&](int entry) { return tape_dev + tp.e[entry].offset; };
+    for (int i = 0; i < NC; ++i) dcat[i] = ws.floats((long long)eg.cat_elems[i]);
+    auto at = [&](int entry) { return tape_dev + tp.t.off(entry); };
 
     // the final edge conv (Cout = 1, bias): the GEMM takes two columns, d_edge and zeros, and column 0 of its result is dW; the
     // padding channels of the edge concat have no entry in the layout
@@ -2170,9 +2176,7 @@ int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const flo
 // ---- the update half of an IRNet step (train_irn.py:86-90, 127-129) and the closing dp_mean pass (148-164); kernels: irn_sgd.hip ----
 int wsc_irn_sgd_step(wsc_ctx *ctx, wsc_irn_grad *g, float *param_dev, const float *grad_dev, float *mom_dev, long long elems, float lr_edge,
                      float lr_dp, float weight_decay, float sgd_momentum) {
-    WSC_CHECK(ctx && g && param_dev && grad_dev && mom_dev, WSC_ERR_INVALID, "wsc_irn_sgd_step: null argument");
-    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_irn_sgd_step: the context is not the one the wsc_irn_grad was created on");
-    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "wsc_irn_sgd_step: buffers of %lld floats, the layout has %lld", elems, g->grad_elems);
+    WSC_TRY(grad_check("wsc_irn_sgd_step", ctx, g, elems, param_dev && grad_dev && mom_dev));
     WSC_CHECK(std::isfinite(lr_edge) && std::isfinite(lr_dp) && std::isfinite(weight_decay) && std::isfinite(sgd_momentum), WSC_ERR_INVALID,
               "wsc_irn_sgd_step: lr_edge %g, lr_dp %g, weight_decay %g, sgd_momentum %g must be finite", (double)lr_edge, (double)lr_dp,
               (double)weight_decay, (double)sgd_momentum);
@@ -2182,12 +2186,9 @@ int wsc_irn_sgd_step(wsc_ctx *ctx, wsc_irn_grad *g, float *param_dev, const floa
 
 int wsc_net_irn_load_params(wsc_ctx *ctx, wsc_net *net, wsc_irn_grad *g, const float *param_dev, long long elems) {
     WSC_CHECK(ctx && net && g && param_dev, WSC_ERR_INVALID, "wsc_net_irn_load_params: null argument");
-    WSC_CHECK(!net->heads.empty() && net->cats.size() >= 2, WSC_ERR_INVALID,
-              "wsc_net_irn_load_params: the network is not an IRNet EdgeDisplacement net");
+    WSC_TRY(need_irn("wsc_net_irn_load_params", net));
     WSC_CHECK(g->net == net, WSC_ERR_INVALID, "wsc_net_irn_load_params: the wsc_irn_grad was created for another net");
-    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "wsc_net_irn_load_params: the context is not the one the wsc_irn_grad was created on");
-    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "wsc_net_irn_load_params: a buffer of %lld floats, the layout has %lld", elems,
-              g->grad_elems);
+    WSC_TRY(grad_check("wsc_net_irn_load_params", ctx, g, elems, true));
     WSC_CHECK(g->heads.size() == net->heads.size(), WSC_ERR_INVALID, "internal: %d heads of the net, %d of the layout", (int)net->heads.size(),
               (int)g->heads.size());
     WSC_HIP(hipSetDevice(ctx->device));
@@ -2224,25 +2225,11 @@ int wsc_net_irn_load_params(wsc_ctx *ctx, wsc_net *net, wsc_irn_grad *g, const f
                   WSC_ERR_INVALID, "internal: the final convs are not the layout's");
         job(net->edge6, g->edge_w_off, g->edge_b_off, net->edge_in, net->edge6.Cin, g->edge_rot);
         job(net->dp7b, g->dp_w_off, -1, net->dp7b.Cin, 0, g->dp_rot);
-        RepackPlan plan;
-        WSC_TRY(repack_plan(jobs, net->prec, &plan));
-        void *jd = nullptr, *pm = nullptr, *vd = nullptr;
-        WSC_HIP(hipMalloc(&jd, jobs.size() * sizeof(RepackJob)));
-        g->allocs.push_back(jd);
-        WSC_HIP(hipMemcpy(jd, jobs.data(), jobs.size() * sizeof(RepackJob), hipMemcpyHostToDevice));
-        if (plan.pmax_elems > 0) {
-            WSC_HIP(hipMalloc(&pm, (size_t)plan.pmax_elems * sizeof(float)));
-            g->allocs.push_back(pm);
-        }
-        WSC_HIP(hipMalloc(&vd, vecs.size() * sizeof(VecCopyJob)));
-        g->allocs.push_back(vd);
-        WSC_HIP(hipMemcpy(vd, vecs.data(), vecs.size() * sizeof(VecCopyJob), hipMemcpyHostToDevice));
-        g->vec_jobs = (VecCopyJob *)vd;
+        // (the vec-copy table first: jobs_dev, what marks the tables as built, is set last)
+        WSC_TRY(g->upload(vecs.data(), vecs.size() * sizeof(VecCopyJob), (void **)&g->vec_jobs));
         g->n_vec_jobs = (int)vecs.size();
         g->vec_blocks = vec_blocks;
-        plan.pmax = (float *)pm;
-        plan.jobs_dev = (RepackJob *)jd;
-        g->repack = plan;
+        WSC_TRY(g->plan_repack(jobs));
     }
     WSC_TRY(repack_launch(ctx, g->repack, param_dev));
     return vec_copy_launch(ctx, g->vec_jobs, g->n_vec_jobs, g->vec_blocks, param_dev);
@@ -2277,18 +2264,9 @@ int wsc_net_get_mean_shift(const wsc_net *net, float m_out[2]) {
 }
 
 // ---- the update half of the training step: Model.optimize() (model.py:379-404) on the layout of wsc_seg_grad_layout ----------------
-namespace {
-int sgd_check(const char *fn, const wsc_ctx *ctx, const wsc_seg_grad *g, long long elems, bool pointers) {
-    WSC_CHECK(ctx && g && pointers, WSC_ERR_INVALID, "%s: null argument", fn);
-    WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "%s: the context is not the one the wsc_seg_grad was created on", fn);
-    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "%s: buffers of %lld floats, the layout has %lld", fn, elems, g->grad_elems);
-    return WSC_OK;
-}
-} // namespace
-
 int wsc_seg_sgd_accumulate(wsc_ctx *ctx, wsc_seg_grad *g, const float *param_dev, const float *grad_dev, float *accum_dev, long long elems,
                            float weight_decay, int accum_num, float *l2_dev) {
-    WSC_TRY(sgd_check("wsc_seg_sgd_accumulate", ctx, g, elems, param_dev && grad_dev && accum_dev));
+    WSC_TRY(grad_check("wsc_seg_sgd_accumulate", ctx, g, elems, param_dev && grad_dev && accum_dev));
     WSC_CHECK(accum_num >= 1, WSC_ERR_INVALID, "wsc_seg_sgd_accumulate: accum_num=%d", accum_num);
     WSC_HIP(hipSetDevice(ctx->device));
     return sgd_accumulate_launch(ctx, g->segs, g->n_segs, param_dev, grad_dev, accum_dev, elems, weight_decay, accum_num, g->l2_partials,
@@ -2297,16 +2275,16 @@ int wsc_seg_sgd_accumulate(wsc_ctx *ctx, wsc_seg_grad *g, const float *param_dev
 
 int wsc_seg_sgd_apply(wsc_ctx *ctx, wsc_seg_grad *g, float *param_dev, float *accum_dev, float *mom_dev, long long elems, float lr,
                       float momentum, int clear_accum) {
-    WSC_TRY(sgd_check("wsc_seg_sgd_apply", ctx, g, elems, param_dev && accum_dev && mom_dev));
+    WSC_TRY(grad_check("wsc_seg_sgd_apply", ctx, g, elems, param_dev && accum_dev && mom_dev));
     WSC_HIP(hipSetDevice(ctx->device));
     return sgd_apply_launch(ctx, param_dev, accum_dev, mom_dev, elems, lr, momentum, clear_accum);
 }
 
 int wsc_net_seg_load_params(wsc_ctx *ctx, wsc_net *net, wsc_seg_grad *g, const float *param_dev, long long elems) {
     WSC_CHECK(ctx && net && g && param_dev, WSC_ERR_INVALID, "wsc_net_seg_load_params: null argument");
-    WSC_CHECK(!net->seg.empty(), WSC_ERR_INVALID, "wsc_net_seg_load_params: the network is not a WSC_ARCH_DEEPLAB_* net");
+    WSC_TRY(need_seg("wsc_net_seg_load_params", net));
     WSC_CHECK(g->net == net, WSC_ERR_INVALID, "wsc_net_seg_load_params: the wsc_seg_grad was created for another net");
-    WSC_TRY(sgd_check("wsc_net_seg_load_params", ctx, g, elems, true));
+    WSC_TRY(grad_check("wsc_net_seg_load_params", ctx, g, elems, true));
     // the layers in the order wsc_seg_grad_create listed them: the trunk's convs in op order, then fc6, fc7, fc8 of every branch
     std::vector<ConvW *> convs;
     for (const Op &op : net->ops)
@@ -2339,19 +2317,7 @@ int wsc_net_seg_load_params(wsc_ctx *ctx, wsc_net *net, wsc_seg_grad *g, const f
             J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
             J.w_rot = L.w_rot;
         }
-        RepackPlan plan;
-        WSC_TRY(repack_plan(jobs, net->prec, &plan));
-        void *jd = nullptr, *pm = nullptr;
-        WSC_HIP(hipMalloc(&jd, jobs.size() * sizeof(RepackJob)));
-        g->allocs.push_back(jd);
-        WSC_HIP(hipMemcpy(jd, jobs.data(), jobs.size() * sizeof(RepackJob), hipMemcpyHostToDevice));
-        if (plan.pmax_elems > 0) {
-            WSC_HIP(hipMalloc(&pm, (size_t)plan.pmax_elems * sizeof(float)));
-            g->allocs.push_back(pm);
-        }
-        plan.pmax = (float *)pm;
-        plan.jobs_dev = (RepackJob *)jd;
-        g->repack = plan;
+        WSC_TRY(g->plan_repack(jobs));
     }
     return repack_launch(ctx, g->repack, param_dev);
 }

@@ -296,6 +296,23 @@ def _ptr(x):
     raise TypeError("cannot take a pointer of %r" % type(x))
 
 
+def _two_call(fn, args, entry_type, extra=0):
+    """The "count, allocate, fill" idiom of every plan / layout entry point: fn(*args, None, 0, &n, &extra...) for the count, then
+    the same call with room for n entries of `entry_type` -> (the entries, the `extra` trailing long long out-parameters)."""
+    n, tail = _i(), [ctypes.c_longlong() for _ in range(extra)]
+    refs = [ctypes.byref(v) for v in [n] + tail]
+    check(fn(*args, None, 0, *refs))
+    ent = (entry_type * n.value)()
+    check(fn(*args, ent, n.value, *refs))
+    return ent, [v.value for v in tail]
+
+
+def _tape_plan(fn, *args):
+    """a wsc_net_*_tape_plan entry point -> ([{'name', 'Ho', 'Wo', 'C', 'offset'}], tape_elems)"""
+    ent, (elems,) = _two_call(fn, args, TapeEntry, 1)
+    return [{"name": e.name.decode(), "Ho": e.Ho, "Wo": e.Wo, "C": e.C, "offset": e.offset} for e in ent], elems
+
+
 class StackChain:
     """One GPU-filling phase at a time across the contexts of a driver's lanes.  `run(ctx, enqueue)` makes what `enqueue()` puts
     on ctx's stream wait -- on the device, wsc_ctx_wait_for_mark -- for the phase the chain ran last on another context.  A conv
@@ -690,11 +707,7 @@ class Net:
         """wsc_net_edge_tape_plan: ([{'name', 'Ho', 'Wo', 'C', 'offset'}], tape_elems) -- what the backward pass of the heads needs
         of a forward pass of N samples of S x S: "x<k>" stage taps, "<head>.z", "<head>.stats" ([N][1][1][2 G] {mean, rstd}
         pairs), "cat<i>" concat buffers, float32 at `offset` floats of one buffer of tape_elems floats."""
-        n, elems = _i(), ctypes.c_longlong()
-        check(self.ctx._lib.wsc_net_edge_tape_plan(self.ctx.h, self.h, int(N), int(S), None, 0, ctypes.byref(n), ctypes.byref(elems)))
-        ent = (TapeEntry * n.value)()
-        check(self.ctx._lib.wsc_net_edge_tape_plan(self.ctx.h, self.h, int(N), int(S), ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
-        return [{"name": e.name.decode(), "Ho": e.Ho, "Wo": e.Wo, "C": e.C, "offset": e.offset} for e in ent], elems.value
+        return _tape_plan(self.ctx._lib.wsc_net_edge_tape_plan, self.ctx.h, self.h, int(N), int(S))
 
     def forward_edge_tape(self, x_dev, N, S, tape_dev, tape_elems, edge_dev, dp_dev, ctx=None):
         """wsc_net_forward_edge_tape: forward_edge_raw (the same bits) that also fills tape_dev (float32, tape_elems of them)."""
@@ -725,11 +738,7 @@ class Net:
     def seg_tape_plan(self, B, H, W):
         """wsc_net_seg_tape_plan: ([{'name', 'Ho', 'Wo', 'C', 'offset'}], tape_elems) -- the tensors a backward pass needs of a
         forward pass of a B x H x W input, float32 NHWC at `offset` floats of one buffer of tape_elems floats."""
-        n, elems = _i(), ctypes.c_longlong()
-        check(self.ctx._lib.wsc_net_seg_tape_plan(self.ctx.h, self.h, int(B), int(H), int(W), None, 0, ctypes.byref(n), ctypes.byref(elems)))
-        ent = (TapeEntry * n.value)()
-        check(self.ctx._lib.wsc_net_seg_tape_plan(self.ctx.h, self.h, int(B), int(H), int(W), ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
-        return [{"name": e.name.decode(), "Ho": e.Ho, "Wo": e.Wo, "C": e.C, "offset": e.offset} for e in ent], elems.value
+        return _tape_plan(self.ctx._lib.wsc_net_seg_tape_plan, self.ctx.h, self.h, int(B), int(H), int(W))
 
     def forward_seg_tape(self, x_dev, B, H, W, tape_dev, tape_elems, prob_dev, fc8_dev=None, min_prob=1e-4, ctx=None):
         """wsc_net_forward_seg_tape: forward_seg with the tape's tensors copied to tape_dev (float32, tape_elems of them)."""
@@ -749,10 +758,7 @@ class Net:
         """wsc_net_trace_plan: one dict per op of the stack for an N x H x W input (+ the CAM head), the fields of wsc_trace_op
         (`in` under its own name, the label as str).  Follows the options of `ctx` (the fused stem)."""
         run = ctx or self.ctx
-        n = _i()
-        check(self.ctx._lib.wsc_net_trace_plan(run.h, self.h, int(N), int(H), int(W), None, 0, ctypes.byref(n)))
-        ops = (TraceOp * n.value)()
-        check(self.ctx._lib.wsc_net_trace_plan(run.h, self.h, int(N), int(H), int(W), ops, n.value, ctypes.byref(n)))
+        ops, _ = _two_call(self.ctx._lib.wsc_net_trace_plan, (run.h, self.h, int(N), int(H), int(W)), TraceOp)
         out = []
         for o in ops:
             d = {name.rstrip("_"): getattr(o, name) for name, _ in TraceOp._fields_ if name != "label"}
@@ -768,29 +774,26 @@ class Net:
                                                   int(trace_elems)))
 
 
-class SegGrad:
-    """wsc_seg_grad: what the backward pass of one ARCH_DEEPLAB_* net keeps (the data-gradient kernels, the workspace).
-    state_dict: the one the net was created from.  The net must outlive it."""
+class _Grad:
+    """The handle of a wsc_<KIND>_grad: created from the net and the state dict the net was created from, `grad_elems` and the
+    entries of wsc_<KIND>_grad_layout (a subclass shapes them into its `layout`), close() / __del__.  The net must outlive it."""
+    KIND = None  # "seg" / "irn"
 
     def __init__(self, net, state_dict):
         self.ctx = net.ctx
         self.net = net
+        lib = self.ctx._lib
         descs, keep = make_tensor_descs(state_dict)
         h = _vp()
-        check(self.ctx._lib.wsc_seg_grad_create(self.ctx.h, net.h, descs, len(descs), ctypes.byref(h)))
+        check(getattr(lib, "wsc_%s_grad_create" % self.KIND)(self.ctx.h, net.h, descs, len(descs), ctypes.byref(h)))
         del keep
         self.h = h
-        n, elems = _i(), ctypes.c_longlong()
-        check(self.ctx._lib.wsc_seg_grad_layout(h, None, 0, ctypes.byref(n), ctypes.byref(elems)))
-        ent = (GradEntry * n.value)()
-        check(self.ctx._lib.wsc_seg_grad_layout(h, ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
-        # layer -> its kernel, channels and the float offsets of dW (HWIO) and db in the gradient buffer
-        self.layout = {e.name.decode(): {"k": e.kh, "Cin": e.Cin, "Cout": e.Cout, "w_off": e.w_off, "b_off": e.b_off} for e in ent}
-        self.grad_elems = elems.value
+        ent, (self.grad_elems,) = _two_call(getattr(lib, "wsc_%s_grad_layout" % self.KIND), (h,), GradEntry, 1)
+        self.layout = self._shape_layout(ent)
 
     def close(self):
         if getattr(self, "h", None) and self.ctx.h:
-            self.ctx._lib.wsc_seg_grad_destroy(self.h)  # (drains the stream)
+            getattr(self.ctx._lib, "wsc_%s_grad_destroy" % self.KIND)(self.h)  # (drains the stream)
         self.h = None
 
     def __del__(self):
@@ -799,81 +802,75 @@ class SegGrad:
         except Exception:
             pass
 
+    def _elems(self, elems):
+        return int(self.grad_elems if elems is None else elems)
+
+
+class SegGrad(_Grad):
+    """wsc_seg_grad: what the backward pass of one ARCH_DEEPLAB_* net keeps (the data-gradient kernels, the workspace).
+    state_dict: the one the net was created from.  The net must outlive it."""
+    KIND = "seg"
+
+    @staticmethod
+    def _shape_layout(ent):
+        # layer -> its kernel, channels and the float offsets of dW (HWIO) and db in the gradient buffer
+        return {e.name.decode(): {"k": e.kh, "Cin": e.Cin, "Cout": e.Cout, "w_off": e.w_off, "b_off": e.b_off} for e in ent}
+
     def backward(self, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, grad_elems=None):
         """wsc_net_backward_seg: dfc8_dev float32 [B][h][w][C] -> every element of grad_dev (self.grad_elems floats), on the
         net's own context (the workspace belongs to its stream)."""
         check(self.ctx._lib.wsc_net_backward_seg(self.ctx.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfc8_dev),
-                                                 _ptr(grad_dev), int(self.grad_elems if grad_elems is None else grad_elems)))
+                                                 _ptr(grad_dev), self._elems(grad_elems)))
 
     def backward_drop(self, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, drop_prob, grad_elems=None):
         """wsc_net_backward_seg_drop: backward() on a tape of forward_seg_train at `drop_prob`."""
         check(self.ctx._lib.wsc_net_backward_seg_drop(self.ctx.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems),
                                                       _ptr(dfc8_dev), _ptr(grad_dev),
-                                                      int(self.grad_elems if grad_elems is None else grad_elems), float(drop_prob)))
+                                                      self._elems(grad_elems), float(drop_prob)))
 
     def sgd_accumulate(self, param_dev, grad_dev, accum_dev, weight_decay, accum_num, l2_dev=None, elems=None, ctx=None):
         """wsc_seg_sgd_accumulate on three buffers of self.grad_elems floats in self.layout: accum += mult (grad [+ weight_decay
         param on weights]) / accum_num; l2_dev (optional, one float) receives loss["l2"]."""
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_seg_sgd_accumulate(run.h, self.h, _ptr(param_dev), _ptr(grad_dev), _ptr(accum_dev),
-                                                   int(self.grad_elems if elems is None else elems), float(weight_decay), int(accum_num),
+                                                   self._elems(elems), float(weight_decay), int(accum_num),
                                                    _ptr(l2_dev)))
 
     def sgd_apply(self, param_dev, accum_dev, mom_dev, lr, momentum, clear_accum=True, elems=None, ctx=None):
         """wsc_seg_sgd_apply: mom = mom momentum + accum, param -= lr mom, and (clear_accum) accum = 0."""
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_seg_sgd_apply(run.h, self.h, _ptr(param_dev), _ptr(accum_dev), _ptr(mom_dev),
-                                              int(self.grad_elems if elems is None else elems), float(lr), float(momentum), int(bool(clear_accum))))
+                                              self._elems(elems), float(lr), float(momentum), int(bool(clear_accum))))
 
     def load_params(self, param_dev, elems=None, net=None, ctx=None):
         """wsc_net_seg_load_params: the net's packed weights and this object's data-gradient kernels rewritten on the device from
         the flat parameter buffer.  The net must not be in use on another stream."""
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_seg_load_params(run.h, (net or self.net).h, self.h, _ptr(param_dev),
-                                                    int(self.grad_elems if elems is None else elems)))
+                                                    self._elems(elems)))
 
 
-class IrnGrad:
+class IrnGrad(_Grad):
     """wsc_irn_grad: what the backward pass of the heads of one ARCH_*_IRN net keeps (the data-gradient kernels, the workspace).
     state_dict: the one the net was created from.  The net must outlive it.
     layout: [{'name', 'shape', 'offset', 'size', 'conv'}] one per parameter in the order of trainable_parameters(), `shape`
     torch's ((Cout, Cin, 1, 1) or (C,)); a conv weight lies as [Cin][Cout] at its offset."""
+    KIND = "irn"
 
-    def __init__(self, net, state_dict):
-        self.ctx = net.ctx
-        self.net = net
-        descs, keep = make_tensor_descs(state_dict)
-        h = _vp()
-        check(self.ctx._lib.wsc_irn_grad_create(self.ctx.h, net.h, descs, len(descs), ctypes.byref(h)))
-        del keep
-        self.h = h
-        n, elems = _i(), ctypes.c_longlong()
-        check(self.ctx._lib.wsc_irn_grad_layout(h, None, 0, ctypes.byref(n), ctypes.byref(elems)))
-        ent = (GradEntry * n.value)()
-        check(self.ctx._lib.wsc_irn_grad_layout(h, ent, n.value, ctypes.byref(n), ctypes.byref(elems)))
-        self.layout = []
+    @staticmethod
+    def _shape_layout(ent):
+        layout = []
         for e in ent:
             conv = e.kh == 1
-            self.layout.append({"name": e.name.decode(), "conv": conv, "shape": (e.Cout, e.Cin, 1, 1) if conv else (e.Cout,),
-                                "offset": e.w_off if conv else e.b_off, "size": e.Cin * e.Cout if conv else e.Cout})
-        self.grad_elems = elems.value
-
-    def close(self):
-        if getattr(self, "h", None) and self.ctx.h:
-            self.ctx._lib.wsc_irn_grad_destroy(self.h)  # (drains the stream)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            layout.append({"name": e.name.decode(), "conv": conv, "shape": (e.Cout, e.Cin, 1, 1) if conv else (e.Cout,),
+                           "offset": e.w_off if conv else e.b_off, "size": e.Cin * e.Cout if conv else e.Cout})
+        return layout
 
     def backward(self, N, S, tape_dev, tape_elems, dedge_dev, ddp_dev, grad_dev, grad_elems=None, ctx=None):
         """wsc_net_backward_edge on the net's own context (the workspace belongs to its stream; `ctx`: another one is an error)."""
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_backward_edge(run.h, self.h, int(N), int(S), _ptr(tape_dev), int(tape_elems), _ptr(dedge_dev),
-                                                  _ptr(ddp_dev), _ptr(grad_dev), int(self.grad_elems if grad_elems is None else grad_elems)))
+                                                  _ptr(ddp_dev), _ptr(grad_dev), self._elems(grad_elems)))
 
 
     def flat_params(self, state_dict):
@@ -898,7 +895,7 @@ class IrnGrad:
         p -= lr m with lr_edge on the `fc_edge*` entries and lr_dp on the rest, every product and sum one fp32 rounding."""
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_irn_sgd_step(run.h, self.h, _ptr(param_dev), _ptr(grad_dev), _ptr(mom_dev),
-                                             int(self.grad_elems if elems is None else elems), float(lr_edge), float(lr_dp),
+                                             self._elems(elems), float(lr_edge), float(lr_dp),
                                              float(weight_decay), float(sgd_momentum)))
 
     def load_params(self, param_dev, elems=None, net=None, ctx=None):
@@ -907,7 +904,7 @@ class IrnGrad:
         stream."""
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_irn_load_params(run.h, (net or self.net).h, self.h, _ptr(param_dev),
-                                                    int(self.grad_elems if elems is None else elems)))
+                                                    self._elems(elems)))
 
 
 def channel_mean_nchw(ctx, x_dev, N, C, H, W, out_dev, sub=None):

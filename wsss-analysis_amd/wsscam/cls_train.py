@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from .misc.imutils import default_context
-from .secdsrg import DeviceMaps
+from .secdsrg import DeviceMaps, device_operand
 
 K_EPSILON = 1e-7  # K.epsilon()
 POOLS = {"mean": _lib.CLS_POOL_MEAN, "max": _lib.CLS_POOL_MAX}
@@ -60,19 +60,7 @@ class ClsLoss:
             raise ValueError("ClsLoss: num_classes = %d (1 .. 64)" % self.C)
 
     def _maps(self, name, a, shape, held):
-        if isinstance(a, DeviceMaps):
-            if a.dtype != np.float32:
-                raise ValueError("ClsLoss: %s is %s on the device, not float32" % (name, a.dtype))
-        else:
-            a = np.asarray(a)
-            if a.dtype.kind not in "fiub":
-                raise ValueError("ClsLoss: %s has dtype %s, not a real number type" % (name, a.dtype))
-        if shape is not None and tuple(a.shape) != tuple(shape):
-            raise ValueError("ClsLoss: %s has shape %r, expected %r" % (name, tuple(a.shape), tuple(shape)))
-        if isinstance(a, DeviceMaps):
-            return a
-        held.append(DeviceMaps.from_host(self.ctx, a, dtype=np.float32))
-        return held[-1]
+        return device_operand(self, self.ctx, name, a, np.float32, shape, held)
 
     def _run(self, feat, w, bias, targets, sample_weight, want_grad):
         ctx, held, grads = self.ctx, [], None

@@ -26,7 +26,7 @@ import numpy as np
 from . import _lib
 from .misc import imutils
 from .misc.torchutils import PolyOptimizer
-from .secdsrg import DeviceMaps
+from .secdsrg import DeviceMaps, Freed, device_operand
 
 
 def reduce_label(label):
@@ -38,7 +38,7 @@ def reduce_label(label):
     return np.ascontiguousarray(imutils.pil_rescale(label.astype(np.uint8), 0.25, 0))
 
 
-class EdgeTape:
+class EdgeTape(Freed):
     """The tape of EdgeDisplacement.forward_train_dev(x, keep=True): `maps` one float32 DeviceMaps of `elems` floats, `entries`
     the plan of Net.edge_tape_plan for N samples of S x S.  entry(name) downloads one tensor ([N][Ho][Wo][C]); free() / a
     context manager releases the buffer."""
@@ -51,18 +51,8 @@ class EdgeTape:
         e = next(e for e in self.entries if e["name"] == name)
         return self.maps.ctx.to_host(self.maps.buf, (self.N, e["Ho"], e["Wo"], e["C"]), np.float32, offset_bytes=4 * e["offset"])
 
-    def free(self):
-        self.maps.free()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
-
-
-class IrnGrads:
+class IrnGrads(Freed):
     """The gradient of every trainable parameter of an EdgeDisplacement net, on the device: `maps` one float32 DeviceMaps and
     `layout`, _lib.IrnGrad.layout ([{'name', 'shape', 'offset', 'size', 'conv'}] in the order of trainable_parameters(); a conv
     weight lies as [Cin][Cout] at its offset).  ptr(name) is a parameter's device address; to_state_dict() downloads everything
@@ -89,16 +79,6 @@ class IrnGrads:
             out[e["name"]] = np.ascontiguousarray(v)
         return out
 
-    def free(self):
-        self.maps.free()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
-
 
 class AffinityLoss:
     """The IRNet training loss on the device.
@@ -124,21 +104,7 @@ class AffinityLoss:
         self.ctx = ctx or imutils.default_context()
 
     def _maps(self, name, a, dtype, shape, held):
-        """-> DeviceMaps of `dtype`; shape: a tuple to match, or a function that says whether the shape fits"""
-        if isinstance(a, DeviceMaps):
-            if a.dtype != np.dtype(dtype):
-                raise ValueError("AffinityLoss: %s is %s on the device, not %s" % (name, a.dtype, np.dtype(dtype)))
-        else:
-            a = np.asarray(a)
-            if a.dtype.kind not in "fiub":
-                raise ValueError("AffinityLoss: %s has dtype %s, not a real number type" % (name, a.dtype))
-        got = tuple(a.shape)
-        if not (shape(got) if callable(shape) else got == tuple(shape)):
-            raise ValueError("AffinityLoss: %s has shape %r%s" % (name, got, "" if callable(shape) else ", expected %r" % (tuple(shape),)))
-        if isinstance(a, DeviceMaps):
-            return a
-        held.append(DeviceMaps.from_host(self.ctx, a, dtype=dtype))
-        return held[-1]
+        return device_operand(self, self.ctx, name, a, dtype, shape, held)
 
     def __call__(self, edge_out, dp_out, label, want_grad=True):
         ctx, held, grads = self.ctx, [], []

@@ -37,7 +37,21 @@ from . import _lib
 from .misc.imutils import default_context, prefetched
 
 
-class DeviceMaps:
+class Freed:
+    """free() on exit of a `with` block; free() itself releases `maps`, the one DeviceMaps a holder class wraps."""
+
+    def free(self):
+        self.maps.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+class DeviceMaps(Freed):
     """A C-contiguous array in ONE pooled device buffer of a context: `shape`, `dtype`, `.ptr` (device address), `.to_host()`,
     `.free()`; a context manager frees it on exit.  The buffer is pooled, so it belongs to its context's stream alone.
     A packed ragged batch of uint8 images (SegNet.preprocess_dev(keep_images=True)) also carries `sizes` [(h, w)] and `offsets`
@@ -74,15 +88,30 @@ class DeviceMaps:
             self.buf.free()
             self.buf = None
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.free()
-        return False
+def device_operand(owner, ctx, name, a, dtype, shape, held):
+    """One operand of a loss class as a DeviceMaps of `dtype`: a DeviceMaps is checked and read in place, a host array is uploaded
+    once and the upload appended to `held` (the caller frees those).  shape: a tuple to match, a function that says whether the
+    shape fits, or None.  A wrong dtype or shape is a ValueError that names the class of `owner` and the argument `name`."""
+    who, dtype = type(owner).__name__, np.dtype(dtype)
+    on_device = isinstance(a, DeviceMaps)
+    if on_device:
+        if a.dtype != dtype:
+            raise ValueError("%s: %s is %s on the device, not %s" % (who, name, a.dtype, dtype))
+    else:
+        a = np.asarray(a)
+        if a.dtype.kind not in "fiub":
+            raise ValueError("%s: %s has dtype %s, not a real number type" % (who, name, a.dtype))
+    got = tuple(a.shape)
+    if shape is not None and not (shape(got) if callable(shape) else got == tuple(shape)):
+        raise ValueError("%s: %s has shape %r%s" % (who, name, got, "" if callable(shape) else ", expected %r" % (tuple(shape),)))
+    if on_device:
+        return a
+    held.append(DeviceMaps.from_host(ctx, a, dtype=dtype))
+    return held[-1]
 
 
-class SegGrads:
+class SegGrads(Freed):
     """The gradient of every weight and bias of a SegNet, on the device: one float32 DeviceMaps (`maps`) and the `layout`
     {layer: {'k', 'Cin', 'Cout', 'w_off', 'b_off'}} (offsets in floats).  grads[layer] downloads that layer as {'w': HWIO array,
     'b': [Cout] array}; .ptr(layer, 'w' | 'b') is the device address for a trainer that wraps the buffer; .to_host() every layer
@@ -116,16 +145,6 @@ class SegGrads:
             out[layer] = {which: flat[e[which + "_off"]:e[which + "_off"] + int(np.prod(self._shape(layer, which)))]
                           .reshape(self._shape(layer, which)).copy() for which in ("w", "b")}
         return out
-
-    def free(self):
-        self.maps.free()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
 
 
 def _image_blocks(images):
@@ -337,24 +356,7 @@ class SegLoss:
         return self._weights[n]
 
     def _maps(self, name, a, shape, held):
-        """-> DeviceMaps of `shape` (None: any (B, h, w, C)); an upload of this call is appended to `held`"""
-        if isinstance(a, DeviceMaps):
-            if a.dtype != np.float32:
-                raise ValueError("SegLoss: %s is %s on the device, not float32" % (name, a.dtype))
-            got = a.shape
-        else:
-            a = np.asarray(a)
-            if a.dtype.kind not in "fiub":
-                raise ValueError("SegLoss: %s has dtype %s, not a real number type" % (name, a.dtype))
-            got = a.shape
-        if name == "labels" and got == (shape[0], 1, 1, shape[1]):
-            got = shape
-        if (shape is None and (len(got) != 4 or got[3] != self.C or 0 in got)) or (shape is not None and tuple(got) != tuple(shape)):
-            raise ValueError("SegLoss: %s has shape %r, expected %s" % (name, tuple(a.shape), "(B, h, w, %d)" % self.C if shape is None else (shape,)))
-        if isinstance(a, DeviceMaps):
-            return a
-        held.append(DeviceMaps.from_host(self.ctx, a, dtype=np.float32))
-        return held[-1]
+        return device_operand(self, self.ctx, name, a, np.float32, shape, held)
 
     def __call__(self, prob, crf, cues, labels=None, want_grad="fc8"):
         if want_grad not in ("fc8", "prob", None):
@@ -364,11 +366,11 @@ class SegLoss:
             raise ValueError("SegLoss: labels is None: SEC's expand loss reads the image labels")
         ctx, held, grad = self.ctx, [], None
         try:
-            p = self._maps("prob", prob, None, held)
+            p = self._maps("prob", prob, lambda s: len(s) == 4 and s[3] == self.C and 0 not in s, held)  # any (B, h, w, C)
             B, h, w, C = p.shape
             q = self._maps("crf", crf, p.shape, held)
             cu = self._maps("cues", cues, p.shape, held)
-            lab = self._maps("labels", labels, (B, C), held) if sec else None
+            lab = self._maps("labels", labels, lambda s: s in ((B, C), (B, 1, 1, C)), held) if sec else None
             w_fg, z_fg, w_bg, z_bg = self.weights(h * w) if sec else (None, 0.0, None, 0.0)
             loss_dev = DeviceMaps(ctx, (len(_lib.SEG_LOSS_SLOTS),), np.float64)
             held.append(loss_dev)
