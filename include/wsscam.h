@@ -871,7 +871,8 @@ int wsc_irn_aff_loss(wsc_ctx *ctx, const float *edge_dev, const float *dp_dev, c
 /* ---- 01_train: the loss head of the classifier with the gradient through the head, and the score side of predict() -----------
  * wsc_cls_loss is model.compile(loss='binary_crossentropy', metrics=['binary_accuracy', f1]) (01_train/demo.py:60-61,
  * utilities.py:69-97) on the head global pool -> Dense -> sigmoid, with the gradient of the loss through that head.  The backward
- * pass through the plain stacks, BatchNorm in training mode, the Nesterov SGD / cyclic-LR step and the generators are not here.
+ * pass through the plain stacks and BatchNorm in training mode follow below (wsc_net_backward_cls); the Nesterov SGD / cyclic-LR
+ * step and the generators are not here.
  *   feat_dev      float32 [B][n][F]  the NHWC map the head reduces, as wsc_net_forward_features writes it; n = h w
  *   pool          WSC_CLS_POOL_MEAN: the mean over the n positions (VGG16);  WSC_CLS_POOL_MAX: their maximum (M7) -- the two
  *                 cases of wsc_gap_linear_sigmoid
@@ -953,6 +954,83 @@ enum { WSC_CLS_COUNT_TP = 0, WSC_CLS_COUNT_FP, WSC_CLS_COUNT_TN, WSC_CLS_COUNT_F
 int wsc_cls_threshold_counts(wsc_ctx *ctx, const float *score_dev, const float *target_dev, int N, int C, const float *thresh_dev,
                              int64_t *counts_dev /* [C][WSC_CLS_COUNT_N] */);
 int wsc_cls_scores_append(wsc_ctx *ctx, const float *src_dev, long long elems, float *dst_dev);
+
+/* ---- 01_train: training-mode forward and backward pass of the plain stacks (WSC_ARCH_VGG16_CAM / WSC_ARCH_M7_CAM) ---------------
+ * The graph is common_cnn.make_layers' (03b_irn/net/common_cnn.py:128-141): conv(bias) -> ReLU -> BatchNorm(eps = 1e-3) per entry,
+ * the max pools between (MaxPool2d(2, 2), or the rows of `pool_spec`).  The `D` dropout entries of VGG16's layer5 are the IDENTITY
+ * here (drop_prob = 0); the Nesterov SGD / cyclic-LR step, the repack of updated weights, the data generators and Keras' list
+ * class_weight are not here.  wsc_cls_loss hands out d loss / d feat on the last feature map (and the gradient of the classifier's
+ * Linear); wsc_net_backward_cls carries it to every conv and BatchNorm parameter in exact fp32 whatever the forward precision.  The
+ * definition is the chain rule EVALUATED AT THE TAPE, as for the other two nets: a ReLU passes dy where its kept output is > 0, a
+ * max pool sends a window's dy to the window's first maximum in row-major window order (recomputed from its kept input; padding is
+ * never a candidate; overlapping windows add in window order), BatchNorm's backward takes xh = (a - mean) rstd from the taped input
+ * and the taped float {mean, rstd}; no gradient is formed for the network input.
+ *
+ * wsc_batch_norm_train_nhwc: BatchNorm in training mode on a_dev float32 [M][C] (M = N H W), asynchronous on the ctx stream.
+ *   Per channel the mean and the POPULATION variance are accumulated in double in one fixed order (per-block partial sums of
+ *   a - a[0][c] and its square, the last block to arrive -- an integer ticket -- adds them in block order): no floating-point atomic,
+ *   two calls give the same bits.  stats_dev float32 [C][2] = {mean, rstd}, rstd = 1 / sqrt(var + eps) formed in double, each
+ *   rounded once.  y_dev float32 [M][C] = fma((a - mean) rstd, gamma, beta) in fp32 from those floats (the difference and the
+ *   product one rounding each).  gamma_dev / beta_dev float32 [C] on the device.
+ *   run_dev: NULL, or float32 [2][C] (running mean, then running variance), updated in place:
+ *     run = keep run + (1 - keep) batch, in double from the unrounded batch value, rounded once; with `unbiased` the batch variance
+ *     is multiplied by M / (M - 1) first.  `keep` IS THE WEIGHT OF THE OLD VALUE: Keras' BatchNormalization(momentum = 0.99) is
+ *     keep = 0.99, while the torch port's nn.BatchNorm2d(v, eps=0.001, momentum=0.99) (common_cnn.py:138) weighs the NEW value
+ *     with its momentum, i.e. keep = 0.01.  KERAS 2.2'S OWN FACTOR ON THE MOVING VARIANCE IS UNPINNED; the contract is torch's /
+ *     TensorFlow's fused batch norm: unbiased = 1.
+ *   WSC_ERR_INVALID before any launch: a NULL among a_dev, gamma_dev, beta_dev, stats_dev, y_dev; C no multiple of 4 or > 1024;
+ *   M < 1 or >= 2^31; M == 1 with `unbiased`; eps < 0 or not finite; keep outside [0, 1] with run_dev given; a_dev / y_dev not
+ *   16-byte aligned.
+ * wsc_batch_norm_grad_nhwc: its backward pass from a_dev, the taped stats_dev (nothing is recomputed), gamma_dev and the gradient
+ *   dy_dev [M][C] of y:  dbeta = sum dy;  dgamma = sum dy xh, xh = (a - mean) rstd in fp32;  both sums in double in that one fixed
+ *   order, rounded once;  da = (gamma rstd) ((dy - mb) - xh mg) in fp32 with mb = float(sum dy / M), mg = float(sum dy xh / M).
+ * wsc_pool_tf_grad_nhwc / wsc_maxpool_grad_nhwc: the gradient of wsc_pool_tf_nhwc (window 2 / 3, stride 1 / 2, SAME / VALID) and of
+ *   wsc_maxpool_nhwc (torch's MaxPool2d(k, stride, pad)) at x_dev [N][H][W][C] (C a multiple of 8) for dy_dev of the pool's output
+ *   size -> every element of dx_dev [N][H][W][C], by the tie rule above.  A pixel no window covers (a VALID pool's last row) is +0.0.
+ *
+ * The tape: wsc_net_cls_tape_plan lists, for a B x H x W input, "input" ([B][H][W][3]); per conv "<state-dict key>" (e.g.
+ * "vgg16.layer1.0"), its post-ReLU output; on a BatchNorm net also "<key>.bn", the normalised output, and "<key>.stats"
+ * ([1][1][1][2 C]: the {mean, rstd} float pairs); "pool:<i>" -- float32 NHWC at `offset` floats of one buffer of *tape_elems_out
+ * floats, each the value the next op read (hi + lo of a two-plane precision); entries start on 256-byte lines and the floats
+ * between them are not written; max_entries = 0 for the count.  Any other net is WSC_ERR_INVALID.
+ * wsc_net_forward_cls_train: x_dev float32 [B][3][H][W] -> tape_dev (256-byte aligned) and feat_dev float32 [B][h][w][F], the map
+ *   wsc_cls_loss reads.  The convolutions run in the net's precision on the packed weights, with the ReLU epilogue and without the
+ *   folded inference affine; BatchNorm takes the batch statistics of wsc_batch_norm_train_nhwc on the taped fp32 output with the
+ *   net's gamma / beta and stores into the net's activation type through the store of the GroupNorm heads (the same fmaf; an
+ *   IEEE-half plane that saturates raises the range flag).  run_dev: NULL, or the running statistics of all BatchNorm layers in
+ *   stack order, layer l's [2][C_l] block behind those of the layers before it, updated in place.  On a net without BatchNorm the
+ *   launches and the bits of feat_dev are wsc_net_forward_features'.  WSC_ERR_INVALID before any launch: a net of another arch, a
+ *   NULL pointer, a tape size other than the plan's, keep outside [0, 1], unbiased other than 0 / 1, `unbiased` with a BatchNorm
+ *   layer whose map is 1 x 1 at B = 1.
+ * wsc_cls_grad: the rotated fp32 kernels of the data-gradient convolutions (packed once from `weights`, the list wsc_net_create
+ *   took; a tensor that is not the net's is WSC_ERR_SHAPE naming the layer) and the backward workspace (grown on demand; it belongs
+ *   to the stream of the ctx the object was created on).  The net must outlive the object.  wsc_cls_grad_layout: ONE ENTRY PER
+ *   PARAMETER in net.common.plain_module_order, under state-dict names -- per conv `<key>.weight`, `<key>.bias`, then its
+ *   BatchNorm's `<bn>.weight`, `<bn>.bias`.  A conv weight has kh = kw = 3, its Cin / Cout, w_off its first float and b_off = -1;
+ *   it lies as [3][3][Cin][Cout] (what the GEMM writes: torch's [Cout][Cin][3][3] transposed).  A vector has kh = kw = 0, Cin = 0,
+ *   Cout its length, b_off its first float and w_off = -1 (the convention of wsc_irn_grad_layout).  No gaps.  The classifier's
+ *   Linear has no entry: its gradient is wsc_cls_loss's.
+ * wsc_net_backward_cls: dfeat_dev float32 [B][h][w][F] -> every element of grad_dev (16-byte aligned both).  Asynchronous on the
+ *   ctx stream (the first call at a larger size allocates the workspace).  A ctx other than the object's, a tape or gradient size
+ *   other than the plan's / the layout's is WSC_ERR_INVALID before any launch.  Two calls give the same bits. */
+int wsc_batch_norm_train_nhwc(wsc_ctx *ctx, const float *a_dev, long long M, int C, const float *gamma_dev, const float *beta_dev, float eps,
+                              float keep, int unbiased, float *run_dev /* [2][C] or NULL */, float *stats_dev /* [C][2] */, float *y_dev);
+int wsc_batch_norm_grad_nhwc(wsc_ctx *ctx, const float *a_dev, const float *stats_dev, const float *gamma_dev, const float *dy_dev, long long M,
+                             int C, float *da_dev, float *dgamma_dev, float *dbeta_dev);
+int wsc_pool_tf_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int k, int stride, int same,
+                          float *dx_dev);
+int wsc_maxpool_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int k, int stride, int pad,
+                          float *dx_dev);
+int wsc_net_cls_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W, wsc_tape_entry *entries_out, int max_entries, int *n_out,
+                          long long *tape_elems_out);
+int wsc_net_forward_cls_train(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float keep, int unbiased,
+                              float *run_dev /* or NULL */, float *tape_dev, long long tape_elems, float *feat_dev);
+typedef struct wsc_cls_grad wsc_cls_grad;
+int wsc_cls_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_cls_grad **out);
+void wsc_cls_grad_destroy(wsc_cls_grad *g);
+int wsc_cls_grad_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out);
+int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                         const float *dfeat_dev, float *grad_dev, long long grad_elems);
 
 /* ---- backward pass of the IRNet heads: total_loss.backward() of step/train_irn.py:127 ------------------------------------------
  * Net.forward detaches every backbone stage (resnet50_irn.py:111-115) and trainable_parameters() is edge_layers + dp_layers, so

@@ -707,3 +707,13 @@ int launch_strided_rows_f32(wsc_ctx *ctx, const float *x, int N, int H, int W, i
 // ddp [N][2][HW] -> out [N HW][Cd], zeros past channel 1
 int launch_dp_to_nhwc(wsc_ctx *ctx, const float *ddp, int N, int HW, int Cd, float *out);
 
+// ---- cls_grad.hip: BatchNorm in training mode on a [M][C] fp32 matrix (the contract: its header and include/wsscam.h) -----------
+// stats [C] float {mean, rstd} pairs of the batch; run: null, or [2][C] running mean / variance updated in place with `keep` the
+// weight of the old value; y (or null: the statistics alone) = fma((a - mean) rstd, gamma, beta), gn_affine's expression.  The
+// scratch is a cached block of the ctx.  C a multiple of 4 up to 1024, M < 2^31
+int launch_batch_norm_train(wsc_ctx *ctx, const float *a, long long M, int C, const float *gamma, const float *beta, float eps, float keep,
+                            int unbiased, float *run, float *stats, float *y);
+// da [M][C], dgamma [C], dbeta [C] from the input a, the forward pass's float statistics and the gradient dy of the output
+int launch_batch_norm_grad(wsc_ctx *ctx, const float *a, const float *stats, const float *gamma, const float *dy, long long M, int C,
+                           float *da, float *dgamma, float *dbeta);
+

@@ -37,6 +37,15 @@ struct ConvW {
     int Cin = 0, Cout = 0, CoutPad = 0, kh = 1, kw = 1, stride = 1, pad = 0, relu = 0;
     int dil = 1; // dilation (tf.nn.atrous_conv2d's rate); make_conv leaves 1, the DeepLab builder sets it
     ConvForm form = CONV_FORM_GENERIC;
+    int bn = -1; // plain stacks: the layer's BatchNorm in wsc_net::bns (s2 / b2 is its inference form), -1 without one
+};
+// the BatchNorm behind a conv -> ReLU of a plain stack as the training pass needs it (wsc_net_forward_cls_train): the affine
+// parameters themselves, not folded with the running statistics
+struct PlainBn {
+    std::string name;                        // the state-dict prefix: `<name>.{weight,bias,running_mean,running_var}`
+    float *gamma = nullptr, *beta = nullptr; // device, [C]
+    int C = 0;
+    float eps = 1e-3f;
 };
 
 // one Conv2d(1x1, bias=False) -> GroupNorm -> [Upsample] -> ReLU head of the IRNet branches
@@ -102,6 +111,7 @@ struct wsc_net {
     int edge_in = 0;             // input channels of the final edge conv before the padding to cats[0].channels
     float mean_shift[2] = {0.f, 0.f};
     std::vector<SegBranch> seg;  // WSC_ARCH_DEEPLAB_*: one branch (LFOV, SEC) or four (ASPP, DSRG); fc8 = their sum
+    std::vector<PlainBn> bns;    // the BatchNorm layers of a plain stack in stack order (ConvW::bn)
     std::vector<void *> allocs;
 };
 
@@ -482,6 +492,13 @@ int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
                     std::vector<float> s2, b2;
                     WSC_TRY(fold_bn(d, bn, v, 1e-3, s2, b2));
                     WSC_TRY(make_conv(net, w, 1, 1, 1, first ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, one, bb, &s2, &b2, &c));
+                    PlainBn pb; // (fold_bn has checked the tensors)
+                    pb.name = bn; pb.C = v;
+                    if (has(d, bn + ".eps")) pb.eps = d.at(bn + ".eps").data[0];
+                    WSC_TRY(upload(net, d.at(bn + ".weight").data, v * sizeof(float), (void **)&pb.gamma));
+                    WSC_TRY(upload(net, d.at(bn + ".bias").data, v * sizeof(float), (void **)&pb.beta));
+                    c.bn = (int)net->bns.size();
+                    net->bns.push_back(pb);
                     idx += 3;
                 } else {
                     WSC_TRY(make_conv(net, w, 1, 1, 1, first ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, one, bb, nullptr, nullptr, &c));
@@ -865,13 +882,40 @@ struct TraceSink {
     float *out;
 };
 
+// wsc_net_forward_cls_train's part of run_backbone: where op i's BatchNorm finds its input a (the trace copy of the conv's output)
+// and leaves its statistics and the value the next op reads, all in the caller's tape; the running statistics (or null)
+struct BnTrainSink {
+    const long long *a_off, *stats_off, *y_off; // per op, floats into `tape`
+    float *tape;
+    float keep;
+    int unbiased;
+    float *run; // [2][C] per BatchNorm layer in stack order, or null
+};
+// a [M][C] -> the batch statistics; the activation `act` = the normalised output through the store the GroupNorm heads use (one
+// "sample" of M pixels, every channel a group of its own: the same fmaf on the same float statistics, the planes' split and the
+// range flag of every other activation store); the tape's entry = the fp32 value those planes hold
+int bn_train_step(wsc_ctx *ctx, const wsc_net *net, const BnTrainSink &s, int op, long long M, Act act) {
+    const PlainBn &bn = net->bns[net->convs[net->ops[op].conv].bn];
+    const float *a = s.tape + s.a_off[op];
+    float *stats = s.tape + s.stats_off[op], *run = nullptr;
+    if (s.run) {
+        run = s.run;
+        for (int k = 0; k < net->convs[net->ops[op].conv].bn; ++k) run += 2 * net->bns[k].C;
+    }
+    WSC_TRY(launch_batch_norm_train(ctx, a, M, bn.C, bn.gamma, bn.beta, bn.eps, s.keep, s.unbiased, run, stats, nullptr));
+    WSC_TRY(launch_group_norm_apply(ctx, a, stats, bn.gamma, bn.beta, 1, (int)M, 1, bn.C, bn.C, 1, 0, act, (int)M, 1, bn.C, 0));
+    return launch_act_to_f32(ctx, act, (size_t)M * bn.C, s.tape + s.y_off[op]);
+}
+
 // Runs the conv stack on N samples; *feat is the final feature map.  *extra: `extra_bytes` of workspace for the caller.  With
 // `taps` the stage outputs x1..x5 (net->taps) are copied to the start of that region, in stage order, and *extra is what
 // follows them -- the rotating activation buffers are overwritten as the stack proceeds.
 int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, int S, size_t extra_bytes, Act *feat, int *hf, int *wf,
                  void **extra, std::vector<Act> *taps = nullptr, int SW = 0, bool nhwc_in = false, Act *spare = nullptr,
-                 const TraceSink *trace = nullptr, Act *xin_out = nullptr) {
+                 const TraceSink *trace = nullptr, Act *xin_out = nullptr, const BnTrainSink *bn_train = nullptr) {
     // (trace: copies between the launches, nothing else -- the launches are the ones of a run without it)
+    // (bn_train: the training form of a plain stack -- a conv runs without its post-ReLU affine, and behind the trace copy of its
+    // output the BatchNorm of the batch statistics rewrites the activation; a net without BatchNorm launches what it launches without)
     // (xin_out: the NHWC4 input activation the first op reads; no op writes it)
     // (spare: a rotating buffer other than *feat, free once the stack has run -- any tensor no larger than the feature map fits)
     // (nhwc_in: x_dev is [N][S][SW][3] instead of [N][3][S][SW] -- the DeepLab nets take TensorFlow's layout)
@@ -929,6 +973,7 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             }
             L.N = N; L.H = d.H; L.W = d.W; L.Ho = d.Ho; L.Wo = d.Wo;
             if (c.form == CONV_FORM_STEM_ROWS && op.in < 0) on_padded_input(L, in_h, in_w);
+            if (bn_train) L.s2 = L.b2 = nullptr;
             WSC_TRY(conv_igemm_launch(ctx, L));
         } else if (op.type == OP_GATHER) {
             WSC_TRY(launch_gather_strided(ctx, src, N, d.H, d.W, d.C, op.ps, d.Ho, d.Wo, buf[op.out].at(op.coff), op.pitch));
@@ -938,6 +983,8 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             WSC_TRY(launch_pool(ctx, src, N, d.H, d.W, d.C, g, buf[op.out]));
         }
         if (trace && trace->off[i] >= 0) WSC_TRY(launch_act_to_f32(ctx, buf[op.out], pl.out_elems(N, (int)i), trace->out + trace->off[i]));
+        if (bn_train && op.type == OP_CONV && net->convs[op.conv].bn >= 0)
+            WSC_TRY(bn_train_step(ctx, net, *bn_train, (int)i, (long long)N * d.Ho * d.Wo, buf[op.out]));
         if (taps)
             for (size_t k = 0; k < net->taps.size(); ++k)
                 if (net->taps[k] == (int)i) {
@@ -2467,6 +2514,262 @@ int wsc_irn_edge_finish(wsc_ctx *ctx, const float *e_dev, int He, int We, const 
     WSC_CHECK(B > 0 && fh > 0 && fw > 0, WSC_ERR_INVALID, "wsc_irn_edge_finish: B=%d, feature size %d x %d", B, fh, fw);
     WSC_HIP(hipSetDevice(ctx->device));
     return launch_edge_finish(ctx, e_dev, He, We, d_dev, Hd, Wd, B, fh, fw, ms0, ms1, edge_dev, dp_dev); // (checks fh, fw against the maps)
+}
+
+// ---- 01_train: the plain stacks (VGG16 / M7) in training mode, and their backward pass ------------------------------------------
+// The graph is common_cnn.make_layers': conv(bias) -> ReLU -> BatchNorm(eps = 1e-3) per entry, the pools between, the `D` entries of
+// VGG16's layer5 the identity (drop_prob = 0).  wsc_cls_loss hands out d loss / d feat on the last feature map; the pass below
+// carries it to every conv and BatchNorm parameter.  Kernels: cls_grad.hip (BatchNorm), pool.hip, seg_grad.hip (the GEMMs).
+namespace {
+int need_cls(const char *fn, const wsc_net *net) {
+    WSC_CHECK(net->arch == WSC_ARCH_VGG16_CAM || net->arch == WSC_ARCH_M7_CAM, WSC_ERR_INVALID,
+              "%s: the network is not a WSC_ARCH_VGG16_CAM / WSC_ARCH_M7_CAM net", fn);
+    return WSC_OK;
+}
+// "input"; per conv "<key>" (its post-ReLU output) and, with BatchNorm, "<key>.bn" (the normalised output) and "<key>.stats"
+// ([1][1][1][2 C] {mean, rstd} pairs); "pool:<i>" -- each the value the next op read
+struct ClsTapePlan {
+    Plan pl;
+    TapeLayout t;
+    std::vector<int> a, stats, out; // per op: the conv's post-ReLU entry and its statistics (-1 without), the entry the next op read
+};
+int cls_tape_plan(const wsc_net *net, int B, int H, int W, ClsTapePlan *tp) {
+    WSC_TRY(plan_dims(net, B, H, W, &tp->pl));
+    tp->t.add("input", B, H, W, 3);
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        const Op &op = net->ops[i];
+        const OpDims &d = tp->pl.ops[i];
+        WSC_CHECK(op.type != OP_GATHER && op.res < 0 && op.in2 < 0 && op.pitch == 0 && (i == 0 ? op.in < 0 : op.in == net->ops[i - 1].out) &&
+                      !(op.type == OP_POOL && op.avg),
+                  WSC_ERR_INVALID, "internal: op %d of a plain stack is no link of a chain", (int)i);
+        const int first = tp->t.add(op.label, B, d.Ho, d.Wo, d.Co);
+        const bool bn = op.type == OP_CONV && net->convs[op.conv].bn >= 0;
+        tp->a.push_back(op.type == OP_CONV ? first : -1);
+        tp->out.push_back(bn ? tp->t.add(op.label + ".bn", B, d.Ho, d.Wo, d.Co) : first);
+        tp->stats.push_back(bn ? tp->t.add(op.label + ".stats", 1, 1, 1, 2 * d.Co) : -1);
+    }
+    return WSC_OK;
+}
+int cls_shape_check(const char *fn, int B, int H, int W, const float *tape_dev) {
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1, WSC_ERR_INVALID, "%s: B=%d input %d x %d", fn, B, H, W);
+    WSC_CHECK(((uintptr_t)tape_dev & 255) == 0, WSC_ERR_INVALID, "%s: the tape must start on a 256-byte line", fn);
+    return WSC_OK;
+}
+} // namespace
+
+int wsc_net_cls_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W, wsc_tape_entry *entries_out, int max_entries, int *n_out,
+                          long long *tape_elems_out) {
+    WSC_CHECK(ctx && net && n_out && tape_elems_out, WSC_ERR_INVALID, "wsc_net_cls_tape_plan: null argument");
+    WSC_TRY(need_cls("wsc_net_cls_tape_plan", net));
+    WSC_CHECK(B >= 1 && H >= 1 && W >= 1 && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
+              "wsc_net_cls_tape_plan: B=%d input %d x %d, room for %d entries", B, H, W, max_entries);
+    ClsTapePlan tp;
+    WSC_TRY(cls_tape_plan(net, B, H, W, &tp));
+    return tape_export(tp.t, entries_out, max_entries, n_out, tape_elems_out);
+}
+
+int wsc_net_forward_cls_train(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float keep, int unbiased,
+                              float *run_dev, float *tape_dev, long long tape_elems, float *feat_dev) {
+    const char *fn = "wsc_net_forward_cls_train";
+    WSC_CHECK(ctx && net && x_dev && tape_dev && feat_dev, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_TRY(need_cls(fn, net));
+    WSC_TRY(cls_shape_check(fn, B, H, W, tape_dev));
+    WSC_CHECK(keep >= 0.f && keep <= 1.f && (unbiased == 0 || unbiased == 1), WSC_ERR_INVALID,
+              "%s: keep = %g (the weight of the old running value, 0 .. 1), unbiased = %d (0 / 1)", fn, (double)keep, unbiased);
+    ClsTapePlan tp;
+    WSC_TRY(cls_tape_plan(net, B, H, W, &tp));
+    WSC_TRY(tape_check(fn, "wsc_net_cls_tape_plan", tape_elems, tp.t));
+    std::vector<long long> a_off, stats_off, y_off;
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        const OpDims &d = tp.pl.ops[i];
+        WSC_CHECK(!(unbiased && tp.stats[i] >= 0 && (long long)B * d.Ho * d.Wo == 1), WSC_ERR_INVALID,
+                  "%s: BatchNorm '%s' sees one value per channel: the unbiased running variance needs more", fn, net->ops[i].label.c_str());
+        a_off.push_back(tp.t.off(tp.a[i] >= 0 ? tp.a[i] : tp.out[i])); // (what the op itself wrote)
+        stats_off.push_back(tp.stats[i] >= 0 ? tp.t.off(tp.stats[i]) : -1);
+        y_off.push_back(tp.t.off(tp.out[i]));
+    }
+    WSC_HIP(hipSetDevice(ctx->device));
+    const TraceSink sink = {a_off.data(), tape_dev};
+    const BnTrainSink bn = {a_off.data(), stats_off.data(), y_off.data(), tape_dev, keep, unbiased, run_dev};
+    // (behind the stack's buffers: the NHWC4 input as fp32 on its way to the tape's 3-channel entry)
+    const size_t in4_elems = (size_t)B * H * W * 4;
+    Act feat, xin;
+    int hf, wf;
+    void *extra;
+    WSC_TRY(run_backbone(ctx, net, x_dev, B, H, in4_elems * sizeof(float), &feat, &hf, &wf, &extra, nullptr, W, false, nullptr, &sink, &xin, &bn));
+    WSC_TRY(launch_act_to_f32(ctx, xin, in4_elems, (float *)extra));
+    WSC_TRY(launch_copy_channels(ctx, (const float *)extra, (long long)B * H * W, 4, 3, tape_dev + tp.t.off(0)));
+    return launch_act_to_f32(ctx, feat, (size_t)B * hf * wf * net->F, feat_dev);
+}
+
+namespace {
+struct ClsGradLayer {
+    int Cin = 0, Cout = 0, bn = -1;
+    float *w_rot = nullptr; // the data-gradient kernel (dgrad_pack); null for the first layer: no gradient goes to the input
+    long long w_off = 0, b_off = 0, g_off = -1, be_off = -1; // conv weight [3][3][Cin][Cout], conv bias, BatchNorm weight, BatchNorm bias
+};
+} // namespace
+struct wsc_cls_grad : GradCore {
+    using GradCore::GradCore;
+    std::vector<ClsGradLayer> layers;   // the convs in op order
+    std::vector<int> op_layer;          // layer of op i, -1 for a pool
+    std::vector<wsc_grad_entry> layout; // one entry per parameter, in plain_module_order
+};
+
+void wsc_cls_grad_destroy(wsc_cls_grad *g) {
+    if (!g) return;
+    g->release();
+    delete g;
+}
+
+int wsc_cls_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc *weights, int n_weights, wsc_cls_grad **out) {
+    WSC_CHECK(ctx && net && weights && out && n_weights > 0, WSC_ERR_INVALID, "wsc_cls_grad_create: null argument");
+    WSC_TRY(need_cls("wsc_cls_grad_create", net));
+    WSC_HIP(hipSetDevice(ctx->device));
+    Dict d;
+    WSC_TRY(descs_to_dict(weights, n_weights, &d));
+    wsc_cls_grad *g = new wsc_cls_grad("wsc_cls_grad", ctx, net);
+    // `<name>` as torch has it, [Cout][Cin][3][3] (Cin = 0: a vector [Cout]); the net's own tensor has that shape
+    auto tensor = [&](const std::string &name, int Cout, int Cin, const HostTensor **t) -> int {
+        auto it = d.find(name);
+        WSC_CHECK(it != d.end() && it->second.data != nullptr, WSC_ERR_SHAPE, "layer '%s': missing", name.c_str());
+        const HostTensor &w = it->second;
+        const bool ok = Cin > 0 ? (w.ndim == 4 && w.shape[0] == Cout && w.shape[1] == Cin && w.shape[2] == 3 && w.shape[3] == 3)
+                                : (w.ndim == 1 && w.shape[0] == Cout);
+        WSC_CHECK(ok, WSC_ERR_SHAPE, "layer '%s': the net has it as [%d]%s, got ndim %d [%lld][%lld][%lld][%lld]", name.c_str(), Cout,
+                  Cin > 0 ? ("[" + std::to_string(Cin) + "][3][3]").c_str() : "", w.ndim, (long long)w.shape[0], (long long)w.shape[1],
+                  (long long)w.shape[2], (long long)w.shape[3]);
+        *t = &w;
+        return WSC_OK;
+    };
+    auto entry = [&](const std::string &name, int Cin, int Cout) {
+        wsc_grad_entry e = {};
+        std::strncpy(e.name, name.c_str(), sizeof(e.name) - 1);
+        e.kh = e.kw = Cin > 0 ? 3 : 0;
+        e.Cin = Cin; e.Cout = Cout;
+        e.w_off = Cin > 0 ? g->grad_elems : -1;
+        e.b_off = Cin > 0 ? -1 : g->grad_elems;
+        g->layout.push_back(e);
+        const long long at = g->grad_elems;
+        g->grad_elems += Cin > 0 ? 9ll * Cin * Cout : Cout; // (no gaps: every float of the buffer is some parameter's)
+        return at;
+    };
+    int widest = 64;
+    auto build = [&]() -> int {
+        for (size_t i = 0; i < net->ops.size(); ++i) {
+            const Op &op = net->ops[i];
+            g->op_layer.push_back(op.type == OP_CONV ? (int)g->layers.size() : -1);
+            if (op.type != OP_CONV) continue;
+            const ConvW &c = net->convs[op.conv];
+            WSC_CHECK(c.kh == 3 && c.kw == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 && c.relu, WSC_ERR_INVALID,
+                      "internal: layer '%s' is no 3 x 3 stride-1 SAME convolution with a ReLU", op.label.c_str());
+            ClsGradLayer L;
+            L.Cin = i == 0 ? 3 : c.Cin; L.Cout = c.Cout; L.bn = c.bn;
+            const HostTensor *w, *b;
+            WSC_TRY(tensor(op.label + ".weight", L.Cout, L.Cin, &w));
+            WSC_TRY(tensor(op.label + ".bias", L.Cout, 0, &b));
+            if (i > 0) { // OIHW -> HWIO -> the rotated kernel
+                std::vector<float> hwio((size_t)9 * L.Cin * L.Cout), packed;
+                for (int co = 0; co < L.Cout; ++co)
+                    for (int ci = 0; ci < L.Cin; ++ci)
+                        for (int t = 0; t < 9; ++t) hwio[((size_t)t * L.Cin + ci) * L.Cout + co] = w->data[((size_t)co * L.Cin + ci) * 9 + t];
+                dgrad_pack(hwio.data(), 3, L.Cin, L.Cout, &packed);
+                WSC_TRY(g->upload(packed, &L.w_rot));
+                widest = std::max(widest, conv_cout_pad(L.Cin));
+            }
+            L.w_off = entry(op.label + ".weight", L.Cin, L.Cout);
+            L.b_off = entry(op.label + ".bias", 0, L.Cout);
+            if (L.bn >= 0) {
+                const HostTensor *ga, *be;
+                const std::string &bn = net->bns[L.bn].name;
+                WSC_TRY(tensor(bn + ".weight", L.Cout, 0, &ga));
+                WSC_TRY(tensor(bn + ".bias", L.Cout, 0, &be));
+                L.g_off = entry(bn + ".weight", 0, L.Cout);
+                L.be_off = entry(bn + ".bias", 0, L.Cout);
+            }
+            g->layers.push_back(L);
+        }
+        return g->ones_zeros(widest);
+    };
+    const int st = build();
+    if (st != WSC_OK) {
+        wsc_cls_grad_destroy(g);
+        return st;
+    }
+    *out = g;
+    return WSC_OK;
+}
+
+int wsc_cls_grad_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out) {
+    WSC_CHECK(g && n_out && grad_elems_out && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
+              "wsc_cls_grad_layout: null argument");
+    *n_out = (int)g->layout.size();
+    *grad_elems_out = g->grad_elems;
+    for (int i = 0; i < max_entries && i < (int)g->layout.size(); ++i) entries_out[i] = g->layout[i];
+    return WSC_OK;
+}
+
+int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                         const float *dfeat_dev, float *grad_dev, long long grad_elems) {
+    const char *fn = "wsc_net_backward_cls";
+    WSC_TRY(grad_check(fn, ctx, g, grad_elems, tape_dev && dfeat_dev && grad_dev));
+    WSC_TRY(cls_shape_check(fn, B, H, W, tape_dev));
+    WSC_CHECK(((uintptr_t)dfeat_dev & 15) == 0 && ((uintptr_t)grad_dev & 15) == 0, WSC_ERR_INVALID, "%s: dfeat_dev / grad_dev must be 16-byte aligned", fn);
+    const wsc_net *net = g->net;
+    ClsTapePlan tp;
+    WSC_TRY(cls_tape_plan(net, B, H, W, &tp));
+    WSC_TRY(tape_check(fn, "wsc_net_cls_tape_plan", tape_elems, tp.t));
+    // every layer's plan and the workspace they need, before anything is launched
+    std::vector<WgradPlan> plans(g->layers.size());
+    long long g_max = 0, dz_max = 0, slab_max = 0, part_max = 0;
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        const OpDims &d = tp.pl.ops[i];
+        g_max = std::max(g_max, (long long)B * d.H * d.W * d.C);
+        if (g->op_layer[i] < 0) continue;
+        const size_t li = (size_t)g->op_layer[i];
+        const ClsGradLayer &L = g->layers[li];
+        WSC_TRY(wgrad_plan(ctx, B, d.Ho, d.Wo, L.Cin, L.Cout, 3, 1, 0, &plans[li]));
+        const long long M = (long long)B * d.Ho * d.Wo;
+        dz_max = std::max(dz_max, M * L.Cout);
+        slab_max = std::max(slab_max, plans[li].slab_elems);
+        part_max = std::max(part_max, (long long)relu_bias_grad_blocks(M) * L.Cout);
+    }
+    auto lines = LineCarver::lines;
+    WSC_TRY(g->workspace(2 * lines(g_max) + 2 * lines(dz_max) + lines(slab_max) + lines(part_max)));
+    LineCarver ws = {(char *)g->ws};
+    float *gfree[2] = {ws.floats(g_max), ws.floats(g_max)};
+    float *dbn = ws.floats(dz_max), *dz = ws.floats(dz_max), *slab = ws.floats(slab_max), *partial = ws.floats(part_max);
+    auto at = [&](int entry) { return tape_dev + tp.t.off(entry); };
+
+    const float *gcur = dfeat_dev; // the gradient of op i's output (behind its BatchNorm, where it has one)
+    int nf = 0;
+    for (int i = (int)net->ops.size() - 1; i >= 0; --i) {
+        const Op &op = net->ops[i];
+        const OpDims &d = tp.pl.ops[i];
+        const float *x = at(i == 0 ? 0 : tp.out[i - 1]);
+        float *gout = gfree[nf];
+        if (op.type == OP_POOL) {
+            PoolGeom pg;
+            WSC_CHECK(pool_geom(op.rule, op.pk, op.ps, op.pp, op.avg, d.H, d.W, &pg), WSC_ERR_INVALID, "internal: a pool plan_dims let through");
+            WSC_TRY(launch_pool_grad(ctx, x, gcur, B, d.H, d.W, d.C, pg, gout));
+        } else {
+            const size_t li = (size_t)g->op_layer[i];
+            const ClsGradLayer &L = g->layers[li];
+            const long long M = (long long)B * d.Ho * d.Wo;
+            const float *a = at(tp.a[i]);
+            if (L.bn >= 0) {
+                WSC_TRY(launch_batch_norm_grad(ctx, a, at(tp.stats[i]), net->bns[L.bn].gamma, gcur, M, L.Cout, dbn, grad_dev + L.g_off,
+                                               grad_dev + L.be_off));
+                gcur = dbn;
+            }
+            WSC_TRY(launch_relu_bias_grad(ctx, a, gcur, M, L.Cout, 1.0f, dz, partial, grad_dev + L.b_off));
+            WSC_TRY(wgrad_launch(ctx, plans[li], x, dz, d.Ho, d.Wo, L.Cin, L.Cout, 3, 1, slab, grad_dev + L.w_off));
+            if (i > 0) WSC_TRY(dgrad_launch(ctx, dz, L.w_rot, g->ones, g->zeros, B, d.Ho, d.Wo, L.Cin, L.Cout, 3, 1, nullptr, gout));
+        }
+        gcur = gout;
+        nf ^= 1;
+    }
+    return WSC_OK;
 }
 
 } // extern "C"

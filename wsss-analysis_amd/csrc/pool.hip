@@ -402,4 +402,30 @@ int wsc_pool_same_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_de
     return launch_pool_grad(ctx, x_dev, dy_dev, N, H, W, C, g, dx_dev);
 }
 
+int wsc_pool_tf_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int k, int stride, int same,
+                          float *dx_dev) {
+    WSC_TRY(check_tensor("wsc_pool_tf_grad_nhwc", ctx, x_dev, dx_dev, N, H, W, C, WSC_PREC_F32));
+    WSC_CHECK(dy_dev != nullptr, WSC_ERR_INVALID, "wsc_pool_tf_grad_nhwc: null argument");
+    WSC_CHECK((k == 2 || k == 3) && (stride == 1 || stride == 2) && stride <= k && (same == 0 || same == 1), WSC_ERR_INVALID,
+              "wsc_pool_tf_grad_nhwc: window %d stride %d same %d (window 2 / 3, stride 1 / 2, same 0 / 1)", k, stride, same);
+    PoolGeom g;
+    WSC_CHECK(pool_geom(same ? POOL_TF_SAME : POOL_TF_VALID, k, stride, 0, false, H, W, &g), WSC_ERR_INVALID,
+              "wsc_pool_tf_grad_nhwc: %d x %d x %d x %d is no input of a %d x %d %s window", N, H, W, C, k, k, same ? "SAME" : "VALID");
+    WSC_HIP(hipSetDevice(ctx->device));
+    return launch_pool_grad(ctx, x_dev, dy_dev, N, H, W, C, g, dx_dev);
+}
+
+int wsc_maxpool_grad_nhwc(wsc_ctx *ctx, const float *x_dev, const float *dy_dev, int N, int H, int W, int C, int k, int stride, int pad,
+                          float *dx_dev) {
+    WSC_TRY(check_tensor("wsc_maxpool_grad_nhwc", ctx, x_dev, dx_dev, N, H, W, C, WSC_PREC_F32));
+    WSC_CHECK(dy_dev != nullptr, WSC_ERR_INVALID, "wsc_maxpool_grad_nhwc: null argument");
+    WSC_CHECK(k >= 1 && stride >= 1 && pad >= 0 && 2 * pad <= k, WSC_ERR_INVALID,
+              "wsc_maxpool_grad_nhwc: window %d stride %d padding %d (padding at most half the window)", k, stride, pad);
+    PoolGeom g;
+    WSC_CHECK(H + 2 * pad >= k && W + 2 * pad >= k && pool_geom(POOL_TORCH, k, stride, pad, false, H, W, &g), WSC_ERR_INVALID,
+              "wsc_maxpool_grad_nhwc: a %d x %d map is smaller than the window %d", H, W, k);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return launch_pool_grad(ctx, x_dev, dy_dev, N, H, W, C, g, dx_dev);
+}
+
 } // extern "C"

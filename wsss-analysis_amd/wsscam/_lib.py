@@ -141,6 +141,17 @@ _SIGNATURES = {
     "wsc_roc_thresholds": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "wsc_cls_threshold_counts": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "wsc_cls_scores_append": (_i, [_vp, _vp, ctypes.c_longlong, _vp]),
+    "wsc_batch_norm_train_nhwc": (_i, [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp]),
+    "wsc_batch_norm_grad_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp]),
+    "wsc_pool_tf_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_maxpool_grad_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "wsc_net_cls_tape_plan": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i),
+                                   ctypes.POINTER(ctypes.c_longlong)]),
+    "wsc_net_forward_cls_train": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, ctypes.c_longlong, _vp]),
+    "wsc_cls_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
+    "wsc_cls_grad_destroy": (None, [_vp]),
+    "wsc_cls_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
+    "wsc_net_backward_cls": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong]),
     "wsc_net_edge_tape_plan": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_forward_edge_tape": (_i, [_vp, _vp, _vp, _i, _i, _vp, ctypes.c_longlong, _vp, _vp]),
     "wsc_irn_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
@@ -754,6 +765,20 @@ class Net:
                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _ptr(tape_dev), int(tape_elems),
                                                       _ptr(fc8_dev), _ptr(prob_dev)))
 
+    def cls_tape_plan(self, B, H, W):
+        """wsc_net_cls_tape_plan: ([{'name', 'Ho', 'Wo', 'C', 'offset'}], tape_elems) -- what the backward pass of an
+        ARCH_VGG16_CAM / ARCH_M7_CAM net needs of a training forward pass of a B x H x W input: "input", per conv "<key>" (post-ReLU),
+        on BatchNorm nets "<key>.bn" and "<key>.stats" ([1][1][1][2 C] {mean, rstd} pairs), "pool:<i>"."""
+        return _tape_plan(self.ctx._lib.wsc_net_cls_tape_plan, self.ctx.h, self.h, int(B), int(H), int(W))
+
+    def forward_cls_train(self, x_dev, B, H, W, tape_dev, tape_elems, feat_dev, keep=0.99, unbiased=True, run_dev=None, ctx=None):
+        """wsc_net_forward_cls_train: x_dev [B][3][H][W] -> the tape and feat_dev [B][h][w][F]; BatchNorm on the batch statistics;
+        run_dev (optional): every BatchNorm layer's [2][C] running mean / variance in stack order, updated in place with `keep`
+        the weight of the OLD value (Keras' momentum)."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_forward_cls_train(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(keep), int(bool(unbiased)),
+                                                      _ptr(run_dev), _ptr(tape_dev), int(tape_elems), _ptr(feat_dev)))
+
     def trace_plan(self, N, H, W, ctx=None):
         """wsc_net_trace_plan: one dict per op of the stack for an N x H x W input (+ the CAM head), the fields of wsc_trace_op
         (`in` under its own name, the label as str).  Follows the options of `ctx` (the fused stem)."""
@@ -905,6 +930,55 @@ class IrnGrad(_Grad):
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_irn_load_params(run.h, (net or self.net).h, self.h, _ptr(param_dev),
                                                     self._elems(elems)))
+
+
+class ClsGrad(_Grad):
+    """wsc_cls_grad: what the backward pass of one ARCH_VGG16_CAM / ARCH_M7_CAM net keeps (the data-gradient kernels, the
+    workspace).  state_dict: the one the net was created from.  The net must outlive it.
+    layout: [{'name', 'shape', 'offset', 'size', 'conv'}] one per parameter in net.common.plain_module_order, `shape` torch's
+    ((Cout, Cin, 3, 3) or (C,)); a conv weight lies as [3][3][Cin][Cout] at its offset."""
+    KIND = "cls"
+
+    @staticmethod
+    def _shape_layout(ent):
+        layout = []
+        for e in ent:
+            conv = e.kh == 3
+            layout.append({"name": e.name.decode(), "conv": conv, "shape": (e.Cout, e.Cin, 3, 3) if conv else (e.Cout,),
+                           "offset": e.w_off if conv else e.b_off, "size": 9 * e.Cin * e.Cout if conv else e.Cout})
+        return layout
+
+    def backward(self, B, H, W, tape_dev, tape_elems, dfeat_dev, grad_dev, grad_elems=None, ctx=None):
+        """wsc_net_backward_cls on the net's own context (the workspace belongs to its stream; `ctx`: another one is an error):
+        dfeat_dev float32 [B][h][w][F] -> every element of grad_dev (self.grad_elems floats in self.layout)."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_backward_cls(run.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfeat_dev),
+                                                 _ptr(grad_dev), self._elems(grad_elems)))
+
+
+def batch_norm_train_nhwc(ctx, a_dev, M, C, gamma_dev, beta_dev, eps, keep, unbiased, run_dev, stats_dev, y_dev):
+    """wsc_batch_norm_train_nhwc: a_dev [M][C] -> stats_dev [C][2] {mean, rstd}, y_dev [M][C]; run_dev None or [2][C], updated in
+    place with `keep` the weight of the old value; gamma_dev / beta_dev on the device."""
+    check(ctx._lib.wsc_batch_norm_train_nhwc(ctx.h, _ptr(a_dev), int(M), int(C), _ptr(gamma_dev), _ptr(beta_dev), float(eps), float(keep),
+                                             int(bool(unbiased)), _ptr(run_dev), _ptr(stats_dev), _ptr(y_dev)))
+
+
+def batch_norm_grad_nhwc(ctx, a_dev, stats_dev, gamma_dev, dy_dev, M, C, da_dev, dgamma_dev, dbeta_dev):
+    """wsc_batch_norm_grad_nhwc: da_dev [M][C], dgamma_dev [C], dbeta_dev [C] from the input, the taped statistics and dy_dev."""
+    check(ctx._lib.wsc_batch_norm_grad_nhwc(ctx.h, _ptr(a_dev), _ptr(stats_dev), _ptr(gamma_dev), _ptr(dy_dev), int(M), int(C), _ptr(da_dev),
+                                            _ptr(dgamma_dev), _ptr(dbeta_dev)))
+
+
+def pool_tf_grad_nhwc(ctx, x_dev, dy_dev, N, H, W, C, k, stride, same, dx_dev):
+    """wsc_pool_tf_grad_nhwc: the gradient of pool_tf_nhwc with respect to its input."""
+    check(ctx._lib.wsc_pool_tf_grad_nhwc(ctx.h, _ptr(x_dev), _ptr(dy_dev), int(N), int(H), int(W), int(C), int(k), int(stride), int(bool(same)),
+                                         _ptr(dx_dev)))
+
+
+def maxpool_grad_nhwc(ctx, x_dev, dy_dev, N, H, W, C, k, stride, pad, dx_dev):
+    """wsc_maxpool_grad_nhwc: the gradient of maxpool_nhwc (torch's MaxPool2d(k, stride, pad)) with respect to its input."""
+    check(ctx._lib.wsc_maxpool_grad_nhwc(ctx.h, _ptr(x_dev), _ptr(dy_dev), int(N), int(H), int(W), int(C), int(k), int(stride), int(pad),
+                                         _ptr(dx_dev)))
 
 
 def channel_mean_nchw(ctx, x_dev, N, C, H, W, out_dev, sub=None):

@@ -9,9 +9,16 @@
                      <sess_id>.mat -- the file net.common.load_pretrained and keras_store.load_model read --, metrics on the split
                      `eval_on` names
 
-Not here: the backward pass through the plain stacks, BatchNorm in training mode, the Nesterov SGD /
-cyclic-LR step and the data generators (the reference's data_loader.py / model_loader.py are missing).  Keras evaluates the loss in
-float32, and what it does with the LIST class_weight of demo.py:80-82,107 is not reproduced: ClsLoss takes per-sample weights."""
+    ClsTape          what a training forward pass of a plain stack keeps for its backward pass (one float32 device buffer, its plan)
+    ClsGrads         the gradient of every conv / BatchNorm parameter of the stack on the device: a flat buffer, its layout,
+                     name -> DeviceMaps views, to_state_dict() in torch's shapes
+    grad_step        one call from a batch to every gradient of a step: net.forward_train_dev (conv -> ReLU -> BatchNorm on the batch
+                     statistics, wsc_net_forward_cls_train), the loss head, net.backward_dev (wsc_net_backward_cls)
+
+Not here: the Nesterov SGD / cyclic-LR step with the repack of the updated weights, the `D` dropout entries of
+VGG16's layer5 (the identity here) and the data generators (the reference's data_loader.py / model_loader.py are missing).  Keras
+evaluates the loss in float32, and what it does with the LIST class_weight of demo.py:80-82,107 is not reproduced: ClsLoss takes
+per-sample weights."""
 import collections
 import os
 
@@ -19,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from .misc.imutils import default_context
-from .secdsrg import DeviceMaps, device_operand
+from .secdsrg import DeviceMaps, Freed, device_operand
 
 K_EPSILON = 1e-7  # K.epsilon()
 POOLS = {"mean": _lib.CLS_POOL_MEAN, "max": _lib.CLS_POOL_MAX}
@@ -94,6 +101,111 @@ class ClsLoss:
 
     def grad_step(self, feat, w, bias, targets, sample_weight=None):
         return self._run(feat, w, bias, targets, sample_weight, True)
+
+
+class ClsTape(Freed):
+    """The tape of CAM.forward_train_dev(x, keep=True): `maps` one float32 DeviceMaps of `elems` floats, `entries` the plan of
+    Net.cls_tape_plan for a (B, 3, H, W) input.  entry(name) downloads one tensor ([B][Ho][Wo][C]; a ".stats" entry (C, 2));
+    free() / a context manager releases the buffer."""
+
+    def __init__(self, maps, entries, B, H, W):
+        self.maps, self.entries, self.B, self.H, self.W = maps, entries, int(B), int(H), int(W)
+        self.elems = maps.shape[0]
+
+    def entry(self, name):
+        e = next(e for e in self.entries if e["name"] == name)
+        shape = (e["C"] // 2, 2) if name.endswith(".stats") else (self.B, e["Ho"], e["Wo"], e["C"])
+        return self.maps.ctx.to_host(self.maps.buf, shape, np.float32, offset_bytes=4 * e["offset"])
+
+
+class _GradView(DeviceMaps):
+    """A parameter's range of a ClsGrads buffer as a DeviceMaps: it owns nothing (free() is a no-op) and dies with the buffer."""
+
+    def __init__(self, parent, offset, shape):
+        self.ctx, self.shape, self.dtype = parent.ctx, tuple(shape), np.dtype(np.float32)
+        self.sizes = self.offsets = None
+        self._parent, self._at = parent, 4 * int(offset)
+
+    @property
+    def buf(self):
+        return self._parent.buf
+
+    @property
+    def ptr(self):
+        return None if self._parent.ptr is None else self._parent.ptr + self._at
+
+    def to_host(self):
+        if self._parent.buf is None:
+            raise ValueError("ClsGrads: freed")
+        return self.ctx.to_host(self._parent.buf, self.shape, self.dtype, offset_bytes=self._at)
+
+    def free(self):
+        pass
+
+
+class ClsGrads(Freed):
+    """The gradient of every conv / BatchNorm parameter of a plain stack, on the device: `maps` one float32 DeviceMaps and `layout`,
+    _lib.ClsGrad.layout ([{'name', 'shape', 'offset', 'size', 'conv'}] in net.common.plain_module_order; a conv weight lies as
+    [3][3][Cin][Cout] at its offset).  grads[name] is a DeviceMaps view of that parameter's floats (a conv weight (3, 3, Cin, Cout),
+    a vector (C,)), ptr(name) its device address; to_state_dict() downloads everything once -> {name: ndarray} in torch's shapes.
+    The classifier's Linear is not here: its gradient is HeadGrads.w / .bias.  free() / a context manager releases the buffer."""
+
+    def __init__(self, maps, layout):
+        self.maps = maps
+        self.layout = layout
+
+    def _entry(self, name):
+        for e in self.layout:
+            if e["name"] == name:
+                return e
+        raise KeyError("ClsGrads: no parameter %r" % (name,))
+
+    def keys(self):
+        return [e["name"] for e in self.layout]
+
+    def ptr(self, name):
+        return self.maps.ptr + 4 * self._entry(name)["offset"]
+
+    def __getitem__(self, name):
+        e = self._entry(name)
+        cout, cin = (e["shape"] + (0,))[:2]
+        return _GradView(self.maps, e["offset"], (3, 3, cin, cout) if e["conv"] else e["shape"])
+
+    def to_state_dict(self):
+        flat = self.maps.to_host()
+        out = {}
+        for e in self.layout:
+            v = flat[e["offset"]:e["offset"] + e["size"]]
+            if e["conv"]:
+                cout, cin = e["shape"][:2]
+                v = v.reshape(3, 3, cin, cout).transpose(3, 2, 0, 1)
+            out[e["name"]] = np.ascontiguousarray(v)
+        return out
+
+
+def grad_step(net, loss, x, targets, sample_weight=None):
+    """One training step of 01_train up to the gradient of every parameter.
+      net      a net.vgg16_cam.CAM / net.m7_cam.CAM with its state dict loaded; loss: a ClsLoss on the net's context whose pool is
+               the net's head ("mean" VGG16, "max" M7)
+      x        (B, 3, H, W) float32, a host array or a DeviceMaps of that context; targets (B, C) 0/1; sample_weight host (B,) or None
+    -> (the metrics dict of ClsLoss, HeadGrads(feat, w, bias), ClsGrads): forward_train_dev on the batch statistics (the net's
+    running statistics are updated with Keras' momentum 0.99), the loss head on the classifier's Linear of the state dict, and
+    backward_dev.  The caller frees the two gradient objects.  The call downloads the six loss values and nothing else."""
+    if net.ctx is not loss.ctx:
+        raise ValueError("grad_step: the network lives on another context than the loss")
+    w, bias = net.classifier_params(loss.C)
+    feat, tape = net.forward_train_dev(x, keep=True)
+    head = None
+    try:
+        metrics, head = loss.grad_step(feat, w, bias, targets, sample_weight)
+        return metrics, head, net.backward_dev(tape, head.feat)
+    except Exception:
+        for m in head or ():
+            m.free()
+        raise
+    finally:
+        feat.free()
+        tape.free()
 
 
 def threshold_ratios(counts, n_samples):

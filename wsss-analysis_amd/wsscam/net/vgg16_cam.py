@@ -60,6 +60,137 @@ class CAM(DeviceCAMBase):
             self.thresholds = np.asarray(self._sd.pop("thresholds"), dtype=np.float32)
         return self
 
+    # ---- 01_train: the stack in training mode (wsc_net_forward_cls_train / wsc_net_backward_cls) --------------------------------
+    def _release_net(self):
+        grad = self.__dict__.pop("_cls_grad", None)
+        if grad is not None:
+            grad.close()
+        run = self.__dict__.pop("_bn_running", None)
+        if run is not None:
+            run.free()
+        super()._release_net()
+
+    def bn_keys(self):
+        """The state-dict prefixes of the stack's BatchNorm layers in stack order ([] for a net without)."""
+        from .common import plain_module_order
+
+        return [key for kind, key in plain_module_order(self.root, True) if kind == "bn" and key + ".running_mean" in self._sd]
+
+    def bn_running_dev(self):
+        """The running statistics forward_train_dev updates: one float32 DeviceMaps, per BatchNorm layer in stack order its
+        running mean then its running variance; created from the state dict on first use, released with the net.  None for a net
+        without BatchNorm."""
+        from ..secdsrg import DeviceMaps
+
+        self._ensure_net()
+        if getattr(self, "_bn_running", None) is None:
+            keys = self.bn_keys()
+            if not keys:
+                return None
+            flat = np.concatenate([self._sd[k + "." + n].reshape(-1) for k in keys for n in ("running_mean", "running_var")])
+            self._bn_running = DeviceMaps.from_host(self._ctx, flat, dtype=np.float32)
+        return self._bn_running
+
+    def bn_running(self):
+        """{'<bn>.running_mean' / '<bn>.running_var': array}: the running statistics as forward_train_dev left them"""
+        run, out, at = self.bn_running_dev(), {}, 0
+        flat = run.to_host() if run is not None else None
+        for k in self.bn_keys():
+            for n in ("running_mean", "running_var"):
+                c = self._sd[k + "." + n].size
+                out[k + "." + n] = flat[at:at + c].copy()
+                at += c
+        return out
+
+    def classifier_params(self, num_classes=None):
+        """(weight (C, F), bias (C,) or None) of the classifier's Linear, the rows the device net uses"""
+        C = self.num_classes if num_classes is None else int(num_classes)
+        bias = self._sd.get(self.root + ".classifier.0.bias")
+        return self._sd[self.root + ".classifier.0.weight"][:C], None if bias is None else bias[:C]
+
+    def cls_grad(self):
+        """The _lib.ClsGrad of the model's net (created on first use, released with the net)."""
+        net = self._ensure_net()
+        if getattr(self, "_cls_grad", None) is None:
+            self._cls_grad = _lib.ClsGrad(net, self._extra_tensors(self._sd))
+        return self._cls_grad
+
+    def forward_train_dev(self, x, keep=True, bn_keep=0.99):
+        """The stack in training mode (make_layers' conv -> ReLU -> BatchNorm on the BATCH statistics; the `D` entries of layer5
+        are the identity): x float32 (B, 3, H, W), a host array / tensor or a secdsrg.DeviceMaps of the model's context (read in
+        place) -> (feat DeviceMaps (B, h, w, F), the map ClsLoss reads, tape): the cls_train.ClsTape backward_dev needs; the caller
+        frees both.  keep=False: feat alone.
+        bn_keep: the weight of the OLD running value in the update of the running statistics (bn_running_dev), Keras' `momentum`:
+        BatchNormalization(momentum=0.99) is 0.99.  torch's nn.BatchNorm2d(momentum=m) weighs the NEW value with m, so the torch
+        port's BatchNorm2d(v, eps=0.001, momentum=0.99) is bn_keep = 0.01.  The batch variance enters unbiased (M / (M - 1)), as
+        in torch and TensorFlow's fused batch norm; Keras 2.2's own factor is unpinned.  None: the running statistics stay."""
+        from ..cls_train import ClsTape
+        from ..secdsrg import DeviceMaps
+
+        net = self._ensure_net()
+        ctx = self._ctx
+        mine = None
+        if isinstance(x, DeviceMaps):
+            if x.dtype != np.float32 or x.ctx is not ctx:
+                raise ValueError("forward_train_dev: x is %s on %s, not float32 on the model's context" %
+                                 (x.dtype, "another context" if x.ctx is not ctx else "this context"))
+            xd = x
+        else:
+            xn = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+            xd = mine = DeviceMaps.from_host(ctx, xn, dtype=np.float32)
+        feat = tape = None
+        try:
+            if len(xd.shape) != 4 or xd.shape[1] != 3 or 0 in xd.shape:
+                raise ValueError("forward_train_dev: x has shape %r, expected (B, 3, H, W)" % (xd.shape,))
+            if bn_keep is not None and not 0.0 <= float(bn_keep) <= 1.0:
+                raise ValueError("forward_train_dev: bn_keep = %r (the weight of the old running value, 0 .. 1)" % (bn_keep,))
+            B, H, W = xd.shape[0], xd.shape[2], xd.shape[3]
+            h, w = net.cam_size_hw(H, W)
+            run = None if bn_keep is None else self.bn_running_dev()
+            entries, elems = net.cls_tape_plan(B, H, W)
+            feat = DeviceMaps(ctx, (B, h, w, net.feat_channels()), np.float32)
+            tape = ClsTape(DeviceMaps(ctx, (elems,), np.float32), entries, B, H, W)
+            net.forward_cls_train(xd.ptr, B, H, W, tape.maps.ptr, elems, feat.ptr, keep=0.0 if bn_keep is None else bn_keep,
+                                  run_dev=None if run is None else run.ptr)
+            if keep:
+                return feat, tape
+            tape.free()
+            return feat
+        except Exception:
+            for m in (feat, tape):
+                if m is not None:
+                    m.free()
+            raise
+        finally:
+            if mine is not None:
+                mine.free()
+
+    def backward_dev(self, tape, dfeat):
+        """The backward pass of the stack (wsc_net_backward_cls): the tape of forward_train_dev and d loss / d feat (B, h, w, F) or
+        (B, h w, F) float32, a DeviceMaps of the model's context (HeadGrads.feat of ClsLoss.grad_step), read in place ->
+        cls_train.ClsGrads (the caller frees it).  The chain rule evaluated at the tape, in exact fp32 whatever the net's precision."""
+        from ..cls_train import ClsGrads, ClsTape
+        from ..secdsrg import DeviceMaps
+
+        net = self._ensure_net()
+        ctx = self._ctx
+        if not isinstance(tape, ClsTape) or tape.maps.ptr is None or tape.maps.ctx is not ctx:
+            raise ValueError("backward_dev: tape is no live ClsTape of the model's context")
+        if not isinstance(dfeat, DeviceMaps) or dfeat.dtype != np.float32 or dfeat.ctx is not ctx or dfeat.ptr is None:
+            raise ValueError("backward_dev: dfeat is no live float32 DeviceMaps of the model's context")
+        h, w = net.cam_size_hw(tape.H, tape.W)
+        F = net.feat_channels()
+        if tuple(dfeat.shape) not in ((tape.B, h, w, F), (tape.B, h * w, F)):
+            raise ValueError("backward_dev: dfeat has shape %r, expected %r" % (tuple(dfeat.shape), (tape.B, h, w, F)))
+        grad = self.cls_grad()
+        out = DeviceMaps(ctx, (grad.grad_elems,), np.float32)
+        try:
+            grad.backward(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, dfeat.ptr, out.ptr)
+        except Exception:
+            out.free()
+            raise
+        return ClsGrads(out, grad.layout)
+
     def predict_labels(self, score):
         """vgg16_cam.py:37-45: score >= thresholds; if nothing passes on non-ADP data force argmax."""
         y = score >= self.thresholds[:len(score)]
