@@ -871,8 +871,8 @@ int wsc_irn_aff_loss(wsc_ctx *ctx, const float *edge_dev, const float *dp_dev, c
 /* ---- 01_train: the loss head of the classifier with the gradient through the head, and the score side of predict() -----------
  * wsc_cls_loss is model.compile(loss='binary_crossentropy', metrics=['binary_accuracy', f1]) (01_train/demo.py:60-61,
  * utilities.py:69-97) on the head global pool -> Dense -> sigmoid, with the gradient of the loss through that head.  The backward
- * pass through the plain stacks and BatchNorm in training mode follow below (wsc_net_backward_cls); the Nesterov SGD / cyclic-LR
- * step and the generators are not here.
+ * pass through the plain stacks and BatchNorm in training mode follow below (wsc_net_backward_cls), then the Nesterov SGD step
+ * with the repack of the updated weights (wsc_cls_sgd_step, wsc_net_cls_load_params); the generators are not here.
  *   feat_dev      float32 [B][n][F]  the NHWC map the head reduces, as wsc_net_forward_features writes it; n = h w
  *   pool          WSC_CLS_POOL_MEAN: the mean over the n positions (VGG16);  WSC_CLS_POOL_MAX: their maximum (M7) -- the two
  *                 cases of wsc_gap_linear_sigmoid
@@ -958,8 +958,8 @@ int wsc_cls_scores_append(wsc_ctx *ctx, const float *src_dev, long long elems, f
 /* ---- 01_train: training-mode forward and backward pass of the plain stacks (WSC_ARCH_VGG16_CAM / WSC_ARCH_M7_CAM) ---------------
  * The graph is common_cnn.make_layers' (03b_irn/net/common_cnn.py:128-141): conv(bias) -> ReLU -> BatchNorm(eps = 1e-3) per entry,
  * the max pools between (MaxPool2d(2, 2), or the rows of `pool_spec`).  The `D` dropout entries of VGG16's layer5 are the IDENTITY
- * here (drop_prob = 0); the Nesterov SGD / cyclic-LR step, the repack of updated weights, the data generators and Keras' list
- * class_weight are not here.  wsc_cls_loss hands out d loss / d feat on the last feature map (and the gradient of the classifier's
+ * here (drop_prob = 0); the data generators, Keras' list class_weight and the writing of .h5 files are not here (the Nesterov SGD
+ * step and the repack of updated weights follow this section).  wsc_cls_loss hands out d loss / d feat on the last feature map (and the gradient of the classifier's
  * Linear); wsc_net_backward_cls carries it to every conv and BatchNorm parameter in exact fp32 whatever the forward precision.  The
  * definition is the chain rule EVALUATED AT THE TAPE, as for the other two nets: a ReLU passes dy where its kept output is > 0, a
  * max pool sends a window's dy to the window's first maximum in row-major window order (recomputed from its kept input; padding is
@@ -1031,6 +1031,61 @@ void wsc_cls_grad_destroy(wsc_cls_grad *g);
 int wsc_cls_grad_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out);
 int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
                          const float *dfeat_dev, float *grad_dev, long long grad_elems);
+
+/* ---- 01_train: the update half of a step -- Keras' SGD with Nesterov momentum and the repack of the updated parameters ----------
+ * wsc_cls_param_layout: the TRAINING layout of a wsc_cls_grad.  Every entry of wsc_cls_grad_layout, unchanged and at the same
+ *   offsets (wsc_cls_grad_layout and its grad_elems do not change); then `<root>.classifier.0.weight` (kh = kw = 1, Cin = F,
+ *   Cout = C, w_off = grad_elems): the C rows of the Linear the net uses, lying as torch's [C][F] -- THE ONE MATRIX OF THE LAYOUT
+ *   THAT IS NOT IN [Cin][Cout] ORDER, because that is how wsc_cls_loss reads w_dev and writes grad_w_dev; then
+ *   `<root>.classifier.0.bias` (a vector entry, b_off = grad_elems + C F) if the net has one.  No gaps; *param_elems_out =
+ *   grad_elems + C F [+ C].  max_entries = 0 for the count.
+ *   Parameters, gradient and momentum are each ONE fp32 device buffer of param_elems floats in this layout, element for element.
+ *   wsc_net_backward_cls writes the first grad_elems floats of such a gradient buffer, wsc_cls_loss writes grad_w_dev /
+ *   grad_bias_dev straight into its tail, and reads w_dev / bias_dev from the tail of the parameter buffer.  ALIGNMENT: grad_elems
+ *   is a multiple of 64 (every conv has Cout % 64 == 0, the first one 27 x 64 weights) and F a multiple of 4, so in a 16-byte
+ *   aligned buffer the front (wsc_net_backward_cls: grad_dev 16-byte aligned) and the classifier weight (wsc_cls_loss: w_dev and
+ *   grad_w_dev 16-byte aligned) are on the 16-byte grid for every C -- C = 20 and C = 5 alike (5 x 1024 and 5 x 256 are multiples
+ *   of 4); the bias behind it is 16-byte aligned too, and needs only its 4 bytes (bias_dev / grad_bias_dev have no alignment rule).
+ *
+ * wsc_cls_sgd_step: Keras 2.2's optimizers.SGD(lr, momentum, decay=0.0, nesterov).get_updates (01_train/demo.py:60: momentum 0.9,
+ *   nesterov=True), per element
+ *     v = momentum m - lr g;   m = v
+ *     p = (p + momentum v) - lr g          (nesterov = 1)
+ *     p = p + v                            (nesterov = 0)
+ *   every product, sum and difference one fp32 rounding in exactly this association (no fused multiply-add), lr g formed ONCE and
+ *   used in both places; one rate for every parameter, no weight decay; a momentum buffer of +0.0 gives the first step.  The
+ *   schedule (cls_train.step_lr / cyclic_lr) is the caller's.  One launch on 16-byte vectors; buffers off the 16-byte grid take the
+ *   scalar form of the same kernel, the same roundings.  grad_dev is only read.  A NaN gradient makes p and m NaN at that element
+ *   and nowhere else.  Asynchronous on the ctx stream.  WSC_ERR_INVALID before any launch: ctx is not the context of `g`, elems is
+ *   not param_elems, a null pointer, lr negative or not finite, momentum outside [0, 1), nesterov other than 0 / 1.
+ *
+ * wsc_net_cls_load_params: the counterpart of wsc_net_seg_load_params / wsc_net_irn_load_params.  Rewrites, in place and without a
+ *   host copy, everything derived from the parameters, from the floats of param_dev (the training layout):
+ *   (a) of every conv of the stack the packed rows in the kernel's K order for the net's precision with s1 and the bias (IEEE-half
+ *       modes: the per-output-channel power-of-two scale from the channel's largest |w|; split modes: both parts; fp32 in
+ *       WSC_PREC_F32), the first layer's small form included;
+ *   (b) the device gamma / beta of every BatchNorm (what wsc_net_forward_cls_train and wsc_net_backward_cls read);
+ *   (c) on a BatchNorm net each conv's inference epilogue s2 / b2 from gamma, beta, the layer's eps and run_dev, the running
+ *       statistics in the layout wsc_net_forward_cls_train updates ([2][C_l] per layer in stack order): sc = gamma / sqrt(var + eps),
+ *       b = beta - mean sc in double -- wsc_net_create's fold, operation for operation, with the correctly rounded double division
+ *       and square root -- each rounded to float once.  run_dev = NULL leaves s2 / b2 as they are; a net without BatchNorm ignores
+ *       run_dev;
+ *   (d) the classifier's fp32 weight and bias, and on a VGG16 net the CAM head's packed rows (the Linear as a 1 x 1 conv; the
+ *       [C][F] matrix is transposed into a buffer of the wsc_cls_grad first).  An M7 net's head is its `gradcam_weights` tensor,
+ *       which is no parameter of this layout: it stays as it is;
+ *   (e) in the wsc_cls_grad the rotated fp32 data-gradient kernels.
+ *   Afterwards the device bytes of both objects are what wsc_net_create / wsc_cls_grad_create make of the same floats and running
+ *   statistics (M7: and the same `gradcam_weights`).  A parameter, scale or shift that is not finite raises the range flag.
+ *   The call WRITES the net, with the ordering caveat of wsc_net_seg_load_params: the net must not be in use on another stream
+ *   during it, and work of other streams that reads the net must be ordered behind it by the caller (wsc_ctx_wait).  A handful of launches whatever the depth: the job
+ *   tables are built by the first call.  WSC_ERR_INVALID before any launch: a net that is no WSC_ARCH_VGG16_CAM /
+ *   WSC_ARCH_M7_CAM net, a `g` of another net, a foreign ctx, a wrong elems, a null param_dev, a VGG16 net built with
+ *   `gradcam_weights` (its head is not the classifier).  Asynchronous on the ctx stream. */
+int wsc_cls_param_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *param_elems_out);
+int wsc_cls_sgd_step(wsc_ctx *ctx, wsc_cls_grad *g, float *param_dev, const float *grad_dev, float *mom_dev, long long elems, float lr,
+                     float momentum, int nesterov);
+int wsc_net_cls_load_params(wsc_ctx *ctx, wsc_net *net, wsc_cls_grad *g, const float *param_dev, long long elems,
+                            const float *run_dev /* or NULL */);
 
 /* ---- backward pass of the IRNet heads: total_loss.backward() of step/train_irn.py:127 ------------------------------------------
  * Net.forward detaches every backbone stage (resnet50_irn.py:111-115) and trainable_parameters() is edge_layers + dp_layers, so

@@ -657,6 +657,25 @@ constexpr int CHANNEL_MEAN_MAX_BLOCKS = 64; // per channel
 constexpr int CHANNEL_MEAN_MAX_C = 1024;
 int channel_mean_launch(wsc_ctx *ctx, const float *x, int N, int C, long long HW, const float *sub_host, double *out);
 
+// ---- cls_sgd.hip: the update half of a 01_train step on the layout of wsc_cls_param_layout, and what the repack of the plain
+// stacks adds to the two files above (the contract: its header) -----------------------------------------------------------------
+// v = momentum m - lr g; m = v; p = (p + momentum v) - lr g (nesterov) / p + v; lr g formed once; every product, sum and difference
+// one fp32 rounding; grad is only read
+int cls_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, float lr, float momentum, int nesterov);
+// One BatchNorm layer's inference epilogue: s2[c] = float(gamma / sqrt(var + eps)), b2[c] = float(beta - mean sc) in double, from
+// gamma / beta at their offsets of the parameter buffer and the layer's [2][C] block of the running statistics
+struct BnFoldJob {
+    long long g_off, be_off, run_off; // floats into the parameter buffer (gamma, beta) / the running statistics (mean; var C floats on)
+    int C, block0;                    // channels; the job's first block in the launch
+    double eps;                       // as fold_bn of net.hip takes it
+    float *s2, *b2;
+};
+constexpr int BN_FOLD_PER_BLOCK = 256;
+// (block0 filled by the caller: jobs in order, ceil(C / BN_FOLD_PER_BLOCK) blocks each)
+int bn_fold_launch(wsc_ctx *ctx, const BnFoldJob *jobs_dev, int n_jobs, int blocks, const float *param, const float *run);
+// dst [F][C] = the transpose of src [C][F]
+int transpose_cf_launch(wsc_ctx *ctx, const float *src, int C, int F, float *dst);
+
 // ---- seg_dropout.hip: the dropout sites behind fc6 / fc7 of the SEC / DSRG training graph (the contract: its header) -----------
 // WSC_ERR_INVALID unless 0 <= drop_prob < 1 (NaN included) and 0 <= step < 2^32; `fn` names the caller in the error text
 int seg_dropout_check(const char *fn, float drop_prob, long long step);

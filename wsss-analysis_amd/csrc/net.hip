@@ -46,6 +46,7 @@ struct PlainBn {
     float *gamma = nullptr, *beta = nullptr; // device, [C]
     int C = 0;
     float eps = 1e-3f;
+    double eps_fold = 1e-3; // the eps fold_bn took for s2 / b2 (the double constant, or the state dict's float): wsc_net_cls_load_params
 };
 
 // one Conv2d(1x1, bias=False) -> GroupNorm -> [Upsample] -> ReLU head of the IRNet branches
@@ -97,6 +98,7 @@ struct wsc_net {
     std::vector<Op> ops;
     int final_buf = 0;
     ConvW head;
+    bool head_is_cls = false; // vgg16 without `gradcam_weights`: the head's rows are the classifier's Linear (wsc_net_cls_load_params)
     float *cls_w = nullptr, *cls_b = nullptr; // classifier branch (vgg16 / m7), fp32 [Ccls][F]
     int Ccls = 0;
     int cls_max = 0; // 1: global max pooling (m7), 0: global average (vgg16)
@@ -494,7 +496,7 @@ int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
                     WSC_TRY(make_conv(net, w, 1, 1, 1, first ? CONV_FORM_SMALL2 : CONV_FORM_GENERIC, one, bb, &s2, &b2, &c));
                     PlainBn pb; // (fold_bn has checked the tensors)
                     pb.name = bn; pb.C = v;
-                    if (has(d, bn + ".eps")) pb.eps = d.at(bn + ".eps").data[0];
+                    if (has(d, bn + ".eps") && d.at(bn + ".eps").data) pb.eps_fold = pb.eps = d.at(bn + ".eps").data[0];
                     WSC_TRY(upload(net, d.at(bn + ".weight").data, v * sizeof(float), (void **)&pb.gamma));
                     WSC_TRY(upload(net, d.at(bn + ".bias").data, v * sizeof(float), (void **)&pb.beta));
                     c.bn = (int)net->bns.size();
@@ -566,7 +568,7 @@ int build_vgg16(wsc_net *net, const Dict &d) {
             for (int c = 0; c < net->C; ++c) wt[(size_t)c * net->F + f] = gw->data[(size_t)f * net->C + c];
         hw.data = wt.data();
         WSC_TRY(gradcam_bias(d, net->C, zero));
-    }
+    } else net->head_is_cls = true;
     WSC_TRY(make_conv(net, &hw, 1, 0, 0, CONV_FORM_GENERIC, one, zero, nullptr, nullptr, &net->head));
     net->Ccls = net->C;
     net->cls_max = 0;
@@ -1765,7 +1767,8 @@ struct GradCore {
         return WSC_OK;
     }
     // the job table of the load-params entry and the scratch of its channel maxima, once per object (the packed buffers never move)
-    int plan_repack(std::vector<RepackJob> &jobs) {
+    // (dst: another plan of the object than `repack`)
+    int plan_repack(std::vector<RepackJob> &jobs, RepackPlan *dst = nullptr) {
         RepackPlan plan;
         void *jd = nullptr, *pm = nullptr;
         WSC_TRY(repack_plan(jobs, net->prec, &plan));
@@ -1773,7 +1776,7 @@ struct GradCore {
         if (plan.pmax_elems > 0) WSC_TRY(own((size_t)plan.pmax_elems * sizeof(float), &pm));
         plan.pmax = (float *)pm;
         plan.jobs_dev = (RepackJob *)jd;
-        repack = plan;
+        *(dst ? dst : &repack) = plan;
         return WSC_OK;
     }
     void release() {
@@ -1784,10 +1787,12 @@ struct GradCore {
 };
 // the arguments every entry that takes a gradient object shares, checked before anything is launched (the workspace and the
 // optimiser's scratch are the object's: one stream uses them, the one release() drains)
-int grad_check(const char *fn, const wsc_ctx *ctx, const GradCore *g, long long elems, bool pointers_ok) {
+// (layout_elems: the size of the layout the entry's buffers are in where that is not the gradient layout -- wsc_cls_param_layout)
+int grad_check(const char *fn, const wsc_ctx *ctx, const GradCore *g, long long elems, bool pointers_ok, long long layout_elems = -1) {
     WSC_CHECK(ctx && g && pointers_ok, WSC_ERR_INVALID, "%s: null argument", fn);
     WSC_CHECK(ctx == g->ctx, WSC_ERR_INVALID, "%s: the context is not the one the %s was created on", fn, g->kind);
-    WSC_CHECK(elems == g->grad_elems, WSC_ERR_INVALID, "%s: buffers of %lld floats, the layout has %lld", fn, elems, g->grad_elems);
+    const long long want = layout_elems >= 0 ? layout_elems : g->grad_elems;
+    WSC_CHECK(elems == want, WSC_ERR_INVALID, "%s: buffers of %lld floats, the layout has %lld", fn, elems, want);
     return WSC_OK;
 }
 // the workspace of GradCore::workspace in 256-byte lines
@@ -2614,6 +2619,16 @@ struct wsc_cls_grad : GradCore {
     std::vector<ClsGradLayer> layers;   // the convs in op order
     std::vector<int> op_layer;          // layer of op i, -1 for a pool
     std::vector<wsc_grad_entry> layout; // one entry per parameter, in plain_module_order
+    // the training layout (wsc_cls_param_layout): the gradient layout, then the classifier's Linear [C][F] and its bias
+    long long param_elems = 0, cls_w_off = 0, cls_b_off = -1;
+    // wsc_net_cls_load_params, built by its first call with the repack jobs: BatchNorm's gamma / beta and the classifier's fp32
+    // copies (a vec-copy table), the inference folds, the CAM head (the transposed Linear in `head_t`, a repack plan of its own)
+    VecCopyJob *vec_jobs = nullptr;
+    int n_vec_jobs = 0, vec_blocks = 0;
+    BnFoldJob *fold_jobs = nullptr;
+    int n_fold_jobs = 0, fold_blocks = 0;
+    float *head_t = nullptr; // [F][C]
+    RepackPlan head_repack;
 };
 
 void wsc_cls_grad_destroy(wsc_cls_grad *g) {
@@ -2689,6 +2704,10 @@ int wsc_cls_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
             }
             g->layers.push_back(L);
         }
+        WSC_CHECK(net->cls_w && net->Ccls > 0 && net->F > 0, WSC_ERR_INVALID, "internal: a plain stack without its classifier");
+        g->cls_w_off = g->grad_elems;
+        g->cls_b_off = net->cls_b ? g->cls_w_off + (long long)net->Ccls * net->F : -1;
+        g->param_elems = g->cls_w_off + (long long)net->Ccls * net->F + (net->cls_b ? net->Ccls : 0);
         return g->ones_zeros(widest);
     };
     const int st = build();
@@ -2768,6 +2787,139 @@ int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, con
         }
         gcur = gout;
         nf ^= 1;
+    }
+    return WSC_OK;
+}
+
+// ---- the update half of a 01_train step (Keras' SGD with Nesterov momentum, 01_train/demo.py:60) and the repack of the updated
+// parameters into the net; kernels: cls_sgd.hip, seg_sgd.hip (the conv rows), irn_sgd.hip (the vectors) ---------------------------
+int wsc_cls_param_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *param_elems_out) {
+    WSC_CHECK(g && n_out && param_elems_out && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
+              "wsc_cls_param_layout: null argument");
+    const wsc_net *net = g->net;
+    const int n_grad = (int)g->layout.size();
+    *n_out = n_grad + (g->cls_b_off >= 0 ? 2 : 1);
+    *param_elems_out = g->param_elems;
+    const std::string root = net->arch == WSC_ARCH_VGG16_CAM ? "vgg16" : "m7";
+    for (int i = 0; i < max_entries && i < *n_out; ++i) {
+        if (i < n_grad) {
+            entries_out[i] = g->layout[i];
+            continue;
+        }
+        wsc_grad_entry e = {};
+        const bool w = i == n_grad;
+        std::strncpy(e.name, (root + (w ? ".classifier.0.weight" : ".classifier.0.bias")).c_str(), sizeof(e.name) - 1);
+        e.kh = e.kw = w ? 1 : 0;
+        e.Cin = w ? net->F : 0; e.Cout = net->Ccls;
+        e.w_off = w ? g->cls_w_off : -1;
+        e.b_off = w ? -1 : g->cls_b_off;
+        entries_out[i] = e;
+    }
+    return WSC_OK;
+}
+
+int wsc_cls_sgd_step(wsc_ctx *ctx, wsc_cls_grad *g, float *param_dev, const float *grad_dev, float *mom_dev, long long elems, float lr,
+                     float momentum, int nesterov) {
+    const char *fn = "wsc_cls_sgd_step";
+    WSC_TRY(grad_check(fn, ctx, g, elems, param_dev && grad_dev && mom_dev, g ? g->param_elems : 0));
+    WSC_CHECK(std::isfinite(lr) && lr >= 0.f, WSC_ERR_INVALID, "%s: lr = %g (finite, >= 0)", fn, (double)lr);
+    WSC_CHECK(momentum >= 0.f && momentum < 1.f, WSC_ERR_INVALID, "%s: momentum = %g (0 <= momentum < 1)", fn, (double)momentum);
+    WSC_CHECK(nesterov == 0 || nesterov == 1, WSC_ERR_INVALID, "%s: nesterov = %d (0 / 1)", fn, nesterov);
+    WSC_CHECK((((uintptr_t)param_dev | (uintptr_t)grad_dev | (uintptr_t)mom_dev) & 3) == 0, WSC_ERR_INVALID, "%s: a buffer is not 4-byte aligned", fn);
+    WSC_HIP(hipSetDevice(ctx->device));
+    return cls_sgd_launch(ctx, param_dev, grad_dev, mom_dev, elems, lr, momentum, nesterov);
+}
+
+int wsc_net_cls_load_params(wsc_ctx *ctx, wsc_net *net, wsc_cls_grad *g, const float *param_dev, long long elems, const float *run_dev) {
+    const char *fn = "wsc_net_cls_load_params";
+    WSC_CHECK(ctx && net && g && param_dev, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_TRY(need_cls(fn, net));
+    WSC_CHECK(g->net == net, WSC_ERR_INVALID, "%s: the wsc_cls_grad was created for another net", fn);
+    WSC_TRY(grad_check(fn, ctx, g, elems, true, g->param_elems));
+    // VGG16's head is the Linear itself unless the net was given a Grad-CAM alpha in its place; M7's head is always its
+    // `gradcam_weights` tensor, which is no parameter of the training layout and stays as it is
+    WSC_CHECK(net->arch != WSC_ARCH_VGG16_CAM || net->head_is_cls, WSC_ERR_INVALID,
+              "%s: the net was built with `gradcam_weights`: its CAM head is not the classifier the parameters hold", fn);
+    WSC_CHECK(((uintptr_t)param_dev & 3) == 0 && ((uintptr_t)run_dev & 3) == 0, WSC_ERR_INVALID, "%s: a buffer is not 4-byte aligned", fn);
+    std::vector<ConvW *> convs;
+    for (const Op &op : net->ops)
+        if (op.type == OP_CONV) convs.push_back(&net->convs[op.conv]);
+    WSC_CHECK(convs.size() == g->layers.size(), WSC_ERR_INVALID, "internal: %d layers of the net, %d of the layout", (int)convs.size(),
+              (int)g->layers.size());
+    for (size_t i = 0; i < convs.size(); ++i) {
+        const ConvW &c = *convs[i];
+        const ClsGradLayer &L = g->layers[i];
+        WSC_CHECK(c.kh == 3 && c.kw == 3 && c.Cout == L.Cout && (c.form == CONV_FORM_GENERIC ? c.Cin == L.Cin : (c.Cin == 4 && L.Cin <= 4)) &&
+                      c.bn == L.bn && (c.bn >= 0) == (c.s2 != nullptr && c.b2 != nullptr),
+                  WSC_ERR_INVALID, "internal: layer %d of the layout is not the net's", (int)i);
+    }
+    WSC_HIP(hipSetDevice(ctx->device));
+    const int C = net->Ccls, F = net->F;
+    if (!g->repack.jobs_dev) { // the job tables: once per wsc_cls_grad (the packed buffers of both objects never move)
+        std::vector<RepackJob> jobs(convs.size());
+        std::vector<VecCopyJob> vecs;
+        std::vector<BnFoldJob> folds;
+        int vec_blocks = 0, fold_blocks = 0;
+        long long run_off = 0;
+        auto vec = [&](long long off, int n, float *dst) {
+            VecCopyJob V;
+            V.off = off; V.n = n; V.block0 = vec_blocks; V.dst = dst;
+            vec_blocks += (n + VEC_COPY_PER_BLOCK - 1) / VEC_COPY_PER_BLOCK;
+            vecs.push_back(V);
+        };
+        for (size_t i = 0; i < convs.size(); ++i) {
+            const ConvW &c = *convs[i];
+            const ClsGradLayer &L = g->layers[i];
+            RepackJob &J = jobs[i];
+            J = RepackJob();
+            J.w_off = L.w_off; J.b_off = L.b_off;
+            J.k = 3; J.Cin = L.Cin; J.Cout = L.Cout;
+            J.small = c.form != CONV_FORM_GENERIC;
+            J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
+            J.w_rot = L.w_rot;
+            if (L.bn < 0) continue;
+            const PlainBn &pb = net->bns[L.bn];
+            vec(L.g_off, L.Cout, pb.gamma);
+            vec(L.be_off, L.Cout, pb.beta);
+            BnFoldJob B;
+            B.g_off = L.g_off; B.be_off = L.be_off; B.run_off = run_off;
+            B.C = L.Cout; B.block0 = fold_blocks; B.eps = pb.eps_fold;
+            B.s2 = c.s2; B.b2 = c.b2;
+            fold_blocks += (L.Cout + BN_FOLD_PER_BLOCK - 1) / BN_FOLD_PER_BLOCK;
+            run_off += 2ll * L.Cout;
+            folds.push_back(B);
+        }
+        vec(g->cls_w_off, C * F, net->cls_w);
+        if (g->cls_b_off >= 0) vec(g->cls_b_off, C, net->cls_b);
+        // (the conv table last: jobs_dev, what marks the tables as built, is set by its plan)
+        WSC_TRY(g->upload(vecs.data(), vecs.size() * sizeof(VecCopyJob), (void **)&g->vec_jobs));
+        g->n_vec_jobs = (int)vecs.size();
+        g->vec_blocks = vec_blocks;
+        if (!folds.empty()) WSC_TRY(g->upload(folds.data(), folds.size() * sizeof(BnFoldJob), (void **)&g->fold_jobs));
+        g->n_fold_jobs = (int)folds.size();
+        g->fold_blocks = fold_blocks;
+        if (net->head_is_cls) { // the head: a 1 x 1 layer [F][C] without a bias, read from the transposed copy
+            const ConvW &h = net->head;
+            WSC_CHECK(h.kh == 1 && h.kw == 1 && h.form == CONV_FORM_GENERIC && h.Cin == F && h.Cout == C && !h.s2, WSC_ERR_INVALID,
+                      "internal: the CAM head is no 1 x 1 layer over the %d feature channels", F);
+            WSC_TRY(g->own((size_t)C * F * sizeof(float), (void **)&g->head_t));
+            std::vector<RepackJob> hj(1);
+            hj[0] = RepackJob();
+            hj[0].w_off = 0; hj[0].b_off = -1;
+            hj[0].k = 1; hj[0].Cin = F; hj[0].Cout = C;
+            hj[0].wp = h.w; hj[0].s1 = h.s1; hj[0].b1 = h.b1;
+            WSC_TRY(g->plan_repack(hj, &g->head_repack));
+        }
+        WSC_TRY(g->plan_repack(jobs));
+    }
+    WSC_TRY(repack_launch(ctx, g->repack, param_dev));
+    WSC_TRY(vec_copy_launch(ctx, g->vec_jobs, g->n_vec_jobs, g->vec_blocks, param_dev));
+    if (run_dev) WSC_TRY(bn_fold_launch(ctx, g->fold_jobs, g->n_fold_jobs, g->fold_blocks, param_dev, run_dev));
+    if (net->head_is_cls) {
+        // (wsc_ctx_scratch_fill: the transposed copy is scratch of this call, kept by the object between calls)
+        if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(g->head_t, ctx->scratch_fill, (size_t)C * F * sizeof(float), ctx->stream));
+        WSC_TRY(transpose_cf_launch(ctx, param_dev + g->cls_w_off, C, F, g->head_t));
+        WSC_TRY(repack_launch(ctx, g->head_repack, g->head_t));
     }
     return WSC_OK;
 }

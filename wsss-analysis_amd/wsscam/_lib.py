@@ -152,6 +152,9 @@ _SIGNATURES = {
     "wsc_cls_grad_destroy": (None, [_vp]),
     "wsc_cls_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_backward_cls": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong]),
+    "wsc_cls_param_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
+    "wsc_cls_sgd_step": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _f, _i]),
+    "wsc_net_cls_load_params": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _vp]),
     "wsc_net_edge_tape_plan": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_forward_edge_tape": (_i, [_vp, _vp, _vp, _i, _i, _vp, ctypes.c_longlong, _vp, _vp]),
     "wsc_irn_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
@@ -954,6 +957,63 @@ class ClsGrad(_Grad):
         run = ctx or self.ctx
         check(self.ctx._lib.wsc_net_backward_cls(run.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfeat_dev),
                                                  _ptr(grad_dev), self._elems(grad_elems)))
+
+    # ---- the update half: the training layout (wsc_cls_param_layout), the Nesterov step, the repack -------------------------------
+    def _param_query(self):
+        if getattr(self, "_param_layout", None) is None:
+            ent, (elems,) = _two_call(self.ctx._lib.wsc_cls_param_layout, (self.h,), GradEntry, 1)
+            layout = self._shape_layout(ent)
+            for d, e in zip(layout, ent):
+                d["linear"] = e.kh == 1
+                if d["linear"]:  # the classifier's Linear: torch's [C][F], the one matrix that is not transposed
+                    d.update(shape=(e.Cout, e.Cin), offset=e.w_off, size=e.Cin * e.Cout)
+            self._param_layout, self._param_elems = layout, elems
+        return self._param_layout, self._param_elems
+
+    @property
+    def param_layout(self):
+        """`layout`, then '<root>.classifier.0.weight' ((C, F), lying as it is: 'linear' True) and, if the net has one,
+        '<root>.classifier.0.bias': the layout of the parameter, gradient and momentum buffers of a training step"""
+        return self._param_query()[0]
+
+    @property
+    def param_elems(self):
+        return self._param_query()[1]
+
+    def flat_params(self, state_dict):
+        """The trainable tensors of a state dict ({name: array in torch's shape}; other keys are ignored) -> one float32 array of
+        param_elems floats in `param_layout` order: conv weights transposed to [3][3][Cin][Cout], the first C rows of the
+        classifier's Linear (and of its bias) as they lie.  The host form of what sgd_step and load_params take."""
+        flat = np.empty((self.param_elems,), np.float32)
+        for e in self.param_layout:
+            if e["name"] not in state_dict:
+                raise ValueError("ClsGrad.flat_params: the state dict has no %r" % e["name"])
+            v = state_dict[e["name"]]
+            v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+            if ".classifier." in e["name"] and v.ndim == len(e["shape"]) and v.shape[0] >= e["shape"][0]:
+                v = v[:e["shape"][0]]  # (a Linear of more rows than the net has classes: the net uses the first C)
+            if tuple(v.shape) != tuple(e["shape"]):
+                raise ValueError("ClsGrad.flat_params: %r is %r, the net has %r" % (e["name"], tuple(v.shape), tuple(e["shape"])))
+            if e["conv"]:
+                v = v.transpose(2, 3, 1, 0)
+            flat[e["offset"]:e["offset"] + e["size"]] = v.reshape(-1)
+        return flat
+
+    def sgd_step(self, param_dev, grad_dev, mom_dev, lr, momentum=0.9, nesterov=True, elems=None, ctx=None):
+        """wsc_cls_sgd_step on three buffers of param_elems floats in `param_layout`: v = momentum m - lr g; m = v;
+        p = (p + momentum v) - lr g (nesterov) or p + v, every product, sum and difference one fp32 rounding."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_cls_sgd_step(run.h, self.h, _ptr(param_dev), _ptr(grad_dev), _ptr(mom_dev),
+                                             int(self.param_elems if elems is None else elems), float(lr), float(momentum),
+                                             int(nesterov)))
+
+    def load_params(self, param_dev, run_dev=None, elems=None, net=None, ctx=None):
+        """wsc_net_cls_load_params: the packed conv rows, BatchNorm's gamma / beta, the inference folds (from run_dev, the running
+        statistics of forward_cls_train; None leaves them), the classifier, VGG16's CAM head and this object's data-gradient
+        kernels rewritten on the device from the flat parameter buffer.  The net must not be in use on another stream."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_cls_load_params(run.h, (net or self.net).h, self.h, _ptr(param_dev),
+                                                    int(self.param_elems if elems is None else elems), _ptr(run_dev)))
 
 
 def batch_norm_train_nhwc(ctx, a_dev, M, C, gamma_dev, beta_dev, eps, keep, unbiased, run_dev, stats_dev, y_dev):

@@ -15,10 +15,15 @@
     grad_step        one call from a batch to every gradient of a step: net.forward_train_dev (conv -> ReLU -> BatchNorm on the batch
                      statistics, wsc_net_forward_cls_train), the loss head, net.backward_dev (wsc_net_backward_cls)
 
-Not here: the Nesterov SGD / cyclic-LR step with the repack of the updated weights, the `D` dropout entries of
-VGG16's layer5 (the identity here) and the data generators (the reference's data_loader.py / model_loader.py are missing).  Keras
-evaluates the loss in float32, and what it does with the LIST class_weight of demo.py:80-82,107 is not reproduced: ClsLoss takes
-per-sample weights."""
+    ClsTrainer       one training step after another on the device: grad_step's three passes into one resident gradient buffer, Keras'
+                     SGD with Nesterov momentum (wsc_cls_sgd_step, demo.py:60) and the repack of the updated parameters into the
+                     net (wsc_net_cls_load_params); save / load with the momentum, bit-exact resume
+    step_lr          the schedule of demo.py:112-113;  cyclic_lr / cyclic_session_rates: the triangular policy of demo.py:95-110
+    fit              an iterable of batches through a trainer -> the per-epoch means fit_generator(verbose=2) prints
+
+Not here: the `D` dropout entries of VGG16's layer5 (the identity here), the data generators (the reference's
+data_loader.py / model_loader.py are missing) and the writing of .h5 files.  Keras evaluates the loss in float32, and what it does
+with the LIST class_weight of demo.py:80-82,107 is not reproduced: ClsLoss takes per-sample weights."""
 import collections
 import os
 
@@ -69,7 +74,7 @@ class ClsLoss:
     def _maps(self, name, a, shape, held):
         return device_operand(self, self.ctx, name, a, np.float32, shape, held)
 
-    def _run(self, feat, w, bias, targets, sample_weight, want_grad):
+    def _run(self, feat, w, bias, targets, sample_weight, want_grad, out=None):
         ctx, held, grads = self.ctx, [], None
         try:
             f = self._maps("feat", feat, None, held)
@@ -82,14 +87,21 @@ class ClsLoss:
             t = self._maps("targets", targets, (B, self.C), held)
             loss_dev = DeviceMaps(ctx, (len(_lib.CLS_LOSS_SLOTS),), np.float64)
             held.append(loss_dev)
-            if want_grad:
+            if want_grad and out is None:
                 grads = HeadGrads(DeviceMaps(ctx, f.shape), DeviceMaps(ctx, (self.C, F)), DeviceMaps(ctx, (self.C,)))
+            elif want_grad:  # the caller's own buffers for w and bias (a trainer: the tail of its gradient buffer)
+                gw, gb = out
+                for name, g, shape in (("out[0]", gw, (self.C, F)), ("out[1]", gb, (self.C,))):
+                    if not (g is None and name == "out[1]") and (not isinstance(g, DeviceMaps) or g.dtype != np.float32 or g.ctx is not ctx
+                                                                  or g.ptr is None or tuple(g.shape) != shape):
+                        raise ValueError("ClsLoss: %s is no live float32 DeviceMaps %r of this context" % (name, shape))
+                grads = HeadGrads(DeviceMaps(ctx, f.shape), gw, gb)
             _lib.cls_loss(ctx, f.ptr, B, n, F, self.pool, wd.ptr, None if bd is None else bd.ptr, self.C, t.ptr, sample_weight,
                           loss_dev.ptr, grad_feat_dev=grads.feat.ptr if grads else None, grad_w_dev=grads.w.ptr if grads else None,
-                          grad_bias_dev=grads.bias.ptr if grads else None)
+                          grad_bias_dev=grads.bias.ptr if grads and grads.bias is not None else None)
             return keras_metrics(loss_dev.to_host(), B * self.C), grads
         except Exception:
-            for d in grads or ():
+            for d in (grads or ())[:3 if out is None else 1]:  # (`out` stays the caller's)
                 d.free()
             raise
         finally:
@@ -99,8 +111,10 @@ class ClsLoss:
     def loss_step(self, feat, w, bias, targets, sample_weight=None):
         return self._run(feat, w, bias, targets, sample_weight, False)[0]
 
-    def grad_step(self, feat, w, bias, targets, sample_weight=None):
-        return self._run(feat, w, bias, targets, sample_weight, True)
+    def grad_step(self, feat, w, bias, targets, sample_weight=None, out=None):
+        """out: None, or (w, bias) -- float32 DeviceMaps (C, F) and (C,) (bias: or None, its gradient is then not formed) that
+        receive the Linear's gradient in place of two new buffers; they stay the caller's, HeadGrads.feat is new as ever"""
+        return self._run(feat, w, bias, targets, sample_weight, True, out)
 
 
 class ClsTape(Freed):
@@ -370,3 +384,225 @@ def predict(score_batches_val, score_batches_test, model_dir, sess_id, eval_on, 
     finally:
         for ev in evs.values():
             ev.close()
+
+
+# ---- the training loop: demo.py:60 (the optimiser), :95-113 (the schedules), fit_generator ------------------------------------------
+def step_lr(epoch, latest_epoch=0, base_lr=1e-3, droprate=0.5, dropstep=20):
+    """lr_scheduler of demo.py:112-113, the schedule of every call in demo.py's __main__: base_lr * droprate ** ((epoch +
+    latest_epoch) // dropstep) in Python floats, rounded to the float32 Keras stores in the optimiser's `lr` variable."""
+    return np.float32(base_lr * (droprate ** ((int(epoch) + int(latest_epoch)) // int(dropstep))))
+
+
+def cyclic_lr(iteration, base_lr, max_lr, step_size):
+    """The triangular policy of the usual clr_callback.CyclicLR (demo.py:95-110 builds it with step_size = lr_dropstep / clr_spc *
+    n // batch_size): cycle = floor(1 + it / (2 step)), x = |it / step - 2 cycle + 1|, lr = base + (max - base) max(0, 1 - x), in
+    float64, rounded to float32.  Batch k (counted from 0) trains at the rate of iteration k: base_lr at 0 and 2 step, max_lr at
+    step.  UNPINNED: clr_callback.py is absent from the reference tree, so the iteration a batch sees (the callback sets the rate
+    in on_batch_end, for the NEXT batch) cannot be held against it."""
+    it, step = float(iteration), float(step_size)
+    if step <= 0 or it < 0:
+        raise ValueError("cyclic_lr: iteration %r, step_size %r" % (iteration, step_size))
+    cycle = np.floor(1 + it / (2 * step))
+    x = np.abs(it / step - 2 * cycle + 1)
+    return np.float32(base_lr + (max_lr - base_lr) * np.maximum(0.0, 1 - x))
+
+
+def cyclic_session_rates(session, base_lr, max_lr, droprate=0.5):
+    """(base_lr, max_lr) of the 20-epoch session `session` (0, 1, ...) of demo.py:95-110: both halved (droprate) per session by
+    clr._reset; cyclic_lr takes them with the iteration counted from the session's start."""
+    return base_lr * droprate ** int(session), max_lr * droprate ** int(session)
+
+
+class ClsTrainer:
+    """One 01_train step after another on the device: compile(SGD(momentum, nesterov)) + train_on_batch of demo.py:60-61.
+
+        ClsTrainer(model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99)
+          model      a net.vgg16_cam.CAM / net.m7_cam.CAM with its state dict loaded; the trainer trains ITS net in place
+          pool       "mean" (VGG16's head) / "max" (M7's), ClsLoss's
+          bn_keep    forward_train_dev's: the weight of the old running statistics (Keras' momentum 0.99)
+    Parameters and momentum are two resident float32 DeviceMaps of cls_grad().param_elems floats in its param_layout, initialised
+    from the model's state dict and zeros; `grads` is ONE reusable gradient buffer of the same layout.  A step never downloads them.
+
+    step(x, targets, lr, sample_weight=None) -> ClsLoss's metrics dict.  In order: forward_train_dev (the running statistics
+                    move), the loss head reading the Linear from the parameter buffer's tail and writing its gradient into the
+                    gradient buffer's tail, wsc_net_backward_cls into its front, wsc_cls_sgd_step at `lr`, wsc_net_cls_load_params
+                    with the running statistics: afterwards the net -- training and inference form -- computes with the updated
+                    parameters.  Downloads the six loss values and nothing else; frees what it allocates on every path.
+                    A loss that is not finite (or a raised range flag, e.g. a NaN in x: the flag stays raised for the caller to
+                    clear) is a FloatingPointError BEFORE the update is enqueued: parameters, momentum and the packed weights
+                    stay as they were.  THE RUNNING STATISTICS HAVE ALREADY MOVED by then, as in any forward pass.
+    global_step     steps taken (kept by save / load)
+    params_host() / momentum_host()   {name: array in torch's shape}
+    state_dict()    the model's full state dict with the updated tensors and running statistics; also refreshes the wrapper's own
+                    copy, so the trained model and a fresh one loaded from the dict behave identically.  An M7 model's Grad-CAM
+                    head is no parameter: it is the alpha the model had when the trainer was made, and travels in the dict as
+                    `gradcam_weights` (drop the key to have a fresh model derive alpha from the trained weights).
+    save(path) / ClsTrainer.load(path, model, pool, num_classes, ...)   np.save / np.load(...).item() of state_dict() with the
+                    momentum under "__momentum__" and the step count under "__step__"; a resumed run continues bit for bit
+    close() / a context manager releases the three buffers (the model stays the caller's)"""
+
+    def __init__(self, model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99, ctx=None):
+        self.params = self.mom = self.grads = None
+        self.model = model
+        self.ctx = model.ctx
+        if ctx is not None and ctx is not self.ctx:
+            raise ValueError("ClsTrainer: the model lives on another context")
+        self.loss = ClsLoss(self.ctx, pool, num_classes)
+        self.momentum, self.nesterov, self.bn_keep = float(momentum), bool(nesterov), bn_keep
+        if not 0.0 <= self.momentum < 1.0:
+            raise ValueError("ClsTrainer: momentum = %r (0 <= momentum < 1)" % (momentum,))
+        self.global_step = 0
+        extra = model._extra_tensors(model._sd)
+        if "gradcam_weights" in extra and "gradcam_weights" not in model._sd:  # M7: the head the net was built with, kept
+            model._sd["gradcam_weights"] = np.ascontiguousarray(extra["gradcam_weights"], dtype=np.float32)
+        self.grad = model.cls_grad()
+        self._tail = {e["name"].rsplit(".", 1)[1]: e for e in self.grad.param_layout if ".classifier." in e["name"]}
+        if self._tail["weight"]["shape"][0] != self.loss.C:
+            raise ValueError("ClsTrainer: num_classes = %d, the net's classifier has %d rows" % (self.loss.C, self._tail["weight"]["shape"][0]))
+        try:
+            flat = self.grad.flat_params(model._sd)
+            self.params = DeviceMaps.from_host(self.ctx, flat)
+            self.mom = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
+            self.grads = DeviceMaps(self.ctx, flat.shape, np.float32)
+            model.bn_running_dev()  # (the model's own resident buffer, made on first use: here, not inside the first step)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for name in ("params", "mom", "grads"):
+            buf = getattr(self, name, None)
+            if buf is not None:
+                buf.free()
+            setattr(self, name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if self.params is None or getattr(self.model, "_cls_grad", None) is not self.grad:
+            raise ValueError("ClsTrainer: closed, or the model's net was rebuilt since the trainer was made")
+
+    def _tail_views(self, buf):
+        """(weight (C, F), bias (C,) or None): the classifier's ranges of a buffer in param_layout"""
+        w, b = self._tail["weight"], self._tail.get("bias")
+        return _GradView(buf, w["offset"], w["shape"]), None if b is None else _GradView(buf, b["offset"], b["shape"])
+
+    def step(self, x, targets, lr, sample_weight=None):
+        self._live()
+        lr = float(lr)
+        if not np.isfinite(lr) or lr < 0:
+            raise ValueError("ClsTrainer.step: lr = %r" % (lr,))
+        model, grad = self.model, self.grad
+        feat, tape = model.forward_train_dev(x, keep=True, bn_keep=self.bn_keep)
+        head = None
+        try:
+            w, bias = self._tail_views(self.params)
+            try:
+                metrics, head = self.loss.grad_step(feat, w, bias, targets, sample_weight, out=self._tail_views(self.grads))
+            except _lib.WscError as e:
+                if e.status != _lib.WSC_ERR_RANGE:
+                    raise
+                raise FloatingPointError("ClsTrainer.step: the range flag is raised (a value that is not finite, or beyond the "
+                                         "precision's range, entered the net): no update") from e
+            if not np.isfinite(metrics["loss"]):
+                raise FloatingPointError("ClsTrainer.step: the loss is %r: no update" % (metrics["loss"],))
+            grad.backward(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, head.feat.ptr, self.grads.ptr)
+            grad.sgd_step(self.params.ptr, self.grads.ptr, self.mom.ptr, lr, self.momentum, self.nesterov)
+            model.load_params_dev(self.params)
+            self.global_step += 1
+            return metrics
+        finally:
+            for m in (feat, tape, head.feat if head else None):
+                if m is not None:
+                    m.free()
+
+    def _host(self, buf):
+        flat = buf.to_host()
+        out = {}
+        for e in self.grad.param_layout:
+            v = flat[e["offset"]:e["offset"] + e["size"]]
+            if e["conv"]:
+                cout, cin = e["shape"][:2]
+                v = v.reshape(3, 3, cin, cout).transpose(3, 2, 0, 1)
+            out[e["name"]] = np.ascontiguousarray(v.reshape(e["shape"]) if not e["conv"] else v)
+        return out
+
+    def params_host(self):
+        return self._host(self.params)
+
+    def momentum_host(self):
+        return self._host(self.mom)
+
+    def state_dict(self):
+        self._live()
+        sd = self.model._sd
+        for k, v in self.params_host().items():
+            if sd[k].shape == v.shape:
+                sd[k] = v
+            else:  # a Linear of more rows than the net has classes: the trained ones are the first C
+                sd[k] = sd[k].copy()
+                sd[k][:v.shape[0]] = v
+        sd.update(self.model.bn_running())
+        return {k: v.copy() for k, v in sd.items()}
+
+    def save(self, path):
+        d = self.state_dict()
+        d["__momentum__"] = self.momentum_host()
+        d["__step__"] = {"global_step": self.global_step}
+        with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
+            np.save(fh, d, allow_pickle=True)
+
+    @classmethod
+    def load(cls, path, model, pool, num_classes, **kwargs):
+        d = np.load(path, encoding="latin1", allow_pickle=True).item()
+        model.load_state_dict({k: v for k, v in d.items() if not k.startswith("__")})
+        model.cuda()
+        tr = cls(model, pool, num_classes, **kwargs)
+        try:
+            if "__momentum__" in d:
+                flat = tr.grad.flat_params(d["__momentum__"])  # (a slot has the parameters' shapes)
+                tr.mom.free()
+                tr.mom = None
+                tr.mom = DeviceMaps.from_host(tr.ctx, flat)
+            tr.global_step = int(d.get("__step__", {}).get("global_step", 0))
+        except Exception:
+            tr.close()
+            raise
+        return tr
+
+
+def fit(trainer, batches, lr_of_step, steps_per_epoch=None):
+    """`batches`: an iterable of (x, targets) or (x, targets, sample_weight), each through trainer.step at lr_of_step(k), k the
+    trainer's global_step before the step (step_lr(k // steps_per_epoch, ...), cyclic_lr(k, ...)).  -> one dict per epoch of
+    steps_per_epoch batches (None: the whole iterable is one epoch; a last, shorter epoch counts) with the means Keras'
+    fit_generator(verbose=2) prints -- 'loss', 'binary_accuracy', 'f1', each batch weighing with its sample count (BaseLogger) --
+    and 'steps', 'samples'."""
+    epochs, tot, steps, seen = [], {}, 0, 0
+
+    def flush():
+        epochs.append(dict({k: v / seen for k, v in tot.items()}, steps=steps, samples=seen))
+
+    for batch in batches:
+        x, targets = batch[0], batch[1]
+        m = trainer.step(x, targets, lr_of_step(trainer.global_step), batch[2] if len(batch) > 2 else None)
+        n = int(x.shape[0])
+        for k in ("loss", "binary_accuracy", "f1"):
+            tot[k] = tot.get(k, 0.0) + m[k] * n
+        steps, seen = steps + 1, seen + n
+        if steps_per_epoch is not None and steps == int(steps_per_epoch):
+            flush()
+            tot, steps, seen = {}, 0, 0
+    if steps:
+        flush()
+    return epochs

@@ -191,6 +191,37 @@ class CAM(DeviceCAMBase):
             raise
         return ClsGrads(out, grad.layout)
 
+    def load_params_dev(self, flat):
+        """The net rewritten in place from a flat parameter buffer in cls_grad().param_layout (wsc_net_cls_load_params): `flat` a
+        host array of param_elems floats (uploaded once) or a float32 DeviceMaps of the model's context (read in place).  The
+        packed conv rows, BatchNorm's gamma / beta and its inference fold -- from bn_running_dev(), the running statistics as
+        forward_train_dev left them --, the classifier and VGG16's CAM head afterwards have the bits of a model created from the
+        same floats and statistics; an M7 head, the Grad-CAM alpha, is no parameter and stays.  The wrapper's state dict is NOT
+        touched (cls_train.ClsTrainer.state_dict downloads).  The model's cached gradcam_net()s hold packed copies of the old
+        weights: they are released."""
+        from ..secdsrg import DeviceMaps
+
+        self._ensure_net()
+        ctx, grad = self._ctx, self.cls_grad()
+        mine = None
+        if isinstance(flat, DeviceMaps):
+            if flat.dtype != np.float32 or flat.ctx is not ctx or flat.ptr is None:
+                raise ValueError("load_params_dev: flat is no live float32 DeviceMaps of the model's context")
+            fd = flat
+        else:
+            fd = mine = DeviceMaps.from_host(ctx, np.asarray(flat), dtype=np.float32)
+        try:
+            if int(np.prod(fd.shape)) != grad.param_elems:
+                raise ValueError("load_params_dev: %d floats, the layout has %d" % (int(np.prod(fd.shape)), grad.param_elems))
+            run = self.bn_running_dev()
+            grad.load_params(fd.ptr, None if run is None else run.ptr)
+        finally:
+            if mine is not None:
+                mine.free()  # (pooled: reuse is ordered behind the launches on the context's stream)
+        for net in self.__dict__.pop("_gradcam_nets", {}).values():
+            net.close()
+        return self
+
     def predict_labels(self, score):
         """vgg16_cam.py:37-45: score >= thresholds; if nothing passes on non-ADP data force argmax."""
         y = score >= self.thresholds[:len(score)]
