@@ -872,7 +872,8 @@ int wsc_irn_aff_loss(wsc_ctx *ctx, const float *edge_dev, const float *dp_dev, c
  * wsc_cls_loss is model.compile(loss='binary_crossentropy', metrics=['binary_accuracy', f1]) (01_train/demo.py:60-61,
  * utilities.py:69-97) on the head global pool -> Dense -> sigmoid, with the gradient of the loss through that head.  The backward
  * pass through the plain stacks and BatchNorm in training mode follow below (wsc_net_backward_cls), then the Nesterov SGD step
- * with the repack of the updated weights (wsc_cls_sgd_step, wsc_net_cls_load_params); the generators are not here.
+ * with the repack of the updated weights (wsc_cls_sgd_step, wsc_net_cls_load_params), then the generators' sample transform
+ * (wsc_cls_train_batch).
  *   feat_dev      float32 [B][n][F]  the NHWC map the head reduces, as wsc_net_forward_features writes it; n = h w
  *   pool          WSC_CLS_POOL_MEAN: the mean over the n positions (VGG16);  WSC_CLS_POOL_MAX: their maximum (M7) -- the two
  *                 cases of wsc_gap_linear_sigmoid
@@ -1086,6 +1087,49 @@ int wsc_cls_sgd_step(wsc_ctx *ctx, wsc_cls_grad *g, float *param_dev, const floa
                      float momentum, int nesterov);
 int wsc_net_cls_load_params(wsc_ctx *ctx, wsc_net *net, wsc_cls_grad *g, const float *param_dev, long long elems,
                             const float *run_dev /* or NULL */);
+
+/* One 01_train batch of network inputs from decoded uint8 RGB images (csrc/cls_batch.hip): what Keras' ImageDataGenerator behind
+ * flow_from_dataframe(target_size=(H, W)) does to a sample (the generators of 02_cues/dataset.py:28-96 and 03c_hsn/dataset.py;
+ * 01_train/demo.py:56,100-124 trains on them), in Keras' order, for given random choices --
+ *   1. resize       load_img: PIL Image.resize((W, H), NEAREST), skipped when the image is H x W already; the index tables of
+ *                   wsc_pil_resize_u8's order 0, built on the host.  The resized image is never written: every tap below reads the
+ *                   source through the tables.
+ *   2. warp         where bit 0 of the sample's flags is set: scipy.ndimage.affine_transform(plane, M, off, order=1, mode, cval)
+ *                   on each float32 H x W plane, in double and in scipy's order of operations (ni_interpolation.c):
+ *                     c_k = 0; c_k += row M[k][0]; c_k += col M[k][1]; c_k += off[k]   (k = 0 the row axis; the offset is
+ *                     added LAST), mapped by the mode;
+ *                     c_k <= -1 (constant mode outside the image): cval;  else start = floor(c_k), f = c_k - start,
+ *                     w0 = 1 - f, w1 = 1 - w0, both tap indices mapped by the mode again (nearest and constant: a clamp),
+ *                     t = 0; t += (v[i][j] wy[i]) wx[j] in (i, j) order; ONE rounding to float32.
+ *                   fill_mode WSC_CLS_FILL_NEAREST / _REFLECT (scipy's grid reflection d c b a | a b c d) / _CONSTANT.  scipy's
+ *                   'wrap' is WSC_ERR_INVALID: no reference generator uses it.
+ *   3. flips        flip_axis on the columns (bit 1) and / or the rows (bit 2), AFTER the warp
+ *   4. standardise  preprocessing_function, then rescale: y = ((v - sub[c]) / div) * mul, each operation one fp32 rounding.
+ *                   ADP: sub = 193.09203 on every channel, div = float32(56.450138 + 1e-7), mul = 1; VOC2012: sub = (104, 117, 123)
+ *                   on R, G, B as the reference writes it, div = 1, mul = float32(1 / 255); DeepGlobe: sub = 0, div = 1,
+ *                   mul = float32(1 / 255)
+ *   5. HWC -> CHW   the channels stay R, G, B (what cues.utilities._to_nchw feeds the same nets)
+ * Equal to PIL 12 + scipy 1.15 + numpy on every bit: tests/test_cls_batch_oracle.py pins the numpy restatement
+ * tests/cls_batch_ref.py against them, tests/test_gpu_cls_batch.py the kernel against the restatement.
+ *   images_dev uint8: sample b's image [H_b][W_b][3] at byte offset_host[b];  size_hw_host int32 [B][2];
+ *   affine_host double [B][6]: M00 M01 M10 M11 off0 off1, axis 0 = the row (read only where bit 0 of the flags is set);
+ *   flags_host int32 [B]: bit 0 warp, bit 1 flip columns, bit 2 flip rows;  sub3_host float [3];
+ *   x_dev float32 [B][3][H][W].  One launch; 16-byte stores over the flat output when x_dev is 16-byte aligned, the same
+ *   arithmetic in scalar stores otherwise and for the last (B 3 H W) % 4 floats.  Asynchronous on the ctx stream; the staged
+ *   table is the only scratch.
+ * WSC_ERR_INVALID, naming the sample and before any launch: a matrix or offset that is not finite; a warp that maps one of the
+ * four output corners further than 2^20 pixels from the image (the integer conversions of the reflection stay defined); div = 0
+ * or a standardisation constant or cval that is not finite; B outside 1 .. 65535; H or W outside 1 .. 32768; a source side
+ * outside 1 .. 32768; a negative offset; flag bits above bit 2; an unknown fill_mode; a null pointer. */
+#define WSC_CLS_FILL_NEAREST 0
+#define WSC_CLS_FILL_REFLECT 1
+#define WSC_CLS_FILL_CONSTANT 2
+#define WSC_CLS_FLAG_WARP 1
+#define WSC_CLS_FLAG_FLIP_COLS 2
+#define WSC_CLS_FLAG_FLIP_ROWS 4
+int wsc_cls_train_batch(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int32_t *size_hw_host, const int64_t *offset_host,
+                        int H, int W, const double *affine_host /* [B][6] */, const int32_t *flags_host /* [B] */,
+                        int fill_mode /* WSC_CLS_FILL_* */, float cval, const float *sub3_host, float div, float mul, float *x_dev);
 
 /* ---- backward pass of the IRNet heads: total_loss.backward() of step/train_irn.py:127 ------------------------------------------
  * Net.forward detaches every backbone stage (resnet50_irn.py:111-115) and trainable_parameters() is edge_layers + dp_layers, so

@@ -24,6 +24,7 @@
 // This file is compiled with -ffp-contract=off: stage 2's interpolation is the sequence of float64 products and sums of
 // input.hip's msf_input_kernel, the normalisation one fp32 subtract and one fp32 divide.
 #include "common.h"
+#include "pil_nearest.h"
 
 #include <math.h>
 
@@ -248,20 +249,6 @@ int add_resample(std::vector<int32_t> &tab, int in, int out, int o0, int cnt, in
     return (int)off;
 }
 
-// ImagingScaleAffine's source index of every output index of an axis in -> out: the running sum in double
-int add_nearest(std::vector<int32_t> &tab, int in, int out) {
-    const size_t off = tab.size();
-    tab.resize(off + out);
-    const double a = (double)in / (double)out;
-    double v = a * 0.5;
-    for (int i = 0; i < out; ++i) {
-        int idx = (int)v;
-        tab[off + i] = idx < in ? idx : in - 1; // (PIL leaves such a pixel unwritten; it does not occur below 2^31 / in outputs)
-        v += a;
-    }
-    return (int)off;
-}
-
 constexpr size_t TAB_MAX_INTS = (size_t)1 << 28; // int32 indices into the table
 
 unsigned grid_x(long long n, int cap) {
@@ -306,8 +293,8 @@ int wsc_pil_resize_u8(wsc_ctx *ctx, const uint8_t *images_dev, int B, const int3
         j.row0 = 0;
         j.nrows = j.H0;
         if (order == 0) {
-            j.ny_off = add_nearest(tab, j.H0, j.sh);
-            j.nx_off = add_nearest(tab, j.W0, j.sw);
+            j.ny_off = pil_add_nearest(tab, j.H0, j.sh);
+            j.nx_off = pil_add_nearest(tab, j.W0, j.sw);
         } else {
             if (j.sh != j.H0) {
                 int lo, hi;
@@ -389,7 +376,7 @@ int wsc_irn_train_batch(wsc_ctx *ctx, const uint8_t *images_dev, const uint8_t *
     WSC_HIP(hipSetDevice(ctx->device));
     std::vector<BatchJob> jobs(B);
     std::vector<int32_t> tab;
-    const int r_off = add_nearest(tab, S, s);
+    const int r_off = pil_add_nearest(tab, S, s);
     long long tmp_bytes = 0, max_h = 1;
     bool any_h = false;
     for (int b = 0; b < B; ++b) {
@@ -406,8 +393,8 @@ int wsc_irn_train_batch(wsc_ctx *ctx, const uint8_t *images_dev, const uint8_t *
         j.row0 = j.img_top;
         j.nrows = j.ch;
         if (stage == 1 && (j.sh != j.H0 || j.sw != j.W0)) {
-            j.ny_off = add_nearest(tab, j.H0, j.sh);
-            j.nx_off = add_nearest(tab, j.W0, j.sw);
+            j.ny_off = pil_add_nearest(tab, j.H0, j.sh);
+            j.nx_off = pil_add_nearest(tab, j.W0, j.sw);
             if (j.sh != j.H0) { // the vertical taps of the window's rows, and the source rows they touch
                 int lo, hi;
                 j.v_first = j.img_top;

@@ -155,6 +155,7 @@ _SIGNATURES = {
     "wsc_cls_param_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_cls_sgd_step": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _f, _i]),
     "wsc_net_cls_load_params": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _vp]),
+    "wsc_cls_train_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _f, _f, _vp]),
     "wsc_net_edge_tape_plan": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(TapeEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_forward_edge_tape": (_i, [_vp, _vp, _vp, _i, _i, _vp, ctypes.c_longlong, _vp, _vp]),
     "wsc_irn_grad_create": (_i, [_vp, _vp, ctypes.POINTER(TensorDesc), _i, ctypes.POINTER(_vp)]),
@@ -1602,6 +1603,40 @@ def irn_train_batch(ctx, images_dev, labels_dev, sizes, image_offsets, label_off
     check(ctx._lib.wsc_irn_train_batch(ctx.h, _ptr(images_dev), _ptr(labels_dev), B, size_hw.ctypes.data, ioff.ctypes.data,
                                        loff.ctypes.data, p.ctypes.data, int(S), m.ctypes.data, sd.ctypes.data, int(bool(pre_div255)),
                                        int(stage), _ptr(x_dev), _ptr(label_dev), _ptr(reduced_dev)))
+
+
+CLS_FILL_MODES = {"nearest": 0, "reflect": 1, "constant": 2}  # WSC_CLS_FILL_*
+CLS_FLAG_WARP, CLS_FLAG_FLIP_COLS, CLS_FLAG_FLIP_ROWS = 1, 2, 4  # WSC_CLS_FLAG_*
+
+
+def cls_train_batch(ctx, images_dev, sizes, offsets, hw, affine, flags, fill_mode, cval, sub3, div, mul, x_dev):
+    """wsc_cls_train_batch: packed decoded RGB images ([H_b][W_b][3] at byte `offsets`) -> x_dev float32 [B][3][H][W]: PIL nearest
+    resize to hw = (H, W), scipy's order-1 affine warp where bit 0 of a sample's flags is set, the flips (bits 1, 2), ((v - sub[c])
+    / div) * mul.  affine: (B, 6) float64 rows M00 M01 M10 M11 off0 off1 (axis 0 the row); flags: B integers; fill_mode: 'nearest' /
+    'reflect' / 'constant' or its number.  Shapes and dtypes are checked here, before any C call; the values by the library."""
+    B = len(sizes)
+    if not 1 <= B <= 65535:
+        raise ValueError("cls_train_batch: %d samples (1 .. 65535)" % B)
+    size_hw = _hw_table("cls_train_batch: sizes", sizes, B)
+    off = _offset_table("cls_train_batch: offsets", offsets, B)
+    a = np.asarray(affine)
+    if a.shape != (B, 6) or a.dtype.kind != "f":
+        raise ValueError("cls_train_batch: affine %r %s, expected float (%d, 6)" % (a.shape, a.dtype, B))
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    f = np.asarray(flags)
+    if f.shape != (B,) or f.dtype.kind not in "iu":
+        raise ValueError("cls_train_batch: flags %r %s, expected %d integers" % (f.shape, f.dtype, B))
+    f = np.ascontiguousarray(f, dtype=np.int32)
+    s = np.ascontiguousarray(sub3, dtype=np.float32)
+    if s.shape != (3,):
+        raise ValueError("cls_train_batch: sub3 has shape %r, expected (3,)" % (s.shape,))
+    if isinstance(fill_mode, str):
+        if fill_mode not in CLS_FILL_MODES:
+            raise ValueError("cls_train_batch: fill_mode %r (one of %s)" % (fill_mode, sorted(CLS_FILL_MODES)))
+        fill_mode = CLS_FILL_MODES[fill_mode]
+    H, W = int(hw[0]), int(hw[1])
+    check(ctx._lib.wsc_cls_train_batch(ctx.h, _ptr(images_dev), B, size_hw.ctypes.data, off.ctypes.data, H, W, a.ctypes.data,
+                                       f.ctypes.data, int(fill_mode), float(cval), s.ctypes.data, float(div), float(mul), _ptr(x_dev)))
 
 
 def label_unary_from_cam(ctx, highres_dev, B, K, N, thres, gt_prob, unary_dev, labels_dev=None):

@@ -21,9 +21,17 @@
     step_lr          the schedule of demo.py:112-113;  cyclic_lr / cyclic_session_rates: the triangular policy of demo.py:95-110
     fit              an iterable of batches through a trainer -> the per-epoch means fit_generator(verbose=2) prints
 
-Not here: the `D` dropout entries of VGG16's layer5 (the identity here), the data generators (the reference's
-data_loader.py / model_loader.py are missing) and the writing of .h5 files.  Keras evaluates the loss in float32, and what it does
-with the LIST class_weight of demo.py:80-82,107 is not reproduced: ClsLoss takes per-sample weights."""
+    ImageAugmenter   Keras' ImageDataGenerator as 02_cues/dataset.py:28-96 configures it: the random draws, the affine matrix, the
+                     standardisation constants (the reference's 01_train/data_loader.py is missing; these are 02_cues' settings)
+    ClsBatcher       flow_from_dataframe(class_mode='other'): files -> PIL decode on the host -> ONE upload of the ragged uint8
+                     batch -> wsc_cls_train_batch (nearest resize, scipy's order-1 warp, flips, standardise, CHW) -> a float32
+                     DeviceMaps (b, 3, H, W) and the label rows; state() / set_state() for bit-exact resume
+    train            the loop of demo.py:21-127 from files to checkpoints: schedule, ClsTrainer.step per batch, validation per
+                     epoch, <ckpt_dir>/<sess_id>-<epoch>.npy every lr_dropstep epochs, resume, <model_dir>/<sess_id>.npy
+
+Not here: the `D` dropout entries of VGG16's layer5 (the identity here), the writing of .h5 files and
+TensorBoard.  Keras evaluates the loss in float32, and what it does with the LIST class_weight of demo.py:80-82,107 is not
+reproduced: ClsLoss takes per-sample weights, and train passes none (sample_weight=None)."""
 import collections
 import os
 
@@ -438,7 +446,8 @@ class ClsTrainer:
                     head is no parameter: it is the alpha the model had when the trainer was made, and travels in the dict as
                     `gradcam_weights` (drop the key to have a fresh model derive alpha from the trained weights).
     save(path) / ClsTrainer.load(path, model, pool, num_classes, ...)   np.save / np.load(...).item() of state_dict() with the
-                    momentum under "__momentum__" and the step count under "__step__"; a resumed run continues bit for bit
+                    momentum under "__momentum__" and the step count under "__step__"; a resumed run continues bit for bit.
+                    save(path, extra={"__name__": value}) stores more keys of that form; load leaves them in `loaded_extra`
     close() / a context manager releases the three buffers (the model stays the caller's)"""
 
     def __init__(self, model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99, ctx=None):
@@ -452,6 +461,7 @@ class ClsTrainer:
         if not 0.0 <= self.momentum < 1.0:
             raise ValueError("ClsTrainer: momentum = %r (0 <= momentum < 1)" % (momentum,))
         self.global_step = 0
+        self.loaded_extra = {}  # (ClsTrainer.load: the file's own "__name__" keys)
         extra = model._extra_tensors(model._sd)
         if "gradcam_weights" in extra and "gradcam_weights" not in model._sd:  # M7: the head the net was built with, kept
             model._sd["gradcam_weights"] = np.ascontiguousarray(extra["gradcam_weights"], dtype=np.float32)
@@ -556,10 +566,14 @@ class ClsTrainer:
         sd.update(self.model.bn_running())
         return {k: v.copy() for k, v in sd.items()}
 
-    def save(self, path):
+    def save(self, path, extra=None):
         d = self.state_dict()
         d["__momentum__"] = self.momentum_host()
         d["__step__"] = {"global_step": self.global_step}
+        for k, v in (extra or {}).items():
+            if not k.startswith("__") or k in d:
+                raise ValueError("ClsTrainer.save: extra key %r (a new name beginning with '__')" % (k,))
+            d[k] = v
         with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
             np.save(fh, d, allow_pickle=True)
 
@@ -576,6 +590,7 @@ class ClsTrainer:
                 tr.mom = None
                 tr.mom = DeviceMaps.from_host(tr.ctx, flat)
             tr.global_step = int(d.get("__step__", {}).get("global_step", 0))
+            tr.loaded_extra = {k: v for k, v in d.items() if k.startswith("__") and k not in ("__momentum__", "__step__")}
         except Exception:
             tr.close()
             raise
@@ -606,3 +621,394 @@ def fit(trainer, batches, lr_of_step, steps_per_epoch=None):
     if steps:
         flush()
     return epochs
+
+
+# ---- the generators: ImageDataGenerator + flow_from_dataframe (02_cues/dataset.py:28-96), on the device -----------------------------
+class ImageAugmenter:
+    """Keras' ImageDataGenerator, the part the reference configures (02_cues/dataset.py:28-96, 03c_hsn/dataset.py):
+
+        ImageAugmenter(rotation_range=0, width_shift_range=0, height_shift_range=0, shear_range=0, zoom_range=0,
+                       horizontal_flip=False, vertical_flip=False, fill_mode='nearest', cval=0.0, rescale=None, preprocessing=None)
+          rotation_range, shear_range     degrees;  width / height_shift_range: a float, < 1 a fraction of the side, else pixels
+                          (Keras' integer and list forms, drawn with np.random.choice, are a ValueError)
+          zoom_range      z -> [1 - z, 1 + z], or (lower, upper)
+          fill_mode       'nearest' / 'reflect' / 'constant' ('wrap': ValueError, wsc_cls_train_batch does not have it)
+          preprocessing   None, ('sub', (r, g, b)) for x[:, :, c] -= value, or ('affine', a, b) for (x - a) / b -- the three
+                          normalize() functions of dataset.py; applied BEFORE rescale, as ImageDataGenerator.standardize does
+        channel_shift_range, brightness_range, the featurewise / samplewise options and zca_whitening raise ValueError: the
+        reference sets none of them.
+
+        get_random_transform(img_shape, rng) -> {'theta', 'tx', 'ty', 'shear', 'zx', 'zy', 'flip_horizontal', 'flip_vertical'}
+                          from the caller's np.random.RandomState, never the global one.  Draw order: theta, tx (times the
+                          height), ty (times the width), shear, (zx, zy) as ONE uniform(size=2), then the two flip coins, which
+                          are drawn whether or not flipping is enabled.
+        transform_matrix(params, h, w) -> float64 (3, 3) or None (identity parameters, as Keras): rotation . shift . shear . zoom
+                          with numpy's dot, then transform_matrix_offset_center with o = n / 2 + 0.5.
+        affine(params, h, w) -> (six doubles M00 M01 M10 M11 off0 off1 or None, flags): what wsc_cls_train_batch takes
+        standardisation() -> (sub3, div, mul) float32: ((v - sub[c]) / div) * mul
+
+    UNPINNED: the draw order and the composition are restated from the published source of keras_preprocessing 1.1
+    (image/image_data_generator.py get_random_transform, image/affine_transformations.py apply_affine_transform); the package is
+    not available offline, so neither can be held against it.  What IS pinned is everything after the
+    matrix: PIL's resize and scipy's warp, bit for bit (tests/test_cls_batch_oracle.py).
+
+    for_dataset('ADP' | 'VOC2012' | 'DeepGlobe', train) reproduces datagen_aug / datagen_nonaug of 02_cues/dataset.py:28-96; they
+    are 02_cues' settings standing in for the reference's missing 01_train/data_loader.py."""
+
+    def __init__(self, rotation_range=0, width_shift_range=0, height_shift_range=0, shear_range=0, zoom_range=0, horizontal_flip=False,
+                 vertical_flip=False, fill_mode="nearest", cval=0.0, rescale=None, preprocessing=None, **unsupported):
+        for k, v in unsupported.items():
+            if k not in ("channel_shift_range", "brightness_range", "featurewise_center", "samplewise_center", "zca_whitening",
+                         "featurewise_std_normalization", "samplewise_std_normalization"):
+                raise TypeError("ImageAugmenter: unknown argument %r" % (k,))
+            if v:
+                raise ValueError("ImageAugmenter: %s is not mirrored (the reference's generators do not set it)" % k)
+        for name, v in (("width_shift_range", width_shift_range), ("height_shift_range", height_shift_range)):
+            if v and not isinstance(v, (float, np.floating)):
+                raise ValueError("ImageAugmenter: %s = %r: only the float form is mirrored" % (name, v))
+        if fill_mode not in _lib.CLS_FILL_MODES:
+            raise ValueError("ImageAugmenter: fill_mode %r (one of %s)" % (fill_mode, sorted(_lib.CLS_FILL_MODES)))
+        self.rotation_range, self.shear_range = rotation_range, shear_range
+        self.width_shift_range, self.height_shift_range = width_shift_range, height_shift_range
+        if np.isscalar(zoom_range):
+            self.zoom_range = [1 - zoom_range, 1 + zoom_range]
+        elif len(zoom_range) == 2:
+            self.zoom_range = [zoom_range[0], zoom_range[1]]
+        else:
+            raise ValueError("ImageAugmenter: zoom_range %r (a float or (lower, upper))" % (zoom_range,))
+        self.horizontal_flip, self.vertical_flip = bool(horizontal_flip), bool(vertical_flip)
+        self.fill_mode, self.cval, self.rescale = fill_mode, float(cval), rescale
+        if preprocessing is not None and not (len(preprocessing) == 2 and preprocessing[0] == "sub" and len(preprocessing[1]) == 3) \
+                and not (len(preprocessing) == 3 and preprocessing[0] == "affine"):
+            raise ValueError("ImageAugmenter: preprocessing %r (None, ('sub', (r, g, b)) or ('affine', a, b))" % (preprocessing,))
+        self.preprocessing = preprocessing
+
+    @classmethod
+    def for_dataset(cls, dataset, train):
+        if dataset == "ADP":
+            return cls(horizontal_flip=train, vertical_flip=train, preprocessing=("affine", 193.09203, 56.450138 + 1e-7))
+        if dataset == "VOC2012":
+            aug = dict(horizontal_flip=True, width_shift_range=0.1, height_shift_range=0.1, zoom_range=0.2, rotation_range=30,
+                       fill_mode="reflect") if train else {}
+            return cls(rescale=1. / 255, preprocessing=("sub", (104, 117, 123)), **aug)
+        if dataset.startswith("DeepGlobe"):
+            return cls(rescale=1. / 255, horizontal_flip=train, vertical_flip=train)
+        raise ValueError("ImageAugmenter.for_dataset: %r is none of 'ADP', 'VOC2012', 'DeepGlobe'" % (dataset,))
+
+    def get_random_transform(self, img_shape, rng):
+        if not isinstance(rng, np.random.RandomState):
+            raise TypeError("ImageAugmenter.get_random_transform: rng must be the caller's np.random.RandomState")
+        theta = rng.uniform(-self.rotation_range, self.rotation_range) if self.rotation_range else 0
+        tx = ty = 0
+        if self.height_shift_range:
+            tx = rng.uniform(-self.height_shift_range, self.height_shift_range)
+            if self.height_shift_range < 1:
+                tx *= img_shape[0]
+        if self.width_shift_range:
+            ty = rng.uniform(-self.width_shift_range, self.width_shift_range)
+            if self.width_shift_range < 1:
+                ty *= img_shape[1]
+        shear = rng.uniform(-self.shear_range, self.shear_range) if self.shear_range else 0
+        if self.zoom_range[0] == 1 and self.zoom_range[1] == 1:
+            zx, zy = 1, 1
+        else:
+            zx, zy = rng.uniform(self.zoom_range[0], self.zoom_range[1], 2)
+        flip_horizontal = bool(rng.random_sample() < 0.5) and self.horizontal_flip
+        flip_vertical = bool(rng.random_sample() < 0.5) and self.vertical_flip
+        return {"theta": theta, "tx": tx, "ty": ty, "shear": shear, "zx": zx, "zy": zy, "flip_horizontal": flip_horizontal,
+                "flip_vertical": flip_vertical}
+
+    @staticmethod
+    def transform_matrix(params, h, w):
+        theta, tx, ty, shear = params.get("theta", 0), params.get("tx", 0), params.get("ty", 0), params.get("shear", 0)
+        zx, zy = params.get("zx", 1), params.get("zy", 1)
+        m = None
+        if theta != 0:
+            t = np.deg2rad(theta)
+            m = np.array([[np.cos(t), -np.sin(t), 0], [np.sin(t), np.cos(t), 0], [0, 0, 1]])
+        if tx != 0 or ty != 0:
+            s = np.array([[1, 0, tx], [0, 1, ty], [0, 0, 1]])
+            m = s if m is None else np.dot(m, s)
+        if shear != 0:
+            t = np.deg2rad(shear)
+            s = np.array([[1, -np.sin(t), 0], [0, np.cos(t), 0], [0, 0, 1]])
+            m = s if m is None else np.dot(m, s)
+        if zx != 1 or zy != 1:
+            s = np.array([[zx, 0, 0], [0, zy, 0], [0, 0, 1]])
+            m = s if m is None else np.dot(m, s)
+        if m is None:
+            return None
+        o_x, o_y = float(h) / 2 + 0.5, float(w) / 2 + 0.5
+        offset = np.array([[1, 0, o_x], [0, 1, o_y], [0, 0, 1]])
+        reset = np.array([[1, 0, -o_x], [0, 1, -o_y], [0, 0, 1]])
+        return np.dot(np.dot(offset, m), reset)
+
+    def affine(self, params, h, w):
+        m = self.transform_matrix(params, h, w)
+        flags = (_lib.CLS_FLAG_FLIP_COLS if params.get("flip_horizontal") else 0) | (_lib.CLS_FLAG_FLIP_ROWS if params.get("flip_vertical") else 0)
+        if m is None:
+            return None, flags
+        return np.array([m[0, 0], m[0, 1], m[1, 0], m[1, 1], m[0, 2], m[1, 2]], np.float64), flags | _lib.CLS_FLAG_WARP
+
+    def standardisation(self):
+        sub, div = (0.0, 0.0, 0.0), np.float32(1.0)
+        if self.preprocessing is not None and self.preprocessing[0] == "sub":
+            sub = tuple(self.preprocessing[1])
+        elif self.preprocessing is not None:
+            sub, div = (self.preprocessing[1],) * 3, np.float32(self.preprocessing[2])
+        return np.asarray(sub, np.float32), div, np.float32(1.0 if not self.rescale else self.rescale)
+
+
+def _pack_images(images):
+    """uint8 (H, W, 3) arrays -> (one uint8 vector, byte offsets, sizes)"""
+    images = [np.asarray(a) for a in images]
+    for i, a in enumerate(images):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or 0 in a.shape:
+            raise ValueError("ClsBatcher: image %d is %r %s, expected uint8 (H, W, 3)" % (i, a.shape, a.dtype))
+    offs = np.concatenate([[0], np.cumsum([a.size for a in images])]).astype(np.int64)
+    flat = np.empty(int(offs[-1]), np.uint8)
+    for a, o in zip(images, offs):
+        flat[o:o + a.size] = a.reshape(-1)
+    return flat, offs[:-1], [a.shape[:2] for a in images]
+
+
+class ClsBatcher:
+    """flow_from_dataframe(class_mode='other', target_size=(size, size)) of an ImageDataGenerator: an endless stream of batches.
+
+        ClsBatcher(paths, labels, augmenter, size, batch_size, shuffle, seed, ctx=None)
+          paths, labels   n image files and the (n, C) label array;  size: an int or (H, W)
+          shuffle, seed   the order of an epoch is a permutation from the batcher's OWN np.random.RandomState(seed) (False:
+                          0 .. n - 1); the same generator then draws every sample's transform, in batch order
+        .n, .data (the (n, C) float32 label array demo.py:80 sums), len() = ceil(n / batch_size); the last batch of an epoch is
+        the shorter one, and the next epoch begins behind it.
+        next(batcher) -> (x, labels): x a float32 DeviceMaps (b, 3, H, W) the caller frees, labels the (b, C) host rows.  Decoding
+        is PIL on the host (load_img: convert('RGB')); then ONE upload of the ragged uint8 batch and wsc_cls_train_batch.
+        plan()          the host half of a batch -> (indices, affine (b, 6) float64, flags (b,) int32); advances the state
+        apply(images, affine, flags) -> x: the device half on decoded uint8 (H, W, 3) arrays
+        state() / set_state(s)   epoch, position, the epoch's order and the generator's state: a batcher set to a saved state
+                          continues bit for bit
+        Everything a call allocates is freed on every path, x excepted on success."""
+
+    def __init__(self, paths, labels, augmenter, size, batch_size, shuffle, seed, ctx=None):
+        self.paths = list(paths)
+        self.data = np.ascontiguousarray(labels, dtype=np.float32)
+        self.n = len(self.paths)
+        if self.n < 1 or self.data.ndim != 2 or self.data.shape[0] != self.n:
+            raise ValueError("ClsBatcher: %d paths, labels of shape %r" % (self.n, self.data.shape))
+        self.augmenter = augmenter
+        self.hw = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1 or min(self.hw) < 1:
+            raise ValueError("ClsBatcher: batch_size %r, size %r" % (batch_size, size))
+        self.shuffle = bool(shuffle)
+        self._ctx = ctx
+        self.rng = np.random.RandomState(seed)
+        self.epoch, self.pos, self.order = 0, 0, None
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    def __len__(self):
+        return (self.n + self.batch_size - 1) // self.batch_size
+
+    def reset(self):
+        """back to the first batch of the current order's epoch (an unshuffled pass over a validation split)"""
+        self.pos = 0
+
+    def state(self):
+        return {"epoch": self.epoch, "pos": self.pos, "order": None if self.order is None else self.order.copy(),
+                "rng": self.rng.get_state()}
+
+    def set_state(self, s):
+        self.epoch, self.pos = int(s["epoch"]), int(s["pos"])
+        self.order = None if s["order"] is None else np.array(s["order"], np.int64)
+        self.rng.set_state(s["rng"])
+
+    def plan(self):
+        if self.order is None or self.pos >= self.n:
+            if self.order is not None:
+                self.epoch += 1
+            self.order = self.rng.permutation(self.n).astype(np.int64) if self.shuffle else np.arange(self.n, dtype=np.int64)
+            self.pos = 0
+        idx = self.order[self.pos:self.pos + self.batch_size]
+        self.pos += len(idx)
+        H, W = self.hw
+        affine, flags = np.zeros((len(idx), 6), np.float64), np.zeros(len(idx), np.int32)
+        for k in range(len(idx)):
+            a, flags[k] = self.augmenter.affine(self.augmenter.get_random_transform((H, W, 3), self.rng), H, W)
+            if a is not None:
+                affine[k] = a
+        return idx, affine, flags
+
+    def decode(self, idx):
+        from PIL import Image
+
+        out = []
+        for i in idx:
+            with Image.open(self.paths[int(i)]) as im:
+                out.append(np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8))
+        return out
+
+    def apply(self, images, affine, flags):
+        H, W = self.hw
+        flat, offs, sizes = _pack_images(images)
+        sub, div, mul = self.augmenter.standardisation()
+        ctx, src, x = self.ctx, None, None
+        try:
+            src = DeviceMaps.from_host(ctx, flat)
+            x = DeviceMaps(ctx, (len(images), 3, H, W), np.float32)
+            _lib.cls_train_batch(ctx, src.ptr, sizes, offs, (H, W), affine, flags, self.augmenter.fill_mode, self.augmenter.cval, sub, div,
+                                 mul, x.ptr)
+            return x
+        except Exception:
+            if x is not None:
+                x.free()
+            raise
+        finally:
+            if src is not None:  # (pooled: reuse is ordered behind the launch on the context's stream)
+                src.free()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        idx, affine, flags = self.plan()
+        return self.apply(self.decode(idx), affine, flags), self.data[idx]
+
+
+def find_latest_checkpoint(filedir, sess_id):
+    """utilities.py:60-67 for the '<sess_id>-<epoch:02d>.npy' files train writes: the newest file (two of one timestamp: the
+    later epoch) -> (path, epoch), or (None, 0)"""
+    found = []
+    for name in os.listdir(filedir) if os.path.isdir(filedir) else []:
+        stem, ext = os.path.splitext(name)
+        if ext == ".npy" and "-" in stem and "-".join(stem.split("-")[:-1]) == sess_id and stem.split("-")[-1].isdigit():
+            path = os.path.join(filedir, name)
+            found.append((os.path.getmtime(path), int(stem.split("-")[-1]), path))
+    if not found:
+        return None, 0
+    found.sort()
+    return found[-1][2], found[-1][1]
+
+
+def train_schedule(n, batch_size, should_clr=False, base_lr=1e-3, lr_dropstep=20, lr_droprate=0.5, clr_base_lr=1e-3, clr_max_lr=2e-2,
+                   clr_spc=4):
+    """-> rate(epoch, k): the float32 learning rate of batch k (from 0) of epoch `epoch` (from 0, counted over resumes) in train:
+    step_lr(epoch) per epoch (demo.py:112-113), or with should_clr the triangular policy in sessions of lr_dropstep epochs
+    (demo.py:95-110): cyclic_lr(iteration counted from the session's start, *cyclic_session_rates(session), step_size) with
+    step_size = lr_dropstep / clr_spc * n // batch_size, the reference's expression."""
+    steps = int(n) // int(batch_size)
+    step_size = lr_dropstep / clr_spc * n // batch_size
+
+    def rate(epoch, k):
+        if not should_clr:
+            return step_lr(epoch, 0, base_lr, lr_droprate, lr_dropstep)
+        session, within = divmod(int(epoch), int(lr_dropstep))
+        lo, hi = cyclic_session_rates(session, clr_base_lr, clr_max_lr, lr_droprate)
+        return cyclic_lr(within * steps + int(k), lo, hi, step_size)
+
+    return rate
+
+
+def _validate(model, trainer, batcher):
+    """One unshuffled pass of `batcher` over its split through the net's inference feature pass (wsc_net_forward_features: the
+    running statistics) and ClsLoss.loss_step on the trainer's Linear -> {'val_loss', 'val_binary_accuracy', 'val_f1'}, each
+    batch weighing with its sample count."""
+    H, W = batcher.hw
+    if H != W:
+        raise ValueError("train: the inference feature pass takes square inputs, not %dx%d" % (H, W))
+    net, ctx = model._ensure_net(), model.ctx
+    h, F = net.cam_size(H), net.feat_channels()
+    w, bias = trainer._tail_views(trainer.params)
+    tot, seen = {"loss": 0.0, "binary_accuracy": 0.0, "f1": 0.0}, 0
+    batcher.reset()
+    for _ in range(len(batcher)):
+        x, targets = next(batcher)
+        try:
+            b = x.shape[0]
+            with DeviceMaps(ctx, (b, h, h, F), np.float32) as feat:
+                net.forward_features(x.ptr, b, H, feat.ptr)
+                m = trainer.loss.loss_step(feat, w, bias, targets)
+        finally:
+            x.free()
+        for k in tot:
+            tot[k] += m[k] * b
+        seen += b
+    return {"val_" + k: v / seen for k, v in tot.items()}
+
+
+def train(paths, labels, val_paths, val_labels, model, pool, sess_id, model_dir, ckpt_dir, epochs, batch_size, should_clr=False, seed=0,
+          size=321, augmenter="VOC2012", val_augmenter=None, base_lr=1e-3, lr_dropstep=20, lr_droprate=0.5, momentum=0.9,
+          clr_base_lr=1e-3, clr_max_lr=2e-2, clr_spc=4):
+    """train() of 01_train/demo.py:21-127 from image files to checkpoints, on the device.
+
+      paths, labels / val_paths, val_labels   the image files and (n, C) 0/1 label arrays of the two splits (gen_train, gen_val)
+      model, pool     a net.vgg16_cam.CAM / net.m7_cam.CAM with its state dict loaded, and its head ("mean" / "max"): ClsTrainer's
+      augmenter       an ImageAugmenter or a dataset name for ImageAugmenter.for_dataset(name, train=True); val_augmenter: the
+                      same for the validation split (default: the non-augmenting generator of that dataset)
+      size            img_size of demo.py:29-32 (321 VGG16, 224 the M nets)
+    steps_per_epoch = n // batch_size batches of ONE endless ClsBatcher(shuffle=True, seed) per epoch, as fit_generator draws them
+    (the short last batch of a pass opens the next epoch); every batch through ClsTrainer.step(x, labels, rate, None) at
+    train_schedule's rate; after every epoch _validate on the WHOLE validation split in file order (the reference's
+    validation_steps = n // batch_size of a never-reset iterator drifts through the split instead).  Every lr_dropstep epochs
+    <ckpt_dir>/<sess_id>-<epoch:02d>.npy = ClsTrainer.save plus the epoch and the batcher's state; a run finds the latest one
+    (find_latest_checkpoint) and continues from it bit for bit.  At the end <model_dir>/<sess_id>.npy is the state dict.
+    -> one dict per epoch run: {'epoch' (from 1), 'lr' (the last batch's), 'loss', 'binary_accuracy', 'f1', 'val_loss',
+    'val_binary_accuracy', 'val_f1', 'steps', 'samples'}.
+    Not mirrored: validation_steps = n // batch_size (the whole split is validated, see above), class_weight
+    (sample_weight=None), layer5's dropout, the .h5 / .hdf5 formats, the .json architecture file, TensorBoard."""
+    labels = np.ascontiguousarray(labels, dtype=np.float32)
+    n, C = labels.shape
+    epochs, batch_size, lr_dropstep = int(epochs), int(batch_size), int(lr_dropstep)
+    steps = n // batch_size
+    if epochs < 1 or batch_size < 1 or steps < 1:
+        raise ValueError("train: epochs %d, batch_size %d, %d samples" % (epochs, batch_size, n))
+    if isinstance(augmenter, str):
+        if val_augmenter is None:
+            val_augmenter = ImageAugmenter.for_dataset(augmenter, False)
+        augmenter = ImageAugmenter.for_dataset(augmenter, True)
+    if val_augmenter is None:
+        raise ValueError("train: an ImageAugmenter for the training split needs a val_augmenter")
+    for d in (model_dir, ckpt_dir):
+        os.makedirs(d, exist_ok=True)
+    rate = train_schedule(n, batch_size, should_clr, base_lr, lr_dropstep, lr_droprate, clr_base_lr, clr_max_lr, clr_spc)
+    latest, latest_epoch = find_latest_checkpoint(ckpt_dir, sess_id)
+    if latest is not None:
+        trainer = ClsTrainer.load(latest, model, pool, C, momentum=momentum, nesterov=True)
+    else:
+        model.cuda()
+        trainer = ClsTrainer(model, pool, C, momentum=momentum, nesterov=True)
+    history = []
+    try:
+        gen = ClsBatcher(paths, labels, augmenter, size, batch_size, True, seed, ctx=trainer.ctx)
+        gen_val = ClsBatcher(val_paths, val_labels, val_augmenter, size, batch_size, False, seed, ctx=trainer.ctx)
+        if latest is not None:
+            saved = trainer.loaded_extra["__train__"]
+            latest_epoch = int(saved["epoch"])
+            gen.set_state(saved["batcher"])
+        for epoch in range(latest_epoch, epochs):
+            tot, seen, lr = {"loss": 0.0, "binary_accuracy": 0.0, "f1": 0.0}, 0, None
+            for k in range(steps):
+                x, targets = next(gen)
+                try:
+                    lr = rate(epoch, k)
+                    m = trainer.step(x, targets, lr, None)
+                finally:
+                    x.free()
+                for key in tot:
+                    tot[key] += m[key] * len(targets)
+                seen += len(targets)
+            row = dict({key: v / seen for key, v in tot.items()}, epoch=epoch + 1, lr=float(lr), steps=steps, samples=seen)
+            row.update(_validate(model, trainer, gen_val))
+            history.append(row)
+            if (epoch + 1) % lr_dropstep == 0:
+                trainer.save(os.path.join(ckpt_dir, "%s-%02d.npy" % (sess_id, epoch + 1)),
+                             extra={"__train__": {"epoch": epoch + 1, "batcher": gen.state()}})
+        with open(os.path.join(model_dir, sess_id + ".npy"), "wb") as fh:
+            np.save(fh, trainer.state_dict(), allow_pickle=True)
+        return history
+    finally:
+        trainer.close()
