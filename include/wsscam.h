@@ -958,8 +958,9 @@ int wsc_cls_scores_append(wsc_ctx *ctx, const float *src_dev, long long elems, f
 
 /* ---- 01_train: training-mode forward and backward pass of the plain stacks (WSC_ARCH_VGG16_CAM / WSC_ARCH_M7_CAM) ---------------
  * The graph is common_cnn.make_layers' (03b_irn/net/common_cnn.py:128-141): conv(bias) -> ReLU -> BatchNorm(eps = 1e-3) per entry,
- * the max pools between (MaxPool2d(2, 2), or the rows of `pool_spec`).  The `D` dropout entries of VGG16's layer5 are the IDENTITY
- * here (drop_prob = 0); the data generators, Keras' list class_weight and the writing of .h5 files are not here (the Nesterov SGD
+ * the max pools between (MaxPool2d(2, 2), or the rows of `pool_spec`).  The `D` dropout entries (VGG16's layer5, M7's classifier
+ * branch) are the identity in the two entry points of this block and active in the *_drop entry points of the next one;
+ * the data generators, Keras' list class_weight and the writing of .h5 files are not here (the Nesterov SGD
  * step and the repack of updated weights follow this section).  wsc_cls_loss hands out d loss / d feat on the last feature map (and the gradient of the classifier's
  * Linear); wsc_net_backward_cls carries it to every conv and BatchNorm parameter in exact fp32 whatever the forward precision.  The
  * definition is the chain rule EVALUATED AT THE TAPE, as for the other two nets: a ReLU passes dy where its kept output is > 0, a
@@ -1032,6 +1033,59 @@ void wsc_cls_grad_destroy(wsc_cls_grad *g);
 int wsc_cls_grad_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *grad_elems_out);
 int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
                          const float *dfeat_dev, float *grad_dev, long long grad_elems);
+
+/* ---- 01_train: the dropout sites of the plain stacks (nn.Dropout(p=0.5), common_cnn.py:133-134) ----------------------------------
+ * The contract is the one of the SEC / DSRG sites above (wsc_seg_dropout_f32's block), restated: PARITY WITH TENSORFLOW'S AND
+ * KERAS' RANDOM STREAMS IS UNPINNED -- their generators are not reproduced.  A keep-mask depends on (seed, step, site, element
+ * index) alone.
+ *   mask    element i, the linear NHWC index of the site's [B][h][w][C] tensor, draws Philox4x32-10 with key (seed low, seed high)
+ *           and counter (low(i >> 2), high(i >> 2), step, site) and takes output word i & 3; u = float(word >> 8) 2^-24; keep iff
+ *           u >= drop_prob in fp32
+ *   value   d = fmul_rn(y, scale) where kept, +0.0 where dropped; scale = 1.0f / (1.0f - drop_prob); 0 <= drop_prob < 1 (NaN:
+ *           WSC_ERR_INVALID); 0 <= step < 2^32
+ *   sites   numbered by the order of the 'D' entries of the stack's table (net/vgg16.py:44, net/m7.py:41).  VGG16: site 0 behind
+ *           layer5's first entry, site 1 behind its second.  M7: site 0 behind the layer3_p2 pool of the classifier branch
+ *   where   on the value the next op reads.  On a BatchNorm net y is the fp32 fma((a - mean) rstd, gamma, beta) of
+ *           wsc_batch_norm_train_nhwc: it is dropped and scaled in fp32 and then stored ONCE into the net's activation type
+ *           (the two-plane split and the range flag of the un-dropped BatchNorm store); the tape entry "<key>.bn" is the fp32 value
+ *           those planes hold.  On a net without BatchNorm (the ADP VGG16) the post-ReLU entry "<key>" is dropped, exactly as
+ *           fc6 / fc7 are.  M7's pooled map is dropped as fp32.  The tape plan (wsc_net_cls_tape_plan) does not change: no mask entry
+ *   back    a site behind a BatchNorm cannot take its mask from the tape (a kept output may be negative or exactly 0.0): the
+ *           gradient kernels REGENERATE the keep bits from (seed, step, site).  A post-ReLU site uses scale [tape > 0], as fc6 / fc7.
+ *           M7's site sits in front of the global max: a dropped +0.0 can win the maximum of a channel whose kept values are all
+ *           negative; wsc_cls_loss then hands its gradient to that element, and the site's backward makes it +0.0
+ *
+ * wsc_batch_norm_train_drop_nhwc: wsc_batch_norm_train_nhwc with y_dev = the dropped fp32 output; the statistics and the running
+ *   statistics are those of the un-dropped call, bit for bit.  y_dev may lie off the 16-byte grid (4-byte aligned: the scalar form,
+ *   the same bits).  At drop_prob = 0 the kernel keeps everything and scale = 1: y_dev has the un-dropped bits.
+ * wsc_batch_norm_grad_drop_nhwc: wsc_batch_norm_grad_nhwc where dy_dev is the gradient BEHIND the dropout: both kernels replace
+ *   dy on load by keep ? fmul_rn(dy, scale) : +0.0 -- the bits of the un-dropped call on a dy masked that way; no buffer, no pass.
+ *   Both: site < 0, drop_prob outside [0, 1) or NaN, step outside [0, 2^32) and everything the un-dropped entries refuse are
+ *   WSC_ERR_INVALID before any launch.
+ * wsc_net_cls_feat_dims: the h x w of feat_dev / dfeat_dev for an H x W input.  With `dropping` (non-zero: drop_prob > 0) an M7
+ *   net's map is the dropped layer3_p2 map [B][hp][wp][F], which the global max of wsc_cls_loss then reduces; a VGG16 net's stays
+ *   [B][h][w][F], then the dropped output of site 1.  dropping = 0: the last feature map of either net.
+ * wsc_net_forward_cls_train_drop / wsc_net_backward_cls_drop: the two passes with the sites active.  feat_elems / dfeat_elems: the
+ *   floats of feat_dev / dfeat_dev, B h w F of wsc_net_cls_feat_dims(dropping = drop_prob > 0); any other value is
+ *   WSC_ERR_INVALID, as are the dropout arguments above and everything the un-dropped entry points refuse -- all before any launch.
+ *   AT drop_prob = 0 BOTH ISSUE THE LAUNCHES OF wsc_net_forward_cls_train / wsc_net_backward_cls AND GIVE THEIR BITS (M7: the
+ *   un-pooled feature map and its size).  At a BatchNorm site one kernel replaces the apply-and-copy pair of the forward pass; M7
+ *   adds the pool, the fp32 copy and wsc_seg_dropout_f32's kernel forward, that kernel on dfeat_dev and the pool gradient backward.
+ *   wsc_net_backward_cls_drop MUST BE GIVEN THE (drop_prob, seed, step) OF THE FORWARD PASS THAT WROTE THE TAPE: nothing on the tape
+ *   records them, and other values give the gradient of another mask without any error. */
+int wsc_batch_norm_train_drop_nhwc(wsc_ctx *ctx, const float *a_dev, long long M, int C, const float *gamma_dev, const float *beta_dev, float eps,
+                                   float keep, int unbiased, float *run_dev /* [2][C] or NULL */, float *stats_dev /* [C][2] */, float *y_dev,
+                                   float drop_prob, unsigned long long seed, long long step, int site);
+int wsc_batch_norm_grad_drop_nhwc(wsc_ctx *ctx, const float *a_dev, const float *stats_dev, const float *gamma_dev, const float *dy_dev,
+                                  long long M, int C, float *da_dev, float *dgamma_dev, float *dbeta_dev, float drop_prob,
+                                  unsigned long long seed, long long step, int site);
+int wsc_net_cls_feat_dims(const wsc_net *net, int H, int W, int dropping, int *h, int *w);
+int wsc_net_forward_cls_train_drop(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float keep, int unbiased,
+                                   float *run_dev /* or NULL */, float *tape_dev, long long tape_elems, float *feat_dev, long long feat_elems,
+                                   float drop_prob, unsigned long long seed, long long step);
+int wsc_net_backward_cls_drop(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                              const float *dfeat_dev, float *grad_dev, long long grad_elems, long long dfeat_elems, float drop_prob,
+                              unsigned long long seed, long long step);
 
 /* ---- 01_train: the update half of a step -- Keras' SGD with Nesterov momentum and the repack of the updated parameters ----------
  * wsc_cls_param_layout: the TRAINING layout of a wsc_cls_grad.  Every entry of wsc_cls_grad_layout, unchanged and at the same

@@ -735,4 +735,15 @@ int launch_batch_norm_train(wsc_ctx *ctx, const float *a, long long M, int C, co
 // da [M][C], dgamma [C], dbeta [C] from the input a, the forward pass's float statistics and the gradient dy of the output
 int launch_batch_norm_grad(wsc_ctx *ctx, const float *a, const float *stats, const float *gamma, const float *dy, long long M, int C,
                            float *da, float *dgamma, float *dbeta);
+// A dropout site behind a BatchNorm (dropout_rng.h's contract; the caller has checked drop_prob and step: seg_dropout_check).
+// Forward: y = fma((a - mean) rstd, gamma, beta) from the stats launch_batch_norm_train left, dropped and scaled in fp32, stored
+// ONCE into `act` (any precision; the GroupNorm store's split and range flag) and, as the fp32 value `act` then holds, into tape
+// (or null) -- in place of launch_group_norm_apply + launch_act_to_f32.  16-byte accesses where gamma, beta, act and tape allow,
+// else the scalar form: the same bits
+int launch_batch_norm_apply_drop(wsc_ctx *ctx, const float *a, const float *stats, const float *gamma, const float *beta, long long M, int C,
+                                 Act act, float *tape, float drop_prob, unsigned long long seed, unsigned step, unsigned site);
+// Backward: launch_batch_norm_grad with dy the gradient BEHIND the dropout -- the kernels replace it on load by
+// keep ? fmul_rn(dy, scale) : +0.0 with the keep bits regenerated from (seed, step, site)
+int launch_batch_norm_grad_drop(wsc_ctx *ctx, const float *a, const float *stats, const float *gamma, const float *dy, long long M, int C,
+                                float *da, float *dgamma, float *dbeta, float drop_prob, unsigned long long seed, unsigned step, unsigned site);
 

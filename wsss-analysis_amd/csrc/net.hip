@@ -83,6 +83,7 @@ struct Op {
     bool avg = false;               // OP_POOL: the average instead of the maximum
     int pitch = 0;                  // channels per output row when the op writes a channel range of a wider (concatenated) tensor, else 0
     int coff = 0;                   // first channel of that range
+    int drop_site = -1;             // OP_CONV of a plain stack: the dropout site behind it (a 'D' entry, in table order), -1 without one
     int in2 = -1;                   // OP_CONV, 1x1: buffer whose pixels (ho * ps, wo * ps) supply the LAST input channels (ConvLaunch::x2), or -1
     std::string label;              // the state-dict layers the op implements (wsc_net_trace_plan): a conv's weight key without ".weight",
                                     // "<block>.conv3+downsample" for the stage-entry GEMM, "<block>.gather", "pool:<ordinal>"
@@ -466,6 +467,7 @@ int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
     int in_ch = 3;
     bool first = true;
     size_t n_pool = 0;
+    int n_drop = 0;
     for (const auto &layer : cfg) {
         int idx = 0;
         for (int v : layer.second) {
@@ -478,7 +480,10 @@ int build_plain_stack(wsc_net *net, const Dict &d, const std::string &root,
                 } else add_pool_op(net, POOL_TORCH, 2, 2, 0, false, cur, out);
                 cur = out;
                 idx += 1;
-            } else if (v == -2) { // nn.Dropout: identity in eval()
+            } else if (v == -2) { // nn.Dropout: identity in eval(); a site of wsc_net_forward_cls_train_drop
+                // (numbered in table order; one behind a pool -- the IRN flavour of M7 -- belongs to no training pass)
+                if (!net->ops.empty() && net->ops.back().type == OP_CONV) net->ops.back().drop_site = n_drop;
+                n_drop += 1;
                 idx += 1;
             } else {
                 const std::string key = root + "." + layer.first + "." + std::to_string(idx);
@@ -886,12 +891,19 @@ struct TraceSink {
 
 // wsc_net_forward_cls_train's part of run_backbone: where op i's BatchNorm finds its input a (the trace copy of the conv's output)
 // and leaves its statistics and the value the next op reads, all in the caller's tape; the running statistics (or null)
+// the dropout of a training pass through a plain stack (wsc_net_forward_cls_train_drop / wsc_net_backward_cls_drop), drop_prob > 0
+struct ClsDrop {
+    float drop_prob;
+    unsigned long long seed;
+    unsigned step;
+};
 struct BnTrainSink {
     const long long *a_off, *stats_off, *y_off; // per op, floats into `tape`
     float *tape;
     float keep;
     int unbiased;
     float *run; // [2][C] per BatchNorm layer in stack order, or null
+    const ClsDrop *drop; // null: every Op::drop_site is the identity
 };
 // a [M][C] -> the batch statistics; the activation `act` = the normalised output through the store the GroupNorm heads use (one
 // "sample" of M pixels, every channel a group of its own: the same fmaf on the same float statistics, the planes' split and the
@@ -905,6 +917,9 @@ int bn_train_step(wsc_ctx *ctx, const wsc_net *net, const BnTrainSink &s, int op
         for (int k = 0; k < net->convs[net->ops[op].conv].bn; ++k) run += 2 * net->bns[k].C;
     }
     WSC_TRY(launch_batch_norm_train(ctx, a, M, bn.C, bn.gamma, bn.beta, bn.eps, s.keep, s.unbiased, run, stats, nullptr));
+    if (s.drop && net->ops[op].drop_site >= 0) // (one pass: the dropped value into the planes and into the tape)
+        return launch_batch_norm_apply_drop(ctx, a, stats, bn.gamma, bn.beta, M, bn.C, act, s.tape + s.y_off[op], s.drop->drop_prob,
+                                            s.drop->seed, s.drop->step, (unsigned)net->ops[op].drop_site);
     WSC_TRY(launch_group_norm_apply(ctx, a, stats, bn.gamma, bn.beta, 1, (int)M, 1, bn.C, bn.C, 1, 0, act, (int)M, 1, bn.C, 0));
     return launch_act_to_f32(ctx, act, (size_t)M * bn.C, s.tape + s.y_off[op]);
 }
@@ -984,7 +999,13 @@ int run_backbone(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int N, in
             WSC_CHECK(pool_geom(op.rule, op.pk, op.ps, op.pp, op.avg, d.H, d.W, &g), WSC_ERR_INVALID, "internal: a pool plan_dims let through");
             WSC_TRY(launch_pool(ctx, src, N, d.H, d.W, d.C, g, buf[op.out]));
         }
-        if (trace && trace->off[i] >= 0) WSC_TRY(launch_act_to_f32(ctx, buf[op.out], pl.out_elems(N, (int)i), trace->out + trace->off[i]));
+        // (a dropout site of a stack without BatchNorm: the post-ReLU value dropped in place of the copy, as behind fc6 / fc7)
+        const bool relu_site = bn_train && bn_train->drop && op.type == OP_CONV && op.drop_site >= 0 && net->convs[op.conv].bn < 0;
+        if (relu_site) {
+            WSC_CHECK(trace && trace->off[i] >= 0 && op.pitch == 0, WSC_ERR_INVALID, "internal: a dropout site without its tape entry");
+            WSC_TRY(launch_seg_dropout(ctx, buf[op.out], pl.out_elems(N, (int)i), d.Co, bn_train->drop->drop_prob, bn_train->drop->seed,
+                                       bn_train->drop->step, (unsigned)op.drop_site, trace->out + trace->off[i]));
+        } else if (trace && trace->off[i] >= 0) WSC_TRY(launch_act_to_f32(ctx, buf[op.out], pl.out_elems(N, (int)i), trace->out + trace->off[i]));
         if (bn_train && op.type == OP_CONV && net->convs[op.conv].bn >= 0)
             WSC_TRY(bn_train_step(ctx, net, *bn_train, (int)i, (long long)N * d.Ho * d.Wo, buf[op.out]));
         if (taps)
@@ -2523,8 +2544,10 @@ int wsc_irn_edge_finish(wsc_ctx *ctx, const float *e_dev, int He, int We, const 
 
 // ---- 01_train: the plain stacks (VGG16 / M7) in training mode, and their backward pass ------------------------------------------
 // The graph is common_cnn.make_layers': conv(bias) -> ReLU -> BatchNorm(eps = 1e-3) per entry, the pools between, the `D` entries of
-// VGG16's layer5 the identity (drop_prob = 0).  wsc_cls_loss hands out d loss / d feat on the last feature map; the pass below
-// carries it to every conv and BatchNorm parameter.  Kernels: cls_grad.hip (BatchNorm), pool.hip, seg_grad.hip (the GEMMs).
+// VGG16's layer5 and of M7's classifier branch the identity in wsc_net_forward_cls_train / wsc_net_backward_cls and the sites of
+// the *_drop entry points (Op::drop_site, M7_DROP_SITE; the contract: dropout_rng.h).  wsc_cls_loss hands out d loss / d feat on
+// the last feature map; the pass below carries it to every conv and BatchNorm parameter.  Kernels: cls_grad.hip (BatchNorm),
+// pool.hip, seg_grad.hip (the GEMMs).
 namespace {
 int need_cls(const char *fn, const wsc_net *net) {
     WSC_CHECK(net->arch == WSC_ARCH_VGG16_CAM || net->arch == WSC_ARCH_M7_CAM, WSC_ERR_INVALID,
@@ -2560,7 +2583,36 @@ int cls_shape_check(const char *fn, int B, int H, int W, const float *tape_dev) 
     WSC_CHECK(((uintptr_t)tape_dev & 255) == 0, WSC_ERR_INVALID, "%s: the tape must start on a 256-byte line", fn);
     return WSC_OK;
 }
+// M7's classifier branch (layer3_p2: MaxPool2d(2, 2), or the third row of `pool_spec`) on the hf x wf feature map
+int cls_branch_pool(const char *fn, const wsc_net *net, int hf, int wf, PoolGeom *g) {
+    const bool ok = net->cls_pool_set ? pool_geom(net->cls_pool.rule(), net->cls_pool.k, net->cls_pool.stride, 0, false, hf, wf, g)
+                                      : pool_geom(POOL_TORCH, 2, 2, 0, false, hf, wf, g);
+    WSC_CHECK(ok, WSC_ERR_INVALID, "%s: the %d x %d feature map is smaller than the classifier branch's pool", fn, hf, wf);
+    return WSC_OK;
+}
+// the map wsc_cls_loss reduces: the last feature map -- or, with M7's dropout site active, the pooled map the site drops
+int cls_feat_dims(const char *fn, const wsc_net *net, const Plan &pl, bool dropping, int *h, int *w) {
+    *h = pl.hf;
+    *w = pl.wf;
+    if (!dropping || !net->cls_max) return WSC_OK;
+    PoolGeom g;
+    WSC_TRY(cls_branch_pool(fn, net, pl.hf, pl.wf, &g));
+    *h = g.Ho;
+    *w = g.Wo;
+    return WSC_OK;
+}
+constexpr unsigned M7_DROP_SITE = 0; // the one 'D' entry of m7.py:41, behind layer3_p2
 } // namespace
+
+int wsc_net_cls_feat_dims(const wsc_net *net, int H, int W, int dropping, int *h, int *w) {
+    const char *fn = "wsc_net_cls_feat_dims";
+    WSC_CHECK(net && h && w, WSC_ERR_INVALID, "%s: null argument", fn);
+    WSC_TRY(need_cls(fn, net));
+    WSC_CHECK(H >= 1 && W >= 1, WSC_ERR_INVALID, "%s: input %d x %d", fn, H, W);
+    Plan pl;
+    WSC_TRY(plan_dims(net, 1, H, W, &pl));
+    return cls_feat_dims(fn, net, pl, dropping != 0, h, w);
+}
 
 int wsc_net_cls_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W, wsc_tape_entry *entries_out, int max_entries, int *n_out,
                           long long *tape_elems_out) {
@@ -2573,9 +2625,10 @@ int wsc_net_cls_tape_plan(wsc_ctx *ctx, const wsc_net *net, int B, int H, int W,
     return tape_export(tp.t, entries_out, max_entries, n_out, tape_elems_out);
 }
 
-int wsc_net_forward_cls_train(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float keep, int unbiased,
-                              float *run_dev, float *tape_dev, long long tape_elems, float *feat_dev) {
-    const char *fn = "wsc_net_forward_cls_train";
+namespace {
+// wsc_net_forward_cls_train (drop null) and wsc_net_forward_cls_train_drop (drop null at drop_prob = 0: the same launches)
+int cls_forward(const char *fn, wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float keep, int unbiased,
+                float *run_dev, float *tape_dev, long long tape_elems, float *feat_dev, const long long *feat_elems, const ClsDrop *drop) {
     WSC_CHECK(ctx && net && x_dev && tape_dev && feat_dev, WSC_ERR_INVALID, "%s: null argument", fn);
     WSC_TRY(need_cls(fn, net));
     WSC_TRY(cls_shape_check(fn, B, H, W, tape_dev));
@@ -2584,6 +2637,10 @@ int wsc_net_forward_cls_train(wsc_ctx *ctx, const wsc_net *net, const float *x_d
     ClsTapePlan tp;
     WSC_TRY(cls_tape_plan(net, B, H, W, &tp));
     WSC_TRY(tape_check(fn, "wsc_net_cls_tape_plan", tape_elems, tp.t));
+    int h_out, w_out;
+    WSC_TRY(cls_feat_dims(fn, net, tp.pl, drop != nullptr, &h_out, &w_out));
+    WSC_CHECK(!feat_elems || *feat_elems == (long long)B * h_out * w_out * net->F, WSC_ERR_INVALID,
+              "%s: feat_elems = %lld, the map is [%d][%d][%d][%d] (wsc_net_cls_feat_dims)", fn, feat_elems ? *feat_elems : 0ll, B, h_out, w_out, net->F);
     std::vector<long long> a_off, stats_off, y_off;
     for (size_t i = 0; i < net->ops.size(); ++i) {
         const OpDims &d = tp.pl.ops[i];
@@ -2595,16 +2652,41 @@ int wsc_net_forward_cls_train(wsc_ctx *ctx, const wsc_net *net, const float *x_d
     }
     WSC_HIP(hipSetDevice(ctx->device));
     const TraceSink sink = {a_off.data(), tape_dev};
-    const BnTrainSink bn = {a_off.data(), stats_off.data(), y_off.data(), tape_dev, keep, unbiased, run_dev};
+    const BnTrainSink bn = {a_off.data(), stats_off.data(), y_off.data(), tape_dev, keep, unbiased, run_dev, drop};
     // (behind the stack's buffers: the NHWC4 input as fp32 on its way to the tape's 3-channel entry)
     const size_t in4_elems = (size_t)B * H * W * 4;
-    Act feat, xin;
+    Act feat, xin, spare;
     int hf, wf;
     void *extra;
-    WSC_TRY(run_backbone(ctx, net, x_dev, B, H, in4_elems * sizeof(float), &feat, &hf, &wf, &extra, nullptr, W, false, nullptr, &sink, &xin, &bn));
+    WSC_TRY(run_backbone(ctx, net, x_dev, B, H, in4_elems * sizeof(float), &feat, &hf, &wf, &extra, nullptr, W, false, &spare, &sink, &xin, &bn));
     WSC_TRY(launch_act_to_f32(ctx, xin, in4_elems, (float *)extra));
     WSC_TRY(launch_copy_channels(ctx, (const float *)extra, (long long)B * H * W, 4, 3, tape_dev + tp.t.off(0)));
+    if (drop && net->cls_max) { // M7: layer3_p2 -> the site -> (wsc_cls_loss's) global max; the pooled map is dropped as fp32
+        PoolGeom g;
+        WSC_TRY(cls_branch_pool(fn, net, hf, wf, &g));
+        const long long n = (long long)B * g.Ho * g.Wo * net->F;
+        WSC_TRY(launch_pool(ctx, feat, B, hf, wf, net->F, g, spare));
+        WSC_TRY(launch_act_to_f32(ctx, spare, (size_t)n, feat_dev));
+        return launch_seg_dropout_f32(ctx, feat_dev, feat_dev, nullptr, nullptr, n, 0ull, drop->drop_prob, drop->seed, drop->step, M7_DROP_SITE);
+    }
     return launch_act_to_f32(ctx, feat, (size_t)B * hf * wf * net->F, feat_dev);
+}
+} // namespace
+
+int wsc_net_forward_cls_train(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float keep, int unbiased,
+                              float *run_dev, float *tape_dev, long long tape_elems, float *feat_dev) {
+    return cls_forward("wsc_net_forward_cls_train", ctx, net, x_dev, B, H, W, keep, unbiased, run_dev, tape_dev, tape_elems, feat_dev, nullptr,
+                       nullptr);
+}
+
+int wsc_net_forward_cls_train_drop(wsc_ctx *ctx, const wsc_net *net, const float *x_dev, int B, int H, int W, float keep, int unbiased,
+                                   float *run_dev, float *tape_dev, long long tape_elems, float *feat_dev, long long feat_elems, float drop_prob,
+                                   unsigned long long seed, long long step) {
+    const char *fn = "wsc_net_forward_cls_train_drop";
+    WSC_TRY(seg_dropout_check(fn, drop_prob, step));
+    const ClsDrop drop = {drop_prob, seed, (unsigned)step};
+    return cls_forward(fn, ctx, net, x_dev, B, H, W, keep, unbiased, run_dev, tape_dev, tape_elems, feat_dev, &feat_elems,
+                       drop_prob > 0.f ? &drop : nullptr);
 }
 
 namespace {
@@ -2728,9 +2810,10 @@ int wsc_cls_grad_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int 
     return WSC_OK;
 }
 
-int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
-                         const float *dfeat_dev, float *grad_dev, long long grad_elems) {
-    const char *fn = "wsc_net_backward_cls";
+namespace {
+// wsc_net_backward_cls (drop null) and wsc_net_backward_cls_drop (drop null at drop_prob = 0: the same launches)
+int cls_backward(const char *fn, wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                 const float *dfeat_dev, const long long *dfeat_elems, float *grad_dev, long long grad_elems, const ClsDrop *drop) {
     WSC_TRY(grad_check(fn, ctx, g, grad_elems, tape_dev && dfeat_dev && grad_dev));
     WSC_TRY(cls_shape_check(fn, B, H, W, tape_dev));
     WSC_CHECK(((uintptr_t)dfeat_dev & 15) == 0 && ((uintptr_t)grad_dev & 15) == 0, WSC_ERR_INVALID, "%s: dfeat_dev / grad_dev must be 16-byte aligned", fn);
@@ -2738,9 +2821,16 @@ int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, con
     ClsTapePlan tp;
     WSC_TRY(cls_tape_plan(net, B, H, W, &tp));
     WSC_TRY(tape_check(fn, "wsc_net_cls_tape_plan", tape_elems, tp.t));
+    int h_in, w_in;
+    WSC_TRY(cls_feat_dims(fn, net, tp.pl, drop != nullptr, &h_in, &w_in));
+    WSC_CHECK(!dfeat_elems || *dfeat_elems == (long long)B * h_in * w_in * net->F, WSC_ERR_INVALID,
+              "%s: dfeat_elems = %lld, the map is [%d][%d][%d][%d] (wsc_net_cls_feat_dims)", fn, dfeat_elems ? *dfeat_elems : 0ll, B, h_in, w_in, net->F);
+    const bool m7_site = drop && net->cls_max;
+    PoolGeom branch;
+    if (m7_site) WSC_TRY(cls_branch_pool(fn, net, tp.pl.hf, tp.pl.wf, &branch));
     // every layer's plan and the workspace they need, before anything is launched
     std::vector<WgradPlan> plans(g->layers.size());
-    long long g_max = 0, dz_max = 0, slab_max = 0, part_max = 0;
+    long long g_max = m7_site ? (long long)B * tp.pl.hf * tp.pl.wf * net->F : 0, dz_max = 0, slab_max = 0, part_max = 0;
     for (size_t i = 0; i < net->ops.size(); ++i) {
         const OpDims &d = tp.pl.ops[i];
         g_max = std::max(g_max, (long long)B * d.H * d.W * d.C);
@@ -2760,8 +2850,14 @@ int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, con
     float *dbn = ws.floats(dz_max), *dz = ws.floats(dz_max), *slab = ws.floats(slab_max), *partial = ws.floats(part_max);
     auto at = [&](int entry) { return tape_dev + tp.t.off(entry); };
 
-    const float *gcur = dfeat_dev; // the gradient of op i's output (behind its BatchNorm, where it has one)
+    const float *gcur = dfeat_dev; // the gradient of op i's output (behind its BatchNorm and its dropout site, where it has them)
     int nf = 0;
+    if (m7_site) { // the site's own gradient (a dropped +0.0 that won the global max passes nothing on), then layer3_p2's
+        const long long n = (long long)B * branch.Ho * branch.Wo * net->F;
+        WSC_TRY(launch_seg_dropout_f32(ctx, dfeat_dev, gfree[0], nullptr, nullptr, n, 0ull, drop->drop_prob, drop->seed, drop->step, M7_DROP_SITE));
+        WSC_TRY(launch_pool_grad(ctx, at(tp.out.back()), gfree[0], B, tp.pl.hf, tp.pl.wf, net->F, branch, gfree[1]));
+        gcur = gfree[1];
+    }
     for (int i = (int)net->ops.size() - 1; i >= 0; --i) {
         const Op &op = net->ops[i];
         const OpDims &d = tp.pl.ops[i];
@@ -2776,12 +2872,19 @@ int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, con
             const ClsGradLayer &L = g->layers[li];
             const long long M = (long long)B * d.Ho * d.Wo;
             const float *a = at(tp.a[i]);
+            const bool site = drop && op.drop_site >= 0;
             if (L.bn >= 0) {
-                WSC_TRY(launch_batch_norm_grad(ctx, a, at(tp.stats[i]), net->bns[L.bn].gamma, gcur, M, L.Cout, dbn, grad_dev + L.g_off,
-                                               grad_dev + L.be_off));
+                if (site) // (the mask regenerated from the counter: a kept BatchNorm output may be negative or 0.0)
+                    WSC_TRY(launch_batch_norm_grad_drop(ctx, a, at(tp.stats[i]), net->bns[L.bn].gamma, gcur, M, L.Cout, dbn, grad_dev + L.g_off,
+                                                        grad_dev + L.be_off, drop->drop_prob, drop->seed, drop->step, (unsigned)op.drop_site));
+                else
+                    WSC_TRY(launch_batch_norm_grad(ctx, a, at(tp.stats[i]), net->bns[L.bn].gamma, gcur, M, L.Cout, dbn, grad_dev + L.g_off,
+                                                   grad_dev + L.be_off));
                 gcur = dbn;
             }
-            WSC_TRY(launch_relu_bias_grad(ctx, a, gcur, M, L.Cout, 1.0f, dz, partial, grad_dev + L.b_off));
+            // (a site without BatchNorm: the taped post-ReLU value is > 0 exactly where kept and positive, as behind fc6 / fc7)
+            const float relu_scale = site && L.bn < 0 ? seg_dropout_scale(drop->drop_prob) : 1.0f;
+            WSC_TRY(launch_relu_bias_grad(ctx, a, gcur, M, L.Cout, relu_scale, dz, partial, grad_dev + L.b_off));
             WSC_TRY(wgrad_launch(ctx, plans[li], x, dz, d.Ho, d.Wo, L.Cin, L.Cout, 3, 1, slab, grad_dev + L.w_off));
             if (i > 0) WSC_TRY(dgrad_launch(ctx, dz, L.w_rot, g->ones, g->zeros, B, d.Ho, d.Wo, L.Cin, L.Cout, 3, 1, nullptr, gout));
         }
@@ -2789,6 +2892,21 @@ int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, con
         nf ^= 1;
     }
     return WSC_OK;
+}
+} // namespace
+
+int wsc_net_backward_cls(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                         const float *dfeat_dev, float *grad_dev, long long grad_elems) {
+    return cls_backward("wsc_net_backward_cls", ctx, g, B, H, W, tape_dev, tape_elems, dfeat_dev, nullptr, grad_dev, grad_elems, nullptr);
+}
+
+int wsc_net_backward_cls_drop(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W, const float *tape_dev, long long tape_elems,
+                              const float *dfeat_dev, float *grad_dev, long long grad_elems, long long dfeat_elems, float drop_prob,
+                              unsigned long long seed, long long step) {
+    const char *fn = "wsc_net_backward_cls_drop";
+    WSC_TRY(seg_dropout_check(fn, drop_prob, step));
+    const ClsDrop drop = {drop_prob, seed, (unsigned)step};
+    return cls_backward(fn, ctx, g, B, H, W, tape_dev, tape_elems, dfeat_dev, &dfeat_elems, grad_dev, grad_elems, drop_prob > 0.f ? &drop : nullptr);
 }
 
 // ---- the update half of a 01_train step (Keras' SGD with Nesterov momentum, 01_train/demo.py:60) and the repack of the updated

@@ -15,37 +15,11 @@
 //             round depends on a loaded value.  A tensor whose first element is off the 4-element grid of the counter, or a buffer
 //             off the 16-byte grid, takes the scalar form: one element and one block per thread, the same words.
 #include "common.h"
+#include "dropout_rng.h" // (Philox4x32-10, DropRng, the keep rule and the value: one definition of the counter layout)
 
 namespace {
 
 constexpr int DROP_BLOCK = 256; // four waves of 64
-
-struct DropRng {
-    uint32_t k0, k1;   // the seed
-    uint32_t step, site;
-    float drop_prob, scale;
-};
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// the four words of counter block `blk` (= element index >> 2)
-__device__ __forceinline__ void drop_words(const DropRng &g, unsigned long long blk, uint32_t out[4]) {
-    philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), g.step, g.site, g.k0, g.k1, out);
-}
-__device__ __forceinline__ bool drop_keeps(const DropRng &g, uint32_t word) { return (float)(word >> 8) * 0x1p-24f >= g.drop_prob; }
-__device__ __forceinline__ float drop_value(const DropRng &g, float y, bool keep) { return keep ? __fmul_rn(y, g.scale) : 0.f; }
 
 // fp32: y[i] = dropout of x[i] (y may be x), element i has index first + i; keep / tape: optional.  VEC: first % 4 == 0 and every
 // buffer on its vector grid (16 bytes; 4 for keep).
@@ -193,15 +167,6 @@ __global__ __launch_bounds__(DROP_BLOCK) void dropout_h16_kernel(uint16_t *hi, u
 }
 
 bool aligned_to(const void *p, unsigned a) { return p == nullptr || ((uintptr_t)p & (a - 1)) == 0; }
-
-DropRng drop_rng(float drop_prob, unsigned long long seed, unsigned step, unsigned site) {
-    DropRng g;
-    g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32);
-    g.step = step; g.site = site;
-    g.drop_prob = drop_prob;
-    g.scale = 1.0f / (1.0f - drop_prob);
-    return g;
-}
 
 int drop_grid(long long n, int per, unsigned *blocks) {
     const long long b = ((n + per - 1) / per + DROP_BLOCK - 1) / DROP_BLOCK;

@@ -152,6 +152,15 @@ _SIGNATURES = {
     "wsc_cls_grad_destroy": (None, [_vp]),
     "wsc_cls_grad_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_net_backward_cls": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong]),
+    "wsc_batch_norm_train_drop_nhwc": (_i, [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _f, ctypes.c_ulonglong,
+                                            ctypes.c_longlong, _i]),
+    "wsc_batch_norm_grad_drop_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _f, ctypes.c_ulonglong,
+                                           ctypes.c_longlong, _i]),
+    "wsc_net_cls_feat_dims": (_i, [_vp, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "wsc_net_forward_cls_train_drop": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _f,
+                                            ctypes.c_ulonglong, ctypes.c_longlong]),
+    "wsc_net_backward_cls_drop": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _f,
+                                       ctypes.c_ulonglong, ctypes.c_longlong]),
     "wsc_cls_param_layout": (_i, [_vp, ctypes.POINTER(GradEntry), _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_longlong)]),
     "wsc_cls_sgd_step": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _f, _f, _i]),
     "wsc_net_cls_load_params": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _vp]),
@@ -783,6 +792,23 @@ class Net:
         check(self.ctx._lib.wsc_net_forward_cls_train(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(keep), int(bool(unbiased)),
                                                       _ptr(run_dev), _ptr(tape_dev), int(tape_elems), _ptr(feat_dev)))
 
+    def cls_feat_dims(self, H, W, dropping=False):
+        """wsc_net_cls_feat_dims: (h, w) of the map forward_cls_train[_drop] writes and ClsLoss reduces for an H x W input; with
+        `dropping` (drop_prob > 0) an M7 net's is the pooled, dropped layer3_p2 map."""
+        h, w = _i(), _i()
+        check(self.ctx._lib.wsc_net_cls_feat_dims(self.h, int(H), int(W), int(bool(dropping)), ctypes.byref(h), ctypes.byref(w)))
+        return h.value, w.value
+
+    def forward_cls_train_drop(self, x_dev, B, H, W, tape_dev, tape_elems, feat_dev, feat_elems, drop_prob, seed, step, keep=0.99,
+                               unbiased=True, run_dev=None, ctx=None):
+        """wsc_net_forward_cls_train_drop: forward_cls_train with the dropout sites active -- keep-masks of (seed, step, site,
+        element index); feat_dev holds feat_elems = B h w F floats, (h, w) = cls_feat_dims(H, W, drop_prob > 0).  At drop_prob = 0
+        the launches and bits of forward_cls_train."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_forward_cls_train_drop(run.h, self.h, _ptr(x_dev), int(B), int(H), int(W), float(keep), int(bool(unbiased)),
+                                                           _ptr(run_dev), _ptr(tape_dev), int(tape_elems), _ptr(feat_dev), int(feat_elems),
+                                                           float(drop_prob), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step)))
+
     def trace_plan(self, N, H, W, ctx=None):
         """wsc_net_trace_plan: one dict per op of the stack for an N x H x W input (+ the CAM head), the fields of wsc_trace_op
         (`in` under its own name, the label as str).  Follows the options of `ctx` (the fused stem)."""
@@ -959,6 +985,14 @@ class ClsGrad(_Grad):
         check(self.ctx._lib.wsc_net_backward_cls(run.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfeat_dev),
                                                  _ptr(grad_dev), self._elems(grad_elems)))
 
+    def backward_drop(self, B, H, W, tape_dev, tape_elems, dfeat_dev, dfeat_elems, grad_dev, drop_prob, seed, step, grad_elems=None, ctx=None):
+        """wsc_net_backward_cls_drop: backward() on a tape of Net.forward_cls_train_drop -- WITH THAT PASS'S (drop_prob, seed, step);
+        dfeat_dev holds dfeat_elems floats, the shape of that pass's feat."""
+        run = ctx or self.ctx
+        check(self.ctx._lib.wsc_net_backward_cls_drop(run.h, self.h, int(B), int(H), int(W), _ptr(tape_dev), int(tape_elems), _ptr(dfeat_dev),
+                                                      _ptr(grad_dev), self._elems(grad_elems), int(dfeat_elems), float(drop_prob),
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(step)))
+
     # ---- the update half: the training layout (wsc_cls_param_layout), the Nesterov step, the repack -------------------------------
     def _param_query(self):
         if getattr(self, "_param_layout", None) is None:
@@ -1028,6 +1062,21 @@ def batch_norm_grad_nhwc(ctx, a_dev, stats_dev, gamma_dev, dy_dev, M, C, da_dev,
     """wsc_batch_norm_grad_nhwc: da_dev [M][C], dgamma_dev [C], dbeta_dev [C] from the input, the taped statistics and dy_dev."""
     check(ctx._lib.wsc_batch_norm_grad_nhwc(ctx.h, _ptr(a_dev), _ptr(stats_dev), _ptr(gamma_dev), _ptr(dy_dev), int(M), int(C), _ptr(da_dev),
                                             _ptr(dgamma_dev), _ptr(dbeta_dev)))
+
+
+def batch_norm_train_drop_nhwc(ctx, a_dev, M, C, gamma_dev, beta_dev, eps, keep, unbiased, run_dev, stats_dev, y_dev, drop_prob, seed, step,
+                               site):
+    """wsc_batch_norm_train_drop_nhwc: batch_norm_train_nhwc with y_dev the dropped, scaled output (keep-mask of (seed, step, site))."""
+    check(ctx._lib.wsc_batch_norm_train_drop_nhwc(ctx.h, _ptr(a_dev), int(M), int(C), _ptr(gamma_dev), _ptr(beta_dev), float(eps), float(keep),
+                                                  int(bool(unbiased)), _ptr(run_dev), _ptr(stats_dev), _ptr(y_dev), float(drop_prob),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(site)))
+
+
+def batch_norm_grad_drop_nhwc(ctx, a_dev, stats_dev, gamma_dev, dy_dev, M, C, da_dev, dgamma_dev, dbeta_dev, drop_prob, seed, step, site):
+    """wsc_batch_norm_grad_drop_nhwc: batch_norm_grad_nhwc with dy_dev the gradient BEHIND the dropout (the mask is regenerated)."""
+    check(ctx._lib.wsc_batch_norm_grad_drop_nhwc(ctx.h, _ptr(a_dev), _ptr(stats_dev), _ptr(gamma_dev), _ptr(dy_dev), int(M), int(C),
+                                                 _ptr(da_dev), _ptr(dgamma_dev), _ptr(dbeta_dev), float(drop_prob),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(site)))
 
 
 def pool_tf_grad_nhwc(ctx, x_dev, dy_dev, N, H, W, C, k, stride, same, dx_dev):

@@ -13,11 +13,13 @@
     ClsGrads         the gradient of every conv / BatchNorm parameter of the stack on the device: a flat buffer, its layout,
                      name -> DeviceMaps views, to_state_dict() in torch's shapes
     grad_step        one call from a batch to every gradient of a step: net.forward_train_dev (conv -> ReLU -> BatchNorm on the batch
-                     statistics, wsc_net_forward_cls_train), the loss head, net.backward_dev (wsc_net_backward_cls)
+                     statistics, wsc_net_forward_cls_train), the loss head, net.backward_dev (wsc_net_backward_cls); with
+                     dropout=(drop_prob, seed, step) the `D` sites of the stacks are active (the *_drop entry points)
 
     ClsTrainer       one training step after another on the device: grad_step's three passes into one resident gradient buffer, Keras'
                      SGD with Nesterov momentum (wsc_cls_sgd_step, demo.py:60) and the repack of the updated parameters into the
-                     net (wsc_net_cls_load_params); save / load with the momentum, bit-exact resume
+                     net (wsc_net_cls_load_params); drop_prob / seed: dropout at (drop_prob, seed, global_step); save / load
+                     with the momentum and the dropout settings, bit-exact resume
     step_lr          the schedule of demo.py:112-113;  cyclic_lr / cyclic_session_rates: the triangular policy of demo.py:95-110
     fit              an iterable of batches through a trainer -> the per-epoch means fit_generator(verbose=2) prints
 
@@ -29,9 +31,11 @@
     train            the loop of demo.py:21-127 from files to checkpoints: schedule, ClsTrainer.step per batch, validation per
                      epoch, <ckpt_dir>/<sess_id>-<epoch>.npy every lr_dropstep epochs, resume, <model_dir>/<sess_id>.npy
 
-Not here: the `D` dropout entries of VGG16's layer5 (the identity here), the writing of .h5 files and
-TensorBoard.  Keras evaluates the loss in float32, and what it does with the LIST class_weight of demo.py:80-82,107 is not
-reproduced: ClsLoss takes per-sample weights, and train passes none (sample_weight=None)."""
+Dropout (the `D` entries of VGG16's layer5 and of M7's classifier branch, nn.Dropout(p=0.5)): the project's own counter-based
+keep-masks, not Keras' random stream; off (drop_prob = 0.0) unless asked for.
+Not here: the writing of .h5 files and TensorBoard.  Keras evaluates the loss in float32, and what it does
+with the LIST class_weight of demo.py:80-82,107 is not reproduced: ClsLoss takes per-sample weights, and train passes none
+(sample_weight=None)."""
 import collections
 import os
 
@@ -127,11 +131,13 @@ class ClsLoss:
 
 class ClsTape(Freed):
     """The tape of CAM.forward_train_dev(x, keep=True): `maps` one float32 DeviceMaps of `elems` floats, `entries` the plan of
-    Net.cls_tape_plan for a (B, 3, H, W) input.  entry(name) downloads one tensor ([B][Ho][Wo][C]; a ".stats" entry (C, 2));
-    free() / a context manager releases the buffer."""
+    Net.cls_tape_plan for a (B, 3, H, W) input, `dropout` None or the (drop_prob, seed, step) of the pass that wrote it (what
+    backward_dev regenerates the keep-masks from: the tape itself holds no mask).  entry(name) downloads one tensor
+    ([B][Ho][Wo][C]; a ".stats" entry (C, 2)); free() / a context manager releases the buffer."""
 
-    def __init__(self, maps, entries, B, H, W):
+    def __init__(self, maps, entries, B, H, W, dropout=None):
         self.maps, self.entries, self.B, self.H, self.W = maps, entries, int(B), int(H), int(W)
+        self.dropout = None if dropout is None else (float(dropout[0]), int(dropout[1]), int(dropout[2]))
         self.elems = maps.shape[0]
 
     def entry(self, name):
@@ -205,18 +211,20 @@ class ClsGrads(Freed):
         return out
 
 
-def grad_step(net, loss, x, targets, sample_weight=None):
+def grad_step(net, loss, x, targets, sample_weight=None, dropout=None):
     """One training step of 01_train up to the gradient of every parameter.
       net      a net.vgg16_cam.CAM / net.m7_cam.CAM with its state dict loaded; loss: a ClsLoss on the net's context whose pool is
                the net's head ("mean" VGG16, "max" M7)
       x        (B, 3, H, W) float32, a host array or a DeviceMaps of that context; targets (B, C) 0/1; sample_weight host (B,) or None
     -> (the metrics dict of ClsLoss, HeadGrads(feat, w, bias), ClsGrads): forward_train_dev on the batch statistics (the net's
     running statistics are updated with Keras' momentum 0.99), the loss head on the classifier's Linear of the state dict, and
-    backward_dev.  The caller frees the two gradient objects.  The call downloads the six loss values and nothing else."""
+    backward_dev.  The caller frees the two gradient objects.  The call downloads the six loss values and nothing else.
+      dropout  None, or (drop_prob, seed, step): forward_train_dev's -- the dropout sites active in both passes; HeadGrads.feat
+               then has the shape of the map the loss reduced (M7: the pooled, dropped layer3_p2 map)"""
     if net.ctx is not loss.ctx:
         raise ValueError("grad_step: the network lives on another context than the loss")
     w, bias = net.classifier_params(loss.C)
-    feat, tape = net.forward_train_dev(x, keep=True)
+    feat, tape = net.forward_train_dev(x, keep=True, dropout=dropout)
     head = None
     try:
         metrics, head = loss.grad_step(feat, w, bias, targets, sample_weight)
@@ -424,10 +432,13 @@ def cyclic_session_rates(session, base_lr, max_lr, droprate=0.5):
 class ClsTrainer:
     """One 01_train step after another on the device: compile(SGD(momentum, nesterov)) + train_on_batch of demo.py:60-61.
 
-        ClsTrainer(model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99)
+        ClsTrainer(model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99, drop_prob=0.0, seed=0)
           model      a net.vgg16_cam.CAM / net.m7_cam.CAM with its state dict loaded; the trainer trains ITS net in place
           pool       "mean" (VGG16's head) / "max" (M7's), ClsLoss's
           bn_keep    forward_train_dev's: the weight of the old running statistics (Keras' momentum 0.99)
+          drop_prob, seed   > 0: step k (global_step before the step) runs forward_train_dev(dropout=(drop_prob, seed, k)) -- the
+                     `D` sites of the stack under the counter-based keep-masks; the reference's models are 0.5.  0.0: no dropout,
+                     the launches and bits of a trainer without the keywords
     Parameters and momentum are two resident float32 DeviceMaps of cls_grad().param_elems floats in its param_layout, initialised
     from the model's state dict and zeros; `grads` is ONE reusable gradient buffer of the same layout.  A step never downloads them.
 
@@ -446,11 +457,13 @@ class ClsTrainer:
                     head is no parameter: it is the alpha the model had when the trainer was made, and travels in the dict as
                     `gradcam_weights` (drop the key to have a fresh model derive alpha from the trained weights).
     save(path) / ClsTrainer.load(path, model, pool, num_classes, ...)   np.save / np.load(...).item() of state_dict() with the
-                    momentum under "__momentum__" and the step count under "__step__"; a resumed run continues bit for bit.
+                    momentum under "__momentum__" and the step count under "__step__" -- with dropout on, `seed` and
+                    `drop_prob` beside it; a resumed run continues bit for bit, dropout masks included.  load restores seed
+                    and drop_prob from the file (a file without them: 0) unless the keyword is given, which wins.
                     save(path, extra={"__name__": value}) stores more keys of that form; load leaves them in `loaded_extra`
     close() / a context manager releases the three buffers (the model stays the caller's)"""
 
-    def __init__(self, model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99, ctx=None):
+    def __init__(self, model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99, ctx=None, drop_prob=0.0, seed=0):
         self.params = self.mom = self.grads = None
         self.model = model
         self.ctx = model.ctx
@@ -460,6 +473,9 @@ class ClsTrainer:
         self.momentum, self.nesterov, self.bn_keep = float(momentum), bool(nesterov), bn_keep
         if not 0.0 <= self.momentum < 1.0:
             raise ValueError("ClsTrainer: momentum = %r (0 <= momentum < 1)" % (momentum,))
+        self.drop_prob, self.seed = float(drop_prob), int(seed)
+        if not 0.0 <= self.drop_prob < 1.0:  # (NaN fails both)
+            raise ValueError("ClsTrainer: drop_prob = %r (0 <= drop_prob < 1)" % (drop_prob,))
         self.global_step = 0
         self.loaded_extra = {}  # (ClsTrainer.load: the file's own "__name__" keys)
         extra = model._extra_tensors(model._sd)
@@ -514,7 +530,8 @@ class ClsTrainer:
         if not np.isfinite(lr) or lr < 0:
             raise ValueError("ClsTrainer.step: lr = %r" % (lr,))
         model, grad = self.model, self.grad
-        feat, tape = model.forward_train_dev(x, keep=True, bn_keep=self.bn_keep)
+        dropout = (self.drop_prob, self.seed, self.global_step) if self.drop_prob > 0.0 else None
+        feat, tape = model.forward_train_dev(x, keep=True, bn_keep=self.bn_keep, dropout=dropout)
         head = None
         try:
             w, bias = self._tail_views(self.params)
@@ -527,7 +544,11 @@ class ClsTrainer:
                                          "precision's range, entered the net): no update") from e
             if not np.isfinite(metrics["loss"]):
                 raise FloatingPointError("ClsTrainer.step: the loss is %r: no update" % (metrics["loss"],))
-            grad.backward(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, head.feat.ptr, self.grads.ptr)
+            if dropout is None:
+                grad.backward(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, head.feat.ptr, self.grads.ptr)
+            else:
+                grad.backward_drop(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, head.feat.ptr, int(np.prod(head.feat.shape)),
+                                   self.grads.ptr, *dropout)
             grad.sgd_step(self.params.ptr, self.grads.ptr, self.mom.ptr, lr, self.momentum, self.nesterov)
             model.load_params_dev(self.params)
             self.global_step += 1
@@ -570,6 +591,8 @@ class ClsTrainer:
         d = self.state_dict()
         d["__momentum__"] = self.momentum_host()
         d["__step__"] = {"global_step": self.global_step}
+        if self.drop_prob > 0.0:  # (a trainer without dropout writes the file it always wrote)
+            d["__step__"].update(seed=self.seed, drop_prob=self.drop_prob)
         for k, v in (extra or {}).items():
             if not k.startswith("__") or k in d:
                 raise ValueError("ClsTrainer.save: extra key %r (a new name beginning with '__')" % (k,))
@@ -582,6 +605,8 @@ class ClsTrainer:
         d = np.load(path, encoding="latin1", allow_pickle=True).item()
         model.load_state_dict({k: v for k, v in d.items() if not k.startswith("__")})
         model.cuda()
+        for key, default in (("drop_prob", 0.0), ("seed", 0)):  # (the file's unless the caller says otherwise)
+            kwargs.setdefault(key, d.get("__step__", {}).get(key, default))
         tr = cls(model, pool, num_classes, **kwargs)
         try:
             if "__momentum__" in d:
@@ -942,7 +967,7 @@ def _validate(model, trainer, batcher):
 
 def train(paths, labels, val_paths, val_labels, model, pool, sess_id, model_dir, ckpt_dir, epochs, batch_size, should_clr=False, seed=0,
           size=321, augmenter="VOC2012", val_augmenter=None, base_lr=1e-3, lr_dropstep=20, lr_droprate=0.5, momentum=0.9,
-          clr_base_lr=1e-3, clr_max_lr=2e-2, clr_spc=4):
+          clr_base_lr=1e-3, clr_max_lr=2e-2, clr_spc=4, drop_prob=0.0):
     """train() of 01_train/demo.py:21-127 from image files to checkpoints, on the device.
 
       paths, labels / val_paths, val_labels   the image files and (n, C) 0/1 label arrays of the two splits (gen_train, gen_val)
@@ -950,6 +975,11 @@ def train(paths, labels, val_paths, val_labels, model, pool, sess_id, model_dir,
       augmenter       an ImageAugmenter or a dataset name for ImageAugmenter.for_dataset(name, train=True); val_augmenter: the
                       same for the validation split (default: the non-augmenting generator of that dataset)
       size            img_size of demo.py:29-32 (321 VGG16, 224 the M nets)
+      drop_prob       ClsTrainer's, with `seed` (the batcher's seed as well) as the masks' seed: THE REFERENCE'S MODELS ARE 0.5
+                      (nn.Dropout(p=0.5), common_cnn.py:133-134); the default 0.0 leaves dropout off, the launches and bits of a
+                      call without the keyword (nothing is passed to the trainer: a run resumed from a checkpoint continues with
+                      the checkpoint's own drop_prob and seed).  A resumed run continues with the checkpoint's step counter, so
+                      its masks are those of the uninterrupted run.  Validation is the inference feature pass: never dropped.
     steps_per_epoch = n // batch_size batches of ONE endless ClsBatcher(shuffle=True, seed) per epoch, as fit_generator draws them
     (the short last batch of a pass opens the next epoch); every batch through ClsTrainer.step(x, labels, rate, None) at
     train_schedule's rate; after every epoch _validate on the WHOLE validation split in file order (the reference's
@@ -959,7 +989,8 @@ def train(paths, labels, val_paths, val_labels, model, pool, sess_id, model_dir,
     -> one dict per epoch run: {'epoch' (from 1), 'lr' (the last batch's), 'loss', 'binary_accuracy', 'f1', 'val_loss',
     'val_binary_accuracy', 'val_f1', 'steps', 'samples'}.
     Not mirrored: validation_steps = n // batch_size (the whole split is validated, see above), class_weight
-    (sample_weight=None), layer5's dropout, the .h5 / .hdf5 formats, the .json architecture file, TensorBoard."""
+    (sample_weight=None), Keras' random stream behind the dropout masks, the .h5 / .hdf5 formats, the .json architecture file,
+    TensorBoard."""
     labels = np.ascontiguousarray(labels, dtype=np.float32)
     n, C = labels.shape
     epochs, batch_size, lr_dropstep = int(epochs), int(batch_size), int(lr_dropstep)
@@ -974,13 +1005,14 @@ def train(paths, labels, val_paths, val_labels, model, pool, sess_id, model_dir,
         raise ValueError("train: an ImageAugmenter for the training split needs a val_augmenter")
     for d in (model_dir, ckpt_dir):
         os.makedirs(d, exist_ok=True)
+    drop = {"drop_prob": drop_prob, "seed": 0 if seed is None else seed} if drop_prob else {}  # (0.0: the trainer's own defaults)
     rate = train_schedule(n, batch_size, should_clr, base_lr, lr_dropstep, lr_droprate, clr_base_lr, clr_max_lr, clr_spc)
     latest, latest_epoch = find_latest_checkpoint(ckpt_dir, sess_id)
     if latest is not None:
-        trainer = ClsTrainer.load(latest, model, pool, C, momentum=momentum, nesterov=True)
+        trainer = ClsTrainer.load(latest, model, pool, C, momentum=momentum, nesterov=True, **drop)
     else:
         model.cuda()
-        trainer = ClsTrainer(model, pool, C, momentum=momentum, nesterov=True)
+        trainer = ClsTrainer(model, pool, C, momentum=momentum, nesterov=True, **drop)
     history = []
     try:
         gen = ClsBatcher(paths, labels, augmenter, size, batch_size, True, seed, ctx=trainer.ctx)

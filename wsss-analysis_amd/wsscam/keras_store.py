@@ -227,6 +227,39 @@ def read_architecture(path, model_type):
     return normalize_pooling(pooling), bool(has_bn)
 
 
+def read_dropout(path, model_type):
+    """The `rate` of the Dropout layers of a session's architecture file (the format read_architecture takes) -> a float, or None
+    if the file has no Dropout layer (such a session was trained without).  The model type's table has net.common.DROP_SITES of
+    them (VGG16: two in layer5; M7: one behind layer3_p2) and nn.Dropout(p=0.5) at each; any other count, or sites whose rates
+    disagree, raise ValueError with the layer's index: ClsTrainer has ONE drop_prob for all sites.  The value is what
+    cls_train.train(drop_prob=...) takes; the masks are the project's own, not Keras' stream."""
+    import json
+
+    from .net.common import DROP_SITES
+
+    root = "vgg16" if "VGG16" in model_type else "m7"
+    with open(path) as f:
+        doc = json.load(f)
+    cfg = doc.get("config") if isinstance(doc, dict) else None
+    if isinstance(cfg, dict):
+        cfg = cfg.get("layers")
+    if not isinstance(cfg, list):
+        raise ValueError("%s: no layer list under 'config'" % path)
+    found = [(i, (l.get("config") or {}).get("rate")) for i, l in enumerate(cfg) if l.get("class_name") == "Dropout"]
+    if not found:
+        return None
+    if len(found) != DROP_SITES[root]:
+        i = found[min(len(found), DROP_SITES[root] + 1) - 1][0]
+        raise ValueError("%s: layer %d: %d Dropout layers, a %s model has %d" % (path, i, len(found), model_type, DROP_SITES[root]))
+    for i, rate in found:
+        if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= rate < 1.0:
+            raise ValueError("%s: layer %d: Dropout rate %r (0 <= rate < 1)" % (path, i, rate))
+        if float(rate) != float(found[0][1]):
+            raise ValueError("%s: layer %d: Dropout rate %r, layer %d has %r -- one rate for every site is supported"
+                             % (path, i, rate, found[0][0], found[0][1]))
+    return float(found[0][1])
+
+
 def load_model(model_dir, sess_id, model_type, dataset, device=0, precision=None):
     """02_cues/demo.py:104-124 / 03c_hsn/utilities.py build_model + load_thresholds + get_grad_cam_weights:
     (device CAM wrapper with the session's weights, alpha (F, C), final layer name, thresholds (1, C))."""

@@ -189,6 +189,9 @@ PLAIN_CFG = {
               ("layer4", [512, 512, 512, 512, 512, 512]), ("layer5", [1024, "D", 1024, "D"])],
     "m7": [("layer1", [64, 64, "M"]), ("layer2", [128, 128, "M"]), ("layer3_p1", [256, 256, 256])],
 }
+# the dropout sites of a training pass, numbered by the order of the 'D' entries: VGG16's two of layer5 above; M7's one lies in
+# the classifier branch, ("layer3_p2", ["M", "D"]) of net/m7.py:41, which -- like that branch's pool -- is no part of the stack
+DROP_SITES = {"vgg16": sum(v == "D" for _, layer in PLAIN_CFG["vgg16"] for v in layer), "m7": 1}
 
 
 def plain_module_order(root, batchnorm):

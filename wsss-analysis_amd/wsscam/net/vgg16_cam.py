@@ -115,11 +115,16 @@ class CAM(DeviceCAMBase):
             self._cls_grad = _lib.ClsGrad(net, self._extra_tensors(self._sd))
         return self._cls_grad
 
-    def forward_train_dev(self, x, keep=True, bn_keep=0.99):
-        """The stack in training mode (make_layers' conv -> ReLU -> BatchNorm on the BATCH statistics; the `D` entries of layer5
-        are the identity): x float32 (B, 3, H, W), a host array / tensor or a secdsrg.DeviceMaps of the model's context (read in
-        place) -> (feat DeviceMaps (B, h, w, F), the map ClsLoss reads, tape): the cls_train.ClsTape backward_dev needs; the caller
-        frees both.  keep=False: feat alone.
+    def forward_train_dev(self, x, keep=True, bn_keep=0.99, dropout=None):
+        """The stack in training mode (make_layers' conv -> ReLU -> BatchNorm on the BATCH statistics): x float32 (B, 3, H, W), a
+        host array / tensor or a secdsrg.DeviceMaps of the model's context (read in place) -> (feat DeviceMaps (B, h, w, F), the
+        map ClsLoss reads, tape): the cls_train.ClsTape backward_dev needs; the caller frees both.  keep=False: feat alone.
+        dropout: None (the `D` entries of the table are the identity: wsc_net_forward_cls_train), or (drop_prob, seed, step) --
+        the shape SegNet.forward_dev takes -- for wsc_net_forward_cls_train_drop: the sites active under the project's own
+        counter-based keep-masks of (seed, step, site, element index) (not Keras' random stream).  VGG16:
+        behind both entries of layer5; feat is the dropped output of the second.  M7: behind layer3_p2, and feat is then the
+        POOLED, dropped map (B, hp, wp, F) whose global max ClsLoss takes.  The reference's models use 0.5.  The tape records the
+        triple for backward_dev; needs keep=True.
         bn_keep: the weight of the OLD running value in the update of the running statistics (bn_running_dev), Keras' `momentum`:
         BatchNormalization(momentum=0.99) is 0.99.  torch's nn.BatchNorm2d(momentum=m) weighs the NEW value with m, so the torch
         port's BatchNorm2d(v, eps=0.001, momentum=0.99) is bn_keep = 0.01.  The batch variance enters unbiased (M / (M - 1)), as
@@ -127,6 +132,8 @@ class CAM(DeviceCAMBase):
         from ..cls_train import ClsTape
         from ..secdsrg import DeviceMaps
 
+        if dropout is not None and not keep:
+            raise ValueError("forward_train_dev: dropout=%r needs keep=True (the backward pass needs the triple the tape records)" % (dropout,))
         net = self._ensure_net()
         ctx = self._ctx
         mine = None
@@ -145,13 +152,20 @@ class CAM(DeviceCAMBase):
             if bn_keep is not None and not 0.0 <= float(bn_keep) <= 1.0:
                 raise ValueError("forward_train_dev: bn_keep = %r (the weight of the old running value, 0 .. 1)" % (bn_keep,))
             B, H, W = xd.shape[0], xd.shape[2], xd.shape[3]
-            h, w = net.cam_size_hw(H, W)
+            if dropout is not None:
+                drop_prob, seed, step = float(dropout[0]), int(dropout[1]), int(dropout[2])
+            h, w = net.cam_size_hw(H, W) if dropout is None else net.cls_feat_dims(H, W, drop_prob > 0)
             run = None if bn_keep is None else self.bn_running_dev()
             entries, elems = net.cls_tape_plan(B, H, W)
             feat = DeviceMaps(ctx, (B, h, w, net.feat_channels()), np.float32)
-            tape = ClsTape(DeviceMaps(ctx, (elems,), np.float32), entries, B, H, W)
-            net.forward_cls_train(xd.ptr, B, H, W, tape.maps.ptr, elems, feat.ptr, keep=0.0 if bn_keep is None else bn_keep,
-                                  run_dev=None if run is None else run.ptr)
+            tape = ClsTape(DeviceMaps(ctx, (elems,), np.float32), entries, B, H, W,
+                           None if dropout is None else (drop_prob, seed, step))
+            if dropout is None:
+                net.forward_cls_train(xd.ptr, B, H, W, tape.maps.ptr, elems, feat.ptr, keep=0.0 if bn_keep is None else bn_keep,
+                                      run_dev=None if run is None else run.ptr)
+            else:
+                net.forward_cls_train_drop(xd.ptr, B, H, W, tape.maps.ptr, elems, feat.ptr, B * h * w * net.feat_channels(), drop_prob,
+                                           seed, step, keep=0.0 if bn_keep is None else bn_keep, run_dev=None if run is None else run.ptr)
             if keep:
                 return feat, tape
             tape.free()
@@ -168,7 +182,9 @@ class CAM(DeviceCAMBase):
     def backward_dev(self, tape, dfeat):
         """The backward pass of the stack (wsc_net_backward_cls): the tape of forward_train_dev and d loss / d feat (B, h, w, F) or
         (B, h w, F) float32, a DeviceMaps of the model's context (HeadGrads.feat of ClsLoss.grad_step), read in place ->
-        cls_train.ClsGrads (the caller frees it).  The chain rule evaluated at the tape, in exact fp32 whatever the net's precision."""
+        cls_train.ClsGrads (the caller frees it).  The chain rule evaluated at the tape, in exact fp32 whatever the net's precision.
+        A tape of forward_train_dev(dropout=(drop_prob, seed, step)) carries the triple: wsc_net_backward_cls_drop regenerates
+        the masks from it, and dfeat has the shape of that pass's feat (M7: the pooled (B, hp, wp, F))."""
         from ..cls_train import ClsGrads, ClsTape
         from ..secdsrg import DeviceMaps
 
@@ -178,14 +194,18 @@ class CAM(DeviceCAMBase):
             raise ValueError("backward_dev: tape is no live ClsTape of the model's context")
         if not isinstance(dfeat, DeviceMaps) or dfeat.dtype != np.float32 or dfeat.ctx is not ctx or dfeat.ptr is None:
             raise ValueError("backward_dev: dfeat is no live float32 DeviceMaps of the model's context")
-        h, w = net.cam_size_hw(tape.H, tape.W)
+        drop = getattr(tape, "dropout", None)
+        h, w = net.cam_size_hw(tape.H, tape.W) if drop is None else net.cls_feat_dims(tape.H, tape.W, drop[0] > 0)
         F = net.feat_channels()
         if tuple(dfeat.shape) not in ((tape.B, h, w, F), (tape.B, h * w, F)):
             raise ValueError("backward_dev: dfeat has shape %r, expected %r" % (tuple(dfeat.shape), (tape.B, h, w, F)))
         grad = self.cls_grad()
         out = DeviceMaps(ctx, (grad.grad_elems,), np.float32)
         try:
-            grad.backward(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, dfeat.ptr, out.ptr)
+            if drop is None:
+                grad.backward(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, dfeat.ptr, out.ptr)
+            else:
+                grad.backward_drop(tape.B, tape.H, tape.W, tape.maps.ptr, tape.elems, dfeat.ptr, tape.B * h * w * F, out.ptr, *drop)
         except Exception:
             out.free()
             raise
