@@ -349,8 +349,6 @@ __global__ __launch_bounds__(256) void bn_grad_apply_kernel(const float *__restr
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 int bn_shape_check(const char *who, long long M, int C) {
     WSC_CHECK(M >= 1 && M < (1ll << 31) && C >= 4 && C % 4 == 0 && C <= BN_MAX_C, WSC_ERR_INVALID,
               "%s: %lld x %d (1 <= M < 2^31, C a multiple of 4 up to %d)", who, M, C, BN_MAX_C);

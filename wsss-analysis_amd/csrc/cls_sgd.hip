@@ -82,8 +82,6 @@ __global__ __launch_bounds__(256) void transpose_cf_kernel(const float *__restri
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 } // namespace
 
 int cls_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, float lr, float momentum, int nesterov) {

@@ -585,6 +585,9 @@ void dgrad_pack(const float *w_hwio, int k, int Cin, int Cout, std::vector<float
 int dgrad_launch(wsc_ctx *ctx, const float *dz, const float *w_packed, const float *ones, const float *zeros, int N, int H, int W, int Cin,
                  int Cout, int k, int dil, const float *sum_with, float *dx);
 
+// whether a launch may take the 16-byte forms of its loads and stores on `p`
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
 // ---- seg_sgd.hip: the SGD-momentum step on the flat parameter layout of wsc_seg_grad_layout, and the device repack --------------
 // One run of floats of that layout with one learning-rate multiplier: a layer's w (decay = 1: the weight-decay term applies and
 // the floats count into loss["l2"]) or its b.  The table has a segment per run in offset order; the kernels find an element's

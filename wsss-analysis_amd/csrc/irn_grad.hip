@@ -238,8 +238,6 @@ __global__ __launch_bounds__(256) void dp_to_nhwc_kernel(const float *__restrict
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 int check_up_grad(const char *fn, int N, int H, int W, int C, int up, int Hd, int Wd, int Ctot, int coff) {
     WSC_CHECK(N > 0 && H > 0 && W > 0 && C > 0, WSC_ERR_INVALID, "%s: %d x %d x %d x %d", fn, N, H, W, C);
     WSC_CHECK(up == 1 || up == 2 || up == 4, WSC_ERR_INVALID, "%s: upsample factor %d (1, 2 or 4)", fn, up);

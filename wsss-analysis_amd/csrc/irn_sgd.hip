@@ -124,8 +124,6 @@ __global__ __launch_bounds__(ISGD_BLOCK) void channel_mean_kernel(ChannelMeanArg
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 } // namespace
 
 int irn_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, long long boundary, float lr_a, float lr_b,

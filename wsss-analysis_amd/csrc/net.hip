@@ -1736,7 +1736,8 @@ int wsc_net_forward_seg_train(wsc_ctx *ctx, const wsc_net *net, const float *x_d
 namespace {
 // What the gradient object of every training path owns: the context and the net it was made for, its device allocations, the ones
 // and zeros of the data-gradient GEMM, the backward workspace, the repack jobs of its load-params entry, the size of its flat
-// layout.  wsc_seg_grad and wsc_irn_grad derive from it and keep only what differs (embed it, do not copy it).
+// layout.  wsc_seg_grad, wsc_irn_grad and wsc_cls_grad derive from it and keep only what differs (embed it, do not
+// copy it).
 struct GradCore {
     const char *kind; // the C type's name, for the messages
     wsc_ctx *ctx;
@@ -1806,6 +1807,52 @@ struct GradCore {
         if (ws) (void)hipFree(ws);
     }
 };
+// A device table of jobs that each carry `block0`, their first block in one launch: add() hands a job its blocks, jobs in order,
+// ceil(n / per_block) each; upload() moves the table into an allocation of the gradient object and leaves dev / n / blocks, what
+// the launch takes.  A load-params entry builds one locally and assigns it to its object once it is uploaded.
+extern "C++" { // (a template, and functions that return C++ types, inside this file's extern "C")
+template <class Job> struct JobTable {
+    std::vector<Job> host;
+    Job *dev = nullptr;
+    int n = 0, blocks = 0;
+    void add(Job job, int elems, int per_block) {
+        job.block0 = blocks;
+        blocks += (elems + per_block - 1) / per_block;
+        host.push_back(job);
+    }
+    int upload(GradCore *g) {
+        n = (int)host.size();
+        if (n > 0) WSC_TRY(g->upload(host.data(), host.size() * sizeof(Job), (void **)&dev));
+        host = std::vector<Job>();
+        return WSC_OK;
+    }
+};
+// `n` floats at `off` of the parameter buffer that a repack copies to `dst` as they are
+void add_vec(JobTable<VecCopyJob> &vecs, long long off, int n, float *dst) { vecs.add({off, n, 0, dst}, n, VEC_COPY_PER_BLOCK); }
+// the ops of a net's trunk that are convs, in op order: the layers the *_grad_create functions list first and the load-params
+// entries rewrite
+std::vector<size_t> trunk_conv_ops(const wsc_net *net) {
+    std::vector<size_t> ops;
+    for (size_t i = 0; i < net->ops.size(); ++i)
+        if (net->ops[i].type == OP_CONV) ops.push_back(i);
+    return ops;
+}
+// whether the net's conv `c` is the layer [k][k][Cin][Cout] of a layout (the first layer's 3 channels lie in the small form's 4)
+bool conv_is_layer(const ConvW &c, int k, int Cin, int Cout) {
+    return c.kh == k && c.kw == k && c.Cout == Cout && (c.form == CONV_FORM_GENERIC ? c.Cin == Cin : (c.Cin == 4 && Cin <= 4));
+}
+// the RepackJob of the net's conv `c`: its tensor [k][k][Cin][Cout] at w_off of the parameter buffer, its bias at b_off (-1: none),
+// the data-gradient kernel it also rewrites (or null), cin_pad: the channels of its input where wider than the tensor
+RepackJob conv_repack_job(const ConvW &c, int k, int Cin, int Cout, long long w_off, long long b_off, float *w_rot, int cin_pad = 0) {
+    RepackJob J = RepackJob();
+    J.w_off = w_off; J.b_off = b_off;
+    J.k = k; J.Cin = Cin; J.Cout = Cout; J.Cin_pad = cin_pad;
+    J.small = c.form != CONV_FORM_GENERIC;
+    J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
+    J.w_rot = w_rot;
+    return J;
+}
+} // extern "C++"
 // the arguments every entry that takes a gradient object shares, checked before anything is launched (the workspace and the
 // optimiser's scratch are the object's: one stream uses them, the one release() drains)
 // (layout_elems: the size of the layout the entry's buffers are in where that is not the gradient layout -- wsc_cls_param_layout)
@@ -1886,11 +1933,10 @@ int wsc_seg_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
         g->layers.push_back(L);
         return WSC_OK;
     };
-    for (size_t i = 0; i < net->ops.size(); ++i) {
-        const Op &op = net->ops[i];
-        g->op_layer.push_back(op.type == OP_CONV ? (int)g->layers.size() : -1);
-        if (op.type != OP_CONV) continue;
-        const int st = add(op.label, net->convs[op.conv], i == 0);
+    g->op_layer.assign(net->ops.size(), -1);
+    for (size_t i : trunk_conv_ops(net)) {
+        g->op_layer[i] = (int)g->layers.size();
+        const int st = add(net->ops[i].label, net->convs[net->ops[i].conv], i == 0);
         if (st != WSC_OK) return fail(st);
     }
     for (size_t k = 0; k < net->seg.size(); ++k) {
@@ -2058,8 +2104,7 @@ struct wsc_irn_grad : GradCore {
     long long edge_w_off = 0, edge_b_off = 0, dp_w_off = 0;
     long long dp_start = 0; // the first float of the dp group (train_irn.py:86-90: 10 lr); the edge group lies before it
     float *edge_rot = nullptr, *dp_rot = nullptr;
-    VecCopyJob *vec_jobs = nullptr; // the GroupNorm vectors of wsc_net_irn_load_params, built with its repack jobs
-    int n_vec_jobs = 0, vec_blocks = 0;
+    JobTable<VecCopyJob> vecs; // the GroupNorm vectors of wsc_net_irn_load_params, built with its repack jobs
     std::vector<wsc_grad_entry> layout; // one entry per parameter, in the order of trainable_parameters()
 };
 
@@ -2266,46 +2311,30 @@ int wsc_net_irn_load_params(wsc_ctx *ctx, wsc_net *net, wsc_irn_grad *g, const f
               (int)g->heads.size());
     WSC_HIP(hipSetDevice(ctx->device));
     if (!g->repack.jobs_dev) { // the job tables: once per wsc_irn_grad (the packed buffers of both objects never move)
-        std::vector<RepackJob> jobs;
-        std::vector<VecCopyJob> vecs;
-        int vec_blocks = 0;
-        // a 1 x 1 layer [Cin][Cout] at w_off; bias: b_off or -1; cin_pad: the channels of its input where wider
-        auto job = [&](const ConvW &c, long long w_off, long long b_off, int Cin, int cin_pad, float *w_rot) {
-            RepackJob J = RepackJob();
-            J.w_off = w_off; J.b_off = b_off;
-            J.k = 1; J.Cin = Cin; J.Cout = c.Cout; J.Cin_pad = cin_pad;
-            J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
-            J.w_rot = w_rot;
-            jobs.push_back(J);
-        };
-        auto vec = [&](long long off, int n, float *dst) {
-            VecCopyJob V;
-            V.off = off; V.n = n; V.block0 = vec_blocks; V.dst = dst;
-            vec_blocks += (n + VEC_COPY_PER_BLOCK - 1) / VEC_COPY_PER_BLOCK;
-            vecs.push_back(V);
-        };
+        std::vector<RepackJob> jobs; // 1 x 1 layers [Cin][Cout]
+        JobTable<VecCopyJob> vecs;
         for (size_t j = 0; j < net->heads.size(); ++j) {
             const IrnHead &h = net->heads[j];
             const IrnGradHead &gh = g->heads[j];
             WSC_CHECK(h.conv.kh == 1 && h.conv.kw == 1 && h.conv.form == CONV_FORM_GENERIC && !h.conv.s2, WSC_ERR_INVALID,
                       "internal: head '%s' is no 1 x 1 layer", h.name.c_str());
-            job(h.conv, gh.w_off, -1, h.conv.Cin, 0, gh.w_rot);
-            vec(gh.g_off, h.conv.Cout, h.gamma);
-            vec(gh.b_off, h.conv.Cout, h.beta);
+            jobs.push_back(conv_repack_job(h.conv, 1, h.conv.Cin, h.conv.Cout, gh.w_off, -1, gh.w_rot));
+            add_vec(vecs, gh.g_off, h.conv.Cout, h.gamma);
+            add_vec(vecs, gh.b_off, h.conv.Cout, h.beta);
         }
         WSC_CHECK(net->edge6.Cin == net->cats[0].channels && net->edge6.Cout == 1 && net->dp7b.Cin == net->cats.back().channels &&
                       net->dp7b.Cout == 2,
                   WSC_ERR_INVALID, "internal: the final convs are not the layout's");
-        job(net->edge6, g->edge_w_off, g->edge_b_off, net->edge_in, net->edge6.Cin, g->edge_rot);
-        job(net->dp7b, g->dp_w_off, -1, net->dp7b.Cin, 0, g->dp_rot);
+        WSC_CHECK(net->edge6.form == CONV_FORM_GENERIC && net->dp7b.form == CONV_FORM_GENERIC, WSC_ERR_INVALID, "internal: a final conv in the small form");
+        jobs.push_back(conv_repack_job(net->edge6, 1, net->edge_in, 1, g->edge_w_off, g->edge_b_off, g->edge_rot, net->edge6.Cin));
+        jobs.push_back(conv_repack_job(net->dp7b, 1, net->dp7b.Cin, 2, g->dp_w_off, -1, g->dp_rot));
         // (the vec-copy table first: jobs_dev, what marks the tables as built, is set last)
-        WSC_TRY(g->upload(vecs.data(), vecs.size() * sizeof(VecCopyJob), (void **)&g->vec_jobs));
-        g->n_vec_jobs = (int)vecs.size();
-        g->vec_blocks = vec_blocks;
+        WSC_TRY(vecs.upload(g));
+        g->vecs = vecs;
         WSC_TRY(g->plan_repack(jobs));
     }
     WSC_TRY(repack_launch(ctx, g->repack, param_dev));
-    return vec_copy_launch(ctx, g->vec_jobs, g->n_vec_jobs, g->vec_blocks, param_dev);
+    return vec_copy_launch(ctx, g->vecs.dev, g->vecs.n, g->vecs.blocks, param_dev);
 }
 
 int wsc_channel_mean_nchw(wsc_ctx *ctx, const float *x_dev, int N, int C, int H, int W, const float *sub_host, double *out_dev) {
@@ -2360,8 +2389,7 @@ int wsc_net_seg_load_params(wsc_ctx *ctx, wsc_net *net, wsc_seg_grad *g, const f
     WSC_TRY(grad_check("wsc_net_seg_load_params", ctx, g, elems, true));
     // the layers in the order wsc_seg_grad_create listed them: the trunk's convs in op order, then fc6, fc7, fc8 of every branch
     std::vector<ConvW *> convs;
-    for (const Op &op : net->ops)
-        if (op.type == OP_CONV) convs.push_back(&net->convs[op.conv]);
+    for (size_t i : trunk_conv_ops(net)) convs.push_back(&net->convs[net->ops[i].conv]);
     for (SegBranch &br : net->seg) {
         convs.push_back(&br.fc6);
         convs.push_back(&br.fc7);
@@ -2372,23 +2400,15 @@ int wsc_net_seg_load_params(wsc_ctx *ctx, wsc_net *net, wsc_seg_grad *g, const f
     for (size_t i = 0; i < convs.size(); ++i) {
         const ConvW &c = *convs[i];
         const GradLayer &L = g->layers[i];
-        WSC_CHECK(c.kh == L.k && c.kw == L.k && c.Cout == L.Cout && (c.form == CONV_FORM_GENERIC ? c.Cin == L.Cin : (c.Cin == 4 && L.Cin <= 4)) &&
-                      !c.s2 && !c.b2,
-                  WSC_ERR_INVALID, "internal: layer '%s' of the layout is not the net's", L.name.c_str());
+        WSC_CHECK(conv_is_layer(c, L.k, L.Cin, L.Cout) && !c.s2 && !c.b2, WSC_ERR_INVALID, "internal: layer '%s' of the layout is not the net's",
+                  L.name.c_str());
     }
     WSC_HIP(hipSetDevice(ctx->device));
     if (!g->repack.jobs_dev) { // the job table: once per wsc_seg_grad (the packed buffers of both objects never move)
-        std::vector<RepackJob> jobs(convs.size());
+        std::vector<RepackJob> jobs;
         for (size_t i = 0; i < convs.size(); ++i) {
-            const ConvW &c = *convs[i];
             const GradLayer &L = g->layers[i];
-            RepackJob &J = jobs[i];
-            J = RepackJob();
-            J.w_off = L.w_off; J.b_off = L.b_off;
-            J.k = L.k; J.Cin = L.Cin; J.Cout = L.Cout;
-            J.small = c.form != CONV_FORM_GENERIC;
-            J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
-            J.w_rot = L.w_rot;
+            jobs.push_back(conv_repack_job(*convs[i], L.k, L.Cin, L.Cout, L.w_off, L.b_off, L.w_rot));
         }
         WSC_TRY(g->plan_repack(jobs));
     }
@@ -2705,10 +2725,8 @@ struct wsc_cls_grad : GradCore {
     long long param_elems = 0, cls_w_off = 0, cls_b_off = -1;
     // wsc_net_cls_load_params, built by its first call with the repack jobs: BatchNorm's gamma / beta and the classifier's fp32
     // copies (a vec-copy table), the inference folds, the CAM head (the transposed Linear in `head_t`, a repack plan of its own)
-    VecCopyJob *vec_jobs = nullptr;
-    int n_vec_jobs = 0, vec_blocks = 0;
-    BnFoldJob *fold_jobs = nullptr;
-    int n_fold_jobs = 0, fold_blocks = 0;
+    JobTable<VecCopyJob> vecs;
+    JobTable<BnFoldJob> folds;
     float *head_t = nullptr; // [F][C]
     RepackPlan head_repack;
 };
@@ -2753,10 +2771,10 @@ int wsc_cls_grad_create(wsc_ctx *ctx, const wsc_net *net, const wsc_tensor_desc 
     };
     int widest = 64;
     auto build = [&]() -> int {
-        for (size_t i = 0; i < net->ops.size(); ++i) {
+        g->op_layer.assign(net->ops.size(), -1);
+        for (size_t i : trunk_conv_ops(net)) {
             const Op &op = net->ops[i];
-            g->op_layer.push_back(op.type == OP_CONV ? (int)g->layers.size() : -1);
-            if (op.type != OP_CONV) continue;
+            g->op_layer[i] = (int)g->layers.size();
             const ConvW &c = net->convs[op.conv];
             WSC_CHECK(c.kh == 3 && c.kw == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 && c.relu, WSC_ERR_INVALID,
                       "internal: layer '%s' is no 3 x 3 stride-1 SAME convolution with a ReLU", op.label.c_str());
@@ -2960,79 +2978,53 @@ int wsc_net_cls_load_params(wsc_ctx *ctx, wsc_net *net, wsc_cls_grad *g, const f
               "%s: the net was built with `gradcam_weights`: its CAM head is not the classifier the parameters hold", fn);
     WSC_CHECK(((uintptr_t)param_dev & 3) == 0 && ((uintptr_t)run_dev & 3) == 0, WSC_ERR_INVALID, "%s: a buffer is not 4-byte aligned", fn);
     std::vector<ConvW *> convs;
-    for (const Op &op : net->ops)
-        if (op.type == OP_CONV) convs.push_back(&net->convs[op.conv]);
+    for (size_t i : trunk_conv_ops(net)) convs.push_back(&net->convs[net->ops[i].conv]);
     WSC_CHECK(convs.size() == g->layers.size(), WSC_ERR_INVALID, "internal: %d layers of the net, %d of the layout", (int)convs.size(),
               (int)g->layers.size());
     for (size_t i = 0; i < convs.size(); ++i) {
         const ConvW &c = *convs[i];
         const ClsGradLayer &L = g->layers[i];
-        WSC_CHECK(c.kh == 3 && c.kw == 3 && c.Cout == L.Cout && (c.form == CONV_FORM_GENERIC ? c.Cin == L.Cin : (c.Cin == 4 && L.Cin <= 4)) &&
-                      c.bn == L.bn && (c.bn >= 0) == (c.s2 != nullptr && c.b2 != nullptr),
-                  WSC_ERR_INVALID, "internal: layer %d of the layout is not the net's", (int)i);
+        WSC_CHECK(conv_is_layer(c, 3, L.Cin, L.Cout) && c.bn == L.bn && (c.bn >= 0) == (c.s2 != nullptr && c.b2 != nullptr), WSC_ERR_INVALID,
+                  "internal: layer %d of the layout is not the net's", (int)i);
     }
     WSC_HIP(hipSetDevice(ctx->device));
     const int C = net->Ccls, F = net->F;
     if (!g->repack.jobs_dev) { // the job tables: once per wsc_cls_grad (the packed buffers of both objects never move)
-        std::vector<RepackJob> jobs(convs.size());
-        std::vector<VecCopyJob> vecs;
-        std::vector<BnFoldJob> folds;
-        int vec_blocks = 0, fold_blocks = 0;
+        std::vector<RepackJob> jobs;
+        JobTable<VecCopyJob> vecs;
+        JobTable<BnFoldJob> folds;
         long long run_off = 0;
-        auto vec = [&](long long off, int n, float *dst) {
-            VecCopyJob V;
-            V.off = off; V.n = n; V.block0 = vec_blocks; V.dst = dst;
-            vec_blocks += (n + VEC_COPY_PER_BLOCK - 1) / VEC_COPY_PER_BLOCK;
-            vecs.push_back(V);
-        };
         for (size_t i = 0; i < convs.size(); ++i) {
             const ConvW &c = *convs[i];
             const ClsGradLayer &L = g->layers[i];
-            RepackJob &J = jobs[i];
-            J = RepackJob();
-            J.w_off = L.w_off; J.b_off = L.b_off;
-            J.k = 3; J.Cin = L.Cin; J.Cout = L.Cout;
-            J.small = c.form != CONV_FORM_GENERIC;
-            J.wp = c.w; J.s1 = c.s1; J.b1 = c.b1;
-            J.w_rot = L.w_rot;
+            jobs.push_back(conv_repack_job(c, 3, L.Cin, L.Cout, L.w_off, L.b_off, L.w_rot));
             if (L.bn < 0) continue;
             const PlainBn &pb = net->bns[L.bn];
-            vec(L.g_off, L.Cout, pb.gamma);
-            vec(L.be_off, L.Cout, pb.beta);
-            BnFoldJob B;
-            B.g_off = L.g_off; B.be_off = L.be_off; B.run_off = run_off;
-            B.C = L.Cout; B.block0 = fold_blocks; B.eps = pb.eps_fold;
-            B.s2 = c.s2; B.b2 = c.b2;
-            fold_blocks += (L.Cout + BN_FOLD_PER_BLOCK - 1) / BN_FOLD_PER_BLOCK;
+            add_vec(vecs, L.g_off, L.Cout, pb.gamma);
+            add_vec(vecs, L.be_off, L.Cout, pb.beta);
+            folds.add({L.g_off, L.be_off, run_off, L.Cout, 0, pb.eps_fold, c.s2, c.b2}, L.Cout, BN_FOLD_PER_BLOCK);
             run_off += 2ll * L.Cout;
-            folds.push_back(B);
         }
-        vec(g->cls_w_off, C * F, net->cls_w);
-        if (g->cls_b_off >= 0) vec(g->cls_b_off, C, net->cls_b);
+        add_vec(vecs, g->cls_w_off, C * F, net->cls_w);
+        if (g->cls_b_off >= 0) add_vec(vecs, g->cls_b_off, C, net->cls_b);
         // (the conv table last: jobs_dev, what marks the tables as built, is set by its plan)
-        WSC_TRY(g->upload(vecs.data(), vecs.size() * sizeof(VecCopyJob), (void **)&g->vec_jobs));
-        g->n_vec_jobs = (int)vecs.size();
-        g->vec_blocks = vec_blocks;
-        if (!folds.empty()) WSC_TRY(g->upload(folds.data(), folds.size() * sizeof(BnFoldJob), (void **)&g->fold_jobs));
-        g->n_fold_jobs = (int)folds.size();
-        g->fold_blocks = fold_blocks;
+        WSC_TRY(vecs.upload(g));
+        WSC_TRY(folds.upload(g));
+        g->vecs = vecs;
+        g->folds = folds;
         if (net->head_is_cls) { // the head: a 1 x 1 layer [F][C] without a bias, read from the transposed copy
             const ConvW &h = net->head;
             WSC_CHECK(h.kh == 1 && h.kw == 1 && h.form == CONV_FORM_GENERIC && h.Cin == F && h.Cout == C && !h.s2, WSC_ERR_INVALID,
                       "internal: the CAM head is no 1 x 1 layer over the %d feature channels", F);
             WSC_TRY(g->own((size_t)C * F * sizeof(float), (void **)&g->head_t));
-            std::vector<RepackJob> hj(1);
-            hj[0] = RepackJob();
-            hj[0].w_off = 0; hj[0].b_off = -1;
-            hj[0].k = 1; hj[0].Cin = F; hj[0].Cout = C;
-            hj[0].wp = h.w; hj[0].s1 = h.s1; hj[0].b1 = h.b1;
+            std::vector<RepackJob> hj(1, conv_repack_job(h, 1, F, C, 0, -1, nullptr));
             WSC_TRY(g->plan_repack(hj, &g->head_repack));
         }
         WSC_TRY(g->plan_repack(jobs));
     }
     WSC_TRY(repack_launch(ctx, g->repack, param_dev));
-    WSC_TRY(vec_copy_launch(ctx, g->vec_jobs, g->n_vec_jobs, g->vec_blocks, param_dev));
-    if (run_dev) WSC_TRY(bn_fold_launch(ctx, g->fold_jobs, g->n_fold_jobs, g->fold_blocks, param_dev, run_dev));
+    WSC_TRY(vec_copy_launch(ctx, g->vecs.dev, g->vecs.n, g->vecs.blocks, param_dev));
+    if (run_dev) WSC_TRY(bn_fold_launch(ctx, g->folds.dev, g->folds.n, g->folds.blocks, param_dev, run_dev));
     if (net->head_is_cls) {
         // (wsc_ctx_scratch_fill: the transposed copy is scratch of this call, kept by the object between calls)
         if (ctx->scratch_fill >= 0) WSC_HIP(hipMemsetAsync(g->head_t, ctx->scratch_fill, (size_t)C * F * sizeof(float), ctx->stream));

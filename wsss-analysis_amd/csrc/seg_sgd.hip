@@ -163,7 +163,6 @@ __global__ __launch_bounds__(SGD_BLOCK) void sgd_apply_kernel(float *param, floa
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 int sgd_blocks(long long elems, bool vec) {
     const long long nvec = vec ? (elems + 3) / 4 : elems;
     return (int)std::min<long long>(std::max<long long>((nvec + SGD_BLOCK - 1) / SGD_BLOCK, 1), SGD_L2_MAX_BLOCKS);

@@ -3,6 +3,7 @@
 The product path has no CPU fallback: if the shared library is missing, or no gfx950
 device is present, the calls fail loudly (WscError).
 """
+import collections
 import ctypes
 import os
 import re
@@ -829,10 +830,61 @@ class Net:
                                                   int(trace_elems)))
 
 
+# ---- the parameter codec: {name: tensor} <-> one flat float32 buffer in a gradient layout.  Layouts and arrays in, nothing else: no
+# device, no library.  Every flat_params / to_state_dict / to_host / params_host of the training modules is a call into these two.
+# Field: one tensor of a flat buffer -- `key` its name (a tuple is a path into nested dicts: ('conv1_1', 'w')), `offset` and `size` in
+# floats, `shape` as the caller sees it, `perm` the axis permutation into the stored order (None: it lies as it is), `head`: a tensor
+# of more rows than shape[0] gives its first shape[0] (a Linear of more rows than the net has classes).
+Field = collections.namedtuple("Field", "key offset size shape perm head", defaults=(None, False))
+
+
+def flatten(tensors, fields, elems=None):
+    """tensors by the fields' keys (arrays or torch tensors; other keys are ignored) -> one float32 array of `elems` floats (None:
+    up to the last field's end), every field's tensor in its stored order at its offset.  A missing tensor or a shape that is not
+    the field's is a ValueError that names it."""
+    flat = np.empty((max([f.offset + f.size for f in fields] + [0]) if elems is None else int(elems),), np.float32)
+    for f in fields:
+        v = tensors
+        for k in f.key if isinstance(f.key, tuple) else (f.key,):
+            if not hasattr(v, "keys") or k not in v:
+                raise ValueError("flatten: there is no tensor %r" % (f.key,))
+            v = v[k]
+        v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+        if f.head and v.ndim == len(f.shape) and v.shape[0] >= f.shape[0]:
+            v = v[:f.shape[0]]
+        if tuple(v.shape) != tuple(f.shape):
+            raise ValueError("flatten: %r is %r, the layout has %r" % (f.key, tuple(v.shape), tuple(f.shape)))
+        flat[f.offset:f.offset + f.size] = (v if f.perm is None else v.transpose(f.perm)).reshape(-1)
+    return flat
+
+
+def unflatten(flat, fields):
+    """The inverse of flatten: -> {key: a new array of the field's shape} (a tuple key nests: {'conv1_1': {'w': ...}})."""
+    out = {}
+    for f in fields:
+        v = flat[f.offset:f.offset + f.size]
+        if f.perm is None:
+            v = v.reshape(f.shape).copy()
+        else:
+            v = np.ascontiguousarray(v.reshape([f.shape[a] for a in f.perm]).transpose([int(a) for a in np.argsort(f.perm)]))
+        path, d = f.key if isinstance(f.key, tuple) else (f.key,), out
+        for k in path[:-1]:
+            d = d.setdefault(k, {})
+        d[path[-1]] = v
+    return out
+
+
+def _named_fields(layout, perm):
+    """the fields of an irn / cls layout ([{'name', 'shape', 'offset', 'size', 'conv'}]): conv weights stored under `perm`"""
+    return [Field(e["name"], e["offset"], e["size"], tuple(e["shape"]), perm if e["conv"] else None, ".classifier." in e["name"])
+            for e in layout]
+
+
 class _Grad:
     """The handle of a wsc_<KIND>_grad: created from the net and the state dict the net was created from, `grad_elems` and the
-    entries of wsc_<KIND>_grad_layout (a subclass shapes them into its `layout`), close() / __del__.  The net must outlive it."""
-    KIND = None  # "seg" / "irn"
+    entries of wsc_<KIND>_grad_layout (a subclass shapes them into its `layout`, and fields(layout) says how a layout's tensors
+    lie for the codec above), close() / __del__.  The net must outlive it."""
+    KIND = None  # "seg" / "irn" / "cls"
 
     def __init__(self, net, state_dict):
         self.ctx = net.ctx
@@ -870,6 +922,15 @@ class SegGrad(_Grad):
     def _shape_layout(ent):
         # layer -> its kernel, channels and the float offsets of dW (HWIO) and db in the gradient buffer
         return {e.name.decode(): {"k": e.kh, "Cin": e.Cin, "Cout": e.Cout, "w_off": e.w_off, "b_off": e.b_off} for e in ent}
+
+    @staticmethod
+    def fields(layout):
+        """per layer (layer, 'w'), HWIO as it lies, and (layer, 'b')"""
+        out = []
+        for layer, e in layout.items():
+            shape = (e["k"], e["k"], e["Cin"], e["Cout"])
+            out += [Field((layer, "w"), e["w_off"], e["k"] * e["k"] * e["Cin"] * e["Cout"], shape), Field((layer, "b"), e["b_off"], e["Cout"], (e["Cout"],))]
+        return out
 
     def backward(self, B, H, W, tape_dev, tape_elems, dfc8_dev, grad_dev, grad_elems=None):
         """wsc_net_backward_seg: dfc8_dev float32 [B][h][w][C] -> every element of grad_dev (self.grad_elems floats), on the
@@ -927,23 +988,15 @@ class IrnGrad(_Grad):
         check(self.ctx._lib.wsc_net_backward_edge(run.h, self.h, int(N), int(S), _ptr(tape_dev), int(tape_elems), _ptr(dedge_dev),
                                                   _ptr(ddp_dev), _ptr(grad_dev), self._elems(grad_elems)))
 
+    @staticmethod
+    def fields(layout):
+        """torch's OIHW 1 x 1 weights stored as [Cin][Cout], the vectors as they lie"""
+        return _named_fields(layout, (1, 0, 2, 3))
 
     def flat_params(self, state_dict):
         """The head tensors of a state dict ({name: array in torch's shape}; other keys are ignored) -> one float32 array of
-        grad_elems floats in `layout` order, conv weights transposed to [Cin][Cout]: the host form of what sgd_step and
-        load_params take, the inverse of irn_train.IrnGrads.to_state_dict."""
-        flat = np.empty((self.grad_elems,), np.float32)
-        for e in self.layout:
-            if e["name"] not in state_dict:
-                raise ValueError("IrnGrad.flat_params: the state dict has no %r" % e["name"])
-            v = state_dict[e["name"]]
-            v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
-            if tuple(v.shape) != tuple(e["shape"]):
-                raise ValueError("IrnGrad.flat_params: %r is %r, the net has %r" % (e["name"], tuple(v.shape), tuple(e["shape"])))
-            if e["conv"]:
-                v = v.reshape(e["shape"][0], e["shape"][1]).T
-            flat[e["offset"]:e["offset"] + e["size"]] = v.reshape(-1)
-        return flat
+        grad_elems floats in `layout`: the host form of what sgd_step and load_params take (IrnGrads.to_state_dict's inverse)."""
+        return flatten(state_dict, self.fields(self.layout), self.grad_elems)
 
     def sgd_step(self, param_dev, grad_dev, mom_dev, lr_edge, lr_dp, weight_decay, sgd_momentum, elems=None, ctx=None):
         """wsc_irn_sgd_step on three buffers of grad_elems floats in `layout`: g = grad + weight_decay p; m = sgd_momentum m + g;
@@ -1015,24 +1068,16 @@ class ClsGrad(_Grad):
     def param_elems(self):
         return self._param_query()[1]
 
+    @staticmethod
+    def fields(layout):
+        """torch's OIHW 3 x 3 weights stored as [3][3][Cin][Cout]; the vectors and the classifier's Linear [C][F] as they lie, the
+        classifier's two tensors cut to their first C rows"""
+        return _named_fields(layout, (2, 3, 1, 0))
+
     def flat_params(self, state_dict):
         """The trainable tensors of a state dict ({name: array in torch's shape}; other keys are ignored) -> one float32 array of
-        param_elems floats in `param_layout` order: conv weights transposed to [3][3][Cin][Cout], the first C rows of the
-        classifier's Linear (and of its bias) as they lie.  The host form of what sgd_step and load_params take."""
-        flat = np.empty((self.param_elems,), np.float32)
-        for e in self.param_layout:
-            if e["name"] not in state_dict:
-                raise ValueError("ClsGrad.flat_params: the state dict has no %r" % e["name"])
-            v = state_dict[e["name"]]
-            v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
-            if ".classifier." in e["name"] and v.ndim == len(e["shape"]) and v.shape[0] >= e["shape"][0]:
-                v = v[:e["shape"][0]]  # (a Linear of more rows than the net has classes: the net uses the first C)
-            if tuple(v.shape) != tuple(e["shape"]):
-                raise ValueError("ClsGrad.flat_params: %r is %r, the net has %r" % (e["name"], tuple(v.shape), tuple(e["shape"])))
-            if e["conv"]:
-                v = v.transpose(2, 3, 1, 0)
-            flat[e["offset"]:e["offset"] + e["size"]] = v.reshape(-1)
-        return flat
+        param_elems floats in `param_layout`: the host form of what sgd_step and load_params take."""
+        return flatten(state_dict, self.fields(self.param_layout), self.param_elems)
 
     def sgd_step(self, param_dev, grad_dev, mom_dev, lr, momentum=0.9, nesterov=True, elems=None, ctx=None):
         """wsc_cls_sgd_step on three buffers of param_elems floats in `param_layout`: v = momentum m - lr g; m = v;

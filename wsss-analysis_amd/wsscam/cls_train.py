@@ -43,7 +43,8 @@ import numpy as np
 
 from . import _lib
 from .misc.imutils import default_context
-from .secdsrg import DeviceMaps, Freed, device_operand
+from .device import DeviceMaps, Freed, Tape, device_operand
+from .trainer import TrainerCore
 
 K_EPSILON = 1e-7  # K.epsilon()
 POOLS = {"mean": _lib.CLS_POOL_MEAN, "max": _lib.CLS_POOL_MAX}
@@ -129,46 +130,18 @@ class ClsLoss:
         return self._run(feat, w, bias, targets, sample_weight, True, out)
 
 
-class ClsTape(Freed):
-    """The tape of CAM.forward_train_dev(x, keep=True): `maps` one float32 DeviceMaps of `elems` floats, `entries` the plan of
-    Net.cls_tape_plan for a (B, 3, H, W) input, `dropout` None or the (drop_prob, seed, step) of the pass that wrote it (what
-    backward_dev regenerates the keep-masks from: the tape itself holds no mask).  entry(name) downloads one tensor
-    ([B][Ho][Wo][C]; a ".stats" entry (C, 2)); free() / a context manager releases the buffer."""
+class ClsTape(Tape):
+    """The tape of CAM.forward_train_dev(x, keep=True): a device.Tape on the plan of Net.cls_tape_plan for a (B, 3, H, W) input;
+    `dropout` None or the (drop_prob, seed, step) of the pass that wrote it (what backward_dev regenerates the keep-masks from: the
+    tape itself holds no mask).  A ".stats" entry downloads as (C, 2)."""
 
     def __init__(self, maps, entries, B, H, W, dropout=None):
-        self.maps, self.entries, self.B, self.H, self.W = maps, entries, int(B), int(H), int(W)
+        super().__init__(maps, entries, B)
+        self.B, self.H, self.W = int(B), int(H), int(W)
         self.dropout = None if dropout is None else (float(dropout[0]), int(dropout[1]), int(dropout[2]))
-        self.elems = maps.shape[0]
 
-    def entry(self, name):
-        e = next(e for e in self.entries if e["name"] == name)
-        shape = (e["C"] // 2, 2) if name.endswith(".stats") else (self.B, e["Ho"], e["Wo"], e["C"])
-        return self.maps.ctx.to_host(self.maps.buf, shape, np.float32, offset_bytes=4 * e["offset"])
-
-
-class _GradView(DeviceMaps):
-    """A parameter's range of a ClsGrads buffer as a DeviceMaps: it owns nothing (free() is a no-op) and dies with the buffer."""
-
-    def __init__(self, parent, offset, shape):
-        self.ctx, self.shape, self.dtype = parent.ctx, tuple(shape), np.dtype(np.float32)
-        self.sizes = self.offsets = None
-        self._parent, self._at = parent, 4 * int(offset)
-
-    @property
-    def buf(self):
-        return self._parent.buf
-
-    @property
-    def ptr(self):
-        return None if self._parent.ptr is None else self._parent.ptr + self._at
-
-    def to_host(self):
-        if self._parent.buf is None:
-            raise ValueError("ClsGrads: freed")
-        return self.ctx.to_host(self._parent.buf, self.shape, self.dtype, offset_bytes=self._at)
-
-    def free(self):
-        pass
+    def entry_shape(self, e):
+        return (e["C"] // 2, 2) if e["name"].endswith(".stats") else super().entry_shape(e)
 
 
 class ClsGrads(Freed):
@@ -197,18 +170,10 @@ class ClsGrads(Freed):
     def __getitem__(self, name):
         e = self._entry(name)
         cout, cin = (e["shape"] + (0,))[:2]
-        return _GradView(self.maps, e["offset"], (3, 3, cin, cout) if e["conv"] else e["shape"])
+        return self.maps.view(e["offset"], (3, 3, cin, cout) if e["conv"] else e["shape"])
 
     def to_state_dict(self):
-        flat = self.maps.to_host()
-        out = {}
-        for e in self.layout:
-            v = flat[e["offset"]:e["offset"] + e["size"]]
-            if e["conv"]:
-                cout, cin = e["shape"][:2]
-                v = v.reshape(3, 3, cin, cout).transpose(3, 2, 0, 1)
-            out[e["name"]] = np.ascontiguousarray(v)
-        return out
+        return _lib.unflatten(self.maps.to_host(), _lib.ClsGrad.fields(self.layout))
 
 
 def grad_step(net, loss, x, targets, sample_weight=None, dropout=None):
@@ -429,7 +394,7 @@ def cyclic_session_rates(session, base_lr, max_lr, droprate=0.5):
     return base_lr * droprate ** int(session), max_lr * droprate ** int(session)
 
 
-class ClsTrainer:
+class ClsTrainer(TrainerCore):
     """One 01_train step after another on the device: compile(SGD(momentum, nesterov)) + train_on_batch of demo.py:60-61.
 
         ClsTrainer(model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99, drop_prob=0.0, seed=0)
@@ -462,9 +427,9 @@ class ClsTrainer:
                     and drop_prob from the file (a file without them: 0) unless the keyword is given, which wins.
                     save(path, extra={"__name__": value}) stores more keys of that form; load leaves them in `loaded_extra`
     close() / a context manager releases the three buffers (the model stays the caller's)"""
+    BUFFERS = ("params", "mom", "grads")
 
     def __init__(self, model, pool, num_classes, momentum=0.9, nesterov=True, bn_keep=0.99, ctx=None, drop_prob=0.0, seed=0):
-        self.params = self.mom = self.grads = None
         self.model = model
         self.ctx = model.ctx
         if ctx is not None and ctx is not self.ctx:
@@ -485,44 +450,23 @@ class ClsTrainer:
         self._tail = {e["name"].rsplit(".", 1)[1]: e for e in self.grad.param_layout if ".classifier." in e["name"]}
         if self._tail["weight"]["shape"][0] != self.loss.C:
             raise ValueError("ClsTrainer: num_classes = %d, the net's classifier has %d rows" % (self.loss.C, self._tail["weight"]["shape"][0]))
+        self._init_buffers(lambda: self.grad.flat_params(model._sd), scratch=("grads",))
         try:
-            flat = self.grad.flat_params(model._sd)
-            self.params = DeviceMaps.from_host(self.ctx, flat)
-            self.mom = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
-            self.grads = DeviceMaps(self.ctx, flat.shape, np.float32)
             model.bn_running_dev()  # (the model's own resident buffer, made on first use: here, not inside the first step)
         except Exception:
             self.close()
             raise
 
-    def close(self):
-        for name in ("params", "mom", "grads"):
-            buf = getattr(self, name, None)
-            if buf is not None:
-                buf.free()
-            setattr(self, name, None)
+    def _fields(self):
+        return _lib.ClsGrad.fields(self.grad.param_layout)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _live(self):
-        if self.params is None or getattr(self.model, "_cls_grad", None) is not self.grad:
-            raise ValueError("ClsTrainer: closed, or the model's net was rebuilt since the trainer was made")
+    def _grad_now(self):
+        return getattr(self.model, "_cls_grad", None)
 
     def _tail_views(self, buf):
         """(weight (C, F), bias (C,) or None): the classifier's ranges of a buffer in param_layout"""
         w, b = self._tail["weight"], self._tail.get("bias")
-        return _GradView(buf, w["offset"], w["shape"]), None if b is None else _GradView(buf, b["offset"], b["shape"])
+        return buf.view(w["offset"], w["shape"]), None if b is None else buf.view(b["offset"], b["shape"])
 
     def step(self, x, targets, lr, sample_weight=None):
         self._live()
@@ -558,23 +502,6 @@ class ClsTrainer:
                 if m is not None:
                     m.free()
 
-    def _host(self, buf):
-        flat = buf.to_host()
-        out = {}
-        for e in self.grad.param_layout:
-            v = flat[e["offset"]:e["offset"] + e["size"]]
-            if e["conv"]:
-                cout, cin = e["shape"][:2]
-                v = v.reshape(3, 3, cin, cout).transpose(3, 2, 0, 1)
-            out[e["name"]] = np.ascontiguousarray(v.reshape(e["shape"]) if not e["conv"] else v)
-        return out
-
-    def params_host(self):
-        return self._host(self.params)
-
-    def momentum_host(self):
-        return self._host(self.mom)
-
     def state_dict(self):
         self._live()
         sd = self.model._sd
@@ -587,39 +514,25 @@ class ClsTrainer:
         sd.update(self.model.bn_running())
         return {k: v.copy() for k, v in sd.items()}
 
-    def save(self, path, extra=None):
-        d = self.state_dict()
-        d["__momentum__"] = self.momentum_host()
-        d["__step__"] = {"global_step": self.global_step}
+    _params_dict = state_dict
+
+    def _step_dict(self):
+        step = {"global_step": self.global_step}
         if self.drop_prob > 0.0:  # (a trainer without dropout writes the file it always wrote)
-            d["__step__"].update(seed=self.seed, drop_prob=self.drop_prob)
-        for k, v in (extra or {}).items():
-            if not k.startswith("__") or k in d:
-                raise ValueError("ClsTrainer.save: extra key %r (a new name beginning with '__')" % (k,))
-            d[k] = v
-        with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
-            np.save(fh, d, allow_pickle=True)
+            step.update(seed=self.seed, drop_prob=self.drop_prob)
+        return step
+
+    def _set_step(self, step):
+        self.global_step = int(step.get("global_step", 0))
 
     @classmethod
     def load(cls, path, model, pool, num_classes, **kwargs):
-        d = np.load(path, encoding="latin1", allow_pickle=True).item()
-        model.load_state_dict({k: v for k, v in d.items() if not k.startswith("__")})
+        tensors, marked = cls._read(path)
+        model.load_state_dict(tensors)
         model.cuda()
         for key, default in (("drop_prob", 0.0), ("seed", 0)):  # (the file's unless the caller says otherwise)
-            kwargs.setdefault(key, d.get("__step__", {}).get(key, default))
-        tr = cls(model, pool, num_classes, **kwargs)
-        try:
-            if "__momentum__" in d:
-                flat = tr.grad.flat_params(d["__momentum__"])  # (a slot has the parameters' shapes)
-                tr.mom.free()
-                tr.mom = None
-                tr.mom = DeviceMaps.from_host(tr.ctx, flat)
-            tr.global_step = int(d.get("__step__", {}).get("global_step", 0))
-            tr.loaded_extra = {k: v for k, v in d.items() if k.startswith("__") and k not in ("__momentum__", "__step__")}
-        except Exception:
-            tr.close()
-            raise
-        return tr
+            kwargs.setdefault(key, marked.get("__step__", {}).get(key, default))
+        return cls(model, pool, num_classes, **kwargs)._resume(marked)
 
 
 def fit(trainer, batches, lr_of_step, steps_per_epoch=None):
@@ -1039,8 +952,7 @@ def train(paths, labels, val_paths, val_labels, model, pool, sess_id, model_dir,
             if (epoch + 1) % lr_dropstep == 0:
                 trainer.save(os.path.join(ckpt_dir, "%s-%02d.npy" % (sess_id, epoch + 1)),
                              extra={"__train__": {"epoch": epoch + 1, "batcher": gen.state()}})
-        with open(os.path.join(model_dir, sess_id + ".npy"), "wb") as fh:
-            np.save(fh, trainer.state_dict(), allow_pickle=True)
+        TrainerCore._write(os.path.join(model_dir, sess_id + ".npy"), trainer.state_dict())
         return history
     finally:
         trainer.close()

@@ -26,7 +26,8 @@ import numpy as np
 from . import _lib
 from .misc import imutils
 from .misc.torchutils import PolyOptimizer
-from .secdsrg import DeviceMaps, Freed, device_operand
+from .device import DeviceMaps, Freed, Tape, device_operand
+from .trainer import TrainerCore
 
 
 def reduce_label(label):
@@ -38,18 +39,13 @@ def reduce_label(label):
     return np.ascontiguousarray(imutils.pil_rescale(label.astype(np.uint8), 0.25, 0))
 
 
-class EdgeTape(Freed):
-    """The tape of EdgeDisplacement.forward_train_dev(x, keep=True): `maps` one float32 DeviceMaps of `elems` floats, `entries`
-    the plan of Net.edge_tape_plan for N samples of S x S.  entry(name) downloads one tensor ([N][Ho][Wo][C]); free() / a
-    context manager releases the buffer."""
+class EdgeTape(Tape):
+    """The tape of EdgeDisplacement.forward_train_dev(x, keep=True): a device.Tape on the plan of Net.edge_tape_plan for N samples
+    of S x S."""
 
     def __init__(self, maps, entries, N, S):
-        self.maps, self.entries, self.N, self.S = maps, entries, int(N), int(S)
-        self.elems = maps.shape[0]
-
-    def entry(self, name):
-        e = next(e for e in self.entries if e["name"] == name)
-        return self.maps.ctx.to_host(self.maps.buf, (self.N, e["Ho"], e["Wo"], e["C"]), np.float32, offset_bytes=4 * e["offset"])
+        super().__init__(maps, entries, N)
+        self.N, self.S = int(N), int(S)
 
 
 class IrnGrads(Freed):
@@ -69,15 +65,7 @@ class IrnGrads(Freed):
         return self.maps.ptr + 4 * next(e for e in self.layout if e["name"] == name)["offset"]
 
     def to_state_dict(self):
-        flat = self.maps.to_host()
-        out = {}
-        for e in self.layout:
-            v = flat[e["offset"]:e["offset"] + e["size"]]
-            if e["conv"]:
-                cout, cin = e["shape"][:2]
-                v = v.reshape(cin, cout).T.reshape(e["shape"])
-            out[e["name"]] = np.ascontiguousarray(v)
-        return out
+        return _lib.unflatten(self.maps.to_host(), _lib.IrnGrad.fields(self.layout))
 
 
 class AffinityLoss:
@@ -236,7 +224,7 @@ class TrainBatcher:
                 m.free()
 
 
-class IrnTrainer:
+class IrnTrainer(TrainerCore):
     """One IRNet training step after another, and the closing pass: step/train_irn.py:86-90, 105-164 on the device.
 
         IrnTrainer(model, path_index, lr, weight_decay, max_step, power=0.9, sgd_momentum=None, valid_below=21)
@@ -262,7 +250,6 @@ class IrnTrainer:
     close() / a context manager releases the two buffers (the model stays the caller's)"""
 
     def __init__(self, model, path_index, lr, weight_decay, max_step, power=0.9, sgd_momentum=None, valid_below=21, ctx=None):
-        self.params = self.mom = None
         self.model = model
         self.ctx = model.ctx
         if ctx is not None and ctx is not self.ctx:
@@ -270,33 +257,13 @@ class IrnTrainer:
         self.loss = AffinityLoss(path_index, valid_below=valid_below, ctx=self.ctx)
         self.grad = model.irn_grad()
         self.opt = PolyOptimizer(self.grad, lr, weight_decay, max_step, momentum=power, sgd_momentum=sgd_momentum)
-        try:
-            flat = self.grad.flat_params(model._sd)
-            self.params = DeviceMaps.from_host(self.ctx, flat)
-            self.mom = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
-        except Exception:
-            self.close()
-            raise
+        self._init_buffers(lambda: self.grad.flat_params(model._sd))
 
-    def close(self):
-        for name in ("params", "mom"):
-            buf = getattr(self, name, None)
-            if buf is not None:
-                buf.free()
-            setattr(self, name, None)
+    def _fields(self):
+        return _lib.IrnGrad.fields(self.grad.layout)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _grad_now(self):
+        return self.model.irn_grad()
 
     @property
     def global_step(self):
@@ -305,10 +272,6 @@ class IrnTrainer:
     @property
     def lr(self):
         return self.opt.lr_now()
-
-    def _live(self):
-        if self.params is None or self.model.irn_grad() is not self.grad:
-            raise ValueError("IrnTrainer: closed, or the model's net was rebuilt since the trainer was made")
 
     def step(self, x, label):
         self._live()
@@ -319,12 +282,6 @@ class IrnTrainer:
         finally:
             grads.free()
         return losses
-
-    def params_host(self):
-        return IrnGrads(self.params, self.grad.layout).to_state_dict()
-
-    def momentum_host(self):
-        return IrnGrads(self.mom, self.grad.layout).to_state_dict()
 
     def fit_dp_mean(self, batches, n_batches=None):
         """n_batches: the count of an iterable that is consumed one batch at a time (step.train_irn: each batch is a DeviceMaps
@@ -363,27 +320,17 @@ class IrnTrainer:
         sd["mean_shift.running_mean"] = self.model._ensure_net().get_mean_shift()
         return {k: v.copy() for k, v in sd.items()}
 
-    def save(self, path):
-        d = self.state_dict()
-        d["__momentum__"] = self.momentum_host()
-        d["__step__"] = {"global_step": self.global_step}
-        with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
-            np.save(fh, d, allow_pickle=True)
+    _params_dict = state_dict
+
+    def _step_dict(self):
+        return {"global_step": self.global_step}
+
+    def _set_step(self, step):
+        self.opt.global_step = int(step.get("global_step", 0))
 
     @classmethod
     def load(cls, path, model, path_index, lr, weight_decay, max_step, **kwargs):
-        d = np.load(path, encoding="latin1", allow_pickle=True).item()
-        model.load_state_dict({k: v for k, v in d.items() if not k.startswith("__")})
+        tensors, marked = cls._read(path)
+        model.load_state_dict(tensors)
         model.cuda()
-        tr = cls(model, path_index, lr, weight_decay, max_step, **kwargs)
-        try:
-            if "__momentum__" in d:
-                flat = tr.grad.flat_params(d["__momentum__"])  # (a slot has the parameters' shapes)
-                tr.mom.free()
-                tr.mom = None
-                tr.mom = DeviceMaps.from_host(tr.ctx, flat)
-            tr.opt.global_step = int(d.get("__step__", {}).get("global_step", 0))
-        except Exception:
-            tr.close()
-            raise
-        return tr
+        return cls(model, path_index, lr, weight_decay, max_step, **kwargs)._resume(marked)

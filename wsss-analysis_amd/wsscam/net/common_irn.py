@@ -2,6 +2,7 @@
 import numpy as np
 
 from .. import _lib
+from ..device import DeviceMaps, device_input
 from .common import DeviceCAMBase
 
 
@@ -69,24 +70,15 @@ class EdgeDisplacementBase(DeviceCAMBase):
 
     def forward_train_dev(self, x, keep=False):
         """Net.forward in training mode (resnet50_irn.py:110-133, what AffinityDisplacementLoss.forward calls at :200), outputs
-        left in HBM: x float32 (N,3,S,S), a host array / tensor or a secdsrg.DeviceMaps of the model's context (read in place)
+        left in HBM: x float32 (N,3,S,S), a host array / tensor or a device.DeviceMaps of the model's context (read in place)
         -> (edge_out DeviceMaps (N,He,We), dp_out DeviceMaps (N,2,Hd,Wd)): plain samples, no flip pairing, no crop, no mean shift
         (MeanShift is the identity while training), no sigmoid.  keep=True: (edge_out, dp_out, tape) -- the same launches and
         bits, and the tape backward_dev needs (an irn_train.EdgeTape; the caller frees it)."""
         from ..irn_train import EdgeTape
-        from ..secdsrg import DeviceMaps
 
         net = self._ensure_net()
         ctx = self._ctx
-        mine = None
-        if isinstance(x, DeviceMaps):
-            if x.dtype != np.float32 or x.ctx is not ctx:
-                raise ValueError("forward_train_dev: x is %s on %s, not float32 on the model's context" %
-                                 (x.dtype, "another context" if x.ctx is not ctx else "this context"))
-            xd = x
-        else:
-            xn = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-            xd = mine = DeviceMaps.from_host(ctx, xn, dtype=np.float32)
+        xd, mine = device_input(ctx, x, np.float32, "forward_train_dev")
         edge = dp = tape = None
         try:
             if len(xd.shape) != 4 or xd.shape[1] != 3 or xd.shape[2] != xd.shape[3] or 0 in xd.shape:
@@ -131,26 +123,21 @@ class EdgeDisplacementBase(DeviceCAMBase):
         DeviceMaps of the model's context (read in place), or a host array (uploaded once; irn_grad().flat_params(sd) makes one).
         Afterwards the net has the bits of a model loaded with those head tensors.  The wrapper's own state dict is not touched
         (irn_train.IrnTrainer.state_dict does both)."""
-        from ..secdsrg import DeviceMaps
-
         g = self.irn_grad()
-        fd, mine = flat, False
-        if not isinstance(flat, DeviceMaps):
-            fd, mine = DeviceMaps.from_host(self._ctx, np.asarray(flat).reshape(-1), dtype=np.float32), True
+        fd, mine = device_input(self._ctx, flat if isinstance(flat, DeviceMaps) else np.asarray(flat).reshape(-1), np.float32, "load_params_dev")
         try:
-            if fd.dtype != np.float32 or fd.shape != (g.grad_elems,) or fd.ctx is not self._ctx or fd.ptr is None:
-                raise ValueError("load_params_dev: %r %s must be a live float32 (%d,) of the model's context" % (fd.shape, fd.dtype, g.grad_elems))
+            if fd.shape != (g.grad_elems,):
+                raise ValueError("load_params_dev: %r must be (%d,), the layout's size" % (fd.shape, g.grad_elems))
             g.load_params(fd.ptr)
         finally:
-            if mine:
-                fd.free()
+            if mine is not None:
+                mine.free()
 
     def backward_dev(self, tape, grad_edge, grad_dp):
         """total_loss.backward() through the heads (train_irn.py:127; the backbone stages are detached): tape of
         forward_train_dev(x, keep=True), grad_edge (N,He,We) or (N,1,He,We) and grad_dp (N,2,Hd,Wd) float32 DeviceMaps of the
         model's context (what AffinityLoss hands out), read in place -> irn_train.IrnGrads (the caller frees it)."""
         from ..irn_train import EdgeTape, IrnGrads
-        from ..secdsrg import DeviceMaps
 
         net = self._ensure_net()
         ctx = self._ctx

@@ -10,6 +10,7 @@ architecture file; None is the fixed architecture."""
 import numpy as np
 
 from .. import _lib
+from ..device import DeviceMaps, device_input
 from .common import DeviceCAMBase, normalize_pooling
 
 ADP_INDS_X17 = [2, 3, 4, 6, 7, 8, 9, 12, 13, 14, 16, 17, 18, 21, 22, 23, 25, 26, 28, 29, 30, 32, 33, 35, 37, 38, 40,
@@ -80,8 +81,6 @@ class CAM(DeviceCAMBase):
         """The running statistics forward_train_dev updates: one float32 DeviceMaps, per BatchNorm layer in stack order its
         running mean then its running variance; created from the state dict on first use, released with the net.  None for a net
         without BatchNorm."""
-        from ..secdsrg import DeviceMaps
-
         self._ensure_net()
         if getattr(self, "_bn_running", None) is None:
             keys = self.bn_keys()
@@ -117,7 +116,7 @@ class CAM(DeviceCAMBase):
 
     def forward_train_dev(self, x, keep=True, bn_keep=0.99, dropout=None):
         """The stack in training mode (make_layers' conv -> ReLU -> BatchNorm on the BATCH statistics): x float32 (B, 3, H, W), a
-        host array / tensor or a secdsrg.DeviceMaps of the model's context (read in place) -> (feat DeviceMaps (B, h, w, F), the
+        host array / tensor or a device.DeviceMaps of the model's context (read in place) -> (feat DeviceMaps (B, h, w, F), the
         map ClsLoss reads, tape): the cls_train.ClsTape backward_dev needs; the caller frees both.  keep=False: feat alone.
         dropout: None (the `D` entries of the table are the identity: wsc_net_forward_cls_train), or (drop_prob, seed, step) --
         the shape SegNet.forward_dev takes -- for wsc_net_forward_cls_train_drop: the sites active under the project's own
@@ -130,21 +129,12 @@ class CAM(DeviceCAMBase):
         port's BatchNorm2d(v, eps=0.001, momentum=0.99) is bn_keep = 0.01.  The batch variance enters unbiased (M / (M - 1)), as
         in torch and TensorFlow's fused batch norm; Keras 2.2's own factor is unpinned.  None: the running statistics stay."""
         from ..cls_train import ClsTape
-        from ..secdsrg import DeviceMaps
 
         if dropout is not None and not keep:
             raise ValueError("forward_train_dev: dropout=%r needs keep=True (the backward pass needs the triple the tape records)" % (dropout,))
         net = self._ensure_net()
         ctx = self._ctx
-        mine = None
-        if isinstance(x, DeviceMaps):
-            if x.dtype != np.float32 or x.ctx is not ctx:
-                raise ValueError("forward_train_dev: x is %s on %s, not float32 on the model's context" %
-                                 (x.dtype, "another context" if x.ctx is not ctx else "this context"))
-            xd = x
-        else:
-            xn = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-            xd = mine = DeviceMaps.from_host(ctx, xn, dtype=np.float32)
+        xd, mine = device_input(ctx, x, np.float32, "forward_train_dev")
         feat = tape = None
         try:
             if len(xd.shape) != 4 or xd.shape[1] != 3 or 0 in xd.shape:
@@ -186,7 +176,6 @@ class CAM(DeviceCAMBase):
         A tape of forward_train_dev(dropout=(drop_prob, seed, step)) carries the triple: wsc_net_backward_cls_drop regenerates
         the masks from it, and dfeat has the shape of that pass's feat (M7: the pooled (B, hp, wp, F))."""
         from ..cls_train import ClsGrads, ClsTape
-        from ..secdsrg import DeviceMaps
 
         net = self._ensure_net()
         ctx = self._ctx
@@ -219,17 +208,9 @@ class CAM(DeviceCAMBase):
         same floats and statistics; an M7 head, the Grad-CAM alpha, is no parameter and stays.  The wrapper's state dict is NOT
         touched (cls_train.ClsTrainer.state_dict downloads).  The model's cached gradcam_net()s hold packed copies of the old
         weights: they are released."""
-        from ..secdsrg import DeviceMaps
-
         self._ensure_net()
         ctx, grad = self._ctx, self.cls_grad()
-        mine = None
-        if isinstance(flat, DeviceMaps):
-            if flat.dtype != np.float32 or flat.ctx is not ctx or flat.ptr is None:
-                raise ValueError("load_params_dev: flat is no live float32 DeviceMaps of the model's context")
-            fd = flat
-        else:
-            fd = mine = DeviceMaps.from_host(ctx, np.asarray(flat), dtype=np.float32)
+        fd, mine = device_input(ctx, flat, np.float32, "load_params_dev")
         try:
             if int(np.prod(fd.shape)) != grad.param_elems:
                 raise ValueError("load_params_dev: %d floats, the layout has %d" % (int(np.prod(fd.shape)), grad.param_elems))

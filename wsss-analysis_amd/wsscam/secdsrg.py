@@ -34,81 +34,9 @@ TensorFlow: Model.predict runs on this module alone."""
 import numpy as np
 
 from . import _lib
+from .device import DeviceMaps, Freed, device_input, device_operand  # noqa: F401  (DeviceMaps, Freed, device_operand: re-exported)
 from .misc.imutils import default_context, prefetched
-
-
-class Freed:
-    """free() on exit of a `with` block; free() itself releases `maps`, the one DeviceMaps a holder class wraps."""
-
-    def free(self):
-        self.maps.free()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
-
-
-class DeviceMaps(Freed):
-    """A C-contiguous array in ONE pooled device buffer of a context: `shape`, `dtype`, `.ptr` (device address), `.to_host()`,
-    `.free()`; a context manager frees it on exit.  The buffer is pooled, so it belongs to its context's stream alone.
-    A packed ragged batch of uint8 images (SegNet.preprocess_dev(keep_images=True)) also carries `sizes` [(h, w)] and `offsets`
-    (bytes); its shape is the flat byte count."""
-
-    def __init__(self, ctx, shape, dtype=np.float32, buf=None):
-        self.ctx = ctx
-        self.shape = tuple(int(v) for v in shape)
-        self.dtype = np.dtype(dtype)
-        self.sizes = self.offsets = None
-        self.buf = buf if buf is not None else ctx.alloc(max(self.nbytes, 1), pooled=True)
-
-    @classmethod
-    def from_host(cls, ctx, arr, dtype=None):
-        """One upload of a host array."""
-        a = np.ascontiguousarray(arr, dtype=dtype)
-        return cls(ctx, a.shape, a.dtype, ctx.to_device(a, pooled=True))
-
-    @property
-    def nbytes(self):
-        return int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
-
-    @property
-    def ptr(self):
-        return None if self.buf is None else self.buf.ptr
-
-    def to_host(self):
-        if self.buf is None:
-            raise ValueError("DeviceMaps: freed")
-        return self.ctx.to_host(self.buf, self.shape, self.dtype)
-
-    def free(self):
-        if self.buf is not None:
-            self.buf.free()
-            self.buf = None
-
-
-def device_operand(owner, ctx, name, a, dtype, shape, held):
-    """One operand of a loss class as a DeviceMaps of `dtype`: a DeviceMaps is checked and read in place, a host array is uploaded
-    once and the upload appended to `held` (the caller frees those).  shape: a tuple to match, a function that says whether the
-    shape fits, or None.  A wrong dtype or shape is a ValueError that names the class of `owner` and the argument `name`."""
-    who, dtype = type(owner).__name__, np.dtype(dtype)
-    on_device = isinstance(a, DeviceMaps)
-    if on_device:
-        if a.dtype != dtype:
-            raise ValueError("%s: %s is %s on the device, not %s" % (who, name, a.dtype, dtype))
-    else:
-        a = np.asarray(a)
-        if a.dtype.kind not in "fiub":
-            raise ValueError("%s: %s has dtype %s, not a real number type" % (who, name, a.dtype))
-    got = tuple(a.shape)
-    if shape is not None and not (shape(got) if callable(shape) else got == tuple(shape)):
-        raise ValueError("%s: %s has shape %r%s" % (who, name, got, "" if callable(shape) else ", expected %r" % (tuple(shape),)))
-    if on_device:
-        return a
-    held.append(DeviceMaps.from_host(ctx, a, dtype=dtype))
-    return held[-1]
+from .trainer import TrainerCore
 
 
 class SegGrads(Freed):
@@ -139,12 +67,16 @@ class SegGrads(Freed):
                 for which in ("w", "b")}
 
     def to_host(self):
-        flat = self.maps.to_host()
-        out = {}
-        for layer, e in self.layout.items():
-            out[layer] = {which: flat[e[which + "_off"]:e[which + "_off"] + int(np.prod(self._shape(layer, which)))]
-                          .reshape(self._shape(layer, which)).copy() for which in ("w", "b")}
-        return out
+        return _lib.unflatten(self.maps.to_host(), _lib.SegGrad.fields(self.layout))
+
+
+class SegTape(DeviceMaps):
+    """The tape of SegNet.forward_dev(keep=True): a flat float32 DeviceMaps of `elems` floats with `entries` (the plan of
+    wsc_net_seg_tape_plan), `input_shape` (B, H, W) and `drop_prob` (0.0: a forward pass without dropout)."""
+
+    def __init__(self, ctx, elems, entries, input_shape, drop_prob=0.0):
+        super().__init__(ctx, (elems,), np.float32)
+        self.entries, self.input_shape, self.drop_prob = entries, tuple(input_shape), float(drop_prob)
 
 
 def _image_blocks(images):
@@ -799,22 +731,19 @@ class SegNet:
 
     # ---- device-resident twins: the same kernels, DeviceMaps in and out, no host array in between -----------------------------
     def _on_device(self, x):
-        """-> (DeviceMaps (B, H, W, 3), whether this call uploaded it and so frees it)"""
-        if isinstance(x, DeviceMaps):
-            if x.dtype != np.float32 or len(x.shape) != 4 or x.shape[3] != 3:
-                raise ValueError("SegNet: input %r %s must be float32 (B, H, W, 3)" % (x.shape, x.dtype))
-            return x, False
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        if x.ndim != 4 or x.shape[3] != 3:
+        """-> (DeviceMaps (B, H, W, 3), the upload this call made and so frees, or None)"""
+        if not isinstance(x, DeviceMaps):
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        if len(x.shape) != 4 or x.shape[3] != 3:
             raise ValueError("SegNet: input %r must be (B, H, W, 3)" % (x.shape,))
-        return DeviceMaps.from_host(self.ctx, x), True
+        return device_input(self.ctx, x, np.float32, "SegNet")
 
     def forward_dev(self, x, want_fc8=False, keep=False, dropout=None):
         """forward() with the maps left on the device: x a DeviceMaps (B, H, W, 3) (a host array is uploaded once) ->
         DeviceMaps (B, h, w, C) fc8-softmax; with want_fc8 (softmax, logits).  The range flag as in forward(): the stream is
         drained through range_status(clear=True) and a saturated forward raises WscError(WSC_ERR_RANGE) once.
-        keep: the last element returned is the tape backward_dev takes -- a flat float32 DeviceMaps with `.entries` (the plan of
-        wsc_net_seg_tape_plan), `.input_shape` (B, H, W) and `.drop_prob`; the maps have the bits of a forward without it.
+        keep: the last element returned is the tape backward_dev takes -- a SegTape: a flat float32 DeviceMaps with `.entries` (the
+        plan of wsc_net_seg_tape_plan), `.input_shape` (B, H, W) and `.drop_prob`; the maps have the bits of a forward without it.
         dropout: None, or (drop_prob, seed, step) -- the training forward pass (wsc_net_forward_seg_train) with the dropout sites
         behind fc6 / fc7 active: keep-masks of (seed, step, site, element index) under the project's own counter-based contract
         (not TensorFlow's stream), the tape's fc6* / fc7* entries the dropped, scaled activations.  0.5 is
@@ -830,14 +759,12 @@ class SegNet:
             outs = [DeviceMaps(ctx, (B, h, w, self.C), np.float32) for _ in range(2 if want_fc8 else 1)]
             if keep:
                 entries, elems = self.net.seg_tape_plan(B, H, W)
-                tape = DeviceMaps(ctx, (elems,), np.float32)
-                tape.entries, tape.input_shape, tape.drop_prob = entries, (B, H, W), 0.0
+                tape = SegTape(ctx, elems, entries, (B, H, W), 0.0 if dropout is None else dropout[0])
                 outs.append(tape)
                 if dropout is None:
                     self.net.forward_seg_tape(xd.ptr, B, H, W, tape.ptr, elems, outs[0].ptr, outs[1].ptr if want_fc8 else None, self.min_prob)
                 else:
                     drop_prob, seed, step = dropout
-                    tape.drop_prob = float(drop_prob)
                     self.net.forward_seg_train(xd.ptr, B, H, W, drop_prob, seed, step, tape.ptr, elems, outs[0].ptr,
                                                outs[1].ptr if want_fc8 else None, self.min_prob)
             else:
@@ -859,25 +786,20 @@ class SegNet:
         """opt.compute_gradients (wsc_net_backward_seg; wsc_net_backward_seg_drop where tape.drop_prob > 0): the tape of forward_dev(keep=True) and d loss / d fc8
         (B, h, w, C) float32 -- a DeviceMaps, e.g. the gradient loss_step_dev returns, or a host array -- -> SegGrads.  The chain rule
         evaluated at the tape, in exact fp32 whatever the net's precision.  The caller frees the result."""
-        ctx = self.ctx
-        if self._grad is None:
-            self._grad = _lib.SegGrad(self.net, self._sd)
+        ctx, g = self.ctx, self._ensure_grad()
         B, H, W = tape.input_shape
         want = (B,) + tuple(self.map_size(H, W)) + (self.C,)
-        gd, mine = dfc8, False
-        if not isinstance(dfc8, DeviceMaps):
-            gd, mine = DeviceMaps.from_host(ctx, dfc8, dtype=np.float32), True
+        gd, mine = device_input(ctx, dfc8, np.float32, "SegNet.backward_dev")
         out = None
         try:
-            if gd.dtype != np.float32 or gd.shape != want:
-                raise ValueError("SegNet.backward_dev: dfc8 %r %s must be float32 %r, the fc8 map's shape" % (gd.shape, gd.dtype, want))
-            out = DeviceMaps(ctx, (self._grad.grad_elems,), np.float32)
-            drop_prob = float(getattr(tape, "drop_prob", 0.0))
-            if drop_prob == 0.0:
-                self._grad.backward(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr)
+            if gd.shape != want:
+                raise ValueError("SegNet.backward_dev: dfc8 %r must be %r, the fc8 map's shape" % (gd.shape, want))
+            out = DeviceMaps(ctx, (g.grad_elems,), np.float32)
+            if tape.drop_prob == 0.0:
+                g.backward(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr)
             else:
-                self._grad.backward_drop(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr, drop_prob)
-            return SegGrads(out, self._grad.layout)
+                g.backward_drop(B, H, W, tape.ptr, tape.shape[0], gd.ptr, out.ptr, tape.drop_prob)
+            return SegGrads(out, g.layout)
         except Exception:
             if out is not None:
                 out.free()
@@ -896,14 +818,7 @@ class SegNet:
         HWIO, then b): the host form of what load_params_dev takes.  The shapes must be the net's."""
         g = self._ensure_grad()
         sd = seg_state_dict(self.method, weights, self.C)
-        flat = np.empty((g.grad_elems,), np.float32)
-        for layer, e in g.layout.items():
-            w, b = sd[layer + ".w"], sd[layer + ".b"]
-            if w.shape != (e["k"], e["k"], e["Cin"], e["Cout"]):
-                raise ValueError("SegNet.flat_params: layer %r is %r, the net has %r" % (layer, w.shape, (e["k"], e["k"], e["Cin"], e["Cout"])))
-            flat[e["w_off"]:e["w_off"] + w.size] = w.reshape(-1)
-            flat[e["b_off"]:e["b_off"] + b.size] = b
-        return flat
+        return _lib.flatten({layer: {"w": sd[layer + ".w"], "b": sd[layer + ".b"]} for layer in g.layout}, _lib.SegGrad.fields(g.layout), g.grad_elems)
 
     def load_params_dev(self, flat):
         """wsc_net_seg_load_params: every packed weight of the net and every data-gradient kernel of its backward pass rewritten on
@@ -911,12 +826,10 @@ class SegNet:
         (uploaded once).  Afterwards the net has the bits of a SegNet created from those weights.  The net must not be in use on
         another context's stream during the call."""
         g = self._ensure_grad()
-        fd, mine = flat, False
-        if not isinstance(flat, DeviceMaps):
-            fd, mine = DeviceMaps.from_host(self.ctx, np.asarray(flat).reshape(-1), dtype=np.float32), True
+        fd, mine = device_input(self.ctx, flat if isinstance(flat, DeviceMaps) else np.asarray(flat).reshape(-1), np.float32, "SegNet.load_params_dev")
         try:
-            if fd.dtype != np.float32 or fd.shape != (g.grad_elems,):
-                raise ValueError("SegNet.load_params_dev: %r %s must be float32 (%d,), the layout's size" % (fd.shape, fd.dtype, g.grad_elems))
+            if fd.shape != (g.grad_elems,):
+                raise ValueError("SegNet.load_params_dev: %r must be (%d,), the layout's size" % (fd.shape, g.grad_elems))
             g.load_params(fd.ptr)
         finally:
             if mine:
@@ -1065,7 +978,7 @@ class SegNet:
         return x
 
 
-class SegTrainer:
+class SegTrainer(TrainerCore):
     """One SEC / DSRG training step after another: Model.optimize() and the update branch of Model.train() (model.py:379-404,
     491-504).  drop_prob = 0.0 (the default) is the reference's phase == 'debug' graph, 0.5 its 'train' phase (SEC.py:81 /
     DSRG.py:128): dropout behind fc6 / fc7 with the keep-masks of (seed, RNG step = self.calls, site, element index) under the
@@ -1085,6 +998,8 @@ class SegTrainer:
                     load_init_model reads (DSRG.py:374-377) -- with the slots under "__momentum__", "__accum__" and the step count
                     (the RNG step of the next call), rate, seed and drop_prob under "__step__" (a file without the last two loads as 0)
     close()         releases everything"""
+    BUFFERS = ("params", "mom", "accum")
+    SLOTS = (("__momentum__", "mom"), ("__accum__", "accum"))
 
     def __init__(self, method, weights, num_classes, precision=_lib.PREC_F16X3, ctx=None, base_lr=1e-4, momentum=0.9, weight_decay=5e-4,
                  accum_num=1, lr_decay=0.5, lr_step=4, min_prob=1e-4, drop_prob=0.0, seed=0):
@@ -1097,37 +1012,25 @@ class SegTrainer:
         self.accum_num, self.lr_decay, self.lr_step = int(accum_num), float(lr_decay), lr_step
         self.lr = np.float32(base_lr)
         self.calls = 0
-        self.params = self.mom = self.accum = None
         self.net = SegNet(method, weights, num_classes, precision=precision, ctx=ctx, min_prob=min_prob)
         self.ctx = self.net.ctx
-        try:
-            flat = self.net.flat_params(weights)
-            self.params = DeviceMaps.from_host(self.ctx, flat)
-            self.mom = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
-            self.accum = DeviceMaps.from_host(self.ctx, np.zeros_like(flat))
-        except Exception:
-            self.close()
-            raise
+        self._init_buffers(lambda: self.net.flat_params(weights))
 
     @property
     def layout(self):
         return self.net._grad.layout
 
+    def _fields(self):
+        return _lib.SegGrad.fields(self.layout)
+
+    def _flat(self, tensors):
+        return self.net.flat_params(tensors)
+
     def close(self):
-        for name in ("params", "mom", "accum"):
-            buf = getattr(self, name, None)
-            if buf is not None:
-                buf.free()
-            setattr(self, name, None)
+        super().close()
         if getattr(self, "net", None) is not None:
             self.net.close()
             self.net = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def lr_at(self, epoch):
         return np.float32(self.base_lr * self.lr_decay ** (epoch // self.lr_step))
@@ -1160,50 +1063,24 @@ class SegTrainer:
         losses["total"] = losses["norm"] + self.weight_decay * l2_value
         return losses, new_cues
 
-    def _unflatten(self, flat):
-        out = {}
-        for layer, e in self.layout.items():
-            shape = (e["k"], e["k"], e["Cin"], e["Cout"])
-            out[layer] = {"w": flat[e["w_off"]:e["w_off"] + int(np.prod(shape))].reshape(shape).copy(),
-                          "b": flat[e["b_off"]:e["b_off"] + e["Cout"]].copy()}
-        return out
+    def _params_dict(self):
+        return self.params_host()
 
-    def params_host(self):
-        return self._unflatten(self.params.to_host())
+    def _step_dict(self):
+        return {"calls": self.calls, "lr": float(self.lr), "seed": self.seed, "drop_prob": self.drop_prob}
 
-    def momentum_host(self):
-        return self._unflatten(self.mom.to_host())
-
-    def save(self, path):
-        d = self.params_host()
-        d["__momentum__"] = self.momentum_host()
-        d["__accum__"] = self._unflatten(self.accum.to_host())
-        d["__step__"] = {"calls": self.calls, "lr": float(self.lr), "seed": self.seed, "drop_prob": self.drop_prob}
-        with open(path, "wb") as fh:  # (np.save appends '.npy' to a bare name, not to a file object)
-            np.save(fh, d, allow_pickle=True)
+    def _set_step(self, step):
+        if step:
+            self.calls, self.lr = int(step["calls"]), np.float32(step["lr"])
 
     @classmethod
     def load(cls, path, method, num_classes, **kwargs):
-        d = np.load(path, encoding="latin1", allow_pickle=True).item()
-        step = d.get("__step__", {})
+        weights, marked = cls._read(path)
+        step = marked.get("__step__", {})
         # (the RNG's seed and drop_prob travel with the file, 0 where it has none; an explicit keyword wins)
         kwargs.setdefault("seed", int(step.get("seed", 0)))
         kwargs.setdefault("drop_prob", float(step.get("drop_prob", 0.0)))
-        tr = cls(method, {k: v for k, v in d.items() if not k.startswith("__")}, num_classes, **kwargs)
-        try:
-            for key, name in (("__momentum__", "mom"), ("__accum__", "accum")):
-                if key in d:
-                    flat = tr.net.flat_params(d[key])  # (a slot has the weights' shapes)
-                    getattr(tr, name).free()
-                    setattr(tr, name, None)
-                    setattr(tr, name, DeviceMaps.from_host(tr.ctx, flat))
-            if "__step__" in d:
-                tr.calls = int(d["__step__"]["calls"])
-                tr.lr = np.float32(d["__step__"]["lr"])
-        except Exception:
-            tr.close()
-            raise
-        return tr
+        return cls(method, weights, num_classes, **kwargs)._resume(marked)
 
 
 class Predictor:
@@ -1518,7 +1395,7 @@ class SegTrainLoop:
                     weights = final if os.path.exists(final) else latest_checkpoint(weights)[0]
                     if weights is None:
                         raise ValueError("SegTrainLoop: the weights directory holds no final-0.npy and no epoch-<i>.npy")
-                weights = {k: v for k, v in np.load(weights, encoding="latin1", allow_pickle=True).item().items() if not k.startswith("__")}
+                weights = SegTrainer._read(weights)[0]
             self.trainer = SegTrainer(method, weights, num_classes, **kwargs)
         self.batcher = SegBatcher(num_classes, img_mean, size=size, seed_size=seed_size, colours=colours, ctx=self.trainer.ctx)
 

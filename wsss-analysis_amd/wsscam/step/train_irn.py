@@ -56,7 +56,7 @@ def _initial_state_dict(args):
     name = getattr(args, "irn_init_weights_name", None)
     if not name:
         raise ValueError("train_irn.run: args.state_dict (or args.irn_init_weights_name) must give the initial EdgeDisplacement state dict")
-    return {k: v for k, v in np.load(name, encoding="latin1", allow_pickle=True).item().items() if not k.startswith("__")}
+    return irn_train.IrnTrainer._read(name)[0]
 
 
 def _infer_batches(pool, batcher, infer_dataset, bs):
