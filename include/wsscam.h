@@ -643,6 +643,34 @@ int wsc_sem_seg_finish(wsc_ctx *ctx, const float *rw_dev, int B, const int64_t *
                        const int32_t *up_hw_host /*[B][2]*/, const int32_t *out_hw_host /*[B][2]*/, const int32_t *keys_host,
                        const int32_t *key_off_host /*[B+1]*/, int has_bg, float bg_thres, uint8_t *label_dev);
 
+/* The should_saveimg debug images of every stage for a ragged batch, in one launch: the colour-coded segmentation and its
+ * overlay on the input image (03c_hsn/demo.py:183-199, :211-232, :395-418; 02_cues/demo.py:433-477, :604-608;
+ * 03a_sec-dsrg/model.py:596-612), from label maps that are already on the device:
+ *   pred_idx = cv2.resize(labels, out_hw, INTER_NEAREST)      cv2's rule as above: min(floor(x * (1. / (out / src))), src - 1)
+ *   pred_segmask = sum_k (pred_idx == k)[..., None] * palette[k];  a label outside [0, n_colours) -- a negative int32, 255 --
+ *                                                             takes other_rgb (zeros in 03c / 02_cues, white in 03a's label2rgb)
+ *   overlay[p][ch] = blend[e][ch][img[p][ch]]                  e = the pixel's palette entry, n_colours for 'other'
+ * Two nearest stages (mid_hw_host given and image b's entry not 0 x 0: src -> mid -> out, 03c_hsn/demo.py:394,411) are composed
+ * per output pixel; no mid-size map is written.  Equal sizes pass the label through.
+ * The blend is a TABLE the host builds with the reference's own numpy expression (wsscam.render.blend_table: the float64
+ * np.uint8((1 - R) * img + R * mask), or 02_cues' float form handed to imsave), uint8 [n_colours + 1][3][256]: the device does
+ * no floating-point blending and so matches numpy for every R.
+ * labels_dev: uint8 (WSC_RENDER_LABELS_U8) or int32 (WSC_RENDER_LABELS_I32), image b's h_b x w_b map at ELEMENT offset
+ * labels_off[b].  colour_dev, and overlay_dev / img_dev when an overlay is wanted (overlay_dev may be NULL; blend_host and
+ * img_dev are then not read): uint8 [out_h][out_w][3] per image at BYTE offset out_off[b], the same offsets in all three
+ * (packed back to back: 3 * pixels; any offsets will do, 16-byte stores are used between an image's unaligned head and tail).
+ * palette_host uint8 [n_colours][3], other_rgb_host uint8 [3].  Asynchronous on the ctx stream; the host arrays are copied
+ * during the call.  WSC_ERR_INVALID, naming the argument, before any launch: a NULL among the required pointers; label_type;
+ * B outside 1 .. 65535; n_colours outside 1 .. 63; a size < 1 (mid: 0 x 0 or both >= 1) or a pixel count beyond int32; a
+ * negative offset. */
+#define WSC_RENDER_LABELS_U8 0
+#define WSC_RENDER_LABELS_I32 1
+int wsc_render_labels(wsc_ctx *ctx, const void *labels_dev, int label_type /* WSC_RENDER_LABELS_* */, int B,
+                      const int32_t *src_hw_host /*[B][2]*/, const int32_t *mid_hw_host /*[B][2] or NULL*/,
+                      const int32_t *out_hw_host /*[B][2]*/, const int64_t *labels_off_host /*[B]*/,
+                      const int64_t *out_off_host /*[B]*/, const uint8_t *palette_host, int n_colours, const uint8_t *other_rgb_host,
+                      const uint8_t *img_dev, const uint8_t *blend_host, uint8_t *colour_dev, uint8_t *overlay_dev);
+
 /* wsc_cam_postprocess (all C classes, every image at H0 x W0) followed by wsc_unary_from_maps, fused: the
  * max-normalised high-resolution maps are never written to HBM, only the unaries are (bit-identical to the
  * two-step path).  Replaces, for a whole batch, make_cam.py:64-76 (upsample to the strided-up size, crop,

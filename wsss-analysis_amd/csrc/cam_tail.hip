@@ -14,6 +14,7 @@
 //   out = lh0*(lw0*a + lw1*b) + lh1*(lw0*c + lw1*d)
 #include "common.h"
 #include "bilerp.h" // src_index, bilerp: shared with cue_seeds.hip
+#include "cv2_nearest.h" // cv2_nearest_inv, cv2_nearest_index: shared with render.hip
 
 #include <algorithm>
 
@@ -385,8 +386,8 @@ __global__ __launch_bounds__(256) void cam_eval_nn_kernel(const float *__restric
     const long long n_out = (long long)job.out_h * job.out_w, n_src = (long long)job.h * job.w;
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n_out; p += (long long)gridDim.x * blockDim.x) {
         const int Y = (int)(p / job.out_w), X = (int)(p - (long long)Y * job.out_w);
-        const int sy = min((int)floor((double)Y * job.inv_y), job.h - 1);
-        const int sx = min((int)floor((double)X * job.inv_x), job.w - 1);
+        const int sy = cv2_nearest_index(Y, job.inv_y, job.h);
+        const int sx = cv2_nearest_index(X, job.inv_x, job.w);
         const long long sp = (long long)sy * job.w + sx;
         int cls;
         if (LABELS) {
@@ -547,9 +548,8 @@ static int eval_nn_jobs(const char *who, int B, const int32_t *src_hw_host, cons
         j.key_base = key_off_host ? key_off_host[b] : 0;
         j.maps_off = maps_off_host[b];
         j.pix_off = pix;
-        // cv2.resize: inv_scale = 1. / (dsize / ssize), both in double
-        j.inv_y = 1.0 / ((double)j.out_h / (double)j.h);
-        j.inv_x = 1.0 / ((double)j.out_w / (double)j.w);
+        j.inv_y = cv2_nearest_inv(j.h, j.out_h);
+        j.inv_x = cv2_nearest_inv(j.w, j.out_w);
         pix += (long long)j.out_h * j.out_w;
         *max_pix = std::max(*max_pix, (long long)j.out_h * j.out_w);
     }

@@ -223,6 +223,7 @@ _SIGNATURES = {
     "wsc_cam_sum_scales": (_i, [_vp, _vp, _i, _i, ctypes.c_longlong, _vp]),
     "wsc_cam_eval_confusion_nn": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "wsc_label_confusion_nn": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "wsc_render_labels": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "wsc_sem_seg_finish": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp]),
     "wsc_bilinear_resize": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
     "wsc_msf_input_u8": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
@@ -1405,6 +1406,28 @@ def label_confusion_nn(ctx, labels_dev, src_sizes, out_sizes, labels_off, gt_dev
     off = np.ascontiguousarray(labels_off, dtype=np.int64)
     check(ctx._lib.wsc_label_confusion_nn(ctx.h, _ptr(labels_dev), B, src_hw.ctypes.data, out_hw.ctypes.data, off.ctypes.data,
                                           _ptr(gt_dev), int(n_class), int(ignore_label), _ptr(pred_dev), _ptr(confusion_dev)))
+
+
+def render_labels(ctx, labels_dev, label_dtype, src_sizes, out_sizes, labels_off, out_off, palette, other_rgb, colour_dev,
+                  mid_sizes=None, img_dev=None, blend=None, overlay_dev=None):
+    """The debug images of a ragged batch (wsc_render_labels): label maps (uint8 or int32, per `label_dtype`) -> cv2 nearest
+    resize in one or two stages -> palette lookup into colour_dev and, with overlay_dev, the blend-table overlay on img_dev.
+    labels_off in elements, out_off in bytes; `blend`: uint8 (n_colours + 1, 3, 256) of wsscam.render.blend_table."""
+    B = len(src_sizes)
+    src_hw, out_hw = _size_table(src_sizes, B), _size_table(out_sizes, B)
+    mid_hw = _size_table(mid_sizes, B) if mid_sizes is not None else None
+    l_off, o_off = np.ascontiguousarray(labels_off, dtype=np.int64), np.ascontiguousarray(out_off, dtype=np.int64)
+    assert l_off.shape == (B,) and o_off.shape == (B,)
+    pal = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 3)
+    other = np.ascontiguousarray(other_rgb, dtype=np.uint8).reshape(3)
+    kind = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1}[np.dtype(label_dtype)]
+    if blend is not None:
+        blend = np.ascontiguousarray(blend, dtype=np.uint8)
+        assert blend.shape == (len(pal) + 1, 3, 256), blend.shape
+    check(ctx._lib.wsc_render_labels(ctx.h, _ptr(labels_dev), kind, B, src_hw.ctypes.data,
+                                     None if mid_hw is None else mid_hw.ctypes.data, out_hw.ctypes.data, l_off.ctypes.data,
+                                     o_off.ctypes.data, pal.ctypes.data, len(pal), other.ctypes.data, _ptr(img_dev), _ptr(blend),
+                                     _ptr(colour_dev), _ptr(overlay_dev)))
 
 
 def sem_seg_finish(ctx, rw_dev, rw_off, khw, up_hw, out_hw, keys_per_image, has_bg, bg_thres, label_dev):

@@ -39,6 +39,12 @@ class _LazyImages:
         return self.set_list.images(sl, sl + 1)[0]
 
 
+def debug_image_names(filenames):
+    """The stems the should_saveimg branches name their files by: `filename.replace('.jpg', '')` (02_cues/demo.py:475-476,
+    03c_hsn/demo.py:196-198) -> `<stem>.png`, `<stem>_overlay.png`."""
+    return [f.replace(".jpg", "") for f in filenames]
+
+
 def read_batch_u8(images, size, ctx=None):
     """The uint8 batch of read_batch: `img_batch = np.empty(..., dtype='uint8'); img_batch[i] = cv2.resize(tmp, size)`
     (02_cues/utilities.py:172-176, 02_cues/adp_cues.py / 03c_hsn/adp_cues.py:122-128, 03c_hsn/utilities.py:170-181) -- OpenCV's
@@ -227,23 +233,28 @@ VOC_SEG_CLASS_NAMES = ["__background__", "aeroplane", "bicycle", "bird", "boat",
                        "diningtable", "dog", "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor"]
 
 
-def cue_label_map(cues_i, n_classes, seed_size=SEED_SIZE, empty_label=0):
+def cue_label_map(cues_i, n_classes, seed_size=SEED_SIZE, empty_label=0, exclusive=False):
     """demo.py:423-427 / :446-451: `cues_pred[cues_i[1], cues_i[2], cues_i[0]] = 1; argmax(cues_pred, -1)` -- the class of every
     seed pixel, `empty_label` where no class claims it (VOC2012: arg-max of an all-zero vector = 0, the background; DeepGlobe:
-    `ignore_ind`, a class outside the scored ones)."""
+    `ignore_ind`, a class outside the scored ones).  `exclusive`: the caller reads the map as the per-class masks themselves (the
+    ADP evaluation and every debug image: `pred_segmask += mask_k * colour_k` is one palette lookup only then), so a pixel that two
+    classes claim is an error here -- the overlap resolution of the seed generation leaves none."""
     cues_i = np.asarray(cues_i)
     pred = np.zeros((seed_size, seed_size, n_classes))
     if cues_i.size:
         pred[cues_i[1], cues_i[2], cues_i[0]] = 1.0
+    assert not exclusive or np.sum(pred, axis=-1).max() <= 1.0, "a seed pixel is claimed by more than one class"
     lab = np.argmax(pred, axis=-1).astype(np.int32)
     lab[np.sum(pred, axis=-1) == 0] = empty_label
     return lab
 
 
-def cue_confusion(ctx, cues, gt_index_maps, n, empty_label, batch_size, is_verbose=False, first_index=0):
+def cue_confusion(ctx, cues, gt_index_maps, n, empty_label, batch_size, is_verbose=False, first_index=0, exclusive=False,
+                  on_batch=None):
     """Confusion counts [gt][pred] of (n + 1) x (n + 1) classes (index n: 'no class') between the cue label maps -- arg-max of
     the one-hot seeds, cv2 nearest-neighbour resized to each ground truth's own size -- and the ground-truth index maps, on the
-    device (wsc_label_confusion_nn).  Every quantity of 02_cues/demo.py:428-433 / :586-597 is a sum over this matrix."""
+    device (wsc_label_confusion_nn).  Every quantity of 02_cues/demo.py:428-433 / :586-597 is a sum over this matrix.
+    `on_batch(lo, hi, lab_dev)`: called per batch with the int32 label maps still on the device (the debug-image writers)."""
     from .. import _lib
 
     conf_dev = ctx.alloc((n + 1) * (n + 1) * 8)
@@ -251,19 +262,23 @@ def cue_confusion(ctx, cues, gt_index_maps, n, empty_label, batch_size, is_verbo
     n_img = len(gt_index_maps)
     for lo in range(0, n_img, batch_size):
         hi = min(lo + batch_size, n_img)
-        labs = [cue_label_map(cues["%d_cues" % (first_index + i)], n, empty_label=empty_label) for i in range(lo, hi)]
+        labs = [cue_label_map(cues["%d_cues" % (first_index + i)], n, empty_label=empty_label, exclusive=exclusive)
+                for i in range(lo, hi)]
         gidx = [np.ascontiguousarray(gt_index_maps[i], dtype=np.uint8) for i in range(lo, hi)]
         lab_dev = ctx.to_device(np.ascontiguousarray(np.stack(labs)), pooled=True)
         gt_dev = ctx.to_device(np.concatenate([g.reshape(-1) for g in gidx]), pooled=True)
         _lib.label_confusion_nn(ctx, lab_dev, [(SEED_SIZE, SEED_SIZE)] * (hi - lo), [g.shape for g in gidx],
                                 [b * SEED_SIZE * SEED_SIZE for b in range(hi - lo)], gt_dev, n + 1, conf_dev, ignore_label=-1)
+        if on_batch is not None:
+            on_batch(lo, hi, lab_dev)
         if is_verbose:
             print("\tImages %d-%d of %d" % (lo + 1, hi, n_img))
     return ctx.to_host(conf_dev, (n + 1, n + 1), np.int64)
 
 
 def eval_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=False, should_saveimg=False, is_verbose=True, *,
-              cues=None, gts=None, colours=None, class_names=None, out_dir=None, ctx=None, settings=None):
+              cues=None, gts=None, colours=None, class_names=None, out_dir=None, ctx=None, settings=None, images=None, names=None,
+              img_out_dir=None):
     """02_cues/demo.py:323-484 for VOC2012 / DeepGlobe: every image's cues -> 41 x 41 class map -> cv2 nearest-neighbour
     resize to the ground truth's size -> per-class intersections and unions over the whole set -> IoU = I / (U + 1e-7), mIoU
     = their mean; written as `metrics_<sess_id>_<set>.csv` (and `.xlsx` when openpyxl is installed, the reference's format).
@@ -272,8 +287,14 @@ def eval_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=
       gts      per image: VOC2012 the class-index map (H, W) uint8 (what `cv2.imread(png)[:, :, 0]` of the reference reads);
                DeepGlobe the colour-coded (H, W, 3) RGB map, matched against `colours`
     Both default to what the reference reads from disk: ./eval/<sess_id>/localization_cues_val.pickle and the PNGs under
-    SegmentationClassAug next to the evaluation images (wsscam.keras_store).  Debug images (`should_saveimg`) are not
-    rendered.  Returns {'intersects', 'unions', 'IoU', 'mIoU', 'classes'}."""
+    SegmentationClassAug next to the evaluation images (wsscam.keras_store).
+    `should_saveimg` (demo.py:467-477): per image `<name>.png` and `<name>_overlay.png` under `img_out_dir` (the settings form:
+    the reference's ./out/<sess_id>), rendered on the device from the label maps the counting pass leaves there
+    (wsc_render_labels): OVERLAY_R 0.75 for VOC2012 and 0.25 for DeepGlobe, the reference's FLOAT form -- pred_segmask / 256.0 and
+    (1 - R) * img / 256.0 + R * pred_segmask / 256.0 handed to imsave (wsscam.render, rule "float256") -- and for DeepGlobe both
+    at `dsize=(shape[0] // 4, shape[1] // 4)`, the image through cv2's 8-bit INTER_LINEAR.  `images` / `names`: the original
+    uint8 RGB images and the file names without '.jpg' (read from disk in the settings form); with in-memory images and no
+    `img_out_dir` nothing is written.  Returns {'intersects', 'unions', 'IoU', 'mIoU', 'classes'}."""
     from .. import _lib
     from ..misc.imutils import default_context
 
@@ -295,6 +316,12 @@ def eval_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=
                         database_dir=st["DATA_ROOT"] if settings is not None else None)
         eval_set = ds.sets[ds.is_evals.index(True)]
         gen_eval = ds.set_gens[eval_set]
+        if should_saveimg and images is None:
+            images = _LazyImages(gen_eval)
+        if should_saveimg and names is None:
+            names = debug_image_names(gen_eval.filenames)
+        if img_out_dir is None:
+            img_out_dir = os.path.join("./out", sess_id)  # demo.py:379
         if cues is None:
             path = os.path.join(eval_dir, "localization_cues_val.pickle")
             if not os.path.exists(path):  # generate first if not already existing (demo.py:398-400)
@@ -304,11 +331,11 @@ def eval_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=
                 cues = pickle.load(f, encoding="iso-8859-1")
         if gts is None:
             gt_dir = os.path.join(os.path.dirname(gen_eval.directory), "SegmentationClassAug")
-            names = [os.path.splitext(f)[0] + ".png" for f in gen_eval.filenames]
+            gt_files = [os.path.splitext(f)[0] + ".png" for f in gen_eval.filenames]  # (not `names`: those name the debug images)
             if dataset == "VOC2012":  # palette PNG: the index IS the class (cv2.imread(...)[:, :, 0] after the colour swap)
-                gts = [np.asarray(Image.open(os.path.join(gt_dir, n))) for n in names]
+                gts = [np.asarray(Image.open(os.path.join(gt_dir, n))) for n in gt_files]
             else:
-                gts = [np.asarray(Image.open(os.path.join(gt_dir, n)).convert("RGB")) for n in names]
+                gts = [np.asarray(Image.open(os.path.join(gt_dir, n)).convert("RGB")) for n in gt_files]
     if dataset == "VOC2012":
         names_c = list(class_names or VOC_SEG_CLASS_NAMES)
         n, empty = len(names_c), 0
@@ -327,7 +354,28 @@ def eval_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=
 
         return gt_index_from_colours(g, colours)
 
-    conf = cue_confusion(ctx, cues, [gt_index(np.asarray(g)) for g in gts], n, empty, batch_size, is_verbose)
+    on_batch = None
+    if should_saveimg and images is not None and img_out_dir is not None:
+        from .. import render
+
+        palette = render.colours_for(dataset) if dataset == "VOC2012" else colours
+        names = list(names) if names is not None else [str(i) for i in range(len(gts))]
+
+        def on_batch(lo, hi, lab_dev):
+            origs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images[lo:hi]]
+            gt_hw = [np.asarray(gts[i]).shape[:2] for i in range(lo, hi)]
+            if dataset == "VOC2012":
+                mids, outs, imgs = None, gt_hw, origs
+            else:  # demo.py:471-474: image and coloured mask to a quarter, the mask through the ground truth's size
+                mids, outs = gt_hw, [render.quarter_size(hw) for hw in gt_hw]
+                imgs = render.resize_u8_grouped(ctx, origs, [render.quarter_size(im.shape) for im in origs])
+            cols, overs = render.render_labels(ctx, lab_dev, [(SEED_SIZE, SEED_SIZE)] * (hi - lo), outs, palette, (0, 0, 0), mid_sizes=mids,
+                                               images=imgs, overlay_r=0.75 if dataset == "VOC2012" else 0.25, rule="float256",
+                                               label_dtype=np.int32)
+            for name, c, o in zip(names[lo:hi], cols, overs):
+                render.save_pair(img_out_dir, name, c, o)
+
+    conf = cue_confusion(ctx, cues, [gt_index(np.asarray(g)) for g in gts], n, empty, batch_size, is_verbose, on_batch=on_batch)
     inter = np.diag(conf)[:n].astype(np.float64)
     union = conf[:n, :].sum(1) + conf[:, :n].sum(0) - inter  # (gt == k) | (pred == k) over every pixel
     iou = inter / (union + 1e-7)
@@ -348,7 +396,7 @@ def eval_cues(dataset, model_type, thresh, batch_size, set_name=None, run_train=
 
 
 def eval_cues_adp(model_type, sess_id, batch_size, size, set_name, should_saveimg=False, is_verbose=True, *, model, alpha,
-                  thresholds, images, gts, thresh=0.2, all_classes=None, out_dir=None):
+                  thresholds, images, gts, thresh=0.2, all_classes=None, out_dir=None, names=None, img_out_dirs=None):
     """02_cues/demo.py:487-640 (ADP): the seeds of gen_cues_adp for both HTT types, then per type and class
     `pred_mask = cv2.resize(cues[:, :, k], (size, size), INTER_NEAREST) == 1` against the colour-coded ground truth:
     intersects, unions, predicted_totals, gt_totals over the set; IoU = I / U (no epsilon: NaN for a class that never occurs,
@@ -356,23 +404,41 @@ def eval_cues_adp(model_type, sess_id, batch_size, size, set_name, should_saveim
     names for these two ratios, kept -- and their means; `metrics_ADP-<htt>_<set>_<model>.csv` (+ `.xlsx` with openpyxl).
     `gts` {'morph': [...], 'func': [...]}: (size, size, 3) RGB ground-truth maps (ADPCues.read_gt_batch).  The one-hot seeds are
     exclusive after the overlap resolution, so the per-class masks are one label map and all four sums come from one confusion
-    matrix on the device.  Debug images are not rendered."""
+    matrix on the device (the label map asserts that exclusiveness where it is made).
+    `should_saveimg` (:604-608) with `img_out_dirs` {'morph': dir, 'func': dir} (the reference: ./out/<sess_id>/<htt>) and `names`:
+    `<name>.png` = np.uint8(pred_segmask) and `<name>_overlay.png` = np.uint8(0.25 * img_batch[j] + 0.75 * pred_segmask) against
+    the batch image at (size, size) -- ADPCues.read_batch's uint8 batch --, rendered on the device (wsc_render_labels)."""
     from ..hsn.demo import ADPClasses, gt_index_from_colours
     from ..step.eval_cam import ADP_CLS_COLOURS
 
     cues = gen_cues_adp(model_type, thresh, batch_size, size, None, set_name, is_verbose, model=model, alpha=alpha,
                         thresholds=thresholds, images=images, all_classes=all_classes)
     ac = ADPClasses(all_classes)
+    if should_saveimg and img_out_dirs is not None:
+        names = [str(i) for i in range(len(images))] if names is None else list(names)
+        if len(names) != len(images):
+            raise ValueError("eval_cues_adp: %d names for %d images" % (len(names), len(images)))
     eval_dir = out_dir or os.path.join("./eval", sess_id)
     os.makedirs(eval_dir, exist_ok=True)
     out = {}
     for htt in ("morph", "func"):
         colours = [tuple(int(v) for v in c) for c in ADP_CLS_COLOURS[htt]]
-        names = ac.classes["valid_" + htt]
+        names_c = ac.classes["valid_" + htt]  # (the class names; `names` are the images' file names)
         n = len(colours)
-        assert n == len(names)
+        assert n == len(names_c)
         gidx = [gt_index_from_colours(np.asarray(g), colours) for g in gts[htt]]
-        conf = cue_confusion(model.ctx, cues[htt], gidx, n, n, batch_size)
+        on_batch = None
+        if should_saveimg and img_out_dirs is not None:
+            from .. import render
+
+            def on_batch(lo, hi, lab_dev, htt=htt, colours=colours):
+                raw = read_batch_u8(images[lo:hi], (size, size), ctx=model.ctx)
+                cols, overs = render.render_labels(model.ctx, lab_dev, [(SEED_SIZE, SEED_SIZE)] * (hi - lo), [(size, size)] * (hi - lo),
+                                                   colours, (0, 0, 0), images=list(raw), overlay_r=0.75, label_dtype=np.int32)
+                for name, c, o in zip(names[lo:hi], cols, overs):
+                    render.save_pair(img_out_dirs[htt], os.path.splitext(name)[0], c, o)
+
+        conf = cue_confusion(model.ctx, cues[htt], gidx, n, n, batch_size, exclusive=True, on_batch=on_batch)
         inter = np.diag(conf)[:n].astype(np.float64)
         gt_tot, pred_tot = conf[:n, :].sum(1).astype(np.float64), conf[:, :n].sum(0).astype(np.float64)
         union = gt_tot + pred_tot - inter
@@ -380,19 +446,19 @@ def eval_cues_adp(model_type, sess_id, batch_size, size, set_name, should_saveim
             iou = inter / union
         prec, rec = inter / (gt_tot + 1e-5), inter / (pred_tot + 1e-5)
         out[htt] = {"intersects": inter, "unions": union, "gt_totals": gt_tot, "predicted_totals": pred_tot, "IoU": iou,
-                    "Precision": prec, "Recall": rec, "mIoU": float(np.mean(iou)), "classes": list(names)}
+                    "Precision": prec, "Recall": rec, "mIoU": float(np.mean(iou)), "classes": list(names_c)}
         if is_verbose:
             print("\tmIoU (%s): %s" % (htt, out[htt]["mIoU"]))
         base = os.path.join(eval_dir, "metrics_ADP-" + htt + "_" + str(set_name) + "_" + model_type)
         with open(base + ".csv", "w") as f:
             f.write(",Class,IoU,Precision,Recall\n")
-            rows = zip(list(names) + ["Mean"], list(iou) + [np.mean(iou)], list(prec) + [np.mean(prec)], list(rec) + [np.mean(rec)])
+            rows = zip(list(names_c) + ["Mean"], list(iou) + [np.mean(iou)], list(prec) + [np.mean(prec)], list(rec) + [np.mean(rec)])
             for k, (c, a, b, d) in enumerate(rows):
                 f.write("%d,%s,%r,%r,%r\n" % (k, c, float(a), float(b), float(d)))
         try:
             import pandas as pd
 
-            pd.DataFrame({"Class": list(names) + ["Mean"], "IoU": list(iou) + [np.mean(iou)], "Precision": list(prec) + [np.mean(prec)],
+            pd.DataFrame({"Class": list(names_c) + ["Mean"], "IoU": list(iou) + [np.mean(iou)], "Precision": list(prec) + [np.mean(prec)],
                           "Recall": list(rec) + [np.mean(rec)]}, columns=["Class", "IoU", "Precision", "Recall"]).to_excel(base + ".xlsx")
         except Exception:
             pass

@@ -4,7 +4,8 @@ size -> foreground/background combination (VOC: bg channel 0.15 * expit(max_batc
 -> label maps.  `segment(dataset, model_type, batch_size)` alone loads models and the evaluation image list from settings.ini's
 MODEL_ROOT / DATA_ROOT like the reference (wsscam.keras_store); callers that hold the objects pass them keyword-only:
   models {'fg': CAM wrapper[, 'bg': CAM wrapper]}, alphas {'fg': (F,C)[, 'bg']}, images: list of uint8 RGB.
-Returns the list of (S, S) int64 label maps (what the reference feeds its evaluation / image writers)."""
+Returns the list of (S, S) int64 label maps (what the reference feeds its evaluation / image writers).  `should_saveimg` with
+an output directory writes the reference's debug images, rendered on the device (wsscam.render, wsc_render_labels)."""
 import math
 import os
 
@@ -12,7 +13,7 @@ import numpy as np
 import scipy.special
 
 from ..cues import utilities as cu
-from ..cues.demo import read_batch_u8
+from ..cues.demo import debug_image_names, read_batch_u8
 from . import utilities as hu
 
 
@@ -24,8 +25,16 @@ def dcrf_config_for(dataset, model_type):
 
 
 def segment(dataset, model_type, batch_size, set_name=None, should_saveimg=True, is_verbose=True, *, models=None, alphas=None,
-            images=None, n_seg_classes=None, settings=None, reference_normalize_quirk=None):
-    """`reference_normalize_quirk`: the reference's VOC2012 normalisation (03c_hsn/utilities.py:142-146) runs
+            images=None, n_seg_classes=None, settings=None, reference_normalize_quirk=None, out_dir=None, names=None, colours=None):
+    """`should_saveimg` (03c_hsn/demo.py:193-199 VOC2012, :223-232 DeepGlobe): per image `<name>.png`, the colour-coded label
+    map, and `<name>_overlay.png`, its blend with the original image, under `out_dir` -- VOC2012 at the original image's size
+    with OVERLAY_R 0.75; DeepGlobe with 0.25 and both at a quarter of it (the image through cv2's 8-bit INTER_LINEAR,
+    wsc_resize_u8, the label map through two nearest stages).  `names` default to the evaluation list's file names without
+    '.jpg' (the settings form) or to the image's index; `colours` to get_colours(dataset).  From the settings form `out_dir`
+    defaults to the reference's ./out/<sess_id>; a call with in-memory images and no `out_dir` writes nothing.  The label maps
+    returned do not depend on the flag.
+
+    `reference_normalize_quirk`: the reference's VOC2012 normalisation (03c_hsn/utilities.py:142-146) runs
     `x[:, :, 0] -= 104; x[:, :, 1] -= 117; x[:, :, 2] -= 123` on the 4-D uint8 BATCH -- that indexes image COLUMNS 0..2 of
     every row and channel, wraps around in uint8, and works in place, so the array later handed to the CRF is modified
     too; the result is divided by 255.  This arithmetic is the DEFAULT (True): the package is a drop-in, its VOC2012 label
@@ -56,6 +65,10 @@ def segment(dataset, model_type, batch_size, set_name=None, should_saveimg=True,
         if images is None:
             ds = ks.Dataset(data_type=dataset, size=img_size, batch_size=batch_size, database_dir=st["DATA_ROOT"], layout="hsn")
             images = _LazyImages(ds.set_gens[ds.sets[ds.is_evals.index(True)]])
+            if names is None:
+                names = debug_image_names(images.set_list.filenames)
+        if out_dir is None:
+            out_dir = os.path.join("./out", sess_id)  # demo.py:68
         if models is None:
             models, alphas = {}, {}
             for m in (["fg", "bg"] if dataset == "VOC2012" else ["fg"]):  # demo.py:80-85: one directory, both modes
@@ -74,6 +87,9 @@ def segment(dataset, model_type, batch_size, set_name=None, should_saveimg=True,
                                               if reference_normalize_quirk else "per channel (x - [104, 117, 123]) / 255"))
     mean, std = ([104, 117, 123], [255, 255, 255]) if voc else ([0, 0, 0], [255, 255, 255])
     cfg = dcrf_config_for(dataset, model_type)
+    save = bool(should_saveimg) and out_dir is not None
+    if save and names is None:
+        names = [str(i) for i in range(len(images))]
     out = []
     N = img_size * img_size
     n_batches = math.ceil(len(images) / batch_size)
@@ -114,10 +130,46 @@ def segment(dataset, model_type, batch_size, set_name=None, should_saveimg=True,
         _lib.hsn_class_mass(ctx, y_dev, B * Cv, N, mass_dev)
         mass = ctx.to_host(mass_dev, (B, Cv), np.uint32)
         mass[:, [c for c in range(Cv) if c not in valid]] = 0
-        out.extend(list(hu.dcrf_process_device(ctx, y_dev, mass, raw_u8, Cv, img_size, img_size, cfg)))
+        kept = [] if save else None
+        labs = list(hu.dcrf_process_device(ctx, y_dev, mass, raw_u8, Cv, img_size, img_size, cfg, keep_dev=kept))
+        out.extend(labs)
+        if save:
+            save_debug_images(ctx, dataset, labs, chunk, names[lo:hi], out_dir, colours, on_device=kept)
         if is_verbose:
             print("\tBatch #%d of %d" % (ib + 1, n_batches))
     return out
+
+
+def device_label_maps(label_maps, on_device):
+    """What render_labels takes for a batch of the CRF's label maps: (the uint8 maps dcrf_process_device left on the device, uint8)
+    when every image of the batch is among them (`on_device`: its keep_dev list), else -- an image without a passing class
+    has no map there -- (the host maps as np.uint8(Y_crf) does them, None)."""
+    if on_device and len(on_device[0][1]) == len(label_maps):
+        return on_device[0][0], np.uint8
+    return [np.asarray(m).astype(np.uint8).astype(np.int32) for m in label_maps], None  # np.uint8(Y_crf[iter_file])
+
+
+def save_debug_images(ctx, dataset, label_maps, originals, names, out_dir, colours=None, on_device=None):
+    """The should_saveimg branch of 03c_hsn/demo.py:175-232 for one batch: `pred_idx = cv2.resize(np.uint8(Y_crf), original size,
+    INTER_NEAREST)`, the per-class colouring, and np.uint8((1 - OVERLAY_R) * orig_img + OVERLAY_R * pred_segmask) -- one launch.
+    DeepGlobe: both at `dsize=(shape[0] // 4, shape[1] // 4)` (render.quarter_size), the label map through the original size.
+    `on_device`: dcrf_process_device's keep_dev list -- the launch then reads the label maps where the CRF left them."""
+    from .. import render
+
+    voc = dataset == "VOC2012"
+    colours = render.colours_for(dataset) if colours is None else colours
+    origs = [np.ascontiguousarray(im, dtype=np.uint8) for im in originals]
+    maps, dtype = device_label_maps(label_maps, on_device)
+    if voc:
+        mids, outs, imgs = None, [im.shape[:2] for im in origs], origs
+    else:
+        mids = [im.shape[:2] for im in origs]
+        outs = [render.quarter_size(im.shape) for im in origs]
+        imgs = render.resize_u8_grouped(ctx, origs, outs)  # cv2.resize(orig_img, dsize): INTER_LINEAR, 8-bit
+    cols, overs = render.render_labels(ctx, maps, [np.asarray(m).shape for m in label_maps], outs, colours, (0, 0, 0), mid_sizes=mids,
+                                       images=imgs, overlay_r=0.75 if voc else 0.25, label_dtype=dtype)
+    for name, c, o in zip(names, cols, overs):
+        render.save_pair(out_dir, name, c, o)
 
 
 # ---- ADP (03c_hsn/demo.py:271-407 with the class bookkeeping of 03c_hsn/adp_cues.py:20-58) --------------------------
@@ -184,7 +236,7 @@ def run_batches_on_lanes(n_batches, ctxs, one_batch):
 
 
 def segment_adp(model, alpha, thresholds, images, dcrf_configs, size, batch_size, is_verbose=False, all_classes=None, stats=None,
-                n_lanes=3, chain_stacks=False):
+                n_lanes=3, chain_stacks=False, should_saveimg=False, out_dirs=None, names=None, eval_size=(1088, 1088)):
     """demo.py:271-380 for one ADP model: per batch scores >= thresholds -> HSN Grad-CAM at (size, size) -> per
     HTT type {morph, func}: scatter into the valid-class stack, modify_by_htt (background / other channels),
     get_cs_gradcam, dense CRF with that type's configuration.  `images` are uint8 RGB (any size; resized like
@@ -197,7 +249,11 @@ def segment_adp(model, alpha, thresholds, images, dcrf_configs, size, batch_size
     classes with mass -- the M its dense CRF ran with (dcrf_process keeps the classes whose maps are not all zero, :425).
     `n_lanes` batches are in flight at once, each on its own stream (run_batches_on_lanes); a batch's results do not depend
     on the lane it ran on.  `chain_stacks`: the lanes' VGG16 passes take turns on the device (_lib.StackChain) -- measured neutral
-    here (1067-1140 against 1053-1181 images/s, profiles/r06_chain_ab.txt: a batch is mostly CRF), so off by default."""
+    here (1067-1140 against 1053-1181 images/s, profiles/r06_chain_ab.txt: a batch is mostly CRF), so off by default.
+    `should_saveimg` with `out_dirs` {'morph': dir, 'func': dir} and `names`: the debug images of demo.py:408-418 per HTT type,
+    `<name>.png` and `<name>_overlay.png` (OVERLAY_R 0.75) at the original image's size -- the label map goes through the two
+    nearest stages of :394 and :411, (size, size) -> eval_size -> original, composed on the device (wsc_render_labels).  A run
+    that also evaluates can let LabelEvaluator.update write the same files from its resized prediction instead."""
     from .. import _lib
 
     ac = ADPClasses(all_classes)
@@ -208,6 +264,11 @@ def segment_adp(model, alpha, thresholds, images, dcrf_configs, size, batch_size
     # stack's channels 18..20 = S.R, A.W, A.B (off by one; the 02_cues twin has the same line, demo.py:307-308).  Reproduced:
     # those channels of the valid stack, traced back to their source channels of the all-class stack (a quirk found in round 5).
     adipose_all = adipose_source_channels(ac)
+    save = bool(should_saveimg) and out_dirs is not None
+    if save:
+        names = [str(i) for i in range(len(images))] if names is None else list(names)
+        if len(names) != len(images):
+            raise ValueError("segment_adp: %d names for %d images" % (len(names), len(images)))
     bounds = [(lo, min(lo + batch_size, len(images))) for lo in range(0, len(images), batch_size)]
     model.gradcam_net(np.asarray(alpha))  # (built once, before the lanes' threads ask for it)
     # several batches in flight: their VGG16 stacks take turns on the device, everything else of a batch overlaps (_lib.StackChain)
@@ -236,7 +297,19 @@ def segment_adp(model, alpha, thresholds, images, dcrf_configs, size, batch_size
                                 adipose_all if htt == "func" else None, cs_dev, None, mass_dev)
             mass = ctx.to_host(mass_dev, (B, Cv), np.uint32)
             res["stats"][htt] = [int(v) for v in (mass > 0).sum(1)]
-            res[htt] = list(hu.dcrf_process_device(ctx, cs_dev, mass, raw, Cv, size, size, dcrf_configs[htt]))
+            kept = [] if save else None
+            res[htt] = list(hu.dcrf_process_device(ctx, cs_dev, mass, raw, Cv, size, size, dcrf_configs[htt], keep_dev=kept))
+            if save:
+                from .. import render
+
+                origs = [np.ascontiguousarray(im, dtype=np.uint8) for im in chunk]
+                outs = [(im.shape[1], im.shape[0]) for im in origs]  # dsize=(shape[0], shape[1]) is (width, height): :411, literally
+                assert all(im.shape[:2] == o for im, o in zip(origs, outs)), "the reference blends a (W, H) mask with an (H, W) image"
+                maps, dtype = device_label_maps(res[htt], kept)
+                cols, overs = render.render_labels(ctx, maps, [(size, size)] * B, outs, render.colours_for("ADP-" + htt), (0, 0, 0),
+                                                   mid_sizes=[tuple(eval_size)] * B, images=origs, overlay_r=0.75, label_dtype=dtype)
+                for name, c, o in zip(names[lo:hi], cols, overs):
+                    render.save_pair(out_dirs[htt], name, c, o)
         if is_verbose:
             print("\tBatch %d-%d" % (lo, hi))
         return res
@@ -278,18 +351,37 @@ class LabelEvaluator:
 
         _lib.check(ctx._lib.wsc_memset(ctx.h, self.conf_dev.ptr, 0, (self.n + 1) * (self.n + 1) * 8))
 
-    def update(self, label_maps, gt_rgb, want_pred=False):
+    def update(self, label_maps, gt_rgb, want_pred=False, *, saveimg_dir=None, images=None, names=None, overlay_r=0.75):
+        """`saveimg_dir` with the batch's original `images` (uint8 RGB) and `names`: the should_saveimg branch of demo.py:408-418 --
+        `<name>.png` and `<name>_overlay.png`, rendered on the device from the resized prediction this pass leaves there
+        (pred_dev: the second nearest stage and the colouring start from it, nothing is downloaded but the finished images).
+        The reference's `dsize=(orig_img.shape[0], orig_img.shape[1])` is restated literally: cv2's dsize is (width, height),
+        so the rendered images are as wide as the original is high -- moot on ADP's square patches, an error in the
+        reference's blend otherwise."""
         from .. import _lib
 
+        save = saveimg_dir is not None
+        if save:
+            from .. import render
+
+            origs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+            outs = [(im.shape[1], im.shape[0]) for im in origs]
+            assert all(im.shape[:2] == o for im, o in zip(origs, outs)), "the reference blends a (W, H) mask with an (H, W) image"
+            assert len(origs) == len(label_maps) == len(names)
         B = len(label_maps)
         lab = np.ascontiguousarray(np.stack([np.asarray(m) for m in label_maps]).astype(np.int32))
         h, w = lab.shape[1:]
         gt = np.ascontiguousarray(np.stack([gt_index_from_colours(g, self.colours) for g in gt_rgb]))
         assert gt.shape == (B,) + self.out_size, (gt.shape, self.out_size)
         lab_dev, gt_dev = self.ctx.to_device(lab, pooled=True), self.ctx.to_device(gt, pooled=True)
-        pred_dev = self.ctx.alloc(B * self.out_size[0] * self.out_size[1], pooled=True) if want_pred else None
+        pred_dev = self.ctx.alloc(B * self.out_size[0] * self.out_size[1], pooled=True) if want_pred or save else None
         _lib.label_confusion_nn(self.ctx, lab_dev, [(h, w)] * B, [self.out_size] * B, [b * h * w for b in range(B)], gt_dev,
                                 self.n + 1, self.conf_dev, pred_dev=pred_dev, ignore_label=255)
+        if save:
+            cols, overs = render.render_labels(self.ctx, pred_dev, [self.out_size] * B, outs, self.colours, (0, 0, 0), images=origs,
+                                               overlay_r=overlay_r, label_dtype=np.uint8)
+            for name, c, o in zip(names, cols, overs):
+                render.save_pair(saveimg_dir, name, c, o)
         if want_pred:
             return self.ctx.to_host(pred_dev, (B,) + self.out_size, np.uint8)
 

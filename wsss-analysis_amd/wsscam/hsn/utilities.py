@@ -134,12 +134,14 @@ def get_cs_gradcam(gradcam, classes, htt_class, ctx=None):
     return ctx.to_host(cs_dev, (B, Cv, Hh, Ww), np.float32).astype(gradcam.dtype if gradcam.dtype.kind == "f" else np.float64)
 
 
-def dcrf_process_device(ctx, cs_dev, mass, rgb_host, Cv, H, W, config):
+def dcrf_process_device(ctx, cs_dev, mass, rgb_host, Cv, H, W, config, keep_dev=None):
     """dcrf_process (03c_hsn/utilities.py:399-445) on class-specific maps that are already in HBM: per image the
     classes with positive mass (`mass` (B, Cv) from wsc_hsn_cs_gradcam, :425), unaries gathered on the device (:431),
     ONE ragged CRF object for the batch -- every image runs with its own class count len(pass_inds[i]), as the reference's
     per-image DenseCRF2D does (wsc_crf_v; round 3 ran one wsc_crf per distinct class count: 13 loops for 16 patches) --
-    and the arg-max mapped back through each image's class list.  -> (B, H, W) int64."""
+    and the arg-max mapped back through each image's class list.  -> (B, H, W) int64.
+    keep_dev: a list that receives (the uint8 label maps on the device, one H x W map per image of `idxs`, back to back; idxs) --
+    what the debug-image renderer starts from; nothing is appended when no image has a passing class."""
     gauss_sxy, gauss_compat, bilat_sxy, bilat_srgb, bilat_compat, n_infer = config
     B = mass.shape[0]
     N = H * W
@@ -168,6 +170,8 @@ def dcrf_process_device(ctx, cs_dev, mass, rgb_host, Cv, H, W, config):
         conf_dev = ctx.alloc(Bv * N, pooled=True)
         _lib.ir_label_combine(ctx, a_dev, None, keys, N, conf_dev)
         out[idxs] = ctx.to_host(conf_dev, (Bv, H, W), np.uint8)
+        if keep_dev is not None:
+            keep_dev.append((conf_dev, idxs))
     finally:
         d.close()
     return out

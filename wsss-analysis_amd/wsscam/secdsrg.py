@@ -372,9 +372,21 @@ class SegEvaluator:
     crf_config: {g_sxy, g_compat, bi_sxy, bi_srgb, bi_compat, iterations} (model.crf_config_test).
     crf=False: the is_eval=False pass (:666-669, :698-719) -- no resize and no CRF, the arg-max of the map as it is against a
     ground truth of the map's size; crf_config, resize_after_crf and update()'s images are not used.
-    The matrix stays on the device over the whole run; metrics() downloads it."""
+    The matrix stays on the device over the whole run; metrics() downloads it.
 
-    def __init__(self, num_classes, crf_config, colours=None, resize_after_crf=False, ctx=None, crf=True):
+    saveimg_dir (eval_miou's saveimg_dir with single_crf_metrics, model.py:596-612, the is_eval pass): update(..., ids=...) writes
+    per image `<id>_img.png` (the image at the ground truth's size), `<id>_pred.png` (label2rgb of the arg-max) and
+    `<id>_output.png` (should_overlay: np.uint8(0.25 * img + 0.75 * label2rgb), else the colour map again), the colour map and the
+    overlay rendered on the device from the label maps the counting pass reads (wsc_render_labels).  quarter_size=True is the
+    DeepGlobe branch (:597-600): image (cv2's 8-bit INTER_LINEAR) and map (nearest; a nearest resize of the marginals commutes
+    with their arg-max) at `dsize=(shape[0] // 4, shape[1] // 4)`.  palette: the dataset's label2rgb_colors (:95-140), default
+    `colours`.  model.label2rgb hands skimage's label2rgb `colors=label2rgb_colors[unique labels present]`; skimage cycles through
+    that list in the order of the labels it finds, so label k gets label2rgb_colors[k]: a plain palette lookup for every label
+    below category_num -- the only ones an arg-max over category_num channels gives.  (skimage is not installed where this package
+    was developed: that reading of label2rgb is UNPINNED)"""
+
+    def __init__(self, num_classes, crf_config, colours=None, resize_after_crf=False, ctx=None, crf=True, saveimg_dir=None,
+                 should_overlay=False, quarter_size=False, palette=None):
         self.ctx = ctx or default_context()
         self.C = int(num_classes)
         if not 1 <= self.C <= 32:
@@ -385,6 +397,10 @@ class SegEvaluator:
             raise ValueError("SegEvaluator: %d colours for %d classes" % (len(self.colours), self.C))
         self.resize_after_crf = bool(resize_after_crf)
         self.crf = bool(crf)
+        self.saveimg_dir, self.should_overlay, self.quarter_size = saveimg_dir, bool(should_overlay), bool(quarter_size)
+        self.palette = self.colours if palette is None else [tuple(int(v) for v in c) for c in palette]
+        if saveimg_dir is not None and (self.palette is None or len(self.palette) != self.C):
+            raise ValueError("SegEvaluator: saveimg_dir needs a palette of %d colours (label2rgb_colors)" % self.C)
         nbytes = (self.C + 1) * (self.C + 1) * 8
         self.conf_dev = self.ctx.alloc(nbytes, pooled=True)
         _lib.check(self.ctx._lib.wsc_memset(self.ctx.h, self.conf_dev.ptr, 0, nbytes))
@@ -404,14 +420,18 @@ class SegEvaluator:
         maps = [np.ascontiguousarray(p, dtype=np.float32) for p in probs]
         return maps, [tuple(m.shape[:2]) for m in maps]
 
-    def update(self, probs, images, gts, want_pred=False):
+    def update(self, probs, images, gts, want_pred=False, ids=None, orig_images=None):
         """probs[b] (h_b, w_b, C) float32 softmax (> 0) -- a list of host arrays, or ONE DeviceMaps (B, h, w, C) that is read in
         place (no upload); images[b] (H, W, 3) uint8 -- host arrays, or a uint8 DeviceMaps: (B, H, W, 3), or the packed ragged
         batch SegNet.preprocess_dev(keep_images=True) returns; gts[b] as seg_gt_index takes it (crf=False: or one uint8 DeviceMaps
         (B, h, w) of class indices, SegBatcher.val_batch's).
+        ids (with saveimg_dir): the images' names, the debug images are written (an entry that is None is skipped: the
+        reference's `j != 0` rule, :722); orig_images[b]: the decoded RGB image the reference re-reads from disk for them (:672,
+        default `images`), brought to the ground truth's size; with crf=False the uint8 image to show at the map's size
+        (:667 `np.uint8(img[j] + self.img_mean)`), required there.
         -> with want_pred the list of (H_b, W_b) uint8 label maps at the ground truths' sizes, else None."""
         if not self.crf:
-            return self._update_argmax(probs, gts, want_pred)
+            return self._update_argmax(probs, gts, want_pred, ids, orig_images)
         ctx, C, cfg = self.ctx, self.C, self.cfg
         dev_imgs = isinstance(images, DeviceMaps)
         B = probs.shape[0] if isinstance(probs, DeviceMaps) else len(probs)
@@ -502,12 +522,43 @@ class SegEvaluator:
             else:
                 crf.inference(u_ptr, [C] * B, cfg["g_compat"], cfg["bi_compat"], int(cfg["iterations"]),
                               argmax_ptrs=[lab_dev.ptr + int(out_off[b]) * 4 for b in range(B)])
-            return self._count(lab_dev, out_hw, out_off, u8_dev.ptr + gt_at, want_pred, dev)
+            res = self._count(lab_dev, out_hw, out_off, u8_dev.ptr + gt_at, want_pred, dev)
+            if self.saveimg_dir is not None and ids is not None:
+                if orig_images is None:
+                    orig_images = imgs if imgs is not None else [ctx.to_host(img_ptr + img_at[b], img_hw[b] + (3,), np.uint8) for b in range(B)]
+                self._save_images(lab_dev, out_hw, out_off, orig_images, ids)
+            return res
         finally:
             if crf is not None:
                 crf.close()
             for d in bufs:
                 d.free()
+
+    def _save_images(self, lab_dev, out_hw, out_off, orig_images, ids):
+        """single_crf_metrics (model.py:596-612) for a batch whose int32 label maps lie at the ground truths' sizes on the device"""
+        import os
+
+        from . import render
+
+        ctx = self.ctx
+        keep = [b for b, id_ in enumerate(ids) if id_ is not None]
+        if not keep:
+            return
+        ids, orig_images = [ids[b] for b in keep], [orig_images[b] for b in keep]
+        out_hw, lab_off = [tuple(int(v) for v in out_hw[b]) for b in keep], [int(out_off[b]) for b in keep]
+        shown = render.resize_u8_grouped(ctx, orig_images, out_hw)  # :687 / :696 (a copy at equal sizes)
+        show_hw = out_hw
+        if self.quarter_size:
+            show_hw = [render.quarter_size(hw) for hw in out_hw]
+            shown = render.resize_u8_grouped(ctx, shown, show_hw)
+        cols, overs = render.render_labels(ctx, lab_dev, out_hw, show_hw, self.palette, (255, 255, 255), overlay_r=0.75, label_dtype=np.int32,
+                                           images=shown if self.should_overlay else None, labels_off=lab_off)
+        os.makedirs(self.saveimg_dir, exist_ok=True)
+        for b, id_ in enumerate(ids):
+            id_ = id_.decode() if isinstance(id_, bytes) else str(id_)
+            render.save_png(os.path.join(self.saveimg_dir, "%s_img.png" % id_), shown[b])
+            render.save_png(os.path.join(self.saveimg_dir, "%s_output.png" % id_), overs[b] if self.should_overlay else cols[b])
+            render.save_png(os.path.join(self.saveimg_dir, "%s_pred.png" % id_), cols[b])
 
     def _count(self, lab_dev, out_hw, out_off, gt_ptr, want_pred, dev):
         """int32 labels at the ground truths' sizes -> the confusion matrix (accumulated) and, with want_pred, the uint8 maps"""
@@ -521,7 +572,7 @@ class SegEvaluator:
             return [flat[out_off[b]:out_off[b + 1]].reshape(out_hw[b]) for b in range(len(out_hw))]
         return None
 
-    def _update_argmax(self, probs, gts, want_pred):
+    def _update_argmax(self, probs, gts, want_pred, ids=None, orig_images=None):
         """crf=False: np.argmax(pred_curr, axis=-1) of the map as it is (first maximum: wsc_seg_resize_argmax at equal sizes, on
         the class-major planes wsc_seg_planes_from_nhwc writes) and the same counting.  gts may also be ONE uint8 DeviceMaps
         (B, h, w) of class indices in [0, num_classes] (SegBatcher.val_batch): it is counted against where it lies, no host copy
@@ -566,7 +617,12 @@ class SegEvaluator:
                     _lib.seg_planes_from_nhwc(ctx, prob_ptr + o, 1, C, n_pix[b], planes.ptr + o)
             lab_dev = dev(ctx.alloc(int(out_off[-1]) * 4, pooled=True))
             _lib.seg_resize_argmax(ctx, planes, C, src_hw, src_hw, out_off[:-1] * C, out_off[:-1], lab_dev)
-            return self._count(lab_dev, src_hw, out_off, gt_ptr, want_pred, dev)
+            res = self._count(lab_dev, src_hw, out_off, gt_ptr, want_pred, dev)
+            if self.saveimg_dir is not None and ids is not None:
+                if orig_images is None or len(orig_images) != B or len(ids) != B:
+                    raise ValueError("SegEvaluator.update: without the CRF the debug images need %d ids and orig_images" % B)
+                self._save_images(lab_dev, src_hw, out_off, orig_images, ids)
+            return res
         finally:
             for d in bufs:
                 d.free()
@@ -1096,7 +1152,7 @@ class Predictor:
     precision, ctx, weights: as SegNet takes them;  crf_config_test, colours: as SegEvaluator."""
 
     def __init__(self, method, weights, num_classes, crf_config_test, img_mean, size=(321, 321), colours=None, resize_after_crf=False,
-                 precision=_lib.PREC_F16X3, ctx=None):
+                 precision=_lib.PREC_F16X3, ctx=None, saveimg_dir=None, should_overlay=True, palette=None):
         self.ctx = ctx or default_context()
         self.size = (int(size[0]), int(size[1]))
         self.img_mean = np.asarray(img_mean, dtype=np.float32).reshape(3)
@@ -1104,13 +1160,17 @@ class Predictor:
         self.net = self.ev = None
         self.net = SegNet(method, weights, num_classes, precision=precision, ctx=self.ctx)
         try:
-            self.ev = SegEvaluator(num_classes, crf_config_test, colours=colours, resize_after_crf=resize_after_crf, ctx=self.ctx)
+            # Model.predict (:577-582): saveimg_dir = <out_dir>/predict_<category>/<layer>, should_overlay=True; DeepGlobe is the
+            # dataset that runs the CRF before the resize and shows its images at a quarter (:597-600)
+            self.ev = SegEvaluator(num_classes, crf_config_test, colours=colours, resize_after_crf=resize_after_crf, ctx=self.ctx,
+                                   saveimg_dir=saveimg_dir, should_overlay=should_overlay, quarter_size=resize_after_crf, palette=palette)
         except Exception:
             self.close()
             raise
 
-    def update(self, img_list, gt_list, want_pred=False):
-        """img_list[b] (H_b, W_b, 3) uint8 RGB, gt_list[b] as seg_gt_index takes it -> SegEvaluator.update's return value."""
+    def update(self, img_list, gt_list, want_pred=False, ids=None):
+        """img_list[b] (H_b, W_b, 3) uint8 RGB, gt_list[b] as seg_gt_index takes it -> SegEvaluator.update's return value.
+        ids: the images' names; with the constructor's saveimg_dir the three debug images per id are written."""
         ctx, held = self.ctx, []
         try:
             x, images = self.net.preprocess_dev(img_list, self.img_mean, self.size, keep_images=True)
@@ -1123,7 +1183,7 @@ class Predictor:
                 images = DeviceMaps(ctx, (B, h, w, 3), np.uint8)
                 held.append(images)
                 _lib.seg_crf_image_u8(ctx, x.ptr, B, self.size[0], self.size[1], np.zeros(3, np.float32), (h, w), images.ptr)
-            return self.ev.update(prob, images, gt_list, want_pred=want_pred)
+            return self.ev.update(prob, images, gt_list, want_pred=want_pred, ids=ids, orig_images=img_list if ids is not None else None)
         finally:
             for d in held:
                 d.free()
@@ -1358,12 +1418,13 @@ class SegTrainLoop:
       2. its checkpoints hold the trainable variables only: on resume momentum restarts at zero and the shuffle restarts.  Here
          momentum, accumulator, RNG step and shuffle position (i * batch_size emissions) are restored: a resumed run equals the
          uninterrupted one bit for bit.  (final-0.npy is an output only; the reference would resume from it at i = 0.)
-      3. the debug-image writers (should_saveimg), the TensorBoard summaries and TF checkpoint files are out of scope."""
+      3. the TensorBoard summaries and TF checkpoint files are out of scope.  (The debug images are written: should_saveimg with
+         out_dir puts the validation's under <out_dir>/train/<i>/, see validate(); Model.predict's come from Predictor.)"""
 
     def __init__(self, method, weights, num_classes, train_ids, load_image, cues_data, val_sets=None, batch_size=16, max_epochs=1,
                  accum_num=1, base_lr=1e-4, lr_decay=0.5, lr_step=4, momentum=0.9, weight_decay=5e-4, drop_prob=0.5, seed=0,
                  img_mean=None, crf_config_train=None, size=(321, 321), seed_size=41, save_dir=None, report_every=200, colours=None,
-                 precision=_lib.PREC_F16X3, ctx=None, num_workers=4):
+                 precision=_lib.PREC_F16X3, ctx=None, num_workers=4, should_saveimg=False, out_dir=None, dataset=None, palette=None):
         import os
 
         self.ids, self.load_image, self.cues_data = list(train_ids), load_image, cues_data
@@ -1376,6 +1437,12 @@ class SegTrainLoop:
         if img_mean is None:
             raise ValueError("SegTrainLoop: img_mean (BGR) is the dataset's and has no default")
         self.C, self.seed, self.save_dir = int(num_classes), int(seed), save_dir
+        # --saveimg (model.py:513-518, :721-728): <out_dir>/train/<i>/ per report; `dataset` picks the reference's three special cases
+        self.should_saveimg, self.out_dir, self.dataset = bool(should_saveimg), out_dir, str(dataset or "")
+        self.palette = palette if palette is not None else colours
+        self.img_mean64 = np.asarray(img_mean, dtype=np.float64).reshape(1, 1, 3)
+        if self.should_saveimg and (out_dir is None or self.palette is None or len(self.palette) != int(num_classes)):
+            raise ValueError("SegTrainLoop: should_saveimg needs out_dir and a palette of %d colours (label2rgb_colors)" % int(num_classes))
         self.val_sets = dict(val_sets or {})
         self.crf_cfg = dict(CRF_CONFIG_TRAIN if crf_config_train is None else crf_config_train)
         self.num_workers = max(1, int(num_workers))
@@ -1411,17 +1478,28 @@ class SegTrainLoop:
         self.close()
         return False
 
-    def validate(self, pool, ids, load_image, load_gt):
-        """the mIoU of the is_eval=False pass over `ids`, in batches of batch_size (the last one may be smaller)"""
+    def validate(self, pool, ids, load_image, load_gt, saveimg_dir=None):
+        """the mIoU of the is_eval=False pass over `ids`, in batches of batch_size (the last one may be smaller).
+        saveimg_dir (the reference's --saveimg, model.py:721-728): per image `<id>_img.png`, `<id>_output.png` and `<id>_pred.png` --
+        the image is `np.uint8(img[j] + self.img_mean)`, the network's own input with the mean added back (BGR; for an ADP dataset
+        the channels are reversed, :724-725), the other two the label2rgb map of the arg-max (should_overlay is False in this
+        call, :521-524); VOC2012 keeps the first image of every batch only (:722-723), DeepGlobe shows a quarter (:597-600)."""
         tr, bs = self.trainer, self.batch_size
-        ev = SegEvaluator(self.C, None, ctx=tr.ctx, crf=False)
+        ev = SegEvaluator(self.C, None, ctx=tr.ctx, crf=False, saveimg_dir=saveimg_dir, should_overlay=False,
+                          quarter_size="DeepGlobe" in self.dataset, palette=self.palette if saveimg_dir is not None else None)
         try:
             chunks = (ids[k:k + bs] for k in range(0, len(ids), bs))
-            for _, loaded in prefetched(pool, chunks, lambda i: (load_image(i), load_gt(i))):
+            for chunk, loaded in prefetched(pool, chunks, lambda i: (load_image(i), load_gt(i))):
                 x, gt = self.batcher.val_batch([d[0] for d in loaded], [d[1] for d in loaded])
                 with x, gt:
+                    names = shown = None
+                    if saveimg_dir is not None:
+                        names = [i if (j == 0 or self.dataset != "VOC2012") else None for j, i in enumerate(chunk)]
+                        shown = [np.uint8(im + self.img_mean64) for im in x.to_host()]  # img_curr = np.uint8(img[j] + self.img_mean)
+                        if "ADP" in self.dataset:
+                            shown = [np.ascontiguousarray(im[:, :, ::-1]) for im in shown]
                     with tr.net.rescale_output_dev(x, self.batcher.img_mean, self.crf_cfg, seed_size=self.batcher.seed_size) as out:
-                        ev.update(out, None, gt)
+                        ev.update(out, None, gt, ids=names, orig_images=shown)
             return ev.metrics()["mIoU"]
         finally:
             ev.close()
@@ -1450,7 +1528,8 @@ class SegTrainLoop:
                 if i % self.report_every == 0:
                     means = sums / count
                     sums, count = np.zeros(3), 0
-                    miou = {cat: self.validate(pool, list(v[0]), v[1], v[2]) for cat, v in self.val_sets.items()}
+                    saveimg_dir = os.path.join(self.out_dir, "train", str(i)) if self.should_saveimg else None  # :513-518
+                    miou = {cat: self.validate(pool, list(v[0]), v[1], v[2], saveimg_dir) for cat, v in self.val_sets.items()}
                     reports.append({"iteration": i, "epoch": epoch, "lr": float(tr.lr), "seed": float(means[0]),
                                     "constrain": float(means[1]), "total": float(means[2]), "miou": miou})
                     print("epoch=%f | seed_loss=%f, constrain_loss=%f, total_loss=%f" % (epoch, means[0], means[1], means[2])
