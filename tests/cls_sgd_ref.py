@@ -1,4 +1,4 @@
-"""Reference of the update half of a 01_train step (csrc/cls_sgd.hip; wsc_cls_param_layout, wsc_cls_sgd_step, wsc_net_cls_load_params;
+"""Reference of the update half of a 01_train step (csrc/sgd.hip, csrc/repack.hip; wsc_cls_param_layout, wsc_cls_sgd_step, wsc_net_cls_load_params;
 cls_train.ClsTrainer, step_lr, cyclic_lr), in numpy.
 
   sgd_step32     Keras 2.2 optimizers.SGD(lr, momentum, decay=0.0, nesterov).get_updates restated with ONE np.float32 operation per

@@ -1,4 +1,4 @@
-"""numpy restatement of the update half of a SEC / DSRG training step (03a_sec-dsrg/model.py:379-404, 491-504; csrc/seg_sgd.hip):
+"""numpy restatement of the update half of a SEC / DSRG training step (03a_sec-dsrg/model.py:379-404, 491-504; csrc/sgd.hip, csrc/repack.hip):
 
     accumulate   t = grad + weight_decay * param on weights (every layer, fc8 included), t = grad on biases;
                  t = mult * t with mult 1 (weights), 2 (biases), 10 (fc8 weights), 20 (fc8 biases);  accum += t / accum_num

@@ -1,4 +1,4 @@
-"""GPU: the update half of a 01_train step (csrc/cls_sgd.hip; wsc_cls_param_layout, wsc_cls_sgd_step, wsc_net_cls_load_params;
+"""GPU: the update half of a 01_train step (csrc/sgd.hip, csrc/repack.hip; wsc_cls_param_layout, wsc_cls_sgd_step, wsc_net_cls_load_params;
 vgg16_cam.CAM.load_params_dev, cls_train.ClsTrainer) against tests/cls_sgd_ref.py.
 
   step bits    parameters and momentum bit for bit those of the float32 one-rounding-per-operation restatement (the definition), in

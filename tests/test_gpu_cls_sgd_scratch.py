@@ -1,4 +1,4 @@
-"""GPU: the scratch sweep of tests/test_gpu_scratch.py for the update half of a 01_train step (csrc/cls_sgd.hip, wsc_cls_sgd_step /
+"""GPU: the scratch sweep of tests/test_gpu_scratch.py for the update half of a 01_train step (csrc/sgd.hip, csrc/repack.hip, wsc_cls_sgd_step /
 wsc_net_cls_load_params of csrc/net.hip): a whole ClsTrainer.step on a VGG16 net -- the arena, cached blocks, the gradient object's
 workspace, the repack's partial channel maxima and the transposed copy of the classifier the CAM head is packed from -- gives the same
 bits whatever the scratch held before (fill off, 0x00, 0xFF, 0x3F), and writes nothing outside the caller's buffers.

@@ -1,4 +1,4 @@
-"""GPU: the update half of an IRNet training step and the closing dp_mean pass (csrc/irn_sgd.hip; wsc_irn_sgd_step,
+"""GPU: the update half of an IRNet training step and the closing dp_mean pass (csrc/sgd.hip, csrc/repack.hip, csrc/irn_grad.hip; wsc_irn_sgd_step,
 wsc_net_irn_load_params, wsc_channel_mean_nchw, wsc_net_set_mean_shift; misc.torchutils.PolyOptimizer, irn_train.IrnTrainer)
 against tests/irn_sgd_ref.py.
 

@@ -1,4 +1,4 @@
-"""GPU: the update half of a SEC / DSRG training step (csrc/seg_sgd.hip; wsc_seg_sgd_accumulate, wsc_seg_sgd_apply,
+"""GPU: the update half of a SEC / DSRG training step (csrc/sgd.hip, csrc/repack.hip; wsc_seg_sgd_accumulate, wsc_seg_sgd_apply,
 wsc_net_seg_load_params of csrc/net.hip; secdsrg.SegNet.load_params_dev, secdsrg.SegTrainer).
 
   optimiser   accumulate + apply on a thin net's whole flat buffer against tests/seg_sgd_ref.py in float32, BIT FOR BIT (param,

@@ -20,7 +20,7 @@
 //   clamp for nearest and for constant);  t = 0; t += (v[i][j] * wy[i]) * wx[j] in (i, j) order;  one rounding to float32.
 // Double because scipy computes in double and the result is held to its bits (tests/cls_batch_ref.py is pinned against scipy,
 // the kernel against it); -ffp-contract=off because a fused multiply-add would round once where scipy rounds twice, and because
-// the standardisation is three single fp32 roundings (as cls_sgd.hip's step).
+// the standardisation is three single fp32 roundings (as sgd.hip's steps).
 //
 // Work: one thread per 16 output bytes.  x_dev is taken as ONE flat array of B * 3 * H * W floats: a thread owns four consecutive
 // floats -- they may straddle a row, a plane or a sample (W = 321 is no multiple of 4, nor is 321 * 321), so every element is

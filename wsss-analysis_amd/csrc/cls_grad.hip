@@ -8,7 +8,7 @@
 //   grid (row blocks, ceil(C / 64)); a block owns `rows_per` rows of a 64-channel slab; thread (lane r = tid / 16, group g = tid % 16)
 //   reads 16 bytes -- channels 4 g .. 4 g + 3 of the slab -- of rows r, r + 16, ... and keeps two double sums per channel;
 //   the 16 lanes of a channel are added in lane order through LDS; the block's partial goes to partials[slab][block][channel];
-//   the last block of a slab to arrive (an integer ticket, agent-scope release / acquire: the pattern of channel_mean_kernel) adds
+//   the last block of a slab to arrive (an integer ticket per slab: ticket_publish / ticket_is_last of common.h) adds
 //   the partials in block order and finishes the slab's channels.
 // No floating-point atomic, one fixed order: two calls give the same bits (on one device: the block count follows the CU count).
 //   forward   the sums are of d = a - p and d d with the pivot p = a[0][c], formed in double (d is exact): mean = p + S / M,
@@ -125,18 +125,10 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_sums_kernel(BnSumArgs a) {
             t.y += red[l][tid].y;
         }
         mine[(long long)blockIdx.x * BN_SLAB + tid] = t;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ticket_publish();
     }
     __syncthreads();
-    if (tid == 0) {
-        const unsigned ticket = __hip_atomic_fetch_add(a.tickets + slab, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = ticket == gridDim.x - 1;
-        if (s_last) { // every block's partial of this slab is out
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
+    if (tid == 0) s_last = ticket_is_last(a.tickets + slab, gridDim.x);
     __syncthreads();
     if (!s_last || tid >= BN_SLAB || c >= a.C) return;
     double S = 0.0, Q = 0.0;

@@ -190,7 +190,7 @@ struct wsc_ctx {
     // blocks, handed back when the cache is destroyed and freed with everything else at destroy
     WscGaussCache *gauss_cache = nullptr;
     // wsc_ctx_scratch_fill: -1 = off, else the byte that the arena (on the call and at every request), every cached block
-    // handed out and the grad objects' own workspaces (net.hip, seg_sgd.hip) are set to.  Not a path selector: a test hook that
+    // handed out and the grad objects' own workspaces (net.hip, repack.hip) are set to.  Not a path selector: a test hook that
     // makes a read of scratch nobody wrote show up in values
     int scratch_fill = -1;
 };
@@ -270,6 +270,32 @@ template <int NV> __device__ __forceinline__ void block_sum(double (&v)[NV], dou
         for (int w = 0; w < n_waves; ++w) s += scratch[w * NV + k];
         v[k] = s;
     }
+}
+// "The last block to arrive adds the partials": every block of a group of `n` stores its partial sums with plain stores, the block
+// that finds itself last reads all n of them and finishes, in block order -- a fixed order without a second launch.  `ticket`
+// counts the arrivals; the launcher zeroes it in front of every launch.  The memory-ordering argument, stated once:
+//   ticket_publish   by EVERY thread that has just stored a partial.  The agent-scope release writes the thread's stores back to
+//                    where every CU of the device reads them; the wait holds the wave until they have left (the compiler may
+//                    drop the fence's own wait, so it is spelled, behind the fence).  Where the storing threads are not the one
+//                    that takes the ticket, a __syncthreads() stands between the two calls.
+//   ticket_is_last   by ONE thread of the block, behind the above.  The increment is relaxed: it orders nothing, it only
+//                    counts, and it is an atomic at agent scope, so the n blocks see n different values.  Whoever draws n - 1
+//                    knows that every other block's publish is complete, because each incremented behind its own.  Its acquire
+//                    drops what this CU's cache may hold of the partials, and the wait holds the wave until that is done: the
+//                    block's loads behind the caller's next __syncthreads() read what the other blocks wrote.  The other blocks
+//                    read nothing and pay for no acquire.
+// The caller hands the result to the block through LDS and that __syncthreads().
+__device__ __forceinline__ void ticket_publish() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+__device__ __forceinline__ bool ticket_is_last(unsigned *ticket, unsigned n) {
+    const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n - 1;
+    if (last) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    return last;
 }
 
 // float -> uint32 whose unsigned order is the float order (-0 counts as +0: equal values must tie), and back: the sort keys of
@@ -365,7 +391,7 @@ inline ConvKLayout conv_k_layout(int kh, int kw, int Cin, ConvForm form, wsc_pre
 // The IEEE-half modes store every output channel's weights times 2^shift, the power of two that puts the channel's largest |w|
 // (`mx`) into [2^12, 2^13): mx = m 2^e with m in [0.5, 1) (frexp, fp32 denormals included), shift = 13 - e bounded to +-100 (a
 // channel of ~1e-40 would otherwise ask for 2^(13 - e) = inf); a channel whose maximum is zero or not finite keeps shift 0.
-// Integer arithmetic on the bits: the host packing (net.hip make_conv) and the device repack (seg_sgd.hip) get the same shift.
+// Integer arithmetic on the bits: the host packing (net.hip make_conv) and the device repack (repack.hip) get the same shift.
 __host__ __device__ inline int conv_half_shift(float mx) {
     union { float f; uint32_t u; } v;
     v.f = mx;
@@ -588,10 +614,11 @@ int dgrad_launch(wsc_ctx *ctx, const float *dz, const float *w_packed, const flo
 // whether a launch may take the 16-byte forms of its loads and stores on `p`
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
-// ---- seg_sgd.hip: the SGD-momentum step on the flat parameter layout of wsc_seg_grad_layout, and the device repack --------------
-// One run of floats of that layout with one learning-rate multiplier: a layer's w (decay = 1: the weight-decay term applies and
-// the floats count into loss["l2"]) or its b.  The table has a segment per run in offset order; the kernels find an element's
-// segment themselves, so the offsets may be any (odd ones included).
+// ---- sgd.hip: the optimiser steps of the three training paths, each on the flat fp32 parameter layout of its gradient object
+// (the contract: its header); every product, sum and quotient one fp32 rounding ----------------------------------------------------
+// SEC / DSRG, the layout of wsc_seg_grad_layout.  One run of floats of that layout with one learning-rate multiplier: a layer's w
+// (decay = 1: the weight-decay term applies and the floats count into loss["l2"]) or its b.  The table has a segment per run in
+// offset order; the kernel finds an element's segment itself, so the offsets may be any (odd ones included).
 struct SgdSegment {
     long long start; // first float
     float mult;      // 1 / 2 (bias) / 10 (fc8 w) / 20 (fc8 b)
@@ -599,18 +626,28 @@ struct SgdSegment {
 };
 constexpr int SGD_MAX_SEGMENTS = 128;  // (a DSRG net has 50)
 constexpr int SGD_L2_MAX_BLOCKS = 1024; // blocks of the accumulate kernel = doubles of `l2_partials`
-// accum += mult (grad [+ wd param]) / accum_num, every operation rounded to fp32 on its own; l2_dev (or null) = sum w^2 / 2 over the
-// decay segments, summed in double in a fixed order (l2_partials: SGD_L2_MAX_BLOCKS doubles, l2_counter: one unsigned, both the
-// caller's and used by one stream)
+// accum += mult (grad [+ wd param]) / accum_num; l2_dev (or null) = sum w^2 / 2 over the decay segments, summed in double in a
+// fixed order (l2_partials: SGD_L2_MAX_BLOCKS doubles, l2_counter: one unsigned, both the caller's and used by one stream)
 int sgd_accumulate_launch(wsc_ctx *ctx, const SgdSegment *segs_dev, int n_segs, const float *param, const float *grad, float *accum,
                           long long elems, float weight_decay, int accum_num, double *l2_partials, unsigned *l2_counter, float *l2_dev);
 // mom = mom momentum + accum, param -= lr mom (TensorFlow's ApplyMomentum, use_nesterov = False); clear_accum: accum = +0.0
 int sgd_apply_launch(wsc_ctx *ctx, float *param, float *accum, float *mom, long long elems, float lr, float momentum, int clear_accum);
-// The device repack: every DeepLab layer's weights w [k][k][Cin][Cout] (HWIO) and bias b [Cout], at their offsets of the flat
-// parameter buffer, into everything derived from them -- the packed rows `wp` [CoutPad][Kw] of conv_k_layout(k, k, Cin or 4, form,
-// prec) with s1 / b1, the bytes make_conv gives, and (w_rot non-null) the rotated, channel-transposed fp32 kernel of dgrad_pack.
-// One RepackJob per layer in a device table built once per wsc_seg_grad: the caller fills the layer's fields, repack_plan adds the
-// layout, the split of the channel maxima and where the layer's blocks lie in each of the (at most four) launches of a repack.
+// IRNet, the layout of wsc_irn_grad_layout: g = grad + wd p; m = momentum m + g; p = p - lr m with lr = lr_a for the elements
+// before `boundary`, lr_b from there on; grad is only read
+int irn_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, long long boundary, float lr_a, float lr_b,
+                   float weight_decay, float momentum);
+// 01_train, the layout of wsc_cls_param_layout: v = momentum m - lr g; m = v; p = (p + momentum v) - lr g (nesterov) / p + v; lr g
+// formed once; grad is only read
+int cls_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, float lr, float momentum, int nesterov);
+
+// ---- repack.hip: the updated floats of a parameter buffer into a net, what the three wsc_net_*_load_params launch (the
+// contract: its header).  Each launch below serves every job of a device table: a job carries its first block in that launch, jobs
+// in order, the block offsets non-decreasing (an empty range: no blocks); a kernel finds its block's job there ----------------------
+// The conv rows: a layer's weights w [k][k][Cin][Cout] (HWIO) and bias b [Cout], at their offsets of the flat parameter buffer,
+// into everything derived from them -- the packed rows `wp` [CoutPad][Kw] of conv_k_layout(k, k, Cin or 4, form, prec) with
+// s1 / b1, the bytes make_conv gives, and (w_rot non-null) the rotated, channel-transposed fp32 kernel of dgrad_pack.
+// One RepackJob per layer in a device table built once per gradient object: the caller fills the layer's fields, repack_plan adds
+// the layout, the split of the channel maxima and where the layer's blocks lie in each of the (at most four) launches of a repack.
 struct RepackJob {
     long long w_off, b_off;          // floats into the parameter buffer; b_off < 0: no bias, b1 = 0 (the IRNet heads)
     int k, Cin, Cout;                // Cin as in the HWIO tensor (3 for the first layer)
@@ -638,13 +675,6 @@ struct RepackPlan {
 };
 int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *plan);
 int repack_launch(wsc_ctx *ctx, const RepackPlan &plan, const float *param);
-
-// ---- irn_sgd.hip: the update half of an IRNet training step on the layout of wsc_irn_grad_layout, the vectors of its repack and
-// the per-channel mean of the closing dp_mean pass (the contract: its header) ---------------------------------------------------
-// g = grad + wd p; m = momentum m + g; p = p - lr m with lr = lr_a for the elements before `boundary`, lr_b from there on; every
-// product and sum one fp32 rounding; grad is only read
-int irn_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, long long boundary, float lr_a, float lr_b,
-                   float weight_decay, float momentum);
 // One run of floats of the parameter buffer that a repack copies as it is (GroupNorm weight / bias of a head)
 struct VecCopyJob {
     long long off; // floats into the parameter buffer
@@ -652,19 +682,8 @@ struct VecCopyJob {
     float *dst;
 };
 constexpr int VEC_COPY_PER_BLOCK = 256;
-// (block0 filled by the caller: jobs in order, ceil(n / VEC_COPY_PER_BLOCK) blocks each)
+// (block0 filled by the caller: ceil(n / VEC_COPY_PER_BLOCK) blocks each)
 int vec_copy_launch(wsc_ctx *ctx, const VecCopyJob *jobs_dev, int n_jobs, int blocks, const float *param);
-// out[c] (device doubles) = mean over (n, p) of x[n][c][p] in double, minus sub_host[c] (floats, or null); the scratch (tickets,
-// partials, the uploaded sub) is one cached block of the ctx, handed back behind the launch
-constexpr int CHANNEL_MEAN_MAX_BLOCKS = 64; // per channel
-constexpr int CHANNEL_MEAN_MAX_C = 1024;
-int channel_mean_launch(wsc_ctx *ctx, const float *x, int N, int C, long long HW, const float *sub_host, double *out);
-
-// ---- cls_sgd.hip: the update half of a 01_train step on the layout of wsc_cls_param_layout, and what the repack of the plain
-// stacks adds to the two files above (the contract: its header) -----------------------------------------------------------------
-// v = momentum m - lr g; m = v; p = (p + momentum v) - lr g (nesterov) / p + v; lr g formed once; every product, sum and difference
-// one fp32 rounding; grad is only read
-int cls_sgd_launch(wsc_ctx *ctx, float *param, const float *grad, float *mom, long long elems, float lr, float momentum, int nesterov);
 // One BatchNorm layer's inference epilogue: s2[c] = float(gamma / sqrt(var + eps)), b2[c] = float(beta - mean sc) in double, from
 // gamma / beta at their offsets of the parameter buffer and the layer's [2][C] block of the running statistics
 struct BnFoldJob {
@@ -674,9 +693,9 @@ struct BnFoldJob {
     float *s2, *b2;
 };
 constexpr int BN_FOLD_PER_BLOCK = 256;
-// (block0 filled by the caller: jobs in order, ceil(C / BN_FOLD_PER_BLOCK) blocks each)
+// (block0 filled by the caller: ceil(C / BN_FOLD_PER_BLOCK) blocks each)
 int bn_fold_launch(wsc_ctx *ctx, const BnFoldJob *jobs_dev, int n_jobs, int blocks, const float *param, const float *run);
-// dst [F][C] = the transpose of src [C][F]
+// dst [F][C] = the transpose of src [C][F] (the classifier's Linear, torch's layout, as the conv rows read it)
 int transpose_cf_launch(wsc_ctx *ctx, const float *src, int C, int F, float *dst);
 
 // ---- seg_dropout.hip: the dropout sites behind fc6 / fc7 of the SEC / DSRG training graph (the contract: its header) -----------
@@ -714,7 +733,8 @@ int launch_edge_finish(wsc_ctx *ctx, const float *e, int He, int We, const float
 // e [N][He][We], d [N][Hd][Wd][2] (8-byte aligned) -> edge [N][He][We], dp [N][2][Hd][Wd]
 int launch_edge_raw(wsc_ctx *ctx, const float *e, int He, int We, const float *d, int Hd, int Wd, int N, float *edge, float *dp);
 
-// ---- irn_grad.hip: the fp32 / double kernels of the backward pass of the IRNet heads (the contract: its header) ----------------
+// ---- irn_grad.hip: the fp32 / double kernels of the backward pass of the IRNet heads and the channel mean of the closing dp_mean
+// pass (the contract: its header) ---------------------------------------------------------------------------------------------
 // dy [N][H][W][C] = the adjoint of "upsample by `up`, crop to Hd x Wd, ReLU, write channels [coff, coff + C)" applied to dcat
 // [N][Hd][Wd][Ctot]; the ReLU mask is cat > 0 (the taped concat values); every element of dy is written
 int launch_relu_upsample_grad(wsc_ctx *ctx, const float *dcat, const float *cat, int N, int H, int W, int C, int up, int Hd, int Wd, int Ctot,
@@ -728,6 +748,11 @@ int launch_group_norm_grad(wsc_ctx *ctx, const float *z, const void *stats, cons
 int launch_strided_rows_f32(wsc_ctx *ctx, const float *x, int N, int H, int W, int C, int stride, int Ho, int Wo, float *y);
 // ddp [N][2][HW] -> out [N HW][Cd], zeros past channel 1
 int launch_dp_to_nhwc(wsc_ctx *ctx, const float *ddp, int N, int HW, int Cd, float *out);
+// out[c] (device doubles) = mean over (n, p) of x[n][c][p] in double, minus sub_host[c] (floats, or null); the scratch (tickets,
+// partials, the uploaded sub) is one cached block of the ctx, handed back behind the launch
+constexpr int CHANNEL_MEAN_MAX_BLOCKS = 64; // per channel
+constexpr int CHANNEL_MEAN_MAX_C = 1024;
+int channel_mean_launch(wsc_ctx *ctx, const float *x, int N, int C, long long HW, const float *sub_host, double *out);
 
 // ---- cls_grad.hip: BatchNorm in training mode on a [M][C] fp32 matrix (the contract: its header and include/wsscam.h) -----------
 // stats [C] float {mean, rstd} pairs of the batch; run: null, or [2][C] running mean / variance updated in place with `keep` the

@@ -19,6 +19,12 @@
 //                     dz = rstd (gamma_c dy - m1 - xh m2), formed in double and rounded once.
 //   strided rows      x[:, ::s, ::s, :] as a dense operand of the weight-gradient GEMM (the stride-2 heads of VGG16 and M7)
 //   dp_out's gradient [N][2][Hd][Wd] -> [N Hd Wd][Cd] pixel-major, zeros past channel 1
+//   channel mean      the closing dp_mean pass (train_irn.py:148-164, wsc_channel_mean_nchw of net.hip): x [N][C][HW] -> mean[c] over
+//                     (n, p) in double: block (b, c) sums the items b 256 + t + k B 256 of channel c, each thread in ascending k,
+//                     the block in block_sum's order; partial[c][b] to HBM; the block of a channel that arrives last (common.h's
+//                     ticket, one per channel) adds the partials in block order, divides by N HW and subtracts sub[c].  An item
+//                     is four consecutive floats of one plane (added in order) where HW % 4 == 0 and x is 16-byte aligned, else
+//                     one float.
 // The element kernels have a 16-byte form (four channels per thread) and a scalar form with the same expressions per element.
 #include "common.h"
 
@@ -27,6 +33,7 @@
 namespace {
 
 constexpr int GNG_CHUNK = 256; // pixels per block of pass 1
+constexpr int CM_BLOCK = 256;  // threads of the channel mean
 
 struct UpGradArgs {
     const float *dcat, *cat; // [N][Hd][Wd][Ctot]
@@ -238,6 +245,53 @@ __global__ __launch_bounds__(256) void dp_to_nhwc_kernel(const float *__restrict
     }
 }
 
+struct ChannelMeanArgs {
+    const float *x;
+    long long HW, count; // count = N HW
+    int C;
+    const float *sub; // or null
+    double *partials; // [C][gridDim.x]
+    unsigned *tickets; // [C], zero at launch
+    double *out;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(CM_BLOCK) void channel_mean_kernel(ChannelMeanArgs a) {
+    __shared__ double scratch[CM_BLOCK / 64], fin[CHANNEL_MEAN_MAX_BLOCKS];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, c = blockIdx.y;
+    constexpr int PER = VEC ? 4 : 1;
+    const long long items = a.count / PER, per_plane = a.HW / PER; // (VEC: HW % 4 == 0)
+    double s[1] = {0.0};
+    for (long long i = (long long)blockIdx.x * CM_BLOCK + tid; i < items; i += (long long)gridDim.x * CM_BLOCK) {
+        const long long n = i / per_plane, q = i - n * per_plane;
+        const float *src = a.x + (n * a.C + c) * a.HW + q * PER;
+        if (VEC) {
+            const float4 v = *reinterpret_cast<const float4 *>(src);
+            s[0] += (((double)v.x + (double)v.y) + (double)v.z) + (double)v.w;
+        } else {
+            s[0] += (double)*src;
+        }
+    }
+    block_sum<1>(s, scratch);
+    if (tid == 0) {
+        a.partials[(long long)c * gridDim.x + blockIdx.x] = s[0];
+        ticket_publish();
+        s_last = ticket_is_last(a.tickets + c, gridDim.x);
+    }
+    __syncthreads();
+    if (!s_last) return;
+    for (unsigned b = tid; b < gridDim.x; b += CM_BLOCK) fin[b] = a.partials[(long long)c * gridDim.x + b];
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (unsigned b = 0; b < gridDim.x; ++b) t += fin[b];
+        t /= (double)a.count;
+        if (a.sub) t -= (double)a.sub[c];
+        a.out[c] = t;
+    }
+}
+
 int check_up_grad(const char *fn, int N, int H, int W, int C, int up, int Hd, int Wd, int Ctot, int coff) {
     WSC_CHECK(N > 0 && H > 0 && W > 0 && C > 0, WSC_ERR_INVALID, "%s: %d x %d x %d x %d", fn, N, H, W, C);
     WSC_CHECK(up == 1 || up == 2 || up == 4, WSC_ERR_INVALID, "%s: upsample factor %d (1, 2 or 4)", fn, up);
@@ -312,6 +366,32 @@ int launch_dp_to_nhwc(wsc_ctx *ctx, const float *ddp, int N, int HW, int Cd, flo
     WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, (double)M * (2 + Cd) * 4);
     hipLaunchKernelGGL(dp_to_nhwc_kernel, dim3(wsc_grid_for(M * Cd)), dim3(256), 0, ctx->stream, ddp, M, HW, Cd, out);
     WSC_HIP(hipGetLastError());
+    return WSC_OK;
+}
+
+int channel_mean_launch(wsc_ctx *ctx, const float *x, int N, int C, long long HW, const float *sub_host, double *out) {
+    WSC_CHECK(N > 0 && C > 0 && C <= CHANNEL_MEAN_MAX_C && HW > 0, WSC_ERR_INVALID, "channel mean: %d x %d x %lld", N, C, HW);
+    const bool vec = HW % 4 == 0 && aligned16(x);
+    const long long count = (long long)N * HW, items = vec ? count / 4 : count;
+    const int blocks = (int)std::min<long long>(std::max<long long>((items + 4 * CM_BLOCK - 1) / (4 * CM_BLOCK), 1), CHANNEL_MEAN_MAX_BLOCKS);
+    // one block of scratch: the tickets, the subtrahend, the partials
+    const size_t vec_b = ((size_t)C * 4 + 255) / 256 * 256;
+    void *blk = nullptr;
+    WSC_TRY(wsc_ctx_cached_alloc(ctx, 2 * vec_b + sizeof(double) * (size_t)C * blocks, &blk));
+    WscCachedGuard guard(ctx, blk);
+    ChannelMeanArgs a;
+    a.x = x; a.HW = HW; a.count = count; a.C = C;
+    a.tickets = (unsigned *)blk;
+    a.sub = sub_host ? (const float *)((char *)blk + vec_b) : nullptr;
+    a.partials = (double *)((char *)blk + 2 * vec_b);
+    a.out = out;
+    WSC_HIP(hipMemsetAsync(a.tickets, 0, vec_b, ctx->stream)); // (the tickets start at zero whatever the block held)
+    if (sub_host) WSC_TRY(wsc_ctx_upload_small(ctx, (char *)blk + vec_b, sub_host, sizeof(float) * C));
+    WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, 4.0 * count * C);
+    if (vec) hipLaunchKernelGGL(channel_mean_kernel<true>, dim3(blocks, C), dim3(CM_BLOCK), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(channel_mean_kernel<false>, dim3(blocks, C), dim3(CM_BLOCK), 0, ctx->stream, a);
+    WSC_HIP(hipGetLastError());
+    guard.free_now();
     return WSC_OK;
 }
 

@@ -241,7 +241,7 @@ int make_conv(wsc_net *net, const HostTensor *w, int stride, int pad, int relu, 
             // (bounded shift: a dead channel in fp32's denormal range -- weight decay leaves |w| ~ 1e-40 -- would otherwise
             // ask for 2^(13 - e) = inf, every weight * inf = inf, lo = inf - inf = NaN; with the bound such a channel keeps
             // its tiny values as half subnormals / zeros like before the packing)
-            const int sh = conv_half_shift(mx); // (common.h: the device repack of seg_sgd.hip takes the same shift)
+            const int sh = conv_half_shift(mx); // (common.h: the device repack of repack.hip takes the same shift)
             wscale[co] = conv_pow2(sh);
             s1v[co] = s1[co] * conv_pow2(-sh);
         }
@@ -1808,8 +1808,9 @@ struct GradCore {
     }
 };
 // A device table of jobs that each carry `block0`, their first block in one launch: add() hands a job its blocks, jobs in order,
-// ceil(n / per_block) each; upload() moves the table into an allocation of the gradient object and leaves dev / n / blocks, what
-// the launch takes.  A load-params entry builds one locally and assigns it to its object once it is uploaded.
+// ceil(n / per_block) each, so block0 never decreases -- what find_job of repack.hip, the device half of the contract, relies on;
+// upload() moves the table into an allocation of the gradient object and leaves dev / n / blocks, what the launch takes.  A
+// load-params entry builds one locally and assigns it to its object once it is uploaded.
 extern "C++" { // (a template, and functions that return C++ types, inside this file's extern "C")
 template <class Job> struct JobTable {
     std::vector<Job> host;
@@ -1882,7 +1883,7 @@ struct wsc_seg_grad : GradCore {
     using GradCore::GradCore;
     std::vector<GradLayer> layers; // the trunk's convs in op order, then fc6, fc7, fc8 of every branch
     std::vector<int> op_layer;     // layer of op i, -1 for a pool
-    // the optimiser's view of the layout (seg_sgd.hip): a segment per w and per b in offset order, built once; the partials and
+    // the optimiser's view of the layout (sgd.hip): a segment per w and per b in offset order, built once; the partials and
     // the arrival counter of loss["l2"]
     SgdSegment *segs = nullptr;
     int n_segs = 0;
@@ -2291,7 +2292,8 @@ int wsc_net_backward_edge(wsc_ctx *ctx, wsc_irn_grad *g, int N, int S, const flo
     return WSC_OK;
 }
 
-// ---- the update half of an IRNet step (train_irn.py:86-90, 127-129) and the closing dp_mean pass (148-164); kernels: irn_sgd.hip ----
+// ---- the update half of an IRNet step (train_irn.py:86-90, 127-129) and the closing dp_mean pass (148-164); kernels: sgd.hip,
+// repack.hip, irn_grad.hip (the channel mean) -------------------------------------------------------------------------------------
 int wsc_irn_sgd_step(wsc_ctx *ctx, wsc_irn_grad *g, float *param_dev, const float *grad_dev, float *mom_dev, long long elems, float lr_edge,
                      float lr_dp, float weight_decay, float sgd_momentum) {
     WSC_TRY(grad_check("wsc_irn_sgd_step", ctx, g, elems, param_dev && grad_dev && mom_dev));
@@ -2928,7 +2930,7 @@ int wsc_net_backward_cls_drop(wsc_ctx *ctx, wsc_cls_grad *g, int B, int H, int W
 }
 
 // ---- the update half of a 01_train step (Keras' SGD with Nesterov momentum, 01_train/demo.py:60) and the repack of the updated
-// parameters into the net; kernels: cls_sgd.hip, seg_sgd.hip (the conv rows), irn_sgd.hip (the vectors) ---------------------------
+// parameters into the net; kernels: sgd.hip (the step), repack.hip ------------------------------------------------------
 int wsc_cls_param_layout(const wsc_cls_grad *g, wsc_grad_entry *entries_out, int max_entries, int *n_out, long long *param_elems_out) {
     WSC_CHECK(g && n_out && param_elems_out && max_entries >= 0 && (entries_out != nullptr || max_entries == 0), WSC_ERR_INVALID,
               "wsc_cls_param_layout: null argument");

@@ -1,181 +1,44 @@
-// seg_sgd.hip -- the update half of a SEC / DSRG training step (Model.optimize(), model.py:379-404) on the flat fp32 layout of
-// wsc_seg_grad_layout, and the device repack that brings the updated floats into a net (wsc_seg_sgd_accumulate, wsc_seg_sgd_apply,
-// wsc_net_seg_load_params of net.hip).  Built with -ffp-contract=off: every product, sum and quotient below is one fp32 rounding.
+// repack.hip -- the device repack that brings the floats of a flat fp32 parameter buffer, as an optimiser step of sgd.hip leaves
+// them, into a net: what wsc_net_seg_load_params, wsc_net_irn_load_params and wsc_net_cls_load_params of net.hip launch.  Built
+// with -ffp-contract=off, and the BatchNorm fold's operations are spelled with their round-to-nearest intrinsics: one rounding each.
 //
-//   accumulate   t = grad + wd param (weights), t = grad (biases); t = mult t; accum += t / accum_num.  One thread per 16-byte vector
-//                of the WHOLE buffer: the layers' offsets are any (a 5-class fc8 bias makes every later one odd), so a vector may
-//                straddle segments; an element's segment is found by bisection of the table (in LDS) for the vector's first float
-//                and stepped forward per element.  A buffer that is not 16-byte aligned takes the scalar form of the same kernel.
-//                loss["l2"] = sum w^2 / 2: per thread in double over its grid-stride elements, a fixed LDS tree per block, the
-//                block partials to HBM; the block that arrives last (an integer ticket, agent-scope release / acquire) adds the
-//                partials in block order and rounds once.  No floating-point atomic: two calls give the same bits.
-//   apply        mom = mom momentum + accum; param = param - lr mom; accum = +0.0 (clear): three streams in, three out.
-//   repack       HWIO has Cout fastest, the packed rows K fastest: a transpose.  Per K-step (one tap of one channel chunk) a
+//   conv rows    HWIO has Cout fastest, the packed rows K fastest: a transpose.  Per K-step (one tap of one channel chunk) a
 //                block moves a [ck channels][64 output channels] tile through LDS: rows of 256 bytes in, and out 16 bytes per
 //                lane with ck / 8 adjacent lanes on one row's 128-byte K-step (hi | lo of the interleaved layout included).  The
 //                per-channel maximum of the IEEE-half modes is a column reduction with the lanes along Cout, split over row
 //                ranges into partial maxima the pack blocks finish (a maximum is exact in any order).  The rotated kernel of the
 //                data gradient keeps 32 output channels contiguous: a gather copy, one thread per output float.
 //                The first layer (Cin = 3 in a 4-channel slot, 27 weights per channel) has a small kernel of its own.
-//                The IRNet heads (wsc_net_irn_load_params) come through the same jobs at k = 1: a job without a bias (b_off < 0)
-//                gets b1 = 0, and one whose input is wider than its tensor (Cin_pad: the final edge conv, 160 in 192) packs
-//                zeros for the channels past Cin; a DeepLab job has neither, and its bits and launches are what they were.
+//                The IRNet heads and the plain stacks come through the same jobs, the heads at k = 1: a job without a bias
+//                (b_off < 0) gets b1 = 0, and one whose input is wider than its tensor (Cin_pad: the final edge conv, 160 in 192)
+//                packs zeros for the channels past Cin; a DeepLab job has neither.
 //                Four launches for the whole net, whatever its depth: each kernel finds its layer in a device table of per-layer
-//                jobs built once per wsc_seg_grad (a launch per layer and kernel was launch-bound: ~10 us each, 75 of them).
+//                jobs built once per gradient object (a launch per layer and kernel was launch-bound: ~10 us each, 75 of them).
+//   vectors      GroupNorm weight / bias of every head (IRNet), BatchNorm gamma / beta and biases (01_train), copied from the
+//                parameter buffer to the net's device vectors: one launch from a job table.
+//   fold         BatchNorm's inference form of a conv's epilogue from the updated affine parameters and the running statistics the
+//                training forward pass keeps on the device: sc = gamma / sqrt(var + eps), b = beta - mean sc in double (net.hip's
+//                fold_bn, operation for operation), each rounded to float once.  One thread per channel, one launch from a job table.
+//   transpose    the classifier's Linear lies as torch's [C][F]; the conv rows read [Cin][Cout] = [F][C]: a copy through one index
+//                swap into the gradient object's own buffer (20 x 1024 floats: nothing to tile).
 #include "common.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int SGD_BLOCK = 256;
-constexpr int SGD_PMAX_SPLITS = 64; // row ranges of a layer's partial channel maxima, at most
+constexpr int REPACK_PMAX_SPLITS = 64; // row ranges of a layer's partial channel maxima, at most
 
-struct SgdAccArgs {
-    const SgdSegment *segs;
-    int n_segs;
-    const float *param, *grad;
-    float *accum;
-    long long elems;
-    float wd, div;
-    double *partials; // null: no l2
-    unsigned *counter;
-    float *l2;
-};
-
-__device__ __forceinline__ float sgd_acc_one(float p, float g, float a, float wd, float mult, int decay, float div) {
-    float t = g;
-    if (decay) t = __fadd_rn(g, __fmul_rn(wd, p));
-    t = __fmul_rn(mult, t);
-    return __fadd_rn(a, __fdiv_rn(t, div));
+// Every job-table kernel below is ONE launch over all jobs: block b belongs to the job whose block range holds it.  BLOCK0 is the
+// member with the job's first block in this launch; the host half of the contract (JobTable<Job>::add of net.hip, repack_plan
+// here): jobs in order, BLOCK0 non-decreasing, a job without blocks in a launch has an empty range.  Returns the job; *lb: the
+// block's index inside it.
+template <class Job, int Job::*BLOCK0> __device__ __forceinline__ const Job &find_job(const Job *jobs, int n_jobs, int *lb) {
+    int ji = 0;
+    while (ji + 1 < n_jobs && (int)blockIdx.x >= jobs[ji + 1].*BLOCK0) ++ji;
+    *lb = (int)blockIdx.x - jobs[ji].*BLOCK0;
+    return jobs[ji];
 }
-
-template <bool VEC>
-__global__ __launch_bounds__(SGD_BLOCK) void sgd_accumulate_kernel(SgdAccArgs a) {
-    __shared__ long long s_start[SGD_MAX_SEGMENTS + 1];
-    __shared__ float s_mult[SGD_MAX_SEGMENTS];
-    __shared__ int s_decay[SGD_MAX_SEGMENTS];
-    __shared__ double red[SGD_BLOCK], fin[SGD_L2_MAX_BLOCKS];
-    __shared__ int s_last;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < a.n_segs; i += SGD_BLOCK) {
-        s_start[i] = a.segs[i].start;
-        s_mult[i] = a.segs[i].mult;
-        s_decay[i] = a.segs[i].decay;
-    }
-    if (tid == 0) s_start[a.n_segs] = a.elems;
-    __syncthreads();
-
-    const bool want_l2 = a.partials != nullptr;
-    double sq = 0.0;
-    constexpr int PER = VEC ? 4 : 1;
-    const long long nvec = (a.elems + PER - 1) / PER;
-    for (long long v = (long long)blockIdx.x * SGD_BLOCK + tid; v < nvec; v += (long long)gridDim.x * SGD_BLOCK) {
-        const long long base = v * PER;
-        int seg = 0, hi = a.n_segs - 1; // the last segment that starts at or before `base`
-        while (seg < hi) {
-            const int mid = (seg + hi + 1) >> 1;
-            if (s_start[mid] <= base) seg = mid;
-            else hi = mid - 1;
-        }
-        if (VEC && base + 4 <= a.elems) {
-            const float4 p4 = *reinterpret_cast<const float4 *>(a.param + base);
-            const float4 g4 = *reinterpret_cast<const float4 *>(a.grad + base);
-            const float4 a4 = *reinterpret_cast<const float4 *>(a.accum + base);
-            const float p[4] = {p4.x, p4.y, p4.z, p4.w}, g[4] = {g4.x, g4.y, g4.z, g4.w}, ac[4] = {a4.x, a4.y, a4.z, a4.w};
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                while (base + e >= s_start[seg + 1]) ++seg; // (a boundary inside the vector; s_start[n_segs] = elems ends it)
-                const int decay = s_decay[seg];
-                o[e] = sgd_acc_one(p[e], g[e], ac[e], a.wd, s_mult[seg], decay, a.div);
-                if (want_l2 && decay) sq += (double)p[e] * (double)p[e];
-            }
-            *reinterpret_cast<float4 *>(a.accum + base) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-            for (long long i = base; i < base + PER && i < a.elems; ++i) {
-                while (i >= s_start[seg + 1]) ++seg;
-                const int decay = s_decay[seg];
-                const float p = a.param[i];
-                a.accum[i] = sgd_acc_one(p, a.grad[i], a.accum[i], a.wd, s_mult[seg], decay, a.div);
-                if (want_l2 && decay) sq += (double)p * (double)p;
-            }
-        }
-    }
-    if (!want_l2) return; // (block-uniform)
-
-    red[tid] = sq;
-    __syncthreads();
-    for (int s = SGD_BLOCK / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        a.partials[blockIdx.x] = red[0];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned ticket = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = ticket == gridDim.x - 1;
-        if (s_last) { // every block's partial is out
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // the finishing block: the partials come in side by side, thread 0 adds them in block order
-    for (unsigned b = tid; b < gridDim.x; b += SGD_BLOCK) fin[b] = a.partials[b];
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0.0;
-        for (unsigned b = 0; b < gridDim.x; ++b) s += fin[b];
-        *a.l2 = (float)(0.5 * s);
-    }
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(SGD_BLOCK) void sgd_apply_kernel(float *param, float *accum, float *mom, long long elems, float lr, float momentum,
-                                                              int clear) {
-    constexpr int PER = VEC ? 4 : 1;
-    const long long nvec = (elems + PER - 1) / PER;
-    for (long long v = (long long)blockIdx.x * SGD_BLOCK + threadIdx.x; v < nvec; v += (long long)gridDim.x * SGD_BLOCK) {
-        const long long base = v * PER;
-        if (VEC && base + 4 <= elems) {
-            const float4 p4 = *reinterpret_cast<const float4 *>(param + base);
-            const float4 a4 = *reinterpret_cast<const float4 *>(accum + base);
-            const float4 m4 = *reinterpret_cast<const float4 *>(mom + base);
-            float4 m, p;
-            m.x = __fadd_rn(__fmul_rn(m4.x, momentum), a4.x); p.x = __fsub_rn(p4.x, __fmul_rn(lr, m.x));
-            m.y = __fadd_rn(__fmul_rn(m4.y, momentum), a4.y); p.y = __fsub_rn(p4.y, __fmul_rn(lr, m.y));
-            m.z = __fadd_rn(__fmul_rn(m4.z, momentum), a4.z); p.z = __fsub_rn(p4.z, __fmul_rn(lr, m.z));
-            m.w = __fadd_rn(__fmul_rn(m4.w, momentum), a4.w); p.w = __fsub_rn(p4.w, __fmul_rn(lr, m.w));
-            *reinterpret_cast<float4 *>(mom + base) = m;
-            *reinterpret_cast<float4 *>(param + base) = p;
-            if (clear) *reinterpret_cast<float4 *>(accum + base) = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            for (long long i = base; i < base + PER && i < elems; ++i) {
-                const float m = __fadd_rn(__fmul_rn(mom[i], momentum), accum[i]);
-                mom[i] = m;
-                param[i] = __fsub_rn(param[i], __fmul_rn(lr, m));
-                if (clear) accum[i] = 0.f;
-            }
-        }
-    }
-}
-
-int sgd_blocks(long long elems, bool vec) {
-    const long long nvec = vec ? (elems + 3) / 4 : elems;
-    return (int)std::min<long long>(std::max<long long>((nvec + SGD_BLOCK - 1) / SGD_BLOCK, 1), SGD_L2_MAX_BLOCKS);
-}
-
-// ---- repack -----------------------------------------------------------------------------------------------------------------------
-// Every kernel below is ONE launch over all layers: block b belongs to the layer whose block range holds it (the table's
-// *_block0, in layer order; a layer without blocks in a launch has an empty range).
-#define REPACK_FIND_JOB(field)                                                        \
-    int ji = 0;                                                                       \
-    while (ji + 1 < n_jobs && (int)blockIdx.x >= jobs[ji + 1].field) ++ji;            \
-    const RepackJob &J = jobs[ji];                                                    \
-    const int lb = (int)blockIdx.x - J.field /* the block's index inside the layer */
 
 // pmax[split][c] = max |w[r][c]| over the split's rows (a NaN is passed over, as std::max passes it over in make_conv: the pack
 // kernels below raise the range flag for it);
@@ -183,7 +46,8 @@ int sgd_blocks(long long elems, bool vec) {
 __global__ __launch_bounds__(256) void repack_colmax_kernel(const RepackJob *__restrict__ jobs, int n_jobs, const float *__restrict__ param,
                                                             float *__restrict__ pmax_all) {
     __shared__ float red[4][64];
-    REPACK_FIND_JOB(max_block0);
+    int lb;
+    const RepackJob &J = find_job<RepackJob, &RepackJob::max_block0>(jobs, n_jobs, &lb);
     const float *w = param + J.w_off;
     float *pmax = pmax_all + J.pmax_off;
     const int Cout = J.Cout, R = J.k * J.k * J.Cin;
@@ -216,7 +80,8 @@ __global__ __launch_bounds__(256) void repack_generic_kernel(const RepackJob *__
     bool bad = false;
     __shared__ float tile[CK][LD];
     __shared__ float s_scale[64];
-    REPACK_FIND_JOB(pack_block0);
+    int lb;
+    const RepackJob &J = find_job<RepackJob, &RepackJob::pack_block0>(jobs, n_jobs, &lb);
     const float *w = param + J.w_off;
     const int Cout = J.Cout, Cin = J.Cin, k = J.k, Kw = J.Kw, kstep = J.kstep;
     const int bx = lb % J.tiles, by = lb / J.tiles;
@@ -326,8 +191,10 @@ __global__ __launch_bounds__(64) void repack_small2_kernel(const RepackJob *__re
 // rot[ci][((co / 32) k + r) k + s][co % 32] = w[k - 1 - r][k - 1 - s][ci][co], co < Cout (the floats past Cout keep their zeros);
 // one thread per output float, a grid-stride loop over the layer's blocks
 __global__ __launch_bounds__(256) void repack_rot_kernel(const RepackJob *__restrict__ jobs, int n_jobs, const float *__restrict__ param) {
-    REPACK_FIND_JOB(rot_block0);
-    const int nb = (ji + 1 < n_jobs ? jobs[ji + 1].rot_block0 : (int)gridDim.x) - J.rot_block0;
+    int lb;
+    const RepackJob &J = find_job<RepackJob, &RepackJob::rot_block0>(jobs, n_jobs, &lb);
+    const RepackJob *next = &J + 1; // the layer's blocks end where the next layer's begin
+    const int nb = (next < jobs + n_jobs ? next->rot_block0 : (int)gridDim.x) - J.rot_block0;
     const float *w = param + J.w_off;
     float *rot = J.w_rot;
     const int k = J.k, Cin = J.Cin, Cout = J.Cout, Kw = J.rot_Kw;
@@ -341,39 +208,46 @@ __global__ __launch_bounds__(256) void repack_rot_kernel(const RepackJob *__rest
     }
 }
 
+// block lb of a job copies its floats [VEC_COPY_PER_BLOCK lb, ...)
+__global__ __launch_bounds__(VEC_COPY_PER_BLOCK) void vec_copy_kernel(const VecCopyJob *__restrict__ jobs, int n_jobs,
+                                                                      const float *__restrict__ param, unsigned *range) {
+    int lb;
+    const VecCopyJob &J = find_job<VecCopyJob, &VecCopyJob::block0>(jobs, n_jobs, &lb);
+    const int i = lb * VEC_COPY_PER_BLOCK + threadIdx.x;
+    if (i < J.n) {
+        const float v = param[J.off + i];
+        J.dst[i] = v;
+        if (!(fabsf(v) < INFINITY)) *range = (unsigned)J.n; // (a non-finite parameter: the door of the range guard, as the conv rows')
+    }
+}
+
+// block lb of a job folds its channels [BN_FOLD_PER_BLOCK lb, ...)
+__global__ __launch_bounds__(BN_FOLD_PER_BLOCK) void bn_fold_kernel(const BnFoldJob *__restrict__ jobs, int n_jobs, const float *__restrict__ param,
+                                                                    const float *__restrict__ run, unsigned *range) {
+    int lb;
+    const BnFoldJob &J = find_job<BnFoldJob, &BnFoldJob::block0>(jobs, n_jobs, &lb);
+    const int c = lb * BN_FOLD_PER_BLOCK + threadIdx.x;
+    if (c >= J.C) return;
+    const double gamma = (double)param[J.g_off + c], beta = (double)param[J.be_off + c];
+    const double mean = (double)run[J.run_off + c], var = (double)run[J.run_off + J.C + c];
+    const double sc = __ddiv_rn(gamma, __dsqrt_rn(__dadd_rn(var, J.eps)));
+    const float s = __double2float_rn(sc), b = __double2float_rn(__dsub_rn(beta, __dmul_rn(mean, sc)));
+    J.s2[c] = s;
+    J.b2[c] = b;
+    // (a scale / shift that is not finite: the door of the range guard, as make_conv's for what the host folds)
+    if (!(fabsf(s) < INFINITY) || !(fabsf(b) < INFINITY)) *range = (unsigned)J.C;
+}
+
+// dst[f][c] = src[c][f]: one thread per float of dst
+__global__ __launch_bounds__(256) void transpose_cf_kernel(const float *__restrict__ src, int C, int F, float *__restrict__ dst) {
+    const int total = C * F;
+    for (int o = blockIdx.x * 256 + threadIdx.x; o < total; o += gridDim.x * 256) {
+        const int f = o / C, c = o - f * C;
+        dst[o] = src[(long long)c * F + f];
+    }
+}
+
 } // namespace
-
-int sgd_accumulate_launch(wsc_ctx *ctx, const SgdSegment *segs_dev, int n_segs, const float *param, const float *grad, float *accum,
-                          long long elems, float weight_decay, int accum_num, double *l2_partials, unsigned *l2_counter, float *l2_dev) {
-    WSC_CHECK(n_segs >= 1 && n_segs <= SGD_MAX_SEGMENTS, WSC_ERR_INVALID, "internal: %d segments", n_segs);
-    SgdAccArgs a = {};
-    a.segs = segs_dev; a.n_segs = n_segs;
-    a.param = param; a.grad = grad; a.accum = accum;
-    a.elems = elems;
-    a.wd = weight_decay; a.div = (float)accum_num;
-    a.partials = l2_dev ? l2_partials : nullptr;
-    a.counter = l2_counter; a.l2 = l2_dev;
-    const bool vec = aligned16(param) && aligned16(grad) && aligned16(accum);
-    WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, 16.0 * elems);
-    if (l2_dev) WSC_HIP(hipMemsetAsync(l2_counter, 0, sizeof(unsigned), ctx->stream)); // (the ticket starts at zero whatever came before)
-    if (vec) hipLaunchKernelGGL(sgd_accumulate_kernel<true>, dim3(sgd_blocks(elems, true)), dim3(SGD_BLOCK), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(sgd_accumulate_kernel<false>, dim3(sgd_blocks(elems, false)), dim3(SGD_BLOCK), 0, ctx->stream, a);
-    WSC_HIP(hipGetLastError());
-    return WSC_OK;
-}
-
-int sgd_apply_launch(wsc_ctx *ctx, float *param, float *accum, float *mom, long long elems, float lr, float momentum, int clear_accum) {
-    const bool vec = aligned16(param) && aligned16(accum) && aligned16(mom);
-    WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, (clear_accum ? 24.0 : 20.0) * elems);
-    if (vec)
-        hipLaunchKernelGGL(sgd_apply_kernel<true>, dim3(sgd_blocks(elems, true)), dim3(SGD_BLOCK), 0, ctx->stream, param, accum, mom, elems, lr,
-                           momentum, clear_accum);
-    else
-        hipLaunchKernelGGL(sgd_apply_kernel<false>, dim3(sgd_blocks(elems, false)), dim3(SGD_BLOCK), 0, ctx->stream, param, accum, mom, elems, lr,
-                           momentum, clear_accum);
-    WSC_HIP(hipGetLastError());
-    return WSC_OK;
-}
 
 int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *plan) {
     *plan = RepackPlan();
@@ -402,7 +276,7 @@ int repack_plan(std::vector<RepackJob> &jobs, wsc_precision prec, RepackPlan *pl
             plan->small_tiles = (J.Cout + 63) / 64;
         } else {
             if (fmt == 1) { // the partial maxima: ~512 blocks a layer, at least 16 rows each
-                int splits = std::max(1, std::min(std::min(512 / J.tiles, SGD_PMAX_SPLITS), (R + 15) / 16));
+                int splits = std::max(1, std::min(std::min(512 / J.tiles, REPACK_PMAX_SPLITS), (R + 15) / 16));
                 J.rows_per = (R + splits - 1) / splits;
                 J.splits = (R + J.rows_per - 1) / J.rows_per; // (no empty split)
                 J.pmax_off = plan->pmax_elems;
@@ -443,5 +317,28 @@ int repack_launch(wsc_ctx *ctx, const RepackPlan &plan, const float *param) {
         hipLaunchKernelGGL(repack_rot_kernel, dim3(plan.rot_blocks), dim3(256), 0, ctx->stream, plan.jobs_dev, plan.n_jobs, param);
         WSC_HIP(hipGetLastError());
     }
+    return WSC_OK;
+}
+
+int vec_copy_launch(wsc_ctx *ctx, const VecCopyJob *jobs_dev, int n_jobs, int blocks, const float *param) {
+    if (n_jobs <= 0 || blocks <= 0) return WSC_OK;
+    WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, 8.0 * blocks * VEC_COPY_PER_BLOCK);
+    hipLaunchKernelGGL(vec_copy_kernel, dim3(blocks), dim3(VEC_COPY_PER_BLOCK), 0, ctx->stream, jobs_dev, n_jobs, param, ctx->range_dev);
+    WSC_HIP(hipGetLastError());
+    return WSC_OK;
+}
+
+int bn_fold_launch(wsc_ctx *ctx, const BnFoldJob *jobs_dev, int n_jobs, int blocks, const float *param, const float *run) {
+    if (n_jobs <= 0 || blocks <= 0) return WSC_OK;
+    WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, 24.0 * blocks * BN_FOLD_PER_BLOCK);
+    hipLaunchKernelGGL(bn_fold_kernel, dim3(blocks), dim3(BN_FOLD_PER_BLOCK), 0, ctx->stream, jobs_dev, n_jobs, param, run, ctx->range_dev);
+    WSC_HIP(hipGetLastError());
+    return WSC_OK;
+}
+
+int transpose_cf_launch(wsc_ctx *ctx, const float *src, int C, int F, float *dst) {
+    WscKernelTimer timer(ctx, WSC_K_GRAD_MISC, 8.0 * C * F);
+    hipLaunchKernelGGL(transpose_cf_kernel, dim3(wsc_grid_for((long long)C * F)), dim3(256), 0, ctx->stream, src, C, F, dst);
+    WSC_HIP(hipGetLastError());
     return WSC_OK;
 }
