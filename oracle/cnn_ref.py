@@ -4,7 +4,9 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 Each function cites the reference lines it follows (paths relative to /root/reference).
 The ResNet50 restatement is pinned against the reference's own module
 (03b_irn/net/resnet50.py, imported in this container by oracle/gen_golden.py) through
-the committed fixtures under tests/golden/.
+the committed fixtures under tests/golden/ (regenerate: `python oracle/gen_golden.py`).
+normalize_int / normalize_float are pinned bit for bit against the reference's own TorchvisionNormalize classes by
+tests/golden/ref_normalize.npz (regenerate: `python oracle/gen_golden_ref.py normalize`).
 
 Everything here is a floating-point kernel restated with plain torch fp32 ops -- the
 "plain PyTorch fp32 reference" the numerics tests compare the HIP kernels against.

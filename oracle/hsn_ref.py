@@ -6,6 +6,9 @@ tests/test_dataloaders_host.py pins against OpenCV's INTER_LINEAR rule).  Only t
   modify_by_htt   utilities.py:306-364
   get_cs_gradcam  utilities.py:367-397
   pass_classes / unary   dcrf_process :425, :431
+
+modify_by_htt and get_cs_gradcam are pinned to the bit against the reference's own functions by tests/golden/ref_hsn.npz
+(tests/test_reference_pins.py); regenerate it with `python oracle/gen_golden_ref.py hsn`.
 """
 import numpy as np
 import scipy.ndimage

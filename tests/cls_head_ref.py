@@ -3,7 +3,8 @@ wsc_cls_threshold_counts; 01_train/demo.py:60-61, utilities.py:69-165).
 
 A restatement of the header's formulas: float32 inputs promoted to float64, p and 1 - p both formed from exp(-|l|), the clip
 bounds eps = float32(1e-7) and hi = float32(1) - eps promoted.  tests/test_cls_head_oracle.py holds the loss and its gradients to
-torch.autograd and the curve rule to sklearn.metrics.roc_curve."""
+torch.autograd and the curve rule to sklearn.metrics.roc_curve; tests/test_reference_pins.py holds roc_thresholds and threshold_counts to
+what the reference's own functions returned (tests/golden/ref_roc.npz; regenerate with `python oracle/gen_golden_ref.py roc`)."""
 import numpy as np
 
 EPS = np.float64(np.float32(1e-7))

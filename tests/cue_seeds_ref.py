@@ -9,6 +9,8 @@ The oracle is the per-pixel statement of include/wsscam.h (wsc_cue_seeds), vecto
                     (= painting from the largest to the smallest mask under np.argsort(-area, kind='stable')), 0 if uncovered
 A pixel is AMBIGUOUS when its smallest covering area is shared by two or more covering masks: there the reference's own
 np.argsort(-area) (default kind, unspecified order among ties) may paint either way.
+tests/test_reference_pins.py holds the oracle, on every other pixel, to the labels that the reference's own get_fgbg_cues / get_fg_cues /
+update_cues returned (tests/golden/ref_cue_seeds.npz; regenerate with `python oracle/gen_golden_ref.py cue_seeds`);
 tests/test_cue_seeds_oracle.py holds the oracle to the host functions of wsscam.cues.utilities on every other pixel;
 tests/test_gpu_cue_seeds.py holds the device to the oracle on every pixel."""
 import numpy as np

@@ -2,7 +2,8 @@
 
 The oracle is vectorised numpy + scipy.ndimage.label with a full 3 x 3 structure (8-connectivity: the reference's own
 labeller, lib/CC_labeling_8.py, is not in the reference tree; label 0 = not in the class's candidate set, never filled).
-tests/test_dsrg_oracle.py holds it to a per-pixel scan with its own union-find; tests/test_gpu_dsrg.py holds the device to it."""
+tests/test_reference_pins.py holds it to what the reference's own single_generate_seed_step returned with a labeller stand-in
+(tests/golden/ref_dsrg.npz; regenerate with `python oracle/gen_golden_ref.py dsrg`); tests/test_dsrg_oracle.py holds it to a per-pixel scan with its own union-find; tests/test_gpu_dsrg.py holds the device to it."""
 import numpy as np
 import scipy.ndimage
 

@@ -8,7 +8,9 @@
   pair_loop     a plain loop over (image, source, direction): labels, the path maximum, the terms, math.fsum.  Losses and counts
                 only; small maps only.
 
-Every input reaches the arithmetic as a float64 copy of a float32 value."""
+Every input reaches the arithmetic as a float64 copy of a float32 value.  tests/test_reference_pins.py holds tensor_form(sigmoid_first=True)
+and pair_labels to the per-pair tensors of the reference's own AffinityDisplacementLoss and GetAffinityLabelFromIndices
+(tests/golden/ref_irn_loss.npz; regenerate with `python oracle/gen_golden_ref.py irn_loss`)."""
 import math
 
 import numpy as np
